@@ -204,6 +204,39 @@ def parity_block(hip_dt, hip_state, oracle_run, source):
     return out
 
 
+DUMP_MAX_ELEMENTS = 1 << 19  # per array: longer ones are cut to a fixed, seeded sample of this many entries
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs``: every array as ``out_dir/<name>.npy`` in float64 (complex ones as ``<name>_real`` and
+    ``<name>_imag``).  An array longer than DUMP_MAX_ELEMENTS keeps the entries at a sorted sample of indices drawn
+    with a fixed seed; those indices are written too, as ``sample_index_<length>.npy``.  The inputs of a workload are
+    the same from run to run (seeded mesh, fixed field and options), so two builds can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    files, samples = {}, {}
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = np.asarray(a)
+        parts = {name + "_real": a.real, name + "_imag": a.imag} if np.iscomplexobj(a) else {name: a}
+        for key, v in parts.items():
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if len(v) > DUMP_MAX_ELEMENTS:
+                idx = samples.get(len(v))
+                if idx is None:
+                    idx = samples[len(v)] = np.sort(np.random.default_rng(0).choice(len(v), DUMP_MAX_ELEMENTS, replace=False))
+                    files[f"sample_index_{len(v)}"] = idx.astype(np.float64)
+                v = v[idx]
+            files[key] = v
+    total = sum(v.nbytes for v in files.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    for key, v in files.items():
+        np.save(os.path.join(out_dir, key + ".npy"), v)
+    log(f"--dump-outputs: {len(files)} arrays, {total / 2**20:.1f} MB in {out_dir}")
+
+
 def build_workload(name):
     """Synthetic mesh + inputs of one workload."""
     from tdgl_amd.finite_volume import Mesh
@@ -357,6 +390,9 @@ def main():
                     help="seconds config 5 may take before the headline line is printed without it")
     ap.add_argument("--trace-iterations", default=None,
                     help="write dt / PCG iterations of every step (pre-roll included) to this .json file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed in their last step (final psi, mu, J_s, J_n; per-step dt, PCG "
+                         "iterations, probe values) to DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--timeout", type=int, default=1500,
                     help="hard limit in seconds for the whole run (SIGALRM ends a hung rank instead of blocking the node); 0 = none")
     args = ap.parse_args()
@@ -648,6 +684,14 @@ def main():
         direct_solves, direct_ms = ctx.profile_read_direct() if not use_dd else (0, 0.0)
         ctx.profile_enable(False)
         work = ctx.step_stats()
+        # --dump-outputs: what the timed steps computed, read back before anything else runs on the context
+        outputs = None
+        if args.dump_outputs and name == args.workload:
+            st_end = drun.gather_state() if use_dd else ctx.get_state()
+            if rank == 0:
+                outputs = dict(dt=res["dt"], pcg_iterations=res["pcg_iters"], probe_mu=res["mu"], probe_theta=res["theta"],
+                               psi=st_end["psi"], mu=st_end["mu"], supercurrent=st_end["supercurrent"],
+                               normal_current=st_end["normal_current"])
         ev_over = ctx.profile_event_overhead(50)  # (after the timed region)
         # K1 once more, after the timed region: ONE event pair around 16 back-to-back launches on the state the timed
         # steps ended on -- the pair's own ~4.5 us is amortised over 16 launches instead of sitting in every sample
@@ -683,7 +727,7 @@ def main():
         out = SimpleNamespace(
             wl=wl, name=name, ctx=ctx, drun=drun, n=n, m=m, n_loc=n_loc, m_loc=m_loc, elapsed=elapsed, res=res,
             k1=(launches, k1_ms), k1_burst_ms=k1_burst_ms, axp=(axp_launches, axp_ms), direct=(direct_solves, direct_ms), ev_over=ev_over, comm=comm, sizes=list(h.sizes), start_state=start_state,
-            end_state=end_state, work=work, setup=setup, windows={}, conservation=conservation,
+            end_state=end_state, work=work, setup=setup, windows={}, conservation=conservation, outputs=outputs,
             stats=dict(ctx.poisson_stats(), guess=ctx.guess_stats(), batch_prediction=ctx.pcg_prediction_stats(),
                        **(dict(direct_switching=ctx.direct_switching()) if getattr(ctx, "dense_direct", False) else {}),
                        **(dict(preconditioner=ctx.precond_direct_stats()) if getattr(ctx, "precond_direct", None) else {})),
@@ -695,6 +739,8 @@ def main():
         return out
 
     main_run = run_workload(args.workload, want_cpu_state=(rank == 0 and not use_dd and not args.no_cpu_baseline))
+    if main_run.outputs is not None:
+        dump_outputs(args.dump_outputs, main_run.outputs)
     def vortex_window(r):
         """The regime the headline window does not see: run on until the order parameter has collapsed
         somewhere (min |psi|^2 < 0.05 outside the terminals: vortex cores / phase slips), let the

@@ -5,7 +5,7 @@ the library's host-callback transport (ghost values and all-reduces staged throu
 buffers and torch.distributed/gloo): every kernel, the pack/unpack, the sliced hierarchy and the
 step logic are exactly those of a multi-GPU run; only the three RCCL calls are swapped.  The RCCL
 transport itself is exercised with world_size 1 (communicator creation, all-reduce, the
-no-neighbour halo).
+no-neighbour halo).  At most 6 processes may hold the shared GPU at once: this one and up to 5 ranks.
 """
 
 import os
@@ -127,11 +127,11 @@ def test_multi_rank_run_matches_single_gpu(world, transport, tmp_path):
     assert abs(got["iters"].mean() - ref_res["pcg_iters"].mean()) < 2.0
 
 
-@pytest.mark.parametrize("world,transport,choice", [(2, "gloo", 1), (3, "ipc", 1), (8, "ipc", 1), (3, "ipc", 0)])
+@pytest.mark.parametrize("world,transport,choice", [(2, "gloo", 1), (3, "ipc", 1), (5, "ipc", 1), (3, "ipc", 0)])
 def test_rank_level_dissection_as_the_preconditioner_matches_single_gpu(world, transport, choice, tmp_path, monkeypatch):
     """`tdgl_amd/schur_dd.py`, `csrc/schur.inc`: the cut between the ranks as the top level of a nested dissection --
     every rank holds the fp32-stored factors of its interior block, all hold the pseudo-inverse of the interface
-    complement -- as the CG's second preconditioner in one-process-per-GPU mode.  12.7k sites on 2 / 3 / 8 ranks
+    complement -- as the CG's second preconditioner in one-process-per-GPU mode.  12.7k sites on 2 / 3 / 5 ranks
     sharing one GPU, every solve through the factors (choice 1) or the cheaper preconditioner per solve (choice 0),
     against the single-GPU run: the same trajectory at 1e-9, ONE or two CG iterations per solve, and per step a handful
     of sums where the distributed AMG cycle needs two per iteration."""
@@ -401,13 +401,14 @@ def test_peer_mapped_transport_is_bit_identical_to_the_host_transport_over_a_lon
     assert (np.abs(a["psi"]) ** 2).min() < 0.5  # vortices are in
 
 
-def test_eight_ranks_match_single_gpu(tmp_path):
-    """The node size of the scaling runs: 8 ranks (here sharing one GPU through the callback
-    transport), 2x4 RCB blocks with up to 5 neighbours per rank, corner-only contacts included."""
+def test_five_ranks_match_single_gpu(tmp_path):
+    """The most ranks that may share the test box's one GPU (5, plus this process: at most 6 processes may hold it),
+    through the callback transport: an uneven RCB split (2 + 3) with up to 4 neighbours per rank, corner-only contacts
+    included."""
     size = (120, 60)
     mesh, ref_res, ref = _single_gpu_reference(size)
-    mp.spawn(_worker, args=(8, _free_port(), "gloo", str(tmp_path), "auto", size), nprocs=8, join=True)
-    got = np.load(os.path.join(tmp_path, "dist_gloo_8.npz"))
+    mp.spawn(_worker, args=(5, _free_port(), "gloo", str(tmp_path), "auto", size), nprocs=5, join=True)
+    got = np.load(os.path.join(tmp_path, "dist_gloo_5.npz"))
     assert len(got["dt"]) == N_STEPS
     assert np.abs(got["dt"] - ref_res["dt"]).max() <= 1e-9 * ref_res["dt"].max()
     assert np.abs(np.abs(got["psi"]) ** 2 - np.abs(ref["psi"]) ** 2).max() < 1e-9
@@ -420,7 +421,7 @@ def test_eight_ranks_match_single_gpu(tmp_path):
 DEEP_KW = dict(deep=True, max_coarse=50, plan_kw=dict(tail_rows=1200, dense_rows=400))
 
 
-@pytest.mark.parametrize("world,transport", [(2, "gloo"), (3, "gloo"), (8, "gloo"), (1, "rccl"), (1, "ipc"), (2, "ipc"), (3, "ipc"), (8, "ipc")])
+@pytest.mark.parametrize("world,transport", [(2, "gloo"), (3, "gloo"), (5, "gloo"), (1, "rccl"), (1, "ipc"), (2, "ipc"), (3, "ipc"), (5, "ipc")])
 def test_two_distributed_levels_match_single_gpu(world, transport, tmp_path):
     """The decomposition the scaling run uses from ~30k sites per job on (forced here on a 16k-site film by making
     level 1 an intermediate level of the collapsed chain): per-rank aggregates, level 1 distributed through its
