@@ -727,6 +727,46 @@ int tdgl_vcycle(tdgl_ctx *ctx, const double *r, double *z);
 int tdgl_guess_dots(tdgl_ctx *ctx, int32_t k, int64_t n, const double *vectors, const double *b, int32_t newest,
                     double *out_pairs);
 
+/* ------------------------------------------------------------------ ensembles
+ * R independent replicas of the context's device in one batched time loop (csrc/ensemble.inc).  The context must be
+ * a single-GPU one with the explicit dense inverse (tdgl_poisson_build_dense_inverse); the replicas share its mesh,
+ * site graph and G, and each has its own link exponents, mu boundary values, epsilon, state (psi, mu), controller
+ * and Runner clock (time, stage step, adaptive dt, retries).  One round of the loop is one attempt of every live
+ * replica in five launches over all of them; the host synchronises once per batch of rounds.  The per-replica
+ * setters form their input with the context's own entry point of the same name and copy it: the context's own run
+ * state is overwritten.  Static inputs only (no dA/dt, no time tables, no screening).  Release the ensemble before
+ * the context. */
+typedef struct tdgl_ensemble tdgl_ensemble;
+#define TDGL_ENSEMBLE_MAX_REPLICAS 4096
+int tdgl_ensemble_create(tdgl_ensemble **out, tdgl_ctx *ctx, int32_t n_replicas);
+void tdgl_ensemble_destroy(tdgl_ensemble *ens);
+int tdgl_ensemble_size(tdgl_ensemble *ens, int32_t *n_replicas);
+/* Per replica r: A [n_edges, 2] (tdgl_set_link_exponents), mu_boundary [n_boundary_edges], epsilon [n_sites],
+ * psi [n_sites] complex + mu [n_sites], the controller (resets it like tdgl_set_controller; adaptive_window in
+ * [1, 128] when adaptive), and the start of a stage (Runner time and step = 0). */
+int tdgl_ensemble_set_link_exponents(tdgl_ensemble *ens, int32_t r, const double *A);
+int tdgl_ensemble_set_mu_boundary(tdgl_ensemble *ens, int32_t r, const double *mu_boundary);
+int tdgl_ensemble_set_epsilon(tdgl_ensemble *ens, int32_t r, const double *epsilon);
+int tdgl_ensemble_set_state(tdgl_ensemble *ens, int32_t r, const double *psi, const double *mu);
+int tdgl_ensemble_set_controller(tdgl_ensemble *ens, int32_t r, const tdgl_controller *c);
+int tdgl_ensemble_begin_stage(tdgl_ensemble *ens, int32_t r);
+/* The same probe sites for every replica. */
+int tdgl_ensemble_set_probes(tdgl_ensemble *ens, const int32_t *sites, int32_t n_probe);
+int tdgl_ensemble_get_loop_state(tdgl_ensemble *ens, int32_t r, int64_t *step, double *time, double *runner_dt,
+                                 double *tentative_dt);
+/* Up to max_steps[r] <= capacity accepted steps of every replica r, each stopping at end_time[r] (tdgl_run per
+ * replica).  Outputs: out_dt [R, capacity], out_mu_probe / out_theta_probe [R, capacity, n_probe] (may be NULL),
+ * steps_done[R], reached_end[R], failed[R] (may be NULL).  A replica that spends its retry budget ends the call after
+ * the batch: TDGL_ERR_PSI_RETRIES, tdgl_last_error = "replica <r>: " + the reference's message. */
+int tdgl_ensemble_run(tdgl_ensemble *ens, const int64_t *max_steps, const double *end_time, int64_t capacity,
+                      double *out_dt, double *out_mu_probe, double *out_theta_probe, int64_t *steps_done,
+                      int32_t *reached_end, int32_t *failed);
+/* psi, mu of replica r and J_s, J_n formed from them (any may be NULL), reference order. */
+int tdgl_ensemble_get_state(tdgl_ensemble *ens, int32_t r, double *psi, double *mu, double *supercurrent,
+                            double *normal_current);
+/* Rounds queued and host synchronisations since the ensemble was created. */
+int tdgl_ensemble_get_stats(tdgl_ensemble *ens, int64_t *rounds, int64_t *batches);
+
 /* ------------------------------------------------------------------ measurement */
 /* Average duration (ms) of `reps` back-to-back launches of one kernel on the context's
  * stream, timed with HIP events.  kernel: 0 = psi-Laplacian SpMV (K1), 1 = fused

@@ -1,0 +1,606 @@
+// Ensemble of R independent replicas of one device in one batched time loop (include/tdgl_hip.h:
+// tdgl_ensemble_*).  Included at the end of tdgl_hip.hip.
+//
+// The replicas share the context's mesh, SELL-64 pattern and dense inverse G (tdgl_poisson_build_dense_inverse);
+// each has its own link variables (and covariant-Laplacian values), boundary term of the Poisson right-hand side,
+// epsilon, state (psi, L psi double-buffered, mu) and controller (a StepCtl in device memory).  The loop is the
+// run-ahead loop of run.inc with the replica as a grid dimension: one ROUND is one attempt per live replica, five
+// launches over all replicas,
+//   K1 k_ens_psi_update      psi update (psi_update_body) per replica
+//   K2 k_ens_laplacian       L psi' and the Poisson right-hand side (psi_laplacian_body<true>) per replica
+//   K3 k_ens_dense_tiles     G [b_1 .. b_R]: each symmetric tile read once per 16 replicas, used for its block
+//                            and its transpose
+//   K4 k_ens_finish          slot sums of K3 (dense_sym_finish_body) and the controller (step_controller) per replica
+//   K5 k_ens_probes          probe read-outs of the accepted attempts
+// and the host synchronises once per batch of rounds.  A failed psi update is that replica's next attempt, with
+// the smaller dt, in the next round; a replica that has reached its end time, spent its retry budget or taken the
+// steps asked of this call is poisoned and its launches return at once.  Per replica the arithmetic is that of the
+// run-ahead loop, operation for operation, except for the order of the sums inside the dense product.
+//
+// Per-replica inputs are formed by the context's own entry points (tdgl_set_link_exponents, tdgl_set_mu_boundary,
+// tdgl_set_epsilon, tdgl_set_state: the site / edge permutations, the link variables, the boundary term) and copied
+// from the context's buffers into the replica's; the context's own run state is scratch for the ensemble.
+
+#include <memory>
+
+namespace tdgl {
+
+constexpr int ENS_RG = 16;  // replicas per workgroup of the dense product
+constexpr int ENS_CH = 16;  // tile rows per LDS chunk
+
+__global__ __launch_bounds__(BLOCK) void k_ens_psi_update(int64_t n, int64_t n_pad, double2 *__restrict__ psi0, double2 *__restrict__ psi1,
+                                                          const double2 *__restrict__ lap0, const double2 *__restrict__ lap1,
+                                                          const double *__restrict__ mu, const double *__restrict__ eps, double u,
+                                                          double gamma, double *__restrict__ dmax_part, int32_t *__restrict__ fail_part,
+                                                          StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    StepCtl *c = ctl + r;
+    if (c->poisoned) {  // (uniform over the replica's workgroups: `poisoned` only changes in K4)
+        if (blockIdx.x == 0 && threadIdx.x == 0) c->live = 0;
+        return;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) c->live = 1;
+    const int64_t o = (int64_t)r * n_pad;
+    const bool c1 = c->cur != 0;
+    psi_update_body(blockIdx.x, gridDim.x, n, (c1 ? psi1 : psi0) + o, mu + o, eps + o, (c1 ? lap1 : lap0) + o, c->attempt_dt, u, gamma,
+                    (c1 ? psi0 : psi1) + o, nullptr, dmax_part + (int64_t)r * gridDim.x, fail_part + (int64_t)r * gridDim.x, nullptr);
+}
+
+template <class IT>
+__global__ __launch_bounds__(BLOCK) void k_ens_laplacian(int n_slices, int per_xcd, int64_t n_rows, const int32_t *__restrict__ slice_off,
+                                                         const IT *__restrict__ cols, const double2 *__restrict__ vals, int64_t n_slots,
+                                                         const double *__restrict__ diag, const uint8_t *__restrict__ fixed,
+                                                         const double2 *__restrict__ psi0, const double2 *__restrict__ psi1,
+                                                         double2 *__restrict__ lap0, double2 *__restrict__ lap1, const double *__restrict__ area,
+                                                         const double *__restrict__ ceff, double *__restrict__ bvec, int64_t n_pad,
+                                                         const StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    const StepCtl *c = ctl + r;
+    if (!c->live) return;
+    const bool to1 = c->cur == 0;
+    const int64_t o = (int64_t)r * n_pad;
+    psi_laplacian_body<true, IT>(n_slices, per_xcd, 0, n_rows, slice_off, cols, vals + (int64_t)r * n_slots, diag, fixed,
+                                 (to1 ? psi1 : psi0) + o, (to1 ? lap1 : lap0) + o, area, ceff + o, bvec + o);
+}
+
+// Y = G B on the symmetric tiles of k_dense_sym_tiles (tile (I, J), J <= I, DT x DT, row major), B = [b_1 .. b_R] with
+// replica r's vector at b + r * ldb.  Workgroup (t, g): tile t for the replicas 16 g .. 16 g + 15.  The tile streams
+// through LDS in chunks of ENS_CH rows; both b blocks of the 16 replicas sit in LDS for the whole tile.
+//   transpose part  y_J[c][q] += sum_r T[r][c] b_I[r][q]: thread = 4 columns (c0 + 32 k) x 2 replicas, summed over
+//                   the tile's rows in registers; 8 FMAs per 6 LDS reads;
+//   block part      y_I[r][q] += sum_c T[r][c] b_J[c][q]: per chunk, thread = 4 rows x 4 replicas x 1/16 of the
+//                   columns (16 FMAs per 8 LDS reads), the 16 column slices summed by a butterfly over 16 lanes.
+// The two contributions go to the fixed slots of `part` the single-vector kernel uses (slot J of row block I, slot I
+// of row block J), per replica at part + r * ldpart: no atomics, the result does not depend on the schedule.
+// Plain fp64 FMAs: gfx950's fp64 matrix instructions run at the vector rate (78.6 TF either way, spec), so they
+// buy nothing here, and the kernel is bound by LDS and the stream of G, not by the FMA rate.
+__global__ __launch_bounds__(BLOCK) void k_ens_dense_tiles(int n, int nt, const double *__restrict__ Gp, const double *__restrict__ b,
+                                                           int64_t ldb, double *__restrict__ part, int64_t ldpart, int R,
+                                                           const StepCtl *__restrict__ ctl) {
+    __shared__ double sT[ENS_CH][DT];
+    __shared__ double sBI[DT][ENS_RG + 1];  // (+1: the block part's reads of 16 rows x 4 replicas spread over the banks)
+    __shared__ double sBJ[DT][ENS_RG + 1];
+    const int tid = threadIdx.x;
+    const int g0 = blockIdx.y * ENS_RG;
+    int live = 0;
+    if (tid < ENS_RG && g0 + tid < R) live = ctl[g0 + tid].live;
+    if (!__syncthreads_or(live)) return;  // (every replica of the group is dead this round)
+    const int t = blockIdx.x;
+    int I = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+    while ((I + 1) * (I + 2) / 2 <= t) ++I;
+    while (I * (I + 1) / 2 > t) --I;
+    const int J = t - I * (I + 1) / 2;
+    for (int f = tid; f < ENS_RG * DT; f += BLOCK) {
+        const int q = f / DT, c = f % DT;
+        const bool okq = g0 + q < R;
+        const int ri = I * DT + c, cj = J * DT + c;
+        sBI[c][q] = okq && ri < n ? b[(int64_t)(g0 + q) * ldb + ri] : 0.0;
+        sBJ[c][q] = okq && cj < n ? b[(int64_t)(g0 + q) * ldb + cj] : 0.0;
+    }
+    const double2 *__restrict__ g = reinterpret_cast<const double2 *>(Gp + (int64_t)t * DT * DT);
+    // transpose part: columns cg + 32 k, replicas 2 gp, 2 gp + 1
+    const int cg = tid & 31, gp = tid >> 5;
+    double accT[4][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+    // block part: rows 4 rq .. 4 rq + 3 of the chunk (rq = the wave), replicas 4 gq .. 4 gq + 3, columns ks + 16 j
+    const int rq = tid >> 6, gq = (tid >> 4) & 3, ks = tid & 15;
+    const int64_t ldp = (int64_t)nt * DT;
+    constexpr int PER = ENS_CH * DT / 2 / BLOCK;  // double2 loads per thread and chunk
+    for (int r0 = 0; r0 < DT; r0 += ENS_CH) {
+        double2 v[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) v[k] = g[(int64_t)r0 * (DT / 2) + tid + k * BLOCK];
+        __syncthreads();  // (the previous chunk has been read by everyone; the first time: the b blocks are in place)
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int f = 2 * (tid + k * BLOCK);
+            sT[f / DT][f % DT] = v[k].x;
+            sT[f / DT][f % DT + 1] = v[k].y;
+        }
+        __syncthreads();
+        if (I != J) {  // (workgroup-uniform; a diagonal tile holds its whole block: the block part alone covers it)
+#pragma unroll 4
+            for (int k = 0; k < ENS_CH; ++k) {
+                const double bi0 = sBI[r0 + k][2 * gp], bi1 = sBI[r0 + k][2 * gp + 1];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double tv = sT[k][cg + 32 * q];
+                    accT[q][0] += tv * bi0;
+                    accT[q][1] += tv * bi1;
+                }
+            }
+        }
+        double acc[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc[k] = 0.0;
+#pragma unroll
+        for (int j = 0; j < DT / 16; ++j) {
+            const int c = ks + 16 * j;
+            double tv[4], bv[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tv[i] = sT[4 * rq + i][c];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bv[q] = sBJ[c][4 * gq + q];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[4 * i + q] += tv[i] * bv[q];
+        }
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1)
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc[k] += __shfl_xor(acc[k], off, WAVE);
+        {  // lane ks stores entry ks = 4 i + q
+            double mine = acc[0];
+#pragma unroll
+            for (int k = 1; k < 16; ++k) mine = ks == k ? acc[k] : mine;
+            const int i = ks >> 2, q = g0 + 4 * gq + (ks & 3);
+            if (q < R) part[(int64_t)q * ldpart + (int64_t)J * ldp + I * DT + r0 + 4 * rq + i] = mine;
+        }
+    }
+    if (I != J) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int q = g0 + 2 * gp + e;
+            if (q >= R) continue;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) part[(int64_t)q * ldpart + (int64_t)I * ldp + J * DT + cg + 32 * k] = accT[k][e];
+        }
+    }
+}
+
+// mu of every replica whose psi update succeeded = the slot sums of K3; the replica's controller.  A replica that has
+// taken the steps asked of this call (limit) is poisoned like one that reached its end time.
+__global__ __launch_bounds__(BLOCK) void k_ens_finish(int n, int nt, const double *__restrict__ part, int64_t ldpart,
+                                                      const double *__restrict__ dmax_part, const int32_t *__restrict__ fail_part,
+                                                      int nfail, double *__restrict__ mu, int64_t n_pad, StepCtl *__restrict__ ctl,
+                                                      StepRec *__restrict__ rec, const int32_t *__restrict__ limit) {
+    const int r = blockIdx.y;
+    StepCtl *c = ctl + r;
+    dense_sym_finish_body(blockIdx.x, n, nt, part + (int64_t)r * ldpart, dmax_part + (int64_t)r * nfail, fail_part + (int64_t)r * nfail,
+                          nfail, nullptr, 1, mu + (int64_t)r * n_pad, nullptr, nullptr, c, rec + (int64_t)r * RA_BATCH_MAX);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && c->live && !c->poisoned && c->n_acc >= limit[r]) c->poisoned = 1;
+}
+
+// probe read-outs of an accepted attempt into slot n_acc - 1 of the replica's records (k_ra_probes per replica)
+__global__ void k_ens_probes(int n_probe, const int32_t *__restrict__ sites, const double2 *__restrict__ psi0,
+                             const double2 *__restrict__ psi1, const double *__restrict__ mu, int64_t n_pad, double *__restrict__ ring,
+                             const StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    const StepCtl *c = ctl + r;
+    if (!c->live || !c->last_ok) return;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_probe) return;
+    const int s = sites[k];
+    const int64_t o = (int64_t)r * n_pad;
+    const double2 p = (c->cur != 0 ? psi1 : psi0)[o + s];  // (the controller has flipped cur: psi^{n+1})
+    double *__restrict__ out = ring + ((int64_t)r * RA_BATCH_MAX + c->n_acc - 1) * 2 * n_probe;
+    out[k] = mu[o + s];
+    out[n_probe + k] = atan2(p.y, p.x);
+}
+
+}  // namespace tdgl
+
+struct EnsReplica {
+    tdgl_controller ctl{};
+    bool have_ctl = false, have_links = false, have_eps = false, have_state = false, lap_valid = false;
+    double tentative_dt = 0.0, dt_cap = 0.0, runner_dt = 0.0, time = 0.0, attempt_dt = 0.0;
+    int64_t stage_step = 0;
+    int cur = 0, retries = 0;
+    std::vector<double> hist;  // d_psi_sq_vals (solver.py:318, 701), bounded like the context's
+};
+
+struct tdgl_ensemble {
+    tdgl_ctx *ctx = nullptr;
+    int R = 0, nt = 0, np_ = 0;
+    int64_t n = 0, n_pad = 0, m_pad = 0, n_slots = 0, ldpart = 0;
+    int batch = 4;  // rounds per synchronisation: doubles up to RA_BATCH_MAX
+    DevBuf<double2> U, lapv, psi0, psi1, lap0, lap1;
+    DevBuf<double> ceff, eps, mu, bvec, part, dmax_part, probe;
+    DevBuf<int32_t> fail_part, limit, d_probes;
+    DevBuf<StepCtl> d_ctl;
+    DevBuf<StepRec> d_rec;
+    std::vector<StepCtl> h_ctl;
+    std::vector<StepRec> h_rec;
+    std::vector<double> h_probe;
+    std::vector<int32_t> h_limit;
+    std::vector<EnsReplica> rep;
+    int64_t stat_rounds = 0, stat_batches = 0;
+};
+
+static int ens_check(tdgl_ensemble *e, int32_t r) {
+    if (!e) return TDGL_ERR_ARG;
+    if (r < 0 || r >= e->R) TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "ensemble: replica %d out of range [0, %d)", r, e->R);
+    HIP_TRY(e->ctx, hipSetDevice(e->ctx->device));
+    return TDGL_OK;
+}
+
+template <class T>
+static int ens_copy(tdgl_ctx *ctx, T *dst, const T *src, int64_t count) {
+    HIP_TRY(ctx, hipMemcpyAsync(dst, src, (size_t)count * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_create(tdgl_ensemble **out, tdgl_ctx *ctx, int32_t n_replicas) {
+    if (!out) return TDGL_ERR_ARG;
+    *out = nullptr;
+    CTX_GUARD(ctx);
+    if (distributed(ctx)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_create: single-GPU contexts only");
+    if (n_replicas < 1 || n_replicas > TDGL_ENSEMBLE_MAX_REPLICAS)
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_create: n_replicas must be in [1, %d] (got %d)", TDGL_ENSEMBLE_MAX_REPLICAS, n_replicas);
+    if (!(ctx->dense_tiles > 0 && ctx->dense_ld > 0 && ctx->sub_parts == 0 && !ctx->sub_fp32 && ctx->dense_n == ctx->n))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_create: the context has no dense inverse (tdgl_poisson_build_dense_inverse)");
+    if (ctx->scr_enabled) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_create: screening is not supported");
+    std::unique_ptr<tdgl_ensemble> e(new tdgl_ensemble());
+    e->ctx = ctx;
+    e->R = n_replicas;
+    e->n = ctx->n;
+    e->n_pad = ctx->n_pad;
+    e->m_pad = ctx->m_pad;
+    e->n_slots = ctx->lap_pat.n_slots;
+    e->nt = ctx->dense_tiles;
+    e->ldpart = (int64_t)e->nt * e->nt * DT;
+    const size_t R = (size_t)n_replicas;
+    HIP_TRY(ctx, e->U.alloc(R * e->m_pad));
+    HIP_TRY(ctx, e->lapv.alloc(R * std::max<int64_t>(e->n_slots, 1)));
+    HIP_TRY(ctx, e->psi0.alloc(R * e->n_pad));
+    HIP_TRY(ctx, e->psi1.alloc(R * e->n_pad));
+    HIP_TRY(ctx, e->lap0.alloc(R * e->n_pad));
+    HIP_TRY(ctx, e->lap1.alloc(R * e->n_pad));
+    HIP_TRY(ctx, e->ceff.alloc(R * e->n_pad));
+    HIP_TRY(ctx, e->eps.alloc(R * e->n_pad));
+    HIP_TRY(ctx, e->mu.alloc(R * e->n_pad));
+    HIP_TRY(ctx, e->bvec.alloc(R * e->n_pad));
+    HIP_TRY(ctx, e->part.alloc(R * e->ldpart));
+    HIP_TRY(ctx, e->dmax_part.alloc(R * ctx->psi_blocks));
+    HIP_TRY(ctx, e->fail_part.alloc(R * ctx->psi_blocks));
+    HIP_TRY(ctx, e->limit.alloc(R));
+    HIP_TRY(ctx, e->d_ctl.alloc(R));
+    HIP_TRY(ctx, e->d_rec.alloc(R * RA_BATCH_MAX));
+    e->h_ctl.resize(R);
+    e->h_rec.resize(R * RA_BATCH_MAX);
+    e->h_limit.resize(R);
+    e->rep.resize(R);
+    *out = e.release();
+    return TDGL_OK;
+}
+
+extern "C" void tdgl_ensemble_destroy(tdgl_ensemble *e) {
+    if (!e) return;
+    (void)hipSetDevice(e->ctx->device);
+    (void)hipStreamSynchronize(e->ctx->stream);
+    delete e;
+}
+
+extern "C" int tdgl_ensemble_size(tdgl_ensemble *e, int32_t *n_replicas) {
+    if (!e || !n_replicas) return TDGL_ERR_ARG;
+    *n_replicas = e->R;
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_set_link_exponents(tdgl_ensemble *e, int32_t r, const double *A) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    TDGL_TRY(tdgl_set_link_exponents(ctx, A));  // (link variables and covariant-Laplacian values, in the context's buffers)
+    TDGL_TRY(ens_copy(ctx, e->U.p + r * e->m_pad, ctx->e_U.p, e->m_pad));
+    TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
+    e->rep[r].have_links = true;
+    e->rep[r].lap_valid = false;
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_set_mu_boundary(tdgl_ensemble *e, int32_t r, const double *mu_boundary) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    if (ctx->has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary: the context's links are time dependent");
+    TDGL_TRY(tdgl_set_mu_boundary(ctx, mu_boundary));  // (static links: the boundary term as the run-ahead loop reads it)
+    TDGL_TRY(ens_copy(ctx, e->ceff.p + r * e->n_pad, ctx->ceff.p, e->n_pad));
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_set_epsilon(tdgl_ensemble *e, int32_t r, const double *epsilon) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    TDGL_TRY(tdgl_set_epsilon(ctx, epsilon));
+    TDGL_TRY(ens_copy(ctx, e->eps.p + r * e->n_pad, ctx->eps.p, e->n_pad));
+    e->rep[r].have_eps = true;
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_set_state(tdgl_ensemble *e, int32_t r, const double *psi, const double *mu) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    TDGL_TRY(tdgl_set_state(ctx, psi, mu));
+    EnsReplica &p = e->rep[r];
+    p.cur = 0;
+    p.retries = 0;
+    TDGL_TRY(ens_copy(ctx, e->psi0.p + r * e->n_pad, ctx->psi[ctx->cur].p, e->n_pad));
+    TDGL_TRY(ens_copy(ctx, e->mu.p + r * e->n_pad, ctx->mu.p, e->n_pad));
+    p.have_state = true;
+    p.lap_valid = false;
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_set_controller(tdgl_ensemble *e, int32_t r, const tdgl_controller *c) {
+    TDGL_TRY(ens_check(e, r));
+    if (!c) TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_controller: null controller");
+    if (c->dt_init > c->dt_max) TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "dt_init must be less than or equal to dt_max.");
+    if (!(c->adaptive_time_step_multiplier > 0 && c->adaptive_time_step_multiplier < 1))
+        TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "adaptive_time_step_multiplier must be in (0, 1) (got %g).", c->adaptive_time_step_multiplier);
+    if (c->adaptive && (c->adaptive_window < 1 || c->adaptive_window > RA_HIST_MAX))
+        TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "ensemble: adaptive_window must be in [1, %d] (got %d)", RA_HIST_MAX, c->adaptive_window);
+    EnsReplica &p = e->rep[r];
+    p.ctl = *c;  // (tdgl_set_controller's resets: solver.py:316-320, runner.py:262)
+    p.tentative_dt = c->dt_init;
+    p.dt_cap = c->adaptive ? c->dt_max : c->dt_init;
+    p.hist.clear();
+    p.runner_dt = c->dt_init;
+    p.time = 0.0;
+    p.stage_step = 0;
+    p.retries = 0;
+    p.have_ctl = true;
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_set_probes(tdgl_ensemble *e, const int32_t *sites, int32_t n_probe) {
+    if (!e) return TDGL_ERR_ARG;
+    tdgl_ctx *ctx = e->ctx;
+    TDGL_TRY(tdgl_set_probes(ctx, sites, n_probe));  // (validation and the site permutation)
+    std::vector<int32_t> internal(ctx->probes.begin(), ctx->probes.end());
+    HIP_TRY(ctx, e->d_probes.alloc(std::max<size_t>(internal.size(), 1)));
+    HIP_TRY(ctx, e->probe.alloc((size_t)e->R * RA_BATCH_MAX * 2 * std::max<int32_t>(n_probe, 1)));
+    if (!internal.empty())
+        HIP_TRY(ctx, hipMemcpy(e->d_probes.p, internal.data(), internal.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    e->np_ = n_probe;
+    e->h_probe.assign((size_t)e->R * RA_BATCH_MAX * 2 * std::max<int32_t>(n_probe, 1), 0.0);
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_begin_stage(tdgl_ensemble *e, int32_t r) {
+    TDGL_TRY(ens_check(e, r));
+    e->rep[r].time = 0.0;      // runner.py:294, 315
+    e->rep[r].stage_step = 0;  // runner.py:295, 316
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_get_loop_state(tdgl_ensemble *e, int32_t r, int64_t *step, double *time, double *runner_dt,
+                                            double *tentative_dt) {
+    TDGL_TRY(ens_check(e, r));
+    const EnsReplica &p = e->rep[r];
+    if (step) *step = p.stage_step;
+    if (time) *time = p.time;
+    if (runner_dt) *runner_dt = p.runner_dt;
+    if (tentative_dt) *tentative_dt = p.tentative_dt;
+    return TDGL_OK;
+}
+
+// psi, mu of replica r and the currents formed from them: the replica's state goes through the context, whose
+// tdgl_get_state forms J_s, J_n with the replica's link variables (the arithmetic of the single run)
+extern "C" int tdgl_ensemble_get_state(tdgl_ensemble *e, int32_t r, double *psi, double *mu, double *supercurrent,
+                                       double *normal_current) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    const EnsReplica &p = e->rep[r];
+    if (!p.have_state || !p.have_links) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_get_state: replica %d has no state or links", r);
+    if (ctx->has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_state: the context's links are time dependent");
+    TDGL_TRY(ens_copy(ctx, ctx->psi[ctx->cur].p, (p.cur ? e->psi1.p : e->psi0.p) + r * e->n_pad, e->n_pad));
+    TDGL_TRY(ens_copy(ctx, ctx->mu.p, e->mu.p + r * e->n_pad, e->n_pad));
+    TDGL_TRY(ens_copy(ctx, ctx->e_U.p, e->U.p + r * e->m_pad, e->m_pad));
+    ctx->have_state = true;
+    ctx->lap_valid = false;  // (the context's Laplacian values belong to whatever links it was last given)
+    ctx->currents_valid = false;
+    ctx->currents_deferred = false;
+    return tdgl_get_state(ctx, psi, mu, supercurrent, normal_current);
+}
+
+static void ens_launch_laplacian_cache(tdgl_ensemble *e, int r) {
+    tdgl_ctx *ctx = e->ctx;
+    const SellPattern &pat = ctx->lap_pat;
+    const int tiles = (pat.n_slices + BLOCK / WAVE - 1) / (BLOCK / WAVE);
+    const int per_xcd = (tiles + XCDS - 1) / XCDS, grid = per_xcd * XCDS;
+    const EnsReplica &p = e->rep[r];
+    const double2 *psi = (p.cur ? e->psi1.p : e->psi0.p) + r * e->n_pad;
+    double2 *lap = (p.cur ? e->lap1.p : e->lap0.p) + r * e->n_pad;
+    const double2 *vals = e->lapv.p + r * e->n_slots;
+    if (pat.use16)
+        hipLaunchKernelGGL((k_psi_laplacian<false, int16_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, 0, pat.n_rows,
+                           pat.slice_off.p, pat.cols16.p, vals, ctx->lap_diag.p, ctx->fixed_mask.p, psi, lap, (const double *)nullptr,
+                           (const double *)nullptr, (double *)nullptr);
+    else
+        hipLaunchKernelGGL((k_psi_laplacian<false, int32_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, 0, pat.n_rows,
+                           pat.slice_off.p, pat.cols.p, vals, ctx->lap_diag.p, ctx->fixed_mask.p, psi, lap, (const double *)nullptr,
+                           (const double *)nullptr, (double *)nullptr);
+}
+
+static void ens_queue_round(tdgl_ensemble *e) {
+    tdgl_ctx *ctx = e->ctx;
+    const unsigned R = (unsigned)e->R;
+    hipLaunchKernelGGL(k_ens_psi_update, dim3(ctx->psi_blocks, R), dim3(BLOCK), 0, ctx->stream, ctx->n_own, e->n_pad, e->psi0.p, e->psi1.p,
+                       (const double2 *)e->lap0.p, (const double2 *)e->lap1.p, (const double *)e->mu.p, (const double *)e->eps.p, ctx->u,
+                       ctx->gamma, e->dmax_part.p, e->fail_part.p, e->d_ctl.p);
+    const SellPattern &pat = ctx->lap_pat;
+    const int tiles = (pat.n_slices + BLOCK / WAVE - 1) / (BLOCK / WAVE);
+    const int per_xcd = (tiles + XCDS - 1) / XCDS, grid = per_xcd * XCDS;
+#define TDGL_KENS(IT, COLS)                                                                                                       \
+    hipLaunchKernelGGL((k_ens_laplacian<IT>), dim3(grid, R), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, pat.n_rows,       \
+                       pat.slice_off.p, COLS, (const double2 *)e->lapv.p, e->n_slots, ctx->lap_diag.p, ctx->fixed_mask.p,         \
+                       (const double2 *)e->psi0.p, (const double2 *)e->psi1.p, e->lap0.p, e->lap1.p, ctx->area.p,                 \
+                       (const double *)e->ceff.p, e->bvec.p, e->n_pad, (const StepCtl *)e->d_ctl.p)
+    if (pat.use16) TDGL_KENS(int16_t, pat.cols16.p); else TDGL_KENS(int32_t, pat.cols.p);
+#undef TDGL_KENS
+    const int nt = e->nt;
+    hipLaunchKernelGGL(k_ens_dense_tiles, dim3(nt * (nt + 1) / 2, (R + ENS_RG - 1) / ENS_RG), dim3(BLOCK), 0, ctx->stream, (int)e->n, nt,
+                       (const double *)ctx->denseG.p, (const double *)e->bvec.p, e->n_pad, e->part.p, e->ldpart, (int)R,
+                       (const StepCtl *)e->d_ctl.p);
+    hipLaunchKernelGGL(k_ens_finish, dim3((unsigned)((e->n + WAVE - 1) / WAVE), R), dim3(BLOCK), 0, ctx->stream, (int)e->n, nt,
+                       (const double *)e->part.p, e->ldpart, (const double *)e->dmax_part.p, (const int32_t *)e->fail_part.p,
+                       ctx->psi_blocks, e->mu.p, e->n_pad, e->d_ctl.p, e->d_rec.p, (const int32_t *)e->limit.p);
+    if (e->np_ > 0)
+        hipLaunchKernelGGL(k_ens_probes, dim3((e->np_ + 63) / 64, R), dim3(64), 0, ctx->stream, e->np_, (const int32_t *)e->d_probes.p,
+                           (const double2 *)e->psi0.p, (const double2 *)e->psi1.p, (const double *)e->mu.p, e->n_pad, e->probe.p,
+                           (const StepCtl *)e->d_ctl.p);
+}
+
+// Up to max_steps[r] accepted steps of every replica (the loop of tdgl_run per replica: runner.py:379-433), stopping
+// a replica at end_time[r].  Outputs per replica r: out_dt[r * capacity + k], out_mu_probe / out_theta_probe
+// [r * capacity + k][n_probe], steps_done[r], reached_end[r].  A replica that spends its retry budget stops the call
+// after the batch it happened in: TDGL_ERR_PSI_RETRIES with the reference's message prefixed by the replica index
+// (the first such replica); the steps before it are delivered.
+extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, const double *end_time, int64_t capacity,
+                                 double *out_dt, double *out_mu_probe, double *out_theta_probe, int64_t *steps_done,
+                                 int32_t *reached_end, int32_t *failed) {
+    if (!e) return TDGL_ERR_ARG;
+    tdgl_ctx *ctx = e->ctx;
+    CTX_GUARD(ctx);
+    if (!max_steps || !end_time || capacity < 0 || !out_dt || !steps_done || !reached_end)
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_run: bad arguments");
+    const int R = e->R, np_ = e->np_;
+    for (int r = 0; r < R; ++r) {
+        const EnsReplica &p = e->rep[r];
+        if (max_steps[r] < 0 || max_steps[r] > capacity) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_run: max_steps[%d] outside [0, capacity]", r);
+        if (max_steps[r] > 0 && (!p.have_links || !p.have_eps || !p.have_state || !p.have_ctl))
+            TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_run: replica %d needs link exponents, epsilon, state and controller", r);
+        steps_done[r] = 0;
+        reached_end[r] = 0;
+        if (failed) failed[r] = 0;
+    }
+    for (int r = 0; r < R; ++r)
+        if (!e->rep[r].lap_valid && max_steps[r] > 0) {
+            ens_launch_laplacian_cache(e, r);
+            e->rep[r].lap_valid = true;
+        }
+    HIP_TRY(ctx, hipGetLastError());
+    int err_replica = -1;
+    double err_dt = 0.0;
+    int64_t err_step = 0;
+    for (;;) {
+        int active = 0;
+        for (int r = 0; r < R; ++r) {
+            const EnsReplica &p = e->rep[r];
+            const bool on = !reached_end[r] && steps_done[r] < max_steps[r];
+            active += on;
+            StepCtl &h = e->h_ctl[r];
+            memset(&h, 0, sizeof(h));
+            h.tentative_dt = p.tentative_dt;
+            h.attempt_dt = p.retries > 0 ? p.attempt_dt : p.tentative_dt;
+            h.time = p.time;
+            h.end_time = end_time[r];
+            h.dt_init = p.ctl.dt_init;
+            h.dt_cap = p.dt_cap;
+            h.multiplier = p.ctl.adaptive_time_step_multiplier;
+            h.stage_step = p.stage_step;
+            h.adaptive = p.ctl.adaptive;
+            h.window = p.ctl.adaptive_window;
+            h.max_retries = p.ctl.max_solve_retries;
+            h.cur = p.cur;
+            h.retries = p.retries;
+            h.poisoned = on ? 0 : 1;
+            h.runner_dt = p.runner_dt;
+            if (p.ctl.adaptive) {
+                const int64_t have = (int64_t)p.hist.size(), cnt = std::min<int64_t>(have, p.ctl.adaptive_window);
+                h.hist_count = (int)cnt;
+                for (int64_t i = 0; i < cnt; ++i) h.hist[i] = p.hist[have - cnt + i];
+            }
+            e->h_limit[r] = on ? (int32_t)std::min<int64_t>(max_steps[r] - steps_done[r], RA_BATCH_MAX) : 0;
+        }
+        if (active == 0 || err_replica >= 0) break;
+        const int batch = std::min(e->batch, RA_BATCH_MAX);
+        HIP_TRY(ctx, hipMemcpyAsync(e->d_ctl.p, e->h_ctl.data(), (size_t)R * sizeof(StepCtl), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(e->limit.p, e->h_limit.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        for (int s = 0; s < batch; ++s) ens_queue_round(e);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(e->h_ctl.data(), e->d_ctl.p, (size_t)R * sizeof(StepCtl), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(e->h_rec.data(), e->d_rec.p, (size_t)R * RA_BATCH_MAX * sizeof(StepRec), hipMemcpyDeviceToHost, ctx->stream));
+        if (np_ > 0)
+            HIP_TRY(ctx, hipMemcpyAsync(e->h_probe.data(), e->probe.p, e->h_probe.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        e->stat_rounds += batch;
+        e->stat_batches += 1;
+        for (int r = 0; r < R; ++r) {
+            if (reached_end[r] || steps_done[r] >= max_steps[r]) continue;  // (was poisoned for the whole batch)
+            EnsReplica &p = e->rep[r];
+            const StepCtl &h = e->h_ctl[r];
+            const StepRec *rec = e->h_rec.data() + (size_t)r * RA_BATCH_MAX;
+            const int done = h.n_done;
+            if (done < 0 || done > batch || h.n_acc < 0 || h.n_acc > done || h.n_acc > e->h_limit[r])
+                TDGL_FAIL(ctx, TDGL_ERR_HIP, "ensemble: corrupt attempt records of replica %d (%d processed, %d accepted of %d)", r, done,
+                          h.n_acc, batch);
+            int acc = 0;
+            double last_fail_dt = 0.0;
+            double *dts = out_dt + (size_t)r * capacity + steps_done[r];
+            for (int s = 0; s < done; ++s) {
+                if (!rec[s].ok) {
+                    last_fail_dt = rec[s].dt;
+                    continue;
+                }
+                dts[acc++] = rec[s].dt;
+                if (p.ctl.adaptive) p.hist.push_back(rec[s].dmax);
+            }
+            if (acc != h.n_acc) TDGL_FAIL(ctx, TDGL_ERR_HIP, "ensemble: replica %d's records disagree with its controller", r);
+            if (np_ > 0)
+                for (int k = 0; k < acc; ++k) {
+                    const double *row = e->h_probe.data() + ((size_t)r * RA_BATCH_MAX + k) * 2 * np_;
+                    const size_t at = ((size_t)r * capacity + steps_done[r] + k) * np_;
+                    if (out_mu_probe) memcpy(out_mu_probe + at, row, np_ * sizeof(double));
+                    if (out_theta_probe) memcpy(out_theta_probe + at, row + np_, np_ * sizeof(double));
+                }
+            const bool reached = h.reached_end != 0;
+            if (acc > 0) {
+                const int last = reached ? acc - 2 : acc - 1;  // (Runner.dt is not touched by the step that reached end_time)
+                if (last >= 0) p.runner_dt = dts[last];
+            }
+            p.cur = h.cur;
+            p.retries = h.error ? 0 : h.retries;
+            p.attempt_dt = h.attempt_dt;
+            p.tentative_dt = h.tentative_dt;
+            p.time = h.time;
+            p.stage_step = h.stage_step;
+            if (p.ctl.adaptive && (int64_t)p.hist.size() > 4 * (int64_t)p.ctl.adaptive_window + 64)
+                p.hist.erase(p.hist.begin(), p.hist.end() - p.ctl.adaptive_window);
+            steps_done[r] += acc;
+            if (reached) reached_end[r] = 1;
+            if (h.error) {
+                if (failed) failed[r] = 1;
+                if (err_replica < 0) {
+                    err_replica = r;
+                    err_dt = last_fail_dt;
+                    err_step = p.stage_step;
+                }
+            }
+        }
+        e->batch = std::min(2 * batch, RA_BATCH_MAX);
+    }
+    if (err_replica >= 0)
+        TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES,
+                  "replica %d: Solver failed to converge in %d retries at step %lld with dt = %.2e."
+                  " Try using a smaller dt_init.",
+                  err_replica, e->rep[err_replica].ctl.max_solve_retries, (long long)err_step, err_dt);
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_get_stats(tdgl_ensemble *e, int64_t *rounds, int64_t *batches) {
+    if (!e) return TDGL_ERR_ARG;
+    if (rounds) *rounds = e->stat_rounds;
+    if (batches) *batches = e->stat_batches;
+    return TDGL_OK;
+}

@@ -2191,16 +2191,17 @@ __device__ __forceinline__ void step_controller(StepCtl *__restrict__ ctl, StepR
 // in a fixed order.  Held back when the psi update of this step failed.  In the time
 // loop workgroup 0 also publishes the step's status block (failure flag, max d|psi|^2: what
 // k_publish_status does on the iterative path) -- one launch less per step.
-__global__ __launch_bounds__(BLOCK) void k_dense_sym_finish(int n, int nt, const double *__restrict__ part,
-                                                            const double *__restrict__ dmax_part,
-                                                            const int32_t *__restrict__ fail_part, int nfail,
-                                                            StepStatus *__restrict__ st, int guard, double *__restrict__ y,
-                                                            const double *__restrict__ u, double *__restrict__ upart,
-                                                            StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
+// (body: workgroup `blk` of the launch; the ensemble's launch, ensemble.inc, runs one per replica)
+__device__ __forceinline__ void dense_sym_finish_body(int blk, int n, int nt, const double *__restrict__ part,
+                                                      const double *__restrict__ dmax_part,
+                                                      const int32_t *__restrict__ fail_part, int nfail,
+                                                      StepStatus *__restrict__ st, int guard, double *__restrict__ y,
+                                                      const double *__restrict__ u, double *__restrict__ upart,
+                                                      StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
     __shared__ double sh[BLOCK / WAVE][WAVE];
     if (ctl && !ctl->live) return;  // run-ahead: a dead step (behind a failed one / the end) does nothing
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    const int i = blockIdx.x * WAVE + lane;
+    const int i = blk * WAVE + lane;
     const int64_t ldp = (int64_t)nt * DT;
     int bad = 0;
     if (guard && fail_part)
@@ -2225,10 +2226,10 @@ __global__ __launch_bounds__(BLOCK) void k_dense_sym_finish(int n, int nt, const
         if (i < n && !anybad) y[i] = v;
         if (u) {  // substructured solve: this workgroup's share of u . x_S (k_sub_up removes the mean with it)
             const double c = wave_sum(i < n ? u[i] * v : 0.0);
-            if (lane == 0) upart[blockIdx.x] = c;
+            if (lane == 0) upart[blk] = c;
         }
     }
-    if ((st || ctl) && blockIdx.x == 0) {  // (workgroup-uniform)
+    if ((st || ctl) && blk == 0) {  // (workgroup-uniform)
         double m;
         int f;
         reduce_psi_status(dmax_part, fail_part, nfail, &m, &f);
@@ -2243,6 +2244,15 @@ __global__ __launch_bounds__(BLOCK) void k_dense_sym_finish(int n, int nt, const
         }
         if (st && threadIdx.x > 0 && threadIdx.x < XCDS) st->dmax_bits[threadIdx.x] = 0ull;
     }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_dense_sym_finish(int n, int nt, const double *__restrict__ part,
+                                                            const double *__restrict__ dmax_part,
+                                                            const int32_t *__restrict__ fail_part, int nfail,
+                                                            StepStatus *__restrict__ st, int guard, double *__restrict__ y,
+                                                            const double *__restrict__ u, double *__restrict__ upart,
+                                                            StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
+    dense_sym_finish_body(blockIdx.x, n, nt, part, dmax_part, fail_part, nfail, st, guard, y, u, upart, ctl, rec);
 }
 
 // ------------------------------------------------------------------ substructured direct solve

@@ -1360,3 +1360,5 @@ extern "C" int tdgl_time_kernel(tdgl_ctx *ctx, int32_t kernel, int32_t reps, dou
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
 }
+
+#include "ensemble.inc"

@@ -226,6 +226,7 @@ class ScreeningOptions(C.Structure):
 
 # name -> (restype, argtypes); also the list of symbols the header declares
 _CTX = C.c_void_p
+_ENS = C.c_void_p  # tdgl_ensemble *
 SIGNATURES = {
     "tdgl_device_count": (C.c_int, []),
     "tdgl_version": (C.c_char_p, []),
@@ -318,6 +319,24 @@ SIGNATURES = {
     "tdgl_get_controller_state": (C.c_int, [_CTX, c_f64p, c_f64p, C.c_int64, C.POINTER(C.c_int64)]),
     "tdgl_set_controller_state": (C.c_int, [_CTX, C.c_double, c_f64p, C.c_int64]),
     "tdgl_get_state": (C.c_int, [_CTX, c_f64p, c_f64p, c_f64p, c_f64p]),
+    # ensembles (csrc/ensemble.inc)
+    "tdgl_ensemble_create": (C.c_int, [C.POINTER(_ENS), _CTX, C.c_int32]),
+    "tdgl_ensemble_destroy": (None, [_ENS]),
+    "tdgl_ensemble_size": (C.c_int, [_ENS, C.POINTER(C.c_int32)]),
+    "tdgl_ensemble_set_link_exponents": (C.c_int, [_ENS, C.c_int32, c_f64p]),
+    "tdgl_ensemble_set_mu_boundary": (C.c_int, [_ENS, C.c_int32, c_f64p]),
+    "tdgl_ensemble_set_epsilon": (C.c_int, [_ENS, C.c_int32, c_f64p]),
+    "tdgl_ensemble_set_state": (C.c_int, [_ENS, C.c_int32, c_f64p, c_f64p]),
+    "tdgl_ensemble_set_controller": (C.c_int, [_ENS, C.c_int32, C.POINTER(Controller)]),
+    "tdgl_ensemble_begin_stage": (C.c_int, [_ENS, C.c_int32]),
+    "tdgl_ensemble_set_probes": (C.c_int, [_ENS, c_i32p, C.c_int32]),
+    "tdgl_ensemble_get_loop_state": (C.c_int, [_ENS, C.c_int32, C.POINTER(C.c_int64), c_f64p, c_f64p, c_f64p]),
+    "tdgl_ensemble_run": (
+        C.c_int,
+        [_ENS, C.POINTER(C.c_int64), c_f64p, C.c_int64, c_f64p, c_f64p, c_f64p, C.POINTER(C.c_int64), c_i32p, c_i32p],
+    ),
+    "tdgl_ensemble_get_state": (C.c_int, [_ENS, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "tdgl_ensemble_get_stats": (C.c_int, [_ENS, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tdgl_apply_psi_laplacian": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_supercurrent": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_psi_update": (

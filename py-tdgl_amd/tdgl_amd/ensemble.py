@@ -1,0 +1,393 @@
+"""``solve_ensemble``: R independent replicas of ONE device -- an IV curve, a field sweep, a set of disorder
+realisations -- advanced together in one batched time loop on the GPU (``csrc/ensemble.inc``).
+
+Each replica is what ``tdgl.solve(device, options, ...)`` would run for its own inputs: same saved steps, dynamics,
+thermalisation, adaptive dt, retries and errors.  The replicas share the device, its mesh and the ``SolverOptions``;
+the mu solve is the dense pseudo-inverse of the Poisson matrix, applied to all replicas' right-hand sides in one
+pass over it.  Static inputs only: no screening, no time dependence, no ``output_file``, at most
+``ENSEMBLE_MAX_SITES`` sites.
+
+The per-replica set-up (vector potential, epsilon, terminal currents -> mu boundary values) is ``TDGLSolver``'s
+own, run without creating a device context (``_ReplicaInputs``).
+"""
+
+import ctypes as C
+import time as _time
+from typing import Callable, Dict, List, Optional, Sequence, Union
+
+import numpy as np
+
+from . import _lib
+from ._lib import c128, f64, i32, p_f64, p_i32
+from .device import Device
+from .options import SolverOptions
+from .solution import DynamicsData, Solution, TDGLData
+from .solver import TDGLSolver
+
+# Largest mesh the ensemble takes, set by measurement (DESIGN.md "Ensembles"): one round reads the dense inverse
+# (n^2 / 2 doubles) once per 16 replicas, and at R = 32 the ensemble's aggregate rate over tdgl.solve run one replica
+# after another falls from 5.4x at 5,791 sites to 1.4x at 11,774 and 0.85x at 15,745 sites.
+ENSEMBLE_MAX_SITES = 12_000
+
+
+class _ReplicaInputs(TDGLSolver):
+    """``TDGLSolver``'s set-up of one replica's inputs (link exponents, epsilon, terminal currents, initial values)
+    without the device context: ``_setup`` stops after the host half."""
+
+    def _setup(self, mesh) -> None:
+        self._setup_host(mesh)
+        self.ctx = None
+        self._currents_on_device = self._epsilon_on_device = False
+        self._evaluate_mu_boundary(0.0)
+
+
+def _is_per_replica(value) -> bool:
+    return isinstance(value, (list, tuple)) or (isinstance(value, np.ndarray) and value.ndim == 1)
+
+
+def broadcast_replicas(**per_replica) -> tuple:
+    """``(R, {name: list of R values})``: a list (tuple, 1-D array) gives one value per replica, anything else is
+    the value of every replica.  R is the length of the lists (1 without any); lists of different lengths raise."""
+    lengths = {name: len(v) for name, v in per_replica.items() if _is_per_replica(v)}
+    if len(set(lengths.values())) > 1:
+        raise ValueError(f"solve_ensemble: per-replica lists of different lengths: {lengths}")
+    R = next(iter(lengths.values())) if lengths else 1
+    if R < 1:
+        raise ValueError(f"solve_ensemble: empty per-replica lists: {lengths}")
+    return R, {name: list(v) if name in lengths else [v] * R for name, v in per_replica.items()}
+
+
+def _refuse_options(options: SolverOptions, n_sites: int) -> None:
+    if options.include_screening:
+        raise ValueError("solve_ensemble: include_screening=True is not supported (the ensemble has static link variables).")
+    if options.output_file is not None:
+        raise ValueError("solve_ensemble: output_file is not supported (the solutions are returned in memory).")
+    if n_sites > ENSEMBLE_MAX_SITES:
+        raise ValueError(f"solve_ensemble: the mesh has {n_sites} sites, more than ENSEMBLE_MAX_SITES = {ENSEMBLE_MAX_SITES}.")
+    if options.adaptive and not 1 <= options.adaptive_window <= 128:
+        raise ValueError(f"solve_ensemble: adaptive_window must be in [1, 128] (got {options.adaptive_window}).")
+
+
+def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
+    if rep.dynamic_vector_potential:
+        raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is not supported.")
+    if rep.dynamic_currents:
+        raise ValueError(f"solve_ensemble: replica {r}: time-dependent terminal_currents are not supported.")
+    if rep.dynamic_epsilon or rep._eps_table is not None:
+        raise ValueError(f"solve_ensemble: replica {r}: a time-dependent disorder_epsilon is not supported.")
+
+
+def _check_seeds(device, mesh, seeds) -> None:
+    for r, seed in enumerate(seeds):
+        if seed is None:
+            continue
+        if seed.device != device:
+            raise ValueError(f"solve_ensemble: replica {r}: the seed_solution.device must be equal to the device being simulated.")
+        if len(seed.tdgl_data.psi) != len(mesh.sites):
+            raise ValueError(f"solve_ensemble: replica {r}: the seed solution has {len(seed.tdgl_data.psi)} sites, "
+                             f"the device's mesh {len(mesh.sites)}.")
+
+
+def solve_ensemble(
+    device: Device,
+    options: SolverOptions,
+    applied_vector_potential: Union[Callable, float, Sequence] = 0,
+    terminal_currents: Union[Dict[str, float], None, Sequence] = None,
+    disorder_epsilon: Union[float, Callable, Sequence] = 1,
+    seed_solutions: Optional[Sequence[Optional[Solution]]] = None,
+) -> List[Solution]:
+    """Solve R replicas of one device together; returns the R ``Solution`` objects ``tdgl.solve`` returns for each
+    of them alone.  Every per-replica argument is a list of length R or one value for all replicas.
+
+    A replica that spends its retry budget raises ``RuntimeError`` with the reference's message, prefixed by the
+    replica index; no solution is returned then (like ``tdgl.solve``)."""
+    if device.mesh is None:
+        raise ValueError("The device has no mesh: call device.make_mesh() first.")
+    _refuse_options(options, len(device.mesh.sites))
+    R, args = broadcast_replicas(
+        applied_vector_potential=applied_vector_potential, terminal_currents=terminal_currents,
+        disorder_epsilon=disorder_epsilon, seed_solutions=seed_solutions,
+    )
+    _check_seeds(device, device.mesh, args["seed_solutions"])
+    reps = []
+    for r in range(R):
+        rep = _ReplicaInputs(device, options, applied_vector_potential=args["applied_vector_potential"][r],
+                             terminal_currents=args["terminal_currents"][r], disorder_epsilon=args["disorder_epsilon"][r],
+                             seed_solution=args["seed_solutions"][r])
+        _refuse_dynamic(r, rep)
+        reps.append(rep)
+    return EnsembleSolver(device.mesh, options, reps).solve()
+
+
+def solve_ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
+                                 gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
+                                 seed_states=None) -> List[Solution]:
+    """``solve_ensemble`` from dimensionless inputs (``TDGLSolver.from_dimensionless``): ``link_exponents`` A[m, 2]
+    (an array, or a list of them), ``epsilon`` (a scalar or an [n] array, or a list), ``currents``
+    ({terminal: dimensionless current}, or a list), ``seed_states`` (None or a list of (psi, mu) / None)."""
+    return ensemble_dimensionless(mesh, options, link_exponents, epsilon, u, gamma, terminal_info, currents, probe_points,
+                                  seed_states).solve()
+
+
+def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
+                           gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
+                           seed_states=None) -> "EnsembleSolver":
+    """The `EnsembleSolver` behind `solve_ensemble_dimensionless` (its ``solve()`` returns the solutions)."""
+    _refuse_options(options, len(mesh.sites))
+    per = dict(link_exponents=link_exponents, currents=currents, seed_states=seed_states)
+    if isinstance(epsilon, (list, tuple)):
+        per["epsilon"] = epsilon
+    R, args = broadcast_replicas(**per)
+    eps = args.get("epsilon", [epsilon] * R)
+    reps = []
+    for r in range(R):
+        rep = _ReplicaInputs.from_dimensionless(mesh, options, args["link_exponents"][r], eps[r], u, gamma,
+                                                terminal_info=terminal_info, current_func=args["currents"][r],
+                                                probe_points=probe_points)
+        _refuse_dynamic(r, rep)
+        if args["seed_states"][r] is not None:
+            rep.seed_state = args["seed_states"][r]
+        reps.append(rep)
+    return EnsembleSolver(mesh, options, reps)
+
+
+class EnsembleContext:
+    """Owns one ``tdgl_ensemble`` attached to a ``TDGLContext`` with a dense inverse."""
+
+    def __init__(self, ctx, n_replicas: int):
+        self.ctx = ctx
+        self._lib = _lib.load()
+        self.R = int(n_replicas)
+        self.n_probe = 0
+        self._ens = C.c_void_p()
+        self._chk(self._lib.tdgl_ensemble_create(C.byref(self._ens), ctx._ctx, self.R))
+
+    def _chk(self, status):
+        _lib.check(status, self.ctx._ctx)
+
+    def close(self):
+        if self._ens:
+            self._lib.tdgl_ensemble_destroy(self._ens)
+            self._ens = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_link_exponents(self, r, A):
+        A = f64(A)
+        assert A.shape == (self.ctx.m, 2)
+        self._chk(self._lib.tdgl_ensemble_set_link_exponents(self._ens, r, p_f64(A)))
+
+    def set_mu_boundary(self, r, mu_b):
+        mu_b = f64(mu_b)
+        assert mu_b.shape == (self.ctx.n_boundary,)
+        self._chk(self._lib.tdgl_ensemble_set_mu_boundary(self._ens, r, p_f64(mu_b) if len(mu_b) else None))
+
+    def set_epsilon(self, r, eps):
+        eps = f64(eps)
+        assert eps.shape == (self.ctx.n,)
+        self._chk(self._lib.tdgl_ensemble_set_epsilon(self._ens, r, p_f64(eps)))
+
+    def set_state(self, r, psi, mu):
+        psi, mu = c128(psi), f64(mu)
+        assert psi.shape == (self.ctx.n,) and mu.shape == (self.ctx.n,)
+        self._chk(self._lib.tdgl_ensemble_set_state(self._ens, r, p_f64(psi), p_f64(mu)))
+
+    def set_controller(self, r, options: SolverOptions):
+        c = _lib.Controller(float(options.dt_init), float(options.dt_max), int(bool(options.adaptive)),
+                            int(options.adaptive_window), int(options.max_solve_retries),
+                            float(options.adaptive_time_step_multiplier))
+        self._chk(self._lib.tdgl_ensemble_set_controller(self._ens, r, C.byref(c)))
+
+    def set_probes(self, sites):
+        sites = i32([] if sites is None else sites)
+        self.n_probe = len(sites)
+        self._chk(self._lib.tdgl_ensemble_set_probes(self._ens, p_i32(sites) if len(sites) else None, len(sites)))
+
+    def begin_stage(self, r):
+        self._chk(self._lib.tdgl_ensemble_begin_stage(self._ens, r))
+
+    def loop_state(self, r):
+        step, t, rdt, tdt = C.c_int64(0), C.c_double(0), C.c_double(0), C.c_double(0)
+        self._chk(self._lib.tdgl_ensemble_get_loop_state(self._ens, r, C.byref(step), C.byref(t), C.byref(rdt), C.byref(tdt)))
+        return dict(step=step.value, time=t.value, dt=rdt.value, tentative_dt=tdt.value)
+
+    def run(self, max_steps, end_time):
+        """Up to ``max_steps[r]`` steps of every replica r, stopping at ``end_time[r]``.  Returns a list of dicts
+        (``dt``, ``mu``, ``theta``, ``reached_end``) like ``TDGLContext.run``."""
+        R = self.R
+        ms = np.ascontiguousarray(max_steps, dtype=np.int64)
+        et = f64(end_time)
+        assert ms.shape == (R,) and et.shape == (R,)
+        cap = max(int(ms.max()), 1)
+        npb = self.n_probe
+        dts = np.zeros((R, cap))
+        mu_p = np.zeros((R, cap, npb)) if npb else None
+        th_p = np.zeros((R, cap, npb)) if npb else None
+        done = np.zeros(R, dtype=np.int64)
+        reached = np.zeros(R, dtype=np.int32)
+        failed = np.zeros(R, dtype=np.int32)
+        status = self._lib.tdgl_ensemble_run(
+            self._ens, ms.ctypes.data_as(C.POINTER(C.c_int64)), p_f64(et), cap, p_f64(dts), p_f64(mu_p), p_f64(th_p),
+            done.ctypes.data_as(C.POINTER(C.c_int64)), p_i32(reached), p_i32(failed))
+        self._chk(status)
+        return [dict(dt=dts[r, :done[r]], mu=None if mu_p is None else mu_p[r, :done[r]],
+                     theta=None if th_p is None else th_p[r, :done[r]], reached_end=bool(reached[r])) for r in range(R)]
+
+    def get_state(self, r, currents=True):
+        n, m = self.ctx.n, self.ctx.m
+        psi, mu = np.empty(n, dtype=np.complex128), np.empty(n)
+        js = np.empty(m) if currents else None
+        jn = np.empty(m) if currents else None
+        self._chk(self._lib.tdgl_ensemble_get_state(self._ens, r, p_f64(psi), p_f64(mu), p_f64(js), p_f64(jn)))
+        return dict(psi=psi, mu=mu, supercurrent=js, normal_current=jn)
+
+    def stats(self):
+        rounds, batches = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.tdgl_ensemble_get_stats(self._ens, C.byref(rounds), C.byref(batches)))
+        return dict(rounds=rounds.value, batches=batches.value)
+
+
+def build_context(mesh, options: SolverOptions, fixed_sites, u: float, gamma: float):
+    """A single-GPU context on ``mesh`` with the dense inverse, whatever `TDGLContext.DENSE_MAX_SITES` says."""
+    from .hipcore import TDGLContext
+
+    ctx = TDGLContext(mesh, fixed_sites=fixed_sites, fix_psi=options.terminal_psi is not None, u=u, gamma=gamma,
+                      device_id=options.device_id)
+    try:
+        ctx.build_poisson(rtol=options.pcg_rtol, max_iter=options.pcg_max_iter, nu=options.amg_smoothing_sweeps,
+                          dense_max_sites=ENSEMBLE_MAX_SITES)
+        if not getattr(ctx, "dense_direct", False):
+            raise RuntimeError("solve_ensemble: the dense inverse of the Poisson matrix could not be built "
+                               "(a mesh in several pieces?)")
+    except BaseException:
+        ctx.close()
+        raise
+    return ctx
+
+
+class EnsembleSolver:
+    """The Runner's loop (runner.py:288-454, ``TDGLSolver.solve``) for every replica of an ensemble."""
+
+    def __init__(self, mesh, options: SolverOptions, replicas: Sequence[TDGLSolver]):
+        self.mesh = mesh
+        self.options = options
+        self.reps = list(replicas)
+
+    def solve(self) -> List[Solution]:
+        opts = self.options
+        opts.validate()
+        reps, R = self.reps, len(self.reps)
+        t_start = _time.perf_counter()
+        r0 = reps[0]
+        ctx = build_context(self.mesh, opts, r0.fixed_sites, r0.u, r0.gamma)
+        ens = None
+        try:
+            ens = EnsembleContext(ctx, R)
+            self.setup_seconds = _time.perf_counter() - t_start
+            return self._run(ctx, ens, t_start)
+        finally:
+            if ens is not None:
+                self.ensemble_stats = ens.stats()
+                ens.close()
+            ctx.close()
+
+    def _run(self, ctx, ens: EnsembleContext, t_start: float) -> List[Solution]:
+        opts = self.options
+        reps, R = self.reps, len(self.reps)
+        probes = reps[0].probe_points
+        ens.set_probes(probes)
+        for r, rep in enumerate(reps):
+            ens.set_link_exponents(r, rep.current_A_applied)
+            ens.set_mu_boundary(r, rep.mu_boundary)
+            ens.set_epsilon(r, rep.epsilon)
+            seed = getattr(rep, "seed_state", None)
+            if rep.seed_solution is not None:
+                seed = (rep.seed_solution.tdgl_data.psi, rep.seed_solution.tdgl_data.mu)
+            ens.set_state(r, *(seed if seed is not None else (rep.psi_init, rep.mu_init)))
+            ens.set_controller(r, opts)
+        seeded = [rep.seed_solution is not None or getattr(rep, "seed_state", None) is not None for rep in reps]
+        stages = ([("Thermalizing", opts.skip_time, False)] if opts.skip_time else []) + [("Simulating", opts.solve_time, True)]
+        stage = [0] * R
+        i = [0] * R
+        saved = [[] for _ in range(R)]
+        dyn = [dict(dt=[], time=[], mu=[], theta=[]) for _ in range(R)]
+        n_steps = [{"Thermalizing": 0, "Simulating": 0} for _ in range(R)]
+        active = [True] * R
+        for r in range(R):
+            ens.begin_stage(r)
+
+        def save_step(r):
+            ls = ens.loop_state(r)
+            if ls["step"] == 0 and not saved[r] and not seeded[r]:
+                st = ens.get_state(r, currents=False)
+                js = jn = np.zeros(ctx.m)  # reference initial values (solver.py:736-737)
+            else:
+                st = ens.get_state(r)
+                js, jn = st["supercurrent"], st["normal_current"]
+            saved[r].append(TDGLData(ls["step"], ls["time"], ls["dt"], st["psi"], st["mu"], js, jn,
+                                     applied_vector_potential=reps[r].current_A_applied, epsilon=reps[r].epsilon,
+                                     induced_vector_potential=None))
+
+        while any(active):
+            max_steps = np.zeros(R, dtype=np.int64)
+            end_time = np.zeros(R)
+            t_before = np.zeros(R)
+            for r in range(R):
+                if not active[r]:
+                    continue
+                name, end, save = stages[stage[r]]
+                if i[r] % opts.save_every == 0 and save:  # runner.py:398-401
+                    save_step(r)
+                max_steps[r] = opts.save_every - (i[r] % opts.save_every)
+                end_time[r] = end
+                t_before[r] = ens.loop_state(r)["time"]
+            res = ens.run(max_steps, end_time)
+            for r in range(R):
+                if not active[r]:
+                    continue
+                name, end, save = stages[stage[r]]
+                out = res[r]
+                k = len(out["dt"])
+                n_steps[r][name] += k
+                if save:
+                    dyn[r]["dt"].append(out["dt"])
+                    dyn[r]["time"].append(t_before[r] + np.concatenate([[0.0], np.cumsum(out["dt"][:-1])]))
+                    if out["mu"] is not None:
+                        dyn[r]["mu"].append(out["mu"])
+                        dyn[r]["theta"].append(out["theta"])
+                if not out["reached_end"]:
+                    i[r] += k
+                    continue
+                i[r] += k - 1
+                if save and (i[r] % opts.save_every):
+                    save_step(r)
+                if stage[r] + 1 < len(stages):
+                    stage[r] += 1
+                    i[r] = 0
+                    ens.begin_stage(r)
+                else:
+                    active[r] = False
+        ctx.synchronize()
+        total = _time.perf_counter() - t_start
+        cat = lambda xs: np.concatenate(xs) if xs else np.array([])  # noqa: E731
+        solutions = []
+        for r, rep in enumerate(reps):
+            d = dyn[r]
+            dynamics = DynamicsData(
+                dt=cat(d["dt"]), time=cat(d["time"]),
+                mu=cat(d["mu"]).T if d["mu"] else None, theta=cat(d["theta"]).T if d["theta"] else None,
+                pcg_iterations=np.zeros(sum(len(x) for x in d["dt"]), dtype=np.int32),
+            )
+            solutions.append(Solution(
+                device=rep.device, options=opts, saved_steps=saved[r], dynamics=dynamics,
+                dynamic_vector_potential=False, dynamic_epsilon=False,
+                applied_vector_potential=rep.applied_vector_potential, terminal_currents=rep.terminal_currents,
+                disorder_epsilon=rep.disorder_epsilon, total_seconds=total,
+                stats=dict(steps_thermalizing=n_steps[r]["Thermalizing"], steps_simulating=n_steps[r]["Simulating"],
+                           mean_pcg_iterations=0.0, mu_solver="dense_ensemble", replica=r, replicas=R),
+            ))
+        return solutions

@@ -282,14 +282,22 @@ class TDGLSolver:
         self._setup(mesh)
         return self
 
+    def _setup_host(self, mesh) -> None:
+        """The host-side part of the set-up (solver.py:258-289): fixed sites, initial values, mu boundary values."""
+        em = mesh.edge_mesh
+        idx = [np.asarray(t.site_indices) for t in self.terminal_info]
+        self.fixed_sites = np.concatenate(idx).astype(np.int64) if idx else np.array([], dtype=np.int64)
+        self.terminal_current_densities = {name: 0 for name in self.terminal_names}
+        self.psi_init = np.ones(len(mesh.sites), dtype=np.complex128)
+        if self.options.terminal_psi is not None:
+            self.psi_init[self.fixed_sites] = self.options.terminal_psi
+        self.mu_init = np.zeros(len(mesh.sites))
+        self.mu_boundary = np.zeros(len(em.boundary_edge_indices))
+
     def _setup(self, mesh) -> None:
         """Device-side set-up shared by both constructors (solver.py:258-320)."""
         options = self.options
-        em = mesh.edge_mesh
-        names = self.terminal_names
-        idx = [np.asarray(t.site_indices) for t in self.terminal_info]
-        self.fixed_sites = np.concatenate(idx).astype(np.int64) if idx else np.array([], dtype=np.int64)
-        self.terminal_current_densities = {name: 0 for name in names}
+        self._setup_host(mesh)
 
         # ---- operators on the device (solver.py:267-282) --------------------------------------
         terminal_psi = options.terminal_psi
@@ -316,12 +324,7 @@ class TDGLSolver:
         else:
             self.operators.set_link_exponents(self.current_A_applied)
 
-        # ---- initial values (solver.py:284-289) ------------------------------------------------
-        self.psi_init = np.ones(len(mesh.sites), dtype=np.complex128)
-        if terminal_psi is not None:
-            self.psi_init[self.fixed_sites] = terminal_psi
-        self.mu_init = np.zeros(len(mesh.sites))
-        self.mu_boundary = np.zeros(len(em.boundary_edge_indices))
+        # ---- initial values (solver.py:284-289): _setup_host ----------------------------------------
         self.ctx.set_epsilon(self.epsilon)
         self.ctx.set_mu_boundary(self.mu_boundary)
         self.ctx.set_probes(self.probe_points)
@@ -360,6 +363,13 @@ class TDGLSolver:
         """solver.py:325-345.  Returns True if mu_boundary changed (and was re-uploaded)."""
         if self._currents_on_device:
             return False  # tdgl_run evaluates the tables itself (tdgl_set_mu_boundary_table)
+        changed = self._evaluate_mu_boundary(time)
+        if changed:
+            self.ctx.set_mu_boundary(self.mu_boundary)
+        return changed
+
+    def _evaluate_mu_boundary(self, time: float) -> bool:
+        """The host half of update_mu_boundary: self.mu_boundary at ``time``; True if it changed."""
         currents = self.current_func(time)
         changed = False
         for term in self.terminal_info:
@@ -370,8 +380,6 @@ class TDGLSolver:
                 self.terminal_current_densities[term.name] = density
                 self.mu_boundary[term.boundary_edge_indices] = density
                 changed = True
-        if changed:
-            self.ctx.set_mu_boundary(self.mu_boundary)
         return changed
 
     def update_dynamic_inputs(self, time: float, dt_prev: float) -> None:
