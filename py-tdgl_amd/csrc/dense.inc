@@ -239,14 +239,8 @@ __global__ __launch_bounds__(BLOCK) void k_dense_pack_sym(int64_t n, int64_t N, 
 }  // namespace tdgl
 
 // M [N x N] (N = a multiple of GB, identity on the padding) -> symmetric tiles of -(swept M)[:n, :n] - shift_out
-// in ctx->denseG, with the work array of k_dense_sym_tiles / _finish
-static int dense_sweep_pack_to(tdgl_ctx *ctx, DevBuf<double> &M, int64_t n, int64_t N, double shift_out, DevBuf<double> &G,
-                               DevBuf<double> &part, int *tiles_out);
-static int dense_sweep_pack(tdgl_ctx *ctx, DevBuf<double> &M, int64_t n, int64_t N, double shift_out) {
-    return dense_sweep_pack_to(ctx, M, n, N, shift_out, ctx->denseG, ctx->dense_part, &ctx->dense_tiles);
-}
-static int dense_sweep_pack_to(tdgl_ctx *ctx, DevBuf<double> &M, int64_t n, int64_t N, double shift_out, DevBuf<double> &G,
-                               DevBuf<double> &part, int *tiles_out) {
+// in D, with the work array of k_dense_sym_tiles / _finish
+static int dense_sweep_pack(tdgl_ctx *ctx, DevBuf<double> &M, int64_t n, int64_t N, double shift_out, DenseTiles &D) {
     const int nb = (int)(N / GB);
     DevBuf<double> Pbuf, Wbuf, Dbuf;
     DevBuf<int32_t> d_flag;
@@ -270,52 +264,26 @@ static int dense_sweep_pack_to(tdgl_ctx *ctx, DevBuf<double> &M, int64_t n, int6
                   " (a mesh in several pieces?)");
     const int nt = (int)((n + DT - 1) / DT);
     const size_t tiles = (size_t)nt * (nt + 1) / 2;
-    HIP_TRY(ctx, G.alloc(tiles * DT * DT, false));
+    HIP_TRY(ctx, D.G.alloc(tiles * DT * DT, false));
     hipLaunchKernelGGL(k_dense_pack_sym, dim3((unsigned)tiles), dim3(BLOCK), 0, ctx->stream, n, N, (const double *)M.p, shift_out,
-                       G.p);
+                       D.G.p);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, part.alloc((size_t)nt * nt * DT));
+    HIP_TRY(ctx, D.part.alloc((size_t)nt * nt * DT));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *tiles_out = nt;
-    if (&G == &ctx->denseG) ctx->dense_n = n;
+    D.tiles = nt;
+    D.n = n;
     return TDGL_OK;
 }
 
-static void dense_release(tdgl_ctx *ctx) {
-    ctx->denseG.release();
-    ctx->dense_part.release();
-    ctx->dense_ld = 0;
-    ctx->dense_tiles = 0;
-    ctx->dense_n = 0;
-    ctx->sub_parts = 0;
-    ctx->sub_vals.release();
-    ctx->sub_vals32.release();
-    ctx->denseG32.release();
-    if (!ctx->schur_pending) {  // (between tdgl_poisson_schur_begin and _finish the index map and work vectors are already in place)
-        ctx->sub_map.release();
-        ctx->sub_bp.release();
-        ctx->sub_xp.release();
-        ctx->sub_z.release();
-    }
-    ctx->sub_precond = ctx->sub_fp32 = ctx->sub_lanes = false;
-    ctx->sub_sym_lds[0] = ctx->sub_sym_lds[1] = ctx->sub_sym_lds[2] = 0;
-    ctx->sub_up_R[0] = ctx->sub_up_R[1] = ctx->sub_up_R[2] = 1;
-    ctx->sub_ident[0] = ctx->sub_ident[1] = ctx->sub_ident[2] = false;
-    ctx->sub_e.release();
-    ctx->sub_w.release();
-    ctx->sub_coupling.nnz = 0;
-    for (auto &I : ctx->sub_in) {
-        I.parts = 0;
-        I.coupling.nnz = 0;
-        I.vals.release();
-        I.vals32.release();
-        I.e.release();
-        I.w.release();
-    }
-    ctx->sub_n_inner = 0;
-    ctx->sub_outer_parts_pending = 0;
-    ctx->sub_need_coupling[0] = ctx->sub_need_coupling[1] = ctx->sub_need_coupling[2] = false;
-    ctx->sub_wait_inner = false;
+// the tiles in fp32 (G released)
+static int dense_to_fp32(tdgl_ctx *ctx, DenseTiles &D) {
+    HIP_TRY(ctx, D.G32.alloc(std::max<size_t>(D.G.n, 1), false));
+    if (D.G.n > 0)
+        hipLaunchKernelGGL(k_to_float, dim3(vec_grid((int64_t)D.G.n)), dim3(BLOCK), 0, ctx->stream, (int64_t)D.G.n, (const double *)D.G.p,
+                           D.G32.p);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    D.G.release();
+    return TDGL_OK;
 }
 
 extern "C" int tdgl_poisson_build_dense_inverse(tdgl_ctx *ctx, double *seconds) {
@@ -326,7 +294,6 @@ extern "C" int tdgl_poisson_build_dense_inverse(tdgl_ctx *ctx, double *seconds) 
     if (n < 2 || n > 46000) TDGL_FAIL(ctx, TDGL_ERR_ARG, "dense inverse: %lld sites is outside what a dense matrix is meant for", (long long)n);
     const int64_t t_begin = now_ns();
     AmgLevel &L0 = *ctx->levels[0];
-    dense_release(ctx);
     // s = mean diagonal of A: the added eigenvalue sits inside the spectrum
     DevBuf<double> d_s;
     HIP_TRY(ctx, d_s.alloc(1));
@@ -343,8 +310,10 @@ extern "C" int tdgl_poisson_build_dense_inverse(tdgl_ctx *ctx, double *seconds) 
     const SellPattern &pat = L0.A.pat;
     hipLaunchKernelGGL(k_dense_scatter_sell, dim3(grid_for((int64_t)pat.n_slices * WAVE)), dim3(BLOCK), 0, ctx->stream,
                        pat.n_slices, n, pat.slice_off.p, pat.cols.p, L0.A.vals.p, N, M.p);
-    TDGL_TRY(dense_sweep_pack(ctx, M, n, N, 1.0 / (s * (double)n)));
-    ctx->dense_ld = round_up(n, 2);
+    auto f = std::make_unique<DirectFactors>();
+    TDGL_TRY(dense_sweep_pack(ctx, M, n, N, 1.0 / (s * (double)n), f->dense));
+    f->ld = round_up(n, 2);
+    ctx->direct = std::move(f);
     if (seconds) *seconds = (double)(now_ns() - t_begin) * 1e-9;
     return TDGL_OK;
 }
@@ -361,6 +330,14 @@ __global__ __launch_bounds__(BLOCK) void k_dense_from(int64_t n, int64_t N, doub
     M[i] = (r < n && c < n) ? src[r * n + c] + shift : (r == c ? 1.0 : 0.0);
 }
 }  // namespace tdgl
+
+// a CSR-like offset array of n entries (n + 1 offsets): from 0, never decreasing
+static bool offsets_ok(const int32_t *ptr, int64_t n) {
+    if (ptr[0] != 0) return false;
+    for (int64_t i = 0; i < n; ++i)
+        if (ptr[i + 1] < ptr[i]) return false;
+    return true;
+}
 
 // The way up's work list (k_sub_up): chunks of <= 64 rows of one part, a wavefront each, reading the part's -E_p^T
 // block of the value pool (et_off[p]: [s_p, n_p] row major).
@@ -413,20 +390,9 @@ static int sub_upload_down_lists(tdgl_ctx *ctx, int P, int64_t n_rows, const int
     return TDGL_OK;
 }
 
-// Everything of one level except the dense matrix: checks, index arrays, value pools.  `n` = length of the
-// vector the level works on (the site count, or the first level's separator for the second level).
-struct SubLevelDst {
-    tdgl::DevBuf<int32_t> &part_ptr, &seg_ptr, &seg_x, &seg_len, &sep_ptr, &sep_idx, &row_part;
-    tdgl::DevBuf<int64_t> &seg_val, &e_off, &g_off;
-    tdgl::DevBuf<double> &vals, &e, &u, &w;
-    tdgl::DevBuf<tdgl::SubUpChunk> &chunks;
-    tdgl::DevBuf<tdgl::SubDownChunk> &down_chunks;
-    tdgl::DevBuf<tdgl::SubDownRow> &down_rows;
-    bool *sparse_sep;
-    bool *ident_sep;
-};
-
-static int sub_upload_level(tdgl_ctx *ctx, const tdgl_substructure *sub, int64_t n, SubLevelDst d, const char *who) {
+// Everything of one level except the dense matrix: checks, index arrays, value pools, into a level under construction.
+// `n` = length of the vector the level works on (the site count, a rank's interior, or the previous level's separator).
+static int sub_upload_level(tdgl_ctx *ctx, const tdgl_substructure *sub, int64_t n, SubLevel &d, const char *who) {
     const int64_t nI = sub->n_interior, nS = sub->n_sep;
     const int P = sub->n_parts;
     if (nI + nS != n || P < 1 || nS < 2 || !sub->part_ptr || !sub->seg_ptr || !sub->seg_val || !sub->seg_x ||
@@ -435,6 +401,8 @@ static int sub_upload_level(tdgl_ctx *ctx, const tdgl_substructure *sub, int64_t
     if (sub->part_ptr[0] != 0 || sub->part_ptr[P] != nI)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: part_ptr must run from 0 to n_interior", who);
     const int64_t n_rows = n + P;
+    if (!offsets_ok(sub->seg_ptr, n_rows) || !offsets_ok(sub->sep_ptr, P))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: seg_ptr and sep_ptr must run from 0 and not decrease", who);
     const int64_t n_seg = sub->seg_ptr[n_rows];
     for (int64_t k = 0; k < n_seg; ++k)
         if (sub->seg_len[k] < 0 || sub->seg_val[k] < 0 || sub->seg_val[k] + sub->seg_len[k] > sub->n_vals || sub->seg_x[k] < 0 ||
@@ -474,7 +442,6 @@ static int sub_upload_level(tdgl_ctx *ctx, const tdgl_substructure *sub, int64_t
     HIP_TRY(ctx, d.seg_len.upload(std::vector<int32_t>(sub->seg_len, sub->seg_len + n_seg)));
     HIP_TRY(ctx, d.sep_ptr.upload(std::vector<int32_t>(sub->sep_ptr, sub->sep_ptr + P + 1)));
     HIP_TRY(ctx, d.sep_idx.upload(std::vector<int32_t>(sub->sep_idx, sub->sep_idx + n_sidx)));
-    HIP_TRY(ctx, d.e_off.upload(std::vector<int64_t>(sub->e_off, sub->e_off + P)));
     HIP_TRY(ctx, d.row_part.upload(row_part));
     {
         // the -E_p^T blocks follow the G blocks in the pool, [s_p, n_p] row major, part after part: where the way up
@@ -482,14 +449,14 @@ static int sub_upload_level(tdgl_ctx *ctx, const tdgl_substructure *sub, int64_t
         // (every separator row its identity segment alone: the form that goes with tdgl_poisson_set_substructure_coupling)
         bool sparse_sep = n_sidx > 0;
         for (int64_t row = nI; row < n && sparse_sep; ++row) sparse_sep = sub->seg_ptr[row + 1] - sub->seg_ptr[row] == 1;
-        *d.sparse_sep = sparse_sep;
+        d.need_coupling = sparse_sep;
         // ... and that one segment the unit entry on the row itself (what pack_for_device writes): the row is a copy
         bool ident = sparse_sep;
         for (int64_t row = nI; row < n && ident; ++row) {
             const int64_t k = sub->seg_ptr[row];
             ident = sub->seg_len[k] == 1 && sub->seg_x[k] == row && sub->vals[sub->seg_val[k]] == 1.0;
         }
-        *d.ident_sep = ident;
+        d.ident = ident;
         std::vector<int64_t> et_off(P);
         int64_t off = 1;
         for (int p = 0; p < P; ++p) off += (int64_t)(sub->part_ptr[p + 1] - sub->part_ptr[p]) * (sub->part_ptr[p + 1] - sub->part_ptr[p]);
@@ -509,7 +476,7 @@ static int sub_upload_level(tdgl_ctx *ctx, const tdgl_substructure *sub, int64_t
             off += rows * cnt;
         }
         if (off > sub->n_vals) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: the value pool is shorter than its G and -E^T blocks", who);
-        TDGL_TRY(sub_upload_chunks(ctx, P, sub->part_ptr, sub->sep_ptr, et_off.data(), d.chunks, who));
+        TDGL_TRY(sub_upload_chunks(ctx, P, sub->part_ptr, sub->sep_ptr, et_off.data(), d.up_chunks, who));
     }
     TDGL_TRY(sub_upload_down_lists(ctx, P, n_rows, sub->part_ptr, g_off.data(), sub->seg_ptr, sub->seg_val, sub->seg_x, sub->seg_len,
                                    d.down_chunks, d.down_rows));
@@ -517,16 +484,19 @@ static int sub_upload_level(tdgl_ctx *ctx, const tdgl_substructure *sub, int64_t
     HIP_TRY(ctx, d.vals.alloc((size_t)sub->n_vals, false));
     HIP_TRY(ctx, hipMemcpy(d.vals.p, sub->vals, (size_t)sub->n_vals * sizeof(double), hipMemcpyHostToDevice));
     // (e_vals, the row-major copy of the E_p blocks, is not uploaded: the way up reads the pool's -E_p^T blocks)
-    d.e.release();
     HIP_TRY(ctx, d.u.upload(std::vector<double>(sub->u, sub->u + nS)));
     HIP_TRY(ctx, d.w.alloc((size_t)n_rows));
+    HIP_TRY(ctx, d.xs.alloc((size_t)nS));
+    d.parts = P;
+    d.nI = nI;
+    d.nS = nS;
     return TDGL_OK;
 }
 
 // pseudo-inverse of a singular Schur complement [m, m] (null space: the constants) on the device, into
-// denseG: (S + (s / m) 1 1^T)^-1 - 1 1^T / (s m)
-// (ctx->sub_nonsingular -- the factors of a rank's interior block, tdgl_poisson_schur_begin: the plain inverse)
-static int sub_schur_pinv(tdgl_ctx *ctx, const double *schur, int64_t m, const char *who) {
+// D: (S + (s / m) 1 1^T)^-1 - 1 1^T / (s m)
+// (plain -- the factors of a rank's interior block, tdgl_poisson_schur_begin: the plain inverse)
+static int sub_schur_pinv(tdgl_ctx *ctx, const double *schur, int64_t m, bool plain, DenseTiles &D, const char *who) {
     double s = 0.0;
     for (int64_t i = 0; i < m; ++i) s += schur[i * m + i];
     s /= (double)m;
@@ -536,48 +506,57 @@ static int sub_schur_pinv(tdgl_ctx *ctx, const double *schur, int64_t m, const c
     HIP_TRY(ctx, src.alloc((size_t)m * m, false));
     HIP_TRY(ctx, hipMemcpy(src.p, schur, (size_t)m * m * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(ctx, M.alloc((size_t)N * N, false));
-    const bool plain = ctx->sub_nonsingular;
     hipLaunchKernelGGL(k_dense_from, dim3(grid_for(N * N)), dim3(BLOCK), 0, ctx->stream, m, N, plain ? 0.0 : s / (double)m, (const double *)src.p, M.p);
-    TDGL_TRY(dense_sweep_pack(ctx, M, m, N, plain ? 0.0 : 1.0 / (s * (double)m)));
+    TDGL_TRY(dense_sweep_pack(ctx, M, m, N, plain ? 0.0 : 1.0 / (s * (double)m), D));
     return TDGL_OK;
+}
+
+// the last level's separator: its dense pseudo-inverse and the partials of its finish, staged in f (a new object, or the
+// commit of an inner level)
+static int sub_top(tdgl_ctx *ctx, DirectFactors &f, const double *schur, int64_t nS, const char *who) {
+    f.nfin = (int)((nS + WAVE - 1) / WAVE);
+    HIP_TRY(ctx, f.upart.alloc((size_t)f.nfin));
+    if (f.levels > 1) HIP_TRY(ctx, f.mean.alloc(1));
+    return sub_schur_pinv(ctx, schur, nS, f.n_local > 0, f.dense, who);
 }
 
 extern "C" int tdgl_poisson_set_substructure(tdgl_ctx *ctx, const tdgl_substructure *sub, double *seconds) {
     CTX_GUARD(ctx);
     if (!sub) {
-        dense_release(ctx);
-        schur_release(ctx);
+        ctx->direct.reset();
         return TDGL_OK;
     }
-    if (!ctx->schur_pending) schur_release(ctx);  // (a description outside tdgl_poisson_schur_begin / _finish is of the whole matrix)
-    if (distributed(ctx) && !ctx->schur_pending)
+    // (between tdgl_poisson_schur_begin and _finish: this rank's interior; otherwise the whole matrix)
+    DirectFactors *cur = ctx->direct.get();
+    const bool schur = cur && cur->in_schur_setup();
+    if (distributed(ctx) && !schur)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure: single-GPU contexts only (one process per GPU: inside tdgl_poisson_schur_begin / _finish)");
     if (ctx->levels.empty()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_set_substructure: set the hierarchy first");
-    // (schur == NULL: the Schur system is solved by a second level, tdgl_poisson_set_substructure_inner)
+    // (schur == NULL: the Schur system is solved by further levels, tdgl_poisson_set_substructure_inner)
     if (sub->schur && sub->n_sep > 46000)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure: a separator of %lld sites is outside what a dense matrix is meant for",
                   (long long)sub->n_sep);
     const int64_t t_begin = now_ns();
-    dense_release(ctx);
-    TDGL_TRY(sub_upload_level(ctx, sub, ctx->sub_n_local > 0 ? ctx->sub_n_local : ctx->n,
-                              SubLevelDst{ctx->sub_part_ptr, ctx->sub_seg_ptr, ctx->sub_seg_x, ctx->sub_seg_len, ctx->sub_sep_ptr,
-                                          ctx->sub_sep_idx, ctx->sub_row_part, ctx->sub_seg_val, ctx->sub_e_off, ctx->sub_g_off,
-                                          ctx->sub_vals, ctx->sub_e, ctx->sub_u, ctx->sub_w, ctx->sub_chunks, ctx->sub_down_chunks, ctx->sub_down_rows, &ctx->sub_need_coupling[0], &ctx->sub_ident[0]},
-                              "tdgl_poisson_set_substructure"));
-    const int64_t nS = sub->n_sep;
-    HIP_TRY(ctx, ctx->sub_xs.alloc((size_t)nS));
-    ctx->sub_nI = sub->n_interior;
-    ctx->sub_nS = nS;
-    if (sub->schur) {
-        ctx->sub_nfin = (int)((nS + WAVE - 1) / WAVE);
-        HIP_TRY(ctx, ctx->sub_upart.alloc((size_t)ctx->sub_nfin));
-        TDGL_TRY(sub_schur_pinv(ctx, sub->schur, nS, "tdgl_poisson_set_substructure"));
-        ctx->sub_parts = sub->n_parts;
-    } else {
-        ctx->sub_parts = 0;
-        ctx->sub_outer_parts_pending = sub->n_parts;  // (remembered until the inner levels have arrived)
-        ctx->sub_wait_inner = true;
+    auto f = std::make_unique<DirectFactors>();
+    f->n_local = schur ? cur->n_local : 0;
+    TDGL_TRY(sub_upload_level(ctx, sub, schur ? cur->n_local : ctx->n, f->lv[0], "tdgl_poisson_set_substructure"));
+    f->levels = 1;
+    if (sub->schur) TDGL_TRY(sub_top(ctx, *f, sub->schur, sub->n_sep, "tdgl_poisson_set_substructure"));
+    f->stage = sub->schur ? f->settled() : DirectFactors::INNER_PENDING;
+    if (schur) {  // the interface and the work vectors of tdgl_poisson_schur_begin stay
+        f->ng = cur->ng;
+        f->ngo = cur->ngo;
+        f->owner_local = std::move(cur->owner_local);
+        f->go_local = std::move(cur->go_local);
+        f->go_gid = std::move(cur->go_gid);
+        f->GI = std::move(cur->GI);
+        f->IG = std::move(cur->IG);
+        f->map = std::move(cur->map);
+        for (auto b : {&DirectFactors::bp, &DirectFactors::xp, &DirectFactors::z, &DirectFactors::t, &DirectFactors::rg, &DirectFactors::xg,
+                       &DirectFactors::y, &DirectFactors::v, &DirectFactors::c})
+            (*f).*b = std::move((*cur).*b);
     }
+    ctx->direct = std::move(f);
     if (seconds) *seconds = (double)(now_ns() - t_begin) * 1e-9;
     return TDGL_OK;
 }
@@ -586,54 +565,55 @@ extern "C" int tdgl_poisson_set_substructure_coupling(tdgl_ctx *ctx, int32_t lev
                                                       const double *data) {
     CTX_GUARD(ctx);
     if (level < 0 || level > 2) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_coupling: level must be 0, 1 or 2");
-    const bool ready = level == 0 ? (ctx->sub_parts > 0 || ctx->sub_wait_inner) : ctx->sub_in[level - 1].parts > 0;
-    if (!ready) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_set_substructure_coupling: set that level's factors first");
-    Csr &M = level == 0 ? ctx->sub_coupling : ctx->sub_in[level - 1].coupling;
+    DirectFactors *f = ctx->direct.get();
+    if (!f || level >= f->levels || f->stage == DirectFactors::PRECOND)
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_set_substructure_coupling: set that level's factors first (and before they precondition the CG)");
+    SubLevel &L = f->lv[level];
     if (!indptr)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_coupling: the operator is required (a level described WITH its -E^T rows "
                   "needs no coupling block; one described without cannot do without)");
-    const int64_t rows = level == 0 ? ctx->sub_nS : ctx->sub_in[level - 1].nS, cols = level == 0 ? ctx->sub_nI : ctx->sub_in[level - 1].nI;
-    if (!indices || !data || indptr[0] != 0) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_coupling: inconsistent operator");
-    for (int64_t r = 0; r < rows; ++r)
-        if (indptr[r + 1] < indptr[r]) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_coupling: indptr must not decrease");
+    const int64_t rows = L.nS, cols = L.nI;
+    if (!offsets_ok(indptr, rows) || (indptr[rows] > 0 && (!indices || !data)))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_coupling: inconsistent operator");
     for (int64_t k = 0; k < indptr[rows]; ++k)
         if (indices[k] < 0 || indices[k] >= cols) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_coupling: column out of range");
     // the separator rows of that level's way down must then be their identity segment alone
+    Csr M;
     TDGL_TRY(upload_csr(ctx, rows, cols, indptr, indices, data, M));
-    ctx->sub_need_coupling[level] = false;
+    L.coupling = std::move(M);
+    L.need_coupling = false;
+    if (f->stage == DirectFactors::COUPLING_PENDING) f->stage = f->settled();
     return TDGL_OK;
 }
 
 extern "C" int tdgl_poisson_set_substructure_inner(tdgl_ctx *ctx, const tdgl_substructure *sub, double *seconds) {
     CTX_GUARD(ctx);
     if (!sub) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_inner: a description is required");
-    if (!ctx->sub_wait_inner)
+    DirectFactors *f = ctx->direct.get();
+    if (!f || f->stage != DirectFactors::INNER_PENDING)
         TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_set_substructure_inner: set the first level without a Schur complement first");
-    const int k = ctx->sub_n_inner;  // this call describes inner level k (the second level of the solve is k = 0)
-    if (k >= 2 || (k == 1 && !sub->schur))
+    const int k = f->levels;  // this call describes level k (the second level of the solve is k = 1)
+    if (k >= 3 || (k == 2 && !sub->schur))
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_inner: at most two inner levels, and the last one carries the Schur complement");
     if (sub->schur && sub->n_sep > 46000)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_inner: a top separator of %lld sites is outside what a dense matrix is meant for",
                   (long long)sub->n_sep);
     const int64_t t_begin = now_ns();
-    auto &I = ctx->sub_in[k];
-    const int64_t n_vec = k == 0 ? ctx->sub_nS : ctx->sub_in[k - 1].nS;  // the level works on the previous level's separator vector
-    TDGL_TRY(sub_upload_level(ctx, sub, n_vec,
-                              SubLevelDst{I.part_ptr, I.seg_ptr, I.seg_x, I.seg_len, I.sep_ptr, I.sep_idx, I.row_part, I.seg_val, I.e_off,
-                                          I.g_off, I.vals, I.e, I.u, I.w, I.chunks, I.down_chunks, I.down_rows, &ctx->sub_need_coupling[k + 1], &ctx->sub_ident[k + 1]},
-                              "tdgl_poisson_set_substructure_inner"));
-    I.nI = sub->n_interior;
-    I.nS = sub->n_sep;
-    HIP_TRY(ctx, I.xt.alloc((size_t)I.nS));
-    I.parts = sub->n_parts;
-    ctx->sub_n_inner = k + 1;
+    // built aside: the level (the previous level's separator vector is its vector) and, with the Schur complement, the top
+    SubLevel L;
+    TDGL_TRY(sub_upload_level(ctx, sub, f->lv[k - 1].nS, L, "tdgl_poisson_set_substructure_inner"));
+    DirectFactors top;
+    top.levels = k + 1;
+    top.n_local = f->n_local;
+    if (sub->schur) TDGL_TRY(sub_top(ctx, top, sub->schur, L.nS, "tdgl_poisson_set_substructure_inner"));
+    f->lv[k] = std::move(L);
+    f->levels = k + 1;
     if (sub->schur) {  // the last level: the dense top separator, and the solve is complete
-        HIP_TRY(ctx, ctx->sub_mean.alloc(1));
-        ctx->sub_nfin = (int)((I.nS + WAVE - 1) / WAVE);
-        HIP_TRY(ctx, ctx->sub_upart.alloc((size_t)ctx->sub_nfin));
-        TDGL_TRY(sub_schur_pinv(ctx, sub->schur, I.nS, "tdgl_poisson_set_substructure_inner"));
-        ctx->sub_parts = ctx->sub_outer_parts_pending;
-        ctx->sub_wait_inner = false;
+        f->dense = std::move(top.dense);
+        f->nfin = top.nfin;
+        f->upart = std::move(top.upart);
+        f->mean = std::move(top.mean);
+        f->stage = f->settled();
     }
     if (seconds) *seconds = (double)(now_ns() - t_begin) * 1e-9;
     return TDGL_OK;
@@ -648,26 +628,15 @@ static bool env_force_sym() {  // TDGL_PD_SYM=2: symmetric tiles also on levels 
     return env && env[0] == '2';
 }
 
-struct SubLevelRefs {
-    int P;
-    int64_t nI, n_vec;  // interior rows, length of the level's vector (n_rows of the way down = n_vec + P)
-    DevBuf<int32_t> &part_ptr, &sep_ptr, &seg_ptr;
-    DevBuf<int64_t> &g_off, &seg_val;
-    DevBuf<double> &vals;
-    DevBuf<float> &vals32;
-    DevBuf<SubDownChunk> &down_chunks;
-    DevBuf<SubUpChunk> &up_chunks;
-    int *sym_lds;  // out: rows of b_p the symmetric way down stages (0: the level keeps whole blocks)
-    int *up_R;     // out: chunks of 64 rows per workgroup of the way up (> 1: a whole part each, on the levels stored as tiles)
-};
-
 // fp64_tiles: the direct SOLVE's form (tdgl_poisson_set_substructure_layout) -- a level that qualifies for symmetric tiles
 // is repacked into a new fp64 pool (tiles, padded -E^T rows) and gets the tile kernel's work list; any other level is left
 // exactly as it was uploaded (k_sub_down / k_sub_up on the original pool).
-static int sub_level_to_precond(tdgl_ctx *ctx, SubLevelRefs L, bool fp32_storage, bool allow_sym, const char *who, bool fp64_tiles = false) {
-    const int P = L.P;
-    *L.sym_lds = 0;
-    *L.up_R = 1;
+// Sets L.sym_lds (rows of b_p the symmetric way down stages, 0: the level keeps whole blocks) and L.up_R (chunks of 64
+// rows per workgroup of the way up, > 1: a whole part each on the levels stored as tiles).
+static int sub_level_to_precond(tdgl_ctx *ctx, SubLevel &L, bool fp32_storage, bool allow_sym, const char *who, bool fp64_tiles = false) {
+    const int P = L.parts;
+    L.sym_lds = 0;
+    L.up_R = 1;
     std::vector<int32_t> pp((size_t)P + 1), sp((size_t)P + 1);
     std::vector<int64_t> go((size_t)P);
     HIP_TRY(ctx, hipMemcpy(pp.data(), L.part_ptr.p, pp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -730,7 +699,7 @@ static int sub_level_to_precond(tdgl_ctx *ctx, SubLevelRefs L, bool fp32_storage
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         // the segment lists (the rows the lane form leaves to a wavefront each: (G_p 1)^T, separator rows with -E^T segments)
-        const int64_t n_rows = L.n_vec + P;
+        const int64_t n_rows = L.nI + L.nS + P;
         std::vector<int32_t> segp((size_t)n_rows + 1);
         HIP_TRY(ctx, hipMemcpy(segp.data(), L.seg_ptr.p, segp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
         std::vector<int64_t> sv((size_t)segp[n_rows]);
@@ -800,36 +769,28 @@ static int sub_level_to_precond(tdgl_ctx *ctx, SubLevelRefs L, bool fp32_storage
     if (up.empty()) up.push_back(SubUpChunk{0, 0, 0, 0, 0, 0});
     HIP_TRY(ctx, L.down_chunks.upload(ch));
     HIP_TRY(ctx, L.up_chunks.upload(up));
-    if (sym) *L.sym_lds = (int)round_up(np_max, ST);
-    *L.up_R = up_parts ? (np_max + WAVE - 1) / WAVE : 1;
+    if (sym) L.sym_lds = (int)round_up(np_max, ST);
+    L.up_R = up_parts ? (np_max + WAVE - 1) / WAVE : 1;
     return TDGL_OK;
 }
 
+// The resident factors, READY and not laid out for the direct solve (checked by the callers), become the preconditioner's:
+// lane-per-row work lists, fp32 storage if asked.  The levels are converted in place: if that fails part way, the factors
+// are released (the CG goes on with the AMG V-cycle alone).
 static int sub_factors_to_precond(tdgl_ctx *ctx, bool fp32_storage, const char *who) {
-    const bool convert = fp32_storage && !ctx->sub_fp32;
-    if (!ctx->sub_fp32 && (ctx->sub_sym_lds[0] > 0 || ctx->sub_sym_lds[1] > 0 || ctx->sub_sym_lds[2] > 0))
-        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "%s: the fp64 pools were laid out for the direct solve (tdgl_poisson_set_substructure_layout); describe the factors again", who);
+    DirectFactors &f = *ctx->direct;
     // (TDGL_PD_SYM=0: whole G blocks on every level, the form of the earlier rounds -- for A/B measurements)
     const char *env = getenv("TDGL_PD_SYM");
     const bool allow_sym = !(env && env[0] == '0');
-    TDGL_TRY(sub_level_to_precond(ctx, SubLevelRefs{ctx->sub_parts, ctx->sub_nI, ctx->sub_nI + ctx->sub_nS, ctx->sub_part_ptr, ctx->sub_sep_ptr,
-                                                    ctx->sub_seg_ptr, ctx->sub_g_off, ctx->sub_seg_val, ctx->sub_vals, ctx->sub_vals32,
-                                                    ctx->sub_down_chunks, ctx->sub_chunks, &ctx->sub_sym_lds[0], &ctx->sub_up_R[0]}, convert, allow_sym, who));
-    for (int k = 0; k < ctx->sub_n_inner; ++k) {
-        auto &I = ctx->sub_in[k];
-        TDGL_TRY(sub_level_to_precond(ctx, SubLevelRefs{I.parts, I.nI, I.nI + I.nS, I.part_ptr, I.sep_ptr, I.seg_ptr, I.g_off, I.seg_val, I.vals,
-                                                        I.vals32, I.down_chunks, I.chunks, &ctx->sub_sym_lds[k + 1], &ctx->sub_up_R[k + 1]}, convert, allow_sym, who));
+    int rc = TDGL_OK;
+    for (int k = 0; k < f.levels && rc == TDGL_OK; ++k) rc = sub_level_to_precond(ctx, f.lv[k], fp32_storage, allow_sym, who);
+    if (rc == TDGL_OK && fp32_storage) rc = dense_to_fp32(ctx, f.dense);
+    if (rc != TDGL_OK) {
+        ctx->direct.reset();
+        return rc;
     }
-    if (convert) {
-        HIP_TRY(ctx, ctx->denseG32.alloc(std::max<size_t>(ctx->denseG.n, 1), false));
-        if (ctx->denseG.n > 0)
-            hipLaunchKernelGGL(k_to_float, dim3(vec_grid((int64_t)ctx->denseG.n)), dim3(BLOCK), 0, ctx->stream, (int64_t)ctx->denseG.n,
-                               (const double *)ctx->denseG.p, ctx->denseG32.p);
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->denseG.release();
-        ctx->sub_fp32 = true;
-    }
-    ctx->sub_lanes = true;
+    f.fp32 = fp32_storage;
+    f.stage = DirectFactors::PRECOND;
     return TDGL_OK;
 }
 
@@ -859,7 +820,7 @@ static int precond_calibrate(tdgl_ctx *ctx, double *t_apply_us, double *t_vcycle
         *out = t[t.size() / 2];
         return TDGL_OK;
     };
-    TDGL_TRY(median_us([&]() -> int { return precond_factors_apply(ctx, ctx->pcg_r.p, ctx->sub_z.p, ctx->part_pair[0].p); }, &ctx->pd_t_apply_us));
+    TDGL_TRY(median_us([&]() -> int { return precond_factors_apply(ctx, ctx->pcg_r.p, ctx->direct->z.p, ctx->part_pair[0].p); }, &ctx->pd_t_apply_us));
     TDGL_TRY(median_us(
         [&]() -> int {
             if (precond_f32_on(ctx) && ctx->deep) {
@@ -880,33 +841,47 @@ static int precond_calibrate(tdgl_ctx *ctx, double *t_apply_us, double *t_vcycle
     return TDGL_OK;
 }
 
+// factors laid out for the fp64 direct solve (tdgl_poisson_set_substructure_layout) cannot be converted
+static bool sub_laid_out(const DirectFactors &f) {
+    for (int k = 0; k < f.levels; ++k)
+        if (f.lv[k].sym_lds > 0) return true;
+    return false;
+}
+
 // The resident substructure factors become the CG's PRECONDITIONER instead of the solver (include/tdgl_hip.h).
 extern "C" int tdgl_poisson_set_substructure_precond(tdgl_ctx *ctx, const int32_t *site_map, int32_t fp32_storage, double *t_apply_us,
                                                      double *t_vcycle_us) {
     CTX_GUARD(ctx);
-    if (!site_map) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_precond: the site map is required");
-    if (ctx->sub_parts <= 0 || ctx->sub_wait_inner || ctx->sub_need_coupling[0] || ctx->sub_need_coupling[1] || ctx->sub_need_coupling[2])
-        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_set_substructure_precond: describe the factors first (every level, every coupling block)");
-    if (distributed(ctx) || ctx->levels.empty() || ctx->sub_n_local > 0)
-        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_set_substructure_precond: single-GPU contexts with a hierarchy only "
-                  "(one process per GPU: tdgl_poisson_schur_begin / _finish)");
+    const char *who = "tdgl_poisson_set_substructure_precond";
+    if (!site_map) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: the site map is required", who);
+    DirectFactors *f = ctx->direct.get();
+    if (!f || f->levels == 0 || f->stage != DirectFactors::READY)
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "%s: describe the factors first (every level, every coupling block); once converted, describe them again", who);
+    if (distributed(ctx) || ctx->levels.empty() || f->n_local > 0)
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "%s: single-GPU contexts with a hierarchy only (one process per GPU: tdgl_poisson_schur_begin / _finish)", who);
+    if (sub_laid_out(*f))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "%s: the fp64 pools were laid out for the direct solve (tdgl_poisson_set_substructure_layout); describe the factors again", who);
     const int64_t n = ctx->n;
-    {  // dissection position -> the caller's site -> the context's index; must be a permutation
-        std::vector<int32_t> map(n);
-        std::vector<char> seen(n, 0);
-        for (int64_t i = 0; i < n; ++i) {
-            const int32_t s = site_map[i];
-            if (s < 0 || s >= n || seen[s]) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_precond: site_map is not a permutation of the sites");
-            seen[s] = 1;
-            map[i] = ctx->iperm[s];
-        }
-        HIP_TRY(ctx, ctx->sub_map.upload(map));
+    // dissection position -> the caller's site -> the context's index; must be a permutation
+    std::vector<int32_t> map(n);
+    std::vector<char> seen(n, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t s = site_map[i];
+        if (s < 0 || s >= n || seen[s]) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: site_map is not a permutation of the sites", who);
+        seen[s] = 1;
+        map[i] = ctx->iperm[s];
     }
-    HIP_TRY(ctx, ctx->sub_bp.alloc((size_t)n));
-    HIP_TRY(ctx, ctx->sub_xp.alloc((size_t)n));
-    HIP_TRY(ctx, ctx->sub_z.alloc((size_t)ctx->n_pad));
-    TDGL_TRY(sub_factors_to_precond(ctx, fp32_storage != 0, "tdgl_poisson_set_substructure_precond"));
-    ctx->sub_precond = true;
+    DevBuf<int32_t> d_map;
+    DevBuf<double> bp, xp, z;
+    HIP_TRY(ctx, d_map.upload(map));
+    HIP_TRY(ctx, bp.alloc((size_t)n));
+    HIP_TRY(ctx, xp.alloc((size_t)n));
+    HIP_TRY(ctx, z.alloc((size_t)ctx->n_pad));
+    f->map = std::move(d_map);
+    f->bp = std::move(bp);
+    f->xp = std::move(xp);
+    f->z = std::move(z);
+    TDGL_TRY(sub_factors_to_precond(ctx, fp32_storage != 0, who));
     ctx->direct_switch_on = false;
     ctx->direct_paused = false;
     ctx->pcg_epoch += 1;
@@ -940,29 +915,30 @@ extern "C" int tdgl_get_precond_direct_stats(tdgl_ctx *ctx, int64_t *out4, doubl
 
 extern "C" int tdgl_get_precond_direct_layout(tdgl_ctx *ctx, int32_t *sym_rows3) {
     if (!ctx || !sym_rows3) return TDGL_ERR_ARG;
-    for (int k = 0; k < 3; ++k) sym_rows3[k] = ctx->sub_sym_lds[k];
+    for (int k = 0; k < 3; ++k) sym_rows3[k] = ctx->direct ? ctx->direct->lv[k].sym_lds : 0;
     return TDGL_OK;
 }
 
 // The direct SOLVE (fp64 factors, run-ahead loop): levels of many small parts keep only the tiles on or below the diagonal
-// of their symmetric G blocks and run the tile kernel on the way down; everything else stays as uploaded.
+// of their symmetric G blocks and run the tile kernel on the way down; everything else stays as uploaded.  The levels are
+// repacked in place: if that fails part way, the factors are released (AMG-PCG).
 extern "C" int tdgl_poisson_set_substructure_layout(tdgl_ctx *ctx, int32_t symmetric_tiles) {
     CTX_GUARD(ctx);
-    if (ctx->sub_parts <= 0) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_set_substructure_layout: describe the factors first (every level)");
-    if (ctx->sub_precond || ctx->sub_fp32 || ctx->sub_lanes)
-        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_substructure_layout: the factors already precondition the CG (their layout is set there)");
+    const char *who = "tdgl_poisson_set_substructure_layout";
+    DirectFactors *f = ctx->direct.get();
+    if (!f || f->levels == 0 || f->stage < DirectFactors::COUPLING_PENDING)
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "%s: describe the factors first (every level)", who);
+    if (f->stage == DirectFactors::PRECOND)
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: the factors already precondition the CG (their layout is set there)", who);
     const char *env = getenv("TDGL_PD_SYM");
     if (!symmetric_tiles || (env && env[0] == '0')) return TDGL_OK;
-    const char *who = "tdgl_poisson_set_substructure_layout";
-    if (ctx->sub_sym_lds[0] == 0)
-        TDGL_TRY(sub_level_to_precond(ctx, SubLevelRefs{ctx->sub_parts, ctx->sub_nI, ctx->sub_nI + ctx->sub_nS, ctx->sub_part_ptr, ctx->sub_sep_ptr,
-                                                        ctx->sub_seg_ptr, ctx->sub_g_off, ctx->sub_seg_val, ctx->sub_vals, ctx->sub_vals32,
-                                                        ctx->sub_down_chunks, ctx->sub_chunks, &ctx->sub_sym_lds[0], &ctx->sub_up_R[0]}, false, true, who, true));
-    for (int k = 0; k < ctx->sub_n_inner; ++k) {
-        auto &I = ctx->sub_in[k];
-        if (ctx->sub_sym_lds[k + 1] == 0)
-            TDGL_TRY(sub_level_to_precond(ctx, SubLevelRefs{I.parts, I.nI, I.nI + I.nS, I.part_ptr, I.sep_ptr, I.seg_ptr, I.g_off, I.seg_val, I.vals,
-                                                            I.vals32, I.down_chunks, I.chunks, &ctx->sub_sym_lds[k + 1], &ctx->sub_up_R[k + 1]}, false, true, who, true));
+    for (int k = 0; k < f->levels; ++k) {
+        if (f->lv[k].sym_lds > 0) continue;
+        const int rc = sub_level_to_precond(ctx, f->lv[k], false, true, who, true);
+        if (rc != TDGL_OK) {
+            ctx->direct.reset();
+            return rc;
+        }
     }
     return TDGL_OK;
 }
@@ -1106,7 +1082,11 @@ extern "C" int tdgl_poisson_build_substructure(tdgl_ctx *ctx, const tdgl_substru
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_build_substructure: inconsistent plan (n_interior + n_sep must be the site count)");
     if (pl->part_ptr[0] != 0 || pl->part_ptr[P] != nI) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_build_substructure: part_ptr must run from 0 to n_interior");
     const int64_t t_begin = now_ns();
-    const int64_t n_rows = n + P, n_seg = pl->seg_ptr[n_rows], Q = pl->sep_ptr[P], n_ent = pl->ent_ptr[Q];
+    const int64_t n_rows = n + P;
+    if (!offsets_ok(pl->seg_ptr, n_rows) || !offsets_ok(pl->sep_ptr, P) || !offsets_ok(pl->ent_ptr, pl->sep_ptr[P]) ||
+        !offsets_ok(pl->node_ptr, nS) || !offsets_ok(pl->ass_indptr, nS))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_build_substructure: an offset array does not run from 0 or decreases");
+    const int64_t n_seg = pl->seg_ptr[n_rows], Q = pl->sep_ptr[P], n_ent = pl->ent_ptr[Q];
     if (pl->node_ptr[nS] != Q) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_build_substructure: node_ptr must cover every pair");
     // host-side index checks and derived tables
     std::vector<int32_t> row_part(nI), pair_part(Q), nbq(P);
@@ -1161,39 +1141,41 @@ extern "C" int tdgl_poisson_build_substructure(tdgl_ctx *ctx, const tdgl_substru
         }
     s /= (double)nS;
     if (!(s > 0.0) || !std::isfinite(s)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_build_substructure: A_SS has a non-positive mean diagonal");
-    dense_release(ctx);
+    // built aside, moved in once complete
+    auto f = std::make_unique<DirectFactors>();
+    SubLevel &L = f->lv[0];
     // index arrays of the solve
-    HIP_TRY(ctx, ctx->sub_part_ptr.upload(std::vector<int32_t>(pl->part_ptr, pl->part_ptr + P + 1)));
-    HIP_TRY(ctx, ctx->sub_seg_ptr.upload(std::vector<int32_t>(pl->seg_ptr, pl->seg_ptr + n_rows + 1)));
-    HIP_TRY(ctx, ctx->sub_seg_val.upload(std::vector<int64_t>(pl->seg_val, pl->seg_val + n_seg)));
-    HIP_TRY(ctx, ctx->sub_seg_x.upload(std::vector<int32_t>(pl->seg_x, pl->seg_x + n_seg)));
-    HIP_TRY(ctx, ctx->sub_seg_len.upload(std::vector<int32_t>(pl->seg_len, pl->seg_len + n_seg)));
-    HIP_TRY(ctx, ctx->sub_sep_ptr.upload(std::vector<int32_t>(pl->sep_ptr, pl->sep_ptr + P + 1)));
-    HIP_TRY(ctx, ctx->sub_sep_idx.upload(std::vector<int32_t>(pl->sep_idx, pl->sep_idx + Q)));
-    HIP_TRY(ctx, ctx->sub_e_off.upload(std::vector<int64_t>(pl->e_off, pl->e_off + P)));
-    HIP_TRY(ctx, ctx->sub_row_part.upload(row_part));
-    TDGL_TRY(sub_upload_chunks(ctx, P, pl->part_ptr, pl->sep_ptr, pl->et_off, ctx->sub_chunks, "tdgl_poisson_build_substructure"));
+    HIP_TRY(ctx, L.part_ptr.upload(std::vector<int32_t>(pl->part_ptr, pl->part_ptr + P + 1)));
+    HIP_TRY(ctx, L.seg_ptr.upload(std::vector<int32_t>(pl->seg_ptr, pl->seg_ptr + n_rows + 1)));
+    HIP_TRY(ctx, L.seg_val.upload(std::vector<int64_t>(pl->seg_val, pl->seg_val + n_seg)));
+    HIP_TRY(ctx, L.seg_x.upload(std::vector<int32_t>(pl->seg_x, pl->seg_x + n_seg)));
+    HIP_TRY(ctx, L.seg_len.upload(std::vector<int32_t>(pl->seg_len, pl->seg_len + n_seg)));
+    HIP_TRY(ctx, L.sep_ptr.upload(std::vector<int32_t>(pl->sep_ptr, pl->sep_ptr + P + 1)));
+    HIP_TRY(ctx, L.sep_idx.upload(std::vector<int32_t>(pl->sep_idx, pl->sep_idx + Q)));
+    HIP_TRY(ctx, L.row_part.upload(row_part));
+    TDGL_TRY(sub_upload_chunks(ctx, P, pl->part_ptr, pl->sep_ptr, pl->et_off, L.up_chunks, "tdgl_poisson_build_substructure"));
     TDGL_TRY(sub_upload_down_lists(ctx, P, n_rows, pl->part_ptr, pl->g_off, pl->seg_ptr, pl->seg_val, pl->seg_x, pl->seg_len,
-                                   ctx->sub_down_chunks, ctx->sub_down_rows));
-    HIP_TRY(ctx, ctx->sub_vals.alloc((size_t)pl->n_vals, false));
-    HIP_TRY(ctx, ctx->sub_e.alloc((size_t)std::max<int64_t>(pl->n_e, 1), false));
-    HIP_TRY(ctx, ctx->sub_u.alloc((size_t)nS));
-    HIP_TRY(ctx, ctx->sub_w.alloc((size_t)n_rows));
-    HIP_TRY(ctx, ctx->sub_xs.alloc((size_t)nS));
-    ctx->sub_nfin = (int)((nS + WAVE - 1) / WAVE);
-    HIP_TRY(ctx, ctx->sub_upart.alloc((size_t)ctx->sub_nfin));
+                                   L.down_chunks, L.down_rows));
+    HIP_TRY(ctx, L.vals.alloc((size_t)pl->n_vals, false));
+    HIP_TRY(ctx, L.u.alloc((size_t)nS));
+    HIP_TRY(ctx, L.w.alloc((size_t)n_rows));
+    HIP_TRY(ctx, L.xs.alloc((size_t)nS));
+    f->nfin = (int)((nS + WAVE - 1) / WAVE);
+    HIP_TRY(ctx, f->upart.alloc((size_t)f->nfin));
     // set-up-only tables
     DevBuf<int32_t> d_pair_part, d_nbq, d_ent_ptr, d_ent_row, d_node_ptr, d_node_pair, d_ass_p, d_ass_i, d_flag;
-    DevBuf<int64_t> d_moff, d_poff, d_coff, d_goff, d_etoff;
-    DevBuf<double> d_ent_val, d_ass_v, Mp, Pb, Wb, Db, Cpool, colsum;
+    DevBuf<int64_t> d_moff, d_poff, d_coff, d_goff, d_etoff, d_eoff;
+    DevBuf<double> d_ent_val, d_ass_v, Mp, Pb, Wb, Db, Cpool, colsum, E;  // (E: the row-major E_p blocks, which only the build reads)
     HIP_TRY(ctx, d_pair_part.upload(pair_part));
     HIP_TRY(ctx, d_nbq.upload(nbq));
     HIP_TRY(ctx, d_moff.upload(moff));
     HIP_TRY(ctx, d_poff.upload(poff));
     HIP_TRY(ctx, d_coff.upload(c_off));
     HIP_TRY(ctx, d_goff.upload(std::vector<int64_t>(pl->g_off, pl->g_off + P)));
-    HIP_TRY(ctx, ctx->sub_g_off.upload(std::vector<int64_t>(pl->g_off, pl->g_off + P)));
+    HIP_TRY(ctx, L.g_off.upload(std::vector<int64_t>(pl->g_off, pl->g_off + P)));
     HIP_TRY(ctx, d_etoff.upload(std::vector<int64_t>(pl->et_off, pl->et_off + P)));
+    HIP_TRY(ctx, d_eoff.upload(std::vector<int64_t>(pl->e_off, pl->e_off + P)));
+    HIP_TRY(ctx, E.alloc((size_t)std::max<int64_t>(pl->n_e, 1), false));
     HIP_TRY(ctx, d_ent_ptr.upload(std::vector<int32_t>(pl->ent_ptr, pl->ent_ptr + Q + 1)));
     HIP_TRY(ctx, d_ent_row.upload(std::vector<int32_t>(pl->ent_row, pl->ent_row + n_ent)));
     HIP_TRY(ctx, d_ent_val.upload(std::vector<double>(pl->ent_val, pl->ent_val + n_ent)));
@@ -1212,12 +1194,12 @@ extern "C" int tdgl_poisson_build_substructure(tdgl_ctx *ctx, const tdgl_substru
     // 1. interior blocks, inverted all at once
     const int64_t Nmax = (int64_t)max_nb * GB;
     hipLaunchKernelGGL(k_sub_blocks_init, dim3((unsigned)grid_for(Nmax * Nmax), (unsigned)P), dim3(BLOCK), 0, ctx->stream,
-                       (const int32_t *)d_nbq.p, (const int64_t *)d_moff.p, (const int32_t *)ctx->sub_part_ptr.p, Mp.p);
+                       (const int32_t *)d_nbq.p, (const int64_t *)d_moff.p, (const int32_t *)L.part_ptr.p, Mp.p);
     AmgLevel &L0 = *ctx->levels[0];
     const SellPattern &pat = L0.A.pat;
     hipLaunchKernelGGL(k_sub_blocks_scatter, dim3(grid_for((int64_t)pat.n_slices * WAVE)), dim3(BLOCK), 0, ctx->stream, pat.n_slices, nI,
                        (const int32_t *)pat.slice_off.p, (const int32_t *)pat.cols.p, (const double *)L0.A.vals.p,
-                       (const int32_t *)ctx->sub_row_part.p, (const int32_t *)ctx->sub_part_ptr.p, (const int32_t *)d_nbq.p,
+                       (const int32_t *)L.row_part.p, (const int32_t *)L.part_ptr.p, (const int32_t *)d_nbq.p,
                        (const int64_t *)d_moff.p, Mp.p);
     for (int k = 0; k < max_nb; ++k) {
         hipLaunchKernelGGL(k_gj_panel_batch, dim3((unsigned)max_nb, (unsigned)P), dim3(BLOCK), 0, ctx->stream, k, (const int32_t *)d_nbq.p,
@@ -1228,18 +1210,18 @@ extern "C" int tdgl_poisson_build_substructure(tdgl_ctx *ctx, const tdgl_substru
     }
     // 2. value pool: 1.0, G_p rows and row sums; E_p, -E_p^T, column sums; C_p
     const double one = 1.0;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->sub_vals.p, &one, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(L.vals.p, &one, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_sub_unpack_G, dim3((unsigned)((nI + BLOCK / WAVE - 1) / (BLOCK / WAVE))), dim3(BLOCK), 0, ctx->stream, nI,
-                       (const int32_t *)ctx->sub_row_part.p, (const int32_t *)ctx->sub_part_ptr.p, (const int32_t *)d_nbq.p,
-                       (const int64_t *)d_moff.p, (const double *)Mp.p, (const int64_t *)d_goff.p, pl->gvec_off, ctx->sub_vals.p);
+                       (const int32_t *)L.row_part.p, (const int32_t *)L.part_ptr.p, (const int32_t *)d_nbq.p,
+                       (const int64_t *)d_moff.p, (const double *)Mp.p, (const int64_t *)d_goff.p, pl->gvec_off, L.vals.p);
     hipLaunchKernelGGL(k_sub_E, dim3((unsigned)Q), dim3(BLOCK), 0, ctx->stream, (const int32_t *)d_pair_part.p,
-                       (const int32_t *)ctx->sub_part_ptr.p, (const int32_t *)ctx->sub_sep_ptr.p, (const int32_t *)d_ent_ptr.p,
+                       (const int32_t *)L.part_ptr.p, (const int32_t *)L.sep_ptr.p, (const int32_t *)d_ent_ptr.p,
                        (const int32_t *)d_ent_row.p, (const double *)d_ent_val.p, (const int64_t *)d_goff.p, (const int64_t *)d_etoff.p,
-                       (const int64_t *)ctx->sub_e_off.p, ctx->sub_vals.p, ctx->sub_e.p, colsum.p);
+                       (const int64_t *)d_eoff.p, L.vals.p, E.p, colsum.p);
     hipLaunchKernelGGL(k_sub_C, dim3((unsigned)Q), dim3(BLOCK), 0, ctx->stream, (const int32_t *)d_pair_part.p,
-                       (const int32_t *)ctx->sub_part_ptr.p, (const int32_t *)ctx->sub_sep_ptr.p, (const int32_t *)d_ent_ptr.p,
-                       (const int32_t *)d_ent_row.p, (const double *)d_ent_val.p, (const int64_t *)ctx->sub_e_off.p,
-                       (const double *)ctx->sub_e.p, (const int64_t *)d_coff.p, Cpool.p);
+                       (const int32_t *)L.part_ptr.p, (const int32_t *)L.sep_ptr.p, (const int32_t *)d_ent_ptr.p,
+                       (const int32_t *)d_ent_row.p, (const double *)d_ent_val.p, (const int64_t *)d_eoff.p,
+                       (const double *)E.p, (const int64_t *)d_coff.p, Cpool.p);
     // 3. Schur complement (+ shift) assembled into the padded matrix, u; pseudo-inverse by the sweep
     {
         const int64_t N = round_up(nS, GB);
@@ -1248,19 +1230,20 @@ extern "C" int tdgl_poisson_build_substructure(tdgl_ctx *ctx, const tdgl_substru
         hipLaunchKernelGGL(k_sub_schur_row, dim3((unsigned)N), dim3(BLOCK), 0, ctx->stream, nS, N, s / (double)nS,
                            (const int32_t *)d_ass_p.p, (const int32_t *)d_ass_i.p, (const double *)d_ass_v.p,
                            (const int32_t *)d_node_ptr.p, (const int32_t *)d_node_pair.p, (const int32_t *)d_pair_part.p,
-                           (const int32_t *)ctx->sub_sep_ptr.p, (const int32_t *)ctx->sub_sep_idx.p, (const int64_t *)d_coff.p,
-                           (const double *)Cpool.p, (const double *)colsum.p, M.p, ctx->sub_u.p);
+                           (const int32_t *)L.sep_ptr.p, (const int32_t *)L.sep_idx.p, (const int64_t *)d_coff.p,
+                           (const double *)Cpool.p, (const double *)colsum.p, M.p, L.u.p);
         HIP_TRY(ctx, hipGetLastError());
         int32_t flag = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&flag, d_flag.p, sizeof(flag), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (flag) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_build_substructure: an interior block is not positive definite");
-        TDGL_TRY(dense_sweep_pack(ctx, M, nS, N, 1.0 / (s * (double)nS)));
+        TDGL_TRY(dense_sweep_pack(ctx, M, nS, N, 1.0 / (s * (double)nS), f->dense));
     }
-    ctx->sub_e.release();  // (only the build needed the row-major E_p blocks: the way up reads the pool's -E_p^T)
-    ctx->sub_parts = P;
-    ctx->sub_nI = nI;
-    ctx->sub_nS = nS;
+    L.parts = P;
+    L.nI = nI;
+    L.nS = nS;
+    f->levels = 1;
+    ctx->direct = std::move(f);
     if (seconds) *seconds = (double)(now_ns() - t_begin) * 1e-9;
     return TDGL_OK;
 }

@@ -248,7 +248,7 @@ extern "C" int tdgl_ensemble_create(tdgl_ensemble **out, tdgl_ctx *ctx, int32_t 
     if (distributed(ctx)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_create: single-GPU contexts only");
     if (n_replicas < 1 || n_replicas > TDGL_ENSEMBLE_MAX_REPLICAS)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_create: n_replicas must be in [1, %d] (got %d)", TDGL_ENSEMBLE_MAX_REPLICAS, n_replicas);
-    if (!(ctx->dense_tiles > 0 && ctx->dense_ld > 0 && ctx->sub_parts == 0 && !ctx->sub_fp32 && ctx->dense_n == ctx->n))
+    if (!(ctx->direct && ctx->direct->ld > 0 && ctx->direct->dense.n == ctx->n))
         TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_create: the context has no dense inverse (tdgl_poisson_build_dense_inverse)");
     if (ctx->scr_enabled) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_create: screening is not supported");
     std::unique_ptr<tdgl_ensemble> e(new tdgl_ensemble());
@@ -258,7 +258,7 @@ extern "C" int tdgl_ensemble_create(tdgl_ensemble **out, tdgl_ctx *ctx, int32_t 
     e->n_pad = ctx->n_pad;
     e->m_pad = ctx->m_pad;
     e->n_slots = ctx->lap_pat.n_slots;
-    e->nt = ctx->dense_tiles;
+    e->nt = ctx->direct->dense.tiles;
     e->ldpart = (int64_t)e->nt * e->nt * DT;
     const size_t R = (size_t)n_replicas;
     HIP_TRY(ctx, e->U.alloc(R * e->m_pad));
@@ -450,7 +450,7 @@ static void ens_queue_round(tdgl_ensemble *e) {
 #undef TDGL_KENS
     const int nt = e->nt;
     hipLaunchKernelGGL(k_ens_dense_tiles, dim3(nt * (nt + 1) / 2, (R + ENS_RG - 1) / ENS_RG), dim3(BLOCK), 0, ctx->stream, (int)e->n, nt,
-                       (const double *)ctx->denseG.p, (const double *)e->bvec.p, e->n_pad, e->part.p, e->ldpart, (int)R,
+                       (const double *)ctx->direct->dense.G.p, (const double *)e->bvec.p, e->n_pad, e->part.p, e->ldpart, (int)R,
                        (const StepCtl *)e->d_ctl.p);
     hipLaunchKernelGGL(k_ens_finish, dim3((unsigned)((e->n + WAVE - 1) / WAVE), R), dim3(BLOCK), 0, ctx->stream, (int)e->n, nt,
                        (const double *)e->part.p, e->ldpart, (const double *)e->dmax_part.p, (const int32_t *)e->fail_part.p,
@@ -474,6 +474,8 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
     CTX_GUARD(ctx);
     if (!max_steps || !end_time || capacity < 0 || !out_dt || !steps_done || !reached_end)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_run: bad arguments");
+    if (!(ctx->direct && ctx->direct->ld > 0 && ctx->direct->dense.tiles == e->nt))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_run: the context's dense inverse has been released");
     const int R = e->R, np_ = e->np_;
     for (int r = 0; r < R; ++r) {
         const EnsReplica &p = e->rep[r];

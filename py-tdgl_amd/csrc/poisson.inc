@@ -65,8 +65,6 @@ extern "C" int tdgl_get_guess_gram(tdgl_ctx *ctx, int32_t *k, double *G_rowmajor
     return TDGL_OK;
 }
 
-static void dense_release(tdgl_ctx *ctx);  // dense.inc
-static void schur_release(tdgl_ctx *ctx);  // schur.inc
 static int precond_schur_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part);  // schur.inc
 
 static int csr_to_sell(tdgl_ctx *ctx, int64_t n_rows, const int32_t *indptr, const int32_t *indices,
@@ -109,7 +107,7 @@ extern "C" int tdgl_poisson_set_hierarchy(tdgl_ctx *ctx, const tdgl_amg_level *l
     ctx->f32_ready = false;
     ctx->coarse32_ready = false;
     ctx->pcg_epoch += 1;
-    dense_release(ctx);  // the explicit inverses belong to the previous operator
+    ctx->direct.reset();  // the explicit inverses belong to the previous operator
     for (int k = 0; k < n_levels; ++k) {
         const tdgl_amg_level &in = lv[k];
         const bool last = (k == n_levels - 1);
@@ -186,7 +184,7 @@ extern "C" int tdgl_poisson_set_hierarchy(tdgl_ctx *ctx, const tdgl_amg_level *l
 extern "C" int tdgl_poisson_set_dense_inverse(tdgl_ctx *ctx, const double *G, int64_t n) {
     CTX_GUARD(ctx);
     if (!G) {
-        dense_release(ctx);
+        ctx->direct.reset();
         return TDGL_OK;
     }
     if (distributed(ctx)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_set_dense_inverse: single-GPU contexts only");
@@ -194,7 +192,6 @@ extern "C" int tdgl_poisson_set_dense_inverse(tdgl_ctx *ctx, const double *G, in
     if (n != ctx->n) TDGL_FAIL(ctx, TDGL_ERR_ARG, "dense inverse has %lld rows, the mesh %lld sites", (long long)n, (long long)ctx->n);
     if (n > 46000) TDGL_FAIL(ctx, TDGL_ERR_ARG, "dense inverse: %lld sites is beyond what a dense matrix is meant for", (long long)n);
     const int64_t ld = round_up(n, 2);
-    dense_release(ctx);
     {
         // symmetric packed storage: tiles (I, J), J <= I, of DT x DT entries, zero padded
         const int nt = (int)((n + DT - 1) / DT);
@@ -217,21 +214,22 @@ extern "C" int tdgl_poisson_set_dense_inverse(tdgl_ctx *ctx, const double *G, in
             }
         if (asym > 1e-12 * gmax)
             TDGL_FAIL(ctx, TDGL_ERR_ARG, "dense inverse is not symmetric (max |G - G^T| = %.3e, max |G| = %.3e)", asym, gmax);
-        HIP_TRY(ctx, ctx->denseG.upload(packed));
-        HIP_TRY(ctx, ctx->dense_part.alloc((size_t)nt * nt * DT));
-        ctx->dense_tiles = nt;
-        ctx->dense_n = n;
-        ctx->dense_ld = ld;
+        auto f = std::make_unique<DirectFactors>();
+        HIP_TRY(ctx, f->dense.G.upload(packed));
+        HIP_TRY(ctx, f->dense.part.alloc((size_t)nt * nt * DT));
+        f->dense.tiles = nt;
+        f->dense.n = n;
+        f->ld = ld;
+        ctx->direct = std::move(f);
         return TDGL_OK;
     }
 }
 
 // a direct solve is set (the explicit inverse of the whole matrix, or the substructured one)
+// (not while a description is incomplete -- AMG-PCG meanwhile --, nor when the factors precondition the CG)
 static inline bool dense_on(const tdgl_ctx *ctx) {
-    if (ctx->sub_need_coupling[0] || ctx->sub_need_coupling[1] || ctx->sub_need_coupling[2]) return false;  // (an incomplete description: AMG-PCG meanwhile)
     if (ctx->direct_paused) return false;  // (a stationary state: the iterative solve is the cheaper one, see tdgl_direct_switching)
-    if (ctx->sub_precond) return false;    // (the factors precondition the CG: tdgl_poisson_set_substructure_precond)
-    return (ctx->dense_ld > 0 || ctx->sub_parts > 0) && !distributed(ctx);
+    return ctx->direct && ctx->direct->stage == DirectFactors::READY && !distributed(ctx);
 }
 
 // Optional: M = R0 (I - c A0 D0^-1) as one CSR matrix [n_1, n_0].  With degree-1 smoothing on
@@ -1206,38 +1204,35 @@ extern "C" int tdgl_host_solve_gram(int32_t k, const double *G_pairs, const doub
 // to abandon the solve (the step driver retries a failed psi update without finishing a solve
 // whose right-hand side is garbage).
 //
-// The launches of a direct mu solve, x = pinv(A) b (dense inverse or substructured; see the header).
-// in_step: inside the time loop -- the kernels that write x hold back when this step's psi update failed and
-// the status block is published by k_dense_sym_finish (returns true then).  ctl / rec: the run-ahead loop's
-// device-resident controller and the record of this step (run.inc), else NULL.
+// where the factors live, by storage type (fp64: the direct SOLVE; fp32: the preconditioner, DirectFactors::fp32)
+template <class VT> struct SubPools;
+template <> struct SubPools<double> {
+    static const double *level(const SubLevel &L) { return L.vals.p; }
+    static const double *dense(const DenseTiles &D) { return D.G.p; }
+};
+template <> struct SubPools<float> {
+    static const float *level(const SubLevel &L) { return L.vals32.p; }
+    static const float *dense(const DenseTiles &D) { return D.G32.p; }
+};
+
+// the way up of one level: its separator solution L.xs and the way down's L.w -> out
 template <class VT>
-static void launch_sub_up(tdgl_ctx *ctx, int R, const tdgl::DevBuf<tdgl::SubUpChunk> &chunks, int64_t nI, int64_t nS, const int32_t *sep_idx,
-                          const VT *vals, const double *w, const double *xs, const SubMean &m, const int32_t *fail, double *x,
-                          const StepCtl *ctl) {
-    const int nblk_int = nI > 0 ? (int)chunks.n : 0, nblk_sep = grid_for(nS);
+static void launch_sub_up(tdgl_ctx *ctx, const SubLevel &L, double *out, const SubMean &m, const int32_t *fail, const StepCtl *ctl) {
+    const int64_t nI = L.nI, nS = L.nS;
+    const int nblk_int = nI > 0 ? (int)L.up_chunks.n : 0, nblk_sep = grid_for(nS);
+    const int32_t *sep_idx = L.sep_idx.p;
+    const VT *vals = SubPools<VT>::level(L);
+    const double *w = L.w.p, *xs = L.xs.p;
     // (R: 64-row chunks per workgroup -- 1, or a whole part of up to 256 rows on the levels stored as symmetric tiles)
 #define TDGL_LAUNCH_UP(RR)                                                                                                       \
     hipLaunchKernelGGL((k_sub_up<VT, RR>), dim3(nblk_int + nblk_sep), dim3(BLOCK), 0, ctx->stream, nI, nS, nblk_int,            \
-                       (const SubUpChunk *)chunks.p, sep_idx, vals, w, xs, m, fail, ctx->psi_blocks, x, ctl)
-    if (R >= 4) TDGL_LAUNCH_UP(4);
-    else if (R == 3) TDGL_LAUNCH_UP(3);
-    else if (R == 2) TDGL_LAUNCH_UP(2);
+                       (const SubUpChunk *)L.up_chunks.p, sep_idx, vals, w, xs, m, fail, ctx->psi_blocks, out, ctl)
+    if (L.up_R >= 4) TDGL_LAUNCH_UP(4);
+    else if (L.up_R == 3) TDGL_LAUNCH_UP(3);
+    else if (L.up_R == 2) TDGL_LAUNCH_UP(2);
     else TDGL_LAUNCH_UP(1);
 #undef TDGL_LAUNCH_UP
 }
-
-// where the factors live, by storage type (fp64: the direct SOLVE; fp32: the preconditioner, sub_fp32)
-template <class VT> struct SubPools;
-template <> struct SubPools<double> {
-    static const double *outer(const tdgl_ctx *ctx) { return ctx->sub_vals.p; }
-    static const double *inner(const tdgl_ctx::SubInner &I) { return I.vals.p; }
-    static const double *dense(const tdgl_ctx *ctx) { return ctx->denseG.p; }
-};
-template <> struct SubPools<float> {
-    static const float *outer(const tdgl_ctx *ctx) { return ctx->sub_vals32.p; }
-    static const float *inner(const tdgl_ctx::SubInner &I) { return I.vals32.p; }
-    static const float *dense(const tdgl_ctx *ctx) { return ctx->denseG32.p; }
-};
 
 template <class VT> static size_t sym_lds_bytes(int np_lds) {  // k_sub_down_sym: b_p, eight accumulators, eight tiles
     return (size_t)(1 + 2 * (BLOCK / WAVE)) * np_lds * sizeof(double) + (size_t)(2 * (BLOCK / WAVE)) * ST * STP * sizeof(VT);
@@ -1249,125 +1244,94 @@ template <class VT, class... Args> static void launch_sub_down_sym(tdgl_ctx *ctx
     hipLaunchKernelGGL((k_sub_down_sym<VT, 1>), dim3(grid), dim3(BLOCK), lds, ctx->stream, args...);
 }
 
+// the way down of one level: b (the level's vector) -> L.w.  `lanes`: the preconditioner's lane-per-row work lists;
+// `first`: the first level (its coupling product takes 8 lanes per row, the inner levels' 16)
+template <class VT>
+static void launch_sub_down(tdgl_ctx *ctx, const SubLevel &L, bool first, bool lanes, const double *b, const StepCtl *ctl) {
+    const int64_t nI = L.nI, nS = L.nS, rows = nI + nS + L.parts;
+    const int nblk_dint = nI > 0 ? (int)L.down_chunks.n : 0;
+    const int nblk_drest = (int)((rows - nI + BLOCK / WAVE - 1) / (BLOCK / WAVE));
+    const SubDownChunk *chunks = L.down_chunks.p;
+    const SubDownRow *drows = L.down_rows.p;
+    const int32_t *seg_ptr = L.seg_ptr.p, *seg_x = L.seg_x.p, *seg_len = L.seg_len.p;
+    const int64_t *seg_val = L.seg_val.p;
+    const VT *vals = SubPools<VT>::level(L);
+    if (lanes || L.sym_lds > 0) {  // (tiles: also a level of the fp64 direct solve, tdgl_poisson_set_substructure_layout)
+        const int64_t n_id = L.ident ? nS : 0;
+        const int nblk_id = grid_for(n_id) * (n_id > 0), nblk_w = (int)((rows - nI - n_id + BLOCK / WAVE - 1) / (BLOCK / WAVE));
+        if (L.sym_lds > 0)
+            launch_sub_down_sym<VT>(ctx, (unsigned)(nblk_dint + nblk_id + nblk_w), sym_lds_bytes<VT>(L.sym_lds), nI, n_id, rows, nblk_dint,
+                                    nblk_id, L.sym_lds, chunks, seg_ptr, seg_val, seg_x, seg_len, vals, b, L.w.p, ctl);
+        else
+            hipLaunchKernelGGL((k_sub_down_lanes<VT>), dim3((unsigned)(nblk_dint + nblk_id + nblk_w)), dim3(BLOCK), 0, ctx->stream, nI, n_id, rows,
+                               nblk_dint, nblk_id, chunks, drows, seg_ptr, seg_val, seg_x, seg_len, vals, b, L.w.p, ctl);
+    } else
+        hipLaunchKernelGGL((k_sub_down<VT>), dim3((unsigned)(nblk_dint + nblk_drest)), dim3(BLOCK), 0, ctx->stream, nI, rows, nblk_dint, chunks,
+                           drows, seg_ptr, seg_val, seg_x, seg_len, vals, b, L.w.p, ctl);
+    // (optional: the separator rows above were b_S alone; r_S = b_S - A_SI y_I with the sparse coupling block)
+    if (L.coupling.nnz > 0) {
+        if (first) launch_csr<8, C_RESID, 4>(ctx, L.coupling, L.w.p, L.w.p + nI, nullptr, 0.0, 0.0, nullptr, L.w.p + nI);
+        else launch_csr<16, C_RESID, 4>(ctx, L.coupling, L.w.p, L.w.p + nI, nullptr, 0.0, 0.0, nullptr, L.w.p + nI);
+    }
+}
+
+// The launches of a direct mu solve, x = pinv(A) b (dense inverse or substructured; see the header).
+// in_step: inside the time loop -- the kernels that write x hold back when this step's psi update failed and
+// the status block is published by k_dense_sym_finish (returns true then).  ctl / rec: the run-ahead loop's
+// device-resident controller and the record of this step (run.inc), else NULL.
 template <class VT>
 static bool direct_solve_launch_t(tdgl_ctx *ctx, const double *b, double *x, bool in_step, StepCtl *ctl, StepRec *rec) {
-    typedef SubPools<VT> PL;
+    const DirectFactors &f = *ctx->direct;
     const double inv_n = 1.0 / (double)ctx->n_global;
     const int32_t *fail = in_step ? (const int32_t *)ctx->psi_fail_part.p : (const int32_t *)nullptr;
     StepStatus *st = (in_step && !ctl) ? ctx->status_dev : (StepStatus *)nullptr;
-    if (ctx->sub_parts > 0) {
-        // substructured: way down, separator solve (tiles + finish, which also publishes the step's
-        // status), way up with the mean removed
-        const int nt = ctx->dense_tiles, P = ctx->sub_parts;
-        const int64_t nI = ctx->sub_nI, nS = ctx->sub_nS, rows = nI + nS + P;
-        const int nblk_dint = nI > 0 ? (int)ctx->sub_down_chunks.n : 0;
-        const int nblk_drest = (int)((rows - nI + BLOCK / WAVE - 1) / (BLOCK / WAVE));
-        if (ctx->sub_lanes || ctx->sub_sym_lds[0] > 0) {  // (tiles: also a level of the fp64 direct solve, tdgl_poisson_set_substructure_layout)
-            const int64_t n_id = ctx->sub_ident[0] ? nS : 0;
-            const int nblk_id = grid_for(n_id) * (n_id > 0), nblk_w = (int)((rows - nI - n_id + BLOCK / WAVE - 1) / (BLOCK / WAVE));
-            if (ctx->sub_sym_lds[0] > 0)
-                launch_sub_down_sym<VT>(ctx, (unsigned)(nblk_dint + nblk_id + nblk_w), sym_lds_bytes<VT>(ctx->sub_sym_lds[0]), nI, n_id, rows, nblk_dint, nblk_id, ctx->sub_sym_lds[0], (const SubDownChunk *)ctx->sub_down_chunks.p,
-                                   (const int32_t *)ctx->sub_seg_ptr.p, (const int64_t *)ctx->sub_seg_val.p, (const int32_t *)ctx->sub_seg_x.p,
-                                   (const int32_t *)ctx->sub_seg_len.p, PL::outer(ctx), b, ctx->sub_w.p, (const StepCtl *)ctl);
-            else
-            hipLaunchKernelGGL((k_sub_down_lanes<VT>), dim3((unsigned)(nblk_dint + nblk_id + nblk_w)), dim3(BLOCK), 0, ctx->stream, nI, n_id, rows,
-                               nblk_dint, nblk_id, (const SubDownChunk *)ctx->sub_down_chunks.p, (const SubDownRow *)ctx->sub_down_rows.p,
-                               (const int32_t *)ctx->sub_seg_ptr.p, (const int64_t *)ctx->sub_seg_val.p, (const int32_t *)ctx->sub_seg_x.p,
-                               (const int32_t *)ctx->sub_seg_len.p, PL::outer(ctx), b, ctx->sub_w.p, (const StepCtl *)ctl);
-        } else
-        hipLaunchKernelGGL((k_sub_down<VT>), dim3((unsigned)(nblk_dint + nblk_drest)), dim3(BLOCK), 0, ctx->stream, nI, rows, nblk_dint,
-                           (const SubDownChunk *)ctx->sub_down_chunks.p, (const SubDownRow *)ctx->sub_down_rows.p,
-                           (const int32_t *)ctx->sub_seg_ptr.p, (const int64_t *)ctx->sub_seg_val.p, (const int32_t *)ctx->sub_seg_x.p,
-                           (const int32_t *)ctx->sub_seg_len.p, PL::outer(ctx), b, ctx->sub_w.p, (const StepCtl *)ctl);
-        // (optional: the separator rows above were b_S alone; r_S = b_S - A_SI y_I with the sparse coupling block)
-        if (ctx->sub_coupling.nnz > 0)
-            launch_csr<8, C_RESID, 4>(ctx, ctx->sub_coupling, ctx->sub_w.p, ctx->sub_w.p + nI, nullptr, 0.0, 0.0, nullptr, ctx->sub_w.p + nI);
-        if (ctx->sub_n_inner > 0) {
-            // more levels: the Schur system of a level is solved by the next -- way down on the previous level's
-            // separator vector --, the LAST level's separator by the dense pair (which publishes the step's status); then
-            // the ways up, innermost first, without a gauge: the first of them leaves the mean (all levels' shares of
-            // sum x) for the first level's way up
-            const int K = ctx->sub_n_inner;
-            const double *vec = ctx->sub_w.p + nI;  // the separator vector the next level works on
-            int64_t n_vec = nS;
-            for (int k = 0; k < K; ++k) {
-                auto &I = ctx->sub_in[k];
-                const int64_t rows_k = n_vec + I.parts;
-                const int nblk_dint_k = I.nI > 0 ? (int)I.down_chunks.n : 0;
-                const int nblk_drest_k = (int)((rows_k - I.nI + BLOCK / WAVE - 1) / (BLOCK / WAVE));
-                if (ctx->sub_lanes || ctx->sub_sym_lds[k + 1] > 0) {
-                    const int64_t n_id = ctx->sub_ident[k + 1] ? I.nS : 0;
-                    const int nblk_id = grid_for(n_id) * (n_id > 0);
-                    const int nblk_w = (int)((rows_k - I.nI - n_id + BLOCK / WAVE - 1) / (BLOCK / WAVE));
-                    if (ctx->sub_sym_lds[k + 1] > 0)
-                        launch_sub_down_sym<VT>(ctx, (unsigned)(nblk_dint_k + nblk_id + nblk_w), sym_lds_bytes<VT>(ctx->sub_sym_lds[k + 1]), I.nI, n_id, rows_k, nblk_dint_k, nblk_id,
-                                           ctx->sub_sym_lds[k + 1], (const SubDownChunk *)I.down_chunks.p, (const int32_t *)I.seg_ptr.p,
-                                           (const int64_t *)I.seg_val.p, (const int32_t *)I.seg_x.p, (const int32_t *)I.seg_len.p, PL::inner(I), vec,
-                                           I.w.p, (const StepCtl *)ctl);
-                    else
-                    hipLaunchKernelGGL((k_sub_down_lanes<VT>), dim3((unsigned)(nblk_dint_k + nblk_id + nblk_w)), dim3(BLOCK), 0, ctx->stream, I.nI,
-                                       n_id, rows_k, nblk_dint_k, nblk_id, (const SubDownChunk *)I.down_chunks.p, (const SubDownRow *)I.down_rows.p,
-                                       (const int32_t *)I.seg_ptr.p, (const int64_t *)I.seg_val.p, (const int32_t *)I.seg_x.p,
-                                       (const int32_t *)I.seg_len.p, PL::inner(I), vec, I.w.p, (const StepCtl *)ctl);
-                } else
-                hipLaunchKernelGGL((k_sub_down<VT>), dim3((unsigned)(nblk_dint_k + nblk_drest_k)), dim3(BLOCK), 0, ctx->stream, I.nI, rows_k,
-                                   nblk_dint_k, (const SubDownChunk *)I.down_chunks.p, (const SubDownRow *)I.down_rows.p,
-                                   (const int32_t *)I.seg_ptr.p, (const int64_t *)I.seg_val.p, (const int32_t *)I.seg_x.p,
-                                   (const int32_t *)I.seg_len.p, PL::inner(I), vec, I.w.p, (const StepCtl *)ctl);
-                if (I.coupling.nnz > 0)
-                    launch_csr<16, C_RESID, 4>(ctx, I.coupling, I.w.p, I.w.p + I.nI, nullptr, 0.0, 0.0, nullptr, I.w.p + I.nI);
-                vec = I.w.p + I.nI;
-                n_vec = I.nS;
-            }
-            auto &T = ctx->sub_in[K - 1];
-            hipLaunchKernelGGL((k_dense_sym_tiles<VT>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt,
-                               PL::dense(ctx), vec, ctx->dense_part.p, (const StepCtl *)ctl);
-            hipLaunchKernelGGL(k_dense_sym_finish, dim3(ctx->sub_nfin), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt,
-                               (const double *)ctx->dense_part.p, (const double *)ctx->psi_dmax_part.p,
-                               (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, 0, T.xt.p, (const double *)T.u.p,
-                               ctx->sub_upart.p, ctl, rec);
-            for (int k = K - 1; k >= 0; --k) {
-                auto &I = ctx->sub_in[k];
-                double *out = k == 0 ? ctx->sub_xs.p : ctx->sub_in[k - 1].xt.p;
-                SubMean m{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0.0, 0.0, nullptr, nullptr};
-                if (k == K - 1) {  // (the (G v)^T rows of an inner level sit behind its vector: w + nI + nS)
-                    auto &I0 = ctx->sub_in[0];
-                    m = SubMean{ctx->sub_w.p + nI + nS, ctx->sub_upart.p, I0.w.p + I0.nI + I0.nS,
-                                K > 1 ? ctx->sub_in[1].w.p + ctx->sub_in[1].nI + ctx->sub_in[1].nS : (const double *)nullptr,
-                                P, ctx->sub_nfin, I0.parts, K > 1 ? ctx->sub_in[1].parts : 0, 0.0, inv_n, ctx->sub_mean.p, nullptr};
-                }
-                launch_sub_up<VT>(ctx, ctx->sub_up_R[k + 1], I.chunks, I.nI, I.nS, I.sep_idx.p, PL::inner(I), I.w.p, I.xt.p, m, fail, out, ctl);
-            }
-            launch_sub_up<VT>(ctx, ctx->sub_up_R[0], ctx->sub_chunks, nI, nS, ctx->sub_sep_idx.p, PL::outer(ctx), ctx->sub_w.p, ctx->sub_xs.p,
-                              SubMean{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0.0, 0.0, nullptr, ctx->sub_mean.p}, fail, x, ctl);
-            return in_step;
-        }
-        hipLaunchKernelGGL((k_dense_sym_tiles<VT>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)nS, nt,
-                           PL::dense(ctx), (const double *)(ctx->sub_w.p + nI), ctx->dense_part.p, (const StepCtl *)ctl);
-        hipLaunchKernelGGL(k_dense_sym_finish, dim3(ctx->sub_nfin), dim3(BLOCK), 0, ctx->stream, (int)nS, nt,
-                           (const double *)ctx->dense_part.p, (const double *)ctx->psi_dmax_part.p,
-                           (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, 0, ctx->sub_xs.p, (const double *)ctx->sub_u.p,
-                           ctx->sub_upart.p, ctl, rec);
-        launch_sub_up<VT>(ctx, ctx->sub_up_R[0], ctx->sub_chunks, nI, nS, ctx->sub_sep_idx.p, PL::outer(ctx), ctx->sub_w.p, ctx->sub_xs.p,
-                          SubMean{ctx->sub_w.p + nI + nS, ctx->sub_upart.p, nullptr, nullptr, P, ctx->sub_nfin, 0, 0, inv_n, 0.0, nullptr, nullptr}, fail, x,
-                          ctl);
-        return in_step;
-    }
-    if (ctx->dense_tiles > 0) {
-        const int nt = ctx->dense_tiles;
+    const int nt = f.dense.tiles;
+    if (f.levels == 0) {  // the dense inverse of the whole matrix
         hipLaunchKernelGGL((k_dense_sym_tiles<double>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)ctx->n, nt,
-                           (const double *)ctx->denseG.p, b, ctx->dense_part.p, (const StepCtl *)ctl);
+                           (const double *)f.dense.G.p, b, f.dense.part.p, (const StepCtl *)ctl);
         // (in the time loop the same launch publishes the step's status block)
         hipLaunchKernelGGL(k_dense_sym_finish, dim3((int)((ctx->n + WAVE - 1) / WAVE)), dim3(BLOCK), 0, ctx->stream, (int)ctx->n,
-                           nt, (const double *)ctx->dense_part.p, (const double *)ctx->psi_dmax_part.p, fail, ctx->psi_blocks, st, 1,
+                           nt, (const double *)f.dense.part.p, (const double *)ctx->psi_dmax_part.p, fail, ctx->psi_blocks, st, 1,
                            x, (const double *)nullptr, (double *)nullptr, ctl, rec);
         return in_step;
     }
-    return false;  // (not reached: dense_on() means one of the two forms above)
+    // substructured: the ways down level after level (a level works on the previous level's separator vector), the last
+    // level's separator by the dense pair (which also publishes the step's status), the ways up innermost first.  With
+    // one level its way up removes the mean; with more the inner ones go without a gauge, and the first of them leaves
+    // the mean (all levels' shares of sum x) for the first level's way up.
+    const bool lanes = f.stage == DirectFactors::PRECOND;
+    const int K = f.levels;
+    const double *vec = b;
+    for (int k = 0; k < K; ++k) {
+        launch_sub_down<VT>(ctx, f.lv[k], k == 0, lanes, vec, ctl);
+        vec = f.lv[k].w.p + f.lv[k].nI;
+    }
+    const SubLevel &L0 = f.lv[0], &T = f.lv[K - 1];
+    hipLaunchKernelGGL((k_dense_sym_tiles<VT>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt,
+                       SubPools<VT>::dense(f.dense), vec, f.dense.part.p, (const StepCtl *)ctl);
+    hipLaunchKernelGGL(k_dense_sym_finish, dim3(f.nfin), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt, (const double *)f.dense.part.p,
+                       (const double *)ctx->psi_dmax_part.p, (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, 0, T.xs.p,
+                       (const double *)T.u.p, f.upart.p, ctl, rec);
+    if (K == 1) {
+        launch_sub_up<VT>(ctx, L0, x, SubMean{L0.w.p + L0.nI + L0.nS, f.upart.p, nullptr, nullptr, L0.parts, f.nfin, 0, 0, inv_n, 0.0, nullptr, nullptr},
+                          fail, ctl);
+        return in_step;
+    }
+    for (int k = K - 1; k >= 1; --k) {
+        SubMean m{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0.0, 0.0, nullptr, nullptr};
+        if (k == K - 1) {  // (the (G v)^T rows of a level sit behind its vector: w + nI + nS)
+            const SubLevel &L1 = f.lv[1], &L2 = f.lv[2];
+            m = SubMean{L0.w.p + L0.nI + L0.nS, f.upart.p, L1.w.p + L1.nI + L1.nS, K > 2 ? L2.w.p + L2.nI + L2.nS : (const double *)nullptr,
+                        L0.parts, f.nfin, L1.parts, K > 2 ? L2.parts : 0, 0.0, inv_n, f.mean.p, nullptr};
+        }
+        launch_sub_up<VT>(ctx, f.lv[k], f.lv[k - 1].xs.p, m, fail, ctl);
+    }
+    launch_sub_up<VT>(ctx, L0, x, SubMean{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0.0, 0.0, nullptr, f.mean.p}, fail, ctl);
+    return in_step;
 }
 
 static bool direct_solve_launch(tdgl_ctx *ctx, const double *b, double *x, bool in_step, StepCtl *ctl, StepRec *rec) {
-    return ctx->sub_fp32 ? direct_solve_launch_t<float>(ctx, b, x, in_step, ctl, rec) : direct_solve_launch_t<double>(ctx, b, x, in_step, ctl, rec);
+    return ctx->direct->fp32 ? direct_solve_launch_t<float>(ctx, b, x, in_step, ctl, rec) : direct_solve_launch_t<double>(ctx, b, x, in_step, ctl, rec);
 }
 
 // ---- the factors as preconditioner (tdgl_poisson_set_substructure_precond) ---------------------------------------
@@ -1375,21 +1339,22 @@ static bool direct_solve_launch(tdgl_ctx *ctx, const double *b, double *x, bool 
 // on the fp32-stored factors, the result scattered back together with the partials of r . z.
 static void precond_direct_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part) {
     const int64_t n = ctx->n;
-    hipLaunchKernelGGL(k_pd_gather, dim3(vec_grid(n)), dim3(BLOCK), 0, ctx->stream, n, (const int32_t *)ctx->sub_map.p, r, ctx->sub_bp.p);
-    (void)direct_solve_launch(ctx, ctx->sub_bp.p, ctx->sub_xp.p, false, nullptr, nullptr);
-    hipLaunchKernelGGL(k_pd_scatter, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, n, (const int32_t *)ctx->sub_map.p,
-                       (const double *)ctx->sub_xp.p, r, z, rz_part);
+    const DirectFactors &f = *ctx->direct;
+    hipLaunchKernelGGL(k_pd_gather, dim3(vec_grid(n)), dim3(BLOCK), 0, ctx->stream, n, (const int32_t *)f.map.p, r, f.bp.p);
+    (void)direct_solve_launch(ctx, f.bp.p, f.xp.p, false, nullptr, nullptr);
+    hipLaunchKernelGGL(k_pd_scatter, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, n, (const int32_t *)f.map.p, (const double *)f.xp.p, r, z,
+                       rz_part);
 }
 
 // ... on one GPU the factors of the whole matrix, in one-process-per-GPU mode the rank-level dissection (schur.inc)
 static int precond_factors_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part) {
-    if (ctx->schur_on) return precond_schur_apply(ctx, r, z, rz_part);
+    if (ctx->direct->n_local > 0) return precond_schur_apply(ctx, r, z, rz_part);
     precond_direct_apply(ctx, r, z, rz_part);
     return TDGL_OK;
 }
 
 static inline bool precond_factors_available(const tdgl_ctx *ctx) {
-    return ctx->sub_precond && ctx->sub_parts > 0 && (ctx->schur_on || !distributed(ctx));
+    return ctx->direct && ctx->direct->stage == DirectFactors::PRECOND;
 }
 
 // ---- in-loop guard of the direct mu solves ----------------------------------------------------------
@@ -1419,7 +1384,7 @@ static void direct_guard_read(tdgl_ctx *ctx, bool valid) {
     ctx->direct_checks += 1;
     if (!(relres <= ctx->direct_relres_max)) ctx->direct_relres_max = relres;
     if (!(relres <= ctx->direct_guard_limit)) {
-        dense_release(ctx);  // run_ahead_ok / dense_on are false from now on: AMG-PCG
+        ctx->direct.reset();  // run_ahead_ok / dense_on are false from now on: AMG-PCG
         ctx->direct_fell_back = 1;
     }
 }
@@ -1739,7 +1704,7 @@ static int pcg_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool al
         double *rz_new = part_rz[it & 1], *rz_old = part_rz[(it + 1) & 1];
         const bool cg1 = f32i && ctx->deep;  // (two distributed levels: single-reduction CG on fp32 z, no exchange of z)
         if (use_pd) {
-            z = ctx->sub_z.p;
+            z = ctx->direct->z.p;
             // (profile mode: every application of the first 64 bracketed by an event pair -> tdgl_profile_read_direct)
             hipEvent_t fa = nullptr, fb = nullptr;
             if (ctx->profile && ctx->prof3_launches + (int64_t)ctx->prof3_pending.size() < 64) {
@@ -1961,7 +1926,7 @@ restart:
             if (rr0 > 100.0 * tol2) ctx->pd_rate = 0.8 * ctx->pd_rate + 0.2 * std::min(8.0, std::max(1.0, seen));
         }
     } else {
-        if (ctx->sub_precond) {
+        if (precond_factors_available(ctx)) {
             ctx->pd_amg_solves += 1;
             ctx->pd_amg_iters += it;
         }

@@ -498,7 +498,7 @@ static bool run_ahead_ok(const tdgl_ctx *ctx) {
     // needs the previous step's dt: from the second step of a stage on)
     const bool ramping = ctx->ramp_on && !ramp_settled(ctx);
     if (ramping ? !(ctx->runner_dt > 0.0) : ctx->has_dadt) return false;
-    return !off && dense_on(ctx) && (ctx->dense_tiles > 0) && !ctx->scr_enabled &&
+    return !off && dense_on(ctx) && (ctx->direct->dense.tiles > 0) && !ctx->scr_enabled &&
            (ctx->tab_mu_t.empty() || ctx->tab_mu_on_device) && (ctx->tab_eps_t.empty() || ctx->tab_eps_on_device) &&
            ctx->popt.edge_currents_every_step != 0 && ctx->have_links &&
            ctx->have_state && ctx->have_eps && (!ctl.adaptive || (ctl.adaptive_window >= 1 && ctl.adaptive_window <= RA_HIST_MAX));

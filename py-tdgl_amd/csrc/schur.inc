@@ -3,7 +3,7 @@
 // tdgl/finite_volume/operators.py:305-308 applied at tdgl/solver/solver.py:516.
 //
 // Gamma = a vertex cover of the edges between ranks.  Every rank holds the explicit multi-level factors of ITS interior
-// block A_II (the machinery of dense.inc on a vector of sub_n_local entries; positive definite, so the top separator
+// block A_II (the machinery of dense.inc on a vector of n_local entries; positive definite, so the top separator
 // carries a plain inverse and no gauge), its coupling blocks A_GI / A_IG, and -- like every other rank -- the pseudo-
 // inverse of the interface complement S = A_GG - sum_r A_GI_r A_II_r^-1 A_I_rG as symmetric fp32 tiles.  One application
 //     y_I = A_II^-1 r_I                                  local: gather, the factors' launch sequence
@@ -59,22 +59,9 @@ __global__ __launch_bounds__(BLOCK) void k_schur_column(int32_t k0, int32_t k1, 
 
 }  // namespace tdgl
 
-static void schur_release(tdgl_ctx *ctx) {
-    ctx->sub_n_local = 0;
-    ctx->sub_nonsingular = false;
-    ctx->schur_pending = ctx->schur_on = false;
-    ctx->schur_ng = ctx->schur_ngo = 0;
-    ctx->schur_owner_local.release();
-    ctx->schur_go_local.release();
-    ctx->schur_go_gid.release();
-    ctx->schur_GI.nnz = ctx->schur_IG.nnz = 0;
-    ctx->schurS64.release();
-    ctx->schurS32.release();
-    ctx->schur_part.release();
-    ctx->schur_tiles = 0;
-    for (auto *b : {&ctx->schur_t, &ctx->schur_rg, &ctx->schur_xg, &ctx->schur_y, &ctx->schur_v, &ctx->schur_c}) b->release();
-}
-
+// Every check comes before the resident factors are touched: a refused description leaves them (and a working
+// preconditioner) as they were.  On success a new object holds the interface; the interior's levels follow
+// (tdgl_poisson_set_substructure / _inner / _coupling), then _complement and _finish.
 extern "C" int tdgl_poisson_schur_begin(tdgl_ctx *ctx, const tdgl_schur_piece *pc) {
     CTX_GUARD(ctx);
     if (!pc || pc->n_interior < 2 || pc->n_gamma < 2 || !pc->interior || !pc->gi_indptr || !pc->ig_indptr ||
@@ -84,8 +71,6 @@ extern "C" int tdgl_poisson_schur_begin(tdgl_ctx *ctx, const tdgl_schur_piece *p
     if (pc->n_interior + pc->n_gamma_owned != ctx->n_own)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_begin: interior (%lld) + owned interface sites (%lld) must be the owned sites (%lld)",
                   (long long)pc->n_interior, (long long)pc->n_gamma_owned, (long long)ctx->n_own);
-    dense_release(ctx);
-    schur_release(ctx);
     const int64_t nI = pc->n_interior, ng = pc->n_gamma, ngo = pc->n_gamma_owned;
     std::vector<char> seen((size_t)ctx->n_own, 0);
     for (int64_t i = 0; i < nI; ++i) {
@@ -101,32 +86,37 @@ extern "C" int tdgl_poisson_schur_begin(tdgl_ctx *ctx, const tdgl_schur_piece *p
         seen[l] = 1;
         owner[g] = l;
     }
-    HIP_TRY(ctx, ctx->sub_map.upload(std::vector<int32_t>(pc->interior, pc->interior + nI)));
-    HIP_TRY(ctx, ctx->schur_owner_local.upload(owner));
-    HIP_TRY(ctx, ctx->schur_go_local.upload(ngo > 0 ? std::vector<int32_t>(pc->gamma_owned_local, pc->gamma_owned_local + ngo) : std::vector<int32_t>(1, 0)));
-    HIP_TRY(ctx, ctx->schur_go_gid.upload(ngo > 0 ? std::vector<int32_t>(pc->gamma_owned_gid, pc->gamma_owned_gid + ngo) : std::vector<int32_t>(1, 0)));
+    if (!offsets_ok(pc->gi_indptr, ng) || (pc->gi_indptr[ng] > 0 && (!pc->gi_indices || !pc->gi_data)))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_begin: inconsistent A_GI");
+    if (!offsets_ok(pc->ig_indptr, nI) || (pc->ig_indptr[nI] > 0 && (!pc->ig_indices || !pc->ig_data)))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_begin: inconsistent A_IG");
     for (int64_t k = 0; k < pc->gi_indptr[ng]; ++k)
         if (pc->gi_indices[k] < 0 || pc->gi_indices[k] >= nI) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_begin: A_GI column out of range");
     for (int64_t k = 0; k < pc->ig_indptr[nI]; ++k)
         if (pc->ig_indices[k] < 0 || pc->ig_indices[k] >= ng) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_begin: A_IG column out of range");
-    TDGL_TRY(upload_csr(ctx, ng, nI, pc->gi_indptr, pc->gi_indices, pc->gi_data, ctx->schur_GI));
-    TDGL_TRY(upload_csr(ctx, nI, ng, pc->ig_indptr, pc->ig_indices, pc->ig_data, ctx->schur_IG));
-    HIP_TRY(ctx, ctx->sub_bp.alloc((size_t)nI));
-    HIP_TRY(ctx, ctx->sub_xp.alloc((size_t)nI));
-    HIP_TRY(ctx, ctx->sub_z.alloc((size_t)ctx->n_pad));
-    for (auto *b : {&ctx->schur_t, &ctx->schur_rg, &ctx->schur_xg}) HIP_TRY(ctx, b->alloc((size_t)ng));
-    for (auto *b : {&ctx->schur_y, &ctx->schur_v, &ctx->schur_c}) HIP_TRY(ctx, b->alloc((size_t)nI));
-    ctx->schur_ng = ng;
-    ctx->schur_ngo = ngo;
-    ctx->sub_n_local = nI;
-    ctx->sub_nonsingular = true;
-    ctx->schur_pending = true;
+    auto f = std::make_unique<DirectFactors>();
+    HIP_TRY(ctx, f->map.upload(std::vector<int32_t>(pc->interior, pc->interior + nI)));
+    HIP_TRY(ctx, f->owner_local.upload(owner));
+    HIP_TRY(ctx, f->go_local.upload(ngo > 0 ? std::vector<int32_t>(pc->gamma_owned_local, pc->gamma_owned_local + ngo) : std::vector<int32_t>(1, 0)));
+    HIP_TRY(ctx, f->go_gid.upload(ngo > 0 ? std::vector<int32_t>(pc->gamma_owned_gid, pc->gamma_owned_gid + ngo) : std::vector<int32_t>(1, 0)));
+    TDGL_TRY(upload_csr(ctx, ng, nI, pc->gi_indptr, pc->gi_indices, pc->gi_data, f->GI));
+    TDGL_TRY(upload_csr(ctx, nI, ng, pc->ig_indptr, pc->ig_indices, pc->ig_data, f->IG));
+    HIP_TRY(ctx, f->bp.alloc((size_t)nI));
+    HIP_TRY(ctx, f->xp.alloc((size_t)nI));
+    HIP_TRY(ctx, f->z.alloc((size_t)ctx->n_pad));
+    for (auto *b : {&f->t, &f->rg, &f->xg}) HIP_TRY(ctx, b->alloc((size_t)ng));
+    for (auto *b : {&f->y, &f->v, &f->c}) HIP_TRY(ctx, b->alloc((size_t)nI));
+    f->ng = ng;
+    f->ngo = ngo;
+    f->n_local = nI;
+    f->stage = DirectFactors::SCHUR_BEGUN;
+    ctx->direct = std::move(f);
     return TDGL_OK;
 }
 
+// between tdgl_poisson_schur_begin and _finish, with the interior's factors complete
 static inline bool schur_factors_ready(const tdgl_ctx *ctx) {
-    return ctx->schur_pending && ctx->sub_parts > 0 && !ctx->sub_wait_inner && !ctx->sub_need_coupling[0] && !ctx->sub_need_coupling[1] &&
-           !ctx->sub_need_coupling[2];
+    return ctx->direct && ctx->direct->n_local > 0 && ctx->direct->stage == DirectFactors::READY;
 }
 
 // C = A_GI A_II^-1 A_IG restricted to the interface sites this rank's interior touches, column by column with the
@@ -134,26 +124,27 @@ static inline bool schur_factors_ready(const tdgl_ctx *ctx) {
 extern "C" int tdgl_poisson_schur_complement(tdgl_ctx *ctx, double *out) {
     CTX_GUARD(ctx);
     if (!out) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_complement: null output");
-    if (!schur_factors_ready(ctx) || ctx->sub_fp32)
+    if (!schur_factors_ready(ctx))
         TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_schur_complement: between tdgl_poisson_schur_begin and _finish, with the interior's factors described");
-    const int64_t ng = ctx->schur_ng, nI = ctx->sub_n_local;
+    DirectFactors &f = *ctx->direct;
+    const int64_t ng = f.ng, nI = f.n_local;
     std::vector<int32_t> gp((size_t)ng + 1);
-    HIP_TRY(ctx, hipMemcpy(gp.data(), ctx->schur_GI.indptr.p, gp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(gp.data(), f.GI.indptr.p, gp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     std::vector<int64_t> touched;
     for (int64_t g = 0; g < ng; ++g)
         if (gp[g + 1] > gp[g]) touched.push_back(g);
     DevBuf<double> cols;  // [touched, ng]: one result column (a row of the symmetric C) per touched site
     HIP_TRY(ctx, cols.alloc(std::max<size_t>(1, touched.size() * (size_t)ng)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->sub_bp.p, 0, nI * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(f.bp.p, 0, nI * sizeof(double), ctx->stream));
     for (size_t k = 0; k < touched.size(); ++k) {
         const int64_t g = touched[k];
         const int cnt = gp[g + 1] - gp[g];
-        hipLaunchKernelGGL(k_schur_column, dim3(grid_for(cnt)), dim3(BLOCK), 0, ctx->stream, gp[g], gp[g + 1], (const int32_t *)ctx->schur_GI.indices.p,
-                           (const double *)ctx->schur_GI.data.p, 1, ctx->sub_bp.p);
-        (void)direct_solve_launch(ctx, ctx->sub_bp.p, ctx->schur_y.p, false, nullptr, nullptr);
-        launch_csr<8, C_AX, 4>(ctx, ctx->schur_GI, ctx->schur_y.p, nullptr, nullptr, 0.0, 0.0, nullptr, cols.p + k * (size_t)ng);
-        hipLaunchKernelGGL(k_schur_column, dim3(grid_for(cnt)), dim3(BLOCK), 0, ctx->stream, gp[g], gp[g + 1], (const int32_t *)ctx->schur_GI.indices.p,
-                           (const double *)ctx->schur_GI.data.p, 0, ctx->sub_bp.p);
+        hipLaunchKernelGGL(k_schur_column, dim3(grid_for(cnt)), dim3(BLOCK), 0, ctx->stream, gp[g], gp[g + 1], (const int32_t *)f.GI.indices.p,
+                           (const double *)f.GI.data.p, 1, f.bp.p);
+        (void)direct_solve_launch(ctx, f.bp.p, f.y.p, false, nullptr, nullptr);
+        launch_csr<8, C_AX, 4>(ctx, f.GI, f.y.p, nullptr, nullptr, 0.0, 0.0, nullptr, cols.p + k * (size_t)ng);
+        hipLaunchKernelGGL(k_schur_column, dim3(grid_for(cnt)), dim3(BLOCK), 0, ctx->stream, gp[g], gp[g + 1], (const int32_t *)f.GI.indices.p,
+                           (const double *)f.GI.data.p, 0, f.bp.p);
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -167,62 +158,58 @@ extern "C" int tdgl_poisson_schur_complement(tdgl_ctx *ctx, double *out) {
 }
 
 static int precond_schur_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part) {
-    const int64_t nI = ctx->sub_n_local, ng = ctx->schur_ng;
-    hipLaunchKernelGGL(k_pd_gather, dim3(vec_grid(nI)), dim3(BLOCK), 0, ctx->stream, nI, (const int32_t *)ctx->sub_map.p, r, ctx->sub_bp.p);
-    (void)direct_solve_launch(ctx, ctx->sub_bp.p, ctx->schur_y.p, false, nullptr, nullptr);
-    hipLaunchKernelGGL(k_schur_owned_rhs, dim3(grid_for(ng)), dim3(BLOCK), 0, ctx->stream, ng, (const int32_t *)ctx->schur_owner_local.p, r,
-                       ctx->schur_rg.p);
-    launch_csr<8, C_RESID, 4>(ctx, ctx->schur_GI, ctx->schur_y.p, ctx->schur_rg.p, nullptr, 0.0, 0.0, nullptr, ctx->schur_t.p);
-    TDGL_TRY(comm_allreduce(ctx, ctx->schur_t.p, ng, 0));  // THE collective of an application
-    const int nt = ctx->schur_tiles;
-    if (ctx->schurS32.n > 0)
-        hipLaunchKernelGGL((k_dense_sym_tiles<float>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)ng, nt, (const float *)ctx->schurS32.p,
-                           (const double *)ctx->schur_t.p, ctx->schur_part.p, (const StepCtl *)nullptr);
+    const DirectFactors &f = *ctx->direct;
+    const int64_t nI = f.n_local, ng = f.ng;
+    hipLaunchKernelGGL(k_pd_gather, dim3(vec_grid(nI)), dim3(BLOCK), 0, ctx->stream, nI, (const int32_t *)f.map.p, r, f.bp.p);
+    (void)direct_solve_launch(ctx, f.bp.p, f.y.p, false, nullptr, nullptr);
+    hipLaunchKernelGGL(k_schur_owned_rhs, dim3(grid_for(ng)), dim3(BLOCK), 0, ctx->stream, ng, (const int32_t *)f.owner_local.p, r, f.rg.p);
+    launch_csr<8, C_RESID, 4>(ctx, f.GI, f.y.p, f.rg.p, nullptr, 0.0, 0.0, nullptr, f.t.p);
+    TDGL_TRY(comm_allreduce(ctx, f.t.p, ng, 0));  // THE collective of an application
+    const int nt = f.S.tiles;
+    if (f.S.G32.n > 0)
+        hipLaunchKernelGGL((k_dense_sym_tiles<float>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)ng, nt, (const float *)f.S.G32.p,
+                           (const double *)f.t.p, f.S.part.p, (const StepCtl *)nullptr);
     else
-        hipLaunchKernelGGL((k_dense_sym_tiles<double>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)ng, nt, (const double *)ctx->schurS64.p,
-                           (const double *)ctx->schur_t.p, ctx->schur_part.p, (const StepCtl *)nullptr);
+        hipLaunchKernelGGL((k_dense_sym_tiles<double>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)ng, nt, (const double *)f.S.G.p,
+                           (const double *)f.t.p, f.S.part.p, (const StepCtl *)nullptr);
     hipLaunchKernelGGL(k_dense_sym_finish, dim3((int)((ng + WAVE - 1) / WAVE)), dim3(BLOCK), 0, ctx->stream, (int)ng, nt,
-                       (const double *)ctx->schur_part.p, (const double *)nullptr, (const int32_t *)nullptr, 0, (StepStatus *)nullptr, 0,
-                       ctx->schur_xg.p, (const double *)nullptr, (double *)nullptr, (StepCtl *)nullptr, (StepRec *)nullptr);
-    launch_csr<8, C_AX, 4>(ctx, ctx->schur_IG, ctx->schur_xg.p, nullptr, nullptr, 0.0, 0.0, nullptr, ctx->schur_c.p);
-    (void)direct_solve_launch(ctx, ctx->schur_c.p, ctx->schur_v.p, false, nullptr, nullptr);
-    hipLaunchKernelGGL(k_schur_scatter, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, nI, (const int32_t *)ctx->sub_map.p,
-                       (const double *)ctx->schur_y.p, (const double *)ctx->schur_v.p, ctx->schur_ngo, (const int32_t *)ctx->schur_go_local.p,
-                       (const int32_t *)ctx->schur_go_gid.p, (const double *)ctx->schur_xg.p, r, z, rz_part);
+                       (const double *)f.S.part.p, (const double *)nullptr, (const int32_t *)nullptr, 0, (StepStatus *)nullptr, 0,
+                       f.xg.p, (const double *)nullptr, (double *)nullptr, (StepCtl *)nullptr, (StepRec *)nullptr);
+    launch_csr<8, C_AX, 4>(ctx, f.IG, f.xg.p, nullptr, nullptr, 0.0, 0.0, nullptr, f.c.p);
+    (void)direct_solve_launch(ctx, f.c.p, f.v.p, false, nullptr, nullptr);
+    hipLaunchKernelGGL(k_schur_scatter, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, nI, (const int32_t *)f.map.p, (const double *)f.y.p,
+                       (const double *)f.v.p, f.ngo, (const int32_t *)f.go_local.p, (const int32_t *)f.go_gid.p, (const double *)f.xg.p, r, z,
+                       rz_part);
     return TDGL_OK;
 }
 
-// S [n_gamma, n_gamma] row major: the interface complement summed over the ranks (the same array on every rank)
+// S [n_gamma, n_gamma] row major: the interface complement summed over the ranks (the same array on every rank).  The
+// interior's factors are converted in place (sub_factors_to_precond): a failure after the checks releases them.
 extern "C" int tdgl_poisson_schur_finish(tdgl_ctx *ctx, const double *S, int32_t fp32_storage, double *t_apply_us, double *t_vcycle_us) {
     CTX_GUARD(ctx);
     if (!S) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_finish: the interface complement is required");
-    if (!schur_factors_ready(ctx))
+    if (!schur_factors_ready(ctx) || sub_laid_out(*ctx->direct))
         TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_schur_finish: tdgl_poisson_schur_begin and the interior's factors (every level, every coupling block) first");
-    const int64_t m = ctx->schur_ng;
-    {  // pseudo-inverse on the device (null space: the constants), symmetric tiles
-        double s = 0.0;
-        for (int64_t i = 0; i < m; ++i) s += S[i * m + i];
-        s /= (double)m;
-        if (!(s > 0.0) || !std::isfinite(s)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_finish: the interface complement has a non-positive mean diagonal");
-        const int64_t N = round_up(m, GB);
+    DirectFactors &f = *ctx->direct;
+    const int64_t m = f.ng;
+    // pseudo-inverse on the device (null space: the constants), symmetric tiles
+    double s = 0.0;
+    for (int64_t i = 0; i < m; ++i) s += S[i * m + i];
+    s /= (double)m;
+    if (!(s > 0.0) || !std::isfinite(s)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_finish: the interface complement has a non-positive mean diagonal");
+    const int64_t N = round_up(m, GB);
+    DenseTiles D;
+    {
         DevBuf<double> src, M;
         HIP_TRY(ctx, src.alloc((size_t)m * m, false));
         HIP_TRY(ctx, hipMemcpy(src.p, S, (size_t)m * m * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(ctx, M.alloc((size_t)N * N, false));
         hipLaunchKernelGGL(k_dense_from, dim3(grid_for(N * N)), dim3(BLOCK), 0, ctx->stream, m, N, s / (double)m, (const double *)src.p, M.p);
-        TDGL_TRY(dense_sweep_pack_to(ctx, M, m, N, 1.0 / (s * (double)m), ctx->schurS64, ctx->schur_part, &ctx->schur_tiles));
+        TDGL_TRY(dense_sweep_pack(ctx, M, m, N, 1.0 / (s * (double)m), D));
     }
-    if (fp32_storage) {
-        HIP_TRY(ctx, ctx->schurS32.alloc(ctx->schurS64.n, false));
-        hipLaunchKernelGGL(k_to_float, dim3(vec_grid((int64_t)ctx->schurS64.n)), dim3(BLOCK), 0, ctx->stream, (int64_t)ctx->schurS64.n,
-                           (const double *)ctx->schurS64.p, ctx->schurS32.p);
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->schurS64.release();
-    }
+    if (fp32_storage) TDGL_TRY(dense_to_fp32(ctx, D));
+    f.S = std::move(D);
     TDGL_TRY(sub_factors_to_precond(ctx, fp32_storage != 0, "tdgl_poisson_schur_finish"));
-    ctx->schur_pending = false;
-    ctx->schur_on = true;
-    ctx->sub_precond = true;
     ctx->direct_switch_on = false;
     ctx->direct_paused = false;
     ctx->pcg_epoch += 1;

@@ -12,6 +12,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -37,6 +38,11 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&other) noexcept { take(other); }
+    DevBuf &operator=(DevBuf &&other) noexcept {
+        if (this != &other) take(other);
+        return *this;
+    }
     ~DevBuf() { release(); }
     void release() {
         if (p) (void)hipFree(p);
@@ -234,6 +240,81 @@ struct StepStatus {
     double gdot[2 * (2 * GUESS_MAX + 2)];
 };
 
+// One level of the nested-dissection factors (dense.inc: sub_upload_level; include/tdgl_hip.h: tdgl_substructure).  The
+// first level works on the site vector (or a rank's interior), every further one on the previous level's separator.
+struct SubLevel {
+    int32_t parts = 0;
+    int64_t nI = 0, nS = 0;                // interior rows / separator rows; nI + nS = the length of the level's vector
+    DevBuf<int32_t> part_ptr, seg_ptr, seg_x, seg_len, sep_ptr, sep_idx, row_part;
+    DevBuf<int64_t> seg_val, g_off;
+    DevBuf<double> vals, u;
+    DevBuf<float> vals32;                  // the pool in fp32 (the preconditioner's storage; `vals` released)
+    DevBuf<SubUpChunk> up_chunks;
+    DevBuf<SubDownChunk> down_chunks;
+    DevBuf<SubDownRow> down_rows;
+    DevBuf<double> w;                      // [nI + nS + parts] result of the way down
+    DevBuf<double> xs;                     // [nS] separator solution
+    Csr coupling;                          // (optional) A_SI [nS x nI]: r_S = r_S - coupling y_I behind the way down
+    int sym_lds = 0;                       // rows of b_p k_sub_down_sym stages (0: whole blocks)
+    int up_R = 1;                          // chunks of 64 rows a workgroup of the way up takes (a whole part where > 1)
+    bool ident = false;                    // the separator rows are their identity segment alone (out = b)
+    bool need_coupling = false;            // described without its -E^T rows: the coupling block must follow
+};
+
+// a symmetric matrix as its tiles on or below the diagonal (kernels.inc: k_dense_sym_tiles)
+struct DenseTiles {
+    DevBuf<double> G;
+    DevBuf<float> G32;                     // (fp32 storage: G released)
+    DevBuf<double> part;                   // per-tile contributions of k_dense_sym_tiles [tiles][tiles * DT]
+    int tiles = 0;                         // tiles per side
+    int64_t n = 0;                         // order of the matrix
+};
+
+// Everything a direct mu solve owns (dense.inc, schur.inc): the dense inverse of the whole matrix, or the levels of a
+// nested dissection with the dense pseudo-inverse of the last level's separator; as the CG's preconditioner also the
+// dissection map and its work vectors; in one-process-per-GPU mode the rank-level interface.  tdgl_ctx::direct holds it,
+// and releasing it is a reset of that pointer.  Every set-up entry point checks its input before it touches the object
+// and builds into a new object or a new level, which it moves in only once complete.
+struct DirectFactors {
+    enum Stage {
+        SCHUR_BEGUN,       // tdgl_poisson_schur_begin: the interface is in place, the interior's levels are not
+        INNER_PENDING,     // the first level came without a Schur complement: inner levels until one carries it
+        COUPLING_PENDING,  // every level is there, some coupling block is not
+        READY,             // a complete direct solve (one GPU), or the interior's factors (between schur_begin and _finish)
+        PRECOND,           // the factors precondition the CG (tdgl_poisson_set_substructure_precond / _schur_finish)
+    };
+    Stage stage = READY;
+    DenseTiles dense;                      // pinv of the whole matrix (levels == 0), or of the last level's separator
+    int64_t ld = 0;                        // > 0: `dense` is the inverse of the whole matrix (tdgl_poisson_set_dense_inverse)
+    // nested dissection
+    SubLevel lv[3];
+    int levels = 0;                        // levels described so far
+    int nfin = 0;                          // workgroups of the separator's k_dense_sym_finish
+    DevBuf<double> upart;                  // their partials of u . x_S
+    DevBuf<double> mean;                   // [1] several levels: the mean of the solution, left for the first level's way up
+    bool fp32 = false;                     // the pools and the dense tiles are stored in fp32
+    // the preconditioner's application in the dissection order: map[i] = the context's index of dissection position i
+    DevBuf<int32_t> map;
+    DevBuf<double> bp, xp, z;              // gathered residual / solution in dissection order / z in the context's order
+    // rank-level dissection (schur.inc): the levels are those of this rank's interior block A_II (n_local sites,
+    // positive definite: plain inverse of the top separator, no gauge), Gamma = the interface between the ranks
+    int64_t n_local = 0;                   // > 0: rank-level dissection
+    int64_t ng = 0, ngo = 0;
+    DevBuf<int32_t> owner_local;           // [ng] local index of the Gamma site if this rank owns it, else -1
+    DevBuf<int32_t> go_local, go_gid;      // [ngo] owned Gamma sites: local index, position in Gamma
+    Csr GI, IG;                            // A_GI [ng x n_I], A_IG [n_I x ng] (columns / rows in the local dissection order)
+    DenseTiles S;                          // pinv of the interface complement, the same on every rank
+    DevBuf<double> t, rg, xg, y, v, c;     // [ng] x 3, [n_I] x 3
+
+    bool in_schur_setup() const { return n_local > 0 && stage != PRECOND; }
+    // the stage a complete set of levels has reached
+    Stage settled() const {
+        for (int k = 0; k < levels; ++k)
+            if (lv[k].need_coupling) return COUPLING_PENDING;
+        return READY;
+    }
+};
+
 }  // namespace tdgl
 
 struct IpcState;  // peer-mapped transport (ipc.inc)
@@ -358,91 +439,14 @@ struct tdgl_ctx {
     int64_t f32_fallbacks = 0;            // solves that had to be finished with the fp64 operators
     tdgl::DevBuf<double> coarse_pinv;
     int64_t n_coarsest = 0;
-    // direct solve for small meshes (tdgl_poisson_set_dense_inverse): mu = G b, G = pinv(A) dense
-    // [n, dense_ld] row major; replaces the PCG iteration while set (single GPU only)
-    tdgl::DevBuf<double> denseG;
-    int64_t dense_ld = 0;                 // > 0: in use
-    int dense_tiles = 0;                  // > 0: symmetric packed storage, tiles per side (k_dense_sym_tiles)
-    tdgl::DevBuf<double> dense_part;      // its per-tile contributions [dense_tiles][dense_tiles * DT]
-    // substructured direct solve (tdgl_poisson_set_substructure): the Schur pseudo-inverse lives in
-    // denseG / dense_part / dense_tiles (dense_n = n_sep)
-    int64_t dense_n = 0;                  // order of the matrix in denseG (n, or n_sep)
-    int32_t sub_parts = 0;                // > 0: in use
-    int64_t sub_nI = 0, sub_nS = 0;
-    tdgl::DevBuf<int32_t> sub_part_ptr, sub_seg_ptr, sub_seg_x, sub_seg_len, sub_sep_ptr, sub_sep_idx, sub_row_part;
-    tdgl::DevBuf<int64_t> sub_seg_val, sub_e_off, sub_g_off;
-    tdgl::DevBuf<double> sub_vals, sub_e, sub_u;
-    tdgl::DevBuf<double> sub_w;           // [n + parts] result of the way down
-    tdgl::DevBuf<double> sub_xs;          // [n_sep] separator solution before the mean is removed
-    tdgl::DevBuf<double> sub_upart;       // per-workgroup partials of u . x_S
-    int sub_nfin = 0;                     // workgroups of k_dense_sym_finish
-    // further levels (tdgl_poisson_set_substructure_inner, once or twice): the same construction on the previous level's
-    // Schur complement -- the second level's "parts" are the fine separators of the super-blocks, its separator the top
-    // separator T; a third level cuts T the same way.  The LAST level's separator is the one whose pseudo-inverse is the
-    // matrix in denseG.  sub_n_inner == 0: one level.
-    struct SubInner {
-        int32_t parts = 0;
-        int64_t nI = 0, nS = 0;           // fine-separator sites / |T|; nI + nS = sub_nS
-        tdgl::DevBuf<int32_t> part_ptr, seg_ptr, seg_x, seg_len, sep_ptr, sep_idx, row_part;
-        tdgl::DevBuf<int64_t> seg_val, e_off, g_off;
-        tdgl::DevBuf<double> vals, e, u;
-        tdgl::DevBuf<float> vals32;       // (sub_fp32: the pool in fp32, `vals` released)
-        tdgl::DevBuf<tdgl::SubUpChunk> chunks;
-        tdgl::DevBuf<tdgl::SubDownChunk> down_chunks;
-        tdgl::DevBuf<tdgl::SubDownRow> down_rows;
-        tdgl::DevBuf<double> w;           // [sub_nS + parts] way down of the second level
-        tdgl::DevBuf<double> xt;          // [|T|] top separator solution
-        tdgl::Csr coupling;               // (optional) S1_TS' [|T| x nI]: r_T = r_T - coupling y_q, see sub_coupling
-    } sub_in[2];
-    int sub_n_inner = 0;                  // inner levels set so far (the last one carries the dense top separator)
-    int sub_outer_parts_pending = 0;      // parts of the first level while it waits for its inner levels
-    tdgl::DevBuf<tdgl::SubUpChunk> sub_chunks;
-    tdgl::DevBuf<tdgl::SubDownChunk> sub_down_chunks;
-    tdgl::DevBuf<tdgl::SubDownRow> sub_down_rows;
-    tdgl::DevBuf<double> sub_mean;        // [1] two levels: the mean of the solution, left by the second level's way up
-    // (optional, tdgl_poisson_set_substructure_coupling) A_SI [sub_nS x sub_nI]: the separator right-hand side of the way
-    // down as r_S = b_S - A_SI y_I, a sparse product behind the dense one, instead of the -E_p^T rows inside it
-    tdgl::Csr sub_coupling;
-    // The factors as the CG's PRECONDITIONER (tdgl_poisson_set_substructure_precond; 650k - 1.3M sites): value pools and
-    // the top separator's tiles stored in fp32 (sub_vals32 / SubInner::vals32 / denseG32; the fp64 pools are released),
-    // every multiply-add fp64; the context stays in reverse Cuthill-McKee order, the dissection order lives inside the
-    // application (sub_map[i] = the context's index of the site at dissection position i).  One application contracts
-    // the residual by ~1e-5 .. 1e-6 (the rounding of the stored entries), so the CG needs ONE iteration wherever the
-    // projection guess is good to 1e-4 -- at half the bytes of the fp64 factors.  pcg_solve chooses between this and the
-    // AMG V-cycle per solve, by predicted cost (iterations x measured time per application).
-    bool sub_precond = false;
-    bool sub_fp32 = false;
-    int sub_up_R[3] = {1, 1, 1};          // per level: chunks of 64 rows a workgroup of the way up takes (a whole part where > 1)
-    int sub_sym_lds[3] = {0, 0, 0};       // per level: rows of b_p k_sub_down_sym stages (0: whole blocks, k_sub_down_lanes)
-    bool sub_lanes = false;               // the ways down run k_sub_down_lanes (chunk lists rebuilt for it)
-    bool sub_ident[3] = {false, false, false};  // level k's separator rows are their identity segment alone (out = b)
-    tdgl::DevBuf<float> sub_vals32, denseG32;
-    tdgl::DevBuf<int32_t> sub_map;
-    tdgl::DevBuf<double> sub_bp, sub_xp, sub_z;   // [n] gathered residual / solution in dissection order / z in the context's order
+    // direct mu solve (tdgl_poisson_set_dense_inverse / _build_dense_inverse / _set_substructure* / _schur_*): null = AMG-PCG
+    std::unique_ptr<tdgl::DirectFactors> direct;
     int32_t pd_choice = 0;                // 0: by predicted cost, 1: always the factors, 2: never (AMG V-cycle)
     double pd_rate = 4.5;                 // decades per iteration observed with the factors as preconditioner (running mean)
     double pd_t_apply_us = 0.0, pd_t_vcycle_us = 0.0;  // measured at set-up: one application of either preconditioner
     int64_t pd_solves = 0, pd_iters = 0, pd_amg_solves = 0, pd_amg_iters = 0;  // solves / iterations by preconditioner since the last reset
     bool pd_last = false;                 // the last solve used the factors
     int64_t pd_handovers = 0;             // solves that began with the factors and were finished by the V-cycle
-    // Rank-level nested dissection (one process per GPU; schur.inc, tdgl_poisson_schur_begin / _complement / _finish): the
-    // resident factors are those of THIS RANK'S INTERIOR block A_II (sub_n_local sites in the local dissection order, positive
-    // definite: plain inverse of the top separator, no gauge), Gamma = the interface between the ranks (schur_ng sites,
-    // global numbering), schurS32 = pinv of the interface complement in symmetric fp32 tiles on every rank.  One
-    // application = two local solves + ONE all-reduce of schur_ng doubles + a replicated dense product.
-    int64_t sub_n_local = 0;               // > 0: length of the vector the first level works on (instead of n)
-    bool sub_nonsingular = false;
-    bool schur_pending = false, schur_on = false;
-    int64_t schur_ng = 0, schur_ngo = 0;
-    tdgl::DevBuf<int32_t> schur_owner_local;   // [ng] local index of the Gamma site if this rank owns it, else -1
-    tdgl::DevBuf<int32_t> schur_go_local, schur_go_gid;  // [ngo] owned Gamma sites: local index, position in Gamma
-    tdgl::Csr schur_GI, schur_IG;          // A_GI [ng x n_I], A_IG [n_I x ng] (columns / rows in the local dissection order)
-    tdgl::DevBuf<double> schurS64;         // tiles of the pseudo-inverse (fp64 until the conversion)
-    tdgl::DevBuf<float> schurS32;
-    tdgl::DevBuf<double> schur_part;
-    int schur_tiles = 0;
-    tdgl::DevBuf<double> schur_t, schur_rg, schur_xg, schur_y, schur_v, schur_c;  // [ng] x 3, [n_I] x 3
-    bool sub_need_coupling[3] = {false, false, false};  // a level was described without its -E^T rows and its coupling block is not there yet
     // Solver choice in the time loop (tdgl_direct_switching; meshes where BOTH a direct solve and the hierarchy are
     // resident and large enough for the choice to matter).  A direct solve costs the same whatever the state; AMG-PCG
     // started from the projection guess costs next to nothing once the state is stationary (a transport current
@@ -458,7 +462,6 @@ struct tdgl_ctx {
     int64_t direct_recent_n = 0;
     double direct_win_max[4] = {0, 0, 0, 0};  // maxima of the last four complete windows of 64 steps, oldest first
     double direct_pcg_ema = 0.0;
-    bool sub_wait_inner = false;          // first level set without a Schur complement: not usable before the second is
     // run-ahead time loop (direct solves, static links): device-resident controller + per-step records
     tdgl::DevBuf<tdgl::StepCtl> d_ctl;
     tdgl::DevBuf<tdgl::StepRec> d_rec;
