@@ -734,8 +734,10 @@ int tdgl_guess_dots(tdgl_ctx *ctx, int32_t k, int64_t n, const double *vectors, 
  * and Runner clock (time, stage step, adaptive dt, retries).  One round of the loop is one attempt of every live
  * replica in five launches over all of them; the host synchronises once per batch of rounds.  The per-replica
  * setters form their input with the context's own entry point of the same name and copy it: the context's own run
- * state is overwritten.  Static inputs only (no dA/dt, no time tables, no screening).  Release the ensemble before
- * the context. */
+ * state is overwritten.  Time-dependent inputs are the three forms the run-ahead loop evaluates on the device: a
+ * replica's field ramp (tdgl_ensemble_set_link_ramp), tabulated terminal currents and separable epsilon, each
+ * evaluated at the replica's own time; no per-step host input, no screening.  Release the ensemble before the
+ * context. */
 typedef struct tdgl_ensemble tdgl_ensemble;
 #define TDGL_ENSEMBLE_MAX_REPLICAS 4096
 int tdgl_ensemble_create(tdgl_ensemble **out, tdgl_ctx *ctx, int32_t n_replicas);
@@ -750,6 +752,23 @@ int tdgl_ensemble_set_epsilon(tdgl_ensemble *ens, int32_t r, const double *epsil
 int tdgl_ensemble_set_state(tdgl_ensemble *ens, int32_t r, const double *psi, const double *mu);
 int tdgl_ensemble_set_controller(tdgl_ensemble *ens, int32_t r, const tdgl_controller *c);
 int tdgl_ensemble_begin_stage(tdgl_ensemble *ens, int32_t r);
+/* Time dependence of replica r, with the rules of the context's entry point of the same name.  A failed call leaves
+ * the replica's previous tables untouched (a failed set_link_ramp leaves it without links).
+ * set_link_ramp: A(t) = LinearRamp(tmin, tmax, initial, final)(t) * A_base [n_edges, 2]; sets the links to their
+ *   value at t = 0 and moves them before the first attempt of every step inside tdgl_ensemble_run (dA/dt with the
+ *   previous step's dt, the link variables only where A moved beyond np.allclose's tolerance).
+ *   tdgl_ensemble_set_link_exponents switches the ramp off.  get_link_scale: the factor of the last step taken.
+ * set_mu_boundary_table: terminal current densities as piecewise-linear tables (tdgl_set_mu_boundary_table);
+ *   n_nodes may differ between replicas; n_nodes = 0: off.
+ * set_epsilon_table: epsilon(r, t) = factor(t) epsilon0(r) (tdgl_set_epsilon_table); n_nodes = 0: off. */
+int tdgl_ensemble_set_link_ramp(tdgl_ensemble *ens, int32_t r, const double *A_base, double tmin, double tmax,
+                                double initial, double final_);
+int tdgl_ensemble_get_link_scale(tdgl_ensemble *ens, int32_t r, double *scale);
+int tdgl_ensemble_set_mu_boundary_table(tdgl_ensemble *ens, int32_t r, int32_t n_nodes, const double *times,
+                                        int32_t n_groups, const int32_t *group_ptr, const int32_t *group_pos,
+                                        const double *density);
+int tdgl_ensemble_set_epsilon_table(tdgl_ensemble *ens, int32_t r, const double *epsilon0, int32_t n_nodes,
+                                    const double *times, const double *factor);
 /* The same probe sites for every replica. */
 int tdgl_ensemble_set_probes(tdgl_ensemble *ens, const int32_t *sites, int32_t n_probe);
 int tdgl_ensemble_get_loop_state(tdgl_ensemble *ens, int32_t r, int64_t *step, double *time, double *runner_dt,
@@ -761,7 +780,8 @@ int tdgl_ensemble_get_loop_state(tdgl_ensemble *ens, int32_t r, int64_t *step, d
 int tdgl_ensemble_run(tdgl_ensemble *ens, const int64_t *max_steps, const double *end_time, int64_t capacity,
                       double *out_dt, double *out_mu_probe, double *out_theta_probe, int64_t *steps_done,
                       int32_t *reached_end, int32_t *failed);
-/* psi, mu of replica r and J_s, J_n formed from them (any may be NULL), reference order. */
+/* psi, mu of replica r and J_s, J_n formed from them (any may be NULL), reference order; J_n with the dA/dt of the
+ * replica's last step. */
 int tdgl_ensemble_get_state(tdgl_ensemble *ens, int32_t r, double *psi, double *mu, double *supercurrent,
                             double *normal_current);
 /* Rounds queued and host synchronisations since the ensemble was created. */

@@ -198,6 +198,128 @@ __global__ void k_ens_probes(int n_probe, const int32_t *__restrict__ sites, con
     out[n_probe + k] = atan2(p.y, p.x);
 }
 
+// ---- time-dependent inputs per replica, queued in front of K1 (run.inc's run-ahead loop, the replica as grid.y) ----
+// A replica's field ramp A(t) = LinearRamp(t) A_base moves in three launches over the ramping replicas -- R1 ramp
+// begin (ramp_begin_body), R2 A, A_prev, dA/dt and "did it move" (ramp_link_body), R3 ceff with the dA/dt term and
+// the link variables (ceff_body, link_variable_body) -- and two more rebuild what depends on the links: R4 the
+// covariant-Laplacian values (fill_laplacian_body) and R5 L psi^n with them (psi_laplacian_body).  Retries, dead
+// replicas and replicas whose ramp does not move this step return at once (ramp_do, moved).  Tabulated terminal
+// currents (T1, mu_table_body: one workgroup per replica) and separable epsilon (T2, eps_table_body) are evaluated at
+// the replica's own time.  Every body is the single run's, so each replica's arithmetic is its run-ahead loop's.
+
+// R1: one thread per replica (a replica that is not ramping in this batch: ramp_do = 0, as the single run that
+// queues no ramp launch at all)
+__global__ void k_ens_ramp_begin(int R, StepCtl *__restrict__ ctl, const int32_t *__restrict__ ramping, int32_t *__restrict__ moved) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    if (ramping[r])
+        ramp_begin_body(ctl + r);
+    else
+        ctl[r].ramp_do = 0;
+    moved[r] = 0;
+}
+
+// R2: moved[r] = OR over the replica's workgroups (k_ra_ramp_links + k_any_flag)
+__global__ __launch_bounds__(BLOCK) void k_ens_ramp_links(int64_t m, int64_t m_pad, const double *__restrict__ base, double *__restrict__ A,
+                                                          double *__restrict__ Aprev, const double *__restrict__ dx,
+                                                          const double *__restrict__ dy, const double *__restrict__ inv_len,
+                                                          double *__restrict__ dadt, int32_t *__restrict__ moved,
+                                                          const StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    const StepCtl *c = ctl + r;
+    if (!c->ramp_do) return;
+    const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x, o2 = 2 * (int64_t)r * m_pad;
+    const int changed = e < m ? ramp_link_body(e, m, c->link_scale, 1.0 / c->runner_dt, base + o2, A + o2, Aprev + o2, dx, dy, inv_len,
+                                               dadt + (int64_t)r * m_pad)
+                              : 0;
+    const int any = __syncthreads_or(changed);
+    if (threadIdx.x == 0 && any) atomicOr(moved + r, 1);
+}
+
+// R3: workgroups [0, nblk_ceff): ceff = cvec + div dA/dt (k_ceff); the rest: the link variables where A moved
+// (k_link_variables)
+__global__ __launch_bounds__(BLOCK) void k_ens_ceff_links(int nblk_ceff, int n_slices, int64_t n_rows, const int32_t *__restrict__ slice_off,
+                                                          const int32_t *__restrict__ slot_edge, const double *__restrict__ slot_w,
+                                                          const double *__restrict__ inv_len, const double *__restrict__ dadt,
+                                                          const double *__restrict__ cvec, double *__restrict__ ceff, int64_t n_pad,
+                                                          int64_t m, int64_t m_pad, const double *__restrict__ A, const double *__restrict__ dx,
+                                                          const double *__restrict__ dy, double2 *__restrict__ U,
+                                                          const int32_t *__restrict__ moved, const StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    if (!ctl[r].ramp_do) return;
+    if ((int)blockIdx.x < nblk_ceff) {
+        const int slice = blockIdx.x * (BLOCK / WAVE) + threadIdx.x / WAVE;
+        if (slice >= n_slices) return;
+        const int lane = threadIdx.x & (WAVE - 1);
+        const int64_t row = (int64_t)slice * WAVE + lane;
+        if (row >= n_rows) return;
+        const int64_t o = (int64_t)r * n_pad;
+        ceff_body(slice, lane, row, slice_off, slot_edge, slot_w, inv_len, dadt + (int64_t)r * m_pad, cvec + o, ceff + o);
+        return;
+    }
+    if (!moved[r]) return;
+    const int64_t e = (blockIdx.x - nblk_ceff) * (int64_t)BLOCK + threadIdx.x;
+    if (e < m) link_variable_body(e, A + 2 * (int64_t)r * m_pad, nullptr, dx, dy, U + (int64_t)r * m_pad);
+}
+
+// R4: covariant-Laplacian values of the replicas whose links moved (k_fill_laplacian)
+__global__ __launch_bounds__(BLOCK) void k_ens_fill_laplacian(int64_t n_slots, const int32_t *__restrict__ slot_edge,
+                                                              const double *__restrict__ slot_w, const double2 *__restrict__ U,
+                                                              int64_t m_pad, double2 *__restrict__ vals, const int32_t *__restrict__ moved) {
+    const int r = blockIdx.y;
+    const int64_t s = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+    if (s >= n_slots || !moved[r]) return;
+    fill_laplacian_body(s, slot_edge, slot_w, U + (int64_t)r * m_pad, vals + (int64_t)r * n_slots);
+}
+
+// R5: L psi^n with the links of this step (k_psi_laplacian_ra_fresh)
+template <class IT>
+__global__ __launch_bounds__(BLOCK) void k_ens_laplacian_fresh(int n_slices, int per_xcd, int64_t n_rows, const int32_t *__restrict__ slice_off,
+                                                               const IT *__restrict__ cols, const double2 *__restrict__ vals, int64_t n_slots,
+                                                               const double *__restrict__ diag, const uint8_t *__restrict__ fixed,
+                                                               const double2 *__restrict__ psi0, const double2 *__restrict__ psi1,
+                                                               double2 *__restrict__ lap0, double2 *__restrict__ lap1, int64_t n_pad,
+                                                               const StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    const StepCtl *c = ctl + r;
+    if (!c->ramp_do) return;
+    const bool c1 = c->cur != 0;
+    const int64_t o = (int64_t)r * n_pad;
+    psi_laplacian_body<false, IT>(n_slices, per_xcd, 0, n_rows, slice_off, cols, vals + (int64_t)r * n_slots, diag, fixed,
+                                  (c1 ? psi1 : psi0) + o, (c1 ? lap1 : lap0) + o, nullptr, nullptr, nullptr);
+}
+
+// T1: replica r's current table (nodes t_off[r] .. t_off[r + 1] of the pool, densities from d_off[r]) at its time
+// (k_ra_mu_table); replicas without a table and dead replicas return
+__global__ __launch_bounds__(BLOCK) void k_ens_mu_table(int nb, int n_sites, const int32_t *__restrict__ b_sites,
+                                                        const int32_t *__restrict__ s0, const int32_t *__restrict__ s1,
+                                                        const double *__restrict__ c0, const double *__restrict__ c1,
+                                                        double *__restrict__ mu_b, double *__restrict__ cvec, double *__restrict__ ceff,
+                                                        int64_t n_pad, const int32_t *__restrict__ t_off, const int64_t *__restrict__ d_off,
+                                                        const double *__restrict__ times, const double *__restrict__ dens,
+                                                        const int32_t *__restrict__ group, const StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    const StepCtl *c = ctl + r;
+    const int t0 = t_off[r], nn = t_off[r + 1] - t0;
+    if (nn == 0 || c->poisoned) return;
+    const int64_t o = (int64_t)r * n_pad;
+    mu_table_body(nb, n_sites, b_sites, s0, s1, c0, c1, mu_b + (int64_t)r * nb, cvec + o, ceff + o, nn, times + t0, dens + d_off[r],
+                  group + (int64_t)r * nb, c->time);
+}
+
+// T2: epsilon = factor_r(t) epsilon0_r (k_ra_eps_table); nodes e_off[r] .. e_off[r + 1] of the pools
+__global__ __launch_bounds__(BLOCK) void k_ens_eps_table(int64_t n_pad, const double *__restrict__ eps0, double *__restrict__ eps,
+                                                         const int32_t *__restrict__ e_off, const double *__restrict__ times,
+                                                         const double *__restrict__ factor, const StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    const StepCtl *c = ctl + r;
+    const int t0 = e_off[r], nn = e_off[r + 1] - t0;
+    const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+    if (nn == 0 || c->poisoned || i >= n_pad) return;
+    const int64_t o = (int64_t)r * n_pad;
+    eps_table_body(i, eps0 + o, eps + o, nn, times + t0, factor + t0, c->time);
+}
+
 }  // namespace tdgl
 
 struct EnsReplica {
@@ -207,6 +329,12 @@ struct EnsReplica {
     int64_t stage_step = 0;
     int cur = 0, retries = 0;
     std::vector<double> hist;  // d_psi_sq_vals (solver.py:318, 701), bounded like the context's
+    // field ramp A(t) = LinearRamp(t) A_base (tdgl_ensemble_set_link_ramp): the host's mirror of the device's
+    bool ramp_on = false, has_dadt = false;
+    double ramp_tmin = 0.0, ramp_tmax = 0.0, ramp_initial = 0.0, ramp_final = 0.0, link_scale = 0.0, link_scale_prev = 0.0;
+    // tabulated terminal currents / separable epsilon (empty: none)
+    std::vector<double> mu_t, mu_dens, eps_t, eps_f;
+    std::vector<int32_t> mu_group;  // [nb]: table row of each boundary position, -1 where no table applies
 };
 
 struct tdgl_ensemble {
@@ -219,6 +347,14 @@ struct tdgl_ensemble {
     DevBuf<int32_t> fail_part, limit, d_probes;
     DevBuf<StepCtl> d_ctl;
     DevBuf<StepRec> d_rec;
+    // time-dependent inputs (allocated when the first replica asks): per replica A_base, A, A_prev (2 m_pad), dA/dt
+    // (m_pad), the boundary term before dA/dt (n_pad), mu_boundary (nb), epsilon0 (n_pad); the tables as pools
+    DevBuf<double> Abase, A, Aprev, dadt, cvec, mu_b, eps0;
+    DevBuf<double> tab_mu_t, tab_mu_dens, tab_eps_t, tab_eps_f;
+    DevBuf<int32_t> tab_mu_toff, tab_mu_group, tab_eps_off, ramping, moved;
+    DevBuf<int64_t> tab_mu_doff;
+    bool tables_dirty = false, any_mu_table = false, any_eps_table = false;
+    std::vector<int32_t> h_ramping;
     std::vector<StepCtl> h_ctl;
     std::vector<StepRec> h_rec;
     std::vector<double> h_probe;
@@ -277,6 +413,10 @@ extern "C" int tdgl_ensemble_create(tdgl_ensemble **out, tdgl_ctx *ctx, int32_t 
     HIP_TRY(ctx, e->limit.alloc(R));
     HIP_TRY(ctx, e->d_ctl.alloc(R));
     HIP_TRY(ctx, e->d_rec.alloc(R * RA_BATCH_MAX));
+    HIP_TRY(ctx, e->cvec.alloc(R * e->n_pad));
+    HIP_TRY(ctx, e->ramping.alloc(R));
+    HIP_TRY(ctx, e->moved.alloc(R));
+    e->h_ramping.assign(R, 0);
     e->h_ctl.resize(R);
     e->h_rec.resize(R * RA_BATCH_MAX);
     e->h_limit.resize(R);
@@ -306,6 +446,147 @@ extern "C" int tdgl_ensemble_set_link_exponents(tdgl_ensemble *e, int32_t r, con
     TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
     e->rep[r].have_links = true;
     e->rep[r].lap_valid = false;
+    e->rep[r].ramp_on = e->rep[r].has_dadt = false;
+    return TDGL_OK;
+}
+
+// A(t) = LinearRamp(t) A_base for replica r (tdgl_set_link_exponents_base + tdgl_set_link_ramp of the context): the
+// links start at the ramp's value at t = 0 and move inside tdgl_ensemble_run
+extern "C" int tdgl_ensemble_set_link_ramp(tdgl_ensemble *e, int32_t r, const double *A_base, double tmin, double tmax, double initial,
+                                           double final_) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    if (!A_base) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_ramp: null A_base");
+    if (!(std::isfinite(tmin) && std::isfinite(tmax) && std::isfinite(initial) && std::isfinite(final_)))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_ramp: the ramp's parameters must be finite");
+    if (!(tmax > tmin)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_ramp: tmax must be > tmin");
+    EnsReplica &p = e->rep[r];
+    const size_t R = (size_t)e->R;
+    if (e->Abase.n == 0) {
+        DevBuf<double> base, a, prev, dadt;
+        HIP_TRY(ctx, base.alloc(R * 2 * e->m_pad));
+        HIP_TRY(ctx, a.alloc(R * 2 * e->m_pad));
+        HIP_TRY(ctx, prev.alloc(R * 2 * e->m_pad));
+        HIP_TRY(ctx, dadt.alloc(R * e->m_pad));
+        e->Abase.take(base);
+        e->A.take(a);
+        e->Aprev.take(prev);
+        e->dadt.take(dadt);
+    }
+    p.have_links = false;  // (until the replica's arrays are complete)
+    p.ramp_on = false;
+    const double scale = linear_ramp_value(0.0, tmin, tmax, initial, final_);
+    TDGL_TRY(tdgl_set_link_exponents_base(ctx, A_base, scale));  // (A = scale A_base, A_prev = A, links, Laplacian values)
+    const int64_t o2 = 2 * (int64_t)r * e->m_pad;
+    TDGL_TRY(ens_copy(ctx, e->Abase.p + o2, ctx->e_Abase.p, 2 * e->m_pad));
+    TDGL_TRY(ens_copy(ctx, e->A.p + o2, ctx->e_A.p, 2 * e->m_pad));
+    TDGL_TRY(ens_copy(ctx, e->Aprev.p + o2, ctx->e_Aprev.p, 2 * e->m_pad));
+    HIP_TRY(ctx, hipMemset(e->dadt.p + r * e->m_pad, 0, e->m_pad * sizeof(double)));
+    TDGL_TRY(ens_copy(ctx, e->U.p + r * e->m_pad, ctx->e_U.p, e->m_pad));
+    TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
+    p.ramp_on = true;
+    p.has_dadt = false;
+    p.ramp_tmin = tmin, p.ramp_tmax = tmax, p.ramp_initial = initial, p.ramp_final = final_;
+    p.link_scale = p.link_scale_prev = scale;
+    p.have_links = true;
+    p.lap_valid = false;
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_get_link_scale(tdgl_ensemble *e, int32_t r, double *scale) {
+    TDGL_TRY(ens_check(e, r));
+    if (!scale) TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_link_scale: null scale");
+    *scale = e->rep[r].link_scale;
+    return TDGL_OK;
+}
+
+// replica r's terminal currents as tables (tdgl_set_mu_boundary_table's arguments and rules); n_nodes = 0: off
+extern "C" int tdgl_ensemble_set_mu_boundary_table(tdgl_ensemble *e, int32_t r, int32_t n_nodes, const double *times, int32_t n_groups,
+                                                   const int32_t *group_ptr, const int32_t *group_pos, const double *density) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    EnsReplica &p = e->rep[r];
+    if (n_nodes != 0) {
+        if (n_nodes < 1 || n_groups < 1 || !times || !group_ptr || !group_pos || !density || !table_times_ok(times, n_nodes))
+            TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: bad table (times must increase strictly)");
+        if (group_ptr[0] != 0) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: group_ptr must start at 0");
+        for (int32_t g = 0; g < n_groups; ++g)
+            if (group_ptr[g + 1] < group_ptr[g]) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: group_ptr decreases");
+        for (int32_t k = 0; k < group_ptr[n_groups]; ++k)
+            if (group_pos[k] < 0 || group_pos[k] >= ctx->nb)
+                TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: boundary position %d out of range", group_pos[k]);
+        for (int64_t k = 0; k < (int64_t)n_groups * n_nodes; ++k)
+            if (!std::isfinite(density[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: non-finite density");
+        TDGL_TRY(ensure_boundary_sites(ctx));
+        if (e->mu_b.n == 0) HIP_TRY(ctx, e->mu_b.alloc((size_t)e->R * std::max<int64_t>(ctx->nb, 1)));
+        // solver.py:289, 323: mu_boundary and the densities start at 0; the table rewrites its positions
+        HIP_TRY(ctx, hipMemset(e->mu_b.p + (int64_t)r * ctx->nb, 0, ctx->nb * sizeof(double)));
+    }
+    p.mu_t.assign(times, times + n_nodes);
+    p.mu_dens.assign(density, density + (n_nodes ? (size_t)n_groups * n_nodes : 0));
+    p.mu_group.assign(n_nodes ? (size_t)ctx->nb : 0, -1);
+    for (int32_t g = 0; n_nodes && g < n_groups; ++g)
+        for (int32_t k = group_ptr[g]; k < group_ptr[g + 1]; ++k) p.mu_group[(size_t)group_pos[k]] = g;
+    e->tables_dirty = true;
+    return TDGL_OK;
+}
+
+// replica r's epsilon(r, t) = factor(t) epsilon0(r) (tdgl_set_epsilon_table's arguments and rules); n_nodes = 0: off
+extern "C" int tdgl_ensemble_set_epsilon_table(tdgl_ensemble *e, int32_t r, const double *epsilon0, int32_t n_nodes, const double *times,
+                                               const double *factor) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    EnsReplica &p = e->rep[r];
+    if (n_nodes != 0) {
+        if (n_nodes < 1 || !epsilon0 || !times || !factor || !table_times_ok(times, n_nodes))
+            TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_epsilon_table: bad table (times must increase strictly)");
+        for (int32_t k = 0; k < n_nodes; ++k)
+            if (!std::isfinite(factor[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_epsilon_table: non-finite factor");
+        if (e->eps0.n == 0) HIP_TRY(ctx, e->eps0.alloc((size_t)e->R * e->n_pad));
+        DevBuf<double> tmp;
+        HIP_TRY(ctx, tmp.alloc(e->n_pad));
+        TDGL_TRY(upload_sites(ctx, epsilon0, tmp));
+        TDGL_TRY(ens_copy(ctx, e->eps0.p + r * e->n_pad, tmp.p, e->n_pad));
+    }
+    p.eps_t.assign(times, times + n_nodes);
+    p.eps_f.assign(factor, factor + n_nodes);
+    e->tables_dirty = true;
+    return TDGL_OK;
+}
+
+// the replicas' tables as pools on the device
+static int ens_upload_tables(tdgl_ensemble *e) {
+    tdgl_ctx *ctx = e->ctx;
+    const int R = e->R;
+    const int64_t nb = std::max<int64_t>(ctx->nb, 1);
+    std::vector<int32_t> toff(R + 1, 0), eoff(R + 1, 0), group((size_t)R * nb, -1);
+    std::vector<int64_t> doff(R, 0);
+    std::vector<double> mt, md, et, ef;
+    e->any_mu_table = e->any_eps_table = false;
+    for (int r = 0; r < R; ++r) {
+        const EnsReplica &p = e->rep[r];
+        doff[r] = (int64_t)md.size();
+        mt.insert(mt.end(), p.mu_t.begin(), p.mu_t.end());
+        md.insert(md.end(), p.mu_dens.begin(), p.mu_dens.end());
+        if (!p.mu_group.empty()) std::copy(p.mu_group.begin(), p.mu_group.end(), group.begin() + (size_t)r * nb);
+        toff[r + 1] = (int32_t)mt.size();
+        et.insert(et.end(), p.eps_t.begin(), p.eps_t.end());
+        ef.insert(ef.end(), p.eps_f.begin(), p.eps_f.end());
+        eoff[r + 1] = (int32_t)et.size();
+        e->any_mu_table |= !p.mu_t.empty();
+        e->any_eps_table |= !p.eps_t.empty();
+    }
+    if (mt.empty()) mt.push_back(0.0), md.push_back(0.0);  // (never read: every replica's node count is 0)
+    if (et.empty()) et.push_back(0.0), ef.push_back(0.0);
+    HIP_TRY(ctx, e->tab_mu_toff.upload(toff));
+    HIP_TRY(ctx, e->tab_mu_doff.upload(doff));
+    HIP_TRY(ctx, e->tab_mu_group.upload(group));
+    HIP_TRY(ctx, e->tab_mu_t.upload(mt));
+    HIP_TRY(ctx, e->tab_mu_dens.upload(md));
+    HIP_TRY(ctx, e->tab_eps_off.upload(eoff));
+    HIP_TRY(ctx, e->tab_eps_t.upload(et));
+    HIP_TRY(ctx, e->tab_eps_f.upload(ef));
+    e->tables_dirty = false;
     return TDGL_OK;
 }
 
@@ -315,6 +596,7 @@ extern "C" int tdgl_ensemble_set_mu_boundary(tdgl_ensemble *e, int32_t r, const 
     if (ctx->has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary: the context's links are time dependent");
     TDGL_TRY(tdgl_set_mu_boundary(ctx, mu_boundary));  // (static links: the boundary term as the run-ahead loop reads it)
     TDGL_TRY(ens_copy(ctx, e->ceff.p + r * e->n_pad, ctx->ceff.p, e->n_pad));
+    TDGL_TRY(ens_copy(ctx, e->cvec.p + r * e->n_pad, ctx->cvec.p, e->n_pad));  // (a ramp adds its dA/dt term to this)
     return TDGL_OK;
 }
 
@@ -406,11 +688,18 @@ extern "C" int tdgl_ensemble_get_state(tdgl_ensemble *e, int32_t r, double *psi,
     TDGL_TRY(ens_copy(ctx, ctx->psi[ctx->cur].p, (p.cur ? e->psi1.p : e->psi0.p) + r * e->n_pad, e->n_pad));
     TDGL_TRY(ens_copy(ctx, ctx->mu.p, e->mu.p + r * e->n_pad, e->n_pad));
     TDGL_TRY(ens_copy(ctx, ctx->e_U.p, e->U.p + r * e->m_pad, e->m_pad));
+    // a ramping replica: J_n with its dA/dt -- that of the step that produced psi (the next step's ramp moves at the
+    // start of its first attempt, in the next tdgl_ensemble_run)
+    const bool dadt = p.ramp_on && p.has_dadt;
+    if (dadt) TDGL_TRY(ens_copy(ctx, ctx->e_dAdt.p, e->dadt.p + r * e->m_pad, e->m_pad));
     ctx->have_state = true;
     ctx->lap_valid = false;  // (the context's Laplacian values belong to whatever links it was last given)
     ctx->currents_valid = false;
     ctx->currents_deferred = false;
-    return tdgl_get_state(ctx, psi, mu, supercurrent, normal_current);
+    ctx->has_dadt = dadt;
+    const int status = tdgl_get_state(ctx, psi, mu, supercurrent, normal_current);
+    ctx->has_dadt = false;  // (the context's own links are static)
+    return status;
 }
 
 static void ens_launch_laplacian_cache(tdgl_ensemble *e, int r) {
@@ -432,9 +721,52 @@ static void ens_launch_laplacian_cache(tdgl_ensemble *e, int r) {
                            (const double *)nullptr, (double *)nullptr);
 }
 
-static void ens_queue_round(tdgl_ensemble *e) {
+// the time-dependent inputs of the round's attempts (T1, T2, R1 - R5), in the single run's order (run.inc: run_ahead)
+static void ens_queue_drives(tdgl_ensemble *e, bool ramping) {
     tdgl_ctx *ctx = e->ctx;
     const unsigned R = (unsigned)e->R;
+    if (e->any_mu_table)
+        hipLaunchKernelGGL(k_ens_mu_table, dim3(1, R), dim3(BLOCK), 0, ctx->stream, (int)ctx->nb, (int)ctx->n_b_sites,
+                           (const int32_t *)ctx->d_b_sites.p, (const int32_t *)ctx->b_s0.p, (const int32_t *)ctx->b_s1.p,
+                           (const double *)ctx->b_c0.p, (const double *)ctx->b_c1.p, e->mu_b.p, e->cvec.p, e->ceff.p, e->n_pad,
+                           (const int32_t *)e->tab_mu_toff.p, (const int64_t *)e->tab_mu_doff.p, (const double *)e->tab_mu_t.p,
+                           (const double *)e->tab_mu_dens.p, (const int32_t *)e->tab_mu_group.p, (const StepCtl *)e->d_ctl.p);
+    if (e->any_eps_table)
+        hipLaunchKernelGGL(k_ens_eps_table, dim3(grid_for(e->n_pad), R), dim3(BLOCK), 0, ctx->stream, e->n_pad, (const double *)e->eps0.p,
+                           e->eps.p, (const int32_t *)e->tab_eps_off.p, (const double *)e->tab_eps_t.p, (const double *)e->tab_eps_f.p,
+                           (const StepCtl *)e->d_ctl.p);
+    if (!ramping) return;
+    const SellPattern &pat = ctx->lap_pat;
+    hipLaunchKernelGGL(k_ens_ramp_begin, dim3((R + 63) / 64), dim3(64), 0, ctx->stream, (int)R, e->d_ctl.p, (const int32_t *)e->ramping.p,
+                       e->moved.p);
+    const int nblk = grid_for(ctx->m);
+    hipLaunchKernelGGL(k_ens_ramp_links, dim3(nblk, R), dim3(BLOCK), 0, ctx->stream, ctx->m, e->m_pad, (const double *)e->Abase.p, e->A.p,
+                       e->Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
+                       e->dadt.p, e->moved.p, (const StepCtl *)e->d_ctl.p);
+    const int nblk_ceff = grid_for((int64_t)pat.n_slices * WAVE);
+    hipLaunchKernelGGL(k_ens_ceff_links, dim3(nblk_ceff + nblk, R), dim3(BLOCK), 0, ctx->stream, nblk_ceff, pat.n_slices, pat.n_rows,
+                       (const int32_t *)pat.slice_off.p, (const int32_t *)ctx->lap_slot_edge.p, (const double *)ctx->lap_slot_w.p,
+                       (const double *)ctx->e_inv_len.p, (const double *)e->dadt.p, (const double *)e->cvec.p, e->ceff.p, e->n_pad, ctx->m,
+                       e->m_pad, (const double *)e->A.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, e->U.p,
+                       (const int32_t *)e->moved.p, (const StepCtl *)e->d_ctl.p);
+    hipLaunchKernelGGL(k_ens_fill_laplacian, dim3(grid_for(pat.n_slots), R), dim3(BLOCK), 0, ctx->stream, pat.n_slots,
+                       (const int32_t *)ctx->lap_slot_edge.p, (const double *)ctx->lap_slot_w.p, (const double2 *)e->U.p, e->m_pad,
+                       e->lapv.p, (const int32_t *)e->moved.p);
+    const int tiles = (pat.n_slices + BLOCK / WAVE - 1) / (BLOCK / WAVE);
+    const int per_xcd = (tiles + XCDS - 1) / XCDS, grid = per_xcd * XCDS;
+#define TDGL_KENS(IT, COLS)                                                                                                      \
+    hipLaunchKernelGGL((k_ens_laplacian_fresh<IT>), dim3(grid, R), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, pat.n_rows, \
+                       pat.slice_off.p, COLS, (const double2 *)e->lapv.p, e->n_slots, ctx->lap_diag.p, ctx->fixed_mask.p,        \
+                       (const double2 *)e->psi0.p, (const double2 *)e->psi1.p, e->lap0.p, e->lap1.p, e->n_pad,                  \
+                       (const StepCtl *)e->d_ctl.p)
+    if (pat.use16) TDGL_KENS(int16_t, pat.cols16.p); else TDGL_KENS(int32_t, pat.cols.p);
+#undef TDGL_KENS
+}
+
+static void ens_queue_round(tdgl_ensemble *e, bool ramping) {
+    tdgl_ctx *ctx = e->ctx;
+    const unsigned R = (unsigned)e->R;
+    ens_queue_drives(e, ramping);
     hipLaunchKernelGGL(k_ens_psi_update, dim3(ctx->psi_blocks, R), dim3(BLOCK), 0, ctx->stream, ctx->n_own, e->n_pad, e->psi0.p, e->psi1.p,
                        (const double2 *)e->lap0.p, (const double2 *)e->lap1.p, (const double *)e->mu.p, (const double *)e->eps.p, ctx->u,
                        ctx->gamma, e->dmax_part.p, e->fail_part.p, e->d_ctl.p);
@@ -486,6 +818,7 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
         reached_end[r] = 0;
         if (failed) failed[r] = 0;
     }
+    if (e->tables_dirty) TDGL_TRY(ens_upload_tables(e));
     for (int r = 0; r < R; ++r)
         if (!e->rep[r].lap_valid && max_steps[r] > 0) {
             ens_launch_laplacian_cache(e, r);
@@ -496,11 +829,17 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
     double err_dt = 0.0;
     int64_t err_step = 0;
     for (;;) {
-        int active = 0;
+        int active = 0, n_ramping = 0;
         for (int r = 0; r < R; ++r) {
-            const EnsReplica &p = e->rep[r];
+            EnsReplica &p = e->rep[r];
             const bool on = !reached_end[r] && steps_done[r] < max_steps[r];
             active += on;
+            // a ramp that has reached its end: dA/dt is identically zero from here on, and a replica whose ramp has
+            // settled costs what a static one does (run.inc: tdgl_run, ramp_settled)
+            const bool settled = p.ramp_on && p.time >= p.ramp_tmax && p.link_scale == p.ramp_final && p.link_scale_prev == p.ramp_final;
+            if (settled) p.has_dadt = false;
+            e->h_ramping[r] = on && p.ramp_on && !settled;
+            n_ramping += e->h_ramping[r];
             StepCtl &h = e->h_ctl[r];
             memset(&h, 0, sizeof(h));
             h.tentative_dt = p.tentative_dt;
@@ -518,6 +857,9 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
             h.retries = p.retries;
             h.poisoned = on ? 0 : 1;
             h.runner_dt = p.runner_dt;
+            h.ramp_tmin = p.ramp_tmin, h.ramp_tmax = p.ramp_tmax, h.ramp_initial = p.ramp_initial, h.ramp_final = p.ramp_final;
+            h.link_scale = p.link_scale, h.link_scale_prev = p.link_scale_prev;
+            h.has_dadt = p.has_dadt ? 1 : 0;
             if (p.ctl.adaptive) {
                 const int64_t have = (int64_t)p.hist.size(), cnt = std::min<int64_t>(have, p.ctl.adaptive_window);
                 h.hist_count = (int)cnt;
@@ -529,7 +871,9 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
         const int batch = std::min(e->batch, RA_BATCH_MAX);
         HIP_TRY(ctx, hipMemcpyAsync(e->d_ctl.p, e->h_ctl.data(), (size_t)R * sizeof(StepCtl), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(e->limit.p, e->h_limit.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        for (int s = 0; s < batch; ++s) ens_queue_round(e);
+        if (n_ramping > 0)
+            HIP_TRY(ctx, hipMemcpyAsync(e->ramping.p, e->h_ramping.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        for (int s = 0; s < batch; ++s) ens_queue_round(e, n_ramping > 0);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(e->h_ctl.data(), e->d_ctl.p, (size_t)R * sizeof(StepCtl), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(e->h_rec.data(), e->d_rec.p, (size_t)R * RA_BATCH_MAX * sizeof(StepRec), hipMemcpyDeviceToHost, ctx->stream));
@@ -570,6 +914,11 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
             if (acc > 0) {
                 const int last = reached ? acc - 2 : acc - 1;  // (Runner.dt is not touched by the step that reached end_time)
                 if (last >= 0) p.runner_dt = dts[last];
+            }
+            if (e->h_ramping[r]) {
+                p.link_scale = h.link_scale;
+                p.link_scale_prev = h.link_scale_prev;
+                p.has_dadt = h.has_dadt != 0;
             }
             p.cur = h.cur;
             p.retries = h.error ? 0 : h.retries;

@@ -62,14 +62,9 @@ __device__ __forceinline__ double block_max(double v) {
 // ------------------------------------------------------------------ link variables
 // U_e = exp(-i A_e . d_e)   (operators.py:109-111, 153-155)
 // (A2, if given, is added: applied + induced vector potential, solver.py:673)
-__global__ __launch_bounds__(BLOCK) void k_link_variables(int64_t m, const double *__restrict__ A,
-                                                          const double *__restrict__ A2,
-                                                          const double *__restrict__ dx,
-                                                          const double *__restrict__ dy,
-                                                          double2 *__restrict__ U,
-                                                          const int32_t *__restrict__ only_if) {
-    int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-    if (e >= m || (only_if && !only_if[0])) return;
+__device__ __forceinline__ void link_variable_body(int64_t e, const double *__restrict__ A, const double *__restrict__ A2,
+                                                   const double *__restrict__ dx, const double *__restrict__ dy,
+                                                   double2 *__restrict__ U) {
     double ax = A[2 * e], ay = A[2 * e + 1];
     if (A2) {
         ax += A2[2 * e];
@@ -79,6 +74,17 @@ __global__ __launch_bounds__(BLOCK) void k_link_variables(int64_t m, const doubl
     double s, c;
     sincos(theta, &s, &c);
     U[e] = make_double2(c, -s);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_link_variables(int64_t m, const double *__restrict__ A,
+                                                          const double *__restrict__ A2,
+                                                          const double *__restrict__ dx,
+                                                          const double *__restrict__ dy,
+                                                          double2 *__restrict__ U,
+                                                          const int32_t *__restrict__ only_if) {
+    int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+    if (e >= m || (only_if && !only_if[0])) return;
+    link_variable_body(e, A, A2, dx, dy, U);
 }
 
 // A = scale * A_base (a time-dependent factor times a static field: sources/scaling.py ramps)
@@ -129,19 +135,11 @@ __global__ __launch_bounds__(BLOCK) void k_any_flag(int n, const int32_t *__rest
 
 // ceff = cvec + divergence(dA/dt)  (operators.py:59-84 applied to the edge field dA/dt), gathered
 // over the row's incident edges through the SELL slots of the site graph.
-__global__ __launch_bounds__(BLOCK) void k_ceff(int n_slices, int64_t n_rows, const int32_t *__restrict__ slice_off,
-                                                const int32_t *__restrict__ slot_edge,
-                                                const double *__restrict__ slot_w,
-                                                const double *__restrict__ inv_len,
-                                                const double *__restrict__ dadt,
-                                                const double *__restrict__ cvec, double *__restrict__ ceff,
-                                                const int32_t *__restrict__ only_if = nullptr) {
-    if (only_if && !*only_if) return;
-    const int slice = blockIdx.x * (BLOCK / WAVE) + threadIdx.x / WAVE;
-    if (slice >= n_slices) return;
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int64_t row = (int64_t)slice * WAVE + lane;
-    if (row >= n_rows) return;
+// (body: one row of `slice`; the row must be < n_rows)
+__device__ __forceinline__ void ceff_body(int slice, int lane, int64_t row, const int32_t *__restrict__ slice_off,
+                                          const int32_t *__restrict__ slot_edge, const double *__restrict__ slot_w,
+                                          const double *__restrict__ inv_len, const double *__restrict__ dadt,
+                                          const double *__restrict__ cvec, double *__restrict__ ceff) {
     double acc = 0.0;
     if (dadt) {
         int64_t idx = (int64_t)slice_off[slice] * WAVE + lane;
@@ -156,16 +154,27 @@ __global__ __launch_bounds__(BLOCK) void k_ceff(int n_slices, int64_t n_rows, co
     ceff[row] = (cvec ? cvec[row] : 0.0) + acc;
 }
 
+__global__ __launch_bounds__(BLOCK) void k_ceff(int n_slices, int64_t n_rows, const int32_t *__restrict__ slice_off,
+                                                const int32_t *__restrict__ slot_edge,
+                                                const double *__restrict__ slot_w,
+                                                const double *__restrict__ inv_len,
+                                                const double *__restrict__ dadt,
+                                                const double *__restrict__ cvec, double *__restrict__ ceff,
+                                                const int32_t *__restrict__ only_if = nullptr) {
+    if (only_if && !*only_if) return;
+    const int slice = blockIdx.x * (BLOCK / WAVE) + threadIdx.x / WAVE;
+    if (slice >= n_slices) return;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t row = (int64_t)slice * WAVE + lane;
+    if (row >= n_rows) return;
+    ceff_body(slice, lane, row, slice_off, slot_edge, slot_w, inv_len, dadt, cvec, ceff);
+}
+
 // Covariant-Laplacian values per SELL slot: (w_e / a_i) * U_e for the edge's own
 // orientation, conj(U_e) for the reversed one (operators.py:162-168).
-__global__ __launch_bounds__(BLOCK) void k_fill_laplacian(int64_t n_slots,
-                                                          const int32_t *__restrict__ slot_edge,
-                                                          const double *__restrict__ slot_w,
-                                                          const double2 *__restrict__ U,
-                                                          double2 *__restrict__ vals,
-                                                          const int32_t *__restrict__ only_if) {
-    int64_t s = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-    if (s >= n_slots || (only_if && !only_if[0])) return;
+__device__ __forceinline__ void fill_laplacian_body(int64_t s, const int32_t *__restrict__ slot_edge,
+                                                    const double *__restrict__ slot_w, const double2 *__restrict__ U,
+                                                    double2 *__restrict__ vals) {
     int32_t code = slot_edge[s];
     double2 v = make_double2(0.0, 0.0);
     if (code >= 0) {
@@ -174,6 +183,17 @@ __global__ __launch_bounds__(BLOCK) void k_fill_laplacian(int64_t n_slots,
         v = make_double2(w * u.x, (code & 1) ? -(w * u.y) : w * u.y);
     }
     vals[s] = v;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_fill_laplacian(int64_t n_slots,
+                                                          const int32_t *__restrict__ slot_edge,
+                                                          const double *__restrict__ slot_w,
+                                                          const double2 *__restrict__ U,
+                                                          double2 *__restrict__ vals,
+                                                          const int32_t *__restrict__ only_if) {
+    int64_t s = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+    if (s >= n_slots || (only_if && !only_if[0])) return;
+    fill_laplacian_body(s, slot_edge, slot_w, U, vals);
 }
 
 constexpr int SELL_BATCH = 8;
@@ -421,9 +441,9 @@ __host__ __device__ inline double linear_ramp_value(double t, double tmin, doubl
     return final_;
 }
 
-__global__ void k_ra_ramp_begin(StepCtl *__restrict__ ctl) {
+// (body: one thread per controller)
+__device__ __forceinline__ void ramp_begin_body(StepCtl *__restrict__ ctl) {
 #pragma clang fp contract(off)
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int go = 0;
     if (!ctl->poisoned && ctl->retries == 0) {
         const double scale = linear_ramp_value(ctl->time, ctl->ramp_tmin, ctl->ramp_tmax, ctl->ramp_initial, ctl->ramp_final);
@@ -438,25 +458,34 @@ __global__ void k_ra_ramp_begin(StepCtl *__restrict__ ctl) {
     ctl->ramp_do = go;
 }
 
-// A = scale A_base, dA/dt along the edge with the previous accepted step's dt, A_prev <- A, "did it move" per workgroup
+__global__ void k_ra_ramp_begin(StepCtl *__restrict__ ctl) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    ramp_begin_body(ctl);
+}
+
+// A = scale A_base, dA/dt along the edge with the previous accepted step's dt, A_prev <- A; 1 if the edge moved
+__device__ __forceinline__ int ramp_link_body(int64_t e, int64_t m, double scale, double inv_dt, const double *__restrict__ base,
+                                              double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
+                                              const double *__restrict__ dy, const double *__restrict__ inv_len,
+                                              double *__restrict__ dadt) {
+    // (rounded products, as k_scale_links stores them: the empty asm keeps the compiler from contracting them
+    // into the difference A - A_prev that dadt_body forms -- __dmul_rn is a plain product to it)
+    double ax = scale * base[2 * e], ay = scale * base[2 * e + 1];
+    asm volatile("" : "+v"(ax), "+v"(ay));
+    A[2 * e] = ax;
+    A[2 * e + 1] = ay;
+    return dadt_body(e, m, inv_dt, ax, ay, Aprev, dx, dy, inv_len, dadt);
+}
+
+// ... per workgroup: "did it move"
 __global__ __launch_bounds__(BLOCK) void k_ra_ramp_links(int64_t m, const double *__restrict__ base, double *__restrict__ A,
                                                          double *__restrict__ Aprev, const double *__restrict__ dx,
                                                          const double *__restrict__ dy, const double *__restrict__ inv_len,
                                                          double *__restrict__ dadt, int32_t *__restrict__ block_changed,
                                                          const StepCtl *__restrict__ ctl) {
     if (!ctl->ramp_do) return;
-    const double scale = ctl->link_scale, inv_dt = 1.0 / ctl->runner_dt;
     const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-    int changed = 0;
-    if (e < m) {
-        // (rounded products, as k_scale_links stores them: the empty asm keeps the compiler from contracting them
-        // into the difference A - A_prev that dadt_body forms -- __dmul_rn is a plain product to it)
-        double ax = scale * base[2 * e], ay = scale * base[2 * e + 1];
-        asm volatile("" : "+v"(ax), "+v"(ay));
-        A[2 * e] = ax;
-        A[2 * e + 1] = ay;
-        changed = dadt_body(e, m, inv_dt, ax, ay, Aprev, dx, dy, inv_len, dadt);
-    }
+    const int changed = e < m ? ramp_link_body(e, m, ctl->link_scale, 1.0 / ctl->runner_dt, base, A, Aprev, dx, dy, inv_len, dadt) : 0;
     const int any = __syncthreads_or(changed);
     if (threadIdx.x == 0) block_changed[blockIdx.x] = any;
 }
@@ -599,15 +628,13 @@ __device__ __forceinline__ double table_value_dev(const double *__restrict__ tim
 // on the sites boundary edges touch (every such site receives exactly two contributions: the atomics commute) and
 // ceff = c (no dA/dt term in this loop).  Same arithmetic, operation for operation, as the host's table_value +
 // k_boundary_term + k_ceff: the run-ahead loop stays bit-identical to the loop with one synchronisation per step.
-__global__ __launch_bounds__(BLOCK) void k_ra_mu_table(int nb, int n_sites, const int32_t *__restrict__ b_sites,
-                                                       const int32_t *__restrict__ s0, const int32_t *__restrict__ s1,
-                                                       const double *__restrict__ c0, const double *__restrict__ c1,
-                                                       double *__restrict__ mu_b, double *__restrict__ cvec,
-                                                       double *__restrict__ ceff, int n_nodes,
-                                                       const double *__restrict__ times, const double *__restrict__ dens,
-                                                       const int32_t *__restrict__ group, const StepCtl *__restrict__ ctl) {
+// (body: one whole workgroup)
+__device__ __forceinline__ void mu_table_body(int nb, int n_sites, const int32_t *__restrict__ b_sites, const int32_t *__restrict__ s0,
+                                              const int32_t *__restrict__ s1, const double *__restrict__ c0,
+                                              const double *__restrict__ c1, double *__restrict__ mu_b, double *__restrict__ cvec,
+                                              double *__restrict__ ceff, int n_nodes, const double *__restrict__ times,
+                                              const double *__restrict__ dens, const int32_t *__restrict__ group, double time) {
 #pragma clang fp contract(off)
-    const double time = ctl->time;
     for (int k = threadIdx.x; k < nb; k += BLOCK) {
         const int g = group[k];
         if (g >= 0) mu_b[k] = table_value_dev(times, dens + (int64_t)g * n_nodes, n_nodes, time);
@@ -630,16 +657,31 @@ __global__ __launch_bounds__(BLOCK) void k_ra_mu_table(int nb, int n_sites, cons
     }
 }
 
+__global__ __launch_bounds__(BLOCK) void k_ra_mu_table(int nb, int n_sites, const int32_t *__restrict__ b_sites,
+                                                       const int32_t *__restrict__ s0, const int32_t *__restrict__ s1,
+                                                       const double *__restrict__ c0, const double *__restrict__ c1,
+                                                       double *__restrict__ mu_b, double *__restrict__ cvec,
+                                                       double *__restrict__ ceff, int n_nodes,
+                                                       const double *__restrict__ times, const double *__restrict__ dens,
+                                                       const int32_t *__restrict__ group, const StepCtl *__restrict__ ctl) {
+    mu_table_body(nb, n_sites, b_sites, s0, s1, c0, c1, mu_b, cvec, ceff, n_nodes, times, dens, group, ctl->time);
+}
+
 // ... and with a separable disorder parameter epsilon(r, t) = factor(t) * epsilon0(r) (update_epsilon,
 // solver.py:364-381): the host's table_value + k_scale_links at the device's time.
+__device__ __forceinline__ void eps_table_body(int64_t i, const double *__restrict__ eps0, double *__restrict__ eps, int n_nodes,
+                                               const double *__restrict__ times, const double *__restrict__ factor, double time) {
+#pragma clang fp contract(off)
+    const double f = table_value_dev(times, factor, n_nodes, time);
+    eps[i] = f * eps0[i];
+}
+
 __global__ __launch_bounds__(BLOCK) void k_ra_eps_table(int64_t n, const double *__restrict__ eps0, double *__restrict__ eps,
                                                         int n_nodes, const double *__restrict__ times,
                                                         const double *__restrict__ factor, const StepCtl *__restrict__ ctl) {
-#pragma clang fp contract(off)
     const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
     if (i >= n) return;
-    const double f = table_value_dev(times, factor, n_nodes, ctl->time);
-    eps[i] = f * eps0[i];
+    eps_table_body(i, eps0, eps, n_nodes, times, factor, ctl->time);
 }
 
 __global__ void k_probes(int n_probe, const int32_t *__restrict__ sites,

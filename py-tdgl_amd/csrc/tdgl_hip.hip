@@ -784,6 +784,20 @@ static bool table_times_ok(const double *times, int32_t n) {
     return true;
 }
 
+// the sites boundary edges touch, once (the table kernels rebuild the boundary term there)
+static int ensure_boundary_sites(tdgl_ctx *ctx) {
+    if (ctx->d_b_sites.n != 0) return TDGL_OK;
+    std::vector<int32_t> s0((size_t)ctx->nb), s1((size_t)ctx->nb);
+    HIP_TRY(ctx, hipMemcpy(s0.data(), ctx->b_s0.p, s0.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(s1.data(), ctx->b_s1.p, s1.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    s0.insert(s0.end(), s1.begin(), s1.end());
+    std::sort(s0.begin(), s0.end());
+    s0.erase(std::unique(s0.begin(), s0.end()), s0.end());
+    HIP_TRY(ctx, ctx->d_b_sites.upload(s0));
+    ctx->n_b_sites = (int32_t)s0.size();
+    return TDGL_OK;
+}
+
 extern "C" int tdgl_set_mu_boundary_table(tdgl_ctx *ctx, int32_t n_nodes, const double *times, int32_t n_groups,
                                           const int32_t *group_ptr, const int32_t *group_pos, const double *density) {
     CTX_GUARD(ctx);
@@ -811,16 +825,7 @@ extern "C" int tdgl_set_mu_boundary_table(tdgl_ctx *ctx, int32_t n_nodes, const 
         HIP_TRY(ctx, ctx->d_tab_mu_group.upload(group));
         HIP_TRY(ctx, ctx->d_tab_mu_t.upload(ctx->tab_mu_t));
         HIP_TRY(ctx, ctx->d_tab_mu_dens.upload(ctx->tab_mu_dens));
-        if (ctx->d_b_sites.n == 0) {
-            std::vector<int32_t> s0((size_t)ctx->nb), s1((size_t)ctx->nb);
-            HIP_TRY(ctx, hipMemcpy(s0.data(), ctx->b_s0.p, s0.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(ctx, hipMemcpy(s1.data(), ctx->b_s1.p, s1.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-            s0.insert(s0.end(), s1.begin(), s1.end());
-            std::sort(s0.begin(), s0.end());
-            s0.erase(std::unique(s0.begin(), s0.end()), s0.end());
-            HIP_TRY(ctx, ctx->d_b_sites.upload(s0));
-            ctx->n_b_sites = (int32_t)s0.size();
-        }
+        TDGL_TRY(ensure_boundary_sites(ctx));
         ctx->tab_mu_on_device = true;
     }
     return TDGL_OK;

@@ -4,8 +4,10 @@ realisations -- advanced together in one batched time loop on the GPU (``csrc/en
 Each replica is what ``tdgl.solve(device, options, ...)`` would run for its own inputs: same saved steps, dynamics,
 thermalisation, adaptive dt, retries and errors.  The replicas share the device, its mesh and the ``SolverOptions``;
 the mu solve is the dense pseudo-inverse of the Poisson matrix, applied to all replicas' right-hand sides in one
-pass over it.  Static inputs only: no screening, no time dependence, no ``output_file``, at most
-``ENSEMBLE_MAX_SITES`` sites.
+pass over it.  A replica may be time dependent in the three forms the device evaluates itself, each with its own
+parameters: a field ramp ``LinearRamp * (static field)``, ``TabulatedCurrents`` and a ``SeparableEpsilon``.  Not
+supported: other time-dependent inputs, a ramp combined with a table in one replica, screening, ``output_file``, more
+than ``ENSEMBLE_MAX_SITES`` sites.
 
 The per-replica set-up (vector potential, epsilon, terminal currents -> mu boundary values) is ``TDGLSolver``'s
 own, run without creating a device context (``_ReplicaInputs``).
@@ -69,12 +71,22 @@ def _refuse_options(options: SolverOptions, n_sites: int) -> None:
 
 
 def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
-    if rep.dynamic_vector_potential:
+    """Time dependence the ensemble evaluates on the device passes: a separable A whose factor is a LinearRamp,
+    TabulatedCurrents, a SeparableEpsilon.  Anything else raises."""
+    if rep.dynamic_vector_potential and rep._A_ramp is None:
+        if rep._A_base is not None:
+            raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
+                             "LinearRamp(...) * (static field); this one's time factor is not a LinearRamp.")
         raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is not supported.")
-    if rep.dynamic_currents:
-        raise ValueError(f"solve_ensemble: replica {r}: time-dependent terminal_currents are not supported.")
-    if rep.dynamic_epsilon or rep._eps_table is not None:
-        raise ValueError(f"solve_ensemble: replica {r}: a time-dependent disorder_epsilon is not supported.")
+    if rep.dynamic_currents and rep._current_table is None:
+        raise ValueError(f"solve_ensemble: replica {r}: time-dependent terminal_currents are not supported "
+                         "(TabulatedCurrents are).")
+    if rep.dynamic_epsilon and rep._eps_table is None:
+        raise ValueError(f"solve_ensemble: replica {r}: a time-dependent disorder_epsilon is not supported "
+                         "(SeparableEpsilon is).")
+    if rep._A_ramp is not None and (rep._current_table is not None or rep._eps_table is not None):
+        raise ValueError(f"solve_ensemble: replica {r}: a field ramp combined with TabulatedCurrents or a SeparableEpsilon "
+                         "in one replica is not supported.")
 
 
 def _check_seeds(device, mesh, seeds) -> None:
@@ -99,6 +111,11 @@ def solve_ensemble(
     """Solve R replicas of one device together; returns the R ``Solution`` objects ``tdgl.solve`` returns for each
     of them alone.  Every per-replica argument is a list of length R or one value for all replicas.
 
+    Time-dependent replicas: ``applied_vector_potential`` may be ``LinearRamp(...) * <static field>``,
+    ``terminal_currents`` a ``TabulatedCurrents``, ``disorder_epsilon`` a ``SeparableEpsilon`` (one kind of table or
+    ramp per replica, except that tabulated currents and a separable epsilon may go together).  Static, ramped and
+    tabulated replicas may share one ensemble.
+
     A replica that spends its retry budget raises ``RuntimeError`` with the reference's message, prefixed by the
     replica index; no solution is returned then (like ``tdgl.solve``)."""
     if device.mesh is None:
@@ -121,29 +138,78 @@ def solve_ensemble(
 
 def solve_ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
                                  gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
-                                 seed_states=None) -> List[Solution]:
+                                 seed_states=None, vector_potential_ramp=None, epsilon_table=None) -> List[Solution]:
     """``solve_ensemble`` from dimensionless inputs (``TDGLSolver.from_dimensionless``): ``link_exponents`` A[m, 2]
     (an array, or a list of them), ``epsilon`` (a scalar or an [n] array, or a list), ``currents``
-    ({terminal: dimensionless current}, or a list), ``seed_states`` (None or a list of (psi, mu) / None)."""
+    ({terminal: dimensionless current} or a ``TabulatedCurrents``, or a list), ``seed_states`` (None or a list of
+    (psi, mu) / None).  Time dependence, one value or a list with None for the replicas without:
+    ``vector_potential_ramp`` ``(A_base[m, 2], dict(tmin, tmax, initial, final))`` as in
+    ``TDGLSolver.from_dimensionless`` (the replica's ``link_exponents`` may then be None: the ramp's value at t = 0),
+    ``epsilon_table`` ``(epsilon0[n], times, factor)``: epsilon(t) = PiecewiseLinear(times, factor)(t) * epsilon0."""
     return ensemble_dimensionless(mesh, options, link_exponents, epsilon, u, gamma, terminal_info, currents, probe_points,
-                                  seed_states).solve()
+                                  seed_states, vector_potential_ramp, epsilon_table).solve()
+
+
+def _one_or_list(value, is_one):
+    """A tuple-valued per-replica argument: one value (``is_one``) stays as it is, a list is per replica."""
+    if value is None or is_one(value):
+        return _Same(value)
+    if not isinstance(value, list):
+        raise ValueError(f"solve_ensemble: expected one value or a list of them, got {type(value).__name__}")
+    return value
+
+
+class _Same:
+    """One value for every replica (broadcast_replicas would take a tuple for a per-replica list)."""
+
+    def __init__(self, value):
+        self.value = value
+
+
+def _with_epsilon_table(rep: TDGLSolver, table, n: int) -> None:
+    """epsilon(t) = PiecewiseLinear(times, factor)(t) * epsilon0 on a dimensionless replica: what the constructor does
+    for a SeparableEpsilon."""
+    from .parameter import PiecewiseLinear
+
+    eps0, times, factor = table
+    eps0 = np.asarray(eps0, dtype=float) * np.ones(n)
+    f = PiecewiseLinear(times, factor)
+    rep._eps_table = (eps0, f.times, f.values)
+    rep.epsilon_func = lambda t: f(t) * eps0  # noqa: E731
+    rep.dynamic_epsilon = True
+    rep.disorder_epsilon = eps0
+    rep.epsilon = rep.epsilon_func(0.0)
 
 
 def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
                            gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
-                           seed_states=None) -> "EnsembleSolver":
+                           seed_states=None, vector_potential_ramp=None, epsilon_table=None) -> "EnsembleSolver":
     """The `EnsembleSolver` behind `solve_ensemble_dimensionless` (its ``solve()`` returns the solutions)."""
     _refuse_options(options, len(mesh.sites))
     per = dict(link_exponents=link_exponents, currents=currents, seed_states=seed_states)
     if isinstance(epsilon, (list, tuple)):
         per["epsilon"] = epsilon
+    ramps = _one_or_list(vector_potential_ramp, lambda v: isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], dict))
+    tables = _one_or_list(epsilon_table, lambda v: isinstance(v, tuple) and len(v) == 3)
+    for name, v in (("vector_potential_ramp", ramps), ("epsilon_table", tables)):
+        if not isinstance(v, _Same):
+            per[name] = v
     R, args = broadcast_replicas(**per)
     eps = args.get("epsilon", [epsilon] * R)
+    ramps = args.get("vector_potential_ramp", [getattr(ramps, "value", None)] * R)
+    tables = args.get("epsilon_table", [getattr(tables, "value", None)] * R)
     reps = []
     for r in range(R):
-        rep = _ReplicaInputs.from_dimensionless(mesh, options, args["link_exponents"][r], eps[r], u, gamma,
+        A = args["link_exponents"][r]
+        if A is None and ramps[r] is not None:
+            from .parameter import LinearRamp
+
+            A = LinearRamp(**ramps[r][1]).scalar(0.0) * np.asarray(ramps[r][0], dtype=float)
+        rep = _ReplicaInputs.from_dimensionless(mesh, options, A, eps[r], u, gamma,
                                                 terminal_info=terminal_info, current_func=args["currents"][r],
-                                                probe_points=probe_points)
+                                                probe_points=probe_points, vector_potential_ramp=ramps[r])
+        if tables[r] is not None:
+            _with_epsilon_table(rep, tables[r], len(mesh.sites))
         _refuse_dynamic(r, rep)
         if args["seed_states"][r] is not None:
             rep.seed_state = args["seed_states"][r]
@@ -190,6 +256,41 @@ class EnsembleContext:
         eps = f64(eps)
         assert eps.shape == (self.ctx.n,)
         self._chk(self._lib.tdgl_ensemble_set_epsilon(self._ens, r, p_f64(eps)))
+
+    def set_link_ramp(self, r, A_base, tmin, tmax, initial, final):
+        """A(t) = LinearRamp(tmin, tmax, initial, final)(t) * A_base, evaluated inside ``run``."""
+        A_base = f64(A_base)
+        assert A_base.shape == (self.ctx.m, 2)
+        self._chk(self._lib.tdgl_ensemble_set_link_ramp(self._ens, r, p_f64(A_base), float(tmin), float(tmax), float(initial),
+                                                        float(final)))
+
+    def link_scale(self, r) -> float:
+        v = C.c_double(0)
+        self._chk(self._lib.tdgl_ensemble_get_link_scale(self._ens, r, C.byref(v)))
+        return v.value
+
+    def set_mu_boundary_table(self, r, times, groups, densities):
+        """``TDGLContext.set_mu_boundary_table`` for replica r; ``times=None``: off."""
+        if times is None:
+            self._chk(self._lib.tdgl_ensemble_set_mu_boundary_table(self._ens, r, 0, None, 0, None, None, None))
+            return
+        t, d = f64(times), f64(densities)
+        ptr = i32(np.concatenate([[0], np.cumsum([len(g) for g in groups])]))
+        pos = i32(np.concatenate([np.asarray(g, dtype=np.int64) for g in groups]) if len(groups) else [])
+        if d.shape != (len(groups), len(t)):
+            raise ValueError(f"densities must have shape ({len(groups)}, {len(t)}), got {d.shape}")
+        self._chk(self._lib.tdgl_ensemble_set_mu_boundary_table(self._ens, r, len(t), p_f64(t), len(groups), p_i32(ptr),
+                                                                p_i32(pos) if len(pos) else p_i32(i32([0])), p_f64(d)))
+
+    def set_epsilon_table(self, r, epsilon0, times, factors):
+        """``TDGLContext.set_epsilon_table`` for replica r; ``times=None``: off."""
+        if times is None:
+            self._chk(self._lib.tdgl_ensemble_set_epsilon_table(self._ens, r, None, 0, None, None))
+            return
+        e0, t, fac = f64(np.broadcast_to(epsilon0, (self.ctx.n,))), f64(times), f64(factors)
+        if t.shape != fac.shape:
+            raise ValueError("times and factors must have the same length")
+        self._chk(self._lib.tdgl_ensemble_set_epsilon_table(self._ens, r, p_f64(e0), len(t), p_f64(t), p_f64(fac)))
 
     def set_state(self, r, psi, mu):
         psi, mu = c128(psi), f64(mu)
@@ -301,9 +402,19 @@ class EnsembleSolver:
         probes = reps[0].probe_points
         ens.set_probes(probes)
         for r, rep in enumerate(reps):
-            ens.set_link_exponents(r, rep.current_A_applied)
+            if rep._A_ramp is not None:  # (TDGLSolver._setup: the links start at the ramp's value at t = 0)
+                ens.set_link_ramp(r, rep._A_base, **rep._A_ramp)
+            else:
+                ens.set_link_exponents(r, rep.current_A_applied)
             ens.set_mu_boundary(r, rep.mu_boundary)
             ens.set_epsilon(r, rep.epsilon)
+            if rep._current_table is not None and rep.terminal_info:
+                ens.set_mu_boundary_table(r, *rep._current_table_arrays())
+            if rep._eps_table is not None:
+                eps0, times, values = rep._eps_table
+                if max(float(np.max(f * eps0)) for f in values) > 1:
+                    raise ValueError(f"replica {r}: The disorder parameter epsilon must be <= 1")
+                ens.set_epsilon_table(r, eps0, times, values)
             seed = getattr(rep, "seed_state", None)
             if rep.seed_solution is not None:
                 seed = (rep.seed_solution.tdgl_data.psi, rep.seed_solution.tdgl_data.mu)
@@ -320,8 +431,15 @@ class EnsembleSolver:
         for r in range(R):
             ens.begin_stage(r)
 
-        def save_step(r):
+        def save_step(r, final=False):
+            rep = reps[r]
             ls = ens.loop_state(r)
+            if rep._eps_table is not None:
+                # the epsilon of the last step taken, as TDGLSolver.solve saves it (solver.py:645-648)
+                t_last = ls["time"] if (final or ls["step"] == 0) else ls["time"] - ls["dt"]
+                rep.epsilon = np.asarray(rep.epsilon_func(max(t_last, 0.0)), dtype=float)
+            if rep._A_ramp is not None:  # A_applied of the last step taken (the links may lag behind it)
+                rep.current_A_applied = ens.link_scale(r) * rep._A_base
             if ls["step"] == 0 and not saved[r] and not seeded[r]:
                 st = ens.get_state(r, currents=False)
                 js = jn = np.zeros(ctx.m)  # reference initial values (solver.py:736-737)
@@ -364,7 +482,7 @@ class EnsembleSolver:
                     continue
                 i[r] += k - 1
                 if save and (i[r] % opts.save_every):
-                    save_step(r)
+                    save_step(r, final=True)
                 if stage[r] + 1 < len(stages):
                     stage[r] += 1
                     i[r] = 0
@@ -384,7 +502,7 @@ class EnsembleSolver:
             )
             solutions.append(Solution(
                 device=rep.device, options=opts, saved_steps=saved[r], dynamics=dynamics,
-                dynamic_vector_potential=False, dynamic_epsilon=False,
+                dynamic_vector_potential=rep.dynamic_vector_potential, dynamic_epsilon=rep.dynamic_epsilon,
                 applied_vector_potential=rep.applied_vector_potential, terminal_currents=rep.terminal_currents,
                 disorder_epsilon=rep.disorder_epsilon, total_seconds=total,
                 stats=dict(steps_thermalizing=n_steps[r]["Thermalizing"], steps_simulating=n_steps[r]["Simulating"],

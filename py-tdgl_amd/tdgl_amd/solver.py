@@ -341,14 +341,7 @@ class TDGLSolver:
         # tabulated time dependence: uploaded once, evaluated by tdgl_run at every step's time
         self._currents_on_device = self._epsilon_on_device = False
         if self._current_table is not None and self.terminal_info:
-            tab = self._current_table
-            names = self.terminal_names
-            dens = np.array([
-                (-1.0 / term.length) * sum(tab.tables[nm].values for nm in names if nm != term.name and nm in tab.tables)
-                * np.ones(len(tab.times))
-                for term in self.terminal_info
-            ])
-            self.ctx.set_mu_boundary_table(tab.times, [np.asarray(t.boundary_edge_indices) for t in self.terminal_info], dens)
+            self.ctx.set_mu_boundary_table(*self._current_table_arrays())
             self._currents_on_device = True
         if self._eps_table is not None:
             eps0, times, values = self._eps_table
@@ -357,6 +350,18 @@ class TDGLSolver:
             self.ctx.set_epsilon_table(eps0, times, values)
             self._epsilon_on_device = True
         self._device_holds = None  # (psi, mu) arrays known to equal the device state
+
+    def _current_table_arrays(self):
+        """The tabulated terminal currents as ``set_mu_boundary_table`` takes them: the times, the boundary-edge
+        positions of each terminal and the current density of each terminal at each time."""
+        tab = self._current_table
+        names = self.terminal_names
+        dens = np.array([
+            (-1.0 / term.length) * sum(tab.tables[nm].values for nm in names if nm != term.name and nm in tab.tables)
+            * np.ones(len(tab.times))
+            for term in self.terminal_info
+        ])
+        return tab.times, [np.asarray(t.boundary_edge_indices) for t in self.terminal_info], dens
 
     # -- boundary conditions --------------------------------------------------------------------
     def update_mu_boundary(self, time: float) -> bool:

@@ -3,6 +3,7 @@
 
     python tools/bench_ensemble.py --side 70 --replicas 32 --solve-time 20
     python tools/bench_ensemble.py --side 116 --replicas 32 --max-sites 16000    # beyond ENSEMBLE_MAX_SITES
+    python tools/bench_ensemble.py --side 70 --replicas 32 --ramp                 # field ramps evaluated on the device
 
 Synthetic square film (`hex_jitter_points(side, side)`: side 70 = 5,791 sites, 100 = 11,774, 116 = 15,745) in a uniform field, one
 field per replica spread over [b_min, b_max].  Prints ONE JSON line:
@@ -14,6 +15,13 @@ field per replica spread over [b_min, b_max].  Prints ONE JSON line:
   dense_bytes_per_round                  bytes of G one round streams (the tiles, once per 16 replicas)
   dense_GBps_if_whole_round              those bytes / round_us: a floor on the dense product's achieved bandwidth
   max_dev_*                              largest deviation of any sequentially-run replica from its ensemble copy
+With --ramp every replica's field is LinearRamp(tmin=0, tmax=T/2, final=b_r) x the uniform field, held after T/2
+(T = --solve-time); the numbers above are then those of the ramped runs (sequential: tdgl.solve of the same ramps),
+and it adds
+  static_round_us                        round_us of the same ensemble with the static fields b_r
+  ramp_round_us, settled_round_us        round_us of the ramped ensemble over [0, T/2] (every replica ramping) and
+                                         over (T/2, T] (every ramp settled): the difference of a run to T/2 and one
+                                         to T
 """
 
 import argparse
@@ -37,6 +45,7 @@ def main():
     ap.add_argument("--b-max", type=float, default=0.6)
     ap.add_argument("--sequential", type=int, default=4, help="replicas also run one after another (their rate is the baseline)")
     ap.add_argument("--max-sites", type=int, default=None, help="raise ENSEMBLE_MAX_SITES (to measure beyond the cap)")
+    ap.add_argument("--ramp", action="store_true", help="ramp each replica's field over the first half of the run")
     args = ap.parse_args()
 
     from tdgl_amd import SolverOptions, TDGLSolver, ensemble
@@ -58,18 +67,39 @@ def main():
 
     R = args.replicas
     fields = np.linspace(args.b_min, args.b_max, R)
+
+    def ramp(b):  # A(t) = LinearRamp(0, T/2, 0 -> 1)(t) x A(b)
+        return (A(b), dict(tmin=0.0, tmax=args.solve_time / 2, initial=0.0, final=1.0))
+
+    def run(solve_time, ramped):
+        opts = SolverOptions(solve_time=solve_time, save_every=100_000)
+        if ramped:
+            solver = ensemble_dimensionless(mesh, opts, [None] * R, vector_potential_ramp=[ramp(b) for b in fields])
+        else:
+            solver = ensemble_dimensionless(mesh, opts, [A(b) for b in fields])
+        t0 = time.perf_counter()
+        sols = solver.solve()
+        return solver, sols, time.perf_counter() - t0 - solver.setup_seconds
+
+    extra = {}
+    if args.ramp:
+        s_static, _, loop_static = run(args.solve_time, False)
+        s_half, _, loop_half = run(args.solve_time / 2, True)
+        extra["static_round_us"] = round(1e6 * loop_static / max(s_static.ensemble_stats["rounds"], 1), 2)
+        extra["ramp_round_us"] = round(1e6 * loop_half / max(s_half.ensemble_stats["rounds"], 1), 2)
     opts = SolverOptions(solve_time=args.solve_time, save_every=100_000)
-    solver = ensemble_dimensionless(mesh, opts, [A(b) for b in fields])
-    t0 = time.perf_counter()
-    sols = solver.solve()
-    total = time.perf_counter() - t0
-    loop = total - solver.setup_seconds
+    solver, sols, loop = run(args.solve_time, args.ramp)
     steps = sum(len(s.dynamics.dt) for s in sols)
     rounds = solver.ensemble_stats["rounds"]
+    if args.ramp:
+        extra["settled_round_us"] = round(1e6 * (loop - loop_half) / max(rounds - s_half.ensemble_stats["rounds"], 1), 2)
 
     seq_steps, seq_time, dev = 0, 0.0, dict(dt=0.0, abs_psi2=0.0, mu=0.0, js=0.0)
     for r in range(min(args.sequential, R)):
-        one = TDGLSolver.from_dimensionless(mesh, opts, A(fields[r])).solve()
+        if args.ramp:
+            one = TDGLSolver.from_dimensionless(mesh, opts, 0.0 * A(fields[r]), vector_potential_ramp=ramp(fields[r])).solve()
+        else:
+            one = TDGLSolver.from_dimensionless(mesh, opts, A(fields[r])).solve()
         seq_steps += len(one.dynamics.dt)
         seq_time += one.total_seconds
         a, b = sols[r], one
@@ -95,6 +125,7 @@ def main():
         dense_bytes_per_round=dense_bytes, dense_GBps_if_whole_round=round(dense_bytes / (round_us * 1e-6) / 1e9, 1),
         steps_min=min(len(s.dynamics.dt) for s in sols), steps_max=max(len(s.dynamics.dt) for s in sols),
         max_dev_dt_rel=dev["dt"], max_dev_abs_psi2=dev["abs_psi2"], max_dev_mu=dev["mu"], max_dev_js=dev["js"],
+        ramp=args.ramp, **extra,
     )))
 
 
