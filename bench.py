@@ -15,11 +15,15 @@ Steady state: whatever ``--warmup`` says, the run first takes ``--preroll`` unti
 200) so that the timed window sits where the adaptive time step has opened up -- the first ~100
 steps of the trajectory are cheaper and not representative.
 
-Beyond ``value`` (the headline window) a single-GPU run carries on and reports, each with its own
-``parity_vs_oracle`` where the CPU leg runs: ``vortex_window`` (the same number of steps once vortices
-have entered), ``sustained`` (the ``--late-steps`` = 6,000 consecutive steps that follow, timed as a
-whole: what a production run sees) and ``late_window`` (t ~ 440 tau: the adaptive step at dt_max, a
-psi-update retry every few steps).
+A plain run does only what the headline figure needs: set-up, pre-roll and warm-up, the timed steps,
+``--dump-outputs`` if given, the JSON line.  Everything else the benchmark measures or checks runs with
+``--full``: the CPU oracle's ``cpu_baseline`` and ``parity_vs_oracle``, the roofline figures that take
+launches of their own (``frac_net``, ``frac_burst``), the decomposed run's current-conservation check and
+config 5 (several GPUs), and, on a single GPU, the later windows, each with its own ``parity_vs_oracle``
+where the CPU leg runs: ``vortex_window`` (the same number of steps once vortices have entered),
+``sustained`` (the ``--late-steps`` = 6,000 consecutive steps that follow, timed as a whole: what a
+production run sees) and ``late_window`` (t ~ 440 tau: the adaptive step at dt_max, a psi-update retry
+every few steps).
 """
 
 import argparse
@@ -347,13 +351,17 @@ def main():
                     help="0.65 - 1.3M sites: which preconditioner the CG of the mu solve uses -- auto (default): per solve the cheaper "
                          "of the AMG V-cycle and the fp32-stored nested-dissection factors by predicted cost; factors / vcycle: always that one")
     ap.add_argument("--sub-limits", default="", help=argparse.SUPPRESS)  # "SUB_MAX,SUB2_MAX,SUB2_BLOCK,SUB2_SUPER" (tuning runs)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline window, everything else the benchmark measures or checks: the CPU oracle's "
+                         "baseline and parity_vs_oracle, the vortex / sustained / late windows (single GPU), the roofline "
+                         "figures that take launches of their own, the conservation check and config 5 (several GPUs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle leg")
     ap.add_argument("--no-parity", action="store_true",
                     help="skip `parity_vs_oracle` (it needs the CPU baseline leg: the oracle's steps are the reference side)")
     ap.add_argument("--no-probes", action="store_true", help="strip workloads: run without the two probe points")
     ap.add_argument("--vortex-window", choices=["auto", "on", "off"], default="auto",
                     help="after the headline window, run on until the order parameter has collapsed somewhere "
-                         "(min |psi|^2 < 0.05; vortices / phase slips) and time a second window there; auto = single GPU")
+                         "(min |psi|^2 < 0.05; vortices / phase slips) and time a second window there; auto = single GPU with --full")
     ap.add_argument("--vortex-max-steps", type=int, default=5000, help="steps the search for that state may take")
     ap.add_argument("--vortex-settle", type=int, default=500, help="steps between reaching that state and the window")
     ap.add_argument("--late-steps", type=int, default=6000,
@@ -385,7 +393,7 @@ def main():
                     help="use the domain-decomposition driver (RCCL communicator) even on one GPU")
     ap.add_argument("--config5", choices=["auto", "on", "off"], default="auto",
                     help="also run BASELINE config 5 (4M-site film, same decomposition) and report it as `config5`; "
-                         "auto = when more than one GPU is used")
+                         "auto = with --full when more than one GPU is used")
     ap.add_argument("--config5-timeout", type=int, default=900,
                     help="seconds config 5 may take before the headline line is printed without it")
     ap.add_argument("--trace-iterations", default=None,
@@ -653,7 +661,7 @@ def main():
         # Decomposed runs at a size the oracle can follow: the state before and after the timed steps is assembled
         # from all ranks (a collective: every rank takes part, rank 0 keeps the result) so that rank 0 can let the
         # oracle take the same steps from the same state -- `parity_vs_oracle` of the decomposed path.
-        dd_parity = (use_dd and not args.no_parity and not args.no_cpu_baseline and args.steps <= PARITY_STEPS
+        dd_parity = (use_dd and args.full and not args.no_parity and not args.no_cpu_baseline and args.steps <= PARITY_STEPS
                      and n <= DD_PARITY_MAX_SITES)
         if want_cpu_state or dd_parity:
             st = drun.gather_state() if use_dd else ctx.get_state(supercurrent=False, normal_current=False)
@@ -692,10 +700,11 @@ def main():
                 outputs = dict(dt=res["dt"], pcg_iterations=res["pcg_iters"], probe_mu=res["mu"], probe_theta=res["theta"],
                                psi=st_end["psi"], mu=st_end["mu"], supercurrent=st_end["supercurrent"],
                                normal_current=st_end["normal_current"])
-        ev_over = ctx.profile_event_overhead(50)  # (after the timed region)
-        # K1 once more, after the timed region: ONE event pair around 16 back-to-back launches on the state the timed
-        # steps ended on -- the pair's own ~4.5 us is amortised over 16 launches instead of sitting in every sample
-        k1_burst_ms = ctx.time_kernel(1, 16) if not use_dd else None
+        # --full: launches of their own after the timed region.  An empty event pair's reading ...
+        ev_over = ctx.profile_event_overhead(50) if args.full else None
+        # ... and K1 once more: ONE event pair around 16 back-to-back launches on the state the timed steps ended on --
+        # the pair's own ~4.5 us is amortised over 16 launches instead of sitting in every sample
+        k1_burst_ms = ctx.time_kernel(1, 16) if (args.full and not use_dd) else None
         comm = ctx.comm_stats()
         # parity_vs_oracle, direct form: the fields the timed steps themselves ended on
         end_state = ctx.get_state() if (want_cpu_state and not args.no_parity and args.steps <= PARITY_STEPS) else None
@@ -705,12 +714,12 @@ def main():
             tmax = torch.tensor([elapsed], dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             elapsed = float(tmax.item())
-        # Decomposed runs: a physical check of the state the timed steps ended on, assembled from ALL ranks.  The step
-        # enforces div(J_s + J_n) = 0 at every site through the mu solve; on the sites next to a cut that sum runs over
-        # edges whose currents were formed from EXCHANGED psi and mu -- a stale or misplaced ghost value anywhere shows
-        # up as a divergence of the size of the currents, not of the solver's tolerance.
+        # Decomposed runs with --full: a physical check of the state the timed steps ended on, assembled from ALL ranks.
+        # The step enforces div(J_s + J_n) = 0 at every site through the mu solve; on the sites next to a cut that sum
+        # runs over edges whose currents were formed from EXCHANGED psi and mu -- a stale or misplaced ghost value
+        # anywhere shows up as a divergence of the size of the currents, not of the solver's tolerance.
         conservation = None
-        if use_dd:
+        if use_dd and args.full:
             fields = drun.gather_state()
             if rank == 0 and dd_parity:
                 end_state = fields
@@ -738,7 +747,7 @@ def main():
         )
         return out
 
-    main_run = run_workload(args.workload, want_cpu_state=(rank == 0 and not use_dd and not args.no_cpu_baseline))
+    main_run = run_workload(args.workload, want_cpu_state=(rank == 0 and not use_dd and args.full and not args.no_cpu_baseline))
     if main_run.outputs is not None:
         dump_outputs(args.dump_outputs, main_run.outputs)
     def vortex_window(r):
@@ -849,7 +858,7 @@ def main():
         return out_w
 
     vortex = late = None
-    want_vortex = args.vortex_window == "on" or (args.vortex_window == "auto" and not use_dd)
+    want_vortex = args.vortex_window == "on" or (args.vortex_window == "auto" and args.full and not use_dd)
     if want_vortex and rank == 0 and not use_dd:
         vortex = vortex_window(main_run)
         log(f"vortex window: {vortex}")
@@ -861,6 +870,10 @@ def main():
             json.dump(dict(workload=args.workload, preroll=args.preroll, warmup=args.warmup, steps=args.steps,
                            **main_run.trace), f)
 
+    def event_pair_ms(r):
+        """An empty event pair's own reading (--full: measured after the timed region; else None)."""
+        return None if r.ev_over is None else round(r.ev_over, 5)
+
     def roofline_k1(r):
         ab = algorithmic_bytes(r.n_loc, r.m_loc)  # the kernel rank 0 launches covers its own rows
         launches, k1_ms = r.k1
@@ -868,7 +881,7 @@ def main():
         achieved = ab["K1_psi_laplacian_spmv"] / (avg * 1e-3) / 1e9 if avg > 0 else 0.0
         table, src = pmc_traffic(r.name) if not use_dd else ({}, None)
         nbytes = ab["K1_psi_laplacian_spmv"]
-        net = avg - r.ev_over  # the same samples without the reading of an empty event pair
+        net = None if r.ev_over is None else avg - r.ev_over  # the same samples without the reading of an empty event pair
         burst = getattr(r, "k1_burst_ms", None)
         return dict(
             bound="hbm",
@@ -880,7 +893,7 @@ def main():
             # frac_burst is one pair around 16 back-to-back launches after the region (overhead amortised; repeated
             # launches may find part of the operator in the Infinity Cache, so it is an upper bracket).  The kernel
             # trace under profiles/ (rocprofv3 dispatch durations, no events) should fall between frac_net and frac_burst.
-            frac_net=round(nbytes / (net * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if net > 0 else None,
+            frac_net=round(nbytes / (net * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if net is not None and net > 0 else None,
             frac_burst=None if not burst else round(nbytes / (burst * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
             avg_launch_ms_burst=None if not burst else round(burst, 5),
             traffic=traffic_of(table, "void tdgl::k_psi_laplacian<true"),
@@ -888,7 +901,7 @@ def main():
             algorithmic_bytes_per_launch=ab["K1_psi_laplacian_spmv"], avg_launch_ms=round(avg, 5), launches=launches,
             # `achieved` uses the raw event readings; an empty event pair reads this much by itself
             # (rocprofv3's dispatch durations in profiles/ do not contain it)
-            event_pair_overhead_ms=round(r.ev_over, 5),
+            event_pair_overhead_ms=event_pair_ms(r),
         )
 
     def line_for(r):
@@ -974,12 +987,12 @@ def main():
             # frac_traffic = PMC bytes / time, frac_traffic_net the same without the event pair's own overhead
             frac_traffic=(lambda t: None if not t else round(t / (axp_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))(
                 traffic_of(table, "void tdgl::k_sell_axp")),
-            frac_traffic_net=(lambda t: None if (not t or axp_avg_ms <= main_run.ev_over) else round(
+            frac_traffic_net=(lambda t: None if (not t or main_run.ev_over is None or axp_avg_ms <= main_run.ev_over) else round(
                 t / ((axp_avg_ms - main_run.ev_over) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))(traffic_of(table, "void tdgl::k_sell_axp")),
             traffic=traffic_of(table, "void tdgl::k_sell_axp"),
             traffic_source=None if src is None else f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (two passes, gfx950 correction), {src}",
             algorithmic_bytes_per_launch=int(axp_alg), avg_launch_ms=round(axp_avg_ms, 5), launches=main_run.axp[0],
-            event_pair_overhead_ms=round(main_run.ev_over, 5),
+            event_pair_overhead_ms=event_pair_ms(main_run),
         )
     # direct mu solves (small / mid-size workloads): the solve's launches (k_dense_sym_tiles + k_dense_sym_finish, or
     # k_sub_down + those two + k_sub_up) bracketed by one event pair per batch of the run-ahead loop; bytes = the factors
@@ -1004,7 +1017,7 @@ def main():
                                                        "k_dense_sym_tiles + k_dense_sym_finish"),
             achieved=round(solve_bytes / (avg_ms * 1e-3) / 1e9, 1), peak=HBM_PEAK_GBS, unit="GB/s",
             frac=round(solve_bytes / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), bytes_per_solve=solve_bytes,
-            avg_solve_ms=round(avg_ms, 5), samples=main_run.direct[0], event_pair_overhead_ms=round(main_run.ev_over, 5),
+            avg_solve_ms=round(avg_ms, 5), samples=main_run.direct[0], event_pair_overhead_ms=event_pair_ms(main_run),
             note="launch sequence bracketed by one HIP event pair per batch of the run-ahead loop (the pair's own overhead included)",
         )
     # 0.4 - 1.3M sites: one application of the fp32-stored factors as the CG's preconditioner (gather, the solve's launch
@@ -1021,7 +1034,7 @@ def main():
                                 + " + sparse couplings x 3 + k_dense_sym_tiles + k_dense_sym_finish + k_sub_up x 3 + k_pd_scatter",
             achieved=round(pdi["bytes_per_application"] / (avg_ms * 1e-3) / 1e9, 1), peak=HBM_PEAK_GBS, unit="GB/s",
             frac=round(pdi["bytes_per_application"] / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), bytes_per_application=int(pdi["bytes_per_application"]),
-            avg_application_ms=round(avg_ms, 5), samples=main_run.direct[0], event_pair_overhead_ms=round(main_run.ev_over, 5),
+            avg_application_ms=round(avg_ms, 5), samples=main_run.direct[0], event_pair_overhead_ms=event_pair_ms(main_run),
             note="share of the step: applications per step x this time / ms_per_step; the pair's own overhead included")
     r = main_run
     desc = WORKLOADS[args.workload][1]
@@ -1086,7 +1099,7 @@ def main():
     # complete at this point: a watchdog thread prints it if the second workload does not finish in
     # time (a hung collective blocks inside the library, where no Python signal handler runs), so the
     # driver gets its line either way.
-    want5 = args.config5 == "on" or (args.config5 == "auto" and world > 1)
+    want5 = args.config5 == "on" or (args.config5 == "auto" and args.full and world > 1)
     if want5 and args.workload != "4M":
         import threading
 

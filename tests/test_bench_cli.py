@@ -27,7 +27,7 @@ def test_two_ranks_sharing_the_gpu_race_the_transports_and_report_it():
     transport passes its self-test on both ranks, RCCL refuses two ranks on one device and is recorded as out, the
     line says which transport ran, what a step communicated, and that the timing is a dry run."""
     d = _run("--gpus", "2", "--share-devices", "--workload", "250k", "--steps", "10", "--warmup", "5", "--preroll", "60",
-             "--no-cpu-baseline", "--config5", "off")
+             "--full", "--no-cpu-baseline", "--config5", "off")
     assert d["n_gpus"] == 2 and d["steps"] == 10 and d["scaling"] == "strong" and d["value"] > 0
     tr = d["transport"]
     assert tr["used"] == "ipc"
@@ -72,7 +72,7 @@ def test_four_ranks_sharing_the_gpu_run_the_drivers_command_shape():
     final state conserves current across all three cuts.  (The full-size rehearsal -- 1M sites cut 8 ways with
     config 5 attached, 233 s of wall time -- is profiles/BENCH_r08c_1M_8ranks_sharing_one_gpu_DRY_RUN.json.)"""
     d = _run("--gpus", "4", "--share-devices", "--workload", "60k", "--steps", "10", "--warmup", "5", "--preroll", "45",
-             "--config5", "off", timeout=900)
+             "--full", "--config5", "off", timeout=900)
     assert d["n_gpus"] == 4 and d["value"] > 0 and "DRY RUN" in d["config"]["parallelism"]
     by = {t["transport"]: t for t in d["transport"]["selftest"]}
     assert d["transport"]["used"] == "ipc" and by["ipc"]["ok"] and by["ipc"]["checks_per_rank"] >= 5
@@ -86,7 +86,7 @@ def test_decomposed_run_is_followed_by_the_oracle_from_the_same_state():
     both ranks before the clock started: `parity_vs_oracle` of the decomposed path (no `cpu_baseline`: that is a
     single-GPU figure)."""
     d = _run("--gpus", "2", "--share-devices", "--workload", "60k", "--steps", "10", "--warmup", "5", "--preroll", "45",
-             "--config5", "off")
+             "--full", "--config5", "off")
     par = d["parity_vs_oracle"]
     assert par["ok"] and par["steps"] == 10 and "2 rank(s)" in par["source"], par
     assert max(par[k] for k in ("dt", "abs_sq_psi", "mu_zero_mean", "J_s", "J_n")) <= par["tolerance"] == 1e-8
@@ -102,7 +102,8 @@ def test_when_no_device_transport_works_the_host_transport_still_yields_a_line()
 
 
 def test_single_gpu_line_carries_the_contract_fields():
-    d = _run("--workload", "60k", "--steps", "20", "--warmup", "5", "--preroll", "40", "--cpu-seconds", "2", "--vortex-window", "off")
+    d = _run("--workload", "60k", "--steps", "20", "--warmup", "5", "--preroll", "40", "--full", "--cpu-seconds", "2",
+             "--vortex-window", "off")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -117,6 +118,18 @@ def test_single_gpu_line_carries_the_contract_fields():
     rd = d["roofline_direct"]
     assert rd is not None and rd["samples"] >= 1 and 0.0 < rd["frac"] <= 1.0 and d["roofline_pcg"] is None
     assert 0.0 < r["frac"] <= 1.0
+
+
+def test_a_plain_single_gpu_run_times_the_headline_window_and_nothing_else():
+    """Without `--full` the run sets up, warms up, times its K steps and prints the line: no CPU oracle, no later
+    windows, no launches of its own after the timed region -- the roofline figures that need them are null."""
+    d = _run("--workload", "60k", "--steps", "12", "--warmup", "3", "--preroll", "40")
+    assert d["metric"] == "tdgl_steps_per_sec" and d["steps"] == 12 and d["warmup"] == 3 and d["value"] > 0
+    assert abs(d["ms_per_step"] * d["value"] - 1e3) < 1e-2 * 1e3 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    for key in ("cpu_baseline", "speedup_vs_cpu_baseline", "parity_vs_oracle", "vortex_window", "sustained", "late_window", "config5"):
+        assert key not in d, key
+    r = d["roofline"]
+    assert 0.0 < r["frac"] <= 1.0 and r["frac_net"] is None and r["frac_burst"] is None and r["event_pair_overhead_ms"] is None
 
 
 def test_a_window_in_which_the_loop_has_paused_the_direct_solve_reports_no_direct_roofline():

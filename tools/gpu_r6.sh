@@ -13,7 +13,7 @@ newtests)
   ;;
 bench3)
   for M in auto factors vcycle; do
-    timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --mu-precond $M > $OUT/BENCH_${TAG}_1M_$M.json 2> $OUT/${TAG}_bench_$M.err
+    timeout 900 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --mu-precond $M > $OUT/BENCH_${TAG}_1M_$M.json 2> $OUT/${TAG}_bench_$M.err
     echo "bench $M rc=$?"; python - <<PY
 import json
 try:
@@ -50,7 +50,7 @@ pdmid)
   for W in ${PD_WORKLOADS:-250k 450k strip250k strip500k}; do
     for V in default pd; do
       EXTRA=""; [ $V = pd ] && EXTRA="--sub-limits 32000,100000"
-      timeout 900 python bench.py --workload $W --steps 20 --warmup 5 --no-cpu-baseline --late-steps 3000 $EXTRA > $OUT/BENCH_${TAG}_${W}_$V.json 2> $OUT/${TAG}_${W}_$V.err
+      timeout 900 python bench.py --workload $W --steps 20 --warmup 5 --full --no-cpu-baseline --late-steps 3000 $EXTRA > $OUT/BENCH_${TAG}_${W}_$V.json 2> $OUT/${TAG}_${W}_$V.err
       python - <<PY
 import json
 try:
@@ -66,7 +66,7 @@ PY
 symab)
   # symmetric tiles on the first level (k_sub_down_sym) against whole blocks (TDGL_PD_SYM=0): factors forced, 1M
   for V in 1 0; do
-    TDGL_PD_SYM=$V timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --mu-precond factors --late-steps 2000 > $OUT/BENCH_${TAG}_1M_sym$V.json 2> $OUT/${TAG}_sym$V.err
+    TDGL_PD_SYM=$V timeout 900 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --mu-precond factors --late-steps 2000 > $OUT/BENCH_${TAG}_1M_sym$V.json 2> $OUT/${TAG}_sym$V.err
     python - <<PY
 import json
 try:

@@ -12,9 +12,9 @@ if [ "$TESTS" = tests ]; then
   echo "tests rc=$?" >> $OUT/${TAG}_tests.log
   tail -4 $OUT/${TAG}_tests.log; grep -E "^(FAILED|ERROR)" $OUT/${TAG}_tests.log | head
 fi
-timeout 900 python bench.py --steps 20 --warmup 5 --trace-iterations $OUT/${TAG}_trace_1M.json "$@" > $OUT/BENCH_${TAG}_1M_driver.json 2> $OUT/${TAG}_bench_driver.err
+timeout 900 python bench.py --steps 20 --warmup 5 --full --trace-iterations $OUT/${TAG}_trace_1M.json "$@" > $OUT/BENCH_${TAG}_1M_driver.json 2> $OUT/${TAG}_bench_driver.err
 echo "bench(driver flags) rc=$?"; cat $OUT/BENCH_${TAG}_1M_driver.json | cut -c1-300
-timeout 900 python bench.py --no-cpu-baseline "$@" > $OUT/BENCH_${TAG}_1M.json 2> $OUT/${TAG}_bench.err
+timeout 900 python bench.py --full --no-cpu-baseline "$@" > $OUT/BENCH_${TAG}_1M.json 2> $OUT/${TAG}_bench.err
 echo "bench(default) rc=$?"; cat $OUT/BENCH_${TAG}_1M.json | cut -c1-300
 cd /tmp
 timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof_${TAG} -o ${TAG} -- python $OLDPWD/bench.py --steps 100 --warmup 20 --no-cpu-baseline --vortex-window off "$@" > $OUT/prof_${TAG}_bench.json 2> $OUT/prof_${TAG}_err.log
