@@ -729,10 +729,14 @@ int tdgl_guess_dots(tdgl_ctx *ctx, int32_t k, int64_t n, const double *vectors, 
 
 /* ------------------------------------------------------------------ ensembles
  * R independent replicas of the context's device in one batched time loop (csrc/ensemble.inc).  The context must be
- * a single-GPU one with the explicit dense inverse (tdgl_poisson_build_dense_inverse); the replicas share its mesh,
- * site graph and G, and each has its own link exponents, mu boundary values, epsilon, state (psi, mu), controller
+ * a single-GPU one with a direct mu solve: the explicit dense inverse (tdgl_poisson_build_dense_inverse), or the
+ * substructured factors of one or two levels in fp64, READY, whose separator right-hand sides come from the -E^T rows
+ * (tdgl_poisson_set_substructure / _inner / tdgl_poisson_build_substructure, whole blocks or symmetric tiles:
+ * csrc/ensemble_sub.inc).  Three levels, sparse coupling blocks and factors in the preconditioner's form are refused
+ * (TDGL_ERR_ARG), a context without a direct solve too (TDGL_ERR_NOT_READY).  The replicas share its mesh, site graph
+ * and factors, and each has its own link exponents, mu boundary values, epsilon, state (psi, mu), controller
  * and Runner clock (time, stage step, adaptive dt, retries).  One round of the loop is one attempt of every live
- * replica in five launches over all of them; the host synchronises once per batch of rounds.  The per-replica
+ * replica in five launches over all of them (dense inverse; 6 + 2 per level with the substructured factors); the host synchronises once per batch of rounds.  The per-replica
  * setters form their input with the context's own entry point of the same name and copy it: the context's own run
  * state is overwritten.  Time-dependent inputs are the three forms the run-ahead loop evaluates on the device: a
  * replica's field ramp (tdgl_ensemble_set_link_ramp), tabulated terminal currents and separable epsilon, each
@@ -786,6 +790,10 @@ int tdgl_ensemble_get_state(tdgl_ensemble *ens, int32_t r, double *psi, double *
                             double *normal_current);
 /* Rounds queued and host synchronisations since the ensemble was created. */
 int tdgl_ensemble_get_stats(tdgl_ensemble *ens, int64_t *rounds, int64_t *batches);
+/* The mu solve the ensemble applies: *levels = 0 for the dense inverse, else the levels of the substructured factors;
+ * *factor_bytes = bytes of the factors one round reads (the dense tiles once per 16 replicas, the levels' value pools
+ * once per 8).  Either may be NULL. */
+int tdgl_ensemble_get_mu_path(tdgl_ensemble *ens, int32_t *levels, int64_t *factor_bytes);
 
 /* ------------------------------------------------------------------ measurement */
 /* Average duration (ms) of `reps` back-to-back launches of one kernel on the context's

@@ -12,6 +12,7 @@
 //                            and its transpose
 //   K4 k_ens_finish          slot sums of K3 (dense_sym_finish_body) and the controller (step_controller) per replica
 //   K5 k_ens_probes          probe read-outs of the accepted attempts
+// (above the dense inverse's cap K3 / K4 become the substructured solve's S1 - S6, ensemble_sub.inc)
 // and the host synchronises once per batch of rounds.  A failed psi update is that replica's next attempt, with
 // the smaller dt, in the next round; a replica that has reached its end time, spent its retry budget or taken the
 // steps asked of this call is poisoned and its launches return at once.  Per replica the arithmetic is that of the
@@ -361,7 +362,77 @@ struct tdgl_ensemble {
     std::vector<int32_t> h_limit;
     std::vector<EnsReplica> rep;
     int64_t stat_rounds = 0, stat_batches = 0;
+    // the mu solve on the substructured factors (levels > 0; ensemble_sub.inc): the factors it was set up for, per level
+    // the work lists of the ways down and up and the replicas' w [R][ldw] and x_S [R][nS]; the shares of u . x_S, the means
+    int levels = 0;
+    const DirectFactors *fac = nullptr;
+    int64_t factor_bytes = 0;  // bytes of the factors one round reads (every block once per group of replicas)
+    DevBuf<EnsSubChunk> sub_down[2], sub_up[2];
+    int n_down[2] = {0, 0}, n_up[2] = {0, 0};
+    DevBuf<double> sub_w[2], sub_xs[2], upart, mean;
+    int64_t ldw[2] = {0, 0};
 };
+
+// The ensemble's work lists of one level (EnsSubChunk: chunks of at most 64 rows) from the single run's: whole G_p blocks
+// (k_sub_down's chunks of 32 rows, the first of a part at its first row) or a part's tiles (k_sub_down_sym: one chunk
+// per part), and the way up's chunks (of 64 rows, or whole parts).  Every chunk is checked against the level's arrays.
+static int ens_sub_lists(tdgl_ctx *ctx, const SubLevel &L, int64_t n, DevBuf<EnsSubChunk> &down, int &n_down, DevBuf<EnsSubChunk> &up,
+                         int &n_up) {
+    const char *who = "tdgl_ensemble_create";
+    std::vector<SubDownChunk> dc(L.down_chunks.n);
+    std::vector<SubUpChunk> uc(L.up_chunks.n);
+    if (!dc.empty()) HIP_TRY(ctx, hipMemcpy(dc.data(), L.down_chunks.p, dc.size() * sizeof(SubDownChunk), hipMemcpyDeviceToHost));
+    if (!uc.empty()) HIP_TRY(ctx, hipMemcpy(uc.data(), L.up_chunks.p, uc.size() * sizeof(SubUpChunk), hipMemcpyDeviceToHost));
+    const bool tiles = L.sym_lds > 0;
+    const int64_t nv = (int64_t)L.vals.n;
+    std::vector<EnsSubChunk> d, u;
+    for (const SubDownChunk &c : dc) {
+        if (c.n_rows <= 0 || (!tiles && c.row0 != c.x0)) continue;  // (whole blocks: a part once, from its first chunk)
+        const int32_t np_ = c.ncols;
+        const int64_t nt = (np_ + ST - 1) / ST;
+        const bool ok = np_ > 0 && c.x0 >= 0 && c.x0 + (int64_t)np_ <= L.nI && c.g >= 0 &&
+                        (tiles ? c.g + nt * (nt + 1) / 2 * (ST * ST) <= nv : c.g + (int64_t)np_ * np_ <= nv);
+        if (!ok) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: the factors' way-down work list is inconsistent", who);
+        for (int32_t r0 = 0; r0 < np_; r0 += WAVE)
+            d.push_back(EnsSubChunk{tiles ? c.g : c.g + r0, tiles ? 0 : np_, np_, c.x0, c.x0 + r0, std::min<int32_t>(WAVE, np_ - r0), r0});
+    }
+    for (const SubUpChunk &c : uc) {
+        if (c.n_rows <= 0) continue;
+        const bool ok = c.np >= c.n_rows && c.cnt >= 0 && c.s0 >= 0 && c.s0 + (int64_t)c.cnt <= (int64_t)L.sep_idx.n && c.row0 >= 0 &&
+                        c.row0 + (int64_t)c.n_rows <= L.nI && c.et >= 0 &&
+                        (c.cnt == 0 || c.et + (int64_t)(c.cnt - 1) * c.np + c.n_rows <= nv);
+        if (!ok) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: the factors' way-up work list is inconsistent", who);
+        for (int32_t r0 = 0; r0 < c.n_rows; r0 += WAVE)
+            u.push_back(EnsSubChunk{c.et + r0, c.np, c.cnt, c.s0, c.row0 + r0, std::min<int32_t>(WAVE, c.n_rows - r0), 0});
+    }
+    int64_t rows = 0;
+    for (const EnsSubChunk &c : d) rows += c.n_rows;
+    if (rows != L.nI || L.nI + L.nS != n) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: the factors' work lists do not cover the level", who);
+    n_down = (int)d.size();
+    n_up = (int)u.size();
+    if (d.empty()) d.push_back(EnsSubChunk{0, 0, 0, 0, 0, 0, 0});
+    if (u.empty()) u.push_back(EnsSubChunk{0, 0, 0, 0, 0, 0, 0});
+    HIP_TRY(ctx, down.upload(d));
+    HIP_TRY(ctx, up.upload(u));
+    return TDGL_OK;
+}
+
+// The substructured factors the ensemble applies: a READY fp64 direct solve of one or two levels whose separator
+// right-hand sides come from the -E^T rows (no sparse coupling blocks).  Anything else is refused with TDGL_ERR_ARG.
+static int ens_sub_check(tdgl_ctx *ctx, const DirectFactors &f) {
+    const char *who = "tdgl_ensemble_create";
+    if (f.stage != DirectFactors::READY || f.fp32)
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: the substructured factors precondition the CG (fp32 / preconditioner form): the ensemble "
+                  "needs the fp64 direct solve", who);
+    if (f.levels > 2)
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: substructured factors of %d levels are not supported (one or two)", who, f.levels);
+    for (int k = 0; k < f.levels; ++k)
+        if (f.lv[k].coupling.nnz > 0 || f.lv[k].need_coupling || f.lv[k].ident || f.lv[k].vals.n == 0)
+            TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: substructured factors with sparse coupling blocks are not supported", who);
+    if (f.dense.n != f.lv[f.levels - 1].nS || f.dense.tiles <= 0 || f.dense.G.n == 0 || f.nfin != (int)((f.dense.n + WAVE - 1) / WAVE))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: the substructured factors have no fp64 top separator", who);
+    return TDGL_OK;
+}
 
 static int ens_check(tdgl_ensemble *e, int32_t r) {
     if (!e) return TDGL_ERR_ARG;
@@ -384,8 +455,12 @@ extern "C" int tdgl_ensemble_create(tdgl_ensemble **out, tdgl_ctx *ctx, int32_t 
     if (distributed(ctx)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_create: single-GPU contexts only");
     if (n_replicas < 1 || n_replicas > TDGL_ENSEMBLE_MAX_REPLICAS)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_create: n_replicas must be in [1, %d] (got %d)", TDGL_ENSEMBLE_MAX_REPLICAS, n_replicas);
-    if (!(ctx->direct && ctx->direct->ld > 0 && ctx->direct->dense.n == ctx->n))
-        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_create: the context has no dense inverse (tdgl_poisson_build_dense_inverse)");
+    const DirectFactors *fac = ctx->direct.get();
+    const bool dense = fac && fac->ld > 0 && fac->dense.n == ctx->n;
+    if (!dense && !(fac && fac->levels > 0 && fac->n_local == 0))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_create: the context has no dense inverse (tdgl_poisson_build_dense_inverse) "
+                  "and no substructured direct solve");
+    if (!dense) TDGL_TRY(ens_sub_check(ctx, *fac));
     if (ctx->scr_enabled) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_create: screening is not supported");
     std::unique_ptr<tdgl_ensemble> e(new tdgl_ensemble());
     e->ctx = ctx;
@@ -394,9 +469,26 @@ extern "C" int tdgl_ensemble_create(tdgl_ensemble **out, tdgl_ctx *ctx, int32_t 
     e->n_pad = ctx->n_pad;
     e->m_pad = ctx->m_pad;
     e->n_slots = ctx->lap_pat.n_slots;
-    e->nt = ctx->direct->dense.tiles;
+    e->nt = fac->dense.tiles;
     e->ldpart = (int64_t)e->nt * e->nt * DT;
+    e->fac = fac;
     const size_t R = (size_t)n_replicas;
+    e->factor_bytes = (int64_t)fac->dense.G.n * (int64_t)sizeof(double) * (int64_t)((R + ENS_RG - 1) / ENS_RG);
+    if (!dense) {
+        e->levels = fac->levels;
+        int64_t len = ctx->n;  // (the length of the vector a level works on)
+        for (int k = 0; k < e->levels; ++k) {
+            const SubLevel &L = fac->lv[k];
+            TDGL_TRY(ens_sub_lists(ctx, L, len, e->sub_down[k], e->n_down[k], e->sub_up[k], e->n_up[k]));
+            e->ldw[k] = L.nI + L.nS + L.parts;
+            HIP_TRY(ctx, e->sub_w[k].alloc(R * e->ldw[k]));
+            HIP_TRY(ctx, e->sub_xs[k].alloc(R * L.nS));
+            e->factor_bytes += (int64_t)L.vals.n * (int64_t)sizeof(double) * (int64_t)((R + ENS_SG - 1) / ENS_SG);
+            len = L.nS;
+        }
+        HIP_TRY(ctx, e->upart.alloc(R * fac->nfin));
+        HIP_TRY(ctx, e->mean.alloc(R));
+    }
     HIP_TRY(ctx, e->U.alloc(R * e->m_pad));
     HIP_TRY(ctx, e->lapv.alloc(R * std::max<int64_t>(e->n_slots, 1)));
     HIP_TRY(ctx, e->psi0.alloc(R * e->n_pad));
@@ -763,6 +855,50 @@ static void ens_queue_drives(tdgl_ensemble *e, bool ramping) {
 #undef TDGL_KENS
 }
 
+// mu = pinv(A) bvec of every live replica on the substructured factors, then the controllers (S1 - S6, ensemble_sub.inc):
+// the ways down level after level, the top separator, the means, the ways up innermost first
+static void ens_queue_sub_solve(tdgl_ensemble *e) {
+    tdgl_ctx *ctx = e->ctx;
+    const DirectFactors &f = *e->fac;
+    const int R = e->R, K = e->levels, nt = e->nt;
+    const unsigned groups = (unsigned)((R + ENS_SG - 1) / ENS_SG);
+    const StepCtl *ctl = e->d_ctl.p;
+    const double *vec = e->bvec.p;
+    int64_t ldv = e->n_pad;
+    for (int k = 0; k < K; ++k) {
+        const SubLevel &L = f.lv[k];
+        const int64_t rows = L.nI + L.nS + L.parts;
+        const int nblk_rest = (int)((rows - L.nI + BLOCK / WAVE - 1) / (BLOCK / WAVE));
+        hipLaunchKernelGGL(k_ens_sub_down, dim3((unsigned)(e->n_down[k] + nblk_rest), groups), dim3(BLOCK), 0, ctx->stream, e->n_down[k],
+                           (const EnsSubChunk *)e->sub_down[k].p, L.nI, rows, (const int32_t *)L.seg_ptr.p, (const int64_t *)L.seg_val.p,
+                           (const int32_t *)L.seg_x.p, (const int32_t *)L.seg_len.p, (const double *)L.vals.p, vec, ldv, e->sub_w[k].p,
+                           e->ldw[k], R, ctl);
+        vec = e->sub_w[k].p + L.nI;  // (the separator rows of the way down: the next level's vector)
+        ldv = e->ldw[k];
+    }
+    const SubLevel &L0 = f.lv[0], &T = f.lv[K - 1];
+    hipLaunchKernelGGL(k_ens_dense_tiles, dim3(nt * (nt + 1) / 2, (R + ENS_RG - 1) / ENS_RG), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt,
+                       (const double *)f.dense.G.p, vec, ldv, e->part.p, e->ldpart, R, ctl);
+    hipLaunchKernelGGL(k_ens_sub_top, dim3(f.nfin, R), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt, (const double *)e->part.p, e->ldpart,
+                       e->sub_xs[K - 1].p, (const double *)T.u.p, e->upart.p, f.nfin, ctl);
+    const SubLevel &L1 = f.lv[1];
+    hipLaunchKernelGGL(k_ens_sub_mean, dim3(R), dim3(BLOCK), 0, ctx->stream, (const double *)(e->sub_w[0].p + L0.nI + L0.nS), L0.parts,
+                       e->ldw[0], K > 1 ? (const double *)(e->sub_w[1].p + L1.nI + L1.nS) : (const double *)nullptr, K > 1 ? L1.parts : 0,
+                       e->ldw[1], (const double *)e->upart.p, f.nfin, 1.0 / (double)ctx->n_global, e->mean.p, ctl);
+    for (int k = K - 1; k >= 0; --k) {
+        const SubLevel &L = f.lv[k];
+        double *out = k == 0 ? e->mu.p : e->sub_xs[k - 1].p;
+        const int64_t ldo = k == 0 ? e->n_pad : f.lv[k - 1].nS;
+        hipLaunchKernelGGL(k_ens_sub_up, dim3((unsigned)(e->n_up[k] + grid_for(L.nS)), groups), dim3(BLOCK), 0, ctx->stream, e->n_up[k],
+                           (const EnsSubChunk *)e->sub_up[k].p, L.nI, L.nS, (const int32_t *)L.sep_idx.p, (const double *)L.vals.p,
+                           (const double *)e->sub_w[k].p, e->ldw[k], (const double *)e->sub_xs[k].p, L.nS,
+                           k == 0 ? (const double *)e->mean.p : (const double *)nullptr,
+                           k == 0 ? (const int32_t *)e->fail_part.p : (const int32_t *)nullptr, ctx->psi_blocks, out, ldo, R, ctl);
+    }
+    hipLaunchKernelGGL(k_ens_sub_control, dim3(R), dim3(BLOCK), 0, ctx->stream, (const double *)e->dmax_part.p,
+                       (const int32_t *)e->fail_part.p, ctx->psi_blocks, e->d_ctl.p, e->d_rec.p, (const int32_t *)e->limit.p);
+}
+
 static void ens_queue_round(tdgl_ensemble *e, bool ramping) {
     tdgl_ctx *ctx = e->ctx;
     const unsigned R = (unsigned)e->R;
@@ -781,12 +917,16 @@ static void ens_queue_round(tdgl_ensemble *e, bool ramping) {
     if (pat.use16) TDGL_KENS(int16_t, pat.cols16.p); else TDGL_KENS(int32_t, pat.cols.p);
 #undef TDGL_KENS
     const int nt = e->nt;
-    hipLaunchKernelGGL(k_ens_dense_tiles, dim3(nt * (nt + 1) / 2, (R + ENS_RG - 1) / ENS_RG), dim3(BLOCK), 0, ctx->stream, (int)e->n, nt,
-                       (const double *)ctx->direct->dense.G.p, (const double *)e->bvec.p, e->n_pad, e->part.p, e->ldpart, (int)R,
-                       (const StepCtl *)e->d_ctl.p);
-    hipLaunchKernelGGL(k_ens_finish, dim3((unsigned)((e->n + WAVE - 1) / WAVE), R), dim3(BLOCK), 0, ctx->stream, (int)e->n, nt,
-                       (const double *)e->part.p, e->ldpart, (const double *)e->dmax_part.p, (const int32_t *)e->fail_part.p,
-                       ctx->psi_blocks, e->mu.p, e->n_pad, e->d_ctl.p, e->d_rec.p, (const int32_t *)e->limit.p);
+    if (e->levels > 0) {
+        ens_queue_sub_solve(e);
+    } else {
+        hipLaunchKernelGGL(k_ens_dense_tiles, dim3(nt * (nt + 1) / 2, (R + ENS_RG - 1) / ENS_RG), dim3(BLOCK), 0, ctx->stream, (int)e->n, nt,
+                           (const double *)ctx->direct->dense.G.p, (const double *)e->bvec.p, e->n_pad, e->part.p, e->ldpart, (int)R,
+                           (const StepCtl *)e->d_ctl.p);
+        hipLaunchKernelGGL(k_ens_finish, dim3((unsigned)((e->n + WAVE - 1) / WAVE), R), dim3(BLOCK), 0, ctx->stream, (int)e->n, nt,
+                           (const double *)e->part.p, e->ldpart, (const double *)e->dmax_part.p, (const int32_t *)e->fail_part.p,
+                           ctx->psi_blocks, e->mu.p, e->n_pad, e->d_ctl.p, e->d_rec.p, (const int32_t *)e->limit.p);
+    }
     if (e->np_ > 0)
         hipLaunchKernelGGL(k_ens_probes, dim3((e->np_ + 63) / 64, R), dim3(64), 0, ctx->stream, e->np_, (const int32_t *)e->d_probes.p,
                            (const double2 *)e->psi0.p, (const double2 *)e->psi1.p, (const double *)e->mu.p, e->n_pad, e->probe.p,
@@ -806,8 +946,11 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
     CTX_GUARD(ctx);
     if (!max_steps || !end_time || capacity < 0 || !out_dt || !steps_done || !reached_end)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_run: bad arguments");
-    if (!(ctx->direct && ctx->direct->ld > 0 && ctx->direct->dense.tiles == e->nt))
+    if (e->levels == 0 && !(ctx->direct && ctx->direct->ld > 0 && ctx->direct->dense.tiles == e->nt))
         TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_run: the context's dense inverse has been released");
+    if (e->levels > 0 && !(ctx->direct.get() == e->fac && e->fac->levels == e->levels && e->fac->stage == DirectFactors::READY &&
+                           e->fac->dense.tiles == e->nt))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_run: the context's substructured factors have been released or replaced");
     const int R = e->R, np_ = e->np_;
     for (int r = 0; r < R; ++r) {
         const EnsReplica &p = e->rep[r];
@@ -946,6 +1089,13 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
                   "replica %d: Solver failed to converge in %d retries at step %lld with dt = %.2e."
                   " Try using a smaller dt_init.",
                   err_replica, e->rep[err_replica].ctl.max_solve_retries, (long long)err_step, err_dt);
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_get_mu_path(tdgl_ensemble *e, int32_t *levels, int64_t *factor_bytes) {
+    if (!e) return TDGL_ERR_ARG;
+    if (levels) *levels = e->levels;
+    if (factor_bytes) *factor_bytes = e->factor_bytes;
     return TDGL_OK;
 }
 

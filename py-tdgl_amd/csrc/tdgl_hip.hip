@@ -1366,4 +1366,5 @@ extern "C" int tdgl_time_kernel(tdgl_ctx *ctx, int32_t kernel, int32_t reps, dou
     return TDGL_OK;
 }
 
+#include "ensemble_sub.inc"
 #include "ensemble.inc"

@@ -343,6 +343,7 @@ SIGNATURES = {
     ),
     "tdgl_ensemble_get_state": (C.c_int, [_ENS, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p]),
     "tdgl_ensemble_get_stats": (C.c_int, [_ENS, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tdgl_ensemble_get_mu_path": (C.c_int, [_ENS, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "tdgl_apply_psi_laplacian": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_supercurrent": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_psi_update": (

@@ -3,8 +3,9 @@ realisations -- advanced together in one batched time loop on the GPU (``csrc/en
 
 Each replica is what ``tdgl.solve(device, options, ...)`` would run for its own inputs: same saved steps, dynamics,
 thermalisation, adaptive dt, retries and errors.  The replicas share the device, its mesh and the ``SolverOptions``;
-the mu solve is the dense pseudo-inverse of the Poisson matrix, applied to all replicas' right-hand sides in one
-pass over it.  A replica may be time dependent in the three forms the device evaluates itself, each with its own
+the mu solve is the dense pseudo-inverse of the Poisson matrix up to ``ENSEMBLE_DENSE_MAX_SITES`` sites and the
+substructured direct solve of one or two levels above (`ensemble_mu_path`), applied to all replicas' right-hand
+sides in one pass over the factors per group of replicas.  A replica may be time dependent in the three forms the device evaluates itself, each with its own
 parameters: a field ramp ``LinearRamp * (static field)``, ``TabulatedCurrents`` and a ``SeparableEpsilon``.  Not
 supported: other time-dependent inputs, a ramp combined with a table in one replica, screening, ``output_file``, more
 than ``ENSEMBLE_MAX_SITES`` sites.
@@ -26,10 +27,25 @@ from .options import SolverOptions
 from .solution import DynamicsData, Solution, TDGLData
 from .solver import TDGLSolver
 
-# Largest mesh the ensemble takes, set by measurement (DESIGN.md "Ensembles"): one round reads the dense inverse
-# (n^2 / 2 doubles) once per 16 replicas, and at R = 32 the ensemble's aggregate rate over tdgl.solve run one replica
-# after another falls from 5.4x at 5,791 sites to 1.4x at 11,774 and 0.85x at 15,745 sites.
-ENSEMBLE_MAX_SITES = 12_000
+# The ensemble's mu solve by mesh size, set by measurement (DESIGN.md "Ensembles").  Up to ENSEMBLE_DENSE_MAX_SITES the
+# dense inverse (n^2 / 2 doubles, read once per 16 replicas and round: at R = 32 the ensemble's aggregate rate over
+# tdgl.solve run one replica after another falls from 5.4x at 5,791 sites to 1.4x at 11,774 and 0.85x at 15,745 sites);
+# above it the substructured factors of the single run (growing like n^1.5, read once per 8 replicas and round), one
+# level up to ENSEMBLE_SUB_MAX_SITES (the single run's `TDGLContext.SUB_MAX_SITES`), two levels up to
+# ENSEMBLE_MAX_SITES -- the single run's `DIRECT_SWITCH_MIN_SITES`, below which it takes the direct solve in every state.
+ENSEMBLE_DENSE_MAX_SITES = 12_000
+ENSEMBLE_SUB_MAX_SITES = 32_000
+ENSEMBLE_MAX_SITES = 150_000
+
+
+def ensemble_mu_path(n_sites: int) -> int:
+    """Levels of the substructured mu solve the ensemble takes for a mesh of ``n_sites`` sites; 0: the dense inverse.
+    Depends on the module's constants alone (not on `TDGLContext`'s size rule, which tests switch off)."""
+    if n_sites > ENSEMBLE_MAX_SITES:
+        raise ValueError(f"solve_ensemble: the mesh has {n_sites} sites, more than ENSEMBLE_MAX_SITES = {ENSEMBLE_MAX_SITES}.")
+    if n_sites <= ENSEMBLE_DENSE_MAX_SITES:
+        return 0
+    return 1 if n_sites <= ENSEMBLE_SUB_MAX_SITES else 2
 
 
 class _ReplicaInputs(TDGLSolver):
@@ -64,8 +80,7 @@ def _refuse_options(options: SolverOptions, n_sites: int) -> None:
         raise ValueError("solve_ensemble: include_screening=True is not supported (the ensemble has static link variables).")
     if options.output_file is not None:
         raise ValueError("solve_ensemble: output_file is not supported (the solutions are returned in memory).")
-    if n_sites > ENSEMBLE_MAX_SITES:
-        raise ValueError(f"solve_ensemble: the mesh has {n_sites} sites, more than ENSEMBLE_MAX_SITES = {ENSEMBLE_MAX_SITES}.")
+    ensemble_mu_path(n_sites)  # (raises above ENSEMBLE_MAX_SITES)
     if options.adaptive and not 1 <= options.adaptive_window <= 128:
         raise ValueError(f"solve_ensemble: adaptive_window must be in [1, 128] (got {options.adaptive_window}).")
 
@@ -218,7 +233,8 @@ def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon
 
 
 class EnsembleContext:
-    """Owns one ``tdgl_ensemble`` attached to a ``TDGLContext`` with a dense inverse."""
+    """Owns one ``tdgl_ensemble`` attached to a ``TDGLContext`` with a direct mu solve (the dense inverse, or the
+    substructured factors of one or two levels)."""
 
     def __init__(self, ctx, n_replicas: int):
         self.ctx = ctx
@@ -346,6 +362,12 @@ class EnsembleContext:
         self._chk(self._lib.tdgl_ensemble_get_state(self._ens, r, p_f64(psi), p_f64(mu), p_f64(js), p_f64(jn)))
         return dict(psi=psi, mu=mu, supercurrent=js, normal_current=jn)
 
+    def mu_path(self):
+        """``(levels, factor_bytes)``: 0 levels = the dense inverse; the bytes of the factors one round reads."""
+        levels, nbytes = C.c_int32(0), C.c_int64(0)
+        self._chk(self._lib.tdgl_ensemble_get_mu_path(self._ens, C.byref(levels), C.byref(nbytes)))
+        return levels.value, nbytes.value
+
     def stats(self):
         rounds, batches = C.c_int64(0), C.c_int64(0)
         self._chk(self._lib.tdgl_ensemble_get_stats(self._ens, C.byref(rounds), C.byref(batches)))
@@ -353,14 +375,20 @@ class EnsembleContext:
 
 
 def build_context(mesh, options: SolverOptions, fixed_sites, u: float, gamma: float):
-    """A single-GPU context on ``mesh`` with the dense inverse, whatever `TDGLContext.DENSE_MAX_SITES` says."""
+    """A single-GPU context on ``mesh`` with the ensemble's direct mu solve (`ensemble_mu_path`): the dense inverse or
+    the substructured factors, whatever `TDGLContext.DENSE_MAX_SITES` / `SUB_MAX_SITES` / `SUB2_MAX_SITES` say."""
     from .hipcore import TDGLContext
 
+    levels = ensemble_mu_path(len(mesh.sites))
     ctx = TDGLContext(mesh, fixed_sites=fixed_sites, fix_psi=options.terminal_psi is not None, u=u, gamma=gamma,
-                      device_id=options.device_id)
+                      device_id=options.device_id, substructure_levels=levels or None)
     try:
+        # (the substructured path: one AMG hierarchy, which the ensemble never runs; the factors built explicitly)
         ctx.build_poisson(rtol=options.pcg_rtol, max_iter=options.pcg_max_iter, nu=options.amg_smoothing_sweeps,
-                          dense_max_sites=ENSEMBLE_MAX_SITES)
+                          dense_max_sites=ENSEMBLE_DENSE_MAX_SITES, **(dict(amg_candidates=1) if levels else {}))
+        if levels and not ctx.build_substructure(check_rtol=min(1e-11, float(options.pcg_rtol))):
+            raise RuntimeError("solve_ensemble: the substructured factors of the Poisson matrix could not be built "
+                               f"({ctx.setup_times.get('substructure_error', 'their residual check failed')})")
         if not getattr(ctx, "dense_direct", False):
             raise RuntimeError("solve_ensemble: the dense inverse of the Poisson matrix could not be built "
                                "(a mesh in several pieces?)")
@@ -388,6 +416,7 @@ class EnsembleSolver:
         ens = None
         try:
             ens = EnsembleContext(ctx, R)
+            self.mu_path = ens.mu_path()
             self.setup_seconds = _time.perf_counter() - t_start
             return self._run(ctx, ens, t_start)
         finally:
@@ -490,6 +519,7 @@ class EnsembleSolver:
                 else:
                     active[r] = False
         ctx.synchronize()
+        mu_levels = self.mu_path[0]
         total = _time.perf_counter() - t_start
         cat = lambda xs: np.concatenate(xs) if xs else np.array([])  # noqa: E731
         solutions = []
@@ -506,6 +536,7 @@ class EnsembleSolver:
                 applied_vector_potential=rep.applied_vector_potential, terminal_currents=rep.terminal_currents,
                 disorder_epsilon=rep.disorder_epsilon, total_seconds=total,
                 stats=dict(steps_thermalizing=n_steps[r]["Thermalizing"], steps_simulating=n_steps[r]["Simulating"],
-                           mean_pcg_iterations=0.0, mu_solver="dense_ensemble", replica=r, replicas=R),
+                           mean_pcg_iterations=0.0, mu_solver="substructured_ensemble" if mu_levels else "dense_ensemble",
+                           replica=r, replicas=R, **(dict(mu_levels=mu_levels) if mu_levels else {})),
             ))
         return solutions

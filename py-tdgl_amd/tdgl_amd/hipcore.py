@@ -69,11 +69,14 @@ class TDGLContext:
     """Owns one ``tdgl_ctx`` (device buffers + stream) for a mesh."""
 
     def __init__(self, mesh, fixed_sites=None, fix_psi=True, u=5.79, gamma=10.0, device_id=0,
-                 reorder="rcm", n_owned=0, direct_solve=True):
+                 reorder="rcm", n_owned=0, direct_solve=True, substructure_levels=None):
         """``n_owned`` > 0: one-process-per-GPU mode, ``mesh`` is a rank's sub-mesh from
         `partition.build_local_problem` (owned sites first, then ghosts; no reordering).
         ``direct_solve=False``: never use a direct mu solve (plain RCM site order, AMG-PCG whatever the
-        mesh size; ``SolverOptions(sparse_solver="amg_pcg")``)."""
+        mesh size; ``SolverOptions(sparse_solver="amg_pcg")``).
+        ``substructure_levels`` 1 or 2: the site order of the substructured direct solve of that many levels
+        whatever the mesh size and `DENSE_MAX_SITES` / `SUB_MAX_SITES` / `SUB2_MAX_SITES` say (part and
+        super-block sizes as the size rule picks them; the factors: `build_substructure`)."""
         _lib.require_gpu()
         self._lib = _lib.load()
         self._ctx = C.c_void_p()
@@ -98,7 +101,11 @@ class TDGLContext:
         if reorder == "rcm":
             with _Stopwatch(self.setup_times, "reorder"):
                 perm = rcm_permutation(em.edges, self.n)
-                if self.direct_solve and 0 < max(self.SUB_MAX_SITES, self.DENSE_MAX_SITES) < self.n <= self.SUB2_MAX_SITES \
+                if substructure_levels is not None:
+                    if substructure_levels not in (1, 2) or not self.direct_solve:
+                        raise ValueError(f"substructure_levels must be 1 or 2 with a direct solve (got {substructure_levels})")
+                    perm = self._substructure_order(mesh, em, perm, substructure_levels)
+                elif self.direct_solve and 0 < max(self.SUB_MAX_SITES, self.DENSE_MAX_SITES) < self.n <= self.SUB2_MAX_SITES \
                         and self.SUB_MAX_SITES > 0:
                     # ... and beyond, up to SUB2_MAX_SITES, two levels of it (part interiors, the fine separators
                     # super-block by super-block, the top separator)
@@ -114,9 +121,7 @@ class TDGLContext:
                         perm, self._sub_part_ptr, self._sub_super_ptr, self._sub_big_ptr = substructure_order3(
                             np.asarray(mesh.sites), em.edges, block2, self.SUB2_SUPER or 4096, self.SUB3_BIG, rank_hint=rank)
                     else:
-                        super2 = self.SUB2_SUPER or max(2048, self.n // 60)
-                        perm, self._sub_part_ptr, self._sub_super_ptr = substructure_order2(
-                            np.asarray(mesh.sites), em.edges, block2, super2, rank_hint=rank)
+                        perm = self._substructure_order(mesh, em, perm, 2)
                 elif self.direct_solve and 0 < self.SUB_MAX_SITES and max(self.SUB_MAX_SITES, self.SUB2_MAX_SITES) < self.n <= self.PD_MAX_SITES:
                     # larger still: the context KEEPS the reverse Cuthill-McKee order (what the stencil kernels and the AMG
                     # hierarchy are fastest in); three levels of dissection are cut all the same, their factors become the
@@ -132,12 +137,7 @@ class TDGLContext:
                     # mid-size meshes: the substructured direct mu solve wants "interiors part by part,
                     # then the separator" as the site order (substructure.py); inside a part the sites keep
                     # their reverse Cuthill-McKee order
-                    from .substructure import substructure_order
-
-                    rank = np.empty(self.n, dtype=np.int64)
-                    rank[perm] = np.arange(self.n)
-                    block = self.SUB_BLOCK or (192 if self.n <= 8000 else max(320, int(320 * (self.n / 60000.0) ** (2.0 / 3.0))))
-                    perm, self._sub_part_ptr = substructure_order(np.asarray(mesh.sites), em.edges, block, rank_hint=rank)
+                    perm = self._substructure_order(mesh, em, perm, 1)
         elif reorder is None or reorder == "none":
             perm = np.arange(self.n, dtype=np.int32)
         else:
@@ -166,6 +166,26 @@ class TDGLContext:
         self.hierarchy = None
         self.dense_direct = False  # mu solve = a direct one (set_dense_inverse / build_substructure)
         self.substructure = None
+
+    def _substructure_order(self, mesh, em, perm, levels):
+        """The site order of the substructured direct solve of one or two levels (parts of `SUB_BLOCK` sites, or
+        of `SUB2_BLOCK` inside super-blocks of `SUB2_SUPER`; 0 = by size), the parts' sites kept in the order of
+        ``perm`` (reverse Cuthill-McKee).  Sets the part pointers; returns the permutation."""
+        rank = np.empty(self.n, dtype=np.int64)
+        rank[perm] = np.arange(self.n)
+        if levels == 1:
+            from .substructure import substructure_order
+
+            block = self.SUB_BLOCK or (192 if self.n <= 8000 else max(320, int(320 * (self.n / 60000.0) ** (2.0 / 3.0))))
+            perm, self._sub_part_ptr = substructure_order(np.asarray(mesh.sites), em.edges, block, rank_hint=rank)
+            return perm
+        from .substructure import substructure_order2
+
+        block2 = self.SUB2_BLOCK or (128 if self.n < 200_000 else 160)
+        super2 = self.SUB2_SUPER or max(2048, self.n // 60)
+        perm, self._sub_part_ptr, self._sub_super_ptr = substructure_order2(
+            np.asarray(mesh.sites), em.edges, block2, super2, rank_hint=rank)
+        return perm
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):

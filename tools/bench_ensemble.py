@@ -2,18 +2,21 @@
 """Aggregate throughput of `solve_ensemble` against the same runs made one after another with `tdgl.solve`.
 
     python tools/bench_ensemble.py --side 70 --replicas 32 --solve-time 20
-    python tools/bench_ensemble.py --side 116 --replicas 32 --max-sites 16000    # beyond ENSEMBLE_MAX_SITES
+    python tools/bench_ensemble.py --side 116 --replicas 32 --dense-max-sites 16000   # the dense inverse beyond its cap
+    python tools/bench_ensemble.py --side 224 --replicas 32 --solve-time 5        # substructured factors, two levels
     python tools/bench_ensemble.py --side 70 --replicas 32 --ramp                 # field ramps evaluated on the device
 
-Synthetic square film (`hex_jitter_points(side, side)`: side 70 = 5,791 sites, 100 = 11,774, 116 = 15,745) in a uniform field, one
-field per replica spread over [b_min, b_max].  Prints ONE JSON line:
+Synthetic square film (`hex_jitter_points(side, side)`: side 70 = 5,791 sites, 100 = 11,774, 116 = 15,745, 140 ~ 23k,
+224 ~ 59k, 320 ~ 120k) in a uniform field, one field per replica spread over [b_min, b_max].  Prints ONE JSON line:
   replicas, sites, replica_steps_per_s   the ensemble's loop (set-up excluded): accepted steps of all replicas / s
   sequential_steps_per_s                 `TDGLSolver.solve` (the product's single-run path) of the first
                                          `--sequential` replicas, one after another, set-up excluded
   speedup                                replica_steps_per_s / sequential_steps_per_s
   round_us, rounds                       mean wall time of one round (one attempt of every live replica)
-  dense_bytes_per_round                  bytes of G one round streams (the tiles, once per 16 replicas)
-  dense_GBps_if_whole_round              those bytes / round_us: a floor on the dense product's achieved bandwidth
+  mu_levels                              the ensemble's mu solve: 0 = dense inverse, 1 or 2 = substructured levels
+  factor_bytes_per_round                 bytes of the factors one round streams (dense tiles once per 16 replicas,
+                                         the levels' pools once per 8)
+  factor_GBps_if_whole_round             those bytes / round_us: a floor on the mu solve's achieved bandwidth
   max_dev_*                              largest deviation of any sequentially-run replica from its ensemble copy
 With --ramp every replica's field is LinearRamp(tmin=0, tmax=T/2, final=b_r) x the uniform field, held after T/2
 (T = --solve-time); the numbers above are then those of the ramped runs (sequential: tdgl.solve of the same ramps),
@@ -45,6 +48,7 @@ def main():
     ap.add_argument("--b-max", type=float, default=0.6)
     ap.add_argument("--sequential", type=int, default=4, help="replicas also run one after another (their rate is the baseline)")
     ap.add_argument("--max-sites", type=int, default=None, help="raise ENSEMBLE_MAX_SITES (to measure beyond the cap)")
+    ap.add_argument("--dense-max-sites", type=int, default=None, help="set ENSEMBLE_DENSE_MAX_SITES (the dense / substructured crossover)")
     ap.add_argument("--ramp", action="store_true", help="ramp each replica's field over the first half of the run")
     args = ap.parse_args()
 
@@ -53,6 +57,9 @@ def main():
 
     if args.max_sites is not None:
         ensemble.ENSEMBLE_MAX_SITES = args.max_sites
+    if args.dense_max_sites is not None:
+        ensemble.ENSEMBLE_DENSE_MAX_SITES = args.dense_max_sites
+        ensemble.ENSEMBLE_MAX_SITES = max(ensemble.ENSEMBLE_MAX_SITES, args.dense_max_sites)
     from tdgl_amd.finite_volume import Mesh
     from tdgl_amd.meshgen import hex_jitter_points, triangulate
 
@@ -111,9 +118,7 @@ def main():
         dev["mu"] = max(dev["mu"], float(np.abs((x.mu - x.mu.mean()) - (y.mu - y.mu.mean())).max()))
         dev["js"] = max(dev["js"], float(np.abs(x.supercurrent - y.supercurrent).max()))
 
-    DT = 128
-    nt = (n + DT - 1) // DT
-    dense_bytes = nt * (nt + 1) // 2 * DT * DT * 8 * ((R + 15) // 16)
+    levels, factor_bytes = solver.mu_path
     ens_rate = steps / loop
     seq_rate = seq_steps / seq_time if seq_time > 0 else float("nan")
     round_us = 1e6 * loop / max(rounds, 1)
@@ -122,7 +127,8 @@ def main():
         replica_steps=steps, loop_seconds=round(loop, 4), setup_seconds=round(solver.setup_seconds, 3),
         replica_steps_per_s=round(ens_rate, 1), sequential_runs=min(args.sequential, R), sequential_steps_per_s=round(seq_rate, 1),
         speedup=round(ens_rate / seq_rate, 2), rounds=rounds, batches=solver.ensemble_stats["batches"], round_us=round(round_us, 2),
-        dense_bytes_per_round=dense_bytes, dense_GBps_if_whole_round=round(dense_bytes / (round_us * 1e-6) / 1e9, 1),
+        mu_levels=levels, factor_bytes_per_round=factor_bytes,
+        factor_GBps_if_whole_round=round(factor_bytes / (round_us * 1e-6) / 1e9, 1),
         steps_min=min(len(s.dynamics.dt) for s in sols), steps_max=max(len(s.dynamics.dt) for s in sols),
         max_dev_dt_rel=dev["dt"], max_dev_abs_psi2=dev["abs_psi2"], max_dev_mu=dev["mu"], max_dev_js=dev["js"],
         ramp=args.ramp, **extra,
