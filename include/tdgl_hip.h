@@ -372,6 +372,12 @@ int tdgl_poisson_schur_finish(tdgl_ctx *ctx, const double *S, int32_t fp32_stora
 int tdgl_poisson_set_precond_times(tdgl_ctx *ctx, double t_apply_us, double t_vcycle_us);
 int tdgl_get_precond_direct_stats(tdgl_ctx *ctx, int64_t *out4, double *out4d, int32_t reset);
 int tdgl_get_precond_direct_layout(tdgl_ctx *ctx, int32_t *sym_rows3);
+/* With fp32 storage on one GPU the top separator's pseudo-inverse is kept in block low-rank form: every tile pair
+ * (128 x 128) off the diagonal whose rank at tau * ||G||_2 (TDGL_PD_BLR_TOL, default 3e-9) is at most 32 as fp32 factors
+ * U W^T, the rest as dense tiles (TDGL_PD_BLR=0: dense tiles only).  tdgl_get_precond_direct_blr: out6 = {in use,
+ * pairs stored as factors, tiles kept dense, largest rank, bytes one application streams, the same with dense tiles},
+ * out2 = {tau, ||G||_2 estimate}; zeros when not in use. */
+int tdgl_get_precond_direct_blr(tdgl_ctx *ctx, int64_t *out6, double *out2);
 /* The same storage for the direct SOLVE (fp64 factors; reference: the LU solve of tdgl/solver/solver.py:516): after every level
  * has been described, symmetric_tiles != 0 repacks the fp64 pool of each level that qualifies (all parts <= 256 rows, >= 256
  * parts) into tiles on or below the diagonal + -E^T rows on 64-byte lines and switches that level's way down to the tile
@@ -591,6 +597,10 @@ int tdgl_set_controller(tdgl_ctx *ctx, const tdgl_controller *c);
  * the arithmetic of the controller at solver.py:702-704; window == 0 averages the whole list like
  * Python's `vals[-0:]`.  No device work. */
 double tdgl_host_mean_tail(const double *values, int64_t n, int32_t window);
+/* Host-only: the block low-rank compression of one B x B block A (row major) -- column-pivoted, reorthogonalised
+ * Gram-Schmidt until the Frobenius norm of the remainder is <= tol; A ~ Q W^T with Q, W [kmax * B] column by column.
+ * Returns the rank, or -1 when kmax columns do not reach tol (-2: bad arguments).  No device work. */
+int32_t tdgl_host_blr_compress(const double *A, int32_t B, double tol, int32_t kmax, double *Q, double *W);
 /* Probe sites (device.probe_point_indices, solver.py:142, 691-694); n_probe may be 0. */
 int tdgl_set_probes(tdgl_ctx *ctx, const int32_t *sites, int32_t n_probe);
 

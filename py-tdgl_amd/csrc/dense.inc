@@ -774,6 +774,243 @@ static int sub_level_to_precond(tdgl_ctx *ctx, SubLevel &L, bool fp32_storage, b
     return TDGL_OK;
 }
 
+// ------------------------------------------------------------------ the preconditioner's top separator, block low-rank
+// Away from its diagonal the inverse of a separator's Schur complement is smooth (a discrete Green's function on the
+// separator curves): its off-diagonal tiles are numerically of low rank.  One tile A = G_IJ (DT x DT, row major) is
+// compressed by Gram-Schmidt with column pivoting (a rank-revealing QR, reorthogonalised): columns are taken until the
+// Frobenius norm of the remainder (I - Q Q^T) A -- a bound on its 2-norm -- is at most tol; then A ~ Q (A^T Q)^T.
+// Returns the rank (Q, W = A^T Q: column j at [j * B]), or -1 when kmax columns do not reach tol (the tile stays dense).
+static int blr_compress_block(const double *A, int B, double tol, int kmax, std::vector<double> &Q, std::vector<double> &W) {
+    std::vector<double> R(A, A + (size_t)B * B), cn((size_t)B), w((size_t)B);
+    Q.assign((size_t)B * kmax, 0.0);
+    const double tol2 = tol * tol;
+    int k = 0;
+    for (;;) {
+        double tot = 0.0, best = -1.0;
+        int piv = 0;
+        for (int c = 0; c < B; ++c) cn[c] = 0.0;
+        for (int r = 0; r < B; ++r)
+            for (int c = 0; c < B; ++c) cn[c] += R[(size_t)r * B + c] * R[(size_t)r * B + c];
+        for (int c = 0; c < B; ++c) {
+            tot += cn[c];
+            if (cn[c] > best) best = cn[c], piv = c;
+        }
+        if (tot <= tol2) break;
+        if (k == kmax) return -1;
+        double *q = &Q[(size_t)k * B];
+        for (int r = 0; r < B; ++r) q[r] = R[(size_t)r * B + piv];
+        for (int pass = 0; pass < 2; ++pass)  // (against the earlier columns, twice: orthogonal to working precision)
+            for (int j = 0; j < k; ++j) {
+                const double *qj = &Q[(size_t)j * B];
+                double d = 0.0;
+                for (int r = 0; r < B; ++r) d += qj[r] * q[r];
+                for (int r = 0; r < B; ++r) q[r] -= d * qj[r];
+            }
+        double nrm = 0.0;
+        for (int r = 0; r < B; ++r) nrm += q[r] * q[r];
+        nrm = std::sqrt(nrm);
+        if (!(nrm > 0.0)) break;
+        for (int r = 0; r < B; ++r) q[r] /= nrm;
+        for (int c = 0; c < B; ++c) w[c] = 0.0;
+        for (int r = 0; r < B; ++r)
+            for (int c = 0; c < B; ++c) w[c] += q[r] * R[(size_t)r * B + c];
+        for (int r = 0; r < B; ++r)
+            for (int c = 0; c < B; ++c) R[(size_t)r * B + c] -= q[r] * w[c];
+        ++k;
+    }
+    Q.resize((size_t)k * B);
+    W.assign((size_t)k * B, 0.0);
+    for (int j = 0; j < k; ++j)
+        for (int r = 0; r < B; ++r) {
+            const double qr = Q[(size_t)j * B + r];
+            for (int c = 0; c < B; ++c) W[(size_t)j * B + c] += A[(size_t)r * B + c] * qr;
+        }
+    return k;
+}
+
+// (the compression of one block, for the host tests: Q and W [kmax * B] column by column; returns the rank or -1)
+extern "C" int32_t tdgl_host_blr_compress(const double *A, int32_t B, double tol, int32_t kmax, double *Q, double *W) {
+    if (!A || !Q || !W || B <= 0 || kmax < 0) return -2;
+    std::vector<double> q, w;
+    const int k = blr_compress_block(A, B, tol, kmax, q, w);
+    if (k > 0) {
+        std::copy(q.begin(), q.end(), Q);
+        std::copy(w.begin(), w.end(), W);
+    }
+    return k;
+}
+
+static double env_double(const char *name, double dflt) {
+    const char *env = getenv(name);
+    if (!env || !env[0]) return dflt;
+    char *end = nullptr;
+    const double v = strtod(env, &end);
+    return (end && end != env && v > 0.0) ? v : dflt;
+}
+
+// The fp64 tiles of the top separator (f.dense.G) -> the block low-rank form f.blr (fp32), the fp64 tiles released.
+// Truncation tau * ||G||_2 per tile pair (||G||_2 by power iteration on the device, on the tiles as they are); tiles
+// whose rank would exceed DT / 4 stay dense.  If the form does not save at least 40 % of the bytes the dense fp32 tiles
+// are kept (dense_to_fp32).  (TDGL_PD_BLR=0: the dense tiles always -- for A/B measurements; TDGL_PD_BLR_TOL: tau.)
+constexpr double BLR_TOL = 3e-9;
+constexpr int BLR_MIN_TILES = 8;
+
+static int dense_to_blr(tdgl_ctx *ctx, DirectFactors &f) {
+    DenseTiles &D = f.dense;
+    BlrTop &Z = f.blr;
+    Z = BlrTop();
+    const int nt = D.tiles;
+    const int64_t n = D.n, ntile = (int64_t)nt * (nt + 1) / 2, T2 = (int64_t)DT * DT;
+    const double tau = env_double("TDGL_PD_BLR_TOL", BLR_TOL);
+    // ||G||_2: power iteration on a deterministic start vector of mean zero (G 1 = 0)
+    {
+        DevBuf<double> xv, yv;
+        HIP_TRY(ctx, xv.alloc((size_t)n, false));
+        HIP_TRY(ctx, yv.alloc((size_t)n));
+        std::vector<double> hx((size_t)n);
+        uint64_t st = 0x9e3779b97f4a7c15ull;
+        double mean = 0.0;
+        for (int64_t i = 0; i < n; ++i) {
+            st = st * 6364136223846793005ull + 1442695040888963407ull;
+            hx[i] = (double)(st >> 11) * 0x1.0p-53 - 0.5;
+            mean += hx[i];
+        }
+        mean /= (double)n;
+        for (auto &v : hx) v -= mean;
+        double lam = 0.0;
+        for (int it = 0; it < 30; ++it) {
+            double nx = 0.0;
+            for (double v : hx) nx += v * v;
+            nx = std::sqrt(nx);
+            if (!(nx > 0.0)) break;
+            for (auto &v : hx) v /= nx;
+            HIP_TRY(ctx, hipMemcpyAsync(xv.p, hx.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL((k_dense_sym_tiles<double>), dim3((unsigned)ntile), dim3(BLOCK), 0, ctx->stream, (int)n, nt,
+                               (const double *)D.G.p, (const double *)xv.p, D.part.p, (const StepCtl *)nullptr);
+            hipLaunchKernelGGL(k_dense_sym_finish, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(BLOCK), 0, ctx->stream, (int)n, nt,
+                               (const double *)D.part.p, (const double *)nullptr, (const int32_t *)nullptr, 0, (StepStatus *)nullptr, 0,
+                               yv.p, (const double *)nullptr, (double *)nullptr, (StepCtl *)nullptr, (StepRec *)nullptr);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipMemcpyAsync(hx.data(), yv.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            double ny = 0.0;
+            for (double v : hx) ny += v * v;
+            lam = std::sqrt(ny);
+        }
+        Z.norm = lam;
+    }
+    if (!(Z.norm > 0.0) || !std::isfinite(Z.norm)) return dense_to_fp32(ctx, D);
+    Z.tol = tau;
+    std::vector<double> hG((size_t)D.G.n);
+    HIP_TRY(ctx, hipMemcpy(hG.data(), D.G.p, hG.size() * sizeof(double), hipMemcpyDeviceToHost));
+    // every off-diagonal tile, on up to 16 host threads (tile order: t = I (I + 1) / 2 + J)
+    const int kmax = DT / 4;
+    std::vector<int> rank((size_t)ntile, -1);
+    std::vector<std::vector<double>> Qs((size_t)ntile), Ws((size_t)ntile);
+    std::atomic<int64_t> next{0};
+    auto work = [&]() {
+        for (int64_t t; (t = next.fetch_add(1)) < ntile;) {
+            int I = (int)((std::sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+            while ((int64_t)(I + 1) * (I + 2) / 2 <= t) ++I;
+            while ((int64_t)I * (I + 1) / 2 > t) --I;
+            if (t - (int64_t)I * (I + 1) / 2 == I) continue;  // (diagonal tile: dense)
+            rank[t] = blr_compress_block(&hG[(size_t)t * T2], DT, tau * Z.norm, kmax, Qs[t], Ws[t]);
+        }
+    };
+    {
+        const int nth = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+        std::vector<std::thread> pool;
+        for (int k = 1; k < nth; ++k) pool.emplace_back(work);
+        work();
+        for (auto &th : pool) th.join();
+    }
+    // columns per row block, in pair order: U_IJ in block I, W_IJ in block J
+    std::vector<int64_t> R((size_t)nt, 0), posU((size_t)ntile, 0), posW((size_t)ntile, 0);
+    std::vector<int32_t> dense_ij;
+    std::vector<char> is_dense((size_t)ntile, 0);
+    for (int I = 0; I < nt; ++I)
+        for (int J = 0; J <= I; ++J) {
+            const int64_t t = (int64_t)I * (I + 1) / 2 + J;
+            if (rank[t] < 0) {
+                is_dense[t] = 1;
+                dense_ij.push_back((I << 16) | J);
+                continue;
+            }
+            posU[t] = R[I];
+            R[I] += rank[t];
+            posW[t] = R[J];
+            R[J] += rank[t];
+            Z.pairs += 1;
+            Z.rank_max = std::max<int64_t>(Z.rank_max, rank[t]);
+        }
+    std::vector<int64_t> colbase((size_t)nt + 1, 0);
+    for (int K = 0; K < nt; ++K) colbase[K + 1] = colbase[K] + round_up(R[K], 4);
+    Z.cols = colbase[nt];
+    Z.ndense = (int)dense_ij.size();
+    Z.dense_bytes = ntile * T2 * (int64_t)sizeof(float);
+    Z.bytes = (int64_t)Z.ndense * T2 * (int64_t)sizeof(float) + 2 * Z.cols * DT * (int64_t)sizeof(float);
+    if (Z.bytes > Z.dense_bytes * 6 / 10) {  // (does not pay)
+        Z = BlrTop();
+        return dense_to_fp32(ctx, D);
+    }
+    std::vector<float> F((size_t)(Z.cols * DT), 0.0f), Gd((size_t)Z.ndense * T2);
+    std::vector<int32_t> twin((size_t)Z.cols, -1);
+    for (int I = 0, d = 0; I < nt; ++I)
+        for (int J = 0; J <= I; ++J) {
+            const int64_t t = (int64_t)I * (I + 1) / 2 + J;
+            if (is_dense[t]) {
+                for (int64_t e = 0; e < T2; ++e) Gd[(size_t)d * T2 + e] = (float)hG[(size_t)t * T2 + e];
+                ++d;
+                continue;
+            }
+            const int r = rank[t];
+            for (int c = 0; c < r; ++c) {
+                const int64_t cu = posU[t] + c, cw = posW[t] + c;
+                for (int row = 0; row < DT; ++row) {
+                    const int h = row / WAVE, rl = row % WAVE;
+                    F[(size_t)(DT * colbase[I] + ((int64_t)h * (colbase[I + 1] - colbase[I]) + cu) * WAVE + rl)] = (float)Qs[t][(size_t)c * DT + row];
+                    F[(size_t)(DT * colbase[J] + ((int64_t)h * (colbase[J + 1] - colbase[J]) + cw) * WAVE + rl)] = (float)Ws[t][(size_t)c * DT + row];
+                }
+                twin[(size_t)(colbase[I] + cu)] = (int32_t)(colbase[J] + cw);
+                twin[(size_t)(colbase[J] + cw)] = (int32_t)(colbase[I] + cu);
+            }
+        }
+    std::vector<int32_t> items, dslot_ptr((size_t)nt + 1, 0), dslot;
+    for (int K = 0; K < nt; ++K) {
+        const int32_t ng = (int32_t)((colbase[K + 1] - colbase[K]) / 4);
+        for (int32_t g0 = 0; g0 < ng; g0 += BLR_ITEM_GROUPS) {
+            items.insert(items.end(), {K, g0, std::min<int32_t>(g0 + BLR_ITEM_GROUPS, ng), 0});
+        }
+        for (int J = 0; J < nt; ++J) {
+            const int I = std::max(K, J), Jm = std::min(K, J);
+            if (is_dense[(size_t)((int64_t)I * (I + 1) / 2 + Jm)]) dslot.push_back(J);
+        }
+        dslot_ptr[K + 1] = (int32_t)dslot.size();
+    }
+    Z.nitems = (int)(items.size() / 4);
+    if (items.empty()) items.assign(4, 0);
+    HIP_TRY(ctx, Z.Gd.upload(Gd));
+    HIP_TRY(ctx, Z.dense_ij.upload(dense_ij));
+    if (F.empty()) F.assign(4, 0.0f);
+    if (twin.empty()) twin.assign(1, -1);
+    HIP_TRY(ctx, Z.F.upload(F));
+    HIP_TRY(ctx, Z.colbase.upload(colbase));
+    HIP_TRY(ctx, Z.twin.upload(twin));
+    HIP_TRY(ctx, Z.items.upload(items));
+    HIP_TRY(ctx, Z.coef.alloc((size_t)std::max<int64_t>(Z.cols, 1)));  // (zeroed: the padding columns)
+    HIP_TRY(ctx, Z.dslot_ptr.upload(dslot_ptr));
+    if (dslot.empty()) dslot.push_back(0);
+    HIP_TRY(ctx, Z.dslot.upload(dslot));
+    D.G.release();
+    return TDGL_OK;
+}
+
+static bool blr_wanted(const DirectFactors &f) {
+    const char *env = getenv("TDGL_PD_BLR");
+    if (env && env[0] == '0') return false;
+    return f.n_local == 0 && f.levels > 0 && f.dense.tiles >= BLR_MIN_TILES && f.dense.G.n > 0;
+}
+
 // The resident factors, READY and not laid out for the direct solve (checked by the callers), become the preconditioner's:
 // lane-per-row work lists, fp32 storage if asked.  The levels are converted in place: if that fails part way, the factors
 // are released (the CG goes on with the AMG V-cycle alone).
@@ -784,7 +1021,7 @@ static int sub_factors_to_precond(tdgl_ctx *ctx, bool fp32_storage, const char *
     const bool allow_sym = !(env && env[0] == '0');
     int rc = TDGL_OK;
     for (int k = 0; k < f.levels && rc == TDGL_OK; ++k) rc = sub_level_to_precond(ctx, f.lv[k], fp32_storage, allow_sym, who);
-    if (rc == TDGL_OK && fp32_storage) rc = dense_to_fp32(ctx, f.dense);
+    if (rc == TDGL_OK && fp32_storage) rc = blr_wanted(f) ? dense_to_blr(ctx, f) : dense_to_fp32(ctx, f.dense);
     if (rc != TDGL_OK) {
         ctx->direct.reset();
         return rc;
@@ -916,6 +1153,21 @@ extern "C" int tdgl_get_precond_direct_stats(tdgl_ctx *ctx, int64_t *out4, doubl
 extern "C" int tdgl_get_precond_direct_layout(tdgl_ctx *ctx, int32_t *sym_rows3) {
     if (!ctx || !sym_rows3) return TDGL_ERR_ARG;
     for (int k = 0; k < 3; ++k) sym_rows3[k] = ctx->direct ? ctx->direct->lv[k].sym_lds : 0;
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_get_precond_direct_blr(tdgl_ctx *ctx, int64_t *out6, double *out2) {
+    if (!ctx || !out6 || !out2) return TDGL_ERR_ARG;
+    const BlrTop *Z = ctx->direct ? &ctx->direct->blr : nullptr;
+    const bool on = Z && Z->ndense > 0;
+    out6[0] = on ? 1 : 0;
+    out6[1] = on ? Z->pairs : 0;
+    out6[2] = on ? Z->ndense : 0;
+    out6[3] = on ? Z->rank_max : 0;
+    out6[4] = on ? Z->bytes : 0;
+    out6[5] = on ? Z->dense_bytes : 0;
+    out2[0] = on ? Z->tol : 0.0;
+    out2[1] = on ? Z->norm : 0.0;
     return TDGL_OK;
 }
 

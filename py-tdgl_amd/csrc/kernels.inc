@@ -1363,21 +1363,14 @@ template <class VT> struct Pair2;
 template <> struct Pair2<double> { typedef double2 type; };
 template <> struct Pair2<float> { typedef float2 type; };
 
+// (body: tile (I, J) at `tile`; k_blr_project runs it on the tiles the block low-rank form keeps dense)
 template <class VT>
-__global__ __launch_bounds__(BLOCK, 4) void k_dense_sym_tiles(int n, int nt, const VT *__restrict__ Gp,
-                                                           const double *__restrict__ b, double *__restrict__ part,
-                                                           const StepCtl *__restrict__ ctl) {
+__device__ __forceinline__ void dense_sym_tile_body(int I, int J, int n, int nt, const VT *__restrict__ tile,
+                                                    const double *__restrict__ b, double *__restrict__ part) {
     typedef typename Pair2<VT>::type V2;
     __shared__ double shc[BLOCK / WAVE][DT];
-    if (ctl && !ctl->live) return;  // run-ahead: dead step
-    const int t = blockIdx.x;
-    int I = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-    while ((I + 1) * (I + 2) / 2 <= t) ++I;
-    while (I * (I + 1) / 2 > t) --I;
-    const int J = t - I * (I + 1) / 2;
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    const V2 *__restrict__ g =
-        reinterpret_cast<const V2 *>(Gp + (int64_t)t * DT * DT) + (w * 32) * (DT / 2) + lane;
+    const V2 *__restrict__ g = reinterpret_cast<const V2 *>(tile) + (w * 32) * (DT / 2) + lane;
     const int cj = J * DT + 2 * lane;
     const double bjx = cj < n ? b[cj] : 0.0, bjy = cj + 1 < n ? b[cj + 1] : 0.0;
     double cx = 0.0, cy = 0.0;
@@ -1422,6 +1415,19 @@ __global__ __launch_bounds__(BLOCK, 4) void k_dense_sym_tiles(int n, int nt, con
             part[(int64_t)I * ldp + J * DT + threadIdx.x] = s;
         }
     }
+}
+
+template <class VT>
+__global__ __launch_bounds__(BLOCK, 4) void k_dense_sym_tiles(int n, int nt, const VT *__restrict__ Gp,
+                                                           const double *__restrict__ b, double *__restrict__ part,
+                                                           const StepCtl *__restrict__ ctl) {
+    if (ctl && !ctl->live) return;  // run-ahead: dead step
+    const int t = blockIdx.x;
+    int I = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+    while ((I + 1) * (I + 2) / 2 <= t) ++I;
+    while (I * (I + 1) / 2 > t) --I;
+    const int J = t - I * (I + 1) / 2;
+    dense_sym_tile_body<VT>(I, J, n, nt, Gp + (int64_t)t * DT * DT, b, part);
 }
 
 // y = W x + V v: sparse W (CSR) plus dense row-major V [n_rows, ldv] (zero padded to a 16-byte
@@ -2228,6 +2234,12 @@ __device__ __forceinline__ void step_controller(StepCtl *__restrict__ ctl, StepR
     }
 }
 
+__device__ __forceinline__ void dense_finish_tail(int blk, int n, double v, int anybad, const double *__restrict__ dmax_part,
+                                                  const int32_t *__restrict__ fail_part, int nfail,
+                                                  StepStatus *__restrict__ st, double *__restrict__ y,
+                                                  const double *__restrict__ u, double *__restrict__ upart,
+                                                  StepCtl *__restrict__ ctl, StepRec *__restrict__ rec);
+
 // Second half of the symmetric dense solve: y_i = sum over the nt slots of `part`, in slot order; 64 outputs
 // per workgroup, wave w takes the slots w, w + 4, ... (all loads independent), the four waves meet in LDS
 // in a fixed order.  Held back when the psi update of this step failed.  In the time
@@ -2263,8 +2275,20 @@ __device__ __forceinline__ void dense_sym_finish_body(int blk, int n, int nt, co
     }
     sh[w][lane] = (s[0] + s[1]) + (s[2] + s[3]);
     const int anybad = __syncthreads_or(bad);
+    const double v = (sh[0][lane] + sh[1][lane]) + (sh[2][lane] + sh[3][lane]);
+    dense_finish_tail(blk, n, v, anybad, dmax_part, fail_part, nfail, st, y, u, upart, ctl, rec);
+}
+
+// What the second launch of a dense solve does with its 64 sums v (lane = row; wave 0 writes them): the held-back write
+// of y, the workgroup's share of u . x_S, and (workgroup 0) the step's status block / the run-ahead controller
+__device__ __forceinline__ void dense_finish_tail(int blk, int n, double v, int anybad, const double *__restrict__ dmax_part,
+                                                  const int32_t *__restrict__ fail_part, int nfail,
+                                                  StepStatus *__restrict__ st, double *__restrict__ y,
+                                                  const double *__restrict__ u, double *__restrict__ upart,
+                                                  StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    const int i = blk * WAVE + lane;
     if (w == 0) {
-        const double v = (sh[0][lane] + sh[1][lane]) + (sh[2][lane] + sh[3][lane]);
         if (i < n && !anybad) y[i] = v;
         if (u) {  // substructured solve: this workgroup's share of u . x_S (k_sub_up removes the mean with it)
             const double c = wave_sum(i < n ? u[i] * v : 0.0);
@@ -2295,6 +2319,145 @@ __global__ __launch_bounds__(BLOCK) void k_dense_sym_finish(int n, int nt, const
                                                             const double *__restrict__ u, double *__restrict__ upart,
                                                             StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
     dense_sym_finish_body(blockIdx.x, n, nt, part, dmax_part, fail_part, nfail, st, guard, y, u, upart, ctl, rec);
+}
+
+// The preconditioner's top separator in block low-rank form (dense.inc: dense_to_blr).  The tile pairs (I, J), I > J,
+// whose fp64 block is numerically of low rank are kept as G_IJ ~ U_IJ W_IJ^T (fp32 factors of r columns); the
+// diagonal tiles and the blocks that do not pay stay dense tiles.  Row block K of DT rows owns the columns F_K = every
+// U_KJ (J < K) and every W_IK (I > K) in pair order: y_K = sum over K's dense tiles + F_K c_K, where the coefficient
+// of a U_KJ column is the matching W_KJ column's projection onto x_J and vice versa -- so both launches stream the
+// same columns, once as projections (c = F^T x, written to the twin column's slot) and once back into y.  Storage of
+// F_K: its columns padded to a multiple of 4, row half h (64 rows) of column c at F + DT * colbase[K] + (h * R + c) * 64:
+// four columns of one half are one contiguous kilobyte, what a wavefront reads in one request (float4 per lane).
+struct BlrItem {
+    int32_t K, g0, g1, pad;  // a wavefront's groups [g0, g1) of four columns of row block K
+};
+
+struct BlrArgs {
+    int ndense;                          // dense tiles: the first workgroups of k_blr_project
+    int nitems;                          // wavefront items of the projections
+    const int32_t *__restrict__ dense_ij;  // [ndense] I << 16 | J
+    const float *__restrict__ Gd;        // [ndense][DT * DT] the dense tiles, as k_dense_sym_tiles stores them
+    const float *__restrict__ F;         // the columns
+    const int64_t *__restrict__ colbase;  // [nt + 1] first column of row block K (multiples of 4)
+    const int32_t *__restrict__ twin;    // [columns] the slot of coef the column's projection goes to (-1: padding)
+    const BlrItem *__restrict__ items;   // [nitems]
+    double *__restrict__ coef;           // [columns] (padding: 0, never written)
+    const int32_t *__restrict__ dslot_ptr;  // [nt + 1] the dense slots of part row block K sums ...
+    const int32_t *__restrict__ dslot;   // ... (the J of its dense tiles, the diagonal included)
+};
+
+constexpr int BLR_ITEM_GROUPS = 8;  // groups of four columns per wavefront item of k_blr_project
+
+// Launch 1: the dense tiles (k_dense_sym_tiles' body, slots of `part`) and every column's projection c = F_K^T x_K.
+// A wavefront takes BLR_ITEM_GROUPS groups of four columns; lane l reads rows 4 (l & 15) .. + 3 of column 4 g + l / 16
+// in both halves (two 1-KB requests per group and wavefront), the 16 lanes of a column are summed by a butterfly.
+__global__ __launch_bounds__(BLOCK, 4) void k_blr_project(int n, int nt, BlrArgs a, const double *__restrict__ b,
+                                                       double *__restrict__ part, const StepCtl *__restrict__ ctl) {
+    if (ctl && !ctl->live) return;  // run-ahead: dead step
+    if ((int)blockIdx.x < a.ndense) {  // (workgroup-uniform)
+        const int ij = a.dense_ij[blockIdx.x];
+        dense_sym_tile_body<float>(ij >> 16, ij & 0xffff, n, nt, a.Gd + (int64_t)blockIdx.x * DT * DT, b, part);
+        return;
+    }
+    const int item = ((int)blockIdx.x - a.ndense) * (BLOCK / WAVE) + (int)(threadIdx.x / WAVE);
+    if (item >= a.nitems) return;  // (wave-uniform)
+    const BlrItem it = a.items[item];
+    const int lane = threadIdx.x & (WAVE - 1), rr = 4 * (lane & 15), cl = lane >> 4;
+    const int64_t cb = a.colbase[it.K];
+    const int R = (int)(a.colbase[it.K + 1] - cb);
+    const float *__restrict__ Fk = a.F + cb * DT;
+    double xv[2][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int row = it.K * DT + h * WAVE + rr + j;
+            xv[h][j] = row < n ? b[row] : 0.0;
+        }
+    float4 f[BLR_ITEM_GROUPS][2];
+#pragma unroll
+    for (int u = 0; u < BLR_ITEM_GROUPS; ++u) {  // (every request first: groups past the item's end repeat its last)
+        const int col = 4 * min(it.g0 + u, it.g1 - 1) + cl;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) f[u][h] = *reinterpret_cast<const float4 *>(Fk + ((int64_t)h * R + col) * WAVE + rr);
+    }
+#pragma unroll
+    for (int u = 0; u < BLR_ITEM_GROUPS; ++u) {
+        double s = 0.0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            s += ((double)f[u][h].x * xv[h][0] + (double)f[u][h].y * xv[h][1]) + ((double)f[u][h].z * xv[h][2] + (double)f[u][h].w * xv[h][3]);
+        s += __shfl_xor(s, 1, WAVE);
+        s += __shfl_xor(s, 2, WAVE);
+        s += __shfl_xor(s, 4, WAVE);
+        s += __shfl_xor(s, 8, WAVE);
+        if ((lane & 15) == 0 && it.g0 + u < it.g1) {
+            const int32_t t = a.twin[cb + 4 * (it.g0 + u) + cl];
+            if (t >= 0) a.coef[t] = s;
+        }
+    }
+}
+
+// Launch 2: y of 64 rows (half h of row block K = blk / 2) = its dense slots of `part` + F_K c_K, then everything
+// k_dense_sym_finish does (dense_finish_tail).  Wave w takes the groups w, w + 4, ... (eight requests of a kilobyte in
+// flight per lane), lanes l, l + 16, l + 32, l + 48 are summed by shuffles, the four waves meet in LDS in a fixed order.
+__global__ __launch_bounds__(BLOCK) void k_blr_finish(int n, int nt, BlrArgs a, const double *__restrict__ part,
+                                                      const double *__restrict__ dmax_part, const int32_t *__restrict__ fail_part,
+                                                      int nfail, StepStatus *__restrict__ st, int guard, double *__restrict__ y,
+                                                      const double *__restrict__ u, double *__restrict__ upart,
+                                                      StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
+    __shared__ double shl[BLOCK / WAVE][WAVE];
+    __shared__ double shd[BLOCK / WAVE][WAVE];
+    if (ctl && !ctl->live) return;  // run-ahead: a dead step does nothing
+    const int blk = blockIdx.x, K = blk >> 1, h = blk & 1;
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    const int rr = 4 * (lane & 15), cl = lane >> 4;
+    const int i = blk * WAVE + lane;
+    const int64_t ldp = (int64_t)nt * DT;
+    int bad = 0;
+    if (guard && fail_part)
+        for (int k = threadIdx.x; k < nfail; k += BLOCK) bad |= fail_part[k];
+    const int64_t cb = a.colbase[K];
+    const int R = (int)(a.colbase[K + 1] - cb), ng = R / 4;
+    const float *__restrict__ Fh = a.F + cb * DT + (int64_t)h * R * WAVE + rr;
+    const double *__restrict__ ck = a.coef + cb;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    constexpr int U = 8;
+    for (int g0 = w; g0 < ng; g0 += U * (BLOCK / WAVE)) {
+        float4 f[U];
+        double c[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int g = g0 + k * (BLOCK / WAVE), col = 4 * min(g, ng - 1) + cl;
+            f[k] = *reinterpret_cast<const float4 *>(Fh + (int64_t)col * WAVE);
+            c[k] = ck[col];
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const double cc = g0 + k * (BLOCK / WAVE) < ng ? c[k] : 0.0;
+            acc[0] += (double)f[k].x * cc;
+            acc[1] += (double)f[k].y * cc;
+            acc[2] += (double)f[k].z * cc;
+            acc[3] += (double)f[k].w * cc;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        acc[j] += __shfl_xor(acc[j], 16, WAVE);
+        acc[j] += __shfl_xor(acc[j], 32, WAVE);
+    }
+    if (lane < 16)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) shl[w][rr + j] = acc[j];
+    double ds = 0.0;
+    if (i < n)
+        for (int k = a.dslot_ptr[K] + w; k < a.dslot_ptr[K + 1]; k += BLOCK / WAVE) ds += part[(int64_t)a.dslot[k] * ldp + i];
+    shd[w][lane] = ds;
+    const int anybad = __syncthreads_or(bad);
+    const double v = ((shd[0][lane] + shl[0][lane]) + (shd[1][lane] + shl[1][lane])) +
+                     ((shd[2][lane] + shl[2][lane]) + (shd[3][lane] + shl[3][lane]));
+    dense_finish_tail(blk, n, v, anybad, dmax_part, fail_part, nfail, st, y, u, upart, ctl, rec);
 }
 
 // ------------------------------------------------------------------ substructured direct solve

@@ -1307,11 +1307,22 @@ static bool direct_solve_launch_t(tdgl_ctx *ctx, const double *b, double *x, boo
         vec = f.lv[k].w.p + f.lv[k].nI;
     }
     const SubLevel &L0 = f.lv[0], &T = f.lv[K - 1];
-    hipLaunchKernelGGL((k_dense_sym_tiles<VT>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt,
-                       SubPools<VT>::dense(f.dense), vec, f.dense.part.p, (const StepCtl *)ctl);
-    hipLaunchKernelGGL(k_dense_sym_finish, dim3(f.nfin), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt, (const double *)f.dense.part.p,
-                       (const double *)ctx->psi_dmax_part.p, (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, 0, T.xs.p,
-                       (const double *)T.u.p, f.upart.p, ctl, rec);
+    if (f.blr.ndense > 0) {  // the top separator in block low-rank form (preconditioner, dense.inc: dense_to_blr)
+        const BlrTop &Z = f.blr;
+        const BlrArgs a{Z.ndense, Z.nitems, Z.dense_ij.p, Z.Gd.p, Z.F.p, Z.colbase.p, Z.twin.p,
+                        reinterpret_cast<const BlrItem *>(Z.items.p), Z.coef.p, Z.dslot_ptr.p, Z.dslot.p};
+        hipLaunchKernelGGL(k_blr_project, dim3((unsigned)(Z.ndense + (Z.nitems + BLOCK / WAVE - 1) / (BLOCK / WAVE))), dim3(BLOCK), 0,
+                           ctx->stream, (int)T.nS, nt, a, vec, f.dense.part.p, (const StepCtl *)ctl);
+        hipLaunchKernelGGL(k_blr_finish, dim3(f.nfin), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt, a, (const double *)f.dense.part.p,
+                           (const double *)ctx->psi_dmax_part.p, (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, 0, T.xs.p,
+                           (const double *)T.u.p, f.upart.p, ctl, rec);
+    } else {
+        hipLaunchKernelGGL((k_dense_sym_tiles<VT>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt,
+                           SubPools<VT>::dense(f.dense), vec, f.dense.part.p, (const StepCtl *)ctl);
+        hipLaunchKernelGGL(k_dense_sym_finish, dim3(f.nfin), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt, (const double *)f.dense.part.p,
+                           (const double *)ctx->psi_dmax_part.p, (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, 0, T.xs.p,
+                           (const double *)T.u.p, f.upart.p, ctl, rec);
+    }
     if (K == 1) {
         launch_sub_up<VT>(ctx, L0, x, SubMean{L0.w.p + L0.nI + L0.nS, f.upart.p, nullptr, nullptr, L0.parts, f.nfin, 0, 0, inv_n, 0.0, nullptr, nullptr},
                           fail, ctl);

@@ -7,6 +7,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -15,6 +16,7 @@
 #include <memory>
 #include <numeric>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "tdgl_hip.h"
@@ -270,6 +272,26 @@ struct DenseTiles {
     int64_t n = 0;                         // order of the matrix
 };
 
+// the preconditioner's top separator in block low-rank form (dense.inc: dense_to_blr; kernels.inc: k_blr_project /
+// k_blr_finish).  ndense == 0: not in use (the dense fp32 tiles of DirectFactors::dense are)
+struct BlrTop {
+    DevBuf<float> Gd;                      // [ndense][DT * DT] the tiles kept dense (the diagonal, the blocks that do not pay)
+    DevBuf<int32_t> dense_ij;              // [ndense] I << 16 | J
+    DevBuf<float> F;                       // the low-rank columns of every row block
+    DevBuf<int64_t> colbase;               // [tiles + 1]
+    DevBuf<int32_t> twin;                  // [cols]
+    DevBuf<int32_t> items;                 // [nitems][4] BlrItem
+    DevBuf<double> coef;                   // [cols]
+    DevBuf<int32_t> dslot_ptr, dslot;      // the dense slots of each row block
+    int ndense = 0, nitems = 0;
+    int64_t cols = 0;                      // columns (padded), summed over the row blocks
+    int64_t pairs = 0;                     // tile pairs stored as factors
+    int64_t bytes = 0;                     // what one application streams (each column twice: projection and way back)
+    int64_t dense_bytes = 0;               // the same with every tile dense (k_dense_sym_tiles)
+    int64_t rank_max = 0;
+    double tol = 0.0, norm = 0.0;          // truncation tau, ||G||_2 estimate
+};
+
 // Everything a direct mu solve owns (dense.inc, schur.inc): the dense inverse of the whole matrix, or the levels of a
 // nested dissection with the dense pseudo-inverse of the last level's separator; as the CG's preconditioner also the
 // dissection map and its work vectors; in one-process-per-GPU mode the rank-level interface.  tdgl_ctx::direct holds it,
@@ -292,6 +314,7 @@ struct DirectFactors {
     int nfin = 0;                          // workgroups of the separator's k_dense_sym_finish
     DevBuf<double> upart;                  // their partials of u . x_S
     DevBuf<double> mean;                   // [1] several levels: the mean of the solution, left for the first level's way up
+    BlrTop blr;                            // (preconditioner, fp32) the top separator in block low-rank form
     bool fp32 = false;                     // the pools and the dense tiles are stored in fp32
     // the preconditioner's application in the dissection order: map[i] = the context's index of dissection position i
     DevBuf<int32_t> map;

@@ -264,6 +264,7 @@ SIGNATURES = {
     "tdgl_poisson_set_precond_times": (C.c_int, [_CTX, C.c_double, C.c_double]),
     "tdgl_get_precond_direct_stats": (C.c_int, [_CTX, C.POINTER(C.c_int64), c_f64p, C.c_int32]),
     "tdgl_get_precond_direct_layout": (C.c_int, [_CTX, C.POINTER(C.c_int32)]),
+    "tdgl_get_precond_direct_blr": (C.c_int, [_CTX, c_i64p, c_f64p]),
     "tdgl_poisson_set_substructure_layout": (C.c_int, [_CTX, C.c_int32]),
     "tdgl_poisson_build_substructure": (C.c_int, [_CTX, C.POINTER(SubstructurePlan), c_f64p]),
     "tdgl_set_halo_plan": (C.c_int, [_CTX, C.POINTER(HaloPlan)]),
@@ -293,6 +294,7 @@ SIGNATURES = {
     "tdgl_set_controller": (C.c_int, [_CTX, C.POINTER(Controller)]),
     "tdgl_set_probes": (C.c_int, [_CTX, c_i32p, C.c_int32]),
     "tdgl_host_mean_tail": (C.c_double, [c_f64p, C.c_int64, C.c_int32]),
+    "tdgl_host_blr_compress": (C.c_int32, [c_f64p, C.c_int32, C.c_double, C.c_int32, c_f64p, c_f64p]),
     "tdgl_begin_stage": (C.c_int, [_CTX]),
     "tdgl_run": (
         C.c_int,

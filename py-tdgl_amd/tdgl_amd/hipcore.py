@@ -558,6 +558,10 @@ class TDGLContext:
                     top_separator=levels[1].n_sep, super_super_blocks=levels[2].n_parts, top_top_separator=levels[2].n_sep,
                     bytes_per_application=int(4 * entries + 12 * sum(lv.coupling.nnz for lv in levels) + 2 * 20 * self.n),
                     t_apply_us=round(ta.value, 1), t_vcycle_us=round(tv.value, 1))
+        blr = self.precond_direct_blr()
+        if blr["on"]:  # (the top separator's tiles replaced by the block low-rank form)
+            info["bytes_per_application"] += blr["bytes"] - 4 * sym(levels[2].n_sep)
+            info["top_separator_blr"] = blr
         del levels, packed
         # the check: with the factors forced, a white-noise right-hand side from a zero guess
         self._chk(self._lib.tdgl_poisson_precond_choice(self._ctx, 1))
@@ -645,6 +649,15 @@ class TDGLContext:
         self._chk(self._lib.tdgl_get_precond_direct_stats(self._ctx, o4, o3, int(bool(reset))))
         return dict(solves_factors=int(o4[0]), iterations_factors=int(o4[1]), solves_vcycle=int(o4[2]), iterations_vcycle=int(o4[3]),
                     handovers=int(o3[3]), t_apply_us=round(o3[0], 1), t_vcycle_us=round(o3[1], 1), decades_per_application=round(o3[2], 2))
+
+    def precond_direct_blr(self):
+        """`tdgl_get_precond_direct_blr`: the top separator of the fp32 factors in block low-rank form -- whether it is,
+        tile pairs stored as factors, tiles kept dense, the largest rank, bytes per application (and with dense tiles),
+        the truncation tau and the ||G||_2 it is relative to."""
+        o6, o2 = (C.c_int64 * 6)(), (C.c_double * 2)()
+        self._chk(self._lib.tdgl_get_precond_direct_blr(self._ctx, o6, o2))
+        return dict(on=bool(o6[0]), pairs=int(o6[1]), dense_tiles=int(o6[2]), rank_max=int(o6[3]), bytes=int(o6[4]),
+                    dense_bytes=int(o6[5]), tau=float(o2[0]), norm=float(o2[1]))
 
     def precond_direct_layout(self):
         """Per level of the fp32-stored factors: the rows of a part its way down stages when the level keeps only the
