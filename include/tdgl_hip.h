@@ -634,6 +634,17 @@ int tdgl_get_induced_vector_potential(tdgl_ctx *ctx, double *A_induced);
  * edge_current [n_edges] -> site average -> A_new [n_edges, 2] = sum_j <K>_j area_j / |r_e - r_j|.
  * No heavy-ball update, A_induced is not touched. */
 int tdgl_induced_vector_potential(tdgl_ctx *ctx, const double *edge_current, double *A_new);
+/* Opt-in fast evaluation of the same sum: a barycentric Lagrange treecode (csrc/screening_tree.inc).
+ * Call after tdgl_set_screening.  degree p in [2, 16]: every far cluster acts through its (p + 1)^2 Chebyshev proxy
+ * points; theta in (0, 1): a cluster is far from a batch of edge centres when (r_cluster + r_batch) < theta * distance.
+ * The trees, proxies, transfer matrices and interaction lists are built here, once, on the host; the screening
+ * iterations of tdgl_run and tdgl_induced_vector_potential then use the treecode.  degree == 0 returns to the
+ * all-pairs kernel (bit for bit).  Invalid values fail with TDGL_ERR_ARG and leave the previous method in place;
+ * one-process-per-GPU mode is refused (TDGL_ERR_ARG).  A later tdgl_set_screening returns to the all-pairs kernel. */
+int tdgl_set_screening_tree(tdgl_ctx *ctx, int32_t degree, double theta);
+/* out6 = {clusters, levels, target batches, far pairs, near pairs, set-up microseconds} of the active treecode (pairs
+ * summed over all edge centres: proxies of far clusters, sources of near ones); all zero with the all-pairs kernel. */
+int tdgl_get_screening_tree_stats(tdgl_ctx *ctx, int64_t *out6);
 
 /* ------------------------------------------------------------------ the time loop */
 /* Start a Runner stage (runner.py:294-297, 315-318): time = 0, stage step = 0.  Runner.dt
@@ -821,7 +832,8 @@ int tdgl_ensemble_get_mu_path(tdgl_ensemble *ens, int32_t *levels, int64_t *fact
  * tdgl_last_error then reports stale reads and the XCC_ID of workgroups 0-15;
  * 16-20 = HBM-cold streaming over a 1 GiB buffer: grid-stride read-only sum (16; 18 with 8 loads per lane
  * in flight, 19 with 16 workgroups per CU, 20 one workgroup per 512 entries), copy 512 MiB -> 512 MiB (17);
- * 21 = one workgroup of 1024 threads reading an L2-resident 2 MiB buffer 50 times (bytes one CU gets).
+ * 21 = one workgroup of 1024 threads reading an L2-resident 2 MiB buffer 50 times (bytes one CU gets);
+ * 22 = one evaluation of the screening treecode (gather, upward pass, evaluation; tdgl_set_screening_tree).
  * tools/bench_barrier.py prints all of them. */
 int tdgl_time_kernel(tdgl_ctx *ctx, int32_t kernel, int32_t reps, double *avg_ms);
 /* Enable/disable HIP-event timing of the fused psi-Laplacian kernel inside tdgl_run, and

@@ -157,6 +157,7 @@ static int set_screening_impl(tdgl_ctx *ctx, const tdgl_screening_options *o, co
     if (!(o->step_size > 0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "screening_step_size must be in > 0 (got %g).", o->step_size);
     if (!(o->tolerance > 0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "screening_tolerance must be in > 0 (got %g).", o->tolerance);
     ctx->scr = *o;
+    ctx->scr_tree.reset();  // (new geometry: the all-pairs kernel until tdgl_set_screening_tree is called again)
     const bool global = owned_gid != nullptr;
     const int64_t n = ctx->n, m = ctx->m;
     const int64_t ns = global ? ctx->n_global : n;  // sites of the 1/r sum
@@ -219,6 +220,7 @@ extern "C" int tdgl_set_screening(tdgl_ctx *ctx, const tdgl_screening_options *o
     CTX_GUARD(ctx);
     if (!o) {
         ctx->scr_enabled = false;
+        ctx->scr_tree.reset();
         return TDGL_OK;
     }
     if (distributed(ctx) || ctx->n_own != ctx->n)
@@ -232,6 +234,7 @@ extern "C" int tdgl_set_screening_distributed(tdgl_ctx *ctx, const tdgl_screenin
     CTX_GUARD(ctx);
     if (!o) {
         ctx->scr_enabled = false;
+        ctx->scr_tree.reset();
         return TDGL_OK;
     }
     if (ctx->send_ptr.empty() || ctx->n_global < ctx->n_own)
@@ -271,13 +274,26 @@ extern "C" int tdgl_get_induced_vector_potential(tdgl_ctx *ctx, double *A) {
     return TDGL_OK;
 }
 
-static void launch_induced(tdgl_ctx *ctx) {
+static void launch_direct(tdgl_ctx *ctx) {
     const int gx = (int)((ctx->m + (int64_t)EPT * BLOCK - 1) / ((int64_t)EPT * BLOCK));
     const bool global = ctx->scr_Jglobal.n > 0;
     hipLaunchKernelGGL(k_induced_vector_potential, dim3(gx, ctx->scr_chunks), dim3(BLOCK), 0, ctx->stream, ctx->m,
                        ctx->scr_n_sites, ctx->m_pad, ctx->scr_tiles_per_chunk, ctx->scr_edge_xy.p, ctx->scr_site_xyw.p,
                        global ? ctx->scr_Jglobal.p : ctx->scr_Jsite.p, ctx->scr_Anew.p);
 }
+
+static bool tree_active(const tdgl_ctx *ctx);
+static void launch_tree(tdgl_ctx *ctx);  // (screening_tree.inc)
+
+// A_new for the site currents in scr_Jsite with the active method: partial sums in the first induced_chunks()
+// chunks of scr_Anew (the treecode writes one)
+static void launch_induced(tdgl_ctx *ctx) {
+    if (tree_active(ctx))
+        launch_tree(ctx);
+    else
+        launch_direct(ctx);
+}
+static int induced_chunks(const tdgl_ctx *ctx) { return tree_active(ctx) ? 1 : ctx->scr_chunks; }
 
 // Single-operator entry point: A_new = sum_j <K>_j area_j / |r_e - r_j| for an edge current K
 // (reference edge order in and out), without the heavy-ball update.
@@ -296,13 +312,14 @@ extern "C" int tdgl_induced_vector_potential(tdgl_ctx *ctx, const double *edge_c
                        ctx->lap_pat.n_rows, ctx->lap_pat.slice_off.p, ctx->lap_slot_edge.p, dk.p, zero.p,
                        ctx->e_dirx.p, ctx->e_diry.p, ctx->e_inv_len.p, ctx->scr_inv_2deg.p, ctx->scr_Jsite.p);
     launch_induced(ctx);
-    std::vector<double> part((size_t)ctx->scr_chunks * 2 * ctx->m_pad);
+    const int chunks = induced_chunks(ctx);
+    std::vector<double> part((size_t)chunks * 2 * ctx->m_pad);
     HIP_TRY(ctx, hipMemcpyAsync(part.data(), ctx->scr_Anew.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipGetLastError());
     for (int64_t k = 0; k < m; ++k) {
         double ax = 0.0, ay = 0.0;
-        for (int c = 0; c < ctx->scr_chunks; ++c) {  // same order as k_polyak
+        for (int c = 0; c < chunks; ++c) {  // same order as k_polyak
             ax += part[(size_t)c * 2 * ctx->m_pad + 2 * k];
             ay += part[(size_t)c * 2 * ctx->m_pad + 2 * k + 1];
         }
@@ -337,7 +354,7 @@ static int screening_update_A(tdgl_ctx *ctx, double *err) {
     launch_induced(ctx);
     HIP_TRY(ctx, hipMemsetAsync(ctx->scr_err_bits.p, 0, sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_polyak, dim3(grid_for(ctx->m)), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad,
-                       ctx->scr_chunks, ctx->scr.step_size, ctx->scr.step_drag, ctx->scr_Anew.p, ctx->scr_Aind.p,
+                       induced_chunks(ctx), ctx->scr.step_size, ctx->scr.step_drag, ctx->scr_Anew.p, ctx->scr_Aind.p,
                        ctx->scr_vel.p, ctx->scr_err_bits.p);
     unsigned long long bits = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&bits, ctx->scr_err_bits.p, sizeof(bits), hipMemcpyDeviceToHost, ctx->stream));

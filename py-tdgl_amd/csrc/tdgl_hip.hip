@@ -604,6 +604,7 @@ static inline int64_t now_ns() {
 #include "dense.inc"
 #include "schur.inc"
 #include "screening.inc"
+#include "screening_tree.inc"
 #include "run.inc"
 
 // ---------------------------------------------------------------------------------------
@@ -1276,7 +1277,11 @@ extern "C" int tdgl_time_kernel(tdgl_ctx *ctx, int32_t kernel, int32_t reps, dou
                 break;
             case 7:
                 if (!ctx->scr_enabled) return TDGL_ERR_ARG;
-                launch_induced(ctx);
+                launch_direct(ctx);
+                break;
+            case 22:  // one evaluation of the screening treecode
+                if (!ctx->scr_enabled || !tree_active(ctx)) return TDGL_ERR_ARG;
+                launch_tree(ctx);
                 break;
             case 8:  // two trivial kernels, the second on the communication stream and back
                 hipLaunchKernelGGL(k_copy_d2, dim3(1), dim3(BLOCK), 0, ctx->stream, 64, psi, tmp_c.p);

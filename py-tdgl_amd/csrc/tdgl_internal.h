@@ -338,6 +338,8 @@ struct DirectFactors {
     }
 };
 
+struct ScrTree;  // the screening treecode's set-up (screening_tree.inc)
+
 }  // namespace tdgl
 
 struct IpcState;  // peer-mapped transport (ipc.inc)
@@ -599,6 +601,8 @@ struct tdgl_ctx {
     tdgl::DevBuf<int64_t> scr_owned_gid; // global id of each owned site
     tdgl::DevBuf<double> scr_Jglobal;    // [2 * n_global_pad]
     int32_t last_screening_iters = 0;
+    // the barycentric Lagrange treecode (screening_tree.inc, tdgl_set_screening_tree); null: the all-pairs kernel
+    std::shared_ptr<tdgl::ScrTree> scr_tree;
 
     // ---- measurement -------------------------------------------------------------------
     bool profile = false;

@@ -205,6 +205,8 @@ class DistributedTDGL:
         self.mesh = mesh
         self.options = options
         options.validate()
+        if options.screening_method == "tree" and (options.include_screening or screening is not None):
+            raise ValueError("screening_method='tree' is not supported in one-process-per-GPU mode; use 'direct'.")
         if payload is None:
             if root is None:
                 payload = _own_payload(mesh, self.world, self.rank, link_exponents, epsilon, terminal_info,

@@ -1270,6 +1270,19 @@ class TDGLContext:
         self._chk(self._lib.tdgl_induced_vector_potential(self._ctx, p_f64(k), p_f64(A)))
         return A
 
+    def set_screening_tree(self, degree, theta):
+        """Evaluate the induced vector potential with the barycentric Lagrange treecode from now on (after
+        `set_screening`): degree p in [2, 16] ((p + 1)^2 proxies per far cluster), acceptance parameter theta in
+        (0, 1).  ``degree=0`` returns to the all-pairs kernel.  A refused call leaves the previous method in place."""
+        self._chk(self._lib.tdgl_set_screening_tree(self._ctx, int(degree), float(theta)))
+
+    def screening_tree_stats(self):
+        """``dict(clusters, levels, batches, far_pairs, near_pairs, setup_us)`` of the active treecode (pairs summed
+        over all edge centres); all zero with the all-pairs kernel."""
+        out = (C.c_int64 * 6)()
+        self._chk(self._lib.tdgl_get_screening_tree_stats(self._ctx, out))
+        return dict(zip(("clusters", "levels", "batches", "far_pairs", "near_pairs", "setup_us"), (int(v) for v in out)))
+
     def induced_vector_potential(self):
         A = np.empty((self.m, 2))
         self._chk(self._lib.tdgl_get_induced_vector_potential(self._ctx, p_f64(A)))

@@ -12,6 +12,10 @@ Differences, all at the backend seam:
   AMG-preconditioned CG above; ``sparse_solver="amg_pcg"`` forces the iterative solve at every size;
 * ``pcg_rtol`` / ``pcg_max_iter`` / ``amg_smoothing_sweeps`` / ``pcg_precond_fp32`` control the
   iterative solve and are ignored by the direct ones;
+* ``include_screening`` evaluates the induced vector potential's 1/r sum over all (edge centre, site)
+  pairs, like the reference; ``screening_method="tree"`` evaluates it with a barycentric Lagrange
+  treecode instead (``screening_tree_degree``, ``screening_tree_theta``; within 1e-8 of the direct
+  sum at the defaults), which pays off on large meshes; not in one-process-per-GPU mode;
 * results are returned in memory (``tdgl_amd.solution.Solution``); ``output_file`` additionally
   writes them in the reference's HDF5 layout at the end of the run (`tdgl_amd/io.py`, needs
   h5py); ``monitor`` (the reference's live viewer) is accepted and ignored.
@@ -87,6 +91,12 @@ class SolverOptions:
     pcg_precond_fp32: Union[bool, int] = True
     edge_currents_every_step: bool = True
     device_id: int = 0
+    # --- evaluation of the screening sum (no reference counterpart) ---
+    # "direct": all pairs (edge centre, site); "tree": barycentric Lagrange treecode of that degree and acceptance
+    # parameter theta, for large meshes (defaults: the cheapest pair meeting 1e-8, DESIGN.md §3 "Screening")
+    screening_method: str = "direct"
+    screening_tree_degree: int = 12
+    screening_tree_theta: float = 0.6
 
     def validate(self) -> None:
         def fail(msg):
@@ -118,6 +128,13 @@ class SolverOptions:
             fail(f"sparse solver must be a SparseSolver or str, got {self.sparse_solver!r}.")
         if self.include_screening and self.max_iterations_per_step < 1:
             fail("max_iterations_per_step must be >= 1.")
+        if self.screening_method not in ("direct", "tree"):
+            fail(f"screening_method must be one of ['direct', 'tree'] (got {self.screening_method!r}).")
+        deg = self.screening_tree_degree
+        if isinstance(deg, bool) or int(deg) != deg or not (2 <= deg <= 16):
+            fail(f"screening_tree_degree must be in [2, 16] (got {deg}).")
+        if not (0 < self.screening_tree_theta < 1):
+            fail(f"screening_tree_theta must be in (0, 1) (got {self.screening_tree_theta}).")
         if not (self.pcg_rtol > 0):
             fail(f"pcg_rtol must be > 0 (got {self.pcg_rtol}).")
         if self.pcg_max_iter < 1 or self.amg_smoothing_sweeps < 1:

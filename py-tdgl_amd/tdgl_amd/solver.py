@@ -338,6 +338,8 @@ class TDGLSolver:
                 max_iterations=options.max_iterations_per_step, tolerance=options.screening_tolerance,
                 step_size=options.screening_step_size, step_drag=options.screening_step_drag,
             )
+            if options.screening_method == "tree":
+                self.ctx.set_screening_tree(options.screening_tree_degree, options.screening_tree_theta)
         # tabulated time dependence: uploaded once, evaluated by tdgl_run at every step's time
         self._currents_on_device = self._epsilon_on_device = False
         if self._current_table is not None and self.terminal_info:
