@@ -646,6 +646,33 @@ int tdgl_set_screening_tree(tdgl_ctx *ctx, int32_t degree, double theta);
  * summed over all edge centres: proxies of far clusters, sources of near ones); all zero with the all-pairs kernel. */
 int tdgl_get_screening_tree_stats(tdgl_ctx *ctx, int64_t *out6);
 
+/* ------------------------------------------------------------------ fields of the currents (post-processing) */
+/* Vector potential and magnetic field of sheet currents at arbitrary points: the all-pairs sums of
+ * tdgl/em.py:_biot_savart_2d_z / _biot_savart_2d_vector and Solution.vector_potential_at_position, on the device
+ * (csrc/fields.inc).  The plan owns its device buffers and its stream and needs no tdgl_ctx.
+ * sources: n sites (x, y) in one plane z = z0, weights area_j; targets: m points (x, y, z).  All in one length unit.
+ * Errors go to the global tdgl_last_error(NULL).  TDGL_ERR_ARG: null arrays, n < 1, m < 1, a non-finite coordinate
+ * or area, a coordinate beyond +-1e100 (the bound that keeps every squared distance, also to the kernel's padding
+ * sources at 1e150, finite), no such device. */
+typedef struct tdgl_field_plan tdgl_field_plan;
+int tdgl_field_plan_create(tdgl_field_plan **out, int device_id, int64_t n, const double *src_xy,
+                           const double *src_area, double z0, int64_t m, const double *target_xyz);
+void tdgl_field_plan_destroy(tdgl_field_plan *plan);
+/* K: n_fields sheet-current fields, [n_fields][n][2] (n_fields 1 or 2: supercurrent, normal current).
+ * what: bit 0 = vector potential sums  S_A[f][i][0:2] = sum_j a_j K_j / |r_i - r_j|
+ *       bit 1 = B_z sums               S_z[f][i]      = sum_j a_j (Kx_j dy - Ky_j dx) / |r|^3
+ *       bit 2 = in-plane B sums        S_xy[f][i][0:2] = ( dz sum_j a_j Ky_j / |r|^3 , -dz sum_j a_j Kx_j / |r|^3 )
+ * with (dx, dy, dz) = r_i - r_j.  Outputs that are not asked for may be NULL and are not touched.  No physical
+ * prefactor: mu_0 / 4 pi and units stay with the caller.  One pass computes everything asked for (one reciprocal
+ * square root per pair); the result is deterministic (fixed summation order, no atomics).  A target that coincides
+ * with a source (dz = 0 on a site) comes out non-finite; every other target is unaffected.
+ * TDGL_ERR_ARG (the plan stays usable): null plan / K / requested output, n_fields outside {1, 2}, what outside 1..7. */
+int tdgl_field_plan_eval(tdgl_field_plan *plan, int32_t n_fields, const double *K, int32_t what,
+                         double *S_A, double *S_z, double *S_xy);
+/* out4 = {pairs, kernel launches, source chunks (first target batch), target batches} of the last evaluation;
+ * *last_ms its device time between the upload of K and the read-back (either may be NULL). */
+int tdgl_field_plan_stats(tdgl_field_plan *plan, int64_t *out4, double *last_ms);
+
 /* ------------------------------------------------------------------ the time loop */
 /* Start a Runner stage (runner.py:294-297, 315-318): time = 0, stage step = 0.  Runner.dt
  * and the controller state are deliberately NOT reset. */

@@ -605,6 +605,7 @@ static inline int64_t now_ns() {
 #include "schur.inc"
 #include "screening.inc"
 #include "screening_tree.inc"
+#include "fields.inc"
 #include "run.inc"
 
 // ---------------------------------------------------------------------------------------

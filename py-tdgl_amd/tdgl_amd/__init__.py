@@ -2,7 +2,8 @@
 
 Public surface (mirrors `tdgl/__init__.py:1-23` of the reference for the solver path):
 ``Layer, Polygon, Device, SolverOptions, SolverOptionsError, SparseSolver, solve, TDGLSolver,
-Solution`` and the ``geometry`` helpers; beyond it, ``solve_ensemble`` (many replicas of one device at once).
+Solution`` and the ``geometry`` helpers; beyond it, ``solve_ensemble`` (many replicas of one device at once)
+and ``FieldEvaluator`` (fields of the currents at many points, on the device).
 """
 
 from . import geometry  # noqa: F401
@@ -17,5 +18,6 @@ from .options import SolverOptions, SolverOptionsError, SparseSolver  # noqa: F4
 from .solution import BiotSavartField, DynamicsData, Fluxoid, Solution, TDGLData  # noqa: F401
 from .solver import SolverResult, TDGLSolver, solve  # noqa: F401
 from .ensemble import ENSEMBLE_MAX_SITES, solve_ensemble  # noqa: F401
+from .fields import FieldEvaluator  # noqa: F401
 
 __version__ = "0.1.0"

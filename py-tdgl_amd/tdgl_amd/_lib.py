@@ -312,6 +312,12 @@ SIGNATURES = {
     "tdgl_induced_vector_potential": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_set_screening_tree": (C.c_int, [_CTX, C.c_int32, C.c_double]),
     "tdgl_get_screening_tree_stats": (C.c_int, [_CTX, C.POINTER(C.c_int64)]),
+    # fields of the currents (csrc/fields.inc); the plan is an opaque pointer
+    "tdgl_field_plan_create": (
+        C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, c_f64p, c_f64p, C.c_double, C.c_int64, c_f64p]),
+    "tdgl_field_plan_destroy": (None, [C.c_void_p]),
+    "tdgl_field_plan_eval": (C.c_int, [C.c_void_p, C.c_int32, c_f64p, C.c_int32, c_f64p, c_f64p, c_f64p]),
+    "tdgl_field_plan_stats": (C.c_int, [C.c_void_p, c_i64p, c_f64p]),
     "tdgl_get_step_stats": (C.c_int, [_CTX, C.POINTER(C.c_int64), C.c_int32]),
     "tdgl_get_direct_stats": (C.c_int, [_CTX, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "tdgl_set_direct_guard": (C.c_int, [_CTX, C.c_double]),

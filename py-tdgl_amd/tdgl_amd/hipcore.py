@@ -1498,3 +1498,66 @@ class TDGLContext:
         n, ms = C.c_int64(0), C.c_double(0)
         self._chk(self._lib.tdgl_profile_read(self._ctx, C.byref(n), C.byref(ms)))
         return n.value, ms.value
+
+
+class FieldPlan:
+    """Owns one ``tdgl_field_plan`` (csrc/fields.inc): ``n`` current-carrying sites in the plane ``z = z0`` and ``m``
+    target points kept on the device; :meth:`eval` returns the bare all-pairs sums for given site currents (no
+    ``mu_0 / 4 pi``, no units).  Needs no ``TDGLContext``.  A context manager; freed on ``__del__`` too."""
+
+    VECTOR_POTENTIAL, BZ, BXY = 1, 2, 4  # bits of ``what``
+
+    def __init__(self, sites_xy, areas, z0, targets_xyz, device_id=0):
+        _lib.require_gpu()
+        self._lib = _lib.load()
+        self._plan = C.c_void_p()
+        sites_xy, areas, targets_xyz = f64(sites_xy), f64(areas), f64(targets_xyz)
+        if sites_xy.ndim != 2 or sites_xy.shape[1] != 2 or areas.shape != (len(sites_xy),):
+            raise ValueError(f"Expected sites [n, 2] and areas [n] (got {sites_xy.shape}, {areas.shape}).")
+        if targets_xyz.ndim != 2 or targets_xyz.shape[1] != 3:
+            raise ValueError(f"Expected targets [m, 3] (got {targets_xyz.shape}).")
+        self.n, self.m = len(sites_xy), len(targets_xyz)
+        _lib.check(self._lib.tdgl_field_plan_create(
+            C.byref(self._plan), int(device_id), self.n, p_f64(sites_xy), p_f64(areas), float(z0), self.m,
+            p_f64(targets_xyz)))
+
+    def eval(self, K, what=7):
+        """``K``: [n, 2] or [n_fields, n, 2] with ``n_fields`` 1 or 2.  Returns ``(S_A, S_z, S_xy)`` of shapes
+        [n_fields, m, 2], [n_fields, m], [n_fields, m, 2]; ``None`` for the sums ``what`` does not ask for."""
+        if not self._plan.value:
+            raise RuntimeError("FieldPlan is closed.")
+        K = f64(K)
+        if K.ndim == 2:
+            K = K[None]
+        if K.ndim != 3 or K.shape[1:] != (self.n, 2):
+            raise ValueError(f"Expected currents of shape [n_fields, {self.n}, 2] (got {K.shape}).")
+        nf, what = K.shape[0], int(what)
+        S_A = np.empty((nf, self.m, 2)) if what & 1 else None
+        S_z = np.empty((nf, self.m)) if what & 2 else None
+        S_xy = np.empty((nf, self.m, 2)) if what & 4 else None
+        _lib.check(self._lib.tdgl_field_plan_eval(self._plan, nf, p_f64(K), what, p_f64(S_A), p_f64(S_z), p_f64(S_xy)))
+        return S_A, S_z, S_xy
+
+    def stats(self) -> dict:
+        """Of the last evaluation: pairs, kernel launches, source chunks of the first target batch, target batches,
+        and the device time in milliseconds between the upload of the currents and the read-back."""
+        out, ms = (C.c_int64 * 4)(), C.c_double(0)
+        _lib.check(self._lib.tdgl_field_plan_stats(self._plan, out, C.byref(ms)))
+        return dict(pairs=out[0], launches=out[1], source_chunks=out[2], target_batches=out[3], last_ms=ms.value)
+
+    def close(self):
+        if getattr(self, "_plan", None) is not None and self._plan.value:
+            self._lib.tdgl_field_plan_destroy(self._plan)
+            self._plan = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

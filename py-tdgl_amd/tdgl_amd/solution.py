@@ -188,6 +188,30 @@ class DynamicsData:
                 h5group[name] = getattr(self, name)
 
 
+BACKENDS = ("host", "hip")
+
+
+def _check_backend(backend: str) -> str:
+    if backend not in BACKENDS:
+        raise ValueError(f"backend must be one of {BACKENDS} (got {backend!r}).")
+    return backend
+
+
+def positions_and_heights(positions, zs):
+    """Evaluation points as ([m, 2], [m]) from (m, 3) positions, or (m, 2) positions and a number or an array of
+    heights (solution.py:716-731)."""
+    positions = np.atleast_2d(np.asarray(positions, dtype=float))
+    if positions.shape[1] == 3:
+        if zs is not None:
+            raise ValueError("If positions has shape (m, 3) then zs cannot be specified.")
+        zs, positions = positions[:, 2], positions[:, :2]
+    elif isinstance(zs, numbers.Real):
+        zs = zs * np.ones(len(positions))
+    if not isinstance(zs, np.ndarray):
+        raise ValueError(f"Expected zs to be an ndarray, but got {type(zs)}.")
+    return positions, np.asarray(zs, dtype=float).reshape(-1)
+
+
 def _split_units(units: str, sep: str):
     parts = [p.strip() for p in units.replace("**", "^").split(sep)]
     return parts
@@ -471,16 +495,18 @@ class Solution:
 
     # -- fields of the currents ----------------------------------------------------------------------
     def _positions_and_heights(self, positions, zs):
-        positions = np.atleast_2d(np.asarray(positions, dtype=float))
-        if positions.shape[1] == 3:
-            if zs is not None:
-                raise ValueError("If positions has shape (m, 3) then zs cannot be specified.")
-            zs, positions = positions[:, 2], positions[:, :2]
-        elif isinstance(zs, numbers.Real):
-            zs = zs * np.ones(len(positions))
-        if not isinstance(zs, np.ndarray):
-            raise ValueError(f"Expected zs to be an ndarray, but got {type(zs)}.")
-        return positions, np.asarray(zs, dtype=float).reshape(-1)
+        return positions_and_heights(positions, zs)
+
+    def _device_sums(self, evaluator, positions, zs, what):
+        """The all-pairs sums of both current fields from the HIP kernel (`tdgl_amd.fields`): through ``evaluator``,
+        or through a one-shot evaluator for these points on ``options.device_id``."""
+        from .fields import FieldEvaluator
+
+        K = np.stack([self.supercurrent_density, self.normal_current_density])
+        if evaluator is not None:
+            return evaluator.plan.eval(K, what)
+        with FieldEvaluator(self.device, positions, zs, device_id=getattr(self.options, "device_id", 0)) as one_shot:
+            return one_shot.plan.eval(K, what)
 
     def _applied_vector_potential_at(self, positions: np.ndarray, zs: np.ndarray) -> np.ndarray:
         """A_applied at points, [m, 3], in ``field_units * length_units``: the user's parameter, or
@@ -502,11 +528,15 @@ class Solution:
         return out
 
     def vector_potential_at_position(self, positions: np.ndarray, *, zs=None, units: Union[str, None] = None,
-                                     with_units: bool = True, return_sum: bool = True):
+                                     with_units: bool = True, return_sum: bool = True, backend: str = "host"):
         """Applied vector potential plus the one of the sheet currents,
         ``A(r) = mu_0 / (4 pi) sum_j K_j a_j / |r - r_j|`` (solution.py:768-872), shape [m, 3], in
         ``field_units * length_units``.  ``return_sum=False``: a dict with the parts ``applied``,
-        ``supercurrent_density``, ``normal_current_density``."""
+        ``supercurrent_density``, ``normal_current_density``.  ``backend``: ``"host"`` (NumPy, [m, n] temporaries)
+        or ``"hip"`` (the all-pairs kernel on ``options.device_id``; needs a GPU, never chosen automatically)."""
+        return self._vector_potential_at(positions, zs, units, with_units, return_sum, _check_backend(backend), None)
+
+    def _vector_potential_at(self, positions, zs, units, with_units, return_sum, backend, evaluator):
         from .device import CURRENT_UNITS, FIELD_UNITS, LENGTH_UNITS, MU_0
 
         dev = self.device
@@ -516,27 +546,39 @@ class Solution:
         positions, zs = self._positions_and_heights(positions, zs)
         wrap = (lambda a: Quantity(a, default)) if with_units else (lambda a: a)
         parts = {"applied": wrap(self._applied_vector_potential_at(positions, zs))}
-        points = dev.points
-        areas = dev.mesh.areas * dev.coherence_length**2
-        d = positions[:, None, :] - points[None, :, :]
-        rho = np.sqrt((d**2).sum(axis=2) + (zs[:, None] - dev.layer.z0) ** 2)
         # mu_0/(4 pi) [current_units] -> [field_units * length_units]:  T m = (N/A^2) A
         to_units = MU_0 / (4 * np.pi) * CURRENT_UNITS[self.current_units] / (
             FIELD_UNITS[self.field_units] * LENGTH_UNITS[dev.length_units])
-        for name in ("supercurrent_density", "normal_current_density"):
-            J = getattr(self, name)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                Axy = (J[None, :, :] / rho[:, :, None] * areas[None, :, None]).sum(axis=1)
+        if backend == "hip":
+            S_A = self._device_sums(evaluator, positions, zs, 1)[0]
+        else:
+            points = dev.points
+            areas = dev.mesh.areas * dev.coherence_length**2
+            d = positions[:, None, :] - points[None, :, :]
+            rho = np.sqrt((d**2).sum(axis=2) + (zs[:, None] - dev.layer.z0) ** 2)
+        for f, name in enumerate(("supercurrent_density", "normal_current_density")):
+            if backend == "hip":
+                Axy = S_A[f]
+            else:
+                J = getattr(self, name)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    Axy = (J[None, :, :] / rho[:, :, None] * areas[None, :, None]).sum(axis=1)
             parts[name] = wrap(to_units * np.concatenate([Axy, np.zeros_like(Axy[:, :1])], axis=1))
         if return_sum:
             return sum(parts.values())
         return parts
 
     def field_at_position(self, positions: np.ndarray, *, zs=None, vector: bool = False,
-                          units: Union[str, None] = None, with_units: bool = True, return_sum: bool = True):
+                          units: Union[str, None] = None, with_units: bool = True, return_sum: bool = True,
+                          backend: str = "host"):
         """Magnetic field of the sheet currents (Biot-Savart over the sites' Voronoi cells,
         solution.py:669-766, `tdgl/em.py:252-330`), in ``field_units``; the z component, or with
-        ``vector=True`` all three.  Not defined in the plane of the film inside the film."""
+        ``vector=True`` all three.  Not defined in the plane of the film inside the film.  ``backend``: ``"host"``
+        (NumPy, [m, n] temporaries) or ``"hip"`` (the all-pairs kernel on ``options.device_id``; needs a GPU, never
+        chosen automatically)."""
+        return self._field_at(positions, zs, vector, units, with_units, return_sum, _check_backend(backend), None)
+
+    def _field_at(self, positions, zs, vector, units, with_units, return_sum, backend, evaluator):
         from .device import CURRENT_UNITS, FIELD_UNITS, LENGTH_UNITS, MU_0
 
         dev = self.device
@@ -546,22 +588,31 @@ class Solution:
         dz = zs - dev.layer.z0
         if np.all(dz == 0) and dev.film.contains_points(positions).any():
             raise ValueError("Cannot interpolate fields within a film.")
-        points = dev.points
-        areas = dev.mesh.areas * dev.coherence_length**2
-        dx = positions[:, None, 0] - points[None, :, 0]
-        dy = positions[:, None, 1] - points[None, :, 1]
-        r3 = (dx**2 + dy**2 + dz[:, None] ** 2) ** 1.5
+        if backend == "hip":
+            _, S_z, S_xy = self._device_sums(evaluator, positions, zs, 6 if vector else 2)
+        else:
+            points = dev.points
+            areas = dev.mesh.areas * dev.coherence_length**2
+            dx = positions[:, None, 0] - points[None, :, 0]
+            dy = positions[:, None, 1] - points[None, :, 1]
+            r3 = (dx**2 + dy**2 + dz[:, None] ** 2) ** 1.5
         # mu_0/(4 pi) [current/length * length^2 / length^2] -> tesla -> field_units
         to_units = MU_0 / (4 * np.pi) * (CURRENT_UNITS[self.current_units] / LENGTH_UNITS[dev.length_units]) / (
             FIELD_UNITS[self.field_units])
         fields = []
-        for name in ("supercurrent_density", "normal_current_density"):
-            J = getattr(self, name)
-            jx, jy = (J[:, 0] * areas)[None, :], (J[:, 1] * areas)[None, :]
-            Hz = ((jx * dy - jy * dx) / r3).sum(axis=1)
+        for f, name in enumerate(("supercurrent_density", "normal_current_density")):
+            if backend == "hip":
+                Hz = S_z[f]
+                if vector:
+                    Hx, Hy = S_xy[f, :, 0], S_xy[f, :, 1]
+            else:
+                J = getattr(self, name)
+                jx, jy = (J[:, 0] * areas)[None, :], (J[:, 1] * areas)[None, :]
+                Hz = ((jx * dy - jy * dx) / r3).sum(axis=1)
+                if vector:
+                    Hx = (jy * dz[:, None] / r3).sum(axis=1)
+                    Hy = (-jx * dz[:, None] / r3).sum(axis=1)
             if vector:
-                Hx = (jy * dz[:, None] / r3).sum(axis=1)
-                Hy = (-jx * dz[:, None] / r3).sum(axis=1)
                 H = np.stack([Hx, Hy, Hz], axis=1)
             else:
                 H = Hz
@@ -571,15 +622,16 @@ class Solution:
         return sum(fields) if return_sum else fields
 
     def polygon_fluxoid(self, polygon_points, interp_method: str = "linear", units: Union[str, None] = "Phi_0",
-                        with_units: bool = True) -> Fluxoid:
+                        with_units: bool = True, backend: str = "host") -> Fluxoid:
         """Fluxoid of a closed polygon inside the film (solution.py:464-548):
         ``oint A . dl  +  mu_0 oint Lambda / |psi|^2  K_s . dl`` with A the applied plus the
         currents' vector potential, both line integrals as the reference accumulates them
         (``dl`` = backward differences of the closed, counter-clockwise vertex list; trapezoid rule
         over the per-vertex terms).  In ``units``: ``"Phi_0"`` (default) or ``None`` =
-        ``field_units * length_units**2``."""
+        ``field_units * length_units**2``.  ``backend`` is passed to :meth:`vector_potential_at_position`."""
         from .device import CURRENT_UNITS, FIELD_UNITS, LENGTH_UNITS, MU_0, PHI_0, Polygon
 
+        _check_backend(backend)
         dev = self.device
         points = Polygon(points=polygon_points).points
         if not dev.film.contains_points(points).all():
@@ -596,7 +648,7 @@ class Solution:
         J_poly = self.interp_current_density(points, dataset="supercurrent", method=interp_method)
         zs = dev.layer.z0 * np.ones(len(points))
         dl = np.diff(points, axis=0, prepend=points[:1])
-        A_poly = self.vector_potential_at_position(points, zs=zs, with_units=False)[:, :2]
+        A_poly = self.vector_potential_at_position(points, zs=zs, with_units=False, backend=backend)[:, :2]
         trapz = lambda y: float(np.sum((y[1:] + y[:-1]) / 2))  # noqa: E731
         flux_part = trapz((A_poly * dl).sum(axis=1)) * scale
         ns = np.abs(self.interp_order_parameter(points, method=interp_method)) ** 2
