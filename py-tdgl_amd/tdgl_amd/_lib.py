@@ -167,6 +167,18 @@ class Substructure(C.Structure):
     ]
 
 
+def describe(pk) -> Substructure:
+    """`tdgl_substructure` over the arrays of `substructure.pack_for_device` (``pk`` keeps them alive)."""
+    p_i64 = lambda a: a.ctypes.data_as(c_i64p)
+    return Substructure(
+        n_interior=pk["n_interior"], n_sep=pk["n_sep"], n_parts=pk["n_parts"], part_ptr=p_i32(pk["part_ptr"]),
+        seg_ptr=p_i32(pk["seg_ptr"]), seg_val=p_i64(pk["seg_val"]), seg_x=p_i32(pk["seg_x"]),
+        seg_len=p_i32(pk["seg_len"]), vals=p_f64(pk["vals"]), n_vals=len(pk["vals"]), sep_ptr=p_i32(pk["sep_ptr"]),
+        sep_idx=p_i32(pk["sep_idx"]), e_off=p_i64(pk["e_off"]), e_vals=p_f64(pk["e_vals"]),
+        n_e=len(pk["e_vals"]), u=p_f64(pk["u"]), schur=None if pk["schur"] is None else p_f64(pk["schur"]),
+    )
+
+
 class SchurPiece(C.Structure):
     """`tdgl_schur_piece` (include/tdgl_hip.h): one rank's share of the rank-level dissection."""
 

@@ -1,6 +1,8 @@
 """Object wrapper over the C ABI (one method per entry point of include/tdgl_hip.h)."""
 
 import ctypes as C
+import os
+from dataclasses import dataclass
 
 import numpy as np
 import scipy.sparse as sp
@@ -65,6 +67,45 @@ class _Stopwatch:
         self.table[self.name] = self.table.get(self.name, 0.0) + time.perf_counter() - self.t0
 
 
+@dataclass(frozen=True)
+class MuPlan:
+    """What a context does about the mu equation (`TDGLContext.mu_plan`): decided once from the mesh size and the class's
+    limits, it fixes the site order (`TDGLContext.__init__`) and what `TDGLContext.build_poisson` builds."""
+    form: str                  # "amg": AMG-PCG alone | "dense": explicit pseudo-inverse | "sub": substructured direct solve
+    #                            | "precond": three levels of fp32 factors as the CG's second preconditioner
+    levels: int = 0            # dissection levels of "sub" (1-3) and "precond" (3)
+    blocks: tuple = ()         # target sizes of a part, a super-block, a super-super-block (one per level)
+    sparse_sep: bool = False   # separator right-hand sides through the sparse coupling blocks (no -E^T rows)
+    switching: bool = False    # the time loop may pause the direct solve in stationary states
+    amg_candidates: int = 1    # hierarchies built, the best one kept
+
+
+_LEVEL_NAMES = (("parts", "separator"), ("super_blocks", "top_separator"), ("super_super_blocks", "top_top_separator"))
+
+
+def _level_counts(levels) -> dict:
+    """Parts and separator sites of every dissection level, under the names of `substructure` / `precond_direct`."""
+    return {name: v for (a, b), lv in zip(_LEVEL_NAMES, levels) for name, v in ((a, lv.n_parts), (b, lv.n_sep))}
+
+
+def _sym_tile_entries(m: int) -> int:
+    """Entries of a symmetric m x m matrix kept as the 128 x 128 tiles on or below its diagonal (the top separator)."""
+    t = (m + 127) // 128
+    return t * (t + 1) // 2 * 128 * 128
+
+
+def _factor_bytes(levels, tiles, sparse_sep=True, word=8, top=True) -> int:
+    """Bytes one application of a dissection's explicit factors streams (``word`` bytes per entry): the G blocks of
+    level k whole, or as the 16 x 16 tiles on or below their diagonal where ``tiles[k]``; the E blocks once on the way up
+    and, as -E^T rows, once more on the way down unless ``sparse_sep`` replaces those by the coupling blocks (12 bytes
+    per non-zero); ``top``: the last level's separator inverse."""
+    tri = lambda m: ((m + 15) // 16) * (((m + 15) // 16) + 1) // 2 * 256
+    entries = (sum((tri(g.shape[0]) if tiles[k] else g.size) for k, lv in enumerate(levels) for g in lv.G)
+               + (1 if sparse_sep else 2) * sum(e.size for lv in levels for e in lv.E)
+               + (_sym_tile_entries(levels[-1].n_sep) if top else 0))
+    return int(word * entries + (12 * sum(lv.coupling.nnz for lv in levels) if sparse_sep else 0))
+
+
 class TDGLContext:
     """Owns one ``tdgl_ctx`` (device buffers + stream) for a mesh."""
 
@@ -92,52 +133,16 @@ class TDGLContext:
         self.n_owned = int(n_owned) if n_owned else self.n
         if n_owned:
             reorder = None
-        self._sub_part_ptr = None
-        self._sub_super_ptr = None
-        self._sub_big_ptr = None
+        self._sub_ptrs = []  # pointer arrays of the substructure site order, one per level (`build_substructure`)
         self._pd_order = None
         self.precond_direct = None
         self.direct_solve = bool(direct_solve)
+        self.mu = self.mu_plan(self.n, n_owned, self.direct_solve, substructure_levels, reordered=reorder == "rcm")
         if reorder == "rcm":
             with _Stopwatch(self.setup_times, "reorder"):
                 perm = rcm_permutation(em.edges, self.n)
-                if substructure_levels is not None:
-                    if substructure_levels not in (1, 2) or not self.direct_solve:
-                        raise ValueError(f"substructure_levels must be 1 or 2 with a direct solve (got {substructure_levels})")
-                    perm = self._substructure_order(mesh, em, perm, substructure_levels)
-                elif self.direct_solve and 0 < max(self.SUB_MAX_SITES, self.DENSE_MAX_SITES) < self.n <= self.SUB2_MAX_SITES \
-                        and self.SUB_MAX_SITES > 0:
-                    # ... and beyond, up to SUB2_MAX_SITES, two levels of it (part interiors, the fine separators
-                    # super-block by super-block, the top separator)
-                    from .substructure import substructure_order2
-
-                    rank = np.empty(self.n, dtype=np.int64)
-                    rank[perm] = np.arange(self.n)
-                    block2 = self.SUB2_BLOCK or (128 if self.n < 200_000 else 160)
-                    if self.n >= self.SUB3_MIN_SITES:
-                        # ... and three levels: one more cut above, so that the dense top separator stays small
-                        from .substructure import substructure_order3
-
-                        perm, self._sub_part_ptr, self._sub_super_ptr, self._sub_big_ptr = substructure_order3(
-                            np.asarray(mesh.sites), em.edges, block2, self.SUB2_SUPER or 4096, self.SUB3_BIG, rank_hint=rank)
-                    else:
-                        perm = self._substructure_order(mesh, em, perm, 2)
-                elif self.direct_solve and 0 < self.SUB_MAX_SITES and max(self.SUB_MAX_SITES, self.SUB2_MAX_SITES) < self.n <= self.PD_MAX_SITES:
-                    # larger still: the context KEEPS the reverse Cuthill-McKee order (what the stencil kernels and the AMG
-                    # hierarchy are fastest in); three levels of dissection are cut all the same, their factors become the
-                    # CG's preconditioner and their order lives inside its application (`build_precond_direct`)
-                    from .substructure import substructure_order3
-
-                    rank = np.empty(self.n, dtype=np.int64)
-                    rank[perm] = np.arange(self.n)
-                    self._pd_order = substructure_order3(
-                        np.asarray(mesh.sites), em.edges, self.SUB2_BLOCK or self.PD_BLOCKS[0], self.SUB2_SUPER or self.PD_BLOCKS[1],
-                        self.PD_BLOCKS[2] if self.SUB3_BIG == 32768 else self.SUB3_BIG, rank_hint=rank)
-                elif self.direct_solve and self.DENSE_MAX_SITES < self.n <= self.SUB_MAX_SITES:
-                    # mid-size meshes: the substructured direct mu solve wants "interiors part by part,
-                    # then the separator" as the site order (substructure.py); inside a part the sites keep
-                    # their reverse Cuthill-McKee order
-                    perm = self._substructure_order(mesh, em, perm, 1)
+                if self.mu.levels:
+                    perm = self._dissection_order(mesh, em, perm)
         elif reorder is None or reorder == "none":
             perm = np.arange(self.n, dtype=np.int32)
         else:
@@ -167,25 +172,23 @@ class TDGLContext:
         self.dense_direct = False  # mu solve = a direct one (set_dense_inverse / build_substructure)
         self.substructure = None
 
-    def _substructure_order(self, mesh, em, perm, levels):
-        """The site order of the substructured direct solve of one or two levels (parts of `SUB_BLOCK` sites, or
-        of `SUB2_BLOCK` inside super-blocks of `SUB2_SUPER`; 0 = by size), the parts' sites kept in the order of
-        ``perm`` (reverse Cuthill-McKee).  Sets the part pointers; returns the permutation."""
+    def _dissection_order(self, mesh, em, perm):
+        """Cuts the plan's dissection (`MuPlan.levels`, `MuPlan.blocks`), the sites of a part kept in the order of ``perm``
+        (reverse Cuthill-McKee: the stencil's gathers stay local).  Form "sub": interiors part by part, then the
+        separators level by level IS the context's site order -- sets `_sub_ptrs`, returns that permutation.  Form
+        "precond": the context KEEPS ``perm`` (what the stencil kernels and the AMG hierarchy are fastest in); the factors
+        become the CG's preconditioner and their order (`_pd_order`) lives inside its application."""
+        from . import substructure
+
         rank = np.empty(self.n, dtype=np.int64)
         rank[perm] = np.arange(self.n)
-        if levels == 1:
-            from .substructure import substructure_order
-
-            block = self.SUB_BLOCK or (192 if self.n <= 8000 else max(320, int(320 * (self.n / 60000.0) ** (2.0 / 3.0))))
-            perm, self._sub_part_ptr = substructure_order(np.asarray(mesh.sites), em.edges, block, rank_hint=rank)
+        order = (substructure.substructure_order, substructure.substructure_order2, substructure.substructure_order3)[self.mu.levels - 1]
+        cut = order(np.asarray(mesh.sites), em.edges, *self.mu.blocks, rank_hint=rank)
+        if self.mu.form == "precond":
+            self._pd_order = cut
             return perm
-        from .substructure import substructure_order2
-
-        block2 = self.SUB2_BLOCK or (128 if self.n < 200_000 else 160)
-        super2 = self.SUB2_SUPER or max(2048, self.n // 60)
-        perm, self._sub_part_ptr, self._sub_super_ptr = substructure_order2(
-            np.asarray(mesh.sites), em.edges, block2, super2, rank_hint=rank)
-        return perm
+        self._sub_ptrs = list(cut[1:])
+        return cut[0]
 
     # -- lifetime ---------------------------------------------------------------------
     def close(self):
@@ -210,13 +213,13 @@ class TDGLContext:
     # `tdgl_poisson_set_dense_inverse`) unless build_poisson is told otherwise
     AMG_CANDIDATES = 3               # hierarchies built per iterative-regime mesh (the best one stays)
     AMG_CANDIDATES_MIN_SITES = 100_000
-    DENSE_MAX_SITES = int(__import__("os").environ.get("TDGL_DENSE_MAX_SITES", "5000"))
+    DENSE_MAX_SITES = int(os.environ.get("TDGL_DENSE_MAX_SITES", "5000"))
     # ... and up to this many the substructured direct solve (`tdgl_poisson_set_substructure`): parts of
     # ~SUB_BLOCK sites with explicit inverses, a dense Schur complement on the separator
-    SUB_MAX_SITES = int(__import__("os").environ.get("TDGL_SUB_MAX_SITES", "32000"))
+    SUB_MAX_SITES = int(os.environ.get("TDGL_SUB_MAX_SITES", "32000"))
     # (0 = by size: 192 sites per part up to 8k sites, 320 up to 60k, growing like n^(2/3) beyond -- the dense
     # Schur complement of the separator, ~2 n / sqrt(block) sites, is what grows fastest)
-    SUB_BLOCK = int(__import__("os").environ.get("TDGL_SUB_BLOCK", "0"))
+    SUB_BLOCK = int(os.environ.get("TDGL_SUB_BLOCK", "0"))
     # two levels of it (`tdgl_poisson_set_substructure_inner`) from there up to SUB2_MAX_SITES: parts of SUB2_BLOCK
     # sites inside super-blocks of SUB2_SUPER sites (0 = by size: 128 / 160 sites per part below / above 200k sites,
     # super-blocks of n / 60 sites but at least 2,048 -- the dense matrix of the top separator grows like n^2 /
@@ -259,12 +262,63 @@ class TDGLContext:
     # iteration from the projection guess.  Per solve the library takes the V-cycle or the factors by predicted cost:
     # no state, no hysteresis -- a stationary strip runs on the V-cycle from its first step, a film in flux flow on the
     # factors, and the context keeps the reverse Cuthill-McKee order (16-bit column offsets in the stencil kernels).
-    PD_MAX_SITES = int(__import__("os").environ.get("TDGL_PD_MAX_SITES", "1300000"))
+    PD_MAX_SITES = int(os.environ.get("TDGL_PD_MAX_SITES", "1300000"))
     PD_CHOICE = 0  # 0: by predicted cost, 1: always the factors, 2: never (tests / A-B runs)
     # (part, super-block, super-super-block) sizes of the factors when they precondition: measured time of one application
     # at 1M sites with the final kernels (tools/exp_pd_blocks.py) 160/4096/32768 409 us, 128/4096/32768 407, 128/3072/24576 389,
     # 144/3072/24576 390 (and the shortest host set-up, 4.9 s), 112/3072/24576 398, 128/2048/16384 397, 128/3072/32768 390
     PD_BLOCKS = (144, 3072, 24576)
+
+    @classmethod
+    def mu_plan(cls, n, n_owned=0, direct_solve=True, substructure_levels=None, dense_max_sites=None, reordered=True) -> MuPlan:
+        """The mu solver of a context on ``n`` sites (no GPU needed; the limits above are read from the class now).
+        ``n_owned`` > 0 (one process per GPU) or ``reordered=False`` (the caller fixes the site order): no form that
+        needs a site order or factors of its own -- and a rank that does not own every site solves iteratively.
+        ``substructure_levels`` 1 or 2: the substructured solve of that many levels whatever the size rule says.
+        ``dense_max_sites`` (`build_poisson` told its own dense limit): that limit instead of `DENSE_MAX_SITES`, and
+        neither the substructured solve nor the preconditioner."""
+        single = not n_owned or n_owned == n
+        levels, precond = 0, False
+        if reordered and not n_owned and dense_max_sites is None:
+            if substructure_levels is not None:
+                if substructure_levels not in (1, 2) or not direct_solve:
+                    raise ValueError(f"substructure_levels must be 1 or 2 with a direct solve (got {substructure_levels})")
+                levels = substructure_levels
+            elif direct_solve and cls.SUB_MAX_SITES > 0:  # (SUB_MAX_SITES = 0 switches every form with factors off)
+                if max(cls.SUB_MAX_SITES, cls.DENSE_MAX_SITES) < n <= cls.SUB2_MAX_SITES:
+                    # beyond one level, up to SUB2_MAX_SITES, two levels (part interiors, the fine separators super-block
+                    # by super-block, the top separator) -- and three from SUB3_MIN_SITES on: one more cut above, so
+                    # that the dense top separator stays small
+                    levels = 3 if n >= cls.SUB3_MIN_SITES else 2
+                elif max(cls.SUB_MAX_SITES, cls.SUB2_MAX_SITES) < n <= cls.PD_MAX_SITES:
+                    # larger still: three levels of dissection are cut all the same, their factors precondition the CG
+                    levels, precond = 3, True
+                elif cls.DENSE_MAX_SITES < n <= cls.SUB_MAX_SITES:
+                    # mid-size meshes: one level ("interiors part by part, then the separator", substructure.py)
+                    levels = 1
+        if levels == 1:
+            blocks = (cls.SUB_BLOCK or (192 if n <= 8000 else max(320, int(320 * (n / 60000.0) ** (2.0 / 3.0)))),)
+        elif precond:
+            blocks = (cls.SUB2_BLOCK or cls.PD_BLOCKS[0], cls.SUB2_SUPER or cls.PD_BLOCKS[1],
+                      cls.PD_BLOCKS[2] if cls.SUB3_BIG == 32768 else cls.SUB3_BIG)
+        elif levels:
+            blocks = (cls.SUB2_BLOCK or (128 if n < 200_000 else 160),
+                      *((cls.SUB2_SUPER or max(2048, n // 60),) if levels == 2 else (cls.SUB2_SUPER or 4096, cls.SUB3_BIG)))
+        else:
+            blocks = ()
+        if levels:
+            form = "precond" if precond else "sub"
+        elif single and direct_solve and 2 <= n <= (cls.DENSE_MAX_SITES if dense_max_sites is None else int(dense_max_sites)):
+            form = "dense"
+        else:
+            form = "amg"
+        # (with the factors as second preconditioner the V-cycle only runs where the guess is good -- two or three
+        # iterations per solve --, and 3 % fewer of those do not pay for two more hierarchies: 4.5 s of set-up at 1M sites)
+        candidates = cls.AMG_CANDIDATES if (form == "amg" and single and n >= cls.AMG_CANDIDATES_MIN_SITES) else 1
+        return MuPlan(form=form, levels=levels, blocks=blocks,
+                      sparse_sep=levels == 3 or (levels == 2 and n >= cls.SUB2_SPARSE_SEP_MIN_SITES),
+                      # large enough for the iterative solve to beat the direct one in a stationary state: let the loop choose
+                      switching=form == "sub" and n >= cls.DIRECT_SWITCH_MIN_SITES, amg_candidates=candidates)
 
     def build_poisson(self, rtol=1e-10, max_iter=500, nu=2, check_every=0,
                       edge_currents_every_step=True, max_coarse=600, smoother="chebyshev",
@@ -283,15 +337,10 @@ class TDGLContext:
         k = self._keep
         with _Stopwatch(self.setup_times, "amg_host"):
             A = poisson_matrix(k["edges"].astype(np.int64), k["dl"] / k["el"], self.n, self.iperm)
-        iterative = not (self.n_owned == self.n and self.direct_solve and (
-            (self._sub_part_ptr is not None and dense_max_sites is None)
-            or 2 <= self.n <= (self.DENSE_MAX_SITES if dense_max_sites is None else int(dense_max_sites))))
+        plan = self.mu if dense_max_sites is None else self.mu_plan(self.n, self.n_owned, self.direct_solve,
+                                                                    dense_max_sites=dense_max_sites)
         if amg_candidates is None:
-            amg_candidates = self.AMG_CANDIDATES if (iterative and self.n >= self.AMG_CANDIDATES_MIN_SITES) else 1
-            # (with the factors as second preconditioner the V-cycle only runs where the guess is good -- two or three
-            # iterations per solve --, and 3 % fewer of those do not pay for two more hierarchies: 4.5 s of set-up at 1M sites)
-            if self._pd_order is not None and dense_max_sites is None and self.direct_solve:
-                amg_candidates = 1
+            amg_candidates = plan.amg_candidates
         if self.n_owned != self.n:
             amg_candidates = 1
         best, scores = None, []
@@ -323,16 +372,13 @@ class TDGLContext:
                 self.set_poisson_options(rtol, max_iter, nu, check_every, edge_currents_every_step,
                                          smoother, cheb_lo, extrapolate, nu_fine)
         h = best[2]
-        limit = self.DENSE_MAX_SITES if dense_max_sites is None else int(dense_max_sites)
-        if not self.direct_solve:
-            limit = 0
         # (the factors are held to the tighter of 1e-11 and the iterative solve's tolerance)
         check = min(1e-11, float(rtol))
-        if self.n_owned == self.n and self._sub_part_ptr is not None and dense_max_sites is None and self.direct_solve:
+        if plan.form == "sub":
             self.build_substructure(A, check_rtol=check)
-        elif self.n_owned == self.n and self._pd_order is not None and dense_max_sites is None and self.direct_solve:
+        elif plan.form == "precond":
             self.build_precond_direct(rtol=float(rtol))
-        elif self.n_owned == self.n and 2 <= self.n <= limit:
+        elif plan.form == "dense":
             self.build_dense_inverse(A, check_rtol=check)
         return h
 
@@ -349,95 +395,42 @@ class TDGLContext:
         """Switch the mu solve to the substructured direct solve (`tdgl_poisson_set_substructure`); the
         context must have been created with the substructure site order (mid-size meshes are).  Checked on a
         random right-hand side like `build_dense_inverse`; returns whether it is on."""
-        import os
+        from . import substructure  # (its functions are looked up when called: tests replace `pack_for_device` there)
 
-        from .substructure import build_substructure, pack_for_device, plan_for_device
-
-        if self._sub_part_ptr is None:
+        if not self._sub_ptrs:
             raise ValueError("this context's site order is not a substructure order")
         if A is None:
             k = self._keep
             A = poisson_matrix(k["edges"].astype(np.int64), k["dl"] / k["el"], self.n, self.iperm)
         sec = C.c_double(0.0)
-        p_i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-
-        def describe(pk):
-            return _lib.Substructure(
-                n_interior=pk["n_interior"], n_sep=pk["n_sep"], n_parts=pk["n_parts"], part_ptr=p_i32(pk["part_ptr"]),
-                seg_ptr=p_i32(pk["seg_ptr"]), seg_val=p_i64(pk["seg_val"]), seg_x=p_i32(pk["seg_x"]),
-                seg_len=p_i32(pk["seg_len"]), vals=p_f64(pk["vals"]), n_vals=len(pk["vals"]), sep_ptr=p_i32(pk["sep_ptr"]),
-                sep_idx=p_i32(pk["sep_idx"]), e_off=p_i64(pk["e_off"]), e_vals=p_f64(pk["e_vals"]),
-                n_e=len(pk["e_vals"]), u=p_f64(pk["u"]), schur=None if pk["schur"] is None else p_f64(pk["schur"]),
-            )
-
-        if self._sub_big_ptr is not None:
-            # three levels: the factors are formed on the host, the top separator's pseudo-inverse on the device
-            from .substructure import build_substructure_levels
-
+        if len(self._sub_ptrs) > 1:
+            # two or three levels: the factors are formed on the host, the top separator's pseudo-inverse on the device
+            sparse_sep = self.mu.sparse_sep
             with _Stopwatch(self.setup_times, "substructure_host"):
                 try:
-                    levels = build_substructure_levels(A, [self._sub_part_ptr, self._sub_super_ptr, self._sub_big_ptr])
-                    packed = [pack_for_device(lv, True) for lv in levels]
-                except (ValueError, IndexError, np.linalg.LinAlgError) as exc:
-                    self.setup_times["substructure_error"] = repr(exc)
-                    return False
-            status, t_dev = self._upload_levels(levels, packed)
-            tiles = [0, 0, 0]
-            if status == _lib.TDGL_OK:
-                status, tiles = self._compact_direct_factors()
-            sec = C.c_double(t_dev)
-            sym = lambda m: 8 * ((m + 127) // 128) * (((m + 127) // 128) + 1) // 2 * 128 * 128
-            info = dict(levels=3, sparse_separator_rhs=True, parts=levels[0].n_parts, separator=levels[0].n_sep,
-                        super_blocks=levels[1].n_parts, top_separator=levels[1].n_sep, super_super_blocks=levels[2].n_parts,
-                        top_top_separator=levels[2].n_sep, built_on="host", symmetric_tiles=[bool(t) for t in tiles],
-                        bytes_per_solve=int(sum(8 * g.size for lv in levels for g in lv.G) + sum(8 * e.size for lv in levels for e in lv.E)
-                                            + 12 * sum(lv.coupling.nnz for lv in levels) + sym(levels[2].n_sep)
-                                            - self._tile_savings([lv.G for lv in levels], tiles)))
-            del levels, packed
-        elif self._sub_super_ptr is not None:
-            # two levels: the factors of both are formed on the host, the top separator's pseudo-inverse on the device
-            from .substructure import build_substructure2
-
-            with _Stopwatch(self.setup_times, "substructure_host"):
-                try:
-                    sub2 = build_substructure2(A, self._sub_part_ptr, self._sub_super_ptr)
-                    sparse_sep = self.n >= self.SUB2_SPARSE_SEP_MIN_SITES
-                    pk_o, pk_i = pack_for_device(sub2.outer, sparse_sep), pack_for_device(sub2.inner, sparse_sep)
+                    levels = substructure.build_substructure_levels(A, self._sub_ptrs)
+                    packed = [substructure.pack_for_device(lv, sparse_sep) for lv in levels]
                 except (ValueError, IndexError, np.linalg.LinAlgError) as exc:
                     # (a mesh the dissection cannot cut as it expects -- a super-block without interior, pieces that are
                     # not connected: the iterative solve takes it)
                     self.setup_times["substructure_error"] = repr(exc)
                     return False
-            status = self._lib.tdgl_poisson_set_substructure(self._ctx, C.byref(describe(pk_o)), C.byref(sec))
-            t_dev = sec.value
-            if status == _lib.TDGL_OK:
-                status = self._lib.tdgl_poisson_set_substructure_inner(self._ctx, C.byref(describe(pk_i)), C.byref(sec))
-                t_dev += sec.value
-            if status == _lib.TDGL_OK and sparse_sep:
-                for level, M in ((0, sub2.outer.coupling), (1, sub2.inner.coupling)):
-                    keep_c = (i32(M.indptr), i32(M.indices), f64(M.data))
-                    status = self._lib.tdgl_poisson_set_substructure_coupling(self._ctx, level, p_i32(keep_c[0]), p_i32(keep_c[1]),
-                                                                              p_f64(keep_c[2]))
-                    if status != _lib.TDGL_OK:
-                        break
+            status, t_dev = self._upload_levels(levels, packed, sparse_sep)
             tiles = [0, 0, 0]
             if status == _lib.TDGL_OK:
                 status, tiles = self._compact_direct_factors()
             sec = C.c_double(t_dev)
-            info = dict(levels=2, sparse_separator_rhs=bool(sparse_sep), parts=sub2.outer.n_parts, separator=sub2.outer.n_sep, super_blocks=sub2.inner.n_parts,
-                        top_separator=sub2.inner.n_sep, built_on="host", symmetric_tiles=[bool(t) for t in tiles[:2]],
-                        bytes_per_solve=sub2.bytes_per_solve() - (0 if not sparse_sep else sum(
-                            8 * e.size for lv in (sub2.outer, sub2.inner) for e in lv.E) - 12 * (
-                                sub2.outer.coupling.nnz + sub2.inner.coupling.nnz))
-                        - self._tile_savings([sub2.outer.G, sub2.inner.G], tiles))
-            del sub2, pk_o, pk_i
+            info = dict(levels=len(levels), sparse_separator_rhs=sparse_sep, **_level_counts(levels), built_on="host",
+                        symmetric_tiles=[bool(t) for t in tiles[:len(levels)]], bytes_per_solve=_factor_bytes(levels, tiles, sparse_sep))
+            del levels, packed
         elif not os.environ.get("TDGL_SUB_HOST"):
             # the factors are formed on the device; the host only describes the structure
             with _Stopwatch(self.setup_times, "substructure_host"):
                 try:
-                    pl = plan_for_device(A, self._sub_part_ptr)
+                    pl = substructure.plan_for_device(A, self._sub_ptrs[0])
                 except ValueError:
                     return False
+            p_i64 = lambda a: a.ctypes.data_as(_lib.c_i64p)
             d = _lib.SubstructurePlan(
                 n_interior=pl["n_interior"], n_sep=pl["n_sep"], n_parts=pl["n_parts"], part_ptr=p_i32(pl["part_ptr"]),
                 sep_ptr=p_i32(pl["sep_ptr"]), sep_idx=p_i32(pl["sep_idx"]), ent_ptr=p_i32(pl["ent_ptr"]), ent_row=p_i32(pl["ent_row"]),
@@ -452,15 +445,14 @@ class TDGLContext:
         else:
             with _Stopwatch(self.setup_times, "substructure_host"):
                 try:
-                    sub = build_substructure(A, self._sub_part_ptr)
+                    sub = substructure.build_substructure(A, self._sub_ptrs[0])
                 except (ValueError, np.linalg.LinAlgError):
                     return False
-                pk = pack_for_device(sub)
-            status = self._lib.tdgl_poisson_set_substructure(self._ctx, C.byref(describe(pk)), C.byref(sec))
-            info = dict(parts=sub.n_parts, separator=sub.n_sep, bytes_per_solve=sub.bytes_per_solve(), built_on="host")
+                pk = substructure.pack_for_device(sub)
+            status = self._lib.tdgl_poisson_set_substructure(self._ctx, C.byref(_lib.describe(pk)), C.byref(sec))
+            info = dict(parts=sub.n_parts, separator=sub.n_sep, bytes_per_solve=_factor_bytes([sub], [0], sparse_sep=False), built_on="host")
         if status != _lib.TDGL_OK:
-            err = self._lib.tdgl_last_error(self._ctx)
-            self.setup_times["substructure_error"] = err.decode() if isinstance(err, bytes) else str(err)
+            self._note_library_error()
             return False
         self.setup_times["substructure_device"] = sec.value
         if not self._direct_solve_passes(check_rtol):
@@ -468,8 +460,7 @@ class TDGLContext:
             return False
         self.substructure = info
         self.dense_direct = True
-        # large enough for the iterative solve to beat the direct one in a stationary state: let the loop choose
-        if self.n >= self.DIRECT_SWITCH_MIN_SITES:
+        if self.mu.switching:
             self.direct_switching(True)
         return True
 
@@ -482,35 +473,24 @@ class TDGLContext:
         status = self._lib.tdgl_poisson_set_substructure_layout(self._ctx, int(bool(self.SUB_SYM_TILES)))
         return status, (self.precond_direct_layout() if status == _lib.TDGL_OK else [0, 0, 0])
 
-    @staticmethod
-    def _tile_savings(G_by_level, tiles) -> int:
-        """Bytes per solve a level stored as fp64 tiles on or below the diagonal does not stream."""
-        tri = lambda m: ((m + 15) // 16) * (((m + 15) // 16) + 1) // 2 * 256
-        return int(sum(8 * (g.size - tri(g.shape[0])) for k, Gs in enumerate(G_by_level) if tiles[k] for g in Gs))
+    def _note_library_error(self):
+        """A refused upload: the library's message goes into ``setup_times["substructure_error"]``."""
+        err = self._lib.tdgl_last_error(self._ctx)
+        self.setup_times["substructure_error"] = err.decode() if isinstance(err, bytes) else str(err)
 
-    def _upload_levels(self, levels, packed):
-        """The factors of a multi-level dissection (`substructure.build_substructure_levels`, `pack_for_device(..., True)`)
-        into the library: first level, inner levels, every level's sparse coupling block.  Returns (status, device seconds)."""
+    def _upload_levels(self, levels, packed, sparse_sep=True):
+        """The factors of a multi-level dissection (`substructure.build_substructure_levels`, `pack_for_device`) into the
+        library: first level, inner levels, and with ``sparse_sep`` every level's sparse coupling block.  Returns
+        (status, device seconds)."""
         sec = C.c_double(0.0)
-        p_i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
-
-        def describe(pk):
-            return _lib.Substructure(
-                n_interior=pk["n_interior"], n_sep=pk["n_sep"], n_parts=pk["n_parts"], part_ptr=p_i32(pk["part_ptr"]),
-                seg_ptr=p_i32(pk["seg_ptr"]), seg_val=p_i64(pk["seg_val"]), seg_x=p_i32(pk["seg_x"]),
-                seg_len=p_i32(pk["seg_len"]), vals=p_f64(pk["vals"]), n_vals=len(pk["vals"]), sep_ptr=p_i32(pk["sep_ptr"]),
-                sep_idx=p_i32(pk["sep_idx"]), e_off=p_i64(pk["e_off"]), e_vals=p_f64(pk["e_vals"]),
-                n_e=len(pk["e_vals"]), u=p_f64(pk["u"]), schur=None if pk["schur"] is None else p_f64(pk["schur"]),
-            )
-
         t_dev, status = 0.0, _lib.TDGL_OK
         for k, pk in enumerate(packed):
             call = self._lib.tdgl_poisson_set_substructure if k == 0 else self._lib.tdgl_poisson_set_substructure_inner
-            status = call(self._ctx, C.byref(describe(pk)), C.byref(sec))
+            status = call(self._ctx, C.byref(_lib.describe(pk)), C.byref(sec))
             t_dev += sec.value
             if status != _lib.TDGL_OK:
                 return status, t_dev
-        for k, lv in enumerate(levels):
+        for k, lv in enumerate(levels if sparse_sep else ()):
             M = lv.coupling
             keep_c = (i32(M.indptr), i32(M.indices), f64(M.data))
             status = self._lib.tdgl_poisson_set_substructure_coupling(self._ctx, k, p_i32(keep_c[0]), p_i32(keep_c[1]), p_f64(keep_c[2]))
@@ -524,7 +504,7 @@ class TDGLContext:
         the dissection's order (`_pd_order`), stored in fp32 on the device, applied through a gather / scatter so that
         the context keeps its reverse Cuthill-McKee order.  Checked on a white-noise right-hand side from a zero guess
         (the CG must get to ``rtol`` in at most three applications); returns whether it is on."""
-        from .substructure import build_substructure_levels, pack_for_device
+        from . import substructure
 
         perm_d, p1, p2, p3 = self._pd_order
         k = self._keep
@@ -533,8 +513,8 @@ class TDGLContext:
         with _Stopwatch(self.setup_times, "substructure_host"):
             try:
                 A_d = poisson_matrix(k["edges"].astype(np.int64), k["dl"] / k["el"], self.n, iperm_d)
-                levels = build_substructure_levels(A_d, [p1, p2, p3])
-                packed = [pack_for_device(lv, True) for lv in levels]
+                levels = substructure.build_substructure_levels(A_d, [p1, p2, p3])
+                packed = [substructure.pack_for_device(lv, True) for lv in levels]
             except (ValueError, IndexError, np.linalg.LinAlgError) as exc:
                 self.setup_times["substructure_error"] = repr(exc)
                 return False
@@ -544,23 +524,17 @@ class TDGLContext:
             keep_map = i32(perm_d)
             status = self._lib.tdgl_poisson_set_substructure_precond(self._ctx, p_i32(keep_map), 1, C.byref(ta), C.byref(tv))
         if status != _lib.TDGL_OK:
-            err = self._lib.tdgl_last_error(self._ctx)
-            self.setup_times["substructure_error"] = err.decode() if isinstance(err, bytes) else str(err)
+            self._note_library_error()
             self._chk(self._lib.tdgl_poisson_set_substructure(self._ctx, None, None))
             return False
         self.setup_times["substructure_device"] = t_dev
-        sym = lambda m: ((m + 127) // 128) * (((m + 127) // 128) + 1) // 2 * 128 * 128
         tiles = self.precond_direct_layout()  # per level: G blocks as 16 x 16 tiles on or below the diagonal?
-        tri = lambda m: ((m + 15) // 16) * (((m + 15) // 16) + 1) // 2 * 256
-        entries = (sum((tri(g.shape[0]) if tiles[k] else g.size) for k, lv in enumerate(levels) for g in lv.G)
-                   + sum(e.size for lv in levels for e in lv.E) + sym(levels[2].n_sep))
-        info = dict(levels=3, storage="fp32", symmetric_tiles=[bool(t) for t in tiles], parts=levels[0].n_parts, separator=levels[0].n_sep, super_blocks=levels[1].n_parts,
-                    top_separator=levels[1].n_sep, super_super_blocks=levels[2].n_parts, top_top_separator=levels[2].n_sep,
-                    bytes_per_application=int(4 * entries + 12 * sum(lv.coupling.nnz for lv in levels) + 2 * 20 * self.n),
+        info = dict(levels=3, storage="fp32", symmetric_tiles=[bool(t) for t in tiles], **_level_counts(levels),
+                    bytes_per_application=_factor_bytes(levels, tiles, word=4) + 2 * 20 * self.n,
                     t_apply_us=round(ta.value, 1), t_vcycle_us=round(tv.value, 1))
         blr = self.precond_direct_blr()
         if blr["on"]:  # (the top separator's tiles replaced by the block low-rank form)
-            info["bytes_per_application"] += blr["bytes"] - 4 * sym(levels[2].n_sep)
+            info["bytes_per_application"] += blr["bytes"] - 4 * _sym_tile_entries(levels[2].n_sep)
             info["top_separator_blr"] = blr
         del levels, packed
         # the check: with the factors forced, a white-noise right-hand side from a zero guess
@@ -583,14 +557,14 @@ class TDGLContext:
         ``allreduce_max(array) -> array`` over the bootstrap group: the interface complement is summed ONCE, the measured
         times of the two preconditioners are agreed on (so that every rank takes the same choice in every solve).  Every
         rank calls this at the same point; returns whether the preconditioner is on (the same answer on every rank)."""
-        from .substructure import build_substructure_levels, pack_for_device
+        from . import substructure
 
         ok = 1.0
         levels = packed = None
         with _Stopwatch(self.setup_times, "substructure_host"):
             try:
-                levels = build_substructure_levels(piece.A_II, piece.ptrs, gauge=False)
-                packed = [pack_for_device(lv, True) for lv in levels]
+                levels = substructure.build_substructure_levels(piece.A_II, piece.ptrs, gauge=False)
+                packed = [substructure.pack_for_device(lv, True) for lv in levels]
             except (ValueError, IndexError, np.linalg.LinAlgError) as exc:
                 self.setup_times["substructure_error"] = repr(exc)
                 ok = 0.0
@@ -617,8 +591,7 @@ class TDGLContext:
         failed = float(allreduce_max(np.array([0.0 if status == _lib.TDGL_OK else 1.0]))[0]) > 0.0
         if failed:
             if status != _lib.TDGL_OK:
-                err = self._lib.tdgl_last_error(self._ctx)
-                self.setup_times["substructure_error"] = err.decode() if isinstance(err, bytes) else str(err)
+                self._note_library_error()
             self._chk(self._lib.tdgl_poisson_set_substructure(self._ctx, None, None))
             return False
         with _Stopwatch(self.setup_times, "schur_sum"):
@@ -630,13 +603,10 @@ class TDGLContext:
         self._chk(self._lib.tdgl_poisson_precond_choice(self._ctx, int(self.PD_CHOICE if choice is None else choice)))
         self.setup_times["substructure_device"] = t_dev
         tiles = self.precond_direct_layout()
-        tri = lambda m: ((m + 15) // 16) * (((m + 15) // 16) + 1) // 2 * 256
-        entries = (sum((tri(g.shape[0]) if tiles[k] else g.size) for k, lv in enumerate(levels) for g in lv.G)
-                   + sum(e.size for lv in levels for e in lv.E))
         self.precond_direct = dict(
             kind="rank-level nested dissection", levels=len(levels), storage="fp32", symmetric_tiles=[bool(t) for t in tiles[:len(levels)]], interior=int(piece.n_interior), interface=ng,
             interface_owned=int(len(keep["gl"])), parts=levels[0].n_parts, separator=levels[0].n_sep,
-            bytes_per_application=int(2 * (4 * entries + 12 * sum(lv.coupling.nnz for lv in levels)) + 4 * ng * ng // 2
+            bytes_per_application=int(2 * _factor_bytes(levels, tiles, word=4, top=False) + 4 * ng * ng // 2
                                       + 12 * (piece.A_GI.nnz + piece.A_IG.nnz)),
             allreduce_doubles_per_application=ng, t_apply_us=round(float(times[0]), 1), t_vcycle_us=round(float(times[1]), 1))
         self.precond_direct_stats(reset=True)
@@ -685,8 +655,6 @@ class TDGLContext:
         the residual the library reports for a one-off solve); a matrix that fails, or whose
         factorisation breaks down (a mesh in several pieces), stays with AMG-PCG.  Returns whether the
         direct solve is on."""
-        import os
-
         ok = False
         if not os.environ.get("TDGL_DENSE_HOST"):
             sec = C.c_double(0.0)

@@ -21,7 +21,8 @@ Bytes per solve at 59k sites with 128 parts: 220 MB of G, 2 x 36 MB of E, 117 MB
 inverse -- 0.4 GB, ~75 us, against nine PCG iterations of ~30 us.  The crossover with AMG-PCG is where the
 separator's dense inverse stops fitting the time budget (~150k sites).
 
-`solve_host` restates the device algorithm in NumPy (CPU tests; not used by the product path).
+`solve_host_levels` restates the device algorithm in NumPy, for any number of levels (CPU tests; not used by the
+product path).
 """
 
 from dataclasses import dataclass
@@ -80,16 +81,11 @@ class Substructure:
     def n_sep(self):
         return self.n - self.n_interior
 
-    def bytes_per_solve(self):
-        sym = lambda m: 8 * ((m + 127) // 128) * (((m + 127) // 128) + 1) // 2 * 128 * 128
-        return (sum(8 * g.size for g in self.G) + 2 * sum(8 * e.size for e in self.E)
-                + (sym(self.n_sep) if self.schur is not None else 0))
-
 
 def build_substructure(A: sp.spmatrix, part_ptr: np.ndarray, weights: np.ndarray = None, with_schur: bool = True) -> Substructure:
     """``A`` = the level-0 Poisson matrix in the internal order `substructure_order` produced.
 
-    ``weights`` (two-level form, `build_substructure2`): the functional whose value on the solution the factors
+    ``weights`` (the levels below the first, `build_substructure_levels`): the functional whose value on the solution the factors
     must deliver -- ``g = G_p w_p`` and ``u = w_S - sum_p E_p^T w_p`` so that ``w . x = g . b_I + u . x_S``
     (default: ``w = 1`` with the ``1_S . x_S`` term dropped, x_S being the zero-sum solution of the Schur system).
     ``with_schur=False``: the Schur complement is not formed densely (`Substructure.schur` is None); the blocks
@@ -198,98 +194,6 @@ def substructure_order2(sites: np.ndarray, edges: np.ndarray, target_block: int 
     return perm, part_ptr, super_ptr
 
 
-@dataclass
-class Substructure2:
-    """Two-level factors: `outer` eliminates the part interiors (no dense Schur complement), `inner` is the
-    same construction applied to the outer level's Schur complement S1 on [S'_0 .. S'_{Q-1} | T]."""
-    outer: Substructure
-    inner: Substructure
-
-    def bytes_per_solve(self):
-        return self.outer.bytes_per_solve() + self.inner.bytes_per_solve()
-
-
-def build_substructure2(A: sp.spmatrix, part_ptr: np.ndarray, super_ptr: np.ndarray) -> Substructure2:
-    """``A`` in the internal order of `substructure_order2`."""
-    A = A.tocsr()
-    n = A.shape[0]
-    nI = int(part_ptr[-1])
-    nS = n - nI
-    outer = build_substructure(A, part_ptr, with_schur=False)
-    # S1 = A_SS - sum_p A_Sp E_p as a sparse matrix: the blocks of different super-blocks do not overlap
-    # outside T, so it has ~ (|S'_Q| + |T_Q|)^2 entries per super-block
-    rows, cols, vals = [], [], []
-    for idx, C in zip(outer.sep_idx, outer.C):
-        k = len(idx)
-        rows.append(np.repeat(idx, k))
-        cols.append(np.tile(idx, k))
-        vals.append(-C.ravel())
-    ASS = A[nI:, nI:].tocoo()
-    rows.append(ASS.row)
-    cols.append(ASS.col)
-    vals.append(ASS.data)
-    S1 = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(nS, nS)).tocsr()
-    S1 = (0.5 * (S1 + S1.T)).tocsr()
-    outer.C = None
-    # the functional sum x = sum_p g_p . b_p + v . x_S with v = 1_S - sum_p E_p^T 1 is carried down a level
-    v = 1.0 + outer.u
-    inner = build_substructure(S1, np.asarray(super_ptr, dtype=np.int64) - nI, weights=v)
-    # the sparse coupling blocks (separator rows x interior columns) of both levels: r_S = b_S - A_SI y_I
-    outer.coupling = A[nI:, :nI].tocsr()
-    nI2 = int(super_ptr[-1]) - nI
-    inner.coupling = S1[nI2:, :nI2].tocsr()
-    return Substructure2(outer=outer, inner=inner)
-
-
-def solve_host2(sub2: Substructure2, b: np.ndarray, spinv: np.ndarray = None, remove_mean: bool = True,
-                sparse_sep: bool = False) -> np.ndarray:
-    """The two-level device sequence in NumPy (six launches: down, down, dense pair, up, up; ``sparse_sep``: the
-    separator right-hand sides through the sparse coupling blocks, two more launches, a fifth of the bytes less)."""
-    o, q = sub2.outer, sub2.inner
-    nI, P = o.n_interior, o.n_parts
-    if remove_mean:
-        b = b - b.mean()
-    y = np.empty(nI)
-    r = b[nI:].copy()
-    total = 0.0
-    for p in range(P):
-        a, e = int(o.part_ptr[p]), int(o.part_ptr[p + 1])
-        y[a:e] = o.G[p] @ b[a:e]
-        if not sparse_sep:
-            r[o.sep_idx[p]] -= o.E[p].T @ b[a:e]
-        total += o.g[a:e] @ b[a:e]
-    if sparse_sep:
-        r -= o.coupling @ y
-    # the Schur system S1 x_S = r on the second level; no gauge: v . x_S is what the first level needs
-    nI2, Q = q.n_interior, q.n_parts
-    if spinv is None:
-        spinv = schur_pinv(q.schur)
-    y2 = np.empty(nI2)
-    rT = r[nI2:].copy()
-    for k in range(Q):
-        a, e = int(q.part_ptr[k]), int(q.part_ptr[k + 1])
-        y2[a:e] = q.G[k] @ r[a:e]
-        if not sparse_sep:
-            rT[q.sep_idx[k]] -= q.E[k].T @ r[a:e]
-        total += q.g[a:e] @ r[a:e]
-    if sparse_sep:
-        rT -= q.coupling @ y2
-    xT = spinv @ rT
-    total += q.u @ xT
-    xs = np.empty(o.n_sep)
-    for k in range(Q):
-        a, e = int(q.part_ptr[k]), int(q.part_ptr[k + 1])
-        xs[a:e] = y2[a:e] - q.E[k] @ xT[q.sep_idx[k]]
-    xs[nI2:] = xT
-    mean = total / o.n
-    x = np.empty(o.n)
-    for p in range(P):
-        a, e = int(o.part_ptr[p]), int(o.part_ptr[p + 1])
-        x[a:e] = y[a:e] - o.E[p] @ xs[o.sep_idx[p]] - mean
-    x[nI:] = xs - mean
-    return x
-
-
 def substructure_order3(sites: np.ndarray, edges: np.ndarray, target_block: int = 160, target_super: int = 4096,
                         target_big: int = 32768, rank_hint=None):
     """Three levels: like `substructure_order2` with one more cut above it -- super-super-blocks of ``target_big`` sites
@@ -377,10 +281,20 @@ def build_substructure_levels(A: sp.spmatrix, ptrs, gauge: bool = True) -> List[
     return levels
 
 
-def solve_host_levels(levels: List[Substructure], b: np.ndarray, sparse_sep: bool = True) -> np.ndarray:
-    """The multi-level device sequence in NumPy: ways down, the dense top separator, ways up, the mean removed."""
+def solve_host_levels(levels: List[Substructure], b: np.ndarray, sparse_sep: bool = True, remove_mean: bool = True) -> np.ndarray:
+    """The device algorithm in NumPy for any number of levels -- ways down, the dense top separator, ways up, the mean
+    removed: ``pinv(A) b``, the zero-mean solution of ``A x = b - mean(b)`` (``sparse_sep``: the separator right-hand
+    sides through the sparse coupling blocks, a launch more per level, instead of the -E^T rows).
+
+    The launches themselves assume a right-hand side orthogonal to the constants: the pseudo-inverse
+    of the Schur complement projects the SEPARATOR residual only, so for ``sum(b) != 0`` the bare sequence
+    answers ``A x = b - (sum(b) / n_S) e_S`` instead (an error ~25x ``mean(b)`` on a 1.5k-site mesh).  In the
+    time loop ``sum(b) = 0`` holds to round-off (the divergence of an edge field sums to zero site-area
+    weighted, and `validate_terminal_currents` makes the terminal currents add up to zero), and the
+    library's one-off entry point `tdgl_poisson_solve` removes the mean first, as ``remove_mean`` does here;
+    ``remove_mean=False`` reproduces the bare sequence (tests)."""
     n = levels[0].n
-    vec = b - b.mean()
+    vec = b - b.mean() if remove_mean else b
     ys, total = [], 0.0
     for lv in levels:
         nI = lv.n_interior
@@ -414,39 +328,6 @@ def schur_pinv(schur: np.ndarray) -> np.ndarray:
     s = float(np.diag(schur).mean())
     inv = np.linalg.inv(schur + s / m)
     return 0.5 * (inv + inv.T) - 1.0 / (s * m)
-
-
-def solve_host(sub: Substructure, b: np.ndarray, spinv: np.ndarray = None, remove_mean: bool = True) -> np.ndarray:
-    """The device algorithm in NumPy: ``pinv(A) b``, the zero-mean solution of ``A x = b - mean(b)``.
-
-    The four launches themselves assume a right-hand side orthogonal to the constants: the pseudo-inverse
-    of the Schur complement projects the SEPARATOR residual only, so for ``sum(b) != 0`` the bare sequence
-    answers ``A x = b - (sum(b) / n_S) e_S`` instead (an error ~25x ``mean(b)`` on a 1.5k-site mesh).  In the
-    time loop ``sum(b) = 0`` holds to round-off (the divergence of an edge field sums to zero site-area
-    weighted, and `validate_terminal_currents` makes the terminal currents add up to zero), and the
-    library's one-off entry point `tdgl_poisson_solve` removes the mean first, as ``remove_mean`` does here;
-    ``remove_mean=False`` reproduces the bare sequence (tests)."""
-    nI, P = sub.n_interior, sub.n_parts
-    if remove_mean:
-        b = b - b.mean()
-    if spinv is None:
-        spinv = schur_pinv(sub.schur)
-    y = np.empty(nI)
-    r = b[nI:].copy()
-    gd = np.empty(P)
-    for p in range(P):
-        a, e = int(sub.part_ptr[p]), int(sub.part_ptr[p + 1])
-        y[a:e] = sub.G[p] @ b[a:e]
-        r[sub.sep_idx[p]] -= sub.E[p].T @ b[a:e]
-        gd[p] = sub.g[a:e] @ b[a:e]
-    xs = spinv @ r
-    mean = (gd.sum() + sub.u @ xs) / sub.n
-    x = np.empty(sub.n)
-    for p in range(P):
-        a, e = int(sub.part_ptr[p]), int(sub.part_ptr[p + 1])
-        x[a:e] = y[a:e] - sub.E[p] @ xs[sub.sep_idx[p]] - mean
-    x[nI:] = xs - mean
-    return x
 
 
 def pack_for_device(sub: Substructure, sparse_sep: bool = False):

@@ -1073,11 +1073,11 @@ def test_rho_estimate_stays_above_the_spectrum():
 
 def test_substructured_solve_on_the_host():
     """Set-up of the substructured direct solve (tdgl_amd/substructure.py): the order (interiors part by part,
-    then a separator that covers every cut edge), the block formulas (solve_host = the device algorithm) against
+    then a separator that covers every cut edge), the block formulas (solve_host_levels = the device algorithm) against
     the dense pseudo-inverse, and the packed segment form the library consumes."""
     from tdgl_amd.amg import exact_pinv
     from tdgl_amd.hipcore import poisson_matrix, rcm_permutation
-    from tdgl_amd.substructure import build_substructure, down_host, pack_for_device, solve_host, substructure_order
+    from tdgl_amd.substructure import build_substructure, down_host, pack_for_device, solve_host_levels, substructure_order
 
     mesh = synthetic_mesh(30)
     em = mesh.edge_mesh
@@ -1095,14 +1095,14 @@ def test_substructured_solve_on_the_host():
     assert np.abs(sub.schur.sum(axis=1)).max() < 1e-12 * np.abs(sub.schur).max()  # singular like A
     b = np.random.default_rng(2).standard_normal(n)
     b -= b.mean()
-    x = solve_host(sub, b)
+    x = solve_host_levels([sub], b, sparse_sep=False)
     want = exact_pinv(A) @ b
     assert np.abs(x - want).max() < 1e-11 * np.abs(want).max() and abs(x.mean()) < 1e-14
     # a right-hand side with a mean: pinv(A) b all the same -- the mean is removed first; the bare launch
     # sequence is only valid for sum(b) = 0 (it projects the separator residual only)
     b1 = b + 1e-3
-    assert np.abs(solve_host(sub, b1) - want).max() < 1e-11 * np.abs(want).max()
-    assert np.abs(solve_host(sub, b1, remove_mean=False) - want).max() > 1e-4 * np.abs(want).max()
+    assert np.abs(solve_host_levels([sub], b1, sparse_sep=False) - want).max() < 1e-11 * np.abs(want).max()
+    assert np.abs(solve_host_levels([sub], b1, sparse_sep=False, remove_mean=False) - want).max() > 1e-4 * np.abs(want).max()
     pk = pack_for_device(sub)
     w = down_host(pk, b)
     nI, P = sub.n_interior, sub.n_parts
@@ -1115,13 +1115,13 @@ def test_substructured_solve_on_the_host():
 
 
 def test_two_level_substructured_solve_on_the_host():
-    """Two levels of nested dissection (substructure_order2 / build_substructure2): the order -- part interiors, the
+    """Two levels of nested dissection (substructure_order2 / build_substructure_levels): the order -- part interiors, the
     fine separators super-block by super-block, the top separator -- decouples what it must, the second level is the
-    first level's construction applied to its Schur complement, and the six-launch sequence (solve_host2) returns
+    first level's construction applied to its Schur complement, and the six-launch sequence (solve_host_levels) returns
     pinv(A) b with the gauge carried down as a functional."""
     from tdgl_amd.amg import exact_pinv
     from tdgl_amd.hipcore import poisson_matrix, rcm_permutation
-    from tdgl_amd.substructure import build_substructure2, pack_for_device, down_host, solve_host2, substructure_order2
+    from tdgl_amd.substructure import build_substructure_levels, pack_for_device, down_host, solve_host_levels, substructure_order2
 
     mesh = synthetic_mesh(40)
     em = mesh.edge_mesh
@@ -1140,16 +1140,16 @@ def test_two_level_substructured_solve_on_the_host():
     blk = np.searchsorted(sp_, np.arange(sp_[0], sp_[-1]), side="right")
     C = A[sp_[0]:sp_[-1], sp_[0]:sp_[-1]].tocoo()
     assert np.all(blk[C.row] == blk[C.col])
-    sub2 = build_substructure2(A, pp, sp_)  # ... nor through a part (the second level's build raises otherwise)
-    o, q = sub2.outer, sub2.inner
+    levels = build_substructure_levels(A, [pp, sp_])  # ... nor through a part (the second level's build raises otherwise)
+    o, q = levels
     assert o.schur is None and o.n_interior + o.n_sep == n and q.n_interior + q.n_sep == o.n_sep and q.n_parts == Q
     assert np.abs(q.schur.sum(axis=1)).max() < 1e-11 * np.abs(q.schur).max()  # singular like A
     b = np.random.default_rng(3).standard_normal(n)
     b -= b.mean()
-    x = solve_host2(sub2, b)
+    x = solve_host_levels(levels, b, sparse_sep=False)
     want = exact_pinv(A) @ b
     assert np.abs(x - want).max() < 1e-11 * np.abs(want).max() and abs(x.mean()) < 1e-14
-    assert np.abs(solve_host2(sub2, b + 1e-3) - want).max() < 1e-11 * np.abs(want).max()
+    assert np.abs(solve_host_levels(levels, b + 1e-3, sparse_sep=False) - want).max() < 1e-11 * np.abs(want).max()
     # the packed form of the second level works on the first level's separator vector
     pk = pack_for_device(q)
     r = np.random.default_rng(4).standard_normal(o.n_sep)
@@ -1163,7 +1163,7 @@ def test_two_level_substructured_solve_on_the_host():
     assert np.abs(w - np.concatenate([y, rT, gd])).max() < 1e-12 * np.abs(w).max()
     assert pack_for_device(o)["schur"] is None
     # the sparse form of the separator right-hand sides: r_S = b_S - A_SI y_I, no -E^T rows on the way down
-    assert np.abs(solve_host2(sub2, b, sparse_sep=True) - want).max() < 1e-11 * np.abs(want).max()
+    assert np.abs(solve_host_levels(levels, b, sparse_sep=True) - want).max() < 1e-11 * np.abs(want).max()
     assert o.coupling.shape == (o.n_sep, o.n_interior) and q.coupling.shape == (q.n_sep, q.n_interior)
     pks = pack_for_device(q, sparse_sep=True)
     assert np.all(np.diff(pks["seg_ptr"])[q.n_interior:q.n_interior + q.n_sep] == 1)  # the identity segment alone
@@ -1201,6 +1201,210 @@ def test_three_level_substructured_solve_on_the_host():
         assert np.abs(x - want).max() < 1e-11 * np.abs(want).max() and abs(x.mean()) < 1e-14
     pk = pack_for_device(levels[2], True)
     assert pk["schur"].shape == (levels[2].n_sep, levels[2].n_sep) and pack_for_device(levels[1], True)["schur"] is None
+
+
+# the product's limits and block sizes (hipcore.py; the TDGL_*_SITES environment variables' defaults) ...
+_MU_PRODUCT = dict(DENSE_MAX_SITES=5000, SUB_MAX_SITES=32000, SUB_BLOCK=0, SUB2_MAX_SITES=400_000, SUB2_BLOCK=0, SUB2_SUPER=0,
+                   SUB2_SPARSE_SEP_MIN_SITES=200_000, SUB3_MIN_SITES=350_000, SUB3_BIG=32768, PD_MAX_SITES=1_300_000,
+                   PD_BLOCKS=(144, 3072, 24576), DIRECT_SWITCH_MIN_SITES=150_000, AMG_CANDIDATES=3, AMG_CANDIDATES_MIN_SITES=100_000)
+# ... and what the fixtures of tests/conftest.py put on top of them (they stack)
+_MU_SUITE = dict(DENSE_MAX_SITES=0, SUB_MAX_SITES=0, SUB2_MAX_SITES=0)
+_MU_TWO = dict(_MU_SUITE, DENSE_MAX_SITES=199, SUB_MAX_SITES=199, SUB2_MAX_SITES=10 ** 9, SUB2_BLOCK=60, SUB2_SUPER=500, SUB3_MIN_SITES=10 ** 9)
+_MU_THREE = dict(_MU_TWO, SUB3_MIN_SITES=200, SUB3_BIG=3000)
+_MU_SETTINGS = dict(
+    product={}, suite_default=_MU_SUITE, substructured_solve=dict(_MU_SUITE, DENSE_MAX_SITES=199, SUB_MAX_SITES=10 ** 9, SUB_BLOCK=150),
+    two_level_solve=_MU_TWO, three_level_solve=_MU_THREE, precond_direct_solve=dict(_MU_THREE, SUB2_MAX_SITES=199, PD_MAX_SITES=10 ** 9))
+# (n, form, levels, blocks, sparse_sep, switching, amg_candidates): tabulated from the conditions of the constructor and of
+# `build_poisson` as they stood BEFORE there was a plan (the chain of elifs over the limits and the block-size expressions,
+# copied out as a function of n and the settings), not from `mu_plan`
+_MU_TABLE = {
+    'product': [
+        (2, 'dense', 0, (), False, False, 1),
+        (5000, 'dense', 0, (), False, False, 1),
+        (5001, 'sub', 1, (192,), False, False, 1),
+        (8000, 'sub', 1, (192,), False, False, 1),
+        (8001, 'sub', 1, (320,), False, False, 1),
+        (32000, 'sub', 1, (320,), False, False, 1),
+        (32001, 'sub', 2, (128, 2048), False, False, 1),
+        (150000, 'sub', 2, (128, 2500), False, True, 1),
+        (199999, 'sub', 2, (128, 3333), False, True, 1),
+        (200000, 'sub', 2, (160, 3333), True, True, 1),
+        (349999, 'sub', 2, (160, 5833), True, True, 1),
+        (350000, 'sub', 3, (160, 4096, 32768), True, True, 1),
+        (400000, 'sub', 3, (160, 4096, 32768), True, True, 1),
+        (400001, 'precond', 3, (144, 3072, 24576), True, False, 1),
+        (1300000, 'precond', 3, (144, 3072, 24576), True, False, 1),
+        (1300001, 'amg', 0, (), False, False, 3),
+    ],
+    'suite_default': [
+        (2, 'amg', 0, (), False, False, 1),
+        (199, 'amg', 0, (), False, False, 1),
+        (200, 'amg', 0, (), False, False, 1),
+        (5000, 'amg', 0, (), False, False, 1),
+        (5001, 'amg', 0, (), False, False, 1),
+        (5791, 'amg', 0, (), False, False, 1),
+        (8000, 'amg', 0, (), False, False, 1),
+        (8001, 'amg', 0, (), False, False, 1),
+        (32000, 'amg', 0, (), False, False, 1),
+        (32001, 'amg', 0, (), False, False, 1),
+        (150000, 'amg', 0, (), False, False, 3),
+        (199999, 'amg', 0, (), False, False, 3),
+        (200000, 'amg', 0, (), False, False, 3),
+        (349999, 'amg', 0, (), False, False, 3),
+        (350000, 'amg', 0, (), False, False, 3),
+        (400000, 'amg', 0, (), False, False, 3),
+        (400001, 'amg', 0, (), False, False, 3),
+        (1300000, 'amg', 0, (), False, False, 3),
+        (1300001, 'amg', 0, (), False, False, 3),
+    ],
+    'substructured_solve': [
+        (2, 'dense', 0, (), False, False, 1),
+        (199, 'dense', 0, (), False, False, 1),
+        (200, 'sub', 1, (150,), False, False, 1),
+        (5000, 'sub', 1, (150,), False, False, 1),
+        (5001, 'sub', 1, (150,), False, False, 1),
+        (5791, 'sub', 1, (150,), False, False, 1),
+        (8000, 'sub', 1, (150,), False, False, 1),
+        (8001, 'sub', 1, (150,), False, False, 1),
+        (32000, 'sub', 1, (150,), False, False, 1),
+        (32001, 'sub', 1, (150,), False, False, 1),
+        (150000, 'sub', 1, (150,), False, True, 1),
+        (199999, 'sub', 1, (150,), False, True, 1),
+        (200000, 'sub', 1, (150,), False, True, 1),
+        (349999, 'sub', 1, (150,), False, True, 1),
+        (350000, 'sub', 1, (150,), False, True, 1),
+        (400000, 'sub', 1, (150,), False, True, 1),
+        (400001, 'sub', 1, (150,), False, True, 1),
+        (1300000, 'sub', 1, (150,), False, True, 1),
+        (1300001, 'sub', 1, (150,), False, True, 1),
+    ],
+    'two_level_solve': [
+        (2, 'dense', 0, (), False, False, 1),
+        (199, 'dense', 0, (), False, False, 1),
+        (200, 'sub', 2, (60, 500), False, False, 1),
+        (5000, 'sub', 2, (60, 500), False, False, 1),
+        (5001, 'sub', 2, (60, 500), False, False, 1),
+        (5791, 'sub', 2, (60, 500), False, False, 1),
+        (8000, 'sub', 2, (60, 500), False, False, 1),
+        (8001, 'sub', 2, (60, 500), False, False, 1),
+        (32000, 'sub', 2, (60, 500), False, False, 1),
+        (32001, 'sub', 2, (60, 500), False, False, 1),
+        (150000, 'sub', 2, (60, 500), False, True, 1),
+        (199999, 'sub', 2, (60, 500), False, True, 1),
+        (200000, 'sub', 2, (60, 500), True, True, 1),
+        (349999, 'sub', 2, (60, 500), True, True, 1),
+        (350000, 'sub', 2, (60, 500), True, True, 1),
+        (400000, 'sub', 2, (60, 500), True, True, 1),
+        (400001, 'sub', 2, (60, 500), True, True, 1),
+        (1300000, 'sub', 2, (60, 500), True, True, 1),
+        (1300001, 'sub', 2, (60, 500), True, True, 1),
+    ],
+    'three_level_solve': [
+        (2, 'dense', 0, (), False, False, 1),
+        (199, 'dense', 0, (), False, False, 1),
+        (200, 'sub', 3, (60, 500, 3000), True, False, 1),
+        (5000, 'sub', 3, (60, 500, 3000), True, False, 1),
+        (5001, 'sub', 3, (60, 500, 3000), True, False, 1),
+        (5791, 'sub', 3, (60, 500, 3000), True, False, 1),
+        (8000, 'sub', 3, (60, 500, 3000), True, False, 1),
+        (8001, 'sub', 3, (60, 500, 3000), True, False, 1),
+        (32000, 'sub', 3, (60, 500, 3000), True, False, 1),
+        (32001, 'sub', 3, (60, 500, 3000), True, False, 1),
+        (150000, 'sub', 3, (60, 500, 3000), True, True, 1),
+        (199999, 'sub', 3, (60, 500, 3000), True, True, 1),
+        (200000, 'sub', 3, (60, 500, 3000), True, True, 1),
+        (349999, 'sub', 3, (60, 500, 3000), True, True, 1),
+        (350000, 'sub', 3, (60, 500, 3000), True, True, 1),
+        (400000, 'sub', 3, (60, 500, 3000), True, True, 1),
+        (400001, 'sub', 3, (60, 500, 3000), True, True, 1),
+        (1300000, 'sub', 3, (60, 500, 3000), True, True, 1),
+        (1300001, 'sub', 3, (60, 500, 3000), True, True, 1),
+    ],
+    'precond_direct_solve': [
+        (2, 'dense', 0, (), False, False, 1),
+        (199, 'dense', 0, (), False, False, 1),
+        (200, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (5000, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (5001, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (5791, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (8000, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (8001, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (32000, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (32001, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (150000, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (199999, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (200000, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (349999, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (350000, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (400000, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (400001, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (1300000, 'precond', 3, (60, 500, 3000), True, False, 1),
+        (1300001, 'precond', 3, (60, 500, 3000), True, False, 1),
+    ],
+}
+# at the product's settings: (n, arguments, form, levels, blocks, sparse_sep, switching, amg_candidates)
+_MU_ARGUMENTS = [
+        (3000, {'direct_solve': False}, 'amg', 0, (), False, False, 1),
+        (3000, {'n_owned': 1500}, 'amg', 0, (), False, False, 1),
+        (3000, {'n_owned': 3000}, 'dense', 0, (), False, False, 1),
+        (3000, {'substructure_levels': 1}, 'sub', 1, (192,), False, False, 1),
+        (3000, {'substructure_levels': 2}, 'sub', 2, (128, 2048), False, False, 1),
+        (3000, {'dense_max_sites': 12000}, 'dense', 0, (), False, False, 1),
+        (3000, {'dense_max_sites': 0}, 'amg', 0, (), False, False, 1),
+        (20000, {'direct_solve': False}, 'amg', 0, (), False, False, 1),
+        (20000, {'n_owned': 10000}, 'amg', 0, (), False, False, 1),
+        (20000, {'n_owned': 20000}, 'amg', 0, (), False, False, 1),
+        (20000, {'substructure_levels': 1}, 'sub', 1, (320,), False, False, 1),
+        (20000, {'substructure_levels': 2}, 'sub', 2, (128, 2048), False, False, 1),
+        (20000, {'dense_max_sites': 12000}, 'amg', 0, (), False, False, 1),
+        (20000, {'dense_max_sites': 0}, 'amg', 0, (), False, False, 1),
+        (120000, {'direct_solve': False}, 'amg', 0, (), False, False, 3),
+        (120000, {'n_owned': 60000}, 'amg', 0, (), False, False, 1),
+        (120000, {'n_owned': 120000}, 'amg', 0, (), False, False, 3),
+        (120000, {'substructure_levels': 1}, 'sub', 1, (507,), False, False, 1),
+        (120000, {'substructure_levels': 2}, 'sub', 2, (128, 2048), False, False, 1),
+        (120000, {'dense_max_sites': 12000}, 'amg', 0, (), False, False, 3),
+        (120000, {'dense_max_sites': 0}, 'amg', 0, (), False, False, 3),
+        (250000, {'direct_solve': False}, 'amg', 0, (), False, False, 3),
+        (250000, {'n_owned': 125000}, 'amg', 0, (), False, False, 1),
+        (250000, {'n_owned': 250000}, 'amg', 0, (), False, False, 3),
+        (250000, {'substructure_levels': 1}, 'sub', 1, (828,), False, True, 1),
+        (250000, {'substructure_levels': 2}, 'sub', 2, (160, 4166), True, True, 1),
+        (250000, {'dense_max_sites': 12000}, 'amg', 0, (), False, False, 3),
+        (250000, {'dense_max_sites': 0}, 'amg', 0, (), False, False, 3),
+]
+
+
+def test_mu_plan_reproduces_the_choice_of_solver_by_size_and_settings(direct_solve, monkeypatch):
+    """`TDGLContext.mu_plan` -- the one place that decides the mu solver, read by the constructor (site order) and by
+    `build_poisson` (what to build, how many AMG candidates) -- against a table of what the earlier conditions chose: at the
+    product's limits on both sides of every threshold, under each setting the fixtures of conftest.py apply, without a
+    direct solve, for a rank of a decomposed mesh, with `substructure_levels` and with a dense limit handed to
+    `build_poisson`.  Every attribute the plan reads is set here (the class may hold anything a session fixture left)."""
+    from tdgl_amd.hipcore import MuPlan, TDGLContext
+
+    for name, settings in _MU_SETTINGS.items():
+        for key, value in dict(_MU_PRODUCT, **settings).items():
+            monkeypatch.setattr(TDGLContext, key, value)
+        for n, *want in _MU_TABLE[name]:
+            assert TDGLContext.mu_plan(n) == MuPlan(*want), (name, n)
+    for key, value in _MU_PRODUCT.items():
+        monkeypatch.setattr(TDGLContext, key, value)
+    for n, kw, *want in _MU_ARGUMENTS:
+        assert TDGLContext.mu_plan(n, **kw) == MuPlan(*want), (n, kw)
+    # the caller's own site order: nothing that needs a dissection, the dense inverse stays
+    assert TDGLContext.mu_plan(3000, reordered=False).form == "dense" and TDGLContext.mu_plan(20000, reordered=False).form == "amg"
+    assert TDGLContext.mu_plan(20000, substructure_levels=2, reordered=False).form == "amg"
+    for kw in (dict(substructure_levels=3), dict(substructure_levels=0), dict(substructure_levels=2, direct_solve=False)):
+        with pytest.raises(ValueError, match="substructure_levels must be 1 or 2 with a direct solve"):
+            TDGLContext.mu_plan(20000, **kw)
+    # SUB_MAX_SITES = 0 switches the one-, two- and three-level solves and the preconditioner off, not the dense inverse
+    monkeypatch.setattr(TDGLContext, "SUB_MAX_SITES", 0)
+    assert [TDGLContext.mu_plan(n).form for n in (5000, 5001, 60000, 380000, 1000000)] == ["dense"] + 4 * ["amg"]
+    # the preconditioner's third block size follows SUB3_BIG once that leaves its default
+    monkeypatch.setattr(TDGLContext, "SUB_MAX_SITES", 32000)
+    monkeypatch.setattr(TDGLContext, "SUB3_BIG", 20000)
+    assert TDGLContext.mu_plan(1000000).blocks == (144, 3072, 20000)
 
 
 # ---------------------------------------------------------------- native mesh set-up (include/tdgl_host_mesh.h)
