@@ -59,9 +59,10 @@ extern "C" int tdgl_get_guess_stats(tdgl_ctx *ctx, int32_t *vectors, double *ini
 
 extern "C" int tdgl_get_guess_gram(tdgl_ctx *ctx, int32_t *k, double *G_rowmajor) {
     if (!ctx || !k || !G_rowmajor) return TDGL_ERR_ARG;
-    *k = ctx->g_count;
-    for (int i = 0; i < ctx->g_count; ++i)
-        for (int j = 0; j < ctx->g_count; ++j) G_rowmajor[i * ctx->g_count + j] = ctx->g_G[i][j][0] + ctx->g_G[i][j][1];
+    const GuessBasis &g = ctx->guess;
+    *k = g.count;
+    for (int i = 0; i < g.count; ++i)
+        for (int j = 0; j < g.count; ++j) G_rowmajor[i * g.count + j] = g.G[i][j][0] + g.G[i][j][1];
     return TDGL_OK;
 }
 
@@ -174,8 +175,7 @@ extern "C" int tdgl_poisson_set_hierarchy(tdgl_ctx *ctx, const tdgl_amg_level *l
     HIP_TRY(ctx, ctx->part_pq.alloc(NB));
     HIP_TRY(ctx, ctx->part_tmp.alloc(NB));
     ctx->prev_dt = ctx->prev_dt2 = 0.0;
-    ctx->g_count = 0;  // the projection basis belongs to the previous operator
-    ctx->g_row_pending = false;
+    ctx->guess.reset();  // the projection basis belongs to the previous operator
     return TDGL_OK;
 }
 
@@ -1027,183 +1027,6 @@ static void vcycle(tdgl_ctx *ctx, const double *b0, double **result) {
     if (result) *result = z;
 }
 
-static int fetch_scalars(tdgl_ctx *ctx, bool guess_start = false, const double *rr_part = nullptr) {
-    publish_status(ctx, guess_start, rr_part);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status, ctx->d_status.p, sizeof(StepStatus), hipMemcpyDeviceToHost, ctx->stream));
-    const int64_t t0 = now_ns();
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    ctx->stat_wait_ns += now_ns() - t0;
-    ctx->stat_host_syncs += 1;
-    HIP_TRY(ctx, e);
-    return TDGL_OK;
-}
-
-// ---- projection guess (popt.extrapolate == 3; kernels.inc "initial guess by projection") ----------
-constexpr int GUESS_DEFAULT = 12;  // window of the projection guess when the options say 0
-static inline int guess_window(const tdgl_ctx *ctx) {
-    return std::min(GK, std::max(1, ctx->popt.guess_window > 0 ? ctx->popt.guess_window : GUESS_DEFAULT));
-}
-
-// Relative pivot below which a window vector counts as dependent on the newer ones (solve_gram_dd).  The
-// Gram entries are double-double sums of stored fp64 vectors (~1e-30 relative); what limits the usable
-// depth is how well y_j = b_j - r_j represents A x_j: the CG's recurrence residual follows the true one to
-// ~1e-13 ||b||, i.e. components below 1e-13 of a vector are not images of the x_j any more: cut = 1e-24.
-// One process per GPU: up to 16 ranks gather each other's totals exactly (k_guess_rank_totals); beyond, hi and
-// lo parts are all-reduced separately and the sums are fp64-accurate only.
-static inline double guess_cut(const tdgl_ctx *ctx) {
-    return (distributed(ctx) && !guess_rank_totals(ctx)) ? 1e-13 : 1e-24;
-}
-
-static int ensure_guess_buffers(tdgl_ctx *ctx) {
-    const int gw = guess_window(ctx);
-    for (int j = 0; j < gw; ++j) {
-        if (ctx->g_x[j].n == 0) HIP_TRY(ctx, ctx->g_x[j].alloc(ctx->n_pad));
-        if (ctx->g_y[j].n == 0) HIP_TRY(ctx, ctx->g_y[j].alloc(ctx->n_pad));
-    }
-    if (ctx->part_gdot.n == 0) {
-        HIP_TRY(ctx, ctx->part_gdot.alloc(2 * G_ARRAYS * NB));
-        HIP_TRY(ctx, ctx->d_gdot.alloc(2 * G_ARRAYS));
-        HIP_TRY(ctx, ctx->part_gdot_rank.alloc(2 * G_ARRAYS * G_RANK_STRIDE));  // (zeroed; a rank only ever writes its own position)
-    }
-    if (ctx->g_count > gw) {  // the window shrank: keep the newest
-        const int drop = ctx->g_count - gw;
-        for (int i = 0; i + drop < ctx->g_count; ++i) {
-            ctx->g_slot[i] = ctx->g_slot[i + drop];
-            for (int j = 0; j + drop < ctx->g_count; ++j)
-                for (int h = 0; h < 2; ++h) ctx->g_G[i][j][h] = ctx->g_G[i + drop][j + drop][h];
-        }
-        ctx->g_count = gw;
-    }
-    return TDGL_OK;
-}
-
-// ---- host double-double arithmetic for the K x K system of the projection guess -------------------
-// (hi, lo) pairs with |lo| <= ulp(hi) / 2, ~32 significant digits.  Compiled without -ffast-math; the
-// error-free transformations below rely on IEEE semantics (std::fma = one rounding).  None of them has a
-// product feeding a sum it must not be fused with (the two-sums are additions only), so the host
-// compiler's contraction default is harmless here -- unlike in the device versions (kernels.inc).
-struct DD {
-    double hi, lo;
-};
-static inline DD dd_make(double a, double b = 0.0) {
-    const double s = a + b;
-    return DD{s, b - (s - a)};
-}
-static inline DD dd_two_sum(double a, double b) {
-    const double s = a + b, v = s - a;
-    return DD{s, (a - (s - v)) + (b - v)};
-}
-static inline DD dd_add(DD a, DD b) {
-    DD s = dd_two_sum(a.hi, b.hi);
-    const DD t = dd_two_sum(a.lo, b.lo);
-    s.lo += t.hi;
-    s = dd_make(s.hi, s.lo);
-    s.lo += t.lo;
-    return dd_make(s.hi, s.lo);
-}
-static inline DD dd_neg(DD a) { return DD{-a.hi, -a.lo}; }
-static inline DD dd_sub(DD a, DD b) { return dd_add(a, dd_neg(b)); }
-static inline DD dd_mul(DD a, DD b) {
-    const double p = a.hi * b.hi;
-    const double e = std::fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi);
-    return dd_make(p, e);
-}
-// v - a b with one renormalisation (the inner loop of the factorisation: ~16 flops instead of ~45 for
-// dd_sub(v, dd_mul(a, b)); relative error ~1e-31)
-static inline DD dd_fms(DD v, DD a, DD b) {
-    const double p = a.hi * b.hi;
-    const double e = std::fma(a.hi, b.hi, -p) + (a.hi * b.lo + a.lo * b.hi);
-    const double s = v.hi - p;
-    const double w = s - v.hi;
-    const double err = (v.hi - (s - w)) + (-p - w);
-    const double l = (v.lo - e) + err;
-    const double hi = s + l;
-    return DD{hi, l - (hi - s)};
-}
-static inline DD dd_div(DD a, DD b) {
-    const double q1 = a.hi / b.hi;
-    DD r = dd_sub(a, dd_mul(b, DD{q1, 0.0}));
-    const double q2 = r.hi / b.hi;
-    r = dd_sub(r, dd_mul(b, DD{q2, 0.0}));
-    const double q3 = r.hi / b.hi;
-    return dd_add(dd_make(q1, q2), DD{q3, 0.0});
-}
-
-// c = argmin || b - Y c ||_2 from the Gram matrix G = Y^T Y and g = Y^T b (double-double, window order:
-// oldest first).  L D L^T WITHOUT pivoting, taken from the NEWEST vector to the oldest; a vector whose
-// pivot falls below `cut` times its own squared norm -- it lies in the span of the newer ones to within
-// sqrt(cut) -- is left out (c_j = 0).  Returns the number of vectors used, or -1 when the matrix is
-// unusable (non-positive diagonal, non-finite entries).
-static int solve_gram_dd(int k, const double G[GK][GK][2], const double g[GK][2], double cut, double *c) {
-    DD L[GK][GK], d[GK], z[GK];
-    int used[GK], nu = 0;
-    for (int j = 0; j < k; ++j) {
-        c[j] = 0.0;
-        if (!(G[j][j][0] > 0.0) || !std::isfinite(G[j][j][0]) || !std::isfinite(g[j][0])) return -1;
-    }
-    // order: position q in the factorisation <-> window index idx(q) = k - 1 - q
-    for (int q = 0; q < k; ++q) {
-        const int j = k - 1 - q;
-        // row of L against the vectors already taken
-        DD piv = DD{G[j][j][0], G[j][j][1]};
-        DD row[GK], rowd[GK];  // rowd[t] = row[t] d[t] (the un-normalised entry: no division needed to get it)
-        for (int a = 0; a < nu; ++a) {
-            const int ja = used[a];
-            DD v = DD{G[j][ja][0], G[j][ja][1]};
-            for (int t = 0; t < a; ++t) v = dd_fms(v, rowd[t], L[a][t]);
-            if (!std::isfinite(v.hi)) return -1;
-            rowd[a] = v;
-            row[a] = dd_div(v, d[a]);
-            piv = dd_fms(piv, row[a], v);
-        }
-        if (!(piv.hi > cut * G[j][j][0])) continue;  // numerically dependent on the newer vectors
-        for (int a = 0; a < nu; ++a) L[nu][a] = row[a];
-        d[nu] = piv;
-        used[nu++] = j;
-    }
-    if (nu == 0) return 0;
-    // forward substitution L z = g, z /= d, back substitution L^T c = z
-    for (int a = 0; a < nu; ++a) {
-        DD v = DD{g[used[a]][0], g[used[a]][1]};
-        for (int t = 0; t < a; ++t) v = dd_fms(v, L[a][t], z[t]);
-        z[a] = v;
-    }
-    for (int a = 0; a < nu; ++a) z[a] = dd_div(z[a], d[a]);
-    for (int a = nu - 1; a >= 0; --a) {
-        DD v = z[a];
-        for (int t = a + 1; t < nu; ++t) v = dd_fms(v, L[t][a], z[t]);
-        z[a] = v;
-        c[used[a]] = v.hi;
-    }
-    for (int j = 0; j < k; ++j)
-        if (!std::isfinite(c[j])) return -1;
-    return nu;
-}
-
-// host-only: the K x K solve behind the projection guess, exported for the CPU tests.  G and g as
-// (hi, lo) pairs, row-major [k][k][2] / [k][2]; *used receives the number of vectors kept.
-extern "C" int tdgl_host_solve_gram(int32_t k, const double *G_pairs, const double *g_pairs, double cut, double *c,
-                                    int32_t *used) {
-    if (k < 1 || k > GK || !G_pairs || !g_pairs || !c) return TDGL_ERR_ARG;
-    double G[GK][GK][2], g[GK][2];
-    for (int i = 0; i < k; ++i) {
-        for (int j = 0; j < k; ++j) {
-            G[i][j][0] = G_pairs[(i * k + j) * 2];
-            G[i][j][1] = G_pairs[(i * k + j) * 2 + 1];
-        }
-        g[i][0] = g_pairs[2 * i];
-        g[i][1] = g_pairs[2 * i + 1];
-    }
-    const int nu = solve_gram_dd(k, G, g, cut, c);
-    if (used) *used = nu;
-    return nu >= 0 ? TDGL_OK : TDGL_ERR_ARG;
-}
-
-// Solve A x = b (b = ctx->bvec, x = ctx->mu holds the initial guess).  `after_first_sync` is
-// called after the first host synchronisation with the status block filled; it returns false
-// to abandon the solve (the step driver retries a failed psi update without finishing a solve
-// whose right-hand side is garbage).
-//
 // where the factors live, by storage type (fp64: the direct SOLVE; fp32: the preconditioner, DirectFactors::fp32)
 template <class VT> struct SubPools;
 template <> struct SubPools<double> {
@@ -1425,416 +1248,265 @@ extern "C" int tdgl_set_direct_guard(tdgl_ctx *ctx, double limit) {
     return TDGL_OK;
 }
 
-// Host synchronisation: once before the iterations, then -- with check_every = 0 (auto) --
-// after `last_pcg_iters` iterations (the count is stable from step to step; an update that finds
-// the residual already converged freezes itself, k_update_xr) and after every
-// iteration from there on; with check_every = k > 0, after every k iterations.
-template <class F>
-static int pcg_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool allow_projection = false) {
-    if (ctx->levels.empty()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "no AMG hierarchy: call tdgl_poisson_set_hierarchy");
-    TDGL_TRY(comm_ready(ctx));
-    AmgLevel &L0 = *ctx->levels[0];
-    // all pointwise work is on the owned rows; sums are over ranks (comm_allreduce is a no-op
-    // on one GPU); the ghost entries of x / p are refreshed before the operator reads them
-    const int64_t no = ctx->n_own;
-    const double inv_n = 1.0 / (double)ctx->n_global;
-    const int gv = vec_grid(no);
-    double *b = ctx->bvec.p, *x = ctx->mu.p, *r = ctx->pcg_r.p, *p = ctx->pcg_p.p, *q = ctx->pcg_q.p;
-    if (abandoned) *abandoned = false;
+// The host's look at the stream: the status block travels to the host, which waits for it (stat_wait_ns,
+// stat_host_syncs).  guard: the scalars of the direct solve's residual check ride behind the status block.
+static int sync_status(tdgl_ctx *ctx, bool guard = false) {
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status, ctx->d_status.p, sizeof(StepStatus), hipMemcpyDeviceToHost, ctx->stream));
+    if (guard) direct_guard_fetch(ctx);
+    const int64_t t0 = now_ns();
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    ctx->stat_wait_ns += now_ns() - t0;
+    ctx->stat_host_syncs += 1;
+    HIP_TRY(ctx, e);
+    return TDGL_OK;
+}
 
-    if (dense_on(ctx)) {
-        // mu = G b in one launch (tdgl_poisson_set_dense_inverse).  In the time loop the kernel itself
-        // holds the result back when the psi update of this step failed, the step driver's edge
-        // currents follow at once, and the step's only synchronisation comes after them.
-        const bool in_step = allow_projection && ctx->psi_status_pending;
-        if (!in_step) {  // one-off solve: b orthogonal to the constants, so that the residual below means something
-            hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, b, (const double *)nullptr, ctx->part_tmp.p);
-            hipLaunchKernelGGL(k_shift_mean, dim3(gv), dim3(BLOCK), 0, ctx->stream, no, ctx->part_tmp.p, inv_n, b);
-        }
-        const bool status_done = direct_solve_launch(ctx, b, x, in_step, nullptr, nullptr);
-        ctx->spec_currents_done = false;
-        if (in_step && ctx->spec_currents) {
-            launch_edge_currents(ctx, ctx->psi[1 - ctx->cur].p, x, ctx->js.p, ctx->jn.p);
-            ctx->spec_currents_done = true;
-        }
-        const double *rr_part = nullptr;
-        if (!in_step) {  // the true residual, for the caller of tdgl_poisson_solve
-            hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, b, b, ctx->part_pq.p);
-            hipLaunchKernelGGL(k_store_sum, dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->part_pq.p, ctx->scal.p, (int)S_BB,
-                               ctx->popt.rtol * ctx->popt.rtol);
-            launch_sell<RESID, DOT_YY>(ctx, L0.A, x, b, nullptr, 0.0, 0.0, nullptr, r, ctx->part_pair[0].p + NB);
-            rr_part = ctx->part_pair[0].p + NB;
-        }
-        bool guard = false;
-        if (in_step && status_done && --ctx->direct_guard_countdown <= 0) {
-            ctx->direct_guard_countdown = DIRECT_GUARD_EVERY;
-            guard = true;
-            direct_guard_launch(ctx);
-        }
-        if (status_done) {  // published by k_dense_sym_finish: only the copy and the step's one synchronisation are left
-            ctx->psi_status_pending = false;
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status, ctx->d_status.p, sizeof(StepStatus), hipMemcpyDeviceToHost, ctx->stream));
-            if (guard) direct_guard_fetch(ctx);
-            const int64_t t0 = now_ns();
-            const hipError_t e = hipStreamSynchronize(ctx->stream);
-            ctx->stat_wait_ns += now_ns() - t0;
-            ctx->stat_host_syncs += 1;
-            HIP_TRY(ctx, e);
-        } else {
-            TDGL_TRY(fetch_scalars(ctx, false, rr_part));
-        }
-        if (!after_first_sync(ctx->h_status)) {
-            if (abandoned) *abandoned = true;
-            return TDGL_OK;
-        }
-        ctx->last_pcg_iters = 0;
-        ctx->last_guess_vectors = 0;
-        if (guard) direct_guard_read(ctx, true);  // (the psi update succeeded: mu = G b was written)
-        const double bb = ctx->h_status->scal[S_BB];
-        ctx->last_relres = (!in_step && bb > 0.0) ? std::sqrt(ctx->h_status->scal[S_RR] / bb) : 0.0;
-        ctx->last_guess_relres = ctx->last_relres;
-        HIP_TRY(ctx, hipGetLastError());
-        return TDGL_OK;
-    }
-    bool f32 = precond_f32_on(ctx);
-    if (ctx->deep && !distributed(ctx))
-        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "a deep halo plan is set but no transport: call tdgl_comm_init_ipc / _rccl / _callbacks");
-    if (ctx->deep && !f32)
-        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "two distributed levels need the fp32-stored V-cycle with degree-1 smoothing on"
-                  " level 0 and the fused restriction (the default options)");
-    if (f32) TDGL_TRY(ensure_f32(ctx));
-    // Flexible (Polak-Ribiere) beta (tdgl_poisson_options.flexible_cg, off by default -- measured no
-    // better than Fletcher-Reeves, see the header) on the path whose preconditioner is not exactly
-    // symmetric: the single-GPU recurrence with the fp32 / binary16-stored V-cycle.  The smoothing step that produces
-    // z_new also forms z_new . q_old (q still holds A p of the previous iteration); the direction
-    // update turns it into beta = -alpha (z_new . q_old) / (r.z)_old.
-    const bool flex_opt = ctx->popt.flexible_cg != 0 && !distributed(ctx);
-    // Initial guess by projection onto the previous solutions: their dot products with the new
-    // right-hand side, b.b and sum b go to the host with the status block; x0 and r0 follow the sync.
-    const bool proj = allow_projection && ctx->popt.extrapolate >= 3;
-    // make b orthogonal to the null space (constants); ||b||^2; r = b - A x; ||r||^2
-    // (projection guess: the mean is removed arithmetically, see k_multi_dot)
-    if (!proj) {
+static int fetch_scalars(tdgl_ctx *ctx, bool guess_start = false, const double *rr_part = nullptr) {
+    publish_status(ctx, guess_start, rr_part);
+    return sync_status(ctx);
+}
+
+// mu = G b in one launch sequence (tdgl_poisson_set_dense_inverse / _substructure).  In the time loop (in_step) the
+// kernels themselves hold the result back when the psi update of this step failed, the step driver's edge currents
+// follow at once, and the step's only synchronisation comes after them.  after_first_sync / abandoned: see pcg_solve.
+template <class F>
+static int direct_mu_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool in_step) {
+    const int64_t no = ctx->n_own;
+    double *b = ctx->bvec.p, *x = ctx->mu.p;
+    if (!in_step) {  // one-off solve: b orthogonal to the constants, so that the residual below means something
         hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, b, (const double *)nullptr, ctx->part_tmp.p);
-        TDGL_TRY(comm_allreduce(ctx, ctx->part_tmp.p, NB, 0));
-        hipLaunchKernelGGL(k_shift_mean, dim3(gv), dim3(BLOCK), 0, ctx->stream, no, ctx->part_tmp.p, inv_n, b);
+        hipLaunchKernelGGL(k_shift_mean, dim3(vec_grid(no)), dim3(BLOCK), 0, ctx->stream, no, ctx->part_tmp.p, 1.0 / (double)ctx->n_global, b);
     }
-    // Partials live in two ping-pong buffers [r.z | ||r||^2]: iteration `it` reads r.z and the
-    // PREVIOUS residual from pair[it & 1] and writes the new residual into pair[(it + 1) & 1].
-    // Keeping both halves adjacent lets the distributed run sum them with ONE all-reduce.
-    double *part_rz[2] = {ctx->part_pair[0].p, ctx->part_pair[1].p};
-    double *part_rr[2] = {ctx->part_pair[0].p + NB, ctx->part_pair[1].p + NB};
-    bool rr_reduced = true;  // the residual partials the next iteration reads are already global
-    VecSet vs{};
-    if (proj) {
-        TDGL_TRY(ensure_guess_buffers(ctx));
-        vs.k = ctx->g_count;
-        for (int j = 0; j < ctx->g_count; ++j) vs.p[j] = ctx->g_y[ctx->g_slot[j]].p;
-        const int newest = ctx->g_row_pending ? ctx->g_count - 1 : -1;
-        const int gg = guess_grid(ctx);
-        if (vs.k <= 8)
-            hipLaunchKernelGGL((k_multi_dot<8>), dim3(gg), dim3(BLOCK), 0, ctx->stream, no, (const double *)b, vs, newest, ctx->part_gdot.p);
-        else if (vs.k <= 12)
-            hipLaunchKernelGGL((k_multi_dot<12>), dim3(gg), dim3(BLOCK), 0, ctx->stream, no, (const double *)b, vs, newest, ctx->part_gdot.p);
-        else
-            hipLaunchKernelGGL((k_multi_dot<GK>), dim3(gg), dim3(BLOCK), 0, ctx->stream, no, (const double *)b, vs, newest, ctx->part_gdot.p);
-        if (guess_rank_totals(ctx)) {  // every rank's double-double totals, gathered exactly (k_guess_rank_totals)
-            hipLaunchKernelGGL(k_guess_rank_totals, dim3(1), dim3(BLOCK), 0, ctx->stream, (const double *)ctx->part_gdot.p, gg, vs.k,
-                               ctx->part_gdot_rank.p, ctx->rank);
-            TDGL_TRY(comm_allreduce(ctx, ctx->part_gdot_rank.p, 2 * G_ARRAYS * G_RANK_STRIDE, 0));
-        } else if (distributed(ctx)) {  // (more ranks than that: hi and lo parts summed separately, fp64 accuracy, see guess_cut)
-            TDGL_TRY(comm_allreduce(ctx, ctx->part_gdot.p, 2 * (G_Y0 + vs.k) * NB, 0));
-            if (newest >= 0) TDGL_TRY(comm_allreduce(ctx, ctx->part_gdot.p + 2 * G_N0 * NB, 2 * vs.k * NB, 0));
-        }
-        // (the sums, S_BB / S_TOL2 and the counter reset happen in the status kernel below)
-    } else {
+    const bool status_done = direct_solve_launch(ctx, b, x, in_step, nullptr, nullptr);
+    ctx->spec_currents_done = false;
+    if (in_step && ctx->spec_currents) {
+        launch_edge_currents(ctx, ctx->psi[1 - ctx->cur].p, x, ctx->js.p, ctx->jn.p);
+        ctx->spec_currents_done = true;
+    }
+    const double *rr_part = nullptr;
+    if (!in_step) {  // the true residual, for the caller of tdgl_poisson_solve
         hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, b, b, ctx->part_pq.p);
-        launch_sell<RESID, DOT_YY>(ctx, L0.A, x, b, nullptr, 0.0, 0.0, nullptr, r, part_rr[0]);
-        TDGL_TRY(comm_allreduce(ctx, ctx->part_pq.p, NB, 0));
-        TDGL_TRY(comm_allreduce(ctx, part_rr[0], NB, 0));
         hipLaunchKernelGGL(k_store_sum, dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->part_pq.p, ctx->scal.p, (int)S_BB,
-                           ctx->popt.rtol * ctx->popt.rtol);  // also scal[S_TOL2]
-        hipLaunchKernelGGL(k_store_sum, dim3(1), dim3(BLOCK), 0, ctx->stream, part_rr[0], ctx->scal.p, (int)S_RR, 0.0);
+                           ctx->popt.rtol * ctx->popt.rtol);
+        launch_sell<RESID, DOT_YY>(ctx, ctx->levels[0]->A, x, b, nullptr, 0.0, 0.0, nullptr, ctx->pcg_r.p, ctx->part_pair[0].p + NB);
+        rr_part = ctx->part_pair[0].p + NB;
     }
-    if (!proj) {
-        static const double init[2] = {-1.0, 0.0};  // S_CONV_IT: "not converged yet"; S_IT: 0
-        static_assert(S_IT == S_CONV_IT + 1, "contiguous");
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->scal.p + S_CONV_IT, init, 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    bool guard = false;
+    if (in_step && status_done && --ctx->direct_guard_countdown <= 0) {
+        ctx->direct_guard_countdown = DIRECT_GUARD_EVERY;
+        guard = true;
+        direct_guard_launch(ctx);
     }
-    if (distributed(ctx)) {  // psi failure flag and max d|psi|^2: identical decisions on all ranks
-        hipLaunchKernelGGL(k_status_pack, dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->psi_dmax_part.p,
-                           ctx->psi_fail_part.p, ctx->psi_blocks, ctx->d_gstat.p);
-        TDGL_TRY(comm_allreduce(ctx, ctx->d_gstat.p, 2, 1));
-        hipLaunchKernelGGL(k_status_unpack, dim3(1), dim3(64), 0, ctx->stream, ctx->d_gstat.p, ctx->status_dev);
-        ctx->psi_status_pending = false;  // d_status now holds the all-reduced outcome
-    }
-    TDGL_TRY(fetch_scalars(ctx, proj));
-    // The Gram row of the window's newest vector arrived with this status block.  Taken BEFORE an abandoned
-    // solve returns: a second pcg_solve for the same step (after a psi retry) would compute it again, which
-    // is harmless, but a window change in between would not be.
-    if (proj && ctx->g_row_pending) {
-        const int kn = ctx->g_count - 1;
-        for (int j = 0; j < ctx->g_count; ++j)
-            for (int h = 0; h < 2; ++h)
-                ctx->g_G[kn][j][h] = ctx->g_G[j][kn][h] = ctx->h_status->gdot[2 * (G_N0 + j) + h];
-        ctx->g_row_pending = false;
+    if (status_done) {  // published by k_dense_sym_finish: only the copy and the step's one synchronisation are left
+        ctx->psi_status_pending = false;
+        TDGL_TRY(sync_status(ctx, guard));
+    } else {
+        TDGL_TRY(fetch_scalars(ctx, false, rr_part));
     }
     if (!after_first_sync(ctx->h_status)) {
         if (abandoned) *abandoned = true;
         return TDGL_OK;
     }
+    ctx->last_pcg_iters = 0;
+    ctx->last_guess_vectors = 0;
+    if (guard) direct_guard_read(ctx, true);  // (the psi update succeeded: mu = G b was written)
     const double bb = ctx->h_status->scal[S_BB];
-    double rr = proj ? INFINITY : ctx->h_status->scal[S_RR];
-    int it = 0;
-    const double b_mean = proj ? ctx->h_status->gdot[2 * G_SB] * inv_n : 0.0;  // still inside b
-    if (!(bb > 0.0)) {  // b = 0: the zero-mean solution is 0
-        HIP_TRY(ctx, hipMemsetAsync(x, 0, ctx->n_pad * sizeof(double), ctx->stream));
-        ctx->last_pcg_iters = 0;
-        ctx->last_relres = 0.0;
-        return TDGL_OK;
+    ctx->last_relres = (!in_step && bb > 0.0) ? std::sqrt(ctx->h_status->scal[S_RR] / bb) : 0.0;
+    ctx->last_guess_relres = ctx->last_relres;
+    HIP_TRY(ctx, hipGetLastError());
+    return TDGL_OK;
+}
+
+// ---- the preconditioned CG ---------------------------------------------------------------------------
+// Which preconditioner (meshes that carry the substructure factors as one, tdgl_poisson_set_substructure_precond):
+// the AMG V-cycle contracts the residual by ~0.3 per iteration at t_V per application, the fp32-stored factors by
+// ~1e-5 at t_D (5-6 x t_V at a million sites).  The cost of the rest of a solve from the squared residual rr, either
+// way: iterations needed x measured time per iteration.
+struct PrecondCost { double amg, pd; double n_amg; };  // predicted time with the V-cycle / the factors; the V-cycle's iterations
+static PrecondCost precond_cost(const tdgl_ctx *ctx, double rr, double tol2) {
+    const double decades = 0.5 * std::log10(rr / tol2);
+    const double n_amg = std::max(1.0, std::ceil(decades / ctx->pcg_rate - 0.25));
+    const double n_pd = std::max(1.0, std::ceil(decades / ctx->pd_rate - 0.05));
+    const double t_common = 0.55 * ctx->pd_t_vcycle_us;  // (A p + the two recurrences: measured 31 of 85 us at 1M sites)
+    return PrecondCost{n_amg * (ctx->pd_t_vcycle_us + t_common), n_pd * (ctx->pd_t_apply_us + t_common), n_amg};
+}
+
+// One CG run: what its iterations share.  A solve is one run, or several -- each starts over from the current iterate
+// (beta = 0) with another preconditioner, see next_phase and the hand-over in cg_iterate.
+struct CgRun {
+    tdgl_ctx *ctx;
+    double *b, *x, *r, *p, *q;
+    // Partials live in two ping-pong buffers [r.z | ||r||^2]: iteration `it` reads r.z and the
+    // PREVIOUS residual from pair[it & 1] and writes the new residual into pair[(it + 1) & 1].
+    // Keeping both halves adjacent lets the distributed run sum them with ONE all-reduce.
+    double *part_rz[2], *part_rr[2];
+    bool flex_opt;             // popt.flexible_cg on the path it applies to (pcg_solve)
+    bool use_pd;               // the factors precondition, else the V-cycle
+    bool f32, coarse32;        // the V-cycle's level 0 / its replicated levels run on the fp32-stored operators
+    int it0, budget;           // first iteration of the current run / its limit
+    int predicted;             // size of the run's first batch
+    bool rr_reduced = true;    // the residual partials the next iteration reads are already global
+    bool sum_x_fresh = false;  // part_tmp holds the partials of sum x (left by k_update_xr)
+    int pd_its = -1;           // iterations taken with the factors before a hand-over to the V-cycle (-1: none)
+    double pd_rr_end = 0.0;    // ... and the squared residual they left
+
+    bool f32i() const { return f32 && !use_pd; }   // (the factors deliver an fp64 z)
+    bool cg1() const { return f32i() && ctx->deep; }  // (two distributed levels: single-reduction CG on fp32 z, no exchange of z)
+    bool flex() const { return flex_opt && f32i(); }
+};
+
+// z = M^-1 r and the partials of r.z: into *z (fp64) or *z32 (fp32), whichever the preconditioner delivers
+static int cg_precondition(CgRun &run, int it, double **z, const float **z32) {
+    tdgl_ctx *ctx = run.ctx;
+    double *r = run.r, *rz_new = run.part_rz[it & 1];
+    if (run.use_pd) {
+        *z = ctx->direct->z.p;
+        // (profile mode: every application of the first 64 bracketed by an event pair -> tdgl_profile_read_direct)
+        hipEvent_t fa = nullptr, fb = nullptr;
+        if (ctx->profile && ctx->prof3_launches + (int64_t)ctx->prof3_pending.size() < 64) {
+            TDGL_TRY(profile_event(ctx, &fa));
+            TDGL_TRY(profile_event(ctx, &fb));
+            HIP_TRY(ctx, hipEventRecord(fa, ctx->stream));
+        }
+        TDGL_TRY(precond_factors_apply(ctx, r, *z, rz_new));
+        if (fa) {
+            HIP_TRY(ctx, hipEventRecord(fb, ctx->stream));
+            ctx->prof3_pending.emplace_back(fa, fb);
+        }
+    } else if (run.cg1()) {
+        *z32 = vcycle0_f32(ctx, r, rz_new, nullptr, nullptr, true);  // (z on the owned rows and the first ghost layer, fp32)
+    } else if (run.f32i() && distributed(ctx)) {
+        *z = ctx->levels[0]->xb.p;  // fp64 copy of z: its ghosts travel as doubles
+        (void)vcycle0_f32(ctx, r, rz_new, *z);
+    } else if (run.f32i()) {
+        *z32 = vcycle0_f32(ctx, r, rz_new, nullptr, run.flex() ? run.q : (const double *)nullptr);
+    } else {
+        vcycle_level(ctx, 0, r, z, rz_new, run.coarse32);
     }
-    ctx->mu_first_saved = false;
-    if (proj && ctx->g_count == 0) {  // no basis yet: keep mu^n so that a failed solve can be rolled back (run.inc)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->mu_prev.p, x, ctx->n_pad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        ctx->mu_first_saved = true;
-    }
-    if (proj) {
-        // x0 = X c with G c = X^T b (host, K x K); then r0 = b - A x0.  ||r0||^2 stays on the device:
-        // the first batch of iterations runs regardless (an update that finds the residual below
-        // the tolerance freezes itself), and the first update records it for the statistics.
-        for (int j = 0; j < ctx->g_count; ++j) {
-            ctx->g_rhs[j][0] = ctx->h_status->gdot[2 * (G_Y0 + j)];
-            ctx->g_rhs[j][1] = ctx->h_status->gdot[2 * (G_Y0 + j) + 1];
-        }
-        {  // ||b - mean||^2 = b.b - (sum b)^2 / n in double-double: the diagonal Gram entry if this solve joins the window
-            const DD sb = DD{ctx->h_status->gdot[2 * G_SB], ctx->h_status->gdot[2 * G_SB + 1]};
-            const DD q = dd_sub(DD{ctx->h_status->gdot[2 * G_BB], ctx->h_status->gdot[2 * G_BB + 1]},
-                                dd_div(dd_mul(sb, sb), DD{(double)ctx->n_global, 0.0}));
-            ctx->g_bb[0] = q.hi;
-            ctx->g_bb[1] = q.lo;
-        }
-        ctx->last_guess_vectors = 0;
-        int used = 0;
-        vs.k = ctx->g_count;
-        for (int j = 0; j < ctx->g_count; ++j) vs.p[j] = ctx->g_x[ctx->g_slot[j]].p;
-        if (ctx->g_count > 0 && (used = solve_gram_dd(ctx->g_count, ctx->g_G, ctx->g_rhs, guess_cut(ctx), vs.c)) > 0) {
-            if (vs.k <= 8)
-                hipLaunchKernelGGL((k_combine<8>), dim3(gv), dim3(BLOCK), 0, ctx->stream, no, vs, x);
-            else if (vs.k <= 12)
-                hipLaunchKernelGGL((k_combine<12>), dim3(gv), dim3(BLOCK), 0, ctx->stream, no, vs, x);
-            else
-                hipLaunchKernelGGL((k_combine<GK>), dim3(gv), dim3(BLOCK), 0, ctx->stream, no, vs, x);
-            TDGL_TRY(comm_halo(ctx, x, 1));
-            ctx->last_guess_vectors = used;
-        }
-        launch_sell<RESID, DOT_YY>(ctx, L0.A, x, b, nullptr, b_mean, 0.0, nullptr, r, part_rr[0]);
-        // (one process per GPU: ||r0||^2 is not summed over the ranks here -- nobody looks at it before the first
-        // iteration, whose one sum of [r.z | ||r||^2 | z.w] takes it along: two sums per step less)
-        if (distributed(ctx)) rr_reduced = false;
-    }
-    const double tol2 = ctx->popt.rtol * ctx->popt.rtol * bb;
-    // Size of the first batch.  Iterations queued beyond convergence freeze themselves but still cost their
-    // launches (84 us each at 1M sites); a batch that is too short costs one more look per missing iteration
-    // (~20 us).  The count of the previous solve is wrong in a third of the steps; the residual of the guess is a
-    // much better predictor, and the host already holds it: ||b - Y c||^2 = b.b - 2 c.g + c.G c from the Gram data
-    // (double-double: it is 8-17 decades below b.b), divided by the contraction per iteration observed so far.
-    int predicted = std::max(1, ctx->last_pcg_iters);
-    if (proj && ctx->pcg_predict_from_guess && ctx->popt.check_every <= 0) {
-        DD rr0 = DD{ctx->g_bb[0], ctx->g_bb[1]};
-        if (ctx->last_guess_vectors > 0) {
-            for (int i = 0; i < ctx->g_count; ++i) {
-                if (vs.c[i] == 0.0) continue;
-                DD row = dd_mul(DD{-2.0 * vs.c[i], 0.0}, DD{ctx->g_rhs[i][0], ctx->g_rhs[i][1]});
-                for (int j = 0; j < ctx->g_count; ++j)
-                    if (vs.c[j] != 0.0)
-                        row = dd_add(row, dd_mul(dd_mul(DD{vs.c[i], 0.0}, DD{vs.c[j], 0.0}), DD{ctx->g_G[i][j][0], ctx->g_G[i][j][1]}));
-                rr0 = dd_add(rr0, row);
-            }
-        }
-        const double est = rr0.hi;
-        if (est > tol2 && std::isfinite(est)) {
-            const double its = 0.5 * std::log10(est / tol2) / ctx->pcg_rate;
-            predicted = (int)std::ceil(its - 0.25);  // (an iteration too many costs four times an iteration too few)
-        } else {
-            predicted = 1;
-        }
-        predicted = std::max(1, std::min(predicted, ctx->popt.max_iter));
-    }
-    // Which preconditioner (meshes that carry the substructure factors as one, tdgl_poisson_set_substructure_precond):
-    // the AMG V-cycle contracts the residual by ~0.3 per iteration at t_V per application, the fp32-stored factors by
-    // ~1e-5 at t_D (5-6 x t_V at a million sites).  The decades to go are known before anything is queued -- the
-    // residual of the projection guess in double-double from the Gram data --, so the choice is the cheaper PREDICTED
-    // solve: iterations needed x measured time per iteration.  Stationary / smoothly evolving states (guess good to
-    // 1e-9: two or three V-cycles) stay with AMG; transients and the long-time regime (guess at 1e-4 .. 1e-6: 8-13
-    // V-cycles) take ONE application of the factors.
-    bool use_pd = false;
-    int pd_its = -1;          // iterations taken with the factors before a hand-over to the V-cycle (-1: none)
-    double pd_rr_end = 0.0;   // ... and the squared residual they left
-    if (precond_factors_available(ctx) && ctx->pd_choice != 2) {
-        double est = proj ? NAN : rr;
-        if (proj) {  // (the same figure the batch prediction above uses)
-            DD rr0 = DD{ctx->g_bb[0], ctx->g_bb[1]};
-            if (ctx->last_guess_vectors > 0)
-                for (int i = 0; i < ctx->g_count; ++i) {
-                    if (vs.c[i] == 0.0) continue;
-                    DD row = dd_mul(DD{-2.0 * vs.c[i], 0.0}, DD{ctx->g_rhs[i][0], ctx->g_rhs[i][1]});
-                    for (int j = 0; j < ctx->g_count; ++j)
-                        if (vs.c[j] != 0.0)
-                            row = dd_add(row, dd_mul(dd_mul(DD{vs.c[i], 0.0}, DD{vs.c[j], 0.0}), DD{ctx->g_G[i][j][0], ctx->g_G[i][j][1]}));
-                    rr0 = dd_add(rr0, row);
-                }
-            est = rr0.hi;
-        }
-        if (ctx->pd_choice == 1) {
-            use_pd = true;
-        } else if (std::isfinite(est) && est > tol2 && ctx->pd_t_apply_us > 0.0 && ctx->pd_t_vcycle_us > 0.0) {
-            const double decades = 0.5 * std::log10(est / tol2);
-            const double n_amg = std::max(1.0, std::ceil(decades / ctx->pcg_rate - 0.25));
-            const double n_pd = std::max(1.0, std::ceil(decades / ctx->pd_rate - 0.05));
-            const double t_common = 0.55 * ctx->pd_t_vcycle_us;  // (A p + the two recurrences: measured 31 of 85 us at 1M sites)
-            use_pd = n_pd * (ctx->pd_t_apply_us + t_common) < n_amg * (ctx->pd_t_vcycle_us + t_common);
-        }
-        if (use_pd) predicted = 1;  // (an application too many costs five V-cycles: look after every one)
-    }
-    ctx->pd_last = use_pd;
-    // (one-process-per-GPU mode runs level 0 in fp64 but shares the fp32-stored replicated levels)
-    bool coarse32 = ctx->popt.precond_fp32 != 0 && ctx->levels.size() > 2;
-    if (coarse32) TDGL_TRY(ensure_coarse_f32(ctx));
-    int it0 = 0, budget = ctx->popt.max_iter;  // first iteration of the current CG run / its limit
-    // one PCG iteration (all launches on ctx->stream; nothing in here depends on host values that
-    // change from iteration to iteration except the parity of `it` and "is this the first one")
-    // (single GPU: the update kernel also leaves the partials of sum x behind, so that the zero-mean gauge at the
-    // end needs no pass over x of its own; valid as soon as one update of this solve has run)
-    const bool sum_x_rides = !distributed(ctx);
-    bool sum_x_fresh = false;
-    auto iteration = [&](int it) -> int {
-        const bool f32i = f32 && !use_pd;  // (the factors deliver an fp64 z)
-        const bool flex = flex_opt && f32i;
-        double *z = nullptr;
-        const float *z32 = nullptr;
-        double *rz_new = part_rz[it & 1], *rz_old = part_rz[(it + 1) & 1];
-        const bool cg1 = f32i && ctx->deep;  // (two distributed levels: single-reduction CG on fp32 z, no exchange of z)
-        if (use_pd) {
-            z = ctx->direct->z.p;
-            // (profile mode: every application of the first 64 bracketed by an event pair -> tdgl_profile_read_direct)
-            hipEvent_t fa = nullptr, fb = nullptr;
-            if (ctx->profile && ctx->prof3_launches + (int64_t)ctx->prof3_pending.size() < 64) {
-                TDGL_TRY(profile_event(ctx, &fa));
-                TDGL_TRY(profile_event(ctx, &fb));
-                HIP_TRY(ctx, hipEventRecord(fa, ctx->stream));
-            }
-            TDGL_TRY(precond_factors_apply(ctx, r, z, rz_new));
-            if (fa) {
-                HIP_TRY(ctx, hipEventRecord(fb, ctx->stream));
-                ctx->prof3_pending.emplace_back(fa, fb);
-            }
-        } else if (cg1) {
-            z32 = vcycle0_f32(ctx, r, rz_new, nullptr, nullptr, true);  // (z on the owned rows and the first ghost layer, fp32)
-        } else if (f32i && distributed(ctx)) {
-            z = ctx->levels[0]->xb.p;  // fp64 copy of z: its ghosts travel as doubles
-            (void)vcycle0_f32(ctx, r, rz_new, z);
-        } else if (f32i) {
-            z32 = vcycle0_f32(ctx, r, rz_new, nullptr, flex ? q : (const double *)nullptr);
-        } else {
-            vcycle_level(ctx, 0, r, &z, rz_new, coarse32);
-        }
-        if (!distributed(ctx) && !cg1) {
-            // direction update fused into A p (double-buffered p)
-            double *p_old = p;
-            p = (p == ctx->pcg_p.p) ? ctx->pcg_p2.p : ctx->pcg_p.p;
-            int per_xcd, grid;
-            sell_fixed_grid(L0.A.pat.n_slices, &per_xcd, &grid);
-            const double *rz_prev = it == it0 ? (const double *)nullptr : (const double *)rz_old;
-            const SellPattern &pat = L0.A.pat;
+    return TDGL_OK;
+}
+
 #define TDGL_AXP(ZT, IT, COLS, Z)                                                                                 \
-hipLaunchKernelGGL((k_sell_axp<ZT, IT>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd,        \
-                   pat.n_rows, pat.slice_off.p, COLS, L0.A.vals.p, Z, (const double *)p_old,                   \
-                   (const double *)rz_new, rz_prev, p, q, ctx->part_pq.p,                                       \
-                   flex ? (const double *)(rz_new + 2 * NB) : (const double *)nullptr, (const double *)ctx->scal.p)
-            hipEvent_t pa = nullptr, pb = nullptr;
-            // (every 8th launch, at most 64 samples: event pairs on every launch would slow a short
-            // timed window down measurably)
-            const bool sample = ctx->profile && ctx->prof2_budget > 0 && (ctx->prof2_seen++ % 8) == 0;
-            if (sample) {
-                ctx->prof2_budget -= 1;
-                TDGL_TRY(profile_event(ctx, &pa));
-                TDGL_TRY(profile_event(ctx, &pb));
-                HIP_TRY(ctx, hipEventRecord(pa, ctx->stream));
-            }
-            if (f32i) {
-                if (pat.use16) TDGL_AXP(float, int16_t, pat.cols16.p, z32); else TDGL_AXP(float, int32_t, pat.cols.p, z32);
-            } else {
-                if (pat.use16) TDGL_AXP(double, int16_t, pat.cols16.p, (const double *)z);
-                else TDGL_AXP(double, int32_t, pat.cols.p, (const double *)z);
-            }
+    hipLaunchKernelGGL((k_sell_axp<ZT, IT>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd,    \
+                       pat.n_rows, pat.slice_off.p, COLS, L0.A.vals.p, Z, (const double *)p_old,                   \
+                       (const double *)rz_new, rz_prev, run.p, run.q, ctx->part_pq.p,                               \
+                       flex ? (const double *)(rz_new + 2 * NB) : (const double *)nullptr, (const double *)ctx->scal.p)
+
+// The rest of an iteration on one GPU: the direction update fused into A p (double-buffered p), then x += alpha p,
+// r -= alpha q with the partials of the new ||r||^2 -- and of sum x, so that the zero-mean gauge at the end of the
+// solve needs no pass over x of its own (valid as soon as one update of this solve has run).
+static int cg_step_single(CgRun &run, int it, const double *z, const float *z32) {
+    tdgl_ctx *ctx = run.ctx;
+    AmgLevel &L0 = *ctx->levels[0];
+    const bool flex = run.flex();
+    double *rz_new = run.part_rz[it & 1], *rz_old = run.part_rz[(it + 1) & 1];
+    double *p_old = run.p;
+    run.p = (run.p == ctx->pcg_p.p) ? ctx->pcg_p2.p : ctx->pcg_p.p;
+    int per_xcd, grid;
+    sell_fixed_grid(L0.A.pat.n_slices, &per_xcd, &grid);
+    const double *rz_prev = it == run.it0 ? (const double *)nullptr : (const double *)rz_old;
+    const SellPattern &pat = L0.A.pat;
+    hipEvent_t pa = nullptr, pb = nullptr;
+    // (every 8th launch, at most 64 samples: event pairs on every launch would slow a short timed window down measurably)
+    const bool sample = ctx->profile && ctx->prof2_budget > 0 && (ctx->prof2_seen++ % 8) == 0;
+    if (sample) {
+        ctx->prof2_budget -= 1;
+        TDGL_TRY(profile_event(ctx, &pa));
+        TDGL_TRY(profile_event(ctx, &pb));
+        HIP_TRY(ctx, hipEventRecord(pa, ctx->stream));
+    }
+    if (run.f32i()) {
+        if (pat.use16) TDGL_AXP(float, int16_t, pat.cols16.p, z32); else TDGL_AXP(float, int32_t, pat.cols.p, z32);
+    } else {
+        if (pat.use16) TDGL_AXP(double, int16_t, pat.cols16.p, z); else TDGL_AXP(double, int32_t, pat.cols.p, z);
+    }
+    if (sample) {
+        HIP_TRY(ctx, hipEventRecord(pb, ctx->stream));
+        ctx->prof2_pending.emplace_back(pa, pb);
+    }
+    const XrArgs upd{run.p, run.q, rz_new, ctx->part_pq.p, run.part_rr[it & 1], ctx->scal.p, run.x, run.r, run.part_rr[(it + 1) & 1],
+                     ctx->n_own, ctx->npart, ctx->part_tmp.p};
+    run.sum_x_fresh = true;
+    hipLaunchKernelGGL(k_update_xr, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, upd);
+    run.rr_reduced = false;
+    return TDGL_OK;
+}
 #undef TDGL_AXP
-            if (sample) {
-                HIP_TRY(ctx, hipEventRecord(pb, ctx->stream));
-                ctx->prof2_pending.emplace_back(pa, pb);
-            }
-        } else {
-            // one-process-per-GPU mode: Chronopoulos-Gear recurrences, one all-reduce for the CG
-            // sums (the other one of the iteration is the coarse right-hand side in the V-cycle).
-            // w = A z lands in the second direction buffer (unused in this mode).
-            double *w = ctx->pcg_p2.p, *zw = rz_new + 2 * NB;
-            if (cg1) {
-                // z is already valid on the first ghost layer (formed there redundantly): no exchange; r.z and z.w
-                // over the owned rows in this one pass
-                const SellPattern &pat = L0.A.pat;
-                const int n_slices = (int)((no + WAVE - 1) / WAVE), tiles = (n_slices + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-                const int per_xcd = std::max(1, (tiles + XCDS - 1) / XCDS);
-                if (pat.use16)
-                    hipLaunchKernelGGL((k_sell_spmv<AX, DOT_BX_XY, int16_t, double, float>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream,
-                                       n_slices, per_xcd, 0, no, pat.slice_off.p, pat.cols16.p, L0.A.vals.p, z32, (const double *)r,
-                                       (const double *)nullptr, 0.0, 0.0, (double *)nullptr, w, rz_new);
-                else
-                    hipLaunchKernelGGL((k_sell_spmv<AX, DOT_BX_XY, int32_t, double, float>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream,
-                                       n_slices, per_xcd, 0, no, pat.slice_off.p, pat.cols.p, L0.A.vals.p, z32, (const double *)r,
-                                       (const double *)nullptr, 0.0, 0.0, (double *)nullptr, w, rz_new);
-            } else if (overlap_on(ctx)) {
-                TDGL_TRY(comm_halo_start(ctx, z, 1));
-                launch_sell<AX, DOT_XY>(ctx, L0.A, z, nullptr, nullptr, 0.0, 0.0, nullptr, w, zw, 1);
-                TDGL_TRY(comm_halo_wait(ctx));
-                launch_sell<AX, DOT_XY>(ctx, L0.A, z, nullptr, nullptr, 0.0, 0.0, nullptr, w, zw, 2);
-            } else {
-                TDGL_TRY(comm_halo(ctx, z, 1));
-                launch_sell<AX, DOT_XY>(ctx, L0.A, z, nullptr, nullptr, 0.0, 0.0, nullptr, w, zw);
-            }
-            if (rr_reduced) {  // ||r_prev||^2 is already global (first iteration, or just after a check)
-                TDGL_TRY(comm_allreduce(ctx, rz_new, NB, 0));
-                TDGL_TRY(comm_allreduce(ctx, zw, NB, 0));
-            } else {
-                TDGL_TRY(comm_allreduce(ctx, rz_new, 3 * NB, 0));
-            }
-            if (cg1)
-                hipLaunchKernelGGL((k_cg_update<float>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, z32,
-                                   (const double *)w, (const double *)rz_new, it == it0 ? 1 : 0, it & 1, ctx->scal.p, p, q,
-                                   x, r, part_rr[(it + 1) & 1]);
-            else
-                hipLaunchKernelGGL((k_cg_update<double>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, (const double *)z,
-                                   (const double *)w, (const double *)rz_new, it == it0 ? 1 : 0, it & 1, ctx->scal.p, p, q,
-                                   x, r, part_rr[(it + 1) & 1]);
-            rr_reduced = false;
-            return TDGL_OK;
-        }
-        // (single GPU from here) x += alpha p, r -= alpha q, the partials of the new ||r||^2 and of sum x
-        const XrArgs upd{p, q, rz_new, ctx->part_pq.p, part_rr[it & 1], ctx->scal.p, x, r, part_rr[(it + 1) & 1], no, ctx->npart,
-                         sum_x_rides ? ctx->part_tmp.p : (double *)nullptr};
-        sum_x_fresh = sum_x_rides;
-        hipLaunchKernelGGL(k_update_xr, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, upd);
-        rr_reduced = false;
-        return TDGL_OK;
-    };
-restart:
-    while (rr > tol2 && it < budget) {
-        int chunk = (ctx->popt.check_every > 0 && !use_pd) ? ctx->popt.check_every : (it == it0 ? predicted : 1);
-        chunk = std::min(chunk, budget - it);
-        for (int c = 0; c < chunk; ++c, ++it) TDGL_TRY(iteration(it));
+
+// ... in one-process-per-GPU mode: Chronopoulos-Gear recurrences, one all-reduce for the CG sums (the other one of
+// the iteration is the coarse right-hand side in the V-cycle).  w = A z lands in the second direction buffer (unused
+// in this mode).
+static int cg_step_ranks(CgRun &run, int it, double *z, const float *z32) {
+    tdgl_ctx *ctx = run.ctx;
+    AmgLevel &L0 = *ctx->levels[0];
+    const int64_t no = ctx->n_own;
+    double *rz_new = run.part_rz[it & 1];
+    double *w = ctx->pcg_p2.p, *zw = rz_new + 2 * NB;
+    const bool cg1 = run.cg1();
+    if (cg1) {
+        // z is already valid on the first ghost layer (formed there redundantly): no exchange; r.z and z.w
+        // over the owned rows in this one pass
+        const SellPattern &pat = L0.A.pat;
+        const int n_slices = (int)((no + WAVE - 1) / WAVE), tiles = (n_slices + BLOCK / WAVE - 1) / (BLOCK / WAVE);
+        const int per_xcd = std::max(1, (tiles + XCDS - 1) / XCDS);
+        if (pat.use16)
+            hipLaunchKernelGGL((k_sell_spmv<AX, DOT_BX_XY, int16_t, double, float>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream,
+                               n_slices, per_xcd, 0, no, pat.slice_off.p, pat.cols16.p, L0.A.vals.p, z32, (const double *)run.r,
+                               (const double *)nullptr, 0.0, 0.0, (double *)nullptr, w, rz_new);
+        else
+            hipLaunchKernelGGL((k_sell_spmv<AX, DOT_BX_XY, int32_t, double, float>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream,
+                               n_slices, per_xcd, 0, no, pat.slice_off.p, pat.cols.p, L0.A.vals.p, z32, (const double *)run.r,
+                               (const double *)nullptr, 0.0, 0.0, (double *)nullptr, w, rz_new);
+    } else if (overlap_on(ctx)) {
+        TDGL_TRY(comm_halo_start(ctx, z, 1));
+        launch_sell<AX, DOT_XY>(ctx, L0.A, z, nullptr, nullptr, 0.0, 0.0, nullptr, w, zw, 1);
+        TDGL_TRY(comm_halo_wait(ctx));
+        launch_sell<AX, DOT_XY>(ctx, L0.A, z, nullptr, nullptr, 0.0, 0.0, nullptr, w, zw, 2);
+    } else {
+        TDGL_TRY(comm_halo(ctx, z, 1));
+        launch_sell<AX, DOT_XY>(ctx, L0.A, z, nullptr, nullptr, 0.0, 0.0, nullptr, w, zw);
+    }
+    if (run.rr_reduced) {  // ||r_prev||^2 is already global (first iteration, or just after a check)
+        TDGL_TRY(comm_allreduce(ctx, rz_new, NB, 0));
+        TDGL_TRY(comm_allreduce(ctx, zw, NB, 0));
+    } else {
+        TDGL_TRY(comm_allreduce(ctx, rz_new, 3 * NB, 0));
+    }
+    if (cg1)
+        hipLaunchKernelGGL((k_cg_update<float>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, z32,
+                           (const double *)w, (const double *)rz_new, it == run.it0 ? 1 : 0, it & 1, ctx->scal.p, run.p, run.q,
+                           run.x, run.r, run.part_rr[(it + 1) & 1]);
+    else
+        hipLaunchKernelGGL((k_cg_update<double>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, (const double *)z,
+                           (const double *)w, (const double *)rz_new, it == run.it0 ? 1 : 0, it & 1, ctx->scal.p, run.p, run.q,
+                           run.x, run.r, run.part_rr[(it + 1) & 1]);
+    run.rr_reduced = false;
+    return TDGL_OK;
+}
+
+// one PCG iteration (all launches on ctx->stream; the only host values in it that change from iteration to iteration are
+// the parity of `it` and "is this the first one")
+static int cg_iteration(CgRun &run, int it) {
+    double *z = nullptr;
+    const float *z32 = nullptr;
+    TDGL_TRY(cg_precondition(run, it, &z, &z32));
+    return (!distributed(run.ctx) && !run.cg1()) ? cg_step_single(run, it, z, z32) : cg_step_ranks(run, it, z, z32);
+}
+
+// The iterations of one run, from `it` on until the residual is below the tolerance or the budget is spent.  The host
+// looks: with check_every = 0 (auto) after `predicted` iterations (an update that finds the residual already converged
+// freezes itself, k_update_xr) and after every iteration from there on; with check_every = k > 0, after every k.
+static int cg_iterate(CgRun &run, double tol2, int &it, double &rr) {
+    tdgl_ctx *ctx = run.ctx;
+    while (rr > tol2 && it < run.budget) {
+        int chunk = (ctx->popt.check_every > 0 && !run.use_pd) ? ctx->popt.check_every : (it == run.it0 ? run.predicted : 1);
+        chunk = std::min(chunk, run.budget - it);
+        for (int c = 0; c < chunk; ++c, ++it) TDGL_TRY(cg_iteration(run, it));
         ctx->stat_pcg_launched += chunk;
-        if (it - chunk != it0) ctx->stat_pcg_extra_syncs += 1;  // not the first batch of this CG run
-        TDGL_TRY(comm_allreduce(ctx, part_rr[it & 1], NB, 0));  // the host looks at it now
-        rr_reduced = true;
-        TDGL_TRY(fetch_scalars(ctx, false, part_rr[it & 1]));  // also scal[S_RR] = sum of the partials
+        if (it - chunk != run.it0) ctx->stat_pcg_extra_syncs += 1;  // not the first batch of this CG run
+        TDGL_TRY(comm_allreduce(ctx, run.part_rr[it & 1], NB, 0));  // the host looks at it now
+        run.rr_reduced = true;
+        TDGL_TRY(fetch_scalars(ctx, false, run.part_rr[it & 1]));  // also scal[S_RR] = sum of the partials
         rr = ctx->h_status->scal[S_RR];
         if (ctx->h_status->scal[S_CONV_IT] >= 0.0) {  // converged inside the batch: the rest was frozen
             it = (int)ctx->h_status->scal[S_CONV_IT];
@@ -1845,89 +1517,54 @@ restart:
         // regime: 1.4e-10 left) does not need a second one -- 6.5 more decades for 450 us -- when one or two V-cycles (0.5
         // decades, 85 us each) finish the job.  The same cost rule as before the solve, on the residual that is left;
         // the CG starts over from the current iterate (beta = 0) with the other preconditioner.
-        if (use_pd && rr > tol2 && ctx->pd_choice == 0 && ctx->pd_t_apply_us > 0.0 && ctx->pd_t_vcycle_us > 0.0) {
-            const double decades = 0.5 * std::log10(rr / tol2);
-            const double n_amg = std::max(1.0, std::ceil(decades / ctx->pcg_rate - 0.25));
-            const double n_pd = std::max(1.0, std::ceil(decades / ctx->pd_rate - 0.05));
-            const double t_common = 0.55 * ctx->pd_t_vcycle_us;
-            if (n_amg * (ctx->pd_t_vcycle_us + t_common) < n_pd * (ctx->pd_t_apply_us + t_common)) {
-                pd_its = it - it0;
-                pd_rr_end = rr;
-                use_pd = false;
-                it0 = it;
-                predicted = (int)std::min<double>(n_amg, (double)(budget - it));
+        if (run.use_pd && rr > tol2 && ctx->pd_choice == 0 && ctx->pd_t_apply_us > 0.0 && ctx->pd_t_vcycle_us > 0.0) {
+            const PrecondCost cost = precond_cost(ctx, rr, tol2);
+            if (cost.amg < cost.pd) {
+                run.pd_its = it - run.it0;
+                run.pd_rr_end = rr;
+                run.use_pd = false;
+                run.it0 = it;
+                run.predicted = (int)std::min<double>(cost.n_amg, (double)(run.budget - it));
                 ctx->pd_handovers += 1;
             }
         }
     }
-    if (rr > tol2 && use_pd) {
+    return TDGL_OK;
+}
+
+// A run ended above the tolerance with its budget spent: is there another preconditioner to go on with, from the
+// current iterate and with a budget of its own?
+static bool next_phase(CgRun &run, int it) {
+    tdgl_ctx *ctx = run.ctx;
+    if (run.use_pd) {
         // (the factors did not get there within the budget -- cannot happen with sound factors: finish with the V-cycle)
-        use_pd = false;
-        it0 = it;
-        budget = it + ctx->popt.max_iter;
-        goto restart;
-    }
-    if (rr > tol2 && f32 && !ctx->deep) {
+        run.use_pd = false;
+    } else if (run.f32 && !ctx->deep) {
         // Safety net: the iteration budget ran out with the fp32-stored level-0 operators.  Restart
         // the CG from the current iterate with the fp64 ones before giving up.
-        f32 = false;
-        coarse32 = false;
-        it0 = it;
-        budget = it + ctx->popt.max_iter;
+        run.f32 = false;
+        run.coarse32 = false;
         ctx->f32_fallbacks += 1;
-        goto restart;
-    }
-    // zero-mean gauge, then ghost values of the solution for the edge kernels / next step
-    if (!sum_x_fresh)
-        hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, x, (const double *)nullptr, ctx->part_tmp.p);
-    TDGL_TRY(comm_allreduce(ctx, ctx->part_tmp.p, NB, 0));
-    if (proj && !(rr > tol2)) {
-        // the solution joins the projection basis (replacing the oldest vector of a full window)
-        const int gw = guess_window(ctx);
-        int slot = 0;
-        if (ctx->g_count >= gw) {
-            slot = ctx->g_slot[0];
-            for (int i = 0; i + 1 < ctx->g_count; ++i) {
-                ctx->g_slot[i] = ctx->g_slot[i + 1];
-                for (int h = 0; h < 2; ++h) ctx->g_rhs[i][h] = ctx->g_rhs[i + 1][h];
-                for (int j = 0; j + 1 < ctx->g_count; ++j)
-                    for (int h = 0; h < 2; ++h) ctx->g_G[i][j][h] = ctx->g_G[i + 1][j + 1][h];
-            }
-            ctx->g_count -= 1;
-        } else {
-            bool used[GK] = {false};
-            for (int i = 0; i < ctx->g_count; ++i) used[ctx->g_slot[i]] = true;
-            while (used[slot]) ++slot;
-        }
-        hipLaunchKernelGGL(k_finish_solution, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, (const double *)ctx->part_tmp.p,
-                           inv_n, x, (const double *)b, b_mean, (const double *)r, ctx->g_x[slot].p, ctx->g_y[slot].p);
-        // (the Gram row of the new pair y_new = (b - mean) - r_final comes with the next solve's dot-product
-        // pass: until then the placeholders below -- y_j . b, off by y_j . r_final -- are never used)
-        const int k = ctx->g_count;
-        ctx->g_slot[k] = slot;
-        for (int j = 0; j < k; ++j)
-            for (int h = 0; h < 2; ++h) ctx->g_G[k][j][h] = ctx->g_G[j][k][h] = ctx->g_rhs[j][h];
-        ctx->g_G[k][k][0] = ctx->g_bb[0];
-        ctx->g_G[k][k][1] = ctx->g_bb[1];
-        ctx->g_row_pending = true;
-        ctx->g_count = k + 1;
     } else {
-        hipLaunchKernelGGL(k_shift_mean, dim3(gv), dim3(BLOCK), 0, ctx->stream, no, ctx->part_tmp.p, inv_n, x);
+        return false;
     }
-    if (ctx->defer_mu_halo && overlap_on(ctx))
-        TDGL_TRY(comm_halo_start(ctx, x, 1));  // the step driver overlaps it with the interior edges
-    else
-        TDGL_TRY(comm_halo(ctx, x, 1));
-    HIP_TRY(ctx, hipGetLastError());
+    run.it0 = it;
+    run.budget = it + ctx->popt.max_iter;
+    return true;
+}
+
+// the bookkeeping behind a solve: counts, the running contraction rates the predictions use, the final error
+static int pcg_note_solve(tdgl_ctx *ctx, const CgRun &run, int it, double rr, double bb, double tol2) {
     ctx->last_pcg_iters = it;
     ctx->stat_pcg_iters += it;
     ctx->stat_pcg_needed += it;
     ctx->last_relres = std::sqrt(rr / bb);
     ctx->last_guess_relres = it > 0 ? std::sqrt(std::max(0.0, ctx->h_status->scal[S_RR0]) / bb) : ctx->last_relres;
+    const int pd_its = run.pd_its;
     if (ctx->pd_last) {
         ctx->pd_solves += 1;
         const int its_f = pd_its >= 0 ? pd_its : it;          // (with the factors; the rest, after a hand-over, with the V-cycle)
-        const double rr_f = pd_its >= 0 ? pd_rr_end : rr;
+        const double rr_f = pd_its >= 0 ? run.pd_rr_end : rr;
         ctx->pd_iters += its_f;
         if (pd_its >= 0) ctx->pd_amg_iters += it - its_f;
         const double rr0 = ctx->h_status->scal[S_RR0];
@@ -1954,6 +1591,165 @@ restart:
         TDGL_FAIL(ctx, TDGL_ERR_PCG, "Poisson solve did not converge: relative residual %.3e after %d iterations (rtol %.1e)",
                   ctx->last_relres, it, ctx->popt.rtol);
     return TDGL_OK;
+}
+
+// Solve A x = b (b = ctx->bvec, x = ctx->mu holds the initial guess).  `after_first_sync` is
+// called after the first host synchronisation with the status block filled; it returns false
+// to abandon the solve (the step driver retries a failed psi update without finishing a solve
+// whose right-hand side is garbage).
+// The host synchronises once before the iterations and then as cg_iterate says.
+template <class F>
+static int pcg_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool allow_projection = false) {
+    if (ctx->levels.empty()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "no AMG hierarchy: call tdgl_poisson_set_hierarchy");
+    TDGL_TRY(comm_ready(ctx));
+    if (abandoned) *abandoned = false;
+    if (dense_on(ctx)) return direct_mu_solve(ctx, after_first_sync, abandoned, allow_projection && ctx->psi_status_pending);
+    AmgLevel &L0 = *ctx->levels[0];
+    GuessBasis &guess = ctx->guess;
+    // all pointwise work is on the owned rows; sums are over ranks (comm_allreduce is a no-op
+    // on one GPU); the ghost entries of x / p are refreshed before the operator reads them
+    const int64_t no = ctx->n_own;
+    const double inv_n = 1.0 / (double)ctx->n_global;
+    const int gv = vec_grid(no);
+    CgRun run{ctx, ctx->bvec.p, ctx->mu.p, ctx->pcg_r.p, ctx->pcg_p.p, ctx->pcg_q.p,
+              {ctx->part_pair[0].p, ctx->part_pair[1].p}, {ctx->part_pair[0].p + NB, ctx->part_pair[1].p + NB}};
+    double *b = run.b, *x = run.x, *r = run.r;
+    run.f32 = precond_f32_on(ctx);
+    if (ctx->deep && !distributed(ctx))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "a deep halo plan is set but no transport: call tdgl_comm_init_ipc / _rccl / _callbacks");
+    if (ctx->deep && !run.f32)
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "two distributed levels need the fp32-stored V-cycle with degree-1 smoothing on"
+                  " level 0 and the fused restriction (the default options)");
+    if (run.f32) TDGL_TRY(ensure_f32(ctx));
+    // Flexible (Polak-Ribiere) beta (tdgl_poisson_options.flexible_cg, off by default -- measured no better than
+    // Fletcher-Reeves, see the header) on the path whose preconditioner is not exactly symmetric: the single-GPU recurrence
+    // with the fp32 / binary16-stored V-cycle.  The smoothing step that produces z_new also forms z_new . q_old (q still
+    // holds A p of the previous iteration); the direction update turns it into beta = -alpha (z_new . q_old) / (r.z)_old.
+    run.flex_opt = ctx->popt.flexible_cg != 0 && !distributed(ctx);
+    // Initial guess by projection onto the previous solutions: their dot products with the new
+    // right-hand side, b.b and sum b go to the host with the status block; x0 and r0 follow the sync.
+    const bool proj = allow_projection && ctx->popt.extrapolate >= 3;
+    if (proj) {  // (the mean of b is removed arithmetically, see k_multi_dot)
+        TDGL_TRY(guess_queue_dots(ctx, b));
+    } else {
+        // make b orthogonal to the null space (constants); ||b||^2; r = b - A x; ||r||^2
+        hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, b, (const double *)nullptr, ctx->part_tmp.p);
+        TDGL_TRY(comm_allreduce(ctx, ctx->part_tmp.p, NB, 0));
+        hipLaunchKernelGGL(k_shift_mean, dim3(gv), dim3(BLOCK), 0, ctx->stream, no, ctx->part_tmp.p, inv_n, b);
+        hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, b, b, ctx->part_pq.p);
+        launch_sell<RESID, DOT_YY>(ctx, L0.A, x, b, nullptr, 0.0, 0.0, nullptr, r, run.part_rr[0]);
+        TDGL_TRY(comm_allreduce(ctx, ctx->part_pq.p, NB, 0));
+        TDGL_TRY(comm_allreduce(ctx, run.part_rr[0], NB, 0));
+        hipLaunchKernelGGL(k_store_sum, dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->part_pq.p, ctx->scal.p, (int)S_BB,
+                           ctx->popt.rtol * ctx->popt.rtol);  // also scal[S_TOL2]
+        hipLaunchKernelGGL(k_store_sum, dim3(1), dim3(BLOCK), 0, ctx->stream, run.part_rr[0], ctx->scal.p, (int)S_RR, 0.0);
+        static const double init[2] = {-1.0, 0.0};  // S_CONV_IT: "not converged yet"; S_IT: 0
+        static_assert(S_IT == S_CONV_IT + 1, "contiguous");
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->scal.p + S_CONV_IT, init, 2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (distributed(ctx)) {  // psi failure flag and max d|psi|^2: identical decisions on all ranks
+        hipLaunchKernelGGL(k_status_pack, dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->psi_dmax_part.p,
+                           ctx->psi_fail_part.p, ctx->psi_blocks, ctx->d_gstat.p);
+        TDGL_TRY(comm_allreduce(ctx, ctx->d_gstat.p, 2, 1));
+        hipLaunchKernelGGL(k_status_unpack, dim3(1), dim3(64), 0, ctx->stream, ctx->d_gstat.p, ctx->status_dev);
+        ctx->psi_status_pending = false;  // d_status now holds the all-reduced outcome
+    }
+    TDGL_TRY(fetch_scalars(ctx, proj));
+    // The Gram row of the window's newest vector arrived with this status block.  Taken BEFORE an abandoned
+    // solve returns: a second pcg_solve for the same step (after a psi retry) would compute it again, which
+    // is harmless, but a window change in between would not be.
+    if (proj) guess.take_gram_row(ctx->h_status);
+    if (!after_first_sync(ctx->h_status)) {
+        if (abandoned) *abandoned = true;
+        return TDGL_OK;
+    }
+    const double bb = ctx->h_status->scal[S_BB];
+    double rr = proj ? INFINITY : ctx->h_status->scal[S_RR];
+    int it = 0;
+    const double b_mean = proj ? ctx->h_status->gdot[2 * G_SB] * inv_n : 0.0;  // still inside b
+    if (!(bb > 0.0)) {  // b = 0: the zero-mean solution is 0
+        HIP_TRY(ctx, hipMemsetAsync(x, 0, ctx->n_pad * sizeof(double), ctx->stream));
+        ctx->last_pcg_iters = 0;
+        ctx->last_relres = 0.0;
+        return TDGL_OK;
+    }
+    guess.mu_first_saved = false;
+    if (proj && guess.count == 0) {  // no basis yet: keep mu^n so that a failed solve can be rolled back (run.inc)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->mu_prev.p, x, ctx->n_pad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        guess.mu_first_saved = true;
+    }
+    VecSet vs{};
+    const double *c_used = nullptr;  // the guess's coefficients, when it used vectors of the window
+    if (proj) {
+        // x0 = X c with G c = X^T b (host, K x K); then r0 = b - A x0.  ||r0||^2 stays on the device:
+        // the first batch of iterations runs regardless (an update that finds the residual below
+        // the tolerance freezes itself), and the first update records it for the statistics.
+        TDGL_TRY(guess_apply(ctx, vs, gv, x, &c_used));
+        launch_sell<RESID, DOT_YY>(ctx, L0.A, x, b, nullptr, b_mean, 0.0, nullptr, r, run.part_rr[0]);
+        // (one process per GPU: ||r0||^2 is not summed over the ranks here -- nobody looks at it before the first
+        // iteration, whose one sum of [r.z | ||r||^2 | z.w] takes it along: two sums per step less)
+        if (distributed(ctx)) run.rr_reduced = false;
+    }
+    const double tol2 = ctx->popt.rtol * ctx->popt.rtol * bb;
+    // The squared residual the iterations start from is known before anything is queued: with the projection guess
+    // ||b - Y c||^2 from the Gram data, which the host already holds.  Both decisions below rest on it.
+    const bool predict = proj && ctx->pcg_predict_from_guess && ctx->popt.check_every <= 0;
+    const bool choose = precond_factors_available(ctx) && ctx->pd_choice != 2;
+    const double est = !proj ? rr : (predict || choose) ? guess.residual_estimate(c_used) : NAN;
+    // Size of the first batch.  Iterations queued beyond convergence freeze themselves but still cost their
+    // launches (84 us each at 1M sites); a batch that is too short costs one more look per missing iteration
+    // (~20 us).  The count of the previous solve is wrong in a third of the steps; the residual of the guess is a
+    // much better predictor, divided by the contraction per iteration observed so far.
+    run.predicted = std::max(1, ctx->last_pcg_iters);
+    if (predict) {
+        if (est > tol2 && std::isfinite(est)) {
+            const double its = 0.5 * std::log10(est / tol2) / ctx->pcg_rate;
+            run.predicted = (int)std::ceil(its - 0.25);  // (an iteration too many costs four times an iteration too few)
+        } else {
+            run.predicted = 1;
+        }
+        run.predicted = std::max(1, std::min(run.predicted, ctx->popt.max_iter));
+    }
+    // Which preconditioner: the cheaper PREDICTED solve (precond_cost).  Stationary / smoothly evolving states (guess
+    // good to 1e-9: two or three V-cycles) stay with AMG; transients and the long-time regime (guess at 1e-4 .. 1e-6:
+    // 8-13 V-cycles) take ONE application of the factors.
+    run.use_pd = false;
+    if (choose) {
+        if (ctx->pd_choice == 1) {
+            run.use_pd = true;
+        } else if (std::isfinite(est) && est > tol2 && ctx->pd_t_apply_us > 0.0 && ctx->pd_t_vcycle_us > 0.0) {
+            const PrecondCost cost = precond_cost(ctx, est, tol2);
+            run.use_pd = cost.pd < cost.amg;
+        }
+        if (run.use_pd) run.predicted = 1;  // (an application too many costs five V-cycles: look after every one)
+    }
+    ctx->pd_last = run.use_pd;
+    // (one-process-per-GPU mode runs level 0 in fp64 but shares the fp32-stored replicated levels)
+    run.coarse32 = ctx->popt.precond_fp32 != 0 && ctx->levels.size() > 2;
+    if (run.coarse32) TDGL_TRY(ensure_coarse_f32(ctx));
+    run.it0 = 0;
+    run.budget = ctx->popt.max_iter;
+    do {  // the phases: one CG run each
+        TDGL_TRY(cg_iterate(run, tol2, it, rr));
+    } while (rr > tol2 && next_phase(run, it));
+    // zero-mean gauge, then ghost values of the solution for the edge kernels / next step
+    if (!run.sum_x_fresh)
+        hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, x, (const double *)nullptr, ctx->part_tmp.p);
+    TDGL_TRY(comm_allreduce(ctx, ctx->part_tmp.p, NB, 0));
+    if (proj && !(rr > tol2)) {
+        // the solution joins the projection basis (replacing the oldest vector of a full window)
+        const int slot = guess.push(guess_window(ctx));
+        hipLaunchKernelGGL(k_finish_solution, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, (const double *)ctx->part_tmp.p,
+                           inv_n, x, (const double *)b, b_mean, (const double *)r, guess.x[slot].p, guess.y[slot].p);
+    } else {
+        hipLaunchKernelGGL(k_shift_mean, dim3(gv), dim3(BLOCK), 0, ctx->stream, no, ctx->part_tmp.p, inv_n, x);
+    }
+    if (ctx->defer_mu_halo && overlap_on(ctx))
+        TDGL_TRY(comm_halo_start(ctx, x, 1));  // the step driver overlaps it with the interior edges
+    else
+        TDGL_TRY(comm_halo(ctx, x, 1));
+    HIP_TRY(ctx, hipGetLastError());
+    return pcg_note_solve(ctx, run, it, rr, bb, tol2);
 }
 
 extern "C" int tdgl_poisson_solve(tdgl_ctx *ctx, const double *rhs, double *mu_inout, int32_t *iters,
@@ -2001,9 +1797,7 @@ extern "C" int tdgl_guess_dots(tdgl_ctx *ctx, int32_t k, int64_t n, const double
     vs.k = k;
     for (int j = 0; j < k; ++j) vs.p[j] = dv.p + (int64_t)j * n_pad;
     const int gg = std::min<int>(512, std::max<int64_t>(8, (n / 2 + BLOCK - 1) / BLOCK));
-    if (k <= 8) hipLaunchKernelGGL((k_multi_dot<8>), dim3(gg), dim3(BLOCK), 0, ctx->stream, n, (const double *)db.p, vs, newest, part.p);
-    else if (k <= 12) hipLaunchKernelGGL((k_multi_dot<12>), dim3(gg), dim3(BLOCK), 0, ctx->stream, n, (const double *)db.p, vs, newest, part.p);
-    else hipLaunchKernelGGL((k_multi_dot<GK>), dim3(gg), dim3(BLOCK), 0, ctx->stream, n, (const double *)db.p, vs, newest, part.p);
+    launch_multi_dot(ctx, gg, n, db.p, vs, newest, part.p);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<double> h((size_t)2 * G_ARRAYS * NB);
     HIP_TRY(ctx, hipMemcpy(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));

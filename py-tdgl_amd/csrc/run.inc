@@ -120,8 +120,7 @@ static void direct_policy(tdgl_ctx *ctx) {
                               wm[2] < 0.9 * wm[1] && wm[1] < 0.9 * wm[0];
         if (!(worst < DIRECT_PAUSE_DMAX) && !relaxing) return;
         ctx->direct_paused = true;  // stationary or on its way there: the iterative solve takes over (its window starts empty)
-        ctx->g_count = 0;
-        ctx->g_row_pending = false;
+        ctx->guess.reset();
         ctx->direct_pcg_ema = 0.0;
     } else {
         if (ctx->direct_switch_steps < DIRECT_PAUSE_WINDOW || ctx->direct_pcg_ema < DIRECT_RESUME_ITERS) return;
@@ -312,8 +311,8 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
             if (ctx->popt.extrapolate >= 3 && !abandoned) {
                 // the newest basis vector IS mu^n (a failed solve does not join the basis); before the
                 // first solve after tdgl_set_state there is none and pcg_solve kept a copy in mu_prev
-                const double *src = ctx->g_count > 0 ? ctx->g_x[ctx->g_slot[ctx->g_count - 1]].p
-                                                     : (ctx->mu_first_saved ? ctx->mu_prev.p : nullptr);
+                const double *src = ctx->guess.newest_x();
+                if (!src && ctx->guess.mu_first_saved) src = ctx->mu_prev.p;
                 if (src) {
                     (void)hipMemcpyAsync(ctx->mu.p, src, ctx->n_pad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream);
                     // (basis vectors hold the owned rows only: the ghost copies come from their owners;

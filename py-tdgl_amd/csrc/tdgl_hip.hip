@@ -558,8 +558,9 @@ static void publish_status(tdgl_ctx *ctx, bool guess_start = false, const double
     hipLaunchKernelGGL(k_publish_status, dim3(1), dim3(BLOCK), 0, ctx->stream, ctx->status_dev, ctx->scal.p,
                        psi ? ctx->psi_dmax_part.p : (const double *)nullptr,
                        psi ? ctx->psi_fail_part.p : (const int32_t *)nullptr, ctx->psi_blocks,
-                       ctx->d_gdot.n ? ctx->d_gdot.p : (double *)nullptr,
-                       guess_start ? (rank_totals ? ctx->part_gdot_rank.p : ctx->part_gdot.p) : (const double *)nullptr, ctx->g_count,
+                       ctx->guess.d_dot.n ? ctx->guess.d_dot.p : (double *)nullptr,
+                       guess_start ? (rank_totals ? ctx->guess.part_dot_rank.p : ctx->guess.part_dot.p) : (const double *)nullptr,
+                       ctx->guess.count,
                        rank_totals ? ctx->world : guess_grid(ctx), rank_totals ? (int)G_RANK_STRIDE : (int)NB, (double)ctx->n_global,
                        ctx->popt.rtol * ctx->popt.rtol, rr_part);
     ctx->psi_status_pending = false;
@@ -600,6 +601,7 @@ static inline int64_t now_ns() {
 
 #include "ipc.inc"
 #include "comm.inc"
+#include "guess.inc"
 #include "poisson.inc"
 #include "dense.inc"
 #include "schur.inc"
@@ -898,8 +900,7 @@ extern "C" int tdgl_set_state(tdgl_ctx *ctx, const double *psi, const double *mu
     ctx->currents_deferred = false;
     ctx->ra_retries = 0;
     ctx->prev_dt = ctx->prev_dt2 = 0.0;  // no mu history: the next solve starts from mu itself
-    ctx->g_count = 0;                     // (nor a projection basis)
-    ctx->g_row_pending = false;
+    ctx->guess.reset();                   // (nor a projection basis)
     direct_policy_reset(ctx);             // (nor a history for the loop's solver choice)
     return TDGL_OK;
 }

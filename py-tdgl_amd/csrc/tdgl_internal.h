@@ -242,6 +242,35 @@ struct StepStatus {
     double gdot[2 * (2 * GUESS_MAX + 2)];
 };
 
+// Projection guess of the mu solve (popt.extrapolate == 3): window of previous solutions x_j and their images
+// y_j = A x_j (= b_j - r_j with the final residual of the CG recurrence), oldest first; G[i][j] = y_i . y_j in
+// window order, kept on the host as double-double numbers (hi, lo).  Written by the functions below only (guess.inc).
+struct GuessBasis {
+    DevBuf<double> x[GUESS_MAX], y[GUESS_MAX];  // by slot; slot[j]: where the window's j-th vector lives
+    int slot[GUESS_MAX] = {0};
+    int count = 0;
+    bool row_pending = false;      // the newest vector's Gram row arrives with the next solve's first status block
+    bool mu_first_saved = false;   // mu_prev holds mu^n of a solve that started without a basis (set by pcg_solve)
+    double G[GUESS_MAX][GUESS_MAX][2] = {{{0}}};
+    double rhs[GUESS_MAX][2] = {{0}};  // y_j . b of the right-hand side being solved
+    double bb[2] = {0, 0};             // its (b - mean) . (b - mean)
+    DevBuf<double> part_dot;       // 2 (2 GUESS_MAX + 2) x NB partials, see StepStatus::gdot
+    DevBuf<double> d_dot;          // their sums
+    DevBuf<double> part_dot_rank;  // one process per GPU: every rank's totals (kernels.inc: k_guess_rank_totals)
+
+    void reset() { count = 0, row_pending = false; }  // (a new operator or state: the basis belongs to the previous one)
+    int ensure(tdgl_ctx *ctx);
+    void take_gram_row(const StepStatus *st);
+    void load_rhs(const StepStatus *st, int64_t n_global);
+    int solve(double cut, double *c) const;
+    double residual_estimate(const double *c) const;
+    int push(int window);
+    const double *newest_x() const { return count > 0 ? x[slot[count - 1]].p : nullptr; }
+
+private:
+    void drop_oldest(int drop);
+};
+
 // One level of the nested-dissection factors (dense.inc: sub_upload_level; include/tdgl_hip.h: tdgl_substructure).  The
 // first level works on the site vector (or a rank's interior), every further one on the previous level's separator.
 struct SubLevel {
@@ -525,20 +554,7 @@ struct tdgl_ctx {
     tdgl::DevBuf<double> mu_prev, mu_prev2;  // mu^{n-1}, mu^{n-2} for the extrapolated initial guess
     double prev_dt = 0.0, prev_dt2 = 0.0;    // dt of the steps that produced mu / mu_prev (0: no history)
     tdgl_poisson_options popt{1e-10, 500, 2, 0, 1, 1, 0.1, 3, 1, 2, 0, 0};
-    // projection guess (popt.extrapolate == 3): window of previous solutions x_j and their images
-    // y_j = A x_j (= b_j - r_j with the final residual of the CG recurrence), oldest first;
-    // g_G[i][j] = y_i . y_j in window order, kept on the host as double-double numbers (hi, lo)
-    tdgl::DevBuf<double> g_x[tdgl::GUESS_MAX], g_y[tdgl::GUESS_MAX];
-    int g_slot[tdgl::GUESS_MAX] = {0};
-    int g_count = 0;
-    bool g_row_pending = false;           // the newest vector's Gram row arrives with the next solve's first status block
-    bool mu_first_saved = false;          // mu_prev holds mu^n of a solve that started without a basis
-    double g_G[tdgl::GUESS_MAX][tdgl::GUESS_MAX][2] = {{{0}}};
-    double g_rhs[tdgl::GUESS_MAX][2] = {{0}};
-    double g_bb[2] = {0, 0};              // (b - mean) . (b - mean) of the right-hand side being solved
-    tdgl::DevBuf<double> part_gdot;       // 2 (2 GUESS_MAX + 2) x NB partials, see StepStatus::gdot
-    tdgl::DevBuf<double> d_gdot;          // their sums
-    tdgl::DevBuf<double> part_gdot_rank;  // one process per GPU: every rank's totals (kernels.inc: k_guess_rank_totals)
+    tdgl::GuessBasis guess;               // projection guess (popt.extrapolate == 3)
     // in-loop guard of the direct mu solves (run.inc: direct_guard_*): ||b - A mu|| / ||b|| of an accepted step,
     // measured with the resident level-0 matrix once per run-ahead batch / every DIRECT_GUARD_EVERY classic steps
     double direct_relres_max = 0.0;
