@@ -597,6 +597,25 @@ int tdgl_set_controller(tdgl_ctx *ctx, const tdgl_controller *c);
  * the arithmetic of the controller at solver.py:702-704; window == 0 averages the whole list like
  * Python's `vals[-0:]`.  No device work. */
 double tdgl_host_mean_tail(const double *values, int64_t n, int32_t window);
+/* Host-only: a scripted sequence of attempts -- attempt i changes |psi|^2 by at most dmax[i], or its psi update fails
+ * (fail[i] != 0) -- played through the time loop's rules from a fresh tdgl_set_controller(c): retry (solver.py:475-485),
+ * adaptive dt (solver.py:698-707), Runner.dt / time / step (runner.py:429-433).  mode 0: the loop with one
+ * synchronisation per step; mode 1: the run-ahead loop in batches of `batch` attempts (1 .. 64; adaptive_window 1 .. 128),
+ * with the controller the device runs.  The two must agree to the last bit.  c_next != NULL: the controller is replaced
+ * in front of attempt next_at (mode 1: a batch ends there).  The replay stops at the end of the script, at the step that
+ * reaches end_time or at a spent retry budget.  out_dt [n_attempts]: dt of the accepted steps; out_attempt_dt
+ * [n_attempts] (may be NULL): dt of every attempt played.  No device work. */
+typedef struct {
+    int64_t n_accepted, n_attempts; /* steps accepted; attempts played */
+    int64_t stage_step;
+    double time, tentative_dt, runner_dt;
+    double attempt_dt;              /* dt of the next attempt while retries > 0 */
+    double error_dt;                /* dt the error message of a spent retry budget reports */
+    int32_t retries, reached, error, pad;
+} tdgl_loop_replay;
+int tdgl_host_loop_replay(const tdgl_controller *c, double end_time, int64_t n_attempts, const double *dmax,
+                          const int32_t *fail, int32_t batch, int32_t mode, const tdgl_controller *c_next, int64_t next_at,
+                          double *out_dt, double *out_attempt_dt, tdgl_loop_replay *res);
 /* Host-only: the block low-rank compression of one B x B block A (row major) -- column-pivoted, reorthogonalised
  * Gram-Schmidt until the Frobenius norm of the remainder is <= tol; A ~ Q W^T with Q, W [kmax * B] column by column.
  * Returns the rank, or -1 when kmax columns do not reach tol (-2: bad arguments).  No device work. */

@@ -324,15 +324,8 @@ __global__ __launch_bounds__(BLOCK) void k_ens_eps_table(int64_t n_pad, const do
 }  // namespace tdgl
 
 struct EnsReplica {
-    tdgl_controller ctl{};
+    LoopState loop;  // controller, loop, retry and ramp state: the host's mirror of the replica's StepCtl
     bool have_ctl = false, have_links = false, have_eps = false, have_state = false, lap_valid = false;
-    double tentative_dt = 0.0, dt_cap = 0.0, runner_dt = 0.0, time = 0.0, attempt_dt = 0.0;
-    int64_t stage_step = 0;
-    int cur = 0, retries = 0;
-    std::vector<double> hist;  // d_psi_sq_vals (solver.py:318, 701), bounded like the context's
-    // field ramp A(t) = LinearRamp(t) A_base (tdgl_ensemble_set_link_ramp): the host's mirror of the device's
-    bool ramp_on = false, has_dadt = false;
-    double ramp_tmin = 0.0, ramp_tmax = 0.0, ramp_initial = 0.0, ramp_final = 0.0, link_scale = 0.0, link_scale_prev = 0.0;
     // tabulated terminal currents / separable epsilon (empty: none)
     std::vector<double> mu_t, mu_dens, eps_t, eps_f;
     std::vector<int32_t> mu_group;  // [nb]: table row of each boundary position, -1 where no table applies
@@ -538,7 +531,7 @@ extern "C" int tdgl_ensemble_set_link_exponents(tdgl_ensemble *e, int32_t r, con
     TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
     e->rep[r].have_links = true;
     e->rep[r].lap_valid = false;
-    e->rep[r].ramp_on = e->rep[r].has_dadt = false;
+    e->rep[r].loop.ramp_on = e->rep[r].loop.has_dadt = false;
     return TDGL_OK;
 }
 
@@ -566,7 +559,7 @@ extern "C" int tdgl_ensemble_set_link_ramp(tdgl_ensemble *e, int32_t r, const do
         e->dadt.take(dadt);
     }
     p.have_links = false;  // (until the replica's arrays are complete)
-    p.ramp_on = false;
+    p.loop.ramp_on = false;
     const double scale = linear_ramp_value(0.0, tmin, tmax, initial, final_);
     TDGL_TRY(tdgl_set_link_exponents_base(ctx, A_base, scale));  // (A = scale A_base, A_prev = A, links, Laplacian values)
     const int64_t o2 = 2 * (int64_t)r * e->m_pad;
@@ -576,10 +569,9 @@ extern "C" int tdgl_ensemble_set_link_ramp(tdgl_ensemble *e, int32_t r, const do
     HIP_TRY(ctx, hipMemset(e->dadt.p + r * e->m_pad, 0, e->m_pad * sizeof(double)));
     TDGL_TRY(ens_copy(ctx, e->U.p + r * e->m_pad, ctx->e_U.p, e->m_pad));
     TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
-    p.ramp_on = true;
-    p.has_dadt = false;
-    p.ramp_tmin = tmin, p.ramp_tmax = tmax, p.ramp_initial = initial, p.ramp_final = final_;
-    p.link_scale = p.link_scale_prev = scale;
+    p.loop.set_ramp(true, tmin, tmax, initial, final_);
+    p.loop.has_dadt = false;
+    p.loop.link_scale = p.loop.link_scale_prev = scale;
     p.have_links = true;
     p.lap_valid = false;
     return TDGL_OK;
@@ -588,7 +580,7 @@ extern "C" int tdgl_ensemble_set_link_ramp(tdgl_ensemble *e, int32_t r, const do
 extern "C" int tdgl_ensemble_get_link_scale(tdgl_ensemble *e, int32_t r, double *scale) {
     TDGL_TRY(ens_check(e, r));
     if (!scale) TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_link_scale: null scale");
-    *scale = e->rep[r].link_scale;
+    *scale = e->rep[r].loop.link_scale;
     return TDGL_OK;
 }
 
@@ -599,16 +591,7 @@ extern "C" int tdgl_ensemble_set_mu_boundary_table(tdgl_ensemble *e, int32_t r, 
     tdgl_ctx *ctx = e->ctx;
     EnsReplica &p = e->rep[r];
     if (n_nodes != 0) {
-        if (n_nodes < 1 || n_groups < 1 || !times || !group_ptr || !group_pos || !density || !table_times_ok(times, n_nodes))
-            TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: bad table (times must increase strictly)");
-        if (group_ptr[0] != 0) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: group_ptr must start at 0");
-        for (int32_t g = 0; g < n_groups; ++g)
-            if (group_ptr[g + 1] < group_ptr[g]) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: group_ptr decreases");
-        for (int32_t k = 0; k < group_ptr[n_groups]; ++k)
-            if (group_pos[k] < 0 || group_pos[k] >= ctx->nb)
-                TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: boundary position %d out of range", group_pos[k]);
-        for (int64_t k = 0; k < (int64_t)n_groups * n_nodes; ++k)
-            if (!std::isfinite(density[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary_table: non-finite density");
+        TDGL_TRY(check_mu_table(ctx, "tdgl_ensemble_set_mu_boundary_table", n_nodes, times, n_groups, group_ptr, group_pos, density));
         TDGL_TRY(ensure_boundary_sites(ctx));
         if (e->mu_b.n == 0) HIP_TRY(ctx, e->mu_b.alloc((size_t)e->R * std::max<int64_t>(ctx->nb, 1)));
         // solver.py:289, 323: mu_boundary and the densities start at 0; the table rewrites its positions
@@ -630,10 +613,7 @@ extern "C" int tdgl_ensemble_set_epsilon_table(tdgl_ensemble *e, int32_t r, cons
     tdgl_ctx *ctx = e->ctx;
     EnsReplica &p = e->rep[r];
     if (n_nodes != 0) {
-        if (n_nodes < 1 || !epsilon0 || !times || !factor || !table_times_ok(times, n_nodes))
-            TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_epsilon_table: bad table (times must increase strictly)");
-        for (int32_t k = 0; k < n_nodes; ++k)
-            if (!std::isfinite(factor[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_epsilon_table: non-finite factor");
+        TDGL_TRY(check_eps_table(ctx, "tdgl_ensemble_set_epsilon_table", epsilon0, n_nodes, times, factor));
         if (e->eps0.n == 0) HIP_TRY(ctx, e->eps0.alloc((size_t)e->R * e->n_pad));
         DevBuf<double> tmp;
         HIP_TRY(ctx, tmp.alloc(e->n_pad));
@@ -685,7 +665,7 @@ static int ens_upload_tables(tdgl_ensemble *e) {
 extern "C" int tdgl_ensemble_set_mu_boundary(tdgl_ensemble *e, int32_t r, const double *mu_boundary) {
     TDGL_TRY(ens_check(e, r));
     tdgl_ctx *ctx = e->ctx;
-    if (ctx->has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary: the context's links are time dependent");
+    if (ctx->loop.has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary: the context's links are time dependent");
     TDGL_TRY(tdgl_set_mu_boundary(ctx, mu_boundary));  // (static links: the boundary term as the run-ahead loop reads it)
     TDGL_TRY(ens_copy(ctx, e->ceff.p + r * e->n_pad, ctx->ceff.p, e->n_pad));
     TDGL_TRY(ens_copy(ctx, e->cvec.p + r * e->n_pad, ctx->cvec.p, e->n_pad));  // (a ramp adds its dA/dt term to this)
@@ -706,9 +686,8 @@ extern "C" int tdgl_ensemble_set_state(tdgl_ensemble *e, int32_t r, const double
     tdgl_ctx *ctx = e->ctx;
     TDGL_TRY(tdgl_set_state(ctx, psi, mu));
     EnsReplica &p = e->rep[r];
-    p.cur = 0;
-    p.retries = 0;
-    TDGL_TRY(ens_copy(ctx, e->psi0.p + r * e->n_pad, ctx->psi[ctx->cur].p, e->n_pad));
+    p.loop.new_state(0);
+    TDGL_TRY(ens_copy(ctx, e->psi0.p + r * e->n_pad, ctx->psi[ctx->loop.cur].p, e->n_pad));
     TDGL_TRY(ens_copy(ctx, e->mu.p + r * e->n_pad, ctx->mu.p, e->n_pad));
     p.have_state = true;
     p.lap_valid = false;
@@ -723,16 +702,8 @@ extern "C" int tdgl_ensemble_set_controller(tdgl_ensemble *e, int32_t r, const t
         TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "adaptive_time_step_multiplier must be in (0, 1) (got %g).", c->adaptive_time_step_multiplier);
     if (c->adaptive && (c->adaptive_window < 1 || c->adaptive_window > RA_HIST_MAX))
         TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "ensemble: adaptive_window must be in [1, %d] (got %d)", RA_HIST_MAX, c->adaptive_window);
-    EnsReplica &p = e->rep[r];
-    p.ctl = *c;  // (tdgl_set_controller's resets: solver.py:316-320, runner.py:262)
-    p.tentative_dt = c->dt_init;
-    p.dt_cap = c->adaptive ? c->dt_max : c->dt_init;
-    p.hist.clear();
-    p.runner_dt = c->dt_init;
-    p.time = 0.0;
-    p.stage_step = 0;
-    p.retries = 0;
-    p.have_ctl = true;
+    e->rep[r].loop.reset(*c);
+    e->rep[r].have_ctl = true;
     return TDGL_OK;
 }
 
@@ -752,19 +723,14 @@ extern "C" int tdgl_ensemble_set_probes(tdgl_ensemble *e, const int32_t *sites, 
 
 extern "C" int tdgl_ensemble_begin_stage(tdgl_ensemble *e, int32_t r) {
     TDGL_TRY(ens_check(e, r));
-    e->rep[r].time = 0.0;      // runner.py:294, 315
-    e->rep[r].stage_step = 0;  // runner.py:295, 316
+    e->rep[r].loop.begin_stage();
     return TDGL_OK;
 }
 
 extern "C" int tdgl_ensemble_get_loop_state(tdgl_ensemble *e, int32_t r, int64_t *step, double *time, double *runner_dt,
                                             double *tentative_dt) {
     TDGL_TRY(ens_check(e, r));
-    const EnsReplica &p = e->rep[r];
-    if (step) *step = p.stage_step;
-    if (time) *time = p.time;
-    if (runner_dt) *runner_dt = p.runner_dt;
-    if (tentative_dt) *tentative_dt = p.tentative_dt;
+    e->rep[r].loop.report(step, time, runner_dt, tentative_dt);
     return TDGL_OK;
 }
 
@@ -776,41 +742,28 @@ extern "C" int tdgl_ensemble_get_state(tdgl_ensemble *e, int32_t r, double *psi,
     tdgl_ctx *ctx = e->ctx;
     const EnsReplica &p = e->rep[r];
     if (!p.have_state || !p.have_links) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_get_state: replica %d has no state or links", r);
-    if (ctx->has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_state: the context's links are time dependent");
-    TDGL_TRY(ens_copy(ctx, ctx->psi[ctx->cur].p, (p.cur ? e->psi1.p : e->psi0.p) + r * e->n_pad, e->n_pad));
+    if (ctx->loop.has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_state: the context's links are time dependent");
+    TDGL_TRY(ens_copy(ctx, ctx->psi[ctx->loop.cur].p, (p.loop.cur ? e->psi1.p : e->psi0.p) + r * e->n_pad, e->n_pad));
     TDGL_TRY(ens_copy(ctx, ctx->mu.p, e->mu.p + r * e->n_pad, e->n_pad));
     TDGL_TRY(ens_copy(ctx, ctx->e_U.p, e->U.p + r * e->m_pad, e->m_pad));
     // a ramping replica: J_n with its dA/dt -- that of the step that produced psi (the next step's ramp moves at the
     // start of its first attempt, in the next tdgl_ensemble_run)
-    const bool dadt = p.ramp_on && p.has_dadt;
+    const bool dadt = p.loop.ramp_on && p.loop.has_dadt;
     if (dadt) TDGL_TRY(ens_copy(ctx, ctx->e_dAdt.p, e->dadt.p + r * e->m_pad, e->m_pad));
     ctx->have_state = true;
     ctx->lap_valid = false;  // (the context's Laplacian values belong to whatever links it was last given)
     ctx->currents_valid = false;
     ctx->currents_deferred = false;
-    ctx->has_dadt = dadt;
+    ctx->loop.has_dadt = dadt;
     const int status = tdgl_get_state(ctx, psi, mu, supercurrent, normal_current);
-    ctx->has_dadt = false;  // (the context's own links are static)
+    ctx->loop.has_dadt = false;  // (the context's own links are static)
     return status;
 }
 
 static void ens_launch_laplacian_cache(tdgl_ensemble *e, int r) {
-    tdgl_ctx *ctx = e->ctx;
-    const SellPattern &pat = ctx->lap_pat;
-    const int tiles = (pat.n_slices + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-    const int per_xcd = (tiles + XCDS - 1) / XCDS, grid = per_xcd * XCDS;
-    const EnsReplica &p = e->rep[r];
-    const double2 *psi = (p.cur ? e->psi1.p : e->psi0.p) + r * e->n_pad;
-    double2 *lap = (p.cur ? e->lap1.p : e->lap0.p) + r * e->n_pad;
-    const double2 *vals = e->lapv.p + r * e->n_slots;
-    if (pat.use16)
-        hipLaunchKernelGGL((k_psi_laplacian<false, int16_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, 0, pat.n_rows,
-                           pat.slice_off.p, pat.cols16.p, vals, ctx->lap_diag.p, ctx->fixed_mask.p, psi, lap, (const double *)nullptr,
-                           (const double *)nullptr, (double *)nullptr);
-    else
-        hipLaunchKernelGGL((k_psi_laplacian<false, int32_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, 0, pat.n_rows,
-                           pat.slice_off.p, pat.cols.p, vals, ctx->lap_diag.p, ctx->fixed_mask.p, psi, lap, (const double *)nullptr,
-                           (const double *)nullptr, (double *)nullptr);
+    const bool c1 = e->rep[r].loop.cur != 0;
+    launch_psi_laplacian(e->ctx, false, (c1 ? e->psi1.p : e->psi0.p) + r * e->n_pad, (c1 ? e->lap1.p : e->lap0.p) + r * e->n_pad, 0,
+                         e->lapv.p + r * e->n_slots);
 }
 
 // the time-dependent inputs of the round's attempts (T1, T2, R1 - R5), in the single run's order (run.inc: run_ahead)
@@ -970,7 +923,6 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
     HIP_TRY(ctx, hipGetLastError());
     int err_replica = -1;
     double err_dt = 0.0;
-    int64_t err_step = 0;
     for (;;) {
         int active = 0, n_ramping = 0;
         for (int r = 0; r < R; ++r) {
@@ -978,36 +930,11 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
             const bool on = !reached_end[r] && steps_done[r] < max_steps[r];
             active += on;
             // a ramp that has reached its end: dA/dt is identically zero from here on, and a replica whose ramp has
-            // settled costs what a static one does (run.inc: tdgl_run, ramp_settled)
-            const bool settled = p.ramp_on && p.time >= p.ramp_tmax && p.link_scale == p.ramp_final && p.link_scale_prev == p.ramp_final;
-            if (settled) p.has_dadt = false;
-            e->h_ramping[r] = on && p.ramp_on && !settled;
+            // settled costs what a static one does (as in tdgl_run)
+            if (p.loop.ramp_settled()) p.loop.has_dadt = false;
+            e->h_ramping[r] = on && p.loop.ramping();
             n_ramping += e->h_ramping[r];
-            StepCtl &h = e->h_ctl[r];
-            memset(&h, 0, sizeof(h));
-            h.tentative_dt = p.tentative_dt;
-            h.attempt_dt = p.retries > 0 ? p.attempt_dt : p.tentative_dt;
-            h.time = p.time;
-            h.end_time = end_time[r];
-            h.dt_init = p.ctl.dt_init;
-            h.dt_cap = p.dt_cap;
-            h.multiplier = p.ctl.adaptive_time_step_multiplier;
-            h.stage_step = p.stage_step;
-            h.adaptive = p.ctl.adaptive;
-            h.window = p.ctl.adaptive_window;
-            h.max_retries = p.ctl.max_solve_retries;
-            h.cur = p.cur;
-            h.retries = p.retries;
-            h.poisoned = on ? 0 : 1;
-            h.runner_dt = p.runner_dt;
-            h.ramp_tmin = p.ramp_tmin, h.ramp_tmax = p.ramp_tmax, h.ramp_initial = p.ramp_initial, h.ramp_final = p.ramp_final;
-            h.link_scale = p.link_scale, h.link_scale_prev = p.link_scale_prev;
-            h.has_dadt = p.has_dadt ? 1 : 0;
-            if (p.ctl.adaptive) {
-                const int64_t have = (int64_t)p.hist.size(), cnt = std::min<int64_t>(have, p.ctl.adaptive_window);
-                h.hist_count = (int)cnt;
-                for (int64_t i = 0; i < cnt; ++i) h.hist[i] = p.hist[have - cnt + i];
-            }
+            p.loop.fill(e->h_ctl[r], end_time[r], on);
             e->h_limit[r] = on ? (int32_t)std::min<int64_t>(max_steps[r] - steps_done[r], RA_BATCH_MAX) : 0;
         }
         if (active == 0 || err_replica >= 0) break;
@@ -1030,22 +957,12 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
             EnsReplica &p = e->rep[r];
             const StepCtl &h = e->h_ctl[r];
             const StepRec *rec = e->h_rec.data() + (size_t)r * RA_BATCH_MAX;
-            const int done = h.n_done;
-            if (done < 0 || done > batch || h.n_acc < 0 || h.n_acc > done || h.n_acc > e->h_limit[r])
-                TDGL_FAIL(ctx, TDGL_ERR_HIP, "ensemble: corrupt attempt records of replica %d (%d processed, %d accepted of %d)", r, done,
-                          h.n_acc, batch);
-            int acc = 0;
-            double last_fail_dt = 0.0;
-            double *dts = out_dt + (size_t)r * capacity + steps_done[r];
-            for (int s = 0; s < done; ++s) {
-                if (!rec[s].ok) {
-                    last_fail_dt = rec[s].dt;
-                    continue;
-                }
-                dts[acc++] = rec[s].dt;
-                if (p.ctl.adaptive) p.hist.push_back(rec[s].dmax);
-            }
-            if (acc != h.n_acc) TDGL_FAIL(ctx, TDGL_ERR_HIP, "ensemble: replica %d's records disagree with its controller", r);
+            const LoopState::Batch b = p.loop.absorb(h, rec, batch, e->h_limit[r], e->h_ramping[r] != 0,
+                                                     out_dt + (size_t)r * capacity + steps_done[r]);
+            if (b.corrupt)
+                TDGL_FAIL(ctx, TDGL_ERR_HIP, "ensemble: corrupt attempt records of replica %d (%d processed, %d accepted of %d; check %d)", r,
+                          h.n_done, h.n_acc, batch, b.corrupt);
+            const int acc = b.accepted;
             if (np_ > 0)
                 for (int k = 0; k < acc; ++k) {
                     const double *row = e->h_probe.data() + ((size_t)r * RA_BATCH_MAX + k) * 2 * np_;
@@ -1053,42 +970,20 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
                     if (out_mu_probe) memcpy(out_mu_probe + at, row, np_ * sizeof(double));
                     if (out_theta_probe) memcpy(out_theta_probe + at, row + np_, np_ * sizeof(double));
                 }
-            const bool reached = h.reached_end != 0;
-            if (acc > 0) {
-                const int last = reached ? acc - 2 : acc - 1;  // (Runner.dt is not touched by the step that reached end_time)
-                if (last >= 0) p.runner_dt = dts[last];
-            }
-            if (e->h_ramping[r]) {
-                p.link_scale = h.link_scale;
-                p.link_scale_prev = h.link_scale_prev;
-                p.has_dadt = h.has_dadt != 0;
-            }
-            p.cur = h.cur;
-            p.retries = h.error ? 0 : h.retries;
-            p.attempt_dt = h.attempt_dt;
-            p.tentative_dt = h.tentative_dt;
-            p.time = h.time;
-            p.stage_step = h.stage_step;
-            if (p.ctl.adaptive && (int64_t)p.hist.size() > 4 * (int64_t)p.ctl.adaptive_window + 64)
-                p.hist.erase(p.hist.begin(), p.hist.end() - p.ctl.adaptive_window);
             steps_done[r] += acc;
-            if (reached) reached_end[r] = 1;
-            if (h.error) {
+            if (b.reached) reached_end[r] = 1;
+            if (b.error) {
                 if (failed) failed[r] = 1;
                 if (err_replica < 0) {
                     err_replica = r;
-                    err_dt = last_fail_dt;
-                    err_step = p.stage_step;
+                    err_dt = b.last_fail_dt;
                 }
             }
         }
         e->batch = std::min(2 * batch, RA_BATCH_MAX);
     }
-    if (err_replica >= 0)
-        TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES,
-                  "replica %d: Solver failed to converge in %d retries at step %lld with dt = %.2e."
-                  " Try using a smaller dt_init.",
-                  err_replica, e->rep[err_replica].ctl.max_solve_retries, (long long)err_step, err_dt);
+    if (err_replica >= 0)  // (the replica has stopped at the step that failed)
+        TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES, "%s", e->rep[err_replica].loop.budget_message(err_replica, err_dt).c_str());
     return TDGL_OK;
 }
 

@@ -433,7 +433,7 @@ __global__ __launch_bounds__(BLOCK) void k_psi_update_with_currents(
 // to the last bit.
 // tdgl/sources/scaling.py:4-14, branch for branch and operation for operation (`initial` before tmin, `final` from
 // tmax on -- exactly, whatever the two values are --, Python's left-to-right product and quotient in between); host
-// and device evaluate THIS, so the two time loops agree to the last bit and `ramp_settled` (run.inc) can test equality
+// and device evaluate THIS, so the two time loops agree to the last bit and `LoopState::ramp_settled` can test equality
 __host__ __device__ inline double linear_ramp_value(double t, double tmin, double tmax, double initial, double final_) {
 #pragma clang fp contract(off)
     if (t < tmin) return initial;
@@ -2145,8 +2145,8 @@ __global__ __launch_bounds__(BLOCK) void k_publish_status(StepStatus *__restrict
     }
 }
 
-// numpy's pairwise summation for fewer than 129 terms (run.inc: numpy_pairwise_sum), on the device
-__device__ __forceinline__ double numpy_sum_le128(const double *a, int n) {
+// numpy's pairwise summation for fewer than 129 terms (loop.inc: numpy_pairwise_sum), on the device and in the host replay
+__host__ __device__ __forceinline__ double numpy_sum_le128(const double *a, int n) {
     if (n < 8) {
         double res = 0.0;
         for (int i = 0; i < n; ++i) res += a[i];
@@ -2175,7 +2175,7 @@ static_assert(offsetof(StepCtl, hist) == sizeof(StepCtlHead), "StepCtlHead mirro
 // One thread: the bookkeeping of an attempt in the run-ahead time loop -- what step_once's retry loop,
 // step_finish and tdgl_run do on the host in the classic loop (solver.py:475-485, 698-707,
 // runner.py:429-433), in the same arithmetic and order.
-__device__ __forceinline__ void step_controller(StepCtl *__restrict__ ctl, StepRec *__restrict__ rec, double dmax, int fail) {
+__host__ __device__ __forceinline__ void step_controller(StepCtl *__restrict__ ctl, StepRec *__restrict__ rec, double dmax, int fail) {
     const StepCtlHead h = *reinterpret_cast<const StepCtlHead *>(ctl);
     if (!h.live) return;
     if (h.n_done >= RA_BATCH_MAX) {  // (the host never queues more: the record array has RA_BATCH_MAX slots)

@@ -1,0 +1,249 @@
+// LoopState (tdgl_internal.h): the time loop's rules on the host -- retry (solver.py:475-485), adaptive dt (solver.py:698-707),
+// Runner.dt / time / step (runner.py:429-433) --, once for the classic, the run-ahead and the ensemble loop.  Plain host C++:
+// nothing here touches the device, so the rules can be replayed without one (tdgl_host_loop_replay).  Included by tdgl_hip.hip.
+
+// numpy's pairwise summation (numpy/core/src/umath/loops_utils.h.src, pairwise_sum): a plain
+// left-to-right sum below 8 elements, an 8-accumulator unrolled loop up to 128, and a recursive
+// split (left half rounded down to a multiple of 8) above.
+static double numpy_pairwise_sum(const double *a, int64_t n) {
+    if (n < 8) {
+        double res = 0.0;
+        for (int64_t i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    if (n <= 128) {
+        double r[8];
+        for (int k = 0; k < 8; ++k) r[k] = a[k];
+        int64_t i = 8;
+        for (; i < n - (n % 8); i += 8)
+            for (int k = 0; k < 8; ++k) r[k] += a[i + k];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += a[i];
+        return res;
+    }
+    int64_t n2 = n / 2;
+    n2 -= n2 % 8;
+    return numpy_pairwise_sum(a, n2) + numpy_pairwise_sum(a + n2, n - n2);
+}
+
+// np.mean(d_psi_sq_vals[-window:]) of a Python list (solver.py:702-704).  window == 0 selects the
+// WHOLE list in Python (`vals[-0:]`), reproduced.
+static double numpy_mean_tail(const std::vector<double> &v, int window) {
+    const int64_t cnt = window > 0 ? std::min<int64_t>(window, (int64_t)v.size()) : (int64_t)v.size();
+    return numpy_pairwise_sum(v.data() + (v.size() - cnt), cnt) / (double)cnt;
+}
+
+// host-only helper behind the controller, exported so that the summation order can be pinned
+// against numpy on any machine (tests/test_host_logic.py)
+extern "C" double tdgl_host_mean_tail(const double *values, int64_t n, int32_t window) {
+    if (!values || n <= 0) return 0.0;
+    return numpy_mean_tail(std::vector<double>(values, values + n), window);
+}
+
+namespace tdgl {
+
+// the reference's error of a spent retry budget at this step (solver.py:480-484); replica >= 0: its index in front
+std::string LoopState::budget_message(int replica, double dt) const {
+    char buf[256];
+    const int at = replica >= 0 ? snprintf(buf, sizeof(buf), "replica %d: ", replica) : 0;
+    snprintf(buf + at, sizeof(buf) - at, "Solver failed to converge in %d retries at step %lld with dt = %.2e. Try using a smaller dt_init.",
+             ctl.max_solve_retries, (long long)stage_step, dt);
+    return buf;
+}
+
+// tdgl_set_controller / tdgl_ensemble_set_controller: solver.py:316-320, runner.py:262; a step's pending retries
+// belonged to the previous controller
+void LoopState::reset(const tdgl_controller &c) {
+    ctl = c;
+    tentative_dt = attempt_dt = c.dt_init;           // solver.py:319
+    dt_cap = c.adaptive ? c.dt_max : c.dt_init;      // solver.py:320
+    hist.clear();                                    // solver.py:318
+    runner_dt = c.dt_init;                           // runner.py:262
+    time = 0.0;
+    stage_step = 0;
+    retries = 0;
+}
+
+// tdgl_get_loop_state / tdgl_ensemble_get_loop_state: every output is optional
+void LoopState::report(int64_t *step, double *time_, double *runner_dt_, double *tentative) const {
+    if (step) *step = stage_step;
+    if (time_) *time_ = time;
+    if (runner_dt_) *runner_dt_ = runner_dt;
+    if (tentative) *tentative = tentative_dt;
+}
+
+// solver.py:475-485 after a failed psi update: false -- the budget is spent (attempt_dt stays the dt that failed) --, or
+// attempt_dt shrinks for the next attempt
+bool LoopState::retry() {
+    if (!ctl.adaptive || retries > ctl.max_solve_retries) {
+        retries = 0;
+        return false;
+    }
+    attempt_dt *= ctl.adaptive_time_step_multiplier;
+    retries += 1;
+    return true;
+}
+
+// the adaptive time-step controller after an accepted step (solver.py:698-707)
+void LoopState::accept(double dt, double dmax) {
+    retries = 0;
+    if (ctl.adaptive) {
+        hist.push_back(dmax);
+        if (stage_step > ctl.adaptive_window) {
+            const double mean = numpy_mean_tail(hist, ctl.adaptive_window);
+            const double new_dt = ctl.dt_init / std::max(1e-10, mean);
+            tentative_dt = std::min(std::max(0.5 * (new_dt + dt), 0.0), dt_cap);
+        }
+        trim();
+    }
+    attempt_dt = tentative_dt;
+}
+
+// runner.py:429-433: true -- the step reached end_time (tested before time advances; Runner.dt is not touched)
+bool LoopState::advance(double dt, double end_time) {
+    if (time >= end_time) return true;
+    runner_dt = dt;
+    time += runner_dt;
+    stage_step += 1;
+    return false;
+}
+
+// the device's controller at the start of a batch; live = false: poisoned from the first attempt on
+void LoopState::fill(StepCtl &h, double end_time, bool live) const {
+    memset(&h, 0, sizeof(h));
+    h.tentative_dt = tentative_dt;
+    h.attempt_dt = retries > 0 ? attempt_dt : tentative_dt;  // (the previous batch ended in the middle of a step's retries)
+    h.time = time;
+    h.end_time = end_time;
+    h.dt_init = ctl.dt_init;
+    h.dt_cap = dt_cap;
+    h.multiplier = ctl.adaptive_time_step_multiplier;
+    h.stage_step = stage_step;
+    h.adaptive = ctl.adaptive;
+    h.window = ctl.adaptive_window;
+    h.max_retries = ctl.max_solve_retries;
+    h.cur = cur;
+    h.retries = retries;
+    h.poisoned = live ? 0 : 1;
+    h.runner_dt = runner_dt;
+    h.ramp_tmin = ramp_tmin, h.ramp_tmax = ramp_tmax, h.ramp_initial = ramp_initial, h.ramp_final = ramp_final;
+    h.link_scale = link_scale, h.link_scale_prev = link_scale_prev;
+    h.has_dadt = has_dadt ? 1 : 0;
+    if (ctl.adaptive) {
+        const int64_t have = (int64_t)hist.size(), cnt = std::min<int64_t>(have, ctl.adaptive_window);
+        h.hist_count = (int)cnt;
+        for (int64_t i = 0; i < cnt; ++i) h.hist[i] = hist[have - cnt + i];
+    }
+}
+
+// The host's mirror after a batch of `batch` attempts of which at most `limit` may have been accepted: the accepted
+// steps' dt to out_dt, their max d|psi|^2 to the history, the controller's state.  ramped: the batch evaluated the ramp.
+LoopState::Batch LoopState::absorb(const StepCtl &h, const StepRec *rec, int batch, int limit, bool ramped, double *out_dt) {
+    Batch b;
+    const int done = h.n_done;
+    if (done < 0 || done > batch || h.n_acc < 0 || h.n_acc > done || h.n_acc > limit) {
+        b.corrupt = 1;
+        return b;
+    }
+    for (int s = 0; s < done; ++s) {
+        if (!rec[s].ok) {
+            b.failed += 1;
+            b.last_fail_dt = rec[s].dt;
+            continue;
+        }
+        out_dt[b.accepted++] = rec[s].dt;
+        b.last_accepted = s;
+        if (ctl.adaptive) hist.push_back(rec[s].dmax);
+    }
+    if (b.accepted != h.n_acc) {
+        b.corrupt = 2;
+        return b;
+    }
+    b.reached = h.reached_end != 0;
+    b.error = h.error != 0;
+    if (ramped) {
+        link_scale = h.link_scale;
+        link_scale_prev = h.link_scale_prev;
+        has_dadt = h.has_dadt != 0;
+    }
+    cur = h.cur;
+    retries = b.error ? 0 : h.retries;
+    attempt_dt = h.attempt_dt;
+    tentative_dt = h.tentative_dt;
+    time = h.time;
+    stage_step = h.stage_step;
+    // Runner.dt (runner.py:431) is not touched by the step that reached end_time (the loop breaks before)
+    const int last = b.reached ? b.accepted - 2 : b.accepted - 1;
+    if (last >= 0) runner_dt = out_dt[last];
+    trim();
+    return b;
+}
+
+}  // namespace tdgl
+
+// Host-only: a scripted sequence of attempts through the loop's rules, see include/tdgl_hip.h
+extern "C" int tdgl_host_loop_replay(const tdgl_controller *c, double end_time, int64_t n_attempts, const double *dmax,
+                                     const int32_t *fail, int32_t batch, int32_t mode, const tdgl_controller *c_next,
+                                     int64_t next_at, double *out_dt, double *out_attempt_dt, tdgl_loop_replay *res) {
+    using namespace tdgl;
+    if (!c || n_attempts < 0 || (n_attempts > 0 && (!dmax || !fail || !out_dt)) || !res || (mode != 0 && mode != 1)) return TDGL_ERR_ARG;
+    if (mode == 1 && (batch < 1 || batch > RA_BATCH_MAX)) return TDGL_ERR_ARG;
+    for (const tdgl_controller *k : {c, c_next})  // (the device's history holds RA_HIST_MAX values)
+        if (k && mode == 1 && k->adaptive && (k->adaptive_window < 1 || k->adaptive_window > RA_HIST_MAX)) return TDGL_ERR_ARG;
+    LoopState L;
+    L.reset(*c);
+    *res = tdgl_loop_replay{};
+    int64_t i = 0, acc = 0;
+    bool stop = false;
+    while (i < n_attempts && !stop) {
+        if (c_next && i == next_at) L.reset(*c_next);
+        if (mode == 0) {  // the classic loop: step_once / step_finish / tdgl_run, one attempt per turn
+            const double dt = L.retries > 0 ? L.attempt_dt : L.begin_step();
+            if (out_attempt_dt) out_attempt_dt[i] = dt;
+            const bool failed = fail[i] != 0;
+            const double d = dmax[i];
+            ++i;
+            if (failed) {
+                if (L.retry()) continue;
+                res->error = 1;
+                res->error_dt = dt;
+                break;
+            }
+            L.accept(dt, d);
+            out_dt[acc++] = dt;
+            if (L.advance(dt, end_time)) {
+                res->reached = 1;
+                break;
+            }
+            continue;
+        }
+        // the run-ahead loop: a batch of attempts behind one fill, the device's controller per attempt, one absorb
+        int64_t room = n_attempts - i;
+        if (c_next && i < next_at) room = std::min(room, next_at - i);
+        const int nb = (int)std::min<int64_t>(batch, room);
+        StepCtl h;
+        StepRec rec[RA_BATCH_MAX];
+        L.fill(h, end_time, true);
+        for (int s = 0; s < nb; ++s) {
+            h.live = h.poisoned ? 0 : 1;  // (k_ra_psi_update: not poisoned when the attempt begins)
+            if (h.live && out_attempt_dt) out_attempt_dt[i + h.n_done] = h.attempt_dt;
+            step_controller(&h, rec, dmax[i + h.n_done], fail[i + h.n_done]);
+        }
+        const LoopState::Batch b = L.absorb(h, rec, nb, nb, false, out_dt + acc);
+        if (b.corrupt) return TDGL_ERR_HIP;
+        i += h.n_done;
+        acc += b.accepted;
+        if (b.error) res->error = 1, res->error_dt = b.last_fail_dt;
+        if (b.reached) res->reached = 1;
+        stop = b.error || b.reached;
+    }
+    res->n_accepted = acc;
+    res->n_attempts = i;
+    res->stage_step = L.stage_step;
+    res->time = L.time;
+    res->tentative_dt = L.tentative_dt;
+    res->runner_dt = L.runner_dt;
+    res->attempt_dt = L.attempt_dt;
+    res->retries = L.retries;
+    return TDGL_OK;
+}

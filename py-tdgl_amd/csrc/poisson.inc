@@ -1280,7 +1280,7 @@ static int direct_mu_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, b
     const bool status_done = direct_solve_launch(ctx, b, x, in_step, nullptr, nullptr);
     ctx->spec_currents_done = false;
     if (in_step && ctx->spec_currents) {
-        launch_edge_currents(ctx, ctx->psi[1 - ctx->cur].p, x, ctx->js.p, ctx->jn.p);
+        launch_edge_currents(ctx, ctx->psi[1 - ctx->loop.cur].p, x, ctx->js.p, ctx->jn.p);
         ctx->spec_currents_done = true;
     }
     const double *rr_part = nullptr;

@@ -16,8 +16,7 @@
 
 extern "C" int tdgl_begin_stage(tdgl_ctx *ctx) {
     if (!ctx) return TDGL_ERR_ARG;
-    ctx->time = 0.0;      // runner.py:294, 315
-    ctx->stage_step = 0;  // runner.py:295, 316
+    ctx->loop.begin_stage();
     direct_policy_reset(ctx);
     return TDGL_OK;
 }
@@ -40,23 +39,16 @@ extern "C" int tdgl_get_step_stats(tdgl_ctx *ctx, int64_t *out6, int32_t reset) 
     return TDGL_OK;
 }
 
-
-
 extern "C" int tdgl_get_loop_state(tdgl_ctx *ctx, int64_t *step, double *time, double *runner_dt,
                                    double *tentative_dt) {
     if (!ctx) return TDGL_ERR_ARG;
-    if (step) *step = ctx->stage_step;
-    if (time) *time = ctx->time;
-    if (runner_dt) *runner_dt = ctx->runner_dt;
-    if (tentative_dt) *tentative_dt = ctx->tentative_dt;
+    ctx->loop.report(step, time, runner_dt, tentative_dt);
     return TDGL_OK;
 }
 
 extern "C" int tdgl_set_loop_state(tdgl_ctx *ctx, int64_t step, double time, double runner_dt) {
     if (!ctx) return TDGL_ERR_ARG;
-    ctx->stage_step = step;
-    ctx->time = time;
-    ctx->runner_dt = runner_dt;
+    ctx->loop.restore(step, time, runner_dt);
     return TDGL_OK;
 }
 
@@ -66,10 +58,10 @@ extern "C" int tdgl_set_loop_state(tdgl_ctx *ctx, int64_t step, double time, dou
 extern "C" int tdgl_get_controller_state(tdgl_ctx *ctx, double *tentative_dt, double *history, int64_t capacity,
                                          int64_t *n_history) {
     if (!ctx || capacity < 0 || (capacity > 0 && !history)) return TDGL_ERR_ARG;
-    if (tentative_dt) *tentative_dt = ctx->tentative_dt;
-    const int64_t have = (int64_t)ctx->d_psi_sq_vals.size(), k = std::min(have, capacity);
+    if (tentative_dt) *tentative_dt = ctx->loop.tentative_dt;
+    const int64_t have = (int64_t)ctx->loop.hist.size(), k = std::min(have, capacity);
     // the newest `k` entries, oldest first
-    for (int64_t i = 0; i < k; ++i) history[i] = ctx->d_psi_sq_vals[have - k + i];
+    for (int64_t i = 0; i < k; ++i) history[i] = ctx->loop.hist[have - k + i];
     if (n_history) *n_history = have;
     return TDGL_OK;
 }
@@ -78,9 +70,7 @@ extern "C" int tdgl_set_controller_state(tdgl_ctx *ctx, double tentative_dt, con
     if (!ctx || n_history < 0 || (n_history > 0 && !history)) return TDGL_ERR_ARG;
     if (!(tentative_dt > 0.0) || !std::isfinite(tentative_dt))
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_controller_state: tentative_dt must be positive and finite (got %g)", tentative_dt);
-    ctx->tentative_dt = tentative_dt;
-    ctx->ra_retries = 0;
-    ctx->d_psi_sq_vals.assign(history, history + n_history);
+    ctx->loop.restore_controller(tentative_dt, history, n_history);
     return TDGL_OK;
 }
 
@@ -133,47 +123,9 @@ static void direct_policy(tdgl_ctx *ctx) {
     ctx->direct_switch_steps = 0;
 }
 
-// numpy's pairwise summation (numpy/core/src/umath/loops_utils.h.src, pairwise_sum): a plain
-// left-to-right sum below 8 elements, an 8-accumulator unrolled loop up to 128, and a recursive
-// split (left half rounded down to a multiple of 8) above.
-static double numpy_pairwise_sum(const double *a, int64_t n) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int64_t i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    if (n <= 128) {
-        double r[8];
-        for (int k = 0; k < 8; ++k) r[k] = a[k];
-        int64_t i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int k = 0; k < 8; ++k) r[k] += a[i + k];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; ++i) res += a[i];
-        return res;
-    }
-    int64_t n2 = n / 2;
-    n2 -= n2 % 8;
-    return numpy_pairwise_sum(a, n2) + numpy_pairwise_sum(a + n2, n - n2);
-}
-
-// np.mean(d_psi_sq_vals[-window:]) of a Python list (solver.py:702-704).  window == 0 selects the
-// WHOLE list in Python (`vals[-0:]`), reproduced.
-static double numpy_mean_tail(const std::vector<double> &v, int window) {
-    const int64_t cnt = window > 0 ? std::min<int64_t>(window, (int64_t)v.size()) : (int64_t)v.size();
-    return numpy_pairwise_sum(v.data() + (v.size() - cnt), cnt) / (double)cnt;
-}
-
-// host-only helper behind the controller, exported so that the summation order can be pinned
-// against numpy on any machine (tests/test_host_logic.py)
-extern "C" double tdgl_host_mean_tail(const double *values, int64_t n, int32_t window) {
-    if (!values || n <= 0) return 0.0;
-    return numpy_mean_tail(std::vector<double>(values, values + n), window);
-}
-
 static int ensure_laplacian_cache(tdgl_ctx *ctx) {
     if (ctx->lap_valid) return TDGL_OK;
-    launch_psi_laplacian(ctx, false, ctx->psi[ctx->cur].p, ctx->lap[ctx->cur].p);
+    launch_psi_laplacian(ctx, false, ctx->psi[ctx->loop.cur].p, ctx->lap[ctx->loop.cur].p);
     HIP_TRY(ctx, hipGetLastError());
     ctx->lap_valid = true;
     return TDGL_OK;
@@ -204,7 +156,6 @@ static int probe_ring_flush(tdgl_ctx *ctx, int64_t first_row, double *out_mu, do
 // One call of TDGLSolver.update.
 static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *probe_theta,
                      int32_t *pcg_iters) {
-    const tdgl_controller &ctl = ctx->ctl;
     if (!ctx->have_links || !ctx->have_state || !ctx->have_eps)
         TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_run: set link exponents, epsilon and state first");
     if (ctx->scr_enabled) {
@@ -213,9 +164,8 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
         return step_finish(ctx, dt_s, dmax_s, dt_used, probe_mu, probe_theta, pcg_iters);
     }
     TDGL_TRY(ensure_laplacian_cache(ctx));
-    ctx->ra_retries = 0;  // (a step begun by the run-ahead loop and continued here starts its retries over)
-    double dt = ctx->tentative_dt;  // solver.py:666-668
-    const int cur = ctx->cur, nxt = 1 - cur;
+    double dt = ctx->loop.begin_step();  // solver.py:666-668
+    const int cur = ctx->loop.cur, nxt = 1 - cur;
     double dmax = 0.0;
     // (extrapolate == 3: the guess is the projection onto the previous solutions, formed inside
     // pcg_solve after the psi update is known to have succeeded -- mu^n stays in place until then)
@@ -224,8 +174,8 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
     // Direct solve (launch-bound sizes) with static link variables: the edge currents of an accepted step
     // are not launched on their own but ride in the NEXT step's psi-update launch (same inputs: the
     // accepted psi and mu), or are formed when tdgl_run returns -- one launch less per step.
-    const bool defer_currents = dense_on(ctx) && ctx->popt.edge_currents_every_step != 0 && !ctx->ramp_on && !ctx->has_dadt;
-    for (int retries = 0;; ++retries) {
+    const bool defer_currents = dense_on(ctx) && ctx->popt.edge_currents_every_step != 0 && !ctx->loop.ramp_on && !ctx->loop.has_dadt;
+    for (bool first = true;; first = false) {
         if (ctx->currents_deferred && mu_n == ctx->mu.p) {
             launch_psi_update_with_currents(ctx, ctx->psi[cur].p, mu_n, ctx->lap[cur].p, dt, ctx->psi[nxt].p);
             ctx->currents_deferred = false;
@@ -233,7 +183,7 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
         } else {
             launch_psi_update(ctx, ctx->psi[cur].p, mu_n, ctx->lap[cur].p, dt, ctx->psi[nxt].p, nullptr);
         }
-        if (extrapolate && retries == 0) {
+        if (extrapolate && first) {
             // Initial guess of the mu solve: linear extrapolation in time.  Runs after the psi
             // update has read mu^n; afterwards mu_prev holds mu^n (a retry reads it from there)
             // and mu holds the guess the solve starts from.
@@ -333,20 +283,17 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
             return solve_status;
         }
         if (!failed) break;
-        // solver.py:475-485
-        if (!ctl.adaptive || retries > ctl.max_solve_retries) roll_back_mu();
-        if (!ctl.adaptive || retries > ctl.max_solve_retries)
-            TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES,
-                      "Solver failed to converge in %d retries at step %lld with dt = %.2e."
-                      " Try using a smaller dt_init.",
-                      ctl.max_solve_retries, (long long)ctx->stage_step, dt);
-        dt *= ctl.adaptive_time_step_multiplier;
+        if (!ctx->loop.retry()) {  // solver.py:475-485
+            roll_back_mu();
+            TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES, "%s", ctx->loop.budget_message(-1, dt).c_str());
+        }
+        dt = ctx->loop.attempt_dt;
         ctx->stat_psi_retries += 1;
     }
     // accept the step
     ctx->prev_dt2 = ctx->prev_dt;
     ctx->prev_dt = dt;
-    ctx->cur = nxt;
+    ctx->loop.cur = nxt;
     ctx->lap_valid = true;
     ctx->currents_valid = false;
     if (ctx->spec_currents_done) {
@@ -370,8 +317,7 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
 // probes (solver.py:690-694) and the adaptive time-step controller (solver.py:698-707)
 static int step_finish(tdgl_ctx *ctx, double dt, double dmax, double *dt_used, double *probe_mu,
                        double *probe_theta, int32_t *pcg_iters) {
-    const tdgl_controller &ctl = ctx->ctl;
-    const int nxt = ctx->cur;
+    const int nxt = ctx->loop.cur;
     const int np_ = (int)ctx->probes.size();
     if (np_ > 0 && (probe_mu || probe_theta)) {
         // running state "mu" / "theta" (solver.py:690-694, runner.py:186-221): written into a device
@@ -385,21 +331,8 @@ static int step_finish(tdgl_ctx *ctx, double dt, double dmax, double *dt_used, d
     *dt_used = dt;
     if (pcg_iters) *pcg_iters = ctx->last_pcg_iters;
     ctx->stat_steps += 1;
-    // adaptive time-step controller (solver.py:698-707)
     direct_note_step(ctx, dmax, ctx->last_pcg_iters);
-    if (ctl.adaptive) {
-        ctx->d_psi_sq_vals.push_back(dmax);
-        if (ctx->stage_step > ctl.adaptive_window) {
-            const double mean = numpy_mean_tail(ctx->d_psi_sq_vals, ctl.adaptive_window);
-            const double new_dt = ctl.dt_init / std::max(1e-10, mean);
-            ctx->tentative_dt = std::min(std::max(0.5 * (new_dt + dt), 0.0), ctx->dt_cap);
-        }
-        // bound the history: only the last `window` entries are ever read
-        if (ctl.adaptive_window > 0 &&
-            (int64_t)ctx->d_psi_sq_vals.size() > 4 * (int64_t)std::max(ctl.adaptive_window, 1) + 64)
-            ctx->d_psi_sq_vals.erase(ctx->d_psi_sq_vals.begin(),
-                                     ctx->d_psi_sq_vals.end() - std::max(ctl.adaptive_window, 1));
-    }
+    ctx->loop.accept(dt, dmax);
     return TDGL_OK;
 }
 
@@ -410,11 +343,10 @@ static int step_finish(tdgl_ctx *ctx, double dt, double dmax, double *dt_used, d
 // heavy-ball step towards the Biot-Savart-like integral of the site-averaged sheet current.  dt
 // shrunk by a failed update stays shrunk for the remaining iterations.
 static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out) {
-    const tdgl_controller &ctl = ctx->ctl;
     if (distributed(ctx) && ctx->scr_Jglobal.n == 0)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "one-process-per-GPU mode: screening must be set with tdgl_set_screening_distributed");
-    double dt = ctx->tentative_dt, dmax = 0.0, err = INFINITY;
-    hipLaunchKernelGGL(k_abs_sq, dim3(grid_for(ctx->n)), dim3(BLOCK), 0, ctx->stream, ctx->n, ctx->psi[ctx->cur].p,
+    double dt = ctx->loop.begin_step(), dmax = 0.0, err = INFINITY;
+    hipLaunchKernelGGL(k_abs_sq, dim3(grid_for(ctx->n)), dim3(BLOCK), 0, ctx->stream, ctx->n, ctx->psi[ctx->loop.cur].p,
                        ctx->abs_sq_old.p);
     HIP_TRY(ctx, hipMemsetAsync(ctx->scr_vel.p, 0, 2 * ctx->m_pad * sizeof(double), ctx->stream));
     int it = 0;
@@ -424,12 +356,13 @@ static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out) {
             TDGL_FAIL(ctx, TDGL_ERR_SCREENING,
                       "Screening calculation failed to converge at step %lld after %d iterations."
                       " Relative error in induced vector potential: %.2e (tolerance: %.2e).",
-                      (long long)ctx->stage_step, ctx->scr.max_iterations, err, ctx->scr.tolerance);
-        const int cur = ctx->cur, nxt = 1 - cur;
+                      (long long)ctx->loop.stage_step, ctx->scr.max_iterations, err, ctx->scr.tolerance);
+        const int cur = ctx->loop.cur, nxt = 1 - cur;
         screening_refresh_links(ctx);
         launch_psi_laplacian(ctx, false, ctx->psi[cur].p, ctx->lap[cur].p);
-        for (int retries = 0;; ++retries) {
-                launch_psi_update(ctx, ctx->psi[cur].p, ctx->mu.p, ctx->lap[cur].p, dt, ctx->psi[nxt].p, nullptr,
+        ctx->loop.restart_retries();  // (every screening iteration has the whole budget; dt stays shrunk)
+        for (;;) {
+            launch_psi_update(ctx, ctx->psi[cur].p, ctx->mu.p, ctx->lap[cur].p, dt, ctx->psi[nxt].p, nullptr,
                               ctx->abs_sq_old.p);
             TDGL_TRY(comm_halo(ctx, reinterpret_cast<double *>(ctx->psi[nxt].p), 2));  // (no-op on one GPU)
             launch_psi_laplacian(ctx, true, ctx->psi[nxt].p, ctx->lap[nxt].p);
@@ -446,15 +379,12 @@ static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out) {
                 },
                 &abandoned, /*allow_projection=*/true));
             if (!failed) break;
-            if (!ctl.adaptive || retries > ctl.max_solve_retries)
-                TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES,
-                          "Solver failed to converge in %d retries at step %lld with dt = %.2e."
-                          " Try using a smaller dt_init.",
-                          ctl.max_solve_retries, (long long)ctx->stage_step, dt);
-            dt *= ctl.adaptive_time_step_multiplier;
+            if (!ctx->loop.retry())
+                TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES, "%s", ctx->loop.budget_message(-1, dt).c_str());
+            dt = ctx->loop.attempt_dt;
             ctx->stat_psi_retries += 1;
         }
-        ctx->cur = nxt;
+        ctx->loop.cur = nxt;
         launch_edge_currents(ctx, ctx->psi[nxt].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
         TDGL_TRY(screening_update_A(ctx, &err));
     }
@@ -481,22 +411,12 @@ static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out) {
 // where it was and shrinks dt; the next queued attempt repeats the step, exactly as the classic retry
 // loop would (one wasted attempt per retry in both).  Reaching end_time or spending the retry budget
 // poisons the rest of the batch: every later kernel returns at once.
-// A LinearRamp (tdgl/sources/scaling.py:4-14) is constant from t_max on.  Once the loop has evaluated it twice at
-// its final value -- the first evaluation still sees dA/dt != 0, the second writes dA/dt = 0 (solver.py:626-642) --
-// the vector potential is static for the rest of the stage: the step needs no dA/dt term and no per-step update,
-// and the run-ahead loop can take over (the reference's flagship example ramps over t = 0..100 and holds to t = 800).
-static inline bool ramp_settled(const tdgl_ctx *ctx) {
-    return ctx->ramp_on && ctx->time >= ctx->ramp_tmax && ctx->link_scale == ctx->ramp_final &&
-           ctx->link_scale_prev == ctx->ramp_final;
-}
-
 static bool run_ahead_ok(const tdgl_ctx *ctx) {
     const bool off = ctx->run_ahead_disabled;  // (TDGL_NO_RUN_AHEAD at tdgl_create)
-    const tdgl_controller &ctl = ctx->ctl;
+    const tdgl_controller &ctl = ctx->loop.ctl;
     // (a moving vector potential: only the ramp the loop evaluates itself rides along -- k_ra_ramp_begin --, and it
     // needs the previous step's dt: from the second step of a stage on)
-    const bool ramping = ctx->ramp_on && !ramp_settled(ctx);
-    if (ramping ? !(ctx->runner_dt > 0.0) : ctx->has_dadt) return false;
+    if (ctx->loop.ramping() ? !(ctx->loop.runner_dt > 0.0) : ctx->loop.has_dadt) return false;
     return !off && dense_on(ctx) && (ctx->direct->dense.tiles > 0) && !ctx->scr_enabled &&
            (ctx->tab_mu_t.empty() || ctx->tab_mu_on_device) && (ctx->tab_eps_t.empty() || ctx->tab_eps_on_device) &&
            ctx->popt.edge_currents_every_step != 0 && ctx->have_links &&
@@ -506,40 +426,15 @@ static bool run_ahead_ok(const tdgl_ctx *ctx) {
 // Queues `batch` attempts, synchronises, delivers the accepted steps (out_dt[0 .. *accepted)).  *reached: the
 // last accepted step reached end_time.  A spent retry budget is reported like the classic loop does.
 static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, bool want_probes, int *accepted, bool *reached) {
-    const tdgl_controller &c = ctx->ctl;
     *accepted = 0;
     *reached = false;
     TDGL_TRY(ensure_laplacian_cache(ctx));
     StepCtl &h = *ctx->h_ctl;
-    memset(&h, 0, sizeof(h));
-    h.tentative_dt = h.attempt_dt = ctx->tentative_dt;
-    h.time = ctx->time;
-    h.end_time = end_time;
-    h.dt_init = c.dt_init;
-    h.dt_cap = ctx->dt_cap;
-    h.multiplier = c.adaptive_time_step_multiplier;
-    h.stage_step = ctx->stage_step;
-    h.adaptive = c.adaptive;
-    h.window = c.adaptive_window;
-    h.max_retries = c.max_solve_retries;
-    h.cur = ctx->cur;
-    const bool ramping = ctx->ramp_on && !ramp_settled(ctx);
-    h.runner_dt = ctx->runner_dt;
-    h.ramp_tmin = ctx->ramp_tmin, h.ramp_tmax = ctx->ramp_tmax, h.ramp_initial = ctx->ramp_initial, h.ramp_final = ctx->ramp_final;
-    h.link_scale = ctx->link_scale, h.link_scale_prev = ctx->link_scale_prev;
-    h.has_dadt = ctx->has_dadt ? 1 : 0;
+    const bool ramping = ctx->loop.ramping();
+    ctx->loop.fill(h, end_time, true);
     if (ramping && ctx->link_block_changed.n == 0) {
         HIP_TRY(ctx, ctx->link_block_changed.alloc(grid_for(ctx->m)));
         HIP_TRY(ctx, ctx->link_changed.alloc(1));
-    }
-    if (ctx->ra_retries > 0) {  // the previous batch ended in the middle of a step's retries
-        h.retries = ctx->ra_retries;
-        h.attempt_dt = ctx->ra_attempt_dt;
-    }
-    if (c.adaptive) {
-        const int64_t have = (int64_t)ctx->d_psi_sq_vals.size(), cnt = std::min<int64_t>(have, c.adaptive_window);
-        h.hist_count = (int)cnt;
-        for (int64_t i = 0; i < cnt; ++i) h.hist[i] = ctx->d_psi_sq_vals[have - cnt + i];
     }
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctl.p, &h, sizeof(StepCtl), hipMemcpyHostToDevice, ctx->stream));
     const int np_ = (int)ctx->probes.size();
@@ -595,19 +490,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
                                (const double *)nullptr, ctx->e_dirx.p, ctx->e_diry.p, ctx->e_U.p, moved);
             hipLaunchKernelGGL(k_fill_laplacian, dim3(grid_for(ctx->lap_pat.n_slots)), dim3(BLOCK), 0, ctx->stream,
                                ctx->lap_pat.n_slots, ctx->lap_slot_edge.p, ctx->lap_slot_w.p, ctx->e_U.p, ctx->lap_vals.p, moved);
-            {
-                const SellPattern &pat = ctx->lap_pat;
-                const int tiles = (pat.n_slices + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-                const int per_xcd = (tiles + XCDS - 1) / XCDS, grid = per_xcd * XCDS;
-                if (pat.use16)
-                    hipLaunchKernelGGL((k_psi_laplacian_ra_fresh<int16_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, pat.n_rows,
-                                       pat.slice_off.p, pat.cols16.p, ctx->lap_vals.p, ctx->lap_diag.p, ctx->fixed_mask.p, (const double2 *)ctx->psi[0].p,
-                                       (const double2 *)ctx->psi[1].p, ctx->lap[0].p, ctx->lap[1].p, (const StepCtl *)dc);
-                else
-                    hipLaunchKernelGGL((k_psi_laplacian_ra_fresh<int32_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, pat.n_rows,
-                                       pat.slice_off.p, pat.cols.p, ctx->lap_vals.p, ctx->lap_diag.p, ctx->fixed_mask.p, (const double2 *)ctx->psi[0].p,
-                                       (const double2 *)ctx->psi[1].p, ctx->lap[0].p, ctx->lap[1].p, (const StepCtl *)dc);
-            }
+            launch_ra_laplacian_fresh(ctx);
         }
         // (the edge currents of psi^n ride along: always behind the first attempt, for the first if they are owed)
         launch_ra_psi(ctx, !ramping && (s > 0 || old_deferred));
@@ -663,52 +546,24 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
     // (mu and b are a pair when the last attempt that ran was accepted)
     if (guard) direct_guard_read(ctx, done > 0 && done <= batch && h.last_ok != 0);
     if (done == 0) TDGL_FAIL(ctx, TDGL_ERR_HIP, "run-ahead: no attempt of the batch ran");  // (cannot happen: the first one is always live)
-    if (done < 0 || done > batch || h.n_acc < 0 || h.n_acc > done)
-        TDGL_FAIL(ctx, TDGL_ERR_HIP, "run-ahead: corrupt attempt records (%d processed, %d accepted of %d)", done, h.n_acc, batch);
-    int acc = 0, last_acc_idx = -1, fails = 0;
-    double last_fail_dt = 0.0;
-    for (int s = 0; s < done; ++s) {
-        if (!ctx->h_rec[s].ok) {
-            ++fails;
-            last_fail_dt = ctx->h_rec[s].dt;
-            continue;
-        }
-        out_dt[acc++] = ctx->h_rec[s].dt;
-        last_acc_idx = s;
-        direct_note_step(ctx, ctx->h_rec[s].dmax, 0);
-        if (c.adaptive) ctx->d_psi_sq_vals.push_back(ctx->h_rec[s].dmax);
-    }
-    if (acc != h.n_acc) TDGL_FAIL(ctx, TDGL_ERR_HIP, "run-ahead: attempt records disagree with the controller (%d vs %d)", acc, h.n_acc);
+    const LoopState::Batch b = ctx->loop.absorb(h, ctx->h_rec, batch, batch, ramping, out_dt);
+    if (b.corrupt)
+        TDGL_FAIL(ctx, TDGL_ERR_HIP, "run-ahead: corrupt attempt records (%d processed, %d accepted of %d; check %d)", done, h.n_acc, batch, b.corrupt);
+    for (int s = 0; s < done; ++s)
+        if (ctx->h_rec[s].ok) direct_note_step(ctx, ctx->h_rec[s].dmax, 0);
+    const int acc = b.accepted, last_acc_idx = b.last_accepted;
     *accepted = acc;
-    *reached = h.reached_end != 0;
+    *reached = b.reached;
     ctx->stat_ra_batches += 1;
     ctx->stat_ra_dead += batch - done;
-    ctx->stat_psi_retries += fails - (h.error ? 1 : 0);
-    // the host's mirror of the loop state
-    if (ramping) {
-        ctx->link_scale = h.link_scale;
-        ctx->link_scale_prev = h.link_scale_prev;
-        ctx->has_dadt = h.has_dadt != 0;
-    }
-    ctx->cur = h.cur;
-    ctx->ra_retries = h.error ? 0 : h.retries;
-    ctx->ra_attempt_dt = h.attempt_dt;
-    ctx->tentative_dt = h.tentative_dt;
-    ctx->time = h.time;
-    ctx->stage_step = h.stage_step;
+    ctx->stat_psi_retries += b.failed - (b.error ? 1 : 0);
     if (acc > 0) {
-        // Runner.dt (runner.py:431) is not touched by the step that reached end_time (the loop breaks before)
-        const int last = *reached ? acc - 2 : acc - 1;
-        if (last >= 0) ctx->runner_dt = out_dt[last];
         ctx->prev_dt = ctx->prev_dt2 = 0.0;
         ctx->stat_steps += acc;
         ctx->last_pcg_iters = 0;
     }
     ctx->lap_valid = true;
     ctx->probe_ring_count += probing ? acc : 0;
-    if (c.adaptive && c.adaptive_window > 0 &&
-        (int64_t)ctx->d_psi_sq_vals.size() > 4 * (int64_t)std::max(c.adaptive_window, 1) + 64)
-        ctx->d_psi_sq_vals.erase(ctx->d_psi_sq_vals.begin(), ctx->d_psi_sq_vals.end() - std::max(c.adaptive_window, 1));
     // edge currents: every live attempt behind the first forms those of psi^n as it stood when the attempt began
     if (acc > 0) {
         if (done > last_acc_idx + 1) {  // a later live attempt (a failed one) saw the last accepted state
@@ -722,11 +577,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
         ctx->currents_valid = true;
         ctx->currents_deferred = false;
     }
-    if (h.error)
-        TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES,
-                  "Solver failed to converge in %d retries at step %lld with dt = %.2e."
-                  " Try using a smaller dt_init.",
-                  c.max_solve_retries, (long long)ctx->stage_step, last_fail_dt);
+    if (b.error) TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES, "%s", ctx->loop.budget_message(-1, b.last_fail_dt).c_str());
     return TDGL_OK;
 }
 
@@ -745,8 +596,8 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
     for (int64_t k = 0; k < max_steps && status == TDGL_OK;) {
         // a ramp that has reached its end: dA/dt is identically zero from here on (the array holds zeros; the
         // kernels drop the term), with or without the run-ahead loop
-        const bool settled = ramp_settled(ctx);
-        if (settled && ctx->has_dadt && !ctx->scr_enabled) ctx->has_dadt = false;
+        const bool settled = ctx->loop.ramp_settled();
+        if (settled && ctx->loop.has_dadt && !ctx->scr_enabled) ctx->loop.has_dadt = false;
         direct_policy(ctx);
         if (run_ahead_ok(ctx)) {
             const bool want_probes = out_mu_probe || out_theta_probe;
@@ -775,16 +626,17 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
             continue;
         }
         double dt = 0.0;
-        if (ctx->ramp_on && !settled) {
+        if (ctx->loop.ramp_on && !settled) {
             // update_applied_vector_potential (solver.py:347-362, 626-642) for
             // A(t) = ramp(t) * A_base, ramp = tdgl/sources/scaling.py LinearRamp; dA/dt uses the
             // previous step's dt (Runner.dt)
-            const double scale = linear_ramp_value(ctx->time, ctx->ramp_tmin, ctx->ramp_tmax, ctx->ramp_initial, ctx->ramp_final);
-            status = update_link_scale(ctx, scale, ctx->runner_dt);
+            const double scale = linear_ramp_value(ctx->loop.time, ctx->loop.ramp_tmin, ctx->loop.ramp_tmax, ctx->loop.ramp_initial, ctx->loop.ramp_final);
+            status = update_link_scale(ctx, scale, ctx->loop.runner_dt);
         }
         if (status == TDGL_OK) status = apply_time_tables(ctx);  // tabulated terminal currents / epsilon factor at this time
         if (status == TDGL_OK)
             status = step_once(ctx, &dt, out_mu_probe, out_theta_probe, out_pcg_iters ? out_pcg_iters + k : nullptr);
+        if (status != TDGL_OK) ctx->loop.restart_retries();  // (a step given up in the middle of its retries leaves none pending)
         if (status != TDGL_OK) break;
         out_dt[k] = dt;
         if (out_screening_iters) out_screening_iters[k] = ctx->scr_enabled ? ctx->last_screening_iters : 0;
@@ -794,17 +646,14 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
             flushed = k + 1;
             if (status != TDGL_OK) break;
         }
-        if (ctx->time >= end_time) {  // runner.py:431-430: tested before time advances
+        if (ctx->loop.advance(dt, end_time)) {  // runner.py:429-433
             *reached_end = 1;
             break;
         }
-        ctx->runner_dt = dt;       // runner.py:431
-        ctx->time += ctx->runner_dt;  // runner.py:433
-        ctx->stage_step += 1;
         ++k;
     }
     if (ctx->currents_deferred) {  // J_s, J_n of the last accepted step (see step_once: defer_currents)
-        launch_edge_currents(ctx, ctx->psi[ctx->cur].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
+        launch_edge_currents(ctx, ctx->psi[ctx->loop.cur].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
         ctx->currents_deferred = false;
         ctx->currents_valid = true;
     }

@@ -477,16 +477,18 @@ static inline void tile_range(const tdgl_ctx *ctx, int n_slices, int part, int *
     }
 }
 
-static void launch_psi_laplacian(tdgl_ctx *ctx, bool rhs, const double2 *psi, double2 *lap, int part = 0) {
+// (vals: covariant-Laplacian values other than the context's -- an ensemble's replica)
+static void launch_psi_laplacian(tdgl_ctx *ctx, bool rhs, const double2 *psi, double2 *lap, int part = 0, const double2 *vals = nullptr) {
     int tile_base, slice_end, tiles;
     tile_range(ctx, ctx->lap_pat.n_slices, part, &tile_base, &slice_end, &tiles);
     if (tiles <= 0) return;
     const int per_xcd = (tiles + XCDS - 1) / XCDS, grid = per_xcd * XCDS;
     const SellPattern &pat = ctx->lap_pat;
     const double *c = rhs ? ctx->ceff.p : ctx->cvec.p;
+    if (!vals) vals = ctx->lap_vals.p;
 #define TDGL_K1(RHS, IT, COLS)                                                                              \
     hipLaunchKernelGGL((k_psi_laplacian<RHS, IT>), dim3(grid), dim3(BLOCK), 0, ctx->stream, slice_end, per_xcd, \
-                       tile_base, pat.n_rows, pat.slice_off.p, COLS, ctx->lap_vals.p, ctx->lap_diag.p,     \
+                       tile_base, pat.n_rows, pat.slice_off.p, COLS, vals, ctx->lap_diag.p,                \
                        ctx->fixed_mask.p, psi, lap, ctx->area.p, c, ctx->bvec.p)
     if (pat.use16) {
         if (rhs) TDGL_K1(true, int16_t, pat.cols16.p); else TDGL_K1(false, int16_t, pat.cols16.p);
@@ -538,6 +540,19 @@ static void launch_ra_laplacian(tdgl_ctx *ctx) {
 #undef TDGL_K1RA
 }
 
+// L psi^n with the links a ramping attempt has just moved (k_psi_laplacian_ra_fresh)
+static void launch_ra_laplacian_fresh(tdgl_ctx *ctx) {
+    const SellPattern &pat = ctx->lap_pat;
+    const int tiles = (pat.n_slices + BLOCK / WAVE - 1) / (BLOCK / WAVE);
+    const int per_xcd = (tiles + XCDS - 1) / XCDS, grid = per_xcd * XCDS;
+#define TDGL_K1RA(IT, COLS)                                                                                                        \
+    hipLaunchKernelGGL((k_psi_laplacian_ra_fresh<IT>), dim3(grid), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, pat.n_rows, \
+                       pat.slice_off.p, COLS, ctx->lap_vals.p, ctx->lap_diag.p, ctx->fixed_mask.p, (const double2 *)ctx->psi[0].p, \
+                       (const double2 *)ctx->psi[1].p, ctx->lap[0].p, ctx->lap[1].p, (const StepCtl *)ctx->d_ctl.p)
+    if (pat.use16) TDGL_K1RA(int16_t, pat.cols16.p); else TDGL_K1RA(int32_t, pat.cols.p);
+#undef TDGL_K1RA
+}
+
 // reduce the outcome of the last psi update into d_status (together with the PCG scalars);
 // guess_start: first synchronisation of a solve with the projection guess (sums its partial arrays,
 // sets S_BB / S_TOL2, resets the iteration counters); rr_part: residual partials to sum into S_RR
@@ -572,7 +587,7 @@ static void launch_edge_currents(tdgl_ctx *ctx, const double2 *psi, const double
     const int64_t base = (part == 2) ? ctx->m_int : 0, end = (part == 1) ? ctx->m_int : ctx->m;
     if (end <= base) return;
     const int grid = grid_for(end - base);
-    const double *dadt = ctx->has_dadt ? ctx->e_dAdt.p : (const double *)nullptr;
+    const double *dadt = ctx->loop.has_dadt ? ctx->e_dAdt.p : (const double *)nullptr;
     if (js && jn)
         hipLaunchKernelGGL((k_edge_currents<true, true>), dim3(grid), dim3(BLOCK), 0, ctx->stream, end,
                            ctx->e0.p, ctx->e1.p, ctx->e_inv_len.p, ctx->e_U.p, psi, mu, js, jn, dadt, base);
@@ -587,7 +602,7 @@ static void launch_edge_currents(tdgl_ctx *ctx, const double2 *psi, const double
 static void refresh_ceff(tdgl_ctx *ctx) {
     hipLaunchKernelGGL(k_ceff, dim3(grid_for((int64_t)ctx->lap_pat.n_slices * WAVE)), dim3(BLOCK), 0, ctx->stream,
                        ctx->lap_pat.n_slices, ctx->lap_pat.n_rows, ctx->lap_pat.slice_off.p, ctx->lap_slot_edge.p,
-                       ctx->lap_slot_w.p, ctx->e_inv_len.p, ctx->has_dadt ? ctx->e_dAdt.p : (const double *)nullptr,
+                       ctx->lap_slot_w.p, ctx->e_inv_len.p, ctx->loop.has_dadt ? ctx->e_dAdt.p : (const double *)nullptr,
                        ctx->cvec.p, ctx->ceff.p);
 }
 
@@ -601,6 +616,7 @@ static inline int64_t now_ns() {
 
 #include "ipc.inc"
 #include "comm.inc"
+#include "loop.inc"
 #include "guess.inc"
 #include "poisson.inc"
 #include "dense.inc"
@@ -642,10 +658,10 @@ static int finish_links(tdgl_ctx *ctx, bool dynamic, double dt_prev) {
         // (with screening the links are rebuilt from A_applied + A_induced in every screening
         // iteration anyway, solver.py:670-673)
         only_if = ctx->link_changed.p;
-        ctx->has_dadt = true;
+        ctx->loop.has_dadt = true;
     } else {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->e_Aprev.p, ctx->e_A.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        ctx->has_dadt = false;
+        ctx->loop.has_dadt = false;
     }
     refresh_ceff(ctx);
     hipLaunchKernelGGL(k_link_variables, dim3(grid_for(ctx->m)), dim3(BLOCK), 0, ctx->stream, ctx->m,
@@ -677,7 +693,7 @@ static int set_links_impl(tdgl_ctx *ctx, const double *A, bool dynamic, double d
     CTX_GUARD(ctx);
     if (!A) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_exponents: null A");
     TDGL_TRY(upload_edge_vectors(ctx, A, ctx->e_A.p));
-    ctx->ramp_on = false;
+    ctx->loop.ramp_on = false;
     TDGL_TRY(finish_links(ctx, dynamic, dt_prev));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
@@ -690,10 +706,10 @@ extern "C" int tdgl_set_link_exponents_base(tdgl_ctx *ctx, const double *A_base,
     if (ctx->e_Abase.n == 0) HIP_TRY(ctx, ctx->e_Abase.alloc(2 * ctx->m_pad));
     TDGL_TRY(upload_edge_vectors(ctx, A_base, ctx->e_Abase.p));
     ctx->have_base = true;
-    ctx->ramp_on = false;
+    ctx->loop.ramp_on = false;
     hipLaunchKernelGGL(k_scale_links, dim3(grid_for(2 * ctx->m_pad)), dim3(BLOCK), 0, ctx->stream, 2 * ctx->m_pad,
                        scale, ctx->e_Abase.p, ctx->e_A.p);
-    ctx->link_scale = ctx->link_scale_prev = scale;
+    ctx->loop.link_scale = ctx->loop.link_scale_prev = scale;
     TDGL_TRY(finish_links(ctx, false, 0.0));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
@@ -702,11 +718,11 @@ extern "C" int tdgl_set_link_exponents_base(tdgl_ctx *ctx, const double *A_base,
 static int update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev) {
     // nothing moves when the factor has been constant over the last two evaluations (A and
     // dA/dt = 0 are already in place)
-    if (scale == ctx->link_scale && scale == ctx->link_scale_prev && ctx->has_dadt) return TDGL_OK;
+    if (scale == ctx->loop.link_scale && scale == ctx->loop.link_scale_prev && ctx->loop.has_dadt) return TDGL_OK;
     hipLaunchKernelGGL(k_scale_links, dim3(grid_for(2 * ctx->m_pad)), dim3(BLOCK), 0, ctx->stream, 2 * ctx->m_pad,
                        scale, ctx->e_Abase.p, ctx->e_A.p);
-    ctx->link_scale_prev = ctx->link_scale;
-    ctx->link_scale = scale;
+    ctx->loop.link_scale_prev = ctx->loop.link_scale;
+    ctx->loop.link_scale = scale;
     return finish_links(ctx, true, dt_prev);
 }
 
@@ -723,17 +739,13 @@ extern "C" int tdgl_set_link_ramp(tdgl_ctx *ctx, int32_t on, double tmin, double
     CTX_GUARD(ctx);
     if (on && !ctx->have_base) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_exponents_base first");
     if (on && !(tmax > tmin)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_ramp: tmax must be > tmin");
-    ctx->ramp_on = on != 0;
-    ctx->ramp_tmin = tmin;
-    ctx->ramp_tmax = tmax;
-    ctx->ramp_initial = initial;
-    ctx->ramp_final = final_;
+    ctx->loop.set_ramp(on != 0, tmin, tmax, initial, final_);
     return TDGL_OK;
 }
 
 extern "C" int tdgl_get_link_scale(tdgl_ctx *ctx, double *scale) {
     if (!ctx || !scale) return TDGL_ERR_ARG;
-    *scale = ctx->link_scale;
+    *scale = ctx->loop.link_scale;
     return TDGL_OK;
 }
 
@@ -788,6 +800,31 @@ static bool table_times_ok(const double *times, int32_t n) {
     return true;
 }
 
+// what tdgl_set_mu_boundary_table and tdgl_ensemble_set_mu_boundary_table refuse (who: the entry point, for the message)
+static int check_mu_table(tdgl_ctx *ctx, const char *who, int32_t n_nodes, const double *times, int32_t n_groups,
+                          const int32_t *group_ptr, const int32_t *group_pos, const double *density) {
+    if (n_nodes < 1 || n_groups < 1 || !times || !group_ptr || !group_pos || !density || !table_times_ok(times, n_nodes))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: bad table (times must increase strictly)", who);
+    if (group_ptr[0] != 0) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: group_ptr must start at 0", who);
+    for (int32_t g = 0; g < n_groups; ++g)
+        if (group_ptr[g + 1] < group_ptr[g]) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: group_ptr decreases", who);
+    for (int32_t k = 0; k < group_ptr[n_groups]; ++k)
+        if (group_pos[k] < 0 || group_pos[k] >= ctx->nb)
+            TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: boundary position %d out of range", who, group_pos[k]);
+    for (int64_t k = 0; k < (int64_t)n_groups * n_nodes; ++k)
+        if (!std::isfinite(density[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: non-finite density", who);
+    return TDGL_OK;
+}
+
+// ... and the two epsilon tables
+static int check_eps_table(tdgl_ctx *ctx, const char *who, const double *epsilon0, int32_t n_nodes, const double *times, const double *factor) {
+    if (n_nodes < 1 || !epsilon0 || !times || !factor || !table_times_ok(times, n_nodes))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: bad table (times must increase strictly)", who);
+    for (int32_t k = 0; k < n_nodes; ++k)
+        if (!std::isfinite(factor[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: non-finite factor", who);
+    return TDGL_OK;
+}
+
 // the sites boundary edges touch, once (the table kernels rebuild the boundary term there)
 static int ensure_boundary_sites(tdgl_ctx *ctx) {
     if (ctx->d_b_sites.n != 0) return TDGL_OK;
@@ -809,11 +846,7 @@ extern "C" int tdgl_set_mu_boundary_table(tdgl_ctx *ctx, int32_t n_nodes, const 
     ctx->tab_mu_host.clear();
     ctx->tab_mu_dev_synced = false;
     if (n_nodes == 0) return TDGL_OK;  // off
-    if (n_nodes < 1 || n_groups < 1 || !times || !group_ptr || !group_pos || !density || !table_times_ok(times, n_nodes))
-        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_mu_boundary_table: bad table (times must increase strictly)");
-    for (int32_t k = 0; k < group_ptr[n_groups]; ++k)
-        if (group_pos[k] < 0 || group_pos[k] >= ctx->nb)
-            TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_mu_boundary_table: boundary position %d out of range", group_pos[k]);
+    TDGL_TRY(check_mu_table(ctx, "tdgl_set_mu_boundary_table", n_nodes, times, n_groups, group_ptr, group_pos, density));
     ctx->tab_mu_t.assign(times, times + n_nodes);
     ctx->tab_mu_dens.assign(density, density + (size_t)n_groups * n_nodes);
     ctx->tab_mu_ptr.assign(group_ptr, group_ptr + n_groups + 1);
@@ -840,8 +873,7 @@ extern "C" int tdgl_set_epsilon_table(tdgl_ctx *ctx, const double *epsilon0, int
     CTX_GUARD(ctx);
     ctx->tab_eps_t.clear();
     if (n_nodes == 0) return TDGL_OK;  // off
-    if (n_nodes < 1 || !epsilon0 || !times || !factor || !table_times_ok(times, n_nodes))
-        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_epsilon_table: bad table (times must increase strictly)");
+    TDGL_TRY(check_eps_table(ctx, "tdgl_set_epsilon_table", epsilon0, n_nodes, times, factor));
     if (ctx->tab_eps0.n == 0) HIP_TRY(ctx, ctx->tab_eps0.alloc(ctx->n_pad));
     TDGL_TRY(upload_sites(ctx, epsilon0, ctx->tab_eps0));
     ctx->tab_eps_t.assign(times, times + n_nodes);
@@ -863,7 +895,7 @@ static int apply_time_tables(tdgl_ctx *ctx) {
         const size_t nn = ctx->tab_mu_t.size(), ng = ctx->tab_mu_last.size();
         bool changed = false;
         for (size_t g = 0; g < ng; ++g) {
-            const double d = table_value(ctx->tab_mu_t, ctx->tab_mu_dens.data() + g * nn, ctx->time);
+            const double d = table_value(ctx->tab_mu_t, ctx->tab_mu_dens.data() + g * nn, ctx->loop.time);
             if (d != ctx->tab_mu_last[g]) {  // solver.py:341: only when the density changed
                 ctx->tab_mu_last[g] = d;
                 for (int32_t k = ctx->tab_mu_ptr[g]; k < ctx->tab_mu_ptr[g + 1]; ++k) ctx->tab_mu_host[ctx->tab_mu_pos[k]] = d;
@@ -878,7 +910,7 @@ static int apply_time_tables(tdgl_ctx *ctx) {
         }
     }
     if (!ctx->tab_eps_t.empty()) {
-        const double f = table_value(ctx->tab_eps_t, ctx->tab_eps_f.data(), ctx->time);
+        const double f = table_value(ctx->tab_eps_t, ctx->tab_eps_f.data(), ctx->loop.time);
         if (!(f == ctx->tab_eps_last)) {
             hipLaunchKernelGGL(k_scale_links, dim3(grid_for(ctx->n_pad)), dim3(BLOCK), 0, ctx->stream, ctx->n_pad, f,
                                (const double *)ctx->tab_eps0.p, ctx->eps.p);
@@ -892,13 +924,13 @@ static int apply_time_tables(tdgl_ctx *ctx) {
 extern "C" int tdgl_set_state(tdgl_ctx *ctx, const double *psi, const double *mu) {
     CTX_GUARD(ctx);
     if (!psi || !mu) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_state: null array");
-    TDGL_TRY(upload_sites(ctx, reinterpret_cast<const double2 *>(psi), ctx->psi[ctx->cur]));
+    TDGL_TRY(upload_sites(ctx, reinterpret_cast<const double2 *>(psi), ctx->psi[ctx->loop.cur]));
     TDGL_TRY(upload_sites(ctx, mu, ctx->mu));
     ctx->have_state = true;
     ctx->lap_valid = false;
     ctx->currents_valid = false;
     ctx->currents_deferred = false;
-    ctx->ra_retries = 0;
+    ctx->loop.new_state(ctx->loop.cur);
     ctx->prev_dt = ctx->prev_dt2 = 0.0;  // no mu history: the next solve starts from mu itself
     ctx->guess.reset();                   // (nor a projection basis)
     direct_policy_reset(ctx);             // (nor a history for the loop's solver choice)
@@ -912,13 +944,7 @@ extern "C" int tdgl_set_controller(tdgl_ctx *ctx, const tdgl_controller *c) {
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "adaptive_time_step_multiplier must be in (0, 1) (got %g).",
                   c->adaptive_time_step_multiplier);
     if (c->adaptive_window < 0) TDGL_FAIL(ctx, TDGL_ERR_ARG, "adaptive_window must be >= 0 (got %d).", c->adaptive_window);
-    ctx->ctl = *c;
-    ctx->tentative_dt = c->dt_init;                       // solver.py:319
-    ctx->dt_cap = c->adaptive ? c->dt_max : c->dt_init;   // solver.py:320
-    ctx->d_psi_sq_vals.clear();                           // solver.py:318
-    ctx->runner_dt = c->dt_init;                          // runner.py:262
-    ctx->time = 0.0;
-    ctx->stage_step = 0;
+    ctx->loop.reset(*c);
     return TDGL_OK;
 }
 
@@ -948,7 +974,7 @@ extern "C" int tdgl_set_probes(tdgl_ctx *ctx, const int32_t *sites, int32_t n_pr
 static int ensure_currents(tdgl_ctx *ctx) {
     if (ctx->currents_valid) return TDGL_OK;
     if (!ctx->have_links) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "link exponents not set");
-    launch_edge_currents(ctx, ctx->psi[ctx->cur].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
+    launch_edge_currents(ctx, ctx->psi[ctx->loop.cur].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
     HIP_TRY(ctx, hipGetLastError());
     ctx->currents_valid = true;
     return TDGL_OK;
@@ -958,7 +984,7 @@ extern "C" int tdgl_get_state(tdgl_ctx *ctx, double *psi, double *mu, double *su
                               double *normal_current) {
     CTX_GUARD(ctx);
     if (!ctx->have_state) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_get_state: no state set");
-    if (psi) TDGL_TRY(download_sites(ctx, ctx->psi[ctx->cur].p, reinterpret_cast<double2 *>(psi)));
+    if (psi) TDGL_TRY(download_sites(ctx, ctx->psi[ctx->loop.cur].p, reinterpret_cast<double2 *>(psi)));
     if (mu) TDGL_TRY(download_sites(ctx, ctx->mu.p, mu));
     if (supercurrent || normal_current) {
         TDGL_TRY(ensure_currents(ctx));
@@ -1264,12 +1290,12 @@ extern "C" int tdgl_time_kernel(tdgl_ctx *ctx, int32_t kernel, int32_t reps, dou
     HIP_TRY(ctx, tmp_c.alloc(ctx->n_pad));
     HIP_TRY(ctx, tmp_r.alloc(std::max<int64_t>(std::max(ctx->n_pad, ctx->m_pad), 256 * BLOCK)));
     HIP_TRY(ctx, tmp_r2.alloc(std::max(ctx->n_pad, ctx->m_pad)));
-    const double2 *psi = ctx->psi[ctx->cur].p;
+    const double2 *psi = ctx->psi[ctx->loop.cur].p;
     auto once = [&]() -> int {
         switch (kernel) {
             case 0: launch_psi_laplacian(ctx, false, psi, tmp_c.p); break;
             case 1: launch_psi_laplacian(ctx, true, psi, tmp_c.p); break;
-            case 2: launch_psi_update(ctx, psi, ctx->mu.p, ctx->lap[ctx->cur].p, 1e-4, tmp_c.p, nullptr); break;
+            case 2: launch_psi_update(ctx, psi, ctx->mu.p, ctx->lap[ctx->loop.cur].p, 1e-4, tmp_c.p, nullptr); break;
             case 3: launch_edge_currents(ctx, psi, ctx->mu.p, tmp_r.p, tmp_r2.p); break;
             case 4: poisson_spmv_level0(ctx, ctx->mu.p, tmp_r.p); break;
             case 5: vcycle(ctx, ctx->bvec.p, /*result*/ nullptr); break;

@@ -232,6 +232,62 @@ struct StepRec {
     int ok, pad;
 };
 
+// The time loop's bookkeeping on the host, one per trajectory (tdgl_ctx, every replica of an ensemble): the controller
+// (solver.py:316-320, 475-485, 698-707), Runner.dt / time / step (runner.py:260-263, 429-433), the retry state a run-ahead
+// batch leaves behind and the field ramp A(t) = LinearRamp(t) A_base.  The classic loop drives it event by event (begin_step,
+// retry, accept, advance); the run-ahead and ensemble loops hand it to the device (fill) and take it back (absorb), where
+// step_controller applies the same rules.  Its functions (loop.inc) are the only writers of the controller, loop and retry
+// members; the ramp members are also written by the link setters, which own the arrays they describe (finish_links).
+struct LoopState {
+    tdgl_controller ctl{1e-6, 1e-1, 1, 10, 10, 0.25};
+    double tentative_dt = 1e-6, dt_cap = 1e-1, runner_dt = 1e-6, time = 0.0;
+    int64_t stage_step = 0;
+    std::vector<double> hist;  // d_psi_sq_vals (solver.py:318, 701): only the last `adaptive_window` entries are ever read
+    int cur = 0;               // which psi / L psi buffer holds psi^n
+    int retries = 0;           // failed attempts of the step in progress (outlives a run-ahead batch) ...
+    double attempt_dt = 0.0;   // ... and the dt its next attempt takes
+    bool ramp_on = false, has_dadt = false;
+    double ramp_tmin = 0.0, ramp_tmax = 1.0, ramp_initial = 0.0, ramp_final = 1.0;
+    double link_scale = 1.0, link_scale_prev = 1.0;  // scale of the current / previous A
+    // what absorb tells its caller about a batch.  corrupt: 1 impossible counts, 2 the records disagree with the controller
+    // (the state is void); last_accepted: index of the last accepted record
+    struct Batch {
+        int corrupt = 0, accepted = 0, failed = 0, last_accepted = -1;
+        bool reached = false, error = false;
+        double last_fail_dt = 0.0;
+    };
+
+    void reset(const tdgl_controller &c);
+    void begin_stage() { time = 0.0, stage_step = 0; }  // runner.py:294-295, 315-316
+    // restart from a checkpoint (tdgl_set_loop_state, tdgl_set_controller_state)
+    void restore(int64_t step, double t, double rdt) { stage_step = step, time = t, runner_dt = rdt; }
+    void restore_controller(double tentative, const double *h, int64_t n) { tentative_dt = tentative, retries = 0, hist.assign(h, h + n); }
+    void new_state(int buffer) { cur = buffer, retries = 0; }  // a new psi in psi[buffer] (tdgl_set_state): no step is in progress
+    void set_ramp(bool on, double tmin, double tmax, double initial, double final_) {
+        ramp_on = on, ramp_tmin = tmin, ramp_tmax = tmax, ramp_initial = initial, ramp_final = final_;
+    }
+    std::string budget_message(int replica, double dt) const;
+    void report(int64_t *step, double *time_, double *runner_dt_, double *tentative) const;
+    // the classic loop's step: its first attempt takes tentative_dt (solver.py:666-668); a step begun by the run-ahead loop and
+    // continued here starts its retries over
+    double begin_step() { return retries = 0, attempt_dt = tentative_dt; }
+    void restart_retries() { retries = 0; }
+    bool retry();
+    void accept(double dt, double dmax);
+    bool advance(double dt, double end_time);
+    // A LinearRamp (tdgl/sources/scaling.py:4-14) is constant from t_max on.  Once the loop has evaluated it twice at its final
+    // value -- the first evaluation still sees dA/dt != 0, the second writes dA/dt = 0 (solver.py:626-642) -- the vector
+    // potential is static for the rest of the stage: no dA/dt term, no per-step update, and the run-ahead loop can take over
+    bool ramp_settled() const { return ramp_on && time >= ramp_tmax && link_scale == ramp_final && link_scale_prev == ramp_final; }
+    bool ramping() const { return ramp_on && !ramp_settled(); }
+    void fill(tdgl::StepCtl &h, double end_time, bool live) const;
+    Batch absorb(const tdgl::StepCtl &h, const tdgl::StepRec *rec, int batch, int limit, bool ramped, double *out_dt);
+    void trim() {  // bound the history: only the last `window` entries are ever read
+        const int w = ctl.adaptive_window;
+        if (ctl.adaptive && w > 0 && (int64_t)hist.size() > 4 * (int64_t)w + 64) hist.erase(hist.begin(), hist.end() - w);
+    }
+};
+
 struct StepStatus {
     int32_t fail_flag;          // psi update: discriminant < 0 or non-finite somewhere
     int32_t pad;
@@ -434,15 +490,11 @@ struct tdgl_ctx {
     tdgl::DevBuf<double> e_inv_len, e_dirx, e_diry;
     tdgl::DevBuf<double2> e_U;
     tdgl::DevBuf<double> e_A, e_Aprev;    // link exponents now / at the previous step [2 * m_pad]
-    tdgl::DevBuf<double> e_dAdt;          // dA/dt along the edges (time-dependent A), else unused
-    bool has_dadt = false;
+    tdgl::DevBuf<double> e_dAdt;          // dA/dt along the edges (time-dependent A: loop.has_dadt), else unused
     tdgl::DevBuf<int32_t> link_block_changed, link_changed;  // allclose(new_A, old_A) test (k_dadt)
     // A(t) = scale(t) * A_base on the device (tdgl_set_link_exponents_base / _scale / _ramp)
     tdgl::DevBuf<double> e_Abase;
     bool have_base = false;
-    bool ramp_on = false;
-    double ramp_tmin = 0.0, ramp_tmax = 1.0, ramp_initial = 0.0, ramp_final = 1.0;
-    double link_scale = 1.0, link_scale_prev = 1.0;  // scale of the current / previous A
     // Piecewise-linear time tables evaluated by tdgl_run itself before every step (no Python round
     // trip per step): terminal current densities -> mu_boundary (tdgl_set_mu_boundary_table) and a
     // time-dependent factor of epsilon (tdgl_set_epsilon_table)
@@ -468,9 +520,8 @@ struct tdgl_ctx {
     tdgl::DevBuf<double> ceff;            // cvec + divergence(dA/dt): what the rhs kernel reads
 
     // ---- state ---------------------------------------------------------------------
-    tdgl::DevBuf<double2> psi[2];
-    int cur = 0;                          // psi[cur] is psi^n
-    tdgl::DevBuf<double2> lap[2];         // lap[cur] = L_psi psi^n (cached between steps)
+    tdgl::DevBuf<double2> psi[2];         // psi[loop.cur] is psi^n
+    tdgl::DevBuf<double2> lap[2];         // lap[loop.cur] = L_psi psi^n (cached between steps)
     bool lap_valid = false;
     tdgl::DevBuf<double> mu, eps, bvec;
     tdgl::DevBuf<double> js, jn;          // per edge, internal order
@@ -523,8 +574,6 @@ struct tdgl_ctx {
     tdgl::StepRec *h_rec = nullptr;       // pinned [RA_BATCH_MAX]
     int ra_batch = 4;                     // attempts queued per synchronisation: doubles up to RA_BATCH_MAX
     bool run_ahead_disabled = false;      // TDGL_NO_RUN_AHEAD, read once when the context is created (tests, A/B runs)
-    int ra_retries = 0;                   // failed attempts of the step in progress when the last batch ended ...
-    double ra_attempt_dt = 0.0;           // ... and the dt its next attempt takes (the retry state outlives a batch)
     int64_t stat_ra_batches = 0, stat_ra_dead = 0;
     bool currents_deferred = false;       // J of the last accepted step ride in the next step's psi-update launch
     bool spec_currents = false;           // step driver: queue the edge currents right behind the dense solve,
@@ -588,12 +637,7 @@ struct tdgl_ctx {
     double *h_probe_out = nullptr;         // pinned, same shape
     int probe_ring_count = 0;              // steps written since the last flush (run.inc: probe_ring_flush)
 
-    // ---- controller / loop state (host; mirrors solver.py:316-320, runner.py:260-263) --
-    tdgl_controller ctl{1e-6, 1e-1, 1, 10, 10, 0.25};
-    double tentative_dt = 1e-6, dt_cap = 1e-1;
-    std::vector<double> d_psi_sq_vals;
-    double runner_dt = 1e-6, time = 0.0;
-    int64_t stage_step = 0;
+    tdgl::LoopState loop;                  // controller, Runner.dt / time / step, retry and ramp state (loop.inc)
     // counters since the last reset (tdgl_get_step_stats): steps accepted, failed psi updates that were
     // repeated with a smaller dt, PCG iterations, host synchronisations inside tdgl_run
     int64_t stat_steps = 0, stat_psi_retries = 0, stat_pcg_iters = 0, stat_host_syncs = 0;

@@ -111,6 +111,23 @@ class Controller(C.Structure):
     ]
 
 
+class LoopReplay(C.Structure):
+    _fields_ = [
+        ("n_accepted", C.c_int64),
+        ("n_attempts", C.c_int64),
+        ("stage_step", C.c_int64),
+        ("time", C.c_double),
+        ("tentative_dt", C.c_double),
+        ("runner_dt", C.c_double),
+        ("attempt_dt", C.c_double),
+        ("error_dt", C.c_double),
+        ("retries", C.c_int32),
+        ("reached", C.c_int32),
+        ("error", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
 class PoissonOptions(C.Structure):
     _fields_ = [
         ("rtol", C.c_double),
@@ -306,6 +323,11 @@ SIGNATURES = {
     "tdgl_set_controller": (C.c_int, [_CTX, C.POINTER(Controller)]),
     "tdgl_set_probes": (C.c_int, [_CTX, c_i32p, C.c_int32]),
     "tdgl_host_mean_tail": (C.c_double, [c_f64p, C.c_int64, C.c_int32]),
+    "tdgl_host_loop_replay": (
+        C.c_int,
+        [C.POINTER(Controller), C.c_double, C.c_int64, c_f64p, c_i32p, C.c_int32, C.c_int32, C.POINTER(Controller),
+         C.c_int64, c_f64p, c_f64p, C.POINTER(LoopReplay)],
+    ),
     "tdgl_host_blr_compress": (C.c_int32, [c_f64p, C.c_int32, C.c_double, C.c_int32, c_f64p, c_f64p]),
     "tdgl_begin_stage": (C.c_int, [_CTX]),
     "tdgl_run": (

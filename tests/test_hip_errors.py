@@ -7,7 +7,9 @@ import copy
 import numpy as np
 import pytest
 
-from helpers import GAMMA_DEFAULT, U_DEFAULT, max_abs, remove_mean, synthetic_mesh, uniform_field_A
+from conftest import load_golden
+from helpers import (GAMMA_DEFAULT, U_DEFAULT, edge_terminal, max_abs, reference_mesh, remove_mean, synthetic_mesh,
+                     uniform_field_A)
 
 pytestmark = pytest.mark.gpu
 
@@ -202,3 +204,59 @@ def test_run_restarts_from_recorded_controller_state():
     assert max_abs(remove_mean(got["mu"]), remove_mean(end["mu"])) < 1e-8 * max(1.0, np.abs(end["mu"]).max())
     with pytest.raises(ValueError, match="tentative_dt must be positive"):
         t.ctx.set_controller_state(0.0, [])
+
+
+def _golden_transport_solver():
+    from tdgl_amd import SolverOptions, TDGLSolver
+
+    mesh = reference_mesh(load_golden("mesh_small"))
+    terms = [edge_terminal(mesh, "source", -10.0), edge_terminal(mesh, "drain", 10.0)]
+    opts = SolverOptions(solve_time=1e9, dt_init=1e-4, save_every=10**9)
+    solver = TDGLSolver.from_dimensionless(mesh, opts, uniform_field_A(mesh, 0.1), 1.0, U_DEFAULT, GAMMA_DEFAULT,
+                                           terminal_info=terms, current_func={"source": 2.0, "drain": -2.0})
+    solver.ctx.set_state(solver.psi_init, solver.mu_init)
+    solver.ctx.begin_stage()
+    solver.update_mu_boundary(0.0)
+    return solver, [np.asarray(t["boundary_edge_indices"], dtype=np.int32) for t in terms]
+
+
+@pytest.fixture(scope="module")
+def run_without_tables():
+    """8 steps of the small transport run with no table installed: what a refused table must leave behind."""
+    solver, _ = _golden_transport_solver()
+    res = solver.ctx.run(8)
+    return res["dt"], solver.ctx.get_state()["psi"]
+
+
+@pytest.mark.parametrize("flaw", ["group_ptr[0] != 0", "group_ptr decreases", "NaN density", "NaN epsilon factor"])
+def test_malformed_time_tables_are_refused_and_leave_no_table(flaw, run_without_tables):
+    """tdgl_set_mu_boundary_table walks group_pos up to group_ptr[n_groups] and keeps group_ptr for the time loop to
+    walk: a group_ptr that does not start at 0 or decreases, a non-finite density and a non-finite epsilon factor
+    are TDGL_ERR_ARG (the ensemble's setters always said so), and the run that follows is the run without a table."""
+    from tdgl_amd._lib import f64, i32, p_f64, p_i32
+
+    solver, groups = _golden_transport_solver()
+    ctx = solver.ctx
+    times = f64([0.0, 1e-3, 1.0])
+    ptr = i32([0, len(groups[0]), len(groups[0]) + len(groups[1])])
+    pos = i32(np.concatenate(groups))
+    dens = f64([[0.0, 5.0, 9.0], [0.0, -5.0, -9.0]])  # (installed, it would change the run from the second step on)
+    eps0, factor = f64(np.full(ctx.n, 0.8)), f64([1.0, 0.5, 0.2])
+    message = flaw
+    if flaw == "group_ptr[0] != 0":
+        ptr[0], message = 1, "group_ptr must start at 0"
+    elif flaw == "group_ptr decreases":
+        ptr[1] = ptr[2] + 1
+    elif flaw == "NaN density":
+        dens[1, 2], message = np.nan, "non-finite density"
+    else:
+        factor[1], message = np.nan, "non-finite factor"
+    with pytest.raises(ValueError, match=message):
+        if flaw == "NaN epsilon factor":
+            ctx._chk(ctx._lib.tdgl_set_epsilon_table(ctx._ctx, p_f64(eps0), len(times), p_f64(times), p_f64(factor)))
+        else:
+            ctx._chk(ctx._lib.tdgl_set_mu_boundary_table(ctx._ctx, len(times), p_f64(times), 2, p_i32(ptr), p_i32(pos), p_f64(dens)))
+    res = ctx.run(8)
+    want_dt, want_psi = run_without_tables
+    assert np.array_equal(res["dt"], want_dt)
+    assert np.array_equal(ctx.get_state()["psi"], want_psi)

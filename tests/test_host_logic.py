@@ -496,6 +496,196 @@ def test_controller_mean_reproduces_numpy_summation_order():
             assert got == want, (size, window, got, want)
 
 
+# ---------------------------------------------------------------- the time loop's rules, replayed on the host
+def _controller(dt_init=1e-3, dt_max=1e-1, adaptive=1, window=10, max_retries=10, multiplier=0.25):
+    from tdgl_amd import _lib
+
+    return _lib.Controller(dt_init, dt_max, adaptive, window, max_retries, multiplier)
+
+
+def _loop_replay(ctl, end_time, dmax, fail, batch, mode, ctl_next=None, next_at=0):
+    """tdgl_host_loop_replay: every figure it reports, as a dict of Python floats / ints."""
+    import ctypes as C
+
+    from tdgl_amd import _lib
+
+    lib = _lib.load()
+    n = len(dmax)
+    d = np.ascontiguousarray(dmax, dtype=np.float64)
+    f = np.ascontiguousarray(fail, dtype=np.int32)
+    out_dt, attempt_dt = np.full(n, np.nan), np.full(n, np.nan)
+    res = _lib.LoopReplay()
+    f64, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    status = lib.tdgl_host_loop_replay(C.byref(ctl), end_time, n, d.ctypes.data_as(f64), f.ctypes.data_as(i32), batch, mode,
+                                       C.byref(ctl_next) if ctl_next is not None else None, next_at,
+                                       out_dt.ctypes.data_as(f64), attempt_dt.ctypes.data_as(f64), C.byref(res))
+    assert status == _lib.TDGL_OK
+    got = {name: getattr(res, name) for name, _ in _lib.LoopReplay._fields_ if name != "pad"}
+    got["dt"] = out_dt[:res.n_accepted].tolist()
+    got["attempt_dt_each"] = attempt_dt[:res.n_attempts].tolist()
+    return got
+
+
+def _reference_loop(ctl, end_time, dmax, fail):
+    """The same script through the reference's own statements: the retry loop of solver.py:475-485, the controller of
+    solver.py:698-707 (np.mean of the list tail, np.clip) and the loop tail of runner.py:429-433."""
+    tentative_dt = ctl.dt_init  # solver.py:319
+    dt_max = ctl.dt_max if ctl.adaptive else ctl.dt_init  # solver.py:320
+    d_psi_sq_vals = []
+    runner_dt, time, step = ctl.dt_init, 0.0, 0
+    out = dict(dt=[], attempt_dt_each=[], reached=0, error=0, error_dt=0.0, retries=0)
+    attempts = iter(zip(dmax, fail))
+    pending_dt = None
+
+    def solve_for_psi_squared(dt):
+        d, failed = next(attempts)  # (StopIteration: the script ends here)
+        out["attempt_dt_each"].append(dt)
+        return None if failed else d
+
+    try:
+        while True:
+            dt = tentative_dt
+            out["retries"], pending_dt = 0, None
+            result = solve_for_psi_squared(dt)
+            retries = 0
+            while result is None:
+                if not ctl.adaptive or retries > ctl.max_solve_retries:
+                    out["error"], out["error_dt"], out["retries"] = 1, dt, 0  # (no retry is pending once it has raised)
+                    raise StopIteration
+                dt = dt * ctl.adaptive_time_step_multiplier
+                retries += 1
+                out["retries"], pending_dt = retries, dt
+                result = solve_for_psi_squared(dt)
+            out["retries"], pending_dt = 0, None
+            if ctl.adaptive:
+                d_psi_sq_vals.append(float(result))
+                window = ctl.adaptive_window
+                if step > window:
+                    new_dt = ctl.dt_init / max(1e-10, np.mean(d_psi_sq_vals[-window:]))
+                    tentative_dt = float(np.clip(0.5 * (new_dt + dt), 0, dt_max))
+            out["dt"].append(dt)
+            if time >= end_time:
+                out["reached"] = 1
+                break
+            runner_dt = dt
+            step += 1
+            time += runner_dt
+    except StopIteration:
+        pass
+    out.update(n_accepted=len(out["dt"]), n_attempts=len(out["attempt_dt_each"]), stage_step=step, time=time,
+               tentative_dt=tentative_dt, runner_dt=runner_dt)
+    if not out["error"]:  # (after a spent budget the library keeps the dt that failed; the reference has raised)
+        out["attempt_dt"] = pending_dt if pending_dt is not None else tentative_dt
+    return out
+
+
+def _loop_scripts():
+    """(name, controller, end_time, dmax, fail): max d|psi|^2 with full mantissas over five decades, failures where
+    the rules have a corner."""
+    rng = np.random.default_rng(11)
+
+    def dmax(n, lo=-6.0, hi=-1.0):
+        return rng.random(n) * 10.0 ** rng.uniform(lo, hi, n)
+
+    def fails(n, at=()):
+        f = np.zeros(n, dtype=np.int32)
+        f[list(at)] = 1
+        return f
+
+    inf = float("inf")
+    scripts = [
+        ("adaptive off", _controller(adaptive=0), inf, dmax(40), fails(40)),
+        ("adaptive off, a failure is final", _controller(adaptive=0), inf, dmax(40), fails(40, [5])),
+        # more than 4 * window + 64 accepted steps: the history is trimmed on the way
+        ("window 1", _controller(window=1), inf, dmax(300), fails(300, [7, 8, 150])),
+        ("window 10", _controller(window=10), inf, dmax(300), fails(300, [30, 31, 32, 200])),
+        # the first 128 steps have stage_step <= window: no controller update yet
+        ("window 128", _controller(window=128), inf, dmax(300), fails(300, [100, 250, 251])),
+        ("no update while step <= window", _controller(window=10), inf, dmax(9), fails(9)),
+        # retries across the ends of batches of 4 and of 64
+        ("retries straddle a batch boundary", _controller(window=10), inf, dmax(120), fails(120, [2, 3, 4, 5, 62, 63, 64, 65])),
+        ("the last tolerated failure", _controller(window=1, max_retries=3), inf, dmax(30), fails(30, [10, 11, 12, 13])),
+        ("one failure too many", _controller(window=1, max_retries=3), inf, dmax(30), fails(30, [10, 11, 12, 13, 14])),
+        ("end_time in the middle of a batch", _controller(dt_init=1e-2, dt_max=10.0, window=1), 0.4, dmax(40, -1.0, 0.0), fails(40)),
+        ("dt_cap binds", _controller(dt_init=1e-4, dt_max=2.5e-4, window=1), inf, dmax(30, -9.0, -7.0), fails(30)),
+    ]
+    return scripts
+
+
+_LOOP_SCRIPTS = _loop_scripts()
+_LOOP_IDS = [s[0] for s in _LOOP_SCRIPTS]
+
+
+@pytest.mark.parametrize("script", _LOOP_SCRIPTS, ids=_LOOP_IDS)
+def test_classic_and_run_ahead_loops_agree_bit_for_bit(script):
+    """One LoopState drives both loops: the classic one event by event (mode 0) and the run-ahead one through fill /
+    the device's step_controller / absorb (mode 1, batches of 1, 4 and 64 attempts).  Every figure of the replay --
+    accepted dt's, the dt of every attempt, time, step, tentative dt, Runner.dt, the pending retry, reached, error and
+    the dt the error reports -- must be the same float64."""
+    name, ctl, end_time, dmax, fail = script
+    classic = _loop_replay(ctl, end_time, dmax, fail, 1, 0)
+    for batch in (1, 4, 64):
+        ahead = _loop_replay(ctl, end_time, dmax, fail, batch, 1)
+        for key, want in classic.items():
+            assert ahead[key] == want, (name, batch, key, ahead[key], want)
+    # the scripts reach the corners they are named after
+    n = len(dmax)
+    if name == "one failure too many":
+        assert classic["error"] == 1 and classic["n_attempts"] == 15
+        # (the reference reports the dt of the attempt that failed last; a factor 1/4 is exact)
+        assert classic["error_dt"] == classic["attempt_dt_each"][14] == classic["attempt_dt_each"][10] * 0.25 ** 4 > 0
+    elif name == "adaptive off, a failure is final":
+        assert classic["error"] == 1 and classic["n_attempts"] == 6 and classic["error_dt"] == ctl.dt_init
+    else:
+        assert classic["error"] == 0
+    if name == "the last tolerated failure":
+        assert classic["n_attempts"] == n and classic["attempt_dt_each"][14] == classic["attempt_dt_each"][10] * 0.25 ** 4
+    if name == "end_time in the middle of a batch":
+        assert classic["reached"] == 1 and classic["n_attempts"] < n and classic["n_attempts"] % 4 != 0
+        # Runner.dt is not touched by the step that reached end_time
+        assert classic["runner_dt"] == classic["dt"][-2] != classic["dt"][-1]
+    else:
+        assert classic["reached"] == 0
+    if name == "dt_cap binds":
+        assert classic["tentative_dt"] == ctl.dt_max and classic["dt"][-1] == ctl.dt_max
+    if name == "no update while step <= window":
+        assert classic["tentative_dt"] == ctl.dt_init and set(classic["dt"]) == {ctl.dt_init}
+    if name in ("window 1", "window 10"):
+        assert classic["n_accepted"] > 4 * ctl.adaptive_window + 64
+    if name == "retries straddle a batch boundary":
+        assert classic["n_accepted"] == n - 8
+
+
+@pytest.mark.parametrize("script", _LOOP_SCRIPTS, ids=_LOOP_IDS)
+def test_loop_replay_matches_the_reference_statements(script):
+    """... and they are the reference's: the same scripts through a restatement of solver.py:475-485, 698-707 and
+    runner.py:429-433 that averages the list tail with np.mean, bit for bit."""
+    name, ctl, end_time, dmax, fail = script
+    want = _reference_loop(ctl, end_time, dmax, fail)
+    for mode in (0, 1):
+        got = _loop_replay(ctl, end_time, dmax, fail, 4, mode)
+        for key, value in want.items():
+            assert got[key] == value, (name, mode, key, got[key], value)
+    assert len(set(want["dt"])) > 1 or name in ("adaptive off", "adaptive off, a failure is final", "no update while step <= window")
+
+
+def test_a_new_controller_clears_a_pending_retry():
+    """A run-ahead batch that ends in the middle of a step's retries leaves the shrunken dt behind for the next batch.
+    A controller installed in between starts over: the next attempt takes the new dt_init, in both loops."""
+    ctl, new = _controller(dt_init=1e-3), _controller(dt_init=3.7e-3)
+    rng = np.random.default_rng(3)
+    dmax = rng.random(8) * 1e-3
+    fail = np.array([0, 0, 1, 1, 0, 0, 0, 0], dtype=np.int32)
+    cut = _loop_replay(ctl, float("inf"), dmax[:4], fail[:4], 4, 1)
+    assert cut["retries"] == 2 and cut["attempt_dt"] == 1e-3 * 0.25 * 0.25  # (the batch ends in mid-retry)
+    same = _loop_replay(ctl, float("inf"), dmax, fail, 4, 1)
+    assert same["attempt_dt_each"][4] == cut["attempt_dt"]
+    for mode in (0, 1):
+        got = _loop_replay(ctl, float("inf"), dmax, fail, 4, mode, ctl_next=new, next_at=4)
+        assert got["attempt_dt_each"][4] == new.dt_init, mode
+        assert got["retries"] == 0 and got["stage_step"] == 4 and got["dt"][-4:] == [new.dt_init] * 4
+
+
 def test_collapsed_coarse_operators_are_the_same_cycle():
     """amg.collapsed_operators: intermediate-level M = R (I - A S), the tail as dense G / sparse W /
     dense V (or one dense matrix).  With one tail cycle the chain is the plain V-cycle re-associated;
