@@ -11,7 +11,8 @@ supported: other time-dependent inputs, a ramp combined with a table in one repl
 than ``ENSEMBLE_MAX_SITES`` sites.
 
 The per-replica set-up (vector potential, epsilon, terminal currents -> mu boundary values) is ``TDGLSolver``'s
-own, run without creating a device context (``_ReplicaInputs``).
+own, run without creating a device context (``_ReplicaInputs``); the stage loop is ``TDGLSolver.solve``'s too: one
+``runloop.RunRecord`` per replica, all served by one ``EnsembleContext.run`` call per round.
 """
 
 import ctypes as C
@@ -21,10 +22,12 @@ from typing import Callable, Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from . import _lib
-from ._lib import c128, f64, i32, p_f64, p_i32
+from ._lib import c128, f64, p_f64, p_i32
 from .device import Device
+from .hipcore import TDGLContext, controller_struct, epsilon_table_args, mu_boundary_table_args, probe_args, read_loop_state
 from .options import SolverOptions
-from .solution import DynamicsData, Solution, TDGLData
+from .runloop import RunRecord, check_epsilon_table, check_seed
+from .solution import Solution
 from .solver import TDGLSolver
 
 # The ensemble's mu solve by mesh size, set by measurement (DESIGN.md "Ensembles").  Up to ENSEMBLE_DENSE_MAX_SITES the
@@ -106,13 +109,8 @@ def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
 
 def _check_seeds(device, mesh, seeds) -> None:
     for r, seed in enumerate(seeds):
-        if seed is None:
-            continue
-        if seed.device != device:
-            raise ValueError(f"solve_ensemble: replica {r}: the seed_solution.device must be equal to the device being simulated.")
-        if len(seed.tdgl_data.psi) != len(mesh.sites):
-            raise ValueError(f"solve_ensemble: replica {r}: the seed solution has {len(seed.tdgl_data.psi)} sites, "
-                             f"the device's mesh {len(mesh.sites)}.")
+        if seed is not None:
+            check_seed(seed, device, mesh, prefix=f"solve_ensemble: replica {r}: ")
 
 
 def solve_ensemble(
@@ -269,8 +267,7 @@ class EnsembleContext:
         self._chk(self._lib.tdgl_ensemble_set_mu_boundary(self._ens, r, p_f64(mu_b) if len(mu_b) else None))
 
     def set_epsilon(self, r, eps):
-        eps = f64(eps)
-        assert eps.shape == (self.ctx.n,)
+        eps = f64(np.broadcast_to(eps, (self.ctx.n,)))  # (a scalar is every site's value, as in TDGLContext.set_epsilon)
         self._chk(self._lib.tdgl_ensemble_set_epsilon(self._ens, r, p_f64(eps)))
 
     def set_link_ramp(self, r, A_base, tmin, tmax, initial, final):
@@ -287,26 +284,11 @@ class EnsembleContext:
 
     def set_mu_boundary_table(self, r, times, groups, densities):
         """``TDGLContext.set_mu_boundary_table`` for replica r; ``times=None``: off."""
-        if times is None:
-            self._chk(self._lib.tdgl_ensemble_set_mu_boundary_table(self._ens, r, 0, None, 0, None, None, None))
-            return
-        t, d = f64(times), f64(densities)
-        ptr = i32(np.concatenate([[0], np.cumsum([len(g) for g in groups])]))
-        pos = i32(np.concatenate([np.asarray(g, dtype=np.int64) for g in groups]) if len(groups) else [])
-        if d.shape != (len(groups), len(t)):
-            raise ValueError(f"densities must have shape ({len(groups)}, {len(t)}), got {d.shape}")
-        self._chk(self._lib.tdgl_ensemble_set_mu_boundary_table(self._ens, r, len(t), p_f64(t), len(groups), p_i32(ptr),
-                                                                p_i32(pos) if len(pos) else p_i32(i32([0])), p_f64(d)))
+        self._chk(self._lib.tdgl_ensemble_set_mu_boundary_table(self._ens, r, *mu_boundary_table_args(times, groups, densities)))
 
     def set_epsilon_table(self, r, epsilon0, times, factors):
         """``TDGLContext.set_epsilon_table`` for replica r; ``times=None``: off."""
-        if times is None:
-            self._chk(self._lib.tdgl_ensemble_set_epsilon_table(self._ens, r, None, 0, None, None))
-            return
-        e0, t, fac = f64(np.broadcast_to(epsilon0, (self.ctx.n,))), f64(times), f64(factors)
-        if t.shape != fac.shape:
-            raise ValueError("times and factors must have the same length")
-        self._chk(self._lib.tdgl_ensemble_set_epsilon_table(self._ens, r, p_f64(e0), len(t), p_f64(t), p_f64(fac)))
+        self._chk(self._lib.tdgl_ensemble_set_epsilon_table(self._ens, r, *epsilon_table_args(self.ctx.n, epsilon0, times, factors)))
 
     def set_state(self, r, psi, mu):
         psi, mu = c128(psi), f64(mu)
@@ -314,23 +296,19 @@ class EnsembleContext:
         self._chk(self._lib.tdgl_ensemble_set_state(self._ens, r, p_f64(psi), p_f64(mu)))
 
     def set_controller(self, r, options: SolverOptions):
-        c = _lib.Controller(float(options.dt_init), float(options.dt_max), int(bool(options.adaptive)),
-                            int(options.adaptive_window), int(options.max_solve_retries),
-                            float(options.adaptive_time_step_multiplier))
+        c = controller_struct(options.dt_init, options.dt_max, options.adaptive, options.adaptive_window,
+                              options.max_solve_retries, options.adaptive_time_step_multiplier)
         self._chk(self._lib.tdgl_ensemble_set_controller(self._ens, r, C.byref(c)))
 
     def set_probes(self, sites):
-        sites = i32([] if sites is None else sites)
-        self.n_probe = len(sites)
-        self._chk(self._lib.tdgl_ensemble_set_probes(self._ens, p_i32(sites) if len(sites) else None, len(sites)))
+        sites, self.n_probe = probe_args(sites)
+        self._chk(self._lib.tdgl_ensemble_set_probes(self._ens, sites, self.n_probe))
 
     def begin_stage(self, r):
         self._chk(self._lib.tdgl_ensemble_begin_stage(self._ens, r))
 
     def loop_state(self, r):
-        step, t, rdt, tdt = C.c_int64(0), C.c_double(0), C.c_double(0), C.c_double(0)
-        self._chk(self._lib.tdgl_ensemble_get_loop_state(self._ens, r, C.byref(step), C.byref(t), C.byref(rdt), C.byref(tdt)))
-        return dict(step=step.value, time=t.value, dt=rdt.value, tentative_dt=tdt.value)
+        return read_loop_state(self._chk, self._lib.tdgl_ensemble_get_loop_state, self._ens, r)
 
     def run(self, max_steps, end_time):
         """Up to ``max_steps[r]`` steps of every replica r, stopping at ``end_time[r]``.  Returns a list of dicts
@@ -374,11 +352,28 @@ class EnsembleContext:
         return dict(rounds=rounds.value, batches=batches.value)
 
 
+class _Replica:
+    """Replica r of an ensemble as the state source of its `runloop.RunRecord` (`TDGLContext`'s method names)."""
+
+    def __init__(self, ens: EnsembleContext, r: int):
+        self.ens, self.r = ens, r
+
+    def begin_stage(self):
+        self.ens.begin_stage(self.r)
+
+    def loop_state(self):
+        return self.ens.loop_state(self.r)
+
+    def link_scale(self):
+        return self.ens.link_scale(self.r)
+
+    def get_state(self, supercurrent=True, normal_current=True):
+        return self.ens.get_state(self.r, currents=supercurrent and normal_current)
+
+
 def build_context(mesh, options: SolverOptions, fixed_sites, u: float, gamma: float):
     """A single-GPU context on ``mesh`` with the ensemble's direct mu solve (`ensemble_mu_path`): the dense inverse or
     the substructured factors, whatever `TDGLContext.DENSE_MAX_SITES` / `SUB_MAX_SITES` / `SUB2_MAX_SITES` say."""
-    from .hipcore import TDGLContext
-
     levels = ensemble_mu_path(len(mesh.sites))
     ctx = TDGLContext(mesh, fixed_sites=fixed_sites, fix_psi=options.terminal_psi is not None, u=u, gamma=gamma,
                       device_id=options.device_id, substructure_levels=levels or None)
@@ -399,7 +394,7 @@ def build_context(mesh, options: SolverOptions, fixed_sites, u: float, gamma: fl
 
 
 class EnsembleSolver:
-    """The Runner's loop (runner.py:288-454, ``TDGLSolver.solve``) for every replica of an ensemble."""
+    """The Runner's loop (runner.py:288-454, `runloop.RunRecord`) for every replica of an ensemble."""
 
     def __init__(self, mesh, options: SolverOptions, replicas: Sequence[TDGLSolver]):
         self.mesh = mesh
@@ -428,8 +423,7 @@ class EnsembleSolver:
     def _run(self, ctx, ens: EnsembleContext, t_start: float) -> List[Solution]:
         opts = self.options
         reps, R = self.reps, len(self.reps)
-        probes = reps[0].probe_points
-        ens.set_probes(probes)
+        ens.set_probes(reps[0].probe_points)
         for r, rep in enumerate(reps):
             if rep._A_ramp is not None:  # (TDGLSolver._setup: the links start at the ramp's value at t = 0)
                 ens.set_link_ramp(r, rep._A_base, **rep._A_ramp)
@@ -441,102 +435,24 @@ class EnsembleSolver:
                 ens.set_mu_boundary_table(r, *rep._current_table_arrays())
             if rep._eps_table is not None:
                 eps0, times, values = rep._eps_table
-                if max(float(np.max(f * eps0)) for f in values) > 1:
-                    raise ValueError(f"replica {r}: The disorder parameter epsilon must be <= 1")
+                check_epsilon_table(eps0, values, prefix=f"replica {r}: ")
                 ens.set_epsilon_table(r, eps0, times, values)
+                rep._epsilon_on_device = True
             seed = getattr(rep, "seed_state", None)
             if rep.seed_solution is not None:
                 seed = (rep.seed_solution.tdgl_data.psi, rep.seed_solution.tdgl_data.mu)
             ens.set_state(r, *(seed if seed is not None else (rep.psi_init, rep.mu_init)))
             ens.set_controller(r, opts)
-        seeded = [rep.seed_solution is not None or getattr(rep, "seed_state", None) is not None for rep in reps]
-        stages = ([("Thermalizing", opts.skip_time, False)] if opts.skip_time else []) + [("Simulating", opts.solve_time, True)]
-        stage = [0] * R
-        i = [0] * R
-        saved = [[] for _ in range(R)]
-        dyn = [dict(dt=[], time=[], mu=[], theta=[]) for _ in range(R)]
-        n_steps = [{"Thermalizing": 0, "Simulating": 0} for _ in range(R)]
-        active = [True] * R
-        for r in range(R):
-            ens.begin_stage(r)
-
-        def save_step(r, final=False):
-            rep = reps[r]
-            ls = ens.loop_state(r)
-            if rep._eps_table is not None:
-                # the epsilon of the last step taken, as TDGLSolver.solve saves it (solver.py:645-648)
-                t_last = ls["time"] if (final or ls["step"] == 0) else ls["time"] - ls["dt"]
-                rep.epsilon = np.asarray(rep.epsilon_func(max(t_last, 0.0)), dtype=float)
-            if rep._A_ramp is not None:  # A_applied of the last step taken (the links may lag behind it)
-                rep.current_A_applied = ens.link_scale(r) * rep._A_base
-            if ls["step"] == 0 and not saved[r] and not seeded[r]:
-                st = ens.get_state(r, currents=False)
-                js = jn = np.zeros(ctx.m)  # reference initial values (solver.py:736-737)
-            else:
-                st = ens.get_state(r)
-                js, jn = st["supercurrent"], st["normal_current"]
-            saved[r].append(TDGLData(ls["step"], ls["time"], ls["dt"], st["psi"], st["mu"], js, jn,
-                                     applied_vector_potential=reps[r].current_A_applied, epsilon=reps[r].epsilon,
-                                     induced_vector_potential=None))
-
-        while any(active):
-            max_steps = np.zeros(R, dtype=np.int64)
-            end_time = np.zeros(R)
-            t_before = np.zeros(R)
-            for r in range(R):
-                if not active[r]:
-                    continue
-                name, end, save = stages[stage[r]]
-                if i[r] % opts.save_every == 0 and save:  # runner.py:398-401
-                    save_step(r)
-                max_steps[r] = opts.save_every - (i[r] % opts.save_every)
-                end_time[r] = end
-                t_before[r] = ens.loop_state(r)["time"]
+        records = [RunRecord(_Replica(ens, r), rep, opts) for r, rep in enumerate(reps)]
+        while not all(rec.done for rec in records):
+            max_steps, end_time = zip(*(rec.request() for rec in records))
             res = ens.run(max_steps, end_time)
-            for r in range(R):
-                if not active[r]:
-                    continue
-                name, end, save = stages[stage[r]]
-                out = res[r]
-                k = len(out["dt"])
-                n_steps[r][name] += k
-                if save:
-                    dyn[r]["dt"].append(out["dt"])
-                    dyn[r]["time"].append(t_before[r] + np.concatenate([[0.0], np.cumsum(out["dt"][:-1])]))
-                    if out["mu"] is not None:
-                        dyn[r]["mu"].append(out["mu"])
-                        dyn[r]["theta"].append(out["theta"])
-                if not out["reached_end"]:
-                    i[r] += k
-                    continue
-                i[r] += k - 1
-                if save and (i[r] % opts.save_every):
-                    save_step(r, final=True)
-                if stage[r] + 1 < len(stages):
-                    stage[r] += 1
-                    i[r] = 0
-                    ens.begin_stage(r)
-                else:
-                    active[r] = False
+            for rec, out in zip(records, res):
+                if not rec.done:
+                    rec.absorb(out)
         ctx.synchronize()
         mu_levels = self.mu_path[0]
         total = _time.perf_counter() - t_start
-        cat = lambda xs: np.concatenate(xs) if xs else np.array([])  # noqa: E731
-        solutions = []
-        for r, rep in enumerate(reps):
-            d = dyn[r]
-            dynamics = DynamicsData(
-                dt=cat(d["dt"]), time=cat(d["time"]),
-                mu=cat(d["mu"]).T if d["mu"] else None, theta=cat(d["theta"]).T if d["theta"] else None,
-                pcg_iterations=np.zeros(sum(len(x) for x in d["dt"]), dtype=np.int32),
-            )
-            solutions.append(Solution(
-                device=rep.device, options=opts, saved_steps=saved[r], dynamics=dynamics,
-                dynamic_vector_potential=rep.dynamic_vector_potential, dynamic_epsilon=rep.dynamic_epsilon,
-                applied_vector_potential=rep.applied_vector_potential, terminal_currents=rep.terminal_currents,
-                disorder_epsilon=rep.disorder_epsilon, total_seconds=total,
-                stats=dict(steps_thermalizing=n_steps[r]["Thermalizing"], steps_simulating=n_steps[r]["Simulating"],
-                           mean_pcg_iterations=0.0, mu_solver="substructured_ensemble" if mu_levels else "dense_ensemble",
-                           replica=r, replicas=R, **(dict(mu_levels=mu_levels) if mu_levels else {})),
-            ))
-        return solutions
+        return [rec.solution(total, mu_solver="substructured_ensemble" if mu_levels else "dense_ensemble", replica=r,
+                             replicas=R, **(dict(mu_levels=mu_levels) if mu_levels else {}))
+                for r, rec in enumerate(records)]

@@ -41,6 +41,50 @@ def poisson_matrix(edges, weights, n, iperm=None) -> sp.csr_matrix:
     return A
 
 
+# ---- argument marshalling shared by `TDGLContext` and `ensemble.EnsembleContext` (the ensemble's entry points take the
+# same arguments after a replica index).  The pointers keep their arrays alive.
+def mu_boundary_table_args(times, groups, densities) -> tuple:
+    """``(n_nodes, times, n_groups, group_ptr, group_pos, density)`` of tdgl_set_mu_boundary_table: ``groups[g]`` = the
+    boundary-edge positions of terminal g, ``densities[g, k]`` at ``times[k]``; ``times=None`` switches the table off."""
+    if times is None:
+        return 0, None, 0, None, None, None
+    t, d = f64(times), f64(densities)
+    ptr = i32(np.concatenate([[0], np.cumsum([len(g) for g in groups])]))
+    pos = i32(np.concatenate([np.asarray(g, dtype=np.int64) for g in groups]) if len(groups) else [])
+    if d.shape != (len(groups), len(t)):
+        raise ValueError(f"densities must have shape ({len(groups)}, {len(t)}), got {d.shape}")
+    return len(t), p_f64(t), len(groups), p_i32(ptr), p_i32(pos if len(pos) else i32([0])), p_f64(d)
+
+
+def epsilon_table_args(n: int, epsilon0, times, factors) -> tuple:
+    """``(epsilon0, n_nodes, times, factor)`` of tdgl_set_epsilon_table on ``n`` sites; ``times=None``: off."""
+    if times is None:
+        return None, 0, None, None
+    e0, t, fac = f64(np.broadcast_to(epsilon0, (n,))), f64(times), f64(factors)
+    if t.shape != fac.shape:
+        raise ValueError("times and factors must have the same length")
+    return p_f64(e0), len(t), p_f64(t), p_f64(fac)
+
+
+def controller_struct(dt_init, dt_max, adaptive, adaptive_window, max_solve_retries,
+                      adaptive_time_step_multiplier) -> "_lib.Controller":
+    return _lib.Controller(float(dt_init), float(dt_max), int(bool(adaptive)), int(adaptive_window),
+                           int(max_solve_retries), float(adaptive_time_step_multiplier))
+
+
+def probe_args(sites) -> tuple:
+    """``(sites, n_probe)`` of tdgl_set_probes; None or an empty list: no probes."""
+    sites = i32([] if sites is None else sites)
+    return (p_i32(sites) if len(sites) else None), len(sites)
+
+
+def read_loop_state(chk, getter, *handle) -> dict:
+    """The four outputs of ``getter(*handle, step, time, runner_dt, tentative_dt)``, its status through ``chk``."""
+    step, t, rdt, tdt = C.c_int64(0), C.c_double(0), C.c_double(0), C.c_double(0)
+    chk(getter(*handle, C.byref(step), C.byref(t), C.byref(rdt), C.byref(tdt)))
+    return dict(step=step.value, time=t.value, dt=rdt.value, tentative_dt=tdt.value)
+
+
 class _HierarchyInfo:
     """A rank's view of a decomposed hierarchy: the local levels plus the global sizes."""
 
@@ -1128,28 +1172,12 @@ class TDGLContext:
         self._chk(self._lib.tdgl_set_mu_boundary(self._ctx, p_f64(mu_b)))
 
     def set_mu_boundary_table(self, times, groups, densities):
-        """Tabulated terminal current densities evaluated inside `run` (``groups[g]`` = boundary-edge
-        positions of terminal g, ``densities[g, k]`` at ``times[k]``); ``times=None`` switches it off."""
-        if times is None:
-            self._chk(self._lib.tdgl_set_mu_boundary_table(self._ctx, 0, None, 0, None, None, None))
-            return
-        t, d = f64(times), f64(densities)
-        ptr = i32(np.concatenate([[0], np.cumsum([len(g) for g in groups])]))
-        pos = i32(np.concatenate([np.asarray(g, dtype=np.int64) for g in groups]) if len(groups) else [])
-        if d.shape != (len(groups), len(t)):
-            raise ValueError(f"densities must have shape ({len(groups)}, {len(t)}), got {d.shape}")
-        self._chk(self._lib.tdgl_set_mu_boundary_table(self._ctx, len(t), p_f64(t), len(groups), p_i32(ptr),
-                                                       p_i32(pos) if len(pos) else p_i32(i32([0])), p_f64(d)))
+        """Tabulated terminal current densities evaluated inside `run` (arguments: `mu_boundary_table_args`)."""
+        self._chk(self._lib.tdgl_set_mu_boundary_table(self._ctx, *mu_boundary_table_args(times, groups, densities)))
 
     def set_epsilon_table(self, epsilon0, times, factors):
         """epsilon(r, t) = factor(t) * epsilon0(r) evaluated inside `run`; ``times=None``: off."""
-        if times is None:
-            self._chk(self._lib.tdgl_set_epsilon_table(self._ctx, None, 0, None, None))
-            return
-        e0, t, fac = f64(np.broadcast_to(epsilon0, (self.n,))), f64(times), f64(factors)
-        if t.shape != fac.shape:
-            raise ValueError("times and factors must have the same length")
-        self._chk(self._lib.tdgl_set_epsilon_table(self._ctx, p_f64(e0), len(t), p_f64(t), p_f64(fac)))
+        self._chk(self._lib.tdgl_set_epsilon_table(self._ctx, *epsilon_table_args(self.n, epsilon0, times, factors)))
 
     def set_state(self, psi, mu):
         psi, mu = c128(psi), f64(mu)
@@ -1158,14 +1186,12 @@ class TDGLContext:
 
     def set_controller(self, dt_init, dt_max, adaptive, adaptive_window, max_solve_retries,
                        adaptive_time_step_multiplier):
-        c = _lib.Controller(float(dt_init), float(dt_max), int(bool(adaptive)), int(adaptive_window),
-                            int(max_solve_retries), float(adaptive_time_step_multiplier))
+        c = controller_struct(dt_init, dt_max, adaptive, adaptive_window, max_solve_retries, adaptive_time_step_multiplier)
         self._chk(self._lib.tdgl_set_controller(self._ctx, C.byref(c)))
 
     def set_probes(self, sites):
-        sites = i32([] if sites is None else sites)
-        self.n_probe = len(sites)
-        self._chk(self._lib.tdgl_set_probes(self._ctx, p_i32(sites) if len(sites) else None, len(sites)))
+        sites, self.n_probe = probe_args(sites)
+        self._chk(self._lib.tdgl_set_probes(self._ctx, sites, self.n_probe))
 
     # -- time loop --------------------------------------------------------------------------
     def begin_stage(self):
@@ -1280,9 +1306,7 @@ class TDGLContext:
         self._chk(self._lib.tdgl_set_direct_guard(self._ctx, float(limit)))
 
     def loop_state(self):
-        step, t, rdt, tdt = C.c_int64(0), C.c_double(0), C.c_double(0), C.c_double(0)
-        self._chk(self._lib.tdgl_get_loop_state(self._ctx, C.byref(step), C.byref(t), C.byref(rdt), C.byref(tdt)))
-        return dict(step=step.value, time=t.value, dt=rdt.value, tentative_dt=tdt.value)
+        return read_loop_state(self._chk, self._lib.tdgl_get_loop_state, self._ctx)
 
     def set_loop_state(self, step, time, runner_dt):
         self._chk(self._lib.tdgl_set_loop_state(self._ctx, int(step), float(time), float(runner_dt)))

@@ -16,7 +16,7 @@ Time-dependent ``applied_vector_potential`` (a ``Parameter`` with a keyword-only
 variables are then formed on the device (``tdgl_update_link_exponents``).
 ``include_screening`` runs the reference's self-consistent loop for the induced vector
 potential (solver.py:522-578, 654-688) entirely on the device; Python only hands over the site /
-edge coordinates and the scaled site areas (solver.py:305-309).  Not supported: HDF5 output.
+edge coordinates and the scaled site areas (solver.py:305-309).  The stage loop around `tdgl_run` is `runloop.RunRecord`.
 """
 
 import inspect
@@ -28,9 +28,11 @@ from typing import Callable, Dict, NamedTuple, Optional, Sequence, Union
 import numpy as np
 
 from .device import Device, TerminalInfo
+from .io import DataHandler, write_solution_group
 from .operators import MeshOperators
 from .options import SolverOptions
-from .solution import DynamicsData, Solution, TDGLData
+from .runloop import RunRecord, check_epsilon_table, check_seed
+from .solution import Solution
 
 logger = logging.getLogger("solver")
 
@@ -347,8 +349,7 @@ class TDGLSolver:
             self._currents_on_device = True
         if self._eps_table is not None:
             eps0, times, values = self._eps_table
-            if max(float(np.max(f * eps0)) for f in values) > 1:
-                raise ValueError("The disorder parameter epsilon must be <= 1")
+            check_epsilon_table(eps0, values)
             self.ctx.set_epsilon_table(eps0, times, values)
             self._epsilon_on_device = True
         self._device_holds = None  # (psi, mu) arrays known to equal the device state
@@ -389,6 +390,10 @@ class TDGLSolver:
                 changed = True
         return changed
 
+    def device_evaluates_epsilon(self) -> bool:
+        """epsilon(t) is a table the time loop evaluates itself (tdgl_set_epsilon_table); the host keeps a copy."""
+        return self.dynamic_epsilon and self._epsilon_on_device
+
     def update_dynamic_inputs(self, time: float, dt_prev: float) -> None:
         """solver.py:626-648: re-evaluate A(t) (-> link variables and dA/dt with the previous
         step's dt) and epsilon(t) before a step."""
@@ -399,13 +404,12 @@ class TDGLSolver:
         elif self.dynamic_vector_potential:
             self.current_A_applied = np.asarray(self.vector_potential_func(time), dtype=float)
             self.ctx.update_link_exponents(self.current_A_applied, dt_prev)
-        if self.dynamic_epsilon and self._epsilon_on_device:
-            self.epsilon = np.asarray(self.epsilon_func(time), dtype=float)  # host copy for the saved steps
-        elif self.dynamic_epsilon:
+        if self.dynamic_epsilon:
             self.epsilon = np.asarray(self.epsilon_func(time), dtype=float)
-            if np.any(self.epsilon > 1):
-                raise ValueError("The disorder parameter epsilon must be <= 1")
-            self.ctx.set_epsilon(self.epsilon)
+            if not self._epsilon_on_device:  # (on the device: this is the host's copy for the saved steps)
+                if np.any(self.epsilon > 1):
+                    raise ValueError("The disorder parameter epsilon must be <= 1")
+                self.ctx.set_epsilon(self.epsilon)
 
     # -- one step through the reference's method seam ---------------------------------------------
     def update(self, state: Dict[str, numbers.Real], running_state, dt: float, *, psi, mu,
@@ -457,43 +461,26 @@ class TDGLSolver:
     # -- the whole simulation ------------------------------------------------------------------------
     def solve(self) -> Optional[Solution]:
         """Run thermalisation + simulation stages with the reference's loop semantics
-        (runner.py:288-454) and return the saved steps in memory."""
+        (runner.py:288-454, `runloop.RunRecord`) and return the saved steps in memory."""
         opts = self.options
         opts.validate()
         ctx = self.ctx
         t_start = _time.perf_counter()
-        if self.seed_solution is None:
-            psi0, mu0 = self.psi_init, self.mu_init
-        else:
-            if self.seed_solution.device != self.device:
-                raise ValueError("The seed_solution.device must be equal to the device being simulated.")
+        seed = None
+        if self.seed_solution is not None:
+            check_seed(self.seed_solution, self.device, self.device.mesh)
             seed = self.seed_solution.tdgl_data
-            if len(seed.psi) != len(self.device.mesh.sites):  # (equal devices may carry different meshes)
-                raise ValueError(
-                    f"The seed solution has {len(seed.psi)} sites, the device's mesh {len(self.device.mesh.sites)}.")
-            psi0, mu0 = seed.psi, seed.mu
-        ctx.set_state(psi0, mu0)
+        ctx.set_state(*((self.psi_init, self.mu_init) if seed is None else (seed.psi, seed.mu)))
         if self.screening is not None:  # solver.py:738-745
-            a0 = None if self.seed_solution is None else self.seed_solution.tdgl_data.induced_vector_potential
+            a0 = None if seed is None else seed.induced_vector_potential
             ctx.set_induced_vector_potential(np.zeros((self.num_edges, 2)) if a0 is None else a0)
         ctx.set_controller(
             opts.dt_init, opts.dt_max, opts.adaptive, opts.adaptive_window,
             opts.max_solve_retries, opts.adaptive_time_step_multiplier,
         )
-        saved = []
-        dyn = dict(dt=[], time=[], mu=[], theta=[], iters=[], scr=[])
-        n_steps = {"Thermalizing": 0, "Simulating": 0}
         # Streaming output (runner.py:104-183): with SolverOptions.output_file every saved step is
         # written when it is taken, and only the latest one is kept in memory.
         handler = None
-        sizes = {"dt": 1}
-        if self.probe_points is not None:
-            sizes["mu"] = sizes["theta"] = len(self.probe_points)
-        if self.screening is not None:
-            sizes["screening_iterations"] = 1
-        from .io import DataHandler, RunningState, write_solution_group
-
-        running = RunningState(sizes, opts.save_every)
         if opts.output_file is not None:
             handler = DataHandler(opts.output_file, file_factory=getattr(self, "_h5_file_factory", None))
             try:
@@ -508,135 +495,37 @@ class TDGLSolver:
             except BaseException:
                 handler.close()  # no open files / stray .tmp left behind
                 raise
-
-        def save_step(final=False):
-            ls = ctx.loop_state()
-            if self.dynamic_epsilon and self._epsilon_on_device:
-                # the reference saves the epsilon its last update() evaluated (solver.py:645-648): at the
-                # time of the last step taken
-                t_last = ls["time"] if (final or ls["step"] == 0) else ls["time"] - ls["dt"]
-                self.epsilon = np.asarray(self.epsilon_func(max(t_last, 0.0)), dtype=float)
-            if ls["step"] == 0 and not saved and self.seed_solution is None:
-                js = jn = np.zeros(self.num_edges)  # reference initial values (solver.py:736-737)
-                st = ctx.get_state(supercurrent=False, normal_current=False)
-            else:
-                st = ctx.get_state()
-                js, jn = st["supercurrent"], st["normal_current"]
-            a_ind = ctx.induced_vector_potential() if self.screening is not None else None
-            if self._A_base is not None:
-                self.current_A_applied = ctx.link_scale() * self._A_base
-            data = TDGLData(ls["step"], ls["time"], ls["dt"], st["psi"], st["mu"], js, jn,
-                            applied_vector_potential=self.current_A_applied, epsilon=self.epsilon,
-                            induced_vector_potential=a_ind)
-            if handler is None:
-                saved.append(data)
-                return
-            fields = dict(psi=data.psi, mu=data.mu, supercurrent=js, normal_current=jn,
-                          induced_vector_potential=np.zeros((self.num_edges, 2)) if a_ind is None else a_ind)
-            if self.dynamic_vector_potential:
-                fields["applied_vector_potential"] = self.current_A_applied
-            if self.dynamic_epsilon:
-                fields["epsilon"] = self.epsilon
-            state = dict(step=int(ls["step"]), time=float(ls["time"]), dt=float(ls["dt"]))
-            handler.save_time_step(state, fields, None if ls["step"] == 0 else running.export())
-            saved[:] = [data]
-            saved_meta.append((data.step, data.time))
-
-        saved_meta = []
-
-        def run_stage(name, end_time, save):
-            ctx.begin_stage()
-            i = 0
-            while True:
-                if i % opts.save_every == 0:  # runner.py:398-401
-                    if save:
-                        save_step()
-                    running.clear()
-                per_step = ((self.dynamic_currents and not self._currents_on_device)
-                            or (self.dynamic_epsilon and not self._epsilon_on_device)
-                            or (self.dynamic_vector_potential and self._A_ramp is None))
-                chunk = 1 if per_step else opts.save_every - (i % opts.save_every)
-                ls = ctx.loop_state()
-                self.update_mu_boundary(ls["time"] if self.dynamic_currents else 0.0)
-                self.update_dynamic_inputs(ls["time"], ls["dt"])
-                t_before = ls["time"]
-                res = ctx.run(chunk, end_time)
-                k = len(res["dt"])
-                n_steps[name] += k
-                cols = {"dt": res["dt"]}
-                if res["mu"] is not None:
-                    cols["mu"], cols["theta"] = res["mu"], res["theta"]
-                if self.screening is not None:
-                    cols["screening_iterations"] = res["screening_iterations"]
-                # (the step that ends the loop is written into the buffer but not counted, runner.py:429-432)
-                running.extend({name_: v[:k - 1] if res["reached_end"] else v for name_, v in cols.items()})
-                if res["reached_end"]:
-                    for name_, v in cols.items():
-                        running.append(name_, np.asarray(v[k - 1]).reshape(-1))
-                if save:
-                    dyn["dt"].append(res["dt"])
-                    times = t_before + np.concatenate([[0.0], np.cumsum(res["dt"][:-1])])
-                    dyn["time"].append(times)
-                    dyn["iters"].append(res["pcg_iters"])
-                    dyn["scr"].append(res["screening_iterations"])
-                    if res["mu"] is not None:
-                        dyn["mu"].append(res["mu"])
-                        dyn["theta"].append(res["theta"])
-                if res["reached_end"]:
-                    i += k - 1
-                    break
-                i += k
-            if save and (i % opts.save_every):
-                save_step(final=True)
-
         try:
-            if opts.skip_time:
-                run_stage("Thermalizing", opts.skip_time, False)
-            run_stage("Simulating", opts.solve_time, True)
+            # inputs that live in Python are re-evaluated before every step
+            per_step = ((self.dynamic_currents and not self._currents_on_device)
+                        or (self.dynamic_epsilon and not self._epsilon_on_device)
+                        or (self.dynamic_vector_potential and self._A_ramp is None))
+            rec = RunRecord(ctx, self, opts, per_step=per_step, handler=handler)
+            while not rec.done:
+                chunk, end_time = rec.request()
+                self.update_mu_boundary(rec.loop["time"] if self.dynamic_currents else 0.0)
+                self.update_dynamic_inputs(rec.loop["time"], rec.loop["dt"])
+                rec.absorb(ctx.run(chunk, end_time))
             ctx.synchronize()
         except BaseException:
             if handler is not None:  # what has been saved stays on disk
                 handler.close()
             raise
-        total = _time.perf_counter() - t_start
-        cat = lambda xs: np.concatenate(xs) if xs else np.array([])  # noqa: E731
-        dynamics = DynamicsData(
-            dt=cat(dyn["dt"]),
-            time=cat(dyn["time"]),
-            mu=cat(dyn["mu"]).T if dyn["mu"] else None,
-            theta=cat(dyn["theta"]).T if dyn["theta"] else None,
-            pcg_iterations=cat(dyn["iters"]),
-            screening_iterations=cat(dyn["scr"]) if self.screening is not None else None,
-        )
-        solution = Solution(
-            device=self.device,
-            options=opts,
-            saved_steps=saved,
-            dynamics=dynamics,
-            dynamic_vector_potential=self.dynamic_vector_potential,
-            dynamic_epsilon=self.dynamic_epsilon,
-            applied_vector_potential=self.applied_vector_potential,
-            terminal_currents=self.terminal_currents,
-            disorder_epsilon=self.disorder_epsilon,
-            total_seconds=total,
-            stats=dict(
-                steps_thermalizing=n_steps["Thermalizing"],
-                steps_simulating=n_steps["Simulating"],
-                mean_pcg_iterations=float(dynamics.pcg_iterations.mean()) if len(dynamics.pcg_iterations) else 0.0,
-                # which mu solve the mesh size selected (hipcore.TDGLContext.build_poisson)
-                mu_solver=("direct (substructured)" if getattr(self.ctx, "substructure", None) else
-                           "direct (dense inverse)" if getattr(self.ctx, "dense_direct", False) else
-                           "pcg (AMG V-cycle or fp32-stored nested-dissection factors, by predicted cost)"
-                           if getattr(self.ctx, "precond_direct", None) else "amg_pcg"),
-                # the direct solves' in-loop guard: largest ||b - A mu|| / ||b|| over the checked steps
-                # (one per batch of queued attempts), how many were checked, and whether a check above
-                # 1e-9 sent the run back to AMG-PCG (never observed; the factors deliver 1e-14)
-                **{"mu_residual_" + k: v for k, v in self.ctx.direct_stats().items()},
-            ),
+        solution = rec.solution(
+            _time.perf_counter() - t_start,
+            # which mu solve the mesh size selected (hipcore.TDGLContext.build_poisson)
+            mu_solver=("direct (substructured)" if getattr(self.ctx, "substructure", None) else
+                       "direct (dense inverse)" if getattr(self.ctx, "dense_direct", False) else
+                       "pcg (AMG V-cycle or fp32-stored nested-dissection factors, by predicted cost)"
+                       if getattr(self.ctx, "precond_direct", None) else "amg_pcg"),
+            # the direct solves' in-loop guard: largest ||b - A mu|| / ||b|| over the checked steps
+            # (one per batch of queued attempts), how many were checked, and whether a check above
+            # 1e-9 sent the run back to AMG-PCG (never observed; the factors deliver 1e-14)
+            **{"mu_residual_" + k: v for k, v in self.ctx.direct_stats().items()},
         )
         if handler is not None:
             solution.path = handler.output_path
-            solution.saved_step_index = saved_meta  # (step, time) of every group data/<k> on disk
+            solution.saved_step_index = rec.saved_meta  # (step, time) of every group data/<k> on disk
             write_solution_group(handler.output_file, solution)  # solver.py:815-826 -> Solution.to_hdf5()
             handler.close()
         return solution
