@@ -724,6 +724,11 @@ int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, double *out_dt,
  * were repeated with a smaller dt (solver.py:475-485), PCG iterations, host synchronisations,
  * nanoseconds the host was blocked in them, nanoseconds inside tdgl_run}. */
 int tdgl_get_step_stats(tdgl_ctx *ctx, int64_t *out6, int32_t reset);
+/* ... and how often J_s / J_n were formed since the last reset, by the loop with one synchronisation per step or on
+ * request (tdgl_get_state): with currents every step, one formation per accepted step -- in front of the next step's psi
+ * update, inside its launch, or behind the first status copy of its mu solve, and when tdgl_run returns.  The run-ahead
+ * loop's predicated launches are not counted. */
+int tdgl_get_edge_current_launches(tdgl_ctx *ctx, int64_t *count, int32_t reset);
 /* In-loop guard of the direct mu solves (explicit inverses are otherwise checked once, at set-up): once per
  * batch of queued attempts (one synchronisation per step: every 64th step) the residual of an accepted
  * step's solve, ||b - A mu|| / ||b|| with the resident level-0 matrix, is measured -- two small launches.

@@ -211,16 +211,20 @@ double GuessBasis::residual_estimate(const double *c) const {
 // one; returns its slot (x[slot], y[slot] are the caller's to fill).  The Gram row of the new pair
 // y_new = (b - mean) - r_final comes with the next solve's dot-product pass: until then the placeholders below --
 // y_j . b, off by y_j . r_final -- are never used.
-int GuessBasis::push(int window) {
+// The slot itself is known beforehand (next_slot): a solution may be written there before the host has decided
+// that it joins -- the slot is free, or holds the oldest vector, which the guess of this solve has already used.
+int GuessBasis::next_slot(int window) const {
+    if (count >= window) return slot[0];
+    bool used[GK] = {false};
+    for (int i = 0; i < count; ++i) used[slot[i]] = true;
     int s = 0;
-    if (count >= window) {
-        s = slot[0];
-        drop_oldest(1);
-    } else {
-        bool used[GK] = {false};
-        for (int i = 0; i < count; ++i) used[slot[i]] = true;
-        while (used[s]) ++s;
-    }
+    while (used[s]) ++s;
+    return s;
+}
+
+int GuessBasis::push(int window) {
+    const int s = next_slot(window);
+    if (count >= window) drop_oldest(1);
     const int k = count;
     slot[k] = s;
     for (int j = 0; j < k; ++j)

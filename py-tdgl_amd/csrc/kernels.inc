@@ -1897,11 +1897,15 @@ __global__ __launch_bounds__(BLOCK) void k_combine(int64_t n, VecSet vs, double 
 
 // End of a solve: zero-mean gauge (as k_shift_mean), copy into the window slot, and the image of the
 // solution y = A x = (b - mean b) - r  (r: the residual the CG recurrence ended with) into its slot.
+// guard (the PCG scalars, or NULL): queued before the host has seen the residual -- the kernel holds back unless the
+// scalars the status kernel has just written say what the host is about to read from their copy: converged
+// (poisson.inc: cg_iterate takes the same decision from the same numbers).
 __global__ __launch_bounds__(BLOCK) void k_finish_solution(int64_t n_real, const double *__restrict__ partial_mean,
                                                            double inv_count, double *__restrict__ x,
                                                            const double *__restrict__ b, double b_mean,
                                                            const double *__restrict__ r, double *__restrict__ slot_x,
-                                                           double *__restrict__ slot_y) {
+                                                           double *__restrict__ slot_y, const double *__restrict__ guard) {
+    if (guard && !(guard[S_CONV_IT] >= 0.0 || guard[S_RR] <= guard[S_TOL2])) return;
     const double mean = sum_partials(partial_mean) * inv_count;
     for (int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x; i < n_real; i += (int64_t)gridDim.x * BLOCK) {
         const double v = x[i] - mean;

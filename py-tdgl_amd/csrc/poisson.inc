@@ -1250,20 +1250,37 @@ extern "C" int tdgl_set_direct_guard(tdgl_ctx *ctx, double limit) {
 
 // The host's look at the stream: the status block travels to the host, which waits for it (stat_wait_ns,
 // stat_host_syncs).  guard: the scalars of the direct solve's residual check ride behind the status block.
-static int sync_status(tdgl_ctx *ctx, bool guard = false) {
+// shadow: launches on ctx->stream that the step needs whatever the host is about to decide.  They are queued behind
+// the copy and run while it lands, the host wakes and does its arithmetic, and its next launch reaches the device:
+// the host then waits for an event recorded right behind the copy, not for the stream.
+struct NoShadow {
+    int operator()() const { return TDGL_OK; }
+};
+template <class S>
+static int sync_status(tdgl_ctx *ctx, bool guard, S shadow) {
+    constexpr bool shadowed = !std::is_same<S, NoShadow>::value;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status, ctx->d_status.p, sizeof(StepStatus), hipMemcpyDeviceToHost, ctx->stream));
     if (guard) direct_guard_fetch(ctx);
+    if (shadowed) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_status, ctx->stream));
+        TDGL_TRY(shadow());
+    }
     const int64_t t0 = now_ns();
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    const hipError_t e = shadowed ? hipEventSynchronize(ctx->ev_status) : hipStreamSynchronize(ctx->stream);
     ctx->stat_wait_ns += now_ns() - t0;
     ctx->stat_host_syncs += 1;
     HIP_TRY(ctx, e);
     return TDGL_OK;
 }
+static int sync_status(tdgl_ctx *ctx, bool guard = false) { return sync_status(ctx, guard, NoShadow{}); }
 
-static int fetch_scalars(tdgl_ctx *ctx, bool guess_start = false, const double *rr_part = nullptr) {
+template <class S>
+static int fetch_scalars(tdgl_ctx *ctx, bool guess_start, const double *rr_part, S shadow) {
     publish_status(ctx, guess_start, rr_part);
-    return sync_status(ctx);
+    return sync_status(ctx, false, shadow);
+}
+static int fetch_scalars(tdgl_ctx *ctx, bool guess_start = false, const double *rr_part = nullptr) {
+    return fetch_scalars(ctx, guess_start, rr_part, NoShadow{});
 }
 
 // mu = G b in one launch sequence (tdgl_poisson_set_dense_inverse / _substructure).  In the time loop (in_step) the
@@ -1347,6 +1364,12 @@ struct CgRun {
     int predicted;             // size of the run's first batch
     bool rr_reduced = true;    // the residual partials the next iteration reads are already global
     bool sum_x_fresh = false;  // part_tmp holds the partials of sum x (left by k_update_xr)
+    // The end of the solve (k_finish_solution) rides behind the status copy of every look after a batch, guarded on the
+    // device by the scalars that copy carries (pcg_solve sets these three; finish_slot < 0: off)
+    int finish_slot = -1;      // the window slot GuessBasis::push will hand out
+    double b_mean = 0.0;       // mean of b, still inside it
+    bool finish_queued = false;  // a look carried it
+    bool finished = false;     // ... and the scalars the host received say that the kernel did its work
     int pd_its = -1;           // iterations taken with the factors before a hand-over to the V-cycle (-1: none)
     double pd_rr_end = 0.0;    // ... and the squared residual they left
 
@@ -1506,7 +1529,21 @@ static int cg_iterate(CgRun &run, double tol2, int &it, double &rr) {
         if (it - chunk != run.it0) ctx->stat_pcg_extra_syncs += 1;  // not the first batch of this CG run
         TDGL_TRY(comm_allreduce(ctx, run.part_rr[it & 1], NB, 0));  // the host looks at it now
         run.rr_reduced = true;
-        TDGL_TRY(fetch_scalars(ctx, false, run.part_rr[it & 1]));  // also scal[S_RR] = sum of the partials
+        if (run.finish_slot >= 0 && run.sum_x_fresh) {
+            // (also scal[S_RR] = sum of the partials, which the guard of the shadow reads)
+            TDGL_TRY(fetch_scalars(ctx, false, run.part_rr[it & 1], [&]() {
+                hipLaunchKernelGGL(k_finish_solution, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, ctx->n_own,
+                                   (const double *)ctx->part_tmp.p, 1.0 / (double)ctx->n_global, run.x, (const double *)run.b, run.b_mean,
+                                   (const double *)run.r, ctx->guess.x[run.finish_slot].p, ctx->guess.y[run.finish_slot].p,
+                                   (const double *)ctx->scal.p);
+                return TDGL_OK;
+            }));
+            run.finish_queued = true;
+            const double *sc = ctx->h_status->scal;  // (the kernel's own test, on the copy of the numbers it read)
+            run.finished = sc[S_CONV_IT] >= 0.0 || sc[S_RR] <= sc[S_TOL2];
+        } else {
+            TDGL_TRY(fetch_scalars(ctx, false, run.part_rr[it & 1]));  // also scal[S_RR] = sum of the partials
+        }
         rr = ctx->h_status->scal[S_RR];
         if (ctx->h_status->scal[S_CONV_IT] >= 0.0) {  // converged inside the batch: the rest was frozen
             it = (int)ctx->h_status->scal[S_CONV_IT];
@@ -1654,7 +1691,19 @@ static int pcg_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool al
         hipLaunchKernelGGL(k_status_unpack, dim3(1), dim3(64), 0, ctx->stream, ctx->d_gstat.p, ctx->status_dev);
         ctx->psi_status_pending = false;  // d_status now holds the all-reduced outcome
     }
-    TDGL_TRY(fetch_scalars(ctx, proj));
+    // The edge currents the previous step owes (run.inc: shadow_currents) fill the wait: they read the accepted psi and
+    // mu^n, which nothing queued so far has written -- the psi update writes the other buffer, mu changes after this
+    // look.  A psi retry comes back here for the same step with nothing owed any more.
+    if (ctx->shadow_currents && ctx->currents_deferred) {
+        TDGL_TRY(fetch_scalars(ctx, proj, nullptr, [&]() {
+            launch_edge_currents(ctx, ctx->psi[ctx->loop.cur].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
+            ctx->currents_deferred = false;
+            ctx->currents_valid = true;
+            return TDGL_OK;
+        }));
+    } else {
+        TDGL_TRY(fetch_scalars(ctx, proj));
+    }
     // The Gram row of the window's newest vector arrived with this status block.  Taken BEFORE an abandoned
     // solve returns: a second pcg_solve for the same step (after a psi retry) would compute it again, which
     // is harmless, but a window change in between would not be.
@@ -1729,18 +1778,29 @@ static int pcg_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool al
     if (run.coarse32) TDGL_TRY(ensure_coarse_f32(ctx));
     run.it0 = 0;
     run.budget = ctx->popt.max_iter;
+    // (the finish behind the look: one GPU -- the sums of the gauge and of the residual are complete as they stand)
+    if (proj && !distributed(ctx) && !ctx->sync_shadow_disabled) {
+        run.finish_slot = guess.next_slot(guess_window(ctx));
+        run.b_mean = b_mean;
+    }
     do {  // the phases: one CG run each
         TDGL_TRY(cg_iterate(run, tol2, it, rr));
-    } while (rr > tol2 && next_phase(run, it));
+    } while (rr > tol2 && !run.finished && next_phase(run, it));
     // zero-mean gauge, then ghost values of the solution for the edge kernels / next step
+    const bool joins = proj && !(rr > tol2);
+    if (run.finished != (joins && run.finish_queued))  // (cannot happen: both sides test the same numbers)
+        TDGL_FAIL(ctx, TDGL_ERR_PCG, "Poisson solve: the device and the host disagree on convergence (rr %.17g, tol2 %.17g)", rr, tol2);
     if (!run.sum_x_fresh)
         hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, x, (const double *)nullptr, ctx->part_tmp.p);
     TDGL_TRY(comm_allreduce(ctx, ctx->part_tmp.p, NB, 0));
-    if (proj && !(rr > tol2)) {
-        // the solution joins the projection basis (replacing the oldest vector of a full window)
+    if (joins) {
+        // the solution joins the projection basis (replacing the oldest vector of a full window): the commit of
+        // what the finish behind the last look has already written, or the finish itself
         const int slot = guess.push(guess_window(ctx));
-        hipLaunchKernelGGL(k_finish_solution, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, (const double *)ctx->part_tmp.p,
-                           inv_n, x, (const double *)b, b_mean, (const double *)r, guess.x[slot].p, guess.y[slot].p);
+        if (!run.finished)
+            hipLaunchKernelGGL(k_finish_solution, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, (const double *)ctx->part_tmp.p,
+                               inv_n, x, (const double *)b, b_mean, (const double *)r, guess.x[slot].p, guess.y[slot].p,
+                               (const double *)nullptr);
     } else {
         hipLaunchKernelGGL(k_shift_mean, dim3(gv), dim3(BLOCK), 0, ctx->stream, no, ctx->part_tmp.p, inv_n, x);
     }

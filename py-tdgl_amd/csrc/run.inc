@@ -39,6 +39,15 @@ extern "C" int tdgl_get_step_stats(tdgl_ctx *ctx, int64_t *out6, int32_t reset) 
     return TDGL_OK;
 }
 
+// ... and how often J_s / J_n were formed by the loop with one synchronisation per step or on request (a launch of
+// k_edge_currents, or the psi update that carries them); the run-ahead loop's predicated launches are not counted
+extern "C" int tdgl_get_edge_current_launches(tdgl_ctx *ctx, int64_t *count, int32_t reset) {
+    if (!ctx || !count) return TDGL_ERR_ARG;
+    *count = ctx->stat_edge_launches;
+    if (reset) ctx->stat_edge_launches = 0;
+    return TDGL_OK;
+}
+
 extern "C" int tdgl_get_loop_state(tdgl_ctx *ctx, int64_t *step, double *time, double *runner_dt,
                                    double *tentative_dt) {
     if (!ctx) return TDGL_ERR_ARG;
@@ -175,8 +184,17 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
     // are not launched on their own but ride in the NEXT step's psi-update launch (same inputs: the
     // accepted psi and mu), or are formed when tdgl_run returns -- one launch less per step.
     const bool defer_currents = dense_on(ctx) && ctx->popt.edge_currents_every_step != 0 && !ctx->loop.ramp_on && !ctx->loop.has_dadt;
+    // Iterative solve on one GPU: the edge currents of an accepted step are not launched in front of the next step's
+    // psi update but behind the first status copy of its solve (pcg_solve), where the GPU would otherwise wait for the
+    // host, or when tdgl_run returns -- every reader of J outside tdgl_run therefore finds them formed.  The old order
+    // stays with: an extrapolated guess (k_extrapolate writes mu before that look), field ramps and dA/dt (the links
+    // change at step begin), screening (its own loop above), one process per GPU, the dense and run-ahead paths
+    // (they have no such look; see defer_currents), currents not formed every step, and TDGL_NO_SYNC_SHADOW.
+    const bool shadow_currents = !ctx->sync_shadow_disabled && !dense_on(ctx) && !distributed(ctx) && !ctx->levels.empty() &&
+                                 ctx->popt.extrapolate >= 3 && ctx->popt.edge_currents_every_step != 0 && !ctx->loop.ramp_on &&
+                                 !ctx->loop.has_dadt;
     for (bool first = true;; first = false) {
-        if (ctx->currents_deferred && mu_n == ctx->mu.p) {
+        if (ctx->currents_deferred && mu_n == ctx->mu.p && !shadow_currents) {
             launch_psi_update_with_currents(ctx, ctx->psi[cur].p, mu_n, ctx->lap[cur].p, dt, ctx->psi[nxt].p);
             ctx->currents_deferred = false;
             ctx->currents_valid = true;
@@ -240,6 +258,7 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
         // after a failed psi update they hold scratch values until the repeated step rewrites them)
         ctx->spec_currents = ctx->popt.edge_currents_every_step != 0 && !defer_currents;
         ctx->spec_currents_done = false;
+        ctx->shadow_currents = shadow_currents;
         const int solve_status = pcg_solve(
             ctx,
             [&](const StepStatus *st) {
@@ -252,6 +271,7 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
             &abandoned, /*allow_projection=*/true);
         ctx->defer_mu_halo = false;
         ctx->spec_currents = false;
+        ctx->shadow_currents = false;
         if (ctx->spec_currents_done && (failed || solve_status != TDGL_OK)) ctx->currents_valid = false;
         // A step that ends in an error must leave the accepted state behind: the extrapolation
         // moved mu^n to mu_prev and wrote a guess into mu.  Put mu^n back (the history is dropped:
@@ -298,8 +318,8 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
     ctx->currents_valid = false;
     if (ctx->spec_currents_done) {
         ctx->currents_valid = true;  // already queued by the direct solve
-    } else if (defer_currents) {
-        ctx->currents_deferred = true;  // with the next psi update, or when tdgl_run returns
+    } else if (defer_currents || shadow_currents) {
+        ctx->currents_deferred = true;  // with the next psi update / behind the next solve's first look, or when tdgl_run returns
     } else if (ctx->popt.edge_currents_every_step) {
         if (ctx->pend_v) {  // ghost values of mu still travelling: edges between owned sites first
             launch_edge_currents(ctx, ctx->psi[nxt].p, ctx->mu.p, ctx->js.p, ctx->jn.p, 1);

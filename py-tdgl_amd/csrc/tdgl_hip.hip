@@ -171,6 +171,7 @@ extern "C" void tdgl_destroy(tdgl_ctx *ctx) {
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev_pack) (void)hipEventDestroy(ctx->ev_pack);
     if (ctx->ev_halo) (void)hipEventDestroy(ctx->ev_halo);
+    if (ctx->ev_status) (void)hipEventDestroy(ctx->ev_status);
     if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
     for (auto &pr : ctx->prof_pending) {
         (void)hipEventDestroy(pr.first);
@@ -367,8 +368,9 @@ static int create_impl(tdgl_ctx *ctx, const tdgl_mesh_desc *d) {
     // synchronisation.
     HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_status), sizeof(StepStatus)));
     memset(ctx->h_status, 0, sizeof(StepStatus));
-    // (the three environment switches of the library: what the test-suite needs to reach a code path -- DESIGN.md section 5)
+    // (the environment switches of the library: what the test-suite needs to reach a code path -- DESIGN.md section 5)
     ctx->run_ahead_disabled = getenv("TDGL_NO_RUN_AHEAD") != nullptr;
+    ctx->sync_shadow_disabled = getenv("TDGL_NO_SYNC_SHADOW") != nullptr;
     if (const char *e = getenv("TDGL_PCG_PREDICT")) ctx->pcg_predict_from_guess = strcmp(e, "last") != 0;
     ctx->status_dev = ctx->d_status.p;
     HIP_TRY(ctx, ctx->scal.alloc(S_COUNT));
@@ -389,6 +391,7 @@ static int create_impl(tdgl_ctx *ctx, const tdgl_mesh_desc *d) {
     HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_pack, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_halo, hipEventDisableTiming));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_status, hipEventDisableTiming));
     return TDGL_OK;
 }
 
@@ -513,6 +516,7 @@ static void launch_psi_update_with_currents(tdgl_ctx *ctx, const double2 *psi, c
                        ctx->psi_blocks, ctx->n_own, psi, mu, ctx->eps.p, lap, dt, ctx->u, ctx->gamma, psi_new,
                        ctx->psi_dmax_part.p, ctx->psi_fail_part.p, ctx->m, ctx->e0.p, ctx->e1.p, ctx->e_inv_len.p,
                        ctx->e_U.p, ctx->js.p, ctx->jn.p);
+    ctx->stat_edge_launches += 1;
     ctx->psi_status_pending = true;
 }
 
@@ -586,6 +590,7 @@ static void launch_edge_currents(tdgl_ctx *ctx, const double2 *psi, const double
                                  double *jn, int part = 0) {
     const int64_t base = (part == 2) ? ctx->m_int : 0, end = (part == 1) ? ctx->m_int : ctx->m;
     if (end <= base) return;
+    if (part != 2) ctx->stat_edge_launches += 1;  // (parts 1 and 2 together form the currents once)
     const int grid = grid_for(end - base);
     const double *dadt = ctx->loop.has_dadt ? ctx->e_dAdt.p : (const double *)nullptr;
     if (js && jn)

@@ -17,6 +17,7 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "tdgl_hip.h"
@@ -320,6 +321,7 @@ struct GuessBasis {
     void load_rhs(const StepStatus *st, int64_t n_global);
     int solve(double cut, double *c) const;
     double residual_estimate(const double *c) const;
+    int next_slot(int window) const;  // where push will put the next solution: a free slot, or the oldest vector's
     int push(int window);
     const double *newest_x() const { return count > 0 ? x[slot[count - 1]].p : nullptr; }
 
@@ -576,6 +578,13 @@ struct tdgl_ctx {
     bool run_ahead_disabled = false;      // TDGL_NO_RUN_AHEAD, read once when the context is created (tests, A/B runs)
     int64_t stat_ra_batches = 0, stat_ra_dead = 0;
     bool currents_deferred = false;       // J of the last accepted step ride in the next step's psi-update launch
+                                          // (dense path) or behind its first status copy (iterative path, run.inc)
+    // Work queued behind a status copy while the host waits for it (poisson.inc: sync_status).  TDGL_NO_SYNC_SHADOW,
+    // read once when the context is created, restores the order without it (tests, A/B runs).
+    bool sync_shadow_disabled = false;
+    hipEvent_t ev_status = nullptr;       // recorded right behind the status copy: the host waits for it, not for the stream
+    bool shadow_currents = false;         // step driver: the owed currents may follow this solve's first status copy
+    int64_t stat_edge_launches = 0;       // formations of J_s / J_n since the last reset (tdgl_get_edge_current_launches)
     bool spec_currents = false;           // step driver: queue the edge currents right behind the dense solve,
     bool spec_currents_done = false;      // before the host has seen the step's status (run.inc)
     // collapsed coarse chain (tdgl_poisson_set_collapsed_tail): everything from level `tail_level`

@@ -353,6 +353,7 @@ SIGNATURES = {
     "tdgl_field_plan_eval": (C.c_int, [C.c_void_p, C.c_int32, c_f64p, C.c_int32, c_f64p, c_f64p, c_f64p]),
     "tdgl_field_plan_stats": (C.c_int, [C.c_void_p, c_i64p, c_f64p]),
     "tdgl_get_step_stats": (C.c_int, [_CTX, C.POINTER(C.c_int64), C.c_int32]),
+    "tdgl_get_edge_current_launches": (C.c_int, [_CTX, C.POINTER(C.c_int64), C.c_int32]),
     "tdgl_get_direct_stats": (C.c_int, [_CTX, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "tdgl_set_direct_guard": (C.c_int, [_CTX, C.c_double]),
     "tdgl_get_loop_state": (

@@ -1283,12 +1283,15 @@ class TDGLContext:
         return A
 
     def step_stats(self, reset=False):
-        """``dict(steps, psi_retries, pcg_iterations, host_syncs, host_wait_s, run_s)`` of `run` since the
-        last reset (``host_wait_s``: time blocked in the synchronisations; ``run_s``: time inside `run`)."""
+        """``dict(steps, psi_retries, pcg_iterations, host_syncs, host_wait_s, run_s, edge_current_launches)`` of
+        `run` since the last reset (``host_wait_s``: time blocked in the synchronisations; ``run_s``: time inside
+        `run`; ``edge_current_launches``: how often J_s / J_n were formed outside the run-ahead loop)."""
         out = (C.c_int64 * 6)()
         self._chk(self._lib.tdgl_get_step_stats(self._ctx, out, int(bool(reset))))
+        edge = C.c_int64(0)
+        self._chk(self._lib.tdgl_get_edge_current_launches(self._ctx, C.byref(edge), int(bool(reset))))
         return dict(steps=out[0], psi_retries=out[1], pcg_iterations=out[2], host_syncs=out[3],
-                    host_wait_s=out[4] * 1e-9, run_s=out[5] * 1e-9)
+                    host_wait_s=out[4] * 1e-9, run_s=out[5] * 1e-9, edge_current_launches=edge.value)
 
     def direct_stats(self):
         """In-loop guard of the direct mu solves: ``dict(max, checks, fell_back)`` -- the largest
