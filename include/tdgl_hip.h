@@ -563,10 +563,20 @@ int tdgl_update_link_exponents(tdgl_ctx *ctx, const double *A_new, double dt_pre
  *   tdgl_set_link_ramp            lets tdgl_run evaluate the factor itself before every step:
  *                                 f(t) = initial + (final - initial) * clip((t - tmin)/(tmax - tmin), 0, 1)
  *                                 (LinearRamp), with dt_prev = Runner.dt; on = 0 switches it off.
+ *   tdgl_set_link_table           the same with the factor as a piecewise-linear table: f(t) linear between the nodes
+ *                                 (times[k], values[k]), k < n_nodes, constant before the first and after the last
+ *                                 (times strictly increasing, everything finite) -- an up-and-down sweep, ramp-hold-ramp,
+ *                                 a pulse, a sampled AC field.  Call it after tdgl_set_link_exponents_base.  The
+ *                                 run-ahead loop evaluates it on the device with the host's arithmetic, operation for
+ *                                 operation, so both loops agree to the last bit as they do for the ramp; while the
+ *                                 factor rests on a plateau nothing is recomputed, and from the last node on the run
+ *                                 costs what a static one does.  n_nodes = 0 switches the table off.  A table and a
+ *                                 ramp exclude each other: the later call wins.
  *   tdgl_get_link_scale           the factor of the current A (for saving A_applied). */
 int tdgl_set_link_exponents_base(tdgl_ctx *ctx, const double *A_base, double scale);
 int tdgl_update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev);
 int tdgl_set_link_ramp(tdgl_ctx *ctx, int32_t on, double tmin, double tmax, double initial, double final_value);
+int tdgl_set_link_table(tdgl_ctx *ctx, int32_t n_nodes, const double *times, const double *values);
 int tdgl_get_link_scale(tdgl_ctx *ctx, double *scale);
 /* self.epsilon (solver.py:191-216, 645-648). */
 int tdgl_set_epsilon(tdgl_ctx *ctx, const double *epsilon);
@@ -810,8 +820,8 @@ int tdgl_guess_dots(tdgl_ctx *ctx, int32_t k, int64_t n, const double *vectors, 
  * and Runner clock (time, stage step, adaptive dt, retries).  One round of the loop is one attempt of every live
  * replica in five launches over all of them (dense inverse; 6 + 2 per level with the substructured factors); the host synchronises once per batch of rounds.  The per-replica
  * setters form their input with the context's own entry point of the same name and copy it: the context's own run
- * state is overwritten.  Time-dependent inputs are the three forms the run-ahead loop evaluates on the device: a
- * replica's field ramp (tdgl_ensemble_set_link_ramp), tabulated terminal currents and separable epsilon, each
+ * state is overwritten.  Time-dependent inputs are the forms the run-ahead loop evaluates on the device: a
+ * replica's field ramp (tdgl_ensemble_set_link_ramp) or field table (tdgl_ensemble_set_link_table), tabulated terminal currents and separable epsilon, each
  * evaluated at the replica's own time; no per-step host input, no screening.  Release the ensemble before the
  * context. */
 typedef struct tdgl_ensemble tdgl_ensemble;
@@ -829,16 +839,21 @@ int tdgl_ensemble_set_state(tdgl_ensemble *ens, int32_t r, const double *psi, co
 int tdgl_ensemble_set_controller(tdgl_ensemble *ens, int32_t r, const tdgl_controller *c);
 int tdgl_ensemble_begin_stage(tdgl_ensemble *ens, int32_t r);
 /* Time dependence of replica r, with the rules of the context's entry point of the same name.  A failed call leaves
- * the replica's previous tables untouched (a failed set_link_ramp leaves it without links).
+ * the replica's previous tables untouched (a failed set_link_ramp or set_link_table leaves it without links).
  * set_link_ramp: A(t) = LinearRamp(tmin, tmax, initial, final)(t) * A_base [n_edges, 2]; sets the links to their
  *   value at t = 0 and moves them before the first attempt of every step inside tdgl_ensemble_run (dA/dt with the
  *   previous step's dt, the link variables only where A moved beyond np.allclose's tolerance).
  *   tdgl_ensemble_set_link_exponents switches the ramp off.  get_link_scale: the factor of the last step taken.
+ * set_link_table: A(t) = table(t) * A_base [n_edges, 2] with the table of tdgl_set_link_table (n_nodes >= 1, which may
+ *   differ between replicas); otherwise as set_link_ramp, which it replaces for the replica and which replaces it.
+ *   tdgl_ensemble_set_link_exponents switches the table off.
  * set_mu_boundary_table: terminal current densities as piecewise-linear tables (tdgl_set_mu_boundary_table);
  *   n_nodes may differ between replicas; n_nodes = 0: off.
  * set_epsilon_table: epsilon(r, t) = factor(t) epsilon0(r) (tdgl_set_epsilon_table); n_nodes = 0: off. */
 int tdgl_ensemble_set_link_ramp(tdgl_ensemble *ens, int32_t r, const double *A_base, double tmin, double tmax,
                                 double initial, double final_);
+int tdgl_ensemble_set_link_table(tdgl_ensemble *ens, int32_t r, const double *A_base, int32_t n_nodes, const double *times,
+                                 const double *values);
 int tdgl_ensemble_get_link_scale(tdgl_ensemble *ens, int32_t r, double *scale);
 int tdgl_ensemble_set_mu_boundary_table(tdgl_ensemble *ens, int32_t r, int32_t n_nodes, const double *times,
                                         int32_t n_groups, const int32_t *group_ptr, const int32_t *group_pos,

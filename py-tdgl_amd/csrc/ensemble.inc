@@ -200,21 +200,29 @@ __global__ void k_ens_probes(int n_probe, const int32_t *__restrict__ sites, con
 }
 
 // ---- time-dependent inputs per replica, queued in front of K1 (run.inc's run-ahead loop, the replica as grid.y) ----
-// A replica's field ramp A(t) = LinearRamp(t) A_base moves in three launches over the ramping replicas -- R1 ramp
-// begin (ramp_begin_body), R2 A, A_prev, dA/dt and "did it move" (ramp_link_body), R3 ceff with the dA/dt term and
+// A replica's field ramp A(t) = LinearRamp(t) A_base, or its field table A(t) = table(t) A_base, moves in three launches
+// over the ramping replicas -- R1 ramp begin (ramp_begin_body / table_begin_body), R2 A, A_prev, dA/dt and "did it
+// move" (ramp_link_body), R3 ceff with the dA/dt term and
 // the link variables (ceff_body, link_variable_body) -- and two more rebuild what depends on the links: R4 the
 // covariant-Laplacian values (fill_laplacian_body) and R5 L psi^n with them (psi_laplacian_body).  Retries, dead
 // replicas and replicas whose ramp does not move this step return at once (ramp_do, moved).  Tabulated terminal
 // currents (T1, mu_table_body: one workgroup per replica) and separable epsilon (T2, eps_table_body) are evaluated at
 // the replica's own time.  Every body is the single run's, so each replica's arithmetic is its run-ahead loop's.
 
-// R1: one thread per replica (a replica that is not ramping in this batch: ramp_do = 0, as the single run that
-// queues no ramp launch at all)
-__global__ void k_ens_ramp_begin(int R, StepCtl *__restrict__ ctl, const int32_t *__restrict__ ramping, int32_t *__restrict__ moved) {
+// R1: one thread per replica.  kind[r] says where the replica's factor comes from in this batch: LINK_RAMP the ramp in its
+// controller (ramp_begin_body), LINK_TABLE its table (table_begin_body: nodes l_off[r] .. l_off[r + 1] of the pools),
+// LINK_NONE nothing moves: ramp_do = 0, as the single run that queues no ramp launch at all
+enum : int32_t { LINK_NONE = 0, LINK_RAMP = 1, LINK_TABLE = 2 };
+__global__ void k_ens_ramp_begin(int R, StepCtl *__restrict__ ctl, const int32_t *__restrict__ kind, const int32_t *__restrict__ l_off,
+                                 const double *__restrict__ times, const double *__restrict__ values, int32_t *__restrict__ moved) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
-    if (ramping[r])
+    const int32_t k = kind[r];
+    const int t0 = l_off[r], nn = l_off[r + 1] - t0;
+    if (k == LINK_RAMP)
         ramp_begin_body(ctl + r);
+    else if (k == LINK_TABLE && nn > 0)
+        table_begin_body(ctl + r, times + t0, values + t0, nn);
     else
         ctl[r].ramp_do = 0;
     moved[r] = 0;
@@ -344,10 +352,10 @@ struct tdgl_ensemble {
     // time-dependent inputs (allocated when the first replica asks): per replica A_base, A, A_prev (2 m_pad), dA/dt
     // (m_pad), the boundary term before dA/dt (n_pad), mu_boundary (nb), epsilon0 (n_pad); the tables as pools
     DevBuf<double> Abase, A, Aprev, dadt, cvec, mu_b, eps0;
-    DevBuf<double> tab_mu_t, tab_mu_dens, tab_eps_t, tab_eps_f;
-    DevBuf<int32_t> tab_mu_toff, tab_mu_group, tab_eps_off, ramping, moved;
+    DevBuf<double> tab_mu_t, tab_mu_dens, tab_eps_t, tab_eps_f, tab_link_t, tab_link_v;
+    DevBuf<int32_t> tab_mu_toff, tab_mu_group, tab_eps_off, tab_link_off, ramping, moved;  // ramping: LINK_NONE / _RAMP / _TABLE of this batch
     DevBuf<int64_t> tab_mu_doff;
-    bool tables_dirty = false, any_mu_table = false, any_eps_table = false;
+    bool tables_dirty = true, any_mu_table = false, any_eps_table = false;  // (dirty: the pools and their offsets exist from the first run on)
     std::vector<int32_t> h_ramping;
     std::vector<StepCtl> h_ctl;
     std::vector<StepRec> h_rec;
@@ -531,20 +539,17 @@ extern "C" int tdgl_ensemble_set_link_exponents(tdgl_ensemble *e, int32_t r, con
     TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
     e->rep[r].have_links = true;
     e->rep[r].lap_valid = false;
-    e->rep[r].loop.ramp_on = e->rep[r].loop.has_dadt = false;
+    if (e->rep[r].loop.tabulated()) e->tables_dirty = true;
+    e->rep[r].loop.links_static();
+    e->rep[r].loop.has_dadt = false;
     return TDGL_OK;
 }
 
-// A(t) = LinearRamp(t) A_base for replica r (tdgl_set_link_exponents_base + tdgl_set_link_ramp of the context): the
-// links start at the ramp's value at t = 0 and move inside tdgl_ensemble_run
-extern "C" int tdgl_ensemble_set_link_ramp(tdgl_ensemble *e, int32_t r, const double *A_base, double tmin, double tmax, double initial,
-                                           double final_) {
-    TDGL_TRY(ens_check(e, r));
+// The arrays of a replica whose links move inside tdgl_ensemble_run, A(t) = f(t) A_base with f(0) = scale (the context's
+// tdgl_set_link_exponents_base): A_base, A = A_prev = scale A_base, dA/dt = 0, the links and the Laplacian values.  The
+// replica is without links and without ramp or table until the caller completes it.
+static int ens_set_link_base(tdgl_ensemble *e, int32_t r, const double *A_base, double scale) {
     tdgl_ctx *ctx = e->ctx;
-    if (!A_base) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_ramp: null A_base");
-    if (!(std::isfinite(tmin) && std::isfinite(tmax) && std::isfinite(initial) && std::isfinite(final_)))
-        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_ramp: the ramp's parameters must be finite");
-    if (!(tmax > tmin)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_ramp: tmax must be > tmin");
     EnsReplica &p = e->rep[r];
     const size_t R = (size_t)e->R;
     if (e->Abase.n == 0) {
@@ -559,8 +564,8 @@ extern "C" int tdgl_ensemble_set_link_ramp(tdgl_ensemble *e, int32_t r, const do
         e->dadt.take(dadt);
     }
     p.have_links = false;  // (until the replica's arrays are complete)
-    p.loop.ramp_on = false;
-    const double scale = linear_ramp_value(0.0, tmin, tmax, initial, final_);
+    if (p.loop.tabulated()) e->tables_dirty = true;
+    p.loop.links_static();
     TDGL_TRY(tdgl_set_link_exponents_base(ctx, A_base, scale));  // (A = scale A_base, A_prev = A, links, Laplacian values)
     const int64_t o2 = 2 * (int64_t)r * e->m_pad;
     TDGL_TRY(ens_copy(ctx, e->Abase.p + o2, ctx->e_Abase.p, 2 * e->m_pad));
@@ -569,11 +574,41 @@ extern "C" int tdgl_ensemble_set_link_ramp(tdgl_ensemble *e, int32_t r, const do
     HIP_TRY(ctx, hipMemset(e->dadt.p + r * e->m_pad, 0, e->m_pad * sizeof(double)));
     TDGL_TRY(ens_copy(ctx, e->U.p + r * e->m_pad, ctx->e_U.p, e->m_pad));
     TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
-    p.loop.set_ramp(true, tmin, tmax, initial, final_);
     p.loop.has_dadt = false;
     p.loop.link_scale = p.loop.link_scale_prev = scale;
-    p.have_links = true;
     p.lap_valid = false;
+    return TDGL_OK;
+}
+
+// A(t) = LinearRamp(t) A_base for replica r (tdgl_set_link_exponents_base + tdgl_set_link_ramp of the context): the
+// links start at the ramp's value at t = 0 and move inside tdgl_ensemble_run
+extern "C" int tdgl_ensemble_set_link_ramp(tdgl_ensemble *e, int32_t r, const double *A_base, double tmin, double tmax, double initial,
+                                           double final_) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    if (!A_base) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_ramp: null A_base");
+    if (!(std::isfinite(tmin) && std::isfinite(tmax) && std::isfinite(initial) && std::isfinite(final_)))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_ramp: the ramp's parameters must be finite");
+    if (!(tmax > tmin)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_ramp: tmax must be > tmin");
+    TDGL_TRY(ens_set_link_base(e, r, A_base, linear_ramp_value(0.0, tmin, tmax, initial, final_)));
+    e->rep[r].loop.set_ramp(true, tmin, tmax, initial, final_);
+    e->rep[r].have_links = true;
+    return TDGL_OK;
+}
+
+// A(t) = table(t) A_base for replica r (tdgl_set_link_exponents_base + tdgl_set_link_table of the context), with the
+// failure rules of tdgl_ensemble_set_link_ramp: the links start at the table's value at t = 0
+extern "C" int tdgl_ensemble_set_link_table(tdgl_ensemble *e, int32_t r, const double *A_base, int32_t n_nodes, const double *times,
+                                            const double *values) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    if (!A_base) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_table: null A_base");
+    TDGL_TRY(check_link_table(ctx, "tdgl_ensemble_set_link_table", n_nodes, times, values));
+    const std::vector<double> t(times, times + n_nodes);
+    TDGL_TRY(ens_set_link_base(e, r, A_base, table_value(t, values, 0.0)));
+    e->rep[r].loop.set_table(times, values, n_nodes);
+    e->rep[r].have_links = true;
+    e->tables_dirty = true;
     return TDGL_OK;
 }
 
@@ -631,9 +666,9 @@ static int ens_upload_tables(tdgl_ensemble *e) {
     tdgl_ctx *ctx = e->ctx;
     const int R = e->R;
     const int64_t nb = std::max<int64_t>(ctx->nb, 1);
-    std::vector<int32_t> toff(R + 1, 0), eoff(R + 1, 0), group((size_t)R * nb, -1);
+    std::vector<int32_t> toff(R + 1, 0), eoff(R + 1, 0), loff(R + 1, 0), group((size_t)R * nb, -1);
     std::vector<int64_t> doff(R, 0);
-    std::vector<double> mt, md, et, ef;
+    std::vector<double> mt, md, et, ef, lt, lv;
     e->any_mu_table = e->any_eps_table = false;
     for (int r = 0; r < R; ++r) {
         const EnsReplica &p = e->rep[r];
@@ -645,11 +680,17 @@ static int ens_upload_tables(tdgl_ensemble *e) {
         et.insert(et.end(), p.eps_t.begin(), p.eps_t.end());
         ef.insert(ef.end(), p.eps_f.begin(), p.eps_f.end());
         eoff[r + 1] = (int32_t)et.size();
+        if (p.loop.tabulated()) {
+            lt.insert(lt.end(), p.loop.tab_t.begin(), p.loop.tab_t.end());
+            lv.insert(lv.end(), p.loop.tab_v.begin(), p.loop.tab_v.end());
+        }
+        loff[r + 1] = (int32_t)lt.size();
         e->any_mu_table |= !p.mu_t.empty();
         e->any_eps_table |= !p.eps_t.empty();
     }
     if (mt.empty()) mt.push_back(0.0), md.push_back(0.0);  // (never read: every replica's node count is 0)
     if (et.empty()) et.push_back(0.0), ef.push_back(0.0);
+    if (lt.empty()) lt.push_back(0.0), lv.push_back(0.0);
     HIP_TRY(ctx, e->tab_mu_toff.upload(toff));
     HIP_TRY(ctx, e->tab_mu_doff.upload(doff));
     HIP_TRY(ctx, e->tab_mu_group.upload(group));
@@ -658,6 +699,9 @@ static int ens_upload_tables(tdgl_ensemble *e) {
     HIP_TRY(ctx, e->tab_eps_off.upload(eoff));
     HIP_TRY(ctx, e->tab_eps_t.upload(et));
     HIP_TRY(ctx, e->tab_eps_f.upload(ef));
+    HIP_TRY(ctx, e->tab_link_off.upload(loff));
+    HIP_TRY(ctx, e->tab_link_t.upload(lt));
+    HIP_TRY(ctx, e->tab_link_v.upload(lv));
     e->tables_dirty = false;
     return TDGL_OK;
 }
@@ -783,7 +827,7 @@ static void ens_queue_drives(tdgl_ensemble *e, bool ramping) {
     if (!ramping) return;
     const SellPattern &pat = ctx->lap_pat;
     hipLaunchKernelGGL(k_ens_ramp_begin, dim3((R + 63) / 64), dim3(64), 0, ctx->stream, (int)R, e->d_ctl.p, (const int32_t *)e->ramping.p,
-                       e->moved.p);
+                       (const int32_t *)e->tab_link_off.p, (const double *)e->tab_link_t.p, (const double *)e->tab_link_v.p, e->moved.p);
     const int nblk = grid_for(ctx->m);
     hipLaunchKernelGGL(k_ens_ramp_links, dim3(nblk, R), dim3(BLOCK), 0, ctx->stream, ctx->m, e->m_pad, (const double *)e->Abase.p, e->A.p,
                        e->Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
@@ -932,8 +976,8 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
             // a ramp that has reached its end: dA/dt is identically zero from here on, and a replica whose ramp has
             // settled costs what a static one does (as in tdgl_run)
             if (p.loop.ramp_settled()) p.loop.has_dadt = false;
-            e->h_ramping[r] = on && p.loop.ramping();
-            n_ramping += e->h_ramping[r];
+            e->h_ramping[r] = !(on && p.loop.ramping()) ? LINK_NONE : p.loop.tabulated() ? LINK_TABLE : LINK_RAMP;
+            n_ramping += e->h_ramping[r] != LINK_NONE;
             p.loop.fill(e->h_ctl[r], end_time[r], on);
             e->h_limit[r] = on ? (int32_t)std::min<int64_t>(max_steps[r] - steps_done[r], RA_BATCH_MAX) : 0;
         }

@@ -441,20 +441,22 @@ __host__ __device__ inline double linear_ramp_value(double t, double tmin, doubl
     return final_;
 }
 
+// the factor of this step is `scale` (update_link_scale: nothing moves when the factor has been constant over the last
+// two evaluations); 1: the links move
+__device__ __forceinline__ int link_scale_step(StepCtl *__restrict__ ctl, double scale) {
+    if (scale == ctl->link_scale && scale == ctl->link_scale_prev && ctl->has_dadt) return 0;
+    ctl->link_scale_prev = ctl->link_scale;
+    ctl->link_scale = scale;
+    ctl->has_dadt = 1;
+    return 1;
+}
+
 // (body: one thread per controller)
 __device__ __forceinline__ void ramp_begin_body(StepCtl *__restrict__ ctl) {
 #pragma clang fp contract(off)
     int go = 0;
-    if (!ctl->poisoned && ctl->retries == 0) {
-        const double scale = linear_ramp_value(ctl->time, ctl->ramp_tmin, ctl->ramp_tmax, ctl->ramp_initial, ctl->ramp_final);
-        // (update_link_scale: nothing moves when the factor has been constant over the last two evaluations)
-        if (!(scale == ctl->link_scale && scale == ctl->link_scale_prev && ctl->has_dadt)) {
-            ctl->link_scale_prev = ctl->link_scale;
-            ctl->link_scale = scale;
-            ctl->has_dadt = 1;
-            go = 1;
-        }
-    }
+    if (!ctl->poisoned && ctl->retries == 0)
+        go = link_scale_step(ctl, linear_ramp_value(ctl->time, ctl->ramp_tmin, ctl->ramp_tmax, ctl->ramp_initial, ctl->ramp_final));
     ctl->ramp_do = go;
 }
 
@@ -620,6 +622,24 @@ __device__ __forceinline__ double table_value_dev(const double *__restrict__ tim
     }
     const double t0 = times[hi - 1], t1 = times[hi];
     return v[hi - 1] + (v[hi] - v[hi - 1]) * ((time - t0) / (t1 - t0));
+}
+
+// The field factor as a table, A(t) = table(t) A_base (tdgl_set_link_table): ramp_begin_body with table_value_dev in the
+// place of linear_ramp_value -- the same step rule, so a plateau inside the table skips the link launches as a finished
+// ramp does, and link_scale_prev, link_scale, has_dadt and ramp_do are left as the ramp leaves them.  `times` and `values`
+// are the n_nodes >= 1 nodes of THIS controller's table.  (body: one thread per controller)
+__device__ __forceinline__ void table_begin_body(StepCtl *__restrict__ ctl, const double *__restrict__ times,
+                                                 const double *__restrict__ values, int n_nodes) {
+#pragma clang fp contract(off)
+    int go = 0;
+    if (!ctl->poisoned && ctl->retries == 0) go = link_scale_step(ctl, table_value_dev(times, values, n_nodes, ctl->time));
+    ctl->ramp_do = go;
+}
+
+__global__ void k_ra_table_begin(StepCtl *__restrict__ ctl, const double *__restrict__ times, const double *__restrict__ values,
+                                 int n_nodes) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    table_begin_body(ctl, times, values, n_nodes);
 }
 
 // Run-ahead loop with tabulated terminal currents (update_mu_boundary, solver.py:325-345, at the time of the step

@@ -434,8 +434,8 @@ static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out) {
 static bool run_ahead_ok(const tdgl_ctx *ctx) {
     const bool off = ctx->run_ahead_disabled;  // (TDGL_NO_RUN_AHEAD at tdgl_create)
     const tdgl_controller &ctl = ctx->loop.ctl;
-    // (a moving vector potential: only the ramp the loop evaluates itself rides along -- k_ra_ramp_begin --, and it
-    // needs the previous step's dt: from the second step of a stage on)
+    // (a moving vector potential: only the ramp or table the loop evaluates itself rides along -- k_ra_ramp_begin,
+    // k_ra_table_begin --, and it needs the previous step's dt: from the second step of a stage on)
     if (ctx->loop.ramping() ? !(ctx->loop.runner_dt > 0.0) : ctx->loop.has_dadt) return false;
     return !off && dense_on(ctx) && (ctx->direct->dense.tiles > 0) && !ctx->scr_enabled &&
            (ctx->tab_mu_t.empty() || ctx->tab_mu_on_device) && (ctx->tab_eps_t.empty() || ctx->tab_eps_on_device) &&
@@ -496,7 +496,13 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
                                    (const int32_t *)ctx->e1.p, (const double *)ctx->e_inv_len.p, (const double2 *)ctx->e_U.p,
                                    (const double2 *)ctx->psi[0].p, (const double2 *)ctx->psi[1].p, (const double *)ctx->mu.p, ctx->js.p, ctx->jn.p,
                                    (const double *)ctx->e_dAdt.p, (const StepCtl *)dc);
-            hipLaunchKernelGGL(k_ra_ramp_begin, dim3(1), dim3(64), 0, ctx->stream, dc);
+            if (ctx->loop.tabulated()) {
+                const int nn = (int)ctx->loop.tab_t.size();
+                hipLaunchKernelGGL(k_ra_table_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const double *)ctx->d_tab_link.p,
+                                   (const double *)ctx->d_tab_link.p + nn, nn);
+            } else {
+                hipLaunchKernelGGL(k_ra_ramp_begin, dim3(1), dim3(64), 0, ctx->stream, dc);
+            }
             const int nblk = grid_for(ctx->m);
             hipLaunchKernelGGL(k_ra_ramp_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, (const double *)ctx->e_Abase.p, ctx->e_A.p,
                                ctx->e_Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
@@ -650,7 +656,10 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
             // update_applied_vector_potential (solver.py:347-362, 626-642) for
             // A(t) = ramp(t) * A_base, ramp = tdgl/sources/scaling.py LinearRamp; dA/dt uses the
             // previous step's dt (Runner.dt)
-            const double scale = linear_ramp_value(ctx->loop.time, ctx->loop.ramp_tmin, ctx->loop.ramp_tmax, ctx->loop.ramp_initial, ctx->loop.ramp_final);
+            // (or a table in the ramp's place: tdgl_set_link_table)
+            const double scale = ctx->loop.tabulated()
+                                     ? table_value(ctx->loop.tab_t, ctx->loop.tab_v.data(), ctx->loop.time)
+                                     : linear_ramp_value(ctx->loop.time, ctx->loop.ramp_tmin, ctx->loop.ramp_tmax, ctx->loop.ramp_initial, ctx->loop.ramp_final);
             status = update_link_scale(ctx, scale, ctx->loop.runner_dt);
         }
         if (status == TDGL_OK) status = apply_time_tables(ctx);  // tabulated terminal currents / epsilon factor at this time

@@ -613,6 +613,8 @@ static void refresh_ceff(tdgl_ctx *ctx) {
 
 static int update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev);  // below
 static int apply_time_tables(tdgl_ctx *ctx);                                 // below
+static double table_value(const std::vector<double> &t, const double *v, double time);  // below
+static int check_link_table(tdgl_ctx *ctx, const char *who, int32_t n_nodes, const double *times, const double *values);  // below
 static int profile_event(tdgl_ctx *ctx, hipEvent_t *ev);                     // below
 
 static inline int64_t now_ns() {
@@ -698,7 +700,7 @@ static int set_links_impl(tdgl_ctx *ctx, const double *A, bool dynamic, double d
     CTX_GUARD(ctx);
     if (!A) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_exponents: null A");
     TDGL_TRY(upload_edge_vectors(ctx, A, ctx->e_A.p));
-    ctx->loop.ramp_on = false;
+    ctx->loop.links_static();
     TDGL_TRY(finish_links(ctx, dynamic, dt_prev));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
@@ -711,7 +713,7 @@ extern "C" int tdgl_set_link_exponents_base(tdgl_ctx *ctx, const double *A_base,
     if (ctx->e_Abase.n == 0) HIP_TRY(ctx, ctx->e_Abase.alloc(2 * ctx->m_pad));
     TDGL_TRY(upload_edge_vectors(ctx, A_base, ctx->e_Abase.p));
     ctx->have_base = true;
-    ctx->loop.ramp_on = false;
+    ctx->loop.links_static();
     hipLaunchKernelGGL(k_scale_links, dim3(grid_for(2 * ctx->m_pad)), dim3(BLOCK), 0, ctx->stream, 2 * ctx->m_pad,
                        scale, ctx->e_Abase.p, ctx->e_A.p);
     ctx->loop.link_scale = ctx->loop.link_scale_prev = scale;
@@ -745,6 +747,23 @@ extern "C" int tdgl_set_link_ramp(tdgl_ctx *ctx, int32_t on, double tmin, double
     if (on && !ctx->have_base) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_exponents_base first");
     if (on && !(tmax > tmin)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_ramp: tmax must be > tmin");
     ctx->loop.set_ramp(on != 0, tmin, tmax, initial, final_);
+    return TDGL_OK;
+}
+
+// A(t) = table(t) A_base: the factor as a piecewise-linear table (constant outside its nodes) that tdgl_run evaluates itself,
+// in the place of the ramp -- a table and a ramp exclude each other, the later call wins
+extern "C" int tdgl_set_link_table(tdgl_ctx *ctx, int32_t n_nodes, const double *times, const double *values) {
+    CTX_GUARD(ctx);
+    if (n_nodes == 0) {  // off (a ramp stays)
+        if (ctx->loop.tabulated()) ctx->loop.links_static();
+        return TDGL_OK;
+    }
+    if (!ctx->have_base) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_exponents_base first");
+    TDGL_TRY(check_link_table(ctx, "tdgl_set_link_table", n_nodes, times, values));
+    std::vector<double> both(times, times + n_nodes);
+    both.insert(both.end(), values, values + n_nodes);
+    HIP_TRY(ctx, ctx->d_tab_link.upload(both));
+    ctx->loop.set_table(times, values, n_nodes);
     return TDGL_OK;
 }
 
@@ -803,6 +822,15 @@ static bool table_times_ok(const double *times, int32_t n) {
     for (int32_t k = 0; k < n; ++k)
         if (!std::isfinite(times[k]) || (k > 0 && !(times[k] > times[k - 1]))) return false;
     return true;
+}
+
+// what tdgl_set_link_table and tdgl_ensemble_set_link_table refuse
+static int check_link_table(tdgl_ctx *ctx, const char *who, int32_t n_nodes, const double *times, const double *values) {
+    if (n_nodes < 1 || !times || !values || !table_times_ok(times, n_nodes))
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: bad table (times must increase strictly)", who);
+    for (int32_t k = 0; k < n_nodes; ++k)
+        if (!std::isfinite(values[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: non-finite factor", who);
+    return TDGL_OK;
 }
 
 // what tdgl_set_mu_boundary_table and tdgl_ensemble_set_mu_boundary_table refuse (who: the entry point, for the message)

@@ -250,6 +250,9 @@ struct LoopState {
     bool ramp_on = false, has_dadt = false;
     double ramp_tmin = 0.0, ramp_tmax = 1.0, ramp_initial = 0.0, ramp_final = 1.0;
     double link_scale = 1.0, link_scale_prev = 1.0;  // scale of the current / previous A
+    // ... or the factor as a piecewise-linear table A(t) = table(t) A_base (tdgl_set_link_table; non-empty: the table is the
+    // source of the factor and ramp_tmin .. ramp_final are unused).  The host's copy of the nodes; the device's is its owner's
+    std::vector<double> tab_t, tab_v;
     // what absorb tells its caller about a batch.  corrupt: 1 impossible counts, 2 the records disagree with the controller
     // (the state is void); last_accepted: index of the last accepted record
     struct Batch {
@@ -266,7 +269,13 @@ struct LoopState {
     void new_state(int buffer) { cur = buffer, retries = 0; }  // a new psi in psi[buffer] (tdgl_set_state): no step is in progress
     void set_ramp(bool on, double tmin, double tmax, double initial, double final_) {
         ramp_on = on, ramp_tmin = tmin, ramp_tmax = tmax, ramp_initial = initial, ramp_final = final_;
+        tab_t.clear(), tab_v.clear();
     }
+    void set_table(const double *times, const double *values, int64_t n) {  // n = 0: off
+        ramp_on = n > 0, tab_t.assign(times, times + n), tab_v.assign(values, values + n);
+    }
+    void links_static() { ramp_on = false, tab_t.clear(), tab_v.clear(); }  // (a setter of static links: neither ramp nor table)
+    bool tabulated() const { return ramp_on && !tab_t.empty(); }
     std::string budget_message(int replica, double dt) const;
     void report(int64_t *step, double *time_, double *runner_dt_, double *tentative) const;
     // the classic loop's step: its first attempt takes tentative_dt (solver.py:666-668); a step begun by the run-ahead loop and
@@ -278,8 +287,12 @@ struct LoopState {
     bool advance(double dt, double end_time);
     // A LinearRamp (tdgl/sources/scaling.py:4-14) is constant from t_max on.  Once the loop has evaluated it twice at its final
     // value -- the first evaluation still sees dA/dt != 0, the second writes dA/dt = 0 (solver.py:626-642) -- the vector
-    // potential is static for the rest of the stage: no dA/dt term, no per-step update, and the run-ahead loop can take over
-    bool ramp_settled() const { return ramp_on && time >= ramp_tmax && link_scale == ramp_final && link_scale_prev == ramp_final; }
+    // potential is static for the rest of the stage: no dA/dt term, no per-step update, and the run-ahead loop can take over.
+    // A table is constant from its last node on, at that node's value: the same rule.
+    bool ramp_settled() const {
+        const double t_end = tabulated() ? tab_t.back() : ramp_tmax, f_end = tabulated() ? tab_v.back() : ramp_final;
+        return ramp_on && time >= t_end && link_scale == f_end && link_scale_prev == f_end;
+    }
     bool ramping() const { return ramp_on && !ramp_settled(); }
     void fill(tdgl::StepCtl &h, double end_time, bool live) const;
     Batch absorb(const tdgl::StepCtl &h, const tdgl::StepRec *rec, int batch, int limit, bool ramped, double *out_dt);
@@ -510,6 +523,7 @@ struct tdgl_ctx {
     tdgl::DevBuf<int32_t> d_b_sites;                 // the sites that boundary edges touch, each once
     int32_t n_b_sites = 0;
     bool tab_mu_on_device = false;
+    tdgl::DevBuf<double> d_tab_link;                 // the field factor's table on the device: n times, then n values (k_ra_table_begin; host copy: loop.tab_t / tab_v)
     tdgl::DevBuf<double> d_tab_eps_t, d_tab_eps_f;   // the epsilon factor's table on the device (k_ra_eps_table)
     bool tab_eps_on_device = false;
     std::vector<double> tab_eps_t, tab_eps_f;

@@ -6,8 +6,9 @@ thermalisation, adaptive dt, retries and errors.  The replicas share the device,
 the mu solve is the dense pseudo-inverse of the Poisson matrix up to ``ENSEMBLE_DENSE_MAX_SITES`` sites and the
 substructured direct solve of one or two levels above (`ensemble_mu_path`), applied to all replicas' right-hand
 sides in one pass over the factors per group of replicas.  A replica may be time dependent in the three forms the device evaluates itself, each with its own
-parameters: a field ramp ``LinearRamp * (static field)``, ``TabulatedCurrents`` and a ``SeparableEpsilon``.  Not
-supported: other time-dependent inputs, a ramp combined with a table in one replica, screening, ``output_file``, more
+parameters: a field ramp ``LinearRamp * (static field)`` or field table ``TabulatedRamp * (static field)``,
+``TabulatedCurrents`` and a ``SeparableEpsilon``.  Not supported: other time-dependent inputs, a field ramp or field
+table combined with one of the other tables in one replica, screening, ``output_file``, more
 than ``ENSEMBLE_MAX_SITES`` sites.
 
 The per-replica set-up (vector potential, epsilon, terminal currents -> mu boundary values) is ``TDGLSolver``'s
@@ -24,7 +25,8 @@ import numpy as np
 from . import _lib
 from ._lib import c128, f64, p_f64, p_i32
 from .device import Device
-from .hipcore import TDGLContext, controller_struct, epsilon_table_args, mu_boundary_table_args, probe_args, read_loop_state
+from .hipcore import (TDGLContext, controller_struct, epsilon_table_args, link_table_args, mu_boundary_table_args, probe_args,
+                      read_loop_state)
 from .options import SolverOptions
 from .runloop import RunRecord, check_epsilon_table, check_seed
 from .solution import Solution
@@ -89,12 +91,13 @@ def _refuse_options(options: SolverOptions, n_sites: int) -> None:
 
 
 def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
-    """Time dependence the ensemble evaluates on the device passes: a separable A whose factor is a LinearRamp,
-    TabulatedCurrents, a SeparableEpsilon.  Anything else raises."""
-    if rep.dynamic_vector_potential and rep._A_ramp is None:
+    """Time dependence the ensemble evaluates on the device passes: a separable A whose factor is a LinearRamp or a
+    TabulatedRamp, TabulatedCurrents, a SeparableEpsilon.  Anything else raises."""
+    if rep.dynamic_vector_potential and not rep.device_evaluates_field():
         if rep._A_base is not None:
             raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
-                             "LinearRamp(...) * (static field); this one's time factor is not a LinearRamp.")
+                             "LinearRamp(...) * (static field) or TabulatedRamp(...) * (static field); this one's time "
+                             "factor is not a LinearRamp or a TabulatedRamp.")
         raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is not supported.")
     if rep.dynamic_currents and rep._current_table is None:
         raise ValueError(f"solve_ensemble: replica {r}: time-dependent terminal_currents are not supported "
@@ -102,8 +105,9 @@ def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
     if rep.dynamic_epsilon and rep._eps_table is None:
         raise ValueError(f"solve_ensemble: replica {r}: a time-dependent disorder_epsilon is not supported "
                          "(SeparableEpsilon is).")
-    if rep._A_ramp is not None and (rep._current_table is not None or rep._eps_table is not None):
-        raise ValueError(f"solve_ensemble: replica {r}: a field ramp combined with TabulatedCurrents or a SeparableEpsilon "
+    if rep.device_evaluates_field() and (rep._current_table is not None or rep._eps_table is not None):
+        what = "a field ramp" if rep._A_ramp is not None else "a field table"
+        raise ValueError(f"solve_ensemble: replica {r}: {what} combined with TabulatedCurrents or a SeparableEpsilon "
                          "in one replica is not supported.")
 
 
@@ -124,7 +128,8 @@ def solve_ensemble(
     """Solve R replicas of one device together; returns the R ``Solution`` objects ``tdgl.solve`` returns for each
     of them alone.  Every per-replica argument is a list of length R or one value for all replicas.
 
-    Time-dependent replicas: ``applied_vector_potential`` may be ``LinearRamp(...) * <static field>``,
+    Time-dependent replicas: ``applied_vector_potential`` may be ``LinearRamp(...) * <static field>`` or
+    ``TabulatedRamp(...) * <static field>`` (tables of any length, each replica its own),
     ``terminal_currents`` a ``TabulatedCurrents``, ``disorder_epsilon`` a ``SeparableEpsilon`` (one kind of table or
     ramp per replica, except that tabulated currents and a separable epsilon may go together).  Static, ramped and
     tabulated replicas may share one ensemble.
@@ -151,16 +156,19 @@ def solve_ensemble(
 
 def solve_ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
                                  gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
-                                 seed_states=None, vector_potential_ramp=None, epsilon_table=None) -> List[Solution]:
+                                 seed_states=None, vector_potential_ramp=None, epsilon_table=None,
+                                 vector_potential_table=None) -> List[Solution]:
     """``solve_ensemble`` from dimensionless inputs (``TDGLSolver.from_dimensionless``): ``link_exponents`` A[m, 2]
     (an array, or a list of them), ``epsilon`` (a scalar or an [n] array, or a list), ``currents``
     ({terminal: dimensionless current} or a ``TabulatedCurrents``, or a list), ``seed_states`` (None or a list of
     (psi, mu) / None).  Time dependence, one value or a list with None for the replicas without:
     ``vector_potential_ramp`` ``(A_base[m, 2], dict(tmin, tmax, initial, final))`` as in
     ``TDGLSolver.from_dimensionless`` (the replica's ``link_exponents`` may then be None: the ramp's value at t = 0),
-    ``epsilon_table`` ``(epsilon0[n], times, factor)``: epsilon(t) = PiecewiseLinear(times, factor)(t) * epsilon0."""
+    ``epsilon_table`` ``(epsilon0[n], times, factor)``: epsilon(t) = PiecewiseLinear(times, factor)(t) * epsilon0,
+    ``vector_potential_table`` ``(A_base[m, 2], times, values)``: A(t) = TabulatedRamp(times, values)(t) * A_base (in a
+    replica without a ramp; ``link_exponents`` may be None as for a ramp)."""
     return ensemble_dimensionless(mesh, options, link_exponents, epsilon, u, gamma, terminal_info, currents, probe_points,
-                                  seed_states, vector_potential_ramp, epsilon_table).solve()
+                                  seed_states, vector_potential_ramp, epsilon_table, vector_potential_table).solve()
 
 
 def _one_or_list(value, is_one):
@@ -196,7 +204,8 @@ def _with_epsilon_table(rep: TDGLSolver, table, n: int) -> None:
 
 def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
                            gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
-                           seed_states=None, vector_potential_ramp=None, epsilon_table=None) -> "EnsembleSolver":
+                           seed_states=None, vector_potential_ramp=None, epsilon_table=None,
+                           vector_potential_table=None) -> "EnsembleSolver":
     """The `EnsembleSolver` behind `solve_ensemble_dimensionless` (its ``solve()`` returns the solutions)."""
     _refuse_options(options, len(mesh.sites))
     per = dict(link_exponents=link_exponents, currents=currents, seed_states=seed_states)
@@ -204,23 +213,32 @@ def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon
         per["epsilon"] = epsilon
     ramps = _one_or_list(vector_potential_ramp, lambda v: isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], dict))
     tables = _one_or_list(epsilon_table, lambda v: isinstance(v, tuple) and len(v) == 3)
-    for name, v in (("vector_potential_ramp", ramps), ("epsilon_table", tables)):
+    fields = _one_or_list(vector_potential_table, lambda v: isinstance(v, tuple) and len(v) == 3)
+    for name, v in (("vector_potential_ramp", ramps), ("epsilon_table", tables), ("vector_potential_table", fields)):
         if not isinstance(v, _Same):
             per[name] = v
     R, args = broadcast_replicas(**per)
     eps = args.get("epsilon", [epsilon] * R)
     ramps = args.get("vector_potential_ramp", [getattr(ramps, "value", None)] * R)
     tables = args.get("epsilon_table", [getattr(tables, "value", None)] * R)
+    fields = args.get("vector_potential_table", [getattr(fields, "value", None)] * R)
     reps = []
     for r in range(R):
         A = args["link_exponents"][r]
+        if ramps[r] is not None and fields[r] is not None:
+            raise ValueError(f"solve_ensemble: replica {r}: vector_potential_ramp and vector_potential_table exclude each other.")
         if A is None and ramps[r] is not None:
             from .parameter import LinearRamp
 
             A = LinearRamp(**ramps[r][1]).scalar(0.0) * np.asarray(ramps[r][0], dtype=float)
+        if A is None and fields[r] is not None:
+            from .parameter import PiecewiseLinear
+
+            A = PiecewiseLinear(*fields[r][1:])(0.0) * np.asarray(fields[r][0], dtype=float)
         rep = _ReplicaInputs.from_dimensionless(mesh, options, A, eps[r], u, gamma,
                                                 terminal_info=terminal_info, current_func=args["currents"][r],
-                                                probe_points=probe_points, vector_potential_ramp=ramps[r])
+                                                probe_points=probe_points, vector_potential_ramp=ramps[r],
+                                                vector_potential_table=fields[r])
         if tables[r] is not None:
             _with_epsilon_table(rep, tables[r], len(mesh.sites))
         _refuse_dynamic(r, rep)
@@ -276,6 +294,12 @@ class EnsembleContext:
         assert A_base.shape == (self.ctx.m, 2)
         self._chk(self._lib.tdgl_ensemble_set_link_ramp(self._ens, r, p_f64(A_base), float(tmin), float(tmax), float(initial),
                                                         float(final)))
+
+    def set_link_table(self, r, A_base, times, values):
+        """A(t) = PiecewiseLinear(times, values)(t) * A_base, evaluated inside ``run``."""
+        A_base = f64(A_base)
+        assert A_base.shape == (self.ctx.m, 2)
+        self._chk(self._lib.tdgl_ensemble_set_link_table(self._ens, r, p_f64(A_base), *link_table_args(times, values)))
 
     def link_scale(self, r) -> float:
         v = C.c_double(0)
@@ -427,6 +451,8 @@ class EnsembleSolver:
         for r, rep in enumerate(reps):
             if rep._A_ramp is not None:  # (TDGLSolver._setup: the links start at the ramp's value at t = 0)
                 ens.set_link_ramp(r, rep._A_base, **rep._A_ramp)
+            elif rep._A_table is not None:
+                ens.set_link_table(r, rep._A_base, *rep._A_table)
             else:
                 ens.set_link_exponents(r, rep.current_A_applied)
             ens.set_mu_boundary(r, rep.mu_boundary)

@@ -66,6 +66,16 @@ def epsilon_table_args(n: int, epsilon0, times, factors) -> tuple:
     return p_f64(e0), len(t), p_f64(t), p_f64(fac)
 
 
+def link_table_args(times, values) -> tuple:
+    """``(n_nodes, times, values)`` of tdgl_set_link_table; ``times=None``: off."""
+    if times is None:
+        return 0, None, None
+    t, v = f64(times), f64(values)
+    if t.ndim != 1 or t.shape != v.shape:
+        raise ValueError("times and values must be one-dimensional and of equal length")
+    return len(t), p_f64(t), p_f64(v)
+
+
 def controller_struct(dt_init, dt_max, adaptive, adaptive_window, max_solve_retries,
                       adaptive_time_step_multiplier) -> "_lib.Controller":
     return _lib.Controller(float(dt_init), float(dt_max), int(bool(adaptive)), int(adaptive_window),
@@ -1156,6 +1166,11 @@ class TDGLContext:
         """Let ``run`` evaluate A(t) = LinearRamp(t) * A_base itself before every step."""
         self._chk(self._lib.tdgl_set_link_ramp(self._ctx, int(bool(on)), float(tmin), float(tmax),
                                                float(initial), float(final)))
+
+    def set_link_table(self, times, values):
+        """Let ``run`` evaluate A(t) = PiecewiseLinear(times, values)(t) * A_base itself before every step (in the
+        ramp's place); ``times=None``: off."""
+        self._chk(self._lib.tdgl_set_link_table(self._ctx, *link_table_args(times, values)))
 
     def link_scale(self):
         v = C.c_double(0)

@@ -100,6 +100,7 @@ class Parameter:
         # recognise A(t) = f(t) * A_static and keep A_static on the device
         self.uniform_in_space = False
         self.ramp = None  # LinearRamp: dict(tmin, tmax, initial, final)
+        self.table = None  # TabulatedRamp: its PiecewiseLinear
 
     def separable_product(self):
         """``(f, static)`` if this parameter is ``f(t) * static(x, y, z)`` with ``f`` uniform in
@@ -230,7 +231,7 @@ class CompositeParameter(Parameter):
         self.kwargs = {}
         self.time_dependent = any(isinstance(v, Parameter) and v.time_dependent for v in (left, right))
         self.uniform_in_space = all((not isinstance(v, Parameter)) or v.uniform_in_space for v in (left, right))
-        self.ramp = None
+        self.ramp = self.table = None
 
     def separable_product(self):
         if self.operator is not operator.mul:
@@ -348,6 +349,29 @@ class PiecewiseLinear:
 
     def __call__(self, t) -> float:
         return float(np.interp(t, self.times, self.values))
+
+    def __eq__(self, other) -> bool:
+        return (isinstance(other, PiecewiseLinear) and np.array_equal(self.times, other.times)
+                and np.array_equal(self.values, other.values))
+
+    __hash__ = None
+
+
+def tabulated_ramp(x, y, z, *, t, table):
+    """The value of ``table`` at ``t`` -- one number for all positions."""
+    return table(t)
+
+
+def TabulatedRamp(times, values) -> Parameter:
+    """A factor given as a table: linear between the nodes ``(times[k], values[k])``, constant before the first node
+    and after the last (a `PiecewiseLinear`, kept as ``.table``).  ``TabulatedRamp(...) * <static field>`` is used
+    exactly as ``LinearRamp(...) * <static field>`` is -- an up-and-down sweep, ramp-hold-ramp, a pulse, a sampled AC
+    field -- and like it the time loop evaluates it on the device (`tdgl_set_link_table`): no Python call, no upload
+    per step."""
+    p = Parameter(tabulated_ramp, table=PiecewiseLinear(times, values), time_dependent=True)
+    p.uniform_in_space = True
+    p.table = p.kwargs["table"]
+    return p
 
 
 class TabulatedCurrents:

@@ -116,16 +116,19 @@ class TDGLSolver:
         self.A_scale = device.field_scale(options.field_units)
         ex, ey = self.edge_centers[:, 0], self.edge_centers[:, 1]
         self.vector_potential_func = None
-        self._A_base = self._A_factor = self._A_ramp = None
+        self._A_base = self._A_factor = self._A_ramp = self._A_table = None
         sep = applied_vector_potential.separable_product() if (
             self.dynamic_vector_potential and hasattr(applied_vector_potential, "separable_product")) else None
         if sep is not None:
             # A(t) = f(t) * A_static (the reference's field-ramp example): A_static stays on the
-            # device, the factor is evaluated per step -- by tdgl_run itself for a LinearRamp
+            # device, the factor is evaluated per step -- by tdgl_run itself for a LinearRamp or a TabulatedRamp
             factor, static = sep
             self._A_base = self.A_scale * np.asarray(static(ex, ey, self.z0))[:, :2]
             self._A_factor = factor.scalar
             self._A_ramp = factor.ramp
+            table = getattr(factor, "table", None)
+            if table is not None:
+                self._A_table = (table.times, table.values)
             self.vector_potential_func = lambda t: factor.scalar(t) * self._A_base
             A = self.vector_potential_func(0)
         elif self.dynamic_vector_potential:
@@ -219,7 +222,7 @@ class TDGLSolver:
                            u: float = 5.79, gamma: float = 10.0, terminal_info=(),
                            current_func=None, probe_points=None, device=None,
                            vector_potential_func=None, epsilon_func=None,
-                           screening=None, vector_potential_ramp=None) -> "TDGLSolver":
+                           screening=None, vector_potential_ramp=None, vector_potential_table=None) -> "TDGLSolver":
         """Build a solver directly from dimensionless inputs -- the arrays the reference's
         ``__init__`` ends up with (solver.py:185, 214, 225, 254-256): ``A[m, 2]``,
         ``epsilon[n]``, ``TerminalInfo`` records and ``t -> {name: dimensionless current}``.
@@ -228,7 +231,9 @@ class TDGLSolver:
         (areas already multiplied by the kernel prefactor, solver.py:307-309); requires
         ``options.include_screening``.  ``vector_potential_ramp``: ``(A_base[m, 2], dict(tmin, tmax,
         initial, final))`` for ``A(t) = LinearRamp(t) * A_base`` evaluated by the library itself
-        (then ``link_exponents`` must be its value at t = 0)."""
+        (then ``link_exponents`` must be its value at t = 0).  ``vector_potential_table``: ``(A_base[m, 2], times,
+        values)`` for ``A(t) = TabulatedRamp(times, values)(t) * A_base``, evaluated by the library in the same way; a
+        ramp and a table exclude each other."""
         self = object.__new__(cls)
         options.validate()
         self.device = device
@@ -243,12 +248,19 @@ class TDGLSolver:
         self.disorder_epsilon = epsilon
         # optional time dependence: t -> A[m, 2] / t -> epsilon[n], already dimensionless
         self.vector_potential_func = vector_potential_func
-        self._A_base = self._A_factor = self._A_ramp = None
-        if vector_potential_ramp is not None:
-            from .parameter import LinearRamp
+        self._A_base = self._A_factor = self._A_ramp = self._A_table = None
+        if vector_potential_ramp is not None and vector_potential_table is not None:
+            raise ValueError("vector_potential_ramp and vector_potential_table exclude each other.")
+        if vector_potential_ramp is not None or vector_potential_table is not None:
+            from .parameter import LinearRamp, TabulatedRamp
 
-            base, ramp = vector_potential_ramp
-            factor = LinearRamp(**ramp)
+            if vector_potential_ramp is not None:
+                base, ramp = vector_potential_ramp
+                factor = LinearRamp(**ramp)
+            else:
+                base, times, values = vector_potential_table
+                factor = TabulatedRamp(times, values)
+                self._A_table = (factor.table.times, factor.table.values)
             self._A_base = np.asarray(base, dtype=float)
             self._A_factor, self._A_ramp = factor.scalar, factor.ramp
             self.vector_potential_func = vector_potential_func = lambda t: factor.scalar(t) * self._A_base
@@ -323,6 +335,8 @@ class TDGLSolver:
             self.ctx.set_link_exponents_base(self._A_base, self._A_factor(0))
             if self._A_ramp is not None:
                 self.ctx.set_link_ramp(**self._A_ramp)
+            elif self._A_table is not None:
+                self.ctx.set_link_table(*self._A_table)
         else:
             self.operators.set_link_exponents(self.current_A_applied)
 
@@ -390,6 +404,10 @@ class TDGLSolver:
                 changed = True
         return changed
 
+    def device_evaluates_field(self) -> bool:
+        """A(t) = f(t) * A_base with f a LinearRamp or a TabulatedRamp: the time loop evaluates f itself."""
+        return self._A_ramp is not None or self._A_table is not None
+
     def device_evaluates_epsilon(self) -> bool:
         """epsilon(t) is a table the time loop evaluates itself (tdgl_set_epsilon_table); the host keeps a copy."""
         return self.dynamic_epsilon and self._epsilon_on_device
@@ -397,8 +415,8 @@ class TDGLSolver:
     def update_dynamic_inputs(self, time: float, dt_prev: float) -> None:
         """solver.py:626-648: re-evaluate A(t) (-> link variables and dA/dt with the previous
         step's dt) and epsilon(t) before a step."""
-        if self._A_ramp is not None:
-            pass  # tdgl_run evaluates the ramp itself (tdgl_set_link_ramp)
+        if self.device_evaluates_field():
+            pass  # tdgl_run evaluates the ramp or the table itself (tdgl_set_link_ramp, tdgl_set_link_table)
         elif self._A_base is not None:
             self.ctx.update_link_scale(self._A_factor(time), dt_prev)
         elif self.dynamic_vector_potential:
@@ -499,7 +517,7 @@ class TDGLSolver:
             # inputs that live in Python are re-evaluated before every step
             per_step = ((self.dynamic_currents and not self._currents_on_device)
                         or (self.dynamic_epsilon and not self._epsilon_on_device)
-                        or (self.dynamic_vector_potential and self._A_ramp is None))
+                        or (self.dynamic_vector_potential and not self.device_evaluates_field()))
             rec = RunRecord(ctx, self, opts, per_step=per_step, handler=handler)
             while not rec.done:
                 chunk, end_time = rec.request()
