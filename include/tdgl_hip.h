@@ -626,6 +626,38 @@ typedef struct {
 int tdgl_host_loop_replay(const tdgl_controller *c, double end_time, int64_t n_attempts, const double *dmax,
                           const int32_t *fail, int32_t batch, int32_t mode, const tdgl_controller *c_next, int64_t next_at,
                           double *out_dt, double *out_attempt_dt, tdgl_loop_replay *res);
+/* Host-only: where the edge currents J_s, J_n of the accepted steps are formed.  The same script of attempts as above, the
+ * plan of every step given (`plan`) or chosen from `facts` (non-NULL) by the function the step driver asks, and the caller's
+ * actions: action k comes in front of attempt action_at[k] (ascending; mode 1: a batch ends there) and is
+ * action_kind[k] = 0: tdgl_run returns and is called again, 1: ... and the currents are read in between, 2: ... and a state is
+ * set.  The script ends with a return.  Events are numbered 4 i + p: p = 0 an action in front of attempt i, 1 the psi
+ * update of attempt i, 2 behind the first look of its mu solve (mu not written yet), 3 its mu solve and what follows it.
+ * formed_at [n_attempts]: per accepted step the event that formed its currents first, -1: never.  res->n_formations counts
+ * the formations of an accepted step's currents (a speculative one whose step failed is none; a live run-ahead attempt that
+ * forms those of a step again is not counted, like tdgl_get_edge_current_launches).  A plan the run-ahead loop does not
+ * take (tdgl_run: no direct solve, or currents on request) plays mode 1 like mode 0.  No device work. */
+typedef enum {
+    TDGL_CURRENTS_NOW = 0,              /* a launch of their own right after the step's mu solve */
+    TDGL_CURRENTS_SPECULATIVE = 1,      /* queued behind the direct solve before the host has seen the step's status */
+    TDGL_CURRENTS_WITH_NEXT_PSI = 2,    /* in the next step's psi-update launch, or when tdgl_run returns */
+    TDGL_CURRENTS_BEHIND_NEXT_LOOK = 3, /* behind the first status copy of the next step's solve, or when tdgl_run returns */
+    TDGL_CURRENTS_ON_REQUEST = 4,       /* when somebody reads them */
+} tdgl_currents_plan;
+typedef struct {
+    int32_t dense_on, distributed, hierarchy; /* direct mu solve in use; one process per GPU; an AMG hierarchy is set */
+    int32_t extrapolate, edge_currents_every_step; /* tdgl_poisson_options */
+    int32_t ramp_on, has_dadt;                /* the loop moves the links; a dA/dt term is in force */
+    int32_t sync_shadow_disabled, screening;  /* TDGL_NO_SYNC_SHADOW; tdgl_set_screening */
+} tdgl_currents_facts;
+typedef struct {
+    int64_t n_accepted, n_attempts, n_formations;
+    int32_t plan, state; /* the plan played; the ledger at the end: 0 stale, 1 formed, 2 owed */
+    int32_t reached, error;
+} tdgl_currents_replay;
+int tdgl_host_currents_replay(int32_t plan, const tdgl_currents_facts *facts, const tdgl_controller *c, double end_time,
+                              int64_t n_attempts, const double *dmax, const int32_t *fail, int32_t batch, int32_t mode,
+                              int64_t n_actions, const int64_t *action_at, const int32_t *action_kind, int64_t *formed_at,
+                              tdgl_currents_replay *res);
 /* Host-only: the block low-rank compression of one B x B block A (row major) -- column-pivoted, reorthogonalised
  * Gram-Schmidt until the Frobenius norm of the remainder is <= tol; A ~ Q W^T with Q, W [kmax * B] column by column.
  * Returns the rank, or -1 when kmax columns do not reach tol (-2: bad arguments).  No device work. */

@@ -796,8 +796,7 @@ extern "C" int tdgl_ensemble_get_state(tdgl_ensemble *e, int32_t r, double *psi,
     if (dadt) TDGL_TRY(ens_copy(ctx, ctx->e_dAdt.p, e->dadt.p + r * e->m_pad, e->m_pad));
     ctx->have_state = true;
     ctx->lap_valid = false;  // (the context's Laplacian values belong to whatever links it was last given)
-    ctx->currents_valid = false;
-    ctx->currents_deferred = false;
+    ctx->currents.new_state();
     ctx->loop.has_dadt = dadt;
     const int status = tdgl_get_state(ctx, psi, mu, supercurrent, normal_current);
     ctx->loop.has_dadt = false;  // (the context's own links are static)

@@ -410,7 +410,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_currents(
 // ONE launch.  Both read psi^{n+1}... of the accepted step (`psi`) and mu only, the currents feed nothing
 // back into the time loop, and a step of the direct solve is five launches, so one launch less is ~8 %.
 // Workgroups [0, nblk_psi) update psi, the others take 256 edges each.  Used only while the link
-// variables are static (run.inc: defer_currents).
+// variables are static (loop.inc: currents_plan, TDGL_CURRENTS_WITH_NEXT_PSI).
 __global__ __launch_bounds__(BLOCK) void k_psi_update_with_currents(
     int nblk_psi, int64_t n, const double2 *__restrict__ psi, const double *__restrict__ mu,
     const double *__restrict__ eps, const double2 *__restrict__ lap, double dt, double u, double gamma,

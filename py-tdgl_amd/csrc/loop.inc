@@ -179,6 +179,78 @@ LoopState::Batch LoopState::absorb(const StepCtl &h, const StepRec *rec, int bat
     return b;
 }
 
+// Where the currents of the step about to be taken are formed -- the one place that decides it.
+tdgl_currents_plan currents_plan(const tdgl_currents_facts &f) {
+    if (f.screening) return TDGL_CURRENTS_NOW;  // (step_screening forms them in every iteration of its own loop)
+    if (!f.edge_currents_every_step) return TDGL_CURRENTS_ON_REQUEST;
+    const bool links_move = f.ramp_on || f.has_dadt;  // (field ramps and dA/dt: the links change at step begin)
+    // Direct solve (launch-bound sizes) with static link variables: the edge currents of an accepted step
+    // are not launched on their own but ride in the NEXT step's psi-update launch (same inputs: the
+    // accepted psi and mu), or are formed when tdgl_run returns -- one launch less per step.  With moving links they
+    // are queued right behind the solve, before the step's synchronisation; after a failed psi update they hold
+    // scratch values until the repeated step rewrites them.
+    if (f.dense_on) return links_move ? TDGL_CURRENTS_SPECULATIVE : TDGL_CURRENTS_WITH_NEXT_PSI;
+    // Iterative solve on one GPU: the edge currents of an accepted step are not launched in front of the next step's
+    // psi update but behind the first status copy of its solve (pcg_solve), where the GPU would otherwise wait for the
+    // host, or when tdgl_run returns -- every reader of J outside tdgl_run therefore finds them formed.  The old order
+    // stays with: an extrapolated guess (k_extrapolate writes mu before that look), moving links, screening, one
+    // process per GPU, the dense and run-ahead paths (they have no such look), currents not formed every step, and
+    // TDGL_NO_SYNC_SHADOW.
+    if (!f.sync_shadow_disabled && !f.distributed && f.hierarchy && f.extrapolate >= 3 && !links_move)
+        return TDGL_CURRENTS_BEHIND_NEXT_LOOK;
+    return TDGL_CURRENTS_NOW;
+}
+
+// new link variables (finish_links): what was formed is void; what is owed stays owed
+void EdgeCurrents::new_links() {
+    if (state == FORMED) state = STALE;
+}
+
+// the psi update of an attempt: true -- it carries the owed currents (every plan but the one that has a better place)
+bool EdgeCurrents::take_with_psi(tdgl_currents_plan plan) {
+    if (state != OWED || plan == TDGL_CURRENTS_BEHIND_NEXT_LOOK) return false;
+    state = FORMED;
+    return true;
+}
+
+// the first status copy of an attempt's iterative solve: true -- the owed currents follow it.  (A psi retry comes back
+// for the same step with nothing owed any more.)
+bool EdgeCurrents::take_behind_look(tdgl_currents_plan plan) {
+    if (state != OWED || plan != TDGL_CURRENTS_BEHIND_NEXT_LOOK) return false;
+    state = FORMED;
+    return true;
+}
+
+// the solve queued the currents behind itself and the step failed or the solve returned an error: js / jn hold scratch
+void EdgeCurrents::speculation_failed() {
+    if (state == FORMED) state = STALE;
+}
+
+// a step is accepted; queued: its solve has queued them already.  true -- the caller launches them now
+bool EdgeCurrents::accept(tdgl_currents_plan plan, bool queued) {
+    const bool later = plan == TDGL_CURRENTS_WITH_NEXT_PSI || plan == TDGL_CURRENTS_BEHIND_NEXT_LOOK;
+    const bool now = !queued && !later && plan != TDGL_CURRENTS_ON_REQUEST;
+    state = queued || now ? FORMED : later ? OWED : STALE;
+    return now;
+}
+
+// somebody reads them: true -- the caller launches them first
+bool EdgeCurrents::request() {
+    if (state == FORMED) return false;
+    state = FORMED;
+    return true;
+}
+
+// A run-ahead batch of which `done` attempts ran and `accepted` were accepted, the last of them as attempt `last_accepted`:
+// every live attempt behind the first (the first too, if they were owed on entry: batch_attempt_takes) forms the currents
+// of psi^n as it stood when the attempt began.
+void EdgeCurrents::absorb_batch(int done, int last_accepted, int accepted, bool owed_on_entry) {
+    if (accepted > 0)
+        state = done > last_accepted + 1 ? FORMED : OWED;  // (FORMED: a later live attempt, a failed one, saw the last accepted state)
+    else if (done > 0 && batch_attempt_takes(done - 1, owed_on_entry))
+        state = FORMED;
+}
+
 }  // namespace tdgl
 
 // Host-only: a scripted sequence of attempts through the loop's rules, see include/tdgl_hip.h
@@ -245,5 +317,97 @@ extern "C" int tdgl_host_loop_replay(const tdgl_controller *c, double end_time, 
     res->runner_dt = L.runner_dt;
     res->attempt_dt = L.attempt_dt;
     res->retries = L.retries;
+    return TDGL_OK;
+}
+
+// Host-only: ... and through the currents' plan and ledger, see include/tdgl_hip.h.  The order of an attempt's launches
+// is step_once's and run_ahead's; every decision is the ledger's.
+extern "C" int tdgl_host_currents_replay(int32_t plan_in, const tdgl_currents_facts *facts, const tdgl_controller *c,
+                                         double end_time, int64_t n_attempts, const double *dmax, const int32_t *fail,
+                                         int32_t batch, int32_t mode, int64_t n_actions, const int64_t *action_at,
+                                         const int32_t *action_kind, int64_t *formed_at, tdgl_currents_replay *res) {
+    using namespace tdgl;
+    if (!c || n_attempts < 0 || (n_attempts > 0 && (!dmax || !fail || !formed_at)) || !res || (mode != 0 && mode != 1) ||
+        n_actions < 0 || (n_actions > 0 && (!action_at || !action_kind)))
+        return TDGL_ERR_ARG;
+    if (!facts && (plan_in < TDGL_CURRENTS_NOW || plan_in > TDGL_CURRENTS_ON_REQUEST)) return TDGL_ERR_ARG;
+    if (mode == 1 && (batch < 1 || batch > RA_BATCH_MAX || (c->adaptive && (c->adaptive_window < 1 || c->adaptive_window > RA_HIST_MAX))))
+        return TDGL_ERR_ARG;
+    const tdgl_currents_plan plan = facts ? currents_plan(*facts) : (tdgl_currents_plan)plan_in;
+    const bool ahead = mode == 1 && currents_plan_runs_ahead(plan);  // (run_ahead_ok)
+    LoopState L;
+    L.reset(*c);
+    EdgeCurrents J;
+    *res = tdgl_currents_replay{};
+    for (int64_t k = 0; k < n_attempts; ++k) formed_at[k] = -1;
+    int64_t i = 0, acc = 0, last = -1, a = 0;  // last: the accepted step whose psi and mu are the state (-1: a state that was set)
+    std::vector<double> out_dt((size_t)n_attempts + 1);
+    auto formed = [&](int64_t event) {
+        if (last < 0) return;
+        if (formed_at[last] < 0) formed_at[last] = event;
+        res->n_formations += 1;
+    };
+    auto act = [&](int kind) {  // tdgl_run returns (its flush), then tdgl_get_state's ensure_currents or tdgl_set_state
+        if (J.flush()) formed(4 * i);
+        if (kind == 1 && J.request()) formed(4 * i);
+        if (kind == 2) J.new_state(), L.new_state(L.cur), last = -1;
+    };
+    bool stop = false;
+    while (i < n_attempts && !stop) {
+        for (; a < n_actions && action_at[a] <= i; ++a) act(action_kind[a]);
+        if (!ahead) {  // step_once: one attempt per turn
+            const double dt = L.retries > 0 ? L.attempt_dt : L.begin_step();
+            if (J.take_with_psi(plan)) formed(4 * i + 1);
+            if (J.take_behind_look(plan)) formed(4 * i + 2);
+            MuSolveArgs solve{false, plan};
+            solve.speculate(true);  // (direct_mu_solve inside a step; no other solve looks at that plan)
+            const bool failed = fail[i] != 0;
+            const double d = dmax[i];
+            ++i;
+            if (failed) {
+                if (solve.currents_queued) J.speculation_failed();
+                if (L.retry()) continue;
+                res->error = 1;
+                break;
+            }
+            last = acc++;
+            if (J.accept(plan, solve.currents_queued) || solve.currents_queued) formed(4 * (i - 1) + 3);
+            L.accept(dt, d);
+            if (L.advance(dt, end_time)) {
+                res->reached = 1;
+                break;
+            }
+            continue;
+        }
+        // run_ahead: a batch of attempts, each with the currents of the state it starts from
+        const int64_t room = a < n_actions ? std::min(n_attempts, action_at[a]) - i : n_attempts - i;
+        const int nb = (int)std::min<int64_t>(batch, room);
+        const bool owed_on_entry = J.owed();
+        StepCtl h;
+        StepRec rec[RA_BATCH_MAX];
+        L.fill(h, end_time, true);
+        for (int s = 0; s < nb; ++s) {
+            h.live = h.poisoned ? 0 : 1;
+            const int64_t at = i + h.n_done;
+            if (h.live && EdgeCurrents::batch_attempt_takes(s, owed_on_entry) && last >= 0 && formed_at[last] < 0) formed(4 * at + 1);
+            const int before = h.n_acc;
+            step_controller(&h, rec, dmax[at], fail[at]);
+            if (h.n_acc > before) last = acc + before;
+        }
+        const LoopState::Batch b = L.absorb(h, rec, nb, nb, false, out_dt.data());
+        if (b.corrupt) return TDGL_ERR_HIP;
+        J.absorb_batch(h.n_done, b.last_accepted, b.accepted, owed_on_entry);
+        i += h.n_done;
+        acc += b.accepted;
+        if (b.error) res->error = 1;
+        if (b.reached) res->reached = 1;
+        stop = b.error || b.reached;
+    }
+    for (; a < n_actions && action_at[a] <= i; ++a) act(action_kind[a]);
+    act(0);
+    res->n_accepted = acc;
+    res->n_attempts = i;
+    res->plan = plan;
+    res->state = J.state;
     return TDGL_OK;
 }

@@ -1287,7 +1287,7 @@ static int fetch_scalars(tdgl_ctx *ctx, bool guess_start = false, const double *
 // kernels themselves hold the result back when the psi update of this step failed, the step driver's edge currents
 // follow at once, and the step's only synchronisation comes after them.  after_first_sync / abandoned: see pcg_solve.
 template <class F>
-static int direct_mu_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool in_step) {
+static int direct_mu_solve(tdgl_ctx *ctx, MuSolveArgs &args, F after_first_sync, bool *abandoned, bool in_step) {
     const int64_t no = ctx->n_own;
     double *b = ctx->bvec.p, *x = ctx->mu.p;
     if (!in_step) {  // one-off solve: b orthogonal to the constants, so that the residual below means something
@@ -1295,11 +1295,7 @@ static int direct_mu_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, b
         hipLaunchKernelGGL(k_shift_mean, dim3(vec_grid(no)), dim3(BLOCK), 0, ctx->stream, no, ctx->part_tmp.p, 1.0 / (double)ctx->n_global, b);
     }
     const bool status_done = direct_solve_launch(ctx, b, x, in_step, nullptr, nullptr);
-    ctx->spec_currents_done = false;
-    if (in_step && ctx->spec_currents) {
-        launch_edge_currents(ctx, ctx->psi[1 - ctx->loop.cur].p, x, ctx->js.p, ctx->jn.p);
-        ctx->spec_currents_done = true;
-    }
+    if (args.speculate(in_step)) launch_edge_currents(ctx, ctx->psi[1 - ctx->loop.cur].p, x, ctx->js.p, ctx->jn.p);
     const double *rr_part = nullptr;
     if (!in_step) {  // the true residual, for the caller of tdgl_poisson_solve
         hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, no, b, b, ctx->part_pq.p);
@@ -1630,17 +1626,18 @@ static int pcg_note_solve(tdgl_ctx *ctx, const CgRun &run, int it, double rr, do
     return TDGL_OK;
 }
 
-// Solve A x = b (b = ctx->bvec, x = ctx->mu holds the initial guess).  `after_first_sync` is
+// Solve A x = b (b = ctx->bvec, x = ctx->mu holds the initial guess).  `args`: what the step driver asks for and hears
+// back (a solve outside the time loop passes a default-constructed one).  `after_first_sync` is
 // called after the first host synchronisation with the status block filled; it returns false
 // to abandon the solve (the step driver retries a failed psi update without finishing a solve
 // whose right-hand side is garbage).
 // The host synchronises once before the iterations and then as cg_iterate says.
 template <class F>
-static int pcg_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool allow_projection = false) {
+static int pcg_solve(tdgl_ctx *ctx, MuSolveArgs &args, F after_first_sync, bool *abandoned, bool allow_projection = false) {
     if (ctx->levels.empty()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "no AMG hierarchy: call tdgl_poisson_set_hierarchy");
     TDGL_TRY(comm_ready(ctx));
     if (abandoned) *abandoned = false;
-    if (dense_on(ctx)) return direct_mu_solve(ctx, after_first_sync, abandoned, allow_projection && ctx->psi_status_pending);
+    if (dense_on(ctx)) return direct_mu_solve(ctx, args, after_first_sync, abandoned, allow_projection && ctx->psi_status_pending);
     AmgLevel &L0 = *ctx->levels[0];
     GuessBasis &guess = ctx->guess;
     // all pointwise work is on the owned rows; sums are over ranks (comm_allreduce is a no-op
@@ -1691,14 +1688,12 @@ static int pcg_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool al
         hipLaunchKernelGGL(k_status_unpack, dim3(1), dim3(64), 0, ctx->stream, ctx->d_gstat.p, ctx->status_dev);
         ctx->psi_status_pending = false;  // d_status now holds the all-reduced outcome
     }
-    // The edge currents the previous step owes (run.inc: shadow_currents) fill the wait: they read the accepted psi and
-    // mu^n, which nothing queued so far has written -- the psi update writes the other buffer, mu changes after this
-    // look.  A psi retry comes back here for the same step with nothing owed any more.
-    if (ctx->shadow_currents && ctx->currents_deferred) {
+    // The edge currents the previous step owes (TDGL_CURRENTS_BEHIND_NEXT_LOOK) fill the wait: they read the accepted psi
+    // and mu^n, which nothing queued so far has written -- the psi update writes the other buffer, mu changes after this
+    // look.
+    if (ctx->currents.take_behind_look(args.plan)) {
         TDGL_TRY(fetch_scalars(ctx, proj, nullptr, [&]() {
             launch_edge_currents(ctx, ctx->psi[ctx->loop.cur].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
-            ctx->currents_deferred = false;
-            ctx->currents_valid = true;
             return TDGL_OK;
         }));
     } else {
@@ -1804,7 +1799,7 @@ static int pcg_solve(tdgl_ctx *ctx, F after_first_sync, bool *abandoned, bool al
     } else {
         hipLaunchKernelGGL(k_shift_mean, dim3(gv), dim3(BLOCK), 0, ctx->stream, no, ctx->part_tmp.p, inv_n, x);
     }
-    if (ctx->defer_mu_halo && overlap_on(ctx))
+    if (args.mu_halo_pending && overlap_on(ctx))
         TDGL_TRY(comm_halo_start(ctx, x, 1));  // the step driver overlaps it with the interior edges
     else
         TDGL_TRY(comm_halo(ctx, x, 1));
@@ -1829,7 +1824,8 @@ extern "C" int tdgl_poisson_solve(tdgl_ctx *ctx, const double *rhs, double *mu_i
     TDGL_TRY(upload_sites(ctx, mu_inout, ctx->mu));
     const int saved_iters = ctx->last_pcg_iters;
     ctx->last_pcg_iters = 0;  // no prediction for a one-off solve
-    int st = pcg_solve(ctx, [](const StepStatus *) { return true; }, nullptr);
+    MuSolveArgs one_off;
+    int st = pcg_solve(ctx, one_off, [](const StepStatus *) { return true; }, nullptr);
     if (iters) *iters = ctx->last_pcg_iters;
     if (relres) *relres = ctx->last_relres;
     ctx->last_pcg_iters = saved_iters;

@@ -140,6 +140,22 @@ static int ensure_laplacian_cache(tdgl_ctx *ctx) {
     return TDGL_OK;
 }
 
+// the plan of the step about to be taken (tdgl_internal.h: currents_plan)
+static tdgl_currents_plan step_plan(const tdgl_ctx *ctx) {
+    return currents_plan({dense_on(ctx), distributed(ctx), !ctx->levels.empty(), ctx->popt.extrapolate, ctx->popt.edge_currents_every_step,
+                          ctx->loop.ramp_on, ctx->loop.has_dadt, ctx->sync_shadow_disabled, ctx->scr_enabled});
+}
+
+// what the step drivers read from the first status block of a solve: did the psi update fail, max d|psi|^2.  Returns
+// pcg_solve's "go on" (false: abandon the solve, the update is repeated)
+static bool psi_outcome(const StepStatus *st, bool *failed, double *dmax) {
+    *failed = st->fail_flag != 0;
+    unsigned long long bits = 0;
+    for (int k = 0; k < 8; ++k) bits = std::max(bits, st->dmax_bits[k]);
+    *dmax = __builtin_bit_cast(double, bits);
+    return !*failed;
+}
+
 static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out);
 static int step_finish(tdgl_ctx *ctx, double dt, double dmax, double *dt_used, double *probe_mu,
                        double *probe_theta, int32_t *pcg_iters);
@@ -180,24 +196,11 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
     // pcg_solve after the psi update is known to have succeeded -- mu^n stays in place until then)
     const bool extrapolate = ctx->popt.extrapolate && ctx->popt.extrapolate < 3 && !ctx->levels.empty();
     const double *mu_n = ctx->mu.p;  // mu^n as read by the psi update
-    // Direct solve (launch-bound sizes) with static link variables: the edge currents of an accepted step
-    // are not launched on their own but ride in the NEXT step's psi-update launch (same inputs: the
-    // accepted psi and mu), or are formed when tdgl_run returns -- one launch less per step.
-    const bool defer_currents = dense_on(ctx) && ctx->popt.edge_currents_every_step != 0 && !ctx->loop.ramp_on && !ctx->loop.has_dadt;
-    // Iterative solve on one GPU: the edge currents of an accepted step are not launched in front of the next step's
-    // psi update but behind the first status copy of its solve (pcg_solve), where the GPU would otherwise wait for the
-    // host, or when tdgl_run returns -- every reader of J outside tdgl_run therefore finds them formed.  The old order
-    // stays with: an extrapolated guess (k_extrapolate writes mu before that look), field ramps and dA/dt (the links
-    // change at step begin), screening (its own loop above), one process per GPU, the dense and run-ahead paths
-    // (they have no such look; see defer_currents), currents not formed every step, and TDGL_NO_SYNC_SHADOW.
-    const bool shadow_currents = !ctx->sync_shadow_disabled && !dense_on(ctx) && !distributed(ctx) && !ctx->levels.empty() &&
-                                 ctx->popt.extrapolate >= 3 && ctx->popt.edge_currents_every_step != 0 && !ctx->loop.ramp_on &&
-                                 !ctx->loop.has_dadt;
+    const tdgl_currents_plan plan = step_plan(ctx);  // where J_s, J_n of this step will be formed
+    MuSolveArgs solve;
     for (bool first = true;; first = false) {
-        if (ctx->currents_deferred && mu_n == ctx->mu.p && !shadow_currents) {
+        if (mu_n == ctx->mu.p && ctx->currents.take_with_psi(plan)) {  // the previous step's, owed
             launch_psi_update_with_currents(ctx, ctx->psi[cur].p, mu_n, ctx->lap[cur].p, dt, ctx->psi[nxt].p);
-            ctx->currents_deferred = false;
-            ctx->currents_valid = true;
         } else {
             launch_psi_update(ctx, ctx->psi[cur].p, mu_n, ctx->lap[cur].p, dt, ctx->psi[nxt].p, nullptr);
         }
@@ -253,26 +256,10 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
             ctx->prof_pending.emplace_back(pa, pb);
         }
         bool failed = false, abandoned = false;
-        ctx->defer_mu_halo = ctx->popt.edge_currents_every_step != 0;
-        // (direct solve: the edge currents are queued right behind it, before the step's synchronisation;
-        // after a failed psi update they hold scratch values until the repeated step rewrites them)
-        ctx->spec_currents = ctx->popt.edge_currents_every_step != 0 && !defer_currents;
-        ctx->spec_currents_done = false;
-        ctx->shadow_currents = shadow_currents;
+        solve = MuSolveArgs{ctx->popt.edge_currents_every_step != 0, plan};
         const int solve_status = pcg_solve(
-            ctx,
-            [&](const StepStatus *st) {
-                failed = st->fail_flag != 0;
-                unsigned long long bits = 0;
-                for (int k = 0; k < 8; ++k) bits = std::max(bits, st->dmax_bits[k]);
-                dmax = __builtin_bit_cast(double, bits);
-                return !failed;
-            },
-            &abandoned, /*allow_projection=*/true);
-        ctx->defer_mu_halo = false;
-        ctx->spec_currents = false;
-        ctx->shadow_currents = false;
-        if (ctx->spec_currents_done && (failed || solve_status != TDGL_OK)) ctx->currents_valid = false;
+            ctx, solve, [&](const StepStatus *st) { return psi_outcome(st, &failed, &dmax); }, &abandoned, /*allow_projection=*/true);
+        if (solve.currents_queued && (failed || solve_status != TDGL_OK)) ctx->currents.speculation_failed();
         // A step that ends in an error must leave the accepted state behind: the extrapolation
         // moved mu^n to mu_prev and wrote a guess into mu.  Put mu^n back (the history is dropped:
         // mu^{n-2} was overwritten) so that tdgl_get_state returns the last accepted step and a
@@ -315,12 +302,7 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
     ctx->prev_dt = dt;
     ctx->loop.cur = nxt;
     ctx->lap_valid = true;
-    ctx->currents_valid = false;
-    if (ctx->spec_currents_done) {
-        ctx->currents_valid = true;  // already queued by the direct solve
-    } else if (defer_currents || shadow_currents) {
-        ctx->currents_deferred = true;  // with the next psi update / behind the next solve's first look, or when tdgl_run returns
-    } else if (ctx->popt.edge_currents_every_step) {
+    if (ctx->currents.accept(plan, solve.currents_queued)) {  // (else: queued by the direct solve already, owed, or on request)
         if (ctx->pend_v) {  // ghost values of mu still travelling: edges between owned sites first
             launch_edge_currents(ctx, ctx->psi[nxt].p, ctx->mu.p, ctx->js.p, ctx->jn.p, 1);
             TDGL_TRY(comm_halo_wait(ctx));
@@ -328,7 +310,6 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
         } else {
             launch_edge_currents(ctx, ctx->psi[nxt].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
         }
-        ctx->currents_valid = true;
     }
     if (ctx->pend_v) TDGL_TRY(comm_halo_wait(ctx));
     return step_finish(ctx, dt, dmax, dt_used, probe_mu, probe_theta, pcg_iters);
@@ -388,16 +369,9 @@ static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out) {
             launch_psi_laplacian(ctx, true, ctx->psi[nxt].p, ctx->lap[nxt].p);
             bool failed = false, abandoned = false;
             // (mu is only written once the update is known to have succeeded)
+            MuSolveArgs solve;  // (the currents follow below, in every iteration)
             TDGL_TRY(pcg_solve(
-                ctx,
-                [&](const StepStatus *st) {
-                    failed = st->fail_flag != 0;
-                    unsigned long long bits = 0;
-                    for (int k = 0; k < 8; ++k) bits = std::max(bits, st->dmax_bits[k]);
-                    dmax = __builtin_bit_cast(double, bits);
-                    return !failed;
-                },
-                &abandoned, /*allow_projection=*/true));
+                ctx, solve, [&](const StepStatus *st) { return psi_outcome(st, &failed, &dmax); }, &abandoned, /*allow_projection=*/true));
             if (!failed) break;
             if (!ctx->loop.retry())
                 TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES, "%s", ctx->loop.budget_message(-1, dt).c_str());
@@ -410,7 +384,7 @@ static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out) {
     }
     ctx->last_screening_iters = it;
     ctx->lap_valid = false;  // the links move with A_induced; the next step rebuilds L psi anyway
-    ctx->currents_valid = true;
+    ctx->currents.screening_done();
     ctx->prev_dt = ctx->prev_dt2 = 0.0;  // no extrapolated initial guess across screening steps
     *dt_out = dt;
     *dmax_out = dmax;
@@ -437,9 +411,9 @@ static bool run_ahead_ok(const tdgl_ctx *ctx) {
     // (a moving vector potential: only the ramp or table the loop evaluates itself rides along -- k_ra_ramp_begin,
     // k_ra_table_begin --, and it needs the previous step's dt: from the second step of a stage on)
     if (ctx->loop.ramping() ? !(ctx->loop.runner_dt > 0.0) : ctx->loop.has_dadt) return false;
-    return !off && dense_on(ctx) && (ctx->direct->dense.tiles > 0) && !ctx->scr_enabled &&
-           (ctx->tab_mu_t.empty() || ctx->tab_mu_on_device) && (ctx->tab_eps_t.empty() || ctx->tab_eps_on_device) &&
-           ctx->popt.edge_currents_every_step != 0 && ctx->have_links &&
+    // (the plans of the direct solve: no screening, currents every step)
+    return !off && dense_on(ctx) && (ctx->direct->dense.tiles > 0) && currents_plan_runs_ahead(step_plan(ctx)) &&
+           (ctx->tab_mu_t.empty() || ctx->tab_mu_on_device) && (ctx->tab_eps_t.empty() || ctx->tab_eps_on_device) && ctx->have_links &&
            ctx->have_state && ctx->have_eps && (!ctl.adaptive || (ctl.adaptive_window >= 1 && ctl.adaptive_window <= RA_HIST_MAX));
 }
 
@@ -459,7 +433,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctl.p, &h, sizeof(StepCtl), hipMemcpyHostToDevice, ctx->stream));
     const int np_ = (int)ctx->probes.size();
     const bool probing = np_ > 0 && want_probes;
-    const bool old_deferred = ctx->currents_deferred;
+    const bool owed_on_entry = ctx->currents.owed();
     const bool mu_table = !ctx->tab_mu_t.empty(), eps_table = !ctx->tab_eps_t.empty();
     if (mu_table) {
         // The positions no table covers keep the host's values: uploaded once, b_mu then stays resident (the table
@@ -491,7 +465,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
             // retries and dead attempts, decided on the device
             StepCtl *dc = ctx->d_ctl.p;
             const int32_t *go = &dc->ramp_do, *moved = ctx->link_changed.p;
-            if (s > 0 || old_deferred)
+            if (EdgeCurrents::batch_attempt_takes(s, owed_on_entry))
                 hipLaunchKernelGGL(k_ra_edge_currents, dim3(grid_for(ctx->m)), dim3(BLOCK), 0, ctx->stream, ctx->m, (const int32_t *)ctx->e0.p,
                                    (const int32_t *)ctx->e1.p, (const double *)ctx->e_inv_len.p, (const double2 *)ctx->e_U.p,
                                    (const double2 *)ctx->psi[0].p, (const double2 *)ctx->psi[1].p, (const double *)ctx->mu.p, ctx->js.p, ctx->jn.p,
@@ -519,7 +493,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
             launch_ra_laplacian_fresh(ctx);
         }
         // (the edge currents of psi^n ride along: always behind the first attempt, for the first if they are owed)
-        launch_ra_psi(ctx, !ramping && (s > 0 || old_deferred));
+        launch_ra_psi(ctx, !ramping && EdgeCurrents::batch_attempt_takes(s, owed_on_entry));
         // (K1 is timed once per batch in profile mode: event markers between back-to-back launches cost more
         // than the launches they bracket at these sizes)
         hipEvent_t pa = nullptr, pb = nullptr;
@@ -577,7 +551,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
         TDGL_FAIL(ctx, TDGL_ERR_HIP, "run-ahead: corrupt attempt records (%d processed, %d accepted of %d; check %d)", done, h.n_acc, batch, b.corrupt);
     for (int s = 0; s < done; ++s)
         if (ctx->h_rec[s].ok) direct_note_step(ctx, ctx->h_rec[s].dmax, 0);
-    const int acc = b.accepted, last_acc_idx = b.last_accepted;
+    const int acc = b.accepted;
     *accepted = acc;
     *reached = b.reached;
     ctx->stat_ra_batches += 1;
@@ -590,19 +564,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
     }
     ctx->lap_valid = true;
     ctx->probe_ring_count += probing ? acc : 0;
-    // edge currents: every live attempt behind the first forms those of psi^n as it stood when the attempt began
-    if (acc > 0) {
-        if (done > last_acc_idx + 1) {  // a later live attempt (a failed one) saw the last accepted state
-            ctx->currents_valid = true;
-            ctx->currents_deferred = false;
-        } else {
-            ctx->currents_valid = false;
-            ctx->currents_deferred = true;
-        }
-    } else if (done > 0 && (old_deferred || done > 1)) {
-        ctx->currents_valid = true;
-        ctx->currents_deferred = false;
-    }
+    ctx->currents.absorb_batch(done, b.last_accepted, acc, owed_on_entry);
     if (b.error) TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES, "%s", ctx->loop.budget_message(-1, b.last_fail_dt).c_str());
     return TDGL_OK;
 }
@@ -681,11 +643,8 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
         }
         ++k;
     }
-    if (ctx->currents_deferred) {  // J_s, J_n of the last accepted step (see step_once: defer_currents)
+    if (ctx->currents.flush())  // J_s, J_n of the last accepted step, still owed
         launch_edge_currents(ctx, ctx->psi[ctx->loop.cur].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
-        ctx->currents_deferred = false;
-        ctx->currents_valid = true;
-    }
     // (also after an error: the steps completed before it keep their read-outs)
     const int flush_status = probe_ring_flush(ctx, flushed, out_mu_probe, out_theta_probe);
     if (status == TDGL_OK && flush_status == TDGL_OK) {

@@ -680,7 +680,7 @@ static int finish_links(tdgl_ctx *ctx, bool dynamic, double dt_prev) {
     HIP_TRY(ctx, hipGetLastError());
     ctx->have_links = true;
     ctx->lap_valid = false;
-    ctx->currents_valid = false;
+    ctx->currents.new_links();
     return TDGL_OK;
 }
 
@@ -961,8 +961,7 @@ extern "C" int tdgl_set_state(tdgl_ctx *ctx, const double *psi, const double *mu
     TDGL_TRY(upload_sites(ctx, mu, ctx->mu));
     ctx->have_state = true;
     ctx->lap_valid = false;
-    ctx->currents_valid = false;
-    ctx->currents_deferred = false;
+    ctx->currents.new_state();
     ctx->loop.new_state(ctx->loop.cur);
     ctx->prev_dt = ctx->prev_dt2 = 0.0;  // no mu history: the next solve starts from mu itself
     ctx->guess.reset();                   // (nor a projection basis)
@@ -1005,11 +1004,11 @@ extern "C" int tdgl_set_probes(tdgl_ctx *ctx, const int32_t *sites, int32_t n_pr
 
 // ---------------------------------------------------------------------------------------
 static int ensure_currents(tdgl_ctx *ctx) {
-    if (ctx->currents_valid) return TDGL_OK;
+    if (ctx->currents.formed()) return TDGL_OK;
     if (!ctx->have_links) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "link exponents not set");
     launch_edge_currents(ctx, ctx->psi[ctx->loop.cur].p, ctx->mu.p, ctx->js.p, ctx->jn.p);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->currents_valid = true;
+    ctx->currents.request();
     return TDGL_OK;
 }
 

@@ -302,6 +302,42 @@ struct LoopState {
     }
 };
 
+// Where the step driver forms J_s, J_n of the step it accepts (tdgl_currents_plan), chosen per step by currents_plan
+// (loop.inc) and by nobody else; the run-ahead loop takes the steps of the two plans of the direct solve.
+tdgl_currents_plan currents_plan(const tdgl_currents_facts &f);
+inline bool currents_plan_runs_ahead(tdgl_currents_plan p) { return p == TDGL_CURRENTS_SPECULATIVE || p == TDGL_CURRENTS_WITH_NEXT_PSI; }
+
+// What js / jn hold, one per context.  FORMED: the currents of psi^n, mu^n with the links in force.  OWED: not formed, but
+// the step that owes them left its inputs intact -- the next launch that may take them (or tdgl_run's return) forms them.
+// STALE: neither.  Its functions (loop.inc) are the only writers; each says whether its caller has a launch to make.
+struct EdgeCurrents {
+    enum State : int32_t { STALE, FORMED, OWED };
+    State state = STALE;
+    bool formed() const { return state == FORMED; }
+    bool owed() const { return state == OWED; }
+    void new_state() { state = STALE; }  // tdgl_set_state, a replica loaded into the context
+    void new_links();
+    bool take_with_psi(tdgl_currents_plan plan);
+    bool take_behind_look(tdgl_currents_plan plan);
+    void speculation_failed();
+    bool accept(tdgl_currents_plan plan, bool queued);
+    bool request();
+    bool flush() { return owed() && request(); }  // tdgl_run returns: what is owed is formed
+    static bool batch_attempt_takes(int s, bool owed_on_entry) { return s > 0 || owed_on_entry; }
+    void absorb_batch(int done, int last_accepted, int accepted, bool owed_on_entry);
+    void screening_done() { state = FORMED; }  // (every screening iteration forms them: step_screening)
+};
+
+// What the step driver tells a mu solve and hears back from it (pcg_solve, direct_mu_solve); a solve outside the time
+// loop passes the default.
+struct MuSolveArgs {
+    bool mu_halo_pending = false;  // in: leave the exchange of mu's ghosts started, the caller overlaps it and waits
+    tdgl_currents_plan plan = TDGL_CURRENTS_ON_REQUEST;  // in: this step's
+    bool currents_queued = false;  // out: the solve queued the step's currents behind itself (TDGL_CURRENTS_SPECULATIVE)
+    // a direct solve inside a step (in_step) queues them at once where the plan says so
+    bool speculate(bool in_step) { return currents_queued = in_step && plan == TDGL_CURRENTS_SPECULATIVE; }
+};
+
 struct StepStatus {
     int32_t fail_flag;          // psi update: discriminant < 0 or non-finite somewhere
     int32_t pad;
@@ -472,7 +508,6 @@ struct tdgl_ctx {
     hipEvent_t ev_pack = nullptr, ev_halo = nullptr;
     int int_tiles = 0;        // leading 256-row tiles whose rows have no ghost neighbour
     int64_t m_int = 0;        // leading edges (internal order) between two owned sites
-    bool defer_mu_halo = false;  // pcg_solve leaves the exchange of mu's ghosts pending (run.inc)
     int overlap = 1;          // tdgl_set_comm_overlap: 0 off, 1 auto (by size), 2 always
     int64_t stat_halos = 0, stat_halo_bytes = 0, stat_allreduces = 0, stat_allreduce_bytes = 0;
     double *pend_v = nullptr; // exchange started by comm_halo_start, completed by comm_halo_wait
@@ -541,7 +576,7 @@ struct tdgl_ctx {
     bool lap_valid = false;
     tdgl::DevBuf<double> mu, eps, bvec;
     tdgl::DevBuf<double> js, jn;          // per edge, internal order
-    bool currents_valid = false;
+    tdgl::EdgeCurrents currents;          // what js / jn hold (loop.inc)
     bool have_links = false, have_state = false, have_eps = false;
 
     // ---- Poisson ---------------------------------------------------------------------
@@ -591,16 +626,11 @@ struct tdgl_ctx {
     int ra_batch = 4;                     // attempts queued per synchronisation: doubles up to RA_BATCH_MAX
     bool run_ahead_disabled = false;      // TDGL_NO_RUN_AHEAD, read once when the context is created (tests, A/B runs)
     int64_t stat_ra_batches = 0, stat_ra_dead = 0;
-    bool currents_deferred = false;       // J of the last accepted step ride in the next step's psi-update launch
-                                          // (dense path) or behind its first status copy (iterative path, run.inc)
     // Work queued behind a status copy while the host waits for it (poisson.inc: sync_status).  TDGL_NO_SYNC_SHADOW,
     // read once when the context is created, restores the order without it (tests, A/B runs).
     bool sync_shadow_disabled = false;
     hipEvent_t ev_status = nullptr;       // recorded right behind the status copy: the host waits for it, not for the stream
-    bool shadow_currents = false;         // step driver: the owed currents may follow this solve's first status copy
     int64_t stat_edge_launches = 0;       // formations of J_s / J_n since the last reset (tdgl_get_edge_current_launches)
-    bool spec_currents = false;           // step driver: queue the edge currents right behind the dense solve,
-    bool spec_currents_done = false;      // before the host has seen the step's status (run.inc)
     // collapsed coarse chain (tdgl_poisson_set_collapsed_tail): everything from level `tail_level`
     // down as explicit operators, built for the smoother settings (tail_nu, tail_smoother, tail_cheb_lo)
     int tail_level = -1;                  // -1: off

@@ -128,6 +128,28 @@ class LoopReplay(C.Structure):
     ]
 
 
+# tdgl_currents_plan: where the step driver forms J_s, J_n of an accepted step
+CURRENTS_NOW, CURRENTS_SPECULATIVE, CURRENTS_WITH_NEXT_PSI, CURRENTS_BEHIND_NEXT_LOOK, CURRENTS_ON_REQUEST = range(5)
+
+
+class CurrentsFacts(C.Structure):
+    _fields_ = [(name, C.c_int32) for name in (
+        "dense_on", "distributed", "hierarchy", "extrapolate", "edge_currents_every_step", "ramp_on", "has_dadt",
+        "sync_shadow_disabled", "screening")]
+
+
+class CurrentsReplay(C.Structure):
+    _fields_ = [
+        ("n_accepted", C.c_int64),
+        ("n_attempts", C.c_int64),
+        ("n_formations", C.c_int64),
+        ("plan", C.c_int32),
+        ("state", C.c_int32),
+        ("reached", C.c_int32),
+        ("error", C.c_int32),
+    ]
+
+
 class PoissonOptions(C.Structure):
     _fields_ = [
         ("rtol", C.c_double),
@@ -328,6 +350,11 @@ SIGNATURES = {
         C.c_int,
         [C.POINTER(Controller), C.c_double, C.c_int64, c_f64p, c_i32p, C.c_int32, C.c_int32, C.POINTER(Controller),
          C.c_int64, c_f64p, c_f64p, C.POINTER(LoopReplay)],
+    ),
+    "tdgl_host_currents_replay": (
+        C.c_int,
+        [C.c_int32, C.POINTER(CurrentsFacts), C.POINTER(Controller), C.c_double, C.c_int64, c_f64p, c_i32p, C.c_int32,
+         C.c_int32, C.c_int64, c_i64p, c_i32p, c_i64p, C.POINTER(CurrentsReplay)],
     ),
     "tdgl_host_blr_compress": (C.c_int32, [c_f64p, C.c_int32, C.c_double, C.c_int32, c_f64p, c_f64p]),
     "tdgl_begin_stage": (C.c_int, [_CTX]),

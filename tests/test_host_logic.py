@@ -686,6 +686,136 @@ def test_a_new_controller_clears_a_pending_retry():
         assert got["retries"] == 0 and got["stage_step"] == 4 and got["dt"][-4:] == [new.dt_init] * 4
 
 
+# ---------------------------------------------------------------- where J_s and J_n are formed, replayed on the host
+_PLANS = ("now", "speculative", "with_next_psi", "behind_next_look", "on_request")  # tdgl_currents_plan, by value
+_FACTS = ("dense_on", "distributed", "hierarchy", "extrapolate", "edge_currents_every_step", "ramp_on", "has_dadt",
+          "sync_shadow_disabled", "screening")
+
+
+def _currents_replay(plan, ctl, end_time, dmax, fail, batch, mode, actions=(), facts=None):
+    """tdgl_host_currents_replay: (formed_at of the accepted steps, result struct as a dict)."""
+    import ctypes as C
+
+    from tdgl_amd import _lib
+
+    lib = _lib.load()
+    n = len(dmax)
+    d = np.ascontiguousarray(dmax, dtype=np.float64)
+    f = np.ascontiguousarray(fail, dtype=np.int32)
+    at = np.ascontiguousarray([a[0] for a in actions], dtype=np.int64)
+    kind = np.ascontiguousarray([a[1] for a in actions], dtype=np.int32)
+    formed_at = np.full(max(n, 1), -7, dtype=np.int64)
+    res = _lib.CurrentsReplay()
+    f64, i32, i64 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    status = lib.tdgl_host_currents_replay(plan, C.byref(facts) if facts is not None else None, C.byref(ctl), end_time, n,
+                                           d.ctypes.data_as(f64), f.ctypes.data_as(i32), batch, mode, len(actions),
+                                           at.ctypes.data_as(i64), kind.ctypes.data_as(i32), formed_at.ctypes.data_as(i64),
+                                           C.byref(res))
+    assert status == _lib.TDGL_OK
+    got = {name: getattr(res, name) for name, _ in _lib.CurrentsReplay._fields_}
+    return formed_at[:res.n_accepted].tolist(), got
+
+
+def _currents_model(plan, accepted_at, actions, formed_at):
+    """Every accepted step's currents are formed once, in time.  Events are numbered 4 i + p (p = 0: a caller's action
+    in front of attempt i, 1: the psi update of attempt i, 2: behind the first look of its solve, 3: its solve, which
+    writes mu, and what follows).  The currents of the step accepted by attempt a read its psi and mu: the event that
+    forms them comes with or after 4 a + 3, before the next accepted attempt's 4 a' + 3 overwrites mu, and no later
+    than the first return that follows (every action is one: 0 return, 1 ... and a read, 2 ... and a set-state).  Currents
+    on request: formed by the first read in that window that no set-state precedes, and by nothing else."""
+    for k, a in enumerate(accepted_at):
+        lo = 4 * a + 3
+        overwritten = 4 * accepted_at[k + 1] + 3 if k + 1 < len(accepted_at) else float("inf")
+        if plan != _PLANS.index("on_request"):
+            deadline = min(4 * at for at, _ in actions if 4 * at > lo)
+            assert lo <= formed_at[k] < overwritten and formed_at[k] <= deadline, (k, formed_at[k], lo, overwritten, deadline)
+            continue
+        later = [(4 * at, kind) for at, kind in actions if lo < 4 * at < overwritten]
+        kinds = [kind for _, kind in later if kind != 0]
+        want = next(e for e, kind in later if kind == 1) if kinds and kinds[0] == 1 else -1
+        assert formed_at[k] == want, (k, formed_at[k], want)
+    return sum(1 for e in formed_at if e >= 0)
+
+
+@pytest.mark.parametrize("plan", range(len(_PLANS)), ids=_PLANS)
+@pytest.mark.parametrize("script", _LOOP_SCRIPTS, ids=_LOOP_IDS)
+def test_every_accepted_steps_currents_are_formed_once_and_in_time(script, plan):
+    """The ledger and the plan the time loops ask (loop.inc: EdgeCurrents, currents_plan), driven by the loop replay's
+    scripts -- no failures, isolated retries, a spent retry budget, an end inside a batch -- in the loop with one
+    synchronisation per step and in run-ahead batches of 1, 4 and 64 attempts, with and without a caller who returns,
+    reads the currents or sets a state in between, against the model above.  Wherever currents are formed every step
+    the number of formations is the number of accepted steps (what tests/test_hip_sync_shadow.py counts on the
+    device)."""
+    name, ctl, end_time, dmax, fail = script
+    played = _loop_replay(ctl, end_time, dmax, fail, 1, 0)
+    accepted_at = [i for i in range(played["n_attempts"]) if not fail[i]]
+    assert len(accepted_at) == played["n_accepted"] > 0
+    # the caller comes back right behind an accepted attempt (tdgl_run returns after a step): early, in the middle, at the end
+    behind = sorted({accepted_at[k] + 1 for k in (0, 1, 2, len(accepted_at) // 2, len(accepted_at) - 1) if k < len(accepted_at)})
+    end = (played["n_attempts"], 0)  # (the replay ends with a return)
+    for kinds in ((), (0, 1, 2), (1, 1, 0), (2, 1, 1)):
+        actions = [(at, kinds[j % len(kinds)]) for j, at in enumerate(behind)] if kinds else []
+        for mode, batch in ((0, 1), (1, 1), (1, 4), (1, 64)):
+            formed_at, got = _currents_replay(plan, ctl, end_time, dmax, fail, batch, mode, actions)
+            where = (name, _PLANS[plan], kinds, mode, batch)
+            assert got["plan"] == plan and got["n_attempts"] == played["n_attempts"], where
+            assert got["n_accepted"] == played["n_accepted"] and got["error"] == played["error"] and got["reached"] == played["reached"], where
+            n_formed = _currents_model(plan, accepted_at, actions + [end], formed_at)
+            assert got["n_formations"] == n_formed, where
+            if plan != _PLANS.index("on_request"):
+                assert got["n_formations"] == got["n_accepted"], where
+            if not kinds:  # nobody in between: every plan forms them at the place it is named after
+                phase = {e % 4 for e in formed_at[:-1]}
+                ahead = mode == 1 and _PLANS[plan] in ("speculative", "with_next_psi")
+                want = {"now": {3}, "speculative": {3}, "with_next_psi": {1}, "behind_next_look": {2}, "on_request": {3}}[_PLANS[plan]]
+                if _PLANS[plan] == "on_request":
+                    assert set(formed_at) == {-1} and got["state"] == 0, where
+                elif len(formed_at) > 1:
+                    assert phase == ({1} if ahead else want), where
+                if _PLANS[plan] != "on_request" and not got["error"]:
+                    assert got["state"] == 1, where  # formed
+
+
+def test_the_plan_of_the_edge_currents_against_the_flags_it_replaces():
+    """currents_plan against the expressions the step driver computed inline before there was a plan (run.inc of the
+    parent commit, lines 186-195 and 259), for every combination of the facts they read:
+      defer_currents  = dense_on && every_step && !ramp_on && !has_dadt                          -> with the next psi update
+      shadow_currents = !sync_shadow_disabled && !dense_on && !distributed && hierarchy && extrapolate >= 3 && every_step
+                        && !ramp_on && !has_dadt                                                 -> behind the next first look
+      spec_currents   = every_step && !defer_currents, read by the direct solve alone            -> speculative
+      none of them: a launch after the solve if every_step, else on request.
+    With screening the step driver never reached those lines (step_screening forms them in its own loop): now."""
+    import itertools
+
+    from tdgl_amd import _lib
+
+    ctl = _controller()
+    seen = set()
+    for bits in itertools.product((0, 1), repeat=8):
+        for extrapolate in (0, 1, 2, 3):
+            f = dict(zip([n for n in _FACTS if n != "extrapolate"], bits), extrapolate=extrapolate)
+            defer = f["dense_on"] and f["edge_currents_every_step"] and not f["ramp_on"] and not f["has_dadt"]
+            shadow = (not f["sync_shadow_disabled"] and not f["dense_on"] and not f["distributed"] and f["hierarchy"]
+                      and extrapolate >= 3 and f["edge_currents_every_step"] and not f["ramp_on"] and not f["has_dadt"])
+            spec = f["edge_currents_every_step"] and not defer
+            assert not (defer and shadow)
+            if f["screening"]:
+                want = "now"
+            elif defer:
+                want = "with_next_psi"
+            elif shadow:
+                want = "behind_next_look"
+            elif spec and f["dense_on"]:
+                want = "speculative"
+            else:
+                want = "now" if f["edge_currents_every_step"] else "on_request"
+            _, got = _currents_replay(-1, ctl, 0.0, [], [], 1, 0, facts=_lib.CurrentsFacts(*[f[n] for n in _FACTS]))
+            assert _PLANS[got["plan"]] == want, (f, _PLANS[got["plan"]], want)
+            seen.add(want)
+    assert seen == set(_PLANS)
+    assert [getattr(_lib, "CURRENTS_" + p.upper()) for p in _PLANS] == list(range(5))
+
+
 def test_collapsed_coarse_operators_are_the_same_cycle():
     """amg.collapsed_operators: intermediate-level M = R (I - A S), the tail as dense G / sparse W /
     dense V (or one dense matrix).  With one tail cycle the chain is the plain V-cycle re-associated;
