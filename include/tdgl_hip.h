@@ -835,6 +835,13 @@ int tdgl_normal_current(tdgl_ctx *ctx, const double *mu, double *out);
 /* One application of the AMG V-cycle preconditioner z = M^-1 r on level-0 vectors given in
  * REFERENCE site order (for cross-checks against the host restatement of the cycle). */
 int tdgl_vcycle(tdgl_ctx *ctx, const double *r, double *z);
+/* One application of the substructure factors as the CG's preconditioner (tdgl_poisson_set_substructure_precond),
+ * z = M r with M ~ pinv(A): r and z [n_sites] in REFERENCE site order like tdgl_vcycle, *rz = r . z as the CG forms it
+ * (the scatter kernel's per-workgroup partials added in index order).  Works on buffers of its own: the CG's vectors,
+ * guess and counters are untouched, a tdgl_poisson_solve before and after returns the same bits.  For cross-checks of
+ * the factor sweeps against a host model of the stored factors.  TDGL_ERR_NOT_READY (with a message) without factors,
+ * when the factors are the mu SOLVER rather than the preconditioner, and in one-process-per-GPU contexts. */
+int tdgl_precond_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz);
 /* The dot-product pass of the projection guess (k_multi_dot) on caller-supplied vectors [k, n] and b [n]
  * (k <= 16): out_pairs[2 a], out_pairs[2 a + 1] = (hi, lo) double-double sums of array a in {0: b . b,
  * 1: sum b, 2 + j: y_j . b, 18 + j: y_newest . y_j (newest = -1: zeros)}; 2 * 34 doubles. */

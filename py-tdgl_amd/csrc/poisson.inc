@@ -1878,3 +1878,33 @@ extern "C" int tdgl_vcycle(tdgl_ctx *ctx, const double *r, double *z) {
     HIP_TRY(ctx, hipGetLastError());
     return download_sites(ctx, res, z);
 }
+
+// Per-kernel entry point (tests of the factor sweeps): ONE application of the factor preconditioner, z = M r, on vectors
+// in the caller's site order, on buffers of its own -- the CG's vectors, partials and counters are not touched (the
+// factors' own work vectors are: every application overwrites them).  *rz = r . z as the CG sees it: k_pd_scatter's
+// partials added up in index order.
+extern "C" int tdgl_precond_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz) {
+    CTX_GUARD(ctx);
+    if (!r || !z || !rz) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_precond_apply: null argument");
+    // (a rank of a one-process-per-GPU run: its preconditioner is the rank-level dissection, whose application has collectives)
+    if (ctx->n_own != ctx->n || distributed(ctx) || (ctx->direct && ctx->direct->n_local > 0))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_precond_apply: single-GPU contexts only (one process per GPU: the rank-level dissection is applied by every rank at once)");
+    if (!ctx->direct || ctx->direct->levels == 0)
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_precond_apply: no substructure factors (tdgl_poisson_set_substructure_precond)");
+    if (!precond_factors_available(ctx))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_precond_apply: the factors are the mu solver, not the CG's preconditioner (tdgl_poisson_solve applies them)");
+    DevBuf<double> in, out, part;
+    HIP_TRY(ctx, in.alloc(ctx->n_pad));
+    HIP_TRY(ctx, out.alloc(ctx->n_pad));
+    HIP_TRY(ctx, part.alloc((size_t)ctx->npart));
+    TDGL_TRY(upload_sites(ctx, r, in));
+    precond_direct_apply(ctx, in.p, out.p, part.p);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<double> h((size_t)ctx->npart);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TDGL_TRY(download_sites(ctx, out.p, z));  // (synchronises the stream)
+    double s = 0.0;
+    for (double v : h) s += v;
+    *rz = s;
+    return TDGL_OK;
+}

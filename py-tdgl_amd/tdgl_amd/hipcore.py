@@ -1460,6 +1460,14 @@ class TDGLContext:
         self._chk(self._lib.tdgl_vcycle(self._ctx, p_f64(r), p_f64(z)))
         return z
 
+    def precond_apply(self, r):
+        """`tdgl_precond_apply`: one application of the factor preconditioner, ``(z, r . z)``; the CG's state stays as it is."""
+        r = f64(r)
+        z = np.empty(self.n)
+        rz = np.zeros(1)
+        self._chk(self._lib.tdgl_precond_apply(self._ctx, p_f64(r), p_f64(z), p_f64(rz)))
+        return z, float(rz[0])
+
     def guess_dots(self, vectors, b, newest=-1):
         """The projection guess's dot-product pass on ``vectors [k, n]`` and ``b [n]`` (parity tests): dict of
         ``(hi, lo)`` double-double sums ``bb, sb, yb [k, 2], yy [k, 2]`` (``yy``: ``vectors[newest] . vectors[j]``)."""
