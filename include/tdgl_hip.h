@@ -572,12 +572,38 @@ int tdgl_update_link_exponents(tdgl_ctx *ctx, const double *A_new, double dt_pre
  *                                 factor rests on a plateau nothing is recomputed, and from the last node on the run
  *                                 costs what a static one does.  n_nodes = 0 switches the table off.  A table and a
  *                                 ramp exclude each other: the later call wins.
- *   tdgl_get_link_scale           the factor of the current A (for saving A_applied). */
+ *   tdgl_get_link_scale           the factor of the current A (for saving A_applied).
+ *
+ * A sum of such terms, A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K with 1 <= K <= TDGL_FIELD_TERMS_MAX (a bias field plus a
+ * pulsed local one, two independently swept components), is evaluated by tdgl_run in the same way:
+ *   tdgl_set_link_terms           A0 [n_edges, 2] or NULL (no static part), bases [n_terms][n_edges, 2], and per term
+ *                                 kind[k] = 1: a LinearRamp with ramp[4 k ..] = tmin, tmax, initial, final; kind[k] = 2: a
+ *                                 table with the nodes tab_off[k] .. tab_off[k + 1] of tab_times / tab_values.  The rules of
+ *                                 tdgl_set_link_ramp (finite, tmax > tmin) and tdgl_set_link_table hold term by term and
+ *                                 are checked before anything in force is touched.  Sets A = A_prev = A(0), dA/dt = 0.
+ *                                 Per edge and component A = ((A_0 + s_1 A_1) + s_2 A_2) + ..., every product rounded
+ *                                 before it is added (no fused multiply-add), without A_0 starting from the first product
+ *                                 -- what NumPy computes from the same factors, bit for bit.  A step moves nothing only
+ *                                 when every factor equals its last two evaluations; once the time has passed every
+ *                                 term's end (tmax, last node) and every factor has been seen twice at its end value the
+ *                                 run costs what a static one does.  It needs no tdgl_set_link_exponents_base; terms,
+ *                                 ramp and table exclude each other, the later call wins.
+ *   tdgl_update_link_terms        moves the field to the given K factors now, dA/dt with dt_prev -- what tdgl_run does
+ *                                 itself before a step of the loop with one synchronisation per step.
+ *   tdgl_get_link_term_scales     the K factors of the current A (n_terms = 0: no terms are set).
+ *   tdgl_get_link_term_moves      how many steps have moved the sum since it was set, in either loop (the others found
+ *                                 every factor unchanged and skipped the edge pass). */
+#define TDGL_FIELD_TERMS_MAX 4
 int tdgl_set_link_exponents_base(tdgl_ctx *ctx, const double *A_base, double scale);
 int tdgl_update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev);
 int tdgl_set_link_ramp(tdgl_ctx *ctx, int32_t on, double tmin, double tmax, double initial, double final_value);
 int tdgl_set_link_table(tdgl_ctx *ctx, int32_t n_nodes, const double *times, const double *values);
 int tdgl_get_link_scale(tdgl_ctx *ctx, double *scale);
+int tdgl_set_link_terms(tdgl_ctx *ctx, const double *A0, int32_t n_terms, const double *bases, const int32_t *kind,
+                        const double *ramp, const int32_t *tab_off, const double *tab_times, const double *tab_values);
+int tdgl_update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev);
+int tdgl_get_link_term_scales(tdgl_ctx *ctx, int32_t *n_terms, double *scales);
+int tdgl_get_link_term_moves(tdgl_ctx *ctx, int64_t *moves);
 /* self.epsilon (solver.py:191-216, 645-648). */
 int tdgl_set_epsilon(tdgl_ctx *ctx, const double *epsilon);
 /* self.mu_boundary (solver.py:289, 325-345): indexed by position in boundary_edge_indices. */
@@ -860,7 +886,7 @@ int tdgl_guess_dots(tdgl_ctx *ctx, int32_t k, int64_t n, const double *vectors, 
  * replica in five launches over all of them (dense inverse; 6 + 2 per level with the substructured factors); the host synchronises once per batch of rounds.  The per-replica
  * setters form their input with the context's own entry point of the same name and copy it: the context's own run
  * state is overwritten.  Time-dependent inputs are the forms the run-ahead loop evaluates on the device: a
- * replica's field ramp (tdgl_ensemble_set_link_ramp) or field table (tdgl_ensemble_set_link_table), tabulated terminal currents and separable epsilon, each
+ * replica's field ramp (tdgl_ensemble_set_link_ramp), field table (tdgl_ensemble_set_link_table) or sum of such terms (tdgl_ensemble_set_link_terms), tabulated terminal currents and separable epsilon, each
  * evaluated at the replica's own time; no per-step host input, no screening.  Release the ensemble before the
  * context. */
 typedef struct tdgl_ensemble tdgl_ensemble;
@@ -886,6 +912,10 @@ int tdgl_ensemble_begin_stage(tdgl_ensemble *ens, int32_t r);
  * set_link_table: A(t) = table(t) * A_base [n_edges, 2] with the table of tdgl_set_link_table (n_nodes >= 1, which may
  *   differ between replicas); otherwise as set_link_ramp, which it replaces for the replica and which replaces it.
  *   tdgl_ensemble_set_link_exponents switches the table off.
+ * set_link_terms: A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K with the arguments and rules of tdgl_set_link_terms, each replica
+ *   with its own terms, tables and copy of the bases ((K + 1) 2 n_edges doubles per replica; a failed allocation is an
+ *   error like any other); it replaces ramp and table for the replica and they replace it.  A refused argument leaves the
+ *   replica as it was.  get_link_term_scales: the factors of the last step taken.
  * set_mu_boundary_table: terminal current densities as piecewise-linear tables (tdgl_set_mu_boundary_table);
  *   n_nodes may differ between replicas; n_nodes = 0: off.
  * set_epsilon_table: epsilon(r, t) = factor(t) epsilon0(r) (tdgl_set_epsilon_table); n_nodes = 0: off. */
@@ -894,6 +924,10 @@ int tdgl_ensemble_set_link_ramp(tdgl_ensemble *ens, int32_t r, const double *A_b
 int tdgl_ensemble_set_link_table(tdgl_ensemble *ens, int32_t r, const double *A_base, int32_t n_nodes, const double *times,
                                  const double *values);
 int tdgl_ensemble_get_link_scale(tdgl_ensemble *ens, int32_t r, double *scale);
+int tdgl_ensemble_set_link_terms(tdgl_ensemble *ens, int32_t r, const double *A0, int32_t n_terms, const double *bases,
+                                 const int32_t *kind, const double *ramp, const int32_t *tab_off, const double *tab_times,
+                                 const double *tab_values);
+int tdgl_ensemble_get_link_term_scales(tdgl_ensemble *ens, int32_t r, int32_t *n_terms, double *scales);
 int tdgl_ensemble_set_mu_boundary_table(tdgl_ensemble *ens, int32_t r, int32_t n_nodes, const double *times,
                                         int32_t n_groups, const int32_t *group_ptr, const int32_t *group_pos,
                                         const double *density);

@@ -212,7 +212,7 @@ __global__ void k_ens_probes(int n_probe, const int32_t *__restrict__ sites, con
 // R1: one thread per replica.  kind[r] says where the replica's factor comes from in this batch: LINK_RAMP the ramp in its
 // controller (ramp_begin_body), LINK_TABLE its table (table_begin_body: nodes l_off[r] .. l_off[r + 1] of the pools),
 // LINK_NONE nothing moves: ramp_do = 0, as the single run that queues no ramp launch at all
-enum : int32_t { LINK_NONE = 0, LINK_RAMP = 1, LINK_TABLE = 2 };
+enum : int32_t { LINK_NONE = 0, LINK_RAMP = 1, LINK_TABLE = 2, LINK_TERMS = 3 };  // (LINK_TERMS: R1t, R2t below)
 __global__ void k_ens_ramp_begin(int R, StepCtl *__restrict__ ctl, const int32_t *__restrict__ kind, const int32_t *__restrict__ l_off,
                                  const double *__restrict__ times, const double *__restrict__ values, int32_t *__restrict__ moved) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -240,6 +240,34 @@ __global__ __launch_bounds__(BLOCK) void k_ens_ramp_links(int64_t m, int64_t m_p
     const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x, o2 = 2 * (int64_t)r * m_pad;
     const int changed = e < m ? ramp_link_body(e, m, c->link_scale, 1.0 / c->runner_dt, base + o2, A + o2, Aprev + o2, dx, dy, inv_len,
                                                dadt + (int64_t)r * m_pad)
+                              : 0;
+    const int any = __syncthreads_or(changed);
+    if (threadIdx.x == 0 && any) atomicOr(moved + r, 1);
+}
+
+// R1t, R2t: the same two for the replicas whose field is a sum of terms (kind[r] == LINK_TERMS; k_ra_terms_begin,
+// k_terms_links), queued BEHIND R1 and R2: R1 has left such a replica with ramp_do = 0, so R2 passes it by, and these two
+// pass by every other replica.  term: FIELD_TERMS_MAX descriptors per replica whose table nodes are offsets into the pools;
+// bases[r]: the replica's A_0 and bases (slot 0, slots 1 .. K; 2 m_pad each)
+__global__ void k_ens_terms_begin(int R, StepCtl *__restrict__ ctl, const int32_t *__restrict__ kind, const FieldTerm *__restrict__ term,
+                                  const double *__restrict__ times, const double *__restrict__ values) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R || kind[r] != LINK_TERMS) return;
+    terms_begin_body(ctl + r, term + (int64_t)r * FIELD_TERMS_MAX, times, values);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_ens_terms_links(int64_t m, int64_t m_pad, const int32_t *__restrict__ kind,
+                                                           const double *const *__restrict__ bases, double *__restrict__ A,
+                                                           double *__restrict__ Aprev, const double *__restrict__ dx,
+                                                           const double *__restrict__ dy, const double *__restrict__ inv_len,
+                                                           double *__restrict__ dadt, int32_t *__restrict__ moved,
+                                                           const StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    const StepCtl *c = ctl + r;
+    if (kind[r] != LINK_TERMS || !c->ramp_do) return;
+    const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x, o2 = 2 * (int64_t)r * m_pad;
+    const int changed = e < m ? terms_link_body(e, m, term_scales_of(c), reinterpret_cast<const double2 *>(bases[r]), m_pad, A + o2,
+                                                Aprev + o2, dx, dy, inv_len, dadt + (int64_t)r * m_pad)
                               : 0;
     const int any = __syncthreads_or(changed);
     if (threadIdx.x == 0 && any) atomicOr(moved + r, 1);
@@ -334,6 +362,7 @@ __global__ __launch_bounds__(BLOCK) void k_ens_eps_table(int64_t n_pad, const do
 struct EnsReplica {
     LoopState loop;  // controller, loop, retry and ramp state: the host's mirror of the replica's StepCtl
     bool have_ctl = false, have_links = false, have_eps = false, have_state = false, lap_valid = false;
+    DevBuf<double> tbase;  // a sum of field terms: the replica's own A_0 and bases, (K + 1) slots of 2 m_pad (tdgl_ensemble_set_link_terms)
     // tabulated terminal currents / separable epsilon (empty: none)
     std::vector<double> mu_t, mu_dens, eps_t, eps_f;
     std::vector<int32_t> mu_group;  // [nb]: table row of each boundary position, -1 where no table applies
@@ -353,8 +382,12 @@ struct tdgl_ensemble {
     // (m_pad), the boundary term before dA/dt (n_pad), mu_boundary (nb), epsilon0 (n_pad); the tables as pools
     DevBuf<double> Abase, A, Aprev, dadt, cvec, mu_b, eps0;
     DevBuf<double> tab_mu_t, tab_mu_dens, tab_eps_t, tab_eps_f, tab_link_t, tab_link_v;
-    DevBuf<int32_t> tab_mu_toff, tab_mu_group, tab_eps_off, tab_link_off, ramping, moved;  // ramping: LINK_NONE / _RAMP / _TABLE of this batch
+    DevBuf<int32_t> tab_mu_toff, tab_mu_group, tab_eps_off, tab_link_off, ramping, moved;  // ramping: LINK_NONE / _RAMP / _TABLE / _TERMS of this batch
     DevBuf<int64_t> tab_mu_doff;
+    // sums of field terms: per replica FIELD_TERMS_MAX descriptors, the pools of their tables' nodes, the replicas' bases
+    DevBuf<FieldTerm> term_desc;
+    DevBuf<double> tab_term_t, tab_term_v;
+    DevBuf<const double *> term_bases;
     bool tables_dirty = true, any_mu_table = false, any_eps_table = false;  // (dirty: the pools and their offsets exist from the first run on)
     std::vector<int32_t> h_ramping;
     std::vector<StepCtl> h_ctl;
@@ -539,9 +572,26 @@ extern "C" int tdgl_ensemble_set_link_exponents(tdgl_ensemble *e, int32_t r, con
     TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
     e->rep[r].have_links = true;
     e->rep[r].lap_valid = false;
-    if (e->rep[r].loop.tabulated()) e->tables_dirty = true;
+    if (e->rep[r].loop.tabulated() || e->rep[r].loop.terms()) e->tables_dirty = true;
     e->rep[r].loop.links_static();
     e->rep[r].loop.has_dadt = false;
+    return TDGL_OK;
+}
+
+// the arrays every replica with moving links has a share of (allocated when the first replica asks)
+static int ens_alloc_moving(tdgl_ensemble *e) {
+    if (e->Abase.n != 0) return TDGL_OK;
+    tdgl_ctx *ctx = e->ctx;
+    const size_t R = (size_t)e->R;
+    DevBuf<double> base, a, prev, dadt;
+    HIP_TRY(ctx, base.alloc(R * 2 * e->m_pad));
+    HIP_TRY(ctx, a.alloc(R * 2 * e->m_pad));
+    HIP_TRY(ctx, prev.alloc(R * 2 * e->m_pad));
+    HIP_TRY(ctx, dadt.alloc(R * e->m_pad));
+    e->Abase.take(base);
+    e->A.take(a);
+    e->Aprev.take(prev);
+    e->dadt.take(dadt);
     return TDGL_OK;
 }
 
@@ -551,20 +601,9 @@ extern "C" int tdgl_ensemble_set_link_exponents(tdgl_ensemble *e, int32_t r, con
 static int ens_set_link_base(tdgl_ensemble *e, int32_t r, const double *A_base, double scale) {
     tdgl_ctx *ctx = e->ctx;
     EnsReplica &p = e->rep[r];
-    const size_t R = (size_t)e->R;
-    if (e->Abase.n == 0) {
-        DevBuf<double> base, a, prev, dadt;
-        HIP_TRY(ctx, base.alloc(R * 2 * e->m_pad));
-        HIP_TRY(ctx, a.alloc(R * 2 * e->m_pad));
-        HIP_TRY(ctx, prev.alloc(R * 2 * e->m_pad));
-        HIP_TRY(ctx, dadt.alloc(R * e->m_pad));
-        e->Abase.take(base);
-        e->A.take(a);
-        e->Aprev.take(prev);
-        e->dadt.take(dadt);
-    }
+    TDGL_TRY(ens_alloc_moving(e));
     p.have_links = false;  // (until the replica's arrays are complete)
-    if (p.loop.tabulated()) e->tables_dirty = true;
+    if (p.loop.tabulated() || p.loop.terms()) e->tables_dirty = true;
     p.loop.links_static();
     TDGL_TRY(tdgl_set_link_exponents_base(ctx, A_base, scale));  // (A = scale A_base, A_prev = A, links, Laplacian values)
     const int64_t o2 = 2 * (int64_t)r * e->m_pad;
@@ -609,6 +648,51 @@ extern "C" int tdgl_ensemble_set_link_table(tdgl_ensemble *e, int32_t r, const d
     e->rep[r].loop.set_table(times, values, n_nodes);
     e->rep[r].have_links = true;
     e->tables_dirty = true;
+    return TDGL_OK;
+}
+
+// A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K for replica r (tdgl_set_link_terms of the context, whose arguments and rules
+// these are), with the failure rules of tdgl_ensemble_set_link_table: a refused argument leaves the replica as it was, a
+// failure behind that leaves it without links.  The replica keeps its own copy of A_0 and the bases.
+extern "C" int tdgl_ensemble_set_link_terms(tdgl_ensemble *e, int32_t r, const double *A0, int32_t n_terms, const double *bases,
+                                            const int32_t *kind, const double *ramp, const int32_t *tab_off, const double *tab_times,
+                                            const double *tab_values) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    TDGL_TRY(check_link_terms(ctx, "tdgl_ensemble_set_link_terms", n_terms, bases, kind, ramp, tab_off, tab_times, tab_values));
+    EnsReplica &p = e->rep[r];
+    TDGL_TRY(ens_alloc_moving(e));
+    const int64_t slots = (int64_t)(n_terms + 1) * 2 * e->m_pad;
+    DevBuf<double> tb;
+    HIP_TRY(ctx, tb.alloc((size_t)slots));
+    p.have_links = false;  // (until the replica's arrays are complete)
+    p.loop.links_static();
+    e->tables_dirty = true;
+    // (A = A_prev = A(0), the links and the Laplacian values, in the context's buffers)
+    TDGL_TRY(tdgl_set_link_terms(ctx, A0, n_terms, bases, kind, ramp, tab_off, tab_times, tab_values));
+    const int64_t o2 = 2 * (int64_t)r * e->m_pad;
+    TDGL_TRY(ens_copy(ctx, tb.p, ctx->e_Tbase.p, slots));
+    TDGL_TRY(ens_copy(ctx, e->A.p + o2, ctx->e_A.p, 2 * e->m_pad));
+    TDGL_TRY(ens_copy(ctx, e->Aprev.p + o2, ctx->e_Aprev.p, 2 * e->m_pad));
+    HIP_TRY(ctx, hipMemset(e->dadt.p + r * e->m_pad, 0, e->m_pad * sizeof(double)));
+    TDGL_TRY(ens_copy(ctx, e->U.p + r * e->m_pad, ctx->e_U.p, e->m_pad));
+    TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
+    p.tbase.take(tb);
+    p.loop.copy_terms(ctx->loop);
+    p.loop.has_dadt = false;
+    p.lap_valid = false;
+    p.have_links = true;
+    // (the context's own links are the ensemble's scratch: they do not stay a moving field of their own)
+    ctx->loop.links_static();
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_get_link_term_scales(tdgl_ensemble *e, int32_t r, int32_t *n_terms, double *scales) {
+    TDGL_TRY(ens_check(e, r));
+    if (!n_terms || !scales) TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_link_term_scales: null output");
+    const LoopState &L = e->rep[r].loop;
+    *n_terms = L.terms() ? L.n_terms : 0;
+    for (int k = 0; k < *n_terms; ++k) scales[k] = L.term_scale[k];
     return TDGL_OK;
 }
 
@@ -688,6 +772,26 @@ static int ens_upload_tables(tdgl_ensemble *e) {
         e->any_mu_table |= !p.mu_t.empty();
         e->any_eps_table |= !p.eps_t.empty();
     }
+    std::vector<FieldTerm> desc((size_t)R * FIELD_TERMS_MAX, FieldTerm{});
+    std::vector<const double *> bases((size_t)R, nullptr);
+    std::vector<double> kt, kv;
+    for (int r = 0; r < R; ++r) {
+        const EnsReplica &p = e->rep[r];
+        if (!p.loop.terms()) continue;
+        bases[r] = p.tbase.p;
+        for (int k = 0; k < p.loop.n_terms; ++k) {
+            FieldTerm d = p.loop.term[k];
+            d.off = (int32_t)kt.size();  // (its nodes in the ensemble's pools)
+            kt.insert(kt.end(), p.loop.term_t[k].begin(), p.loop.term_t[k].end());
+            kv.insert(kv.end(), p.loop.term_v[k].begin(), p.loop.term_v[k].end());
+            desc[(size_t)r * FIELD_TERMS_MAX + k] = d;
+        }
+    }
+    if (kt.empty()) kt.push_back(0.0), kv.push_back(0.0);
+    HIP_TRY(ctx, e->term_desc.upload(desc));
+    HIP_TRY(ctx, e->term_bases.upload(bases));
+    HIP_TRY(ctx, e->tab_term_t.upload(kt));
+    HIP_TRY(ctx, e->tab_term_v.upload(kv));
     if (mt.empty()) mt.push_back(0.0), md.push_back(0.0);  // (never read: every replica's node count is 0)
     if (et.empty()) et.push_back(0.0), ef.push_back(0.0);
     if (lt.empty()) lt.push_back(0.0), lv.push_back(0.0);
@@ -810,7 +914,7 @@ static void ens_launch_laplacian_cache(tdgl_ensemble *e, int r) {
 }
 
 // the time-dependent inputs of the round's attempts (T1, T2, R1 - R5), in the single run's order (run.inc: run_ahead)
-static void ens_queue_drives(tdgl_ensemble *e, bool ramping) {
+static void ens_queue_drives(tdgl_ensemble *e, bool ramping, bool terms) {
     tdgl_ctx *ctx = e->ctx;
     const unsigned R = (unsigned)e->R;
     if (e->any_mu_table)
@@ -831,6 +935,14 @@ static void ens_queue_drives(tdgl_ensemble *e, bool ramping) {
     hipLaunchKernelGGL(k_ens_ramp_links, dim3(nblk, R), dim3(BLOCK), 0, ctx->stream, ctx->m, e->m_pad, (const double *)e->Abase.p, e->A.p,
                        e->Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
                        e->dadt.p, e->moved.p, (const StepCtl *)e->d_ctl.p);
+    if (terms) {
+        hipLaunchKernelGGL(k_ens_terms_begin, dim3((R + 63) / 64), dim3(64), 0, ctx->stream, (int)R, e->d_ctl.p, (const int32_t *)e->ramping.p,
+                           (const FieldTerm *)e->term_desc.p, (const double *)e->tab_term_t.p, (const double *)e->tab_term_v.p);
+        hipLaunchKernelGGL(k_ens_terms_links, dim3(nblk, R), dim3(BLOCK), 0, ctx->stream, ctx->m, e->m_pad, (const int32_t *)e->ramping.p,
+                           (const double *const *)e->term_bases.p, e->A.p, e->Aprev.p, (const double *)ctx->e_dirx.p,
+                           (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p, e->dadt.p, e->moved.p,
+                           (const StepCtl *)e->d_ctl.p);
+    }
     const int nblk_ceff = grid_for((int64_t)pat.n_slices * WAVE);
     hipLaunchKernelGGL(k_ens_ceff_links, dim3(nblk_ceff + nblk, R), dim3(BLOCK), 0, ctx->stream, nblk_ceff, pat.n_slices, pat.n_rows,
                        (const int32_t *)pat.slice_off.p, (const int32_t *)ctx->lap_slot_edge.p, (const double *)ctx->lap_slot_w.p,
@@ -895,10 +1007,10 @@ static void ens_queue_sub_solve(tdgl_ensemble *e) {
                        (const int32_t *)e->fail_part.p, ctx->psi_blocks, e->d_ctl.p, e->d_rec.p, (const int32_t *)e->limit.p);
 }
 
-static void ens_queue_round(tdgl_ensemble *e, bool ramping) {
+static void ens_queue_round(tdgl_ensemble *e, bool ramping, bool terms) {
     tdgl_ctx *ctx = e->ctx;
     const unsigned R = (unsigned)e->R;
-    ens_queue_drives(e, ramping);
+    ens_queue_drives(e, ramping, terms);
     hipLaunchKernelGGL(k_ens_psi_update, dim3(ctx->psi_blocks, R), dim3(BLOCK), 0, ctx->stream, ctx->n_own, e->n_pad, e->psi0.p, e->psi1.p,
                        (const double2 *)e->lap0.p, (const double2 *)e->lap1.p, (const double *)e->mu.p, (const double *)e->eps.p, ctx->u,
                        ctx->gamma, e->dmax_part.p, e->fail_part.p, e->d_ctl.p);
@@ -967,7 +1079,7 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
     int err_replica = -1;
     double err_dt = 0.0;
     for (;;) {
-        int active = 0, n_ramping = 0;
+        int active = 0, n_ramping = 0, n_terms = 0;
         for (int r = 0; r < R; ++r) {
             EnsReplica &p = e->rep[r];
             const bool on = !reached_end[r] && steps_done[r] < max_steps[r];
@@ -975,8 +1087,9 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
             // a ramp that has reached its end: dA/dt is identically zero from here on, and a replica whose ramp has
             // settled costs what a static one does (as in tdgl_run)
             if (p.loop.ramp_settled()) p.loop.has_dadt = false;
-            e->h_ramping[r] = !(on && p.loop.ramping()) ? LINK_NONE : p.loop.tabulated() ? LINK_TABLE : LINK_RAMP;
+            e->h_ramping[r] = !(on && p.loop.ramping()) ? LINK_NONE : p.loop.terms() ? LINK_TERMS : p.loop.tabulated() ? LINK_TABLE : LINK_RAMP;
             n_ramping += e->h_ramping[r] != LINK_NONE;
+            n_terms += e->h_ramping[r] == LINK_TERMS;
             p.loop.fill(e->h_ctl[r], end_time[r], on);
             e->h_limit[r] = on ? (int32_t)std::min<int64_t>(max_steps[r] - steps_done[r], RA_BATCH_MAX) : 0;
         }
@@ -986,7 +1099,7 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
         HIP_TRY(ctx, hipMemcpyAsync(e->limit.p, e->h_limit.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         if (n_ramping > 0)
             HIP_TRY(ctx, hipMemcpyAsync(e->ramping.p, e->h_ramping.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        for (int s = 0; s < batch; ++s) ens_queue_round(e, n_ramping > 0);
+        for (int s = 0; s < batch; ++s) ens_queue_round(e, n_ramping > 0, n_terms > 0);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(e->h_ctl.data(), e->d_ctl.p, (size_t)R * sizeof(StepCtl), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(e->h_rec.data(), e->d_rec.p, (size_t)R * RA_BATCH_MAX * sizeof(StepRec), hipMemcpyDeviceToHost, ctx->stream));

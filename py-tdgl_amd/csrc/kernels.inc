@@ -642,6 +642,118 @@ __global__ void k_ra_table_begin(StepCtl *__restrict__ ctl, const double *__rest
     table_begin_body(ctl, times, values, n_nodes);
 }
 
+// ---- a sum of field terms A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K (tdgl_set_link_terms) ----------------------------
+// The single product's step rule, term by term: the K factors are evaluated at the controller's time with the evaluators
+// above (linear_ramp_value, table_value_dev); nothing moves only when EVERY factor equals its last two evaluations and a
+// dynamic update has run.  `term`: the K = ctl->n_terms descriptors of THIS controller; a table term's nodes are
+// times[off .. off + n), values[off .. off + n).  Leaves has_dadt and ramp_do as ramp_begin_body leaves them.
+// (body: one thread per controller)
+__device__ __forceinline__ void terms_begin_body(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term,
+                                                 const double *__restrict__ times, const double *__restrict__ values) {
+#pragma clang fp contract(off)
+    int go = 0;
+    if (!ctl->poisoned && ctl->retries == 0) {
+        const int K = ctl->n_terms;
+        const double t = ctl->time;
+        double s[FIELD_TERMS_MAX];
+        bool same = ctl->has_dadt != 0;
+#pragma unroll
+        for (int k = 0; k < FIELD_TERMS_MAX; ++k) {
+            s[k] = 0.0;
+            if (k >= K) continue;
+            const FieldTerm d = term[k];
+            s[k] = d.kind == TERM_TABLE ? table_value_dev(times + d.off, values + d.off, d.n, t)
+                                        : linear_ramp_value(t, d.ramp[0], d.ramp[1], d.ramp[2], d.ramp[3]);
+            same = same && s[k] == ctl->term_scale[k] && s[k] == ctl->term_scale_prev[k];
+        }
+        if (!same) {
+#pragma unroll
+            for (int k = 0; k < FIELD_TERMS_MAX; ++k)
+                if (k < K) {
+                    ctl->term_scale_prev[k] = ctl->term_scale[k];
+                    ctl->term_scale[k] = s[k];
+                }
+            ctl->has_dadt = 1;
+            ctl->n_term_moves += 1;
+            go = 1;
+        }
+    }
+    ctl->ramp_do = go;
+}
+
+__global__ void k_ra_terms_begin(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term, const double *__restrict__ times,
+                                 const double *__restrict__ values) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    terms_begin_body(ctl, term, times, values);
+}
+
+// the factors of a sum and what goes with them, by value: the loop with one synchronisation per step evaluates the factors
+// on the host (tdgl_update_link_terms) and hands them to the kernel the run-ahead loop feeds from its controller
+struct TermScales {
+    double s[FIELD_TERMS_MAX];
+    double inv_dt;
+    int n_terms, a0;
+};
+
+// A = ((A_0 + s_1 A_1) + s_2 A_2) + ... per edge and component, terms added in term order, every product rounded before
+// it is added (no contraction: the pragma, and ramp_link_body's empty asm between a product and the sum that takes it);
+// without A_0 the sum starts from the first product.  Then dA/dt, A_prev <- A and "did it move" as for the single product
+// (dadt_body).  `bases`: slot 0 A_0, slot k the k-th base, `stride` double2 apart; a pure stream, 16 bytes per lane and
+// array: (K + 1) 16 read, 16 written for A, and dadt_body's 16 + 24 read, 16 + 8 written.
+__device__ __forceinline__ int terms_link_body(int64_t e, int64_t m, const TermScales &ts, const double2 *__restrict__ bases, int64_t stride,
+                                               double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
+                                               const double *__restrict__ dy, const double *__restrict__ inv_len,
+                                               double *__restrict__ dadt) {
+#pragma clang fp contract(off)
+    const double2 b1 = bases[stride + e];
+    double ax = ts.s[0] * b1.x, ay = ts.s[0] * b1.y;
+    asm volatile("" : "+v"(ax), "+v"(ay));
+    if (ts.a0) {
+        const double2 a0 = bases[e];
+        ax = a0.x + ax;
+        ay = a0.y + ay;
+    }
+#pragma unroll
+    for (int k = 1; k < FIELD_TERMS_MAX; ++k) {
+        if (k >= ts.n_terms) break;
+        const double2 b = bases[(k + 1) * stride + e];
+        double px = ts.s[k] * b.x, py = ts.s[k] * b.y;
+        asm volatile("" : "+v"(px), "+v"(py));
+        ax = ax + px;
+        ay = ay + py;
+    }
+    asm volatile("" : "+v"(ax), "+v"(ay));
+    reinterpret_cast<double2 *>(A)[e] = make_double2(ax, ay);
+    return dadt_body(e, m, ts.inv_dt, ax, ay, Aprev, dx, dy, inv_len, dadt);
+}
+
+// the factors of this attempt from its controller
+__device__ __forceinline__ TermScales term_scales_of(const StepCtl *__restrict__ c) {
+    TermScales ts;
+#pragma unroll
+    for (int k = 0; k < FIELD_TERMS_MAX; ++k) ts.s[k] = c->term_scale[k];
+    ts.inv_dt = 1.0 / c->runner_dt;
+    ts.n_terms = c->n_terms;
+    ts.a0 = c->term_a0;
+    return ts;
+}
+
+// ... per workgroup: "did it move" (k_ra_ramp_links).  ctl: the run-ahead loop's controller, which says whether the
+// attempt moves anything and with which factors; nullptr: the host has decided, the factors are `host`'s
+__global__ __launch_bounds__(BLOCK) void k_terms_links(int64_t m, int64_t m_pad, TermScales host, const double *__restrict__ bases,
+                                                       double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
+                                                       const double *__restrict__ dy, const double *__restrict__ inv_len,
+                                                       double *__restrict__ dadt, int32_t *__restrict__ block_changed,
+                                                       const StepCtl *__restrict__ ctl) {
+    if (ctl && !ctl->ramp_do) return;
+    const TermScales ts = ctl ? term_scales_of(ctl) : host;
+    const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+    const int changed =
+        e < m ? terms_link_body(e, m, ts, reinterpret_cast<const double2 *>(bases), m_pad, A, Aprev, dx, dy, inv_len, dadt) : 0;
+    const int any = __syncthreads_or(changed);
+    if (threadIdx.x == 0) block_changed[blockIdx.x] = any;
+}
+
 // Run-ahead loop with tabulated terminal currents (update_mu_boundary, solver.py:325-345, at the time of the step
 // about to be attempted -- which only the device knows): ONE workgroup evaluates the piecewise-linear tables at
 // ctl->time, rewrites mu_boundary at the tabulated positions, and rebuilds c = mu_boundary_laplacian @ mu_boundary

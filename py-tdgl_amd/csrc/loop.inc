@@ -108,6 +108,52 @@ bool LoopState::advance(double dt, double end_time) {
     return false;
 }
 
+// A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K in the place of ramp and table (tdgl_set_link_terms has validated the arguments)
+void LoopState::set_terms(int n, bool a0, const int32_t *kind, const double *ramp, const int32_t *tab_off, const double *times,
+                          const double *values) {
+    links_static();
+    ramp_on = true, n_terms = n, term_a0 = a0, term_moves = 0;
+    int32_t off = 0;
+    for (int k = 0; k < FIELD_TERMS_MAX; ++k) {
+        term[k] = FieldTerm{};
+        term_t[k].clear(), term_v[k].clear();
+        if (k >= n) continue;
+        term[k].kind = kind[k];
+        if (kind[k] == TERM_TABLE) {
+            term_t[k].assign(times + tab_off[k], times + tab_off[k + 1]);
+            term_v[k].assign(values + tab_off[k], values + tab_off[k + 1]);
+            term[k].off = off, term[k].n = (int32_t)term_t[k].size();
+            off += term[k].n;
+        } else {
+            for (int j = 0; j < 4; ++j) term[k].ramp[j] = ramp[4 * k + j];
+        }
+        term_scale[k] = term_scale_prev[k] = term_value(k, 0.0);
+    }
+}
+
+void LoopState::copy_terms(const LoopState &o) {
+    links_static();
+    ramp_on = o.ramp_on, n_terms = o.n_terms, term_a0 = o.term_a0, term_moves = o.term_moves;
+    for (int k = 0; k < FIELD_TERMS_MAX; ++k) {
+        term[k] = o.term[k], term_t[k] = o.term_t[k], term_v[k] = o.term_v[k];
+        term_scale[k] = o.term_scale[k], term_scale_prev[k] = o.term_scale_prev[k];
+    }
+}
+
+double LoopState::term_value(int k, double t) const {
+    if (term[k].kind == TERM_TABLE) return table_value(term_t[k], term_v[k].data(), t);
+    return linear_ramp_value(t, term[k].ramp[0], term[k].ramp[1], term[k].ramp[2], term[k].ramp[3]);
+}
+
+bool LoopState::terms_step(const double *s) {
+    bool same = has_dadt;
+    for (int k = 0; k < n_terms; ++k) same = same && s[k] == term_scale[k] && s[k] == term_scale_prev[k];
+    if (same) return false;
+    for (int k = 0; k < n_terms; ++k) term_scale_prev[k] = term_scale[k], term_scale[k] = s[k];
+    term_moves += 1;
+    return true;
+}
+
 // the device's controller at the start of a batch; live = false: poisoned from the first attempt on
 void LoopState::fill(StepCtl &h, double end_time, bool live) const {
     memset(&h, 0, sizeof(h));
@@ -129,6 +175,8 @@ void LoopState::fill(StepCtl &h, double end_time, bool live) const {
     h.ramp_tmin = ramp_tmin, h.ramp_tmax = ramp_tmax, h.ramp_initial = ramp_initial, h.ramp_final = ramp_final;
     h.link_scale = link_scale, h.link_scale_prev = link_scale_prev;
     h.has_dadt = has_dadt ? 1 : 0;
+    h.n_terms = terms() ? n_terms : 0, h.term_a0 = term_a0 ? 1 : 0;
+    for (int k = 0; k < h.n_terms; ++k) h.term_scale[k] = term_scale[k], h.term_scale_prev[k] = term_scale_prev[k];
     if (ctl.adaptive) {
         const int64_t have = (int64_t)hist.size(), cnt = std::min<int64_t>(have, ctl.adaptive_window);
         h.hist_count = (int)cnt;
@@ -165,6 +213,8 @@ LoopState::Batch LoopState::absorb(const StepCtl &h, const StepRec *rec, int bat
         link_scale = h.link_scale;
         link_scale_prev = h.link_scale_prev;
         has_dadt = h.has_dadt != 0;
+        for (int k = 0; k < n_terms; ++k) term_scale[k] = h.term_scale[k], term_scale_prev[k] = h.term_scale_prev[k];
+        term_moves += h.n_term_moves;
     }
     cur = h.cur;
     retries = b.error ? 0 : h.retries;

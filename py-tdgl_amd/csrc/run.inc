@@ -408,8 +408,8 @@ static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out) {
 static bool run_ahead_ok(const tdgl_ctx *ctx) {
     const bool off = ctx->run_ahead_disabled;  // (TDGL_NO_RUN_AHEAD at tdgl_create)
     const tdgl_controller &ctl = ctx->loop.ctl;
-    // (a moving vector potential: only the ramp or table the loop evaluates itself rides along -- k_ra_ramp_begin,
-    // k_ra_table_begin --, and it needs the previous step's dt: from the second step of a stage on)
+    // (a moving vector potential: only the ramp, table or sum of terms the loop evaluates itself rides along -- k_ra_ramp_begin,
+    // k_ra_table_begin, k_ra_terms_begin --, and it needs the previous step's dt: from the second step of a stage on)
     if (ctx->loop.ramping() ? !(ctx->loop.runner_dt > 0.0) : ctx->loop.has_dadt) return false;
     // (the plans of the direct solve: no screening, currents every step)
     return !off && dense_on(ctx) && (ctx->direct->dense.tiles > 0) && currents_plan_runs_ahead(step_plan(ctx)) &&
@@ -470,17 +470,28 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
                                    (const int32_t *)ctx->e1.p, (const double *)ctx->e_inv_len.p, (const double2 *)ctx->e_U.p,
                                    (const double2 *)ctx->psi[0].p, (const double2 *)ctx->psi[1].p, (const double *)ctx->mu.p, ctx->js.p, ctx->jn.p,
                                    (const double *)ctx->e_dAdt.p, (const StepCtl *)dc);
-            if (ctx->loop.tabulated()) {
-                const int nn = (int)ctx->loop.tab_t.size();
-                hipLaunchKernelGGL(k_ra_table_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const double *)ctx->d_tab_link.p,
-                                   (const double *)ctx->d_tab_link.p + nn, nn);
-            } else {
-                hipLaunchKernelGGL(k_ra_ramp_begin, dim3(1), dim3(64), 0, ctx->stream, dc);
-            }
             const int nblk = grid_for(ctx->m);
-            hipLaunchKernelGGL(k_ra_ramp_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, (const double *)ctx->e_Abase.p, ctx->e_A.p,
-                               ctx->e_Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
-                               ctx->e_dAdt.p, ctx->link_block_changed.p, (const StepCtl *)dc);
+            if (ctx->loop.terms()) {
+                // a sum of terms: its own begin and links kernels in the place of the single product's pair
+                const double *tab = ctx->d_term_tab.p;
+                hipLaunchKernelGGL(k_ra_terms_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const FieldTerm *)ctx->d_terms.p, tab,
+                                   tab + ctx->d_term_tab.n / 2);
+                hipLaunchKernelGGL(k_terms_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, TermScales{},
+                                   (const double *)ctx->e_Tbase.p, ctx->e_A.p, ctx->e_Aprev.p, (const double *)ctx->e_dirx.p,
+                                   (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p, ctx->e_dAdt.p,
+                                   ctx->link_block_changed.p, (const StepCtl *)dc);
+            } else {
+                if (ctx->loop.tabulated()) {
+                    const int nn = (int)ctx->loop.tab_t.size();
+                    hipLaunchKernelGGL(k_ra_table_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const double *)ctx->d_tab_link.p,
+                                       (const double *)ctx->d_tab_link.p + nn, nn);
+                } else {
+                    hipLaunchKernelGGL(k_ra_ramp_begin, dim3(1), dim3(64), 0, ctx->stream, dc);
+                }
+                hipLaunchKernelGGL(k_ra_ramp_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, (const double *)ctx->e_Abase.p, ctx->e_A.p,
+                                   ctx->e_Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
+                                   ctx->e_dAdt.p, ctx->link_block_changed.p, (const StepCtl *)dc);
+            }
             hipLaunchKernelGGL(k_any_flag, dim3(1), dim3(BLOCK), 0, ctx->stream, nblk, (const int32_t *)ctx->link_block_changed.p,
                                ctx->link_changed.p, go);
             hipLaunchKernelGGL(k_ceff, dim3(grid_for((int64_t)ctx->lap_pat.n_slices * WAVE)), dim3(BLOCK), 0, ctx->stream,
@@ -618,11 +629,17 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
             // update_applied_vector_potential (solver.py:347-362, 626-642) for
             // A(t) = ramp(t) * A_base, ramp = tdgl/sources/scaling.py LinearRamp; dA/dt uses the
             // previous step's dt (Runner.dt)
-            // (or a table in the ramp's place: tdgl_set_link_table)
-            const double scale = ctx->loop.tabulated()
-                                     ? table_value(ctx->loop.tab_t, ctx->loop.tab_v.data(), ctx->loop.time)
-                                     : linear_ramp_value(ctx->loop.time, ctx->loop.ramp_tmin, ctx->loop.ramp_tmax, ctx->loop.ramp_initial, ctx->loop.ramp_final);
-            status = update_link_scale(ctx, scale, ctx->loop.runner_dt);
+            // (or a table in the ramp's place: tdgl_set_link_table; or a sum of such terms: tdgl_set_link_terms)
+            if (ctx->loop.terms()) {
+                double s[FIELD_TERMS_MAX] = {0.0, 0.0, 0.0, 0.0};
+                for (int j = 0; j < ctx->loop.n_terms; ++j) s[j] = ctx->loop.term_value(j, ctx->loop.time);
+                status = update_link_terms(ctx, s, ctx->loop.runner_dt);
+            } else {
+                const double scale = ctx->loop.tabulated()
+                                         ? table_value(ctx->loop.tab_t, ctx->loop.tab_v.data(), ctx->loop.time)
+                                         : linear_ramp_value(ctx->loop.time, ctx->loop.ramp_tmin, ctx->loop.ramp_tmax, ctx->loop.ramp_initial, ctx->loop.ramp_final);
+                status = update_link_scale(ctx, scale, ctx->loop.runner_dt);
+            }
         }
         if (status == TDGL_OK) status = apply_time_tables(ctx);  // tabulated terminal currents / epsilon factor at this time
         if (status == TDGL_OK)

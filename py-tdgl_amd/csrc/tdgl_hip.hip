@@ -612,6 +612,7 @@ static void refresh_ceff(tdgl_ctx *ctx) {
 }
 
 static int update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev);  // below
+static int update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev);  // below
 static int apply_time_tables(tdgl_ctx *ctx);                                 // below
 static double table_value(const std::vector<double> &t, const double *v, double time);  // below
 static int check_link_table(tdgl_ctx *ctx, const char *who, int32_t n_nodes, const double *times, const double *values);  // below
@@ -648,7 +649,8 @@ extern "C" int tdgl_update_link_exponents(tdgl_ctx *ctx, const double *A_new, do
 
 // everything that follows new values in ctx->e_A: dA/dt (dynamic) or A_prev <- A (static), the
 // rhs term of dA/dt, link variables, covariant-Laplacian values
-static int finish_links(tdgl_ctx *ctx, bool dynamic, double dt_prev) {
+// (dadt_done: the caller's own kernel has formed dA/dt, A_prev and the per-workgroup flags already -- k_terms_links)
+static int finish_links(tdgl_ctx *ctx, bool dynamic, double dt_prev, bool dadt_done = false) {
     const size_t bytes = 2 * ctx->m_pad * sizeof(double);
     const int32_t *only_if = nullptr;
     if (dynamic) {
@@ -657,9 +659,10 @@ static int finish_links(tdgl_ctx *ctx, bool dynamic, double dt_prev) {
             HIP_TRY(ctx, ctx->link_block_changed.alloc(nblk));
             HIP_TRY(ctx, ctx->link_changed.alloc(1));
         }
-        hipLaunchKernelGGL(k_dadt, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, 1.0 / dt_prev,
-                           ctx->e_A.p, ctx->e_Aprev.p, ctx->e_dirx.p, ctx->e_diry.p, ctx->e_inv_len.p, ctx->e_dAdt.p,
-                           ctx->link_block_changed.p);
+        if (!dadt_done)
+            hipLaunchKernelGGL(k_dadt, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, 1.0 / dt_prev,
+                               ctx->e_A.p, ctx->e_Aprev.p, ctx->e_dirx.p, ctx->e_diry.p, ctx->e_inv_len.p, ctx->e_dAdt.p,
+                               ctx->link_block_changed.p);
         hipLaunchKernelGGL(k_any_flag, dim3(1), dim3(BLOCK), 0, ctx->stream, nblk, ctx->link_block_changed.p,
                            ctx->link_changed.p);
         // (with screening the links are rebuilt from A_applied + A_induced in every screening
@@ -764,6 +767,112 @@ extern "C" int tdgl_set_link_table(tdgl_ctx *ctx, int32_t n_nodes, const double 
     both.insert(both.end(), values, values + n_nodes);
     HIP_TRY(ctx, ctx->d_tab_link.upload(both));
     ctx->loop.set_table(times, values, n_nodes);
+    return TDGL_OK;
+}
+
+// ---- A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K without leaving the device ------------------------------------------
+static int launch_terms_links(tdgl_ctx *ctx, const double *scales, double inv_dt) {
+    const int nblk = grid_for(ctx->m);
+    if (ctx->link_block_changed.n == 0) {
+        HIP_TRY(ctx, ctx->link_block_changed.alloc(nblk));
+        HIP_TRY(ctx, ctx->link_changed.alloc(1));
+    }
+    TermScales ts{};
+    for (int k = 0; k < ctx->loop.n_terms; ++k) ts.s[k] = scales[k];
+    ts.inv_dt = inv_dt, ts.n_terms = ctx->loop.n_terms, ts.a0 = ctx->loop.term_a0 ? 1 : 0;
+    hipLaunchKernelGGL(k_terms_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, ts, (const double *)ctx->e_Tbase.p,
+                       ctx->e_A.p, ctx->e_Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p,
+                       (const double *)ctx->e_inv_len.p, ctx->e_dAdt.p, ctx->link_block_changed.p, (const StepCtl *)nullptr);
+    return TDGL_OK;
+}
+
+// what tdgl_set_link_terms and tdgl_ensemble_set_link_terms refuse: the rules of tdgl_set_link_ramp and check_link_table, term by term
+static int check_link_terms(tdgl_ctx *ctx, const char *who, int32_t n_terms, const double *bases, const int32_t *kind, const double *ramp,
+                            const int32_t *tab_off, const double *times, const double *values) {
+    if (n_terms < 1 || n_terms > FIELD_TERMS_MAX) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: n_terms must be in [1, %d]", who, FIELD_TERMS_MAX);
+    if (!bases || !kind) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: null bases or kinds", who);
+    for (int32_t k = 0; k < n_terms; ++k) {
+        if (kind[k] == TERM_RAMP) {
+            if (!ramp) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: term %d is a ramp but there are no ramp parameters", who, k);
+            const double *q = ramp + 4 * k;
+            if (!(std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2]) && std::isfinite(q[3])))
+                TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: term %d: the ramp's parameters must be finite", who, k);
+            if (!(q[1] > q[0])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: term %d: tmax must be > tmin", who, k);
+        } else if (kind[k] == TERM_TABLE) {
+            if (!tab_off || !times || !values || tab_off[k] < 0 || tab_off[k + 1] < tab_off[k])
+                TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: term %d is a table but its nodes are missing", who, k);
+            TDGL_TRY(check_link_table(ctx, who, tab_off[k + 1] - tab_off[k], times + tab_off[k], values + tab_off[k]));
+        } else {
+            TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: term %d: kind must be 1 (ramp) or 2 (table)", who, k);
+        }
+    }
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_set_link_terms(tdgl_ctx *ctx, const double *A0, int32_t n_terms, const double *bases, const int32_t *kind,
+                                   const double *ramp, const int32_t *tab_off, const double *tab_times, const double *tab_values) {
+    CTX_GUARD(ctx);
+    TDGL_TRY(check_link_terms(ctx, "tdgl_set_link_terms", n_terms, bases, kind, ramp, tab_off, tab_times, tab_values));
+    // (nothing of the state in force has been touched so far; the device's copies are complete before the loop hears of them)
+    const size_t slot = 2 * (size_t)ctx->m_pad;
+    DevBuf<double> tb;
+    HIP_TRY(ctx, tb.alloc((size_t)(n_terms + 1) * slot));
+    if (A0) TDGL_TRY(upload_edge_vectors(ctx, A0, tb.p));
+    for (int32_t k = 0; k < n_terms; ++k) TDGL_TRY(upload_edge_vectors(ctx, bases + (size_t)k * 2 * ctx->m, tb.p + (size_t)(k + 1) * slot));
+    LoopState next;
+    next.set_terms(n_terms, A0 != nullptr, kind, ramp, tab_off, tab_times, tab_values);
+    std::vector<FieldTerm> desc(next.term, next.term + n_terms);
+    std::vector<double> tt, tv;
+    for (int32_t k = 0; k < n_terms; ++k) {
+        tt.insert(tt.end(), next.term_t[k].begin(), next.term_t[k].end());
+        tv.insert(tv.end(), next.term_v[k].begin(), next.term_v[k].end());
+    }
+    if (tt.empty()) tt.push_back(0.0), tv.push_back(0.0);  // (never read: no term is a table)
+    tt.insert(tt.end(), tv.begin(), tv.end());
+    DevBuf<FieldTerm> d_desc;
+    DevBuf<double> d_tab;
+    HIP_TRY(ctx, d_desc.upload(desc));
+    HIP_TRY(ctx, d_tab.upload(tt));
+    ctx->e_Tbase.take(tb);
+    ctx->d_terms.take(d_desc);
+    ctx->d_term_tab.take(d_tab);
+    ctx->loop.copy_terms(next);
+    // A = A(0) (the links kernel against A_prev = 0 with 1 / dt = 0: dA/dt = 0), then A_prev <- A, the links, the Laplacian values
+    HIP_TRY(ctx, hipMemsetAsync(ctx->e_Aprev.p, 0, slot * sizeof(double), ctx->stream));
+    TDGL_TRY(launch_terms_links(ctx, ctx->loop.term_scale, 0.0));
+    TDGL_TRY(finish_links(ctx, false, 0.0));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TDGL_OK;
+}
+
+static int update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev) {
+    if (!ctx->loop.terms_step(scales)) return TDGL_OK;  // (A and dA/dt = 0 are already in place)
+    TDGL_TRY(launch_terms_links(ctx, scales, 1.0 / dt_prev));
+    return finish_links(ctx, true, dt_prev, true);
+}
+
+extern "C" int tdgl_update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev) {
+    CTX_GUARD(ctx);
+    if (!ctx->loop.terms()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_terms first");
+    if (!scales) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_terms: null scales");
+    for (int k = 0; k < ctx->loop.n_terms; ++k)
+        if (!std::isfinite(scales[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_terms: non-finite factor");
+    if (!(dt_prev > 0.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_terms: dt_prev must be > 0");
+    TDGL_TRY(update_link_terms(ctx, scales, dt_prev));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_get_link_term_moves(tdgl_ctx *ctx, int64_t *moves) {
+    if (!ctx || !moves) return TDGL_ERR_ARG;
+    *moves = ctx->loop.terms() ? ctx->loop.term_moves : 0;
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_get_link_term_scales(tdgl_ctx *ctx, int32_t *n_terms, double *scales) {
+    if (!ctx || !n_terms || !scales) return TDGL_ERR_ARG;
+    *n_terms = ctx->loop.terms() ? ctx->loop.n_terms : 0;
+    for (int k = 0; k < *n_terms; ++k) scales[k] = ctx->loop.term_scale[k];
     return TDGL_OK;
 }
 

@@ -202,6 +202,15 @@ constexpr int GUESS_MAX = 16;  // maximal window of the projection guess (kernel
 // classic way with a smaller dt) or behind the step that reached end_time.
 constexpr int RA_HIST_MAX = 128;   // adaptive_window up to here (numpy's pairwise sum has no recursion below 129 terms)
 constexpr int RA_BATCH_MAX = 64;
+// A sum of field terms A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K (tdgl_set_link_terms): at most this many products, and
+// where the factor of one of them comes from -- a LinearRamp (ramp: tmin, tmax, initial, final) or a table (nodes off ..
+// off + n of the owner's pools of times and values)
+constexpr int FIELD_TERMS_MAX = 4;
+enum : int32_t { TERM_RAMP = 1, TERM_TABLE = 2 };
+struct FieldTerm {
+    int32_t kind, off, n, pad;
+    double ramp[4];
+};
 struct StepCtl {
     double tentative_dt;   // dt the next STEP starts from (solver.py:316-320, 698-707)
     double attempt_dt;     // dt of the next attempt: tentative_dt, times the multiplier per failed attempt of the step
@@ -227,6 +236,11 @@ struct StepCtl {
     double link_scale, link_scale_prev;
     int has_dadt;              // a dynamic update has run (update_link_scale's early return needs one)
     int ramp_do;               // this attempt is the first of a step and the vector potential moves
+    // ... or a sum of field terms (k_ra_terms_begin; n_terms = 0: the single product above): the factors of the current /
+    // previous A, term by term; term_a0: the sum starts from a static A_0
+    int n_terms, term_a0;
+    int n_term_moves, pad2;    // attempts of this batch that moved the sum (ran the body of the links kernel)
+    double term_scale[FIELD_TERMS_MAX], term_scale_prev[FIELD_TERMS_MAX];
 };
 struct StepRec {
     double dt, dmax;
@@ -253,6 +267,15 @@ struct LoopState {
     // ... or the factor as a piecewise-linear table A(t) = table(t) A_base (tdgl_set_link_table; non-empty: the table is the
     // source of the factor and ramp_tmin .. ramp_final are unused).  The host's copy of the nodes; the device's is its owner's
     std::vector<double> tab_t, tab_v;
+    // ... or a sum A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K (tdgl_set_link_terms; n_terms = K > 0: the terms are the source
+    // of A and everything above but ramp_on and has_dadt is unused).  Every factor is a ramp (term[k].ramp) or a table
+    // (term_t[k], term_v[k]); term_scale / term_scale_prev: the factors of the current / previous A
+    int n_terms = 0;
+    bool term_a0 = false;
+    int64_t term_moves = 0;  // steps that moved the sum since it was set (tdgl_get_link_term_moves)
+    tdgl::FieldTerm term[tdgl::FIELD_TERMS_MAX] = {};
+    std::vector<double> term_t[tdgl::FIELD_TERMS_MAX], term_v[tdgl::FIELD_TERMS_MAX];
+    double term_scale[tdgl::FIELD_TERMS_MAX] = {0, 0, 0, 0}, term_scale_prev[tdgl::FIELD_TERMS_MAX] = {0, 0, 0, 0};
     // what absorb tells its caller about a batch.  corrupt: 1 impossible counts, 2 the records disagree with the controller
     // (the state is void); last_accepted: index of the last accepted record
     struct Batch {
@@ -269,13 +292,24 @@ struct LoopState {
     void new_state(int buffer) { cur = buffer, retries = 0; }  // a new psi in psi[buffer] (tdgl_set_state): no step is in progress
     void set_ramp(bool on, double tmin, double tmax, double initial, double final_) {
         ramp_on = on, ramp_tmin = tmin, ramp_tmax = tmax, ramp_initial = initial, ramp_final = final_;
-        tab_t.clear(), tab_v.clear();
+        tab_t.clear(), tab_v.clear(), n_terms = 0;
     }
     void set_table(const double *times, const double *values, int64_t n) {  // n = 0: off
-        ramp_on = n > 0, tab_t.assign(times, times + n), tab_v.assign(values, values + n);
+        ramp_on = n > 0, tab_t.assign(times, times + n), tab_v.assign(values, values + n), n_terms = 0;
     }
-    void links_static() { ramp_on = false, tab_t.clear(), tab_v.clear(); }  // (a setter of static links: neither ramp nor table)
+    void links_static() { ramp_on = false, tab_t.clear(), tab_v.clear(), n_terms = 0; }  // (a setter of static links: neither ramp, table nor terms)
     bool tabulated() const { return ramp_on && !tab_t.empty(); }
+    // the sum of terms in the place of ramp and table (validated by the caller: tdgl_set_link_terms); the factors start at
+    // their values at t = 0
+    void set_terms(int n, bool a0, const int32_t *kind, const double *ramp, const int32_t *tab_off, const double *times, const double *values);
+    void copy_terms(const LoopState &o);
+    bool terms() const { return ramp_on && n_terms > 0; }
+    double term_value(int k, double t) const;  // f_k(t): linear_ramp_value / table_value
+    double term_end_time(int k) const { return term[k].kind == tdgl::TERM_TABLE ? term_t[k].back() : term[k].ramp[1]; }
+    double term_end_value(int k) const { return term[k].kind == tdgl::TERM_TABLE ? term_v[k].back() : term[k].ramp[3]; }
+    // the step rule of the sum (update_link_scale's, term by term): false -- nothing moves, every factor equals its last two
+    // evaluations and a dynamic update has run; true -- the factors are taken over (the caller moves the links)
+    bool terms_step(const double *s);
     std::string budget_message(int replica, double dt) const;
     void report(int64_t *step, double *time_, double *runner_dt_, double *tentative) const;
     // the classic loop's step: its first attempt takes tentative_dt (solver.py:666-668); a step begun by the run-ahead loop and
@@ -289,7 +323,13 @@ struct LoopState {
     // value -- the first evaluation still sees dA/dt != 0, the second writes dA/dt = 0 (solver.py:626-642) -- the vector
     // potential is static for the rest of the stage: no dA/dt term, no per-step update, and the run-ahead loop can take over.
     // A table is constant from its last node on, at that node's value: the same rule.
+    // A sum of terms is settled once the time has passed every term's end and every factor has been seen twice at its end value.
     bool ramp_settled() const {
+        if (terms()) {
+            for (int k = 0; k < n_terms; ++k)
+                if (!(time >= term_end_time(k) && term_scale[k] == term_end_value(k) && term_scale_prev[k] == term_end_value(k))) return false;
+            return true;
+        }
         const double t_end = tabulated() ? tab_t.back() : ramp_tmax, f_end = tabulated() ? tab_v.back() : ramp_final;
         return ramp_on && time >= t_end && link_scale == f_end && link_scale_prev == f_end;
     }
@@ -559,6 +599,10 @@ struct tdgl_ctx {
     int32_t n_b_sites = 0;
     bool tab_mu_on_device = false;
     tdgl::DevBuf<double> d_tab_link;                 // the field factor's table on the device: n times, then n values (k_ra_table_begin; host copy: loop.tab_t / tab_v)
+    // a sum of field terms (tdgl_set_link_terms): A_0 (slot 0, zeros without one) and the K bases (slots 1 .. K), 2 m_pad each,
+    // edge-permuted; the terms' descriptors and their tables' nodes (all times, then all values) for k_ra_terms_begin
+    tdgl::DevBuf<double> e_Tbase, d_term_tab;
+    tdgl::DevBuf<tdgl::FieldTerm> d_terms;
     tdgl::DevBuf<double> d_tab_eps_t, d_tab_eps_f;   // the epsilon factor's table on the device (k_ra_eps_table)
     bool tab_eps_on_device = false;
     std::vector<double> tab_eps_t, tab_eps_f;

@@ -337,6 +337,10 @@ SIGNATURES = {
     "tdgl_set_link_ramp": (C.c_int, [_CTX, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]),
     "tdgl_set_link_table": (C.c_int, [_CTX, C.c_int32, c_f64p, c_f64p]),
     "tdgl_get_link_scale": (C.c_int, [_CTX, c_f64p]),
+    "tdgl_set_link_terms": (C.c_int, [_CTX, c_f64p, C.c_int32, c_f64p, c_i32p, c_f64p, c_i32p, c_f64p, c_f64p]),
+    "tdgl_update_link_terms": (C.c_int, [_CTX, c_f64p, C.c_double]),
+    "tdgl_get_link_term_scales": (C.c_int, [_CTX, c_i32p, c_f64p]),
+    "tdgl_get_link_term_moves": (C.c_int, [_CTX, C.POINTER(C.c_int64)]),
     "tdgl_update_link_exponents": (C.c_int, [_CTX, c_f64p, C.c_double]),
     "tdgl_set_epsilon": (C.c_int, [_CTX, c_f64p]),
     "tdgl_set_mu_boundary": (C.c_int, [_CTX, c_f64p]),
@@ -404,6 +408,9 @@ SIGNATURES = {
         C.c_int, [_ENS, C.c_int32, c_f64p, C.c_double, C.c_double, C.c_double, C.c_double]),
     "tdgl_ensemble_set_link_table": (C.c_int, [_ENS, C.c_int32, c_f64p, C.c_int32, c_f64p, c_f64p]),
     "tdgl_ensemble_get_link_scale": (C.c_int, [_ENS, C.c_int32, c_f64p]),
+    "tdgl_ensemble_set_link_terms": (
+        C.c_int, [_ENS, C.c_int32, c_f64p, C.c_int32, c_f64p, c_i32p, c_f64p, c_i32p, c_f64p, c_f64p]),
+    "tdgl_ensemble_get_link_term_scales": (C.c_int, [_ENS, C.c_int32, c_i32p, c_f64p]),
     "tdgl_ensemble_set_mu_boundary_table": (
         C.c_int, [_ENS, C.c_int32, C.c_int32, c_f64p, C.c_int32, c_i32p, c_i32p, c_f64p]),
     "tdgl_ensemble_set_epsilon_table": (C.c_int, [_ENS, C.c_int32, c_f64p, C.c_int32, c_f64p, c_f64p]),

@@ -6,7 +6,8 @@ thermalisation, adaptive dt, retries and errors.  The replicas share the device,
 the mu solve is the dense pseudo-inverse of the Poisson matrix up to ``ENSEMBLE_DENSE_MAX_SITES`` sites and the
 substructured direct solve of one or two levels above (`ensemble_mu_path`), applied to all replicas' right-hand
 sides in one pass over the factors per group of replicas.  A replica may be time dependent in the three forms the device evaluates itself, each with its own
-parameters: a field ramp ``LinearRamp * (static field)`` or field table ``TabulatedRamp * (static field)``,
+parameters: a field ramp ``LinearRamp * (static field)`` or field table ``TabulatedRamp * (static field)``, or a sum of
+a static field and up to four such products (``ConstantField(b) + TabulatedRamp(...) * <local field>``),
 ``TabulatedCurrents`` and a ``SeparableEpsilon``.  Not supported: other time-dependent inputs, a field ramp or field
 table combined with one of the other tables in one replica, screening, ``output_file``, more
 than ``ENSEMBLE_MAX_SITES`` sites.
@@ -25,8 +26,8 @@ import numpy as np
 from . import _lib
 from ._lib import c128, f64, p_f64, p_i32
 from .device import Device
-from .hipcore import (TDGLContext, controller_struct, epsilon_table_args, link_table_args, mu_boundary_table_args, probe_args,
-                      read_loop_state)
+from .hipcore import (FIELD_TERMS_MAX, TDGLContext, controller_struct, epsilon_table_args, link_table_args, link_terms_args,
+                      mu_boundary_table_args, probe_args, read_loop_state)
 from .options import SolverOptions
 from .runloop import RunRecord, check_epsilon_table, check_seed
 from .solution import Solution
@@ -92,13 +93,16 @@ def _refuse_options(options: SolverOptions, n_sites: int) -> None:
 
 def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
     """Time dependence the ensemble evaluates on the device passes: a separable A whose factor is a LinearRamp or a
-    TabulatedRamp, TabulatedCurrents, a SeparableEpsilon.  Anything else raises."""
+    TabulatedRamp, a sum of a static field and such products, TabulatedCurrents, a SeparableEpsilon.  Anything else
+    raises."""
     if rep.dynamic_vector_potential and not rep.device_evaluates_field():
+        form = ("LinearRamp(...) * (static field), TabulatedRamp(...) * (static field), or a sum (static field) + f_1 * "
+                f"(static field) + ... of up to {FIELD_TERMS_MAX} such products")
         if rep._A_base is not None:
             raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
-                             "LinearRamp(...) * (static field) or TabulatedRamp(...) * (static field); this one's time "
-                             "factor is not a LinearRamp or a TabulatedRamp.")
-        raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is not supported.")
+                             f"{form}; this one's time factor is not a LinearRamp or a TabulatedRamp.")
+        raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
+                         f"{form}; this one is not of that form.")
     if rep.dynamic_currents and rep._current_table is None:
         raise ValueError(f"solve_ensemble: replica {r}: time-dependent terminal_currents are not supported "
                          "(TabulatedCurrents are).")
@@ -106,7 +110,7 @@ def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
         raise ValueError(f"solve_ensemble: replica {r}: a time-dependent disorder_epsilon is not supported "
                          "(SeparableEpsilon is).")
     if rep.device_evaluates_field() and (rep._current_table is not None or rep._eps_table is not None):
-        what = "a field ramp" if rep._A_ramp is not None else "a field table"
+        what = "a field ramp" if rep._A_ramp is not None else "a field table" if rep._A_table is not None else "a sum of field terms"
         raise ValueError(f"solve_ensemble: replica {r}: {what} combined with TabulatedCurrents or a SeparableEpsilon "
                          "in one replica is not supported.")
 
@@ -129,7 +133,8 @@ def solve_ensemble(
     of them alone.  Every per-replica argument is a list of length R or one value for all replicas.
 
     Time-dependent replicas: ``applied_vector_potential`` may be ``LinearRamp(...) * <static field>`` or
-    ``TabulatedRamp(...) * <static field>`` (tables of any length, each replica its own),
+    ``TabulatedRamp(...) * <static field>`` (tables of any length, each replica its own), or a sum of a static field
+    and up to four such products (`Parameter.separable_terms`; each replica its own terms),
     ``terminal_currents`` a ``TabulatedCurrents``, ``disorder_epsilon`` a ``SeparableEpsilon`` (one kind of table or
     ramp per replica, except that tabulated currents and a separable epsilon may go together).  Static, ramped and
     tabulated replicas may share one ensemble.
@@ -157,7 +162,7 @@ def solve_ensemble(
 def solve_ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
                                  gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
                                  seed_states=None, vector_potential_ramp=None, epsilon_table=None,
-                                 vector_potential_table=None) -> List[Solution]:
+                                 vector_potential_table=None, vector_potential_terms=None) -> List[Solution]:
     """``solve_ensemble`` from dimensionless inputs (``TDGLSolver.from_dimensionless``): ``link_exponents`` A[m, 2]
     (an array, or a list of them), ``epsilon`` (a scalar or an [n] array, or a list), ``currents``
     ({terminal: dimensionless current} or a ``TabulatedCurrents``, or a list), ``seed_states`` (None or a list of
@@ -166,9 +171,12 @@ def solve_ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, e
     ``TDGLSolver.from_dimensionless`` (the replica's ``link_exponents`` may then be None: the ramp's value at t = 0),
     ``epsilon_table`` ``(epsilon0[n], times, factor)``: epsilon(t) = PiecewiseLinear(times, factor)(t) * epsilon0,
     ``vector_potential_table`` ``(A_base[m, 2], times, values)``: A(t) = TabulatedRamp(times, values)(t) * A_base (in a
-    replica without a ramp; ``link_exponents`` may be None as for a ramp)."""
+    replica without a ramp; ``link_exponents`` may be None as for a ramp), ``vector_potential_terms`` ``(A0[m, 2] or
+    None, [(A_k[m, 2], spec_k), ...])`` as in ``TDGLSolver.from_dimensionless`` (in a replica without ramp and table;
+    ``link_exponents`` may be None)."""
     return ensemble_dimensionless(mesh, options, link_exponents, epsilon, u, gamma, terminal_info, currents, probe_points,
-                                  seed_states, vector_potential_ramp, epsilon_table, vector_potential_table).solve()
+                                  seed_states, vector_potential_ramp, epsilon_table, vector_potential_table,
+                                  vector_potential_terms).solve()
 
 
 def _one_or_list(value, is_one):
@@ -205,7 +213,7 @@ def _with_epsilon_table(rep: TDGLSolver, table, n: int) -> None:
 def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
                            gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
                            seed_states=None, vector_potential_ramp=None, epsilon_table=None,
-                           vector_potential_table=None) -> "EnsembleSolver":
+                           vector_potential_table=None, vector_potential_terms=None) -> "EnsembleSolver":
     """The `EnsembleSolver` behind `solve_ensemble_dimensionless` (its ``solve()`` returns the solutions)."""
     _refuse_options(options, len(mesh.sites))
     per = dict(link_exponents=link_exponents, currents=currents, seed_states=seed_states)
@@ -214,7 +222,9 @@ def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon
     ramps = _one_or_list(vector_potential_ramp, lambda v: isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], dict))
     tables = _one_or_list(epsilon_table, lambda v: isinstance(v, tuple) and len(v) == 3)
     fields = _one_or_list(vector_potential_table, lambda v: isinstance(v, tuple) and len(v) == 3)
-    for name, v in (("vector_potential_ramp", ramps), ("epsilon_table", tables), ("vector_potential_table", fields)):
+    sums = _one_or_list(vector_potential_terms, lambda v: isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], list))
+    for name, v in (("vector_potential_ramp", ramps), ("epsilon_table", tables), ("vector_potential_table", fields),
+                    ("vector_potential_terms", sums)):
         if not isinstance(v, _Same):
             per[name] = v
     R, args = broadcast_replicas(**per)
@@ -222,11 +232,17 @@ def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon
     ramps = args.get("vector_potential_ramp", [getattr(ramps, "value", None)] * R)
     tables = args.get("epsilon_table", [getattr(tables, "value", None)] * R)
     fields = args.get("vector_potential_table", [getattr(fields, "value", None)] * R)
+    sums = args.get("vector_potential_terms", [getattr(sums, "value", None)] * R)
     reps = []
     for r in range(R):
         A = args["link_exponents"][r]
         if ramps[r] is not None and fields[r] is not None:
             raise ValueError(f"solve_ensemble: replica {r}: vector_potential_ramp and vector_potential_table exclude each other.")
+        if sums[r] is not None and (ramps[r] is not None or fields[r] is not None):
+            raise ValueError(f"solve_ensemble: replica {r}: vector_potential_terms excludes vector_potential_ramp and "
+                             "vector_potential_table.")
+        if A is None and sums[r] is not None:
+            A = np.zeros((len(mesh.edge_mesh.edges), 2))  # (replaced by the terms' value at t = 0 below)
         if A is None and ramps[r] is not None:
             from .parameter import LinearRamp
 
@@ -238,7 +254,9 @@ def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon
         rep = _ReplicaInputs.from_dimensionless(mesh, options, A, eps[r], u, gamma,
                                                 terminal_info=terminal_info, current_func=args["currents"][r],
                                                 probe_points=probe_points, vector_potential_ramp=ramps[r],
-                                                vector_potential_table=fields[r])
+                                                vector_potential_table=fields[r], vector_potential_terms=sums[r])
+        if sums[r] is not None and args["link_exponents"][r] is None:
+            rep.current_A_applied = rep.vector_potential_func(0.0)
         if tables[r] is not None:
             _with_epsilon_table(rep, tables[r], len(mesh.sites))
         _refuse_dynamic(r, rep)
@@ -305,6 +323,16 @@ class EnsembleContext:
         v = C.c_double(0)
         self._chk(self._lib.tdgl_ensemble_get_link_scale(self._ens, r, C.byref(v)))
         return v.value
+
+    def set_link_terms(self, r, A0, terms):
+        """A(t) = A0 + f_1(t) A_1 + ... + f_K(t) A_K for replica r, evaluated inside ``run``
+        (``TDGLContext.set_link_terms``'s arguments)."""
+        self._chk(self._lib.tdgl_ensemble_set_link_terms(self._ens, r, *link_terms_args(self.ctx.m, A0, terms)))
+
+    def link_term_scales(self, r):
+        n, v = C.c_int32(0), np.zeros(FIELD_TERMS_MAX)
+        self._chk(self._lib.tdgl_ensemble_get_link_term_scales(self._ens, r, C.byref(n), p_f64(v)))
+        return v[:n.value]
 
     def set_mu_boundary_table(self, r, times, groups, densities):
         """``TDGLContext.set_mu_boundary_table`` for replica r; ``times=None``: off."""
@@ -391,6 +419,9 @@ class _Replica:
     def link_scale(self):
         return self.ens.link_scale(self.r)
 
+    def link_term_scales(self):
+        return self.ens.link_term_scales(self.r)
+
     def get_state(self, supercurrent=True, normal_current=True):
         return self.ens.get_state(self.r, currents=supercurrent and normal_current)
 
@@ -449,7 +480,9 @@ class EnsembleSolver:
         reps, R = self.reps, len(self.reps)
         ens.set_probes(reps[0].probe_points)
         for r, rep in enumerate(reps):
-            if rep._A_ramp is not None:  # (TDGLSolver._setup: the links start at the ramp's value at t = 0)
+            if rep._A_terms is not None:
+                ens.set_link_terms(r, *rep._A_terms)
+            elif rep._A_ramp is not None:  # (TDGLSolver._setup: the links start at the ramp's value at t = 0)
                 ens.set_link_ramp(r, rep._A_base, **rep._A_ramp)
             elif rep._A_table is not None:
                 ens.set_link_table(r, rep._A_base, *rep._A_table)

@@ -76,6 +76,46 @@ def link_table_args(times, values) -> tuple:
     return len(t), p_f64(t), p_f64(v)
 
 
+FIELD_TERMS_MAX = 4  # TDGL_FIELD_TERMS_MAX
+
+
+def link_terms_args(m: int, A0, terms) -> tuple:
+    """``(A0, n_terms, bases, kind, ramp, tab_off, tab_times, tab_values)`` of tdgl_set_link_terms from ``A0`` ([m, 2]
+    or None) and ``terms``: a list of ``(A_k[m, 2], spec_k)`` with ``spec_k`` a ramp's ``dict(tmin, tmax, initial,
+    final)`` or a table's ``(times, values)``.  What only the shape of the arguments decides is refused here; the
+    values (strictly increasing times, finite numbers, tmax > tmin, 1 <= K <= FIELD_TERMS_MAX) are the library's to
+    refuse."""
+    terms = list(terms)
+    if A0 is not None:
+        A0 = f64(A0)
+        if A0.shape != (m, 2):
+            raise ValueError(f"Unexpected shape for vector_potential: {A0.shape}.")
+    K = len(terms)
+    bases = np.zeros((max(K, 1), m, 2))
+    kind = np.zeros(max(K, 1), dtype=np.int32)
+    ramp = np.zeros((max(K, 1), 4))
+    off = np.zeros(K + 1, dtype=np.int32)
+    tt, tv = [], []
+    for k, (base, spec) in enumerate(terms):
+        base = f64(base)
+        if base.shape != (m, 2):
+            raise ValueError(f"Unexpected shape for vector_potential: {base.shape}.")
+        bases[k] = base
+        if isinstance(spec, dict):
+            kind[k] = 1
+            ramp[k] = [float(spec[name]) for name in ("tmin", "tmax", "initial", "final")]
+        else:
+            link_table_args(*spec)  # (its shape check)
+            kind[k] = 2
+            tt.append(f64(spec[0]))
+            tv.append(f64(spec[1]))
+        off[k + 1] = off[k] + (len(tt[-1]) if kind[k] == 2 else 0)
+    times = f64(np.concatenate(tt)) if tt else np.zeros(1)
+    values = f64(np.concatenate(tv)) if tv else np.zeros(1)
+    return (p_f64(A0) if A0 is not None else None, K, p_f64(f64(bases)), p_i32(kind), p_f64(f64(ramp)), p_i32(off), p_f64(times),
+            p_f64(values))
+
+
 def controller_struct(dt_init, dt_max, adaptive, adaptive_window, max_solve_retries,
                       adaptive_time_step_multiplier) -> "_lib.Controller":
     return _lib.Controller(float(dt_init), float(dt_max), int(bool(adaptive)), int(adaptive_window),
@@ -1175,6 +1215,29 @@ class TDGLContext:
     def link_scale(self):
         v = C.c_double(0)
         self._chk(self._lib.tdgl_get_link_scale(self._ctx, C.byref(v)))
+        return v.value
+
+    def set_link_terms(self, A0, terms):
+        """Let ``run`` evaluate A(t) = A0 + f_1(t) A_1 + ... + f_K(t) A_K itself before every step: ``A0`` [m, 2] or
+        None, ``terms`` a list of ``(A_k[m, 2], spec_k)`` with ``spec_k`` a ramp's dict or a table's ``(times,
+        values)`` (`link_terms_args`).  Replaces ramp and table."""
+        self._chk(self._lib.tdgl_set_link_terms(self._ctx, *link_terms_args(self.m, A0, terms)))
+
+    def update_link_terms(self, scales, dt_prev):
+        """Move the sum of terms to the factors ``scales`` now, with dA/dt from the previous A (no upload)."""
+        scales = f64(scales)
+        self._chk(self._lib.tdgl_update_link_terms(self._ctx, p_f64(scales), float(dt_prev)))
+
+    def link_term_scales(self):
+        """The factors of the current A of a sum of terms (empty: no terms are set)."""
+        n, v = C.c_int32(0), np.zeros(FIELD_TERMS_MAX)
+        self._chk(self._lib.tdgl_get_link_term_scales(self._ctx, C.byref(n), p_f64(v)))
+        return v[:n.value]
+
+    def link_term_moves(self) -> int:
+        """Steps that have moved the sum of terms since it was set (the others skipped the edge pass)."""
+        v = C.c_int64(0)
+        self._chk(self._lib.tdgl_get_link_term_moves(self._ctx, C.byref(v)))
         return v.value
 
     def set_epsilon(self, eps):

@@ -107,6 +107,13 @@ class Parameter:
         space and ``static`` independent of time, else ``None``."""
         return None
 
+    def separable_terms(self):
+        """``(static_or_None, [(f_1, static_1), ..., (f_K, static_K)])`` if this parameter is a sum
+        ``static + f_1(t) * static_1 + ... + f_K(t) * static_K`` the time loop can evaluate itself (see
+        `CompositeParameter.separable_terms`), else ``None``.  A parameter that does not depend on time is the sum
+        without products: ``(self, [])``."""
+        return None if self.time_dependent else (self, [])
+
     def scalar(self, t) -> float:
         """Value of a uniform-in-space factor at time ``t``."""
         z = np.zeros(1)
@@ -242,6 +249,23 @@ class CompositeParameter(Parameter):
                 return f, static
         return None
 
+    def separable_terms(self):
+        """This parameter as ``A_0 + f_1(t) * A_1 + ... + f_K(t) * A_K``: ``(A_0 or None, [(f_k, A_k), ...])`` in the
+        order the products appear, for a tree built from ``+`` and ``-`` whose leaves are parameters independent of
+        time or products `separable_product` accepts with a `LinearRamp` or a `TabulatedRamp` as the factor.  The leaves
+        independent of time fold into the one ``A_0``; a subtracted leaf enters with its static part negated (which is
+        exact).  ``None`` when anything else appears in the tree -- a product of two factors, ``**``, a `Scale` with a
+        function of its own, a bare number -- or when there are more than ``FIELD_TERMS_MAX`` products.  The value of the
+        form, evaluated left to right as ``((A_0 + f_1 A_1) + f_2 A_2) + ...``, is what the time loop computes
+        (`tdgl_set_link_terms`); it differs from ``self(x, y, z, t=t)`` by the rounding of a reordered sum only."""
+        statics, terms = [], []
+        if not _collect_terms(self, 1, statics, terms) or len(terms) > FIELD_TERMS_MAX:
+            return None
+        static = None
+        for leaf in statics:
+            static = leaf if static is None else static + leaf
+        return static, terms
+
     def __call__(self, x, y, z=None, t=None):
         values = []
         for v in (self.left, self.right):
@@ -275,6 +299,28 @@ class CompositeParameter(Parameter):
 
     def __setstate__(self, state):
         self.__dict__.update(state)
+
+
+FIELD_TERMS_MAX = 4  # products in a sum the time loop evaluates itself (TDGL_FIELD_TERMS_MAX)
+
+
+def _collect_terms(p, sign: int, statics: list, terms: list) -> bool:
+    """The leaves of the ``+`` / ``-`` tree under ``p`` into ``statics`` and ``terms`` (``separable_terms``), each with
+    the sign it enters the sum with; False: the tree holds something the form does not cover."""
+    if not isinstance(p, Parameter):
+        return False
+    signed = (lambda q: q) if sign > 0 else (lambda q: -q)  # noqa: E731
+    if isinstance(p, CompositeParameter) and p.operator in (operator.add, operator.sub):
+        right = sign if p.operator is operator.add else -sign
+        return _collect_terms(p.left, sign, statics, terms) and _collect_terms(p.right, right, statics, terms)
+    if not p.time_dependent:
+        statics.append(signed(p))
+        return True
+    sep = p.separable_product()
+    if sep is None or (sep[0].ramp is None and getattr(sep[0], "table", None) is None):
+        return False
+    terms.append((sep[0], signed(sep[1])))
+    return True
 
 
 class Constant(Parameter):

@@ -116,10 +116,22 @@ class TDGLSolver:
         self.A_scale = device.field_scale(options.field_units)
         ex, ey = self.edge_centers[:, 0], self.edge_centers[:, 1]
         self.vector_potential_func = None
-        self._A_base = self._A_factor = self._A_ramp = self._A_table = None
+        self._A_base = self._A_factor = self._A_ramp = self._A_table = self._A_terms = None
         sep = applied_vector_potential.separable_product() if (
             self.dynamic_vector_potential and hasattr(applied_vector_potential, "separable_product")) else None
-        if sep is not None:
+        # (a single product with no static part keeps its own path, call for call; anything else that is a sum of a static
+        # field and such products goes to the device as terms)
+        terms = applied_vector_potential.separable_terms() if (
+            sep is None and self.dynamic_vector_potential and hasattr(applied_vector_potential, "separable_terms")) else None
+        if terms is not None and terms[1]:
+            # A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K with ramps and tables as factors: everything stays on the device,
+            # tdgl_run evaluates the factors itself (tdgl_set_link_terms)
+            static, products = terms
+            on_edges = lambda q: self.A_scale * np.asarray(q(ex, ey, self.z0))[:, :2]  # noqa: E731
+            self._set_terms(None if static is None else on_edges(static),
+                            [(on_edges(q), f.ramp if f.ramp is not None else (f.table.times, f.table.values)) for f, q in products])
+            A = self.vector_potential_func(0)
+        elif sep is not None:
             # A(t) = f(t) * A_static (the reference's field-ramp example): A_static stays on the
             # device, the factor is evaluated per step -- by tdgl_run itself for a LinearRamp or a TabulatedRamp
             factor, static = sep
@@ -222,7 +234,8 @@ class TDGLSolver:
                            u: float = 5.79, gamma: float = 10.0, terminal_info=(),
                            current_func=None, probe_points=None, device=None,
                            vector_potential_func=None, epsilon_func=None,
-                           screening=None, vector_potential_ramp=None, vector_potential_table=None) -> "TDGLSolver":
+                           screening=None, vector_potential_ramp=None, vector_potential_table=None,
+                           vector_potential_terms=None) -> "TDGLSolver":
         """Build a solver directly from dimensionless inputs -- the arrays the reference's
         ``__init__`` ends up with (solver.py:185, 214, 225, 254-256): ``A[m, 2]``,
         ``epsilon[n]``, ``TerminalInfo`` records and ``t -> {name: dimensionless current}``.
@@ -233,7 +246,9 @@ class TDGLSolver:
         initial, final))`` for ``A(t) = LinearRamp(t) * A_base`` evaluated by the library itself
         (then ``link_exponents`` must be its value at t = 0).  ``vector_potential_table``: ``(A_base[m, 2], times,
         values)`` for ``A(t) = TabulatedRamp(times, values)(t) * A_base``, evaluated by the library in the same way; a
-        ramp and a table exclude each other."""
+        ramp and a table exclude each other.  ``vector_potential_terms``: ``(A0[m, 2] or None, [(A_k[m, 2], spec_k),
+        ...])`` for the sum ``A(t) = A0 + f_1(t) A_1 + ... + f_K(t) A_K`` with ``spec_k`` a ramp's dict or a table's
+        ``(times, values)``, evaluated by the library as well; it excludes the ramp and the table."""
         self = object.__new__(cls)
         options.validate()
         self.device = device
@@ -248,9 +263,14 @@ class TDGLSolver:
         self.disorder_epsilon = epsilon
         # optional time dependence: t -> A[m, 2] / t -> epsilon[n], already dimensionless
         self.vector_potential_func = vector_potential_func
-        self._A_base = self._A_factor = self._A_ramp = self._A_table = None
+        self._A_base = self._A_factor = self._A_ramp = self._A_table = self._A_terms = None
         if vector_potential_ramp is not None and vector_potential_table is not None:
             raise ValueError("vector_potential_ramp and vector_potential_table exclude each other.")
+        if vector_potential_terms is not None:
+            if vector_potential_ramp is not None or vector_potential_table is not None:
+                raise ValueError("vector_potential_terms excludes vector_potential_ramp and vector_potential_table.")
+            self._set_terms(*vector_potential_terms)
+            vector_potential_func = self.vector_potential_func
         if vector_potential_ramp is not None or vector_potential_table is not None:
             from .parameter import LinearRamp, TabulatedRamp
 
@@ -296,6 +316,35 @@ class TDGLSolver:
         self._setup(mesh)
         return self
 
+    def _set_terms(self, A0, terms) -> None:
+        """A(t) = A0 + f_1(t) A_1 + ... + f_K(t) A_K from dimensionless arrays: ``terms`` is a list of ``(A_k[m, 2],
+        spec_k)``, ``spec_k`` a ramp's ``dict(tmin, tmax, initial, final)`` or a table's ``(times, values)``."""
+        from .parameter import FIELD_TERMS_MAX, LinearRamp, TabulatedRamp
+
+        terms = list(terms)
+        if not 1 <= len(terms) <= FIELD_TERMS_MAX:
+            raise ValueError(f"vector_potential_terms: between 1 and {FIELD_TERMS_MAX} terms, got {len(terms)}.")
+        factors, specs, bases = [], [], []
+        for base, spec in terms:
+            f = LinearRamp(**spec) if isinstance(spec, dict) else TabulatedRamp(*spec)
+            factors.append(f.scalar)
+            specs.append(f.ramp if f.ramp is not None else (f.table.times, f.table.values))
+            bases.append(np.asarray(base, dtype=float))
+        self._A_terms = (None if A0 is None else np.asarray(A0, dtype=float), list(zip(bases, specs)))
+        self._A_term_factors = factors
+        self.vector_potential_func = lambda t: self.terms_value([f(t) for f in factors])
+
+    def terms_value(self, scales) -> np.ndarray:
+        """``((A0 + s_1 A_1) + s_2 A_2) + ...`` left to right, every product rounded before it is added (NumPy does not
+        contract): the device's value for the same factors, bit for bit."""
+        A0, terms = self._A_terms
+        A = scales[0] * terms[0][0]
+        if A0 is not None:
+            A = A0 + A
+        for s, (base, _) in zip(scales[1:], terms[1:]):
+            A = A + s * base
+        return A
+
     def _setup_host(self, mesh) -> None:
         """The host-side part of the set-up (solver.py:258-289): fixed sites, initial values, mu boundary values."""
         em = mesh.edge_mesh
@@ -331,7 +380,9 @@ class TDGLSolver:
         )
         self.operators.build_operators()
         self.ctx = self.operators.ctx
-        if self._A_base is not None:
+        if self._A_terms is not None:
+            self.ctx.set_link_terms(*self._A_terms)
+        elif self._A_base is not None:
             self.ctx.set_link_exponents_base(self._A_base, self._A_factor(0))
             if self._A_ramp is not None:
                 self.ctx.set_link_ramp(**self._A_ramp)
@@ -405,8 +456,9 @@ class TDGLSolver:
         return changed
 
     def device_evaluates_field(self) -> bool:
-        """A(t) = f(t) * A_base with f a LinearRamp or a TabulatedRamp: the time loop evaluates f itself."""
-        return self._A_ramp is not None or self._A_table is not None
+        """A(t) = f(t) * A_base with f a LinearRamp or a TabulatedRamp, or a sum of a static field and such products
+        (`Parameter.separable_terms`): the time loop evaluates the factors itself."""
+        return self._A_ramp is not None or self._A_table is not None or self._A_terms is not None
 
     def device_evaluates_epsilon(self) -> bool:
         """epsilon(t) is a table the time loop evaluates itself (tdgl_set_epsilon_table); the host keeps a copy."""
@@ -416,7 +468,7 @@ class TDGLSolver:
         """solver.py:626-648: re-evaluate A(t) (-> link variables and dA/dt with the previous
         step's dt) and epsilon(t) before a step."""
         if self.device_evaluates_field():
-            pass  # tdgl_run evaluates the ramp or the table itself (tdgl_set_link_ramp, tdgl_set_link_table)
+            pass  # tdgl_run evaluates the ramp, the table or the terms itself (tdgl_set_link_ramp, _table, _terms)
         elif self._A_base is not None:
             self.ctx.update_link_scale(self._A_factor(time), dt_prev)
         elif self.dynamic_vector_potential:
@@ -468,7 +520,9 @@ class TDGLSolver:
         else:
             a_ind = np.zeros((self.num_edges, 2)) if induced_vector_potential is None else induced_vector_potential
         extra = []
-        if self._A_base is not None:
+        if self._A_terms is not None:
+            self.current_A_applied = self.terms_value(ctx.link_term_scales())
+        elif self._A_base is not None:
             self.current_A_applied = ctx.link_scale() * self._A_base
         if self.dynamic_vector_potential:
             extra.append(self.current_A_applied)
