@@ -592,8 +592,37 @@ int tdgl_update_link_exponents(tdgl_ctx *ctx, const double *A_new, double dt_pre
  *                                 itself before a step of the loop with one synchronisation per step.
  *   tdgl_get_link_term_scales     the K factors of the current A (n_terms = 0: no terms are set).
  *   tdgl_get_link_term_moves      how many steps have moved the sum since it was set, in either loop (the others found
- *                                 every factor unchanged and skipped the edge pass). */
+ *                                 every factor unchanged and skipped the edge pass).
+ *
+ * Moving current loops on top of either -- a susceptometer's field coil, a SQUID-on-tip or a magnetised tip scanned across
+ * the film, with or without a current waveform -- A(t) = [field in force] + sum_l I_l(t) Aloop(r_e - c_l(t); a_l) with
+ * 1 <= L <= TDGL_FIELD_LOOPS_MAX circular loops in planes parallel to the film:
+ *   tdgl_set_link_loops           adds L loops to the field in force: after tdgl_set_link_exponents (A_0 = that A, no
+ *                                 products) or after tdgl_set_link_terms (A_0 + the products); a single ramped or tabulated
+ *                                 product in force is refused.  edge_centres [n_edges, 2] in the caller's edge order, z_film
+ *                                 the film's height; per loop its radius and the nodes tab_off[l] .. tab_off[l + 1] of
+ *                                 tab_times (strictly increasing) with the centre tab_cx, tab_cy, tab_cz and the current
+ *                                 tab_current, each piecewise linear in t and constant outside the nodes.  The current
+ *                                 carries mu_0, the units and the solver's scale: A_phi = I G with the dimensionless
+ *                                 G = ((2 - m) K(m) - 2 E(m)) d / (4 pi rho), d^2 = (a + rho)^2 + z^2, m = 4 a rho / d^2,
+ *                                 evaluated through the arithmetic-geometric mean without cancellation (relative error about
+ *                                 1e-15 for 1e-12 <= m <= 1 - 1e-8, exactly zero on the axis; no atan2, sin or cos).  Every
+ *                                 argument is checked before anything in force is touched -- n_loops in [1, 2], finite
+ *                                 values, radius > 0, and cz on one side of z_film at every node, so that the loop's plane
+ *                                 never meets the film's and m < 1 strictly --: a refused call leaves a working field.
+ *                                 Sets A = A_prev = A(0), dA/dt = 0.  n_loops = 0 removes the loops and leaves what they
+ *                                 were added to, at the factors in force; any other link setter removes them too.  The
+ *                                 step rule is the terms' extended: a step moves nothing only when every factor and every
+ *                                 loop's four values equal their last two evaluations; past every table's last node, and
+ *                                 everything seen twice, the run costs what a static one does.  Both time loops use one
+ *                                 edge kernel and agree to the last bit.
+ *   tdgl_update_link_loops        moves the field to the given K factors (ignored without terms) and L x 4 loop values
+ *                                 (cx, cy, cz, I) now, dA/dt with dt_prev.
+ *   tdgl_get_link_loop_params     the L x 4 values of the current A (n_loops = 0: no loops are set).
+ *   tdgl_get_link_exponents       the current A [n_edges, 2] in the caller's edge order, whatever set it: what was applied.
+ * tdgl_get_link_term_moves counts the moves of the whole sum, loops included. */
 #define TDGL_FIELD_TERMS_MAX 4
+#define TDGL_FIELD_LOOPS_MAX 2
 int tdgl_set_link_exponents_base(tdgl_ctx *ctx, const double *A_base, double scale);
 int tdgl_update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev);
 int tdgl_set_link_ramp(tdgl_ctx *ctx, int32_t on, double tmin, double tmax, double initial, double final_value);
@@ -604,6 +633,12 @@ int tdgl_set_link_terms(tdgl_ctx *ctx, const double *A0, int32_t n_terms, const 
 int tdgl_update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev);
 int tdgl_get_link_term_scales(tdgl_ctx *ctx, int32_t *n_terms, double *scales);
 int tdgl_get_link_term_moves(tdgl_ctx *ctx, int64_t *moves);
+int tdgl_set_link_loops(tdgl_ctx *ctx, int32_t n_loops, const double *edge_centres, double z_film, const double *radius,
+                        const int32_t *tab_off, const double *tab_times, const double *tab_cx, const double *tab_cy,
+                        const double *tab_cz, const double *tab_current);
+int tdgl_update_link_loops(tdgl_ctx *ctx, const double *term_scales, const double *loop_params, double dt_prev);
+int tdgl_get_link_loop_params(tdgl_ctx *ctx, int32_t *n_loops, double *params);
+int tdgl_get_link_exponents(tdgl_ctx *ctx, double *A);
 /* self.epsilon (solver.py:191-216, 645-648). */
 int tdgl_set_epsilon(tdgl_ctx *ctx, const double *epsilon);
 /* self.mu_boundary (solver.py:289, 325-345): indexed by position in boundary_edge_indices. */

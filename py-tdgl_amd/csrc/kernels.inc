@@ -648,31 +648,42 @@ __global__ void k_ra_table_begin(StepCtl *__restrict__ ctl, const double *__rest
 // dynamic update has run.  `term`: the K = ctl->n_terms descriptors of THIS controller; a table term's nodes are
 // times[off .. off + n), values[off .. off + n).  Leaves has_dadt and ramp_do as ramp_begin_body leaves them.
 // (body: one thread per controller)
+// the K factors at time t into s[]; false when one of them differs from its last two evaluations
+__device__ __forceinline__ bool terms_eval(const StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term,
+                                           const double *__restrict__ times, const double *__restrict__ values, double t, double *s) {
+#pragma clang fp contract(off)
+    const int K = ctl->n_terms;
+    bool same = true;
+#pragma unroll
+    for (int k = 0; k < FIELD_TERMS_MAX; ++k) {
+        s[k] = 0.0;
+        if (k >= K) continue;
+        const FieldTerm d = term[k];
+        s[k] = d.kind == TERM_TABLE ? table_value_dev(times + d.off, values + d.off, d.n, t)
+                                    : linear_ramp_value(t, d.ramp[0], d.ramp[1], d.ramp[2], d.ramp[3]);
+        same = same && s[k] == ctl->term_scale[k] && s[k] == ctl->term_scale_prev[k];
+    }
+    return same;
+}
+
+// ... taken over as the factors of the current A
+__device__ __forceinline__ void terms_take(StepCtl *__restrict__ ctl, const double *s) {
+#pragma unroll
+    for (int k = 0; k < FIELD_TERMS_MAX; ++k)
+        if (k < ctl->n_terms) {
+            ctl->term_scale_prev[k] = ctl->term_scale[k];
+            ctl->term_scale[k] = s[k];
+        }
+}
+
 __device__ __forceinline__ void terms_begin_body(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term,
                                                  const double *__restrict__ times, const double *__restrict__ values) {
-#pragma clang fp contract(off)
     int go = 0;
     if (!ctl->poisoned && ctl->retries == 0) {
-        const int K = ctl->n_terms;
-        const double t = ctl->time;
         double s[FIELD_TERMS_MAX];
-        bool same = ctl->has_dadt != 0;
-#pragma unroll
-        for (int k = 0; k < FIELD_TERMS_MAX; ++k) {
-            s[k] = 0.0;
-            if (k >= K) continue;
-            const FieldTerm d = term[k];
-            s[k] = d.kind == TERM_TABLE ? table_value_dev(times + d.off, values + d.off, d.n, t)
-                                        : linear_ramp_value(t, d.ramp[0], d.ramp[1], d.ramp[2], d.ramp[3]);
-            same = same && s[k] == ctl->term_scale[k] && s[k] == ctl->term_scale_prev[k];
-        }
+        const bool same = terms_eval(ctl, term, times, values, ctl->time, s) && ctl->has_dadt != 0;
         if (!same) {
-#pragma unroll
-            for (int k = 0; k < FIELD_TERMS_MAX; ++k)
-                if (k < K) {
-                    ctl->term_scale_prev[k] = ctl->term_scale[k];
-                    ctl->term_scale[k] = s[k];
-                }
+            terms_take(ctl, s);
             ctl->has_dadt = 1;
             ctl->n_term_moves += 1;
             go = 1;
@@ -700,13 +711,11 @@ struct TermScales {
 // without A_0 the sum starts from the first product.  Then dA/dt, A_prev <- A and "did it move" as for the single product
 // (dadt_body).  `bases`: slot 0 A_0, slot k the k-th base, `stride` double2 apart; a pure stream, 16 bytes per lane and
 // array: (K + 1) 16 read, 16 written for A, and dadt_body's 16 + 24 read, 16 + 8 written.
-__device__ __forceinline__ int terms_link_body(int64_t e, int64_t m, const TermScales &ts, const double2 *__restrict__ bases, int64_t stride,
-                                               double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
-                                               const double *__restrict__ dy, const double *__restrict__ inv_len,
-                                               double *__restrict__ dadt) {
+__device__ __forceinline__ void terms_sum(int64_t e, const TermScales &ts, const double2 *__restrict__ bases, int64_t stride, double &ax,
+                                          double &ay) {
 #pragma clang fp contract(off)
     const double2 b1 = bases[stride + e];
-    double ax = ts.s[0] * b1.x, ay = ts.s[0] * b1.y;
+    ax = ts.s[0] * b1.x, ay = ts.s[0] * b1.y;
     asm volatile("" : "+v"(ax), "+v"(ay));
     if (ts.a0) {
         const double2 a0 = bases[e];
@@ -723,6 +732,14 @@ __device__ __forceinline__ int terms_link_body(int64_t e, int64_t m, const TermS
         ay = ay + py;
     }
     asm volatile("" : "+v"(ax), "+v"(ay));
+}
+
+__device__ __forceinline__ int terms_link_body(int64_t e, int64_t m, const TermScales &ts, const double2 *__restrict__ bases, int64_t stride,
+                                               double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
+                                               const double *__restrict__ dy, const double *__restrict__ inv_len,
+                                               double *__restrict__ dadt) {
+    double ax, ay;
+    terms_sum(e, ts, bases, stride, ax, ay);
     reinterpret_cast<double2 *>(A)[e] = make_double2(ax, ay);
     return dadt_body(e, m, ts.inv_dt, ax, ay, Aprev, dx, dy, inv_len, dadt);
 }
@@ -750,6 +767,146 @@ __global__ __launch_bounds__(BLOCK) void k_terms_links(int64_t m, int64_t m_pad,
     const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
     const int changed =
         e < m ? terms_link_body(e, m, ts, reinterpret_cast<const double2 *>(bases), m_pad, A, Aprev, dx, dy, inv_len, dadt) : 0;
+    const int any = __syncthreads_or(changed);
+    if (threadIdx.x == 0) block_changed[blockIdx.x] = any;
+}
+
+// ---- moving current loops on top of that field (tdgl_set_link_loops) -----------------------------------------------------
+// A(t) = [A_0 + sum_k f_k(t) A_k] + sum_l I_l(t) Aloop(r_e - c_l(t); a_l): a circular loop of radius a in a plane parallel to
+// the film, its centre and current piecewise linear in t.  Six numbers per step and one closed form per edge.
+//
+// The loop's potential without cancellation.  With rho the in-plane distance from the axis, z the height of the film above
+// the loop's plane, d^2 = (a + rho)^2 + z^2 and m = 4 a rho / d^2, A_phi = I G with G = ((2 - m) K(m) - 2 E(m)) d / (4 pi rho)
+// (I: the current with mu_0 and the units folded in).  That textbook form subtracts two numbers that agree to O(m^2) and
+// has no correct digit below m ~ 1e-6.  Here
+// (2 - m) K - 2 E = K sum_{n >= 1} 2^n c_n^2 with c_n the differences of the arithmetic-geometric mean: every term positive.
+// b0 = sqrt(1 - m) is formed as sqrt(((a - rho)^2 + z^2) / d^2), never from 1 - m; c_0 / rho = 2 a / (d^2 (1 + b0)) is carried
+// next to c_0, so H = G / rho needs no division by rho and A = I H (-dy, dx) is exactly zero on the axis.  LOOP_AGM_STEPS
+// halvings reach double precision down to 1 - m = 2e-9 (z != 0 is the caller's to guarantee); a fixed count, every lane the
+// same work: per loop and edge 3 + LOOP_AGM_STEPS square roots and 3 + LOOP_AGM_STEPS divisions in fp64.
+constexpr int LOOP_AGM_STEPS = 6;
+__device__ __forceinline__ void loop_potential_add(double ex, double ey, double cx, double cy, double z, double a, double cur, double &ax,
+                                                   double &ay) {
+#pragma clang fp contract(off)
+    const double dx = ex - cx, dy = ey - cy;
+    const double rho = sqrt(dx * dx + dy * dy);
+    const double z2 = z * z, sp = a + rho, sm = a - rho;
+    const double d2 = sp * sp + z2;
+    const double b0 = sqrt((sm * sm + z2) / d2);
+    const double ob = 1.0 + b0;
+    double cr = (2.0 * a) / (d2 * ob);  // c / rho
+    double c = cr * rho;
+    double an = 0.5 * ob, bn = sqrt(b0), sr = 2.0 * (cr * cr), p = 4.0;  // sr = S / rho^2
+#pragma unroll
+    for (int n = 0; n < LOOP_AGM_STEPS; ++n) {
+        const double a1 = 0.5 * (an + bn);
+        bn = sqrt(an * bn);
+        const double q = c / (4.0 * a1);
+        cr = cr * q;
+        c = c * q;
+        sr = sr + p * (cr * cr);
+        p = p * 2.0;
+        an = a1;
+    }
+    const double h = cur * ((sr * sqrt(d2)) / (8.0 * an));
+    double lx = -(dy * h), ly = dx * h;
+    asm volatile("" : "+v"(lx), "+v"(ly));
+    ax = ax + lx;
+    ay = ay + ly;
+}
+
+// what does not move: the loops' radii, the film's height and how many there are; and the 4 values per loop that do
+struct LoopGeom {
+    double radius[FIELD_LOOPS_MAX];
+    double z_film;
+    int n_loops, pad;
+};
+struct LoopPars {
+    double p[FIELD_LOOPS_MAX][4];  // centre x, y, z and current
+};
+
+// (body: one thread per controller)  The terms' rule extended: nothing moves only when every factor AND every loop's four
+// values equal their last two evaluations and a dynamic update has run.  loop[l]: nodes off .. off + n of the pools
+// tab[0 .. T) (times), tab[T ..) centre x, then y, z and the current, T nodes each.
+__device__ __forceinline__ void loops_begin_body(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term,
+                                                 const double *__restrict__ times, const double *__restrict__ values,
+                                                 const FieldLoop *__restrict__ loop, const double *__restrict__ tab, int T) {
+    int go = 0;
+    if (!ctl->poisoned && ctl->retries == 0) {
+        const double t = ctl->time;
+        double s[FIELD_TERMS_MAX], lp[FIELD_LOOPS_MAX][4];
+        bool same = terms_eval(ctl, term, times, values, t, s) && ctl->has_dadt != 0;
+        const int L = ctl->n_loops;
+#pragma unroll
+        for (int l = 0; l < FIELD_LOOPS_MAX; ++l) {
+            if (l >= L) continue;
+            const FieldLoop d = loop[l];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                lp[l][j] = table_value_dev(tab + d.off, tab + (int64_t)(j + 1) * T + d.off, d.n, t);
+                same = same && lp[l][j] == ctl->loop_par[l][j] && lp[l][j] == ctl->loop_par_prev[l][j];
+            }
+        }
+        if (!same) {
+            terms_take(ctl, s);
+#pragma unroll
+            for (int l = 0; l < FIELD_LOOPS_MAX; ++l)
+                if (l < L) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        ctl->loop_par_prev[l][j] = ctl->loop_par[l][j];
+                        ctl->loop_par[l][j] = lp[l][j];
+                    }
+                }
+            ctl->has_dadt = 1;
+            ctl->n_term_moves += 1;
+            go = 1;
+        }
+    }
+    ctl->ramp_do = go;
+}
+
+__global__ void k_ra_loops_begin(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term, const double *__restrict__ times,
+                                 const double *__restrict__ values, const FieldLoop *__restrict__ loop, const double *__restrict__ tab,
+                                 int T) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    loops_begin_body(ctl, term, times, values, loop, tab, T);
+}
+
+// One lane per edge: the sum of terms as k_terms_links forms it (terms_sum; without products A_0 alone), the loops added in
+// loop order, then dA/dt, A_prev <- A and "did it move" (dadt_body).  Over k_terms_links 16 more bytes read per edge (the
+// centre), no LDS, no atomics.  ctl: the run-ahead loop's controller (factors and loop values from there); nullptr: `host`'s
+// and `hostp`'s
+__global__ __launch_bounds__(BLOCK) void k_loops_links(int64_t m, int64_t m_pad, TermScales host, LoopPars hostp, LoopGeom geom,
+                                                       const double *__restrict__ bases, const double *__restrict__ centres,
+                                                       double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
+                                                       const double *__restrict__ dy, const double *__restrict__ inv_len,
+                                                       double *__restrict__ dadt, int32_t *__restrict__ block_changed,
+                                                       const StepCtl *__restrict__ ctl) {
+    if (ctl && !ctl->ramp_do) return;
+    const TermScales ts = ctl ? term_scales_of(ctl) : host;
+    const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+    int changed = 0;
+    if (e < m) {
+        const double2 *b2 = reinterpret_cast<const double2 *>(bases);
+        double ax, ay;
+        if (ts.n_terms > 0) {
+            terms_sum(e, ts, b2, m_pad, ax, ay);
+        } else {
+            const double2 a0 = b2[e];
+            ax = a0.x, ay = a0.y;
+        }
+        const double2 ce = reinterpret_cast<const double2 *>(centres)[e];
+#pragma unroll
+        for (int l = 0; l < FIELD_LOOPS_MAX; ++l) {
+            if (l >= geom.n_loops) break;
+            const double cx = ctl ? ctl->loop_par[l][0] : hostp.p[l][0], cy = ctl ? ctl->loop_par[l][1] : hostp.p[l][1];
+            const double cz = ctl ? ctl->loop_par[l][2] : hostp.p[l][2], cur = ctl ? ctl->loop_par[l][3] : hostp.p[l][3];
+            loop_potential_add(ce.x, ce.y, cx, cy, geom.z_film - cz, geom.radius[l], cur, ax, ay);
+        }
+        reinterpret_cast<double2 *>(A)[e] = make_double2(ax, ay);
+        changed = dadt_body(e, m, ts.inv_dt, ax, ay, Aprev, dx, dy, inv_len, dadt);
+    }
     const int any = __syncthreads_or(changed);
     if (threadIdx.x == 0) block_changed[blockIdx.x] = any;
 }

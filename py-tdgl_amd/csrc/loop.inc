@@ -145,13 +145,39 @@ double LoopState::term_value(int k, double t) const {
     return linear_ramp_value(t, term[k].ramp[0], term[k].ramp[1], term[k].ramp[2], term[k].ramp[3]);
 }
 
-bool LoopState::terms_step(const double *s) {
+bool LoopState::terms_step(const double *s, const double *lp) {
     bool same = has_dadt;
     for (int k = 0; k < n_terms; ++k) same = same && s[k] == term_scale[k] && s[k] == term_scale_prev[k];
+    for (int l = 0; l < n_loops; ++l)
+        for (int j = 0; j < 4; ++j) same = same && lp[4 * l + j] == loop_par[l][j] && lp[4 * l + j] == loop_par_prev[l][j];
     if (same) return false;
     for (int k = 0; k < n_terms; ++k) term_scale_prev[k] = term_scale[k], term_scale[k] = s[k];
+    for (int l = 0; l < n_loops; ++l)
+        for (int j = 0; j < 4; ++j) loop_par_prev[l][j] = loop_par[l][j], loop_par[l][j] = lp[4 * l + j];
     term_moves += 1;
     return true;
+}
+
+void LoopState::set_loops(int n, double z_film, const double *radius, const int32_t *tab_off, const double *times, const double *cx,
+                          const double *cy, const double *cz, const double *current) {
+    n_loops = n, loop_zfilm = z_film, term_moves = 0;
+    const double *src[4] = {cx, cy, cz, current};
+    for (int l = 0; l < FIELD_LOOPS_MAX; ++l) {
+        loop_t[l].clear();
+        for (int j = 0; j < 4; ++j) loop_v[l][j].clear(), loop_par[l][j] = loop_par_prev[l][j] = 0.0;
+        loop_radius[l] = 0.0;
+        if (l >= n) continue;
+        loop_radius[l] = radius[l];
+        loop_t[l].assign(times + tab_off[l], times + tab_off[l + 1]);
+        for (int j = 0; j < 4; ++j) loop_v[l][j].assign(src[j] + tab_off[l], src[j] + tab_off[l + 1]);
+        loop_values(l, 0.0, loop_par[l]);
+        for (int j = 0; j < 4; ++j) loop_par_prev[l][j] = loop_par[l][j];
+    }
+    ramp_on = n > 0 || n_terms > 0;
+}
+
+void LoopState::loop_values(int l, double t, double *out4) const {
+    for (int j = 0; j < 4; ++j) out4[j] = table_value(loop_t[l], loop_v[l][j].data(), t);
 }
 
 // the device's controller at the start of a batch; live = false: poisoned from the first attempt on
@@ -177,6 +203,9 @@ void LoopState::fill(StepCtl &h, double end_time, bool live) const {
     h.has_dadt = has_dadt ? 1 : 0;
     h.n_terms = terms() ? n_terms : 0, h.term_a0 = term_a0 ? 1 : 0;
     for (int k = 0; k < h.n_terms; ++k) h.term_scale[k] = term_scale[k], h.term_scale_prev[k] = term_scale_prev[k];
+    h.n_loops = loops() ? n_loops : 0;
+    for (int l = 0; l < h.n_loops; ++l)
+        for (int j = 0; j < 4; ++j) h.loop_par[l][j] = loop_par[l][j], h.loop_par_prev[l][j] = loop_par_prev[l][j];
     if (ctl.adaptive) {
         const int64_t have = (int64_t)hist.size(), cnt = std::min<int64_t>(have, ctl.adaptive_window);
         h.hist_count = (int)cnt;
@@ -214,6 +243,8 @@ LoopState::Batch LoopState::absorb(const StepCtl &h, const StepRec *rec, int bat
         link_scale_prev = h.link_scale_prev;
         has_dadt = h.has_dadt != 0;
         for (int k = 0; k < n_terms; ++k) term_scale[k] = h.term_scale[k], term_scale_prev[k] = h.term_scale_prev[k];
+        for (int l = 0; l < n_loops; ++l)
+            for (int j = 0; j < 4; ++j) loop_par[l][j] = h.loop_par[l][j], loop_par_prev[l][j] = h.loop_par_prev[l][j];
         term_moves += h.n_term_moves;
     }
     cur = h.cur;

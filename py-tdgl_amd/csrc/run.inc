@@ -471,7 +471,20 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
                                    (const double2 *)ctx->psi[0].p, (const double2 *)ctx->psi[1].p, (const double *)ctx->mu.p, ctx->js.p, ctx->jn.p,
                                    (const double *)ctx->e_dAdt.p, (const StepCtl *)dc);
             const int nblk = grid_for(ctx->m);
-            if (ctx->loop.terms()) {
+            if (ctx->loop.loops()) {
+                // moving loops (on terms or on a static A): their begin and links kernels in the place of the terms' pair
+                const double *tab = ctx->d_term_tab.p;
+                LoopGeom g{};
+                g.n_loops = ctx->loop.n_loops, g.z_film = ctx->loop.loop_zfilm;
+                for (int l = 0; l < g.n_loops; ++l) g.radius[l] = ctx->loop.loop_radius[l];
+                hipLaunchKernelGGL(k_ra_loops_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const FieldTerm *)ctx->d_terms.p, tab,
+                                   tab + ctx->d_term_tab.n / 2, (const FieldLoop *)ctx->d_loops.p, (const double *)ctx->d_loop_tab.p,
+                                   (int)(ctx->d_loop_tab.n / 5));
+                hipLaunchKernelGGL(k_loops_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, TermScales{}, LoopPars{}, g,
+                                   (const double *)ctx->e_Tbase.p, (const double *)ctx->e_centres.p, ctx->e_A.p, ctx->e_Aprev.p,
+                                   (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
+                                   ctx->e_dAdt.p, ctx->link_block_changed.p, (const StepCtl *)dc);
+            } else if (ctx->loop.terms()) {
                 // a sum of terms: its own begin and links kernels in the place of the single product's pair
                 const double *tab = ctx->d_term_tab.p;
                 hipLaunchKernelGGL(k_ra_terms_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const FieldTerm *)ctx->d_terms.p, tab,
@@ -630,10 +643,12 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
             // A(t) = ramp(t) * A_base, ramp = tdgl/sources/scaling.py LinearRamp; dA/dt uses the
             // previous step's dt (Runner.dt)
             // (or a table in the ramp's place: tdgl_set_link_table; or a sum of such terms: tdgl_set_link_terms)
-            if (ctx->loop.terms()) {
-                double s[FIELD_TERMS_MAX] = {0.0, 0.0, 0.0, 0.0};
+            // (... plus moving loops: tdgl_set_link_loops)
+            if (ctx->loop.terms() || ctx->loop.loops()) {
+                double s[FIELD_TERMS_MAX] = {0.0, 0.0, 0.0, 0.0}, lp[FIELD_LOOPS_MAX * 4] = {};
                 for (int j = 0; j < ctx->loop.n_terms; ++j) s[j] = ctx->loop.term_value(j, ctx->loop.time);
-                status = update_link_terms(ctx, s, ctx->loop.runner_dt);
+                for (int l = 0; l < ctx->loop.n_loops; ++l) ctx->loop.loop_values(l, ctx->loop.time, lp + 4 * l);
+                status = ctx->loop.loops() ? update_link_loops(ctx, s, lp, ctx->loop.runner_dt) : update_link_terms(ctx, s, ctx->loop.runner_dt);
             } else {
                 const double scale = ctx->loop.tabulated()
                                          ? table_value(ctx->loop.tab_t, ctx->loop.tab_v.data(), ctx->loop.time)

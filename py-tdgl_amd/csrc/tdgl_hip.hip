@@ -613,6 +613,7 @@ static void refresh_ceff(tdgl_ctx *ctx) {
 
 static int update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev);  // below
 static int update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev);  // below
+static int update_link_loops(tdgl_ctx *ctx, const double *scales, const double *loop_params, double dt_prev);  // below
 static int apply_time_tables(tdgl_ctx *ctx);                                 // below
 static double table_value(const std::vector<double> &t, const double *v, double time);  // below
 static int check_link_table(tdgl_ctx *ctx, const char *who, int32_t n_nodes, const double *times, const double *values);  // below
@@ -854,6 +855,7 @@ static int update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev
 extern "C" int tdgl_update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev) {
     CTX_GUARD(ctx);
     if (!ctx->loop.terms()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_terms first");
+    if (ctx->loop.loops()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "moving loops are set: tdgl_update_link_loops moves the whole sum");
     if (!scales) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_terms: null scales");
     for (int k = 0; k < ctx->loop.n_terms; ++k)
         if (!std::isfinite(scales[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_terms: non-finite factor");
@@ -863,9 +865,166 @@ extern "C" int tdgl_update_link_terms(tdgl_ctx *ctx, const double *scales, doubl
     return TDGL_OK;
 }
 
+// ---- ... plus moving current loops: A(t) = [that] + sum_l I_l(t) Aloop(r_e - c_l(t); a_l) --------------------------------
+static int launch_loops_links(tdgl_ctx *ctx, const double *scales, const double *lp, double inv_dt) {
+    const int nblk = grid_for(ctx->m);
+    if (ctx->link_block_changed.n == 0) {
+        HIP_TRY(ctx, ctx->link_block_changed.alloc(nblk));
+        HIP_TRY(ctx, ctx->link_changed.alloc(1));
+    }
+    const LoopState &L = ctx->loop;
+    TermScales ts{};
+    for (int k = 0; k < L.n_terms; ++k) ts.s[k] = scales[k];
+    ts.inv_dt = inv_dt, ts.n_terms = L.n_terms, ts.a0 = L.term_a0 ? 1 : 0;
+    LoopPars hp{};
+    LoopGeom g{};
+    g.n_loops = L.n_loops, g.z_film = L.loop_zfilm;
+    for (int l = 0; l < L.n_loops; ++l) {
+        g.radius[l] = L.loop_radius[l];
+        for (int j = 0; j < 4; ++j) hp.p[l][j] = lp[4 * l + j];
+    }
+    hipLaunchKernelGGL(k_loops_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, ts, hp, g, (const double *)ctx->e_Tbase.p,
+                       (const double *)ctx->e_centres.p, ctx->e_A.p, ctx->e_Aprev.p, (const double *)ctx->e_dirx.p,
+                       (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p, ctx->e_dAdt.p, ctx->link_block_changed.p,
+                       (const StepCtl *)nullptr);
+    return TDGL_OK;
+}
+
+// A = A_prev = the field at the values in force, dA/dt = 0 (the links kernel against A_prev = 0 with 1 / dt = 0), the links,
+// the Laplacian values -- with the loops, or with the terms alone once the loops are gone
+static int restart_sources(tdgl_ctx *ctx) {
+    HIP_TRY(ctx, hipMemsetAsync(ctx->e_Aprev.p, 0, 2 * (size_t)ctx->m_pad * sizeof(double), ctx->stream));
+    if (ctx->loop.loops())
+        TDGL_TRY(launch_loops_links(ctx, ctx->loop.term_scale, &ctx->loop.loop_par[0][0], 0.0));
+    else
+        TDGL_TRY(launch_terms_links(ctx, ctx->loop.term_scale, 0.0));
+    TDGL_TRY(finish_links(ctx, false, 0.0));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_set_link_loops(tdgl_ctx *ctx, int32_t n_loops, const double *edge_centres, double z_film, const double *radius,
+                                   const int32_t *tab_off, const double *tab_times, const double *tab_cx, const double *tab_cy,
+                                   const double *tab_cz, const double *tab_current) {
+    CTX_GUARD(ctx);
+    const char *who = "tdgl_set_link_loops";
+    if (n_loops == 0) {  // the loops go; what they were added to stays, at the values in force
+        if (!ctx->loop.loops()) return TDGL_OK;
+        ctx->loop.set_loops(0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        if (ctx->loop.terms()) return restart_sources(ctx);
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->e_A.p, ctx->e_Tbase.p, 2 * (size_t)ctx->m_pad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->loop.links_static();
+        TDGL_TRY(finish_links(ctx, false, 0.0));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return TDGL_OK;
+    }
+    // everything is checked before anything in force is touched
+    if (n_loops < 1 || n_loops > FIELD_LOOPS_MAX) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: n_loops must be in [0, %d]", who, FIELD_LOOPS_MAX);
+    if (!ctx->have_links) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "%s: call tdgl_set_link_exponents or tdgl_set_link_terms first", who);
+    if (ctx->loop.ramp_on && !ctx->loop.terms() && !ctx->loop.loops())
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: a single ramped or tabulated product is in force; loops go with a static field or with tdgl_set_link_terms", who);
+    if (!edge_centres || !radius || !tab_off || !tab_times || !tab_cx || !tab_cy || !tab_cz || !tab_current)
+        TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: null argument", who);
+    if (!std::isfinite(z_film)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: z_film must be finite", who);
+    for (int64_t i = 0; i < 2 * ctx->m; ++i)
+        if (!std::isfinite(edge_centres[i])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: non-finite edge centre", who);
+    if (tab_off[0] != 0) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: tab_off must start at 0", who);
+    for (int32_t l = 0; l < n_loops; ++l) {
+        if (!(std::isfinite(radius[l]) && radius[l] > 0.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: loop %d: the radius must be finite and > 0", who, l);
+        const int32_t n = tab_off[l + 1] - tab_off[l];
+        if (n < 1) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: loop %d has no nodes", who, l);
+        const double *tabs[4] = {tab_cx, tab_cy, tab_cz, tab_current};
+        for (int j = 0; j < 4; ++j) TDGL_TRY(check_link_table(ctx, who, n, tab_times + tab_off[l], tabs[j] + tab_off[l]));
+        // the loop's plane stays on one side of the film: between two nodes on the same side the interpolant cannot reach it,
+        // so m < 1 strictly at every time
+        const double side = tab_cz[tab_off[l]] - z_film;
+        for (int32_t i = tab_off[l]; i < tab_off[l + 1]; ++i)
+            if (!((tab_cz[i] - z_film) * side > 0.0))
+                TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: loop %d: the loop's plane must differ from the film's (cz != z_film, on one side of it) at every node", who, l);
+    }
+    const size_t slot = 2 * (size_t)ctx->m_pad;
+    DevBuf<double> centres, base0, d_tab;
+    DevBuf<FieldLoop> d_desc;
+    HIP_TRY(ctx, centres.alloc(slot));
+    TDGL_TRY(upload_edge_vectors(ctx, edge_centres, centres.p));
+    const bool fresh = !ctx->loop.terms() && !ctx->loop.loops();  // on a static A: that A becomes slot 0
+    if (fresh) {
+        HIP_TRY(ctx, base0.alloc(slot));
+        HIP_TRY(ctx, hipMemcpyAsync(base0.p, ctx->e_A.p, slot * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    const int32_t T = tab_off[n_loops];
+    std::vector<FieldLoop> desc((size_t)n_loops);
+    for (int32_t l = 0; l < n_loops; ++l) desc[l] = FieldLoop{tab_off[l], tab_off[l + 1] - tab_off[l], radius[l]};
+    std::vector<double> pool(tab_times, tab_times + T);
+    pool.insert(pool.end(), tab_cx, tab_cx + T);
+    pool.insert(pool.end(), tab_cy, tab_cy + T);
+    pool.insert(pool.end(), tab_cz, tab_cz + T);
+    pool.insert(pool.end(), tab_current, tab_current + T);
+    HIP_TRY(ctx, d_desc.upload(desc));
+    HIP_TRY(ctx, d_tab.upload(pool));
+    if (ctx->d_terms.n == 0) {  // (k_ra_loops_begin reads no term, but is handed valid pointers)
+        HIP_TRY(ctx, ctx->d_terms.upload(std::vector<FieldTerm>(1, FieldTerm{})));
+        HIP_TRY(ctx, ctx->d_term_tab.upload(std::vector<double>(2, 0.0)));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (fresh) ctx->e_Tbase.take(base0);
+    ctx->e_centres.take(centres);
+    ctx->d_loops.take(d_desc);
+    ctx->d_loop_tab.take(d_tab);
+    ctx->loop.set_loops(n_loops, z_film, radius, tab_off, tab_times, tab_cx, tab_cy, tab_cz, tab_current);
+    return restart_sources(ctx);
+}
+
+static int update_link_loops(tdgl_ctx *ctx, const double *scales, const double *lp, double dt_prev) {
+    if (!ctx->loop.terms_step(scales, lp)) return TDGL_OK;  // (A and dA/dt = 0 are already in place)
+    TDGL_TRY(launch_loops_links(ctx, scales, lp, 1.0 / dt_prev));
+    return finish_links(ctx, true, dt_prev, true);
+}
+
+extern "C" int tdgl_update_link_loops(tdgl_ctx *ctx, const double *term_scales, const double *loop_params, double dt_prev) {
+    CTX_GUARD(ctx);
+    if (!ctx->loop.loops()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_loops first");
+    if (!loop_params || (ctx->loop.n_terms > 0 && !term_scales)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: null argument");
+    for (int k = 0; k < ctx->loop.n_terms; ++k)
+        if (!std::isfinite(term_scales[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: non-finite factor");
+    for (int l = 0; l < ctx->loop.n_loops; ++l) {
+        for (int j = 0; j < 4; ++j)
+            if (!std::isfinite(loop_params[4 * l + j])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: non-finite loop value");
+        if (loop_params[4 * l + 2] == ctx->loop.loop_zfilm)
+            TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: loop %d lies in the film's plane", l);
+    }
+    if (!(dt_prev > 0.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: dt_prev must be > 0");
+    TDGL_TRY(update_link_loops(ctx, term_scales, loop_params, dt_prev));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_get_link_loop_params(tdgl_ctx *ctx, int32_t *n_loops, double *params) {
+    if (!ctx || !n_loops || !params) return TDGL_ERR_ARG;
+    *n_loops = ctx->loop.loops() ? ctx->loop.n_loops : 0;
+    for (int l = 0; l < *n_loops; ++l)
+        for (int j = 0; j < 4; ++j) params[4 * l + j] = ctx->loop.loop_par[l][j];
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_get_link_exponents(tdgl_ctx *ctx, double *A) {
+    CTX_GUARD(ctx);
+    if (!A) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_get_link_exponents: null A");
+    if (!ctx->have_links) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_get_link_exponents: no links are set");
+    std::vector<double> tmp(2 * (size_t)ctx->m);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(tmp.data(), ctx->e_A.p, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < ctx->m; ++k) {
+        const int32_t e = ctx->edge_perm[k];
+        A[2 * e] = tmp[2 * k];
+        A[2 * e + 1] = tmp[2 * k + 1];
+    }
+    return TDGL_OK;
+}
+
 extern "C" int tdgl_get_link_term_moves(tdgl_ctx *ctx, int64_t *moves) {
     if (!ctx || !moves) return TDGL_ERR_ARG;
-    *moves = ctx->loop.terms() ? ctx->loop.term_moves : 0;
+    *moves = ctx->loop.terms() || ctx->loop.loops() ? ctx->loop.term_moves : 0;
     return TDGL_OK;
 }
 

@@ -211,6 +211,13 @@ struct FieldTerm {
     int32_t kind, off, n, pad;
     double ramp[4];
 };
+// Moving current loops on top of that field (tdgl_set_link_loops): A += I_l(t) Aloop(r - c_l(t); a_l) for at most this many
+// loops; a loop's four tables (centre x, y, z and current) share the nodes off .. off + n of the owner's pools
+constexpr int FIELD_LOOPS_MAX = 2;
+struct FieldLoop {
+    int32_t off, n;
+    double radius;
+};
 struct StepCtl {
     double tentative_dt;   // dt the next STEP starts from (solver.py:316-320, 698-707)
     double attempt_dt;     // dt of the next attempt: tentative_dt, times the multiplier per failed attempt of the step
@@ -241,6 +248,10 @@ struct StepCtl {
     int n_terms, term_a0;
     int n_term_moves, pad2;    // attempts of this batch that moved the sum (ran the body of the links kernel)
     double term_scale[FIELD_TERMS_MAX], term_scale_prev[FIELD_TERMS_MAX];
+    // ... plus moving current loops (k_ra_loops_begin; n_loops = 0: none): centre x, y, z and current of the current /
+    // previous A, loop by loop.  The step rule covers them with the factors; n_term_moves counts moves of the whole sum
+    int n_loops, pad3;
+    double loop_par[FIELD_LOOPS_MAX][4], loop_par_prev[FIELD_LOOPS_MAX][4];
 };
 struct StepRec {
     double dt, dmax;
@@ -276,6 +287,13 @@ struct LoopState {
     tdgl::FieldTerm term[tdgl::FIELD_TERMS_MAX] = {};
     std::vector<double> term_t[tdgl::FIELD_TERMS_MAX], term_v[tdgl::FIELD_TERMS_MAX];
     double term_scale[tdgl::FIELD_TERMS_MAX] = {0, 0, 0, 0}, term_scale_prev[tdgl::FIELD_TERMS_MAX] = {0, 0, 0, 0};
+    // ... plus n_loops moving current loops on top of the terms (n_terms > 0) or of a static A (n_terms = 0), set by
+    // tdgl_set_link_loops: per loop the radius and four piecewise-linear tables on shared nodes loop_t[l] -- centre x, y, z and
+    // current (loop_v[l][0 .. 3]); loop_par / loop_par_prev: those four values of the current / previous A
+    int n_loops = 0;
+    double loop_zfilm = 0.0, loop_radius[tdgl::FIELD_LOOPS_MAX] = {0, 0};
+    std::vector<double> loop_t[tdgl::FIELD_LOOPS_MAX], loop_v[tdgl::FIELD_LOOPS_MAX][4];
+    double loop_par[tdgl::FIELD_LOOPS_MAX][4] = {}, loop_par_prev[tdgl::FIELD_LOOPS_MAX][4] = {};
     // what absorb tells its caller about a batch.  corrupt: 1 impossible counts, 2 the records disagree with the controller
     // (the state is void); last_accepted: index of the last accepted record
     struct Batch {
@@ -292,12 +310,12 @@ struct LoopState {
     void new_state(int buffer) { cur = buffer, retries = 0; }  // a new psi in psi[buffer] (tdgl_set_state): no step is in progress
     void set_ramp(bool on, double tmin, double tmax, double initial, double final_) {
         ramp_on = on, ramp_tmin = tmin, ramp_tmax = tmax, ramp_initial = initial, ramp_final = final_;
-        tab_t.clear(), tab_v.clear(), n_terms = 0;
+        tab_t.clear(), tab_v.clear(), n_terms = 0, n_loops = 0;
     }
     void set_table(const double *times, const double *values, int64_t n) {  // n = 0: off
-        ramp_on = n > 0, tab_t.assign(times, times + n), tab_v.assign(values, values + n), n_terms = 0;
+        ramp_on = n > 0, tab_t.assign(times, times + n), tab_v.assign(values, values + n), n_terms = 0, n_loops = 0;
     }
-    void links_static() { ramp_on = false, tab_t.clear(), tab_v.clear(), n_terms = 0; }  // (a setter of static links: neither ramp, table nor terms)
+    void links_static() { ramp_on = false, tab_t.clear(), tab_v.clear(), n_terms = 0, n_loops = 0; }  // (a setter of static links: neither ramp, table, terms nor loops)
     bool tabulated() const { return ramp_on && !tab_t.empty(); }
     // the sum of terms in the place of ramp and table (validated by the caller: tdgl_set_link_terms); the factors start at
     // their values at t = 0
@@ -309,7 +327,14 @@ struct LoopState {
     double term_end_value(int k) const { return term[k].kind == tdgl::TERM_TABLE ? term_v[k].back() : term[k].ramp[3]; }
     // the step rule of the sum (update_link_scale's, term by term): false -- nothing moves, every factor equals its last two
     // evaluations and a dynamic update has run; true -- the factors are taken over (the caller moves the links)
-    bool terms_step(const double *s);
+    // (with loops: ... and every loop's four values lp[4 l ..] equal their last two evaluations)
+    bool terms_step(const double *s, const double *lp = nullptr);
+    // moving loops on top of the field in force (validated by the caller: tdgl_set_link_loops); the values start at t = 0.
+    // n = 0: the loops go, and with them ramp_on when no terms are left under them
+    void set_loops(int n, double z_film, const double *radius, const int32_t *tab_off, const double *times, const double *cx,
+                   const double *cy, const double *cz, const double *current);
+    bool loops() const { return ramp_on && n_loops > 0; }
+    void loop_values(int l, double t, double *out4) const;  // centre x, y, z and current of loop l at t (table_value)
     std::string budget_message(int replica, double dt) const;
     void report(int64_t *step, double *time_, double *runner_dt_, double *tentative) const;
     // the classic loop's step: its first attempt takes tentative_dt (solver.py:666-668); a step begun by the run-ahead loop and
@@ -324,10 +349,16 @@ struct LoopState {
     // potential is static for the rest of the stage: no dA/dt term, no per-step update, and the run-ahead loop can take over.
     // A table is constant from its last node on, at that node's value: the same rule.
     // A sum of terms is settled once the time has passed every term's end and every factor has been seen twice at its end value.
+    // Loops are settled once the time has passed every table's last node and their values have been seen twice there.
     bool ramp_settled() const {
-        if (terms()) {
+        if (terms() || loops()) {
             for (int k = 0; k < n_terms; ++k)
                 if (!(time >= term_end_time(k) && term_scale[k] == term_end_value(k) && term_scale_prev[k] == term_end_value(k))) return false;
+            for (int l = 0; l < n_loops; ++l) {
+                if (!(time >= loop_t[l].back())) return false;
+                for (int j = 0; j < 4; ++j)
+                    if (!(loop_par[l][j] == loop_v[l][j].back() && loop_par_prev[l][j] == loop_v[l][j].back())) return false;
+            }
             return true;
         }
         const double t_end = tabulated() ? tab_t.back() : ramp_tmax, f_end = tabulated() ? tab_v.back() : ramp_final;
@@ -603,6 +634,11 @@ struct tdgl_ctx {
     // edge-permuted; the terms' descriptors and their tables' nodes (all times, then all values) for k_ra_terms_begin
     tdgl::DevBuf<double> e_Tbase, d_term_tab;
     tdgl::DevBuf<tdgl::FieldTerm> d_terms;
+    // moving current loops (tdgl_set_link_loops): the edge centres (x, y per edge, edge-permuted), the loops' descriptors and
+    // their tables' nodes (all times, then all cx, cy, cz, currents) for k_ra_loops_begin.  Under loops e_Tbase always holds
+    // slot 0 (the static A they were added to when there are no terms)
+    tdgl::DevBuf<double> e_centres, d_loop_tab;
+    tdgl::DevBuf<tdgl::FieldLoop> d_loops;
     tdgl::DevBuf<double> d_tab_eps_t, d_tab_eps_f;   // the epsilon factor's table on the device (k_ra_eps_table)
     bool tab_eps_on_device = false;
     std::vector<double> tab_eps_t, tab_eps_f;

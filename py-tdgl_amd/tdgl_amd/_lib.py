@@ -341,6 +341,11 @@ SIGNATURES = {
     "tdgl_update_link_terms": (C.c_int, [_CTX, c_f64p, C.c_double]),
     "tdgl_get_link_term_scales": (C.c_int, [_CTX, c_i32p, c_f64p]),
     "tdgl_get_link_term_moves": (C.c_int, [_CTX, C.POINTER(C.c_int64)]),
+    "tdgl_set_link_loops": (
+        C.c_int, [_CTX, C.c_int32, c_f64p, C.c_double, c_f64p, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "tdgl_update_link_loops": (C.c_int, [_CTX, c_f64p, c_f64p, C.c_double]),
+    "tdgl_get_link_loop_params": (C.c_int, [_CTX, c_i32p, c_f64p]),
+    "tdgl_get_link_exponents": (C.c_int, [_CTX, c_f64p]),
     "tdgl_update_link_exponents": (C.c_int, [_CTX, c_f64p, C.c_double]),
     "tdgl_set_epsilon": (C.c_int, [_CTX, c_f64p]),
     "tdgl_set_mu_boundary": (C.c_int, [_CTX, c_f64p]),

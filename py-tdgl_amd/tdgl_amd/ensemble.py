@@ -95,12 +95,15 @@ def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
     """Time dependence the ensemble evaluates on the device passes: a separable A whose factor is a LinearRamp or a
     TabulatedRamp, a sum of a static field and such products, TabulatedCurrents, a SeparableEpsilon.  Anything else
     raises."""
-    if rep.dynamic_vector_potential and not rep.device_evaluates_field():
+    if rep.dynamic_vector_potential and (not rep.device_evaluates_field() or getattr(rep, "_A_loops", None)):
         form = ("LinearRamp(...) * (static field), TabulatedRamp(...) * (static field), or a sum (static field) + f_1 * "
                 f"(static field) + ... of up to {FIELD_TERMS_MAX} such products")
         if rep._A_base is not None:
             raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
                              f"{form}; this one's time factor is not a LinearRamp or a TabulatedRamp.")
+        if getattr(rep, "_A_loops", None):
+            raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
+                             f"{form}; a MovingCurrentLoop is evaluated on the device by solve() alone, not per replica.")
         raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
                          f"{form}; this one is not of that form.")
     if rep.dynamic_currents and rep._current_table is None:

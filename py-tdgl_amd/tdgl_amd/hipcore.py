@@ -116,6 +116,48 @@ def link_terms_args(m: int, A0, terms) -> tuple:
             p_f64(values))
 
 
+FIELD_LOOPS_MAX = 2  # TDGL_FIELD_LOOPS_MAX
+
+
+def link_loops_args(m: int, edge_centres, z_film, loops) -> tuple:
+    """``(n_loops, edge_centres, z_film, radius, tab_off, tab_times, tab_cx, tab_cy, tab_cz, tab_current)`` of
+    tdgl_set_link_loops from ``edge_centres`` [m, 2], the film's height and ``loops``: a list of ``dict(times, centers
+    [n, 3], currents [n], radius)`` -- every length in the units of ``edge_centres``, the currents with mu_0, the units
+    and the solver's scale folded in.  Shapes, the number of loops and a loop's plane meeting the film's are refused
+    here with ``ValueError``; the library checks the values once more."""
+    loops = list(loops)
+    if not 1 <= len(loops) <= FIELD_LOOPS_MAX:
+        raise ValueError(f"between 1 and {FIELD_LOOPS_MAX} moving loops, got {len(loops)}.")
+    ec = f64(edge_centres)
+    if ec.shape != (m, 2):
+        raise ValueError(f"Unexpected shape for the edge centres: {ec.shape}.")
+    z_film = float(z_film)
+    off = np.zeros(len(loops) + 1, dtype=np.int32)
+    radius = np.zeros(len(loops))
+    tt, cc, ii = [], [], []
+    for k, lp in enumerate(loops):
+        t = f64(np.atleast_1d(lp["times"]))
+        c = f64(lp["centers"])
+        cur = f64(np.asarray(lp["currents"], dtype=float) * np.ones(len(t)))
+        if t.ndim != 1 or len(t) < 1 or c.shape != (len(t), 3) or cur.shape != t.shape:
+            raise ValueError("a moving loop needs times [n], centers [n, 3] and currents [n] (or one number).")
+        if np.any(np.diff(t) <= 0):
+            raise ValueError("MovingCurrentLoop: times must increase strictly")
+        side = c[:, 2] - z_film
+        if np.any(side == 0) or np.any(side * side[0] < 0):
+            raise ValueError("MovingCurrentLoop: the loop's plane must differ from the film's (centre z != layer z0, on "
+                             "one side of it) at every node.")
+        if not float(lp["radius"]) > 0:
+            raise ValueError("MovingCurrentLoop: radius must be > 0.")
+        radius[k] = float(lp["radius"])
+        off[k + 1] = off[k] + len(t)
+        tt.append(t), cc.append(c), ii.append(cur)
+    times, cen, cur = f64(np.concatenate(tt)), np.concatenate(cc), f64(np.concatenate(ii))
+    cols = [f64(cen[:, j]) for j in range(3)]
+    return (len(loops), p_f64(ec), z_film, p_f64(radius), p_i32(off), p_f64(times), p_f64(cols[0]), p_f64(cols[1]), p_f64(cols[2]),
+            p_f64(cur))
+
+
 def controller_struct(dt_init, dt_max, adaptive, adaptive_window, max_solve_retries,
                       adaptive_time_step_multiplier) -> "_lib.Controller":
     return _lib.Controller(float(dt_init), float(dt_max), int(bool(adaptive)), int(adaptive_window),
@@ -1239,6 +1281,32 @@ class TDGLContext:
         v = C.c_int64(0)
         self._chk(self._lib.tdgl_get_link_term_moves(self._ctx, C.byref(v)))
         return v.value
+
+    def set_link_loops(self, edge_centres, z_film, loops):
+        """Add moving current loops to the field in force (a static A or a sum of terms): ``run`` evaluates their
+        centres and currents itself before every step (`link_loops_args`).  ``loops`` empty or None: remove them."""
+        if not loops:
+            self._chk(self._lib.tdgl_set_link_loops(self._ctx, 0, None, 0.0, None, None, None, None, None, None, None))
+            return
+        self._chk(self._lib.tdgl_set_link_loops(self._ctx, *link_loops_args(self.m, edge_centres, z_film, loops)))
+
+    def update_link_loops(self, term_scales, loop_params, dt_prev):
+        """Move the field to the K factors and the loops' ``[L, 4]`` values (cx, cy, cz, current) now."""
+        ts = f64(np.atleast_1d(term_scales)) if term_scales is not None and len(term_scales) else np.zeros(1)
+        lp = f64(np.asarray(loop_params, dtype=float).reshape(-1))
+        self._chk(self._lib.tdgl_update_link_loops(self._ctx, p_f64(ts), p_f64(lp), float(dt_prev)))
+
+    def link_loop_params(self):
+        """``[L, 4]``: centre x, y, z and current of every moving loop in the current A (empty: none are set)."""
+        n, v = C.c_int32(0), np.zeros(4 * FIELD_LOOPS_MAX)
+        self._chk(self._lib.tdgl_get_link_loop_params(self._ctx, C.byref(n), p_f64(v)))
+        return v[:4 * n.value].reshape(n.value, 4)
+
+    def link_exponents(self):
+        """The applied vector potential ``A[m, 2]`` in force on the device, whatever set it."""
+        A = np.zeros((self.m, 2))
+        self._chk(self._lib.tdgl_get_link_exponents(self._ctx, p_f64(A)))
+        return A
 
     def set_epsilon(self, eps):
         eps = f64(np.broadcast_to(eps, (self.n,)))

@@ -101,6 +101,7 @@ class Parameter:
         self.uniform_in_space = False
         self.ramp = None  # LinearRamp: dict(tmin, tmax, initial, final)
         self.table = None  # TabulatedRamp: its PiecewiseLinear
+        self.loop = None  # MovingCurrentLoop: dict(times, centers, currents, radius, unit_factor)
 
     def separable_product(self):
         """``(f, static)`` if this parameter is ``f(t) * static(x, y, z)`` with ``f`` uniform in
@@ -113,6 +114,14 @@ class Parameter:
         `CompositeParameter.separable_terms`), else ``None``.  A parameter that does not depend on time is the sum
         without products: ``(self, [])``."""
         return None if self.time_dependent else (self, [])
+
+    def device_sources(self):
+        """``(static_or_None, terms, loops)`` if this parameter is a sum of a static part, products the time loop
+        evaluates (`separable_terms`) and `MovingCurrentLoop` leaves (see `CompositeParameter.device_sources`), else
+        ``None``.  A `MovingCurrentLoop` by itself is ``(None, [], [its .loop])``."""
+        if not self.time_dependent:
+            return self, [], []
+        return (None, [], [dict(self.loop)]) if getattr(self, "loop", None) is not None else None
 
     def scalar(self, t) -> float:
         """Value of a uniform-in-space factor at time ``t``."""
@@ -266,6 +275,21 @@ class CompositeParameter(Parameter):
             static = leaf if static is None else static + leaf
         return static, terms
 
+    def device_sources(self):
+        """`separable_terms` with moving loops: ``(A_0 or None, [(f_k, A_k), ...], [loop_1, ...])`` for a tree built from
+        ``+`` and ``-`` whose leaves are what `separable_terms` accepts or a `MovingCurrentLoop`; each loop is its
+        ``.loop`` dictionary, with the currents negated where the leaf is subtracted.  ``terms`` may be empty when
+        ``loops`` is not.  ``None`` when anything else appears -- a loop times a ramp, for one --, for more than
+        ``FIELD_TERMS_MAX`` products or more than ``FIELD_LOOPS_MAX`` loops.  The time loop evaluates the form as the
+        terms' sum, left to right, then the loops in the order they appear (`tdgl_set_link_loops`)."""
+        statics, terms, loops = [], [], []
+        if not _collect_terms(self, 1, statics, terms, loops) or len(terms) > FIELD_TERMS_MAX or len(loops) > FIELD_LOOPS_MAX:
+            return None
+        static = None
+        for leaf in statics:
+            static = leaf if static is None else static + leaf
+        return static, terms, loops
+
     def __call__(self, x, y, z=None, t=None):
         values = []
         for v in (self.left, self.right):
@@ -302,19 +326,24 @@ class CompositeParameter(Parameter):
 
 
 FIELD_TERMS_MAX = 4  # products in a sum the time loop evaluates itself (TDGL_FIELD_TERMS_MAX)
+FIELD_LOOPS_MAX = 2  # moving current loops on top of them (TDGL_FIELD_LOOPS_MAX)
 
 
-def _collect_terms(p, sign: int, statics: list, terms: list) -> bool:
+def _collect_terms(p, sign: int, statics: list, terms: list, loops: Optional[list] = None) -> bool:
     """The leaves of the ``+`` / ``-`` tree under ``p`` into ``statics`` and ``terms`` (``separable_terms``), each with
-    the sign it enters the sum with; False: the tree holds something the form does not cover."""
+    the sign it enters the sum with; False: the tree holds something the form does not cover.  With ``loops`` a list
+    (``device_sources``) a `MovingCurrentLoop` leaf goes there, its currents carrying the sign."""
     if not isinstance(p, Parameter):
         return False
     signed = (lambda q: q) if sign > 0 else (lambda q: -q)  # noqa: E731
     if isinstance(p, CompositeParameter) and p.operator in (operator.add, operator.sub):
         right = sign if p.operator is operator.add else -sign
-        return _collect_terms(p.left, sign, statics, terms) and _collect_terms(p.right, right, statics, terms)
+        return _collect_terms(p.left, sign, statics, terms, loops) and _collect_terms(p.right, right, statics, terms, loops)
     if not p.time_dependent:
         statics.append(signed(p))
+        return True
+    if loops is not None and getattr(p, "loop", None) is not None and not isinstance(p, CompositeParameter):
+        loops.append(dict(p.loop, currents=sign * p.loop["currents"]))
         return True
     sep = p.separable_product()
     if sep is None or (sep[0].ramp is None and getattr(sep[0], "table", None) is None):
@@ -377,6 +406,120 @@ def Scale(func, **kwargs) -> Parameter:
     (`tdgl/sources/scaling.py:43-54`)."""
     kwargs["time_dependent"] = True
     return Parameter(func, **kwargs)
+
+
+# ---- current loops (tdgl/sources/loop.py), static and moving ------------------------------------------------------------
+LOOP_AGM_STEPS = 6  # halvings of the arithmetic-geometric mean: double precision down to 1 - m = 2e-9
+
+
+def loop_potential_factor(dx, dy, dz, radius):
+    """``H = G / rho`` of a circular loop of ``radius`` at the in-plane offsets ``dx, dy`` from its axis and the height
+    ``dz != 0`` above its plane, so that ``A = mu_0 I H (-dy, dx)``.  ``G = ((2 - m) K(m) - 2 E(m)) d / (4 pi rho)`` with
+    ``d^2 = (a + rho)^2 + dz^2``, ``m = 4 a rho / d^2`` is dimensionless and evaluated as the time loop's kernel does
+    (`tdgl_set_link_loops`): ``(2 - m) K - 2 E = K sum_n 2^n c_n^2`` over the differences ``c_n`` of the
+    arithmetic-geometric mean, every term positive, ``sqrt(1 - m)`` formed without ``1 - m``, ``c_0 / rho`` carried so
+    that nothing is divided by ``rho``.  No elliptic integrals from a library, no angles."""
+    dx, dy, dz = np.broadcast_arrays(np.asarray(dx, dtype=float), np.asarray(dy, dtype=float), np.asarray(dz, dtype=float))
+    if np.any(dz == 0.0):
+        raise ValueError("The loop's plane must differ from the plane of the points (z != loop z): the potential is "
+                         "singular on the wire.")
+    a = float(radius)
+    rho = np.sqrt(dx * dx + dy * dy)
+    z2, sp, sm = dz * dz, a + rho, a - rho
+    d2 = sp * sp + z2
+    b0 = np.sqrt((sm * sm + z2) / d2)
+    ob = 1.0 + b0
+    cr = (2.0 * a) / (d2 * ob)
+    c = cr * rho
+    an, bn, sr, p = 0.5 * ob, np.sqrt(b0), 2.0 * (cr * cr), 4.0
+    with np.errstate(under="ignore"):
+        for _ in range(LOOP_AGM_STEPS):
+            a1 = 0.5 * (an + bn)
+            bn = np.sqrt(an * bn)
+            q = c / (4.0 * a1)
+            cr, c = cr * q, c * q
+            sr = sr + p * (cr * cr)
+            p, an = p * 2.0, a1
+    return (sr * np.sqrt(d2)) / (8.0 * an)
+
+
+def loop_unit_factor(current_units: str, field_units: str, length_units: str) -> float:
+    """``mu_0 I`` of a current of 1 ``current_units`` in ``field_units * length_units``."""
+    from .device import CURRENT_UNITS, FIELD_UNITS, LENGTH_UNITS, MU_0, _unit
+
+    return MU_0 * _unit(CURRENT_UNITS, current_units, "current") / (
+        _unit(FIELD_UNITS, field_units, "field") * _unit(LENGTH_UNITS, length_units, "length"))
+
+
+def _loop_potential(x, y, z, center, radius, amplitude):
+    dx, dy = x - center[0], y - center[1]
+    h = amplitude * loop_potential_factor(dx, dy, np.broadcast_to(z, np.shape(x)) - center[2], radius)
+    return np.stack([-(dy * h), dx * h, np.zeros_like(h)], axis=1)
+
+
+def loop_vector_potential(x, y, z, *, current, radius, center=(0, 0, 0), current_units="uA", field_units="mT",
+                          length_units="um"):
+    """``[n, 3]`` vector potential of a loop of current in ``field_units * length_units`` (`tdgl/sources/loop.py:9-33`)."""
+    return _loop_potential(x, y, z, center, radius, current * loop_unit_factor(current_units, field_units, length_units))
+
+
+def CurrentLoop(*, current: float, radius: float, center, current_units: str = "uA", field_units: str = "mT",
+                length_units: str = "um") -> Parameter:
+    """Vector potential of a circular loop of ``radius`` carrying ``current``, centred at ``center = (x, y, z)`` in a
+    plane parallel to the film, in ``field_units * length_units`` (`tdgl/sources/loop.py:36-69`: the reference's
+    signature and units).
+
+    It deviates from the reference's values on purpose: the reference evaluates ``-(mu_0 I a / (pi m)) ((m - 2) K(m) +
+    2 E(m)) / sqrt(denom)``, which cancels catastrophically for small ``m`` -- far from the loop and near its axis it has
+    no correct digit below ``m ~ 1e-6``, and on the axis it is NaN.  Here the value is finite and correct everywhere off
+    the wire, and exactly zero on the axis (`loop_potential_factor`).  The loop's plane must differ from the plane of
+    the points, else ``ValueError``.  Static, so ``LinearRamp(...) * CurrentLoop(...)`` and ``ConstantField(b) +
+    TabulatedRamp(...) * CurrentLoop(...)`` go to the device as terms."""
+    loop_unit_factor(current_units, field_units, length_units)  # (unknown units are refused here)
+    center = tuple(float(v) for v in center)
+    if len(center) != 3:
+        raise ValueError("center must be (x, y, z).")
+    if not float(radius) > 0:
+        raise ValueError("radius must be > 0.")
+    return Parameter(loop_vector_potential, current=current, radius=radius, center=center, current_units=current_units,
+                     field_units=field_units, length_units=length_units)
+
+
+def moving_loop_vector_potential(x, y, z, *, t, times, centers, currents, radius, current_units="uA", field_units="mT",
+                                 length_units="um"):
+    """`loop_vector_potential` of the loop whose centre and current are piecewise linear in ``t`` on the nodes ``times``
+    (constant outside)."""
+    c = [float(np.interp(t, times, centers[:, j])) for j in range(3)]
+    cur = float(np.interp(t, times, currents))
+    return _loop_potential(x, y, z, c, radius, cur * loop_unit_factor(current_units, field_units, length_units))
+
+
+def MovingCurrentLoop(times, centers, *, radius: float, current, current_units: str = "uA", field_units: str = "mT",
+                      length_units: str = "um") -> Parameter:
+    """A `CurrentLoop` that moves: ``A(r, t) = I(t) A_loop(r - c(t); radius)`` -- a susceptometer's field coil, a
+    SQUID-on-tip or a magnetised tip scanned across the film, with or without a current waveform.  ``centers``
+    ``[n_nodes, 3]`` and ``current`` (a number or ``[n_nodes]``) are piecewise linear in ``t`` on the shared ``times``
+    and constant outside.  The loop's plane must stay on one side of the film.
+
+    Called as a function it evaluates on the host.  Alone or in a sum with static fields, ramped or tabulated products
+    and one more loop (`Parameter.device_sources`) the time loop evaluates it on the device (`tdgl_set_link_loops`): no
+    Python call, no upload per step.  ``.loop`` holds ``dict(times, centers, currents, radius, unit_factor)``."""
+    nodes = PiecewiseLinear(times, np.zeros(np.shape(times)))  # (its checks: one-dimensional, strictly increasing)
+    centers = np.array(centers, dtype=float)
+    if centers.shape != (len(nodes.times), 3):
+        raise ValueError(f"centers must have shape (n_nodes, 3) = ({len(nodes.times)}, 3), got {centers.shape}.")
+    currents = np.array(current, dtype=float) * np.ones(len(nodes.times)) if np.ndim(current) == 0 else np.array(current, dtype=float)
+    if currents.shape != nodes.times.shape:
+        raise ValueError(f"current must be a number or have shape (n_nodes,) = {nodes.times.shape}, got {currents.shape}.")
+    if not (np.all(np.isfinite(centers)) and np.all(np.isfinite(currents)) and np.all(np.isfinite(nodes.times))):
+        raise ValueError("times, centers and current must be finite.")
+    if not float(radius) > 0:
+        raise ValueError("radius must be > 0.")
+    p = Parameter(moving_loop_vector_potential, times=nodes.times, centers=centers, currents=currents, radius=float(radius),
+                  current_units=current_units, field_units=field_units, length_units=length_units, time_dependent=True)
+    p.loop = dict(times=nodes.times, centers=centers, currents=currents, radius=float(radius),
+                  unit_factor=loop_unit_factor(current_units, field_units, length_units))
+    return p
 
 
 # ---- tabulated time dependence, evaluated on the device ------------------------------------------

@@ -4,7 +4,7 @@ once for ``TDGLSolver.solve`` and ``EnsembleSolver``.
 `RunRecord` holds what one run accumulates and owns the loop's rules; a driver asks it how many steps to take
 (`RunRecord.request`), has the library take them and hands the result back (`RunRecord.absorb`).  The record talks to the
 device through a *state source* -- ``begin_stage()``, ``loop_state()``, ``get_state(supercurrent=, normal_current=)``,
-``link_scale()``, ``link_term_scales()`` and, with screening, ``induced_vector_potential()``: `hipcore.TDGLContext` as it is, or one replica of
+``link_scale()``, ``link_term_scales()``, ``link_exponents()`` (with moving loops) and, with screening, ``induced_vector_potential()``: `hipcore.TDGLContext` as it is, or one replica of
 an ensemble (`ensemble._Replica`) -- and reads the run's inputs from the ``TDGLSolver`` that set them up.  Nothing here
 needs the library, so a scripted source can replay a recorded run through either driver.
 """
@@ -49,7 +49,9 @@ def save_step(source, solver, rec: "RunRecord", final: bool = False) -> None:
         st = source.get_state()
         js, jn = st["supercurrent"], st["normal_current"]
     a_ind = source.induced_vector_potential() if solver.screening is not None else None
-    if getattr(solver, "_A_terms", None) is not None:  # A_applied of the last step taken, from the factors the time loop evaluated
+    if getattr(solver, "_A_loops", None):  # moving loops: the device's own A -- what is saved is what was applied
+        solver.current_A_applied = source.link_exponents()
+    elif getattr(solver, "_A_terms", None) is not None:  # A_applied of the last step taken, from the factors the time loop evaluated
         solver.current_A_applied = solver.terms_value(source.link_term_scales())
     elif solver._A_base is not None:  # A_applied of the last step taken (the links may lag behind it)
         solver.current_A_applied = source.link_scale() * solver._A_base

@@ -116,14 +116,30 @@ class TDGLSolver:
         self.A_scale = device.field_scale(options.field_units)
         ex, ey = self.edge_centers[:, 0], self.edge_centers[:, 1]
         self.vector_potential_func = None
-        self._A_base = self._A_factor = self._A_ramp = self._A_table = self._A_terms = None
+        self._A_base = self._A_factor = self._A_ramp = self._A_table = self._A_terms = self._A_loops = None
         sep = applied_vector_potential.separable_product() if (
             self.dynamic_vector_potential and hasattr(applied_vector_potential, "separable_product")) else None
         # (a single product with no static part keeps its own path, call for call; anything else that is a sum of a static
         # field and such products goes to the device as terms)
         terms = applied_vector_potential.separable_terms() if (
             sep is None and self.dynamic_vector_potential and hasattr(applied_vector_potential, "separable_terms")) else None
-        if terms is not None and terms[1]:
+        # (... and with MovingCurrentLoop leaves in the sum, the loops ride on top of the terms or of the static part)
+        sources = applied_vector_potential.device_sources() if (
+            sep is None and terms is None and self.dynamic_vector_potential and hasattr(applied_vector_potential, "device_sources")) else None
+        if sources is not None and sources[2]:
+            static, products, loops = sources
+            on_edges = lambda q: self.A_scale * np.asarray(q(ex, ey, self.z0))[:, :2]  # noqa: E731
+            if products:
+                self._set_terms(None if static is None else on_edges(static),
+                                [(on_edges(q), f.ramp if f.ramp is not None else (f.table.times, f.table.values)) for f, q in products])
+                A0 = None
+            else:
+                A0 = np.zeros_like(self.edge_centers) if static is None else on_edges(static)
+            self._set_loops(A0, [dict(times=lp["times"], centers=lp["centers"], radius=lp["radius"],
+                                      currents=self.A_scale * lp["unit_factor"] * lp["currents"]) for lp in loops],
+                            self.edge_centers, float(device.layer.z0))
+            A = self.vector_potential_func(0)
+        elif terms is not None and terms[1]:
             # A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K with ramps and tables as factors: everything stays on the device,
             # tdgl_run evaluates the factors itself (tdgl_set_link_terms)
             static, products = terms
@@ -235,7 +251,7 @@ class TDGLSolver:
                            current_func=None, probe_points=None, device=None,
                            vector_potential_func=None, epsilon_func=None,
                            screening=None, vector_potential_ramp=None, vector_potential_table=None,
-                           vector_potential_terms=None) -> "TDGLSolver":
+                           vector_potential_terms=None, vector_potential_loops=None) -> "TDGLSolver":
         """Build a solver directly from dimensionless inputs -- the arrays the reference's
         ``__init__`` ends up with (solver.py:185, 214, 225, 254-256): ``A[m, 2]``,
         ``epsilon[n]``, ``TerminalInfo`` records and ``t -> {name: dimensionless current}``.
@@ -248,7 +264,11 @@ class TDGLSolver:
         values)`` for ``A(t) = TabulatedRamp(times, values)(t) * A_base``, evaluated by the library in the same way; a
         ramp and a table exclude each other.  ``vector_potential_terms``: ``(A0[m, 2] or None, [(A_k[m, 2], spec_k),
         ...])`` for the sum ``A(t) = A0 + f_1(t) A_1 + ... + f_K(t) A_K`` with ``spec_k`` a ramp's dict or a table's
-        ``(times, values)``, evaluated by the library as well; it excludes the ramp and the table."""
+        ``(times, values)``, evaluated by the library as well; it excludes the ramp and the table.
+        ``vector_potential_loops``: a list of up to two ``dict(radius=, times=, centers=[n, 3] (or z= with centers
+        [n, 2]), currents=)`` for moving current loops on top of ``vector_potential_terms`` or, without terms, of
+        ``link_exponents`` (then the static part): lengths in the mesh's units, the film at z = 0, the currents with
+        mu_0, the units and the field scale folded in (`tdgl_set_link_loops`); it excludes the ramp and the table too."""
         self = object.__new__(cls)
         options.validate()
         self.device = device
@@ -263,7 +283,7 @@ class TDGLSolver:
         self.disorder_epsilon = epsilon
         # optional time dependence: t -> A[m, 2] / t -> epsilon[n], already dimensionless
         self.vector_potential_func = vector_potential_func
-        self._A_base = self._A_factor = self._A_ramp = self._A_table = self._A_terms = None
+        self._A_base = self._A_factor = self._A_ramp = self._A_table = self._A_terms = self._A_loops = None
         if vector_potential_ramp is not None and vector_potential_table is not None:
             raise ValueError("vector_potential_ramp and vector_potential_table exclude each other.")
         if vector_potential_terms is not None:
@@ -271,6 +291,22 @@ class TDGLSolver:
                 raise ValueError("vector_potential_terms excludes vector_potential_ramp and vector_potential_table.")
             self._set_terms(*vector_potential_terms)
             vector_potential_func = self.vector_potential_func
+        if vector_potential_loops:
+            if vector_potential_ramp is not None or vector_potential_table is not None:
+                raise ValueError("vector_potential_loops excludes vector_potential_ramp and vector_potential_table.")
+            loops = []
+            for lp in vector_potential_loops:
+                c = np.asarray(lp["centers"], dtype=float)
+                if c.ndim == 2 and c.shape[1] == 2:
+                    c = np.column_stack([c, float(lp["z"]) * np.ones(len(c))])
+                loops.append(dict(times=np.asarray(lp["times"], dtype=float), centers=c, radius=float(lp["radius"]),
+                                  currents=np.asarray(lp["currents"], dtype=float) * np.ones(len(c))))
+            static = np.zeros((self.num_edges, 2)) if link_exponents is None else np.asarray(link_exponents, dtype=float)
+            self._set_loops(None if self._A_terms is not None else static, loops,
+                            mesh.edge_mesh.centers, 0.0)
+            vector_potential_func = self.vector_potential_func
+            if self._A_terms is not None or link_exponents is None:
+                link_exponents = vector_potential_func(0.0)
         if vector_potential_ramp is not None or vector_potential_table is not None:
             from .parameter import LinearRamp, TabulatedRamp
 
@@ -334,6 +370,28 @@ class TDGLSolver:
         self._A_term_factors = factors
         self.vector_potential_func = lambda t: self.terms_value([f(t) for f in factors])
 
+    def _set_loops(self, A0, loops, edge_centres, z_film) -> None:
+        """Moving loops on top of the terms set before (``A0`` None) or of the static ``A0[m, 2]``: ``loops`` a list of
+        ``dict(times, centers[n, 3], currents[n], radius)`` in the units of ``edge_centres``, currents dimensionless."""
+        from .hipcore import link_loops_args
+        from .parameter import _loop_potential
+
+        edge_centres = np.asarray(edge_centres, dtype=float)
+        link_loops_args(len(edge_centres), edge_centres, z_film, loops)  # (its refusals, before any device work)
+        self._A_loops = (edge_centres, float(z_film), list(loops))
+        self._A_static = None if A0 is None else np.asarray(A0, dtype=float)
+        under = self.vector_potential_func if self._A_terms is not None else (lambda t: self._A_static)
+        ex, ey = edge_centres[:, 0], edge_centres[:, 1]
+
+        def vector_potential_func(t):  # the host's evaluation: the per-step path and any other consumer
+            A = under(t)
+            for lp in loops:
+                c = [float(np.interp(t, lp["times"], lp["centers"][:, j])) for j in range(3)]
+                A = A + _loop_potential(ex, ey, z_film, c, lp["radius"], float(np.interp(t, lp["times"], lp["currents"])))[:, :2]
+            return A
+
+        self.vector_potential_func = vector_potential_func
+
     def terms_value(self, scales) -> np.ndarray:
         """``((A0 + s_1 A_1) + s_2 A_2) + ...`` left to right, every product rounded before it is added (NumPy does not
         contract): the device's value for the same factors, bit for bit."""
@@ -388,8 +446,13 @@ class TDGLSolver:
                 self.ctx.set_link_ramp(**self._A_ramp)
             elif self._A_table is not None:
                 self.ctx.set_link_table(*self._A_table)
+        elif self._A_loops is not None:
+            self.operators.set_link_exponents(self._A_static)
         else:
             self.operators.set_link_exponents(self.current_A_applied)
+        if self._A_loops is not None:
+            self.ctx.set_link_loops(*self._A_loops)
+            self.current_A_applied = self.ctx.link_exponents()
 
         # ---- initial values (solver.py:284-289): _setup_host ----------------------------------------
         self.ctx.set_epsilon(self.epsilon)
@@ -457,8 +520,9 @@ class TDGLSolver:
 
     def device_evaluates_field(self) -> bool:
         """A(t) = f(t) * A_base with f a LinearRamp or a TabulatedRamp, or a sum of a static field and such products
-        (`Parameter.separable_terms`): the time loop evaluates the factors itself."""
-        return self._A_ramp is not None or self._A_table is not None or self._A_terms is not None
+        (`Parameter.separable_terms`), with or without moving current loops (`Parameter.device_sources`): the time loop
+        evaluates the factors and the loops' centres and currents itself."""
+        return self._A_ramp is not None or self._A_table is not None or self._A_terms is not None or self._A_loops is not None
 
     def device_evaluates_epsilon(self) -> bool:
         """epsilon(t) is a table the time loop evaluates itself (tdgl_set_epsilon_table); the host keeps a copy."""
@@ -520,7 +584,9 @@ class TDGLSolver:
         else:
             a_ind = np.zeros((self.num_edges, 2)) if induced_vector_potential is None else induced_vector_potential
         extra = []
-        if self._A_terms is not None:
+        if self._A_loops is not None:
+            self.current_A_applied = ctx.link_exponents()
+        elif self._A_terms is not None:
             self.current_A_applied = self.terms_value(ctx.link_term_scales())
         elif self._A_base is not None:
             self.current_A_applied = ctx.link_scale() * self._A_base
