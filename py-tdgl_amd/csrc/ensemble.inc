@@ -200,74 +200,43 @@ __global__ void k_ens_probes(int n_probe, const int32_t *__restrict__ sites, con
 }
 
 // ---- time-dependent inputs per replica, queued in front of K1 (run.inc's run-ahead loop, the replica as grid.y) ----
-// A replica's field ramp A(t) = LinearRamp(t) A_base, or its field table A(t) = table(t) A_base, moves in three launches
-// over the ramping replicas -- R1 ramp begin (ramp_begin_body / table_begin_body), R2 A, A_prev, dA/dt and "did it
-// move" (ramp_link_body), R3 ceff with the dA/dt term and
+// A replica's moving applied field (FieldDrive: a single ramped or tabulated product, or a sum of terms) moves in three
+// launches over the replicas -- R1 the step rule (field_begin_body), R2 A, A_prev, dA/dt and "did it move" (field_link_body),
+// R3 ceff with the dA/dt term and
 // the link variables (ceff_body, link_variable_body) -- and two more rebuild what depends on the links: R4 the
 // covariant-Laplacian values (fill_laplacian_body) and R5 L psi^n with them (psi_laplacian_body).  Retries, dead
-// replicas and replicas whose ramp does not move this step return at once (ramp_do, moved).  Tabulated terminal
+// replicas and replicas whose field does not move this step return at once (ramp_do, moved).  Tabulated terminal
 // currents (T1, mu_table_body: one workgroup per replica) and separable epsilon (T2, eps_table_body) are evaluated at
 // the replica's own time.  Every body is the single run's, so each replica's arithmetic is its run-ahead loop's.
 
-// R1: one thread per replica.  kind[r] says where the replica's factor comes from in this batch: LINK_RAMP the ramp in its
-// controller (ramp_begin_body), LINK_TABLE its table (table_begin_body: nodes l_off[r] .. l_off[r + 1] of the pools),
-// LINK_NONE nothing moves: ramp_do = 0, as the single run that queues no ramp launch at all
-enum : int32_t { LINK_NONE = 0, LINK_RAMP = 1, LINK_TABLE = 2, LINK_TERMS = 3 };  // (LINK_TERMS: R1t, R2t below)
-__global__ void k_ens_ramp_begin(int R, StepCtl *__restrict__ ctl, const int32_t *__restrict__ kind, const int32_t *__restrict__ l_off,
-                                 const double *__restrict__ times, const double *__restrict__ values, int32_t *__restrict__ moved) {
+// R1: one thread per replica.  move[r]: the replica's field moves in this batch (else ramp_do = 0, as the single run that
+// queues no field launch at all).  term: FIELD_TERMS_MAX descriptors per replica whose table nodes are offsets into the pools
+__global__ void k_ens_field_begin(int R, StepCtl *__restrict__ ctl, const int32_t *__restrict__ move, const FieldTerm *__restrict__ term,
+                                  const double *__restrict__ times, const double *__restrict__ values, int32_t *__restrict__ moved) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
-    const int32_t k = kind[r];
-    const int t0 = l_off[r], nn = l_off[r + 1] - t0;
-    if (k == LINK_RAMP)
-        ramp_begin_body(ctl + r);
-    else if (k == LINK_TABLE && nn > 0)
-        table_begin_body(ctl + r, times + t0, values + t0, nn);
+    if (move[r])
+        field_begin_body(ctl + r, term + (int64_t)r * FIELD_TERMS_MAX, times, values, nullptr, nullptr, 0);
     else
         ctl[r].ramp_do = 0;
     moved[r] = 0;
 }
 
-// R2: moved[r] = OR over the replica's workgroups (k_ra_ramp_links + k_any_flag)
-__global__ __launch_bounds__(BLOCK) void k_ens_ramp_links(int64_t m, int64_t m_pad, const double *__restrict__ base, double *__restrict__ A,
-                                                          double *__restrict__ Aprev, const double *__restrict__ dx,
-                                                          const double *__restrict__ dy, const double *__restrict__ inv_len,
-                                                          double *__restrict__ dadt, int32_t *__restrict__ moved,
-                                                          const StepCtl *__restrict__ ctl) {
-    const int r = blockIdx.y;
-    const StepCtl *c = ctl + r;
-    if (!c->ramp_do) return;
-    const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x, o2 = 2 * (int64_t)r * m_pad;
-    const int changed = e < m ? ramp_link_body(e, m, c->link_scale, 1.0 / c->runner_dt, base + o2, A + o2, Aprev + o2, dx, dy, inv_len,
-                                               dadt + (int64_t)r * m_pad)
-                              : 0;
-    const int any = __syncthreads_or(changed);
-    if (threadIdx.x == 0 && any) atomicOr(moved + r, 1);
-}
-
-// R1t, R2t: the same two for the replicas whose field is a sum of terms (kind[r] == LINK_TERMS; k_ra_terms_begin,
-// k_terms_links), queued BEHIND R1 and R2: R1 has left such a replica with ramp_do = 0, so R2 passes it by, and these two
-// pass by every other replica.  term: FIELD_TERMS_MAX descriptors per replica whose table nodes are offsets into the pools;
-// bases[r]: the replica's A_0 and bases (slot 0, slots 1 .. K; 2 m_pad each)
-__global__ void k_ens_terms_begin(int R, StepCtl *__restrict__ ctl, const int32_t *__restrict__ kind, const FieldTerm *__restrict__ term,
-                                  const double *__restrict__ times, const double *__restrict__ values) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= R || kind[r] != LINK_TERMS) return;
-    terms_begin_body(ctl + r, term + (int64_t)r * FIELD_TERMS_MAX, times, values);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_ens_terms_links(int64_t m, int64_t m_pad, const int32_t *__restrict__ kind,
-                                                           const double *const *__restrict__ bases, double *__restrict__ A,
+// R2: moved[r] = OR over the replica's workgroups (k_field_links + k_any_flag).  bases[r], a0[r]: the replica's own bases
+// (slots of 2 m_pad) and static part (or nullptr)
+__global__ __launch_bounds__(BLOCK) void k_ens_field_links(int64_t m, int64_t m_pad, const double *const *__restrict__ bases,
+                                                           const double *const *__restrict__ a0, double *__restrict__ A,
                                                            double *__restrict__ Aprev, const double *__restrict__ dx,
                                                            const double *__restrict__ dy, const double *__restrict__ inv_len,
                                                            double *__restrict__ dadt, int32_t *__restrict__ moved,
                                                            const StepCtl *__restrict__ ctl) {
     const int r = blockIdx.y;
     const StepCtl *c = ctl + r;
-    if (kind[r] != LINK_TERMS || !c->ramp_do) return;
+    if (!c->ramp_do) return;
     const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x, o2 = 2 * (int64_t)r * m_pad;
-    const int changed = e < m ? terms_link_body(e, m, term_scales_of(c), reinterpret_cast<const double2 *>(bases[r]), m_pad, A + o2,
-                                                Aprev + o2, dx, dy, inv_len, dadt + (int64_t)r * m_pad)
+    const int changed = e < m ? field_link_body<false>(e, m, field_values_of(c), LoopGeom{}, reinterpret_cast<const double2 *>(bases[r]), m_pad,
+                                                       reinterpret_cast<const double2 *>(a0[r]), nullptr, A + o2, Aprev + o2, dx, dy, inv_len,
+                                                       dadt + (int64_t)r * m_pad)
                               : 0;
     const int any = __syncthreads_or(changed);
     if (threadIdx.x == 0 && any) atomicOr(moved + r, 1);
@@ -360,9 +329,9 @@ __global__ __launch_bounds__(BLOCK) void k_ens_eps_table(int64_t n_pad, const do
 }  // namespace tdgl
 
 struct EnsReplica {
-    LoopState loop;  // controller, loop, retry and ramp state: the host's mirror of the replica's StepCtl
+    LoopState loop;  // controller, loop, retry and field state: the host's mirror of the replica's StepCtl
     bool have_ctl = false, have_links = false, have_eps = false, have_state = false, lap_valid = false;
-    DevBuf<double> tbase;  // a sum of field terms: the replica's own A_0 and bases, (K + 1) slots of 2 m_pad (tdgl_ensemble_set_link_terms)
+    FieldArrays field;  // a moving field: the replica's own bases and A_0 (its descriptors and tables live in the ensemble's pools)
     // tabulated terminal currents / separable epsilon (empty: none)
     std::vector<double> mu_t, mu_dens, eps_t, eps_f;
     std::vector<int32_t> mu_group;  // [nb]: table row of each boundary position, -1 where no table applies
@@ -378,16 +347,16 @@ struct tdgl_ensemble {
     DevBuf<int32_t> fail_part, limit, d_probes;
     DevBuf<StepCtl> d_ctl;
     DevBuf<StepRec> d_rec;
-    // time-dependent inputs (allocated when the first replica asks): per replica A_base, A, A_prev (2 m_pad), dA/dt
+    // time-dependent inputs (allocated when the first replica asks): per replica A, A_prev (2 m_pad), dA/dt
     // (m_pad), the boundary term before dA/dt (n_pad), mu_boundary (nb), epsilon0 (n_pad); the tables as pools
-    DevBuf<double> Abase, A, Aprev, dadt, cvec, mu_b, eps0;
-    DevBuf<double> tab_mu_t, tab_mu_dens, tab_eps_t, tab_eps_f, tab_link_t, tab_link_v;
-    DevBuf<int32_t> tab_mu_toff, tab_mu_group, tab_eps_off, tab_link_off, ramping, moved;  // ramping: LINK_NONE / _RAMP / _TABLE / _TERMS of this batch
+    DevBuf<double> A, Aprev, dadt, cvec, mu_b, eps0;
+    DevBuf<double> tab_mu_t, tab_mu_dens, tab_eps_t, tab_eps_f;
+    DevBuf<int32_t> tab_mu_toff, tab_mu_group, tab_eps_off, ramping, moved;  // ramping[r]: the replica's field moves in this batch
     DevBuf<int64_t> tab_mu_doff;
-    // sums of field terms: per replica FIELD_TERMS_MAX descriptors, the pools of their tables' nodes, the replicas' bases
+    // the moving fields: per replica FIELD_TERMS_MAX descriptors, the pools of their tables' nodes, the replicas' bases and A_0
     DevBuf<FieldTerm> term_desc;
     DevBuf<double> tab_term_t, tab_term_v;
-    DevBuf<const double *> term_bases;
+    DevBuf<const double *> term_bases, term_a0;
     bool tables_dirty = true, any_mu_table = false, any_eps_table = false;  // (dirty: the pools and their offsets exist from the first run on)
     std::vector<int32_t> h_ramping;
     std::vector<StepCtl> h_ctl;
@@ -570,52 +539,54 @@ extern "C" int tdgl_ensemble_set_link_exponents(tdgl_ensemble *e, int32_t r, con
     TDGL_TRY(tdgl_set_link_exponents(ctx, A));  // (link variables and covariant-Laplacian values, in the context's buffers)
     TDGL_TRY(ens_copy(ctx, e->U.p + r * e->m_pad, ctx->e_U.p, e->m_pad));
     TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
-    e->rep[r].have_links = true;
-    e->rep[r].lap_valid = false;
-    if (e->rep[r].loop.tabulated() || e->rep[r].loop.terms()) e->tables_dirty = true;
-    e->rep[r].loop.links_static();
-    e->rep[r].loop.has_dadt = false;
+    EnsReplica &p = e->rep[r];
+    p.have_links = true;
+    p.lap_valid = false;
+    FieldArrays none;
+    p.field.take(none);
+    p.loop.field.clear();
+    p.loop.field.has_dadt = false;
+    e->tables_dirty = true;
     return TDGL_OK;
 }
 
-// the arrays every replica with moving links has a share of (allocated when the first replica asks)
-static int ens_alloc_moving(tdgl_ensemble *e) {
-    if (e->Abase.n != 0) return TDGL_OK;
+// Replica r is about to be given a moving field: it is without links until ens_take_field has completed it.  The arrays every
+// replica with moving links has a share of are allocated when the first replica asks
+static int ens_begin_field(tdgl_ensemble *e, int32_t r) {
+    e->rep[r].have_links = false;
+    e->tables_dirty = true;
+    if (e->A.n != 0) return TDGL_OK;
     tdgl_ctx *ctx = e->ctx;
     const size_t R = (size_t)e->R;
-    DevBuf<double> base, a, prev, dadt;
-    HIP_TRY(ctx, base.alloc(R * 2 * e->m_pad));
+    DevBuf<double> a, prev, dadt;
     HIP_TRY(ctx, a.alloc(R * 2 * e->m_pad));
     HIP_TRY(ctx, prev.alloc(R * 2 * e->m_pad));
     HIP_TRY(ctx, dadt.alloc(R * e->m_pad));
-    e->Abase.take(base);
     e->A.take(a);
     e->Aprev.take(prev);
     e->dadt.take(dadt);
     return TDGL_OK;
 }
 
-// The arrays of a replica whose links move inside tdgl_ensemble_run, A(t) = f(t) A_base with f(0) = scale (the context's
-// tdgl_set_link_exponents_base): A_base, A = A_prev = scale A_base, dA/dt = 0, the links and the Laplacian values.  The
-// replica is without links and without ramp or table until the caller completes it.
-static int ens_set_link_base(tdgl_ensemble *e, int32_t r, const double *A_base, double scale) {
+// A replica whose links move inside tdgl_ensemble_run takes over the field the context has just been given by one of its own
+// setters (A = A_prev = A(0), the links and the Laplacian values in the context's buffers): the drive, its arrays -- moved,
+// not copied: the context's own links do not stay a moving field, they are the ensemble's scratch --, and copies of A,
+// A_prev, the links and the Laplacian values; dA/dt = 0.
+static int ens_take_field(tdgl_ensemble *e, int32_t r) {
     tdgl_ctx *ctx = e->ctx;
     EnsReplica &p = e->rep[r];
-    TDGL_TRY(ens_alloc_moving(e));
-    p.have_links = false;  // (until the replica's arrays are complete)
-    if (p.loop.tabulated() || p.loop.terms()) e->tables_dirty = true;
-    p.loop.links_static();
-    TDGL_TRY(tdgl_set_link_exponents_base(ctx, A_base, scale));  // (A = scale A_base, A_prev = A, links, Laplacian values)
+    p.field.take(ctx->field);
+    p.loop.field = ctx->loop.field;
+    ctx->loop.field.clear();
     const int64_t o2 = 2 * (int64_t)r * e->m_pad;
-    TDGL_TRY(ens_copy(ctx, e->Abase.p + o2, ctx->e_Abase.p, 2 * e->m_pad));
     TDGL_TRY(ens_copy(ctx, e->A.p + o2, ctx->e_A.p, 2 * e->m_pad));
     TDGL_TRY(ens_copy(ctx, e->Aprev.p + o2, ctx->e_Aprev.p, 2 * e->m_pad));
     HIP_TRY(ctx, hipMemset(e->dadt.p + r * e->m_pad, 0, e->m_pad * sizeof(double)));
     TDGL_TRY(ens_copy(ctx, e->U.p + r * e->m_pad, ctx->e_U.p, e->m_pad));
     TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
-    p.loop.has_dadt = false;
-    p.loop.link_scale = p.loop.link_scale_prev = scale;
+    p.loop.field.has_dadt = false;
     p.lap_valid = false;
+    p.have_links = true;
     return TDGL_OK;
 }
 
@@ -629,9 +600,11 @@ extern "C" int tdgl_ensemble_set_link_ramp(tdgl_ensemble *e, int32_t r, const do
     if (!(std::isfinite(tmin) && std::isfinite(tmax) && std::isfinite(initial) && std::isfinite(final_)))
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_ramp: the ramp's parameters must be finite");
     if (!(tmax > tmin)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_ramp: tmax must be > tmin");
-    TDGL_TRY(ens_set_link_base(e, r, A_base, linear_ramp_value(0.0, tmin, tmax, initial, final_)));
-    e->rep[r].loop.set_ramp(true, tmin, tmax, initial, final_);
-    e->rep[r].have_links = true;
+    TDGL_TRY(ens_begin_field(e, r));
+    TDGL_TRY(tdgl_set_link_exponents_base(ctx, A_base, linear_ramp_value(0.0, tmin, tmax, initial, final_)));
+    TDGL_TRY(ens_take_field(e, r));
+    const double q[4] = {tmin, tmax, initial, final_};
+    e->rep[r].loop.field.set_product_source(TERM_RAMP, q, nullptr, nullptr, 0);
     return TDGL_OK;
 }
 
@@ -644,62 +617,41 @@ extern "C" int tdgl_ensemble_set_link_table(tdgl_ensemble *e, int32_t r, const d
     if (!A_base) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_table: null A_base");
     TDGL_TRY(check_link_table(ctx, "tdgl_ensemble_set_link_table", n_nodes, times, values));
     const std::vector<double> t(times, times + n_nodes);
-    TDGL_TRY(ens_set_link_base(e, r, A_base, table_value(t, values, 0.0)));
-    e->rep[r].loop.set_table(times, values, n_nodes);
-    e->rep[r].have_links = true;
-    e->tables_dirty = true;
+    TDGL_TRY(ens_begin_field(e, r));
+    TDGL_TRY(tdgl_set_link_exponents_base(ctx, A_base, table_value(t, values, 0.0)));
+    TDGL_TRY(ens_take_field(e, r));
+    e->rep[r].loop.field.set_product_source(TERM_TABLE, nullptr, times, values, n_nodes);
     return TDGL_OK;
 }
 
 // A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K for replica r (tdgl_set_link_terms of the context, whose arguments and rules
 // these are), with the failure rules of tdgl_ensemble_set_link_table: a refused argument leaves the replica as it was, a
-// failure behind that leaves it without links.  The replica keeps its own copy of A_0 and the bases.
+// failure behind that leaves it without links.
 extern "C" int tdgl_ensemble_set_link_terms(tdgl_ensemble *e, int32_t r, const double *A0, int32_t n_terms, const double *bases,
                                             const int32_t *kind, const double *ramp, const int32_t *tab_off, const double *tab_times,
                                             const double *tab_values) {
     TDGL_TRY(ens_check(e, r));
     tdgl_ctx *ctx = e->ctx;
     TDGL_TRY(check_link_terms(ctx, "tdgl_ensemble_set_link_terms", n_terms, bases, kind, ramp, tab_off, tab_times, tab_values));
-    EnsReplica &p = e->rep[r];
-    TDGL_TRY(ens_alloc_moving(e));
-    const int64_t slots = (int64_t)(n_terms + 1) * 2 * e->m_pad;
-    DevBuf<double> tb;
-    HIP_TRY(ctx, tb.alloc((size_t)slots));
-    p.have_links = false;  // (until the replica's arrays are complete)
-    p.loop.links_static();
-    e->tables_dirty = true;
-    // (A = A_prev = A(0), the links and the Laplacian values, in the context's buffers)
+    TDGL_TRY(ens_begin_field(e, r));
     TDGL_TRY(tdgl_set_link_terms(ctx, A0, n_terms, bases, kind, ramp, tab_off, tab_times, tab_values));
-    const int64_t o2 = 2 * (int64_t)r * e->m_pad;
-    TDGL_TRY(ens_copy(ctx, tb.p, ctx->e_Tbase.p, slots));
-    TDGL_TRY(ens_copy(ctx, e->A.p + o2, ctx->e_A.p, 2 * e->m_pad));
-    TDGL_TRY(ens_copy(ctx, e->Aprev.p + o2, ctx->e_Aprev.p, 2 * e->m_pad));
-    HIP_TRY(ctx, hipMemset(e->dadt.p + r * e->m_pad, 0, e->m_pad * sizeof(double)));
-    TDGL_TRY(ens_copy(ctx, e->U.p + r * e->m_pad, ctx->e_U.p, e->m_pad));
-    TDGL_TRY(ens_copy(ctx, e->lapv.p + r * e->n_slots, ctx->lap_vals.p, e->n_slots));
-    p.tbase.take(tb);
-    p.loop.copy_terms(ctx->loop);
-    p.loop.has_dadt = false;
-    p.lap_valid = false;
-    p.have_links = true;
-    // (the context's own links are the ensemble's scratch: they do not stay a moving field of their own)
-    ctx->loop.links_static();
-    return TDGL_OK;
+    return ens_take_field(e, r);
 }
 
 extern "C" int tdgl_ensemble_get_link_term_scales(tdgl_ensemble *e, int32_t r, int32_t *n_terms, double *scales) {
     TDGL_TRY(ens_check(e, r));
     if (!n_terms || !scales) TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_link_term_scales: null output");
     const LoopState &L = e->rep[r].loop;
-    *n_terms = L.terms() ? L.n_terms : 0;
-    for (int k = 0; k < *n_terms; ++k) scales[k] = L.term_scale[k];
+    *n_terms = L.field.sum() ? L.field.n_terms : 0;
+    for (int k = 0; k < *n_terms; ++k) scales[k] = L.field.scale[k];
     return TDGL_OK;
 }
 
 extern "C" int tdgl_ensemble_get_link_scale(tdgl_ensemble *e, int32_t r, double *scale) {
     TDGL_TRY(ens_check(e, r));
     if (!scale) TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_link_scale: null scale");
-    *scale = e->rep[r].loop.link_scale;
+    const FieldDrive &F = e->rep[r].loop.field;
+    *scale = F.sum() ? 1.0 : F.scale[0];
     return TDGL_OK;
 }
 
@@ -750,9 +702,9 @@ static int ens_upload_tables(tdgl_ensemble *e) {
     tdgl_ctx *ctx = e->ctx;
     const int R = e->R;
     const int64_t nb = std::max<int64_t>(ctx->nb, 1);
-    std::vector<int32_t> toff(R + 1, 0), eoff(R + 1, 0), loff(R + 1, 0), group((size_t)R * nb, -1);
+    std::vector<int32_t> toff(R + 1, 0), eoff(R + 1, 0), group((size_t)R * nb, -1);
     std::vector<int64_t> doff(R, 0);
-    std::vector<double> mt, md, et, ef, lt, lv;
+    std::vector<double> mt, md, et, ef;
     e->any_mu_table = e->any_eps_table = false;
     for (int r = 0; r < R; ++r) {
         const EnsReplica &p = e->rep[r];
@@ -764,37 +716,26 @@ static int ens_upload_tables(tdgl_ensemble *e) {
         et.insert(et.end(), p.eps_t.begin(), p.eps_t.end());
         ef.insert(ef.end(), p.eps_f.begin(), p.eps_f.end());
         eoff[r + 1] = (int32_t)et.size();
-        if (p.loop.tabulated()) {
-            lt.insert(lt.end(), p.loop.tab_t.begin(), p.loop.tab_t.end());
-            lv.insert(lv.end(), p.loop.tab_v.begin(), p.loop.tab_v.end());
-        }
-        loff[r + 1] = (int32_t)lt.size();
         e->any_mu_table |= !p.mu_t.empty();
         e->any_eps_table |= !p.eps_t.empty();
     }
     std::vector<FieldTerm> desc((size_t)R * FIELD_TERMS_MAX, FieldTerm{});
-    std::vector<const double *> bases((size_t)R, nullptr);
+    std::vector<const double *> bases((size_t)R, nullptr), a0s((size_t)R, nullptr);
     std::vector<double> kt, kv;
     for (int r = 0; r < R; ++r) {
         const EnsReplica &p = e->rep[r];
-        if (!p.loop.terms()) continue;
-        bases[r] = p.tbase.p;
-        for (int k = 0; k < p.loop.n_terms; ++k) {
-            FieldTerm d = p.loop.term[k];
-            d.off = (int32_t)kt.size();  // (its nodes in the ensemble's pools)
-            kt.insert(kt.end(), p.loop.term_t[k].begin(), p.loop.term_t[k].end());
-            kv.insert(kv.end(), p.loop.term_v[k].begin(), p.loop.term_v[k].end());
-            desc[(size_t)r * FIELD_TERMS_MAX + k] = d;
-        }
+        if (!p.loop.field.moves) continue;
+        bases[r] = p.field.bases.p, a0s[r] = p.field.a0.p;
+        p.loop.field.describe(desc.data() + (size_t)r * FIELD_TERMS_MAX, kt, kv);  // (its nodes in the ensemble's pools)
     }
     if (kt.empty()) kt.push_back(0.0), kv.push_back(0.0);
     HIP_TRY(ctx, e->term_desc.upload(desc));
     HIP_TRY(ctx, e->term_bases.upload(bases));
+    HIP_TRY(ctx, e->term_a0.upload(a0s));
     HIP_TRY(ctx, e->tab_term_t.upload(kt));
     HIP_TRY(ctx, e->tab_term_v.upload(kv));
     if (mt.empty()) mt.push_back(0.0), md.push_back(0.0);  // (never read: every replica's node count is 0)
     if (et.empty()) et.push_back(0.0), ef.push_back(0.0);
-    if (lt.empty()) lt.push_back(0.0), lv.push_back(0.0);
     HIP_TRY(ctx, e->tab_mu_toff.upload(toff));
     HIP_TRY(ctx, e->tab_mu_doff.upload(doff));
     HIP_TRY(ctx, e->tab_mu_group.upload(group));
@@ -803,9 +744,6 @@ static int ens_upload_tables(tdgl_ensemble *e) {
     HIP_TRY(ctx, e->tab_eps_off.upload(eoff));
     HIP_TRY(ctx, e->tab_eps_t.upload(et));
     HIP_TRY(ctx, e->tab_eps_f.upload(ef));
-    HIP_TRY(ctx, e->tab_link_off.upload(loff));
-    HIP_TRY(ctx, e->tab_link_t.upload(lt));
-    HIP_TRY(ctx, e->tab_link_v.upload(lv));
     e->tables_dirty = false;
     return TDGL_OK;
 }
@@ -813,7 +751,7 @@ static int ens_upload_tables(tdgl_ensemble *e) {
 extern "C" int tdgl_ensemble_set_mu_boundary(tdgl_ensemble *e, int32_t r, const double *mu_boundary) {
     TDGL_TRY(ens_check(e, r));
     tdgl_ctx *ctx = e->ctx;
-    if (ctx->loop.has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary: the context's links are time dependent");
+    if (ctx->loop.field.has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_mu_boundary: the context's links are time dependent");
     TDGL_TRY(tdgl_set_mu_boundary(ctx, mu_boundary));  // (static links: the boundary term as the run-ahead loop reads it)
     TDGL_TRY(ens_copy(ctx, e->ceff.p + r * e->n_pad, ctx->ceff.p, e->n_pad));
     TDGL_TRY(ens_copy(ctx, e->cvec.p + r * e->n_pad, ctx->cvec.p, e->n_pad));  // (a ramp adds its dA/dt term to this)
@@ -890,20 +828,20 @@ extern "C" int tdgl_ensemble_get_state(tdgl_ensemble *e, int32_t r, double *psi,
     tdgl_ctx *ctx = e->ctx;
     const EnsReplica &p = e->rep[r];
     if (!p.have_state || !p.have_links) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_get_state: replica %d has no state or links", r);
-    if (ctx->loop.has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_state: the context's links are time dependent");
+    if (ctx->loop.field.has_dadt) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_state: the context's links are time dependent");
     TDGL_TRY(ens_copy(ctx, ctx->psi[ctx->loop.cur].p, (p.loop.cur ? e->psi1.p : e->psi0.p) + r * e->n_pad, e->n_pad));
     TDGL_TRY(ens_copy(ctx, ctx->mu.p, e->mu.p + r * e->n_pad, e->n_pad));
     TDGL_TRY(ens_copy(ctx, ctx->e_U.p, e->U.p + r * e->m_pad, e->m_pad));
     // a ramping replica: J_n with its dA/dt -- that of the step that produced psi (the next step's ramp moves at the
     // start of its first attempt, in the next tdgl_ensemble_run)
-    const bool dadt = p.loop.ramp_on && p.loop.has_dadt;
+    const bool dadt = p.loop.field.moves && p.loop.field.has_dadt;
     if (dadt) TDGL_TRY(ens_copy(ctx, ctx->e_dAdt.p, e->dadt.p + r * e->m_pad, e->m_pad));
     ctx->have_state = true;
     ctx->lap_valid = false;  // (the context's Laplacian values belong to whatever links it was last given)
     ctx->currents.new_state();
-    ctx->loop.has_dadt = dadt;
+    ctx->loop.field.has_dadt = dadt;
     const int status = tdgl_get_state(ctx, psi, mu, supercurrent, normal_current);
-    ctx->loop.has_dadt = false;  // (the context's own links are static)
+    ctx->loop.field.has_dadt = false;  // (the context's own links are static)
     return status;
 }
 
@@ -914,7 +852,7 @@ static void ens_launch_laplacian_cache(tdgl_ensemble *e, int r) {
 }
 
 // the time-dependent inputs of the round's attempts (T1, T2, R1 - R5), in the single run's order (run.inc: run_ahead)
-static void ens_queue_drives(tdgl_ensemble *e, bool ramping, bool terms) {
+static void ens_queue_drives(tdgl_ensemble *e, bool ramping) {
     tdgl_ctx *ctx = e->ctx;
     const unsigned R = (unsigned)e->R;
     if (e->any_mu_table)
@@ -929,20 +867,12 @@ static void ens_queue_drives(tdgl_ensemble *e, bool ramping, bool terms) {
                            (const StepCtl *)e->d_ctl.p);
     if (!ramping) return;
     const SellPattern &pat = ctx->lap_pat;
-    hipLaunchKernelGGL(k_ens_ramp_begin, dim3((R + 63) / 64), dim3(64), 0, ctx->stream, (int)R, e->d_ctl.p, (const int32_t *)e->ramping.p,
-                       (const int32_t *)e->tab_link_off.p, (const double *)e->tab_link_t.p, (const double *)e->tab_link_v.p, e->moved.p);
+    hipLaunchKernelGGL(k_ens_field_begin, dim3((R + 63) / 64), dim3(64), 0, ctx->stream, (int)R, e->d_ctl.p, (const int32_t *)e->ramping.p,
+                       (const FieldTerm *)e->term_desc.p, (const double *)e->tab_term_t.p, (const double *)e->tab_term_v.p, e->moved.p);
     const int nblk = grid_for(ctx->m);
-    hipLaunchKernelGGL(k_ens_ramp_links, dim3(nblk, R), dim3(BLOCK), 0, ctx->stream, ctx->m, e->m_pad, (const double *)e->Abase.p, e->A.p,
-                       e->Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
-                       e->dadt.p, e->moved.p, (const StepCtl *)e->d_ctl.p);
-    if (terms) {
-        hipLaunchKernelGGL(k_ens_terms_begin, dim3((R + 63) / 64), dim3(64), 0, ctx->stream, (int)R, e->d_ctl.p, (const int32_t *)e->ramping.p,
-                           (const FieldTerm *)e->term_desc.p, (const double *)e->tab_term_t.p, (const double *)e->tab_term_v.p);
-        hipLaunchKernelGGL(k_ens_terms_links, dim3(nblk, R), dim3(BLOCK), 0, ctx->stream, ctx->m, e->m_pad, (const int32_t *)e->ramping.p,
-                           (const double *const *)e->term_bases.p, e->A.p, e->Aprev.p, (const double *)ctx->e_dirx.p,
-                           (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p, e->dadt.p, e->moved.p,
-                           (const StepCtl *)e->d_ctl.p);
-    }
+    hipLaunchKernelGGL(k_ens_field_links, dim3(nblk, R), dim3(BLOCK), 0, ctx->stream, ctx->m, e->m_pad, (const double *const *)e->term_bases.p,
+                       (const double *const *)e->term_a0.p, e->A.p, e->Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p,
+                       (const double *)ctx->e_inv_len.p, e->dadt.p, e->moved.p, (const StepCtl *)e->d_ctl.p);
     const int nblk_ceff = grid_for((int64_t)pat.n_slices * WAVE);
     hipLaunchKernelGGL(k_ens_ceff_links, dim3(nblk_ceff + nblk, R), dim3(BLOCK), 0, ctx->stream, nblk_ceff, pat.n_slices, pat.n_rows,
                        (const int32_t *)pat.slice_off.p, (const int32_t *)ctx->lap_slot_edge.p, (const double *)ctx->lap_slot_w.p,
@@ -1007,10 +937,10 @@ static void ens_queue_sub_solve(tdgl_ensemble *e) {
                        (const int32_t *)e->fail_part.p, ctx->psi_blocks, e->d_ctl.p, e->d_rec.p, (const int32_t *)e->limit.p);
 }
 
-static void ens_queue_round(tdgl_ensemble *e, bool ramping, bool terms) {
+static void ens_queue_round(tdgl_ensemble *e, bool ramping) {
     tdgl_ctx *ctx = e->ctx;
     const unsigned R = (unsigned)e->R;
-    ens_queue_drives(e, ramping, terms);
+    ens_queue_drives(e, ramping);
     hipLaunchKernelGGL(k_ens_psi_update, dim3(ctx->psi_blocks, R), dim3(BLOCK), 0, ctx->stream, ctx->n_own, e->n_pad, e->psi0.p, e->psi1.p,
                        (const double2 *)e->lap0.p, (const double2 *)e->lap1.p, (const double *)e->mu.p, (const double *)e->eps.p, ctx->u,
                        ctx->gamma, e->dmax_part.p, e->fail_part.p, e->d_ctl.p);
@@ -1079,17 +1009,16 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
     int err_replica = -1;
     double err_dt = 0.0;
     for (;;) {
-        int active = 0, n_ramping = 0, n_terms = 0;
+        int active = 0, n_ramping = 0;
         for (int r = 0; r < R; ++r) {
             EnsReplica &p = e->rep[r];
             const bool on = !reached_end[r] && steps_done[r] < max_steps[r];
             active += on;
             // a ramp that has reached its end: dA/dt is identically zero from here on, and a replica whose ramp has
             // settled costs what a static one does (as in tdgl_run)
-            if (p.loop.ramp_settled()) p.loop.has_dadt = false;
-            e->h_ramping[r] = !(on && p.loop.ramping()) ? LINK_NONE : p.loop.terms() ? LINK_TERMS : p.loop.tabulated() ? LINK_TABLE : LINK_RAMP;
-            n_ramping += e->h_ramping[r] != LINK_NONE;
-            n_terms += e->h_ramping[r] == LINK_TERMS;
+            if (p.loop.ramp_settled()) p.loop.field.has_dadt = false;
+            e->h_ramping[r] = on && p.loop.ramping();
+            n_ramping += e->h_ramping[r];
             p.loop.fill(e->h_ctl[r], end_time[r], on);
             e->h_limit[r] = on ? (int32_t)std::min<int64_t>(max_steps[r] - steps_done[r], RA_BATCH_MAX) : 0;
         }
@@ -1099,7 +1028,7 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
         HIP_TRY(ctx, hipMemcpyAsync(e->limit.p, e->h_limit.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         if (n_ramping > 0)
             HIP_TRY(ctx, hipMemcpyAsync(e->ramping.p, e->h_ramping.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        for (int s = 0; s < batch; ++s) ens_queue_round(e, n_ramping > 0, n_terms > 0);
+        for (int s = 0; s < batch; ++s) ens_queue_round(e, n_ramping > 0);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(e->h_ctl.data(), e->d_ctl.p, (size_t)R * sizeof(StepCtl), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(e->h_rec.data(), e->d_rec.p, (size_t)R * RA_BATCH_MAX * sizeof(StepRec), hipMemcpyDeviceToHost, ctx->stream));

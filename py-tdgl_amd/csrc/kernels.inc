@@ -425,71 +425,20 @@ __global__ __launch_bounds__(BLOCK) void k_psi_update_with_currents(
                                        mu, js, jn, nullptr);
 }
 
-// ---- field ramp inside the run-ahead loop (run.inc) ----------------------------------------------------------
-// A(t) = LinearRamp(t) A_base (tdgl/sources/scaling.py:4-14) evaluated on the device at the time the device's loop
+// ---- the moving applied field inside the run-ahead loop (run.inc; FieldDrive in tdgl_internal.h) ----------------------
+// A factor such as LinearRamp(t) (tdgl/sources/scaling.py:4-14) evaluated on the device at the time the device's loop
 // has reached; what TDGLSolver.update does before the psi update of a step (solver.py:626-642), once per STEP: the
 // first attempt of a step moves the links, retries and dead attempts skip everything.  The arithmetic is the host's,
 // operation for operation (no contraction), so that this loop and the one with one synchronisation per step agree
 // to the last bit.
 // tdgl/sources/scaling.py:4-14, branch for branch and operation for operation (`initial` before tmin, `final` from
 // tmax on -- exactly, whatever the two values are --, Python's left-to-right product and quotient in between); host
-// and device evaluate THIS, so the two time loops agree to the last bit and `LoopState::ramp_settled` can test equality
+// and device evaluate THIS, so the two time loops agree to the last bit and `FieldDrive::settled` can test equality
 __host__ __device__ inline double linear_ramp_value(double t, double tmin, double tmax, double initial, double final_) {
 #pragma clang fp contract(off)
     if (t < tmin) return initial;
     if (t < tmax) return initial + (final_ - initial) * (t - tmin) / (tmax - tmin);
     return final_;
-}
-
-// the factor of this step is `scale` (update_link_scale: nothing moves when the factor has been constant over the last
-// two evaluations); 1: the links move
-__device__ __forceinline__ int link_scale_step(StepCtl *__restrict__ ctl, double scale) {
-    if (scale == ctl->link_scale && scale == ctl->link_scale_prev && ctl->has_dadt) return 0;
-    ctl->link_scale_prev = ctl->link_scale;
-    ctl->link_scale = scale;
-    ctl->has_dadt = 1;
-    return 1;
-}
-
-// (body: one thread per controller)
-__device__ __forceinline__ void ramp_begin_body(StepCtl *__restrict__ ctl) {
-#pragma clang fp contract(off)
-    int go = 0;
-    if (!ctl->poisoned && ctl->retries == 0)
-        go = link_scale_step(ctl, linear_ramp_value(ctl->time, ctl->ramp_tmin, ctl->ramp_tmax, ctl->ramp_initial, ctl->ramp_final));
-    ctl->ramp_do = go;
-}
-
-__global__ void k_ra_ramp_begin(StepCtl *__restrict__ ctl) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    ramp_begin_body(ctl);
-}
-
-// A = scale A_base, dA/dt along the edge with the previous accepted step's dt, A_prev <- A; 1 if the edge moved
-__device__ __forceinline__ int ramp_link_body(int64_t e, int64_t m, double scale, double inv_dt, const double *__restrict__ base,
-                                              double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
-                                              const double *__restrict__ dy, const double *__restrict__ inv_len,
-                                              double *__restrict__ dadt) {
-    // (rounded products, as k_scale_links stores them: the empty asm keeps the compiler from contracting them
-    // into the difference A - A_prev that dadt_body forms -- __dmul_rn is a plain product to it)
-    double ax = scale * base[2 * e], ay = scale * base[2 * e + 1];
-    asm volatile("" : "+v"(ax), "+v"(ay));
-    A[2 * e] = ax;
-    A[2 * e + 1] = ay;
-    return dadt_body(e, m, inv_dt, ax, ay, Aprev, dx, dy, inv_len, dadt);
-}
-
-// ... per workgroup: "did it move"
-__global__ __launch_bounds__(BLOCK) void k_ra_ramp_links(int64_t m, const double *__restrict__ base, double *__restrict__ A,
-                                                         double *__restrict__ Aprev, const double *__restrict__ dx,
-                                                         const double *__restrict__ dy, const double *__restrict__ inv_len,
-                                                         double *__restrict__ dadt, int32_t *__restrict__ block_changed,
-                                                         const StepCtl *__restrict__ ctl) {
-    if (!ctl->ramp_do) return;
-    const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-    const int changed = e < m ? ramp_link_body(e, m, ctl->link_scale, 1.0 / ctl->runner_dt, base, A, Aprev, dx, dy, inv_len, dadt) : 0;
-    const int any = __syncthreads_or(changed);
-    if (threadIdx.x == 0) block_changed[blockIdx.x] = any;
 }
 
 // L psi^n with the links of this step (the cached one belongs to the links of the previous step)
@@ -624,30 +573,13 @@ __device__ __forceinline__ double table_value_dev(const double *__restrict__ tim
     return v[hi - 1] + (v[hi] - v[hi - 1]) * ((time - t0) / (t1 - t0));
 }
 
-// The field factor as a table, A(t) = table(t) A_base (tdgl_set_link_table): ramp_begin_body with table_value_dev in the
-// place of linear_ramp_value -- the same step rule, so a plateau inside the table skips the link launches as a finished
-// ramp does, and link_scale_prev, link_scale, has_dadt and ramp_do are left as the ramp leaves them.  `times` and `values`
-// are the n_nodes >= 1 nodes of THIS controller's table.  (body: one thread per controller)
-__device__ __forceinline__ void table_begin_body(StepCtl *__restrict__ ctl, const double *__restrict__ times,
-                                                 const double *__restrict__ values, int n_nodes) {
-#pragma clang fp contract(off)
-    int go = 0;
-    if (!ctl->poisoned && ctl->retries == 0) go = link_scale_step(ctl, table_value_dev(times, values, n_nodes, ctl->time));
-    ctl->ramp_do = go;
-}
-
-__global__ void k_ra_table_begin(StepCtl *__restrict__ ctl, const double *__restrict__ times, const double *__restrict__ values,
-                                 int n_nodes) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    table_begin_body(ctl, times, values, n_nodes);
-}
-
-// ---- a sum of field terms A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K (tdgl_set_link_terms) ----------------------------
-// The single product's step rule, term by term: the K factors are evaluated at the controller's time with the evaluators
-// above (linear_ramp_value, table_value_dev); nothing moves only when EVERY factor equals its last two evaluations and a
-// dynamic update has run.  `term`: the K = ctl->n_terms descriptors of THIS controller; a table term's nodes are
-// times[off .. off + n), values[off .. off + n).  Leaves has_dadt and ramp_do as ramp_begin_body leaves them.
-// (body: one thread per controller)
+// ---- the moving applied field A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K + loops (FieldDrive; tdgl_set_link_exponents_base,
+// tdgl_set_link_terms, tdgl_set_link_loops) ----------------------------------------------------------------------------------
+// The step rule (FieldDrive::step on the host): the K factors and every loop's four values are evaluated at the controller's
+// time with the evaluators above (linear_ramp_value, table_value_dev); nothing moves only when EVERY value equals its last
+// two evaluations and a dynamic update has run -- so a plateau inside a table skips the link launches as a finished ramp
+// does.  `term`: the K = ctl->n_terms descriptors of THIS controller; a table term's nodes are times[off .. off + n),
+// values[off .. off + n).  A factor the caller supplies (TERM_HOST) never comes here: the loop does not evaluate such a field.
 // the K factors at time t into s[]; false when one of them differs from its last two evaluations
 __device__ __forceinline__ bool terms_eval(const StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term,
                                            const double *__restrict__ times, const double *__restrict__ values, double t, double *s) {
@@ -676,102 +608,7 @@ __device__ __forceinline__ void terms_take(StepCtl *__restrict__ ctl, const doub
         }
 }
 
-__device__ __forceinline__ void terms_begin_body(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term,
-                                                 const double *__restrict__ times, const double *__restrict__ values) {
-    int go = 0;
-    if (!ctl->poisoned && ctl->retries == 0) {
-        double s[FIELD_TERMS_MAX];
-        const bool same = terms_eval(ctl, term, times, values, ctl->time, s) && ctl->has_dadt != 0;
-        if (!same) {
-            terms_take(ctl, s);
-            ctl->has_dadt = 1;
-            ctl->n_term_moves += 1;
-            go = 1;
-        }
-    }
-    ctl->ramp_do = go;
-}
-
-__global__ void k_ra_terms_begin(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term, const double *__restrict__ times,
-                                 const double *__restrict__ values) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    terms_begin_body(ctl, term, times, values);
-}
-
-// the factors of a sum and what goes with them, by value: the loop with one synchronisation per step evaluates the factors
-// on the host (tdgl_update_link_terms) and hands them to the kernel the run-ahead loop feeds from its controller
-struct TermScales {
-    double s[FIELD_TERMS_MAX];
-    double inv_dt;
-    int n_terms, a0;
-};
-
-// A = ((A_0 + s_1 A_1) + s_2 A_2) + ... per edge and component, terms added in term order, every product rounded before
-// it is added (no contraction: the pragma, and ramp_link_body's empty asm between a product and the sum that takes it);
-// without A_0 the sum starts from the first product.  Then dA/dt, A_prev <- A and "did it move" as for the single product
-// (dadt_body).  `bases`: slot 0 A_0, slot k the k-th base, `stride` double2 apart; a pure stream, 16 bytes per lane and
-// array: (K + 1) 16 read, 16 written for A, and dadt_body's 16 + 24 read, 16 + 8 written.
-__device__ __forceinline__ void terms_sum(int64_t e, const TermScales &ts, const double2 *__restrict__ bases, int64_t stride, double &ax,
-                                          double &ay) {
-#pragma clang fp contract(off)
-    const double2 b1 = bases[stride + e];
-    ax = ts.s[0] * b1.x, ay = ts.s[0] * b1.y;
-    asm volatile("" : "+v"(ax), "+v"(ay));
-    if (ts.a0) {
-        const double2 a0 = bases[e];
-        ax = a0.x + ax;
-        ay = a0.y + ay;
-    }
-#pragma unroll
-    for (int k = 1; k < FIELD_TERMS_MAX; ++k) {
-        if (k >= ts.n_terms) break;
-        const double2 b = bases[(k + 1) * stride + e];
-        double px = ts.s[k] * b.x, py = ts.s[k] * b.y;
-        asm volatile("" : "+v"(px), "+v"(py));
-        ax = ax + px;
-        ay = ay + py;
-    }
-    asm volatile("" : "+v"(ax), "+v"(ay));
-}
-
-__device__ __forceinline__ int terms_link_body(int64_t e, int64_t m, const TermScales &ts, const double2 *__restrict__ bases, int64_t stride,
-                                               double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
-                                               const double *__restrict__ dy, const double *__restrict__ inv_len,
-                                               double *__restrict__ dadt) {
-    double ax, ay;
-    terms_sum(e, ts, bases, stride, ax, ay);
-    reinterpret_cast<double2 *>(A)[e] = make_double2(ax, ay);
-    return dadt_body(e, m, ts.inv_dt, ax, ay, Aprev, dx, dy, inv_len, dadt);
-}
-
-// the factors of this attempt from its controller
-__device__ __forceinline__ TermScales term_scales_of(const StepCtl *__restrict__ c) {
-    TermScales ts;
-#pragma unroll
-    for (int k = 0; k < FIELD_TERMS_MAX; ++k) ts.s[k] = c->term_scale[k];
-    ts.inv_dt = 1.0 / c->runner_dt;
-    ts.n_terms = c->n_terms;
-    ts.a0 = c->term_a0;
-    return ts;
-}
-
-// ... per workgroup: "did it move" (k_ra_ramp_links).  ctl: the run-ahead loop's controller, which says whether the
-// attempt moves anything and with which factors; nullptr: the host has decided, the factors are `host`'s
-__global__ __launch_bounds__(BLOCK) void k_terms_links(int64_t m, int64_t m_pad, TermScales host, const double *__restrict__ bases,
-                                                       double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
-                                                       const double *__restrict__ dy, const double *__restrict__ inv_len,
-                                                       double *__restrict__ dadt, int32_t *__restrict__ block_changed,
-                                                       const StepCtl *__restrict__ ctl) {
-    if (ctl && !ctl->ramp_do) return;
-    const TermScales ts = ctl ? term_scales_of(ctl) : host;
-    const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-    const int changed =
-        e < m ? terms_link_body(e, m, ts, reinterpret_cast<const double2 *>(bases), m_pad, A, Aprev, dx, dy, inv_len, dadt) : 0;
-    const int any = __syncthreads_or(changed);
-    if (threadIdx.x == 0) block_changed[blockIdx.x] = any;
-}
-
-// ---- moving current loops on top of that field (tdgl_set_link_loops) -----------------------------------------------------
+// ---- moving current loops in that field (tdgl_set_link_loops) -------------------------------------------------------------
 // A(t) = [A_0 + sum_k f_k(t) A_k] + sum_l I_l(t) Aloop(r_e - c_l(t); a_l): a circular loop of radius a in a plane parallel to
 // the film, its centre and current piecewise linear in t.  Six numbers per step and one closed form per edge.
 //
@@ -815,20 +652,10 @@ __device__ __forceinline__ void loop_potential_add(double ex, double ey, double 
     ay = ay + ly;
 }
 
-// what does not move: the loops' radii, the film's height and how many there are; and the 4 values per loop that do
-struct LoopGeom {
-    double radius[FIELD_LOOPS_MAX];
-    double z_film;
-    int n_loops, pad;
-};
-struct LoopPars {
-    double p[FIELD_LOOPS_MAX][4];  // centre x, y, z and current
-};
-
-// (body: one thread per controller)  The terms' rule extended: nothing moves only when every factor AND every loop's four
-// values equal their last two evaluations and a dynamic update has run.  loop[l]: nodes off .. off + n of the pools
-// tab[0 .. T) (times), tab[T ..) centre x, then y, z and the current, T nodes each.
-__device__ __forceinline__ void loops_begin_body(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term,
+// (body: one thread per controller)  loop[l]: nodes off .. off + n of the pools tab[0 .. T) (times), tab[T ..) centre x, then
+// y, z and the current, T nodes each (read only when ctl->n_loops > 0).  Leaves has_dadt = 1 and ramp_do = 1 where the field
+// moves, ramp_do = 0 on retries, dead attempts and where nothing moves.
+__device__ __forceinline__ void field_begin_body(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term,
                                                  const double *__restrict__ times, const double *__restrict__ values,
                                                  const FieldLoop *__restrict__ loop, const double *__restrict__ tab, int T) {
     int go = 0;
@@ -866,47 +693,116 @@ __device__ __forceinline__ void loops_begin_body(StepCtl *__restrict__ ctl, cons
     ctl->ramp_do = go;
 }
 
-__global__ void k_ra_loops_begin(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term, const double *__restrict__ times,
+__global__ void k_ra_field_begin(StepCtl *__restrict__ ctl, const FieldTerm *__restrict__ term, const double *__restrict__ times,
                                  const double *__restrict__ values, const FieldLoop *__restrict__ loop, const double *__restrict__ tab,
                                  int T) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    loops_begin_body(ctl, term, times, values, loop, tab, T);
+    field_begin_body(ctl, term, times, values, loop, tab, T);
 }
 
-// One lane per edge: the sum of terms as k_terms_links forms it (terms_sum; without products A_0 alone), the loops added in
-// loop order, then dA/dt, A_prev <- A and "did it move" (dadt_body).  Over k_terms_links 16 more bytes read per edge (the
-// centre), no LDS, no atomics.  ctl: the run-ahead loop's controller (factors and loop values from there); nullptr: `host`'s
-// and `hostp`'s
-__global__ __launch_bounds__(BLOCK) void k_loops_links(int64_t m, int64_t m_pad, TermScales host, LoopPars hostp, LoopGeom geom,
-                                                       const double *__restrict__ bases, const double *__restrict__ centres,
-                                                       double *__restrict__ A, double *__restrict__ Aprev, const double *__restrict__ dx,
+// the values of a step, by value: the loop with one synchronisation per step evaluates them on the host (update_field) and
+// hands them to the kernel the run-ahead loop feeds from its controller
+struct FieldValues {
+    double s[FIELD_TERMS_MAX];
+    double lp[FIELD_LOOPS_MAX][4];  // centre x, y, z and current
+    double inv_dt;
+    int n_terms, pad;
+};
+// what does not move: the loops' radii, the film's height and how many there are
+struct LoopGeom {
+    double radius[FIELD_LOOPS_MAX];
+    double z_film;
+    int n_loops, pad;
+};
+
+// A = ((A_0 + s_1 A_1) + s_2 A_2) + ... per edge and component, terms added in term order, every product rounded before
+// it is added (no contraction: the pragma, and the empty asm between a product and the sum or difference that takes it --
+// __dmul_rn is a plain product to the compiler, which would contract it into the A - A_prev of dadt_body); without A_0
+// (a0 == nullptr) the sum starts from the first product, without products it is A_0.  `bases`: slot k the (k + 1)-th
+// base, `stride` double2 apart; a pure stream, 16 bytes per lane and array.
+__device__ __forceinline__ void terms_sum(int64_t e, const FieldValues &fv, const double2 *__restrict__ bases, int64_t stride,
+                                          const double2 *__restrict__ a0, double &ax, double &ay) {
+#pragma clang fp contract(off)
+    if (fv.n_terms == 0) {
+        const double2 a = a0[e];
+        ax = a.x, ay = a.y;
+        return;
+    }
+    const double2 b1 = bases[e];
+    ax = fv.s[0] * b1.x, ay = fv.s[0] * b1.y;
+    asm volatile("" : "+v"(ax), "+v"(ay));
+    if (a0) {
+        const double2 a = a0[e];
+        ax = a.x + ax;
+        ay = a.y + ay;
+    }
+#pragma unroll
+    for (int k = 1; k < FIELD_TERMS_MAX; ++k) {
+        if (k >= fv.n_terms) break;
+        const double2 b = bases[k * stride + e];
+        double px = fv.s[k] * b.x, py = fv.s[k] * b.y;
+        asm volatile("" : "+v"(px), "+v"(py));
+        ax = ax + px;
+        ay = ay + py;
+    }
+    asm volatile("" : "+v"(ax), "+v"(ay));
+}
+
+// One lane per edge: the sum of terms, the loops added in loop order (LOOPS; else the instantiation carries neither the
+// registers of the arithmetic-geometric mean nor the centre's 16 bytes), A stored, then dA/dt along the edge with the previous
+// accepted step's dt, A_prev <- A and "did it move" (dadt_body).  No LDS, no atomics.
+template <bool LOOPS>
+__device__ __forceinline__ int field_link_body(int64_t e, int64_t m, const FieldValues &fv, const LoopGeom &geom,
+                                               const double2 *__restrict__ bases, int64_t stride, const double2 *__restrict__ a0,
+                                               const double2 *__restrict__ centres, double *__restrict__ A, double *__restrict__ Aprev,
+                                               const double *__restrict__ dx, const double *__restrict__ dy,
+                                               const double *__restrict__ inv_len, double *__restrict__ dadt) {
+    double ax, ay;
+    terms_sum(e, fv, bases, stride, a0, ax, ay);
+    if (LOOPS) {
+        const double2 ce = centres[e];
+#pragma unroll
+        for (int l = 0; l < FIELD_LOOPS_MAX; ++l) {
+            if (l >= geom.n_loops) break;
+            loop_potential_add(ce.x, ce.y, fv.lp[l][0], fv.lp[l][1], geom.z_film - fv.lp[l][2], geom.radius[l], fv.lp[l][3], ax, ay);
+        }
+    }
+    reinterpret_cast<double2 *>(A)[e] = make_double2(ax, ay);
+    return dadt_body(e, m, fv.inv_dt, ax, ay, Aprev, dx, dy, inv_len, dadt);
+}
+
+// the values of this attempt from its controller
+__device__ __forceinline__ FieldValues field_values_of(const StepCtl *__restrict__ c) {
+    FieldValues fv;
+#pragma unroll
+    for (int k = 0; k < FIELD_TERMS_MAX; ++k) fv.s[k] = c->term_scale[k];
+#pragma unroll
+    for (int l = 0; l < FIELD_LOOPS_MAX; ++l)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fv.lp[l][j] = c->loop_par[l][j];
+    fv.inv_dt = 1.0 / c->runner_dt;
+    fv.n_terms = c->n_terms;
+    fv.pad = 0;
+    return fv;
+}
+
+// ... per workgroup: "did it move".  ctl: the run-ahead loop's controller, which says whether the attempt moves anything and
+// with which values; nullptr: the host has decided, the values are `host`'s
+template <bool LOOPS>
+__global__ __launch_bounds__(BLOCK) void k_field_links(int64_t m, int64_t m_pad, FieldValues host, LoopGeom geom,
+                                                       const double *__restrict__ bases, const double *__restrict__ a0,
+                                                       const double *__restrict__ centres, double *__restrict__ A,
+                                                       double *__restrict__ Aprev, const double *__restrict__ dx,
                                                        const double *__restrict__ dy, const double *__restrict__ inv_len,
                                                        double *__restrict__ dadt, int32_t *__restrict__ block_changed,
                                                        const StepCtl *__restrict__ ctl) {
     if (ctl && !ctl->ramp_do) return;
-    const TermScales ts = ctl ? term_scales_of(ctl) : host;
+    const FieldValues fv = ctl ? field_values_of(ctl) : host;
     const int64_t e = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-    int changed = 0;
-    if (e < m) {
-        const double2 *b2 = reinterpret_cast<const double2 *>(bases);
-        double ax, ay;
-        if (ts.n_terms > 0) {
-            terms_sum(e, ts, b2, m_pad, ax, ay);
-        } else {
-            const double2 a0 = b2[e];
-            ax = a0.x, ay = a0.y;
-        }
-        const double2 ce = reinterpret_cast<const double2 *>(centres)[e];
-#pragma unroll
-        for (int l = 0; l < FIELD_LOOPS_MAX; ++l) {
-            if (l >= geom.n_loops) break;
-            const double cx = ctl ? ctl->loop_par[l][0] : hostp.p[l][0], cy = ctl ? ctl->loop_par[l][1] : hostp.p[l][1];
-            const double cz = ctl ? ctl->loop_par[l][2] : hostp.p[l][2], cur = ctl ? ctl->loop_par[l][3] : hostp.p[l][3];
-            loop_potential_add(ce.x, ce.y, cx, cy, geom.z_film - cz, geom.radius[l], cur, ax, ay);
-        }
-        reinterpret_cast<double2 *>(A)[e] = make_double2(ax, ay);
-        changed = dadt_body(e, m, ts.inv_dt, ax, ay, Aprev, dx, dy, inv_len, dadt);
-    }
+    const int changed = e < m ? field_link_body<LOOPS>(e, m, fv, geom, reinterpret_cast<const double2 *>(bases), m_pad,
+                                                       reinterpret_cast<const double2 *>(a0), reinterpret_cast<const double2 *>(centres),
+                                                       A, Aprev, dx, dy, inv_len, dadt)
+                              : 0;
     const int any = __syncthreads_or(changed);
     if (threadIdx.x == 0) block_changed[blockIdx.x] = any;
 }

@@ -108,16 +108,33 @@ bool LoopState::advance(double dt, double end_time) {
     return false;
 }
 
-// A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K in the place of ramp and table (tdgl_set_link_terms has validated the arguments)
-void LoopState::set_terms(int n, bool a0, const int32_t *kind, const double *ramp, const int32_t *tab_off, const double *times,
-                          const double *values) {
-    links_static();
-    ramp_on = true, n_terms = n, term_a0 = a0, term_moves = 0;
+// ---- FieldDrive (tdgl_internal.h): the moving applied field on the host ---------------------------------------------------
+void FieldDrive::clear() {
+    form = STATIC, moves = false, n_terms = 0, n_loops = 0, a0 = false, n_moves = 0;
+    for (int k = 0; k < FIELD_TERMS_MAX; ++k) term[k] = FieldTerm{}, term_t[k].clear(), term_v[k].clear();
+    set_loops(0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+void FieldDrive::set_product(double s) {
+    clear();
+    form = PRODUCT, n_terms = 1;
+    scale[0] = scale_prev[0] = s;
+}
+
+void FieldDrive::set_product_source(int32_t kind, const double *ramp, const double *times, const double *values, int64_t n) {
+    term[0] = FieldTerm{};
+    term[0].kind = kind, term[0].n = (int32_t)n;
+    for (int j = 0; j < 4 && ramp; ++j) term[0].ramp[j] = ramp[j];
+    term_t[0].assign(times, times + n), term_v[0].assign(values, values + n);
+    moves = kind != TERM_HOST;
+}
+
+void FieldDrive::set_terms(int n, bool with_a0, const int32_t *kind, const double *ramp, const int32_t *tab_off, const double *times,
+                           const double *values) {
+    clear();
+    form = SUM, moves = true, n_terms = n, a0 = with_a0;
     int32_t off = 0;
-    for (int k = 0; k < FIELD_TERMS_MAX; ++k) {
-        term[k] = FieldTerm{};
-        term_t[k].clear(), term_v[k].clear();
-        if (k >= n) continue;
+    for (int k = 0; k < n; ++k) {
         term[k].kind = kind[k];
         if (kind[k] == TERM_TABLE) {
             term_t[k].assign(times + tab_off[k], times + tab_off[k + 1]);
@@ -127,57 +144,96 @@ void LoopState::set_terms(int n, bool a0, const int32_t *kind, const double *ram
         } else {
             for (int j = 0; j < 4; ++j) term[k].ramp[j] = ramp[4 * k + j];
         }
-        term_scale[k] = term_scale_prev[k] = term_value(k, 0.0);
+        scale[k] = scale_prev[k] = value(k, 0.0);
     }
 }
 
-void LoopState::copy_terms(const LoopState &o) {
-    links_static();
-    ramp_on = o.ramp_on, n_terms = o.n_terms, term_a0 = o.term_a0, term_moves = o.term_moves;
-    for (int k = 0; k < FIELD_TERMS_MAX; ++k) {
-        term[k] = o.term[k], term_t[k] = o.term_t[k], term_v[k] = o.term_v[k];
-        term_scale[k] = o.term_scale[k], term_scale_prev[k] = o.term_scale_prev[k];
-    }
-}
-
-double LoopState::term_value(int k, double t) const {
-    if (term[k].kind == TERM_TABLE) return table_value(term_t[k], term_v[k].data(), t);
-    return linear_ramp_value(t, term[k].ramp[0], term[k].ramp[1], term[k].ramp[2], term[k].ramp[3]);
-}
-
-bool LoopState::terms_step(const double *s, const double *lp) {
-    bool same = has_dadt;
-    for (int k = 0; k < n_terms; ++k) same = same && s[k] == term_scale[k] && s[k] == term_scale_prev[k];
-    for (int l = 0; l < n_loops; ++l)
-        for (int j = 0; j < 4; ++j) same = same && lp[4 * l + j] == loop_par[l][j] && lp[4 * l + j] == loop_par_prev[l][j];
-    if (same) return false;
-    for (int k = 0; k < n_terms; ++k) term_scale_prev[k] = term_scale[k], term_scale[k] = s[k];
-    for (int l = 0; l < n_loops; ++l)
-        for (int j = 0; j < 4; ++j) loop_par_prev[l][j] = loop_par[l][j], loop_par[l][j] = lp[4 * l + j];
-    term_moves += 1;
-    return true;
-}
-
-void LoopState::set_loops(int n, double z_film, const double *radius, const int32_t *tab_off, const double *times, const double *cx,
-                          const double *cy, const double *cz, const double *current) {
-    n_loops = n, loop_zfilm = z_film, term_moves = 0;
+void FieldDrive::set_loops(int n, double z_film, const double *radii, const int32_t *tab_off, const double *times, const double *cx,
+                           const double *cy, const double *cz, const double *current) {
+    n_loops = n, zfilm = z_film, n_moves = 0;
     const double *src[4] = {cx, cy, cz, current};
     for (int l = 0; l < FIELD_LOOPS_MAX; ++l) {
         loop_t[l].clear();
         for (int j = 0; j < 4; ++j) loop_v[l][j].clear(), loop_par[l][j] = loop_par_prev[l][j] = 0.0;
-        loop_radius[l] = 0.0;
+        radius[l] = 0.0;
         if (l >= n) continue;
-        loop_radius[l] = radius[l];
+        radius[l] = radii[l];
         loop_t[l].assign(times + tab_off[l], times + tab_off[l + 1]);
         for (int j = 0; j < 4; ++j) loop_v[l][j].assign(src[j] + tab_off[l], src[j] + tab_off[l + 1]);
         loop_values(l, 0.0, loop_par[l]);
         for (int j = 0; j < 4; ++j) loop_par_prev[l][j] = loop_par[l][j];
     }
-    ramp_on = n > 0 || n_terms > 0;
+    if (n > 0) moves = true;
 }
 
-void LoopState::loop_values(int l, double t, double *out4) const {
+double FieldDrive::value(int k, double t) const {
+    if (term[k].kind == TERM_TABLE) return table_value(term_t[k], term_v[k].data(), t);
+    if (term[k].kind == TERM_RAMP) return linear_ramp_value(t, term[k].ramp[0], term[k].ramp[1], term[k].ramp[2], term[k].ramp[3]);
+    return scale[k];  // (the caller's)
+}
+
+void FieldDrive::loop_values(int l, double t, double *out4) const {
     for (int j = 0; j < 4; ++j) out4[j] = table_value(loop_t[l], loop_v[l][j].data(), t);
+}
+
+void FieldDrive::values_at(double t, double *s, double *lp) const {
+    for (int k = 0; k < FIELD_TERMS_MAX; ++k) s[k] = k < n_terms ? value(k, t) : 0.0;
+    for (int l = 0; l < FIELD_LOOPS_MAX; ++l)
+        if (l < n_loops) loop_values(l, t, lp + 4 * l);
+}
+
+bool FieldDrive::step(const double *s, const double *lp) {
+    bool same = has_dadt;
+    for (int k = 0; k < n_terms; ++k) same = same && s[k] == scale[k] && s[k] == scale_prev[k];
+    for (int l = 0; l < n_loops; ++l)
+        for (int j = 0; j < 4; ++j) same = same && lp[4 * l + j] == loop_par[l][j] && lp[4 * l + j] == loop_par_prev[l][j];
+    if (same) return false;
+    for (int k = 0; k < n_terms; ++k) scale_prev[k] = scale[k], scale[k] = s[k];
+    for (int l = 0; l < n_loops; ++l)
+        for (int j = 0; j < 4; ++j) loop_par_prev[l][j] = loop_par[l][j], loop_par[l][j] = lp[4 * l + j];
+    n_moves += 1;
+    return true;
+}
+
+bool FieldDrive::settled(double time) const {
+    if (!moves) return false;
+    for (int k = 0; k < n_terms; ++k) {
+        const bool tab = term[k].kind == TERM_TABLE;
+        const double t_end = tab ? term_t[k].back() : term[k].ramp[1], f_end = tab ? term_v[k].back() : term[k].ramp[3];
+        if (!(time >= t_end && scale[k] == f_end && scale_prev[k] == f_end)) return false;
+    }
+    for (int l = 0; l < n_loops; ++l) {
+        if (!(time >= loop_t[l].back())) return false;
+        for (int j = 0; j < 4; ++j)
+            if (!(loop_par[l][j] == loop_v[l][j].back() && loop_par_prev[l][j] == loop_v[l][j].back())) return false;
+    }
+    return true;
+}
+
+void FieldDrive::fill(StepCtl &h) const {
+    h.has_dadt = has_dadt ? 1 : 0;
+    h.n_terms = n_terms, h.n_loops = n_loops;
+    for (int k = 0; k < n_terms; ++k) h.term_scale[k] = scale[k], h.term_scale_prev[k] = scale_prev[k];
+    for (int l = 0; l < n_loops; ++l)
+        for (int j = 0; j < 4; ++j) h.loop_par[l][j] = loop_par[l][j], h.loop_par_prev[l][j] = loop_par_prev[l][j];
+}
+
+void FieldDrive::absorb(const StepCtl &h) {
+    has_dadt = h.has_dadt != 0;
+    for (int k = 0; k < n_terms; ++k) scale[k] = h.term_scale[k], scale_prev[k] = h.term_scale_prev[k];
+    for (int l = 0; l < n_loops; ++l)
+        for (int j = 0; j < 4; ++j) loop_par[l][j] = h.loop_par[l][j], loop_par_prev[l][j] = h.loop_par_prev[l][j];
+    n_moves += h.n_term_moves;
+}
+
+void FieldDrive::describe(FieldTerm *desc, std::vector<double> &times, std::vector<double> &values) const {
+    for (int k = 0; k < FIELD_TERMS_MAX; ++k) {
+        desc[k] = k < n_terms ? term[k] : FieldTerm{};
+        if (k >= n_terms || term[k].kind != TERM_TABLE) continue;
+        desc[k].off = (int32_t)times.size();
+        times.insert(times.end(), term_t[k].begin(), term_t[k].end());
+        values.insert(values.end(), term_v[k].begin(), term_v[k].end());
+    }
 }
 
 // the device's controller at the start of a batch; live = false: poisoned from the first attempt on
@@ -198,14 +254,7 @@ void LoopState::fill(StepCtl &h, double end_time, bool live) const {
     h.retries = retries;
     h.poisoned = live ? 0 : 1;
     h.runner_dt = runner_dt;
-    h.ramp_tmin = ramp_tmin, h.ramp_tmax = ramp_tmax, h.ramp_initial = ramp_initial, h.ramp_final = ramp_final;
-    h.link_scale = link_scale, h.link_scale_prev = link_scale_prev;
-    h.has_dadt = has_dadt ? 1 : 0;
-    h.n_terms = terms() ? n_terms : 0, h.term_a0 = term_a0 ? 1 : 0;
-    for (int k = 0; k < h.n_terms; ++k) h.term_scale[k] = term_scale[k], h.term_scale_prev[k] = term_scale_prev[k];
-    h.n_loops = loops() ? n_loops : 0;
-    for (int l = 0; l < h.n_loops; ++l)
-        for (int j = 0; j < 4; ++j) h.loop_par[l][j] = loop_par[l][j], h.loop_par_prev[l][j] = loop_par_prev[l][j];
+    field.fill(h);
     if (ctl.adaptive) {
         const int64_t have = (int64_t)hist.size(), cnt = std::min<int64_t>(have, ctl.adaptive_window);
         h.hist_count = (int)cnt;
@@ -238,15 +287,7 @@ LoopState::Batch LoopState::absorb(const StepCtl &h, const StepRec *rec, int bat
     }
     b.reached = h.reached_end != 0;
     b.error = h.error != 0;
-    if (ramped) {
-        link_scale = h.link_scale;
-        link_scale_prev = h.link_scale_prev;
-        has_dadt = h.has_dadt != 0;
-        for (int k = 0; k < n_terms; ++k) term_scale[k] = h.term_scale[k], term_scale_prev[k] = h.term_scale_prev[k];
-        for (int l = 0; l < n_loops; ++l)
-            for (int j = 0; j < 4; ++j) loop_par[l][j] = h.loop_par[l][j], loop_par_prev[l][j] = h.loop_par_prev[l][j];
-        term_moves += h.n_term_moves;
-    }
+    if (ramped) field.absorb(h);
     cur = h.cur;
     retries = b.error ? 0 : h.retries;
     attempt_dt = h.attempt_dt;

@@ -143,7 +143,7 @@ static int ensure_laplacian_cache(tdgl_ctx *ctx) {
 // the plan of the step about to be taken (tdgl_internal.h: currents_plan)
 static tdgl_currents_plan step_plan(const tdgl_ctx *ctx) {
     return currents_plan({dense_on(ctx), distributed(ctx), !ctx->levels.empty(), ctx->popt.extrapolate, ctx->popt.edge_currents_every_step,
-                          ctx->loop.ramp_on, ctx->loop.has_dadt, ctx->sync_shadow_disabled, ctx->scr_enabled});
+                          ctx->loop.field.moves, ctx->loop.field.has_dadt, ctx->sync_shadow_disabled, ctx->scr_enabled});
 }
 
 // what the step drivers read from the first status block of a solve: did the psi update fail, max d|psi|^2.  Returns
@@ -408,9 +408,9 @@ static int step_screening(tdgl_ctx *ctx, double *dt_out, double *dmax_out) {
 static bool run_ahead_ok(const tdgl_ctx *ctx) {
     const bool off = ctx->run_ahead_disabled;  // (TDGL_NO_RUN_AHEAD at tdgl_create)
     const tdgl_controller &ctl = ctx->loop.ctl;
-    // (a moving vector potential: only the ramp, table or sum of terms the loop evaluates itself rides along -- k_ra_ramp_begin,
-    // k_ra_table_begin, k_ra_terms_begin --, and it needs the previous step's dt: from the second step of a stage on)
-    if (ctx->loop.ramping() ? !(ctx->loop.runner_dt > 0.0) : ctx->loop.has_dadt) return false;
+    // (a moving vector potential: only the field the loop evaluates itself rides along -- k_ra_field_begin --, and it needs the
+    // previous step's dt: from the second step of a stage on)
+    if (ctx->loop.ramping() ? !(ctx->loop.runner_dt > 0.0) : ctx->loop.field.has_dadt) return false;
     // (the plans of the direct solve: no screening, currents every step)
     return !off && dense_on(ctx) && (ctx->direct->dense.tiles > 0) && currents_plan_runs_ahead(step_plan(ctx)) &&
            (ctx->tab_mu_t.empty() || ctx->tab_mu_on_device) && (ctx->tab_eps_t.empty() || ctx->tab_eps_on_device) && ctx->have_links &&
@@ -471,40 +471,21 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
                                    (const double2 *)ctx->psi[0].p, (const double2 *)ctx->psi[1].p, (const double *)ctx->mu.p, ctx->js.p, ctx->jn.p,
                                    (const double *)ctx->e_dAdt.p, (const StepCtl *)dc);
             const int nblk = grid_for(ctx->m);
-            if (ctx->loop.loops()) {
-                // moving loops (on terms or on a static A): their begin and links kernels in the place of the terms' pair
-                const double *tab = ctx->d_term_tab.p;
-                LoopGeom g{};
-                g.n_loops = ctx->loop.n_loops, g.z_film = ctx->loop.loop_zfilm;
-                for (int l = 0; l < g.n_loops; ++l) g.radius[l] = ctx->loop.loop_radius[l];
-                hipLaunchKernelGGL(k_ra_loops_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const FieldTerm *)ctx->d_terms.p, tab,
-                                   tab + ctx->d_term_tab.n / 2, (const FieldLoop *)ctx->d_loops.p, (const double *)ctx->d_loop_tab.p,
-                                   (int)(ctx->d_loop_tab.n / 5));
-                hipLaunchKernelGGL(k_loops_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, TermScales{}, LoopPars{}, g,
-                                   (const double *)ctx->e_Tbase.p, (const double *)ctx->e_centres.p, ctx->e_A.p, ctx->e_Aprev.p,
-                                   (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
-                                   ctx->e_dAdt.p, ctx->link_block_changed.p, (const StepCtl *)dc);
-            } else if (ctx->loop.terms()) {
-                // a sum of terms: its own begin and links kernels in the place of the single product's pair
-                const double *tab = ctx->d_term_tab.p;
-                hipLaunchKernelGGL(k_ra_terms_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const FieldTerm *)ctx->d_terms.p, tab,
-                                   tab + ctx->d_term_tab.n / 2);
-                hipLaunchKernelGGL(k_terms_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, TermScales{},
-                                   (const double *)ctx->e_Tbase.p, ctx->e_A.p, ctx->e_Aprev.p, (const double *)ctx->e_dirx.p,
-                                   (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p, ctx->e_dAdt.p,
-                                   ctx->link_block_changed.p, (const StepCtl *)dc);
-            } else {
-                if (ctx->loop.tabulated()) {
-                    const int nn = (int)ctx->loop.tab_t.size();
-                    hipLaunchKernelGGL(k_ra_table_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const double *)ctx->d_tab_link.p,
-                                       (const double *)ctx->d_tab_link.p + nn, nn);
-                } else {
-                    hipLaunchKernelGGL(k_ra_ramp_begin, dim3(1), dim3(64), 0, ctx->stream, dc);
-                }
-                hipLaunchKernelGGL(k_ra_ramp_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, (const double *)ctx->e_Abase.p, ctx->e_A.p,
-                                   ctx->e_Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p,
-                                   ctx->e_dAdt.p, ctx->link_block_changed.p, (const StepCtl *)dc);
-            }
+            const FieldDrive &F = ctx->loop.field;
+            const FieldArrays &fa = ctx->field;
+            LoopGeom g{};
+            g.n_loops = F.n_loops, g.z_film = F.zfilm;
+            for (int l = 0; l < g.n_loops; ++l) g.radius[l] = F.radius[l];
+            const double *tab = fa.tab.p;
+            hipLaunchKernelGGL(k_ra_field_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const FieldTerm *)fa.terms.p, tab, tab + fa.tab.n / 2,
+                               (const FieldLoop *)fa.loops.p, (const double *)fa.loop_tab.p, (int)(fa.loop_tab.n / 5));
+#define TDGL_KLINKS(LOOPS)                                                                                                              \
+    hipLaunchKernelGGL((k_field_links<LOOPS>), dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, FieldValues{}, g,           \
+                       (const double *)fa.bases.p, (const double *)fa.a0.p, (const double *)fa.centres.p, ctx->e_A.p, ctx->e_Aprev.p,   \
+                       (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p, ctx->e_dAdt.p,   \
+                       ctx->link_block_changed.p, (const StepCtl *)dc)
+            if (F.loops()) TDGL_KLINKS(true); else TDGL_KLINKS(false);
+#undef TDGL_KLINKS
             hipLaunchKernelGGL(k_any_flag, dim3(1), dim3(BLOCK), 0, ctx->stream, nblk, (const int32_t *)ctx->link_block_changed.p,
                                ctx->link_changed.p, go);
             hipLaunchKernelGGL(k_ceff, dim3(grid_for((int64_t)ctx->lap_pat.n_slices * WAVE)), dim3(BLOCK), 0, ctx->stream,
@@ -609,7 +590,7 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
         // a ramp that has reached its end: dA/dt is identically zero from here on (the array holds zeros; the
         // kernels drop the term), with or without the run-ahead loop
         const bool settled = ctx->loop.ramp_settled();
-        if (settled && ctx->loop.has_dadt && !ctx->scr_enabled) ctx->loop.has_dadt = false;
+        if (settled && ctx->loop.field.has_dadt && !ctx->scr_enabled) ctx->loop.field.has_dadt = false;
         direct_policy(ctx);
         if (run_ahead_ok(ctx)) {
             const bool want_probes = out_mu_probe || out_theta_probe;
@@ -638,23 +619,13 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
             continue;
         }
         double dt = 0.0;
-        if (ctx->loop.ramp_on && !settled) {
-            // update_applied_vector_potential (solver.py:347-362, 626-642) for
-            // A(t) = ramp(t) * A_base, ramp = tdgl/sources/scaling.py LinearRamp; dA/dt uses the
-            // previous step's dt (Runner.dt)
-            // (or a table in the ramp's place: tdgl_set_link_table; or a sum of such terms: tdgl_set_link_terms)
-            // (... plus moving loops: tdgl_set_link_loops)
-            if (ctx->loop.terms() || ctx->loop.loops()) {
-                double s[FIELD_TERMS_MAX] = {0.0, 0.0, 0.0, 0.0}, lp[FIELD_LOOPS_MAX * 4] = {};
-                for (int j = 0; j < ctx->loop.n_terms; ++j) s[j] = ctx->loop.term_value(j, ctx->loop.time);
-                for (int l = 0; l < ctx->loop.n_loops; ++l) ctx->loop.loop_values(l, ctx->loop.time, lp + 4 * l);
-                status = ctx->loop.loops() ? update_link_loops(ctx, s, lp, ctx->loop.runner_dt) : update_link_terms(ctx, s, ctx->loop.runner_dt);
-            } else {
-                const double scale = ctx->loop.tabulated()
-                                         ? table_value(ctx->loop.tab_t, ctx->loop.tab_v.data(), ctx->loop.time)
-                                         : linear_ramp_value(ctx->loop.time, ctx->loop.ramp_tmin, ctx->loop.ramp_tmax, ctx->loop.ramp_initial, ctx->loop.ramp_final);
-                status = update_link_scale(ctx, scale, ctx->loop.runner_dt);
-            }
+        if (ctx->loop.field.moves && !settled) {
+            // update_applied_vector_potential (solver.py:347-362, 626-642) for the field the loop evaluates itself: every factor
+            // (tdgl/sources/scaling.py LinearRamp, or a table) and every loop's values at this time; dA/dt uses the previous
+            // step's dt (Runner.dt)
+            double s[FIELD_TERMS_MAX], lp[FIELD_LOOPS_MAX * 4] = {};
+            ctx->loop.field.values_at(ctx->loop.time, s, lp);
+            status = update_field(ctx, s, lp, ctx->loop.runner_dt);
         }
         if (status == TDGL_OK) status = apply_time_tables(ctx);  // tabulated terminal currents / epsilon factor at this time
         if (status == TDGL_OK)

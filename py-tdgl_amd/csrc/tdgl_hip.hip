@@ -592,7 +592,7 @@ static void launch_edge_currents(tdgl_ctx *ctx, const double2 *psi, const double
     if (end <= base) return;
     if (part != 2) ctx->stat_edge_launches += 1;  // (parts 1 and 2 together form the currents once)
     const int grid = grid_for(end - base);
-    const double *dadt = ctx->loop.has_dadt ? ctx->e_dAdt.p : (const double *)nullptr;
+    const double *dadt = ctx->loop.field.has_dadt ? ctx->e_dAdt.p : (const double *)nullptr;
     if (js && jn)
         hipLaunchKernelGGL((k_edge_currents<true, true>), dim3(grid), dim3(BLOCK), 0, ctx->stream, end,
                            ctx->e0.p, ctx->e1.p, ctx->e_inv_len.p, ctx->e_U.p, psi, mu, js, jn, dadt, base);
@@ -607,13 +607,11 @@ static void launch_edge_currents(tdgl_ctx *ctx, const double2 *psi, const double
 static void refresh_ceff(tdgl_ctx *ctx) {
     hipLaunchKernelGGL(k_ceff, dim3(grid_for((int64_t)ctx->lap_pat.n_slices * WAVE)), dim3(BLOCK), 0, ctx->stream,
                        ctx->lap_pat.n_slices, ctx->lap_pat.n_rows, ctx->lap_pat.slice_off.p, ctx->lap_slot_edge.p,
-                       ctx->lap_slot_w.p, ctx->e_inv_len.p, ctx->loop.has_dadt ? ctx->e_dAdt.p : (const double *)nullptr,
+                       ctx->lap_slot_w.p, ctx->e_inv_len.p, ctx->loop.field.has_dadt ? ctx->e_dAdt.p : (const double *)nullptr,
                        ctx->cvec.p, ctx->ceff.p);
 }
 
-static int update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev);  // below
-static int update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev);  // below
-static int update_link_loops(tdgl_ctx *ctx, const double *scales, const double *loop_params, double dt_prev);  // below
+static int update_field(tdgl_ctx *ctx, const double *scales, const double *loop_params, double dt_prev);  // below
 static int apply_time_tables(tdgl_ctx *ctx);                                 // below
 static double table_value(const std::vector<double> &t, const double *v, double time);  // below
 static int check_link_table(tdgl_ctx *ctx, const char *who, int32_t n_nodes, const double *times, const double *values);  // below
@@ -650,7 +648,7 @@ extern "C" int tdgl_update_link_exponents(tdgl_ctx *ctx, const double *A_new, do
 
 // everything that follows new values in ctx->e_A: dA/dt (dynamic) or A_prev <- A (static), the
 // rhs term of dA/dt, link variables, covariant-Laplacian values
-// (dadt_done: the caller's own kernel has formed dA/dt, A_prev and the per-workgroup flags already -- k_terms_links)
+// (dadt_done: the caller's own kernel has formed dA/dt, A_prev and the per-workgroup flags already -- k_field_links)
 static int finish_links(tdgl_ctx *ctx, bool dynamic, double dt_prev, bool dadt_done = false) {
     const size_t bytes = 2 * ctx->m_pad * sizeof(double);
     const int32_t *only_if = nullptr;
@@ -669,10 +667,10 @@ static int finish_links(tdgl_ctx *ctx, bool dynamic, double dt_prev, bool dadt_d
         // (with screening the links are rebuilt from A_applied + A_induced in every screening
         // iteration anyway, solver.py:670-673)
         only_if = ctx->link_changed.p;
-        ctx->loop.has_dadt = true;
+        ctx->loop.field.has_dadt = true;
     } else {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->e_Aprev.p, ctx->e_A.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        ctx->loop.has_dadt = false;
+        ctx->loop.field.has_dadt = false;
     }
     refresh_ceff(ctx);
     hipLaunchKernelGGL(k_link_variables, dim3(grid_for(ctx->m)), dim3(BLOCK), 0, ctx->stream, ctx->m,
@@ -704,53 +702,102 @@ static int set_links_impl(tdgl_ctx *ctx, const double *A, bool dynamic, double d
     CTX_GUARD(ctx);
     if (!A) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_exponents: null A");
     TDGL_TRY(upload_edge_vectors(ctx, A, ctx->e_A.p));
-    ctx->loop.links_static();
+    ctx->loop.field.clear();
     TDGL_TRY(finish_links(ctx, dynamic, dt_prev));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
 }
 
-// ---- A(t) = scale(t) * A_base without leaving the device ---------------------------------------
-extern "C" int tdgl_set_link_exponents_base(tdgl_ctx *ctx, const double *A_base, double scale) {
-    CTX_GUARD(ctx);
-    if (!A_base) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_exponents_base: null A_base");
-    if (ctx->e_Abase.n == 0) HIP_TRY(ctx, ctx->e_Abase.alloc(2 * ctx->m_pad));
-    TDGL_TRY(upload_edge_vectors(ctx, A_base, ctx->e_Abase.p));
-    ctx->have_base = true;
-    ctx->loop.links_static();
-    hipLaunchKernelGGL(k_scale_links, dim3(grid_for(2 * ctx->m_pad)), dim3(BLOCK), 0, ctx->stream, 2 * ctx->m_pad,
-                       scale, ctx->e_Abase.p, ctx->e_A.p);
-    ctx->loop.link_scale = ctx->loop.link_scale_prev = scale;
+// ---- the moving applied field (FieldDrive ctx->loop.field, its arrays ctx->field) without leaving the device ---------------
+// the one launch that forms A, dA/dt, A_prev <- A and the per-workgroup "did it move" from the values given
+static int launch_field_links(tdgl_ctx *ctx, const double *scales, const double *lp, double inv_dt) {
+    const int nblk = grid_for(ctx->m);
+    if (ctx->link_block_changed.n == 0) {
+        HIP_TRY(ctx, ctx->link_block_changed.alloc(nblk));
+        HIP_TRY(ctx, ctx->link_changed.alloc(1));
+    }
+    const FieldDrive &F = ctx->loop.field;
+    FieldValues fv{};
+    LoopGeom g{};
+    for (int k = 0; k < F.n_terms; ++k) fv.s[k] = scales[k];
+    fv.inv_dt = inv_dt, fv.n_terms = F.n_terms;
+    g.n_loops = F.n_loops, g.z_film = F.zfilm;
+    for (int l = 0; l < F.n_loops; ++l) {
+        g.radius[l] = F.radius[l];
+        for (int j = 0; j < 4; ++j) fv.lp[l][j] = lp[4 * l + j];
+    }
+    const FieldArrays &a = ctx->field;
+#define TDGL_KLINKS(LOOPS)                                                                                                             \
+    hipLaunchKernelGGL((k_field_links<LOOPS>), dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, fv, g, (const double *)a.bases.p, \
+                       (const double *)a.a0.p, (const double *)a.centres.p, ctx->e_A.p, ctx->e_Aprev.p, (const double *)ctx->e_dirx.p, \
+                       (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p, ctx->e_dAdt.p, ctx->link_block_changed.p,      \
+                       (const StepCtl *)nullptr)
+    if (F.loops()) TDGL_KLINKS(true); else TDGL_KLINKS(false);
+#undef TDGL_KLINKS
+    return TDGL_OK;
+}
+
+// A = A_prev = the field at the values in force, dA/dt = 0 (the links kernel against A_prev = 0 with 1 / dt = 0), the links,
+// the Laplacian values
+static int restart_field(tdgl_ctx *ctx) {
+    HIP_TRY(ctx, hipMemsetAsync(ctx->e_Aprev.p, 0, 2 * (size_t)ctx->m_pad * sizeof(double), ctx->stream));
+    TDGL_TRY(launch_field_links(ctx, ctx->loop.field.scale, &ctx->loop.field.loop_par[0][0], 0.0));
     TDGL_TRY(finish_links(ctx, false, 0.0));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
 }
 
-static int update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev) {
-    // nothing moves when the factor has been constant over the last two evaluations (A and
-    // dA/dt = 0 are already in place)
-    if (scale == ctx->loop.link_scale && scale == ctx->loop.link_scale_prev && ctx->loop.has_dadt) return TDGL_OK;
-    hipLaunchKernelGGL(k_scale_links, dim3(grid_for(2 * ctx->m_pad)), dim3(BLOCK), 0, ctx->stream, 2 * ctx->m_pad,
-                       scale, ctx->e_Abase.p, ctx->e_A.p);
-    ctx->loop.link_scale_prev = ctx->loop.link_scale;
-    ctx->loop.link_scale = scale;
-    return finish_links(ctx, true, dt_prev);
+// the descriptors and table pool of the drive's terms as the begin kernel reads them
+static int upload_term_tables(tdgl_ctx *ctx, const FieldDrive &F, FieldArrays &a) {
+    std::vector<FieldTerm> desc(FIELD_TERMS_MAX);
+    std::vector<double> tt, tv;
+    F.describe(desc.data(), tt, tv);
+    if (tt.empty()) tt.push_back(0.0), tv.push_back(0.0);  // (never read: no term is a table)
+    tt.insert(tt.end(), tv.begin(), tv.end());
+    HIP_TRY(ctx, a.terms.upload(desc));
+    HIP_TRY(ctx, a.tab.upload(tt));
+    return TDGL_OK;
+}
+
+// the step of the loop with one synchronisation per step: the step rule, then the links where something moves
+static int update_field(tdgl_ctx *ctx, const double *scales, const double *lp, double dt_prev) {
+    if (!ctx->loop.field.step(scales, lp)) return TDGL_OK;  // (A and dA/dt = 0 are already in place)
+    TDGL_TRY(launch_field_links(ctx, scales, lp, 1.0 / dt_prev));
+    return finish_links(ctx, true, dt_prev, true);
+}
+
+// A(t) = scale(t) * A_base: the single product, its factor the caller's until a ramp or a table is switched on
+extern "C" int tdgl_set_link_exponents_base(tdgl_ctx *ctx, const double *A_base, double scale) {
+    CTX_GUARD(ctx);
+    if (!A_base) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_exponents_base: null A_base");
+    FieldArrays next;
+    HIP_TRY(ctx, next.bases.alloc(2 * ctx->m_pad));
+    TDGL_TRY(upload_edge_vectors(ctx, A_base, next.bases.p));
+    ctx->field.take(next);
+    ctx->loop.field.set_product(scale);
+    return restart_field(ctx);
 }
 
 extern "C" int tdgl_update_link_scale(tdgl_ctx *ctx, double scale, double dt_prev) {
     CTX_GUARD(ctx);
-    if (!ctx->have_base) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_exponents_base first");
+    if (!ctx->loop.field.product()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_exponents_base first");
     if (!(dt_prev > 0.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_scale: dt_prev must be > 0");
-    TDGL_TRY(update_link_scale(ctx, scale, dt_prev));
+    TDGL_TRY(update_field(ctx, &scale, nullptr, dt_prev));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
 }
 
 extern "C" int tdgl_set_link_ramp(tdgl_ctx *ctx, int32_t on, double tmin, double tmax, double initial, double final_) {
     CTX_GUARD(ctx);
-    if (on && !ctx->have_base) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_exponents_base first");
+    FieldDrive &F = ctx->loop.field;
+    if (on && !F.product()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_exponents_base first");
     if (on && !(tmax > tmin)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_link_ramp: tmax must be > tmin");
-    ctx->loop.set_ramp(on != 0, tmin, tmax, initial, final_);
+    if (!F.product()) return TDGL_OK;  // (off, and there is no product whose factor could be the caller's again)
+    const double q[4] = {tmin, tmax, initial, final_};
+    FieldDrive next = F;
+    next.set_product_source(on ? TERM_RAMP : TERM_HOST, q, nullptr, nullptr, 0);
+    if (on) TDGL_TRY(upload_term_tables(ctx, next, ctx->field));
+    F = next;
     return TDGL_OK;
 }
 
@@ -758,32 +805,17 @@ extern "C" int tdgl_set_link_ramp(tdgl_ctx *ctx, int32_t on, double tmin, double
 // in the place of the ramp -- a table and a ramp exclude each other, the later call wins
 extern "C" int tdgl_set_link_table(tdgl_ctx *ctx, int32_t n_nodes, const double *times, const double *values) {
     CTX_GUARD(ctx);
+    FieldDrive &F = ctx->loop.field;
     if (n_nodes == 0) {  // off (a ramp stays)
-        if (ctx->loop.tabulated()) ctx->loop.links_static();
+        if (F.product() && F.term[0].kind == TERM_TABLE) F.set_product_source(TERM_HOST, nullptr, nullptr, nullptr, 0);
         return TDGL_OK;
     }
-    if (!ctx->have_base) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_exponents_base first");
+    if (!F.product()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_exponents_base first");
     TDGL_TRY(check_link_table(ctx, "tdgl_set_link_table", n_nodes, times, values));
-    std::vector<double> both(times, times + n_nodes);
-    both.insert(both.end(), values, values + n_nodes);
-    HIP_TRY(ctx, ctx->d_tab_link.upload(both));
-    ctx->loop.set_table(times, values, n_nodes);
-    return TDGL_OK;
-}
-
-// ---- A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K without leaving the device ------------------------------------------
-static int launch_terms_links(tdgl_ctx *ctx, const double *scales, double inv_dt) {
-    const int nblk = grid_for(ctx->m);
-    if (ctx->link_block_changed.n == 0) {
-        HIP_TRY(ctx, ctx->link_block_changed.alloc(nblk));
-        HIP_TRY(ctx, ctx->link_changed.alloc(1));
-    }
-    TermScales ts{};
-    for (int k = 0; k < ctx->loop.n_terms; ++k) ts.s[k] = scales[k];
-    ts.inv_dt = inv_dt, ts.n_terms = ctx->loop.n_terms, ts.a0 = ctx->loop.term_a0 ? 1 : 0;
-    hipLaunchKernelGGL(k_terms_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, ts, (const double *)ctx->e_Tbase.p,
-                       ctx->e_A.p, ctx->e_Aprev.p, (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p,
-                       (const double *)ctx->e_inv_len.p, ctx->e_dAdt.p, ctx->link_block_changed.p, (const StepCtl *)nullptr);
+    FieldDrive next = F;
+    next.set_product_source(TERM_TABLE, nullptr, times, values, n_nodes);
+    TDGL_TRY(upload_term_tables(ctx, next, ctx->field));
+    F = next;
     return TDGL_OK;
 }
 
@@ -810,118 +842,65 @@ static int check_link_terms(tdgl_ctx *ctx, const char *who, int32_t n_terms, con
     return TDGL_OK;
 }
 
+// A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K
 extern "C" int tdgl_set_link_terms(tdgl_ctx *ctx, const double *A0, int32_t n_terms, const double *bases, const int32_t *kind,
                                    const double *ramp, const int32_t *tab_off, const double *tab_times, const double *tab_values) {
     CTX_GUARD(ctx);
     TDGL_TRY(check_link_terms(ctx, "tdgl_set_link_terms", n_terms, bases, kind, ramp, tab_off, tab_times, tab_values));
     // (nothing of the state in force has been touched so far; the device's copies are complete before the loop hears of them)
     const size_t slot = 2 * (size_t)ctx->m_pad;
-    DevBuf<double> tb;
-    HIP_TRY(ctx, tb.alloc((size_t)(n_terms + 1) * slot));
-    if (A0) TDGL_TRY(upload_edge_vectors(ctx, A0, tb.p));
-    for (int32_t k = 0; k < n_terms; ++k) TDGL_TRY(upload_edge_vectors(ctx, bases + (size_t)k * 2 * ctx->m, tb.p + (size_t)(k + 1) * slot));
-    LoopState next;
-    next.set_terms(n_terms, A0 != nullptr, kind, ramp, tab_off, tab_times, tab_values);
-    std::vector<FieldTerm> desc(next.term, next.term + n_terms);
-    std::vector<double> tt, tv;
-    for (int32_t k = 0; k < n_terms; ++k) {
-        tt.insert(tt.end(), next.term_t[k].begin(), next.term_t[k].end());
-        tv.insert(tv.end(), next.term_v[k].begin(), next.term_v[k].end());
+    FieldArrays next;
+    HIP_TRY(ctx, next.bases.alloc((size_t)n_terms * slot));
+    for (int32_t k = 0; k < n_terms; ++k) TDGL_TRY(upload_edge_vectors(ctx, bases + (size_t)k * 2 * ctx->m, next.bases.p + (size_t)k * slot));
+    if (A0) {
+        HIP_TRY(ctx, next.a0.alloc(slot));
+        TDGL_TRY(upload_edge_vectors(ctx, A0, next.a0.p));
     }
-    if (tt.empty()) tt.push_back(0.0), tv.push_back(0.0);  // (never read: no term is a table)
-    tt.insert(tt.end(), tv.begin(), tv.end());
-    DevBuf<FieldTerm> d_desc;
-    DevBuf<double> d_tab;
-    HIP_TRY(ctx, d_desc.upload(desc));
-    HIP_TRY(ctx, d_tab.upload(tt));
-    ctx->e_Tbase.take(tb);
-    ctx->d_terms.take(d_desc);
-    ctx->d_term_tab.take(d_tab);
-    ctx->loop.copy_terms(next);
-    // A = A(0) (the links kernel against A_prev = 0 with 1 / dt = 0: dA/dt = 0), then A_prev <- A, the links, the Laplacian values
-    HIP_TRY(ctx, hipMemsetAsync(ctx->e_Aprev.p, 0, slot * sizeof(double), ctx->stream));
-    TDGL_TRY(launch_terms_links(ctx, ctx->loop.term_scale, 0.0));
-    TDGL_TRY(finish_links(ctx, false, 0.0));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TDGL_OK;
-}
-
-static int update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev) {
-    if (!ctx->loop.terms_step(scales)) return TDGL_OK;  // (A and dA/dt = 0 are already in place)
-    TDGL_TRY(launch_terms_links(ctx, scales, 1.0 / dt_prev));
-    return finish_links(ctx, true, dt_prev, true);
+    FieldDrive drive;
+    drive.set_terms(n_terms, A0 != nullptr, kind, ramp, tab_off, tab_times, tab_values);
+    TDGL_TRY(upload_term_tables(ctx, drive, next));
+    ctx->field.take(next);
+    ctx->loop.field = drive;
+    return restart_field(ctx);
 }
 
 extern "C" int tdgl_update_link_terms(tdgl_ctx *ctx, const double *scales, double dt_prev) {
     CTX_GUARD(ctx);
-    if (!ctx->loop.terms()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_terms first");
-    if (ctx->loop.loops()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "moving loops are set: tdgl_update_link_loops moves the whole sum");
+    const FieldDrive &F = ctx->loop.field;
+    if (!F.sum()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_terms first");
+    if (F.loops()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "moving loops are set: tdgl_update_link_loops moves the whole sum");
     if (!scales) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_terms: null scales");
-    for (int k = 0; k < ctx->loop.n_terms; ++k)
+    for (int k = 0; k < F.n_terms; ++k)
         if (!std::isfinite(scales[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_terms: non-finite factor");
     if (!(dt_prev > 0.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_terms: dt_prev must be > 0");
-    TDGL_TRY(update_link_terms(ctx, scales, dt_prev));
+    TDGL_TRY(update_field(ctx, scales, nullptr, dt_prev));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
 }
 
-// ---- ... plus moving current loops: A(t) = [that] + sum_l I_l(t) Aloop(r_e - c_l(t); a_l) --------------------------------
-static int launch_loops_links(tdgl_ctx *ctx, const double *scales, const double *lp, double inv_dt) {
-    const int nblk = grid_for(ctx->m);
-    if (ctx->link_block_changed.n == 0) {
-        HIP_TRY(ctx, ctx->link_block_changed.alloc(nblk));
-        HIP_TRY(ctx, ctx->link_changed.alloc(1));
-    }
-    const LoopState &L = ctx->loop;
-    TermScales ts{};
-    for (int k = 0; k < L.n_terms; ++k) ts.s[k] = scales[k];
-    ts.inv_dt = inv_dt, ts.n_terms = L.n_terms, ts.a0 = L.term_a0 ? 1 : 0;
-    LoopPars hp{};
-    LoopGeom g{};
-    g.n_loops = L.n_loops, g.z_film = L.loop_zfilm;
-    for (int l = 0; l < L.n_loops; ++l) {
-        g.radius[l] = L.loop_radius[l];
-        for (int j = 0; j < 4; ++j) hp.p[l][j] = lp[4 * l + j];
-    }
-    hipLaunchKernelGGL(k_loops_links, dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, ts, hp, g, (const double *)ctx->e_Tbase.p,
-                       (const double *)ctx->e_centres.p, ctx->e_A.p, ctx->e_Aprev.p, (const double *)ctx->e_dirx.p,
-                       (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p, ctx->e_dAdt.p, ctx->link_block_changed.p,
-                       (const StepCtl *)nullptr);
-    return TDGL_OK;
-}
-
-// A = A_prev = the field at the values in force, dA/dt = 0 (the links kernel against A_prev = 0 with 1 / dt = 0), the links,
-// the Laplacian values -- with the loops, or with the terms alone once the loops are gone
-static int restart_sources(tdgl_ctx *ctx) {
-    HIP_TRY(ctx, hipMemsetAsync(ctx->e_Aprev.p, 0, 2 * (size_t)ctx->m_pad * sizeof(double), ctx->stream));
-    if (ctx->loop.loops())
-        TDGL_TRY(launch_loops_links(ctx, ctx->loop.term_scale, &ctx->loop.loop_par[0][0], 0.0));
-    else
-        TDGL_TRY(launch_terms_links(ctx, ctx->loop.term_scale, 0.0));
-    TDGL_TRY(finish_links(ctx, false, 0.0));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TDGL_OK;
-}
-
+// ... plus moving current loops: A(t) = [that] + sum_l I_l(t) Aloop(r_e - c_l(t); a_l), on a sum or on a static A (which
+// becomes the drive's A_0)
 extern "C" int tdgl_set_link_loops(tdgl_ctx *ctx, int32_t n_loops, const double *edge_centres, double z_film, const double *radius,
                                    const int32_t *tab_off, const double *tab_times, const double *tab_cx, const double *tab_cy,
                                    const double *tab_cz, const double *tab_current) {
     CTX_GUARD(ctx);
     const char *who = "tdgl_set_link_loops";
+    FieldDrive &F = ctx->loop.field;
     if (n_loops == 0) {  // the loops go; what they were added to stays, at the values in force
-        if (!ctx->loop.loops()) return TDGL_OK;
-        ctx->loop.set_loops(0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-        if (ctx->loop.terms()) return restart_sources(ctx);
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->e_A.p, ctx->e_Tbase.p, 2 * (size_t)ctx->m_pad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        ctx->loop.links_static();
-        TDGL_TRY(finish_links(ctx, false, 0.0));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (!F.loops()) return TDGL_OK;
+        F.set_loops(0, 0.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        TDGL_TRY(restart_field(ctx));
+        if (!F.sum()) {  // (they stood on a static A: static links again)
+            FieldArrays none;
+            ctx->field.take(none);
+            F.clear();
+        }
         return TDGL_OK;
     }
     // everything is checked before anything in force is touched
     if (n_loops < 1 || n_loops > FIELD_LOOPS_MAX) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: n_loops must be in [0, %d]", who, FIELD_LOOPS_MAX);
     if (!ctx->have_links) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "%s: call tdgl_set_link_exponents or tdgl_set_link_terms first", who);
-    if (ctx->loop.ramp_on && !ctx->loop.terms() && !ctx->loop.loops())
+    if (F.product() && F.moves)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: a single ramped or tabulated product is in force; loops go with a static field or with tdgl_set_link_terms", who);
     if (!edge_centres || !radius || !tab_off || !tab_times || !tab_cx || !tab_cy || !tab_cz || !tab_current)
         TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: null argument", who);
@@ -943,14 +922,13 @@ extern "C" int tdgl_set_link_loops(tdgl_ctx *ctx, int32_t n_loops, const double 
                 TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: loop %d: the loop's plane must differ from the film's (cz != z_film, on one side of it) at every node", who, l);
     }
     const size_t slot = 2 * (size_t)ctx->m_pad;
-    DevBuf<double> centres, base0, d_tab;
-    DevBuf<FieldLoop> d_desc;
-    HIP_TRY(ctx, centres.alloc(slot));
-    TDGL_TRY(upload_edge_vectors(ctx, edge_centres, centres.p));
-    const bool fresh = !ctx->loop.terms() && !ctx->loop.loops();  // on a static A: that A becomes slot 0
+    FieldArrays next;
+    HIP_TRY(ctx, next.centres.alloc(slot));
+    TDGL_TRY(upload_edge_vectors(ctx, edge_centres, next.centres.p));
+    const bool fresh = !F.sum() && !F.loops();  // on a static A: that A becomes A_0, with no products
     if (fresh) {
-        HIP_TRY(ctx, base0.alloc(slot));
-        HIP_TRY(ctx, hipMemcpyAsync(base0.p, ctx->e_A.p, slot * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(ctx, next.a0.alloc(slot));
+        HIP_TRY(ctx, hipMemcpyAsync(next.a0.p, ctx->e_A.p, slot * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     }
     const int32_t T = tab_off[n_loops];
     std::vector<FieldLoop> desc((size_t)n_loops);
@@ -960,50 +938,43 @@ extern "C" int tdgl_set_link_loops(tdgl_ctx *ctx, int32_t n_loops, const double 
     pool.insert(pool.end(), tab_cy, tab_cy + T);
     pool.insert(pool.end(), tab_cz, tab_cz + T);
     pool.insert(pool.end(), tab_current, tab_current + T);
-    HIP_TRY(ctx, d_desc.upload(desc));
-    HIP_TRY(ctx, d_tab.upload(pool));
-    if (ctx->d_terms.n == 0) {  // (k_ra_loops_begin reads no term, but is handed valid pointers)
-        HIP_TRY(ctx, ctx->d_terms.upload(std::vector<FieldTerm>(1, FieldTerm{})));
-        HIP_TRY(ctx, ctx->d_term_tab.upload(std::vector<double>(2, 0.0)));
-    }
+    HIP_TRY(ctx, next.loops.upload(desc));
+    HIP_TRY(ctx, next.loop_tab.upload(pool));
+    if (fresh) TDGL_TRY(upload_term_tables(ctx, FieldDrive{}, next));  // (the begin kernel reads no term, but is handed valid pointers)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (fresh) ctx->e_Tbase.take(base0);
-    ctx->e_centres.take(centres);
-    ctx->d_loops.take(d_desc);
-    ctx->d_loop_tab.take(d_tab);
-    ctx->loop.set_loops(n_loops, z_film, radius, tab_off, tab_times, tab_cx, tab_cy, tab_cz, tab_current);
-    return restart_sources(ctx);
-}
-
-static int update_link_loops(tdgl_ctx *ctx, const double *scales, const double *lp, double dt_prev) {
-    if (!ctx->loop.terms_step(scales, lp)) return TDGL_OK;  // (A and dA/dt = 0 are already in place)
-    TDGL_TRY(launch_loops_links(ctx, scales, lp, 1.0 / dt_prev));
-    return finish_links(ctx, true, dt_prev, true);
+    if (fresh) {
+        F.clear(), F.a0 = true;
+        ctx->field.bases.release(), ctx->field.a0.take(next.a0), ctx->field.terms.take(next.terms), ctx->field.tab.take(next.tab);
+    }
+    ctx->field.centres.take(next.centres), ctx->field.loops.take(next.loops), ctx->field.loop_tab.take(next.loop_tab);
+    F.set_loops(n_loops, z_film, radius, tab_off, tab_times, tab_cx, tab_cy, tab_cz, tab_current);
+    return restart_field(ctx);
 }
 
 extern "C" int tdgl_update_link_loops(tdgl_ctx *ctx, const double *term_scales, const double *loop_params, double dt_prev) {
     CTX_GUARD(ctx);
-    if (!ctx->loop.loops()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_loops first");
-    if (!loop_params || (ctx->loop.n_terms > 0 && !term_scales)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: null argument");
-    for (int k = 0; k < ctx->loop.n_terms; ++k)
+    const FieldDrive &F = ctx->loop.field;
+    if (!F.loops()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_link_loops first");
+    if (!loop_params || (F.n_terms > 0 && !term_scales)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: null argument");
+    for (int k = 0; k < F.n_terms; ++k)
         if (!std::isfinite(term_scales[k])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: non-finite factor");
-    for (int l = 0; l < ctx->loop.n_loops; ++l) {
+    for (int l = 0; l < F.n_loops; ++l) {
         for (int j = 0; j < 4; ++j)
             if (!std::isfinite(loop_params[4 * l + j])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: non-finite loop value");
-        if (loop_params[4 * l + 2] == ctx->loop.loop_zfilm)
+        if (loop_params[4 * l + 2] == F.zfilm)
             TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: loop %d lies in the film's plane", l);
     }
     if (!(dt_prev > 0.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_link_loops: dt_prev must be > 0");
-    TDGL_TRY(update_link_loops(ctx, term_scales, loop_params, dt_prev));
+    TDGL_TRY(update_field(ctx, term_scales, loop_params, dt_prev));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
 }
 
 extern "C" int tdgl_get_link_loop_params(tdgl_ctx *ctx, int32_t *n_loops, double *params) {
     if (!ctx || !n_loops || !params) return TDGL_ERR_ARG;
-    *n_loops = ctx->loop.loops() ? ctx->loop.n_loops : 0;
+    *n_loops = ctx->loop.field.n_loops;
     for (int l = 0; l < *n_loops; ++l)
-        for (int j = 0; j < 4; ++j) params[4 * l + j] = ctx->loop.loop_par[l][j];
+        for (int j = 0; j < 4; ++j) params[4 * l + j] = ctx->loop.field.loop_par[l][j];
     return TDGL_OK;
 }
 
@@ -1024,20 +995,20 @@ extern "C" int tdgl_get_link_exponents(tdgl_ctx *ctx, double *A) {
 
 extern "C" int tdgl_get_link_term_moves(tdgl_ctx *ctx, int64_t *moves) {
     if (!ctx || !moves) return TDGL_ERR_ARG;
-    *moves = ctx->loop.terms() || ctx->loop.loops() ? ctx->loop.term_moves : 0;
+    *moves = ctx->loop.field.sum() || ctx->loop.field.loops() ? ctx->loop.field.n_moves : 0;
     return TDGL_OK;
 }
 
 extern "C" int tdgl_get_link_term_scales(tdgl_ctx *ctx, int32_t *n_terms, double *scales) {
     if (!ctx || !n_terms || !scales) return TDGL_ERR_ARG;
-    *n_terms = ctx->loop.terms() ? ctx->loop.n_terms : 0;
-    for (int k = 0; k < *n_terms; ++k) scales[k] = ctx->loop.term_scale[k];
+    *n_terms = ctx->loop.field.sum() ? ctx->loop.field.n_terms : 0;
+    for (int k = 0; k < *n_terms; ++k) scales[k] = ctx->loop.field.scale[k];
     return TDGL_OK;
 }
 
 extern "C" int tdgl_get_link_scale(tdgl_ctx *ctx, double *scale) {
     if (!ctx || !scale) return TDGL_ERR_ARG;
-    *scale = ctx->loop.link_scale;
+    *scale = ctx->loop.field.sum() ? 1.0 : ctx->loop.field.scale[0];  // (the single product's factor)
     return TDGL_OK;
 }
 

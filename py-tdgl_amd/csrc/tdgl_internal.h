@@ -202,17 +202,17 @@ constexpr int GUESS_MAX = 16;  // maximal window of the projection guess (kernel
 // classic way with a smaller dt) or behind the step that reached end_time.
 constexpr int RA_HIST_MAX = 128;   // adaptive_window up to here (numpy's pairwise sum has no recursion below 129 terms)
 constexpr int RA_BATCH_MAX = 64;
-// A sum of field terms A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K (tdgl_set_link_terms): at most this many products, and
-// where the factor of one of them comes from -- a LinearRamp (ramp: tmin, tmax, initial, final) or a table (nodes off ..
-// off + n of the owner's pools of times and values)
+// A moving applied field A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K + sum_l I_l(t) Aloop(r - c_l(t); a_l) (FieldDrive below): at
+// most this many products, and where the factor of one of them comes from -- the caller (tdgl_update_link_scale), a LinearRamp
+// (ramp: tmin, tmax, initial, final) or a table (nodes off .. off + n of the owner's pools of times and values)
 constexpr int FIELD_TERMS_MAX = 4;
-enum : int32_t { TERM_RAMP = 1, TERM_TABLE = 2 };
+enum : int32_t { TERM_HOST = 0, TERM_RAMP = 1, TERM_TABLE = 2 };
 struct FieldTerm {
     int32_t kind, off, n, pad;
     double ramp[4];
 };
-// Moving current loops on top of that field (tdgl_set_link_loops): A += I_l(t) Aloop(r - c_l(t); a_l) for at most this many
-// loops; a loop's four tables (centre x, y, z and current) share the nodes off .. off + n of the owner's pools
+// ... and at most this many moving current loops (tdgl_set_link_loops); a loop's four tables (centre x, y, z and current) share
+// the nodes off .. off + n of the owner's pools
 constexpr int FIELD_LOOPS_MAX = 2;
 struct FieldLoop {
     int32_t off, n;
@@ -237,20 +237,14 @@ struct StepCtl {
     int hist_count;
     int pad;
     double hist[RA_HIST_MAX];  // the last min(window, count) values of max d|psi|^2, oldest first
-    // field ramp evaluated inside the loop (k_ra_ramp_begin): A(t) = ramp(t) A_base
+    // the moving applied field evaluated inside the loop (k_ra_field_begin; FieldDrive::fill / absorb)
     double runner_dt;          // Runner.dt: dt of the previous accepted step (the dA/dt of this one divides by it)
-    double ramp_tmin, ramp_tmax, ramp_initial, ramp_final;
-    double link_scale, link_scale_prev;
-    int has_dadt;              // a dynamic update has run (update_link_scale's early return needs one)
+    int has_dadt;              // a dynamic update has run (the step rule's "nothing moves" needs one)
     int ramp_do;               // this attempt is the first of a step and the vector potential moves
-    // ... or a sum of field terms (k_ra_terms_begin; n_terms = 0: the single product above): the factors of the current /
-    // previous A, term by term; term_a0: the sum starts from a static A_0
-    int n_terms, term_a0;
-    int n_term_moves, pad2;    // attempts of this batch that moved the sum (ran the body of the links kernel)
+    int n_terms, n_loops;      // products and loops of the field
+    int n_term_moves, pad2;    // attempts of this batch that moved the field (ran the body of the links kernel)
+    // the factors of the current / previous A, term by term; centre x, y, z and current of the current / previous A, loop by loop
     double term_scale[FIELD_TERMS_MAX], term_scale_prev[FIELD_TERMS_MAX];
-    // ... plus moving current loops (k_ra_loops_begin; n_loops = 0: none): centre x, y, z and current of the current /
-    // previous A, loop by loop.  The step rule covers them with the factors; n_term_moves counts moves of the whole sum
-    int n_loops, pad3;
     double loop_par[FIELD_LOOPS_MAX][4], loop_par_prev[FIELD_LOOPS_MAX][4];
 };
 struct StepRec {
@@ -258,12 +252,83 @@ struct StepRec {
     int ok, pad;
 };
 
+// The device arrays of a FieldDrive, one set per context and per replica of an ensemble: the K bases (slot k at 2 m_pad k,
+// edge-permuted), the optional A_0, the descriptors with their table pool (all times, then all values), and for loops the
+// edge centres, the loops' descriptors and their pool (all times, then all cx, cy, cz, currents)
+struct FieldArrays {
+    DevBuf<double> bases, a0, tab, centres, loop_tab;
+    DevBuf<FieldTerm> terms;
+    DevBuf<FieldLoop> loops;
+    void take(FieldArrays &o) {
+        bases.take(o.bases), a0.take(o.a0), tab.take(o.tab), centres.take(o.centres), loop_tab.take(o.loop_tab);
+        terms.take(o.terms), loops.take(o.loops);
+    }
+};
+
+// One description of a moving applied field, whatever entry point gave it:
+//   A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K + sum_l I_l(t) Aloop(r - c_l(t); a_l)
+// with K <= FIELD_TERMS_MAX products, an optional static part A_0 and L <= FIELD_LOOPS_MAX moving current loops.  A factor
+// is a LinearRamp, a piecewise-linear table, or supplied by the caller step by step (TERM_HOST: tdgl_update_link_scale).
+// A single product f(t) A_base (tdgl_set_link_exponents_base, _ramp, _table) is the sum with K = 1 and no A_0; a static A
+// under loops is A_0 with K = 0.  The device's arrays (FieldArrays) belong to the drive's owner.  Its functions (loop.inc)
+// are the one step rule, the one "has it settled" and the one way in and out of the device's controller.
+struct FieldDrive {
+    enum Form : int32_t { STATIC, PRODUCT, SUM };  // which entry point described it (the refusals and getters ask)
+    Form form = STATIC;
+    bool moves = false;     // the time loop evaluates the field before every step
+    bool has_dadt = false;  // a dynamic update has run: e_dAdt holds the dA/dt of the links in force
+    int n_terms = 0, n_loops = 0;
+    bool a0 = false;
+    int64_t n_moves = 0;    // steps that moved the field since it was set (tdgl_get_link_term_moves)
+    FieldTerm term[FIELD_TERMS_MAX] = {};
+    std::vector<double> term_t[FIELD_TERMS_MAX], term_v[FIELD_TERMS_MAX];       // a table term's nodes (the host's copy)
+    double scale[FIELD_TERMS_MAX] = {1, 0, 0, 0}, scale_prev[FIELD_TERMS_MAX] = {1, 0, 0, 0};  // factors of the current / previous A
+    double zfilm = 0.0, radius[FIELD_LOOPS_MAX] = {0, 0};
+    std::vector<double> loop_t[FIELD_LOOPS_MAX], loop_v[FIELD_LOOPS_MAX][4];    // a loop's nodes: centre x, y, z and current
+    double loop_par[FIELD_LOOPS_MAX][4] = {}, loop_par_prev[FIELD_LOOPS_MAX][4] = {};  // those four of the current / previous A
+
+    bool product() const { return form == PRODUCT; }
+    bool sum() const { return form == SUM; }
+    bool loops() const { return n_loops > 0; }
+    // static links: no products, no loops, nothing the loop evaluates (the single product's last factor stays readable)
+    void clear();
+    // the single product f(t) A_base with the caller's factor (tdgl_set_link_exponents_base) ...
+    void set_product(double s);
+    // ... and where its factor comes from: a ramp, a table (n nodes), or the caller again (TERM_HOST).  The factor in force stays
+    void set_product_source(int32_t kind, const double *ramp, const double *times, const double *values, int64_t n);
+    // the sum (validated by the caller: check_link_terms); the factors start at their values at t = 0
+    void set_terms(int n, bool with_a0, const int32_t *kind, const double *ramp, const int32_t *tab_off, const double *times,
+                   const double *values);
+    // moving loops on top of the field in force (validated by the caller: tdgl_set_link_loops); the values start at t = 0.
+    // n = 0: the loops go
+    void set_loops(int n, double z_film, const double *radii, const int32_t *tab_off, const double *times, const double *cx,
+                   const double *cy, const double *cz, const double *current);
+    double value(int k, double t) const;                    // f_k(t): linear_ramp_value / table_value
+    void loop_values(int l, double t, double *out4) const;  // centre x, y, z and current of loop l at t (table_value)
+    // the factors and loop values the loop's own evaluation gives at t: s[FIELD_TERMS_MAX], lp[4 FIELD_LOOPS_MAX]
+    void values_at(double t, double *s, double *lp) const;
+    // The step rule (solver.py:626-642 with the reference's early return): false -- nothing moves, every factor and every loop's
+    // four values equal their last two evaluations and a dynamic update has run; true -- the values are taken over (the
+    // caller moves the links)
+    bool step(const double *s, const double *lp);
+    // A LinearRamp (tdgl/sources/scaling.py:4-14) is constant from t_max on, a table from its last node on.  Once the time has
+    // passed every term's and every loop's end and every value has been seen twice at its end value -- the first evaluation
+    // still sees dA/dt != 0, the second writes dA/dt = 0 (solver.py:626-642) -- the vector potential is static for the rest of
+    // the stage: no dA/dt term, no per-step update, and the run-ahead loop can take over.
+    bool settled(double time) const;
+    void fill(StepCtl &h) const;
+    void absorb(const StepCtl &h);
+    // the descriptors and the table pool (all times, then all values) as the device reads them; off: where this drive's nodes
+    // start in a pool shared with others
+    void describe(FieldTerm *desc, std::vector<double> &times, std::vector<double> &values) const;
+};
+
 // The time loop's bookkeeping on the host, one per trajectory (tdgl_ctx, every replica of an ensemble): the controller
 // (solver.py:316-320, 475-485, 698-707), Runner.dt / time / step (runner.py:260-263, 429-433), the retry state a run-ahead
-// batch leaves behind and the field ramp A(t) = LinearRamp(t) A_base.  The classic loop drives it event by event (begin_step,
+// batch leaves behind and the moving applied field (FieldDrive).  The classic loop drives it event by event (begin_step,
 // retry, accept, advance); the run-ahead and ensemble loops hand it to the device (fill) and take it back (absorb), where
 // step_controller applies the same rules.  Its functions (loop.inc) are the only writers of the controller, loop and retry
-// members; the ramp members are also written by the link setters, which own the arrays they describe (finish_links).
+// members; the field drive is written by the link setters, which own the arrays it describes (finish_links).
 struct LoopState {
     tdgl_controller ctl{1e-6, 1e-1, 1, 10, 10, 0.25};
     double tentative_dt = 1e-6, dt_cap = 1e-1, runner_dt = 1e-6, time = 0.0;
@@ -272,28 +337,7 @@ struct LoopState {
     int cur = 0;               // which psi / L psi buffer holds psi^n
     int retries = 0;           // failed attempts of the step in progress (outlives a run-ahead batch) ...
     double attempt_dt = 0.0;   // ... and the dt its next attempt takes
-    bool ramp_on = false, has_dadt = false;
-    double ramp_tmin = 0.0, ramp_tmax = 1.0, ramp_initial = 0.0, ramp_final = 1.0;
-    double link_scale = 1.0, link_scale_prev = 1.0;  // scale of the current / previous A
-    // ... or the factor as a piecewise-linear table A(t) = table(t) A_base (tdgl_set_link_table; non-empty: the table is the
-    // source of the factor and ramp_tmin .. ramp_final are unused).  The host's copy of the nodes; the device's is its owner's
-    std::vector<double> tab_t, tab_v;
-    // ... or a sum A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K (tdgl_set_link_terms; n_terms = K > 0: the terms are the source
-    // of A and everything above but ramp_on and has_dadt is unused).  Every factor is a ramp (term[k].ramp) or a table
-    // (term_t[k], term_v[k]); term_scale / term_scale_prev: the factors of the current / previous A
-    int n_terms = 0;
-    bool term_a0 = false;
-    int64_t term_moves = 0;  // steps that moved the sum since it was set (tdgl_get_link_term_moves)
-    tdgl::FieldTerm term[tdgl::FIELD_TERMS_MAX] = {};
-    std::vector<double> term_t[tdgl::FIELD_TERMS_MAX], term_v[tdgl::FIELD_TERMS_MAX];
-    double term_scale[tdgl::FIELD_TERMS_MAX] = {0, 0, 0, 0}, term_scale_prev[tdgl::FIELD_TERMS_MAX] = {0, 0, 0, 0};
-    // ... plus n_loops moving current loops on top of the terms (n_terms > 0) or of a static A (n_terms = 0), set by
-    // tdgl_set_link_loops: per loop the radius and four piecewise-linear tables on shared nodes loop_t[l] -- centre x, y, z and
-    // current (loop_v[l][0 .. 3]); loop_par / loop_par_prev: those four values of the current / previous A
-    int n_loops = 0;
-    double loop_zfilm = 0.0, loop_radius[tdgl::FIELD_LOOPS_MAX] = {0, 0};
-    std::vector<double> loop_t[tdgl::FIELD_LOOPS_MAX], loop_v[tdgl::FIELD_LOOPS_MAX][4];
-    double loop_par[tdgl::FIELD_LOOPS_MAX][4] = {}, loop_par_prev[tdgl::FIELD_LOOPS_MAX][4] = {};
+    FieldDrive field;          // the applied field the loop moves, if any
     // what absorb tells its caller about a batch.  corrupt: 1 impossible counts, 2 the records disagree with the controller
     // (the state is void); last_accepted: index of the last accepted record
     struct Batch {
@@ -308,33 +352,6 @@ struct LoopState {
     void restore(int64_t step, double t, double rdt) { stage_step = step, time = t, runner_dt = rdt; }
     void restore_controller(double tentative, const double *h, int64_t n) { tentative_dt = tentative, retries = 0, hist.assign(h, h + n); }
     void new_state(int buffer) { cur = buffer, retries = 0; }  // a new psi in psi[buffer] (tdgl_set_state): no step is in progress
-    void set_ramp(bool on, double tmin, double tmax, double initial, double final_) {
-        ramp_on = on, ramp_tmin = tmin, ramp_tmax = tmax, ramp_initial = initial, ramp_final = final_;
-        tab_t.clear(), tab_v.clear(), n_terms = 0, n_loops = 0;
-    }
-    void set_table(const double *times, const double *values, int64_t n) {  // n = 0: off
-        ramp_on = n > 0, tab_t.assign(times, times + n), tab_v.assign(values, values + n), n_terms = 0, n_loops = 0;
-    }
-    void links_static() { ramp_on = false, tab_t.clear(), tab_v.clear(), n_terms = 0, n_loops = 0; }  // (a setter of static links: neither ramp, table, terms nor loops)
-    bool tabulated() const { return ramp_on && !tab_t.empty(); }
-    // the sum of terms in the place of ramp and table (validated by the caller: tdgl_set_link_terms); the factors start at
-    // their values at t = 0
-    void set_terms(int n, bool a0, const int32_t *kind, const double *ramp, const int32_t *tab_off, const double *times, const double *values);
-    void copy_terms(const LoopState &o);
-    bool terms() const { return ramp_on && n_terms > 0; }
-    double term_value(int k, double t) const;  // f_k(t): linear_ramp_value / table_value
-    double term_end_time(int k) const { return term[k].kind == tdgl::TERM_TABLE ? term_t[k].back() : term[k].ramp[1]; }
-    double term_end_value(int k) const { return term[k].kind == tdgl::TERM_TABLE ? term_v[k].back() : term[k].ramp[3]; }
-    // the step rule of the sum (update_link_scale's, term by term): false -- nothing moves, every factor equals its last two
-    // evaluations and a dynamic update has run; true -- the factors are taken over (the caller moves the links)
-    // (with loops: ... and every loop's four values lp[4 l ..] equal their last two evaluations)
-    bool terms_step(const double *s, const double *lp = nullptr);
-    // moving loops on top of the field in force (validated by the caller: tdgl_set_link_loops); the values start at t = 0.
-    // n = 0: the loops go, and with them ramp_on when no terms are left under them
-    void set_loops(int n, double z_film, const double *radius, const int32_t *tab_off, const double *times, const double *cx,
-                   const double *cy, const double *cz, const double *current);
-    bool loops() const { return ramp_on && n_loops > 0; }
-    void loop_values(int l, double t, double *out4) const;  // centre x, y, z and current of loop l at t (table_value)
     std::string budget_message(int replica, double dt) const;
     void report(int64_t *step, double *time_, double *runner_dt_, double *tentative) const;
     // the classic loop's step: its first attempt takes tentative_dt (solver.py:666-668); a step begun by the run-ahead loop and
@@ -344,27 +361,8 @@ struct LoopState {
     bool retry();
     void accept(double dt, double dmax);
     bool advance(double dt, double end_time);
-    // A LinearRamp (tdgl/sources/scaling.py:4-14) is constant from t_max on.  Once the loop has evaluated it twice at its final
-    // value -- the first evaluation still sees dA/dt != 0, the second writes dA/dt = 0 (solver.py:626-642) -- the vector
-    // potential is static for the rest of the stage: no dA/dt term, no per-step update, and the run-ahead loop can take over.
-    // A table is constant from its last node on, at that node's value: the same rule.
-    // A sum of terms is settled once the time has passed every term's end and every factor has been seen twice at its end value.
-    // Loops are settled once the time has passed every table's last node and their values have been seen twice there.
-    bool ramp_settled() const {
-        if (terms() || loops()) {
-            for (int k = 0; k < n_terms; ++k)
-                if (!(time >= term_end_time(k) && term_scale[k] == term_end_value(k) && term_scale_prev[k] == term_end_value(k))) return false;
-            for (int l = 0; l < n_loops; ++l) {
-                if (!(time >= loop_t[l].back())) return false;
-                for (int j = 0; j < 4; ++j)
-                    if (!(loop_par[l][j] == loop_v[l][j].back() && loop_par_prev[l][j] == loop_v[l][j].back())) return false;
-            }
-            return true;
-        }
-        const double t_end = tabulated() ? tab_t.back() : ramp_tmax, f_end = tabulated() ? tab_v.back() : ramp_final;
-        return ramp_on && time >= t_end && link_scale == f_end && link_scale_prev == f_end;
-    }
-    bool ramping() const { return ramp_on && !ramp_settled(); }
+    bool ramp_settled() const { return field.settled(time); }
+    bool ramping() const { return field.moves && !ramp_settled(); }
     void fill(tdgl::StepCtl &h, double end_time, bool live) const;
     Batch absorb(const tdgl::StepCtl &h, const tdgl::StepRec *rec, int batch, int limit, bool ramped, double *out_dt);
     void trim() {  // bound the history: only the last `window` entries are ever read
@@ -611,11 +609,9 @@ struct tdgl_ctx {
     tdgl::DevBuf<double> e_inv_len, e_dirx, e_diry;
     tdgl::DevBuf<double2> e_U;
     tdgl::DevBuf<double> e_A, e_Aprev;    // link exponents now / at the previous step [2 * m_pad]
-    tdgl::DevBuf<double> e_dAdt;          // dA/dt along the edges (time-dependent A: loop.has_dadt), else unused
+    tdgl::DevBuf<double> e_dAdt;          // dA/dt along the edges (time-dependent A: loop.field.has_dadt), else unused
     tdgl::DevBuf<int32_t> link_block_changed, link_changed;  // allclose(new_A, old_A) test (k_dadt)
-    // A(t) = scale(t) * A_base on the device (tdgl_set_link_exponents_base / _scale / _ramp)
-    tdgl::DevBuf<double> e_Abase;
-    bool have_base = false;
+    tdgl::FieldArrays field;              // the device arrays of loop.field (tdgl_set_link_exponents_base, _terms, _loops)
     // Piecewise-linear time tables evaluated by tdgl_run itself before every step (no Python round
     // trip per step): terminal current densities -> mu_boundary (tdgl_set_mu_boundary_table) and a
     // time-dependent factor of epsilon (tdgl_set_epsilon_table)
@@ -629,16 +625,6 @@ struct tdgl_ctx {
     tdgl::DevBuf<int32_t> d_b_sites;                 // the sites that boundary edges touch, each once
     int32_t n_b_sites = 0;
     bool tab_mu_on_device = false;
-    tdgl::DevBuf<double> d_tab_link;                 // the field factor's table on the device: n times, then n values (k_ra_table_begin; host copy: loop.tab_t / tab_v)
-    // a sum of field terms (tdgl_set_link_terms): A_0 (slot 0, zeros without one) and the K bases (slots 1 .. K), 2 m_pad each,
-    // edge-permuted; the terms' descriptors and their tables' nodes (all times, then all values) for k_ra_terms_begin
-    tdgl::DevBuf<double> e_Tbase, d_term_tab;
-    tdgl::DevBuf<tdgl::FieldTerm> d_terms;
-    // moving current loops (tdgl_set_link_loops): the edge centres (x, y per edge, edge-permuted), the loops' descriptors and
-    // their tables' nodes (all times, then all cx, cy, cz, currents) for k_ra_loops_begin.  Under loops e_Tbase always holds
-    // slot 0 (the static A they were added to when there are no terms)
-    tdgl::DevBuf<double> e_centres, d_loop_tab;
-    tdgl::DevBuf<tdgl::FieldLoop> d_loops;
     tdgl::DevBuf<double> d_tab_eps_t, d_tab_eps_f;   // the epsilon factor's table on the device (k_ra_eps_table)
     bool tab_eps_on_device = false;
     std::vector<double> tab_eps_t, tab_eps_f;

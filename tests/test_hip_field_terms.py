@@ -65,7 +65,7 @@ def _solve(monkeypatch, options, run_ahead=True, A=None, probe_points=PROBES, **
     solver.ctx.step_stats(reset=True)
     sol = solver.solve()
     out = dict(sol=sol, stats=solver.ctx.step_stats(), scales=solver.ctx.link_term_scales(), moves=solver.ctx.link_term_moves(),
-               device_evaluates=solver.device_evaluates_field())
+               link_scale=solver.ctx.link_scale(), device_evaluates=solver.device_evaluates_field())
     solver.ctx.close()
     return out
 
@@ -261,6 +261,34 @@ def test_two_terms_without_a_static_part_and_a_factor_that_starts_at_zero(direct
     assert list(run["scales"]) == [1.0, 0.5]
 
 
+# one factor two ways: a LinearRamp, and a three-node table that holds its first value (the step rule skips there) and then rises
+ONE_FACTOR = {"ramp": dict(tmin=0.1, tmax=0.6, initial=0.25, final=1.0), "table": ([0.05, 0.35, 0.7], [0.4, 0.4, 1.0])}
+
+
+@pytest.mark.parametrize("run_ahead", [True, False], ids=["run_ahead", "classic"])
+@pytest.mark.parametrize("form", ["ramp", "table"])
+def test_a_single_product_and_a_sum_of_one_term_are_one_field(direct_solve, monkeypatch, form, run_ahead):
+    """A(t) = f(t) A_1 described through the single product's entry points (`vector_potential_ramp` /
+    `vector_potential_table`) and as `vector_potential_terms=(None, [(A_1, spec)])`: one drive, one step rule and one links
+    kernel behind both, so nothing may differ -- in the run-ahead loop and in the loop with one synchronisation per step."""
+    A1 = uniform_field_A(_mesh(), 0.2)
+    spec = ONE_FACTOR[form]
+    single_kw = dict(vector_potential_ramp=(A1, spec)) if form == "ramp" else dict(vector_potential_table=(A1, *spec))
+    one = _solve(monkeypatch, _options(), run_ahead=run_ahead, A=factor_value(spec, 0.0) * A1, **single_kw)
+    summed = _solve(monkeypatch, _options(), run_ahead=run_ahead, vector_potential_terms=(None, [(A1, spec)]))
+    a, b = one["sol"], summed["sol"]
+    assert len(a.dynamics.dt) > 10 and one["device_evaluates"] and summed["device_evaluates"]
+    assert np.array_equal(a.dynamics.dt, b.dynamics.dt)
+    assert np.array_equal(a.tdgl_data.psi, b.tdgl_data.psi)
+    assert np.array_equal(a.tdgl_data.mu, b.tdgl_data.mu)
+    assert np.array_equal(a.tdgl_data.supercurrent, b.tdgl_data.supercurrent)
+    assert np.array_equal(a.tdgl_data.normal_current, b.tdgl_data.normal_current)
+    assert len(a.saved_steps) == len(b.saved_steps) >= 2
+    for s, t in zip(a.saved_steps, b.saved_steps):
+        assert np.array_equal(s.applied_vector_potential, t.applied_vector_potential)
+    assert len(one["scales"]) == 0 and list(summed["scales"]) == [one["link_scale"]] == [1.0]
+
+
 def test_a_single_product_keeps_its_own_entry_points(direct_solve, monkeypatch):
     """TabulatedRamp * <static field> with no static part still goes through tdgl_set_link_exponents_base and
     tdgl_set_link_table, and a sum goes through tdgl_set_link_terms: seen by spying on the context's methods."""
@@ -323,7 +351,8 @@ def _assert_like_single(ens, one, tol):
 
 
 def test_ensemble_of_a_static_a_tabulated_and_a_two_term_replica(direct_solve, monkeypatch):
-    """R = 3: a static field, a single table and the fixture's two-term sum in one ensemble, each replica against the
+    """R = 4: a static field, a single table, the fixture's two-term sum and a single LinearRamp product in one ensemble
+    (every kind of replica behind the one pair of field launches), each replica against the
     single run of the same input with the checks, the tolerance (1e-8) and the options of
     tests/test_hip_ensemble_dynamic.py::test_field_ramps_with_lagging_links: fixed dt = 1e-3, pcg_rtol 1e-12."""
     from tdgl_amd.ensemble import ensemble_dimensionless
@@ -334,15 +363,18 @@ def test_ensemble_of_a_static_a_tabulated_and_a_two_term_replica(direct_solve, m
     terms = fixture_terms(g)
     table = (g["A1"], [0.3, 1.1, 2.0], [0.2, 1.0, -0.4])
     static = 0.8 * g["A1"]
-    sols = ensemble_dimensionless(_mesh(), opts, [static, None, None], 1.0, U_DEFAULT, GAMMA_DEFAULT, probe_points=PROBES,
-                                  vector_potential_table=[None, table, None], vector_potential_terms=[None, None, terms]).solve()
-    assert len(sols) == 3
+    ramp = (g["A1"], dict(tmin=0.4, tmax=2.5, initial=0.1, final=0.9))
+    sols = ensemble_dimensionless(_mesh(), opts, [static, None, None, None], 1.0, U_DEFAULT, GAMMA_DEFAULT, probe_points=PROBES,
+                                  vector_potential_table=[None, table, None, None], vector_potential_terms=[None, None, terms, None],
+                                  vector_potential_ramp=[None, None, None, ramp]).solve()
+    assert len(sols) == 4
     singles = [
         _solve(monkeypatch, opts, A=static)["sol"],
         _solve(monkeypatch, opts, A=0.2 * g["A1"], vector_potential_table=table)["sol"],
         _solve(monkeypatch, opts, vector_potential_terms=terms)["sol"],
+        _solve(monkeypatch, opts, A=0.1 * g["A1"], vector_potential_ramp=ramp)["sol"],
     ]
-    for r in range(3):
+    for r in range(4):
         _assert_like_single(sols[r], singles[r], 1e-8)
     # the two-term replica ended settled, its saved A the sum at the end values, exactly as the single run's
     assert np.array_equal(sols[2].tdgl_data.applied_vector_potential, singles[2].tdgl_data.applied_vector_potential)
