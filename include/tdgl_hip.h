@@ -903,6 +903,43 @@ int tdgl_vcycle(tdgl_ctx *ctx, const double *r, double *z);
  * the factor sweeps against a host model of the stored factors.  TDGL_ERR_NOT_READY (with a message) without factors,
  * when the factors are the mu SOLVER rather than the preconditioner, and in one-process-per-GPU contexts. */
 int tdgl_precond_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz);
+/* The block low-rank form of a symmetric matrix of order n (the preconditioner's top separator; layout: csrc/kernels.inc
+ * at BlrArgs), as the product builds it: nt = ceil(n / 128) row blocks of 128 rows, the tiles (I, J),
+ * J <= I, either dense fp32 tiles or pairs of fp32 factor columns.  Filled in two calls: with every array pointer NULL a
+ * call sets the counts only; the caller then allocates
+ *   dense_ij [ndense]  (I << 16 | J),  Gd [ndense * 128 * 128],  F [cols * 128],  colbase [nt + 1],  twin [cols],
+ *   items [nitems * 4]  (K, g0, g1, 0),  dslot_ptr [nt + 1],  dslot [ndslot]
+ * (one element more where a count is 0 keeps the pointer non-NULL), leaves the counts as they are, and calls again: the
+ * arrays are filled.  Some arrays NULL and some not, or counts that are not the ones of this matrix: TDGL_ERR_ARG. */
+typedef struct {
+    int64_t n, nt;
+    int64_t ndense, nitems, cols, ndslot;          /* dense tiles, wavefront items, columns (padded), dense slots */
+    int64_t pairs, rank_max, bytes, dense_bytes;   /* as tdgl_get_precond_direct_blr reports them */
+    int32_t *dense_ij;
+    float *Gd;
+    float *F;
+    int64_t *colbase;
+    int32_t *twin;
+    int32_t *items;
+    int32_t *dslot_ptr;
+    int32_t *dslot;
+} tdgl_blr_form;
+/* Host-only, no context: the form of the symmetric G [n x n] (row major, fp64; the lower triangle is read and packed into
+ * zero-padded 128 x 128 tiles exactly as the product's are) with every off-diagonal tile compressed to the ABSOLUTE
+ * tolerance tol_abs (the product passes tau * ||G||_2).  The compression, the placement of the columns, the items, the
+ * dense slots and the byte counts are the product's own code; its policy (the norm estimate, the minimum of 8 tiles,
+ * the 60 % rule) is not applied.  TDGL_ERR_ARG: a NULL argument, n < 1, tol_abs < 0 or not a number. */
+int tdgl_host_blr_form(int64_t n, const double *G, double tol_abs, tdgl_blr_form *form);
+/* The same arrays for the form the context's preconditioner STORES, copied back from the device.  TDGL_ERR_NOT_READY (with
+ * a message) when the top separator is not in block low-rank form (tdgl_get_precond_direct_blr: not in use). */
+int tdgl_get_precond_direct_blr_form(tdgl_ctx *ctx, tdgl_blr_form *form);
+/* The two kernels of the form alone (k_blr_project, k_blr_finish): the form of G as tdgl_host_blr_form builds it, uploaded
+ * into buffers of this call, applied to each of the n_vec vectors of X [n_vec][n] through the launch sequence of the
+ * preconditioner (ceil(n / 64) finishing workgroups; no status block, no controller, no u); Y [n_vec][n] = the results.
+ * form: NULL, or as above -- the form this call built.  Any context will do: it lends its device and stream, its factors
+ * and the CG's state stay as they are.  TDGL_ERR_ARG (with a message): a NULL array, n < 1, n_vec < 1, tol_abs < 0. */
+int tdgl_blr_apply(tdgl_ctx *ctx, int64_t n, const double *G, double tol_abs, int64_t n_vec, const double *X, double *Y,
+                   tdgl_blr_form *form);
 /* The dot-product pass of the projection guess (k_multi_dot) on caller-supplied vectors [k, n] and b [n]
  * (k <= 16): out_pairs[2 a], out_pairs[2 a + 1] = (hi, lo) double-double sums of array a in {0: b . b,
  * 1: sum b, 2 + j: y_j . b, 18 + j: y_newest . y_j (newest = -1: zeros)}; 2 * 34 doubles. */

@@ -848,6 +848,147 @@ static double env_double(const char *name, double dflt) {
     return (end && end != env && v > 0.0) ? v : dflt;
 }
 
+// The block low-rank form of a symmetric matrix, on the host: everything dense_to_blr uploads and reports.  The arrays
+// are the ones kernels.inc documents (BlrArgs) at their true lengths: `items` is empty when no row block has a column,
+// `F` and `twin` when there is no column at all (blr_upload puts a placeholder element in their place on the device).
+struct BlrForm {
+    std::vector<int32_t> dense_ij;         // [ndense] I << 16 | J, in tile order
+    std::vector<float> Gd;                 // [ndense][DT * DT]
+    std::vector<float> F;                  // [cols * DT]
+    std::vector<int64_t> colbase;          // [nt + 1]
+    std::vector<int32_t> twin;             // [cols]
+    std::vector<int32_t> items;            // [nitems][4] BlrItem
+    std::vector<int32_t> dslot_ptr, dslot;  // [nt + 1], [dslot_ptr[nt]]
+    int ndense = 0, nitems = 0;
+    int64_t cols = 0, pairs = 0, rank_max = 0, bytes = 0, dense_bytes = 0;
+};
+
+// The fp64 tiles hG (tile t = I (I + 1) / 2 + J, J <= I, DT x DT row major, zero beyond n) of a symmetric matrix of order
+// n in nt tiles per side -> its block low-rank form: every off-diagonal tile compressed to the absolute tolerance
+// tol_abs (blr_compress_block, at most DT / 4 columns: else the tile stays dense), the columns placed, the wavefront
+// items, the dense slots, the byte counts.  A pure function of its arguments (the tiles are padded: n itself is not
+// needed); the compression runs on up to 16 host threads.
+static BlrForm blr_form_host(const double *hG, int64_t n, int nt, double tol_abs) {
+    (void)n;
+    BlrForm Z;
+    const int64_t ntile = (int64_t)nt * (nt + 1) / 2, T2 = (int64_t)DT * DT;
+    // every off-diagonal tile, on up to 16 host threads (tile order: t = I (I + 1) / 2 + J)
+    const int kmax = DT / 4;
+    std::vector<int> rank((size_t)ntile, -1);
+    std::vector<std::vector<double>> Qs((size_t)ntile), Ws((size_t)ntile);
+    std::atomic<int64_t> next{0};
+    auto work = [&]() {
+        for (int64_t t; (t = next.fetch_add(1)) < ntile;) {
+            int I = (int)((std::sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+            while ((int64_t)(I + 1) * (I + 2) / 2 <= t) ++I;
+            while ((int64_t)I * (I + 1) / 2 > t) --I;
+            if (t - (int64_t)I * (I + 1) / 2 == I) continue;  // (diagonal tile: dense)
+            rank[t] = blr_compress_block(&hG[(size_t)t * T2], DT, tol_abs, kmax, Qs[t], Ws[t]);
+        }
+    };
+    {
+        const int nth = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+        std::vector<std::thread> pool;
+        for (int k = 1; k < nth; ++k) pool.emplace_back(work);
+        work();
+        for (auto &th : pool) th.join();
+    }
+    // columns per row block, in pair order: U_IJ in block I, W_IJ in block J
+    std::vector<int64_t> R((size_t)nt, 0), posU((size_t)ntile, 0), posW((size_t)ntile, 0);
+    std::vector<int32_t> &dense_ij = Z.dense_ij;
+    std::vector<char> is_dense((size_t)ntile, 0);
+    for (int I = 0; I < nt; ++I)
+        for (int J = 0; J <= I; ++J) {
+            const int64_t t = (int64_t)I * (I + 1) / 2 + J;
+            if (rank[t] < 0) {
+                is_dense[t] = 1;
+                dense_ij.push_back((I << 16) | J);
+                continue;
+            }
+            posU[t] = R[I];
+            R[I] += rank[t];
+            posW[t] = R[J];
+            R[J] += rank[t];
+            Z.pairs += 1;
+            Z.rank_max = std::max<int64_t>(Z.rank_max, rank[t]);
+        }
+    std::vector<int64_t> &colbase = Z.colbase;
+    colbase.assign((size_t)nt + 1, 0);
+    for (int K = 0; K < nt; ++K) colbase[K + 1] = colbase[K] + round_up(R[K], 4);
+    Z.cols = colbase[nt];
+    Z.ndense = (int)dense_ij.size();
+    Z.dense_bytes = ntile * T2 * (int64_t)sizeof(float);
+    Z.bytes = (int64_t)Z.ndense * T2 * (int64_t)sizeof(float) + 2 * Z.cols * DT * (int64_t)sizeof(float);
+    std::vector<float> &F = Z.F, &Gd = Z.Gd;
+    std::vector<int32_t> &twin = Z.twin;
+    F.assign((size_t)(Z.cols * DT), 0.0f);
+    Gd.assign((size_t)Z.ndense * T2, 0.0f);
+    twin.assign((size_t)Z.cols, -1);
+    for (int I = 0, d = 0; I < nt; ++I)
+        for (int J = 0; J <= I; ++J) {
+            const int64_t t = (int64_t)I * (I + 1) / 2 + J;
+            if (is_dense[t]) {
+                for (int64_t e = 0; e < T2; ++e) Gd[(size_t)d * T2 + e] = (float)hG[(size_t)t * T2 + e];
+                ++d;
+                continue;
+            }
+            const int r = rank[t];
+            for (int c = 0; c < r; ++c) {
+                const int64_t cu = posU[t] + c, cw = posW[t] + c;
+                for (int row = 0; row < DT; ++row) {
+                    const int h = row / WAVE, rl = row % WAVE;
+                    F[(size_t)(DT * colbase[I] + ((int64_t)h * (colbase[I + 1] - colbase[I]) + cu) * WAVE + rl)] = (float)Qs[t][(size_t)c * DT + row];
+                    F[(size_t)(DT * colbase[J] + ((int64_t)h * (colbase[J + 1] - colbase[J]) + cw) * WAVE + rl)] = (float)Ws[t][(size_t)c * DT + row];
+                }
+                twin[(size_t)(colbase[I] + cu)] = (int32_t)(colbase[J] + cw);
+                twin[(size_t)(colbase[J] + cw)] = (int32_t)(colbase[I] + cu);
+            }
+        }
+    std::vector<int32_t> &items = Z.items, &dslot_ptr = Z.dslot_ptr, &dslot = Z.dslot;
+    dslot_ptr.assign((size_t)nt + 1, 0);
+    for (int K = 0; K < nt; ++K) {
+        const int32_t ng = (int32_t)((colbase[K + 1] - colbase[K]) / 4);
+        for (int32_t g0 = 0; g0 < ng; g0 += BLR_ITEM_GROUPS) {
+            items.insert(items.end(), {K, g0, std::min<int32_t>(g0 + BLR_ITEM_GROUPS, ng), 0});
+        }
+        for (int J = 0; J < nt; ++J) {
+            const int I = std::max(K, J), Jm = std::min(K, J);
+            if (is_dense[(size_t)((int64_t)I * (I + 1) / 2 + Jm)]) dslot.push_back(J);
+        }
+        dslot_ptr[K + 1] = (int32_t)dslot.size();
+    }
+    Z.nitems = (int)(items.size() / 4);
+    return Z;
+}
+
+// The form's arrays onto the device and its counts into Z (coef zeroed; Z.tol and Z.norm are the caller's).  Arrays that
+// may be empty get one placeholder element (four for F and the items): the kernels are handed no null pointer.
+static int blr_upload(tdgl_ctx *ctx, BlrForm &S, BlrTop &Z) {
+    Z.ndense = S.ndense;
+    Z.nitems = S.nitems;
+    Z.cols = S.cols;
+    Z.pairs = S.pairs;
+    Z.rank_max = S.rank_max;
+    Z.bytes = S.bytes;
+    Z.dense_bytes = S.dense_bytes;
+    std::vector<int32_t> &items = S.items, &twin = S.twin, &dslot = S.dslot;
+    std::vector<float> &F = S.F;
+    if (items.empty()) items.assign(4, 0);
+    HIP_TRY(ctx, Z.Gd.upload(S.Gd));
+    HIP_TRY(ctx, Z.dense_ij.upload(S.dense_ij));
+    if (F.empty()) F.assign(4, 0.0f);
+    if (twin.empty()) twin.assign(1, -1);
+    HIP_TRY(ctx, Z.F.upload(F));
+    HIP_TRY(ctx, Z.colbase.upload(S.colbase));
+    HIP_TRY(ctx, Z.twin.upload(twin));
+    HIP_TRY(ctx, Z.items.upload(items));
+    HIP_TRY(ctx, Z.coef.alloc((size_t)std::max<int64_t>(Z.cols, 1)));  // (zeroed: the padding columns)
+    HIP_TRY(ctx, Z.dslot_ptr.upload(S.dslot_ptr));
+    if (dslot.empty()) dslot.push_back(0);
+    HIP_TRY(ctx, Z.dslot.upload(dslot));
+    return TDGL_OK;
+}
+
 // The fp64 tiles of the top separator (f.dense.G) -> the block low-rank form f.blr (fp32), the fp64 tiles released.
 // Truncation tau * ||G||_2 per tile pair (||G||_2 by power iteration on the device, on the tiles as they are); tiles
 // whose rank would exceed DT / 4 stay dense.  If the form does not save at least 40 % of the bytes the dense fp32 tiles
@@ -860,7 +1001,7 @@ static int dense_to_blr(tdgl_ctx *ctx, DirectFactors &f) {
     BlrTop &Z = f.blr;
     Z = BlrTop();
     const int nt = D.tiles;
-    const int64_t n = D.n, ntile = (int64_t)nt * (nt + 1) / 2, T2 = (int64_t)DT * DT;
+    const int64_t n = D.n, ntile = (int64_t)nt * (nt + 1) / 2;
     const double tau = env_double("TDGL_PD_BLR_TOL", BLR_TOL);
     // ||G||_2: power iteration on a deterministic start vector of mean zero (G 1 = 0)
     {
@@ -903,104 +1044,12 @@ static int dense_to_blr(tdgl_ctx *ctx, DirectFactors &f) {
     Z.tol = tau;
     std::vector<double> hG((size_t)D.G.n);
     HIP_TRY(ctx, hipMemcpy(hG.data(), D.G.p, hG.size() * sizeof(double), hipMemcpyDeviceToHost));
-    // every off-diagonal tile, on up to 16 host threads (tile order: t = I (I + 1) / 2 + J)
-    const int kmax = DT / 4;
-    std::vector<int> rank((size_t)ntile, -1);
-    std::vector<std::vector<double>> Qs((size_t)ntile), Ws((size_t)ntile);
-    std::atomic<int64_t> next{0};
-    auto work = [&]() {
-        for (int64_t t; (t = next.fetch_add(1)) < ntile;) {
-            int I = (int)((std::sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-            while ((int64_t)(I + 1) * (I + 2) / 2 <= t) ++I;
-            while ((int64_t)I * (I + 1) / 2 > t) --I;
-            if (t - (int64_t)I * (I + 1) / 2 == I) continue;  // (diagonal tile: dense)
-            rank[t] = blr_compress_block(&hG[(size_t)t * T2], DT, tau * Z.norm, kmax, Qs[t], Ws[t]);
-        }
-    };
-    {
-        const int nth = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        std::vector<std::thread> pool;
-        for (int k = 1; k < nth; ++k) pool.emplace_back(work);
-        work();
-        for (auto &th : pool) th.join();
-    }
-    // columns per row block, in pair order: U_IJ in block I, W_IJ in block J
-    std::vector<int64_t> R((size_t)nt, 0), posU((size_t)ntile, 0), posW((size_t)ntile, 0);
-    std::vector<int32_t> dense_ij;
-    std::vector<char> is_dense((size_t)ntile, 0);
-    for (int I = 0; I < nt; ++I)
-        for (int J = 0; J <= I; ++J) {
-            const int64_t t = (int64_t)I * (I + 1) / 2 + J;
-            if (rank[t] < 0) {
-                is_dense[t] = 1;
-                dense_ij.push_back((I << 16) | J);
-                continue;
-            }
-            posU[t] = R[I];
-            R[I] += rank[t];
-            posW[t] = R[J];
-            R[J] += rank[t];
-            Z.pairs += 1;
-            Z.rank_max = std::max<int64_t>(Z.rank_max, rank[t]);
-        }
-    std::vector<int64_t> colbase((size_t)nt + 1, 0);
-    for (int K = 0; K < nt; ++K) colbase[K + 1] = colbase[K] + round_up(R[K], 4);
-    Z.cols = colbase[nt];
-    Z.ndense = (int)dense_ij.size();
-    Z.dense_bytes = ntile * T2 * (int64_t)sizeof(float);
-    Z.bytes = (int64_t)Z.ndense * T2 * (int64_t)sizeof(float) + 2 * Z.cols * DT * (int64_t)sizeof(float);
-    if (Z.bytes > Z.dense_bytes * 6 / 10) {  // (does not pay)
+    BlrForm S = blr_form_host(hG.data(), n, nt, tau * Z.norm);
+    if (S.bytes > S.dense_bytes * 6 / 10) {  // (does not pay)
         Z = BlrTop();
         return dense_to_fp32(ctx, D);
     }
-    std::vector<float> F((size_t)(Z.cols * DT), 0.0f), Gd((size_t)Z.ndense * T2);
-    std::vector<int32_t> twin((size_t)Z.cols, -1);
-    for (int I = 0, d = 0; I < nt; ++I)
-        for (int J = 0; J <= I; ++J) {
-            const int64_t t = (int64_t)I * (I + 1) / 2 + J;
-            if (is_dense[t]) {
-                for (int64_t e = 0; e < T2; ++e) Gd[(size_t)d * T2 + e] = (float)hG[(size_t)t * T2 + e];
-                ++d;
-                continue;
-            }
-            const int r = rank[t];
-            for (int c = 0; c < r; ++c) {
-                const int64_t cu = posU[t] + c, cw = posW[t] + c;
-                for (int row = 0; row < DT; ++row) {
-                    const int h = row / WAVE, rl = row % WAVE;
-                    F[(size_t)(DT * colbase[I] + ((int64_t)h * (colbase[I + 1] - colbase[I]) + cu) * WAVE + rl)] = (float)Qs[t][(size_t)c * DT + row];
-                    F[(size_t)(DT * colbase[J] + ((int64_t)h * (colbase[J + 1] - colbase[J]) + cw) * WAVE + rl)] = (float)Ws[t][(size_t)c * DT + row];
-                }
-                twin[(size_t)(colbase[I] + cu)] = (int32_t)(colbase[J] + cw);
-                twin[(size_t)(colbase[J] + cw)] = (int32_t)(colbase[I] + cu);
-            }
-        }
-    std::vector<int32_t> items, dslot_ptr((size_t)nt + 1, 0), dslot;
-    for (int K = 0; K < nt; ++K) {
-        const int32_t ng = (int32_t)((colbase[K + 1] - colbase[K]) / 4);
-        for (int32_t g0 = 0; g0 < ng; g0 += BLR_ITEM_GROUPS) {
-            items.insert(items.end(), {K, g0, std::min<int32_t>(g0 + BLR_ITEM_GROUPS, ng), 0});
-        }
-        for (int J = 0; J < nt; ++J) {
-            const int I = std::max(K, J), Jm = std::min(K, J);
-            if (is_dense[(size_t)((int64_t)I * (I + 1) / 2 + Jm)]) dslot.push_back(J);
-        }
-        dslot_ptr[K + 1] = (int32_t)dslot.size();
-    }
-    Z.nitems = (int)(items.size() / 4);
-    if (items.empty()) items.assign(4, 0);
-    HIP_TRY(ctx, Z.Gd.upload(Gd));
-    HIP_TRY(ctx, Z.dense_ij.upload(dense_ij));
-    if (F.empty()) F.assign(4, 0.0f);
-    if (twin.empty()) twin.assign(1, -1);
-    HIP_TRY(ctx, Z.F.upload(F));
-    HIP_TRY(ctx, Z.colbase.upload(colbase));
-    HIP_TRY(ctx, Z.twin.upload(twin));
-    HIP_TRY(ctx, Z.items.upload(items));
-    HIP_TRY(ctx, Z.coef.alloc((size_t)std::max<int64_t>(Z.cols, 1)));  // (zeroed: the padding columns)
-    HIP_TRY(ctx, Z.dslot_ptr.upload(dslot_ptr));
-    if (dslot.empty()) dslot.push_back(0);
-    HIP_TRY(ctx, Z.dslot.upload(dslot));
+    TDGL_TRY(blr_upload(ctx, S, Z));
     D.G.release();
     return TDGL_OK;
 }
@@ -1168,6 +1217,138 @@ extern "C" int tdgl_get_precond_direct_blr(tdgl_ctx *ctx, int64_t *out6, double 
     out6[5] = on ? Z->dense_bytes : 0;
     out2[0] = on ? Z->tol : 0.0;
     out2[1] = on ? Z->norm : 0.0;
+    return TDGL_OK;
+}
+
+// ---- the block low-rank form through the C interface (include/tdgl_hip.h: tdgl_blr_form) -- for the tests of the form
+// A form into the caller's struct: the counts on the sizing call (every array NULL), the arrays on the second call
+// (every array given, the counts as the sizing call left them).  Returns a message, or NULL when all is well.
+static const char *blr_form_out(const BlrForm &S, int64_t n, int nt, tdgl_blr_form *o) {
+    const int given = (o->dense_ij != nullptr) + (o->Gd != nullptr) + (o->F != nullptr) + (o->colbase != nullptr) + (o->twin != nullptr) +
+                      (o->items != nullptr) + (o->dslot_ptr != nullptr) + (o->dslot != nullptr);
+    if (given != 0 && given != 8) return "every array of the form, or none (the sizing call)";
+    const int64_t ndslot = (int64_t)S.dslot.size();
+    if (given == 8 && (o->n != n || o->nt != nt || o->ndense != S.ndense || o->nitems != S.nitems || o->cols != S.cols || o->ndslot != ndslot))
+        return "the counts are not those of the sizing call for this matrix";
+    o->n = n;
+    o->nt = nt;
+    o->ndense = S.ndense;
+    o->nitems = S.nitems;
+    o->cols = S.cols;
+    o->ndslot = ndslot;
+    o->pairs = S.pairs;
+    o->rank_max = S.rank_max;
+    o->bytes = S.bytes;
+    o->dense_bytes = S.dense_bytes;
+    if (given == 0) return nullptr;
+    std::copy(S.dense_ij.begin(), S.dense_ij.end(), o->dense_ij);
+    std::copy(S.Gd.begin(), S.Gd.end(), o->Gd);
+    std::copy(S.F.begin(), S.F.end(), o->F);
+    std::copy(S.colbase.begin(), S.colbase.end(), o->colbase);
+    std::copy(S.twin.begin(), S.twin.end(), o->twin);
+    std::copy(S.items.begin(), S.items.end(), o->items);
+    std::copy(S.dslot_ptr.begin(), S.dslot_ptr.end(), o->dslot_ptr);
+    std::copy(S.dslot.begin(), S.dslot.end(), o->dslot);
+    return nullptr;
+}
+
+// G [n x n] row major, symmetric (its lower triangle is read) -> the fp64 tiles as k_dense_pack_sym leaves them
+static std::vector<double> blr_pack_tiles(const double *G, int64_t n, int nt) {
+    const int64_t ntile = (int64_t)nt * (nt + 1) / 2, T2 = (int64_t)DT * DT;
+    std::vector<double> hG((size_t)(ntile * T2), 0.0);
+    for (int I = 0; I < nt; ++I)
+        for (int J = 0; J <= I; ++J) {
+            double *dst = &hG[(size_t)(((int64_t)I * (I + 1) / 2 + J) * T2)];
+            for (int e = 0; e < DT * DT; ++e) {
+                const int64_t r = (int64_t)I * DT + e / DT, c = (int64_t)J * DT + e % DT;
+                if (r < n && c < n) dst[e] = G[(r > c ? r : c) * n + (r > c ? c : r)];
+            }
+        }
+    return hG;
+}
+
+constexpr int64_t BLR_TEST_MAX_N = 32767 * (int64_t)DT;  // (dense_ij keeps I in 15 bits)
+
+extern "C" int tdgl_host_blr_form(int64_t n, const double *G, double tol_abs, tdgl_blr_form *form) {
+    if (!G || !form || n < 1 || n > BLR_TEST_MAX_N || !(tol_abs >= 0.0))
+        TDGL_FAIL((tdgl_ctx *)nullptr, TDGL_ERR_ARG, "tdgl_host_blr_form: G and form are required, n in 1 .. %lld, tol_abs >= 0", (long long)BLR_TEST_MAX_N);
+    const int nt = (int)((n + DT - 1) / DT);
+    const std::vector<double> hG = blr_pack_tiles(G, n, nt);
+    const BlrForm S = blr_form_host(hG.data(), n, nt, tol_abs);
+    const char *msg = blr_form_out(S, n, nt, form);
+    if (msg) TDGL_FAIL((tdgl_ctx *)nullptr, TDGL_ERR_ARG, "tdgl_host_blr_form: %s", msg);
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_get_precond_direct_blr_form(tdgl_ctx *ctx, tdgl_blr_form *form) {
+    CTX_GUARD(ctx);
+    const char *who = "tdgl_get_precond_direct_blr_form";
+    if (!form) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: null argument", who);
+    if (!ctx->direct || ctx->direct->blr.ndense == 0)
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "%s: the top separator is not in block low-rank form (tdgl_get_precond_direct_blr)", who);
+    const BlrTop &Z = ctx->direct->blr;
+    const int nt = ctx->direct->dense.tiles;
+    BlrForm S;
+    S.ndense = Z.ndense;
+    S.nitems = Z.nitems;
+    S.cols = Z.cols;
+    S.pairs = Z.pairs;
+    S.rank_max = Z.rank_max;
+    S.bytes = Z.bytes;
+    S.dense_bytes = Z.dense_bytes;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    auto fetch = [&](auto &dst, const auto &src, size_t count) -> hipError_t {
+        dst.resize(count);
+        if (count == 0) return hipSuccess;
+        return hipMemcpy(dst.data(), src.p, count * sizeof(dst[0]), hipMemcpyDeviceToHost);
+    };
+    HIP_TRY(ctx, fetch(S.dslot_ptr, Z.dslot_ptr, (size_t)nt + 1));
+    HIP_TRY(ctx, fetch(S.dslot, Z.dslot, (size_t)S.dslot_ptr[(size_t)nt]));
+    HIP_TRY(ctx, fetch(S.dense_ij, Z.dense_ij, (size_t)Z.ndense));
+    HIP_TRY(ctx, fetch(S.Gd, Z.Gd, (size_t)Z.ndense * DT * DT));
+    HIP_TRY(ctx, fetch(S.F, Z.F, (size_t)(Z.cols * DT)));
+    HIP_TRY(ctx, fetch(S.colbase, Z.colbase, (size_t)nt + 1));
+    HIP_TRY(ctx, fetch(S.twin, Z.twin, (size_t)Z.cols));
+    HIP_TRY(ctx, fetch(S.items, Z.items, (size_t)Z.nitems * 4));
+    const char *msg = blr_form_out(S, ctx->direct->dense.n, nt, form);
+    if (msg) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: %s", who, msg);
+    return TDGL_OK;
+}
+
+// The two kernels of the form alone: the form of G built by blr_form_host, uploaded into buffers of this call, applied
+// to the n_vec vectors of X ([n_vec][n]) one after the other through blr_launch -- the launches of the preconditioner,
+// without status block, controller or u; Y [n_vec][n].  coef is zeroed once and then lives through the applications, as
+// in the product.  The context lends its device and stream: its factors and the CG's state are not touched.
+extern "C" int tdgl_blr_apply(tdgl_ctx *ctx, int64_t n, const double *G, double tol_abs, int64_t n_vec, const double *X, double *Y,
+                              tdgl_blr_form *form) {
+    CTX_GUARD(ctx);
+    const char *who = "tdgl_blr_apply";
+    if (!G || !X || !Y) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: null argument", who);
+    if (n < 1 || n > BLR_TEST_MAX_N) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: n must be in 1 .. %lld", who, (long long)BLR_TEST_MAX_N);
+    if (n_vec < 1) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: no vectors", who);
+    if (!(tol_abs >= 0.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: the tolerance must be >= 0", who);
+    const int nt = (int)((n + DT - 1) / DT), nfin = (int)((n + WAVE - 1) / WAVE);
+    BlrForm S;
+    {
+        const std::vector<double> hG = blr_pack_tiles(G, n, nt);
+        S = blr_form_host(hG.data(), n, nt, tol_abs);
+    }
+    if (form) {
+        const char *msg = blr_form_out(S, n, nt, form);
+        if (msg) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: %s", who, msg);
+    }
+    BlrTop Z;
+    TDGL_TRY(blr_upload(ctx, S, Z));
+    DevBuf<double> part, x, y;
+    HIP_TRY(ctx, part.alloc((size_t)nt * nt * DT));
+    HIP_TRY(ctx, x.alloc((size_t)(n * n_vec), false));
+    HIP_TRY(ctx, y.alloc((size_t)(n * n_vec)));
+    HIP_TRY(ctx, hipMemcpy(x.p, X, (size_t)(n * n_vec) * sizeof(double), hipMemcpyHostToDevice));
+    for (int64_t v = 0; v < n_vec; ++v)
+        blr_launch(ctx, Z, (int)n, nt, nfin, x.p + v * n, part.p, nullptr, nullptr, 0, nullptr, y.p + v * n, nullptr, nullptr, nullptr, nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(Y, y.p, (size_t)(n * n_vec) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
 }
 

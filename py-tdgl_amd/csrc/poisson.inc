@@ -1098,6 +1098,21 @@ static void launch_sub_down(tdgl_ctx *ctx, const SubLevel &L, bool first, bool l
     }
 }
 
+// The two launches of the top separator in block low-rank form (dense.inc: dense_to_blr), y = G b on n rows in nt tiles:
+// k_blr_project (the dense tiles into `part`, every column's projection into its twin's slot of Z.coef), then
+// k_blr_finish on nfin workgroups of 64 rows with everything k_dense_sym_finish is handed.  The preconditioner's
+// application and tdgl_blr_apply (the kernels alone, for the tests) both come through here.
+static void blr_launch(tdgl_ctx *ctx, const BlrTop &Z, int n, int nt, int nfin, const double *b, double *part, const double *dmax_part,
+                       const int32_t *fail_part, int nfail, StepStatus *st, double *y, const double *u, double *upart, StepCtl *ctl,
+                       StepRec *rec) {
+    const BlrArgs a{Z.ndense, Z.nitems, Z.dense_ij.p, Z.Gd.p, Z.F.p, Z.colbase.p, Z.twin.p,
+                    reinterpret_cast<const BlrItem *>(Z.items.p), Z.coef.p, Z.dslot_ptr.p, Z.dslot.p};
+    hipLaunchKernelGGL(k_blr_project, dim3((unsigned)(Z.ndense + (Z.nitems + BLOCK / WAVE - 1) / (BLOCK / WAVE))), dim3(BLOCK), 0,
+                       ctx->stream, n, nt, a, b, part, (const StepCtl *)ctl);
+    hipLaunchKernelGGL(k_blr_finish, dim3(nfin), dim3(BLOCK), 0, ctx->stream, n, nt, a, (const double *)part, dmax_part, fail_part, nfail, st,
+                       0, y, u, upart, ctl, rec);
+}
+
 // The launches of a direct mu solve, x = pinv(A) b (dense inverse or substructured; see the header).
 // in_step: inside the time loop -- the kernels that write x hold back when this step's psi update failed and
 // the status block is published by k_dense_sym_finish (returns true then).  ctl / rec: the run-ahead loop's
@@ -1131,14 +1146,8 @@ static bool direct_solve_launch_t(tdgl_ctx *ctx, const double *b, double *x, boo
     }
     const SubLevel &L0 = f.lv[0], &T = f.lv[K - 1];
     if (f.blr.ndense > 0) {  // the top separator in block low-rank form (preconditioner, dense.inc: dense_to_blr)
-        const BlrTop &Z = f.blr;
-        const BlrArgs a{Z.ndense, Z.nitems, Z.dense_ij.p, Z.Gd.p, Z.F.p, Z.colbase.p, Z.twin.p,
-                        reinterpret_cast<const BlrItem *>(Z.items.p), Z.coef.p, Z.dslot_ptr.p, Z.dslot.p};
-        hipLaunchKernelGGL(k_blr_project, dim3((unsigned)(Z.ndense + (Z.nitems + BLOCK / WAVE - 1) / (BLOCK / WAVE))), dim3(BLOCK), 0,
-                           ctx->stream, (int)T.nS, nt, a, vec, f.dense.part.p, (const StepCtl *)ctl);
-        hipLaunchKernelGGL(k_blr_finish, dim3(f.nfin), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt, a, (const double *)f.dense.part.p,
-                           (const double *)ctx->psi_dmax_part.p, (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, 0, T.xs.p,
-                           (const double *)T.u.p, f.upart.p, ctl, rec);
+        blr_launch(ctx, f.blr, (int)T.nS, nt, f.nfin, vec, f.dense.part.p, (const double *)ctx->psi_dmax_part.p,
+                   (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, T.xs.p, (const double *)T.u.p, f.upart.p, ctl, rec);
     } else {
         hipLaunchKernelGGL((k_dense_sym_tiles<VT>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt,
                            SubPools<VT>::dense(f.dense), vec, f.dense.part.p, (const StepCtl *)ctl);

@@ -275,6 +275,30 @@ class ScreeningOptions(C.Structure):
     ]
 
 
+class BlrForm(C.Structure):
+    """tdgl_blr_form: the counts, then the caller's arrays (NULL on the sizing call)."""
+    _fields_ = [
+        ("n", C.c_int64),
+        ("nt", C.c_int64),
+        ("ndense", C.c_int64),
+        ("nitems", C.c_int64),
+        ("cols", C.c_int64),
+        ("ndslot", C.c_int64),
+        ("pairs", C.c_int64),
+        ("rank_max", C.c_int64),
+        ("bytes", C.c_int64),
+        ("dense_bytes", C.c_int64),
+        ("dense_ij", c_i32p),
+        ("Gd", C.POINTER(C.c_float)),
+        ("F", C.POINTER(C.c_float)),
+        ("colbase", c_i64p),
+        ("twin", c_i32p),
+        ("items", c_i32p),
+        ("dslot_ptr", c_i32p),
+        ("dslot", c_i32p),
+    ]
+
+
 # name -> (restype, argtypes); also the list of symbols the header declares
 _CTX = C.c_void_p
 _ENS = C.c_void_p  # tdgl_ensemble *
@@ -444,6 +468,9 @@ SIGNATURES = {
     "tdgl_apply_mu_boundary_laplacian": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_vcycle": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_precond_apply": (C.c_int, [_CTX, c_f64p, c_f64p, c_f64p]),
+    "tdgl_host_blr_form": (C.c_int, [C.c_int64, c_f64p, C.c_double, C.POINTER(BlrForm)]),
+    "tdgl_get_precond_direct_blr_form": (C.c_int, [_CTX, C.POINTER(BlrForm)]),
+    "tdgl_blr_apply": (C.c_int, [_CTX, C.c_int64, c_f64p, C.c_double, C.c_int64, c_f64p, c_f64p, C.POINTER(BlrForm)]),
     "tdgl_guess_dots": (C.c_int, [_CTX, C.c_int32, C.c_int64, c_f64p, c_f64p, C.c_int32, c_f64p]),
     "tdgl_time_kernel": (C.c_int, [_CTX, C.c_int32, C.c_int32, c_f64p]),
     "tdgl_profile_enable": (C.c_int, [_CTX, C.c_int32]),

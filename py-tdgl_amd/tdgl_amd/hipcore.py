@@ -242,6 +242,45 @@ def _factor_bytes(levels, tiles, sparse_sep=True, word=8, top=True) -> int:
     return int(word * entries + (12 * sum(lv.coupling.nnz for lv in levels) if sparse_sep else 0))
 
 
+_BLR_ARRAYS = (("dense_ij", np.int32, "ndense", 1), ("Gd", np.float32, "ndense", 128 * 128), ("F", np.float32, "cols", 128),
+               ("colbase", np.int64, "nt", 0), ("twin", np.int32, "cols", 1), ("items", np.int32, "nitems", 4),
+               ("dslot_ptr", np.int32, "nt", 0), ("dslot", np.int32, "ndslot", 1))
+_BLR_COUNTS = ("n", "nt", "ndense", "nitems", "cols", "ndslot", "pairs", "rank_max", "bytes", "dense_bytes")
+
+
+def _blr_form_fill(size_call, fill_call=None) -> dict:
+    """The two calls of a `tdgl_blr_form`: ``size_call(form)`` with every array NULL sets the counts, the arrays are
+    allocated, ``fill_call(form)`` (default: the same call) fills them.  Returns the counts and the arrays (``Gd
+    [ndense, 128, 128]``, ``items [nitems, 4]``, the others flat) as a dict."""
+    form = _lib.BlrForm()
+    size_call(form)
+    arrays, keep = {}, {}
+    for name, dtype, count, per in _BLR_ARRAYS:
+        size = int(getattr(form, count)) * per if per else int(form.nt) + 1
+        keep[name] = np.zeros(max(size, 1), dtype=dtype)  # (a count of 0: the pointer still is not NULL)
+        arrays[name] = keep[name][:size]
+        setattr(form, name, keep[name].ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))))
+    (fill_call or size_call)(form)
+    out = {name: int(getattr(form, name)) for name in _BLR_COUNTS}
+    out.update(arrays)
+    out["Gd"] = out["Gd"].reshape(-1, 128, 128)
+    out["items"] = out["items"].reshape(-1, 4)
+    return out
+
+
+def host_blr_form(G, tol_abs) -> dict:
+    """`tdgl_host_blr_form` (host only, no context): the block low-rank form of the symmetric ``G [n, n]`` with every
+    off-diagonal 128 x 128 tile compressed to the absolute tolerance ``tol_abs``, by the code that builds the
+    preconditioner's -- the counts ``n, nt, ndense, nitems, cols, ndslot, pairs, rank_max, bytes, dense_bytes`` and the
+    arrays ``dense_ij, Gd, F, colbase, twin, items, dslot_ptr, dslot`` (layout: csrc/kernels.inc at BlrArgs)."""
+    G = f64(G)
+    n = G.shape[0]
+    if G.shape != (n, n):
+        raise ValueError(f"G must be [n, n], got {G.shape}")
+    lib = _lib.load()
+    return _blr_form_fill(lambda form: _lib.check(lib.tdgl_host_blr_form(n, p_f64(G), float(tol_abs), C.byref(form))))
+
+
 class TDGLContext:
     """Owns one ``tdgl_ctx`` (device buffers + stream) for a mesh."""
 
@@ -1598,6 +1637,27 @@ class TDGLContext:
         rz = np.zeros(1)
         self._chk(self._lib.tdgl_precond_apply(self._ctx, p_f64(r), p_f64(z), p_f64(rz)))
         return z, float(rz[0])
+
+    def precond_direct_blr_form(self):
+        """`tdgl_get_precond_direct_blr_form`: the arrays of the block low-rank form the preconditioner stores, copied
+        back from the device (dict, see `host_blr_form`); RuntimeError when the form is not in use."""
+        return _blr_form_fill(lambda form: self._chk(self._lib.tdgl_get_precond_direct_blr_form(self._ctx, C.byref(form))))
+
+    def blr_apply(self, G, tol_abs, X):
+        """`tdgl_blr_apply`: the block low-rank form of the symmetric ``G [n, n]`` at the absolute tolerance ``tol_abs``
+        applied to every column of ``X [n, k]`` by the form's two kernels alone.  Returns ``(Y [n, k], form)`` with the
+        form this call built; the context's factors and the CG's state stay as they are."""
+        G = f64(G)
+        X = f64(X)
+        n = G.shape[0]
+        if G.shape != (n, n) or X.ndim != 2 or X.shape[0] != n:
+            raise ValueError(f"G must be [n, n] and X [n, k], got {G.shape} and {X.shape}")
+        Xt = np.ascontiguousarray(X.T)
+        Yt = np.empty_like(Xt)
+        form = _blr_form_fill(lambda fm: _lib.check(self._lib.tdgl_host_blr_form(n, p_f64(G), float(tol_abs), C.byref(fm))),
+                              lambda fm: self._chk(self._lib.tdgl_blr_apply(self._ctx, n, p_f64(G), float(tol_abs), Xt.shape[0],
+                                                                            p_f64(Xt), p_f64(Yt), C.byref(fm))))
+        return np.ascontiguousarray(Yt.T), form
 
     def guess_dots(self, vectors, b, newest=-1):
         """The projection guess's dot-product pass on ``vectors [k, n]`` and ``b [n]`` (parity tests): dict of

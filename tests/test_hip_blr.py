@@ -1,5 +1,8 @@
 """The preconditioner's top separator in block low-rank form (dense.inc: dense_to_blr; kernels.inc: k_blr_project /
-k_blr_finish) against the dense fp32 tiles it replaces (TDGL_PD_BLR=0), on a three-level preconditioner of ~110k sites."""
+k_blr_finish) against the dense fp32 tiles it replaces (TDGL_PD_BLR=0), on a three-level preconditioner of ~110k sites:
+what the form does for the CG.  What the form and its two kernels must compute entry by entry is in
+tests/test_blr_form_host.py (the arrays, on the host) and tests/test_hip_blr_form.py (the kernels against the float64 model
+of tests/blr_model.py); the compression of a single block in tests/test_blr_host.py."""
 
 import numpy as np
 import pytest

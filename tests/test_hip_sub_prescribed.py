@@ -85,15 +85,20 @@ def _report(name, lay):
 
 
 # ---- A: the fp32 preconditioner ------------------------------------------------------------------------------------
-def _precond_ctx(name, monkeypatch, sym):
+def _precond_ctx(name, monkeypatch, sym, blr_tol=None, rtol=1e-10):
+    """(``blr_tol``: the top separator in block low-rank form at that tau, ``rtol``: the CG's tolerance to go with it --
+    tests/test_hip_blr_form.py; None: dense tiles.)"""
     from tdgl_amd.hipcore import TDGLContext
 
     lay = _layout(name)
-    # (the settings of test_hip_blr._precond_ctx; the dense fp32 top separator: the low-rank form has its own test)
+    # (the settings of test_hip_blr._precond_ctx; the dense fp32 top separator: the low-rank form has its own test,
+    # tests/test_hip_blr_form.py, which calls this with blr_tol)
     for attr, value in (("DENSE_MAX_SITES", 199), ("SUB_MAX_SITES", 199), ("SUB2_MAX_SITES", 199), ("SUB3_MIN_SITES", 200),
                         ("SUB3_BIG", 6000), ("PD_MAX_SITES", 10 ** 9), ("PD_CHOICE", 1)):
         monkeypatch.setattr(TDGLContext, attr, value)
-    monkeypatch.setenv("TDGL_PD_BLR", "0")
+    monkeypatch.setenv("TDGL_PD_BLR", "0" if blr_tol is None else "1")
+    if blr_tol is not None:
+        monkeypatch.setenv("TDGL_PD_BLR_TOL", repr(float(blr_tol)))
     if sym:
         monkeypatch.setenv("TDGL_PD_SYM", "2")
     else:
@@ -101,7 +106,7 @@ def _precond_ctx(name, monkeypatch, sym):
     monkeypatch.delenv("TDGL_UP_PARTS", raising=False)
     _prescribe(monkeypatch, lay.lists)
     ctx = TDGLContext(lay.mesh)
-    ctx.build_poisson(rtol=1e-10)
+    ctx.build_poisson(rtol=rtol)
     return ctx, lay
 
 
