@@ -903,6 +903,29 @@ int tdgl_vcycle(tdgl_ctx *ctx, const double *r, double *z);
  * the factor sweeps against a host model of the stored factors.  TDGL_ERR_NOT_READY (with a message) without factors,
  * when the factors are the mu SOLVER rather than the preconditioner, and in one-process-per-GPU contexts. */
 int tdgl_precond_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz);
+/* One application of the V-cycle in the precisions the CG applies it in (tdgl_poisson_options.precond_fp32 = 1 or 2: the
+ * level-0 operators in fp32 or binary16 with the two level-0 iterates in fp32, the coarser levels' pre-multiplied
+ * operators in fp32 or binary16; tdgl_vcycle is the fp64 cycle).  r, q and z [n_sites] in REFERENCE site order; z is the
+ * stored fp32 z widened to double; *rz = r . z and, when q is given (may be NULL, then qz is not written), *qz = q . z,
+ * each as the CG forms it: the smoothing pass's per-workgroup partials added in index order (with q the pass is the
+ * flexible CG's two-sum form).  Makes the reduced-precision copies if the last solve did not leave them, as the next solve
+ * would.  Works on a residual copy and partials of its own: the CG's vectors, guess and counters are untouched, a
+ * tdgl_poisson_solve before and after returns the same bits.  For cross-checks against a host model of what the device
+ * stores.  TDGL_ERR_NOT_READY (with the reason in the message) without a hierarchy, in one-process-per-GPU contexts, and
+ * where the CG would apply the fp64 cycle: fp64 storage, a single level, a level-0 degree other than 1, or no fused
+ * restriction for the coefficient in use. */
+int tdgl_vcycle_stored(tdgl_ctx *ctx, const double *r, const double *q, double *z, double *rz, double *qz);
+/* Which index form each operator of that cycle was built with on this context (read-only).  out[TDGL_INDEX_FORMS_LEN],
+ * every entry -1 where the operator does not exist, else 1 = the 16-bit form, 0 = int32:
+ *   [0] level-0 A (row deltas)   [1] level-0 P (offsets from a slice base)   [2] the fused restriction (offsets from a
+ *   row base)   [3] the sparse W of a collapsed tail   [4] 1 when level 0 reads the binary16 copies (known after a solve
+ *   or tdgl_vcycle_stored)   [5] the number of levels   [6] the collapsed tail's level   [7] its mode (0 dense, 1 G / W / V)
+ *   [8] the site graph's pattern behind the psi and mu Laplacian kernels (row deltas; the one entry that needs no hierarchy)
+ *   [8 + k], 1 <= k <= 15: the explicit way up of intermediate level k: bit 0 = 16-bit offsets, bit 1 = binary16 values.
+ * The environment variable TDGL_INDEX32=1, read when the operators are set, makes every 16-bit form count as not fitting
+ * (tests of the int32 forms at small sizes); this reports what was built. */
+#define TDGL_INDEX_FORMS_LEN 24
+int tdgl_get_poisson_index_forms(tdgl_ctx *ctx, int32_t *out);
 /* The block low-rank form of a symmetric matrix of order n (the preconditioner's top separator; layout: csrc/kernels.inc
  * at BlrArgs), as the product builds it: nt = ceil(n / 128) row blocks of 128 rows, the tiles (I, J),
  * J <= I, either dense fp32 tiles or pairs of fp32 factor columns.  Filled in two calls: with every array pointer NULL a

@@ -261,7 +261,7 @@ extern "C" int tdgl_poisson_set_fused_restriction(tdgl_ctx *ctx, int64_t n_rows,
     {
         std::vector<int32_t> base(std::max<int64_t>(n_rows, 1), 0);
         std::vector<uint16_t> off(std::max<int64_t>(indptr[n_rows], 1), 0);
-        bool fits = true;
+        bool fits = !env_index32();
         for (int64_t i = 0; i < n_rows && fits; ++i) {
             if (indptr[i + 1] == indptr[i]) continue;
             int32_t lo = indices[indptr[i]], hi = lo;
@@ -372,7 +372,7 @@ extern "C" int tdgl_poisson_set_collapsed_up(tdgl_ctx *ctx, int32_t level, const
     L.up_woff.release();
     L.up_wbase.release();
     L.up_vidx.release();
-    if (L.n_coarse < 65536) {
+    if (L.n_coarse < 65536 && !env_index32()) {
         std::vector<int32_t> base(std::max<int64_t>(L.n, 1), 0);
         std::vector<uint16_t> off(std::max<int64_t>(w_indptr[L.n], 1), 0), vidx(std::max<int64_t>(v_indptr[L.n], 1), 0);
         bool fits = true;
@@ -440,7 +440,7 @@ extern "C" int tdgl_poisson_set_collapsed_tail(tdgl_ctx *ctx, const tdgl_collaps
         }
         TDGL_TRY(upload_csr(ctx, n, n_pad_t + g, t->W_indptr, wi.data(), t->W_data, ctx->tailW));
         ctx->tailW_idx16.release();
-        if (n_pad_t + g < 65536) {
+        if (n_pad_t + g < 65536 && !env_index32()) {
             std::vector<uint16_t> i16(wi.begin(), wi.end());
             if (i16.empty()) i16.push_back(0);
             HIP_TRY(ctx, ctx->tailW_idx16.upload(i16));
@@ -1915,5 +1915,75 @@ extern "C" int tdgl_precond_apply(tdgl_ctx *ctx, const double *r, double *z, dou
     double s = 0.0;
     for (double v : h) s += v;
     *rz = s;
+    return TDGL_OK;
+}
+
+// Per-kernel entry point (tests of the stored-precision cycle): ONE application of the V-cycle the CG applies above the
+// fp64 one -- vcycle0_f32 with the operators in the storage ensure_f32 gives them -- on vectors in the caller's site
+// order.  The residual copy and the dot partials are this call's own: the CG's vectors, partials and counters are not
+// touched (the cycle's work vectors are: every application overwrites them).  z = the stored fp32 z widened; *rz (and
+// *qz with q, the flexible CG's DOT_BY2 form) = the smoothing pass's partials added up in index order.
+extern "C" int tdgl_vcycle_stored(tdgl_ctx *ctx, const double *r, const double *q, double *z, double *rz, double *qz) {
+    CTX_GUARD(ctx);
+    if (!r || !z || !rz || (q && !qz)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_vcycle_stored: null argument");
+    // (a rank of a one-process-per-GPU run: its cycle exchanges ghosts and sums the coarse right-hand sides over ranks)
+    if (ctx->n_own != ctx->n || distributed(ctx) || ctx->deep)
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_vcycle_stored: single-GPU contexts only (one process per GPU: the cycle has collectives)");
+    if (ctx->levels.empty()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_vcycle_stored: no AMG hierarchy");
+    if (!precond_f32_on(ctx)) {
+        const char *why = !ctx->popt.precond_fp32        ? "the operators are stored in fp64 (precond_fp32 = 0)"
+                          : ctx->levels.size() < 2       ? "the hierarchy has a single level"
+                          : level_degree(ctx, 0) != 1    ? "the level-0 smoother has a degree other than 1"
+                                                         : "no fused restriction for the level-0 coefficient in use";
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_vcycle_stored: the CG applies the fp64 cycle here: %s (tdgl_vcycle)", why);
+    }
+    TDGL_TRY(ensure_f32(ctx));
+    AmgLevel &L = *ctx->levels[0];
+    DevBuf<double> in, qin, part;
+    HIP_TRY(ctx, in.alloc(L.n_pad));
+    HIP_TRY(ctx, part.alloc(3 * NB));
+    TDGL_TRY(upload_sites(ctx, r, in));
+    if (q) {
+        HIP_TRY(ctx, qin.alloc(L.n_pad));
+        TDGL_TRY(upload_sites(ctx, q, qin));
+    }
+    const float *z32 = vcycle0_f32(ctx, in.p, part.p, nullptr, q ? qin.p : (const double *)nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<double> h((size_t)3 * NB);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<float> zf((size_t)ctx->n);
+    TDGL_TRY(download_sites(ctx, z32, zf.data()));  // (synchronises the stream)
+    for (int64_t i = 0; i < ctx->n; ++i) z[i] = (double)zf[i];
+    double s = 0.0, s2 = 0.0;
+    for (int i = 0; i < ctx->npart; ++i) {
+        s += h[i];
+        s2 += h[(size_t)2 * NB + i];
+    }
+    *rz = s;
+    if (q) *qz = s2;
+    return TDGL_OK;
+}
+
+// Which index form each operator of the stored-precision cycle was built with (read-only; tests assert the path they
+// mean to run).  out[TDGL_INDEX_FORMS_LEN]: see include/tdgl_hip.h.
+extern "C" int tdgl_get_poisson_index_forms(tdgl_ctx *ctx, int32_t *out) {
+    if (!ctx || !out) return TDGL_ERR_ARG;
+    for (int i = 0; i < TDGL_INDEX_FORMS_LEN; ++i) out[i] = -1;
+    const int nl = (int)ctx->levels.size();
+    out[5] = nl;
+    out[8] = ctx->lap_pat.use16 ? 1 : 0;
+    if (nl == 0) return TDGL_OK;
+    const AmgLevel &L = *ctx->levels[0];
+    out[0] = L.A.pat.use16 ? 1 : 0;
+    if (nl > 1) out[1] = L.P.pat.use_off16 ? 1 : 0;
+    if (ctx->fusedR.nnz > 0) out[2] = ctx->fusedR_off16.n > 0 ? 1 : 0;
+    if (ctx->tail_level >= 1 && ctx->tail_mode == 1) out[3] = ctx->tailW_idx16.n > 0 ? 1 : 0;
+    out[4] = (ctx->f32_ready && ctx->level0_f16) ? 1 : 0;
+    out[6] = ctx->tail_level;
+    out[7] = ctx->tail_level >= 1 ? ctx->tail_mode : -1;
+    for (int k = 1; k + 1 < nl && 8 + k < TDGL_INDEX_FORMS_LEN; ++k) {
+        const AmgLevel &M = *ctx->levels[k];
+        if (M.Wup.nnz > 0) out[8 + k] = (M.up_woff.n > 0 ? 1 : 0) | (ctx->coarse32_ready && M.up_w16.n > 0 ? 2 : 0);
+    }
     return TDGL_OK;
 }

@@ -35,6 +35,14 @@ using namespace tdgl;
 
 static inline int grid_for(int64_t n, int block = BLOCK) { return (int)((n + block - 1) / block); }
 
+// TDGL_INDEX32=1 (tests): every "do the 16-bit indices fit" question of the set-up is answered no, so that the int32
+// forms of the SELL / CSR kernels run on meshes of any size (P's needs > 65,536 coarse rows otherwise).  Read where
+// the patterns are built, never on the hot path.
+static bool env_index32() {
+    const char *env = getenv("TDGL_INDEX32");
+    return env && env[0] == '1';
+}
+
 // ---------------------------------------------------------------------------------------
 // SELL construction from CSR (host)
 static int build_sell_pattern(tdgl_ctx *ctx, int64_t n_rows, const int32_t *indptr,
@@ -74,7 +82,7 @@ static int build_sell_pattern(tdgl_ctx *ctx, int64_t n_rows, const int32_t *indp
     HIP_TRY(ctx, pat.slice_off.upload(off));
     HIP_TRY(ctx, pat.cols.upload(cols));
     pat.use16 = false;
-    if (want16) {
+    if (want16 && !env_index32()) {
         std::vector<int16_t> d16(pat.n_slots);
         bool fits = true;
         for (int sl = 0; sl < pat.n_slices && fits; ++sl)
@@ -95,7 +103,7 @@ static int build_sell_pattern(tdgl_ctx *ctx, int64_t n_rows, const int32_t *indp
         }
     }
     pat.use_off16 = false;
-    if (want_off16) {
+    if (want_off16 && !env_index32()) {
         std::vector<uint16_t> o16(std::max<int64_t>(pat.n_slots, 1), 0);
         std::vector<int32_t> sbase(std::max<int32_t>(pat.n_slices, 1), 0);
         bool fits = true;

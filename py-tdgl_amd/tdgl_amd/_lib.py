@@ -468,6 +468,8 @@ SIGNATURES = {
     "tdgl_apply_mu_boundary_laplacian": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_vcycle": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_precond_apply": (C.c_int, [_CTX, c_f64p, c_f64p, c_f64p]),
+    "tdgl_vcycle_stored": (C.c_int, [_CTX, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "tdgl_get_poisson_index_forms": (C.c_int, [_CTX, C.POINTER(C.c_int32)]),
     "tdgl_host_blr_form": (C.c_int, [C.c_int64, c_f64p, C.c_double, C.POINTER(BlrForm)]),
     "tdgl_get_precond_direct_blr_form": (C.c_int, [_CTX, C.POINTER(BlrForm)]),
     "tdgl_blr_apply": (C.c_int, [_CTX, C.c_int64, c_f64p, C.c_double, C.c_int64, c_f64p, c_f64p, C.POINTER(BlrForm)]),

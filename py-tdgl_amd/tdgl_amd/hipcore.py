@@ -1638,6 +1638,38 @@ class TDGLContext:
         self._chk(self._lib.tdgl_precond_apply(self._ctx, p_f64(r), p_f64(z), p_f64(rz)))
         return z, float(rz[0])
 
+    def vcycle_stored(self, r, q=None):
+        """`tdgl_vcycle_stored`: one application of the V-cycle in the precisions the CG applies it in
+        (``precond_fp32`` = 1 or 2), ``(z, r . z)`` or, with ``q``, ``(z, r . z, q . z)``: z is the stored fp32 z, the
+        sums are the smoothing pass's partials.  The CG's state stays as it is.  RuntimeError where the CG would
+        apply the fp64 cycle (`vcycle`) and in one-process-per-GPU contexts."""
+        r = f64(r)
+        z = np.empty(self.n)
+        rz, qz = np.zeros(1), np.zeros(1)
+        if q is None:
+            self._chk(self._lib.tdgl_vcycle_stored(self._ctx, p_f64(r), None, p_f64(z), p_f64(rz), None))
+            return z, float(rz[0])
+        q = f64(q)
+        self._chk(self._lib.tdgl_vcycle_stored(self._ctx, p_f64(r), p_f64(q), p_f64(z), p_f64(rz), p_f64(qz)))
+        return z, float(rz[0]), float(qz[0])
+
+    def index_forms(self) -> dict:
+        """`tdgl_get_poisson_index_forms`: the index form every operator of the stored-precision V-cycle was built with
+        on this context.  ``laplacian16`` (the site graph's pattern behind the psi and mu Laplacian kernels: 16-bit row
+        deltas; needs no hierarchy), ``A16`` (level-0 A: 16-bit row deltas), ``P16`` (level-0 P: 16-bit offsets from a slice base),
+        ``F16`` (the fused restriction: 16-bit offsets from a row base), ``tailW16`` (the collapsed tail's sparse W):
+        True / False, None where the operator does not exist; ``level0_f16``: level 0 reads the binary16 copies (known
+        after a solve or `vcycle_stored`); ``levels``; ``tail`` = (level, "dense" | "gwv") or None; ``mid`` = {k:
+        dict(off16, f16)} for every intermediate level with an explicit way up."""
+        n_out = 24
+        out = (C.c_int32 * n_out)()
+        self._chk(self._lib.tdgl_get_poisson_index_forms(self._ctx, out))
+        flag = lambda v: None if v < 0 else bool(v)  # noqa: E731
+        return dict(laplacian16=flag(out[8]), A16=flag(out[0]), P16=flag(out[1]), F16=flag(out[2]), tailW16=flag(out[3]), level0_f16=bool(out[4] > 0),
+                    levels=int(out[5]), tail=None if out[6] < 1 else (int(out[6]), "gwv" if out[7] == 1 else "dense"),
+                    mid={k: dict(off16=bool(out[8 + k] & 1), f16=bool(out[8 + k] & 2))
+                         for k in range(1, n_out - 8) if out[8 + k] >= 0})
+
     def precond_direct_blr_form(self):
         """`tdgl_get_precond_direct_blr_form`: the arrays of the block low-rank form the preconditioner stores, copied
         back from the device (dict, see `host_blr_form`); RuntimeError when the form is not in use."""

@@ -104,6 +104,45 @@ def test_inconsistent_halo_plan_is_rejected():
     ctx.close()
 
 
+def test_vcycle_stored_is_refused_where_the_cg_applies_the_fp64_cycle():
+    """`tdgl_vcycle_stored` answers for the cycle in reduced storage alone: every state in which the CG would apply the
+    fp64 one (`tdgl_vcycle`) is a refusal with its reason, and so is a rank of a decomposed run."""
+    from tdgl_amd.partition import build_local_problem, rcb_partition
+
+    mesh = synthetic_mesh(40)
+    ctx = _ctx(mesh)
+    r = np.zeros(ctx.n)
+    with pytest.raises(RuntimeError, match="tdgl_vcycle_stored: no AMG hierarchy"):
+        ctx.vcycle_stored(r)
+    assert ctx.index_forms()["levels"] == 0 and ctx.index_forms()["A16"] is None
+    h = ctx.build_poisson()
+    assert len(h.levels) >= 2
+    ctx.set_poisson_options(precond_fp32=False)
+    with pytest.raises(RuntimeError, match=r"stored in fp64 \(precond_fp32 = 0\)"):
+        ctx.vcycle_stored(r)
+    ctx.set_poisson_options(nu_fine=2)
+    with pytest.raises(RuntimeError, match="level-0 smoother has a degree other than 1"):
+        ctx.vcycle_stored(r, r)
+    ctx.set_poisson_options(fused_restriction=False)
+    with pytest.raises(RuntimeError, match="no fused restriction for the level-0 coefficient in use"):
+        ctx.vcycle_stored(r)
+    ctx.set_poisson_options()
+    z, rz, qz = ctx.vcycle_stored(r, r)  # (and the defaults are served: zero in, zero out)
+    assert not z.any() and rz == 0.0 and qz == 0.0 and ctx.precond_storage() == 2
+    ctx.close()
+    ctx = _ctx(synthetic_mesh(8))
+    h = ctx.build_poisson()
+    assert len(h.levels) == 1
+    with pytest.raises(RuntimeError, match="the hierarchy has a single level"):
+        ctx.vcycle_stored(np.zeros(ctx.n))
+    ctx.close()
+    lp = build_local_problem(mesh, rcb_partition(mesh.sites, 2), 0)
+    ctx = _ctx(lp.mesh, n_owned=lp.n_own)
+    with pytest.raises(RuntimeError, match="tdgl_vcycle_stored: single-GPU contexts only"):
+        ctx.vcycle_stored(np.zeros(ctx.n))
+    ctx.close()
+
+
 @pytest.mark.parametrize("shape", ["two_triangles", "one_triangle"])
 def test_smallest_meshes_run(shape):
     """4 sites / 5 edges and 3 sites / 3 edges: every site on the boundary, single-level
