@@ -95,17 +95,10 @@ def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
     """Time dependence the ensemble evaluates on the device passes: a separable A whose factor is a LinearRamp or a
     TabulatedRamp, a sum of a static field and such products, TabulatedCurrents, a SeparableEpsilon.  Anything else
     raises."""
-    if rep.dynamic_vector_potential and (not rep.device_evaluates_field() or getattr(rep, "_A_loops", None)):
-        form = ("LinearRamp(...) * (static field), TabulatedRamp(...) * (static field), or a sum (static field) + f_1 * "
-                f"(static field) + ... of up to {FIELD_TERMS_MAX} such products")
-        if rep._A_base is not None:
-            raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
-                             f"{form}; this one's time factor is not a LinearRamp or a TabulatedRamp.")
-        if getattr(rep, "_A_loops", None):
-            raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
-                             f"{form}; a MovingCurrentLoop is evaluated on the device by solve() alone, not per replica.")
+    if rep.field.refusal is not None:
         raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
-                         f"{form}; this one is not of that form.")
+                         "LinearRamp(...) * (static field), TabulatedRamp(...) * (static field), or a sum (static field) + f_1 * "
+                         f"(static field) + ... of up to {FIELD_TERMS_MAX} such products; {rep.field.refusal}")
     if rep.dynamic_currents and rep._current_table is None:
         raise ValueError(f"solve_ensemble: replica {r}: time-dependent terminal_currents are not supported "
                          "(TabulatedCurrents are).")
@@ -113,8 +106,7 @@ def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
         raise ValueError(f"solve_ensemble: replica {r}: a time-dependent disorder_epsilon is not supported "
                          "(SeparableEpsilon is).")
     if rep.device_evaluates_field() and (rep._current_table is not None or rep._eps_table is not None):
-        what = "a field ramp" if rep._A_ramp is not None else "a field table" if rep._A_table is not None else "a sum of field terms"
-        raise ValueError(f"solve_ensemble: replica {r}: {what} combined with TabulatedCurrents or a SeparableEpsilon "
+        raise ValueError(f"solve_ensemble: replica {r}: {rep.field.noun} combined with TabulatedCurrents or a SeparableEpsilon "
                          "in one replica is not supported.")
 
 
@@ -238,28 +230,16 @@ def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon
     sums = args.get("vector_potential_terms", [getattr(sums, "value", None)] * R)
     reps = []
     for r in range(R):
-        A = args["link_exponents"][r]
         if ramps[r] is not None and fields[r] is not None:
             raise ValueError(f"solve_ensemble: replica {r}: vector_potential_ramp and vector_potential_table exclude each other.")
         if sums[r] is not None and (ramps[r] is not None or fields[r] is not None):
             raise ValueError(f"solve_ensemble: replica {r}: vector_potential_terms excludes vector_potential_ramp and "
                              "vector_potential_table.")
-        if A is None and sums[r] is not None:
-            A = np.zeros((len(mesh.edge_mesh.edges), 2))  # (replaced by the terms' value at t = 0 below)
-        if A is None and ramps[r] is not None:
-            from .parameter import LinearRamp
-
-            A = LinearRamp(**ramps[r][1]).scalar(0.0) * np.asarray(ramps[r][0], dtype=float)
-        if A is None and fields[r] is not None:
-            from .parameter import PiecewiseLinear
-
-            A = PiecewiseLinear(*fields[r][1:])(0.0) * np.asarray(fields[r][0], dtype=float)
-        rep = _ReplicaInputs.from_dimensionless(mesh, options, A, eps[r], u, gamma,
+        # (link_exponents None: the field's value at t = 0, `applied_field.from_dimensionless`)
+        rep = _ReplicaInputs.from_dimensionless(mesh, options, args["link_exponents"][r], eps[r], u, gamma,
                                                 terminal_info=terminal_info, current_func=args["currents"][r],
                                                 probe_points=probe_points, vector_potential_ramp=ramps[r],
                                                 vector_potential_table=fields[r], vector_potential_terms=sums[r])
-        if sums[r] is not None and args["link_exponents"][r] is None:
-            rep.current_A_applied = rep.vector_potential_func(0.0)
         if tables[r] is not None:
             _with_epsilon_table(rep, tables[r], len(mesh.sites))
         _refuse_dynamic(r, rep)
@@ -483,14 +463,7 @@ class EnsembleSolver:
         reps, R = self.reps, len(self.reps)
         ens.set_probes(reps[0].probe_points)
         for r, rep in enumerate(reps):
-            if rep._A_terms is not None:
-                ens.set_link_terms(r, *rep._A_terms)
-            elif rep._A_ramp is not None:  # (TDGLSolver._setup: the links start at the ramp's value at t = 0)
-                ens.set_link_ramp(r, rep._A_base, **rep._A_ramp)
-            elif rep._A_table is not None:
-                ens.set_link_table(r, rep._A_base, *rep._A_table)
-            else:
-                ens.set_link_exponents(r, rep.current_A_applied)
+            rep.field.install_replica(ens, r, rep.current_A_applied)
             ens.set_mu_boundary(r, rep.mu_boundary)
             ens.set_epsilon(r, rep.epsilon)
             if rep._current_table is not None and rep.terminal_info:

@@ -267,13 +267,8 @@ class CompositeParameter(Parameter):
         function of its own, a bare number -- or when there are more than ``FIELD_TERMS_MAX`` products.  The value of the
         form, evaluated left to right as ``((A_0 + f_1 A_1) + f_2 A_2) + ...``, is what the time loop computes
         (`tdgl_set_link_terms`); it differs from ``self(x, y, z, t=t)`` by the rounding of a reordered sum only."""
-        statics, terms = [], []
-        if not _collect_terms(self, 1, statics, terms) or len(terms) > FIELD_TERMS_MAX:
-            return None
-        static = None
-        for leaf in statics:
-            static = leaf if static is None else static + leaf
-        return static, terms
+        found = _collect_sum(self, loops=False)
+        return None if found is None else found[:2]
 
     def device_sources(self):
         """`separable_terms` with moving loops: ``(A_0 or None, [(f_k, A_k), ...], [loop_1, ...])`` for a tree built from
@@ -282,13 +277,7 @@ class CompositeParameter(Parameter):
         ``loops`` is not.  ``None`` when anything else appears -- a loop times a ramp, for one --, for more than
         ``FIELD_TERMS_MAX`` products or more than ``FIELD_LOOPS_MAX`` loops.  The time loop evaluates the form as the
         terms' sum, left to right, then the loops in the order they appear (`tdgl_set_link_loops`)."""
-        statics, terms, loops = [], [], []
-        if not _collect_terms(self, 1, statics, terms, loops) or len(terms) > FIELD_TERMS_MAX or len(loops) > FIELD_LOOPS_MAX:
-            return None
-        static = None
-        for leaf in statics:
-            static = leaf if static is None else static + leaf
-        return static, terms, loops
+        return _collect_sum(self, loops=True)
 
     def __call__(self, x, y, z=None, t=None):
         values = []
@@ -327,6 +316,19 @@ class CompositeParameter(Parameter):
 
 FIELD_TERMS_MAX = 4  # products in a sum the time loop evaluates itself (TDGL_FIELD_TERMS_MAX)
 FIELD_LOOPS_MAX = 2  # moving current loops on top of them (TDGL_FIELD_LOOPS_MAX)
+
+
+def _collect_sum(p, loops: bool):
+    """``(static or None, terms, loops)`` of the ``+`` / ``-`` tree under ``p``, the leaves independent of time folded left
+    to right into the one static part; ``None`` where `_collect_terms` refuses the tree or it holds more than
+    ``FIELD_TERMS_MAX`` products or ``FIELD_LOOPS_MAX`` loops.  Without ``loops`` a `MovingCurrentLoop` leaf is refused."""
+    statics, terms, found = [], [], []
+    if not _collect_terms(p, 1, statics, terms, found if loops else None) or len(terms) > FIELD_TERMS_MAX or len(found) > FIELD_LOOPS_MAX:
+        return None
+    static = None
+    for leaf in statics:
+        static = leaf if static is None else static + leaf
+    return static, terms, found
 
 
 def _collect_terms(p, sign: int, statics: list, terms: list, loops: Optional[list] = None) -> bool:

@@ -49,12 +49,7 @@ def save_step(source, solver, rec: "RunRecord", final: bool = False) -> None:
         st = source.get_state()
         js, jn = st["supercurrent"], st["normal_current"]
     a_ind = source.induced_vector_potential() if solver.screening is not None else None
-    if getattr(solver, "_A_loops", None):  # moving loops: the device's own A -- what is saved is what was applied
-        solver.current_A_applied = source.link_exponents()
-    elif getattr(solver, "_A_terms", None) is not None:  # A_applied of the last step taken, from the factors the time loop evaluated
-        solver.current_A_applied = solver.terms_value(source.link_term_scales())
-    elif solver._A_base is not None:  # A_applied of the last step taken (the links may lag behind it)
-        solver.current_A_applied = source.link_scale() * solver._A_base
+    solver.note_applied(solver.field.applied(source))  # A_applied of the last step taken, where the device knows it
     data = TDGLData(ls["step"], ls["time"], ls["dt"], st["psi"], st["mu"], js, jn,
                     applied_vector_potential=solver.current_A_applied, epsilon=solver.epsilon,
                     induced_vector_potential=a_ind)

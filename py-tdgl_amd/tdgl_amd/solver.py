@@ -27,6 +27,7 @@ from typing import Callable, Dict, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 
+from . import applied_field
 from .device import Device, TerminalInfo
 from .io import DataHandler, write_solution_group
 from .operators import MeshOperators
@@ -109,70 +110,10 @@ class TDGLSolver:
         self.z0 = device.layer.z0 * np.ones(len(self.edge_centers))
 
         # ---- applied vector potential on the edges (solver.py:158-189) ------------------
-        self.dynamic_vector_potential = bool(
-            getattr(applied_vector_potential, "time_dependent", False)
-        )
         self.applied_vector_potential = applied_vector_potential
         self.A_scale = device.field_scale(options.field_units)
-        ex, ey = self.edge_centers[:, 0], self.edge_centers[:, 1]
-        self.vector_potential_func = None
-        self._A_base = self._A_factor = self._A_ramp = self._A_table = self._A_terms = self._A_loops = None
-        sep = applied_vector_potential.separable_product() if (
-            self.dynamic_vector_potential and hasattr(applied_vector_potential, "separable_product")) else None
-        # (a single product with no static part keeps its own path, call for call; anything else that is a sum of a static
-        # field and such products goes to the device as terms)
-        terms = applied_vector_potential.separable_terms() if (
-            sep is None and self.dynamic_vector_potential and hasattr(applied_vector_potential, "separable_terms")) else None
-        # (... and with MovingCurrentLoop leaves in the sum, the loops ride on top of the terms or of the static part)
-        sources = applied_vector_potential.device_sources() if (
-            sep is None and terms is None and self.dynamic_vector_potential and hasattr(applied_vector_potential, "device_sources")) else None
-        if sources is not None and sources[2]:
-            static, products, loops = sources
-            on_edges = lambda q: self.A_scale * np.asarray(q(ex, ey, self.z0))[:, :2]  # noqa: E731
-            if products:
-                self._set_terms(None if static is None else on_edges(static),
-                                [(on_edges(q), f.ramp if f.ramp is not None else (f.table.times, f.table.values)) for f, q in products])
-                A0 = None
-            else:
-                A0 = np.zeros_like(self.edge_centers) if static is None else on_edges(static)
-            self._set_loops(A0, [dict(times=lp["times"], centers=lp["centers"], radius=lp["radius"],
-                                      currents=self.A_scale * lp["unit_factor"] * lp["currents"]) for lp in loops],
-                            self.edge_centers, float(device.layer.z0))
-            A = self.vector_potential_func(0)
-        elif terms is not None and terms[1]:
-            # A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K with ramps and tables as factors: everything stays on the device,
-            # tdgl_run evaluates the factors itself (tdgl_set_link_terms)
-            static, products = terms
-            on_edges = lambda q: self.A_scale * np.asarray(q(ex, ey, self.z0))[:, :2]  # noqa: E731
-            self._set_terms(None if static is None else on_edges(static),
-                            [(on_edges(q), f.ramp if f.ramp is not None else (f.table.times, f.table.values)) for f, q in products])
-            A = self.vector_potential_func(0)
-        elif sep is not None:
-            # A(t) = f(t) * A_static (the reference's field-ramp example): A_static stays on the
-            # device, the factor is evaluated per step -- by tdgl_run itself for a LinearRamp or a TabulatedRamp
-            factor, static = sep
-            self._A_base = self.A_scale * np.asarray(static(ex, ey, self.z0))[:, :2]
-            self._A_factor = factor.scalar
-            self._A_ramp = factor.ramp
-            table = getattr(factor, "table", None)
-            if table is not None:
-                self._A_table = (table.times, table.values)
-            self.vector_potential_func = lambda t: factor.scalar(t) * self._A_base
-            A = self.vector_potential_func(0)
-        elif self.dynamic_vector_potential:
-            # solver.py:347-362: A(t) on the edge centres, scaled to dimensionless units
-            def vector_potential_func(t):
-                return self.A_scale * np.asarray(applied_vector_potential(ex, ey, self.z0, t=t))[:, :2]
-
-            self.vector_potential_func = vector_potential_func
-            A = vector_potential_func(0)
-        elif callable(applied_vector_potential):
-            A = self.A_scale * np.asarray(applied_vector_potential(ex, ey, self.z0))[:, :2]
-        else:
-            A = self.A_scale * uniform_field_vector_potential(ex, ey, float(applied_vector_potential))[:, :2]
-        if A.shape != self.edge_centers.shape:
-            raise ValueError(f"Unexpected shape for vector_potential: {A.shape}.")
-        self.current_A_applied = A
+        self._set_field(applied_field.from_parameter(applied_vector_potential, self.edge_centers, self.z0, self.A_scale,
+                                                     float(device.layer.z0)))
 
         # ---- disorder parameter epsilon on the sites (solver.py:191-216) ----------------
         self.epsilon_func = None
@@ -282,51 +223,11 @@ class TDGLSolver:
         self.applied_vector_potential = None
         self.disorder_epsilon = epsilon
         # optional time dependence: t -> A[m, 2] / t -> epsilon[n], already dimensionless
-        self.vector_potential_func = vector_potential_func
-        self._A_base = self._A_factor = self._A_ramp = self._A_table = self._A_terms = self._A_loops = None
-        if vector_potential_ramp is not None and vector_potential_table is not None:
-            raise ValueError("vector_potential_ramp and vector_potential_table exclude each other.")
-        if vector_potential_terms is not None:
-            if vector_potential_ramp is not None or vector_potential_table is not None:
-                raise ValueError("vector_potential_terms excludes vector_potential_ramp and vector_potential_table.")
-            self._set_terms(*vector_potential_terms)
-            vector_potential_func = self.vector_potential_func
-        if vector_potential_loops:
-            if vector_potential_ramp is not None or vector_potential_table is not None:
-                raise ValueError("vector_potential_loops excludes vector_potential_ramp and vector_potential_table.")
-            loops = []
-            for lp in vector_potential_loops:
-                c = np.asarray(lp["centers"], dtype=float)
-                if c.ndim == 2 and c.shape[1] == 2:
-                    c = np.column_stack([c, float(lp["z"]) * np.ones(len(c))])
-                loops.append(dict(times=np.asarray(lp["times"], dtype=float), centers=c, radius=float(lp["radius"]),
-                                  currents=np.asarray(lp["currents"], dtype=float) * np.ones(len(c))))
-            static = np.zeros((self.num_edges, 2)) if link_exponents is None else np.asarray(link_exponents, dtype=float)
-            self._set_loops(None if self._A_terms is not None else static, loops,
-                            mesh.edge_mesh.centers, 0.0)
-            vector_potential_func = self.vector_potential_func
-            if self._A_terms is not None or link_exponents is None:
-                link_exponents = vector_potential_func(0.0)
-        if vector_potential_ramp is not None or vector_potential_table is not None:
-            from .parameter import LinearRamp, TabulatedRamp
-
-            if vector_potential_ramp is not None:
-                base, ramp = vector_potential_ramp
-                factor = LinearRamp(**ramp)
-            else:
-                base, times, values = vector_potential_table
-                factor = TabulatedRamp(times, values)
-                self._A_table = (factor.table.times, factor.table.values)
-            self._A_base = np.asarray(base, dtype=float)
-            self._A_factor, self._A_ramp = factor.scalar, factor.ramp
-            self.vector_potential_func = vector_potential_func = lambda t: factor.scalar(t) * self._A_base
+        self._set_field(applied_field.from_dimensionless(
+            mesh.edge_mesh.centers, link_exponents, vector_potential_func, ramp=vector_potential_ramp,
+            table=vector_potential_table, terms=vector_potential_terms, loops=vector_potential_loops))
         self.epsilon_func = epsilon_func
-        self.dynamic_vector_potential = vector_potential_func is not None
         self.dynamic_epsilon = epsilon_func is not None
-        A = np.asarray(link_exponents, dtype=float)
-        if A.shape != (self.num_edges, 2):
-            raise ValueError(f"Unexpected shape for vector_potential: {A.shape}.")
-        self.current_A_applied = A
         self.epsilon = np.asarray(epsilon, dtype=float) * np.ones(len(mesh.sites))
         if np.any(self.epsilon > 1):
             raise ValueError("The disorder parameter epsilon must be <= 1")
@@ -352,56 +253,24 @@ class TDGLSolver:
         self._setup(mesh)
         return self
 
-    def _set_terms(self, A0, terms) -> None:
-        """A(t) = A0 + f_1(t) A_1 + ... + f_K(t) A_K from dimensionless arrays: ``terms`` is a list of ``(A_k[m, 2],
-        spec_k)``, ``spec_k`` a ramp's ``dict(tmin, tmax, initial, final)`` or a table's ``(times, values)``."""
-        from .parameter import FIELD_TERMS_MAX, LinearRamp, TabulatedRamp
+    def _set_field(self, field: applied_field.AppliedField) -> None:
+        """``field`` describes the applied vector potential from here on; the solver starts with its initial A."""
+        self.field = field
+        self.dynamic_vector_potential = field.time_dependent
+        self.vector_potential_func = field.value if field.time_dependent else None
+        A = np.asarray(field.initial, dtype=float)
+        if A.shape != (self.num_edges, 2):
+            raise ValueError(f"Unexpected shape for vector_potential: {A.shape}.")
+        self.current_A_applied = A
 
-        terms = list(terms)
-        if not 1 <= len(terms) <= FIELD_TERMS_MAX:
-            raise ValueError(f"vector_potential_terms: between 1 and {FIELD_TERMS_MAX} terms, got {len(terms)}.")
-        factors, specs, bases = [], [], []
-        for base, spec in terms:
-            f = LinearRamp(**spec) if isinstance(spec, dict) else TabulatedRamp(*spec)
-            factors.append(f.scalar)
-            specs.append(f.ramp if f.ramp is not None else (f.table.times, f.table.values))
-            bases.append(np.asarray(base, dtype=float))
-        self._A_terms = (None if A0 is None else np.asarray(A0, dtype=float), list(zip(bases, specs)))
-        self._A_term_factors = factors
-        self.vector_potential_func = lambda t: self.terms_value([f(t) for f in factors])
-
-    def _set_loops(self, A0, loops, edge_centres, z_film) -> None:
-        """Moving loops on top of the terms set before (``A0`` None) or of the static ``A0[m, 2]``: ``loops`` a list of
-        ``dict(times, centers[n, 3], currents[n], radius)`` in the units of ``edge_centres``, currents dimensionless."""
-        from .hipcore import link_loops_args
-        from .parameter import _loop_potential
-
-        edge_centres = np.asarray(edge_centres, dtype=float)
-        link_loops_args(len(edge_centres), edge_centres, z_film, loops)  # (its refusals, before any device work)
-        self._A_loops = (edge_centres, float(z_film), list(loops))
-        self._A_static = None if A0 is None else np.asarray(A0, dtype=float)
-        under = self.vector_potential_func if self._A_terms is not None else (lambda t: self._A_static)
-        ex, ey = edge_centres[:, 0], edge_centres[:, 1]
-
-        def vector_potential_func(t):  # the host's evaluation: the per-step path and any other consumer
-            A = under(t)
-            for lp in loops:
-                c = [float(np.interp(t, lp["times"], lp["centers"][:, j])) for j in range(3)]
-                A = A + _loop_potential(ex, ey, z_film, c, lp["radius"], float(np.interp(t, lp["times"], lp["currents"])))[:, :2]
-            return A
-
-        self.vector_potential_func = vector_potential_func
+    def note_applied(self, A) -> None:
+        """Keep ``A``, what the field says was applied, as ``current_A_applied``; None: it has nothing newer."""
+        if A is not None:
+            self.current_A_applied = A
 
     def terms_value(self, scales) -> np.ndarray:
-        """``((A0 + s_1 A_1) + s_2 A_2) + ...`` left to right, every product rounded before it is added (NumPy does not
-        contract): the device's value for the same factors, bit for bit."""
-        A0, terms = self._A_terms
-        A = scales[0] * terms[0][0]
-        if A0 is not None:
-            A = A0 + A
-        for s, (base, _) in zip(scales[1:], terms[1:]):
-            A = A + s * base
-        return A
+        """`applied_field.TermsField.terms_value` of this solver's terms."""
+        return self.field.terms_value(scales)
 
     def _setup_host(self, mesh) -> None:
         """The host-side part of the set-up (solver.py:258-289): fixed sites, initial values, mu boundary values."""
@@ -438,21 +307,7 @@ class TDGLSolver:
         )
         self.operators.build_operators()
         self.ctx = self.operators.ctx
-        if self._A_terms is not None:
-            self.ctx.set_link_terms(*self._A_terms)
-        elif self._A_base is not None:
-            self.ctx.set_link_exponents_base(self._A_base, self._A_factor(0))
-            if self._A_ramp is not None:
-                self.ctx.set_link_ramp(**self._A_ramp)
-            elif self._A_table is not None:
-                self.ctx.set_link_table(*self._A_table)
-        elif self._A_loops is not None:
-            self.operators.set_link_exponents(self._A_static)
-        else:
-            self.operators.set_link_exponents(self.current_A_applied)
-        if self._A_loops is not None:
-            self.ctx.set_link_loops(*self._A_loops)
-            self.current_A_applied = self.ctx.link_exponents()
+        self.note_applied(self.field.install(self.operators))
 
         # ---- initial values (solver.py:284-289): _setup_host ----------------------------------------
         self.ctx.set_epsilon(self.epsilon)
@@ -522,7 +377,7 @@ class TDGLSolver:
         """A(t) = f(t) * A_base with f a LinearRamp or a TabulatedRamp, or a sum of a static field and such products
         (`Parameter.separable_terms`), with or without moving current loops (`Parameter.device_sources`): the time loop
         evaluates the factors and the loops' centres and currents itself."""
-        return self._A_ramp is not None or self._A_table is not None or self._A_terms is not None or self._A_loops is not None
+        return self.field.on_device
 
     def device_evaluates_epsilon(self) -> bool:
         """epsilon(t) is a table the time loop evaluates itself (tdgl_set_epsilon_table); the host keeps a copy."""
@@ -531,13 +386,7 @@ class TDGLSolver:
     def update_dynamic_inputs(self, time: float, dt_prev: float) -> None:
         """solver.py:626-648: re-evaluate A(t) (-> link variables and dA/dt with the previous
         step's dt) and epsilon(t) before a step."""
-        if self.device_evaluates_field():
-            pass  # tdgl_run evaluates the ramp, the table or the terms itself (tdgl_set_link_ramp, _table, _terms)
-        elif self._A_base is not None:
-            self.ctx.update_link_scale(self._A_factor(time), dt_prev)
-        elif self.dynamic_vector_potential:
-            self.current_A_applied = np.asarray(self.vector_potential_func(time), dtype=float)
-            self.ctx.update_link_exponents(self.current_A_applied, dt_prev)
+        self.note_applied(self.field.advance(self.ctx, time, dt_prev))
         if self.dynamic_epsilon:
             self.epsilon = np.asarray(self.epsilon_func(time), dtype=float)
             if not self._epsilon_on_device:  # (on the device: this is the host's copy for the saved steps)
@@ -584,12 +433,7 @@ class TDGLSolver:
         else:
             a_ind = np.zeros((self.num_edges, 2)) if induced_vector_potential is None else induced_vector_potential
         extra = []
-        if self._A_loops is not None:
-            self.current_A_applied = ctx.link_exponents()
-        elif self._A_terms is not None:
-            self.current_A_applied = self.terms_value(ctx.link_term_scales())
-        elif self._A_base is not None:
-            self.current_A_applied = ctx.link_scale() * self._A_base
+        self.note_applied(self.field.applied(ctx))
         if self.dynamic_vector_potential:
             extra.append(self.current_A_applied)
         if self.dynamic_epsilon:

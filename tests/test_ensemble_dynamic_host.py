@@ -62,8 +62,8 @@ def test_device_evaluable_drives_are_accepted(device, no_gpu):
     field = tdgl.ConstantField(1.0, field_units="mT", length_units="um")
     reps = _replicas(lambda: tdgl.solve_ensemble(device, _options(), applied_vector_potential=[
         tdgl.LinearRamp(tmin=0, tmax=2) * field, 0.5, tdgl.LinearRamp(tmin=1, tmax=3, initial=0.2, final=0.7) * field]))
-    assert [r._A_ramp is not None for r in reps] == [True, False, True]
-    assert reps[2]._A_ramp == dict(tmin=1, tmax=3, initial=0.2, final=0.7)
+    assert [r.field.kind for r in reps] == ["ramp", "static", "ramp"]
+    assert reps[2].field.ramp == dict(tmin=1, tmax=3, initial=0.2, final=0.7)
     table = TabulatedCurrents([0.0, 1.0], dict(source=[0.0, 1.0], drain=[0.0, -1.0]))
     reps = _replicas(lambda: tdgl.solve_ensemble(device, _options(), terminal_currents=[table, dict(source=1, drain=-1)]))
     assert reps[0]._current_table is not None and reps[1]._current_table is None
@@ -124,12 +124,12 @@ def test_dimensionless_ramps_and_epsilon_tables_broadcast(device, no_gpu):
     # one (A_base, ramp) for every replica; link exponents from the ramp at t = 0
     ens = ensemble_dimensionless(mesh, opts, [None, None], vector_potential_ramp=(base, ramp))
     assert len(ens.reps) == 2
-    assert all(r._A_ramp is not None and np.array_equal(r.current_A_applied, 0.5 * base) for r in ens.reps)
+    assert all(r.field.kind == "ramp" and np.array_equal(r.current_A_applied, 0.5 * base) for r in ens.reps)
     # a list with None for a static replica
     ens = ensemble_dimensionless(mesh, opts, [None, np.zeros((m, 2)), None],
                                  vector_potential_ramp=[(base, ramp), None, (base, dict(ramp, final=3.0))])
-    assert [r._A_ramp is not None for r in ens.reps] == [True, False, True]
-    assert ens.reps[2]._A_ramp["final"] == 3.0
+    assert [r.field.kind for r in ens.reps] == ["ramp", "static", "ramp"]
+    assert ens.reps[2].field.ramp["final"] == 3.0
     # epsilon tables: one for all, or one per replica
     eps0 = np.full(n, 0.9)
     ens = ensemble_dimensionless(mesh, opts, np.zeros((m, 2)), epsilon_table=(eps0, [0.0, 1.0], [1.0, 0.5]))

@@ -110,16 +110,15 @@ def test_solve_ensemble_accepts_tables_next_to_ramps_and_static_fields(device, n
     reps = _replicas(lambda: tdgl.solve_ensemble(device, _options(), applied_vector_potential=[
         tdgl.TabulatedRamp(TIMES, VALUES) * field, tdgl.LinearRamp(tmin=0, tmax=2) * field, 0.0,
         tdgl.TabulatedRamp([0.0, 0.5], [1.0, 0.25]) * field]))
-    assert [r._A_table is not None for r in reps] == [True, False, False, True]
-    assert [r._A_ramp is not None for r in reps] == [False, True, False, False]
+    assert [r.field.kind for r in reps] == ["table", "ramp", "static", "table"]
     assert [r.device_evaluates_field() for r in reps] == [True, True, False, True]
-    times, values = reps[0]._A_table
+    times, values = reps[0].field.table
     assert np.array_equal(times, TIMES) and np.array_equal(values, VALUES)
-    assert len(reps[3]._A_table[0]) == 2  # (tables of different lengths)
+    assert len(reps[3].field.table[0]) == 2  # (tables of different lengths)
     # the links start at the table's value at t = 0
-    assert np.array_equal(reps[0].current_A_applied, VALUES[0] * reps[0]._A_base)
-    assert np.array_equal(reps[3].current_A_applied, 1.0 * reps[3]._A_base)
-    assert np.abs(reps[3]._A_base).max() > 0
+    assert np.array_equal(reps[0].current_A_applied, VALUES[0] * reps[0].field.base)
+    assert np.array_equal(reps[3].current_A_applied, 1.0 * reps[3].field.base)
+    assert np.abs(reps[3].field.base).max() > 0
 
 
 def test_solve_ensemble_refuses_a_field_table_with_other_tables(device, no_gpu):
@@ -157,15 +156,14 @@ def test_dimensionless_field_tables_broadcast(device, no_gpu):
     # one table for every replica; link exponents from the table at t = 0
     ens = ensemble_dimensionless(mesh, opts, [None, None], vector_potential_table=(base, [0.0, 2.0], [0.5, 1.0]))
     assert len(ens.reps) == 2
-    assert all(r._A_table is not None and r._A_ramp is None and np.array_equal(r.current_A_applied, 0.5 * base) for r in ens.reps)
+    assert all(r.field.kind == "table" and np.array_equal(r.current_A_applied, 0.5 * base) for r in ens.reps)
     assert np.array_equal(ens.reps[0].vector_potential_func(1.0), 0.75 * base)
     # a list with None: static, ramped and tabulated replicas in one ensemble, tables of different lengths
     ramp = dict(tmin=0.0, tmax=2.0, initial=0.5, final=1.0)
     ens = ensemble_dimensionless(mesh, opts, [None, np.zeros((m, 2)), None, None],
                                  vector_potential_ramp=[None, None, (base, ramp), None],
                                  vector_potential_table=[wave, None, None, (2.0 * base, [0.5], [3.0])])
-    assert [r._A_table is not None for r in ens.reps] == [True, False, False, True]
-    assert [r._A_ramp is not None for r in ens.reps] == [False, False, True, False]
+    assert [r.field.kind for r in ens.reps] == ["table", "static", "ramp", "table"]
     assert np.array_equal(ens.reps[3].current_A_applied, 6.0 * base)
     # lists of different lengths
     with pytest.raises(ValueError, match="different lengths"):

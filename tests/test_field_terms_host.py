@@ -226,12 +226,11 @@ def test_solve_ensemble_accepts_sums_next_to_single_products_and_static_fields(d
     B, F, G, ramp, wave = _fields()
     reps = _replicas(lambda: tdgl.solve_ensemble(device, _options(), applied_vector_potential=[
         B + wave * G, wave * F, 0.0, ramp * F - G + wave * B]))
-    assert [r._A_terms is not None for r in reps] == [True, False, False, True]
-    assert [r._A_table is not None for r in reps] == [False, True, False, False]
+    assert [r.field.kind for r in reps] == ["terms", "table", "static", "terms"]
     assert [r.device_evaluates_field() for r in reps] == [True, True, False, True]
-    A0, terms = reps[0]._A_terms
+    A0, terms = reps[0].field.A0, reps[0].field.terms
     assert A0 is not None and len(terms) == 1 and np.array_equal(terms[0][1][0], TIMES) and np.array_equal(terms[0][1][1], VALUES)
-    A0, terms = reps[3]._A_terms
+    A0, terms = reps[3].field.A0, reps[3].field.terms
     assert len(terms) == 2 and isinstance(terms[0][1], dict) and terms[0][1]["final"] == 1.5
     # every base carries the device's field scale, and the links start at the sum's value at t = 0
     ex, ey = reps[3].edge_centers[:, 0], reps[3].edge_centers[:, 1]
@@ -276,7 +275,7 @@ def test_dimensionless_field_terms_broadcast(device, no_gpu):
     # one sum for every replica; link exponents from the sum at t = 0
     ens = ensemble_dimensionless(mesh, opts, [None, None], vector_potential_terms=terms)
     assert len(ens.reps) == 2
-    assert all(r._A_terms is not None and r._A_ramp is None and r._A_table is None for r in ens.reps)
+    assert [r.field.kind for r in ens.reps] == ["terms", "terms"]
     assert all(np.array_equal(r.current_A_applied, 0.75 * base) and r.dynamic_vector_potential for r in ens.reps)
     assert np.array_equal(ens.reps[0].vector_potential_func(2.0), (0.25 * base + 1.0 * base) + 1.0 * (2.0 * base))
     # a list with None: static, ramped, tabulated and summed replicas in one ensemble
@@ -284,9 +283,9 @@ def test_dimensionless_field_terms_broadcast(device, no_gpu):
                                  vector_potential_ramp=[None, None, (base, ramp), None],
                                  vector_potential_table=[(base, TIMES, VALUES), None, None, None],
                                  vector_potential_terms=[None, None, None, (None, [(base, (TIMES, VALUES))])])
-    assert [r._A_terms is not None for r in ens.reps] == [False, False, False, True]
+    assert [r.field.kind for r in ens.reps] == ["table", "static", "ramp", "terms"]
     assert [r.device_evaluates_field() for r in ens.reps] == [True, False, True, True]
-    assert ens.reps[3]._A_terms[0] is None and np.array_equal(ens.reps[3].current_A_applied, 0.0 * base)
+    assert ens.reps[3].field.A0 is None and np.array_equal(ens.reps[3].current_A_applied, 0.0 * base)
     with pytest.raises(ValueError, match="different lengths"):
         ensemble_dimensionless(mesh, opts, [np.zeros((m, 2))] * 2, vector_potential_terms=[terms] * 3)
     # terms exclude the ramp and the table of the same replica

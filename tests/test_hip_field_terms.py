@@ -311,11 +311,11 @@ def test_a_single_product_keeps_its_own_entry_points(direct_solve, monkeypatch):
     field = tdgl.ConstantField(1.0, field_units="mT", length_units="um")
     wave = tdgl.TabulatedRamp([0.1, 0.3], [0.0, 1.0])
     single = tdgl.TDGLSolver(dev, opts, applied_vector_potential=wave * field)
-    assert calls == ["set_link_exponents_base", "set_link_table"] and single._A_terms is None
+    assert calls == ["set_link_exponents_base", "set_link_table"] and single.field.kind == "table"
     single.ctx.close()
     del calls[:]
     summed = tdgl.TDGLSolver(dev, opts, applied_vector_potential=tdgl.ConstantField(0.5) + wave * field)
-    assert calls == ["set_link_terms"] and summed._A_terms is not None and summed.device_evaluates_field()
+    assert calls == ["set_link_terms"] and summed.field.kind == "terms" and summed.device_evaluates_field()
     sol = summed.solve()
     ex, ey = summed.edge_centers[:, 0], summed.edge_centers[:, 1]
     want = summed.A_scale * (np.asarray(tdgl.ConstantField(0.5)(ex, ey, summed.z0))[:, :2] + np.asarray(field(ex, ey, summed.z0))[:, :2])

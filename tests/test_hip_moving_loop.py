@@ -329,7 +329,7 @@ def test_user_script_with_a_moving_current_loop(direct_solve, monkeypatch):
     loop = tdgl.MovingCurrentLoop([0.1, 0.8], [[-1.5, -0.5, 0.4], [1.5, 0.5, 0.4]], radius=0.6, current=[0.0, 2.0], current_units="mA")
     bias = tdgl.ConstantField(0.3, field_units="mT", length_units="um")
     solver = tdgl.TDGLSolver(dev, opts, applied_vector_potential=bias + loop)
-    assert solver.device_evaluates_field() and solver._A_loops is not None
+    assert solver.device_evaluates_field() and solver.field.kind == "loops"
     solver.ctx.step_stats(reset=True)
     a = solver.solve()
     st = solver.ctx.step_stats()

@@ -666,6 +666,7 @@ def test_trajectory_with_lagging_link_variables(path):
     the link variables stay where they were (solver.py:636-637) -- through the per-step upload,
     the device-side scaling and the ramp evaluated inside tdgl_run."""
     from tdgl_amd import SolverOptions, TDGLSolver
+    from tdgl_amd.applied_field import ScaledField
 
     g = load_golden("traj_dynamic_lag")
     mesh = reference_mesh(load_golden("mesh_small"))
@@ -686,8 +687,8 @@ def test_trajectory_with_lagging_link_variables(path):
         kw["vector_potential_func"] = lambda t: scale(t) * A_base
     solver = TDGLSolver.from_dimensionless(mesh, opts, scale(0.0) * A_base, 1.0, U_DEFAULT, GAMMA_DEFAULT, **kw)
     if path == "scale_per_step":  # the same numbers, scaled on the device instead of uploaded
-        solver._A_base, solver._A_factor = A_base, scale
-        solver.ctx.set_link_exponents_base(A_base, scale(0.0))
+        solver.field = ScaledField(A_base, scale)
+        solver.field.install(solver.operators)
     sol = solver.solve()
     _assert_hip_trajectory(g, sol, 1e-8)
     # A_applied that is saved follows the ramp (value at the last step taken) although the links do not

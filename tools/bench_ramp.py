@@ -9,6 +9,7 @@ import numpy as np
 sys.path.insert(0, "tests"); sys.path.insert(0, "py-tdgl_amd"); sys.path.insert(0, ".")
 from helpers import synthetic_mesh, uniform_field_A, U_DEFAULT, GAMMA_DEFAULT  # noqa: E402
 from tdgl_amd import SolverOptions, TDGLSolver  # noqa: E402
+from tdgl_amd.applied_field import ScaledField  # noqa: E402
 
 L = int(sys.argv[1]) if len(sys.argv) > 1 else 465
 mesh = synthetic_mesh(L)
@@ -21,8 +22,8 @@ for path in ("upload_per_step", "scale_per_step", "native_ramp"):
         vector_potential_func=lambda t: scale(t) * A_base)
     s = TDGLSolver.from_dimensionless(mesh, opts, 0.0 * A_base, 1.0, U_DEFAULT, GAMMA_DEFAULT, **kw)
     if path == "scale_per_step":
-        s._A_base, s._A_factor = A_base, scale
-        s.ctx.set_link_exponents_base(A_base, 0.0)
+        s.field = ScaledField(A_base, scale)
+        s.field.install(s.operators)
     ctx = s.ctx
     ctx.set_state(s.psi_init, s.mu_init)
     ctx.begin_stage()
