@@ -1110,12 +1110,11 @@ static int precond_calibrate(tdgl_ctx *ctx, double *t_apply_us, double *t_vcycle
     TDGL_TRY(median_us(
         [&]() -> int {
             if (precond_f32_on(ctx) && ctx->deep) {
-                (void)vcycle0_f32(ctx, ctx->pcg_r.p, ctx->part_pair[0].p, nullptr, nullptr, true);
+                (void)vcycle0_f32(ctx, ctx->pcg_r.p, ctx->part_pair[0].p, Cycle0Out::ghosts_no_sums());
             } else if (precond_f32_on(ctx)) {
-                (void)vcycle0_f32(ctx, ctx->pcg_r.p, ctx->part_pair[0].p, distributed(ctx) ? ctx->levels[0]->xb.p : (double *)nullptr);
+                (void)vcycle0_f32(ctx, ctx->pcg_r.p, ctx->part_pair[0].p, distributed(ctx) ? Cycle0Out::f64_rz(ctx->levels[0]->xb.p) : Cycle0Out::rz());
             } else {
-                double *z = nullptr;
-                vcycle_level(ctx, 0, ctx->pcg_r.p, &z, ctx->part_pair[0].p, false);
+                (void)vcycle_level(ctx, 0, ctx->pcg_r.p, ctx->part_pair[0].p, false);
             }
             return TDGL_OK;
         },

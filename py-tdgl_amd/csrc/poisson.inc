@@ -1,5 +1,6 @@
 // mu Poisson solve: conjugate gradients preconditioned by one smoothed-aggregation AMG
-// V-cycle, all level operators resident in HBM.  Included by tdgl_hip.hip.
+// V-cycle (vcycle.inc), all level operators resident in HBM.  Included by tdgl_hip.hip.  Here: the options and stats,
+// the hierarchy setters, the direct solves, the guard and the CG.
 //
 // Replaces mu = mu_laplacian_lu(rhs) (tdgl/solver/solver.py:516; SuperLU factorisation at
 // tdgl/finite_volume/operators.py:305-308).  The reference matrix L_mu is singular (pure
@@ -455,578 +456,6 @@ extern "C" int tdgl_poisson_set_collapsed_tail(tdgl_ctx *ctx, const tdgl_collaps
     return TDGL_OK;
 }
 
-// the collapsed chain applies while the smoother settings are the ones it was built for
-static inline bool collapsed_on(const tdgl_ctx *ctx) {
-    return ctx->tail_level >= 1 && ctx->tail_level < (int)ctx->levels.size() && ctx->popt.nu == ctx->tail_nu &&
-           ctx->popt.smoother == ctx->tail_smoother && std::fabs(ctx->popt.cheb_lo - ctx->tail_cheb_lo) <= 1e-15;
-}
-
-// ---------------------------------------------------------------------------------------
-// fixed-grid launch geometry: at most NB workgroups, a multiple of 8 (one share per XCD)
-static inline void sell_fixed_grid(int n_slices, int *per_xcd, int *grid) {
-    const int tiles = (n_slices + BLOCK / WAVE - 1) / (BLOCK / WAVE);
-    *per_xcd = std::max(1, (tiles + XCDS - 1) / XCDS);
-    *grid = std::min(NB, *per_xcd * XCDS);
-}
-
-static inline int vec_grid(int64_t n) { return (int)std::min<int64_t>(NB, (n + BLOCK - 1) / BLOCK); }
-
-// `part` (tile_range): a DOT kernel split into the ghost-free tiles (1) and the rest (2) gives
-// each launch one half of the NB-entry partial array.
-template <int MODE, int DOT>
-static void launch_sell(tdgl_ctx *ctx, const SellF64 &A, const double *x, const double *b,
-                        const double *dinv, double c1, double c2, double *d, double *y, double *partial,
-                        int part = 0) {
-    int tile_base, slice_end, tiles;
-    // (two distributed levels: the level-0 operator also has the rows of the first ghost layer, which only the
-    // smoothing pass of the V-cycle uses; every launch through here is about the owned rows)
-    const bool own_only = ctx->deep && !ctx->levels.empty() && &A == &ctx->levels[0]->A;
-    const int64_t n_rows = own_only ? ctx->n_own : A.pat.n_rows;
-    const int n_slices = own_only ? (int)((ctx->n_own + WAVE - 1) / WAVE) : A.pat.n_slices;
-    tile_range(ctx, n_slices, part, &tile_base, &slice_end, &tiles);
-    const int per_xcd = std::max(1, (tiles + XCDS - 1) / XCDS);
-    int grid = std::min(NB, per_xcd * XCDS);
-    // every writer of a partial array fills all of its entries (idle workgroups write 0), so
-    // kernels with different natural grids can share one array
-    if (DOT != DOT_NONE) {
-        grid = part == 0 ? ctx->npart : NB / 2;  // (split launches: one-process-per-GPU mode, npart == NB)
-        if (part == 2) partial += NB / 2;
-    } else if (tiles <= 0) {
-        return;
-    }
-    if (A.pat.use16)
-        hipLaunchKernelGGL((k_sell_spmv<MODE, DOT, int16_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, slice_end,
-                           per_xcd, tile_base, n_rows, A.pat.slice_off.p, A.pat.cols16.p, A.vals.p, x, b, dinv,
-                           c1, c2, d, y, partial);
-    else
-        hipLaunchKernelGGL((k_sell_spmv<MODE, DOT, int32_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, slice_end,
-                           per_xcd, tile_base, n_rows, A.pat.slice_off.p, A.pat.cols.p, A.vals.p, x, b, dinv,
-                           c1, c2, d, y, partial);
-}
-
-template <int TMODE>
-static void launch_transfer(tdgl_ctx *ctx, const SellF64 &M, const double *x, const double *dinv, const double *b,
-                            double c, double *y) {
-    int per_xcd, grid;
-    sell_fixed_grid(M.pat.n_slices, &per_xcd, &grid);
-    hipLaunchKernelGGL((k_sell_transfer<TMODE>), dim3(grid), dim3(BLOCK), 0, ctx->stream, M.pat.n_slices, per_xcd,
-                       M.pat.n_rows, M.pat.slice_off.p, M.pat.cols.p, (const int32_t *)nullptr, M.vals.p, x, dinv, b, c, y);
-}
-
-// grid of the CSR kernels: a multiple of 8 (xcd_tile needs whole rounds over the XCDs)
-static inline int csr_grid(int64_t threads) { return (int)round_up(grid_for(threads), XCDS); }
-
-template <int LANES, int OP, int B = 2>
-static void launch_csr(tdgl_ctx *ctx, const Csr &M, const double *x, const double *b, const double *dinv,
-                       double c1, double c2, double *d, double *y) {
-    hipLaunchKernelGGL((k_csr_multi<LANES, OP, B>), dim3(csr_grid(M.n_rows * LANES)), dim3(BLOCK), 0, ctx->stream,
-                       M.n_rows, M.indptr.p, M.indices.p, M.data.p, x, b, dinv, 0.0, c1, c2, d, y);
-}
-
-// first two smoothing steps from a zero guess, fused (coarse levels, degree >= 2)
-static void launch_csr_pre2(tdgl_ctx *ctx, const Csr &M, const double *b, const double *dinv, double c0, double c1,
-                            double c2, double *d, double *y) {
-    hipLaunchKernelGGL((k_csr_multi<4, C_PRE2, 4>), dim3(csr_grid(M.n_rows * 4)), dim3(BLOCK), 0, ctx->stream, M.n_rows,
-                       M.indptr.p, M.indices.p, M.data.p, b, nullptr, dinv, c0, c1, c2, d, y);
-}
-
-// level operator application: SELL on level 0, 8-lane CSR below
-static void level_smooth(tdgl_ctx *ctx, int k, AmgLevel &L, const double *x, const double *b, double c1,
-                         double c2, double *d, double *y, double *dot_partial) {
-    if (k == 0) {
-        if (dot_partial)
-            launch_sell<SMOOTH, DOT_BY>(ctx, L.A, x, b, L.dinv.p, c1, c2, d, y, dot_partial);
-        else
-            launch_sell<SMOOTH, DOT_NONE>(ctx, L.A, x, b, L.dinv.p, c1, c2, d, y, nullptr);
-    } else {
-        launch_csr<4, C_SMOOTH, 4>(ctx, L.Ac, x, b, L.dinv.p, c1, c2, d, y);
-    }
-}
-
-static void level_residual(tdgl_ctx *ctx, int k, AmgLevel &L, const double *x, const double *b, double *r) {
-    if (k == 0)
-        launch_sell<RESID, DOT_NONE>(ctx, L.A, x, b, nullptr, 0.0, 0.0, nullptr, r, nullptr);
-    else
-        launch_csr<4, C_RESID, 4>(ctx, L.Ac, x, b, nullptr, 0.0, 0.0, nullptr, r);
-}
-
-static void poisson_spmv_level0(tdgl_ctx *ctx, const double *x, double *y) {
-    launch_sell<AX, DOT_NONE>(ctx, ctx->levels[0]->A, x, nullptr, nullptr, 0.0, 0.0, nullptr, y, nullptr);
-}
-
-// Smoother coefficients: step k computes d = c1[k] d + c2[k] dinv (b - A x), x += d.
-struct SmootherCoef {
-    double c1[8], c2[8];
-    bool need_d;
-};
-
-static inline int level_degree(const tdgl_ctx *ctx, int k) {
-    return (k == 0 && ctx->popt.nu_fine > 0) ? ctx->popt.nu_fine : ctx->popt.nu;
-}
-
-static SmootherCoef smoother_coef(const tdgl_ctx *ctx, const AmgLevel &L, int nu) {
-    SmootherCoef s{};
-    if (ctx->popt.smoother == 0) {  // damped Jacobi, omega = (4/3)/rho
-        for (int k = 0; k < nu; ++k) {
-            s.c1[k] = 0.0;
-            s.c2[k] = (4.0 / 3.0) / L.rho;
-        }
-        s.need_d = false;
-        return s;
-    }
-    const double hi = L.rho, lo = ctx->popt.cheb_lo * L.rho;
-    const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
-    double rho_k = 1.0 / sigma;
-    s.c1[0] = 0.0;
-    s.c2[0] = 1.0 / theta;
-    for (int k = 1; k < nu; ++k) {
-        const double rho_new = 1.0 / (2.0 * sigma - rho_k);
-        s.c1[k] = rho_new * rho_k;
-        s.c2[k] = 2.0 * rho_new / delta;
-        rho_k = rho_new;
-    }
-    s.need_d = nu > 1;
-    return s;
-}
-
-static inline bool fused_restriction_on(const tdgl_ctx *ctx, double c);
-
-// One V-cycle on level k: returns (via *result) the level buffer holding the correction for
-// right-hand side b.  With dot_partial set, the last level-0 smoothing step also writes the
-// NB partials of sum(b * result) there.
-static void vcycle_level(tdgl_ctx *ctx, int k, const double *b, double **result, double *dot_partial,
-                         bool f32 = false) {
-    AmgLevel &L = *ctx->levels[k];
-    const int nu = level_degree(ctx, k);
-    if (k == (int)ctx->levels.size() - 1) {
-        const int nc = (int)L.n;
-        hipLaunchKernelGGL(k_dense_matvec, dim3(grid_for((int64_t)nc * WAVE)), dim3(BLOCK), 0, ctx->stream,
-                           nc, ctx->coarse_pinv.p, b, L.xa.p);
-        *result = L.xa.p;
-        if (dot_partial)  // single-level hierarchy
-            hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, L.n_pad, b, L.xa.p, dot_partial);
-        return;
-    }
-    if (k >= 1 && collapsed_on(ctx) && k == ctx->tail_level) {
-        // everything from this level down through explicit operators: one or two launches
-        const bool t32 = f32 && ctx->tailG32.n > 0;
-        const int nt = (int)L.n, g = (int)ctx->tail_g_rows;
-        // (mode 1: y = G b lands right behind b, where the sparse operator's remapped columns point)
-        double *yv = ctx->tail_mode == 0 ? L.xa.p : const_cast<double *>(b) + L.n_pad;
-        (void)nt;
-        if (t32)
-            hipLaunchKernelGGL((k_dense_rows<float>), dim3(g), dim3(BLOCK), 0, ctx->stream, (int)ctx->tail_ldg,
-                               ctx->tailG32.p, b, yv);
-        else
-            hipLaunchKernelGGL((k_dense_rows<double>), dim3(g), dim3(BLOCK), 0, ctx->stream, (int)ctx->tail_ldg,
-                               ctx->tailG.p, b, yv);
-        if (ctx->tail_mode == 1) {
-            const Csr &W = ctx->tailW;
-            const int grid = csr_grid(L.n * WAVE);
-            if (t32 && ctx->tailW_idx16.n > 0)
-                hipLaunchKernelGGL((k_tail_up<8, float, uint16_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, L.n, W.indptr.p,
-                                   ctx->tailW_idx16.p, W.data32.p, b, (int)ctx->tail_ldv, ctx->tailV32.p, (const double *)yv,
-                                   L.xa.p);
-            else if (t32)
-                hipLaunchKernelGGL((k_tail_up<8, float, int32_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, L.n, W.indptr.p,
-                                   W.indices.p, W.data32.p, b, (int)ctx->tail_ldv, ctx->tailV32.p, (const double *)yv, L.xa.p);
-            else
-                hipLaunchKernelGGL((k_tail_up<8, double, int32_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream, L.n, W.indptr.p,
-                                   W.indices.p, W.data.p, b, (int)ctx->tail_ldv, ctx->tailV.p, (const double *)yv, L.xa.p);
-        }
-        *result = L.xa.p;
-        return;
-    }
-    const SmootherCoef sc = smoother_coef(ctx, L, nu);
-    double *d = sc.need_d ? L.d.p : nullptr;
-    double *x = L.xa.p, *y = L.xb.p;
-    if (k == 0 && nu == 1) {
-        // Degree-1 smoothing on level 0 (default): the pre-smoothed iterate x1 = c dinv b is
-        // never stored.  r = b - A x1 gathers dinv*b directly, the prolongation kernel writes
-        // x = c dinv b + P e, one smoothing step follows.  Distributed: ONE exchange (ghosts of
-        // b) covers the residual; x is then valid on the ghost rows too.
-        AmgLevel &C = *ctx->levels[1];
-        if (fused_restriction_on(ctx, sc.c2[0])) {
-            // C.b = R (I - c A D^-1) b in one pass (tdgl_poisson_set_fused_restriction); one process
-            // per GPU: ghosts of b first, the partial coarse right-hand sides summed after
-            if (distributed(ctx)) (void)comm_halo(ctx, const_cast<double *>(b), 1);
-            launch_csr<16, C_AX, 4>(ctx, ctx->fusedR, b, nullptr, nullptr, 0.0, 0.0, nullptr, C.b.p);
-            if (distributed(ctx)) (void)comm_allreduce(ctx, C.b.p, C.n, 0);
-            double *xc = nullptr;
-            vcycle_level(ctx, 1, C.b.p, &xc, nullptr, f32);
-            launch_transfer<T_BASE>(ctx, L.P, xc, L.dinv.p, b, sc.c2[0], x);
-            level_smooth(ctx, 0, L, x, b, 0.0, sc.c2[0], nullptr, y, dot_partial);
-            *result = y;
-            return;
-        }
-        if (overlap_on(ctx)) {  // ghost-free rows run while the ghosts of b travel
-            (void)comm_halo_start(ctx, const_cast<double *>(b), 1);
-            launch_sell<RESID0, DOT_NONE>(ctx, L.A, b, nullptr, L.dinv.p, 0.0, sc.c2[0], nullptr, L.r.p, nullptr, 1);
-            (void)comm_halo_wait(ctx);
-            launch_sell<RESID0, DOT_NONE>(ctx, L.A, b, nullptr, L.dinv.p, 0.0, sc.c2[0], nullptr, L.r.p, nullptr, 2);
-        } else {
-            if (distributed(ctx)) (void)comm_halo(ctx, const_cast<double *>(b), 1);
-            launch_sell<RESID0, DOT_NONE>(ctx, L.A, b, nullptr, L.dinv.p, 0.0, sc.c2[0], nullptr, L.r.p, nullptr);
-        }
-        launch_csr<16, C_AX>(ctx, L.R, L.r.p, nullptr, nullptr, 0.0, 0.0, nullptr, C.b.p);
-        if (distributed(ctx)) (void)comm_allreduce(ctx, C.b.p, C.n, 0);
-        double *xc = nullptr;
-        vcycle_level(ctx, 1, C.b.p, &xc, nullptr, f32);
-        launch_transfer<T_BASE>(ctx, L.P, xc, L.dinv.p, b, sc.c2[0], x);
-        level_smooth(ctx, 0, L, x, b, 0.0, sc.c2[0], nullptr, y, dot_partial);
-        *result = y;
-        return;
-    }
-    // Level 0 is distributed (rows = owned sites): ghost entries of the iterate are refreshed
-    // before every operator application.  Levels >= 1 are replicated on every rank.
-    const bool dist0 = (k == 0) && distributed(ctx);
-    const int64_t n_rows = (k == 0) ? ctx->n_own : L.n;
-    // pre-smoothing from a zero initial guess
-    int s_first = 1;
-    const bool use32 = f32 && k > 0 && (L.explicit_only ? L.M.data32.n > 0 : (L.fused && L.Ac.data32.n > 0));
-    // collapsed chain: the next right-hand side M b and the two-step pre-smoothing in one launch
-    const bool down1 = k > 0 && nu == 2 && (L.fused || L.explicit_only) && L.M.nnz > 0 && collapsed_on(ctx) && k < ctx->tail_level &&
-                       (!use32 || L.M.data32.n > 0);
-    // ... and the way up as one launch too (explicit W, V): then x = S b is not needed at all
-    const bool up1 = down1 && L.Wup.nnz > 0 && (!use32 || L.Wup.data32.n > 0);
-    if (up1) {
-        AmgLevel &Cn = *ctx->levels[k + 1];
-        if (use32)
-            hipLaunchKernelGGL((k_csr_multi<32, C_AX, 8, float>), dim3(csr_grid(Cn.n * 32)), dim3(BLOCK), 0, ctx->stream,
-                               Cn.n, L.M.indptr.p, L.M.indices.p, L.M.data32.p, b, (const double *)nullptr,
-                               (const double *)nullptr, 0.0, 0.0, 0.0, (double *)nullptr, Cn.b.p);
-        else
-            hipLaunchKernelGGL((k_csr_multi<32, C_AX, 8, double>), dim3(csr_grid(Cn.n * 32)), dim3(BLOCK), 0, ctx->stream,
-                               Cn.n, L.M.indptr.p, L.M.indices.p, L.M.data.p, b, (const double *)nullptr,
-                               (const double *)nullptr, 0.0, 0.0, 0.0, (double *)nullptr, Cn.b.p);
-        // two distributed levels: M holds this rank's owned level-1 columns -- the partial level-2 right-hand sides
-        // are summed over ranks (fp32 like the operators that consume them: n2 values, 83 KB at 4M sites)
-        if (L.explicit_only) (void)comm_allreduce_via_f32(ctx, Cn.b.p, Cn.n);
-        double *xn = nullptr;
-        vcycle_level(ctx, k + 1, Cn.b.p, &xn, nullptr, f32);
-        // (8 lanes per row, 8 entries per lane in flight: measured best of 4 / 8 / 16 / 32 lanes and 3 - 8 entries)
-        if (use32 && L.up_woff.n > 0 && L.up_w16.n > 0)
-            hipLaunchKernelGGL((k_mid_up<8, 8, 2, half_t>), dim3(csr_grid(L.n * 8)), dim3(BLOCK), 0, ctx->stream, L.n,
-                               L.Wup.indptr.p, L.up_wbase.p, L.up_woff.p, L.up_w16.p, b, L.Vneg.indptr.p, L.up_vidx.p,
-                               L.up_v16.p, (const double *)xn, x);
-        else if (use32 && L.up_woff.n > 0)
-            hipLaunchKernelGGL((k_mid_up<8, 8, 2, float>), dim3(csr_grid(L.n * 8)), dim3(BLOCK), 0, ctx->stream, L.n,
-                               L.Wup.indptr.p, L.up_wbase.p, L.up_woff.p, L.Wup.data32.p, b, L.Vneg.indptr.p, L.up_vidx.p,
-                               L.Vneg.data32.p, (const double *)xn, x);
-        else if (use32)
-            hipLaunchKernelGGL((k_csr_dual<16, D_RESTRICT, 4, 2, float>), dim3(csr_grid(L.n * 16)), dim3(BLOCK), 0,
-                               ctx->stream, L.n, L.Wup.indptr.p, L.Wup.indices.p, L.Wup.data32.p, b, L.Vneg.indptr.p,
-                               L.Vneg.indices.p, L.Vneg.data32.p, (const float *)nullptr, (const double *)xn,
-                               (const double *)nullptr, (const double *)nullptr, 0.0, (double *)nullptr, x);
-        else
-            hipLaunchKernelGGL((k_csr_dual<16, D_RESTRICT, 4, 2, double>), dim3(csr_grid(L.n * 16)), dim3(BLOCK), 0,
-                               ctx->stream, L.n, L.Wup.indptr.p, L.Wup.indices.p, L.Wup.data.p, b, L.Vneg.indptr.p,
-                               L.Vneg.indices.p, L.Vneg.data.p, (const double *)nullptr, (const double *)xn,
-                               (const double *)nullptr, (const double *)nullptr, 0.0, (double *)nullptr, x);
-        *result = x;
-        return;
-    }
-    if (down1) {
-        AmgLevel &Cn = *ctx->levels[k + 1];
-        const int nbM = csr_grid(Cn.n * 32), nbA = csr_grid(L.Ac.n_rows * 4);
-        if (use32)
-            hipLaunchKernelGGL((k_csr_down<32, 8, float>), dim3(nbM + nbA), dim3(BLOCK), 0, ctx->stream, nbM, Cn.n,
-                               L.M.indptr.p, L.M.indices.p, L.M.data32.p, b, Cn.b.p, L.Ac.n_rows, L.Ac.indptr.p,
-                               L.Ac.indices.p, L.Ac.data32.p, L.dinv.p, sc.c2[0], sc.c1[1], sc.c2[1], d, x);
-        else
-            hipLaunchKernelGGL((k_csr_down<32, 8, double>), dim3(nbM + nbA), dim3(BLOCK), 0, ctx->stream, nbM, Cn.n,
-                               L.M.indptr.p, L.M.indices.p, L.M.data.p, b, Cn.b.p, L.Ac.n_rows, L.Ac.indptr.p,
-                               L.Ac.indices.p, L.Ac.data.p, L.dinv.p, sc.c2[0], sc.c1[1], sc.c2[1], d, x);
-        s_first = 2;
-    } else if (use32 && nu >= 2) {
-        hipLaunchKernelGGL((k_csr_multi<4, C_PRE2, 4, float>), dim3(csr_grid(L.Ac.n_rows * 4)), dim3(BLOCK), 0,
-                           ctx->stream, L.Ac.n_rows, L.Ac.indptr.p, L.Ac.indices.p, L.Ac.data32.p, b,
-                           (const double *)nullptr, L.dinv.p, sc.c2[0], sc.c1[1], sc.c2[1], d, x);
-        s_first = 2;
-    } else if (k > 0 && nu >= 2) {  // steps 0 and 1 in one kernel
-        launch_csr_pre2(ctx, L.Ac, b, L.dinv.p, sc.c2[0], sc.c1[1], sc.c2[1], d, x);
-        s_first = 2;
-    } else {
-        hipLaunchKernelGGL(k_smooth0, dim3(vec_grid(n_rows)), dim3(BLOCK), 0, ctx->stream, n_rows, sc.c2[0],
-                           L.dinv.p, b, d, x);
-    }
-    for (int s = s_first; s < nu; ++s) {
-        if (dist0) (void)comm_halo(ctx, x, 1);
-        level_smooth(ctx, k, L, x, b, sc.c1[s], sc.c2[s], d, y, nullptr);
-        std::swap(x, y);
-    }
-    AmgLevel &C = *ctx->levels[k + 1];
-    const bool fused = k > 0 && L.fused;
-    if (down1) {
-        // C.b is already there
-    } else if (use32) {
-        hipLaunchKernelGGL((k_csr_dual<16, D_RESTRICT, 4, 8, float>), dim3(csr_grid(C.n * 16)), dim3(BLOCK), 0,
-                           ctx->stream, C.n, L.R.indptr.p, L.R.indices.p, L.R.data32.p, b, L.RA.indptr.p,
-                           L.RA.indices.p, L.RA.data32.p, (const float *)nullptr, (const double *)x,
-                           (const double *)nullptr, (const double *)nullptr, 0.0, (double *)nullptr, C.b.p);
-    } else if (fused) {
-        // C.b = R b - (R A) x in one launch
-        hipLaunchKernelGGL((k_csr_dual<16, D_RESTRICT, 4, 8>), dim3(csr_grid(C.n * 16)), dim3(BLOCK), 0, ctx->stream,
-                           C.n, L.R.indptr.p, L.R.indices.p, L.R.data.p, b, L.RA.indptr.p, L.RA.indices.p,
-                           L.RA.data.p, (const double *)nullptr, (const double *)x, (const double *)nullptr,
-                           (const double *)nullptr, 0.0, (double *)nullptr, C.b.p);
-    } else {
-        if (dist0) (void)comm_halo(ctx, x, 1);
-        level_residual(ctx, k, L, x, b, L.r.p);
-        // restriction; in distributed mode R holds the owned fine columns only: the partial coarse
-        // right-hand sides are summed over ranks
-        launch_csr<16, C_AX>(ctx, L.R, L.r.p, nullptr, nullptr, 0.0, 0.0, nullptr, C.b.p);
-        if (dist0) (void)comm_allreduce(ctx, C.b.p, C.n, 0);
-    }
-    double *xc = nullptr;
-    vcycle_level(ctx, k + 1, C.b.p, &xc, nullptr, f32);
-    int s_post = 0;
-    if (use32) {
-        hipLaunchKernelGGL((k_csr_dual<4, D_PSMOOTH, 4, 2, float>), dim3(csr_grid(L.n * 4)), dim3(BLOCK), 0,
-                           ctx->stream, L.n, L.Ac.indptr.p, L.Ac.indices.p, L.Ac.data32.p, (const double *)x,
-                           L.AP.indptr.p, L.AP.indices.p, L.AP.data32.p, (const float *)L.APp32.p, (const double *)xc,
-                           b, L.dinv.p, sc.c2[0], d, y);
-        std::swap(x, y);
-        s_post = 1;
-    } else if (fused) {
-        // x' = x + P e and the first post-smoothing step in one launch (c1[0] = 0)
-        hipLaunchKernelGGL((k_csr_dual<4, D_PSMOOTH, 4, 2>), dim3(csr_grid(L.n * 4)), dim3(BLOCK), 0, ctx->stream,
-                           L.n, L.Ac.indptr.p, L.Ac.indices.p, L.Ac.data.p, (const double *)x, L.AP.indptr.p,
-                           L.AP.indices.p, L.AP.data.p, L.APp.p, (const double *)xc, b, L.dinv.p, sc.c2[0], d, y);
-        std::swap(x, y);
-        s_post = 1;
-    } else if (k == 0) {
-        launch_transfer<T_ADD>(ctx, L.P, xc, nullptr, nullptr, 0.0, x);
-    } else {
-        launch_csr<4, C_ADD, 1>(ctx, L.Pc, xc, nullptr, nullptr, 0.0, 0.0, nullptr, x);
-    }
-    // post-smoothing (the polynomial restarts: c1[0] = 0)
-    // (the prolongation also updated the ghost rows, so the first step needs no exchange)
-    for (int s = s_post; s < nu; ++s) {
-        if (dist0 && s > 0) (void)comm_halo(ctx, x, 1);
-        if (use32)
-            hipLaunchKernelGGL((k_csr_multi<4, C_SMOOTH, 4, float>), dim3(csr_grid(L.Ac.n_rows * 4)), dim3(BLOCK), 0,
-                               ctx->stream, L.Ac.n_rows, L.Ac.indptr.p, L.Ac.indices.p, L.Ac.data32.p,
-                               (const double *)x, b, L.dinv.p, 0.0, sc.c1[s], sc.c2[s], d, y);
-        else
-            level_smooth(ctx, k, L, x, b, sc.c1[s], sc.c2[s], d, y, (s == nu - 1) ? dot_partial : nullptr);
-        std::swap(x, y);
-    }
-    *result = x;
-}
-
-// ---- mixed-precision preconditioner -----------------------------------------------------
-// The V-cycle is an approximation of A^-1 by construction; storing its level-0 operators in
-// fp32 perturbs it by ~1e-7 relative, far below its own approximation error, while the CG that
-// it preconditions (A p, the residual recurrence, dot products, the convergence test) stays
-// fp64 and converges to the same rtol.  What it buys: the three level-0 passes of the cycle
-// stream 8 instead of 12 bytes per matrix entry and 4 instead of 8 per vector entry.
-static inline bool fused_restriction_on(const tdgl_ctx *ctx, double c) {
-    return ctx->fusedR.nnz > 0 && ctx->fusedR.n_cols == ctx->levels[0]->n_cols && std::fabs(ctx->fusedR_c - c) <= 1e-12 * c;
-}
-
-static inline bool precond_f32_on(const tdgl_ctx *ctx) {
-    if (!ctx->popt.precond_fp32 || ctx->levels.size() < 2 || level_degree(ctx, 0) != 1) return false;
-    const SmootherCoef sc = smoother_coef(ctx, *ctx->levels[0], 1);
-    return fused_restriction_on(ctx, sc.c2[0]);
-}
-
-// fp32 copies of the intermediate-level operators (any mode, also one-process-per-GPU: these
-// levels are replicated on every rank)
-static int ensure_coarse_f32(tdgl_ctx *ctx) {
-    if (ctx->coarse32_ready) return TDGL_OK;
-    ctx->pcg_epoch += 1;
-    auto convert = [&](const double *src, DevBuf<float> &dst, int64_t n) -> int {
-        HIP_TRY(ctx, dst.alloc(std::max<int64_t>(n, 1)));
-        if (n > 0) hipLaunchKernelGGL(k_to_f32, dim3(grid_for(n)), dim3(BLOCK), 0, ctx->stream, n, src, dst.p);
-        return TDGL_OK;
-    };
-    if (ctx->tail_level >= 1) {
-        TDGL_TRY(convert(ctx->tailG.p, ctx->tailG32, (int64_t)ctx->tailG.n));
-        if (ctx->tail_mode == 1) {
-            if (ctx->tailV.n > 0) TDGL_TRY(convert(ctx->tailV.p, ctx->tailV32, (int64_t)ctx->tailV.n));
-            else ctx->tailV32.release();
-            TDGL_TRY(convert(ctx->tailW.data.p, ctx->tailW.data32, ctx->tailW.nnz));
-        }
-    } else {
-        ctx->tailG32.release();
-    }
-    for (size_t k = 1; k + 1 < ctx->levels.size(); ++k) {  // levels with pre-multiplied transfers
-        AmgLevel &C = *ctx->levels[k];
-        if (!C.fused && !C.explicit_only) continue;
-        if (C.M.nnz > 0) TDGL_TRY(convert(C.M.data.p, C.M.data32, C.M.nnz));
-        if (C.Wup.nnz > 0) {
-            TDGL_TRY(convert(C.Wup.data.p, C.Wup.data32, C.Wup.nnz));
-            TDGL_TRY(convert(C.Vneg.data.p, C.Vneg.data32, C.Vneg.nnz));
-            C.up_w16.release();
-            if (ctx->popt.precond_fp32 >= 2 && C.up_woff.n > 0) {  // (entries are O(1))
-                HIP_TRY(ctx, C.up_w16.alloc(std::max<int64_t>(C.Wup.nnz, 1)));
-                HIP_TRY(ctx, C.up_v16.alloc(std::max<int64_t>(C.Vneg.nnz, 1)));
-                hipLaunchKernelGGL(k_to_f16, dim3(grid_for(C.Wup.nnz)), dim3(BLOCK), 0, ctx->stream, C.Wup.nnz,
-                                   (const double *)C.Wup.data.p, C.up_w16.p);
-                if (C.Vneg.nnz > 0)
-                    hipLaunchKernelGGL(k_to_f16, dim3(grid_for(C.Vneg.nnz)), dim3(BLOCK), 0, ctx->stream, C.Vneg.nnz,
-                                       (const double *)C.Vneg.data.p, C.up_v16.p);
-            }
-        }
-        if (C.explicit_only) continue;
-        TDGL_TRY(convert(C.Ac.data.p, C.Ac.data32, C.Ac.nnz));
-        TDGL_TRY(convert(C.R.data.p, C.R.data32, C.R.nnz));
-        TDGL_TRY(convert(C.RA.data.p, C.RA.data32, C.RA.nnz));
-        TDGL_TRY(convert(C.AP.data.p, C.AP.data32, C.AP.nnz));
-        TDGL_TRY(convert(C.APp.p, C.APp32, C.AP.nnz));
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->coarse32_ready = true;
-    return TDGL_OK;
-}
-
-static int ensure_f32(tdgl_ctx *ctx) {
-    TDGL_TRY(ensure_coarse_f32(ctx));
-    if (ctx->f32_ready) return TDGL_OK;
-    ctx->pcg_epoch += 1;
-    AmgLevel &L = *ctx->levels[0];
-    auto convert = [&](const double *src, DevBuf<float> &dst, int64_t n) -> int {
-        HIP_TRY(ctx, dst.alloc(std::max<int64_t>(n, 1)));
-        if (n > 0) hipLaunchKernelGGL(k_to_f32, dim3(grid_for(n)), dim3(BLOCK), 0, ctx->stream, n, src, dst.p);
-        return TDGL_OK;
-    };
-    TDGL_TRY(convert(L.A.vals.p, L.A32, L.A.pat.n_slots));
-    TDGL_TRY(convert(L.P.vals.p, L.P32, L.P.pat.n_slots));
-    TDGL_TRY(convert(L.dinv.p, L.dinv32, L.n_pad));
-    TDGL_TRY(convert(ctx->fusedR.data.p, ctx->fusedR32, ctx->fusedR.nnz));
-    // binary16 copies of the three level-0 operator streams
-    // (popt.precond_fp32 >= 2; needs the 16-bit index forms, i.e. RCM-numbered single-GPU operators, and
-    // entries inside binary16's range: |a| < 3e4 -- entries below 6e-5 lose digits, which a
-    // preconditioner does not mind)
-    ctx->level0_f16 = ctx->popt.precond_fp32 >= 2 && ctx->fusedR_off16.n > 0 &&
-                      L.P.pat.use_off16 && L.A.pat.use16 && ctx->level0_absmax < 3.0e4;
-    if (ctx->level0_f16) {
-        auto convert16 = [&](const double *src, DevBuf<half_t> &dst, int64_t n) -> int {
-            HIP_TRY(ctx, dst.alloc(std::max<int64_t>(n, 1)));
-            if (n > 0) hipLaunchKernelGGL(k_to_f16, dim3(grid_for(n)), dim3(BLOCK), 0, ctx->stream, n, src, dst.p);
-            return TDGL_OK;
-        };
-        TDGL_TRY(convert16(L.A.vals.p, L.A16, L.A.pat.n_slots));
-        TDGL_TRY(convert16(L.P.vals.p, L.P16, L.P.pat.n_slots));
-        TDGL_TRY(convert16(ctx->fusedR.data.p, ctx->fusedR16, ctx->fusedR.nnz));
-    }
-    HIP_TRY(ctx, L.x32a.alloc(L.n_pad));
-    HIP_TRY(ctx, L.x32b.alloc(L.n_pad));
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->f32_ready = true;
-    return TDGL_OK;
-}
-
-// z = M^-1 r with the level-0 part in fp32 (degree-1 smoothing, fused restriction); writes the
-// NB partials of r.z to dot_partial and returns z (fp32, level-0 length).
-// In one-process-per-GPU mode `z64` receives z as an fp64 vector (its ghost entries are exchanged
-// as doubles before A z), the ghosts of r are refreshed first and the partial coarse right-hand
-// sides are summed over ranks.
-// `q2`: also write the partials of q2 . z behind them (DOT_BY2; the flexible CG's z_new . q_old).
-static const float *vcycle0_f32(tdgl_ctx *ctx, double *r, double *dot_partial, double *z64 = nullptr,
-                                const double *q2 = nullptr, bool dots_later = false) {
-    AmgLevel &L = *ctx->levels[0], &C = *ctx->levels[1];
-    const SmootherCoef sc = smoother_coef(ctx, L, 1);
-    // rows [r0, r1) of the restriction C.b = F r
-    auto restrict_rows = [&](int64_t r0, int64_t r1) {
-        const int64_t nr = r1 - r0;
-        if (nr <= 0) return;
-        const Csr &F = ctx->fusedR;
-        if (ctx->level0_f16)
-            hipLaunchKernelGGL((k_csr_ax16<16, 4, half_t>), dim3(csr_grid(nr * 16)), dim3(BLOCK), 0, ctx->stream, nr,
-                               (const int32_t *)(F.indptr.p + r0), (const int32_t *)(ctx->fusedR_base.p + r0),
-                               (const uint16_t *)ctx->fusedR_off16.p, (const half_t *)ctx->fusedR16.p, (const double *)r, C.b.p + r0);
-        else if (ctx->fusedR_off16.n > 0)
-            hipLaunchKernelGGL((k_csr_ax16<16, 4, float>), dim3(csr_grid(nr * 16)), dim3(BLOCK), 0, ctx->stream, nr,
-                               (const int32_t *)(F.indptr.p + r0), (const int32_t *)(ctx->fusedR_base.p + r0),
-                               (const uint16_t *)ctx->fusedR_off16.p, (const float *)ctx->fusedR32.p, (const double *)r, C.b.p + r0);
-        else
-            hipLaunchKernelGGL((k_csr_multi<16, C_AX, 4, float>), dim3(csr_grid(nr * 16)), dim3(BLOCK), 0, ctx->stream, nr,
-                               (const int32_t *)(F.indptr.p + r0), (const int32_t *)F.indices.p, (const float *)ctx->fusedR32.p,
-                               (const double *)r, (const double *)nullptr, (const double *)nullptr, 0.0, 0.0, 0.0, (double *)nullptr,
-                               C.b.p + r0);
-    };
-    const int64_t nF = ctx->fusedR.n_rows;
-    if (ctx->deep && ipc_on(ctx) && ctx->overlap && ctx->l1_interior >= 4096 && !ctx->deep_nbrs.empty()) {
-        // the ONE vector exchange of the iteration, hidden: the neighbours' values travel while the level-1 rows whose
-        // restriction reads owned entries only are formed (all on this stream: sending launch, ghost-free rows,
-        // receiving launch, the rest)
-        (void)comm_halo_deep(ctx, r, /*split_phase=*/1);
-        restrict_rows(0, ctx->l1_interior);
-        (void)comm_halo_deep_wait(ctx, r);
-        restrict_rows(ctx->l1_interior, nF);
-    } else {
-        if (ctx->deep) (void)comm_halo_deep(ctx, r);  // the ONE vector exchange of the iteration
-        else if (distributed(ctx)) (void)comm_halo(ctx, r, 1);
-        restrict_rows(0, nF);
-    }
-    // (two distributed levels: b1 is complete on this rank's entries; the sum over ranks happens one level down)
-    if (distributed(ctx) && !ctx->deep) (void)comm_allreduce_via_f32(ctx, C.b.p, C.n);
-    double *xc = nullptr;
-    vcycle_level(ctx, 1, C.b.p, &xc, nullptr, /*f32=*/true);
-    int per_xcd, grid;
-    sell_fixed_grid(L.P.pat.n_slices, &per_xcd, &grid);
-    if (ctx->level0_f16)
-        hipLaunchKernelGGL((k_sell_transfer<T_BASE, half_t, float, uint16_t, float>), dim3(grid), dim3(BLOCK), 0,
-                           ctx->stream, L.P.pat.n_slices, per_xcd, L.P.pat.n_rows, L.P.pat.slice_off.p, L.P.pat.offs16.p,
-                           L.P.pat.slice_base.p, L.P16.p, (const double *)xc, L.dinv32.p, (const double *)r, sc.c2[0],
-                           L.x32a.p);
-    else if (L.P.pat.use_off16)
-        hipLaunchKernelGGL((k_sell_transfer<T_BASE, float, float, uint16_t>), dim3(grid), dim3(BLOCK), 0, ctx->stream,
-                           L.P.pat.n_slices, per_xcd, L.P.pat.n_rows, L.P.pat.slice_off.p, L.P.pat.offs16.p,
-                           L.P.pat.slice_base.p, L.P32.p, (const double *)xc, L.dinv32.p, (const double *)r, sc.c2[0],
-                           L.x32a.p);
-    else
-        hipLaunchKernelGGL((k_sell_transfer<T_BASE, float, float>), dim3(grid), dim3(BLOCK), 0, ctx->stream,
-                           L.P.pat.n_slices, per_xcd, L.P.pat.n_rows, L.P.pat.slice_off.p, L.P.pat.cols.p,
-                           (const int32_t *)nullptr, L.P32.p, (const double *)xc, L.dinv32.p, (const double *)r, sc.c2[0],
-                           L.x32a.p);
-    sell_fixed_grid(L.A.pat.n_slices, &per_xcd, &grid);
-#define TDGL_SM_(DOT, Q, IT, COLS, YT, Y)                                                                        \
-    hipLaunchKernelGGL((k_sell_spmv<SMOOTH, DOT, IT, float, float, YT>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream,    \
-                       L.A.pat.n_slices, per_xcd, 0, L.A.pat.n_rows, L.A.pat.slice_off.p, COLS, L.A32.p,           \
-                       (const float *)L.x32a.p, (const double *)r, (const float *)L.dinv32.p, 0.0, sc.c2[0],       \
-                       (double *)nullptr, Y, dot_partial, Q)
-#define TDGL_SM(IT, COLS, YT, Y) TDGL_SM_(DOT_BY, (const double *)nullptr, IT, COLS, YT, Y)
-#define TDGL_SM16_(DOT, Q, YT, Y)                                                                                   \
-    hipLaunchKernelGGL((k_sell_spmv<SMOOTH, DOT, int16_t, half_t, float, YT, float>), dim3(ctx->npart), dim3(BLOCK), 0,        \
-                       ctx->stream, L.A.pat.n_slices, per_xcd, 0, L.A.pat.n_rows, L.A.pat.slice_off.p,                 \
-                       L.A.pat.cols16.p, L.A16.p, (const float *)L.x32a.p, (const double *)r,                          \
-                       (const float *)L.dinv32.p, 0.0, sc.c2[0], (double *)nullptr, Y, dot_partial, Q)
-#define TDGL_SM16(YT, Y) TDGL_SM16_(DOT_BY, (const double *)nullptr, YT, Y)
-    if (ctx->deep || dots_later) {
-        // z on the owned rows AND the first ghost layer (A's rows), no sums: r.z is formed over the owned rows by
-        // the pass that computes w = A z
-        // (z stays in fp32 like on one GPU: nothing exchanges it any more)
-        if (ctx->level0_f16) TDGL_SM16_(DOT_NONE, (const double *)nullptr, float, L.x32b.p);
-        else if (L.A.pat.use16) TDGL_SM_(DOT_NONE, (const double *)nullptr, int16_t, L.A.pat.cols16.p, float, L.x32b.p);
-        else TDGL_SM_(DOT_NONE, (const double *)nullptr, int32_t, L.A.pat.cols.p, float, L.x32b.p);
-    } else if (q2 && !z64) {  // single GPU, flexible CG: r.z and q.z in one pass
-        if (ctx->level0_f16) TDGL_SM16_(DOT_BY2, q2, float, L.x32b.p);
-        else if (L.A.pat.use16) TDGL_SM_(DOT_BY2, q2, int16_t, L.A.pat.cols16.p, float, L.x32b.p);
-        else TDGL_SM_(DOT_BY2, q2, int32_t, L.A.pat.cols.p, float, L.x32b.p);
-    } else if (ctx->level0_f16) {
-        if (z64) TDGL_SM16(double, z64); else TDGL_SM16(float, L.x32b.p);
-    } else if (z64) {
-        if (L.A.pat.use16) TDGL_SM(int16_t, L.A.pat.cols16.p, double, z64); else TDGL_SM(int32_t, L.A.pat.cols.p, double, z64);
-    } else {
-        if (L.A.pat.use16) TDGL_SM(int16_t, L.A.pat.cols16.p, float, L.x32b.p);
-        else TDGL_SM(int32_t, L.A.pat.cols.p, float, L.x32b.p);
-    }
-#undef TDGL_SM
-#undef TDGL_SM16
-#undef TDGL_SM_
-#undef TDGL_SM16_
-    return L.x32b.p;
-}
-
-static void vcycle(tdgl_ctx *ctx, const double *b0, double **result) {
-    double *z = nullptr;
-    vcycle_level(ctx, 0, b0, &z, nullptr);
-    if (result) *result = z;
-}
-
 // where the factors live, by storage type (fp64: the direct SOLVE; fp32: the preconditioner, DirectFactors::fp32)
 template <class VT> struct SubPools;
 template <> struct SubPools<double> {
@@ -1402,14 +831,14 @@ static int cg_precondition(CgRun &run, int it, double **z, const float **z32) {
             ctx->prof3_pending.emplace_back(fa, fb);
         }
     } else if (run.cg1()) {
-        *z32 = vcycle0_f32(ctx, r, rz_new, nullptr, nullptr, true);  // (z on the owned rows and the first ghost layer, fp32)
+        *z32 = vcycle0_f32(ctx, r, rz_new, Cycle0Out::ghosts_no_sums());
     } else if (run.f32i() && distributed(ctx)) {
         *z = ctx->levels[0]->xb.p;  // fp64 copy of z: its ghosts travel as doubles
-        (void)vcycle0_f32(ctx, r, rz_new, *z);
+        (void)vcycle0_f32(ctx, r, rz_new, Cycle0Out::f64_rz(*z));
     } else if (run.f32i()) {
-        *z32 = vcycle0_f32(ctx, r, rz_new, nullptr, run.flex() ? run.q : (const double *)nullptr);
+        *z32 = vcycle0_f32(ctx, r, rz_new, run.flex() ? Cycle0Out::rz_qz(run.q) : Cycle0Out::rz());
     } else {
-        vcycle_level(ctx, 0, r, z, rz_new, run.coarse32);
+        *z = vcycle_level(ctx, 0, r, rz_new, run.coarse32);
     }
     return TDGL_OK;
 }
@@ -1875,19 +1304,6 @@ extern "C" int tdgl_guess_dots(tdgl_ctx *ctx, int32_t k, int64_t n, const double
     return TDGL_OK;
 }
 
-extern "C" int tdgl_vcycle(tdgl_ctx *ctx, const double *r, double *z) {
-    CTX_GUARD(ctx);
-    if (!r || !z) TDGL_FAIL(ctx, TDGL_ERR_ARG, "null argument");
-    if (ctx->levels.empty()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "no AMG hierarchy");
-    DevBuf<double> in;
-    HIP_TRY(ctx, in.alloc(ctx->n_pad));
-    TDGL_TRY(upload_sites(ctx, r, in));
-    double *res = nullptr;
-    vcycle(ctx, in.p, &res);
-    HIP_TRY(ctx, hipGetLastError());
-    return download_sites(ctx, res, z);
-}
-
 // Per-kernel entry point (tests of the factor sweeps): ONE application of the factor preconditioner, z = M r, on vectors
 // in the caller's site order, on buffers of its own -- the CG's vectors, partials and counters are not touched (the
 // factors' own work vectors are: every application overwrites them).  *rz = r . z as the CG sees it: k_pd_scatter's
@@ -1915,75 +1331,5 @@ extern "C" int tdgl_precond_apply(tdgl_ctx *ctx, const double *r, double *z, dou
     double s = 0.0;
     for (double v : h) s += v;
     *rz = s;
-    return TDGL_OK;
-}
-
-// Per-kernel entry point (tests of the stored-precision cycle): ONE application of the V-cycle the CG applies above the
-// fp64 one -- vcycle0_f32 with the operators in the storage ensure_f32 gives them -- on vectors in the caller's site
-// order.  The residual copy and the dot partials are this call's own: the CG's vectors, partials and counters are not
-// touched (the cycle's work vectors are: every application overwrites them).  z = the stored fp32 z widened; *rz (and
-// *qz with q, the flexible CG's DOT_BY2 form) = the smoothing pass's partials added up in index order.
-extern "C" int tdgl_vcycle_stored(tdgl_ctx *ctx, const double *r, const double *q, double *z, double *rz, double *qz) {
-    CTX_GUARD(ctx);
-    if (!r || !z || !rz || (q && !qz)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_vcycle_stored: null argument");
-    // (a rank of a one-process-per-GPU run: its cycle exchanges ghosts and sums the coarse right-hand sides over ranks)
-    if (ctx->n_own != ctx->n || distributed(ctx) || ctx->deep)
-        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_vcycle_stored: single-GPU contexts only (one process per GPU: the cycle has collectives)");
-    if (ctx->levels.empty()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_vcycle_stored: no AMG hierarchy");
-    if (!precond_f32_on(ctx)) {
-        const char *why = !ctx->popt.precond_fp32        ? "the operators are stored in fp64 (precond_fp32 = 0)"
-                          : ctx->levels.size() < 2       ? "the hierarchy has a single level"
-                          : level_degree(ctx, 0) != 1    ? "the level-0 smoother has a degree other than 1"
-                                                         : "no fused restriction for the level-0 coefficient in use";
-        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_vcycle_stored: the CG applies the fp64 cycle here: %s (tdgl_vcycle)", why);
-    }
-    TDGL_TRY(ensure_f32(ctx));
-    AmgLevel &L = *ctx->levels[0];
-    DevBuf<double> in, qin, part;
-    HIP_TRY(ctx, in.alloc(L.n_pad));
-    HIP_TRY(ctx, part.alloc(3 * NB));
-    TDGL_TRY(upload_sites(ctx, r, in));
-    if (q) {
-        HIP_TRY(ctx, qin.alloc(L.n_pad));
-        TDGL_TRY(upload_sites(ctx, q, qin));
-    }
-    const float *z32 = vcycle0_f32(ctx, in.p, part.p, nullptr, q ? qin.p : (const double *)nullptr);
-    HIP_TRY(ctx, hipGetLastError());
-    std::vector<double> h((size_t)3 * NB);
-    HIP_TRY(ctx, hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<float> zf((size_t)ctx->n);
-    TDGL_TRY(download_sites(ctx, z32, zf.data()));  // (synchronises the stream)
-    for (int64_t i = 0; i < ctx->n; ++i) z[i] = (double)zf[i];
-    double s = 0.0, s2 = 0.0;
-    for (int i = 0; i < ctx->npart; ++i) {
-        s += h[i];
-        s2 += h[(size_t)2 * NB + i];
-    }
-    *rz = s;
-    if (q) *qz = s2;
-    return TDGL_OK;
-}
-
-// Which index form each operator of the stored-precision cycle was built with (read-only; tests assert the path they
-// mean to run).  out[TDGL_INDEX_FORMS_LEN]: see include/tdgl_hip.h.
-extern "C" int tdgl_get_poisson_index_forms(tdgl_ctx *ctx, int32_t *out) {
-    if (!ctx || !out) return TDGL_ERR_ARG;
-    for (int i = 0; i < TDGL_INDEX_FORMS_LEN; ++i) out[i] = -1;
-    const int nl = (int)ctx->levels.size();
-    out[5] = nl;
-    out[8] = ctx->lap_pat.use16 ? 1 : 0;
-    if (nl == 0) return TDGL_OK;
-    const AmgLevel &L = *ctx->levels[0];
-    out[0] = L.A.pat.use16 ? 1 : 0;
-    if (nl > 1) out[1] = L.P.pat.use_off16 ? 1 : 0;
-    if (ctx->fusedR.nnz > 0) out[2] = ctx->fusedR_off16.n > 0 ? 1 : 0;
-    if (ctx->tail_level >= 1 && ctx->tail_mode == 1) out[3] = ctx->tailW_idx16.n > 0 ? 1 : 0;
-    out[4] = (ctx->f32_ready && ctx->level0_f16) ? 1 : 0;
-    out[6] = ctx->tail_level;
-    out[7] = ctx->tail_level >= 1 ? ctx->tail_mode : -1;
-    for (int k = 1; k + 1 < nl && 8 + k < TDGL_INDEX_FORMS_LEN; ++k) {
-        const AmgLevel &M = *ctx->levels[k];
-        if (M.Wup.nnz > 0) out[8 + k] = (M.up_woff.n > 0 ? 1 : 0) | (ctx->coarse32_ready && M.up_w16.n > 0 ? 2 : 0);
-    }
     return TDGL_OK;
 }

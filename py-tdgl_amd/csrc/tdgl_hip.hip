@@ -1,6 +1,6 @@
 // libtdgl_hip: MI355X-native TDGL time-stepping core behind a C ABI (include/tdgl_hip.h).
-// Single translation unit: kernels (kernels.inc), Poisson solver (poisson.inc), the
-// per-step driver (run.inc).
+// Single translation unit: kernels (kernels.inc), the AMG V-cycle (vcycle.inc), Poisson solver
+// (poisson.inc), the per-step driver (run.inc).
 
 #include "tdgl_internal.h"
 
@@ -633,6 +633,7 @@ static inline int64_t now_ns() {
 #include "comm.inc"
 #include "loop.inc"
 #include "guess.inc"
+#include "vcycle.inc"
 #include "poisson.inc"
 #include "dense.inc"
 #include "schur.inc"
@@ -1577,7 +1578,7 @@ extern "C" int tdgl_time_kernel(tdgl_ctx *ctx, int32_t kernel, int32_t reps, dou
             case 2: launch_psi_update(ctx, psi, ctx->mu.p, ctx->lap[ctx->loop.cur].p, 1e-4, tmp_c.p, nullptr); break;
             case 3: launch_edge_currents(ctx, psi, ctx->mu.p, tmp_r.p, tmp_r2.p); break;
             case 4: poisson_spmv_level0(ctx, ctx->mu.p, tmp_r.p); break;
-            case 5: vcycle(ctx, ctx->bvec.p, /*result*/ nullptr); break;
+            case 5: (void)vcycle_level(ctx, 0, ctx->bvec.p, nullptr); break;
             case 6:
                 hipLaunchKernelGGL(k_copy_d2, dim3(grid_for(ctx->n_pad)), dim3(BLOCK), 0, ctx->stream,
                                    ctx->n_pad, psi, tmp_c.p);

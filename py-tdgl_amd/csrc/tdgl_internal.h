@@ -113,6 +113,9 @@ struct Csr {
     DevBuf<float> data32;  // fp32 copy of the values (mixed-precision preconditioner), on demand
 };
 
+// how the stored-precision cycle reads a level-0 operator (A, P, the fused restriction): values and indices
+enum class StoredForm { F32_I32, F32_I16, F16_I16 };
+
 // Level 0 (rows ~ 10^6, 7 entries each) streams through SELL-64, one lane per row.  Coarse
 // levels and the restriction have few, longer rows: one lane per row would be a single long
 // dependent gather chain per wave, so they use CSR with several lanes per row instead.
@@ -652,6 +655,7 @@ struct tdgl_ctx {
     tdgl::DevBuf<float> fusedR32;         // its values in fp32
     tdgl::DevBuf<tdgl::half_t> fusedR16;  // ... in binary16
     bool level0_f16 = false;              // the level-0 V-cycle kernels read the binary16 copies
+    tdgl::StoredForm form_A = tdgl::StoredForm::F32_I32, form_P = form_A, form_R = form_A;  // ... each operator's form (ensure_f32)
     double level0_absmax = 0.0;           // largest |entry| of A0, P0 and the fused restriction (binary16 range check)
     tdgl::DevBuf<uint16_t> fusedR_off16;  // its columns as 16-bit offsets from fusedR_base[row], when they fit
     tdgl::DevBuf<int32_t> fusedR_base;

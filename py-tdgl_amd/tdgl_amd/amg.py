@@ -301,7 +301,7 @@ def build_hierarchy(
 # hierarchy and to cross-check the HIP V-cycle; the product path never calls it.
 def smoother_coefficients(rho, nu=2, smoother="chebyshev", cheb_lo=0.1):
     """(c1[k], c2[k]) of the smoothing recurrence d <- c1 d + c2 D^-1 (b - A x), x <- x + d
-    (same numbers as `smoother_coef` in csrc/poisson.inc)."""
+    (same numbers as `smoother_coef` in csrc/vcycle.inc)."""
     if smoother == "jacobi":
         return [0.0] * nu, [(4.0 / 3.0) / rho] * nu
     hi, lo = rho, cheb_lo * rho

@@ -45,7 +45,7 @@ def allreduce_sum(x):
 
 def vcycle_dist(h, loc0, lp, b_own, nu=2, smoother="chebyshev", cheb_lo=0.1, nu_fine=1):
     """One V-cycle: level 0 distributed (`loc0` from partition.local_hierarchy_level0), levels
-    >= 1 replicated.  Exchanges happen exactly where csrc/poisson.inc places them."""
+    >= 1 replicated.  Exchanges happen exactly where csrc/vcycle.inc places them."""
     A, dinv_loc, P, R = loc0["A"], loc0["dinv"], loc0["P"], loc0["R"]
     n_own = lp.n_own
     dinv = dinv_loc[:n_own]
@@ -122,7 +122,7 @@ def gather_global(lp, local_owned_values, n_global, dtype=np.float64):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# Two distributed AMG levels, one vector exchange per iteration (tdgl_amd.partition.DeepPlan; csrc/poisson.inc with
+# Two distributed AMG levels, one vector exchange per iteration (tdgl_amd.partition.DeepPlan; csrc/vcycle.inc and csrc/poisson.inc with
 # tdgl_set_deep_halo_plan): the same sequence in NumPy.
 def halo_exchange_deep(dp, vec):
     """Refresh ALL ghost entries ``vec[n_own:n_ext]`` (the residual's deep ghost zone) in place."""

@@ -1,4 +1,4 @@
-"""ONE application of the V-cycle in the precisions the CG applies it in (`vcycle0_f32`, csrc/poisson.inc; reached
+"""ONE application of the V-cycle in the precisions the CG applies it in (`vcycle0_f32`, csrc/vcycle.inc; reached
 through `TDGLContext.vcycle_stored`) against the float64 model of what the device stores (tests/vcycle_model.py,
 itself held to the host restatements by tests/test_vcycle_model_host.py).  A CG converges with a preconditioner that
 is wrong in one row, one padded lane or one slice base, so the solves that use this cycle cannot see such a mistake;

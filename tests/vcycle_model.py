@@ -1,5 +1,5 @@
 """Float64 model of ONE application of the V-cycle in the precisions the device stores it in (`vcycle0_f32`,
-csrc/poisson.inc; `TDGLContext.vcycle_stored`), for tests/test_vcycle_model_host.py and tests/test_hip_vcycle_stored.py.
+csrc/vcycle.inc; `TDGLContext.vcycle_stored`), for tests/test_vcycle_model_host.py and tests/test_hip_vcycle_stored.py.
 Host only: NumPy / SciPy and `tdgl_amd.amg`.
 
 The device keeps every VECTOR below level 0 and all its arithmetic in fp64; what is reduced is the storage of the
