@@ -1,5 +1,5 @@
 // Set-up of the direct mu solve on the device (tdgl_poisson_build_dense_inverse).  Included by tdgl_hip.hip
-// after poisson.inc.
+// after poisson.inc (the application of what it sets up: factors.inc).
 //
 // The counterpart of the reference's one-off LU factorisation (tdgl/finite_volume/operators.py:305-308)
 // for meshes small enough for the explicit pseudo-inverse (see tdgl_poisson_set_dense_inverse).  The
@@ -1001,7 +1001,7 @@ static int dense_to_blr(tdgl_ctx *ctx, DirectFactors &f) {
     BlrTop &Z = f.blr;
     Z = BlrTop();
     const int nt = D.tiles;
-    const int64_t n = D.n, ntile = (int64_t)nt * (nt + 1) / 2;
+    const int64_t n = D.n;
     const double tau = env_double("TDGL_PD_BLR_TOL", BLR_TOL);
     // ||G||_2: power iteration on a deterministic start vector of mean zero (G 1 = 0)
     {
@@ -1026,11 +1026,7 @@ static int dense_to_blr(tdgl_ctx *ctx, DirectFactors &f) {
             if (!(nx > 0.0)) break;
             for (auto &v : hx) v /= nx;
             HIP_TRY(ctx, hipMemcpyAsync(xv.p, hx.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL((k_dense_sym_tiles<double>), dim3((unsigned)ntile), dim3(BLOCK), 0, ctx->stream, (int)n, nt,
-                               (const double *)D.G.p, (const double *)xv.p, D.part.p, (const StepCtl *)nullptr);
-            hipLaunchKernelGGL(k_dense_sym_finish, dim3((unsigned)((n + WAVE - 1) / WAVE)), dim3(BLOCK), 0, ctx->stream, (int)n, nt,
-                               (const double *)D.part.p, (const double *)nullptr, (const int32_t *)nullptr, 0, (StepStatus *)nullptr, 0,
-                               yv.p, (const double *)nullptr, (double *)nullptr, (StepCtl *)nullptr, (StepRec *)nullptr);
+            launch_dense_sym(ctx, D, (int)n, (int)((n + WAVE - 1) / WAVE), xv.p, finish_product(yv.p));
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipMemcpyAsync(hx.data(), yv.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1344,7 +1340,7 @@ extern "C" int tdgl_blr_apply(tdgl_ctx *ctx, int64_t n, const double *G, double 
     HIP_TRY(ctx, y.alloc((size_t)(n * n_vec)));
     HIP_TRY(ctx, hipMemcpy(x.p, X, (size_t)(n * n_vec) * sizeof(double), hipMemcpyHostToDevice));
     for (int64_t v = 0; v < n_vec; ++v)
-        blr_launch(ctx, Z, (int)n, nt, nfin, x.p + v * n, part.p, nullptr, nullptr, 0, nullptr, y.p + v * n, nullptr, nullptr, nullptr, nullptr);
+        blr_launch(ctx, Z, (int)n, nt, nfin, x.p + v * n, part.p, finish_product(y.p + v * n));
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(Y, y.p, (size_t)(n * n_vec) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -177,8 +177,10 @@ __global__ __launch_bounds__(BLOCK) void k_ens_finish(int n, int nt, const doubl
                                                       StepRec *__restrict__ rec, const int32_t *__restrict__ limit) {
     const int r = blockIdx.y;
     StepCtl *c = ctl + r;
-    dense_sym_finish_body(blockIdx.x, n, nt, part + (int64_t)r * ldpart, dmax_part + (int64_t)r * nfail, fail_part + (int64_t)r * nfail,
-                          nfail, nullptr, 1, mu + (int64_t)r * n_pad, nullptr, nullptr, c, rec + (int64_t)r * RA_BATCH_MAX);
+    DenseFinish fin = finish_product(mu + (int64_t)r * n_pad);  // (the whole-matrix inverse inside a step: factors.inc)
+    fin.dmax_part = dmax_part + (int64_t)r * nfail, fin.fail_part = fail_part + (int64_t)r * nfail, fin.nfail = nfail, fin.guard = 1;
+    fin.ctl = c, fin.rec = rec + (int64_t)r * RA_BATCH_MAX;
+    dense_sym_finish_body(blockIdx.x, n, nt, part + (int64_t)r * ldpart, fin);
     if (blockIdx.x == 0 && threadIdx.x == 0 && c->live && !c->poisoned && c->n_acc >= limit[r]) c->poisoned = 1;
 }
 

@@ -1,4 +1,4 @@
-// The ensemble's mu solve on the substructured factors (ensemble.inc; the single run's: poisson.inc,
+// The ensemble's mu solve on the substructured factors (ensemble.inc; the single run's: factors.inc,
 // direct_solve_launch_t).  Included from tdgl_hip.hip in front of ensemble.inc.
 //
 // For R right-hand sides b_r (K2's bvec) mu_r = pinv(A) b_r with the single run's factors and gauge, one or two levels
@@ -153,8 +153,7 @@ __global__ __launch_bounds__(BLOCK) void k_ens_sub_top(int n, int nt, const doub
                                                        int nfin, const StepCtl *__restrict__ ctl) {
     const int r = blockIdx.y;
     if (!ctl[r].live) return;
-    dense_sym_finish_body(blockIdx.x, n, nt, part + (int64_t)r * ldpart, nullptr, nullptr, 0, nullptr, 0, xs + (int64_t)r * n, u,
-                          upart + (int64_t)r * nfin, nullptr, nullptr);
+    dense_sym_finish_body(blockIdx.x, n, nt, part + (int64_t)r * ldpart, finish_separator(xs + (int64_t)r * n, u, upart + (int64_t)r * nfin));
 }
 
 // S4: mean[r] = inv_n (sum of the (G_p 1)^T rows of every level + sum of the shares of u . x_S), a workgroup per replica

@@ -2423,11 +2423,55 @@ __host__ __device__ __forceinline__ void step_controller(StepCtl *__restrict__ c
     }
 }
 
-__device__ __forceinline__ void dense_finish_tail(int blk, int n, double v, int anybad, const double *__restrict__ dmax_part,
-                                                  const int32_t *__restrict__ fail_part, int nfail,
-                                                  StepStatus *__restrict__ st, double *__restrict__ y,
-                                                  const double *__restrict__ u, double *__restrict__ upart,
-                                                  StepCtl *__restrict__ ctl, StepRec *__restrict__ rec);
+// What the last launch of a dense product (k_dense_sym_finish, k_blr_finish, the ensemble's k_ens_finish / k_ens_sub_top)
+// does with its 64 sums per workgroup.  Built by finish_product / finish_separator below and, inside a time step, by
+// finish_in_step (factors.inc); the ensemble's kernels fill one per replica.
+struct DenseFinish {
+    const double *__restrict__ dmax_part;   // the step's psi update per workgroup: max d|psi|^2 ...
+    const int32_t *__restrict__ fail_part;  // ... and its failure flags (NULL: none to look at)
+    int nfail;                              // entries of either
+    StepStatus *__restrict__ st;            // classic loop: workgroup 0 publishes the step's status block from them
+    int guard;                              // != 0: a raised flag holds back the write of y
+    double *__restrict__ y;                 // the product
+    const double *__restrict__ u;           // separator solve: the workgroup's share of u . y goes to ...
+    double *__restrict__ upart;             // ... upart[workgroup]
+    StepCtl *__restrict__ ctl;              // run-ahead loop: a dead step does nothing, workgroup 0 runs the controller ...
+    StepRec *__restrict__ rec;              // ... which records the step here
+};
+
+// the bare product (y and nothing else) / the solve of a top separator (x_S and the shares of u . x_S the way up removes
+// the mean with)
+__host__ __device__ inline DenseFinish finish_product(double *y) { DenseFinish f{}; f.y = y; return f; }
+__host__ __device__ inline DenseFinish finish_separator(double *xs, const double *u, double *upart) { DenseFinish f = finish_product(xs); f.u = u, f.upart = upart; return f; }
+
+// What the second launch of a dense solve does with its 64 sums v (lane = row; wave 0 writes them): the held-back write
+// of y, the workgroup's share of u . x_S, and (workgroup 0) the step's status block / the run-ahead controller
+__device__ __forceinline__ void dense_finish_tail(int blk, int n, double v, int anybad, const DenseFinish &fin) {
+    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+    const int i = blk * WAVE + lane;
+    if (w == 0) {
+        if (i < n && !anybad) fin.y[i] = v;
+        if (fin.u) {  // substructured solve: this workgroup's share of u . x_S (k_sub_up removes the mean with it)
+            const double c = wave_sum(i < n ? fin.u[i] * v : 0.0);
+            if (lane == 0) fin.upart[blk] = c;
+        }
+    }
+    if ((fin.st || fin.ctl) && blk == 0) {  // (workgroup-uniform)
+        double m;
+        int f;
+        reduce_psi_status(fin.dmax_part, fin.fail_part, fin.nfail, &m, &f);
+        if (threadIdx.x == 0) {
+            if (fin.st) {
+                fin.st->fail_flag = f ? 1 : 0;
+                fin.st->dmax_bits[0] = (unsigned long long)__double_as_longlong(m);
+            }
+            // run-ahead: the step's bookkeeping (every workgroup of this launch has read ctl->live by now or
+            // reads the value this thread leaves unchanged: only `poisoned` and the counters move)
+            if (fin.ctl) step_controller(fin.ctl, fin.rec, m, f);
+        }
+        if (fin.st && threadIdx.x > 0 && threadIdx.x < XCDS) fin.st->dmax_bits[threadIdx.x] = 0ull;
+    }
+}
 
 // Second half of the symmetric dense solve: y_i = sum over the nt slots of `part`, in slot order; 64 outputs
 // per workgroup, wave w takes the slots w, w + 4, ... (all loads independent), the four waves meet in LDS
@@ -2435,20 +2479,15 @@ __device__ __forceinline__ void dense_finish_tail(int blk, int n, double v, int 
 // loop workgroup 0 also publishes the step's status block (failure flag, max d|psi|^2: what
 // k_publish_status does on the iterative path) -- one launch less per step.
 // (body: workgroup `blk` of the launch; the ensemble's launch, ensemble.inc, runs one per replica)
-__device__ __forceinline__ void dense_sym_finish_body(int blk, int n, int nt, const double *__restrict__ part,
-                                                      const double *__restrict__ dmax_part,
-                                                      const int32_t *__restrict__ fail_part, int nfail,
-                                                      StepStatus *__restrict__ st, int guard, double *__restrict__ y,
-                                                      const double *__restrict__ u, double *__restrict__ upart,
-                                                      StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
+__device__ __forceinline__ void dense_sym_finish_body(int blk, int n, int nt, const double *__restrict__ part, const DenseFinish &fin) {
     __shared__ double sh[BLOCK / WAVE][WAVE];
-    if (ctl && !ctl->live) return;  // run-ahead: a dead step (behind a failed one / the end) does nothing
+    if (fin.ctl && !fin.ctl->live) return;  // run-ahead: a dead step (behind a failed one / the end) does nothing
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
     const int i = blk * WAVE + lane;
     const int64_t ldp = (int64_t)nt * DT;
     int bad = 0;
-    if (guard && fail_part)
-        for (int k = threadIdx.x; k < nfail; k += BLOCK) bad |= fail_part[k];
+    if (fin.guard && fin.fail_part)
+        for (int k = threadIdx.x; k < fin.nfail; k += BLOCK) bad |= fin.fail_part[k];
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     if (i < n) {
         // sixteen slots per batch, all requested before the first is added (unconditional requests on a clamped slot: a
@@ -2465,49 +2504,11 @@ __device__ __forceinline__ void dense_sym_finish_body(int blk, int n, int nt, co
     sh[w][lane] = (s[0] + s[1]) + (s[2] + s[3]);
     const int anybad = __syncthreads_or(bad);
     const double v = (sh[0][lane] + sh[1][lane]) + (sh[2][lane] + sh[3][lane]);
-    dense_finish_tail(blk, n, v, anybad, dmax_part, fail_part, nfail, st, y, u, upart, ctl, rec);
+    dense_finish_tail(blk, n, v, anybad, fin);
 }
 
-// What the second launch of a dense solve does with its 64 sums v (lane = row; wave 0 writes them): the held-back write
-// of y, the workgroup's share of u . x_S, and (workgroup 0) the step's status block / the run-ahead controller
-__device__ __forceinline__ void dense_finish_tail(int blk, int n, double v, int anybad, const double *__restrict__ dmax_part,
-                                                  const int32_t *__restrict__ fail_part, int nfail,
-                                                  StepStatus *__restrict__ st, double *__restrict__ y,
-                                                  const double *__restrict__ u, double *__restrict__ upart,
-                                                  StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
-    const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
-    const int i = blk * WAVE + lane;
-    if (w == 0) {
-        if (i < n && !anybad) y[i] = v;
-        if (u) {  // substructured solve: this workgroup's share of u . x_S (k_sub_up removes the mean with it)
-            const double c = wave_sum(i < n ? u[i] * v : 0.0);
-            if (lane == 0) upart[blk] = c;
-        }
-    }
-    if ((st || ctl) && blk == 0) {  // (workgroup-uniform)
-        double m;
-        int f;
-        reduce_psi_status(dmax_part, fail_part, nfail, &m, &f);
-        if (threadIdx.x == 0) {
-            if (st) {
-                st->fail_flag = f ? 1 : 0;
-                st->dmax_bits[0] = (unsigned long long)__double_as_longlong(m);
-            }
-            // run-ahead: the step's bookkeeping (every workgroup of this launch has read ctl->live by now or
-            // reads the value this thread leaves unchanged: only `poisoned` and the counters move)
-            if (ctl) step_controller(ctl, rec, m, f);
-        }
-        if (st && threadIdx.x > 0 && threadIdx.x < XCDS) st->dmax_bits[threadIdx.x] = 0ull;
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_dense_sym_finish(int n, int nt, const double *__restrict__ part,
-                                                            const double *__restrict__ dmax_part,
-                                                            const int32_t *__restrict__ fail_part, int nfail,
-                                                            StepStatus *__restrict__ st, int guard, double *__restrict__ y,
-                                                            const double *__restrict__ u, double *__restrict__ upart,
-                                                            StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
-    dense_sym_finish_body(blockIdx.x, n, nt, part, dmax_part, fail_part, nfail, st, guard, y, u, upart, ctl, rec);
+__global__ __launch_bounds__(BLOCK) void k_dense_sym_finish(int n, int nt, const double *__restrict__ part, DenseFinish fin) {
+    dense_sym_finish_body(blockIdx.x, n, nt, part, fin);
 }
 
 // The preconditioner's top separator in block low-rank form (dense.inc: dense_to_blr).  The tile pairs (I, J), I > J,
@@ -2591,22 +2592,18 @@ __global__ __launch_bounds__(BLOCK, 4) void k_blr_project(int n, int nt, BlrArgs
 // Launch 2: y of 64 rows (half h of row block K = blk / 2) = its dense slots of `part` + F_K c_K, then everything
 // k_dense_sym_finish does (dense_finish_tail).  Wave w takes the groups w, w + 4, ... (eight requests of a kilobyte in
 // flight per lane), lanes l, l + 16, l + 32, l + 48 are summed by shuffles, the four waves meet in LDS in a fixed order.
-__global__ __launch_bounds__(BLOCK) void k_blr_finish(int n, int nt, BlrArgs a, const double *__restrict__ part,
-                                                      const double *__restrict__ dmax_part, const int32_t *__restrict__ fail_part,
-                                                      int nfail, StepStatus *__restrict__ st, int guard, double *__restrict__ y,
-                                                      const double *__restrict__ u, double *__restrict__ upart,
-                                                      StepCtl *__restrict__ ctl, StepRec *__restrict__ rec) {
+__global__ __launch_bounds__(BLOCK) void k_blr_finish(int n, int nt, BlrArgs a, const double *__restrict__ part, DenseFinish fin) {
     __shared__ double shl[BLOCK / WAVE][WAVE];
     __shared__ double shd[BLOCK / WAVE][WAVE];
-    if (ctl && !ctl->live) return;  // run-ahead: a dead step does nothing
+    if (fin.ctl && !fin.ctl->live) return;  // run-ahead: a dead step does nothing
     const int blk = blockIdx.x, K = blk >> 1, h = blk & 1;
     const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
     const int rr = 4 * (lane & 15), cl = lane >> 4;
     const int i = blk * WAVE + lane;
     const int64_t ldp = (int64_t)nt * DT;
     int bad = 0;
-    if (guard && fail_part)
-        for (int k = threadIdx.x; k < nfail; k += BLOCK) bad |= fail_part[k];
+    if (fin.guard && fin.fail_part)
+        for (int k = threadIdx.x; k < fin.nfail; k += BLOCK) bad |= fin.fail_part[k];
     const int64_t cb = a.colbase[K];
     const int R = (int)(a.colbase[K + 1] - cb), ng = R / 4;
     const float *__restrict__ Fh = a.F + cb * DT + (int64_t)h * R * WAVE + rr;
@@ -2646,7 +2643,7 @@ __global__ __launch_bounds__(BLOCK) void k_blr_finish(int n, int nt, BlrArgs a, 
     const int anybad = __syncthreads_or(bad);
     const double v = ((shd[0][lane] + shl[0][lane]) + (shd[1][lane] + shl[1][lane])) +
                      ((shd[2][lane] + shl[2][lane]) + (shd[3][lane] + shl[3][lane]));
-    dense_finish_tail(blk, n, v, anybad, dmax_part, fail_part, nfail, st, y, u, upart, ctl, rec);
+    dense_finish_tail(blk, n, v, anybad, fin);
 }
 
 // ------------------------------------------------------------------ substructured direct solve
@@ -2796,13 +2793,15 @@ __global__ __launch_bounds__(BLOCK) void k_sub_down(int64_t nI, int64_t n_rows, 
 // x_S per row of E_p -- 8 bytes out of a 128-byte line, 10^7 times per solve at 250k sites -- ran into the L2's request
 // rate, 41 us for 77 MB; rows of 66 entries read by 16 lanes each, 528-byte rows against 128-byte lines: 33 us for 88 MB.)
 // The mean, SubMean: either read from `in` (one number, left there by an earlier launch), or formed here as
-// scale_own * (sum a + sum b + sum c) -- every workgroup adds the few hundred numbers itself, in a fixed order (one
-// level: a = the (G_p 1)^T b_p rows of the way down, b = the shares of u . x_S).  Two levels: the second level's way
-// up runs without a gauge (scale_own = 0) and its workgroup 0 leaves scale_out * (the sum over BOTH levels' shares)
-// in `out` for the first level's way up: ~2,000 parts there, too many for every workgroup to add up again.
+// scale_own * (the sum of the terms, one after the other) -- every workgroup adds the few hundred numbers itself, in a
+// fixed order (the terms: the first level's (G_p 1)^T b_p rows of the way down, the shares of u . x_S, then the
+// (G_p 1)^T b_p rows of every further level; unused terms have n = 0).  Several levels: the inner levels' ways up run
+// without a gauge (scale_own = 0) and workgroup 0 of the innermost leaves scale_out * (the sum over ALL levels' shares)
+// in `out` for the first level's way up: ~2,000 parts there, too many for every workgroup to add up again.  (factors.inc: mean_*)
+constexpr int SUB_MEAN_TERMS = 4;
+static_assert(SUB_MEAN_TERMS == SUB_LEVELS_MAX + 1, "a term per level and one for the shares of u . x_S");
 struct SubMean {
-    const double *a, *b, *c, *d;
-    int na, nb, nc, nd;
+    struct Term { const double *p; int n; } term[SUB_MEAN_TERMS];
     double scale_own, scale_out;
     double *out;
     const double *in;
@@ -2940,10 +2939,9 @@ __global__ __launch_bounds__(BLOCK) void k_sub_up(int64_t nI, int64_t nS, int nb
     const bool leader = m.out && blockIdx.x == 0;
     if (!m.in && (m.scale_own != 0.0 || leader)) {  // (workgroup-uniform)
         double v = 0.0;
-        for (int i = threadIdx.x; i < m.na; i += BLOCK) v += m.a[i];
-        for (int i = threadIdx.x; i < m.nb; i += BLOCK) v += m.b[i];
-        for (int i = threadIdx.x; i < m.nc; i += BLOCK) v += m.c[i];
-        for (int i = threadIdx.x; i < m.nd; i += BLOCK) v += m.d[i];
+#pragma unroll
+        for (int t = 0; t < SUB_MEAN_TERMS; ++t)
+            for (int i = threadIdx.x; i < m.term[t].n; i += BLOCK) v += m.term[t].p[i];
         const double tot = block_sum(v);
         if (threadIdx.x == 0) {
             sh_mean = tot * m.scale_own;
@@ -3157,7 +3155,7 @@ __global__ __launch_bounds__(BLOCK) void k_sub_repack(const SubRepack *__restric
 }
 
 // ------------------------------------------------------------------ the substructure factors as the CG's preconditioner
-// (tdgl_poisson_set_substructure_precond; poisson.inc: precond_direct_apply).  The context keeps its reverse
+// (tdgl_poisson_set_substructure_precond; factors.inc: precond_direct_apply).  The context keeps its reverse
 // Cuthill-McKee site order -- the order the stencil kernels and the AMG hierarchy are fastest in --, the dissection's
 // order exists inside the solve only: `map[i]` = the context's index of the site at dissection position i.
 __global__ __launch_bounds__(BLOCK) void k_pd_gather(int64_t n, const int32_t *__restrict__ map, const double *__restrict__ r,

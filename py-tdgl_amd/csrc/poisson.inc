@@ -1,6 +1,6 @@
 // mu Poisson solve: conjugate gradients preconditioned by one smoothed-aggregation AMG
-// V-cycle (vcycle.inc), all level operators resident in HBM.  Included by tdgl_hip.hip.  Here: the options and stats,
-// the hierarchy setters, the direct solves, the guard and the CG.
+// V-cycle (vcycle.inc), all level operators resident in HBM.  Included by tdgl_hip.hip.  Here: the options and stats, the
+// hierarchy setters, sync_status, the direct solve's driver (its launches and guard: factors.inc) and the CG.
 //
 // Replaces mu = mu_laplacian_lu(rhs) (tdgl/solver/solver.py:516; SuperLU factorisation at
 // tdgl/finite_volume/operators.py:305-308).  The reference matrix L_mu is singular (pure
@@ -66,8 +66,6 @@ extern "C" int tdgl_get_guess_gram(tdgl_ctx *ctx, int32_t *k, double *G_rowmajor
         for (int j = 0; j < g.count; ++j) G_rowmajor[i * g.count + j] = g.G[i][j][0] + g.G[i][j][1];
     return TDGL_OK;
 }
-
-static int precond_schur_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part);  // schur.inc
 
 static int csr_to_sell(tdgl_ctx *ctx, int64_t n_rows, const int32_t *indptr, const int32_t *indices,
                        const double *data, SellF64 &M, bool want16 = false, bool want_off16 = false) {
@@ -453,236 +451,6 @@ extern "C" int tdgl_poisson_set_collapsed_tail(tdgl_ctx *ctx, const tdgl_collaps
     ctx->tail_smoother = t->smoother;
     ctx->tail_cheb_lo = t->cheb_lo;
     ctx->tail_level = t->level;
-    return TDGL_OK;
-}
-
-// where the factors live, by storage type (fp64: the direct SOLVE; fp32: the preconditioner, DirectFactors::fp32)
-template <class VT> struct SubPools;
-template <> struct SubPools<double> {
-    static const double *level(const SubLevel &L) { return L.vals.p; }
-    static const double *dense(const DenseTiles &D) { return D.G.p; }
-};
-template <> struct SubPools<float> {
-    static const float *level(const SubLevel &L) { return L.vals32.p; }
-    static const float *dense(const DenseTiles &D) { return D.G32.p; }
-};
-
-// the way up of one level: its separator solution L.xs and the way down's L.w -> out
-template <class VT>
-static void launch_sub_up(tdgl_ctx *ctx, const SubLevel &L, double *out, const SubMean &m, const int32_t *fail, const StepCtl *ctl) {
-    const int64_t nI = L.nI, nS = L.nS;
-    const int nblk_int = nI > 0 ? (int)L.up_chunks.n : 0, nblk_sep = grid_for(nS);
-    const int32_t *sep_idx = L.sep_idx.p;
-    const VT *vals = SubPools<VT>::level(L);
-    const double *w = L.w.p, *xs = L.xs.p;
-    // (R: 64-row chunks per workgroup -- 1, or a whole part of up to 256 rows on the levels stored as symmetric tiles)
-#define TDGL_LAUNCH_UP(RR)                                                                                                       \
-    hipLaunchKernelGGL((k_sub_up<VT, RR>), dim3(nblk_int + nblk_sep), dim3(BLOCK), 0, ctx->stream, nI, nS, nblk_int,            \
-                       (const SubUpChunk *)L.up_chunks.p, sep_idx, vals, w, xs, m, fail, ctx->psi_blocks, out, ctl)
-    if (L.up_R >= 4) TDGL_LAUNCH_UP(4);
-    else if (L.up_R == 3) TDGL_LAUNCH_UP(3);
-    else if (L.up_R == 2) TDGL_LAUNCH_UP(2);
-    else TDGL_LAUNCH_UP(1);
-#undef TDGL_LAUNCH_UP
-}
-
-template <class VT> static size_t sym_lds_bytes(int np_lds) {  // k_sub_down_sym: b_p, eight accumulators, eight tiles
-    return (size_t)(1 + 2 * (BLOCK / WAVE)) * np_lds * sizeof(double) + (size_t)(2 * (BLOCK / WAVE)) * ST * STP * sizeof(VT);
-}
-
-// (tiles requested one pair ahead: two and three pairs ahead measured the same application time at 1M sites,
-// profiles/EXPERIMENTS.md round 6 -- the kernel is not waiting for its loads)
-template <class VT, class... Args> static void launch_sub_down_sym(tdgl_ctx *ctx, unsigned grid, size_t lds, Args... args) {
-    hipLaunchKernelGGL((k_sub_down_sym<VT, 1>), dim3(grid), dim3(BLOCK), lds, ctx->stream, args...);
-}
-
-// the way down of one level: b (the level's vector) -> L.w.  `lanes`: the preconditioner's lane-per-row work lists;
-// `first`: the first level (its coupling product takes 8 lanes per row, the inner levels' 16)
-template <class VT>
-static void launch_sub_down(tdgl_ctx *ctx, const SubLevel &L, bool first, bool lanes, const double *b, const StepCtl *ctl) {
-    const int64_t nI = L.nI, nS = L.nS, rows = nI + nS + L.parts;
-    const int nblk_dint = nI > 0 ? (int)L.down_chunks.n : 0;
-    const int nblk_drest = (int)((rows - nI + BLOCK / WAVE - 1) / (BLOCK / WAVE));
-    const SubDownChunk *chunks = L.down_chunks.p;
-    const SubDownRow *drows = L.down_rows.p;
-    const int32_t *seg_ptr = L.seg_ptr.p, *seg_x = L.seg_x.p, *seg_len = L.seg_len.p;
-    const int64_t *seg_val = L.seg_val.p;
-    const VT *vals = SubPools<VT>::level(L);
-    if (lanes || L.sym_lds > 0) {  // (tiles: also a level of the fp64 direct solve, tdgl_poisson_set_substructure_layout)
-        const int64_t n_id = L.ident ? nS : 0;
-        const int nblk_id = grid_for(n_id) * (n_id > 0), nblk_w = (int)((rows - nI - n_id + BLOCK / WAVE - 1) / (BLOCK / WAVE));
-        if (L.sym_lds > 0)
-            launch_sub_down_sym<VT>(ctx, (unsigned)(nblk_dint + nblk_id + nblk_w), sym_lds_bytes<VT>(L.sym_lds), nI, n_id, rows, nblk_dint,
-                                    nblk_id, L.sym_lds, chunks, seg_ptr, seg_val, seg_x, seg_len, vals, b, L.w.p, ctl);
-        else
-            hipLaunchKernelGGL((k_sub_down_lanes<VT>), dim3((unsigned)(nblk_dint + nblk_id + nblk_w)), dim3(BLOCK), 0, ctx->stream, nI, n_id, rows,
-                               nblk_dint, nblk_id, chunks, drows, seg_ptr, seg_val, seg_x, seg_len, vals, b, L.w.p, ctl);
-    } else
-        hipLaunchKernelGGL((k_sub_down<VT>), dim3((unsigned)(nblk_dint + nblk_drest)), dim3(BLOCK), 0, ctx->stream, nI, rows, nblk_dint, chunks,
-                           drows, seg_ptr, seg_val, seg_x, seg_len, vals, b, L.w.p, ctl);
-    // (optional: the separator rows above were b_S alone; r_S = b_S - A_SI y_I with the sparse coupling block)
-    if (L.coupling.nnz > 0) {
-        if (first) launch_csr<8, C_RESID, 4>(ctx, L.coupling, L.w.p, L.w.p + nI, nullptr, 0.0, 0.0, nullptr, L.w.p + nI);
-        else launch_csr<16, C_RESID, 4>(ctx, L.coupling, L.w.p, L.w.p + nI, nullptr, 0.0, 0.0, nullptr, L.w.p + nI);
-    }
-}
-
-// The two launches of the top separator in block low-rank form (dense.inc: dense_to_blr), y = G b on n rows in nt tiles:
-// k_blr_project (the dense tiles into `part`, every column's projection into its twin's slot of Z.coef), then
-// k_blr_finish on nfin workgroups of 64 rows with everything k_dense_sym_finish is handed.  The preconditioner's
-// application and tdgl_blr_apply (the kernels alone, for the tests) both come through here.
-static void blr_launch(tdgl_ctx *ctx, const BlrTop &Z, int n, int nt, int nfin, const double *b, double *part, const double *dmax_part,
-                       const int32_t *fail_part, int nfail, StepStatus *st, double *y, const double *u, double *upart, StepCtl *ctl,
-                       StepRec *rec) {
-    const BlrArgs a{Z.ndense, Z.nitems, Z.dense_ij.p, Z.Gd.p, Z.F.p, Z.colbase.p, Z.twin.p,
-                    reinterpret_cast<const BlrItem *>(Z.items.p), Z.coef.p, Z.dslot_ptr.p, Z.dslot.p};
-    hipLaunchKernelGGL(k_blr_project, dim3((unsigned)(Z.ndense + (Z.nitems + BLOCK / WAVE - 1) / (BLOCK / WAVE))), dim3(BLOCK), 0,
-                       ctx->stream, n, nt, a, b, part, (const StepCtl *)ctl);
-    hipLaunchKernelGGL(k_blr_finish, dim3(nfin), dim3(BLOCK), 0, ctx->stream, n, nt, a, (const double *)part, dmax_part, fail_part, nfail, st,
-                       0, y, u, upart, ctl, rec);
-}
-
-// The launches of a direct mu solve, x = pinv(A) b (dense inverse or substructured; see the header).
-// in_step: inside the time loop -- the kernels that write x hold back when this step's psi update failed and
-// the status block is published by k_dense_sym_finish (returns true then).  ctl / rec: the run-ahead loop's
-// device-resident controller and the record of this step (run.inc), else NULL.
-template <class VT>
-static bool direct_solve_launch_t(tdgl_ctx *ctx, const double *b, double *x, bool in_step, StepCtl *ctl, StepRec *rec) {
-    const DirectFactors &f = *ctx->direct;
-    const double inv_n = 1.0 / (double)ctx->n_global;
-    const int32_t *fail = in_step ? (const int32_t *)ctx->psi_fail_part.p : (const int32_t *)nullptr;
-    StepStatus *st = (in_step && !ctl) ? ctx->status_dev : (StepStatus *)nullptr;
-    const int nt = f.dense.tiles;
-    if (f.levels == 0) {  // the dense inverse of the whole matrix
-        hipLaunchKernelGGL((k_dense_sym_tiles<double>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)ctx->n, nt,
-                           (const double *)f.dense.G.p, b, f.dense.part.p, (const StepCtl *)ctl);
-        // (in the time loop the same launch publishes the step's status block)
-        hipLaunchKernelGGL(k_dense_sym_finish, dim3((int)((ctx->n + WAVE - 1) / WAVE)), dim3(BLOCK), 0, ctx->stream, (int)ctx->n,
-                           nt, (const double *)f.dense.part.p, (const double *)ctx->psi_dmax_part.p, fail, ctx->psi_blocks, st, 1,
-                           x, (const double *)nullptr, (double *)nullptr, ctl, rec);
-        return in_step;
-    }
-    // substructured: the ways down level after level (a level works on the previous level's separator vector), the last
-    // level's separator by the dense pair (which also publishes the step's status), the ways up innermost first.  With
-    // one level its way up removes the mean; with more the inner ones go without a gauge, and the first of them leaves
-    // the mean (all levels' shares of sum x) for the first level's way up.
-    const bool lanes = f.stage == DirectFactors::PRECOND;
-    const int K = f.levels;
-    const double *vec = b;
-    for (int k = 0; k < K; ++k) {
-        launch_sub_down<VT>(ctx, f.lv[k], k == 0, lanes, vec, ctl);
-        vec = f.lv[k].w.p + f.lv[k].nI;
-    }
-    const SubLevel &L0 = f.lv[0], &T = f.lv[K - 1];
-    if (f.blr.ndense > 0) {  // the top separator in block low-rank form (preconditioner, dense.inc: dense_to_blr)
-        blr_launch(ctx, f.blr, (int)T.nS, nt, f.nfin, vec, f.dense.part.p, (const double *)ctx->psi_dmax_part.p,
-                   (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, T.xs.p, (const double *)T.u.p, f.upart.p, ctl, rec);
-    } else {
-        hipLaunchKernelGGL((k_dense_sym_tiles<VT>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt,
-                           SubPools<VT>::dense(f.dense), vec, f.dense.part.p, (const StepCtl *)ctl);
-        hipLaunchKernelGGL(k_dense_sym_finish, dim3(f.nfin), dim3(BLOCK), 0, ctx->stream, (int)T.nS, nt, (const double *)f.dense.part.p,
-                           (const double *)ctx->psi_dmax_part.p, (const int32_t *)ctx->psi_fail_part.p, ctx->psi_blocks, st, 0, T.xs.p,
-                           (const double *)T.u.p, f.upart.p, ctl, rec);
-    }
-    if (K == 1) {
-        launch_sub_up<VT>(ctx, L0, x, SubMean{L0.w.p + L0.nI + L0.nS, f.upart.p, nullptr, nullptr, L0.parts, f.nfin, 0, 0, inv_n, 0.0, nullptr, nullptr},
-                          fail, ctl);
-        return in_step;
-    }
-    for (int k = K - 1; k >= 1; --k) {
-        SubMean m{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0.0, 0.0, nullptr, nullptr};
-        if (k == K - 1) {  // (the (G v)^T rows of a level sit behind its vector: w + nI + nS)
-            const SubLevel &L1 = f.lv[1], &L2 = f.lv[2];
-            m = SubMean{L0.w.p + L0.nI + L0.nS, f.upart.p, L1.w.p + L1.nI + L1.nS, K > 2 ? L2.w.p + L2.nI + L2.nS : (const double *)nullptr,
-                        L0.parts, f.nfin, L1.parts, K > 2 ? L2.parts : 0, 0.0, inv_n, f.mean.p, nullptr};
-        }
-        launch_sub_up<VT>(ctx, f.lv[k], f.lv[k - 1].xs.p, m, fail, ctl);
-    }
-    launch_sub_up<VT>(ctx, L0, x, SubMean{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0.0, 0.0, nullptr, f.mean.p}, fail, ctl);
-    return in_step;
-}
-
-static bool direct_solve_launch(tdgl_ctx *ctx, const double *b, double *x, bool in_step, StepCtl *ctl, StepRec *rec) {
-    return ctx->direct->fp32 ? direct_solve_launch_t<float>(ctx, b, x, in_step, ctl, rec) : direct_solve_launch_t<double>(ctx, b, x, in_step, ctl, rec);
-}
-
-// ---- the factors as preconditioner (tdgl_poisson_set_substructure_precond) ---------------------------------------
-// z = M r with M ~ pinv(A): the residual gathered into the dissection's order, the launch sequence of the direct solve
-// on the fp32-stored factors, the result scattered back together with the partials of r . z.
-static void precond_direct_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part) {
-    const int64_t n = ctx->n;
-    const DirectFactors &f = *ctx->direct;
-    hipLaunchKernelGGL(k_pd_gather, dim3(vec_grid(n)), dim3(BLOCK), 0, ctx->stream, n, (const int32_t *)f.map.p, r, f.bp.p);
-    (void)direct_solve_launch(ctx, f.bp.p, f.xp.p, false, nullptr, nullptr);
-    hipLaunchKernelGGL(k_pd_scatter, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, n, (const int32_t *)f.map.p, (const double *)f.xp.p, r, z,
-                       rz_part);
-}
-
-// ... on one GPU the factors of the whole matrix, in one-process-per-GPU mode the rank-level dissection (schur.inc)
-static int precond_factors_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part) {
-    if (ctx->direct->n_local > 0) return precond_schur_apply(ctx, r, z, rz_part);
-    precond_direct_apply(ctx, r, z, rz_part);
-    return TDGL_OK;
-}
-
-static inline bool precond_factors_available(const tdgl_ctx *ctx) {
-    return ctx->direct && ctx->direct->stage == DirectFactors::PRECOND;
-}
-
-// ---- in-loop guard of the direct mu solves ----------------------------------------------------------
-// An explicit inverse is checked once at set-up, on one random right-hand side.  In the time loop the
-// residual of an accepted step's solve, ||b - A mu|| / ||b|| with the resident level-0 matrix (SELL), is
-// measured once per run-ahead batch (classic loop: every DIRECT_GUARD_EVERY steps) -- two small launches
-// next to 64 attempts.  Above direct_guard_limit (1e-9; the factors deliver 1e-14) the factors are
-// released and AMG-PCG takes over from the next step on; tdgl_get_direct_stats reports it.
-constexpr int DIRECT_GUARD_EVERY = 64;
-static void direct_guard_launch(tdgl_ctx *ctx) {
-    AmgLevel &L0 = *ctx->levels[0];
-    hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, ctx->n_own, (const double *)ctx->bvec.p,
-                       (const double *)ctx->bvec.p, ctx->part_pq.p);
-    launch_sell<RESID, DOT_YY>(ctx, L0.A, ctx->mu.p, ctx->bvec.p, nullptr, 0.0, 0.0, nullptr, ctx->pcg_r.p, ctx->part_pair[0].p + NB);
-    hipLaunchKernelGGL(k_store_sum, dim3(1), dim3(BLOCK), 0, ctx->stream, (const double *)ctx->part_pq.p, ctx->scal.p, (int)S_BB, 0.0);
-    hipLaunchKernelGGL(k_store_sum, dim3(1), dim3(BLOCK), 0, ctx->stream, (const double *)(ctx->part_pair[0].p + NB), ctx->scal.p, (int)S_RR, 0.0);
-}
-static inline void direct_guard_fetch(tdgl_ctx *ctx) {  // (queued behind everything that writes the status block)
-    (void)hipMemcpyAsync(ctx->h_status->scal, ctx->scal.p, S_COUNT * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-}
-// after the synchronisation; `valid`: mu and b belong to the same, accepted, step
-static void direct_guard_read(tdgl_ctx *ctx, bool valid) {
-    if (!valid) return;
-    const double bb = ctx->h_status->scal[S_BB], rr = ctx->h_status->scal[S_RR];
-    if (!(bb > 0.0)) return;
-    const double relres = std::isfinite(rr) ? std::sqrt(rr / bb) : INFINITY;
-    ctx->direct_checks += 1;
-    if (!(relres <= ctx->direct_relres_max)) ctx->direct_relres_max = relres;
-    if (!(relres <= ctx->direct_guard_limit)) {
-        ctx->direct.reset();  // run_ahead_ok / dense_on are false from now on: AMG-PCG
-        ctx->direct_fell_back = 1;
-    }
-}
-
-extern "C" int tdgl_get_direct_stats(tdgl_ctx *ctx, double *relres_max, int64_t *checks, int32_t *fell_back) {
-    if (!ctx) return TDGL_ERR_ARG;
-    if (relres_max) *relres_max = ctx->direct_relres_max;
-    if (checks) *checks = ctx->direct_checks;
-    if (fell_back) *fell_back = ctx->direct_fell_back;
-    return TDGL_OK;
-}
-
-extern "C" int tdgl_direct_switching(tdgl_ctx *ctx, int32_t on, int64_t *switches, int32_t *paused) {
-    if (!ctx) return TDGL_ERR_ARG;
-    if (on >= 0) {
-        ctx->direct_switch_on = on != 0;
-        direct_policy_reset(ctx);
-    }
-    if (switches) *switches = ctx->direct_switches;
-    if (paused) *paused = ctx->direct_paused ? 1 : 0;
-    return TDGL_OK;
-}
-
-extern "C" int tdgl_set_direct_guard(tdgl_ctx *ctx, double limit) {
-    if (!ctx || !(limit > 0.0)) return TDGL_ERR_ARG;
-    ctx->direct_guard_limit = limit;
     return TDGL_OK;
 }
 

@@ -6,9 +6,9 @@
 // block A_II (the machinery of dense.inc on a vector of n_local entries; positive definite, so the top separator
 // carries a plain inverse and no gauge), its coupling blocks A_GI / A_IG, and -- like every other rank -- the pseudo-
 // inverse of the interface complement S = A_GG - sum_r A_GI_r A_II_r^-1 A_I_rG as symmetric fp32 tiles.  One application
-//     y_I = A_II^-1 r_I                                  local: gather, the factors' launch sequence
+//     y_I = A_II^-1 r_I                                  local: gather, the factors' launch sequence (factors.inc)
 //     t   = r_G - sum_r A_GI_r y_I                       ONE all-reduce of |Gamma| doubles
-//     x_G = S^+ t                                        replicated: k_dense_sym_tiles + _finish
+//     x_G = S^+ t                                        replicated: the dense pair (factors.inc: launch_dense_sym)
 //     x_I = y_I - A_II^-1 (A_IG x_G)                     local: a second pass of the factors
 // is a direct solve with the exact factors; with fp32 storage it contracts the residual by ~1e-6, and the CG around it
 // (pcg_solve: A p with the fp64 matrix, one exchange of z's ghosts, one sum of 3 x 1024 partials) needs one iteration
@@ -160,21 +160,12 @@ extern "C" int tdgl_poisson_schur_complement(tdgl_ctx *ctx, double *out) {
 static int precond_schur_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part) {
     const DirectFactors &f = *ctx->direct;
     const int64_t nI = f.n_local, ng = f.ng;
-    hipLaunchKernelGGL(k_pd_gather, dim3(vec_grid(nI)), dim3(BLOCK), 0, ctx->stream, nI, (const int32_t *)f.map.p, r, f.bp.p);
+    launch_pd_gather(ctx, nI, f.map.p, r, f.bp.p);
     (void)direct_solve_launch(ctx, f.bp.p, f.y.p, false, nullptr, nullptr);
     hipLaunchKernelGGL(k_schur_owned_rhs, dim3(grid_for(ng)), dim3(BLOCK), 0, ctx->stream, ng, (const int32_t *)f.owner_local.p, r, f.rg.p);
     launch_csr<8, C_RESID, 4>(ctx, f.GI, f.y.p, f.rg.p, nullptr, 0.0, 0.0, nullptr, f.t.p);
     TDGL_TRY(comm_allreduce(ctx, f.t.p, ng, 0));  // THE collective of an application
-    const int nt = f.S.tiles;
-    if (f.S.G32.n > 0)
-        hipLaunchKernelGGL((k_dense_sym_tiles<float>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)ng, nt, (const float *)f.S.G32.p,
-                           (const double *)f.t.p, f.S.part.p, (const StepCtl *)nullptr);
-    else
-        hipLaunchKernelGGL((k_dense_sym_tiles<double>), dim3(nt * (nt + 1) / 2), dim3(BLOCK), 0, ctx->stream, (int)ng, nt, (const double *)f.S.G.p,
-                           (const double *)f.t.p, f.S.part.p, (const StepCtl *)nullptr);
-    hipLaunchKernelGGL(k_dense_sym_finish, dim3((int)((ng + WAVE - 1) / WAVE)), dim3(BLOCK), 0, ctx->stream, (int)ng, nt,
-                       (const double *)f.S.part.p, (const double *)nullptr, (const int32_t *)nullptr, 0, (StepStatus *)nullptr, 0,
-                       f.xg.p, (const double *)nullptr, (double *)nullptr, (StepCtl *)nullptr, (StepRec *)nullptr);
+    launch_dense_sym(ctx, f.S, (int)ng, (int)((ng + WAVE - 1) / WAVE), f.t.p, finish_product(f.xg.p));
     launch_csr<8, C_AX, 4>(ctx, f.IG, f.xg.p, nullptr, nullptr, 0.0, 0.0, nullptr, f.c.p);
     (void)direct_solve_launch(ctx, f.c.p, f.v.p, false, nullptr, nullptr);
     hipLaunchKernelGGL(k_schur_scatter, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, nI, (const int32_t *)f.map.p, (const double *)f.y.p,

@@ -1,6 +1,6 @@
 // libtdgl_hip: MI355X-native TDGL time-stepping core behind a C ABI (include/tdgl_hip.h).
-// Single translation unit: kernels (kernels.inc), the AMG V-cycle (vcycle.inc), Poisson solver
-// (poisson.inc), the per-step driver (run.inc).
+// Single translation unit: kernels (kernels.inc), the AMG V-cycle (vcycle.inc), the mu factors' application (factors.inc),
+// Poisson solver (poisson.inc), the per-step driver (run.inc).
 
 #include "tdgl_internal.h"
 
@@ -634,6 +634,7 @@ static inline int64_t now_ns() {
 #include "loop.inc"
 #include "guess.inc"
 #include "vcycle.inc"
+#include "factors.inc"
 #include "poisson.inc"
 #include "dense.inc"
 #include "schur.inc"

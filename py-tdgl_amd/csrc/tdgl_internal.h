@@ -30,6 +30,7 @@ constexpr int BLOCK = 256;      // 4 waves per workgroup
 constexpr int XCDS = 8;         // MI355X accelerator complex dies (one L2 each)
 constexpr int REDUCE_BLOCK = 1024;
 constexpr int PROBE_RING_STEPS = 1024;  // steps of probe read-outs kept on the device between flushes
+constexpr int SUB_LEVELS_MAX = 3;       // levels of the nested dissection (DirectFactors::lv)
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -517,7 +518,7 @@ struct DirectFactors {
     DenseTiles dense;                      // pinv of the whole matrix (levels == 0), or of the last level's separator
     int64_t ld = 0;                        // > 0: `dense` is the inverse of the whole matrix (tdgl_poisson_set_dense_inverse)
     // nested dissection
-    SubLevel lv[3];
+    SubLevel lv[SUB_LEVELS_MAX];
     int levels = 0;                        // levels described so far
     int nfin = 0;                          // workgroups of the separator's k_dense_sym_finish
     DevBuf<double> upart;                  // their partials of u . x_S
@@ -727,7 +728,7 @@ struct tdgl_ctx {
     double prev_dt = 0.0, prev_dt2 = 0.0;    // dt of the steps that produced mu / mu_prev (0: no history)
     tdgl_poisson_options popt{1e-10, 500, 2, 0, 1, 1, 0.1, 3, 1, 2, 0, 0};
     tdgl::GuessBasis guess;               // projection guess (popt.extrapolate == 3)
-    // in-loop guard of the direct mu solves (run.inc: direct_guard_*): ||b - A mu|| / ||b|| of an accepted step,
+    // in-loop guard of the direct mu solves (factors.inc: direct_guard_*): ||b - A mu|| / ||b|| of an accepted step,
     // measured with the resident level-0 matrix once per run-ahead batch / every DIRECT_GUARD_EVERY classic steps
     double direct_relres_max = 0.0;
     int64_t direct_checks = 0;

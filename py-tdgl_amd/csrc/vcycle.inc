@@ -1,6 +1,6 @@
 // The AMG V-cycle, preconditioner of the mu CG (poisson.inc): the launchers of its kernels, the cycle in fp64
 // (vcycle_level) and in the stored precisions (vcycle0_f32 over ensure_f32's copies), and the entry points that apply one
-// cycle.  Included by tdgl_hip.hip in front of poisson.inc; the substructured solve there and schur.inc share launch_csr.
+// cycle.  Included by tdgl_hip.hip in front of factors.inc and poisson.inc; factors.inc and schur.inc share launch_csr.
 
 // the collapsed chain applies while the smoother settings are the ones it was built for
 static inline bool collapsed_on(const tdgl_ctx *ctx) {

@@ -231,7 +231,7 @@ def schur_setup_dist(lp, piece):
 
 def schur_apply_dist(lp, piece, lu, Spinv, r_own, counts=None):
     """One application ``z = M r`` on the owned rows: two local solves, ONE all-reduce of |Gamma| doubles, a replicated
-    dense product (the sequence of csrc/poisson.inc: precond_schur_apply)."""
+    dense product (the sequence of csrc/schur.inc: precond_schur_apply)."""
     r_loc = np.zeros(lp.n_loc)
     r_loc[: lp.n_own] = r_own
     y = lu.solve(r_loc[piece.interior])

@@ -1,5 +1,5 @@
 """The two kernels of the block low-rank top separator, `k_blr_project` and `k_blr_finish` (kernels.inc; launched by
-`blr_launch`, poisson.inc), entry by entry against the float64 model of the stored form (tests/blr_model.py).
+`blr_launch`, factors.inc), entry by entry against the float64 model of the stored form (tests/blr_model.py).
 
 A. The kernels alone (`tdgl_blr_apply`): on the matrices of tests/test_blr_form_host.py the whole operator is recovered
    with ONE call over all n unit vectors, four standard-normal columns and the all-ones column, and every entry is
