@@ -795,6 +795,42 @@ int tdgl_field_plan_eval(tdgl_field_plan *plan, int32_t n_fields, const double *
  * *last_ms its device time between the upload of K and the read-back (either may be NULL). */
 int tdgl_field_plan_stats(tdgl_field_plan *plan, int64_t *out4, double *last_ms);
 
+/* ------------------------------------------------------------------ vortex cores and windings (post-processing) */
+/* Where psi winds: the integer winding of arg psi around every mesh triangle, with the zero of the linear interpolant
+ * of psi where it is +-1, and around closed loops of sites, for many saved frames in one call (csrc/vortices.inc,
+ * DESIGN.md section 3).  The plan owns its device buffers and its stream and needs no tdgl_ctx.  Errors go to the
+ * global tdgl_last_error(NULL).
+ * sites_xy: [n_sites][2]; elements: [n_tri][3] site numbers; loops in CSR form: loop l is loop_sites[loop_ptr[l] ..
+ * loop_ptr[l + 1]), closed (its first site is not repeated).  n_tri and n_loops may be 0.
+ * TDGL_ERR_ARG: a negative size, n_sites < 1, an element or a loop site out of range, a loop of fewer than 3 sites,
+ * loop_ptr[0] != 0, a null array that is needed, no such device. */
+#define TDGL_WINDING_UNDEFINED INT32_MIN
+typedef struct tdgl_vortex_plan tdgl_vortex_plan;
+int tdgl_vortex_plan_create(tdgl_vortex_plan **out, int device_id, int64_t n_sites, const double *sites_xy,
+                            int64_t n_tri, const int32_t *elements, int32_t n_loops, const int64_t *loop_ptr,
+                            const int32_t *loop_sites);
+void tdgl_vortex_plan_destroy(tdgl_vortex_plan *plan);
+/* psi: [n_frames][n_sites][2] doubles (re, im).  Any output pointer may be NULL and is then not touched.
+ * With p = u.re v.im, q = u.im v.re and s(u, v) = +1 / -1 / 0 for p > q / p < q / otherwise, a triangle (i0, i1, i2)
+ * with values (a, b, c) has charge orient * w: w = +-1 when s(a, b), s(b, c), s(c, a) are all +-1, else 0; orient is
+ * the sign of the triangle's signed area.  A zero or NaN vertex gives 0.
+ *   counts[f]          charged triangles of frame f (always the true number)
+ *   tri_charge[k][2]   (triangle, charge) of record k;  xy[k][2] its core position: sum_k lambda_k r_k with
+ *                      lambda_a = cross(b, c) / S etc., cross(u, v) = p - q, S the sum of the three
+ * Records are in (frame, triangle) order, the same bytes on every call; when there are more than `capacity`, the
+ * first `capacity` of that order are written.
+ *   windings[f][l]     winding of psi around loop l by the crossing rule over its edges u -> v: +1 for u.im <= 0 <
+ *                      v.im with p > q, -1 for v.im <= 0 < u.im with p < q; TDGL_WINDING_UNDEFINED when a vertex is zero
+ *                      or not finite, or an edge is a segment through the origin (p == q with u.re v.re < 0 or
+ *                      u.im v.im < 0)
+ * Frames go up in chunks, so the staging buffer stays bounded whatever n_frames.
+ * TDGL_ERR_ARG (the plan stays usable): null plan / psi, n_frames < 1, capacity < 0. */
+int tdgl_vortex_plan_find(tdgl_vortex_plan *plan, int32_t n_frames, const double *psi, int64_t capacity,
+                          int64_t *counts, int32_t *tri_charge, double *xy, int32_t *windings);
+/* out4 = {charged triangles found, frames, chunks of frames, kernel launches} of the last call; *last_ms its device
+ * time between the uploads of psi and the read-back, summed over the chunks (either may be NULL). */
+int tdgl_vortex_plan_stats(tdgl_vortex_plan *plan, int64_t *out4, double *last_ms);
+
 /* ------------------------------------------------------------------ the time loop */
 /* Start a Runner stage (runner.py:294-297, 315-318): time = 0, stage step = 0.  Runner.dt
  * and the controller state are deliberately NOT reset. */

@@ -641,6 +641,7 @@ static inline int64_t now_ns() {
 #include "screening.inc"
 #include "screening_tree.inc"
 #include "fields.inc"
+#include "vortices.inc"
 #include "run.inc"
 
 // ---------------------------------------------------------------------------------------

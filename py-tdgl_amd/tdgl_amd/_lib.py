@@ -413,6 +413,13 @@ SIGNATURES = {
     "tdgl_field_plan_destroy": (None, [C.c_void_p]),
     "tdgl_field_plan_eval": (C.c_int, [C.c_void_p, C.c_int32, c_f64p, C.c_int32, c_f64p, c_f64p, c_f64p]),
     "tdgl_field_plan_stats": (C.c_int, [C.c_void_p, c_i64p, c_f64p]),
+    # vortex cores and windings (csrc/vortices.inc); the plan is an opaque pointer
+    "tdgl_vortex_plan_create": (
+        C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, c_f64p, C.c_int64, c_i32p, C.c_int32, c_i64p, c_i32p]),
+    "tdgl_vortex_plan_destroy": (None, [C.c_void_p]),
+    "tdgl_vortex_plan_find": (
+        C.c_int, [C.c_void_p, C.c_int32, c_f64p, C.c_int64, c_i64p, c_i32p, c_f64p, c_i32p]),
+    "tdgl_vortex_plan_stats": (C.c_int, [C.c_void_p, c_i64p, c_f64p]),
     "tdgl_get_step_stats": (C.c_int, [_CTX, C.POINTER(C.c_int64), C.c_int32]),
     "tdgl_get_edge_current_launches": (C.c_int, [_CTX, C.POINTER(C.c_int64), C.c_int32]),
     "tdgl_get_direct_stats": (C.c_int, [_CTX, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
@@ -546,6 +553,13 @@ def p_i32(a):
         return None
     assert a.flags["C_CONTIGUOUS"] and a.dtype == np.int32
     return a.ctypes.data_as(c_i32p)
+
+
+def p_i64(a):
+    if a is None:
+        return None
+    assert a.flags["C_CONTIGUOUS"] and a.dtype == np.int64
+    return a.ctypes.data_as(c_i64p)
 
 
 def check(status, ctx=None):

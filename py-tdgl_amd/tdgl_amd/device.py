@@ -472,6 +472,20 @@ class Device:
         xi = self.layer.coherence_length
         return [self.mesh.closest_site(xy) for xy in self.probe_points / xi]
 
+    def boundary_sites(self):
+        """``{polygon_name: site indices}`` of the mesh sites on the boundary of the film and of every hole
+        (`tdgl/device/device.py:308-333`), each in counter-clockwise order without repeating its first site; ``None``
+        without a mesh.  The loops are the closed chains of the mesh's boundary edges (`tdgl_amd.vortices`); where
+        each starts is not specified."""
+        if self.mesh is None:
+            return None
+        from .vortices import boundary_loops, name_loops
+
+        edge_mesh = self.mesh.edge_mesh
+        points = self.points
+        loops = boundary_loops(edge_mesh.edges, edge_mesh.boundary_edge_indices, points)
+        return name_loops(loops, points, [self.film] + list(self.holes))
+
     # -- meshing ----------------------------------------------------------------------------
     def make_mesh(
         self,

@@ -9,7 +9,7 @@ import scipy.sparse as sp
 from scipy.sparse.csgraph import reverse_cuthill_mckee
 
 from . import _lib
-from ._lib import c128, f64, i32, p_f64, p_i32
+from ._lib import c128, f64, i32, p_f64, p_i32, p_i64
 from .amg import Hierarchy, build_hierarchy
 
 
@@ -1789,6 +1789,103 @@ class FieldPlan:
     def close(self):
         if getattr(self, "_plan", None) is not None and self._plan.value:
             self._lib.tdgl_field_plan_destroy(self._plan)
+            self._plan = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+WINDING_UNDEFINED = -(2 ** 31)  # TDGL_WINDING_UNDEFINED
+
+
+class VortexPlan:
+    """Owns one ``tdgl_vortex_plan`` (csrc/vortices.inc): the sites, the triangles with their orientation and closed
+    loops of sites kept on the device; :meth:`find` returns, for a batch of order parameters, the charged triangles with
+    their core positions and the winding around every loop.  ``loops``: a sequence of site-index sequences (at least
+    3 sites each, the first not repeated).  Needs no ``TDGLContext``.  A context manager; freed on ``__del__`` too."""
+
+    def __init__(self, sites_xy, elements, loops=(), device_id=0):
+        _lib.require_gpu()
+        self._lib = _lib.load()
+        self._plan = C.c_void_p()
+        sites_xy = f64(sites_xy)
+        if sites_xy.ndim != 2 or sites_xy.shape[1] != 2:
+            raise ValueError(f"Expected sites [n, 2] (got {sites_xy.shape}).")
+        elements = i32(np.asarray(elements).reshape(-1, 3))
+        loops = [i32(np.asarray(loop).reshape(-1)) for loop in loops]
+        loop_ptr = np.zeros(len(loops) + 1, dtype=np.int64)
+        loop_ptr[1:] = np.cumsum([len(loop) for loop in loops])
+        loop_sites = i32(np.concatenate(loops)) if loops else np.zeros(0, dtype=np.int32)
+        self.n, self.n_tri, self.n_loops = len(sites_xy), len(elements), len(loops)
+        self.last_capacity = 0  # records the last call of find() held: its next call starts there
+        _lib.check(self._lib.tdgl_vortex_plan_create(
+            C.byref(self._plan), int(device_id), self.n, p_f64(sites_xy), self.n_tri, p_i32(elements), self.n_loops,
+            p_i64(loop_ptr), p_i32(loop_sites)))
+
+    def _frames(self, psi):
+        if not self._plan.value:
+            raise RuntimeError("VortexPlan is closed.")
+        psi = c128(psi)
+        if psi.ndim == 1:
+            psi = psi[None]
+        if psi.ndim != 2 or psi.shape[1] != self.n or len(psi) < 1:
+            raise ValueError(f"Expected psi of shape [n_frames, {self.n}] (got {psi.shape}).")
+        return psi
+
+    def find_once(self, psi, capacity, windings=True):
+        """One call of ``tdgl_vortex_plan_find`` with room for ``capacity`` records: ``(counts [F], triangles [k],
+        charges [k], xy [k, 2], windings [F, n_loops] or None)`` with ``k = min(counts.sum(), capacity)``, the first
+        ``k`` records in (frame, triangle) order."""
+        psi = self._frames(psi)
+        capacity = int(capacity)
+        counts = np.zeros(len(psi), dtype=np.int64)
+        tri_charge = np.zeros((max(capacity, 0), 2), dtype=np.int32)
+        xy = np.zeros((max(capacity, 0), 2))
+        wind = np.zeros((len(psi), self.n_loops), dtype=np.int32) if windings else None
+        _lib.check(self._lib.tdgl_vortex_plan_find(self._plan, len(psi), p_f64(psi), capacity, p_i64(counts),
+                                                   p_i32(tri_charge), p_f64(xy), p_i32(wind)))
+        k = min(int(counts.sum()), capacity)
+        return counts, tri_charge[:k, 0].copy(), tri_charge[:k, 1].copy(), xy[:k], wind
+
+    def find(self, psi, windings=True):
+        """All records of ``psi`` ([n] or [F, n]): as :meth:`find_once`, retried exactly once with the exact capacity
+        when the first call's did not hold them."""
+        psi = self._frames(psi)
+        capacity = max(self.last_capacity, 1024)
+        out = self.find_once(psi, capacity, windings)
+        total = int(out[0].sum())
+        if total > capacity:
+            capacity = total
+            out = self.find_once(psi, capacity, windings)
+        self.last_capacity = capacity
+        return out
+
+    def windings(self, psi):
+        """The windings alone, [F, n_loops] int32 with ``WINDING_UNDEFINED`` where a loop's is not defined."""
+        psi = self._frames(psi)
+        wind = np.zeros((len(psi), self.n_loops), dtype=np.int32)
+        _lib.check(self._lib.tdgl_vortex_plan_find(self._plan, len(psi), p_f64(psi), 0, None, None, None, p_i32(wind)))
+        return wind
+
+    def stats(self) -> dict:
+        """Of the last call: charged triangles found, frames, chunks of frames, kernel launches, and the device time
+        in milliseconds between the uploads of psi and the read-back."""
+        out, ms = (C.c_int64 * 4)(), C.c_double(0)
+        _lib.check(self._lib.tdgl_vortex_plan_stats(self._plan, out, C.byref(ms)))
+        return dict(found=out[0], frames=out[1], chunks=out[2], launches=out[3], last_ms=ms.value)
+
+    def close(self):
+        if getattr(self, "_plan", None) is not None and self._plan.value:
+            self._lib.tdgl_vortex_plan_destroy(self._plan)
             self._plan = C.c_void_p()
 
     def __enter__(self):

@@ -52,6 +52,13 @@ class BiotSavartField(NamedTuple):
     normal_current: Any
 
 
+class BoundaryPhases(NamedTuple):
+    """`tdgl/solution/solution.py`: site indices of a boundary loop and the unwrapped phase of psi along them."""
+
+    indices: Any
+    phases: Any
+
+
 def get_data_range(h5file):
     """Smallest and largest ``data/<k>`` in an output file (`tdgl/solution/data.py:14-17`)."""
     keys = np.asarray([int(key) for key in h5file["data"]])
@@ -620,6 +627,52 @@ class Solution:
             fields.append(Quantity(H, self.field_units) if with_units else H)
         fields = BiotSavartField(*fields)
         return sum(fields) if return_sum else fields
+
+    # -- vortices and windings -----------------------------------------------------------------------
+    def boundary_phases(self, delta: bool = False) -> Dict[str, BoundaryPhases]:
+        """``{polygon_name: (boundary_indices, boundary_phases)}`` (solution.py:593-621): the unwrapped phase of psi
+        along the boundary sites of the film and of every hole, as the reference computes it -- over the open chain
+        of sites, so ``(phases[-1] - phases[0]) / (2 pi)`` misses the step from the last site back to the first.
+        ``delta=True`` subtracts ``phases[0]``.  The integer winding is :meth:`boundary_windings`."""
+        theta = np.angle(self.tdgl_data.psi)
+        phases = {}
+        for name, indices in self.device.boundary_sites().items():
+            phase = np.unwrap(theta[indices])
+            if delta:
+                phase -= phase[0]
+            phases[name] = BoundaryPhases(indices, phase)
+        return phases
+
+    def _vortex_finder(self, loops):
+        from .vortices import VortexFinder
+
+        return VortexFinder(self.device, loops=loops, device_id=getattr(self.options, "device_id", 0))
+
+    def boundary_windings(self, backend: str = "host") -> Dict[str, Optional[int]]:
+        """``{polygon_name: winding}`` of the loaded step's psi around the boundary of the film and of every hole,
+        counter-clockwise: an exact integer by the crossing rule of `tdgl_amd.vortices`, or ``None`` where the loop
+        passes through a site with psi = 0 (or a non-finite one) or an edge's segment passes through the origin.
+        ``backend``: ``"host"`` (NumPy) or ``"hip"`` (csrc/vortices.inc on ``options.device_id``; needs a GPU, never
+        chosen automatically)."""
+        from .vortices import loop_winding
+
+        if _check_backend(backend) == "hip":
+            with self._vortex_finder(None) as finder:
+                return finder.windings(self.tdgl_data)
+        psi = self.tdgl_data.psi
+        return {name: loop_winding(psi, loop) for name, loop in self.device.boundary_sites().items()}
+
+    def vortices(self, backend: str = "host"):
+        """The vortex cores of the loaded step: ``Vortices(positions [k, 2] in length_units, charges [k], triangles [k])``
+        in triangle order -- every mesh triangle around which psi winds once, with the zero of the linear interpolant
+        of psi on it (`tdgl_amd.vortices`).  ``backend`` as for :meth:`boundary_windings`; both give the same triangles
+        and charges."""
+        from .vortices import host_find
+
+        if _check_backend(backend) == "hip":
+            with self._vortex_finder({}) as finder:
+                return finder.find(self.tdgl_data)
+        return host_find(self.tdgl_data.psi, self.device.points, self.device.triangles)
 
     def polygon_fluxoid(self, polygon_points, interp_method: str = "linear", units: Union[str, None] = "Phi_0",
                         with_units: bool = True, backend: str = "host") -> Fluxoid:
