@@ -334,9 +334,8 @@ struct EnsReplica {
     LoopState loop;  // controller, loop, retry and field state: the host's mirror of the replica's StepCtl
     bool have_ctl = false, have_links = false, have_eps = false, have_state = false, lap_valid = false;
     FieldArrays field;  // a moving field: the replica's own bases and A_0 (its descriptors and tables live in the ensemble's pools)
-    // tabulated terminal currents / separable epsilon (empty: none)
-    std::vector<double> mu_t, mu_dens, eps_t, eps_f;
-    std::vector<int32_t> mu_group;  // [nb]: table row of each boundary position, -1 where no table applies
+    MuTable mu_tab;    // tabulated terminal currents / separable epsilon: the host's nodes (their device copy is the ensemble's pools)
+    EpsTable eps_tab;
 };
 
 struct tdgl_ensemble {
@@ -352,9 +351,9 @@ struct tdgl_ensemble {
     // time-dependent inputs (allocated when the first replica asks): per replica A, A_prev (2 m_pad), dA/dt
     // (m_pad), the boundary term before dA/dt (n_pad), mu_boundary (nb), epsilon0 (n_pad); the tables as pools
     DevBuf<double> A, Aprev, dadt, cvec, mu_b, eps0;
-    DevBuf<double> tab_mu_t, tab_mu_dens, tab_eps_t, tab_eps_f;
-    DevBuf<int32_t> tab_mu_toff, tab_mu_group, tab_eps_off, ramping, moved;  // ramping[r]: the replica's field moves in this batch
-    DevBuf<int64_t> tab_mu_doff;
+    DevBuf<double> mu_t, mu_dens, eps_t, eps_f;
+    DevBuf<int32_t> mu_toff, mu_group, eps_off, ramping, moved;  // ramping[r]: the replica's field moves in this batch
+    DevBuf<int64_t> mu_doff;
     // the moving fields: per replica FIELD_TERMS_MAX descriptors, the pools of their tables' nodes, the replicas' bases and A_0
     DevBuf<FieldTerm> term_desc;
     DevBuf<double> tab_term_t, tab_term_v;
@@ -618,9 +617,8 @@ extern "C" int tdgl_ensemble_set_link_table(tdgl_ensemble *e, int32_t r, const d
     tdgl_ctx *ctx = e->ctx;
     if (!A_base) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_set_link_table: null A_base");
     TDGL_TRY(check_link_table(ctx, "tdgl_ensemble_set_link_table", n_nodes, times, values));
-    const std::vector<double> t(times, times + n_nodes);
     TDGL_TRY(ens_begin_field(e, r));
-    TDGL_TRY(tdgl_set_link_exponents_base(ctx, A_base, table_value(t, values, 0.0)));
+    TDGL_TRY(tdgl_set_link_exponents_base(ctx, A_base, table_value(times, values, n_nodes, 0.0)));
     TDGL_TRY(ens_take_field(e, r));
     e->rep[r].loop.field.set_product_source(TERM_TABLE, nullptr, times, values, n_nodes);
     return TDGL_OK;
@@ -670,11 +668,8 @@ extern "C" int tdgl_ensemble_set_mu_boundary_table(tdgl_ensemble *e, int32_t r, 
         // solver.py:289, 323: mu_boundary and the densities start at 0; the table rewrites its positions
         HIP_TRY(ctx, hipMemset(e->mu_b.p + (int64_t)r * ctx->nb, 0, ctx->nb * sizeof(double)));
     }
-    p.mu_t.assign(times, times + n_nodes);
-    p.mu_dens.assign(density, density + (n_nodes ? (size_t)n_groups * n_nodes : 0));
-    p.mu_group.assign(n_nodes ? (size_t)ctx->nb : 0, -1);
-    for (int32_t g = 0; n_nodes && g < n_groups; ++g)
-        for (int32_t k = group_ptr[g]; k < group_ptr[g + 1]; ++k) p.mu_group[(size_t)group_pos[k]] = g;
+    if (n_nodes != 0) p.mu_tab.set(n_nodes, times, n_groups, group_ptr, group_pos, density, ctx->nb);
+    else p.mu_tab.clear();
     e->tables_dirty = true;
     return TDGL_OK;
 }
@@ -693,8 +688,8 @@ extern "C" int tdgl_ensemble_set_epsilon_table(tdgl_ensemble *e, int32_t r, cons
         TDGL_TRY(upload_sites(ctx, epsilon0, tmp));
         TDGL_TRY(ens_copy(ctx, e->eps0.p + r * e->n_pad, tmp.p, e->n_pad));
     }
-    p.eps_t.assign(times, times + n_nodes);
-    p.eps_f.assign(factor, factor + n_nodes);
+    if (n_nodes != 0) p.eps_tab.set(n_nodes, times, factor);
+    else p.eps_tab.clear();
     e->tables_dirty = true;
     return TDGL_OK;
 }
@@ -711,15 +706,18 @@ static int ens_upload_tables(tdgl_ensemble *e) {
     for (int r = 0; r < R; ++r) {
         const EnsReplica &p = e->rep[r];
         doff[r] = (int64_t)md.size();
-        mt.insert(mt.end(), p.mu_t.begin(), p.mu_t.end());
-        md.insert(md.end(), p.mu_dens.begin(), p.mu_dens.end());
-        if (!p.mu_group.empty()) std::copy(p.mu_group.begin(), p.mu_group.end(), group.begin() + (size_t)r * nb);
+        const MuTable &M = p.mu_tab;
+        const EpsTable &E = p.eps_tab;
+        const std::vector<int32_t> g = M.on() ? M.groups(ctx->nb) : std::vector<int32_t>();
+        mt.insert(mt.end(), M.t.begin(), M.t.end());
+        md.insert(md.end(), M.dens.begin(), M.dens.end());
+        std::copy(g.begin(), g.end(), group.begin() + (size_t)r * nb);
         toff[r + 1] = (int32_t)mt.size();
-        et.insert(et.end(), p.eps_t.begin(), p.eps_t.end());
-        ef.insert(ef.end(), p.eps_f.begin(), p.eps_f.end());
+        et.insert(et.end(), E.t.begin(), E.t.end());
+        ef.insert(ef.end(), E.f.begin(), E.f.end());
         eoff[r + 1] = (int32_t)et.size();
-        e->any_mu_table |= !p.mu_t.empty();
-        e->any_eps_table |= !p.eps_t.empty();
+        e->any_mu_table |= M.on();
+        e->any_eps_table |= E.on();
     }
     std::vector<FieldTerm> desc((size_t)R * FIELD_TERMS_MAX, FieldTerm{});
     std::vector<const double *> bases((size_t)R, nullptr), a0s((size_t)R, nullptr);
@@ -738,14 +736,14 @@ static int ens_upload_tables(tdgl_ensemble *e) {
     HIP_TRY(ctx, e->tab_term_v.upload(kv));
     if (mt.empty()) mt.push_back(0.0), md.push_back(0.0);  // (never read: every replica's node count is 0)
     if (et.empty()) et.push_back(0.0), ef.push_back(0.0);
-    HIP_TRY(ctx, e->tab_mu_toff.upload(toff));
-    HIP_TRY(ctx, e->tab_mu_doff.upload(doff));
-    HIP_TRY(ctx, e->tab_mu_group.upload(group));
-    HIP_TRY(ctx, e->tab_mu_t.upload(mt));
-    HIP_TRY(ctx, e->tab_mu_dens.upload(md));
-    HIP_TRY(ctx, e->tab_eps_off.upload(eoff));
-    HIP_TRY(ctx, e->tab_eps_t.upload(et));
-    HIP_TRY(ctx, e->tab_eps_f.upload(ef));
+    HIP_TRY(ctx, e->mu_toff.upload(toff));
+    HIP_TRY(ctx, e->mu_doff.upload(doff));
+    HIP_TRY(ctx, e->mu_group.upload(group));
+    HIP_TRY(ctx, e->mu_t.upload(mt));
+    HIP_TRY(ctx, e->mu_dens.upload(md));
+    HIP_TRY(ctx, e->eps_off.upload(eoff));
+    HIP_TRY(ctx, e->eps_t.upload(et));
+    HIP_TRY(ctx, e->eps_f.upload(ef));
     e->tables_dirty = false;
     return TDGL_OK;
 }
@@ -861,11 +859,11 @@ static void ens_queue_drives(tdgl_ensemble *e, bool ramping) {
         hipLaunchKernelGGL(k_ens_mu_table, dim3(1, R), dim3(BLOCK), 0, ctx->stream, (int)ctx->nb, (int)ctx->n_b_sites,
                            (const int32_t *)ctx->d_b_sites.p, (const int32_t *)ctx->b_s0.p, (const int32_t *)ctx->b_s1.p,
                            (const double *)ctx->b_c0.p, (const double *)ctx->b_c1.p, e->mu_b.p, e->cvec.p, e->ceff.p, e->n_pad,
-                           (const int32_t *)e->tab_mu_toff.p, (const int64_t *)e->tab_mu_doff.p, (const double *)e->tab_mu_t.p,
-                           (const double *)e->tab_mu_dens.p, (const int32_t *)e->tab_mu_group.p, (const StepCtl *)e->d_ctl.p);
+                           (const int32_t *)e->mu_toff.p, (const int64_t *)e->mu_doff.p, (const double *)e->mu_t.p,
+                           (const double *)e->mu_dens.p, (const int32_t *)e->mu_group.p, (const StepCtl *)e->d_ctl.p);
     if (e->any_eps_table)
         hipLaunchKernelGGL(k_ens_eps_table, dim3(grid_for(e->n_pad), R), dim3(BLOCK), 0, ctx->stream, e->n_pad, (const double *)e->eps0.p,
-                           e->eps.p, (const int32_t *)e->tab_eps_off.p, (const double *)e->tab_eps_t.p, (const double *)e->tab_eps_f.p,
+                           e->eps.p, (const int32_t *)e->eps_off.p, (const double *)e->eps_t.p, (const double *)e->eps_f.p,
                            (const StepCtl *)e->d_ctl.p);
     if (!ramping) return;
     const SellPattern &pat = ctx->lap_pat;

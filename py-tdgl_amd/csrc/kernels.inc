@@ -87,11 +87,11 @@ __global__ __launch_bounds__(BLOCK) void k_link_variables(int64_t m, const doubl
     link_variable_body(e, A, A2, dx, dy, U);
 }
 
-// A = scale * A_base (a time-dependent factor times a static field: sources/scaling.py ramps)
-__global__ __launch_bounds__(BLOCK) void k_scale_links(int64_t m2, double scale, const double *__restrict__ base,
-                                                       double *__restrict__ A) {
+// out = scale * base (epsilon = factor(t) * epsilon0 of the loop with one synchronisation per step: apply_time_tables)
+__global__ __launch_bounds__(BLOCK) void k_scale(int64_t n, double scale, const double *__restrict__ base,
+                                                 double *__restrict__ out) {
     const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
-    if (i < m2) A[i] = scale * base[i];
+    if (i < n) out[i] = scale * base[i];
 }
 
 // dA/dt along each edge: ((A_new - A_prev) / dt) . e_hat  (solver.py:630-634); A_prev <- A_new.
@@ -441,6 +441,22 @@ __host__ __device__ inline double linear_ramp_value(double t, double tmin, doubl
     return final_;
 }
 
+// Value at time t of the piecewise-linear table (times[k], v[k]), n >= 1 nodes, constant outside the node range.  Like the
+// ramp: host and device evaluate THIS, with no contraction into fused multiply-adds.
+__host__ __device__ inline double table_value(const double *__restrict__ times, const double *__restrict__ v, int n, double t) {
+#pragma clang fp contract(off)
+    if (t <= times[0]) return v[0];
+    if (t >= times[n - 1]) return v[n - 1];
+    int lo = 0, hi = n - 1;  // first node with times[node] > t (std::upper_bound)
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (times[mid] > t) hi = mid;
+        else lo = mid;
+    }
+    const double t0 = times[hi - 1], t1 = times[hi];
+    return v[hi - 1] + (v[hi] - v[hi - 1]) * ((t - t0) / (t1 - t0));
+}
+
 // L psi^n with the links of this step (the cached one belongs to the links of the previous step)
 template <class IT>
 __global__ __launch_bounds__(BLOCK) void k_psi_laplacian_ra_fresh(
@@ -556,27 +572,10 @@ __global__ __launch_bounds__(BLOCK) void k_boundary_term(int64_t nb, const int32
     }
 }
 
-// Value at `time` of the piecewise-linear table (times[k], v[k]), constant outside the node range: the host's
-// table_value (tdgl_hip.hip), operation for operation -- no contraction into fused multiply-adds.
-__device__ __forceinline__ double table_value_dev(const double *__restrict__ times, const double *__restrict__ v, int n_nodes,
-                                                  double time) {
-#pragma clang fp contract(off)
-    if (time <= times[0]) return v[0];
-    if (time >= times[n_nodes - 1]) return v[n_nodes - 1];
-    int lo = 0, hi = n_nodes - 1;  // first node with times[node] > time (std::upper_bound)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (times[mid] > time) hi = mid;
-        else lo = mid;
-    }
-    const double t0 = times[hi - 1], t1 = times[hi];
-    return v[hi - 1] + (v[hi] - v[hi - 1]) * ((time - t0) / (t1 - t0));
-}
-
 // ---- the moving applied field A(t) = A_0 + f_1(t) A_1 + ... + f_K(t) A_K + loops (FieldDrive; tdgl_set_link_exponents_base,
 // tdgl_set_link_terms, tdgl_set_link_loops) ----------------------------------------------------------------------------------
 // The step rule (FieldDrive::step on the host): the K factors and every loop's four values are evaluated at the controller's
-// time with the evaluators above (linear_ramp_value, table_value_dev); nothing moves only when EVERY value equals its last
+// time with the evaluators above (linear_ramp_value, table_value); nothing moves only when EVERY value equals its last
 // two evaluations and a dynamic update has run -- so a plateau inside a table skips the link launches as a finished ramp
 // does.  `term`: the K = ctl->n_terms descriptors of THIS controller; a table term's nodes are times[off .. off + n),
 // values[off .. off + n).  A factor the caller supplies (TERM_HOST) never comes here: the loop does not evaluate such a field.
@@ -591,7 +590,7 @@ __device__ __forceinline__ bool terms_eval(const StepCtl *__restrict__ ctl, cons
         s[k] = 0.0;
         if (k >= K) continue;
         const FieldTerm d = term[k];
-        s[k] = d.kind == TERM_TABLE ? table_value_dev(times + d.off, values + d.off, d.n, t)
+        s[k] = d.kind == TERM_TABLE ? table_value(times + d.off, values + d.off, d.n, t)
                                     : linear_ramp_value(t, d.ramp[0], d.ramp[1], d.ramp[2], d.ramp[3]);
         same = same && s[k] == ctl->term_scale[k] && s[k] == ctl->term_scale_prev[k];
     }
@@ -670,7 +669,7 @@ __device__ __forceinline__ void field_begin_body(StepCtl *__restrict__ ctl, cons
             const FieldLoop d = loop[l];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                lp[l][j] = table_value_dev(tab + d.off, tab + (int64_t)(j + 1) * T + d.off, d.n, t);
+                lp[l][j] = table_value(tab + d.off, tab + (int64_t)(j + 1) * T + d.off, d.n, t);
                 same = same && lp[l][j] == ctl->loop_par[l][j] && lp[l][j] == ctl->loop_par_prev[l][j];
             }
         }
@@ -811,8 +810,8 @@ __global__ __launch_bounds__(BLOCK) void k_field_links(int64_t m, int64_t m_pad,
 // about to be attempted -- which only the device knows): ONE workgroup evaluates the piecewise-linear tables at
 // ctl->time, rewrites mu_boundary at the tabulated positions, and rebuilds c = mu_boundary_laplacian @ mu_boundary
 // on the sites boundary edges touch (every such site receives exactly two contributions: the atomics commute) and
-// ceff = c (no dA/dt term in this loop).  Same arithmetic, operation for operation, as the host's table_value +
-// k_boundary_term + k_ceff: the run-ahead loop stays bit-identical to the loop with one synchronisation per step.
+// ceff = c (no dA/dt term in this loop).  The same table_value as the host's, then the arithmetic of
+// k_boundary_term + k_ceff, operation for operation: the run-ahead loop stays bit-identical to the loop with one synchronisation per step.
 // (body: one whole workgroup)
 __device__ __forceinline__ void mu_table_body(int nb, int n_sites, const int32_t *__restrict__ b_sites, const int32_t *__restrict__ s0,
                                               const int32_t *__restrict__ s1, const double *__restrict__ c0,
@@ -822,7 +821,7 @@ __device__ __forceinline__ void mu_table_body(int nb, int n_sites, const int32_t
 #pragma clang fp contract(off)
     for (int k = threadIdx.x; k < nb; k += BLOCK) {
         const int g = group[k];
-        if (g >= 0) mu_b[k] = table_value_dev(times, dens + (int64_t)g * n_nodes, n_nodes, time);
+        if (g >= 0) mu_b[k] = table_value(times, dens + (int64_t)g * n_nodes, n_nodes, time);
     }
     for (int j = threadIdx.x; j < n_sites; j += BLOCK) cvec[b_sites[j]] = 0.0;
     __threadfence();
@@ -853,11 +852,11 @@ __global__ __launch_bounds__(BLOCK) void k_ra_mu_table(int nb, int n_sites, cons
 }
 
 // ... and with a separable disorder parameter epsilon(r, t) = factor(t) * epsilon0(r) (update_epsilon,
-// solver.py:364-381): the host's table_value + k_scale_links at the device's time.
+// solver.py:364-381): the host's table_value + k_scale at the device's time.
 __device__ __forceinline__ void eps_table_body(int64_t i, const double *__restrict__ eps0, double *__restrict__ eps, int n_nodes,
                                                const double *__restrict__ times, const double *__restrict__ factor, double time) {
 #pragma clang fp contract(off)
-    const double f = table_value_dev(times, factor, n_nodes, time);
+    const double f = table_value(times, factor, n_nodes, time);
     eps[i] = f * eps0[i];
 }
 

@@ -167,13 +167,13 @@ void FieldDrive::set_loops(int n, double z_film, const double *radii, const int3
 }
 
 double FieldDrive::value(int k, double t) const {
-    if (term[k].kind == TERM_TABLE) return table_value(term_t[k], term_v[k].data(), t);
+    if (term[k].kind == TERM_TABLE) return table_value(term_t[k].data(), term_v[k].data(), (int)term_t[k].size(), t);
     if (term[k].kind == TERM_RAMP) return linear_ramp_value(t, term[k].ramp[0], term[k].ramp[1], term[k].ramp[2], term[k].ramp[3]);
     return scale[k];  // (the caller's)
 }
 
 void FieldDrive::loop_values(int l, double t, double *out4) const {
-    for (int j = 0; j < 4; ++j) out4[j] = table_value(loop_t[l], loop_v[l][j].data(), t);
+    for (int j = 0; j < 4; ++j) out4[j] = table_value(loop_t[l].data(), loop_v[l][j].data(), (int)loop_t[l].size(), t);
 }
 
 void FieldDrive::values_at(double t, double *s, double *lp) const {

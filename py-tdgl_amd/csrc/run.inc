@@ -413,7 +413,7 @@ static bool run_ahead_ok(const tdgl_ctx *ctx) {
     if (ctx->loop.ramping() ? !(ctx->loop.runner_dt > 0.0) : ctx->loop.field.has_dadt) return false;
     // (the plans of the direct solve: no screening, currents every step)
     return !off && dense_on(ctx) && (ctx->direct->dense.tiles > 0) && currents_plan_runs_ahead(step_plan(ctx)) &&
-           (ctx->tab_mu_t.empty() || ctx->tab_mu_on_device) && (ctx->tab_eps_t.empty() || ctx->tab_eps_on_device) && ctx->have_links &&
+           ctx->mu_tab.runs_ahead() && ctx->eps_tab.runs_ahead() && ctx->have_links &&
            ctx->have_state && ctx->have_eps && (!ctl.adaptive || (ctl.adaptive_window >= 1 && ctl.adaptive_window <= RA_HIST_MAX));
 }
 
@@ -426,39 +426,17 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
     StepCtl &h = *ctx->h_ctl;
     const bool ramping = ctx->loop.ramping();
     ctx->loop.fill(h, end_time, true);
-    if (ramping && ctx->link_block_changed.n == 0) {
-        HIP_TRY(ctx, ctx->link_block_changed.alloc(grid_for(ctx->m)));
-        HIP_TRY(ctx, ctx->link_changed.alloc(1));
-    }
+    if (ramping) TDGL_TRY(ensure_link_flags(ctx));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctl.p, &h, sizeof(StepCtl), hipMemcpyHostToDevice, ctx->stream));
     const int np_ = (int)ctx->probes.size();
     const bool probing = np_ > 0 && want_probes;
     const bool owed_on_entry = ctx->currents.owed();
-    const bool mu_table = !ctx->tab_mu_t.empty(), eps_table = !ctx->tab_eps_t.empty();
-    if (mu_table) {
-        // The positions no table covers keep the host's values: uploaded once, b_mu then stays resident (the table
-        // kernel rewrites the tabulated positions only).  The device is about to apply densities the host does not
-        // see, so the host's record of "what was applied last" is void from here on -- also if this batch fails:
-        // the next step of the loop with one synchronisation per step re-applies its own (apply_time_tables).
-        if (!ctx->tab_mu_dev_synced) {
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->b_mu.p, ctx->tab_mu_host.data(), ctx->nb * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (pageable source: the host array may change after this call)
-            ctx->tab_mu_dev_synced = true;
-        }
-        for (double &d : ctx->tab_mu_last) d = NAN;
-    }
-    if (eps_table) ctx->tab_eps_last = NAN;  // (same: the host will not have seen the factor the device applied last)
+    const bool mu_table = ctx->mu_tab.on(), eps_table = ctx->eps_tab.on();
+    if (mu_table) TDGL_TRY(ctx->mu_tab.handed_to_device(ctx));
+    if (eps_table) ctx->eps_tab.handed_to_device();
     for (int s = 0; s < batch; ++s) {
-        if (mu_table)  // terminal currents at the time of this attempt (update_mu_boundary, solver.py:325-345)
-            hipLaunchKernelGGL(k_ra_mu_table, dim3(1), dim3(BLOCK), 0, ctx->stream, (int)ctx->nb, (int)ctx->n_b_sites,
-                               (const int32_t *)ctx->d_b_sites.p, (const int32_t *)ctx->b_s0.p, (const int32_t *)ctx->b_s1.p,
-                               (const double *)ctx->b_c0.p, (const double *)ctx->b_c1.p, ctx->b_mu.p, ctx->cvec.p, ctx->ceff.p,
-                               (int)ctx->tab_mu_t.size(), (const double *)ctx->d_tab_mu_t.p, (const double *)ctx->d_tab_mu_dens.p,
-                               (const int32_t *)ctx->d_tab_mu_group.p, (const StepCtl *)ctx->d_ctl.p);
-        if (eps_table)  // epsilon(r, t) = factor(t) epsilon0(r) at the time of this attempt (update_epsilon, solver.py:364-381)
-            hipLaunchKernelGGL(k_ra_eps_table, dim3(grid_for(ctx->n_pad)), dim3(BLOCK), 0, ctx->stream, ctx->n_pad,
-                               (const double *)ctx->tab_eps0.p, ctx->eps.p, (int)ctx->tab_eps_t.size(),
-                               (const double *)ctx->d_tab_eps_t.p, (const double *)ctx->d_tab_eps_f.p, (const StepCtl *)ctx->d_ctl.p);
+        if (mu_table) launch_ra_mu_table(ctx);
+        if (eps_table) launch_ra_eps_table(ctx);
         if (ramping) {
             // A(t) moves: the owed currents of psi^n first (they belong to the links and dA/dt of the step that produced
             // it), then what TDGLSolver.update does before the psi update (solver.py:626-642) -- all of it skipped by
@@ -470,31 +448,11 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
                                    (const int32_t *)ctx->e1.p, (const double *)ctx->e_inv_len.p, (const double2 *)ctx->e_U.p,
                                    (const double2 *)ctx->psi[0].p, (const double2 *)ctx->psi[1].p, (const double *)ctx->mu.p, ctx->js.p, ctx->jn.p,
                                    (const double *)ctx->e_dAdt.p, (const StepCtl *)dc);
-            const int nblk = grid_for(ctx->m);
-            const FieldDrive &F = ctx->loop.field;
-            const FieldArrays &fa = ctx->field;
-            LoopGeom g{};
-            g.n_loops = F.n_loops, g.z_film = F.zfilm;
-            for (int l = 0; l < g.n_loops; ++l) g.radius[l] = F.radius[l];
-            const double *tab = fa.tab.p;
-            hipLaunchKernelGGL(k_ra_field_begin, dim3(1), dim3(64), 0, ctx->stream, dc, (const FieldTerm *)fa.terms.p, tab, tab + fa.tab.n / 2,
-                               (const FieldLoop *)fa.loops.p, (const double *)fa.loop_tab.p, (int)(fa.loop_tab.n / 5));
-#define TDGL_KLINKS(LOOPS)                                                                                                              \
-    hipLaunchKernelGGL((k_field_links<LOOPS>), dim3(nblk), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->m_pad, FieldValues{}, g,           \
-                       (const double *)fa.bases.p, (const double *)fa.a0.p, (const double *)fa.centres.p, ctx->e_A.p, ctx->e_Aprev.p,   \
-                       (const double *)ctx->e_dirx.p, (const double *)ctx->e_diry.p, (const double *)ctx->e_inv_len.p, ctx->e_dAdt.p,   \
-                       ctx->link_block_changed.p, (const StepCtl *)dc)
-            if (F.loops()) TDGL_KLINKS(true); else TDGL_KLINKS(false);
-#undef TDGL_KLINKS
-            hipLaunchKernelGGL(k_any_flag, dim3(1), dim3(BLOCK), 0, ctx->stream, nblk, (const int32_t *)ctx->link_block_changed.p,
-                               ctx->link_changed.p, go);
-            hipLaunchKernelGGL(k_ceff, dim3(grid_for((int64_t)ctx->lap_pat.n_slices * WAVE)), dim3(BLOCK), 0, ctx->stream,
-                               ctx->lap_pat.n_slices, ctx->lap_pat.n_rows, ctx->lap_pat.slice_off.p, ctx->lap_slot_edge.p,
-                               ctx->lap_slot_w.p, ctx->e_inv_len.p, (const double *)ctx->e_dAdt.p, ctx->cvec.p, ctx->ceff.p, go);
-            hipLaunchKernelGGL(k_link_variables, dim3(grid_for(ctx->m)), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->e_A.p,
-                               (const double *)nullptr, ctx->e_dirx.p, ctx->e_diry.p, ctx->e_U.p, moved);
-            hipLaunchKernelGGL(k_fill_laplacian, dim3(grid_for(ctx->lap_pat.n_slots)), dim3(BLOCK), 0, ctx->stream,
-                               ctx->lap_pat.n_slots, ctx->lap_slot_edge.p, ctx->lap_slot_w.p, ctx->e_U.p, ctx->lap_vals.p, moved);
+            launch_ra_field_begin(ctx);
+            launch_field_links(ctx, FieldValues{}, dc);
+            launch_any_flag(ctx, go);
+            launch_ceff(ctx, ctx->e_dAdt.p, ctx->cvec.p, ctx->ceff.p, go);
+            launch_links(ctx, nullptr, moved);
             launch_ra_laplacian_fresh(ctx);
         }
         // (the edge currents of psi^n ride along: always behind the first attempt, for the first if they are owed)

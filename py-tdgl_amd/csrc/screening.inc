@@ -330,13 +330,7 @@ extern "C" int tdgl_induced_vector_potential(tdgl_ctx *ctx, const double *edge_c
 }
 
 // link variables from A_applied + A_induced, and the covariant Laplacian values (solver.py:670-673)
-static void screening_refresh_links(tdgl_ctx *ctx) {
-    hipLaunchKernelGGL(k_link_variables, dim3(grid_for(ctx->m)), dim3(BLOCK), 0, ctx->stream, ctx->m, ctx->e_A.p,
-                       ctx->scr_Aind.p, ctx->e_dirx.p, ctx->e_diry.p, ctx->e_U.p, (const int32_t *)nullptr);
-    hipLaunchKernelGGL(k_fill_laplacian, dim3(grid_for(ctx->lap_pat.n_slots)), dim3(BLOCK), 0, ctx->stream,
-                       ctx->lap_pat.n_slots, ctx->lap_slot_edge.p, ctx->lap_slot_w.p, ctx->e_U.p, ctx->lap_vals.p,
-                       (const int32_t *)nullptr);
-}
+static void screening_refresh_links(tdgl_ctx *ctx) { launch_links(ctx, ctx->scr_Aind.p, nullptr); }
 
 // get_induced_vector_potential (solver.py:522-578) for the currents in ctx->js / ctx->jn;
 // returns the relative change (screening error) through *err.

@@ -327,6 +327,50 @@ struct FieldDrive {
     void describe(FieldTerm *desc, std::vector<double> &times, std::vector<double> &values) const;
 };
 
+// Tabulated terminal currents (tdgl_set_mu_boundary_table, tdgl_ensemble_set_mu_boundary_table): piecewise-linear densities
+// per group of boundary-edge positions, evaluated before every step without a Python round trip -- by the host in the loop with
+// one synchronisation per step (step), by k_ra_mu_table / k_ens_mu_table at the device's own time otherwise.  The host walks the
+// groups as given (CSR), the device the array groups() makes of them; a replica of an ensemble keeps the nodes only (the
+// ensemble's pools are its device copy).  Its functions (drive.inc) are the only writers of its members.
+struct MuTable {
+    std::vector<double> t, dens;     // nodes; densities [n_groups x n_nodes]
+    std::vector<int32_t> ptr, pos;   // groups of boundary-edge positions (CSR-like)
+    std::vector<double> last, host;  // the densities the host applied last (NaN: void); the host's mirror of mu_boundary
+    bool dev_synced = false;         // b_mu on the device holds `host` at the positions no table covers
+    DevBuf<double> d_t, d_dens;      // the device's copy, for the run-ahead loop
+    DevBuf<int32_t> d_group;         // [nb]: group of a boundary position, -1 = not tabulated
+    bool on_device = false;
+
+    bool on() const { return !t.empty(); }
+    bool runs_ahead() const { return !on() || on_device; }  // nothing keeps the run-ahead loop from taking the steps
+    void clear();
+    // from validated arguments (check_mu_table); nb: the mesh's boundary positions.  The densities and the mirror start at 0
+    void set(int32_t n_nodes, const double *times, int32_t n_groups, const int32_t *group_ptr, const int32_t *group_pos,
+             const double *density, int64_t nb);
+    std::vector<int32_t> groups(int64_t nb) const;  // [nb]: as d_group
+    int to_device(tdgl_ctx *ctx);
+    bool step(double time);  // the mirror at `time`; true: a density differs from the one applied last (the caller applies the mirror)
+    void applied(const double *mu_boundary, int64_t nb);  // the caller's array went to the device (tdgl_set_mu_boundary)
+    int handed_to_device(tdgl_ctx *ctx);                  // a run-ahead batch is about to apply densities the host does not see
+};
+
+// The separable epsilon(r, t) = factor(t) epsilon0(r) (tdgl_set_epsilon_table, tdgl_ensemble_set_epsilon_table), likewise
+struct EpsTable {
+    std::vector<double> t, f;
+    double last = NAN;      // the factor the host applied last (NaN: void)
+    DevBuf<double> eps0;    // the static part, internal site order (a replica's lies in the ensemble's pool)
+    DevBuf<double> d_t, d_f;
+    bool on_device = false;
+
+    bool on() const { return !t.empty(); }
+    bool runs_ahead() const { return !on() || on_device; }
+    void clear();
+    void set(int32_t n_nodes, const double *times, const double *factor);  // validated: check_eps_table
+    int to_device(tdgl_ctx *ctx);
+    bool step(double time);  // true: the factor at `time`, now in `last`, differs from the one applied last
+    void handed_to_device();
+};
+
 // The time loop's bookkeeping on the host, one per trajectory (tdgl_ctx, every replica of an ensemble): the controller
 // (solver.py:316-320, 475-485, 698-707), Runner.dt / time / step (runner.py:260-263, 429-433), the retry state a run-ahead
 // batch leaves behind and the moving applied field (FieldDrive).  The classic loop drives it event by event (begin_step,
@@ -616,26 +660,13 @@ struct tdgl_ctx {
     tdgl::DevBuf<double> e_dAdt;          // dA/dt along the edges (time-dependent A: loop.field.has_dadt), else unused
     tdgl::DevBuf<int32_t> link_block_changed, link_changed;  // allclose(new_A, old_A) test (k_dadt)
     tdgl::FieldArrays field;              // the device arrays of loop.field (tdgl_set_link_exponents_base, _terms, _loops)
-    // Piecewise-linear time tables evaluated by tdgl_run itself before every step (no Python round
-    // trip per step): terminal current densities -> mu_boundary (tdgl_set_mu_boundary_table) and a
-    // time-dependent factor of epsilon (tdgl_set_epsilon_table)
-    std::vector<double> tab_mu_t, tab_mu_dens;       // nodes; densities [n_groups x n_nodes]
-    std::vector<int32_t> tab_mu_ptr, tab_mu_pos;     // groups of boundary-edge positions (CSR-like)
-    std::vector<double> tab_mu_last, tab_mu_host;    // last densities applied; host copy of mu_boundary
-    bool tab_mu_dev_synced = false;                  // b_mu on the device holds tab_mu_host at the positions no table covers
-    // the same table on the device, for the run-ahead loop (k_ra_mu_table evaluates it at the device's own time)
-    tdgl::DevBuf<double> d_tab_mu_t, d_tab_mu_dens;
-    tdgl::DevBuf<int32_t> d_tab_mu_group;            // [nb]: group of a boundary position, -1 = not tabulated
-    tdgl::DevBuf<int32_t> d_b_sites;                 // the sites that boundary edges touch, each once
-    int32_t n_b_sites = 0;
-    bool tab_mu_on_device = false;
-    tdgl::DevBuf<double> d_tab_eps_t, d_tab_eps_f;   // the epsilon factor's table on the device (k_ra_eps_table)
-    bool tab_eps_on_device = false;
-    std::vector<double> tab_eps_t, tab_eps_f;
-    tdgl::DevBuf<double> tab_eps0;                   // static part of epsilon, internal site order
-    double tab_eps_last = NAN;
+    // piecewise-linear time tables evaluated by tdgl_run itself before every step (drive.inc)
+    tdgl::MuTable mu_tab;
+    tdgl::EpsTable eps_tab;
     // boundary term: c = mu_boundary_laplacian @ mu_boundary
     tdgl::DevBuf<int32_t> b_s0, b_s1;
+    tdgl::DevBuf<int32_t> d_b_sites;      // the sites that boundary edges touch, each once (ensure_boundary_sites)
+    int32_t n_b_sites = 0;
     tdgl::DevBuf<double> b_c0, b_c1, b_mu;
     tdgl::DevBuf<double> cvec;            // boundary part
     tdgl::DevBuf<double> ceff;            // cvec + divergence(dA/dt): what the rhs kernel reads

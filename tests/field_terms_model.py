@@ -17,7 +17,7 @@ def ramp_value(t, tmin, tmax, initial, final):
 
 
 def table_value(t, times, values):
-    """table_value (csrc/tdgl_hip.hip), operation for operation: not np.interp, whose last bit may differ."""
+    """table_value (csrc/kernels.inc), operation for operation: not np.interp, whose last bit may differ."""
     times, values = [float(x) for x in times], [float(x) for x in values]
     if t <= times[0]:
         return values[0]

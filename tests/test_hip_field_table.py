@@ -162,7 +162,7 @@ def test_waveform_matches_the_callable_evaluated_on_the_host(direct_solve, monke
 
 
 def test_run_ahead_loop_and_classic_loop_agree_to_the_last_bit(direct_solve, monkeypatch):
-    """The device's table_value_dev against the host's table_value (TDGL_NO_RUN_AHEAD=1), operation for operation."""
+    """table_value on the device against table_value on the host (TDGL_NO_RUN_AHEAD=1), operation for operation."""
     ra, cl = _run("table", monkeypatch), _run("table_classic", monkeypatch)
     a, b = ra["sol"], cl["sol"]
     assert np.array_equal(a.dynamics.dt, b.dynamics.dt)

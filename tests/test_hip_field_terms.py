@@ -123,8 +123,8 @@ def test_fixture_through_vector_potential_terms(direct_solve, monkeypatch, name)
 
 
 def test_run_ahead_loop_and_classic_loop_agree_to_the_last_bit(direct_solve, monkeypatch):
-    """One links kernel and one step rule behind both loops, the factors from linear_ramp_value and table_value /
-    table_value_dev: nothing may differ."""
+    """One links kernel and one step rule behind both loops, the factors from linear_ramp_value and table_value on
+    the host and on the device: nothing may differ."""
     ra, cl = _run("terms", monkeypatch), _run("terms_classic", monkeypatch)
     a, b = ra["sol"], cl["sol"]
     assert np.array_equal(a.dynamics.dt, b.dynamics.dt)
