@@ -831,6 +831,52 @@ int tdgl_vortex_plan_find(tdgl_vortex_plan *plan, int32_t n_frames, const double
  * time between the uploads of psi and the read-back, summed over the chunks (either may be NULL). */
 int tdgl_vortex_plan_stats(tdgl_vortex_plan *plan, int64_t *out4, double *last_ms);
 
+/* ------------------------------------------------------------------ currents between the sites (post-processing) */
+/* Sheet current densities on the sites, values between the sites and the dipole moment of saved steps, for many frames
+ * in one call (csrc/sample.inc, DESIGN.md section 3, "Currents between the sites").  The plan owns its device buffers and
+ * its stream and needs no tdgl_ctx.  Errors go to the global tdgl_last_error(NULL).  No physical prefactor is applied:
+ * K0, xi and units stay with the caller.
+ * sites_xy [n_sites][2]; site_weight [n_sites] with centre_xy [2] (both or neither: without them no moments);
+ * edges [n_edges][2] site numbers with edge_dir [n_edges][2] their unit directions; elements [n_tri][3];
+ * points_xy [m][2], located once, here (m may be 0: site quantities only).
+ * TDGL_ERR_ARG, naming the argument: a needed array that is null, a negative size, n_sites < 1, an edge or element index
+ * out of range, a non-finite site, point, weight or direction, a site without an edge, no such device.  The arguments
+ * are checked before the device is touched. */
+typedef struct tdgl_sample_plan tdgl_sample_plan;
+int tdgl_sample_plan_create(tdgl_sample_plan **out, int device_id, int64_t n_sites, const double *sites_xy,
+                            const double *site_weight, const double *centre_xy, int64_t n_edges, const int32_t *edges,
+                            const double *edge_dir, int64_t n_tri, const int32_t *elements, int64_t m,
+                            const double *points_xy);
+void tdgl_sample_plan_destroy(tdgl_sample_plan *plan);
+/* triangle[p]: the lowest-numbered triangle whose three barycentric coordinates of point p are all >= -1e-12, with
+ * l1 = inv0 dx + inv1 dy, l2 = inv2 dx + inv3 dy, l0 = (1 - l1) - l2, (dx, dy) = p - a and inv the inverse of the edge
+ * matrix [b - a, c - a] (a triangle with zero determinant is never chosen); -1 when p is in none.  weights[p] = (l0, l1,
+ * l2), zeros with -1.  Either may be NULL. */
+int tdgl_sample_plan_location(tdgl_sample_plan *plan, int32_t *triangle, double *weights);
+/* edge_values: [n_frames][n_fields][n_edges] (n_fields 0, 1 or 2); psi: [n_frames][n_sites][2] or NULL.  Any output
+ * pointer may be NULL and is then not touched.
+ *   site_density[f][k][i][0:2]   g_i = (sum over the edges e with edges[e][0] == i, e ascending, then over those with
+ *                                edges[e][1] == i, e ascending, of F_e d_e: one running sum) / count_i / 2
+ *   point_density[f][k][p][0:2]  (w0 g_a + w1 g_b) + w2 g_c per component on the point's triangle (a, b, c); NaN with -1
+ *   point_psi[f][p][0:2]         the same of psi
+ *   moment[f][k]                 sum_i 1/2 ((x_i - cx) g_y - (y_i - cy) g_x) weight_i, added in a fixed order: the same
+ *                                bytes on every call and for every chunk length
+ * Frames go up in chunks (TDGL_SAMPLE_CHUNK=<frames>, read at create, fixes the chunk), so the staging buffers stay
+ * bounded whatever n_frames.  Deterministic; no atomics.
+ * TDGL_ERR_ARG (the plan stays usable): n_fields outside 0..2, n_frames < 1, null plan, null edge_values with n_fields
+ * > 0, a requested output whose input is missing: a density or moment with n_fields 0, moment without site_weight,
+ * point_density / point_psi with m = 0, point_psi without psi. */
+int tdgl_sample_plan_eval(tdgl_sample_plan *plan, int32_t n_frames, int32_t n_fields, const double *edge_values,
+                          const double *psi, double *site_density, double *point_density, double *point_psi,
+                          double *moment);
+/* out4 = {points located in a triangle, frames, chunks of frames, kernel launches} of the last call; *last_ms its device
+ * time between the uploads and the read-backs, summed over the chunks (either may be NULL). */
+int tdgl_sample_plan_stats(tdgl_sample_plan *plan, int64_t *out4, double *last_ms);
+/* The location alone on the host, no GPU needed: the same grid and the same per-point search as the plan's kernel
+ * (csrc/sample_grid.h).  TDGL_ERR_ARG as for create. */
+int tdgl_host_sample_locate(int64_t n_sites, const double *sites_xy, int64_t n_tri, const int32_t *elements, int64_t m,
+                            const double *points_xy, int32_t *triangle, double *weights);
+
 /* ------------------------------------------------------------------ the time loop */
 /* Start a Runner stage (runner.py:294-297, 315-318): time = 0, stage step = 0.  Runner.dt
  * and the controller state are deliberately NOT reset. */

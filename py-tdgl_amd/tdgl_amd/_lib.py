@@ -420,6 +420,16 @@ SIGNATURES = {
     "tdgl_vortex_plan_find": (
         C.c_int, [C.c_void_p, C.c_int32, c_f64p, C.c_int64, c_i64p, c_i32p, c_f64p, c_i32p]),
     "tdgl_vortex_plan_stats": (C.c_int, [C.c_void_p, c_i64p, c_f64p]),
+    # currents between the sites (csrc/sample.inc); the plan is an opaque pointer
+    "tdgl_sample_plan_create": (
+        C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, c_f64p, c_f64p, c_f64p, C.c_int64, c_i32p, c_f64p, C.c_int64,
+                  c_i32p, C.c_int64, c_f64p]),
+    "tdgl_sample_plan_destroy": (None, [C.c_void_p]),
+    "tdgl_sample_plan_location": (C.c_int, [C.c_void_p, c_i32p, c_f64p]),
+    "tdgl_sample_plan_eval": (
+        C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "tdgl_sample_plan_stats": (C.c_int, [C.c_void_p, c_i64p, c_f64p]),
+    "tdgl_host_sample_locate": (C.c_int, [C.c_int64, c_f64p, C.c_int64, c_i32p, C.c_int64, c_f64p, c_i32p, c_f64p]),
     "tdgl_get_step_stats": (C.c_int, [_CTX, C.POINTER(C.c_int64), C.c_int32]),
     "tdgl_get_edge_current_launches": (C.c_int, [_CTX, C.POINTER(C.c_int64), C.c_int32]),
     "tdgl_get_direct_stats": (C.c_int, [_CTX, c_f64p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

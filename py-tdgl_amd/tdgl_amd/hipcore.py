@@ -1899,3 +1899,113 @@ class VortexPlan:
             self.close()
         except Exception:
             pass
+
+
+def host_sample_locate(sites_xy, elements, points_xy):
+    """``tdgl_host_sample_locate``: ``(triangle [m] int32, weights [m, 3])`` of the points on the triangulation, on the
+    host (no GPU needed): the lowest-numbered triangle whose barycentric coordinates are all >= -1e-12, or -1."""
+    sites_xy, points_xy = f64(sites_xy), f64(np.asarray(points_xy, dtype=float).reshape(-1, 2))
+    elements = i32(np.asarray(elements).reshape(-1, 3))
+    if sites_xy.ndim != 2 or sites_xy.shape[1] != 2:
+        raise ValueError(f"Expected sites [n, 2] (got {sites_xy.shape}).")
+    triangle = np.empty(len(points_xy), dtype=np.int32)
+    weights = np.empty((len(points_xy), 3))
+    _lib.check(_lib.load().tdgl_host_sample_locate(len(sites_xy), p_f64(sites_xy), len(elements), p_i32(elements),
+                                                   len(points_xy), p_f64(points_xy), p_i32(triangle), p_f64(weights)))
+    return triangle, weights
+
+
+class SamplePlan:
+    """Owns one ``tdgl_sample_plan`` (csrc/sample.inc): the sites, the edges with their unit directions, the triangles
+    and ``m`` fixed points (located once, at construction) kept on the device; :meth:`eval` returns, for a batch of
+    frames, the edge -> site densities, their values and psi's at the points and the dipole moments.  ``weights`` [n] with
+    ``centre`` (x, y) enable the moments.  No physical prefactor.  Needs no ``TDGLContext``.  A context manager; freed on
+    ``__del__`` too."""
+
+    def __init__(self, sites_xy, edges, edge_dir, elements, points_xy=None, weights=None, centre=None, device_id=0):
+        _lib.require_gpu()
+        self._lib = _lib.load()
+        self._plan = C.c_void_p()
+        sites_xy = f64(sites_xy)
+        if sites_xy.ndim != 2 or sites_xy.shape[1] != 2:
+            raise ValueError(f"Expected sites [n, 2] (got {sites_xy.shape}).")
+        edges = i32(np.asarray(edges).reshape(-1, 2))
+        edge_dir = f64(edge_dir)
+        if edge_dir.shape != (len(edges), 2):
+            raise ValueError(f"Expected edge directions [{len(edges)}, 2] (got {edge_dir.shape}).")
+        elements = i32(np.asarray(elements).reshape(-1, 3))
+        points_xy = np.zeros((0, 2)) if points_xy is None else f64(np.asarray(points_xy, dtype=float).reshape(-1, 2))
+        if (weights is None) != (centre is None):
+            raise ValueError("weights and centre go together (both or neither).")
+        if weights is not None:
+            weights, centre = f64(weights), f64(centre)
+            if weights.shape != (len(sites_xy),) or centre.shape != (2,):
+                raise ValueError(f"Expected weights [{len(sites_xy)}] and centre [2] (got {weights.shape}, {centre.shape}).")
+        self.n, self.n_edges, self.n_tri, self.m = len(sites_xy), len(edges), len(elements), len(points_xy)
+        self.has_weights = weights is not None
+        _lib.check(self._lib.tdgl_sample_plan_create(
+            C.byref(self._plan), int(device_id), self.n, p_f64(sites_xy), p_f64(weights), p_f64(centre), self.n_edges,
+            p_i32(edges), p_f64(edge_dir), self.n_tri, p_i32(elements), self.m, p_f64(points_xy)))
+
+    def _open(self):
+        if not self._plan.value:
+            raise RuntimeError("SamplePlan is closed.")
+
+    def location(self):
+        """``(triangle [m] int32, weights [m, 3])`` of the plan's points: -1 and zeros where a point is in no triangle."""
+        self._open()
+        triangle = np.empty(self.m, dtype=np.int32)
+        weights = np.empty((self.m, 3))
+        _lib.check(self._lib.tdgl_sample_plan_location(self._plan, p_i32(triangle), p_f64(weights)))
+        return triangle, weights
+
+    def eval(self, edge_values=None, psi=None, site_density=False, point_density=False, point_psi=False, moment=False):
+        """``edge_values``: [F, n_fields, n_edges] (``n_fields`` 1 or 2) or None; ``psi``: [F, n] complex or None.
+        Returns ``(site_density [F, n_fields, n, 2], point_density [F, n_fields, m, 2], point_psi [F, m] complex,
+        moment [F, n_fields])``, ``None`` for what is not asked for."""
+        self._open()
+        frames = None
+        if edge_values is not None:
+            edge_values = f64(edge_values)
+            if edge_values.ndim != 3 or edge_values.shape[2] != self.n_edges:
+                raise ValueError(f"Expected edge values of shape [n_frames, n_fields, {self.n_edges}] (got {edge_values.shape}).")
+            frames = len(edge_values)
+        if psi is not None:
+            psi = c128(psi)
+            if psi.ndim != 2 or psi.shape[1] != self.n or frames not in (None, len(psi)):
+                raise ValueError(f"Expected psi of shape [n_frames, {self.n}] (got {psi.shape}).")
+            frames = len(psi)
+        if frames is None:
+            raise ValueError("Expected edge values, psi or both.")
+        nf = 0 if edge_values is None else edge_values.shape[1]
+        out_site = np.empty((frames, nf, self.n, 2)) if site_density else None
+        out_point = np.empty((frames, nf, self.m, 2)) if point_density else None
+        out_psi = np.empty((frames, self.m), dtype=np.complex128) if point_psi else None
+        out_moment = np.empty((frames, nf)) if moment else None
+        _lib.check(self._lib.tdgl_sample_plan_eval(self._plan, frames, nf, p_f64(edge_values), p_f64(psi), p_f64(out_site),
+                                                   p_f64(out_point), p_f64(out_psi), p_f64(out_moment)))
+        return out_site, out_point, out_psi, out_moment
+
+    def stats(self) -> dict:
+        """Of the last call: points located in a triangle, frames, chunks of frames, kernel launches, and the device
+        time in milliseconds between the uploads and the read-backs."""
+        out, ms = (C.c_int64 * 4)(), C.c_double(0)
+        _lib.check(self._lib.tdgl_sample_plan_stats(self._plan, out, C.byref(ms)))
+        return dict(located=out[0], frames=out[1], chunks=out[2], launches=out[3], last_ms=ms.value)
+
+    def close(self):
+        if getattr(self, "_plan", None) is not None and self._plan.value:
+            self._lib.tdgl_sample_plan_destroy(self._plan)
+            self._plan = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

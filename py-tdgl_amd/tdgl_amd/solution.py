@@ -408,7 +408,20 @@ class Solution:
         return float(j[crossing].sum())
 
     # -- between the sites --------------------------------------------------------------------------
-    def _interpolator(self, method: str):
+    def _sampler(self, sampler, positions):
+        """``sampler`` kept open by the caller (left open), or a one-shot `tdgl_amd.CurrentSampler` for these positions
+        on ``options.device_id``."""
+        from contextlib import nullcontext
+
+        from .sampling import CurrentSampler
+
+        if sampler is not None:
+            return nullcontext(sampler)
+        positions = None if positions is None else np.atleast_2d(positions)
+        return CurrentSampler(self.device, positions, device_id=getattr(self.options, "device_id", 0))
+
+    @staticmethod
+    def _check_method(method: str) -> None:
         valid_methods = ("linear", "cubic")
         if method not in valid_methods:
             raise ValueError(f"Interpolation method must be one of {valid_methods} (got {method}).")
@@ -416,6 +429,9 @@ class Solution:
             raise NotImplementedError(
                 "Cubic interpolation (matplotlib's CubicTriInterpolator in the reference) is not provided; "
                 "use method='linear'.")
+
+    def _interpolator(self, method: str):
+        self._check_method(method)
         if self._interp is None:
             from .triinterp import TriLinearInterpolator
 
@@ -438,11 +454,21 @@ class Solution:
 
     def interp_current_density(self, positions: np.ndarray, *, dataset: Union[str, None] = None,
                                method: str = "linear", units: Union[str, None] = None,
-                               with_units: bool = False) -> np.ndarray:
+                               with_units: bool = False, backend: str = "host", sampler=None) -> np.ndarray:
         """Sheet current density at arbitrary points (solution.py:364-429): piecewise-linear between
         the site values; zero outside the film and inside holes.  ``dataset``: ``None`` (total),
         ``"supercurrent"`` or ``"normal_current"``.  In ``units`` (default
-        ``current_units / length_units``)."""
+        ``current_units / length_units``).  ``backend``: ``"host"`` (NumPy) or ``"hip"`` (csrc/sample.inc through
+        ``sampler``, a `tdgl_amd.CurrentSampler` opened on these positions, or one opened for this call on
+        ``options.device_id``; needs a GPU, never chosen automatically)."""
+        if _check_backend(backend) == "hip":
+            self._check_method(method)
+            self._density_factor(units)
+            with self._sampler(sampler, positions) as s:
+                J = s.current_density(self, dataset=dataset, units=units)
+            if with_units:
+                return Quantity(J, units or f"{self.current_units} / {self.device.length_units}")
+            return J
         if dataset is None:
             J = self.current_density
         elif dataset == "supercurrent":
@@ -460,22 +486,35 @@ class Solution:
             return Quantity(J, units or f"{self.current_units} / {self.device.length_units}")
         return J
 
-    def interp_order_parameter(self, positions: np.ndarray, method: str = "linear") -> np.ndarray:
-        """psi at arbitrary points (solution.py:431-462); NaN outside the mesh."""
+    def interp_order_parameter(self, positions: np.ndarray, method: str = "linear", *, backend: str = "host",
+                               sampler=None) -> np.ndarray:
+        """psi at arbitrary points (solution.py:431-462); NaN outside the mesh.  ``backend`` and ``sampler`` as for
+        :meth:`interp_current_density`."""
+        if _check_backend(backend) == "hip":
+            self._check_method(method)
+            with self._sampler(sampler, positions) as s:
+                return s.order_parameter(self)
         interp = self._interpolator(method)
         return interp(self.tdgl_data.psi, np.atleast_2d(positions))
 
     def current_through_path(self, path_coords: np.ndarray, dataset: Union[str, None] = None,
-                             method: str = "linear", units: Union[str, None] = None, with_units: bool = True):
+                             method: str = "linear", units: Union[str, None] = None, with_units: bool = True, *,
+                             backend: str = "host", sampler=None):
         """Total current crossing a path (solution.py:623-667): the interpolated current density,
         averaged over each path segment, dotted into the segment's normal ``(dy, -dx)/|d|``, times the
         segment length, for the segments whose centres lie in the device, accumulated with the
         trapezoid rule as the reference does (``np.trapz`` of the per-segment currents).  In
-        ``units`` (default ``current_units``)."""
+        ``units`` (default ``current_units``).  ``backend`` and ``sampler`` as for :meth:`interp_current_density`
+        (the sampler's positions are the path)."""
         from .device import CURRENT_UNITS, _unit
         from .geometry import path_vectors
 
         path_coords = np.asarray(path_coords, dtype=float)
+        if _check_backend(backend) == "hip":
+            self._check_method(method)
+            with self._sampler(sampler, path_coords) as s:
+                total = s.path_current(self, dataset=dataset, units=units)
+            return Quantity(total, units or self.current_units) if with_units else total
         J = self.interp_current_density(path_coords, dataset=dataset, method=method)
         centres = (path_coords[:-1] + path_coords[1:]) / 2
         J_edge = (J[:-1] + J[1:]) / 2
@@ -488,11 +527,17 @@ class Solution:
             total *= CURRENT_UNITS[self.current_units] / _unit(CURRENT_UNITS, units, "current")
         return Quantity(total, units or self.current_units) if with_units else total
 
-    def magnetic_moment(self, units: Union[str, None] = None, with_units: bool = True):
+    def magnetic_moment(self, units: Union[str, None] = None, with_units: bool = True, *, backend: str = "host",
+                        sampler=None):
         """z component of the dipole moment, (1/2) sum_i (r_i - r_cm) x K_i a_i (solution.py:259-289),
-        in ``current_units * length_units**2``."""
+        in ``current_units * length_units**2``.  ``backend`` and ``sampler`` as for :meth:`interp_current_density`
+        (any sampler of this device will do: the moment needs no positions)."""
         if units is not None:
             raise NotImplementedError("magnetic_moment: unit conversion is not provided; pass units=None.")
+        if _check_backend(backend) == "hip":
+            with self._sampler(sampler, None) as s:
+                m = s.magnetic_moment(self)
+            return Quantity(m, f"{self.current_units} * {self.device.length_units}**2") if with_units else m
         mesh, xi = self.device.mesh, self.device.coherence_length
         com = (mesh.sites * mesh.areas[:, None]).sum(axis=0) / mesh.areas.sum()
         r = xi * (mesh.sites - com[None, :])
