@@ -99,6 +99,7 @@ class OracleSolver:
             self._inv_r_area = screening["areas"][None, :] / np.sqrt((d**2).sum(axis=2))
             self.A_induced = np.zeros_like(np.asarray(link_exponents, dtype=float))
             self.last_screening_iterations = 0
+            self.last_screening_errors = []  # the relative change after every iteration of the last step
         self.current_A = np.asarray(link_exponents, dtype=float)
         self.edge_unit = mesh.edge_mesh.directions / np.linalg.norm(
             mesh.edge_mesh.directions, axis=1)[:, None]
@@ -217,7 +218,7 @@ class OracleSolver:
         sc = self.screening
         alpha, beta = sc["step_size"], sc["step_drag"]
         A_ind, velocity = self.A_induced, 0.0
-        error = np.inf
+        error, errors = np.inf, []
         dt = self.tentative_dt
         for it in itertools.count():
             if error < sc["tolerance"]:
@@ -239,7 +240,9 @@ class OracleSolver:
             A_ind = A_ind + velocity
             denom = np.maximum(np.linalg.norm(A_ind, axis=1), 1e-20)
             error = float(np.max(np.linalg.norm(dA, axis=1) / denom))
+            errors.append(error)
         self.A_induced = A_ind
+        self.last_screening_errors = errors
         self.last_screening_iterations = it
         return psi, new_sq, dt, mu, js, jn
 
