@@ -4,7 +4,10 @@ A 6 x 3 um film with a round hole is solved in a perpendicular field strong enou
 `tdgl.VortexFinder` keeps the mesh and the boundary loops on the device and finds, for all saved steps in one call, the
 mesh triangles around which psi winds (with the position of the zero of psi inside each) and the winding around the
 film's rim and around the hole.  Per step one line: the time, the number of cores by sign, the windings, and the check
-that the cores account for them: sum of charges = winding(film) - winding(hole).
+that the cores account for them: sum of charges = winding(film) - winding(hole).  Then `finder.tracks` links the cores
+of consecutive steps into tracks, also on the device, and every track gets one line: its charge, its first and last
+time, its length, how it started and ended (through which boundary loop, or with which other track as a pair) and its
+mean speed.
 Run on an MI355X:  python examples/vortex_tracks.py [field_mT]
 """
 import os
@@ -32,6 +35,10 @@ with tdgl.VortexFinder(device, device_id=options.device_id) as finder:
     windings = finder.windings(solution.saved_steps)
     print(f"{len(frames)} saved steps of {len(device.points)} sites, {len(device.triangles)} triangles: "
           f"{finder.stats()['last_ms']:.3f} ms on the device for the windings of all of them")
+    # the same cores linked from step to step: a vortex moves by less than `reach` between two saved steps
+    reach = 6 * 0.12
+    tracks = finder.tracks(solution.saved_steps, max_distance=reach)
+    print(f"{finder.link_stats()['links']} links into {len(tracks)} tracks: {finder.link_stats()['last_ms']:.3f} ms on the device")
 
 for time, cores, w in zip(solution.times, frames, windings):
     plus, minus = int(np.sum(cores.charges > 0)), int(np.sum(cores.charges < 0))
@@ -46,3 +53,15 @@ last = frames[-1]
 np.save("vortex_cores.npy", np.column_stack([last.positions, last.charges]))
 print(f"cores of the last step (x, y in {device.length_units}, charge) -> vortex_cores.npy; the host backend agrees: "
       f"{np.array_equal(solution.vortices().triangles, last.triangles)}")
+
+print(f"tracks (max_distance {reach:.2f} {device.length_units}): charge, first .. last time, steps, start -> end, mean speed")
+def told(event):
+    if event.kind == "pair":
+        return f"pair with track {event.partner}"
+    return f"{event.kind} ({event.loop})" if event.kind == "boundary" else event.kind
+
+
+for k, track in enumerate(tracks):
+    speed = np.hypot(*track.velocities.T).mean() if len(track.velocities) else 0.0
+    print(f"track {k:3d}: {track.charge:+d}, t = {track.times[0]:7.2f} .. {track.times[-1]:7.2f} tau_0, {len(track.times):3d} steps, "
+          f"{told(track.start)} -> {told(track.end)}, {speed:.4f} {device.length_units}/tau_0")

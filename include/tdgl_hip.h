@@ -830,6 +830,30 @@ int tdgl_vortex_plan_find(tdgl_vortex_plan *plan, int32_t n_frames, const double
 /* out4 = {charged triangles found, frames, chunks of frames, kernel launches} of the last call; *last_ms its device
  * time between the uploads of psi and the read-back, summed over the chunks (either may be NULL). */
 int tdgl_vortex_plan_stats(tdgl_vortex_plan *plan, int64_t *out4, double *last_ms);
+/* Tracks ("Tracks"): the cores of n_frames frames linked from each frame to the next.  Host arrays
+ * in, host arrays out.  counts[f] cores of frame f, in the order of tdgl_vortex_plan_find; xy [total][2] and charges
+ * [total] (+1 / -1) of all frames one after the other; r2 = max_distance * max_distance, rounded once.
+ *   d2(a, b) = (dx * dx) + (dy * dy), dx = b.x - a.x, dy = b.y - a.y, every operation rounded on its own.
+ *   nearest(a; B, accept): the lowest index j of B with accept(j), d2(a, B[j]) <= r2 and d2 minimal, or -1: a scan in
+ *   index order with a strict <, starting from +inf, so a d2 that is NaN or +inf (a non-finite coordinate) is never taken.
+ * Every output has one entry per core, indices count within a frame, -1 is "none"; any output may be NULL, and work
+ * that no output needs is not launched:
+ *   next[i] = j, prev[j] = i   where j = nearest(i; frame f + 1, same charge) and i = nearest(j; frame f, same charge)
+ *   end_partner[i]             ends are the cores of a frame but the last with next == -1; p(i) = nearest(i; ends of
+ *                              the same frame, opposite charge); end_partner[i] = p(i) where p(p(i)) == i
+ *   start_partner[i]           the same among the cores of a frame but the first with prev == -1
+ *   near[i], near_d2[i]        nearest(i; the plan's loop_sites in their order, every one accepted, no radius) and its
+ *                              d2; -1 and +inf for a plan without loops or a core with a non-finite position
+ * The cost is all pairs, counts[f] * counts[f + 1] per pair of frames and direction (meant for up to ~10^4 cores per frame).
+ * TDGL_ERR_ARG (the plan stays usable): null plan / counts, null xy / charges with a total above 0, n_frames < 1, a
+ * negative count, a total of 2^31 or more, a charge other than +-1, max_distance negative or not finite. */
+int tdgl_vortex_plan_link(tdgl_vortex_plan *plan, int32_t n_frames, const int64_t *counts, const double *xy,
+                          const int32_t *charges, double max_distance, int32_t *next, int32_t *prev,
+                          int32_t *end_partner, int32_t *start_partner, int32_t *near, double *near_d2);
+/* out4 = {links (next != -1), frames, pairs of points evaluated, kernel launches} of the last tdgl_vortex_plan_link;
+ * *last_ms its device time between the upload of the records and the read-back (either may be NULL).  Apart from
+ * tdgl_vortex_plan_stats, which stays that of the last find. */
+int tdgl_vortex_plan_link_stats(tdgl_vortex_plan *plan, int64_t *out4, double *last_ms);
 
 /* ------------------------------------------------------------------ currents between the sites (post-processing) */
 /* Sheet current densities on the sites, values between the sites and the dipole moment of saved steps, for many frames

@@ -420,6 +420,10 @@ SIGNATURES = {
     "tdgl_vortex_plan_find": (
         C.c_int, [C.c_void_p, C.c_int32, c_f64p, C.c_int64, c_i64p, c_i32p, c_f64p, c_i32p]),
     "tdgl_vortex_plan_stats": (C.c_int, [C.c_void_p, c_i64p, c_f64p]),
+    "tdgl_vortex_plan_link": (
+        C.c_int, [C.c_void_p, C.c_int32, c_i64p, c_f64p, c_i32p, C.c_double, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p,
+                  c_f64p]),
+    "tdgl_vortex_plan_link_stats": (C.c_int, [C.c_void_p, c_i64p, c_f64p]),
     # currents between the sites (csrc/sample.inc); the plan is an opaque pointer
     "tdgl_sample_plan_create": (
         C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int64, c_f64p, c_f64p, c_f64p, C.c_int64, c_i32p, c_f64p, C.c_int64,

@@ -1883,6 +1883,33 @@ class VortexPlan:
         _lib.check(self._lib.tdgl_vortex_plan_stats(self._plan, out, C.byref(ms)))
         return dict(found=out[0], frames=out[1], chunks=out[2], launches=out[3], last_ms=ms.value)
 
+    def link(self, counts, xy, charges, max_distance):
+        """``tdgl_vortex_plan_link``: the cores of ``len(counts)`` frames (``counts[f]`` cores each, ``xy`` [total, 2]
+        and ``charges`` [total] of all frames one after the other) linked from each frame to the next by mutual nearest
+        neighbour of equal charge within ``max_distance``.  Returns ``(next, prev, end_partner, start_partner, near,
+        near_d2)``, one entry per core: int32 indices within the neighbouring (for the partners: the same) frame or -1,
+        ``near`` the position of the nearest loop site in the plan's concatenated loops with ``near_d2`` its squared
+        distance (-1 and inf without loops).  The rule is DESIGN.md section 3, "Tracks"."""
+        if not self._plan.value:
+            raise RuntimeError("VortexPlan is closed.")
+        counts = np.ascontiguousarray(np.asarray(counts).reshape(-1), dtype=np.int64)
+        total = int(counts.sum()) if len(counts) and counts.min() >= 0 else 0
+        xy = f64(np.asarray(xy, dtype=float).reshape(-1, 2))
+        charges = i32(np.asarray(charges).reshape(-1))
+        if counts.min(initial=0) >= 0 and (len(xy) != total or len(charges) != total):
+            raise ValueError(f"Expected xy [{total}, 2] and charges [{total}] for these counts (got {xy.shape}, {charges.shape}).")
+        out = [np.full(total, -1, dtype=np.int32) for _ in range(5)] + [np.full(total, np.inf)]
+        _lib.check(self._lib.tdgl_vortex_plan_link(self._plan, len(counts), p_i64(counts), p_f64(xy), p_i32(charges),
+                                                   float(max_distance), *[p_i32(a) for a in out[:5]], p_f64(out[5])))
+        return tuple(out)
+
+    def link_stats(self) -> dict:
+        """Of the last :meth:`link`: links made, frames, pairs of points evaluated, kernel launches, and the device time
+        in milliseconds between the upload of the records and the read-back.  :meth:`stats` stays that of the last find."""
+        out, ms = (C.c_int64 * 4)(), C.c_double(0)
+        _lib.check(self._lib.tdgl_vortex_plan_link_stats(self._plan, out, C.byref(ms)))
+        return dict(links=out[0], frames=out[1], pairs=out[2], launches=out[3], last_ms=ms.value)
+
     def close(self):
         if getattr(self, "_plan", None) is not None and self._plan.value:
             self._lib.tdgl_vortex_plan_destroy(self._plan)

@@ -19,6 +19,11 @@ the host functions here and the kernels of csrc/vortices.inc agree bit for bit):
 
 ``Solution.vortices`` / ``Solution.boundary_windings`` use the host functions by default and :class:`VortexFinder`
 (`hipcore.VortexPlan`) with ``backend="hip"``; a finder kept open serves every saved step of a run in one call.
+
+Tracks ("Tracks"): :func:`track_vortices` / `VortexFinder.tracks` link the cores of consecutive
+frames by mutual nearest neighbour of equal charge within ``max_distance`` and explain every start and end of a track
+as a pair event, a passage through a boundary loop, the edge of the call or nothing (:class:`VortexTracks`).
+:func:`link_frames` is the rule in NumPy: the host backend, and the model ``tdgl_vortex_plan_link`` equals exactly.
 """
 
 from typing import NamedTuple
@@ -156,6 +161,286 @@ def name_loops(loops, points, polygons) -> dict:
     return named
 
 
+class Links(NamedTuple):
+    """What linking gives, one entry per core of all frames one after the other (indices count within a frame, -1 is
+    "none"): ``next`` / ``prev`` the same vortex in the next / previous frame, ``end_partner`` / ``start_partner`` the
+    core of the same frame it annihilated with / was nucleated with, ``near`` the position of the nearest loop site
+    among the concatenated loops and ``near_d2`` its squared distance."""
+
+    next: np.ndarray
+    prev: np.ndarray
+    end_partner: np.ndarray
+    start_partner: np.ndarray
+    near: np.ndarray
+    near_d2: np.ndarray
+
+
+LINK_BLOCK = 2048  # sources per block of `keyed_nearest` at the most, and
+LINK_ENTRIES = 1 << 22  # entries of a block's distance matrix at the most (32 MiB): never a k x k matrix of a large frame
+
+
+def keyed_nearest(src_xy, src_key, tgt_xy, tgt_key, r2):
+    """For every source the lowest index among the targets whose key equals its own, with ``d2 <= r2`` and ``d2``
+    minimal, and that ``d2``; -1 and inf where there is none.  ``d2 = (dx * dx) + (dy * dy)`` with ``dx = b.x - a.x``,
+    every operation rounded on its own; a ``d2`` that is NaN or inf is never taken."""
+    index = np.full(len(src_xy), -1, dtype=np.int32)
+    best = np.full(len(src_xy), np.inf)
+    if len(tgt_xy) == 0:
+        return index, best
+    rows = max(1, min(LINK_BLOCK, LINK_ENTRIES // len(tgt_xy)))
+    with np.errstate(invalid="ignore", over="ignore"):
+        for lo in range(0, len(src_xy), rows):
+            a, want = src_xy[lo:lo + rows], src_key[lo:lo + rows]
+            dx = tgt_xy[None, :, 0] - a[:, None, 0]
+            dy = tgt_xy[None, :, 1] - a[:, None, 1]
+            d2 = (dx * dx) + (dy * dy)
+            ok = (tgt_key[None, :] == want[:, None]) & (d2 <= r2) & (d2 < np.inf)
+            d2 = np.where(ok, d2, np.inf)
+            arg = d2.argmin(axis=1)  # (the first of equal minima)
+            low = d2[np.arange(len(a)), arg]
+            found = low < np.inf
+            index[lo:lo + rows] = np.where(found, arg, -1)
+            best[lo:lo + rows] = low
+    return index, best
+
+
+def _mutual(mine, theirs):
+    """``mine[i]`` where ``theirs[mine[i]] == i``, else -1."""
+    out = np.full(len(mine), -1, dtype=np.int32)
+    has = np.flatnonzero(mine >= 0)
+    back = has[theirs[mine[has]] == has]
+    out[back] = mine[back]
+    return out
+
+
+def _frame_arrays(frames):
+    """[(positions [k, 2] float, charges [k] int32)] of a list of `Vortices` or of (positions, charges) pairs."""
+    out = []
+    for frame in frames:
+        positions, charges = (frame.positions, frame.charges) if isinstance(frame, Vortices) else frame[:2]
+        positions = np.asarray(positions, dtype=float).reshape(-1, 2)
+        charges = np.asarray(charges).reshape(-1).astype(np.int32)
+        if len(positions) != len(charges):
+            raise ValueError(f"A frame has {len(positions)} positions and {len(charges)} charges.")
+        if np.any(np.abs(charges) != 1):
+            raise ValueError("Charges must be +1 or -1.")
+        out.append((positions, charges))
+    if not out:
+        raise ValueError("Expected at least one frame.")
+    return out
+
+
+def _check_max_distance(max_distance) -> float:
+    r = float(max_distance)
+    if not (r >= 0.0 and np.isfinite(r)):
+        raise ValueError(f"max_distance must be finite and >= 0 (got {max_distance}).")
+    return r
+
+
+def link_frames(frames, max_distance, loop_sites_xy=None) -> Links:
+    """Link the cores of consecutive frames on the host: the rule of DESIGN.md section 3, "Tracks", in NumPy, and the
+    model ``tdgl_vortex_plan_link`` is held to (equal, not close: every decision compares identically rounded doubles).
+
+    ``frames``: a list of :class:`Vortices` or of ``(positions, charges)``; ``loop_sites_xy`` [q, 2]: the coordinates
+    of the boundary loops' sites one loop after the other (``None``: no loops, ``near`` = -1, ``near_d2`` = inf).
+
+    * ``next[i] = j`` and ``prev[j] = i`` where j is i's nearest core of equal charge in the next frame within
+      ``max_distance`` (ties to the lower index) and i is j's in the frame before: mutual nearest neighbour, one-to-one,
+      no gap closing and not the optimal assignment.
+    * ends (``next == -1``, not in the last frame) pair with their mutually nearest end of opposite charge in the same
+      frame: ``end_partner``; likewise starts (``prev == -1``, not in the first frame): ``start_partner``.
+    * ``near`` / ``near_d2``: the nearest loop site of every core, no radius."""
+    frames = _frame_arrays(frames)
+    r = _check_max_distance(max_distance)
+    r2 = r * r
+    nxt = [np.full(len(c), -1, dtype=np.int32) for _, c in frames]
+    prv = [np.full(len(c), -1, dtype=np.int32) for _, c in frames]
+    for f in range(len(frames) - 1):
+        (a, ka), (b, kb) = frames[f], frames[f + 1]
+        fwd, bwd = keyed_nearest(a, ka, b, kb, r2)[0], keyed_nearest(b, kb, a, ka, r2)[0]
+        nxt[f], prv[f + 1] = _mutual(fwd, bwd), _mutual(bwd, fwd)
+    partners = []
+    for link, frames_with in ((nxt, range(len(frames) - 1)), (prv, range(1, len(frames)))):
+        partner = [np.full(len(c), -1, dtype=np.int32) for _, c in frames]
+        for f in frames_with:
+            xy, charge = frames[f]
+            loose = link[f] < 0
+            choice = keyed_nearest(xy, np.where(loose, -charge, 2), xy, np.where(loose, charge, 0), r2)[0]
+            partner[f] = _mutual(choice, choice)
+        partners.append(partner)
+    every = np.concatenate([xy for xy, _ in frames])
+    if loop_sites_xy is None or len(loop_sites_xy) == 0:
+        near, near_d2 = np.full(len(every), -1, dtype=np.int32), np.full(len(every), np.inf)
+    else:
+        targets = np.asarray(loop_sites_xy, dtype=float).reshape(-1, 2)
+        zeros = np.zeros(max(len(every), len(targets)), dtype=np.int32)
+        near, near_d2 = keyed_nearest(every, zeros[:len(every)], targets, zeros[:len(targets)], np.inf)
+    return Links(np.concatenate(nxt), np.concatenate(prv), np.concatenate(partners[0]), np.concatenate(partners[1]),
+                 near, near_d2)
+
+
+class Event(NamedTuple):
+    """How a track starts or ends.  ``kind``: ``"open"`` (the first / last frame of the call), ``"pair"`` (nucleated /
+    annihilated with the track ``partner``), ``"boundary"`` (not a pair and within ``max_distance`` of a site of the
+    loop named ``loop``: entered / left there) or ``"unexplained"``.  ``distance``: to the partner's core for a pair,
+    to the nearest loop site for ``"boundary"`` and ``"unexplained"`` (inf without loops), ``None`` for ``"open"``."""
+
+    kind: str
+    partner: object
+    loop: object
+    distance: object
+
+
+class Track(NamedTuple):
+    """One vortex followed through consecutive frames: ``charge``, ``frame_indices`` [L], ``core_indices`` [L] (index in
+    the frame's `Vortices`), ``positions`` [L, 2], ``triangles`` [L], ``times`` [L] (empty when none were given),
+    ``velocities`` [L - 1, 2] = delta r / delta t (empty without times), ``rim_distance`` [L] to the nearest loop site,
+    ``start`` and ``end`` (:class:`Event`)."""
+
+    charge: int
+    frame_indices: np.ndarray
+    core_indices: np.ndarray
+    positions: np.ndarray
+    triangles: np.ndarray
+    times: np.ndarray
+    velocities: np.ndarray
+    rim_distance: np.ndarray
+    start: Event
+    end: Event
+
+
+class VortexTracks:
+    """The cores of a sequence of frames linked into tracks.  ``frames``: the list of :class:`Vortices`; ``times`` [F]
+    or ``None``; ``next`` / ``prev``: per frame, the index of the same vortex in the next / previous frame or -1;
+    ``links``: the raw :class:`Links`; ``tracks``: the list of :class:`Track`, numbered by (first frame, index in it) of
+    their first core; ``track_of``: per frame, the track number of every core.  ``loops``: ``{name: site indices}`` the
+    positions ``links.near`` count through, for the events' loop names."""
+
+    def __init__(self, frames, links, max_distance, times=None, loops=None):
+        self.frames = list(frames)
+        self.links = links
+        self.max_distance = _check_max_distance(max_distance)
+        counts = np.array([len(v.charges) for v in self.frames], dtype=np.int64)
+        offset = np.concatenate([[0], np.cumsum(counts)])
+        total = int(offset[-1])
+        if any(len(a) != total for a in links):
+            raise ValueError(f"The links are not those of these frames ({total} cores).")
+        if times is not None:
+            times = np.asarray(times, dtype=float).reshape(-1)
+            if len(times) != len(self.frames):
+                raise ValueError(f"Expected one time per frame ({len(self.frames)}; got {len(times)}).")
+        self.times = times
+        split = lambda a: [a[offset[f]:offset[f + 1]] for f in range(len(counts))]  # noqa: E731
+        self.next, self.prev = split(links.next), split(links.prev)
+        loop_names = list(loops) if loops else []
+        loop_ends = np.cumsum([len(loops[name]) for name in loop_names]) if loop_names else np.zeros(0, dtype=np.int64)
+        frame_of = np.repeat(np.arange(len(counts)), counts)
+        # chains: every core without a predecessor begins one, in (frame, index) order
+        track_of = np.full(total, -1, dtype=np.int64)
+        chains = []
+        for g in np.flatnonzero(links.prev < 0):
+            chain = [int(g)]
+            while links.next[chain[-1]] >= 0:
+                here = chain[-1]
+                chain.append(int(offset[frame_of[here] + 1] + links.next[here]))
+            track_of[chain] = len(chains)
+            chains.append(np.array(chain, dtype=np.int64))
+        self.track_of = split(track_of)
+        xy = np.concatenate([np.asarray(v.positions, dtype=float).reshape(-1, 2) for v in self.frames])
+        charges = np.concatenate([np.asarray(v.charges) for v in self.frames])
+        triangles = np.concatenate([np.asarray(v.triangles) for v in self.frames])
+        rim = np.sqrt(links.near_d2)
+        r2 = self.max_distance * self.max_distance
+
+        def event(g, partner, edge_frame):
+            f = frame_of[g]
+            if f == edge_frame:
+                return Event("open", None, None, None)
+            if partner[g] >= 0:
+                other = offset[f] + partner[g]
+                return Event("pair", int(track_of[other]), None, float(np.hypot(*(xy[other] - xy[g]))))
+            if links.near_d2[g] <= r2:
+                return Event("boundary", None, loop_names[int(np.searchsorted(loop_ends, links.near[g], side="right"))],
+                             float(rim[g]))
+            return Event("unexplained", None, None, float(rim[g]))
+
+        self.tracks = []
+        for chain in chains:
+            frame_indices = frame_of[chain]
+            t = self.times[frame_indices] if self.times is not None else np.zeros(0)
+            positions = xy[chain]
+            velocities = (np.diff(positions, axis=0) / np.diff(t)[:, None]) if self.times is not None else np.zeros((0, 2))
+            self.tracks.append(Track(
+                charge=int(charges[chain[0]]), frame_indices=frame_indices, core_indices=chain - offset[frame_indices],
+                positions=positions, triangles=triangles[chain], times=t, velocities=velocities, rim_distance=rim[chain],
+                start=event(chain[0], links.start_partner, 0), end=event(chain[-1], links.end_partner, len(counts) - 1)))
+
+    def __len__(self):
+        return len(self.tracks)
+
+    def __iter__(self):
+        return iter(self.tracks)
+
+    def __getitem__(self, k):
+        return self.tracks[k]
+
+
+def _psi_frames(x):
+    """(psi [F, n], whether ``x`` was a single frame) of a ``Solution`` (its loaded step), a ``TDGLData``, a list of
+    ``TDGLData`` or an array [n] or [F, n]."""
+    from .solution import Solution, TDGLData
+
+    if isinstance(x, Solution):
+        x = x.tdgl_data
+    if isinstance(x, TDGLData):
+        return np.asarray(x.psi, dtype=complex)[None], True
+    if isinstance(x, (list, tuple)) and all(isinstance(step, TDGLData) for step in x):
+        if not x:
+            raise ValueError("Expected at least one saved step.")
+        x = [np.asarray(step.psi, dtype=complex) for step in x]
+    if isinstance(x, (list, tuple)) and len({np.shape(frame) for frame in x}) > 1:
+        raise ValueError(f"The frames have unequal site counts: {sorted({np.shape(frame) for frame in x})}.")
+    psi = np.asarray(x, dtype=complex)
+    if psi.ndim not in (1, 2):
+        raise TypeError(f"Expected a Solution, a TDGLData, a list of TDGLData or an array [n] or [F, n] (got {type(x)}).")
+    return (psi[None], True) if psi.ndim == 1 else (psi, False)
+
+
+def _track_input(x, times):
+    """(psi [F, n], times [F] or None) for tracking: a ``Solution`` stands for all its saved steps; ``times`` defaults to
+    the saved steps' where ``x`` carries them."""
+    from .solution import Solution, TDGLData
+
+    if isinstance(x, Solution):
+        x = list(x.saved_steps)
+    if times is None and isinstance(x, (list, tuple)) and x and all(isinstance(step, TDGLData) for step in x):
+        times = [step.time for step in x]
+    return _psi_frames(x)[0], times
+
+
+def track_vortices(device, x, max_distance, times=None, backend="host", device_id=0) -> VortexTracks:
+    """The vortex cores of every frame of ``x`` (a ``Solution``: all its saved steps; a list of ``TDGLData``; ``psi``
+    [F, n]) linked into tracks: see :func:`link_frames` for the rule and :class:`VortexTracks` for what comes back.
+    ``max_distance`` (in ``device.length_units``) is how far a vortex may move between two frames; it has no default.
+    ``backend``: ``"host"`` (:func:`host_find` per frame and :func:`link_frames`) or ``"hip"`` (:class:`VortexFinder`;
+    needs a GPU, never falls back).  Both give the same links."""
+    if backend not in ("host", "hip"):
+        raise ValueError(f'backend must be "host" or "hip" (got {backend!r}).')
+    _check_max_distance(max_distance)
+    if backend == "hip":
+        with VortexFinder(device, device_id=device_id) as finder:
+            return finder.tracks(x, max_distance, times=times)
+    psi, times = _track_input(x, times)
+    sites, elements = device.points, device.triangles
+    if psi.shape[1] != len(sites):
+        raise ValueError(f"Expected frames of {len(sites)} sites (got {psi.shape[1]}).")
+    loops = dict(device.boundary_sites() or {})
+    orientations = triangle_orientations(sites, elements)
+    frames = [host_find(frame, sites, elements, orientations) for frame in psi]
+    loop_xy = np.asarray(sites, dtype=float)[np.concatenate([np.asarray(l) for l in loops.values()])] if loops else None
+    return VortexTracks(frames, link_frames(frames, max_distance, loop_xy), max_distance, times=times, loops=loops)
+
+
 class VortexFinder:
     """Cores and windings of many saved order parameters on the GPU.  ``loops``: ``{name: site indices}`` of closed
     loops (default: ``device.boundary_sites()``).  A context manager; the device buffers are freed by :meth:`close` or
@@ -174,20 +459,7 @@ class VortexFinder:
 
     def _frames(self, x):
         """(psi [F, n], whether ``x`` was a single frame)."""
-        from .solution import Solution, TDGLData
-
-        if isinstance(x, Solution):
-            x = x.tdgl_data
-        if isinstance(x, TDGLData):
-            return np.asarray(x.psi, dtype=complex)[None], True
-        if isinstance(x, (list, tuple)) and all(isinstance(step, TDGLData) for step in x):
-            if not x:
-                raise ValueError("Expected at least one saved step.")
-            return np.stack([np.asarray(step.psi, dtype=complex) for step in x]), False
-        psi = np.asarray(x, dtype=complex)
-        if psi.ndim not in (1, 2):
-            raise TypeError(f"Expected a Solution, a TDGLData, a list of TDGLData or an array [n] or [F, n] (got {type(x)}).")
-        return (psi[None], True) if psi.ndim == 1 else (psi, False)
+        return _psi_frames(x)
 
     def find(self, x):
         """The cores of a ``Solution``'s loaded step, of a ``TDGLData`` or of ``psi`` [n]: one :class:`Vortices`; of
@@ -207,9 +479,25 @@ class VortexFinder:
         frames = [{name: (None if w == WINDING_UNDEFINED else int(w)) for name, w in zip(self.loops, row)} for row in wind]
         return frames[0] if single else frames
 
+    def tracks(self, x, max_distance, times=None) -> VortexTracks:
+        """The cores of every frame of ``x`` (a ``Solution``: all its saved steps; a list of ``TDGLData``; ``psi``
+        [F, n]) found and linked into tracks on the device: :meth:`find`, then `hipcore.VortexPlan.link`.
+        ``max_distance``: how far a vortex may move between two frames (no default).  ``times`` [F] defaults to the
+        saved steps' where ``x`` carries them; without times the tracks have no velocities."""
+        r = _check_max_distance(max_distance)
+        psi, times = _track_input(x, times)
+        frames = self.find(psi)
+        links = Links(*self.plan.link([len(v.charges) for v in frames], np.concatenate([v.positions for v in frames]),
+                                      np.concatenate([v.charges for v in frames]), r))
+        return VortexTracks(frames, links, r, times=times, loops=self.loops)
+
     def stats(self) -> dict:
         """`hipcore.VortexPlan.stats` of the last call."""
         return self.plan.stats()
+
+    def link_stats(self) -> dict:
+        """`hipcore.VortexPlan.link_stats` of the last :meth:`tracks`."""
+        return self.plan.link_stats()
 
     def close(self):
         plan = getattr(self, "plan", None)

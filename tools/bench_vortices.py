@@ -11,6 +11,13 @@ orientation + 2 t for the charges written and read back) with the rate that give
 
 psi is a lattice of vortices (a product would overflow; the phase is the sum of the cores' angles, the amplitude a
 tanh profile per core) with about one core per 400 sites, so the record stream is what a vortex state gives.
+
+    python tools/bench_vortices.py --link [--reps K] [--out FILE] [cores ...]   # cores per frame (100 / 1000 / 10000)
+
+The link lines alone (`"link": true`), one per number of cores per frame, 32 frames of random clouds each: the device
+time of one `VortexPlan.link` (between the upload of the records and the read-back), its wall time, the wall time of the
+host backend `tdgl_amd.vortices.link_frames` for the same frames on the same box (timed on the first three frames and
+scaled to all of them where all would take minutes; `host_frames_timed` says which) and their ratio.
 """
 import json
 import os
@@ -22,7 +29,7 @@ import numpy as np
 sys.path.insert(0, "tests"); sys.path.insert(0, "py-tdgl_amd"); sys.path.insert(0, ".")
 from helpers import synthetic_mesh  # noqa: E402
 from tdgl_amd.hipcore import VortexPlan  # noqa: E402
-from tdgl_amd.vortices import boundary_loops, host_find, loop_winding, triangle_orientations  # noqa: E402
+from tdgl_amd.vortices import boundary_loops, host_find, link_frames, loop_winding, triangle_orientations  # noqa: E402
 
 args = sys.argv[1:]
 reps, out_path = 3, os.path.join("profiles", "VORTEX_bench.jsonl")
@@ -46,6 +53,59 @@ def vortex_state(sites, n_cores, rng):
         amp *= np.tanh(np.hypot(dx, dy))
     return amp * np.exp(1j * theta)
 
+
+def bench_link(cores, frames=32):
+    """One line for linking `frames` random clouds of `cores` cores each (`VortexPlan.link`): a cloud of mean spacing 4
+    in a square, every core displaced by a Gaussian step of 0.3 from frame to frame, about 2 % of the cores missing per
+    frame, each frame in an order of its own; r = 1.5; the loop is the square's rim at spacing 1."""
+    rng = np.random.default_rng(cores)
+    side = 4.0 * np.sqrt(cores)
+    home = rng.uniform(0, side, size=(cores, 2))
+    charge = rng.choice([-1, 1], size=cores).astype(np.int32)
+    per_frame = []
+    for f in range(frames):
+        home = home + 0.3 * rng.normal(size=home.shape)
+        keep = rng.permutation(cores)[:cores - cores // 50]
+        per_frame.append((home[keep], charge[keep]))
+    counts = [len(c) for _, c in per_frame]
+    xy, charges = np.concatenate([p for p, _ in per_frame]), np.concatenate([c for _, c in per_frame])
+    k = int(np.ceil(side))
+    edge = np.arange(k, dtype=float) * side / k
+    rim = np.concatenate([np.column_stack([edge, 0 * edge]), np.column_stack([0 * edge + side, edge]),
+                          np.column_stack([side - edge, 0 * edge + side]), np.column_stack([0 * edge, side - edge])])
+    sites = np.concatenate([[[0.0, 0.0], [1.0, 0.0], [0.0, 1.0]], rim])
+    with VortexPlan(sites, np.array([[0, 1, 2]], dtype=np.int32), [np.arange(3, len(sites))]) as plan:
+        plan.link(counts, xy, charges, 1.5)  # warm-up: code object, buffers
+        dev_ms, wall_s = [], []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            got = plan.link(counts, xy, charges, 1.5)
+            wall_s.append(time.perf_counter() - t0)
+            dev_ms.append(plan.link_stats()["last_ms"])
+        stats = plan.link_stats()
+    # the host backend on the same box: all frames where that takes seconds, the first three otherwise (scaled by pairs)
+    host_frames = frames if cores <= 1000 else 3
+    t0 = time.perf_counter()
+    host = link_frames(per_frame[:host_frames], 1.5, sites[3:])
+    host_s = time.perf_counter() - t0
+    n_host = sum(counts[:host_frames - 1])
+    assert np.array_equal(host.next[:n_host], got[0][:n_host]) and np.array_equal(host.near[:n_host], got[4][:n_host])
+    ms = float(np.min(dev_ms))
+    host_ms = 1e3 * host_s * (frames - 1) / (host_frames - 1)
+    return dict(link=True, cores_per_frame=cores, frames=frames, reps=reps, loop_sites=len(rim), links=stats["links"],
+                pairs=stats["pairs"], launches=stats["launches"], device_ms=ms, device_ms_mean=float(np.mean(dev_ms)),
+                wall_ms=1e3 * float(np.min(wall_s)), host_frames_timed=host_frames, host_wall_ms=host_ms,
+                host_over_wall=host_ms / (1e3 * float(np.min(wall_s))), device_gpairs_per_s=stats["pairs"] / (ms * 1e-3) / 1e9)
+
+
+if "--link" in args:  # the link lines alone:  --link [cores per frame ...]
+    args.remove("--link")
+    for cores in [int(a) for a in args] or [100, 1000, 10000]:
+        line = bench_link(cores)
+        print(json.dumps(line), flush=True)
+        with open(out_path, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    sys.exit(0)
 
 for L in [int(a) for a in args] or [70, 460, 920]:
     mesh = synthetic_mesh(L)
