@@ -719,6 +719,20 @@ int tdgl_host_currents_replay(int32_t plan, const tdgl_currents_facts *facts, co
                               int64_t n_attempts, const double *dmax, const int32_t *fail, int32_t batch, int32_t mode,
                               int64_t n_actions, const int64_t *action_at, const int32_t *action_kind, int64_t *formed_at,
                               tdgl_currents_replay *res);
+/* Host-only: a sequence of accepted steps -- step i changes |psi|^2 by at most dmax[i] and would cost iters[i] PCG
+ * iterations if taken while the direct solve is paused -- played through the time loop's choice between the direct mu
+ * solve and AMG-PCG (tdgl_direct_switching) from a fresh tdgl_direct_switching(ctx, 1): the decision in front of every
+ * step, the step's note behind it, as tdgl_run makes them.  reset_at [n_resets] (strictly ascending, each in 0 .. n - 1; may
+ * be NULL with n_resets = 0): in front of these steps the history is dropped first, as tdgl_set_state, tdgl_begin_stage,
+ * tdgl_set_mu_boundary and tdgl_set_epsilon drop it.  paused [n]: 1 where step i ran with the direct solve paused.  res:
+ * the switches made, the steps the direct solve runs at least before its next pause, and the state at the end.  No device
+ * work. */
+typedef struct {
+    int64_t switches, pause_hold;
+    int32_t paused, pad;
+} tdgl_solver_choice_replay;
+int tdgl_host_solver_choice_replay(int64_t n, const double *dmax, const int32_t *iters, int64_t n_resets,
+                                   const int64_t *reset_at, int32_t *paused, tdgl_solver_choice_replay *res);
 /* Host-only: the block low-rank compression of one B x B block A (row major) -- column-pivoted, reorthogonalised
  * Gram-Schmidt until the Frobenius norm of the remainder is <= tol; A ~ Q W^T with Q, W [kmax * B] column by column.
  * Returns the rank, or -1 when kmax columns do not reach tol (-2: bad arguments).  No device work. */

@@ -104,13 +104,9 @@ extern "C" int tdgl_set_halo_plan(tdgl_ctx *ctx, const tdgl_halo_plan *p) {
     HIP_TRY(ctx, ctx->d_send_idx.upload(idx.empty() ? std::vector<int32_t>(1, 0) : idx));
     HIP_TRY(ctx, ctx->d_sendbuf.alloc(std::max<int64_t>(2 * n_send, 2)));
     HIP_TRY(ctx, ctx->d_gstat.alloc(2));
-    if (ctx->h_sendbuf) (void)hipHostFree(ctx->h_sendbuf);
-    if (ctx->h_recvbuf) (void)hipHostFree(ctx->h_recvbuf);
-    ctx->h_sendbuf = ctx->h_recvbuf = nullptr;
-    const size_t hbytes = sizeof(double) * std::max<int64_t>({2 * n_send, 2 * n_recv, (int64_t)NB, 16});
-    HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_sendbuf), hbytes));
-    HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_recvbuf), hbytes));
-    ctx->h_buf_doubles = (int64_t)(hbytes / sizeof(double));
+    const size_t hdoubles = (size_t)std::max<int64_t>({2 * n_send, 2 * n_recv, (int64_t)NB, 16});
+    HIP_TRY(ctx, ctx->h_sendbuf.alloc(hdoubles, false));
+    HIP_TRY(ctx, ctx->h_recvbuf.alloc(hdoubles, false));
     // Longest prefix of owned rows without a ghost neighbour (partition.py numbers the interior
     // sites first): those rows can be processed while a halo exchange is in flight.
     {
@@ -237,11 +233,8 @@ extern "C" int tdgl_set_deep_halo_plan(tdgl_ctx *ctx, const tdgl_deep_halo_plan 
     HIP_TRY(ctx, ctx->d_deep_recv_idx.upload(ri));
     HIP_TRY(ctx, ctx->d_deep_sendbuf.alloc(std::max<int64_t>(n_send, 2)));
     HIP_TRY(ctx, ctx->d_deep_recvbuf.alloc(std::max<int64_t>(n_recv, 2)));
-    if (ctx->h_deep_send) (void)hipHostFree(ctx->h_deep_send);
-    if (ctx->h_deep_recv) (void)hipHostFree(ctx->h_deep_recv);
-    ctx->h_deep_send = ctx->h_deep_recv = nullptr;
-    HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_deep_send), sizeof(double) * std::max<int64_t>(n_send, 2)));
-    HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_deep_recv), sizeof(double) * std::max<int64_t>(n_recv, 2)));
+    HIP_TRY(ctx, ctx->h_deep_send.alloc((size_t)std::max<int64_t>(n_send, 2), false));
+    HIP_TRY(ctx, ctx->h_deep_recv.alloc((size_t)std::max<int64_t>(n_recv, 2), false));
     ctx->n_ext = p->n_ext;
     ctx->l1_interior = std::max<int64_t>(0, p->l1_interior);
     ctx->deep = true;
@@ -280,14 +273,14 @@ static int comm_halo_deep(tdgl_ctx *ctx, double *v, int split_phase = 0) {
         NCCL_TRY(ctx, ncclGroupEnd());
     } else {
         if (n_send > 0)
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_deep_send, ctx->d_deep_sendbuf.p, n_send * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->h_deep_send.p, ctx->d_deep_sendbuf.p, n_send * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         std::vector<int64_t> so(ctx->deep_send_ptr.begin(), ctx->deep_send_ptr.end()), ro(ctx->deep_recv_ptr.begin(), ctx->deep_recv_ptr.end());
-        if (ctx->cb_halo(ctx->cb_user, ctx->h_deep_send, so.data(), ctx->h_deep_recv, ro.data(), (int32_t)ctx->deep_nbrs.size(),
+        if (ctx->cb_halo(ctx->cb_user, ctx->h_deep_send.p, so.data(), ctx->h_deep_recv.p, ro.data(), (int32_t)ctx->deep_nbrs.size(),
                          ctx->deep_nbrs.data()) != 0)
             TDGL_FAIL(ctx, TDGL_ERR_HIP, "halo exchange callback failed");
         if (n_recv > 0)
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_deep_recvbuf.p, ctx->h_deep_recv, n_recv * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_deep_recvbuf.p, ctx->h_deep_recv.p, n_recv * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     }
     if (n_recv > 0)
         hipLaunchKernelGGL(k_halo_unpack, dim3(grid_for(n_recv)), dim3(BLOCK), 0, ctx->stream, n_recv, (const int32_t *)ctx->d_deep_recv_idx.p,
@@ -325,17 +318,17 @@ static int comm_halo(tdgl_ctx *ctx, double *v, int width) {
         NCCL_TRY(ctx, ncclGroupEnd());
         return TDGL_OK;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_sendbuf, ctx->d_sendbuf.p, n_send * width * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_sendbuf.p, ctx->d_sendbuf.p, n_send * width * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<int64_t> so(ctx->send_ptr.size()), ro(ctx->recv_ptr.size());
     for (size_t k = 0; k < so.size(); ++k) {
         so[k] = (int64_t)ctx->send_ptr[k] * width;
         ro[k] = (int64_t)ctx->recv_ptr[k] * width;
     }
-    if (ctx->cb_halo(ctx->cb_user, ctx->h_sendbuf, so.data(), ctx->h_recvbuf, ro.data(), (int32_t)ctx->nbr_ranks.size(),
+    if (ctx->cb_halo(ctx->cb_user, ctx->h_sendbuf.p, so.data(), ctx->h_recvbuf.p, ro.data(), (int32_t)ctx->nbr_ranks.size(),
                      ctx->nbr_ranks.data()) != 0)
         TDGL_FAIL(ctx, TDGL_ERR_HIP, "halo exchange callback failed");
-    HIP_TRY(ctx, hipMemcpyAsync(ghost, ctx->h_recvbuf, n_recv * width * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ghost, ctx->h_recvbuf.p, n_recv * width * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TDGL_OK;
 }
@@ -371,7 +364,7 @@ static int comm_halo_start(tdgl_ctx *ctx, double *v, int width) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_halo, ctx->comm_stream));
         return TDGL_OK;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_sendbuf, ctx->d_sendbuf.p, n_send * width * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_sendbuf.p, ctx->d_sendbuf.p, n_send * width * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_pack, ctx->stream));
     return TDGL_OK;
 }
@@ -393,12 +386,12 @@ static int comm_halo_wait(tdgl_ctx *ctx) {
         so[k] = (int64_t)ctx->send_ptr[k] * width;
         ro[k] = (int64_t)ctx->recv_ptr[k] * width;
     }
-    if (ctx->cb_halo(ctx->cb_user, ctx->h_sendbuf, so.data(), ctx->h_recvbuf, ro.data(), (int32_t)ctx->nbr_ranks.size(),
+    if (ctx->cb_halo(ctx->cb_user, ctx->h_sendbuf.p, so.data(), ctx->h_recvbuf.p, ro.data(), (int32_t)ctx->nbr_ranks.size(),
                      ctx->nbr_ranks.data()) != 0)
         TDGL_FAIL(ctx, TDGL_ERR_HIP, "halo exchange callback failed");
     // the copy goes through the communication stream so that it does not queue behind the
     // ghost-free kernels; the compute stream then waits for it
-    HIP_TRY(ctx, hipMemcpyAsync(v + ctx->n_own * (int64_t)width, ctx->h_recvbuf, n_recv * width * sizeof(double),
+    HIP_TRY(ctx, hipMemcpyAsync(v + ctx->n_own * (int64_t)width, ctx->h_recvbuf.p, n_recv * width * sizeof(double),
                                 hipMemcpyHostToDevice, ctx->comm_stream));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_halo, ctx->comm_stream));
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));
@@ -418,8 +411,8 @@ static int comm_allreduce(tdgl_ctx *ctx, double *dev, int64_t count, int op) {
         return TDGL_OK;
     }
     std::vector<double> big;
-    double *h = ctx->h_sendbuf;
-    if (count > ctx->h_buf_doubles) {
+    double *h = ctx->h_sendbuf.p;
+    if (count > (int64_t)ctx->h_sendbuf.n) {
         big.resize(count);
         h = big.data();
     }

@@ -1083,8 +1083,8 @@ static int sub_factors_to_precond(tdgl_ctx *ctx, bool fp32_storage, const char *
 static int precond_calibrate(tdgl_ctx *ctx, double *t_apply_us, double *t_vcycle_us) {
     if (precond_f32_on(ctx)) TDGL_TRY(ensure_f32(ctx));
     HIP_TRY(ctx, hipMemsetAsync(ctx->pcg_r.p, 0, ctx->n_pad * sizeof(double), ctx->stream));
-    std::vector<hipEvent_t> ev(18);
-    for (auto &e : ev) HIP_TRY(ctx, hipEventCreate(&e));
+    std::vector<Event> ev(18);
+    for (auto &e : ev) HIP_TRY(ctx, e.create());
     auto median_us = [&](auto &&apply, double *out) -> int {
         for (int rep = 0; rep < 9; ++rep) {
             HIP_TRY(ctx, hipEventRecord(ev[2 * rep], ctx->stream));
@@ -1115,7 +1115,6 @@ static int precond_calibrate(tdgl_ctx *ctx, double *t_apply_us, double *t_vcycle
             return TDGL_OK;
         },
         &ctx->pd_t_vcycle_us));
-    for (auto &e : ev) (void)hipEventDestroy(e);
     HIP_TRY(ctx, hipGetLastError());
     if (t_apply_us) *t_apply_us = ctx->pd_t_apply_us;
     if (t_vcycle_us) *t_vcycle_us = ctx->pd_t_vcycle_us;
@@ -1163,8 +1162,7 @@ extern "C" int tdgl_poisson_set_substructure_precond(tdgl_ctx *ctx, const int32_
     f->xp = std::move(xp);
     f->z = std::move(z);
     TDGL_TRY(sub_factors_to_precond(ctx, fp32_storage != 0, who));
-    ctx->direct_switch_on = false;
-    ctx->direct_paused = false;
+    ctx->choice.enable(false);
     ctx->pcg_epoch += 1;
     return precond_calibrate(ctx, t_apply_us, t_vcycle_us);
 }

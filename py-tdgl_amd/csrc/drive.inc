@@ -481,7 +481,7 @@ extern "C" int tdgl_set_epsilon(tdgl_ctx *ctx, const double *epsilon) {
     if (!epsilon) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_epsilon: null epsilon");
     TDGL_TRY(upload_sites(ctx, epsilon, ctx->eps));
     ctx->have_eps = true;
-    direct_policy_reset(ctx);
+    ctx->choice.reset();
     return TDGL_OK;
 }
 
@@ -503,7 +503,7 @@ extern "C" int tdgl_set_mu_boundary(tdgl_ctx *ctx, const double *mu_boundary) {
     TDGL_TRY(apply_mu_boundary(ctx, mu_boundary));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->mu_tab.applied(mu_boundary, ctx->nb);
-    direct_policy_reset(ctx);
+    ctx->choice.reset();
     return TDGL_OK;
 }
 

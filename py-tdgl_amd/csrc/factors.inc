@@ -201,12 +201,12 @@ static void direct_guard_launch(tdgl_ctx *ctx) {
     hipLaunchKernelGGL(k_store_sum, dim3(1), dim3(BLOCK), 0, ctx->stream, (const double *)(ctx->part_pair[0].p + NB), ctx->scal.p, (int)S_RR, 0.0);
 }
 static inline void direct_guard_fetch(tdgl_ctx *ctx) {  // (queued behind everything that writes the status block)
-    (void)hipMemcpyAsync(ctx->h_status->scal, ctx->scal.p, S_COUNT * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    (void)hipMemcpyAsync(ctx->h_status.p->scal, ctx->scal.p, S_COUNT * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
 }
 // after the synchronisation; `valid`: mu and b belong to the same, accepted, step
 static void direct_guard_read(tdgl_ctx *ctx, bool valid) {
     if (!valid) return;
-    const double bb = ctx->h_status->scal[S_BB], rr = ctx->h_status->scal[S_RR];
+    const double bb = ctx->h_status.p->scal[S_BB], rr = ctx->h_status.p->scal[S_RR];
     if (!(bb > 0.0)) return;
     const double relres = std::isfinite(rr) ? std::sqrt(rr / bb) : INFINITY;
     ctx->direct_checks += 1;
@@ -228,11 +228,10 @@ extern "C" int tdgl_get_direct_stats(tdgl_ctx *ctx, double *relres_max, int64_t 
 extern "C" int tdgl_direct_switching(tdgl_ctx *ctx, int32_t on, int64_t *switches, int32_t *paused) {
     if (!ctx) return TDGL_ERR_ARG;
     if (on >= 0) {
-        ctx->direct_switch_on = on != 0;
-        direct_policy_reset(ctx);
+        ctx->choice.enable(on != 0);
     }
-    if (switches) *switches = ctx->direct_switches;
-    if (paused) *paused = ctx->direct_paused ? 1 : 0;
+    if (switches) *switches = ctx->choice.switches();
+    if (paused) *paused = ctx->choice.paused() ? 1 : 0;
     return TDGL_OK;
 }
 

@@ -163,10 +163,8 @@ static constexpr int64_t FIELD_MAX_BATCH = (int64_t)1 << 20;  // targets per lau
 static constexpr int64_t FIELD_MIN_GROUPS = 2048;             // workgroups a launch should have (the source range is split to get there)
 static constexpr int64_t FIELD_GROUP_TARGETS = (int64_t)FIELD_TPT * BLOCK;
 
-struct tdgl_field_plan {
+struct tdgl_field_plan : tdgl::TimedStream {  // (stream, ev0, ev1)
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int64_t n = 0, m = 0;
     int64_t batch = 0;  // targets per launch
     DevBuf<double> src_xyw, tgt, K, part, S_A, S_z, S_xy;
@@ -186,9 +184,6 @@ extern "C" void tdgl_field_plan_destroy(tdgl_field_plan *plan) {
     if (!plan) return;
     (void)hipSetDevice(plan->device);
     if (plan->stream) (void)hipStreamSynchronize(plan->stream);
-    if (plan->ev0) (void)hipEventDestroy(plan->ev0);
-    if (plan->ev1) (void)hipEventDestroy(plan->ev1);
-    if (plan->stream) (void)hipStreamDestroy(plan->stream);
     delete plan;
 }
 
@@ -212,9 +207,7 @@ extern "C" int tdgl_field_plan_create(tdgl_field_plan **out, int device_id, int6
     plan->device = device_id;
     plan->n = n;
     plan->m = m;
-    HIP_TRY(FIELD_NO_CTX, hipStreamCreate(&plan->stream));
-    HIP_TRY(FIELD_NO_CTX, hipEventCreate(&plan->ev0));
-    HIP_TRY(FIELD_NO_CTX, hipEventCreate(&plan->ev1));
+    HIP_TRY(FIELD_NO_CTX, plan->create());
     std::vector<double> sxyw(3 * n), t(3 * m);
     for (int64_t j = 0; j < n; ++j) {
         sxyw[3 * j] = src_xy[2 * j];

@@ -275,7 +275,7 @@ static int guess_queue_dots(tdgl_ctx *ctx, const double *b) {
 // else NULL (x stays as it is).  `vs` keeps them for the caller.
 static int guess_apply(tdgl_ctx *ctx, VecSet &vs, int grid, double *x, const double **c_used) {
     GuessBasis &g = ctx->guess;
-    g.load_rhs(ctx->h_status, ctx->n_global);
+    g.load_rhs(ctx->h_status.p, ctx->n_global);
     ctx->last_guess_vectors = 0;
     *c_used = nullptr;
     vs.k = g.count;

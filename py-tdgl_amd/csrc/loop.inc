@@ -1,6 +1,7 @@
 // LoopState (tdgl_internal.h): the time loop's rules on the host -- retry (solver.py:475-485), adaptive dt (solver.py:698-707),
 // Runner.dt / time / step (runner.py:429-433) --, once for the classic, the run-ahead and the ensemble loop.  Plain host C++:
-// nothing here touches the device, so the rules can be replayed without one (tdgl_host_loop_replay).  Included by tdgl_hip.hip.
+// nothing here touches the device, so the rules can be replayed without one (tdgl_host_loop_replay).  Beside it the currents'
+// ledger (EdgeCurrents) and the loop's choice of solver (SolverChoice), replayed likewise.  Included by tdgl_hip.hip.
 
 // numpy's pairwise summation (numpy/core/src/umath/loops_utils.h.src, pairwise_sum): a plain
 // left-to-right sum below 8 elements, an 8-accumulator unrolled loop up to 128, and a recursive
@@ -373,7 +374,74 @@ void EdgeCurrents::absorb_batch(int done, int last_accepted, int accepted, bool 
         state = FORMED;
 }
 
+// ---- SolverChoice (tdgl_internal.h): direct <-> iterative mu solve, decided by the state ------------------------------------
+void SolverChoice::reset() {
+    is_paused = false;
+    switch_steps = 0;
+    recent_n = 0;
+    hold = 256;
+    pcg_ema = 0.0;
+    for (double &w : win_max) w = 0.0;
+}
+
+void SolverChoice::note_step(double dmax, int pcg_iters) {
+    if (!on) return;
+    recent_dmax[recent_n % WINDOW] = dmax;
+    recent_n += 1;
+    if (recent_n % WINDOW == 0) {  // a window is complete: its maximum joins the last three
+        double worst = 0.0;
+        for (int i = 0; i < WINDOW; ++i) worst = std::max(worst, recent_dmax[i]);
+        win_max[0] = win_max[1];
+        win_max[1] = win_max[2];
+        win_max[2] = win_max[3];
+        win_max[3] = worst;
+    }
+    switch_steps += 1;
+    if (is_paused) pcg_ema = 0.95 * pcg_ema + 0.05 * (double)pcg_iters;
+}
+
+SolverChoice::Change SolverChoice::decide(bool allowed) {
+    if (!on || !allowed) return NONE;
+    if (!is_paused) {
+        if (switch_steps < hold || recent_n < WINDOW) return NONE;
+        double worst = 0.0;
+        for (int i = 0; i < WINDOW; ++i) worst = std::max(worst, recent_dmax[i]);
+        const double *wm = win_max;
+        const bool relaxing = recent_n >= 4 * WINDOW && wm[3] < RELAX_DMAX && wm[3] < 0.9 * wm[2] && wm[2] < 0.9 * wm[1] && wm[1] < 0.9 * wm[0];
+        if (!(worst < PAUSE_DMAX) && !relaxing) return NONE;
+        is_paused = true;  // stationary or on its way there: the iterative solve takes over
+        pcg_ema = 0.0;
+    } else {
+        if (switch_steps < WINDOW || pcg_ema < RESUME_ITERS) return NONE;
+        is_paused = false;  // the state moves again
+        // (a pause that was worth it -- a plateau of an I-V staircase -- leaves the next one its short wait; one that ended
+        // right away doubles it)
+        hold = switch_steps >= 1024 ? 256 : std::min<int64_t>(2 * hold, 16384);
+    }
+    n_switches += 1;
+    switch_steps = 0;
+    return is_paused ? PAUSED : RESUMED;
+}
+
 }  // namespace tdgl
+
+// Host-only: accepted steps through the time loop's solver choice, see include/tdgl_hip.h
+extern "C" int tdgl_host_solver_choice_replay(int64_t n, const double *dmax, const int32_t *iters, int64_t n_resets,
+                                              const int64_t *reset_at, int32_t *paused, tdgl_solver_choice_replay *res) {
+    if (n < 0 || (n > 0 && (!dmax || !iters || !paused)) || !res || n_resets < 0 || (n_resets > 0 && !reset_at)) return TDGL_ERR_ARG;
+    for (int64_t k = 0; k < n_resets; ++k)
+        if (reset_at[k] < 0 || reset_at[k] >= n || (k > 0 && reset_at[k] <= reset_at[k - 1])) return TDGL_ERR_ARG;
+    tdgl::SolverChoice choice;
+    choice.enable(true);
+    for (int64_t i = 0, k = 0; i < n; ++i) {  // tdgl_run's classic branch: the decision in front of the step, the note behind it
+        if (k < n_resets && reset_at[k] == i) choice.reset(), ++k;
+        (void)choice.decide(true);
+        paused[i] = choice.paused() ? 1 : 0;
+        choice.note_step(dmax[i], iters[i]);
+    }
+    *res = tdgl_solver_choice_replay{choice.switches(), choice.pause_hold(), choice.paused() ? 1 : 0, 0};
+    return TDGL_OK;
+}
 
 // Host-only: a scripted sequence of attempts through the loop's rules, see include/tdgl_hip.h
 extern "C" int tdgl_host_loop_replay(const tdgl_controller *c, double end_time, int64_t n_attempts, const double *dmax,

@@ -227,7 +227,7 @@ extern "C" int tdgl_poisson_set_dense_inverse(tdgl_ctx *ctx, const double *G, in
 // a direct solve is set (the explicit inverse of the whole matrix, or the substructured one)
 // (not while a description is incomplete -- AMG-PCG meanwhile --, nor when the factors precondition the CG)
 static inline bool dense_on(const tdgl_ctx *ctx) {
-    if (ctx->direct_paused) return false;  // (a stationary state: the iterative solve is the cheaper one, see tdgl_direct_switching)
+    if (ctx->choice.paused()) return false;  // (a stationary state: the iterative solve is the cheaper one, see tdgl_direct_switching)
     return ctx->direct && ctx->direct->stage == DirectFactors::READY && !distributed(ctx);
 }
 
@@ -465,7 +465,7 @@ struct NoShadow {
 template <class S>
 static int sync_status(tdgl_ctx *ctx, bool guard, S shadow) {
     constexpr bool shadowed = !std::is_same<S, NoShadow>::value;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status, ctx->d_status.p, sizeof(StepStatus), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status.p, ctx->d_status.p, sizeof(StepStatus), hipMemcpyDeviceToHost, ctx->stream));
     if (guard) direct_guard_fetch(ctx);
     if (shadowed) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev_status, ctx->stream));
@@ -522,15 +522,15 @@ static int direct_mu_solve(tdgl_ctx *ctx, MuSolveArgs &args, F after_first_sync,
     } else {
         TDGL_TRY(fetch_scalars(ctx, false, rr_part));
     }
-    if (!after_first_sync(ctx->h_status)) {
+    if (!after_first_sync(ctx->h_status.p)) {
         if (abandoned) *abandoned = true;
         return TDGL_OK;
     }
     ctx->last_pcg_iters = 0;
     ctx->last_guess_vectors = 0;
     if (guard) direct_guard_read(ctx, true);  // (the psi update succeeded: mu = G b was written)
-    const double bb = ctx->h_status->scal[S_BB];
-    ctx->last_relres = (!in_step && bb > 0.0) ? std::sqrt(ctx->h_status->scal[S_RR] / bb) : 0.0;
+    const double bb = ctx->h_status.p->scal[S_BB];
+    ctx->last_relres = (!in_step && bb > 0.0) ? std::sqrt(ctx->h_status.p->scal[S_RR] / bb) : 0.0;
     ctx->last_guess_relres = ctx->last_relres;
     HIP_TRY(ctx, hipGetLastError());
     return TDGL_OK;
@@ -587,17 +587,10 @@ static int cg_precondition(CgRun &run, int it, double **z, const float **z32) {
     if (run.use_pd) {
         *z = ctx->direct->z.p;
         // (profile mode: every application of the first 64 bracketed by an event pair -> tdgl_profile_read_direct)
-        hipEvent_t fa = nullptr, fb = nullptr;
-        if (ctx->profile && ctx->prof3_launches + (int64_t)ctx->prof3_pending.size() < 64) {
-            TDGL_TRY(profile_event(ctx, &fa));
-            TDGL_TRY(profile_event(ctx, &fb));
-            HIP_TRY(ctx, hipEventRecord(fa, ctx->stream));
-        }
+        ProfileScope apply;
+        TDGL_TRY(profile_begin(ctx, ctx->prof.admit_factor_apply(), apply));
         TDGL_TRY(precond_factors_apply(ctx, r, *z, rz_new));
-        if (fa) {
-            HIP_TRY(ctx, hipEventRecord(fb, ctx->stream));
-            ctx->prof3_pending.emplace_back(fa, fb);
-        }
+        TDGL_TRY(profile_end(ctx, apply));
     } else if (run.cg1()) {
         *z32 = vcycle0_f32(ctx, r, rz_new, Cycle0Out::ghosts_no_sums());
     } else if (run.f32i() && distributed(ctx)) {
@@ -631,24 +624,14 @@ static int cg_step_single(CgRun &run, int it, const double *z, const float *z32)
     sell_fixed_grid(L0.A.pat.n_slices, &per_xcd, &grid);
     const double *rz_prev = it == run.it0 ? (const double *)nullptr : (const double *)rz_old;
     const SellPattern &pat = L0.A.pat;
-    hipEvent_t pa = nullptr, pb = nullptr;
-    // (every 8th launch, at most 64 samples: event pairs on every launch would slow a short timed window down measurably)
-    const bool sample = ctx->profile && ctx->prof2_budget > 0 && (ctx->prof2_seen++ % 8) == 0;
-    if (sample) {
-        ctx->prof2_budget -= 1;
-        TDGL_TRY(profile_event(ctx, &pa));
-        TDGL_TRY(profile_event(ctx, &pb));
-        HIP_TRY(ctx, hipEventRecord(pa, ctx->stream));
-    }
+    ProfileScope axp;  // (profile mode: a sample of the launches -> tdgl_profile_read_pcg)
+    TDGL_TRY(profile_begin(ctx, ctx->prof.admit_axp(), axp));
     if (run.f32i()) {
         if (pat.use16) TDGL_AXP(float, int16_t, pat.cols16.p, z32); else TDGL_AXP(float, int32_t, pat.cols.p, z32);
     } else {
         if (pat.use16) TDGL_AXP(double, int16_t, pat.cols16.p, z); else TDGL_AXP(double, int32_t, pat.cols.p, z);
     }
-    if (sample) {
-        HIP_TRY(ctx, hipEventRecord(pb, ctx->stream));
-        ctx->prof2_pending.emplace_back(pa, pb);
-    }
+    TDGL_TRY(profile_end(ctx, axp));
     const XrArgs upd{run.p, run.q, rz_new, ctx->part_pq.p, run.part_rr[it & 1], ctx->scal.p, run.x, run.r, run.part_rr[(it + 1) & 1],
                      ctx->n_own, ctx->npart, ctx->part_tmp.p};
     run.sum_x_fresh = true;
@@ -741,14 +724,14 @@ static int cg_iterate(CgRun &run, double tol2, int &it, double &rr) {
                 return TDGL_OK;
             }));
             run.finish_queued = true;
-            const double *sc = ctx->h_status->scal;  // (the kernel's own test, on the copy of the numbers it read)
+            const double *sc = ctx->h_status.p->scal;  // (the kernel's own test, on the copy of the numbers it read)
             run.finished = sc[S_CONV_IT] >= 0.0 || sc[S_RR] <= sc[S_TOL2];
         } else {
             TDGL_TRY(fetch_scalars(ctx, false, run.part_rr[it & 1]));  // also scal[S_RR] = sum of the partials
         }
-        rr = ctx->h_status->scal[S_RR];
-        if (ctx->h_status->scal[S_CONV_IT] >= 0.0) {  // converged inside the batch: the rest was frozen
-            it = (int)ctx->h_status->scal[S_CONV_IT];
+        rr = ctx->h_status.p->scal[S_RR];
+        if (ctx->h_status.p->scal[S_CONV_IT] >= 0.0) {  // converged inside the batch: the rest was frozen
+            it = (int)ctx->h_status.p->scal[S_CONV_IT];
             break;
         }
         if (!std::isfinite(rr)) TDGL_FAIL(ctx, TDGL_ERR_PCG, "Poisson solve diverged (non-finite residual) after %d iterations", it);
@@ -798,7 +781,7 @@ static int pcg_note_solve(tdgl_ctx *ctx, const CgRun &run, int it, double rr, do
     ctx->stat_pcg_iters += it;
     ctx->stat_pcg_needed += it;
     ctx->last_relres = std::sqrt(rr / bb);
-    ctx->last_guess_relres = it > 0 ? std::sqrt(std::max(0.0, ctx->h_status->scal[S_RR0]) / bb) : ctx->last_relres;
+    ctx->last_guess_relres = it > 0 ? std::sqrt(std::max(0.0, ctx->h_status.p->scal[S_RR0]) / bb) : ctx->last_relres;
     const int pd_its = run.pd_its;
     if (ctx->pd_last) {
         ctx->pd_solves += 1;
@@ -806,7 +789,7 @@ static int pcg_note_solve(tdgl_ctx *ctx, const CgRun &run, int it, double rr, do
         const double rr_f = pd_its >= 0 ? run.pd_rr_end : rr;
         ctx->pd_iters += its_f;
         if (pd_its >= 0) ctx->pd_amg_iters += it - its_f;
-        const double rr0 = ctx->h_status->scal[S_RR0];
+        const double rr0 = ctx->h_status.p->scal[S_RR0];
         if (its_f >= 1 && (pd_its >= 0 || !(rr > tol2)) && rr_f > 0.0 && rr0 > rr_f && std::isfinite(rr0)) {
             // (decades per application; a solve that started within a decade of the tolerance says little about it)
             const double seen = 0.5 * std::log10(rr0 / rr_f) / its_f;
@@ -818,7 +801,7 @@ static int pcg_note_solve(tdgl_ctx *ctx, const CgRun &run, int it, double rr, do
             ctx->pd_amg_iters += it;
         }
         if (it >= 2 && !(rr > tol2) && rr > 0.0) {  // contraction per iteration of this solve -> running mean
-            const double rr0 = ctx->h_status->scal[S_RR0];
+            const double rr0 = ctx->h_status.p->scal[S_RR0];
             if (rr0 > rr && std::isfinite(rr0)) {
                 const double seen = 0.5 * std::log10(rr0 / rr) / it;
                 ctx->pcg_rate = 0.8 * ctx->pcg_rate + 0.2 * std::min(1.5, std::max(0.2, seen));
@@ -908,15 +891,15 @@ static int pcg_solve(tdgl_ctx *ctx, MuSolveArgs &args, F after_first_sync, bool 
     // The Gram row of the window's newest vector arrived with this status block.  Taken BEFORE an abandoned
     // solve returns: a second pcg_solve for the same step (after a psi retry) would compute it again, which
     // is harmless, but a window change in between would not be.
-    if (proj) guess.take_gram_row(ctx->h_status);
-    if (!after_first_sync(ctx->h_status)) {
+    if (proj) guess.take_gram_row(ctx->h_status.p);
+    if (!after_first_sync(ctx->h_status.p)) {
         if (abandoned) *abandoned = true;
         return TDGL_OK;
     }
-    const double bb = ctx->h_status->scal[S_BB];
-    double rr = proj ? INFINITY : ctx->h_status->scal[S_RR];
+    const double bb = ctx->h_status.p->scal[S_BB];
+    double rr = proj ? INFINITY : ctx->h_status.p->scal[S_RR];
     int it = 0;
-    const double b_mean = proj ? ctx->h_status->gdot[2 * G_SB] * inv_n : 0.0;  // still inside b
+    const double b_mean = proj ? ctx->h_status.p->gdot[2 * G_SB] * inv_n : 0.0;  // still inside b
     if (!(bb > 0.0)) {  // b = 0: the zero-mean solution is 0
         HIP_TRY(ctx, hipMemsetAsync(x, 0, ctx->n_pad * sizeof(double), ctx->stream));
         ctx->last_pcg_iters = 0;

@@ -17,7 +17,7 @@
 extern "C" int tdgl_begin_stage(tdgl_ctx *ctx) {
     if (!ctx) return TDGL_ERR_ARG;
     ctx->loop.begin_stage();
-    direct_policy_reset(ctx);
+    ctx->choice.reset();
     return TDGL_OK;
 }
 
@@ -83,55 +83,6 @@ extern "C" int tdgl_set_controller_state(tdgl_ctx *ctx, double tentative_dt, con
     return TDGL_OK;
 }
 
-// ---- direct <-> iterative mu solve, decided by the state (tdgl_internal.h: direct_switch_on) -------------------------
-constexpr double DIRECT_PAUSE_DMAX = 1e-4;   // max d|psi|^2 per step below which AMG-PCG from the projection guess needs ~1 iteration
-constexpr int DIRECT_PAUSE_WINDOW = 64;      // ... for this many accepted steps in a row
-constexpr double DIRECT_RESUME_ITERS = 2.5;  // running mean of the PCG iterations above which the direct solve is the cheaper one again
-// A state that RELAXES smoothly towards a stationary one is extrapolated by the guess window long before it gets there
-// (a strip 300 steps after its current was switched on: 1e-3 per step, 1.5 iterations): three windows in a row, each
-// at least 10 % below the one before and the last below this, pause the direct solve as well
-constexpr double DIRECT_RELAX_DMAX = 2e-3;
-
-static inline void direct_note_step(tdgl_ctx *ctx, double dmax, int pcg_iters) {
-    if (!ctx->direct_switch_on) return;
-    ctx->direct_recent_dmax[ctx->direct_recent_n % DIRECT_PAUSE_WINDOW] = dmax;
-    ctx->direct_recent_n += 1;
-    if (ctx->direct_recent_n % DIRECT_PAUSE_WINDOW == 0) {  // a window is complete: its maximum joins the last three
-        double worst = 0.0;
-        for (int i = 0; i < DIRECT_PAUSE_WINDOW; ++i) worst = std::max(worst, ctx->direct_recent_dmax[i]);
-        ctx->direct_win_max[0] = ctx->direct_win_max[1];
-        ctx->direct_win_max[1] = ctx->direct_win_max[2];
-        ctx->direct_win_max[2] = ctx->direct_win_max[3];
-        ctx->direct_win_max[3] = worst;
-    }
-    ctx->direct_switch_steps += 1;
-    if (ctx->direct_paused) ctx->direct_pcg_ema = 0.95 * ctx->direct_pcg_ema + 0.05 * (double)pcg_iters;
-}
-
-static void direct_policy(tdgl_ctx *ctx) {
-    if (!ctx->direct_switch_on || ctx->direct_fell_back || distributed(ctx)) return;
-    if (!ctx->direct_paused) {
-        if (ctx->direct_switch_steps < ctx->direct_pause_hold || ctx->direct_recent_n < DIRECT_PAUSE_WINDOW) return;
-        double worst = 0.0;
-        for (int i = 0; i < DIRECT_PAUSE_WINDOW; ++i) worst = std::max(worst, ctx->direct_recent_dmax[i]);
-        const double *wm = ctx->direct_win_max;
-        const bool relaxing = ctx->direct_recent_n >= 4 * DIRECT_PAUSE_WINDOW && wm[3] < DIRECT_RELAX_DMAX && wm[3] < 0.9 * wm[2] &&
-                              wm[2] < 0.9 * wm[1] && wm[1] < 0.9 * wm[0];
-        if (!(worst < DIRECT_PAUSE_DMAX) && !relaxing) return;
-        ctx->direct_paused = true;  // stationary or on its way there: the iterative solve takes over (its window starts empty)
-        ctx->guess.reset();
-        ctx->direct_pcg_ema = 0.0;
-    } else {
-        if (ctx->direct_switch_steps < DIRECT_PAUSE_WINDOW || ctx->direct_pcg_ema < DIRECT_RESUME_ITERS) return;
-        ctx->direct_paused = false;  // the state moves again
-        // (a pause that was worth it -- a plateau of an I-V staircase -- leaves the next one its short wait; one that ended
-        // right away doubles it)
-        ctx->direct_pause_hold = ctx->direct_switch_steps >= 1024 ? 256 : std::min<int64_t>(2 * ctx->direct_pause_hold, 16384);
-    }
-    ctx->direct_switches += 1;
-    ctx->direct_switch_steps = 0;
-}
-
 static int ensure_laplacian_cache(tdgl_ctx *ctx) {
     if (ctx->lap_valid) return TDGL_OK;
     launch_psi_laplacian(ctx, false, ctx->psi[ctx->loop.cur].p, ctx->lap[ctx->loop.cur].p);
@@ -166,12 +117,12 @@ static int probe_ring_flush(tdgl_ctx *ctx, int64_t first_row, double *out_mu, do
     const int np_ = (int)ctx->probes.size(), cnt = ctx->probe_ring_count;
     ctx->probe_ring_count = 0;
     if (np_ == 0 || cnt == 0) return TDGL_OK;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_probe_out, ctx->d_probe_out.p, (size_t)cnt * 2 * np_ * sizeof(double),
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_probe_out.p, ctx->d_probe_out.p, (size_t)cnt * 2 * np_ * sizeof(double),
                                 hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->stat_host_syncs += 1;
     for (int k = 0; k < cnt; ++k) {
-        const double *row = ctx->h_probe_out + (size_t)k * 2 * np_;
+        const double *row = ctx->h_probe_out.p + (size_t)k * 2 * np_;
         if (out_mu) memcpy(out_mu + (first_row + k) * np_, row, np_ * sizeof(double));
         if (out_theta) memcpy(out_theta + (first_row + k) * np_, row + np_, np_ * sizeof(double));
     }
@@ -230,7 +181,6 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
         }
         // Speculative: L psi^{n+1}, the Poisson right-hand side and the PCG set-up are queued
         // before the host has seen the failure flag; a failed update simply repeats them.
-        hipEvent_t pa = nullptr, pb = nullptr;
         // (ghost copies of psi^{n+1} come from their owners before the stencil reads them)
         // (overlapped: the ghost-free rows of the stencil run on the compute stream while the
         // exchange travels on the communication stream; the remaining rows follow it)
@@ -239,11 +189,8 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
             TDGL_TRY(comm_halo_start(ctx, reinterpret_cast<double *>(ctx->psi[nxt].p), 2));
         else
             TDGL_TRY(comm_halo(ctx, reinterpret_cast<double *>(ctx->psi[nxt].p), 2));
-        if (ctx->profile) {
-            TDGL_TRY(profile_event(ctx, &pa));
-            TDGL_TRY(profile_event(ctx, &pb));
-            HIP_TRY(ctx, hipEventRecord(pa, ctx->stream));
-        }
+        ProfileScope k1;
+        TDGL_TRY(profile_begin(ctx, ctx->prof.admit_k1(), k1));
         if (ov) {
             launch_psi_laplacian(ctx, true, ctx->psi[nxt].p, ctx->lap[nxt].p, 1);
             TDGL_TRY(comm_halo_wait(ctx));
@@ -251,10 +198,7 @@ static int step_once(tdgl_ctx *ctx, double *dt_used, double *probe_mu, double *p
         } else {
             launch_psi_laplacian(ctx, true, ctx->psi[nxt].p, ctx->lap[nxt].p);
         }
-        if (ctx->profile) {
-            HIP_TRY(ctx, hipEventRecord(pb, ctx->stream));
-            ctx->prof_pending.emplace_back(pa, pb);
-        }
+        TDGL_TRY(profile_end(ctx, k1));
         bool failed = false, abandoned = false;
         solve = MuSolveArgs{ctx->popt.edge_currents_every_step != 0, plan};
         const int solve_status = pcg_solve(
@@ -332,7 +276,7 @@ static int step_finish(tdgl_ctx *ctx, double dt, double dmax, double *dt_used, d
     *dt_used = dt;
     if (pcg_iters) *pcg_iters = ctx->last_pcg_iters;
     ctx->stat_steps += 1;
-    direct_note_step(ctx, dmax, ctx->last_pcg_iters);
+    ctx->choice.note_step(dmax, ctx->last_pcg_iters);
     ctx->loop.accept(dt, dmax);
     return TDGL_OK;
 }
@@ -423,7 +367,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
     *accepted = 0;
     *reached = false;
     TDGL_TRY(ensure_laplacian_cache(ctx));
-    StepCtl &h = *ctx->h_ctl;
+    StepCtl &h = *ctx->h_ctl.p;
     const bool ramping = ctx->loop.ramping();
     ctx->loop.fill(h, end_time, true);
     if (ramping) TDGL_TRY(ensure_link_flags(ctx));
@@ -457,32 +401,14 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
         }
         // (the edge currents of psi^n ride along: always behind the first attempt, for the first if they are owed)
         launch_ra_psi(ctx, !ramping && EdgeCurrents::batch_attempt_takes(s, owed_on_entry));
-        // (K1 is timed once per batch in profile mode: event markers between back-to-back launches cost more
-        // than the launches they bracket at these sizes)
-        hipEvent_t pa = nullptr, pb = nullptr;
-        if (ctx->profile && s == 0) {
-            TDGL_TRY(profile_event(ctx, &pa));
-            TDGL_TRY(profile_event(ctx, &pb));
-            HIP_TRY(ctx, hipEventRecord(pa, ctx->stream));
-        }
+        // (profile mode: K1, then the direct solve's launches, each bracketed once per batch -> tdgl_profile_read, _read_direct)
+        ProfileScope k1, solve;
+        TDGL_TRY(profile_begin(ctx, ctx->prof.admit_k1_batch(s), k1));
         launch_ra_laplacian(ctx);
-        if (pa) {
-            HIP_TRY(ctx, hipEventRecord(pb, ctx->stream));
-            ctx->prof_pending.emplace_back(pa, pb);
-        }
-        // (profile mode: the direct solve's launches bracketed once per batch -> tdgl_profile_read_pcg)
-        hipEvent_t qa = nullptr, qb = nullptr;
-        if (ctx->profile && s == 0 && ctx->prof2_budget > 0) {
-            ctx->prof2_budget -= 1;
-            TDGL_TRY(profile_event(ctx, &qa));
-            TDGL_TRY(profile_event(ctx, &qb));
-            HIP_TRY(ctx, hipEventRecord(qa, ctx->stream));
-        }
+        TDGL_TRY(profile_end(ctx, k1));
+        TDGL_TRY(profile_begin(ctx, ctx->prof.admit_direct_batch(s), solve));
         (void)direct_solve_launch(ctx, ctx->bvec.p, ctx->mu.p, true, ctx->d_ctl.p, ctx->d_rec.p);
-        if (qa) {
-            HIP_TRY(ctx, hipEventRecord(qb, ctx->stream));
-            ctx->prof3_pending.emplace_back(qa, qb);
-        }
+        TDGL_TRY(profile_end(ctx, solve));
         if (probing)
             hipLaunchKernelGGL(k_ra_probes, dim3((np_ + 63) / 64), dim3(64), 0, ctx->stream, np_, (const int32_t *)ctx->d_probes.p,
                                (const double2 *)ctx->psi[0].p, (const double2 *)ctx->psi[1].p, (const double *)ctx->mu.p,
@@ -496,7 +422,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(&h, ctx->d_ctl.p, sizeof(StepCtl), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rec, ctx->d_rec.p, (size_t)batch * sizeof(StepRec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_rec.p, ctx->d_rec.p, (size_t)batch * sizeof(StepRec), hipMemcpyDeviceToHost, ctx->stream));
     {
         const int64_t t0 = now_ns();
         const hipError_t e = hipStreamSynchronize(ctx->stream);
@@ -509,11 +435,11 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
     // (mu and b are a pair when the last attempt that ran was accepted)
     if (guard) direct_guard_read(ctx, done > 0 && done <= batch && h.last_ok != 0);
     if (done == 0) TDGL_FAIL(ctx, TDGL_ERR_HIP, "run-ahead: no attempt of the batch ran");  // (cannot happen: the first one is always live)
-    const LoopState::Batch b = ctx->loop.absorb(h, ctx->h_rec, batch, batch, ramping, out_dt);
+    const LoopState::Batch b = ctx->loop.absorb(h, ctx->h_rec.p, batch, batch, ramping, out_dt);
     if (b.corrupt)
         TDGL_FAIL(ctx, TDGL_ERR_HIP, "run-ahead: corrupt attempt records (%d processed, %d accepted of %d; check %d)", done, h.n_acc, batch, b.corrupt);
     for (int s = 0; s < done; ++s)
-        if (ctx->h_rec[s].ok) direct_note_step(ctx, ctx->h_rec[s].dmax, 0);
+        if (ctx->h_rec.p[s].ok) ctx->choice.note_step(ctx->h_rec.p[s].dmax, 0);
     const int acc = b.accepted;
     *accepted = acc;
     *reached = b.reached;
@@ -549,7 +475,8 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
         // kernels drop the term), with or without the run-ahead loop
         const bool settled = ctx->loop.ramp_settled();
         if (settled && ctx->loop.field.has_dadt && !ctx->scr_enabled) ctx->loop.field.has_dadt = false;
-        direct_policy(ctx);
+        // direct or iterative (a pause hands over to AMG-PCG, whose projection window starts empty)
+        if (ctx->choice.decide(!ctx->direct_fell_back && !distributed(ctx)) == SolverChoice::PAUSED) ctx->guess.reset();
         if (run_ahead_ok(ctx)) {
             const bool want_probes = out_mu_probe || out_theta_probe;
             int batch = (int)std::min<int64_t>(std::min<int64_t>(ctx->ra_batch, RA_BATCH_MAX), max_steps - k);

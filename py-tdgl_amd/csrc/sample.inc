@@ -141,10 +141,8 @@ __global__ __launch_bounds__(BLOCK) void k_sample_moment_finish(int64_t nb, cons
 static constexpr int64_t SAMPLE_MAX_CHUNK = 32;
 static constexpr int64_t SAMPLE_STAGE_BYTES = (int64_t)512 << 20;
 
-struct tdgl_sample_plan {
+struct tdgl_sample_plan : tdgl::TimedStream {  // (stream, ev0, ev1)
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int64_t n_sites = 0, n_edges = 0, n_tri = 0, m = 0;
     int64_t nb = 0;         // workgroups over the sites
     int64_t chunk_env = 0;  // TDGL_SAMPLE_CHUNK, 0: not set
@@ -166,9 +164,6 @@ extern "C" void tdgl_sample_plan_destroy(tdgl_sample_plan *plan) {
     if (!plan) return;
     (void)hipSetDevice(plan->device);
     if (plan->stream) (void)hipStreamSynchronize(plan->stream);
-    if (plan->ev0) (void)hipEventDestroy(plan->ev0);
-    if (plan->ev1) (void)hipEventDestroy(plan->ev1);
-    if (plan->stream) (void)hipStreamDestroy(plan->stream);
     delete plan;
 }
 
@@ -271,9 +266,7 @@ extern "C" int tdgl_sample_plan_create(tdgl_sample_plan **out, int device_id, in
         const long asked = atol(env);
         if (asked >= 1 && asked <= SAMPLE_MAX_CHUNK) plan->chunk_env = asked;
     }
-    HIP_TRY(SAMPLE_NO_CTX, hipStreamCreate(&plan->stream));
-    HIP_TRY(SAMPLE_NO_CTX, hipEventCreate(&plan->ev0));
-    HIP_TRY(SAMPLE_NO_CTX, hipEventCreate(&plan->ev1));
+    HIP_TRY(SAMPLE_NO_CTX, plan->create());
     HIP_TRY(SAMPLE_NO_CTX, plan->sites.upload(std::vector<double>(sites_xy, sites_xy + 2 * n_sites)));
     HIP_TRY(SAMPLE_NO_CTX, plan->row_ptr.upload(row_ptr));
     HIP_TRY(SAMPLE_NO_CTX, plan->row_edge.upload(row_edge));

@@ -201,8 +201,7 @@ extern "C" int tdgl_poisson_schur_finish(tdgl_ctx *ctx, const double *S, int32_t
     if (fp32_storage) TDGL_TRY(dense_to_fp32(ctx, D));
     f.S = std::move(D);
     TDGL_TRY(sub_factors_to_precond(ctx, fp32_storage != 0, "tdgl_poisson_schur_finish"));
-    ctx->direct_switch_on = false;
-    ctx->direct_paused = false;
+    ctx->choice.enable(false);
     ctx->pcg_epoch += 1;
     return precond_calibrate(ctx, t_apply_us, t_vcycle_us);
 }

@@ -1,6 +1,6 @@
 // libtdgl_hip: MI355X-native TDGL time-stepping core behind a C ABI (include/tdgl_hip.h).
 // Single translation unit: kernels (kernels.inc), the AMG V-cycle (vcycle.inc), the mu factors' application (factors.inc),
-// Poisson solver (poisson.inc), the per-step driver (run.inc).
+// Poisson solver (poisson.inc), the in-run timers (profile.inc), the per-step driver (run.inc).
 
 #include "tdgl_internal.h"
 
@@ -167,36 +167,7 @@ extern "C" void tdgl_destroy(tdgl_ctx *ctx) {
     for (auto *lv : ctx->levels) delete lv;
     if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
     ipc_free(ctx);
-    if (ctx->h_sendbuf) (void)hipHostFree(ctx->h_sendbuf);
-    if (ctx->h_recvbuf) (void)hipHostFree(ctx->h_recvbuf);
-    if (ctx->h_deep_send) (void)hipHostFree(ctx->h_deep_send);
-    if (ctx->h_deep_recv) (void)hipHostFree(ctx->h_deep_recv);
-    if (ctx->h_status) (void)hipHostFree(ctx->h_status);
-    if (ctx->h_ctl) (void)hipHostFree(ctx->h_ctl);
-    if (ctx->h_rec) (void)hipHostFree(ctx->h_rec);
-    if (ctx->h_probe_out) (void)hipHostFree(ctx->h_probe_out);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->ev_pack) (void)hipEventDestroy(ctx->ev_pack);
-    if (ctx->ev_halo) (void)hipEventDestroy(ctx->ev_halo);
-    if (ctx->ev_status) (void)hipEventDestroy(ctx->ev_status);
-    if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
-    for (auto &pr : ctx->prof_pending) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (auto &pr : ctx->prof2_pending) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (auto &pr : ctx->prof3_pending) {
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-    }
-    for (hipEvent_t e : ctx->prof_pool) (void)hipEventDestroy(e);
-    hipStream_t s = ctx->stream;
-    delete ctx;  // frees the DevBufs
-    if (s) (void)hipStreamDestroy(s);
+    delete ctx;  // every member releases what it owns, the stream last (tdgl_internal.h: tdgl_ctx)
 }
 
 extern "C" int tdgl_synchronize(tdgl_ctx *ctx) {
@@ -374,8 +345,7 @@ static int create_impl(tdgl_ctx *ctx, const tdgl_mesh_desc *d) {
     HIP_TRY(ctx, ctx->d_status.alloc(1));
     // The status block is published into device memory and copied to this pinned block at every host
     // synchronisation.
-    HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_status), sizeof(StepStatus)));
-    memset(ctx->h_status, 0, sizeof(StepStatus));
+    HIP_TRY(ctx, ctx->h_status.alloc(1));
     // (the environment switches of the library: what the test-suite needs to reach a code path -- DESIGN.md section 5)
     ctx->run_ahead_disabled = getenv("TDGL_NO_RUN_AHEAD") != nullptr;
     ctx->sync_shadow_disabled = getenv("TDGL_NO_SYNC_SHADOW") != nullptr;
@@ -384,10 +354,10 @@ static int create_impl(tdgl_ctx *ctx, const tdgl_mesh_desc *d) {
     HIP_TRY(ctx, ctx->scal.alloc(S_COUNT));
     HIP_TRY(ctx, ctx->d_ctl.alloc(1));
     HIP_TRY(ctx, ctx->d_rec.alloc(RA_BATCH_MAX));
-    HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_ctl), sizeof(StepCtl)));
-    HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_rec), RA_BATCH_MAX * sizeof(StepRec)));
-    HIP_TRY(ctx, hipEventCreate(&ctx->ev0));
-    HIP_TRY(ctx, hipEventCreate(&ctx->ev1));
+    HIP_TRY(ctx, ctx->h_ctl.alloc(1));
+    HIP_TRY(ctx, ctx->h_rec.alloc(RA_BATCH_MAX));
+    HIP_TRY(ctx, ctx->ev0.create());
+    HIP_TRY(ctx, ctx->ev1.create());
     ctx->psi_blocks = (int)std::min<int64_t>(std::max<int64_t>(grid_for(ctx->n_own), 1), 2048);
     {
         const int64_t tiles = (ctx->n_own + BLOCK - 1) / BLOCK;
@@ -396,10 +366,10 @@ static int create_impl(tdgl_ctx *ctx, const tdgl_mesh_desc *d) {
     }
     HIP_TRY(ctx, ctx->psi_dmax_part.alloc(ctx->psi_blocks));
     HIP_TRY(ctx, ctx->psi_fail_part.alloc(ctx->psi_blocks));
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_pack, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_halo, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_status, hipEventDisableTiming));
+    HIP_TRY(ctx, ctx->comm_stream.create(hipStreamNonBlocking));
+    HIP_TRY(ctx, ctx->ev_pack.create(/*timing=*/false));
+    HIP_TRY(ctx, ctx->ev_halo.create(/*timing=*/false));
+    HIP_TRY(ctx, ctx->ev_status.create(/*timing=*/false));
     return TDGL_OK;
 }
 
@@ -423,7 +393,7 @@ extern "C" int tdgl_create(tdgl_ctx **out, const tdgl_mesh_desc *d, int device_i
     tdgl_ctx *ctx = new tdgl_ctx();
     ctx->device = device_id;
     int st = TDGL_OK;
-    if (hipSetDevice(device_id) != hipSuccess || hipStreamCreate(&ctx->stream) != hipSuccess) {
+    if (hipSetDevice(device_id) != hipSuccess || ctx->stream.create() != hipSuccess) {
         g_last_error = "tdgl_create: cannot select device / create stream";
         st = TDGL_ERR_HIP;
     } else {
@@ -612,14 +582,13 @@ static void launch_edge_currents(tdgl_ctx *ctx, const double2 *psi, const double
                            ctx->e0.p, ctx->e1.p, ctx->e_inv_len.p, ctx->e_U.p, psi, mu, js, jn, dadt, base);
 }
 
-static int profile_event(tdgl_ctx *ctx, hipEvent_t *ev);                     // below
-
 static inline int64_t now_ns() {
     return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 #include "ipc.inc"
 #include "comm.inc"
+#include "profile.inc"
 #include "loop.inc"
 #include "guess.inc"
 #include "vcycle.inc"
@@ -646,7 +615,7 @@ extern "C" int tdgl_set_state(tdgl_ctx *ctx, const double *psi, const double *mu
     ctx->loop.new_state(ctx->loop.cur);
     ctx->prev_dt = ctx->prev_dt2 = 0.0;  // no mu history: the next solve starts from mu itself
     ctx->guess.reset();                   // (nor a projection basis)
-    direct_policy_reset(ctx);             // (nor a history for the loop's solver choice)
+    ctx->choice.reset();                  // (nor a history for the loop's solver choice)
     return TDGL_OK;
 }
 
@@ -670,15 +639,11 @@ extern "C" int tdgl_set_probes(tdgl_ctx *ctx, const int32_t *sites, int32_t n_pr
         if (sites[k] < 0 || sites[k] >= ctx->n) TDGL_FAIL(ctx, TDGL_ERR_ARG, "probe site %d out of range", sites[k]);
         ctx->probes.push_back(ctx->iperm[sites[k]]);
     }
-    if (ctx->h_probe_out) {
-        (void)hipHostFree(ctx->h_probe_out);
-        ctx->h_probe_out = nullptr;
-    }
+    ctx->h_probe_out.release();
     if (n_probe > 0) {
         HIP_TRY(ctx, ctx->d_probes.upload(ctx->probes));
         HIP_TRY(ctx, ctx->d_probe_out.alloc((size_t)PROBE_RING_STEPS * 2 * n_probe));
-        HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->h_probe_out),
-                                   (size_t)PROBE_RING_STEPS * 2 * n_probe * sizeof(double)));
+        HIP_TRY(ctx, ctx->h_probe_out.alloc((size_t)PROBE_RING_STEPS * 2 * n_probe, false));
     }
     return TDGL_OK;
 }
@@ -838,9 +803,9 @@ extern "C" int tdgl_psi_update(tdgl_ctx *ctx, const double *psi, const double *m
     launch_psi_update(ctx, s.c0.p, s.r0.p, lap.p, dt, pnew.p, s.r1.p);
     publish_status(ctx);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status, ctx->d_status.p, sizeof(StepStatus), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_status.p, ctx->d_status.p, sizeof(StepStatus), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *ok = ctx->h_status->fail_flag ? 0 : 1;
+    *ok = ctx->h_status.p->fail_flag ? 0 : 1;
     TDGL_TRY(download_sites(ctx, pnew.p, reinterpret_cast<double2 *>(psi_out)));
     if (abs_sq_out) TDGL_TRY(download_sites(ctx, s.r1.p, abs_sq_out));
     return TDGL_OK;
@@ -866,122 +831,6 @@ extern "C" int tdgl_poisson_rhs(tdgl_ctx *ctx, const double *psi, double *rhs) {
 }
 
 // ---------------------------------------------------------------------------------------
-// an event for the in-run timers: from the pool when it has one (no creation in a timed region)
-static int profile_event(tdgl_ctx *ctx, hipEvent_t *ev) {
-    if (!ctx->prof_pool.empty()) {
-        *ev = ctx->prof_pool.back();
-        ctx->prof_pool.pop_back();
-        return TDGL_OK;
-    }
-    HIP_TRY(ctx, hipEventCreate(ev));
-    return TDGL_OK;
-}
-
-extern "C" int tdgl_profile_enable(tdgl_ctx *ctx, int32_t on) {
-    if (!ctx) return TDGL_ERR_ARG;
-    if (on) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        while (ctx->prof_pool.size() < 1024) {  // 448 timed steps + the 64 sampled A p launches per read-out
-            hipEvent_t e;
-            HIP_TRY(ctx, hipEventCreate(&e));
-            ctx->prof_pool.push_back(e);
-        }
-    }
-    ctx->profile = on != 0;
-    ctx->prof_launches = 0;
-    ctx->prof_ms = 0.0;
-    ctx->prof2_launches = 0;
-    ctx->prof2_ms = 0.0;
-    ctx->prof2_budget = on ? 64 : 0;
-    ctx->prof2_seen = 0;
-    ctx->prof3_launches = 0;
-    ctx->prof3_ms = 0.0;
-    return TDGL_OK;
-}
-
-static int profile_drain(tdgl_ctx *ctx) {
-    for (auto &pr : ctx->prof_pending) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventSynchronize(pr.second));
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, pr.first, pr.second));
-        ctx->prof_ms += ms;
-        ctx->prof_launches += 1;
-        ctx->prof_pool.push_back(pr.first);
-        ctx->prof_pool.push_back(pr.second);
-    }
-    ctx->prof_pending.clear();
-    for (auto &pr : ctx->prof2_pending) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventSynchronize(pr.second));
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, pr.first, pr.second));
-        ctx->prof2_ms += ms;
-        ctx->prof2_launches += 1;
-        ctx->prof_pool.push_back(pr.first);
-        ctx->prof_pool.push_back(pr.second);
-    }
-    ctx->prof2_pending.clear();
-    for (auto &pr : ctx->prof3_pending) {
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventSynchronize(pr.second));
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, pr.first, pr.second));
-        ctx->prof3_ms += ms;
-        ctx->prof3_launches += 1;
-        ctx->prof_pool.push_back(pr.first);
-        ctx->prof_pool.push_back(pr.second);
-    }
-    ctx->prof3_pending.clear();
-    return TDGL_OK;
-}
-
-extern "C" int tdgl_profile_read_pcg(tdgl_ctx *ctx, int64_t *launches, double *total_ms) {
-    CTX_GUARD(ctx);
-    TDGL_TRY(profile_drain(ctx));
-    if (launches) *launches = ctx->prof2_launches;
-    if (total_ms) *total_ms = ctx->prof2_ms;
-    return TDGL_OK;
-}
-
-extern "C" int tdgl_profile_read_direct(tdgl_ctx *ctx, int64_t *solves, double *total_ms) {
-    CTX_GUARD(ctx);
-    TDGL_TRY(profile_drain(ctx));
-    if (solves) *solves = ctx->prof3_launches;
-    if (total_ms) *total_ms = ctx->prof3_ms;
-    return TDGL_OK;
-}
-
-extern "C" int tdgl_profile_read(tdgl_ctx *ctx, int64_t *launches, double *total_ms) {
-    CTX_GUARD(ctx);
-    TDGL_TRY(profile_drain(ctx));
-    if (launches) *launches = ctx->prof_launches;
-    if (total_ms) *total_ms = ctx->prof_ms;
-    return TDGL_OK;
-}
-
-// What an event pair reads with nothing between the two records: the marker packets' own
-// processing.  bench.py reports it next to the in-run kernel durations so that they can be
-// reconciled with rocprofv3's dispatch durations (which do not contain it).
-extern "C" int tdgl_profile_event_overhead(tdgl_ctx *ctx, int32_t reps, double *avg_ms) {
-    CTX_GUARD(ctx);
-    if (reps < 1 || !avg_ms) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_profile_event_overhead: reps >= 1 and avg_ms required");
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    double total = 0.0;
-    for (int i = 0; i < reps; ++i) {
-        hipEvent_t e0, e1;
-        HIP_TRY(ctx, hipEventCreate(&e0));
-        HIP_TRY(ctx, hipEventCreate(&e1));
-        HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(e1, ctx->stream));
-        HIP_TRY(ctx, hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, e0, e1));
-        total += ms;
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
-    *avg_ms = total / reps;
-    return TDGL_OK;
-}
-
 extern "C" int tdgl_time_kernel(tdgl_ctx *ctx, int32_t kernel, int32_t reps, double *avg_ms) {
     CTX_GUARD(ctx);
     if (!avg_ms || reps <= 0) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_time_kernel: bad arguments");

@@ -80,6 +80,89 @@ struct DevBuf {
     }
 };
 
+// ---------------------------------------------------------------- pinned host memory, events, streams
+// The same shape for page-locked host memory (what an asynchronous copy lands in or leaves from)
+template <class T>
+struct PinnedBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    PinnedBuf(PinnedBuf &&other) noexcept : p(other.p), n(other.n) { other.p = nullptr, other.n = 0; }
+    PinnedBuf &operator=(PinnedBuf &&other) noexcept {
+        if (this != &other) release(), p = other.p, n = other.n, other.p = nullptr, other.n = 0;
+        return *this;
+    }
+    ~PinnedBuf() { release(); }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    hipError_t alloc(size_t count, bool zero = true) {
+        release();
+        n = count;
+        if (count == 0) return hipSuccess;
+        hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&p), count * sizeof(T));
+        if (e != hipSuccess) {
+            p = nullptr;
+            n = 0;
+            return e;
+        }
+        if (zero) memset(p, 0, count * sizeof(T));
+        return e;
+    }
+};
+
+// An owned runtime handle: empty until created, destroyed with its owner, read wherever the runtime wants the handle
+template <class H, hipError_t (*Destroy)(H)>
+struct Handle {
+    H h = nullptr;
+    Handle() = default;
+    Handle(const Handle &) = delete;
+    Handle &operator=(const Handle &) = delete;
+    Handle(Handle &&other) noexcept : h(other.h) { other.h = nullptr; }
+    Handle &operator=(Handle &&other) noexcept {
+        if (this != &other) release(), h = other.h, other.h = nullptr;
+        return *this;
+    }
+    ~Handle() { release(); }
+    void release() {
+        if (h) (void)Destroy(h);
+        h = nullptr;
+    }
+    operator H() const { return h; }
+};
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+    hipError_t create(bool timing = true) {  // (timing = false: an ordering marker only, cheaper to record)
+        release();
+        const hipError_t e = timing ? hipEventCreate(&h) : hipEventCreateWithFlags(&h, hipEventDisableTiming);
+        if (e != hipSuccess) h = nullptr;
+        return e;
+    }
+};
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+    hipError_t create(unsigned flags = hipStreamDefault) {
+        release();
+        const hipError_t e = hipStreamCreateWithFlags(&h, flags);
+        if (e != hipSuccess) h = nullptr;
+        return e;
+    }
+};
+// A stream of its own with an event pair around the work of one call: what the field, vortex and sample plans are built
+// on.  A plan that derives from it frees its device buffers before the stream goes (bases are destroyed last).
+struct TimedStream {
+    Stream stream;
+    Event ev0, ev1;
+    hipError_t create() {
+        hipError_t e = stream.create();
+        if (e == hipSuccess) e = ev0.create();
+        if (e == hipSuccess) e = ev1.create();
+        return e;
+    }
+};
+
 // SELL-C-sigma with C = 64 (one slice per wavefront, sigma = 1: row order is kept, the
 // site permutation already groups rows of equal degree).  Entry k of row r of slice s is
 // stored at (slice_off[s] + k) * 64 + (r % 64): a wavefront's loads are 64 consecutive
@@ -445,6 +528,100 @@ struct EdgeCurrents {
     void screening_done() { state = FORMED; }  // (every screening iteration forms them: step_screening)
 };
 
+// Solver choice in the time loop (tdgl_direct_switching; meshes where BOTH a direct solve and the hierarchy are
+// resident and large enough for the choice to matter).  A direct solve costs the same whatever the state; AMG-PCG
+// started from the projection guess costs next to nothing once the state is stationary (a transport current
+// through a strip: 0 iterations) and more than the direct solve while vortices move.  So: direct by default; while
+// |psi|^2 has changed by less than PAUSE_DMAX per step for WINDOW steps the direct solve is paused (dense_on() is
+// false: classic loop, AMG-PCG); when the iterations' running mean exceeds RESUME_ITERS it comes back, and the next
+// pause has to wait twice as long.
+// The choice is a function of the run's recent history.  Whatever makes that history meaningless -- a new state, a new
+// stage, new boundary values or a new epsilon handed in by the caller -- returns it to its starting point (reset): the
+// direct solve, no windows, the short wait.  So a restart from a checkpoint (tdgl_set_state + tdgl_set_loop_state +
+// tdgl_set_controller_state) takes the same path whatever came before it.
+// Plain host arithmetic, replayed without a device by tdgl_host_solver_choice_replay.  Its functions (loop.inc) are
+// the only writers.
+struct SolverChoice {
+    static constexpr double PAUSE_DMAX = 1e-4;   // max d|psi|^2 per step below which AMG-PCG from the projection guess needs ~1 iteration
+    static constexpr int WINDOW = 64;            // ... for this many accepted steps in a row
+    static constexpr double RESUME_ITERS = 2.5;  // running mean of the PCG iterations above which the direct solve is the cheaper one again
+    // A state that RELAXES smoothly towards a stationary one is extrapolated by the guess window long before it gets there
+    // (a strip 300 steps after its current was switched on: 1e-3 per step, 1.5 iterations): three windows in a row, each
+    // at least 10 % below the one before and the last below this, pause the direct solve as well
+    static constexpr double RELAX_DMAX = 2e-3;
+    enum Change : int32_t { NONE, PAUSED, RESUMED };
+
+    void enable(bool yes) { on = yes, reset(); }  // tdgl_direct_switching; off wherever the factors become the CG's preconditioner
+    void reset();
+    void note_step(double dmax, int pcg_iters);   // a step was accepted
+    // in front of a step; allowed: the direct solve is still there to choose (no fall-back, one GPU).  PAUSED: the iterative
+    // solve takes over, and its window starts empty -- the caller resets the projection guess
+    Change decide(bool allowed);
+    bool paused() const { return is_paused; }
+    int64_t switches() const { return n_switches; }
+    int64_t pause_hold() const { return hold; }
+
+private:
+    bool on = false, is_paused = false;
+    int64_t switch_steps = 0;         // accepted steps since the last switch
+    int64_t hold = 256;               // steps the direct solve runs at least before it may be paused again
+    int64_t n_switches = 0;           // (survives reset)
+    double recent_dmax[WINDOW] = {0}; // ring of the last accepted steps' max d|psi|^2
+    int64_t recent_n = 0;
+    double win_max[4] = {0, 0, 0, 0}; // maxima of the last four complete windows, oldest first
+    double pcg_ema = 0.0;             // running mean of the iterations while paused
+};
+
+// The in-run timers (tdgl_profile_enable / _read / _read_pcg / _read_direct): event pairs around launches inside
+// tdgl_run, read out afterwards.  A channel is what one read-out reports; `budget` and `seen` are the state of its
+// admission rule (Profile::admit_*).
+struct ProfileChannel {
+    int64_t launches = 0;
+    double ms = 0.0;
+    int64_t budget = 0, seen = 0;
+    std::vector<std::pair<Event, Event>> pending;  // recorded, not read yet
+    void reset(int64_t new_budget) { launches = 0, ms = 0.0, budget = new_budget, seen = 0; }
+};
+struct Profile {
+    bool on = false;
+    std::vector<Event> pool;  // created by tdgl_profile_enable, recycled by profile_drain: no hipEventCreate inside a timed region
+    ProfileChannel k1;        // K1: L psi' and the right-hand side
+    ProfileChannel axp;       // the kernel that dominates the iterative solve (the CG's fused A p), sampled
+    // the launch sequence of a direct mu solve, or of one application of the factors as the CG's preconditioner (its own
+    // counters, so that a window in which the loop changed the solver does not divide one kind of bytes by the other
+    // kind of samples)
+    ProfileChannel direct;
+
+    // The admission rules, one per place that brackets launches: the channel the pair goes to, or null (no pair).
+    // K1 in the classic loop: every attempt
+    ProfileChannel *admit_k1() { return on ? &k1 : nullptr; }
+    // K1 in the run-ahead loop: once per batch (event markers between back-to-back launches cost more than the launches
+    // they bracket at these sizes)
+    ProfileChannel *admit_k1_batch(int attempt) { return on && attempt == 0 ? &k1 : nullptr; }
+    // A p: every 8th launch, at most `budget` samples (pairs on every launch would slow a short timed window down measurably)
+    ProfileChannel *admit_axp() {
+        if (!on || axp.budget <= 0 || (axp.seen++ % 8) != 0) return nullptr;
+        axp.budget -= 1;
+        return &axp;
+    }
+    // the factors as the CG's preconditioner: every application of the first 64
+    ProfileChannel *admit_factor_apply() { return on && direct.launches + (int64_t)direct.pending.size() < 64 ? &direct : nullptr; }
+    // the run-ahead loop's direct solve: once per batch.  Historical: it spends the A p channel's budget (both were one
+    // channel once), so a run whose iterative solves used the budget up times no direct solve any more, and the other way
+    // round.  The read-outs bench.py reports depend on it; kept as it is.
+    ProfileChannel *admit_direct_batch(int attempt) {
+        if (!on || attempt != 0 || axp.budget <= 0) return nullptr;
+        axp.budget -= 1;
+        return &direct;
+    }
+    void reset(bool enable) { on = enable, k1.reset(0), axp.reset(enable ? 64 : 0), direct.reset(0); }
+};
+// one admitted pair between its two records (profile.inc: profile_begin / profile_end); ch == null: declined
+struct ProfileScope {
+    ProfileChannel *ch = nullptr;
+    Event a, b;
+};
+
 // What the step driver tells a mu solve and hears back from it (pcg_solve, direct_mu_solve); a solve outside the time
 // loop passes the default.
 struct MuSolveArgs {
@@ -597,9 +774,13 @@ struct ScrTree;  // the screening treecode's set-up (screening_tree.inc)
 
 struct IpcState;  // peer-mapped transport (ipc.inc)
 
+// Members are destroyed in the reverse order of their declaration: the stream comes first here so that it goes last,
+// behind every device buffer, pinned block, event and the communication stream (tdgl_destroy synchronises it, tears down
+// RCCL and the peer-mapped transport, and deletes the context).  Every owning member is empty until create_impl fills it,
+// so a half-built context is destroyed the same way.
 struct tdgl_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
+    tdgl::Stream stream;
     std::string err;
 
     int64_t n = 0, m = 0, nb = 0, n_pad = 0, m_pad = 0;
@@ -617,12 +798,11 @@ struct tdgl_ctx {
     tdgl::DevBuf<int32_t> d_send_idx;
     tdgl::DevBuf<double> d_sendbuf, d_gstat;
     tdgl::DevBuf<float> d_red32;          // fp32 staging of the coarse right-hand side all-reduce
-    double *h_sendbuf = nullptr, *h_recvbuf = nullptr;  // pinned (callback transport)
-    int64_t h_buf_doubles = 0;
+    tdgl::PinnedBuf<double> h_sendbuf, h_recvbuf;  // (callback transport; both of h_sendbuf.n doubles)
     bool fix_psi = true;
     // halo exchange overlapped with the ghost-free rows (comm.inc): second stream + events
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_pack = nullptr, ev_halo = nullptr;
+    tdgl::Stream comm_stream;
+    tdgl::Event ev_pack, ev_halo;
     int int_tiles = 0;        // leading 256-row tiles whose rows have no ghost neighbour
     int64_t m_int = 0;        // leading edges (internal order) between two owned sites
     int overlap = 1;          // tdgl_set_comm_overlap: 0 off, 1 auto (by size), 2 always
@@ -637,7 +817,7 @@ struct tdgl_ctx {
     std::vector<int32_t> deep_nbrs, deep_send_ptr, deep_recv_ptr;
     tdgl::DevBuf<int32_t> d_deep_send_idx, d_deep_recv_idx;
     tdgl::DevBuf<double> d_deep_sendbuf, d_deep_recvbuf;
-    double *h_deep_send = nullptr, *h_deep_recv = nullptr;  // pinned (callback transport)
+    tdgl::PinnedBuf<double> h_deep_send, h_deep_recv;  // (callback transport)
     int64_t stat_deep_halos = 0;
 
     // permutations (host)
@@ -705,33 +885,19 @@ struct tdgl_ctx {
     int64_t pd_solves = 0, pd_iters = 0, pd_amg_solves = 0, pd_amg_iters = 0;  // solves / iterations by preconditioner since the last reset
     bool pd_last = false;                 // the last solve used the factors
     int64_t pd_handovers = 0;             // solves that began with the factors and were finished by the V-cycle
-    // Solver choice in the time loop (tdgl_direct_switching; meshes where BOTH a direct solve and the hierarchy are
-    // resident and large enough for the choice to matter).  A direct solve costs the same whatever the state; AMG-PCG
-    // started from the projection guess costs next to nothing once the state is stationary (a transport current
-    // through a strip: 0 iterations) and more than the direct solve while vortices move.  So: direct by default; while
-    // |psi|^2 has changed by less than DIRECT_PAUSE_DMAX per step for DIRECT_PAUSE_WINDOW steps the direct solve is
-    // paused (dense_on() is false: classic loop, AMG-PCG); when the iterations' running mean exceeds
-    // DIRECT_RESUME_ITERS it comes back, and the next pause has to wait twice as long.
-    bool direct_switch_on = false, direct_paused = false;
-    int64_t direct_switch_steps = 0;       // accepted steps since the last switch
-    int64_t direct_pause_hold = 256;       // steps the direct solve runs at least before it may be paused again
-    int64_t direct_switches = 0;
-    double direct_recent_dmax[64] = {0};   // ring of the last accepted steps' max d|psi|^2
-    int64_t direct_recent_n = 0;
-    double direct_win_max[4] = {0, 0, 0, 0};  // maxima of the last four complete windows of 64 steps, oldest first
-    double direct_pcg_ema = 0.0;
+    tdgl::SolverChoice choice;            // direct or iterative, step by step (tdgl_direct_switching; loop.inc)
     // run-ahead time loop (direct solves, static links): device-resident controller + per-step records
     tdgl::DevBuf<tdgl::StepCtl> d_ctl;
     tdgl::DevBuf<tdgl::StepRec> d_rec;
-    tdgl::StepCtl *h_ctl = nullptr;       // pinned
-    tdgl::StepRec *h_rec = nullptr;       // pinned [RA_BATCH_MAX]
+    tdgl::PinnedBuf<tdgl::StepCtl> h_ctl;  // [1]
+    tdgl::PinnedBuf<tdgl::StepRec> h_rec;  // [RA_BATCH_MAX]
     int ra_batch = 4;                     // attempts queued per synchronisation: doubles up to RA_BATCH_MAX
     bool run_ahead_disabled = false;      // TDGL_NO_RUN_AHEAD, read once when the context is created (tests, A/B runs)
     int64_t stat_ra_batches = 0, stat_ra_dead = 0;
     // Work queued behind a status copy while the host waits for it (poisson.inc: sync_status).  TDGL_NO_SYNC_SHADOW,
     // read once when the context is created, restores the order without it (tests, A/B runs).
     bool sync_shadow_disabled = false;
-    hipEvent_t ev_status = nullptr;       // recorded right behind the status copy: the host waits for it, not for the stream
+    tdgl::Event ev_status;                // recorded right behind the status copy: the host waits for it, not for the stream
     int64_t stat_edge_launches = 0;       // formations of J_s / J_n since the last reset (tdgl_get_edge_current_launches)
     // collapsed coarse chain (tdgl_poisson_set_collapsed_tail): everything from level `tail_level`
     // down as explicit operators, built for the smoother settings (tail_nu, tail_smoother, tail_cheb_lo)
@@ -784,12 +950,12 @@ struct tdgl_ctx {
     int psi_blocks = 0;                    // its grid
     bool psi_status_pending = false;       // not yet reduced into d_status
     tdgl::DevBuf<tdgl::StepStatus> d_status;
-    tdgl::StepStatus *h_status = nullptr;  // pinned: d_status is copied here at every host synchronisation
+    tdgl::PinnedBuf<tdgl::StepStatus> h_status;  // [1]: d_status is copied here at every host synchronisation
     tdgl::StepStatus *status_dev = nullptr;  // what the kernels write (= d_status.p)
     std::vector<int32_t> probes;           // internal site ids
     tdgl::DevBuf<int32_t> d_probes;
     tdgl::DevBuf<double> d_probe_out;      // ring buffer [PROBE_RING_STEPS][2 * n_probe]: mu | theta per step
-    double *h_probe_out = nullptr;         // pinned, same shape
+    tdgl::PinnedBuf<double> h_probe_out;   // the same shape
     int probe_ring_count = 0;              // steps written since the last flush (run.inc: probe_ring_flush)
 
     tdgl::LoopState loop;                  // controller, Runner.dt / time / step, retry and ramp state (loop.inc)
@@ -820,35 +986,6 @@ struct tdgl_ctx {
     std::shared_ptr<tdgl::ScrTree> scr_tree;
 
     // ---- measurement -------------------------------------------------------------------
-    bool profile = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int64_t prof_launches = 0;
-    double prof_ms = 0.0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_pending;
-    std::vector<hipEvent_t> prof_pool;     // created by tdgl_profile_enable, recycled by profile_drain: no
-                                           // hipEventCreate inside a timed region
-    // the same for the kernel that dominates the run time (the CG's fused A p), sampled: only the
-    // first prof2_budget launches after tdgl_profile_enable are bracketed by events
-    int64_t prof2_launches = 0, prof2_budget = 0, prof2_seen = 0;
-    double prof2_ms = 0.0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof2_pending;
-    // ... and for the launch sequence of a direct mu solve (one pair per run-ahead batch; its own counters, so that a
-    // window in which the loop changed the solver does not divide one kind of bytes by the other kind of samples)
-    int64_t prof3_launches = 0;
-    double prof3_ms = 0.0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof3_pending;
+    tdgl::Event ev0, ev1;                  // tdgl_time_kernel's pair
+    tdgl::Profile prof;                    // the in-run timers (profile.inc)
 };
-
-// The time loop's solver choice (run.inc: direct_policy) is a function of the run's recent history.  Whatever makes that
-// history meaningless -- a new state, a new stage, new boundary values or a new epsilon handed in by the caller --
-// returns it to its starting point: the direct solve, no windows, the short wait.  So a restart from a checkpoint
-// (tdgl_set_state + tdgl_set_loop_state + tdgl_set_controller_state) takes the same path whatever came before it.
-static inline void direct_policy_reset(tdgl_ctx *ctx) {
-    ctx->direct_paused = false;
-    ctx->direct_switch_steps = 0;
-    ctx->direct_recent_n = 0;
-    ctx->direct_pause_hold = 256;
-    ctx->direct_pcg_ema = 0.0;
-    for (double &w : ctx->direct_win_max) w = 0.0;
-}
-

@@ -283,10 +283,8 @@ static constexpr int64_t VORTEX_STAGE_BYTES = (int64_t)256 << 20;
 // grid's y limit is 65,535).  TDGL_VORTEX_LINK_JOBS=<jobs> (tests) lowers it, read at plan creation.
 static constexpr int64_t VORTEX_LINK_MAX_JOBS = 32768;
 
-struct tdgl_vortex_plan {
+struct tdgl_vortex_plan : tdgl::TimedStream {  // (stream, ev0, ev1)
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int64_t n_sites = 0, n_tri = 0, n_loop_sites = 0;
     int32_t n_loops = 0;
     int64_t chunk = 1;  // frames per chunk
@@ -313,9 +311,6 @@ extern "C" void tdgl_vortex_plan_destroy(tdgl_vortex_plan *plan) {
     if (!plan) return;
     (void)hipSetDevice(plan->device);
     if (plan->stream) (void)hipStreamSynchronize(plan->stream);
-    if (plan->ev0) (void)hipEventDestroy(plan->ev0);
-    if (plan->ev1) (void)hipEventDestroy(plan->ev1);
-    if (plan->stream) (void)hipStreamDestroy(plan->stream);
     delete plan;
 }
 
@@ -374,9 +369,7 @@ extern "C" int tdgl_vortex_plan_create(tdgl_vortex_plan **out, int device_id, in
         const long asked = atol(env);
         if (asked >= 1 && asked <= VORTEX_LINK_MAX_JOBS) plan->link_max_jobs = asked;
     }
-    HIP_TRY(VORTEX_NO_CTX, hipStreamCreate(&plan->stream));
-    HIP_TRY(VORTEX_NO_CTX, hipEventCreate(&plan->ev0));
-    HIP_TRY(VORTEX_NO_CTX, hipEventCreate(&plan->ev1));
+    HIP_TRY(VORTEX_NO_CTX, plan->create());
     std::vector<int8_t> orient((size_t)n_tri);
     for (int64_t t = 0; t < n_tri; ++t)
         orient[t] = vortex_orientation(sites_xy + 2 * (int64_t)elements[3 * t], sites_xy + 2 * (int64_t)elements[3 * t + 1],

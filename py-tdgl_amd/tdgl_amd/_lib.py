@@ -150,6 +150,15 @@ class CurrentsReplay(C.Structure):
     ]
 
 
+class SolverChoiceReplay(C.Structure):
+    _fields_ = [
+        ("switches", C.c_int64),
+        ("pause_hold", C.c_int64),
+        ("paused", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
 class PoissonOptions(C.Structure):
     _fields_ = [
         ("rtol", C.c_double),
@@ -389,6 +398,8 @@ SIGNATURES = {
         [C.c_int32, C.POINTER(CurrentsFacts), C.POINTER(Controller), C.c_double, C.c_int64, c_f64p, c_i32p, C.c_int32,
          C.c_int32, C.c_int64, c_i64p, c_i32p, c_i64p, C.POINTER(CurrentsReplay)],
     ),
+    "tdgl_host_solver_choice_replay": (
+        C.c_int, [C.c_int64, c_f64p, c_i32p, C.c_int64, c_i64p, c_i32p, C.POINTER(SolverChoiceReplay)]),
     "tdgl_host_blr_compress": (C.c_int32, [c_f64p, C.c_int32, C.c_double, C.c_int32, c_f64p, c_f64p]),
     "tdgl_begin_stage": (C.c_int, [_CTX]),
     "tdgl_run": (

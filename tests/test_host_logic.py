@@ -816,6 +816,136 @@ def test_the_plan_of_the_edge_currents_against_the_flags_it_replaces():
     assert [getattr(_lib, "CURRENTS_" + p.upper()) for p in _PLANS] == list(range(5))
 
 
+# ---------------------------------------------------------------- ... and its choice between the direct and the iterative solve
+def _choice_replay(dmax, iters, resets=(), expect=None):
+    """tdgl_host_solver_choice_replay: (paused per step as a bool array, result struct as a dict)."""
+    import ctypes as C
+
+    from tdgl_amd import _lib
+
+    lib = _lib.load()
+    d = np.ascontiguousarray(dmax, dtype=np.float64)
+    n = len(d)
+    it = np.ascontiguousarray(np.broadcast_to(iters, (n,)), dtype=np.int32)
+    at = np.ascontiguousarray(resets, dtype=np.int64)
+    paused = np.full(max(n, 1), -7, dtype=np.int32)
+    res = _lib.SolverChoiceReplay()
+    f64, i32, i64 = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    status = lib.tdgl_host_solver_choice_replay(n, d.ctypes.data_as(f64), it.ctypes.data_as(i32), len(at), at.ctypes.data_as(i64),
+                                                paused.ctypes.data_as(i32), C.byref(res))
+    assert status == (_lib.TDGL_OK if expect is None else expect)
+    assert set(paused[:n].tolist()) <= {0, 1}
+    return paused[:n].astype(bool), {name: getattr(res, name) for name, _ in _lib.SolverChoiceReplay._fields_ if name != "pad"}
+
+
+def _first(flags, start=0):
+    """Index of the first true entry from `start` on, -1: none."""
+    hits = np.flatnonzero(flags[start:])
+    return int(hits[0]) + start if len(hits) else -1
+
+
+def _windows(values, n):
+    """dmax per step: values[w] throughout window w of 64 steps."""
+    return np.asarray([values(i // 64) for i in range(n)])
+
+
+def test_solver_choice_pauses_a_stationary_state_and_leaves_a_busy_one_alone():
+    """SolverChoice (loop.inc), the rules of tdgl_run's choice between the direct mu solve and AMG-PCG: a state that changes
+    by less than 1e-4 per step is handed to the iterative solve once the direct one has run its 256 steps; one that changes
+    by 1e-3 per step, constantly, never is."""
+    paused, res = _choice_replay(np.full(2000, 1e-5), 0)
+    assert _first(paused) == 256 and paused[256:].all()
+    assert res == {"switches": 1, "pause_hold": 256, "paused": 1}
+    paused, res = _choice_replay(np.full(2000, 1e-3), 0)
+    assert not paused.any()
+    assert res == {"switches": 0, "pause_hold": 256, "paused": 0}
+
+
+def test_solver_choice_pauses_a_relaxing_state():
+    """Four windows of 64 steps, each below 0.9 of the one before and the last below 2e-3, pause the direct solve although
+    no step is below 1e-4; windows that do not fall, or fall by 5 % only, do not."""
+    paused, res = _choice_replay(_windows(lambda w: 1.5e-3 * 0.8 ** w, 2000), 0)
+    assert _first(paused) == 256 and res["switches"] == 1
+    paused, res = _choice_replay(_windows(lambda w: 1.5e-3, 2000), 0)
+    assert not paused.any() and res["switches"] == 0
+    paused, res = _choice_replay(_windows(lambda w: 1.5e-3 * 0.95 ** w, 2000), 0)
+    assert not paused.any() and res["switches"] == 0
+
+
+def test_solver_choice_resumes_on_the_iterations_running_mean():
+    """While paused the running mean of the iterations, 5 (1 - 0.95^j) after j steps of 5, passes 2.5 at j = 14, but a pause
+    lasts 64 steps at least; one that short doubles the wait for the next.  Without iterations the pause never ends."""
+    paused, res = _choice_replay(np.full(832, 1e-5), 5)
+    assert _first(paused) == 256 and _first(~paused, 256) == 320
+    assert res == {"switches": 2, "pause_hold": 512, "paused": 0}
+    paused, res = _choice_replay(np.full(2000, 1e-5), 5)
+    assert _first(paused, 320) == 832
+    assert _choice_replay(np.full(833, 1e-5), 5)[1] == {"switches": 3, "pause_hold": 512, "paused": 1}
+    paused, res = _choice_replay(np.full(4000, 1e-5), 0)
+    assert paused[256:].all() and res["switches"] == 1
+
+
+def test_solver_choice_keeps_the_short_wait_after_a_pause_that_paid():
+    """A pause of 1024 steps or more leaves the next one its wait of 256."""
+    iters = np.zeros(1400, dtype=np.int32)
+    iters[256 + 1100:] = 5
+    paused, res = _choice_replay(np.full(1400, 1e-5), iters)
+    assert _first(paused) == 256 and _first(~paused, 256) == 256 + 1100 + 14 == 1370
+    assert res == {"switches": 2, "pause_hold": 256, "paused": 0}
+
+
+def test_solver_choice_wait_doubles_up_to_its_cap():
+    """Short pauses one after the other: 256, 512, ... 16384 steps of the direct solve between them, never more."""
+    n = 140000
+    paused, res = _choice_replay(np.full(n, 1e-5), 5)
+    starts = np.flatnonzero(paused[1:] & ~paused[:-1]) + 1
+    ends = np.flatnonzero(~paused[1:] & paused[:-1]) + 1
+    assert (ends - starts[:len(ends)] == 64).all()  # every pause lasts its minimum
+    waits = (starts[1:] - ends[:len(starts) - 1]).tolist()
+    assert waits[:7] == [512, 1024, 2048, 4096, 8192, 16384, 16384] and max(waits) == 16384 and len(waits) >= 8
+    assert res["pause_hold"] == 16384
+
+
+def test_solver_choice_reset_returns_to_the_direct_solve_and_the_short_wait():
+    """What voids the history (a new state, stage, boundary values or epsilon) ends a pause and restores the wait of 256; the
+    windows start over; the count of switches goes on."""
+    paused, res = _choice_replay(np.full(1200, 1e-5), 0, resets=[400])
+    assert paused[256:400].all() and not paused[400:656].any()
+    assert _first(paused, 400) == 656 and res == {"switches": 2, "pause_hold": 256, "paused": 1}
+    # ... also a doubled wait, in the middle of the second pause (steps 832 .. 895)
+    paused, res = _choice_replay(np.full(1107, 1e-5), 5, resets=[850])
+    assert paused[832:850].all() and not paused[850:1106].any() and paused[1106]
+    assert res == {"switches": 4, "pause_hold": 256, "paused": 1}
+    # ... and while the direct solve runs: its 256 steps start over
+    paused, res = _choice_replay(np.full(800, 1e-5), 5, resets=[500])
+    assert _first(paused, 320) == 500 + 256 and res == {"switches": 3, "pause_hold": 256, "paused": 1}
+    # a reset in front of a busy stretch: no pause before 256 steps and a full window of quiet ones
+    d = np.full(1200, 1e-5)
+    d[300:700] = 1e-3
+    paused, res = _choice_replay(d, 0, resets=[300])
+    assert not paused[300:700 + 64].any() and _first(paused, 300) == 700 + 64
+
+
+def test_solver_choice_replay_refuses_bad_arguments():
+    import ctypes as C
+
+    from tdgl_amd import _lib
+
+    lib = _lib.load()
+    d, it, p = (C.c_double * 4)(), (C.c_int32 * 4)(), (C.c_int32 * 4)()
+    res = _lib.SolverChoiceReplay()
+    ok = lambda at: (C.c_int64 * len(at))(*at)
+    assert lib.tdgl_host_solver_choice_replay(4, d, it, 0, None, p, C.byref(res)) == _lib.TDGL_OK
+    assert lib.tdgl_host_solver_choice_replay(0, None, None, 0, None, None, C.byref(res)) == _lib.TDGL_OK
+    assert lib.tdgl_host_solver_choice_replay(4, d, it, 2, ok([1, 3]), p, C.byref(res)) == _lib.TDGL_OK
+    for args in ((4, None, it, 0, None, p, C.byref(res)), (4, d, None, 0, None, p, C.byref(res)), (4, d, it, 0, None, None, C.byref(res)),
+                 (4, d, it, 0, None, p, None), (-1, d, it, 0, None, p, C.byref(res)), (4, d, it, -1, None, p, C.byref(res)),
+                 (4, d, it, 2, None, p, C.byref(res)), (4, d, it, 2, ok([3, 1]), p, C.byref(res)),
+                 (4, d, it, 2, ok([1, 1]), p, C.byref(res)), (4, d, it, 1, ok([4]), p, C.byref(res)),
+                 (4, d, it, 1, ok([-1]), p, C.byref(res))):
+        assert lib.tdgl_host_solver_choice_replay(*args) == _lib.TDGL_ERR_ARG, args[:4]
+
+
 def test_collapsed_coarse_operators_are_the_same_cycle():
     """amg.collapsed_operators: intermediate-level M = R (I - A S), the tail as dense G / sparse W /
     dense V (or one dense matrix).  With one tail cycle the chain is the plain V-cycle re-associated;
