@@ -739,6 +739,19 @@ int tdgl_host_solver_choice_replay(int64_t n, const double *dmax, const int32_t 
 int32_t tdgl_host_blr_compress(const double *A, int32_t B, double tol, int32_t kmax, double *Q, double *W);
 /* Probe sites (device.probe_point_indices, solver.py:142, 691-694); n_probe may be 0. */
 int tdgl_set_probes(tdgl_ctx *ctx, const int32_t *sites, int32_t n_probe);
+/* Census inside the time loops: for every accepted step of tdgl_run one int32 row (n_plus, n_minus, w_0 .. w_{L-1}) --
+ * the number of triangles with charge +1 / -1 by the rule of tdgl_vortex_plan_find and the winding around loop l by
+ * its crossing rule (TDGL_WINDING_UNDEFINED in the same cases), of psi after that step: row k belongs to the same
+ * psi as row k of out_theta_probe.  A failed attempt writes no row.  Arguments and checks as tdgl_vortex_plan_create
+ * (reference site numbers; sites_xy [n_sites][2]); n_tri == 0 && n_loops == 0 switches the census off, which is the
+ * default: then tdgl_run does nothing for it.  One kernel per attempt in every loop, no host synchronisation of its
+ * own while probes are read out.  TDGL_ERR_ARG (the previous census stays): as tdgl_vortex_plan_create; a context of
+ * a one-process-per-GPU run. */
+int tdgl_set_census(tdgl_ctx *ctx, const double *sites_xy, int64_t n_tri, const int32_t *elements, int32_t n_loops,
+                    const int64_t *loop_ptr, const int32_t *loop_sites);
+/* The rows of the last tdgl_run, [n_rows][2 + n_loops] (those of the steps completed before an error included):
+ * *n_rows is always the true number, at most capacity_rows rows are written. */
+int tdgl_get_census(tdgl_ctx *ctx, int64_t capacity_rows, int32_t *rows, int64_t *n_rows);
 
 /* ------------------------------------------------------------------ screening
  * options.include_screening (solver.py:304-314, 522-578, 654-688; kernel: tdgl/solver/screening.py).
@@ -1150,6 +1163,10 @@ int tdgl_ensemble_set_epsilon_table(tdgl_ensemble *ens, int32_t r, const double 
                                     const double *times, const double *factor);
 /* The same probe sites for every replica. */
 int tdgl_ensemble_set_probes(tdgl_ensemble *ens, const int32_t *sites, int32_t n_probe);
+/* The context's census (tdgl_set_census, called before this) for every replica; a context without one switches it
+ * off.  get_census: replica r's rows of the last tdgl_ensemble_run, as tdgl_get_census. */
+int tdgl_ensemble_set_census(tdgl_ensemble *ens);
+int tdgl_ensemble_get_census(tdgl_ensemble *ens, int32_t r, int64_t capacity_rows, int32_t *rows, int64_t *n_rows);
 int tdgl_ensemble_get_loop_state(tdgl_ensemble *ens, int32_t r, int64_t *step, double *time, double *runner_dt,
                                  double *tentative_dt);
 /* Up to max_steps[r] <= capacity accepted steps of every replica r, each stopping at end_time[r] (tdgl_run per

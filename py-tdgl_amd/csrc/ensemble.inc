@@ -363,6 +363,13 @@ struct tdgl_ensemble {
     std::vector<StepCtl> h_ctl;
     std::vector<StepRec> h_rec;
     std::vector<double> h_probe;
+    // the census of every replica (census.inc; tdgl_ensemble_set_census): the batch's rows [R][RA_BATCH_MAX][ncol] with
+    // zero counters before every batch, and per replica the rows of the last tdgl_ensemble_run
+    bool census_on = false;
+    int64_t census_serial = 0;  // Census::serial of the context's census that was taken over
+    DevBuf<int32_t> census;
+    std::vector<int32_t> h_census;
+    std::vector<std::vector<int32_t>> census_rows;
     std::vector<int32_t> h_limit;
     std::vector<EnsReplica> rep;
     int64_t stat_rounds = 0, stat_batches = 0;
@@ -807,6 +814,37 @@ extern "C" int tdgl_ensemble_set_probes(tdgl_ensemble *e, const int32_t *sites, 
     return TDGL_OK;
 }
 
+// Takes over the context's census (tdgl_set_census, whose triangles and loops it keeps reading) for every replica; a
+// context without one switches the ensemble's off.
+extern "C" int tdgl_ensemble_set_census(tdgl_ensemble *e) {
+    if (!e) return TDGL_ERR_ARG;
+    tdgl_ctx *ctx = e->ctx;
+    CTX_GUARD(ctx);
+    e->census_on = false;
+    e->census.release();
+    e->h_census.clear();
+    e->census_rows.assign((size_t)e->R, std::vector<int32_t>());
+    if (!ctx->census.on()) return TDGL_OK;
+    const size_t count = (size_t)e->R * RA_BATCH_MAX * ctx->census.ncol();
+    HIP_TRY(ctx, e->census.alloc(count));
+    e->h_census.assign(count, 0);
+    e->census_serial = ctx->census.serial;
+    e->census_on = true;
+    return TDGL_OK;
+}
+
+extern "C" int tdgl_ensemble_get_census(tdgl_ensemble *e, int32_t r, int64_t capacity_rows, int32_t *rows, int64_t *n_rows) {
+    TDGL_TRY(ens_check(e, r));
+    if (capacity_rows < 0 || (capacity_rows > 0 && !rows) || !n_rows) TDGL_FAIL(e->ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_census: bad arguments");
+    const int ncol = e->ctx->census.ncol();
+    const bool on = e->census_on && e->ctx->census.on() && e->census_serial == e->ctx->census.serial;
+    const int64_t have = on ? (int64_t)(e->census_rows[r].size() / ncol) : 0;
+    *n_rows = have;
+    const int64_t k = std::min(have, capacity_rows);
+    if (k > 0) memcpy(rows, e->census_rows[r].data(), (size_t)k * ncol * sizeof(int32_t));
+    return TDGL_OK;
+}
+
 extern "C" int tdgl_ensemble_begin_stage(tdgl_ensemble *e, int32_t r) {
     TDGL_TRY(ens_check(e, r));
     e->rep[r].loop.begin_stage();
@@ -969,6 +1007,9 @@ static void ens_queue_round(tdgl_ensemble *e, bool ramping) {
         hipLaunchKernelGGL(k_ens_probes, dim3((e->np_ + 63) / 64, R), dim3(64), 0, ctx->stream, e->np_, (const int32_t *)e->d_probes.p,
                            (const double2 *)e->psi0.p, (const double2 *)e->psi1.p, (const double *)e->mu.p, e->n_pad, e->probe.p,
                            (const StepCtl *)e->d_ctl.p);
+    if (e->census_on)
+        hipLaunchKernelGGL(k_ens_census, dim3(ctx->census.grid(), R), dim3(BLOCK), 0, ctx->stream, ctx->census.plan(),
+                           (const double2 *)e->psi0.p, (const double2 *)e->psi1.p, e->n_pad, e->census.p, (const StepCtl *)e->d_ctl.p);
 }
 
 // Up to max_steps[r] accepted steps of every replica (the loop of tdgl_run per replica: runner.py:379-433), stopping
@@ -990,6 +1031,11 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
                            e->fac->dense.tiles == e->nt))
         TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_run: the context's substructured factors have been released or replaced");
     const int R = e->R, np_ = e->np_;
+    // (a census set on the context after tdgl_ensemble_set_census, or taken off it: the ensemble's rows no longer fit)
+    if (e->census_on && (!ctx->census.on() || e->census_serial != ctx->census.serial))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_run: the context's census changed; call tdgl_ensemble_set_census again");
+    const int ncen = e->census_on ? ctx->census.ncol() : 0;
+    for (auto &rows : e->census_rows) rows.clear();
     for (int r = 0; r < R; ++r) {
         const EnsReplica &p = e->rep[r];
         if (max_steps[r] < 0 || max_steps[r] > capacity) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_run: max_steps[%d] outside [0, capacity]", r);
@@ -1028,12 +1074,15 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
         HIP_TRY(ctx, hipMemcpyAsync(e->limit.p, e->h_limit.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         if (n_ramping > 0)
             HIP_TRY(ctx, hipMemcpyAsync(e->ramping.p, e->h_ramping.data(), (size_t)R * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        if (ncen > 0) HIP_TRY(ctx, hipMemsetAsync(e->census.p, 0, e->census.n * sizeof(int32_t), ctx->stream));
         for (int s = 0; s < batch; ++s) ens_queue_round(e, n_ramping > 0);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(e->h_ctl.data(), e->d_ctl.p, (size_t)R * sizeof(StepCtl), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(e->h_rec.data(), e->d_rec.p, (size_t)R * RA_BATCH_MAX * sizeof(StepRec), hipMemcpyDeviceToHost, ctx->stream));
         if (np_ > 0)
             HIP_TRY(ctx, hipMemcpyAsync(e->h_probe.data(), e->probe.p, e->h_probe.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (ncen > 0)
+            HIP_TRY(ctx, hipMemcpyAsync(e->h_census.data(), e->census.p, e->h_census.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         e->stat_rounds += batch;
         e->stat_batches += 1;
@@ -1055,6 +1104,10 @@ extern "C" int tdgl_ensemble_run(tdgl_ensemble *e, const int64_t *max_steps, con
                     if (out_mu_probe) memcpy(out_mu_probe + at, row, np_ * sizeof(double));
                     if (out_theta_probe) memcpy(out_theta_probe + at, row + np_, np_ * sizeof(double));
                 }
+            if (ncen > 0) {
+                const int32_t *rows = e->h_census.data() + (size_t)r * RA_BATCH_MAX * ncen;
+                e->census_rows[r].insert(e->census_rows[r].end(), rows, rows + (size_t)acc * ncen);
+            }
             steps_done[r] += acc;
             if (b.reached) reached_end[r] = 1;
             if (b.error) {

@@ -112,15 +112,21 @@ static int step_finish(tdgl_ctx *ctx, double dt, double dmax, double *dt_used, d
                        double *probe_theta, int32_t *pcg_iters);
 
 // Copy the probe read-outs of the steps since the last flush to the caller's arrays
-// (rows [first_row, first_row + probe_ring_count) of out_mu / out_theta, n_probe columns each).
+// (rows [first_row, first_row + probe_ring_count) of out_mu / out_theta, n_probe columns each), and in the same
+// synchronisation the census rows of those steps to the context's host vector (census.inc).
 static int probe_ring_flush(tdgl_ctx *ctx, int64_t first_row, double *out_mu, double *out_theta) {
-    const int np_ = (int)ctx->probes.size(), cnt = ctx->probe_ring_count;
+    const int np_ = (int)ctx->probes.size();
+    const int cnt = np_ > 0 ? ctx->probe_ring_count : 0;
     ctx->probe_ring_count = 0;
-    if (np_ == 0 || cnt == 0) return TDGL_OK;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_probe_out.p, ctx->d_probe_out.p, (size_t)cnt * 2 * np_ * sizeof(double),
-                                hipMemcpyDeviceToHost, ctx->stream));
+    int census_rows = 0;
+    TDGL_TRY(census_flush_queue(ctx, &census_rows));
+    if (cnt == 0 && census_rows == 0) return TDGL_OK;
+    if (cnt > 0)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_probe_out.p, ctx->d_probe_out.p, (size_t)cnt * 2 * np_ * sizeof(double),
+                                    hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->stat_host_syncs += 1;
+    census_flush_keep(ctx, census_rows);
     for (int k = 0; k < cnt; ++k) {
         const double *row = ctx->h_probe_out.p + (size_t)k * 2 * np_;
         if (out_mu) memcpy(out_mu + (first_row + k) * np_, row, np_ * sizeof(double));
@@ -272,6 +278,7 @@ static int step_finish(tdgl_ctx *ctx, double dt, double dmax, double *dt_used, d
                            ctx->psi[nxt].p, ctx->mu.p, ctx->d_probe_out.p + (size_t)ctx->probe_ring_count * 2 * np_);
         ctx->probe_ring_count += 1;
     }
+    if (ctx->census.on()) census_launch(ctx, ctx->psi[nxt].p);
     HIP_TRY(ctx, hipGetLastError());
     *dt_used = dt;
     if (pcg_iters) *pcg_iters = ctx->last_pcg_iters;
@@ -413,6 +420,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
             hipLaunchKernelGGL(k_ra_probes, dim3((np_ + 63) / 64), dim3(64), 0, ctx->stream, np_, (const int32_t *)ctx->d_probes.p,
                                (const double2 *)ctx->psi[0].p, (const double2 *)ctx->psi[1].p, (const double *)ctx->mu.p,
                                ctx->d_probe_out.p, ctx->probe_ring_count, (const StepCtl *)ctx->d_ctl.p);
+        if (ctx->census.on()) census_launch_ra(ctx);
     }
     ctx->psi_status_pending = false;
     const bool guard = !ctx->levels.empty();
@@ -453,6 +461,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
     }
     ctx->lap_valid = true;
     ctx->probe_ring_count += probing ? acc : 0;
+    ctx->census.ring_count += ctx->census.on() ? acc : 0;
     ctx->currents.absorb_batch(done, b.last_accepted, acc, owed_on_entry);
     if (b.error) TDGL_FAIL(ctx, TDGL_ERR_PSI_RETRIES, "%s", ctx->loop.budget_message(-1, b.last_fail_dt).c_str());
     return TDGL_OK;
@@ -467,6 +476,7 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
     *steps_done = 0;
     *reached_end = 0;
     ctx->probe_ring_count = 0;
+    TDGL_TRY(census_begin_run(ctx));
     const int64_t t_enter = now_ns();
     int64_t flushed = 0;  // rows of the probe outputs already delivered
     int status = TDGL_OK;
@@ -481,6 +491,7 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
             const bool want_probes = out_mu_probe || out_theta_probe;
             int batch = (int)std::min<int64_t>(std::min<int64_t>(ctx->ra_batch, RA_BATCH_MAX), max_steps - k);
             if (!ctx->probes.empty() && want_probes) batch = std::min(batch, PROBE_RING_STEPS - ctx->probe_ring_count);
+            if (ctx->census.on()) batch = std::min(batch, PROBE_RING_STEPS - ctx->census.ring_count);
             int acc = 0;
             bool reached = false;
             status = run_ahead(ctx, batch, end_time, out_dt + k, want_probes, &acc, &reached);
@@ -492,7 +503,7 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
             *steps_done = k;
             if (status != TDGL_OK) break;
             ctx->ra_batch = std::min(2 * ctx->ra_batch, RA_BATCH_MAX);
-            if (ctx->probe_ring_count >= PROBE_RING_STEPS) {
+            if (ctx->probe_ring_count >= PROBE_RING_STEPS || ctx->census.ring_count >= PROBE_RING_STEPS) {
                 status = probe_ring_flush(ctx, flushed, out_mu_probe, out_theta_probe);
                 flushed = k;
                 if (status != TDGL_OK) break;
@@ -520,7 +531,7 @@ extern "C" int tdgl_run(tdgl_ctx *ctx, int64_t max_steps, double end_time, doubl
         out_dt[k] = dt;
         if (out_screening_iters) out_screening_iters[k] = ctx->scr_enabled ? ctx->last_screening_iters : 0;
         *steps_done = k + 1;
-        if (ctx->probe_ring_count >= PROBE_RING_STEPS) {
+        if (ctx->probe_ring_count >= PROBE_RING_STEPS || ctx->census.ring_count >= PROBE_RING_STEPS) {
             status = probe_ring_flush(ctx, flushed, out_mu_probe, out_theta_probe);
             flushed = k + 1;
             if (status != TDGL_OK) break;

@@ -602,6 +602,7 @@ static inline int64_t now_ns() {
 #include "fields.inc"
 #include "vortices.inc"
 #include "sample.inc"
+#include "census.inc"
 #include "run.inc"
 
 extern "C" int tdgl_set_state(tdgl_ctx *ctx, const double *psi, const double *mu) {

@@ -339,6 +339,37 @@ struct StepRec {
     int ok, pad;
 };
 
+// The census of the live state (census.inc): per accepted step one int32 row (n_plus, n_minus, w_0 .. w_{L-1}) --
+// charged triangles by sign and the winding around every loop.  Triangles and loop sites are in the context's internal
+// site numbering.  A device ring of PROBE_RING_STEPS rows rides along in the time loops like the probe ring and is
+// flushed with it; the rows of the last tdgl_run collect on the host.  Off (no triangles and no loops): nothing allocated.
+struct CensusPlan {  // what the kernels take by value
+    int32_t n_tri, nblk_tri, n_loops, ncol;
+    const int32_t *elements;  // [3][n_tri]: vertex k of triangle t at k * n_tri + t
+    const int8_t *orient;     // [n_tri]
+    const int64_t *loop_ptr;  // [n_loops + 1]
+    const int32_t *loop_sites;
+};
+constexpr int CENSUS_MAX_BLOCKS = 1024;  // triangle workgroups of one launch (they stride): bounds the atomics per step at 2 x this
+struct Census {
+    int32_t n_tri = 0, n_loops = 0;
+    int64_t serial = 0;  // which tdgl_set_census call made this one (an ensemble that took it over checks it is still the same)
+    DevBuf<int32_t> elements, loop_sites, ring;  // ring: [PROBE_RING_STEPS][ncol], counter columns zero between uses
+    DevBuf<int8_t> orient;
+    DevBuf<int64_t> loop_ptr;
+    PinnedBuf<int32_t> h_ring;
+    int ring_count = 0;         // rows written since the last flush
+    std::vector<int32_t> rows;  // [n][ncol] of the last tdgl_run
+    bool on() const { return n_tri > 0 || n_loops > 0; }
+    int ncol() const { return 2 + n_loops; }
+    CensusPlan plan() const {
+        return {n_tri, tri_blocks(), n_loops, ncol(), elements.p, orient.p, loop_ptr.p, loop_sites.p};
+    }
+    int32_t tri_blocks() const { return std::min((n_tri + BLOCK - 1) / BLOCK, CENSUS_MAX_BLOCKS); }
+    // workgroups of one launch: the triangles', then one wavefront per loop
+    unsigned grid() const { return (unsigned)(tri_blocks() + (n_loops + BLOCK / WAVE - 1) / (BLOCK / WAVE)); }
+};
+
 // The device arrays of a FieldDrive, one set per context and per replica of an ensemble: the K bases (slot k at 2 m_pad k,
 // edge-permuted), the optional A_0, the descriptors with their table pool (all times, then all values), and for loops the
 // edge centres, the loops' descriptors and their pool (all times, then all cx, cy, cz, currents)
@@ -957,6 +988,7 @@ struct tdgl_ctx {
     tdgl::DevBuf<double> d_probe_out;      // ring buffer [PROBE_RING_STEPS][2 * n_probe]: mu | theta per step
     tdgl::PinnedBuf<double> h_probe_out;   // the same shape
     int probe_ring_count = 0;              // steps written since the last flush (run.inc: probe_ring_flush)
+    tdgl::Census census;                   // vortex counts and loop windings per accepted step (census.inc), flushed with the probes
 
     tdgl::LoopState loop;                  // controller, Runner.dt / time / step, retry and ramp state (loop.inc)
     // counters since the last reset (tdgl_get_step_stats): steps accepted, failed psi updates that were

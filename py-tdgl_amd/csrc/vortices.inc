@@ -18,22 +18,11 @@
 // tdgl_vortex_plan_link links the cores of consecutive frames into tracks: k_vortex_nearest, k_vortex_mutual and
 // k_vortex_event_keys, further down.
 
+#include "vortex_rules.h"  // vortex_triangle_winding, vortex_loop_winding: shared with census.inc
+
 namespace tdgl {
 
 constexpr int VORTEX_WAVES = BLOCK / WAVE;
-
-__device__ inline int vortex_sign(double p, double q) { return (p > q) - (p < q); }
-
-// +1 / -1 when psi winds once around the triangle (a, b, c) in the order given, 0 otherwise (also for a vertex that
-// is zero or NaN: every comparison is then false)
-__device__ inline int vortex_triangle_winding(double2 a, double2 b, double2 c) {
-    const int sab = vortex_sign(a.x * b.y, a.y * b.x);
-    const int sbc = vortex_sign(b.x * c.y, b.y * c.x);
-    const int sca = vortex_sign(c.x * a.y, c.y * a.x);
-    if (sab > 0 && sbc > 0 && sca > 0) return 1;
-    if (sab < 0 && sbc < 0 && sca < 0) return -1;
-    return 0;
-}
 
 // psi: [frames][n_sites] (re, im); charge: [frames][n_tri]; block_count: [frames][gridDim.x]
 __global__ __launch_bounds__(BLOCK) void k_vortex_charge(int64_t n_tri, int64_t n_sites,
@@ -150,24 +139,8 @@ __global__ __launch_bounds__(BLOCK) void k_vortex_windings(int frames, int n_loo
     const int l = (int)(item % n_loops);
     const int lane = threadIdx.x & (WAVE - 1);
     const double2 *__restrict__ z = psi + f * n_sites;
-    const int64_t e0 = loop_ptr[l], e1 = loop_ptr[l + 1];
-    int w = 0, undefined = 0;
-    for (int64_t e = e0 + lane; e < e1; e += WAVE) {
-        const double2 u = z[loop_sites[e]];
-        const double2 v = z[loop_sites[e + 1 < e1 ? e + 1 : e0]];
-        if ((u.x == 0.0 && u.y == 0.0) || !isfinite(u.x) || !isfinite(u.y)) undefined = 1;
-        const double p = u.x * v.y, q = u.y * v.x;
-        const double rr = u.x * v.x, ii = u.y * v.y;
-        if (p == q && (rr < 0.0 || ii < 0.0)) undefined = 1;
-        if (u.y <= 0.0 && v.y > 0.0 && p > q) ++w;
-        if (u.y > 0.0 && v.y <= 0.0 && p < q) --w;
-    }
-#pragma unroll
-    for (int d = WAVE / 2; d > 0; d >>= 1) {
-        w += __shfl_xor(w, d, WAVE);
-        undefined |= __shfl_xor(undefined, d, WAVE);
-    }
-    if (lane == 0) windings[f * n_loops + l] = undefined ? TDGL_WINDING_UNDEFINED : w;
+    const int w = vortex_loop_winding(z, loop_sites, loop_ptr[l], loop_ptr[l + 1], lane);
+    if (lane == 0) windings[f * n_loops + l] = w;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -3,6 +3,8 @@
 Public surface (mirrors `tdgl/__init__.py:1-23` of the reference for the solver path):
 ``Layer, Polygon, Device, SolverOptions, SolverOptionsError, SparseSolver, solve, TDGLSolver,
 Solution`` and the ``geometry`` helpers; beyond it, ``solve_ensemble`` (many replicas of one device at once)
+``SolverOptions.vortex_census`` (vortex counts and boundary windings at every step, counted inside the time loop:
+``DynamicsData.vortex_counts`` / ``windings``, ``WINDING_UNDEFINED``),
 ``FieldEvaluator`` (fields of the currents at many points, on the device), ``VortexFinder`` / ``Vortices`` (vortex
 cores, charges and boundary windings of saved steps, on the device), ``track_vortices`` / ``VortexTracks`` (those cores
 linked into tracks from frame to frame) and ``CurrentSampler`` (sheet currents and psi
@@ -18,7 +20,7 @@ from .parameter import (  # noqa: F401
     SeparableEpsilon, TabulatedCurrents, TabulatedRamp,
 )
 from .options import SolverOptions, SolverOptionsError, SparseSolver  # noqa: F401
-from .solution import BiotSavartField, BoundaryPhases, DynamicsData, Fluxoid, Solution, TDGLData  # noqa: F401
+from .solution import WINDING_UNDEFINED, BiotSavartField, BoundaryPhases, DynamicsData, Fluxoid, Solution, TDGLData  # noqa: F401
 from .solver import SolverResult, TDGLSolver, solve  # noqa: F401
 from .ensemble import ENSEMBLE_MAX_SITES, solve_ensemble  # noqa: F401
 from .fields import FieldEvaluator  # noqa: F401

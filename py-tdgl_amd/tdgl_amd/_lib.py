@@ -387,6 +387,9 @@ SIGNATURES = {
     "tdgl_set_state": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_set_controller": (C.c_int, [_CTX, C.POINTER(Controller)]),
     "tdgl_set_probes": (C.c_int, [_CTX, c_i32p, C.c_int32]),
+    # census inside the time loops (csrc/census.inc)
+    "tdgl_set_census": (C.c_int, [_CTX, c_f64p, C.c_int64, c_i32p, C.c_int32, c_i64p, c_i32p]),
+    "tdgl_get_census": (C.c_int, [_CTX, C.c_int64, c_i32p, C.POINTER(C.c_int64)]),
     "tdgl_host_mean_tail": (C.c_double, [c_f64p, C.c_int64, C.c_int32]),
     "tdgl_host_loop_replay": (
         C.c_int,
@@ -478,6 +481,8 @@ SIGNATURES = {
     "tdgl_ensemble_set_controller": (C.c_int, [_ENS, C.c_int32, C.POINTER(Controller)]),
     "tdgl_ensemble_begin_stage": (C.c_int, [_ENS, C.c_int32]),
     "tdgl_ensemble_set_probes": (C.c_int, [_ENS, c_i32p, C.c_int32]),
+    "tdgl_ensemble_set_census": (C.c_int, [_ENS]),
+    "tdgl_ensemble_get_census": (C.c_int, [_ENS, C.c_int32, C.c_int64, c_i32p, C.POINTER(C.c_int64)]),
     "tdgl_ensemble_get_loop_state": (C.c_int, [_ENS, C.c_int32, C.POINTER(C.c_int64), c_f64p, c_f64p, c_f64p]),
     "tdgl_ensemble_run": (
         C.c_int,

@@ -30,6 +30,7 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC for RCCL 
 
 from .amg import build_hierarchy
 from .hipcore import TDGLContext, poisson_matrix
+from .options import SolverOptionsError
 from .partition import (DeepPlanner, build_local_problem, deep_plan_applicable, link_deep_plans, local_hierarchy_level0,
                         rcb_partition)
 
@@ -205,6 +206,9 @@ class DistributedTDGL:
         self.mesh = mesh
         self.options = options
         options.validate()
+        if options.vortex_census:
+            raise SolverOptionsError("vortex_census=True is not supported in one-process-per-GPU mode (a rank holds a "
+                                     "part of every loop); run on one GPU, or count the saved steps with VortexFinder.")
         if options.screening_method == "tree" and (options.include_screening or screening is not None):
             raise ValueError("screening_method='tree' is not supported in one-process-per-GPU mode; use 'direct'.")
         if payload is None:

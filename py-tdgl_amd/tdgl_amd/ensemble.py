@@ -27,11 +27,11 @@ from . import _lib
 from ._lib import c128, f64, p_f64, p_i32
 from .device import Device
 from .hipcore import (FIELD_TERMS_MAX, TDGLContext, controller_struct, epsilon_table_args, link_table_args, link_terms_args,
-                      mu_boundary_table_args, probe_args, read_loop_state)
+                      mu_boundary_table_args, probe_args, read_census, read_loop_state)
 from .options import SolverOptions
 from .runloop import RunRecord, check_epsilon_table, check_seed
 from .solution import Solution
-from .solver import TDGLSolver
+from .solver import TDGLSolver, install_census
 
 # The ensemble's mu solve by mesh size, set by measurement (DESIGN.md "Ensembles").  Up to ENSEMBLE_DENSE_MAX_SITES the
 # dense inverse (n^2 / 2 doubles, read once per 16 replicas and round: at R = 32 the ensemble's aggregate rate over
@@ -258,6 +258,7 @@ class EnsembleContext:
         self._lib = _lib.load()
         self.R = int(n_replicas)
         self.n_probe = 0
+        self.n_census = 0  # columns of a census row as taken over by set_census; 0: off
         self._ens = C.c_void_p()
         self._chk(self._lib.tdgl_ensemble_create(C.byref(self._ens), ctx._ctx, self.R))
 
@@ -339,6 +340,12 @@ class EnsembleContext:
         sites, self.n_probe = probe_args(sites)
         self._chk(self._lib.tdgl_ensemble_set_probes(self._ens, sites, self.n_probe))
 
+    def set_census(self):
+        """Take over the context's census (``ctx.set_census(...)`` first) for every replica: `run` then returns each
+        replica's ``census`` rows."""
+        self._chk(self._lib.tdgl_ensemble_set_census(self._ens))
+        self.n_census = self.ctx.n_census
+
     def begin_stage(self, r):
         self._chk(self._lib.tdgl_ensemble_begin_stage(self._ens, r))
 
@@ -364,8 +371,12 @@ class EnsembleContext:
             self._ens, ms.ctypes.data_as(C.POINTER(C.c_int64)), p_f64(et), cap, p_f64(dts), p_f64(mu_p), p_f64(th_p),
             done.ctypes.data_as(C.POINTER(C.c_int64)), p_i32(reached), p_i32(failed))
         self._chk(status)
+        ncen = self.n_census
+        census = [read_census(self._chk, ncen, self._lib.tdgl_ensemble_get_census, self._ens, r) if ncen else None
+                  for r in range(R)]
         return [dict(dt=dts[r, :done[r]], mu=None if mu_p is None else mu_p[r, :done[r]],
-                     theta=None if th_p is None else th_p[r, :done[r]], reached_end=bool(reached[r])) for r in range(R)]
+                     theta=None if th_p is None else th_p[r, :done[r]], reached_end=bool(reached[r]), census=census[r])
+                for r in range(R)]
 
     def get_state(self, r, currents=True):
         n, m = self.ctx.n, self.ctx.m
@@ -462,6 +473,11 @@ class EnsembleSolver:
         opts = self.options
         reps, R = self.reps, len(self.reps)
         ens.set_probes(reps[0].probe_points)
+        if opts.vortex_census:
+            names = install_census(ctx, reps[0].device)
+            ens.set_census()
+            for rep in reps:
+                rep.census_loops = names
         for r, rep in enumerate(reps):
             rep.field.install_replica(ens, r, rep.current_A_applied)
             ens.set_mu_boundary(r, rep.mu_boundary)

@@ -164,6 +164,26 @@ def controller_struct(dt_init, dt_max, adaptive, adaptive_window, max_solve_retr
                            int(max_solve_retries), float(adaptive_time_step_multiplier))
 
 
+def census_args(triangles, loops) -> tuple:
+    """``(n_tri, elements, n_loops, loop_ptr, loop_sites)`` of tdgl_set_census (the conventions of `VortexPlan`)."""
+    elements = i32(np.asarray(triangles if triangles is not None else []).reshape(-1, 3))
+    loops = [i32(np.asarray(loop).reshape(-1)) for loop in (loops if loops is not None else ())]
+    loop_ptr = np.zeros(len(loops) + 1, dtype=np.int64)
+    loop_ptr[1:] = np.cumsum([len(loop) for loop in loops])
+    loop_sites = i32(np.concatenate(loops)) if loops else np.zeros(0, dtype=np.int32)
+    return len(elements), elements, len(loops), loop_ptr, loop_sites
+
+
+def read_census(chk, ncol, getter, *handle) -> np.ndarray:
+    """All rows behind ``getter(*handle, capacity, rows, n_rows)``: asked for their number first."""
+    n = C.c_int64(0)
+    chk(getter(*handle, 0, None, C.byref(n)))
+    rows = np.zeros((n.value, ncol), dtype=np.int32)
+    if n.value:
+        chk(getter(*handle, n.value, p_i32(rows), C.byref(n)))
+    return rows
+
+
 def probe_args(sites) -> tuple:
     """``(sites, n_probe)`` of tdgl_set_probes; None or an empty list: no probes."""
     sites = i32([] if sites is None else sites)
@@ -304,6 +324,7 @@ class TDGLContext:
         self.m = len(em.edges)
         self.n_boundary = len(em.boundary_edge_indices)
         self.n_probe = 0
+        self.n_census = 0  # columns of a census row (2 + loops); 0: the census is off
         edges = i32(em.edges)
         self.n_owned = int(n_owned) if n_owned else self.n
         if n_owned:
@@ -1378,6 +1399,29 @@ class TDGLContext:
         sites, self.n_probe = probe_args(sites)
         self._chk(self._lib.tdgl_set_probes(self._ctx, sites, self.n_probe))
 
+    def set_census(self, points=None, triangles=None, loops=()):
+        """Count vortices and loop windings at every accepted step inside `run` (csrc/census.inc): ``points`` [n, 2],
+        ``triangles`` [t, 3] and ``loops`` (site-index sequences, closed, the first site not repeated) as for
+        `VortexPlan`, in the reference numbering.  ``run`` then returns ``census`` [k, 2 + L] int32 rows
+        ``(n_plus, n_minus, w_0 .. w_{L-1})`` with `WINDING_UNDEFINED` where a winding is not defined.  No triangles and
+        no loops (the default arguments): off."""
+        n_tri, elements, n_loops, loop_ptr, loop_sites = census_args(triangles, loops)
+        if n_tri:  # (the points give the triangles' orientations)
+            points = f64(points)
+            if points.shape != (self.n, 2):
+                raise ValueError(f"Expected points [{self.n}, 2] (got {points.shape}).")
+        else:
+            points = None
+        self._chk(self._lib.tdgl_set_census(self._ctx, p_f64(points), n_tri, p_i32(elements), n_loops, p_i64(loop_ptr),
+                                            p_i32(loop_sites)))
+        self.n_census = (2 + n_loops) if (n_tri or n_loops) else 0
+
+    def census(self):
+        """The census rows of the last `run`, [k, 2 + L] int32, or None when the census is off."""
+        if not self.n_census:
+            return None
+        return read_census(self._chk, self.n_census, self._lib.tdgl_get_census, self._ctx)
+
     # -- time loop --------------------------------------------------------------------------
     def begin_stage(self):
         self._chk(self._lib.tdgl_begin_stage(self._ctx))
@@ -1403,7 +1447,7 @@ class TDGLContext:
         return dict(
             dt=dts[:k], mu=None if mu_p is None else mu_p[:k],
             theta=None if th_p is None else th_p[:k], pcg_iters=iters[:k],
-            screening_iterations=scr_iters[:k], reached_end=bool(reached.value),
+            screening_iterations=scr_iters[:k], reached_end=bool(reached.value), census=self.census(),
         )
 
     # -- screening (solver.py:522-578, 654-688) -----------------------------------------------

@@ -213,8 +213,13 @@ def write_solution_group(file, solution) -> None:
     for k, v in dataclasses.asdict(solution.options).items():
         if k == "sparse_solver":
             v = getattr(v, "value", v)
+        if k == "vortex_census" and not v:  # (off: the file is what it was before the option existed)
+            continue
         if v is not None:
             options_grp.attrs[k] = v
+    loop_names = getattr(getattr(solution, "dynamics", None), "loop_names", None)
+    if loop_names is not None:  # vortex_census: which loop each row of running_state/windings belongs to
+        group.attrs["census_loop_names"] = [str(name) for name in loop_names]
     group.attrs["time_created"] = getattr(solution, "time_created", datetime.now()).isoformat()
     group.attrs["current_units"] = solution.options.current_units
     group.attrs["field_units"] = solution.options.field_units
@@ -261,6 +266,8 @@ def _running_state_buffers(solution):
         names["mu"], names["theta"] = np.asarray(dyn.mu), np.asarray(dyn.theta)
     if dyn is not None and dyn.screening_iterations is not None:
         names["screening_iterations"] = np.asarray(dyn.screening_iterations, dtype=float)[None, :]
+    if dyn is not None:  # vortex_census: floats, NaN for a winding that is not defined
+        names.update(dyn._census_as_float())
     out = []
     prev_step = 0
     for s in saves:

@@ -90,6 +90,9 @@ class SolverOptions:
     # binary16; 1 = fp32 only; False = fp64
     pcg_precond_fp32: Union[bool, int] = True
     edge_currents_every_step: bool = True
+    # count the charged mesh triangles and the winding around every boundary loop (device.boundary_sites()) after every
+    # step, inside the time loop: DynamicsData.vortex_counts / windings; single-GPU runs and ensembles
+    vortex_census: bool = False
     device_id: int = 0
     # --- evaluation of the screening sum (no reference counterpart) ---
     # "direct": all pairs (edge centre, site); "tree": barycentric Lagrange treecode of that degree and acceptance
@@ -144,3 +147,7 @@ class SolverOptions:
             fail(f"adaptive_window must be >= 0 (got {self.adaptive_window}).")
         if self.save_every < 1:
             fail(f"save_every must be >= 1 (got {self.save_every}).")
+        import numpy as np
+
+        if not isinstance(self.vortex_census, (bool, np.bool_)):
+            fail(f"vortex_census must be a bool (got {self.vortex_census!r}).")

@@ -12,9 +12,18 @@ needs the library, so a scripted source can replay a recorded run through either
 import numpy as np
 
 from .io import RunningState
-from .solution import DynamicsData, Solution, TDGLData
+from .solution import WINDING_UNDEFINED, DynamicsData, Solution, TDGLData
 
 STAGES = ("Thermalizing", "Simulating")
+
+
+def census_columns(census) -> dict:
+    """The int32 census rows [k, 2 + L] of a ``run`` as the running state's float columns: ``vortex_counts`` [k, 2] and
+    ``windings`` [k, L] with NaN where a winding is not defined."""
+    census = np.asarray(census)
+    windings = census[:, 2:].astype(float)
+    windings[census[:, 2:] == WINDING_UNDEFINED] = np.nan
+    return dict(vortex_counts=census[:, :2].astype(float), windings=windings)
 
 
 def check_seed(seed, device, mesh, prefix: str = "") -> None:
@@ -83,7 +92,8 @@ class RunRecord:
         self.done = False
         self.seeded = solver.seed_solution is not None or getattr(solver, "seed_state", None) is not None
         self.saved, self.saved_meta = [], []
-        self.dyn = dict(dt=[], time=[], mu=[], theta=[], pcg_iters=[], screening_iterations=[])
+        self.dyn = dict(dt=[], time=[], mu=[], theta=[], pcg_iters=[], screening_iterations=[], census=[])
+        self.census_loops = getattr(solver, "census_loops", None)  # names of the census' loops; None: no census
         self.n_steps = dict.fromkeys(STAGES, 0)
         self.running = None  # the per-step scalars between two saves: kept for a handler only
         if handler is not None:
@@ -92,6 +102,8 @@ class RunRecord:
                 sizes["mu"] = sizes["theta"] = len(solver.probe_points)
             if solver.screening is not None:
                 sizes["screening_iterations"] = 1
+            if self.census_loops is not None:
+                sizes["vortex_counts"], sizes["windings"] = 2, len(self.census_loops)
             self.running = RunningState(sizes, self.options.save_every)
         self.loop = None  # the loop state before the steps last asked for
         source.begin_stage()
@@ -122,6 +134,8 @@ class RunRecord:
         k, reached = len(res["dt"]), res["reached_end"]
         self.n_steps[name] += k
         if self.running is not None:
+            if self.census_loops is not None:
+                res = dict(res, **census_columns(res["census"]))
             cols = {key: res[key] for key in self.running.names_and_sizes if res[key] is not None}
             # (the step that ends the loop is written into the buffer but not counted, runner.py:429-432)
             self.running.extend({key: v[:k - 1] if reached else v for key, v in cols.items()})
@@ -153,7 +167,12 @@ class RunRecord:
         dt = cat(d["dt"])
         # (a library that reports no iteration counts -- the ensemble's direct mu solve -- took none)
         pcg = cat(d["pcg_iters"]) if d["pcg_iters"] else np.zeros(len(dt), dtype=np.int32)
+        census = {}
+        if self.census_loops is not None:
+            rows = cat(d["census"]).astype(np.int32).reshape(-1, 2 + len(self.census_loops))
+            census = dict(vortex_counts=rows[:, :2].T.copy(), windings=rows[:, 2:].T.copy(), loop_names=tuple(self.census_loops))
         dynamics = DynamicsData(
+            **census,
             dt=dt, time=cat(d["time"]), mu=cat(d["mu"]).T if d["mu"] else None,
             theta=cat(d["theta"]).T if d["theta"] else None, pcg_iterations=pcg,
             screening_iterations=cat(d["screening_iterations"]) if s.screening is not None else None,

@@ -104,6 +104,9 @@ class TDGLData:
         )
 
 
+WINDING_UNDEFINED = -(2 ** 31)  # a winding that is not defined (TDGL_WINDING_UNDEFINED, hipcore.WINDING_UNDEFINED)
+
+
 @dataclass
 class DynamicsData:
     """Per-step scalars of the saved stage (cf. `tdgl/solution/data.py:145-330`)."""
@@ -114,10 +117,48 @@ class DynamicsData:
     theta: Optional[np.ndarray] = None   # [n_probe, n_steps]
     pcg_iterations: Optional[np.ndarray] = None
     screening_iterations: Optional[np.ndarray] = None  # include_screening only
+    # SolverOptions.vortex_census only: charged triangles by sign and the winding around every boundary loop after
+    # each step, counted inside the time loop
+    vortex_counts: Optional[np.ndarray] = None  # [2, n_steps] int32: n_plus, n_minus
+    windings: Optional[np.ndarray] = None       # [L, n_steps] int32, WINDING_UNDEFINED where not defined
+    loop_names: Optional[tuple] = None          # the L loops: the keys of device.boundary_sites()
 
     def __post_init__(self):
         if self.time is None:  # data.py:167-168
             self.time = np.cumsum(self.dt)
+
+    def net_vorticity(self) -> np.ndarray:
+        """n_plus - n_minus per step."""
+        if self.vortex_counts is None:
+            raise ValueError("No vortex census available (SolverOptions.vortex_census).")
+        return self.vortex_counts[0].astype(np.int64) - self.vortex_counts[1]
+
+    def _loop_index(self, name) -> int:
+        if self.windings is None:
+            raise ValueError("No vortex census available (SolverOptions.vortex_census).")
+        names = list(self.loop_names) if self.loop_names is not None else []
+        if name in names:
+            return names.index(name)
+        if isinstance(name, numbers.Integral) and not isinstance(name, bool) and -len(self.windings) <= name < len(self.windings):
+            return int(name)
+        raise KeyError(f"No loop {name!r}; the census has {names or len(self.windings)}.")
+
+    def winding(self, name) -> np.ndarray:
+        """The winding around loop ``name`` (or its row number) per step as floats, NaN where it is not defined."""
+        w = self.windings[self._loop_index(name)]
+        out = w.astype(float)
+        out[w == WINDING_UNDEFINED] = np.nan
+        return out
+
+    def winding_changes(self, name):
+        """Where a defined winding around loop ``name`` differs from the previous defined one: ``(steps, times, old,
+        new)``, the step indices into this object's arrays, their times and the two integer values."""
+        w = self.windings[self._loop_index(name)]
+        (defined,) = np.nonzero(w != WINDING_UNDEFINED)
+        values = w[defined]
+        (at,) = np.nonzero(values[1:] != values[:-1])
+        steps = defined[at + 1]
+        return steps, np.asarray(self.time)[steps], values[at].astype(np.int64), values[at + 1].astype(np.int64)
 
     def time_slice(self, tmin: float = -np.inf, tmax: float = np.inf) -> np.ndarray:
         (indices,) = np.where((self.time >= tmin) & (self.time <= tmax))
@@ -159,16 +200,40 @@ class DynamicsData:
         return DynamicsData(dt=(ts[1] - ts[0]) * np.ones_like(ts), mu=mu, theta=theta)
 
     @staticmethod
+    def _census_from_float(counts, windings):
+        """The census columns of a file (floats, NaN for an undefined winding) as the int32 arrays kept here."""
+        if counts is not None:
+            counts = np.atleast_2d(np.asarray(counts)).astype(np.int32)
+        if windings is not None:
+            w = np.atleast_2d(np.asarray(windings, dtype=float))
+            windings = np.where(np.isnan(w), float(WINDING_UNDEFINED), w).astype(np.int32)
+        return counts, windings
+
+    def _census_as_float(self):
+        """``{name: float array}`` of the census columns present: what the files hold."""
+        out = {}
+        if self.vortex_counts is not None:
+            out["vortex_counts"] = np.asarray(self.vortex_counts, dtype=float)
+        if self.windings is not None:
+            out["windings"] = np.array([self.winding(l) for l in range(len(self.windings))]).reshape(np.shape(self.windings))
+        return out
+
+    @staticmethod
     def from_hdf5(h5file, step_min: Union[int, None] = None, step_max: Union[int, None] = None) -> "DynamicsData":
         """From ``DynamicsData.to_hdf5`` output, or from the ``running_state`` buffers of the saved
         steps of an output file: concatenated, the zero padding (dt = 0) removed (data.py:369-428)."""
         if "theta" in h5file or ("dt" in h5file and "data" not in h5file):
             get = lambda k: np.array(h5file[k]) if k in h5file else None  # noqa: E731
+            counts, windings = DynamicsData._census_from_float(get("vortex_counts"), get("windings"))
+            names = tuple(str(s.decode() if isinstance(s, bytes) else s) for s in np.atleast_1d(get("loop_names"))) \
+                if "loop_names" in h5file else None
             return DynamicsData(dt=get("dt"), mu=get("mu"), theta=get("theta"),
-                                screening_iterations=get("screening_iterations"))
+                                screening_iterations=get("screening_iterations"), vortex_counts=counts,
+                                windings=windings, loop_names=names)
         if step_min is None:
             step_min, step_max = get_data_range(h5file)
-        cols: Dict[str, list] = {"dt": [], "mu": [], "theta": [], "screening_iterations": []}
+        cols: Dict[str, list] = {"dt": [], "mu": [], "theta": [], "screening_iterations": [], "vortex_counts": [],
+                                 "windings": []}
         for i in range(step_min, step_max + 1):
             grp = h5file[f"data/{i}"]
             if "running_state" not in grp:
@@ -180,7 +245,13 @@ class DynamicsData:
         dt = np.concatenate([np.atleast_1d(d) for d in cols["dt"]])
         mask = dt > 0
         two_d = lambda parts: np.concatenate([np.atleast_2d(p) for p in parts], axis=1)[..., mask]  # noqa: E731
+        counts, windings = DynamicsData._census_from_float(two_d(cols["vortex_counts"]) if cols["vortex_counts"] else None,
+                                                           two_d(cols["windings"]) if cols["windings"] else None)
+        names = None
+        if windings is not None and "solution" in h5file and "census_loop_names" in h5file["solution"].attrs:
+            names = tuple(n.decode() if isinstance(n, bytes) else str(n) for n in h5file["solution"].attrs["census_loop_names"])
         return DynamicsData(
+            vortex_counts=counts, windings=windings, loop_names=names,
             dt=dt[mask],
             mu=two_d(cols["mu"]) if cols["mu"] else None,
             theta=two_d(cols["theta"]) if cols["theta"] else None,
@@ -193,6 +264,10 @@ class DynamicsData:
         for name in ("mu", "theta", "screening_iterations"):
             if getattr(self, name) is not None:
                 h5group[name] = getattr(self, name)
+        for name, values in self._census_as_float().items():
+            h5group[name] = values
+        if self.loop_names is not None and self.windings is not None:
+            h5group["loop_names"] = np.array([str(n).encode() for n in self.loop_names])
 
 
 BACKENDS = ("host", "hip")

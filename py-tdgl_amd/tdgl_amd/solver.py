@@ -31,7 +31,7 @@ from . import applied_field
 from .device import Device, TerminalInfo
 from .io import DataHandler, write_solution_group
 from .operators import MeshOperators
-from .options import SolverOptions
+from .options import SolverOptions, SolverOptionsError
 from .runloop import RunRecord, check_epsilon_table, check_seed
 from .solution import Solution
 
@@ -78,6 +78,16 @@ def uniform_field_vector_potential(x, y, B):
     xs = x - (x.min() + np.ptp(x) / 2)
     ys = y - (y.min() + np.ptp(y) / 2)
     return np.stack([-B * ys / 2, B * xs / 2, np.zeros_like(xs)], axis=1)
+
+
+def install_census(ctx, device) -> tuple:
+    """``SolverOptions.vortex_census``: set the context's census from the device's mesh and boundary loops -- the loops
+    and names `VortexFinder` uses by default -- and return the loops' names."""
+    if device is None or getattr(device, "mesh", None) is None:
+        raise SolverOptionsError("vortex_census=True needs a Device with a mesh (its triangles and boundary loops).")
+    loops = device.boundary_sites()
+    ctx.set_census(device.points, device.triangles, list(loops.values()))
+    return tuple(loops)
 
 
 class TDGLSolver:
@@ -313,6 +323,9 @@ class TDGLSolver:
         self.ctx.set_epsilon(self.epsilon)
         self.ctx.set_mu_boundary(self.mu_boundary)
         self.ctx.set_probes(self.probe_points)
+        self.census_loops = None  # names of the loops of the in-loop census; None: off
+        if options.vortex_census:
+            self.census_loops = install_census(self.ctx, getattr(self, "device", None))
         self.ctx.set_controller(
             options.dt_init, options.dt_max, options.adaptive, options.adaptive_window,
             options.max_solve_retries, options.adaptive_time_step_multiplier,
