@@ -752,6 +752,33 @@ int tdgl_set_census(tdgl_ctx *ctx, const double *sites_xy, int64_t n_tri, const 
 /* The rows of the last tdgl_run, [n_rows][2 + n_loops] (those of the steps completed before an error included):
  * *n_rows is always the true number, at most capacity_rows rows are written. */
 int tdgl_get_census(tdgl_ctx *ctx, int64_t capacity_rows, int32_t *rows, int64_t *n_rows);
+/* Records of the vortex cores themselves, out of the census' launch: after every accepted step whose running index --
+ * counted from this call on, the first step being 0, across tdgl_run calls -- is divisible by `every`, one record per
+ * charged triangle of psi after that step: the triangle (a row of the `elements` given to tdgl_set_census), its charge
+ * +1 / -1 and the zero of the linear interpolant, exactly what tdgl_vortex_plan_find gives for that psi, sorted by
+ * triangle.  sites_xy [n_sites][2] as for tdgl_set_census.  capacity: records the device keeps between two flushes of
+ * the census ring (every 1,024 steps and when tdgl_run ends); a step whose records reach beyond it is incomplete and
+ * delivers none, and so does every later step up to the next flush, while the census rows stay exact.  capacity == 0
+ * switches the records off, and so does every tdgl_set_census.  No kernel and no host synchronisation per step is
+ * added; a flush that holds records synchronises once more.  The ensemble does not record.  TDGL_ERR_ARG (the previous
+ * state stays): no census or one without triangles; capacity < 0; every < 1; a null array; a context of a
+ * one-process-per-GPU run. */
+int tdgl_set_core_records(tdgl_ctx *ctx, const double *sites_xy, int64_t capacity, int64_t every);
+/* The records of the last tdgl_run (those of the steps completed before an error included).  *n_steps recorded steps
+ * and *n_records records are always the true numbers.  Within capacity_steps: step[k] the row of the step among the
+ * run's accepted steps (row k of out_dt), count[k] its records, complete[k]; within capacity_records, step after step:
+ * triangles, charges, xy [..][2]. */
+int tdgl_get_core_records(tdgl_ctx *ctx, int64_t capacity_steps, int64_t *step, int64_t *count, int32_t *complete,
+                          int64_t capacity_records, int32_t *triangles, int32_t *charges, double *xy, int64_t *n_steps,
+                          int64_t *n_records);
+/* Host-only: how a flush puts the records together (csrc/core_records.h).  rows [n_rows][ncol] census rows of a flush
+ * window, recorded [n_rows] nonzero for the steps that recorded, the pool as the device left it (n_pool records, at
+ * least min(sum of the recorded steps' counts, capacity)).  Per recorded step k: row[k], complete[k], its records at
+ * offset[k] .. offset[k + 1] of triangles / charges / xy (room for n_pool), sorted by triangle.  No device work. */
+int tdgl_host_core_records_assemble(int64_t n_rows, int32_t ncol, const int32_t *rows, const uint8_t *recorded, int64_t n_pool,
+                                    const int32_t *pool_triangles, const int32_t *pool_charges, const double *pool_xy,
+                                    int64_t capacity, int64_t *row, int64_t *offset, uint8_t *complete, int32_t *triangles,
+                                    int32_t *charges, double *xy, int64_t *n_steps);
 
 /* ------------------------------------------------------------------ screening
  * options.include_screening (solver.py:304-314, 522-578, 654-688; kernel: tdgl/solver/screening.py).

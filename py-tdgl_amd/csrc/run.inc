@@ -113,7 +113,8 @@ static int step_finish(tdgl_ctx *ctx, double dt, double dmax, double *dt_used, d
 
 // Copy the probe read-outs of the steps since the last flush to the caller's arrays
 // (rows [first_row, first_row + probe_ring_count) of out_mu / out_theta, n_probe columns each), and in the same
-// synchronisation the census rows of those steps to the context's host vector (census.inc).
+// synchronisation the census rows of those steps to the context's host vector (census.inc), followed by the records of
+// those steps' vortex cores when they are on and there are any.
 static int probe_ring_flush(tdgl_ctx *ctx, int64_t first_row, double *out_mu, double *out_theta) {
     const int np_ = (int)ctx->probes.size();
     const int cnt = np_ > 0 ? ctx->probe_ring_count : 0;
@@ -126,7 +127,7 @@ static int probe_ring_flush(tdgl_ctx *ctx, int64_t first_row, double *out_mu, do
                                     hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->stat_host_syncs += 1;
-    census_flush_keep(ctx, census_rows);
+    TDGL_TRY(census_flush_keep(ctx, census_rows));
     for (int k = 0; k < cnt; ++k) {
         const double *row = ctx->h_probe_out.p + (size_t)k * 2 * np_;
         if (out_mu) memcpy(out_mu + (first_row + k) * np_, row, np_ * sizeof(double));

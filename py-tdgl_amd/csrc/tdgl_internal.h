@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "tdgl_hip.h"
+#include "core_records.h"  // tdgl_cores::Record, assemble (plain C++)
 
 namespace tdgl {
 
@@ -351,8 +352,36 @@ struct CensusPlan {  // what the kernels take by value
     const int32_t *loop_sites;
 };
 constexpr int CENSUS_MAX_BLOCKS = 1024;  // triangle workgroups of one launch (they stride): bounds the atomics per step at 2 x this
+// Records of the cores themselves (tdgl_set_core_records; census.inc, core_records.h): one per charged triangle of every
+// recorded step, appended to a pool through a cursor by the census launch.  They belong to the census they were set on.
+struct CoresPlan {  // what the recording kernels take by value
+    const int32_t *tri_id;            // [n_tri]: the caller's number of the census' triangle k
+    const double2 *xy;                // [n]: the sites in the internal numbering
+    tdgl_cores::Record *pool;         // [capacity]
+    unsigned long long *cursor;       // slots reserved since the last flush
+    unsigned long long capacity;
+};
+struct CoreRecords {
+    int64_t capacity = 0, every = 1;  // records per flush window; 0: off
+    int64_t window_first = 0;         // running index (accepted steps since the records were switched on) of the ring's row 0
+    DevBuf<int32_t> tri_id;
+    DevBuf<double2> xy;
+    DevBuf<tdgl_cores::Record> pool;
+    DevBuf<unsigned long long> cursor;
+    PinnedBuf<tdgl_cores::Record> h_pool;
+    // of the last tdgl_run, per recorded step: its row among the run's steps, where its records end, whether it is complete
+    std::vector<int64_t> step, offset{0};
+    std::vector<uint8_t> complete;
+    std::vector<tdgl_cores::Record> records;
+    bool on() const { return capacity > 0; }
+    bool records_index(int64_t index) const { return index % every == 0; }
+    CoresPlan plan() const { return {tri_id.p, xy.p, pool.p, cursor.p, (unsigned long long)capacity}; }
+};
 struct Census {
     int32_t n_tri = 0, n_loops = 0;
+    int32_t max_blocks = CENSUS_MAX_BLOCKS;  // (TDGL_CENSUS_MAX_BLOCKS when the census was set: tests of the stride loop)
+    CoreRecords cores;
+    std::vector<int32_t> tri_order;  // [n_tri]: the caller's number of triangle k of `elements` (what a core record names)
     int64_t serial = 0;  // which tdgl_set_census call made this one (an ensemble that took it over checks it is still the same)
     DevBuf<int32_t> elements, loop_sites, ring;  // ring: [PROBE_RING_STEPS][ncol], counter columns zero between uses
     DevBuf<int8_t> orient;
@@ -365,7 +394,7 @@ struct Census {
     CensusPlan plan() const {
         return {n_tri, tri_blocks(), n_loops, ncol(), elements.p, orient.p, loop_ptr.p, loop_sites.p};
     }
-    int32_t tri_blocks() const { return std::min((n_tri + BLOCK - 1) / BLOCK, CENSUS_MAX_BLOCKS); }
+    int32_t tri_blocks() const { return std::min((n_tri + BLOCK - 1) / BLOCK, max_blocks); }
     // workgroups of one launch: the triangles', then one wavefront per loop
     unsigned grid() const { return (unsigned)(tri_blocks() + (n_loops + BLOCK / WAVE - 1) / (BLOCK / WAVE)); }
 };

@@ -1,6 +1,7 @@
 // The two integer rules of DESIGN.md section 3, "Vortex cores and windings", as device functions: the charge of a
-// triangle and the winding around a closed loop of sites.  One copy for the kernels of vortices.inc (saved order
-// parameters) and of census.inc (the live state inside the time loops); tdgl_amd/vortices.py restates them in NumPy.
+// triangle and the winding around a closed loop of sites -- and the position of the core inside a charged triangle.
+// One copy for the kernels of vortices.inc (saved order parameters) and of census.inc (the live state inside the time
+// loops); tdgl_amd/vortices.py restates them in NumPy.
 //
 // Every sign decision compares two separately rounded products p = u.re v.im and q = u.im v.re and never takes the
 // sign of a difference, so a contraction of p - q into an FMA cannot change a decision.
@@ -19,6 +20,16 @@ __device__ inline int vortex_triangle_winding(double2 a, double2 b, double2 c) {
     if (sab > 0 && sbc > 0 && sca > 0) return 1;
     if (sab < 0 && sbc < 0 && sca < 0) return -1;
     return 0;
+}
+
+// The zero of the linear interpolant of psi on the triangle with values (a, b, c) at the corners (ra, rb, rc): the
+// crosses ca = b x c, cb = c x a, cc = a x b, S = (ca + cb) + cc, the weights c / S, and (la ra + lb rb) + lc rc per
+// coordinate.  The only place that takes p - q; positions are compared within the bound of DESIGN.md section 3.
+__device__ inline double2 vortex_core_position(double2 a, double2 b, double2 c, double2 ra, double2 rb, double2 rc) {
+    const double ca = b.x * c.y - b.y * c.x, cb = c.x * a.y - c.y * a.x, cc = a.x * b.y - a.y * b.x;
+    const double S = (ca + cb) + cc;
+    const double la = ca / S, lb = cb / S, lc = cc / S;
+    return make_double2((la * ra.x + lb * rb.x) + lc * rc.x, (la * ra.y + lb * rb.y) + lc * rc.y);
 }
 
 // One wavefront, all 64 lanes taking part: Sunday's crossing rule around the origin over the edges u -> v of the

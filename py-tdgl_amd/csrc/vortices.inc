@@ -18,7 +18,7 @@
 // tdgl_vortex_plan_link links the cores of consecutive frames into tracks: k_vortex_nearest, k_vortex_mutual and
 // k_vortex_event_keys, further down.
 
-#include "vortex_rules.h"  // vortex_triangle_winding, vortex_loop_winding: shared with census.inc
+#include "vortex_rules.h"  // vortex_triangle_winding, vortex_loop_winding, vortex_core_position: shared with census.inc
 
 namespace tdgl {
 
@@ -118,12 +118,9 @@ __global__ __launch_bounds__(BLOCK) void k_vortex_write(int64_t n_tri, int64_t n
     const int32_t i0 = elements[3 * t], i1 = elements[3 * t + 1], i2 = elements[3 * t + 2];
     const double2 *__restrict__ z = psi + f * n_sites;
     const double2 a = z[i0], b = z[i1], c = z[i2];
-    const double ca = b.x * c.y - b.y * c.x, cb = c.x * a.y - c.y * a.x, cc = a.x * b.y - a.y * b.x;
-    const double S = (ca + cb) + cc;
-    const double la = ca / S, lb = cb / S, lc = cc / S;
-    const double2 ra = sites[i0], rb = sites[i1], rc = sites[i2];
-    xy[2 * pos] = (la * ra.x + lb * rb.x) + lc * rc.x;
-    xy[2 * pos + 1] = (la * ra.y + lb * rb.y) + lc * rc.y;
+    const double2 r = vortex_core_position(a, b, c, sites[i0], sites[i1], sites[i2]);
+    xy[2 * pos] = r.x;
+    xy[2 * pos + 1] = r.y;
 }
 
 // One wavefront per (frame, loop): Sunday's crossing rule around the origin over the loop's edges u -> v, lanes

@@ -390,6 +390,13 @@ SIGNATURES = {
     # census inside the time loops (csrc/census.inc)
     "tdgl_set_census": (C.c_int, [_CTX, c_f64p, C.c_int64, c_i32p, C.c_int32, c_i64p, c_i32p]),
     "tdgl_get_census": (C.c_int, [_CTX, C.c_int64, c_i32p, C.POINTER(C.c_int64)]),
+    # records of the cores themselves, out of the census' launch
+    "tdgl_set_core_records": (C.c_int, [_CTX, c_f64p, C.c_int64, C.c_int64]),
+    "tdgl_get_core_records": (C.c_int, [_CTX, C.c_int64, c_i64p, c_i64p, c_i32p, C.c_int64, c_i32p, c_i32p, c_f64p,
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tdgl_host_core_records_assemble": (C.c_int, [C.c_int64, C.c_int32, c_i32p, C.POINTER(C.c_uint8), C.c_int64, c_i32p, c_i32p,
+                                                  c_f64p, C.c_int64, c_i64p, c_i64p, C.POINTER(C.c_uint8), c_i32p, c_i32p,
+                                                  c_f64p, C.POINTER(C.c_int64)]),
     "tdgl_host_mean_tail": (C.c_double, [c_f64p, C.c_int64, C.c_int32]),
     "tdgl_host_loop_replay": (
         C.c_int,

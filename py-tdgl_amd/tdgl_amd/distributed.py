@@ -209,6 +209,9 @@ class DistributedTDGL:
         if options.vortex_census:
             raise SolverOptionsError("vortex_census=True is not supported in one-process-per-GPU mode (a rank holds a "
                                      "part of every loop); run on one GPU, or count the saved steps with VortexFinder.")
+        if options.vortex_cores:
+            raise SolverOptionsError("vortex_cores=True is not supported in one-process-per-GPU mode (it rides on the "
+                                     "census); run on one GPU, or find the cores of saved steps with VortexFinder.")
         if options.screening_method == "tree" and (options.include_screening or screening is not None):
             raise ValueError("screening_method='tree' is not supported in one-process-per-GPU mode; use 'direct'.")
         if payload is None:

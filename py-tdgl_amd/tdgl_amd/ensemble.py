@@ -28,7 +28,7 @@ from ._lib import c128, f64, p_f64, p_i32
 from .device import Device
 from .hipcore import (FIELD_TERMS_MAX, TDGLContext, controller_struct, epsilon_table_args, link_table_args, link_terms_args,
                       mu_boundary_table_args, probe_args, read_census, read_loop_state)
-from .options import SolverOptions
+from .options import SolverOptions, SolverOptionsError
 from .runloop import RunRecord, check_epsilon_table, check_seed
 from .solution import Solution
 from .solver import TDGLSolver, install_census
@@ -82,6 +82,9 @@ def broadcast_replicas(**per_replica) -> tuple:
 
 
 def _refuse_options(options: SolverOptions, n_sites: int) -> None:
+    if options.vortex_cores:
+        raise SolverOptionsError("solve_ensemble: vortex_cores=True is not supported (the ensemble counts, "
+                                 "vortex_census=True, but does not record cores); use tdgl.solve per replica.")
     if options.include_screening:
         raise ValueError("solve_ensemble: include_screening=True is not supported (the ensemble has static link variables).")
     if options.output_file is not None:

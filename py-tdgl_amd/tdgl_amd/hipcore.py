@@ -184,6 +184,21 @@ def read_census(chk, ncol, getter, *handle) -> np.ndarray:
     return rows
 
 
+def read_core_records(chk, getter, *handle) -> dict:
+    """Everything behind tdgl_get_core_records: asked for the numbers first."""
+    ns, nr = C.c_int64(0), C.c_int64(0)
+    chk(getter(*handle, 0, None, None, None, 0, None, None, None, C.byref(ns), C.byref(nr)))
+    steps, counts = np.zeros(ns.value, dtype=np.int64), np.zeros(ns.value, dtype=np.int64)
+    complete = np.zeros(ns.value, dtype=np.int32)
+    triangles, charges = np.zeros(nr.value, dtype=np.int32), np.zeros(nr.value, dtype=np.int32)
+    positions = np.zeros((nr.value, 2))
+    if ns.value:
+        chk(getter(*handle, ns.value, p_i64(steps), p_i64(counts), p_i32(complete), nr.value, p_i32(triangles),
+                   p_i32(charges), p_f64(positions), C.byref(ns), C.byref(nr)))
+    return dict(steps=steps, counts=counts, complete=complete.astype(bool), triangles=triangles, charges=charges,
+                positions=positions)
+
+
 def probe_args(sites) -> tuple:
     """``(sites, n_probe)`` of tdgl_set_probes; None or an empty list: no probes."""
     sites = i32([] if sites is None else sites)
@@ -325,6 +340,7 @@ class TDGLContext:
         self.n_boundary = len(em.boundary_edge_indices)
         self.n_probe = 0
         self.n_census = 0  # columns of a census row (2 + loops); 0: the census is off
+        self.core_records = False  # set_core_records: `run` returns the cores of the recorded steps
         edges = i32(em.edges)
         self.n_owned = int(n_owned) if n_owned else self.n
         if n_owned:
@@ -1416,11 +1432,35 @@ class TDGLContext:
                                             p_i32(loop_sites)))
         self.n_census = (2 + n_loops) if (n_tri or n_loops) else 0
 
+        self.core_records = False  # (they belong to the census they were set on)
+
     def census(self):
         """The census rows of the last `run`, [k, 2 + L] int32, or None when the census is off."""
         if not self.n_census:
             return None
         return read_census(self._chk, self.n_census, self._lib.tdgl_get_census, self._ctx)
+
+    def set_core_records(self, points, capacity, every=1):
+        """Record the vortex cores themselves after every accepted step whose running index -- counted from this call on,
+        the first step being 0, across `run` calls -- is divisible by ``every``, out of the census' own launch
+        (`set_census` with triangles first; csrc/census.inc).  ``points`` [n, 2] as for `set_census`; ``capacity``:
+        records the device keeps between two flushes (every 1,024 steps and at the end of a `run`), 0 switches the
+        records off, and so does every `set_census`.  ``run`` then returns ``cores``: ``steps`` (rows of the run's
+        ``dt``), ``counts``, ``complete``, and the concatenated ``triangles``, ``charges``, ``positions`` [N, 2] -- per
+        step what `VortexPlan.find` / `vortices.host_find` give for psi after that step.  A step whose records reach
+        beyond the capacity, and every later one up to the next flush, is incomplete and has none."""
+        capacity = int(capacity)
+        points = f64(points) if capacity != 0 and points is not None else None
+        if points is not None and points.shape != (self.n, 2):
+            raise ValueError(f"Expected points [{self.n}, 2] (got {points.shape}).")
+        self._chk(self._lib.tdgl_set_core_records(self._ctx, p_f64(points), capacity, int(every)))
+        self.core_records = capacity > 0
+
+    def cores(self):
+        """The core records of the last `run` (see `set_core_records`), or None when they are off."""
+        if not self.core_records:
+            return None
+        return read_core_records(self._chk, self._lib.tdgl_get_core_records, self._ctx)
 
     # -- time loop --------------------------------------------------------------------------
     def begin_stage(self):
@@ -1448,6 +1488,7 @@ class TDGLContext:
             dt=dts[:k], mu=None if mu_p is None else mu_p[:k],
             theta=None if th_p is None else th_p[:k], pcg_iters=iters[:k],
             screening_iterations=scr_iters[:k], reached_end=bool(reached.value), census=self.census(),
+            cores=self.cores(),
         )
 
     # -- screening (solver.py:522-578, 654-688) -----------------------------------------------

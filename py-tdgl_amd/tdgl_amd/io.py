@@ -29,6 +29,9 @@ from datetime import datetime
 
 import numpy as np
 
+# SolverOptions.vortex_cores*: at these values nothing is written into /solution/options
+CORES_DEFAULTS = dict(vortex_cores=False, vortex_cores_every=1, vortex_cores_capacity=262_144)
+
 
 def _require_h5py():
     try:
@@ -214,6 +217,8 @@ def write_solution_group(file, solution) -> None:
         if k == "sparse_solver":
             v = getattr(v, "value", v)
         if k == "vortex_census" and not v:  # (off: the file is what it was before the option existed)
+            continue
+        if k.startswith("vortex_cores") and v == CORES_DEFAULTS[k]:  # (likewise, each of the three at its default)
             continue
         if v is not None:
             options_grp.attrs[k] = v

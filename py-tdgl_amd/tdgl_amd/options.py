@@ -93,6 +93,14 @@ class SolverOptions:
     # count the charged mesh triangles and the winding around every boundary loop (device.boundary_sites()) after every
     # step, inside the time loop: DynamicsData.vortex_counts / windings; single-GPU runs and ensembles
     vortex_census: bool = False
+    # record the cores themselves -- triangle, charge, position of every charged triangle -- after every
+    # vortex_cores_every-th step, out of the census' launch: Solution.dynamics.vortex_cores (`VortexCores`).  Implies the
+    # census.  vortex_cores_capacity: records kept on the device between two flushes (every 1,024 steps), a cap and not a
+    # tuning result -- 24 bytes each on the device and in pinned memory; steps beyond it come back incomplete.  tdgl.solve
+    # on one GPU only; not written to HDF5
+    vortex_cores: bool = False
+    vortex_cores_every: int = 1
+    vortex_cores_capacity: int = 262_144
     device_id: int = 0
     # --- evaluation of the screening sum (no reference counterpart) ---
     # "direct": all pairs (edge centre, site); "tree": barycentric Lagrange treecode of that degree and acceptance
@@ -151,3 +159,9 @@ class SolverOptions:
 
         if not isinstance(self.vortex_census, (bool, np.bool_)):
             fail(f"vortex_census must be a bool (got {self.vortex_census!r}).")
+        if not isinstance(self.vortex_cores, (bool, np.bool_)):
+            fail(f"vortex_cores must be a bool (got {self.vortex_cores!r}).")
+        for name in ("vortex_cores_every", "vortex_cores_capacity"):
+            value = getattr(self, name)
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1:
+                fail(f"{name} must be an int >= 1 (got {value!r}).")

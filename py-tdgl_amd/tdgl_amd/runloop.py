@@ -94,6 +94,8 @@ class RunRecord:
         self.saved, self.saved_meta = [], []
         self.dyn = dict(dt=[], time=[], mu=[], theta=[], pcg_iters=[], screening_iterations=[], census=[])
         self.census_loops = getattr(solver, "census_loops", None)  # names of the census' loops; None: no census
+        self.cores = [] if getattr(solver, "records_cores", False) else None  # SolverOptions.vortex_cores: per run call
+        self.saved_rows = 0  # rows of the saved stage's dynamics so far
         self.n_steps = dict.fromkeys(STAGES, 0)
         self.running = None  # the per-step scalars between two saves: kept for a handler only
         if handler is not None:
@@ -143,6 +145,9 @@ class RunRecord:
                 for key, v in cols.items():
                     self.running.append(key, np.asarray(v[k - 1]).reshape(-1))
         if save:
+            if self.cores is not None and res.get("cores") is not None:
+                self.cores.append(dict(res["cores"], steps=res["cores"]["steps"] + self.saved_rows))
+            self.saved_rows += k
             self.dyn["time"].append(self.loop["time"] + np.concatenate([[0.0], np.cumsum(res["dt"][:-1])]))
             for key, column in self.dyn.items():
                 if key != "time" and res.get(key) is not None:
@@ -171,6 +176,15 @@ class RunRecord:
         if self.census_loops is not None:
             rows = cat(d["census"]).astype(np.int32).reshape(-1, 2 + len(self.census_loops))
             census = dict(vortex_counts=rows[:, :2].T.copy(), windings=rows[:, 2:].T.copy(), loop_names=tuple(self.census_loops))
+        if self.cores is not None:
+            from .vortices import VortexCores
+
+            join = lambda key, empty: np.concatenate([c[key] for c in self.cores]) if self.cores else empty  # noqa: E731
+            steps = join("steps", np.zeros(0, dtype=np.int64))
+            census["vortex_cores"] = VortexCores(
+                steps, (cat(d["time"]) + dt)[steps], join("counts", np.zeros(0, dtype=np.int64)), join("complete", np.zeros(0, dtype=bool)),
+                join("positions", np.zeros((0, 2))), join("charges", np.zeros(0, dtype=np.int32)),
+                join("triangles", np.zeros(0, dtype=np.int32)), device=s.device)
         dynamics = DynamicsData(
             **census,
             dt=dt, time=cat(d["time"]), mu=cat(d["mu"]).T if d["mu"] else None,

@@ -122,6 +122,9 @@ class DynamicsData:
     vortex_counts: Optional[np.ndarray] = None  # [2, n_steps] int32: n_plus, n_minus
     windings: Optional[np.ndarray] = None       # [L, n_steps] int32, WINDING_UNDEFINED where not defined
     loop_names: Optional[tuple] = None          # the L loops: the keys of device.boundary_sites()
+    # SolverOptions.vortex_cores only: the cores themselves at every recorded step (`vortices.VortexCores`).  In memory
+    # only: to_hdf5 saves without them and from_hdf5 gives None
+    vortex_cores: Optional[object] = None
 
     def __post_init__(self):
         if self.time is None:  # data.py:167-168
@@ -221,7 +224,8 @@ class DynamicsData:
     @staticmethod
     def from_hdf5(h5file, step_min: Union[int, None] = None, step_max: Union[int, None] = None) -> "DynamicsData":
         """From ``DynamicsData.to_hdf5`` output, or from the ``running_state`` buffers of the saved
-        steps of an output file: concatenated, the zero padding (dt = 0) removed (data.py:369-428)."""
+        steps of an output file: concatenated, the zero padding (dt = 0) removed (data.py:369-428).  ``vortex_cores`` is
+        None: the files do not hold the records."""
         if "theta" in h5file or ("dt" in h5file and "data" not in h5file):
             get = lambda k: np.array(h5file[k]) if k in h5file else None  # noqa: E731
             counts, windings = DynamicsData._census_from_float(get("vortex_counts"), get("windings"))
@@ -260,6 +264,7 @@ class DynamicsData:
         )
 
     def to_hdf5(self, h5group) -> None:
+        """(``vortex_cores`` is not written: the records stay in memory.)"""
         h5group["dt"] = self.dt
         for name in ("mu", "theta", "screening_iterations"):
             if getattr(self, name) is not None:

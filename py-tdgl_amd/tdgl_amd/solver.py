@@ -324,8 +324,11 @@ class TDGLSolver:
         self.ctx.set_mu_boundary(self.mu_boundary)
         self.ctx.set_probes(self.probe_points)
         self.census_loops = None  # names of the loops of the in-loop census; None: off
-        if options.vortex_census:
+        self.records_cores = bool(options.vortex_cores)  # Solution.dynamics.vortex_cores; implies the census
+        if options.vortex_census or options.vortex_cores:
             self.census_loops = install_census(self.ctx, getattr(self, "device", None))
+        if options.vortex_cores:
+            self.ctx.set_core_records(self.device.points, options.vortex_cores_capacity, options.vortex_cores_every)
         self.ctx.set_controller(
             options.dt_init, options.dt_max, options.adaptive, options.adaptive_window,
             options.max_solve_retries, options.adaptive_time_step_multiplier,

@@ -509,3 +509,78 @@ class VortexFinder:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class VortexCores:
+    """The vortex cores recorded inside the time loop (``SolverOptions.vortex_cores``): for every recorded step what
+    :func:`host_find` / ``Solution.vortices()`` give for psi after that step, without psi having been saved.
+
+    ``steps`` [F]: the recorded steps as row indices into ``dynamics.time``; ``times`` [F]: when psi was what the frame
+    holds, after the step, ``dynamics.time[steps] + dynamics.dt[steps]``; ``counts`` [F]: records
+    held per step; ``complete`` [F]: False for a step whose records did not fit ``vortex_cores_capacity`` between two
+    flushes of the loop (it holds none; ``dynamics.vortex_counts`` still has its exact numbers); ``offsets`` [F + 1]:
+    frame k's records are ``offsets[k]:offsets[k + 1]`` of ``positions`` [N, 2] (the units of ``device.points``),
+    ``charges`` [N] and ``triangles`` [N] (rows of ``device.triangles``, ascending within a step).  ``len()``: F;
+    iteration and :meth:`frame` give :class:`Vortices`.  Not written to HDF5."""
+
+    def __init__(self, steps, times, counts, complete, positions, charges, triangles, device=None):
+        self.steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+        self.times = np.asarray(times, dtype=float).reshape(-1)
+        self.counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+        self.complete = np.asarray(complete, dtype=bool).reshape(-1)
+        self.offsets = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
+        self.positions = np.asarray(positions, dtype=float).reshape(-1, 2)
+        self.charges = np.asarray(charges, dtype=np.int32).reshape(-1)
+        self.triangles = np.asarray(triangles, dtype=np.int32).reshape(-1)
+        self.device = device
+        if not (len(self.steps) == len(self.times) == len(self.counts) == len(self.complete)):
+            raise ValueError("steps, times, counts and complete must have one entry per recorded step.")
+        if not (self.offsets[-1] == len(self.positions) == len(self.charges) == len(self.triangles)):
+            raise ValueError(f"The counts add up to {self.offsets[-1]} records; got {len(self.positions)} positions, "
+                             f"{len(self.charges)} charges, {len(self.triangles)} triangles.")
+
+    def __len__(self):
+        return len(self.steps)
+
+    def frame(self, k) -> Vortices:
+        """The cores of recorded step ``k`` (negative: from the end)."""
+        k = int(k)
+        if not -len(self) <= k < len(self):
+            raise IndexError(f"frame {k} of {len(self)} recorded steps")
+        k %= len(self)
+        lo, hi = self.offsets[k], self.offsets[k + 1]
+        return Vortices(self.positions[lo:hi], self.charges[lo:hi], self.triangles[lo:hi])
+
+    def __iter__(self):
+        return (self.frame(k) for k in range(len(self)))
+
+    def tracks(self, max_distance, backend="host", first=0, last=None, device_id=0) -> VortexTracks:
+        """The recorded frames ``first`` .. ``last`` (inclusive; default: all) linked into tracks with their times, by
+        :func:`link_frames` (``backend="host"``) or `hipcore.VortexPlan.link` (``"hip"``; needs a GPU, never falls
+        back), with the device's boundary loops: what :func:`track_vortices` gives for the same steps had they been
+        saved, and psi is never uploaded.  Raises ``ValueError`` when a frame in the range is incomplete."""
+        if backend not in ("host", "hip"):
+            raise ValueError(f'backend must be "host" or "hip" (got {backend!r}).')
+        r = _check_max_distance(max_distance)
+        last = len(self) - 1 if last is None else int(last)
+        first = int(first)
+        if not 0 <= first <= last < len(self):
+            raise ValueError(f"Expected 0 <= first <= last < {len(self)} (got {first}, {last}).")
+        bad = np.flatnonzero(~self.complete[first:last + 1])
+        if len(bad):
+            raise ValueError(f"{len(bad)} of the recorded steps {first} .. {last} are incomplete (the first: {first + bad[0]}): "
+                             "their cores did not fit vortex_cores_capacity records between two flushes of the time loop.")
+        if self.device is None:
+            raise ValueError("These records carry no device (its boundary loops are needed).")
+        frames = [self.frame(k) for k in range(first, last + 1)]
+        times = self.times[first:last + 1]
+        loops = dict(self.device.boundary_sites() or {})
+        if backend == "hip":
+            with VortexFinder(self.device, loops=loops, device_id=device_id) as finder:
+                links = Links(*finder.plan.link([len(v.charges) for v in frames], np.concatenate([v.positions for v in frames]),
+                                                np.concatenate([v.charges for v in frames]), r))
+        else:
+            sites = np.asarray(self.device.points, dtype=float)
+            loop_xy = sites[np.concatenate([np.asarray(l) for l in loops.values()])] if loops else None
+            links = link_frames(frames, r, loop_xy)
+        return VortexTracks(frames, links, r, times=times, loops=loops)
