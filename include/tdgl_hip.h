@@ -1058,11 +1058,16 @@ int tdgl_normal_current(tdgl_ctx *ctx, const double *mu, double *out);
 int tdgl_vcycle(tdgl_ctx *ctx, const double *r, double *z);
 /* One application of the substructure factors as the CG's preconditioner (tdgl_poisson_set_substructure_precond),
  * z = M r with M ~ pinv(A): r and z [n_sites] in REFERENCE site order like tdgl_vcycle, *rz = r . z as the CG forms it
- * (the scatter kernel's per-workgroup partials added in index order).  Works on buffers of its own: the CG's vectors,
+ * (per-workgroup partials added in index order).  Works on buffers of its own: the CG's vectors,
  * guess and counters are untouched, a tdgl_poisson_solve before and after returns the same bits.  For cross-checks of
  * the factor sweeps against a host model of the stored factors.  TDGL_ERR_NOT_READY (with a message) without factors,
  * when the factors are the mu SOLVER rather than the preconditioner, and in one-process-per-GPU contexts. */
 int tdgl_precond_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz);
+/* Applications of the factor preconditioner on one GPU since the context was created, by the order they took: `folded`
+ * (the first level's two kernels read r and write z through the dissection's map) and `two_pass` (gather, sequence,
+ * scatter as separate kernels: TDGL_PD_TWO_PASS, read once in tdgl_create; tests, A/B runs).  The calibration at set-up
+ * and tdgl_precond_apply count. */
+int tdgl_get_precond_apply_stats(tdgl_ctx *ctx, int64_t *folded, int64_t *two_pass);
 /* One application of the V-cycle in the precisions the CG applies it in (tdgl_poisson_options.precond_fp32 = 1 or 2: the
  * level-0 operators in fp32 or binary16 with the two level-0 iterates in fp32, the coarser levels' pre-multiplied
  * operators in fp32 or binary16; tdgl_vcycle is the fp64 cycle).  r, q and z [n_sites] in REFERENCE site order; z is the

@@ -1102,7 +1102,8 @@ static int precond_calibrate(tdgl_ctx *ctx, double *t_apply_us, double *t_vcycle
         *out = t[t.size() / 2];
         return TDGL_OK;
     };
-    TDGL_TRY(median_us([&]() -> int { return precond_factors_apply(ctx, ctx->pcg_r.p, ctx->direct->z.p, ctx->part_pair[0].p); }, &ctx->pd_t_apply_us));
+    // (the application as the first iteration of a run launches it: r . z left to k_sell_axp where that is the order)
+    TDGL_TRY(median_us([&]() -> int { return precond_factors_apply(ctx, ctx->pcg_r.p, ctx->direct->z.p, ctx->part_pair[0].p, true); }, &ctx->pd_t_apply_us));
     TDGL_TRY(median_us(
         [&]() -> int {
             if (precond_f32_on(ctx) && ctx->deep) {
@@ -1154,8 +1155,10 @@ extern "C" int tdgl_poisson_set_substructure_precond(tdgl_ctx *ctx, const int32_
     DevBuf<int32_t> d_map;
     DevBuf<double> bp, xp, z;
     HIP_TRY(ctx, d_map.upload(map));
-    HIP_TRY(ctx, bp.alloc((size_t)n));
-    HIP_TRY(ctx, xp.alloc((size_t)n));
+    if (ctx->pd_two_pass) {  // (the folded application reads r and writes z through the map: no vectors in the dissection's order)
+        HIP_TRY(ctx, bp.alloc((size_t)n));
+        HIP_TRY(ctx, xp.alloc((size_t)n));
+    }
     HIP_TRY(ctx, z.alloc((size_t)ctx->n_pad));
     f->map = std::move(d_map);
     f->bp = std::move(bp);

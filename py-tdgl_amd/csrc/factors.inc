@@ -65,14 +65,20 @@ static void blr_launch(tdgl_ctx *ctx, const BlrTop &Z, int n, int nt, int nfin, 
 }
 
 // the way up of one level: its separator solution L.xs and the way down's L.w -> out
-// (R: 64-row chunks per workgroup -- 1, or a whole part of up to 256 rows on the levels stored as symmetric tiles)
+// (R: 64-row chunks per workgroup -- 1, or a whole part of up to 256 rows on the levels stored as symmetric tiles;
+// map: row i goes to out[map[i]] -- the first level of a preconditioner application, precond_direct_apply)
 template <class VT>
-static void launch_sub_up(tdgl_ctx *ctx, const SubLevel &L, const VT *vals, double *out, const SubMean &m, const int32_t *fail, const StepCtl *ctl) {
+static void launch_sub_up(tdgl_ctx *ctx, const SubLevel &L, const VT *vals, double *out, const SubMean &m, const int32_t *fail, const StepCtl *ctl,
+                          const int32_t *map = nullptr) {
     const int nblk_int = L.nI > 0 ? (int)L.up_chunks.n : 0, nblk_sep = grid_for(L.nS);
     auto go = [&](auto R) {
-        hipLaunchKernelGGL((k_sub_up<VT, decltype(R)::value>), dim3(nblk_int + nblk_sep), dim3(BLOCK), 0, ctx->stream, L.nI, L.nS, nblk_int,
-                           (const SubUpChunk *)L.up_chunks.p, (const int32_t *)L.sep_idx.p, vals, (const double *)L.w.p,
-                           (const double *)L.xs.p, m, fail, ctx->psi_blocks, out, ctl);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(nblk_int + nblk_sep), dim3(BLOCK), 0, ctx->stream, L.nI, L.nS, nblk_int,
+                               (const SubUpChunk *)L.up_chunks.p, (const int32_t *)L.sep_idx.p, vals, (const double *)L.w.p,
+                               (const double *)L.xs.p, m, fail, ctx->psi_blocks, out, ctl, map);
+        };
+        if (map) launch(k_sub_up<VT, decltype(R)::value, true>);
+        else launch(k_sub_up<VT, decltype(R)::value, false>);
     };
     if (L.up_R >= 4) go(std::integral_constant<int, 4>{});
     else if (L.up_R == 3) go(std::integral_constant<int, 3>{});
@@ -85,9 +91,11 @@ template <class VT> static size_t sym_lds_bytes(int np_lds) {  // k_sub_down_sym
 }
 
 // the way down of one level: b (the level's vector) -> L.w.  `lanes`: the preconditioner's lane-per-row work lists;
-// `first`: the first level (its coupling product takes 8 lanes per row, the inner levels' 16)
+// `first`: the first level (its coupling product takes 8 lanes per row, the inner levels' 16); map: entry i of the
+// level's vector is b[map[i]] (the first level of a preconditioner application: its work lists are lanes or tiles)
 template <class VT>
-static void launch_sub_down(tdgl_ctx *ctx, const SubLevel &L, const VT *vals, bool first, bool lanes, const double *b, const StepCtl *ctl) {
+static void launch_sub_down(tdgl_ctx *ctx, const SubLevel &L, const VT *vals, bool first, bool lanes, const double *b, const StepCtl *ctl,
+                            const int32_t *map = nullptr) {
     const int64_t nI = L.nI, nS = L.nS, rows = nI + nS + L.parts;
     const int nblk_dint = nI > 0 ? (int)L.down_chunks.n : 0;
     const int nblk_drest = (int)((rows - nI + BLOCK / WAVE - 1) / (BLOCK / WAVE));
@@ -100,13 +108,22 @@ static void launch_sub_down(tdgl_ctx *ctx, const SubLevel &L, const VT *vals, bo
         const int nblk_id = grid_for(n_id) * (n_id > 0), nblk_w = (int)((rows - nI - n_id + BLOCK / WAVE - 1) / (BLOCK / WAVE));
         // (tiles requested one pair ahead: two and three pairs ahead measured the same application time at 1M sites,
         // profiles/EXPERIMENTS.md round 6 -- the kernel is not waiting for its loads)
-        if (L.sym_lds > 0)
-            hipLaunchKernelGGL((k_sub_down_sym<VT, 1>), dim3((unsigned)(nblk_dint + nblk_id + nblk_w)), dim3(BLOCK), sym_lds_bytes<VT>(L.sym_lds),
-                               ctx->stream, nI, n_id, rows, nblk_dint, nblk_id, L.sym_lds, chunks, seg_ptr, seg_val, seg_x, seg_len, vals, b,
-                               L.w.p, ctl);
-        else
-            hipLaunchKernelGGL((k_sub_down_lanes<VT>), dim3((unsigned)(nblk_dint + nblk_id + nblk_w)), dim3(BLOCK), 0, ctx->stream, nI, n_id, rows,
-                               nblk_dint, nblk_id, chunks, drows, seg_ptr, seg_val, seg_x, seg_len, vals, b, L.w.p, ctl);
+        const dim3 grid((unsigned)(nblk_dint + nblk_id + nblk_w));
+        auto sym = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), sym_lds_bytes<VT>(L.sym_lds), ctx->stream, nI, n_id, rows, nblk_dint, nblk_id, L.sym_lds,
+                               chunks, seg_ptr, seg_val, seg_x, seg_len, vals, b, L.w.p, ctl, map);
+        };
+        auto lane_form = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), 0, ctx->stream, nI, n_id, rows, nblk_dint, nblk_id, chunks, drows, seg_ptr, seg_val, seg_x,
+                               seg_len, vals, b, L.w.p, ctl, map);
+        };
+        if (L.sym_lds > 0) {
+            if (map) sym(k_sub_down_sym<VT, 1, true>);
+            else sym(k_sub_down_sym<VT, 1, false>);
+        } else {
+            if (map) lane_form(k_sub_down_lanes<VT, true>);
+            else lane_form(k_sub_down_lanes<VT, false>);
+        }
     } else
         hipLaunchKernelGGL((k_sub_down<VT>), dim3((unsigned)(nblk_dint + nblk_drest)), dim3(BLOCK), 0, ctx->stream, nI, rows, nblk_dint, chunks,
                            drows, seg_ptr, seg_val, seg_x, seg_len, vals, b, L.w.p, ctl);
@@ -125,9 +142,11 @@ static void launch_pd_gather(tdgl_ctx *ctx, int64_t n, const int32_t *map, const
 // The launches of a direct mu solve, x = pinv(A) b (dense inverse or substructured; see the header).
 // in_step: inside the time loop -- the kernels that write x hold back when this step's psi update failed and
 // the status block is published by k_dense_sym_finish (returns true then).  ctl / rec: the run-ahead loop's
-// device-resident controller and the record of this step (run.inc), else NULL.
+// device-resident controller and the record of this step (run.inc), else NULL.  map (the preconditioner's folded
+// application, precond_direct_apply): b and x are in the context's order, entry i of the first level's vector is
+// b[map[i]] / goes to x[map[i]]; NULL: both in the dissection's order.
 template <class VT>
-static bool direct_solve_launch_t(tdgl_ctx *ctx, const double *b, double *x, bool in_step, StepCtl *ctl, StepRec *rec) {
+static bool direct_solve_launch_t(tdgl_ctx *ctx, const double *b, double *x, bool in_step, StepCtl *ctl, StepRec *rec, const int32_t *map) {
     const DirectFactors &f = *ctx->direct;
     const double inv_n = 1.0 / (double)ctx->n_global;
     const int32_t *fail = in_step ? (const int32_t *)ctx->psi_fail_part.p : (const int32_t *)nullptr;
@@ -144,7 +163,7 @@ static bool direct_solve_launch_t(tdgl_ctx *ctx, const double *b, double *x, boo
     const int K = f.levels;
     const double *vec = b;
     for (int k = 0; k < K; ++k) {
-        launch_sub_down(ctx, f.lv[k], Stored<VT>::of(f.lv[k].vals, f.lv[k].vals32), k == 0, lanes, vec, ctl);
+        launch_sub_down(ctx, f.lv[k], Stored<VT>::of(f.lv[k].vals, f.lv[k].vals32), k == 0, lanes, vec, ctl, k == 0 ? map : nullptr);
         vec = f.lv[k].w.p + f.lv[k].nI;
     }
     const SubLevel &T = f.lv[K - 1];
@@ -155,29 +174,47 @@ static bool direct_solve_launch_t(tdgl_ctx *ctx, const double *b, double *x, boo
         launch_dense_sym(ctx, f.dense, (int)T.nS, f.nfin, vec, fin);
     for (int k = K - 1; k >= 1; --k)
         launch_sub_up(ctx, f.lv[k], Stored<VT>::of(f.lv[k].vals, f.lv[k].vals32), f.lv[k - 1].xs.p, k == K - 1 ? mean_left(f, inv_n) : mean_none(), fail, ctl);
-    launch_sub_up(ctx, f.lv[0], Stored<VT>::of(f.lv[0].vals, f.lv[0].vals32), x, K == 1 ? mean_formed(f, inv_n) : mean_read(f), fail, ctl);
+    launch_sub_up(ctx, f.lv[0], Stored<VT>::of(f.lv[0].vals, f.lv[0].vals32), x, K == 1 ? mean_formed(f, inv_n) : mean_read(f), fail, ctl, map);
     return in_step;
 }
 
-static bool direct_solve_launch(tdgl_ctx *ctx, const double *b, double *x, bool in_step, StepCtl *ctl, StepRec *rec) {
-    return ctx->direct->fp32 ? direct_solve_launch_t<float>(ctx, b, x, in_step, ctl, rec) : direct_solve_launch_t<double>(ctx, b, x, in_step, ctl, rec);
+static bool direct_solve_launch(tdgl_ctx *ctx, const double *b, double *x, bool in_step, StepCtl *ctl, StepRec *rec, const int32_t *map = nullptr) {
+    return ctx->direct->fp32 ? direct_solve_launch_t<float>(ctx, b, x, in_step, ctl, rec, map)
+                             : direct_solve_launch_t<double>(ctx, b, x, in_step, ctl, rec, map);
 }
 
 // ---- the factors as preconditioner (tdgl_poisson_set_substructure_precond) ---------------------------------------
-// z = M r with M ~ pinv(A): the residual gathered into the dissection's order, the launch sequence of the direct solve
-// on the fp32-stored factors, the result scattered back together with the partials of r . z.
-static void precond_direct_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part) {
+// z = M r with M ~ pinv(A): the launch sequence of the direct solve on the fp32-stored factors.  r and z stay in the
+// context's order: the first level's way down reads r through the dissection's map and its way up stores z through it --
+// the dissection's order exists inside those two kernels only.  The partials of r . z go into rz_part, by k_dot_partial;
+// with rz_later the caller's next pass over z forms them instead (cg_step_single: k_sell_axp) and rz_part stays as it is.
+// TDGL_PD_TWO_PASS (tdgl_create) keeps the earlier order for comparison: the residual gathered into the dissection's
+// order (bp), the sequence on vectors in that order, the result (xp) scattered back together with the partials of r . z
+// -- the same values in the same order inside the sweeps, so z is the same bit for bit.
+static void precond_direct_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part, bool rz_later) {
     const DirectFactors &f = *ctx->direct;
-    launch_pd_gather(ctx, ctx->n, f.map.p, r, f.bp.p);
-    (void)direct_solve_launch(ctx, f.bp.p, f.xp.p, false, nullptr, nullptr);
-    hipLaunchKernelGGL(k_pd_scatter, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, ctx->n, (const int32_t *)f.map.p, (const double *)f.xp.p, r, z,
-                       rz_part);
+    if (ctx->pd_two_pass) {
+        ctx->pd_applies_two_pass += 1;
+        launch_pd_gather(ctx, ctx->n, f.map.p, r, f.bp.p);
+        (void)direct_solve_launch(ctx, f.bp.p, f.xp.p, false, nullptr, nullptr);
+        hipLaunchKernelGGL(k_pd_scatter, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, ctx->n, (const int32_t *)f.map.p, (const double *)f.xp.p, r,
+                           z, rz_part);
+        return;
+    }
+    ctx->pd_applies_folded += 1;
+    (void)direct_solve_launch(ctx, r, z, false, nullptr, nullptr, f.map.p);
+    if (!rz_later)
+        hipLaunchKernelGGL(k_dot_partial, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, ctx->n, r, (const double *)z, rz_part);
 }
 
+// does an application with rz_later leave r . z to the caller's next pass?  (not on the two-pass order, whose scatter
+// forms it, and not in one-process-per-GPU mode)
+static inline bool precond_rz_left(const tdgl_ctx *ctx) { return ctx->direct->n_local == 0 && !ctx->pd_two_pass; }
+
 // ... on one GPU the factors of the whole matrix, in one-process-per-GPU mode the rank-level dissection (schur.inc)
-static int precond_factors_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part) {
+static int precond_factors_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz_part, bool rz_later = false) {
     if (ctx->direct->n_local > 0) return precond_schur_apply(ctx, r, z, rz_part);
-    precond_direct_apply(ctx, r, z, rz_part);
+    precond_direct_apply(ctx, r, z, rz_part, rz_later);
     return TDGL_OK;
 }
 
@@ -222,6 +259,14 @@ extern "C" int tdgl_get_direct_stats(tdgl_ctx *ctx, double *relres_max, int64_t 
     if (relres_max) *relres_max = ctx->direct_relres_max;
     if (checks) *checks = ctx->direct_checks;
     if (fell_back) *fell_back = ctx->direct_fell_back;
+    return TDGL_OK;
+}
+
+// how many applications of the factor preconditioner took the folded order / the two-pass order (TDGL_PD_TWO_PASS)
+extern "C" int tdgl_get_precond_apply_stats(tdgl_ctx *ctx, int64_t *folded, int64_t *two_pass) {
+    if (!ctx) return TDGL_ERR_ARG;
+    if (folded) *folded = ctx->pd_applies_folded;
+    if (two_pass) *two_pass = ctx->pd_applies_two_pass;
     return TDGL_OK;
 }
 

@@ -1162,13 +1162,16 @@ __global__ __launch_bounds__(BLOCK) void k_sell_spmv(
 //   q = A p_new,  partial[block] = sum p_new q
 // p is double-buffered by the caller: other rows gather p_old while this row's p_new is written.
 // Saves the separate direction-update pass (24 bytes per row and one launch per iteration).
-template <class ZT, class IT>
+// RZ (the first iteration of a run with the factors, whose application leaves z and no sums): r . z is formed here as
+// well, from the z[row] the pass reads anyway -- part_rz_out[block], the slots and the fixed order k_update_xr expects.
+template <class ZT, class IT, bool RZ = false>
 __global__ __launch_bounds__(BLOCK) void k_sell_axp(
     int n_slices, int per_xcd, int64_t n_rows, const int32_t *__restrict__ slice_off,
     const IT *__restrict__ cols, const double *__restrict__ vals, const ZT *__restrict__ z,
     const double *__restrict__ p_old, const double *__restrict__ part_rz_new,
     const double *__restrict__ part_rz_old, double *__restrict__ p_new, double *__restrict__ q,
-    double *__restrict__ partial, const double *__restrict__ part_zq, const double *__restrict__ scal) {
+    double *__restrict__ partial, const double *__restrict__ part_zq, const double *__restrict__ scal,
+    const double *__restrict__ r, double *__restrict__ part_rz_out) {
     const int xcd = blockIdx.x % XCDS, local = blockIdx.x / XCDS, stride = gridDim.x / XCDS;
     const int lane = threadIdx.x & (WAVE - 1);
     double beta = 0.0;
@@ -1178,6 +1181,7 @@ __global__ __launch_bounds__(BLOCK) void k_sell_axp(
         beta = part_zq ? -scal[S_ALPHA] * num / den : num / den;
     }
     double dot = 0.0;
+    [[maybe_unused]] double rz = 0.0;
     for (int t = local; t < per_xcd; t += stride) {
         const int slice = __builtin_amdgcn_readfirstlane((xcd * per_xcd + t) * (BLOCK / WAVE) + (threadIdx.x / WAVE));
         if (slice >= n_slices) continue;
@@ -1186,6 +1190,7 @@ __global__ __launch_bounds__(BLOCK) void k_sell_axp(
         const int beg = slice_off[slice], cnt = slice_off[slice + 1] - beg;
         const double zr = (double)z[row], pr = part_rz_old ? p_old[row] : 0.0;
         const double pn = zr + beta * pr;
+        if constexpr (RZ) rz += r[row] * zr;
         double acc = 0.0;
         const int64_t idx0 = (int64_t)beg * WAVE + lane;
         for (int base = 0; base < cnt; base += SELL_BATCH) {
@@ -1211,6 +1216,10 @@ __global__ __launch_bounds__(BLOCK) void k_sell_axp(
     }
     const double s = block_sum(dot);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
+    if constexpr (RZ) {
+        const double srz = block_sum(rz);
+        if (threadIdx.x == 0) part_rz_out[blockIdx.x] = srz;
+    }
 }
 
 // Row-per-lane SELL SpMV for the level-0 prolongation: y = A x (T_SET), y += A x (T_ADD) or
@@ -2647,14 +2656,45 @@ __global__ __launch_bounds__(BLOCK) void k_blr_finish(int n, int nt, BlrArgs a, 
 
 // ------------------------------------------------------------------ substructured direct solve
 // (tdgl_poisson_set_substructure; host set-up: tdgl_amd/substructure.py)
+// Where entry i of a level's vector sits.  MAP, the first level of a preconditioner application (factors.inc:
+// precond_direct_apply): at map[i] -- the vector is in the context's order, map[i] = the context's index of the site at
+// dissection position i; the values, the products and their order are what they are on a vector in the dissection's order.
+template <bool MAP>
+__device__ __forceinline__ int64_t vec_at(const int32_t *__restrict__ map, int64_t i) {
+    if constexpr (MAP) return map[i];
+    else return i;
+}
 // Way down: out[row] = sum over the row's segments of vals[seg_val ..) . b[seg_x ..): one wavefront per
 // row, 8-byte loads (segments start at arbitrary offsets), four independent pairs in flight per lane.
-template <class VT>
+// (MAP: vec_at -- b read through the map, the indices of a batch requested first)
+template <class VT, bool MAP = false>
 __device__ __forceinline__ void sub_down_row(int64_t row, int lane, const int32_t *__restrict__ seg_ptr,
                                              const int64_t *__restrict__ seg_val, const int32_t *__restrict__ seg_x,
                                              const int32_t *__restrict__ seg_len, const VT *__restrict__ vals,
-                                             const double *__restrict__ b, double *__restrict__ out) {
+                                             const double *__restrict__ b, double *__restrict__ out,
+                                             const int32_t *__restrict__ map = nullptr) {
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    if constexpr (MAP) {
+        for (int k = seg_ptr[row]; k < seg_ptr[row + 1]; ++k) {
+            const VT *__restrict__ v = vals + seg_val[k];
+            const int32_t *__restrict__ mx = map + seg_x[k];
+            const int len = seg_len[k];
+            int c = lane;
+            for (; c + 3 * WAVE < len; c += 4 * WAVE) {
+                const int m0 = mx[c], m1 = mx[c + WAVE], m2 = mx[c + 2 * WAVE], m3 = mx[c + 3 * WAVE];
+                const VT v0 = v[c], v1 = v[c + WAVE], v2 = v[c + 2 * WAVE], v3 = v[c + 3 * WAVE];
+                const double x0 = b[m0], x1 = b[m1], x2 = b[m2], x3 = b[m3];
+                a0 += (double)v0 * x0;
+                a1 += (double)v1 * x1;
+                a2 += (double)v2 * x2;
+                a3 += (double)v3 * x3;
+            }
+            for (; c < len; c += WAVE) a0 += (double)v[c] * b[mx[c]];
+        }
+        const double t = wave_sum((a0 + a1) + (a2 + a3));
+        if (lane == 0) out[row] = t;
+        return;
+    }
     for (int k = seg_ptr[row]; k < seg_ptr[row + 1]; ++k) {
         const VT *__restrict__ v = vals + seg_val[k];
         const double *__restrict__ x = b + seg_x[k];
@@ -2902,12 +2942,14 @@ __device__ __forceinline__ void strided_dot_rows(double (&acc)[R], VT (&cur)[R][
 constexpr int SUB_UP_MAX_SEP = 1024;  // separator sites a part may touch (LDS: 1,024 doubles)
 // (R > 1: a chunk is a whole PART of up to 64 R rows -- the levels stored as symmetric tiles, sub_level_to_precond --, its
 // separator values gathered once for all of them)
-template <class VT, int R>
+// (MAP: vec_at -- row i is stored at x[map[i]]; every entry of the result is written exactly once, so x needs no other pass)
+template <class VT, int R, bool MAP = false>
 __global__ __launch_bounds__(BLOCK) void k_sub_up(int64_t nI, int64_t nS, int nblk_int,
                                                   const SubUpChunk *__restrict__ chunks, const int32_t *__restrict__ sep_idx,
                                                   const VT *__restrict__ vals, const double *__restrict__ w,
                                                   const double *__restrict__ xs, SubMean m, const int32_t *__restrict__ fail_part,
-                                                  int nfail, double *__restrict__ x, const StepCtl *__restrict__ ctl) {
+                                                  int nfail, double *__restrict__ x, const StepCtl *__restrict__ ctl,
+                                                  const int32_t *__restrict__ map) {
     __shared__ double sh_mean;
     __shared__ double sh_xs[SUB_UP_MAX_SEP];
     __shared__ double sh_acc[BLOCK / WAVE][R * WAVE];
@@ -2926,6 +2968,7 @@ __global__ __launch_bounds__(BLOCK) void k_sub_up(int64_t nI, int64_t nS, int nb
 #pragma unroll
     for (int r = 0; r < R; ++r) et[r] = vals;
     double w_row = 0.0;
+    [[maybe_unused]] int at = 0;
     if (interior) {
         ch = chunks[blockIdx.x];
         // (the first batch of -E^T entries and w of the row are requested before the separator values are gathered)
@@ -2933,6 +2976,8 @@ __global__ __launch_bounds__(BLOCK) void k_sub_up(int64_t nI, int64_t nS, int nb
         for (int r = 0; r < R; ++r) et[r] = vals + ch.et + min(r * WAVE + lane, max(ch.n_rows - 1, 0));  // (-E_p^T)[0][this row]
         strided_prefetch_rows<VT, U, R>(cur, et, ch.np, wv, ch.cnt);
         if ((int)threadIdx.x < ch.n_rows) w_row = w[ch.row0 + threadIdx.x];  // (R * 64 <= BLOCK: thread t finishes row t)
+        if constexpr (MAP)
+            if ((int)threadIdx.x < ch.n_rows) at = map[ch.row0 + threadIdx.x];  // (... and where it goes, requested with it)
         for (int j = threadIdx.x; j < ch.cnt; j += BLOCK) sh_xs[j] = xs[sep_idx[ch.s0 + j]];
     }
     const bool leader = m.out && blockIdx.x == 0;
@@ -2957,7 +3002,7 @@ __global__ __launch_bounds__(BLOCK) void k_sub_up(int64_t nI, int64_t nS, int nb
     const double mean = sh_mean;
     if (!interior) {
         const int64_t i = (blockIdx.x - nblk_int) * (int64_t)BLOCK + threadIdx.x;
-        if (i < nS) x[nI + i] = xs[i] - mean;
+        if (i < nS) x[vec_at<MAP>(map, nI + i)] = xs[i] - mean;
         return;
     }
     // wavefront wv: the separator sites wv, wv + 4, ... of the part; lane = row 64 r + lane of the chunk
@@ -2969,7 +3014,8 @@ __global__ __launch_bounds__(BLOCK) void k_sub_up(int64_t nI, int64_t nS, int nb
     if ((int)threadIdx.x < ch.n_rows) {
         const int t = threadIdx.x;
         const double acc = (sh_acc[0][t] + sh_acc[1][t]) + (sh_acc[2][t] + sh_acc[3][t]);
-        x[ch.row0 + t] = w_row + acc - mean;  // (the pool holds -E^T)
+        if constexpr (MAP) x[at] = w_row + acc - mean;
+        else x[ch.row0 + t] = w_row + acc - mean;  // (the pool holds -E^T)
     }
 }
 
@@ -2982,13 +3028,15 @@ __global__ __launch_bounds__(BLOCK) void k_sub_up(int64_t nI, int64_t nS, int nb
 // chunks: the separator rows that are their identity segment alone (sparse coupling form: out = b, a thread per row),
 // then whatever rows are left ((G_p 1)^T: one wavefront each, as in k_sub_down).
 constexpr int SUB_DOWN_MAX_COLS = 2048;  // rows of a part's G block the lane form stages b_p for (LDS: 16 KB)
-template <class VT>
+// (MAP: vec_at)
+template <class VT, bool MAP = false>
 __global__ __launch_bounds__(BLOCK) void k_sub_down_lanes(int64_t nI, int64_t n_ident, int64_t n_rows, int nblk_int, int nblk_ident,
                                                           const SubDownChunk *__restrict__ chunks, const SubDownRow *__restrict__ rest,
                                                           const int32_t *__restrict__ seg_ptr, const int64_t *__restrict__ seg_val,
                                                           const int32_t *__restrict__ seg_x, const int32_t *__restrict__ seg_len,
                                                           const VT *__restrict__ vals, const double *__restrict__ b,
-                                                          double *__restrict__ out, const StepCtl *__restrict__ ctl) {
+                                                          double *__restrict__ out, const StepCtl *__restrict__ ctl,
+                                                          const int32_t *__restrict__ map) {
     __shared__ double sh_b[SUB_DOWN_MAX_COLS];
     __shared__ double sh_acc[BLOCK / WAVE][WAVE];
     if (ctl && !ctl->live) return;  // run-ahead: dead step
@@ -3001,7 +3049,7 @@ __global__ __launch_bounds__(BLOCK) void k_sub_down_lanes(int64_t nI, int64_t n_
         constexpr int U = 8;
         VT cur[U];
         strided_prefetch<VT, U>(cur, g, ch.ld, wv, nc);  // (before b_p is staged: the two chains run side by side)
-        for (int j = threadIdx.x; j < nc; j += BLOCK) sh_b[j] = b[ch.x0 + j];
+        for (int j = threadIdx.x; j < nc; j += BLOCK) sh_b[j] = b[vec_at<MAP>(map, ch.x0 + j)];
         __syncthreads();
         sh_acc[wv][lane] = strided_dot<VT, U>(cur, g, ch.ld, wv, nc, sh_b);
         __syncthreads();
@@ -3010,12 +3058,12 @@ __global__ __launch_bounds__(BLOCK) void k_sub_down_lanes(int64_t nI, int64_t n_
     }
     if ((int)blockIdx.x < nblk_int + nblk_ident) {
         const int64_t i = (blockIdx.x - nblk_int) * (int64_t)BLOCK + threadIdx.x;
-        if (i < n_ident) out[nI + i] = b[nI + i];
+        if (i < n_ident) out[nI + i] = b[vec_at<MAP>(map, nI + i)];
         return;
     }
     const int64_t row = nI + n_ident + (blockIdx.x - nblk_int - nblk_ident) * (int64_t)(BLOCK / WAVE) + wv;
     if (row >= n_rows) return;
-    sub_down_row(row, lane, seg_ptr, seg_val, seg_x, seg_len, vals, b, out);
+    sub_down_row<VT, MAP>(row, lane, seg_ptr, seg_val, seg_x, seg_len, vals, b, out, map);
 }
 
 // The way down on SYMMETRIC storage (round 6; fp32 factors as preconditioner, parts of at most SYM_MAX_ROWS rows): only
@@ -3036,13 +3084,14 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-template <class VT, int D>
+// (MAP: vec_at)
+template <class VT, int D, bool MAP = false>
 __global__ __launch_bounds__(BLOCK) void k_sub_down_sym(int64_t nI, int64_t n_ident, int64_t n_rows, int nblk_int, int nblk_ident, int np_lds,
                                                         const SubDownChunk *__restrict__ parts, const int32_t *__restrict__ seg_ptr,
                                                         const int64_t *__restrict__ seg_val, const int32_t *__restrict__ seg_x,
                                                         const int32_t *__restrict__ seg_len, const VT *__restrict__ vals,
                                                         const double *__restrict__ b, double *__restrict__ out,
-                                                        const StepCtl *__restrict__ ctl) {
+                                                        const StepCtl *__restrict__ ctl, const int32_t *__restrict__ map) {
     extern __shared__ __align__(16) unsigned char sym_lds[];
     if (ctl && !ctl->live) return;  // run-ahead: dead step
     const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
@@ -3070,7 +3119,7 @@ __global__ __launch_bounds__(BLOCK) void k_sub_down_sym(int64_t nI, int64_t n_id
 #pragma unroll
         for (int d = 0; d < D; ++d)
             if (wv + d * NW < npairs) request(buf[d], wv + d * NW);  // (wave-uniform)
-        for (int j = threadIdx.x; j < np_lds; j += BLOCK) sh_b[j] = j < np ? b[ch.x0 + j] : 0.0;
+        for (int j = threadIdx.x; j < np_lds; j += BLOCK) sh_b[j] = j < np ? b[vec_at<MAP>(map, ch.x0 + j)] : 0.0;
         for (int j = threadIdx.x; j < NH * np_lds; j += BLOCK) sh_y[j] = 0.0;
         __syncthreads();
         double *my_y = sh_y + (size_t)(wv * 2 + half) * np_lds;
@@ -3111,12 +3160,12 @@ __global__ __launch_bounds__(BLOCK) void k_sub_down_sym(int64_t nI, int64_t n_id
     }
     if ((int)blockIdx.x < nblk_int + nblk_ident) {
         const int64_t i = (blockIdx.x - nblk_int) * (int64_t)BLOCK + threadIdx.x;
-        if (i < n_ident) out[nI + i] = b[nI + i];
+        if (i < n_ident) out[nI + i] = b[vec_at<MAP>(map, nI + i)];
         return;
     }
     const int64_t row = nI + n_ident + (blockIdx.x - nblk_int - nblk_ident) * (int64_t)(BLOCK / WAVE) + wv;
     if (row >= n_rows) return;
-    sub_down_row(row, lane, seg_ptr, seg_val, seg_x, seg_len, vals, b, out);
+    sub_down_row<VT, MAP>(row, lane, seg_ptr, seg_val, seg_x, seg_len, vals, b, out, map);
 }
 
 // fp64 pool -> fp32 pool with every row of every G_p / -E_p^T block starting on a 64-byte line (row stride ld = np rounded

@@ -589,7 +589,9 @@ static int cg_precondition(CgRun &run, int it, double **z, const float **z32) {
         // (profile mode: every application of the first 64 bracketed by an event pair -> tdgl_profile_read_direct)
         ProfileScope apply;
         TDGL_TRY(profile_begin(ctx, ctx->prof.admit_factor_apply(), apply));
-        TDGL_TRY(precond_factors_apply(ctx, r, *z, rz_new));
+        // (the first iteration of a run: beta = 0, nothing needs r . z before k_sell_axp's pass over z, which forms it --
+        // cg_step_single; a further application of the factors in the same run: k_dot_partial behind the sequence)
+        TDGL_TRY(precond_factors_apply(ctx, r, *z, rz_new, it == run.it0));
         TDGL_TRY(profile_end(ctx, apply));
     } else if (run.cg1()) {
         *z32 = vcycle0_f32(ctx, r, rz_new, Cycle0Out::ghosts_no_sums());
@@ -604,11 +606,12 @@ static int cg_precondition(CgRun &run, int it, double **z, const float **z32) {
     return TDGL_OK;
 }
 
-#define TDGL_AXP(ZT, IT, COLS, Z)                                                                                 \
-    hipLaunchKernelGGL((k_sell_axp<ZT, IT>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd,    \
+#define TDGL_AXP(ZT, IT, RZ, COLS, Z)                                                                             \
+    hipLaunchKernelGGL((k_sell_axp<ZT, IT, RZ>), dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, pat.n_slices, per_xcd, \
                        pat.n_rows, pat.slice_off.p, COLS, L0.A.vals.p, Z, (const double *)p_old,                   \
                        (const double *)rz_new, rz_prev, run.p, run.q, ctx->part_pq.p,                               \
-                       flex ? (const double *)(rz_new + 2 * NB) : (const double *)nullptr, (const double *)ctx->scal.p)
+                       flex ? (const double *)(rz_new + 2 * NB) : (const double *)nullptr, (const double *)ctx->scal.p, \
+                       (const double *)run.r, rz_new)
 
 // The rest of an iteration on one GPU: the direction update fused into A p (double-buffered p), then x += alpha p,
 // r -= alpha q with the partials of the new ||r||^2 -- and of sum x, so that the zero-mean gauge at the end of the
@@ -626,10 +629,15 @@ static int cg_step_single(CgRun &run, int it, const double *z, const float *z32)
     const SellPattern &pat = L0.A.pat;
     ProfileScope axp;  // (profile mode: a sample of the launches -> tdgl_profile_read_pcg)
     TDGL_TRY(profile_begin(ctx, ctx->prof.admit_axp(), axp));
+    // the factors' first application of a run left z alone: r . z is formed in this pass (k_sell_axp<.., RZ>), in the
+    // slots k_update_xr reads; the matrix rows are the sites, so the sum runs over what k_dot_partial's would
+    const bool form_rz = run.use_pd && it == run.it0 && precond_rz_left(ctx);
     if (run.f32i()) {
-        if (pat.use16) TDGL_AXP(float, int16_t, pat.cols16.p, z32); else TDGL_AXP(float, int32_t, pat.cols.p, z32);
+        if (pat.use16) TDGL_AXP(float, int16_t, false, pat.cols16.p, z32); else TDGL_AXP(float, int32_t, false, pat.cols.p, z32);
+    } else if (form_rz) {
+        if (pat.use16) TDGL_AXP(double, int16_t, true, pat.cols16.p, z); else TDGL_AXP(double, int32_t, true, pat.cols.p, z);
     } else {
-        if (pat.use16) TDGL_AXP(double, int16_t, pat.cols16.p, z); else TDGL_AXP(double, int32_t, pat.cols.p, z);
+        if (pat.use16) TDGL_AXP(double, int16_t, false, pat.cols16.p, z); else TDGL_AXP(double, int32_t, false, pat.cols.p, z);
     }
     TDGL_TRY(profile_end(ctx, axp));
     const XrArgs upd{run.p, run.q, rz_new, ctx->part_pq.p, run.part_rr[it & 1], ctx->scal.p, run.x, run.r, run.part_rr[(it + 1) & 1],
@@ -1057,8 +1065,8 @@ extern "C" int tdgl_guess_dots(tdgl_ctx *ctx, int32_t k, int64_t n, const double
 
 // Per-kernel entry point (tests of the factor sweeps): ONE application of the factor preconditioner, z = M r, on vectors
 // in the caller's site order, on buffers of its own -- the CG's vectors, partials and counters are not touched (the
-// factors' own work vectors are: every application overwrites them).  *rz = r . z as the CG sees it: k_pd_scatter's
-// partials added up in index order.
+// factors' own work vectors are: every application overwrites them).  *rz = r . z from k_dot_partial's partials (on the
+// two-pass order, TDGL_PD_TWO_PASS: k_pd_scatter's), added up in index order.
 extern "C" int tdgl_precond_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz) {
     CTX_GUARD(ctx);
     if (!r || !z || !rz) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_precond_apply: null argument");
@@ -1074,7 +1082,7 @@ extern "C" int tdgl_precond_apply(tdgl_ctx *ctx, const double *r, double *z, dou
     HIP_TRY(ctx, out.alloc(ctx->n_pad));
     HIP_TRY(ctx, part.alloc((size_t)ctx->npart));
     TDGL_TRY(upload_sites(ctx, r, in));
-    precond_direct_apply(ctx, in.p, out.p, part.p);
+    precond_direct_apply(ctx, in.p, out.p, part.p, false);
     HIP_TRY(ctx, hipGetLastError());
     std::vector<double> h((size_t)ctx->npart);
     HIP_TRY(ctx, hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

@@ -349,6 +349,7 @@ static int create_impl(tdgl_ctx *ctx, const tdgl_mesh_desc *d) {
     // (the environment switches of the library: what the test-suite needs to reach a code path -- DESIGN.md section 5)
     ctx->run_ahead_disabled = getenv("TDGL_NO_RUN_AHEAD") != nullptr;
     ctx->sync_shadow_disabled = getenv("TDGL_NO_SYNC_SHADOW") != nullptr;
+    ctx->pd_two_pass = getenv("TDGL_PD_TWO_PASS") != nullptr;
     if (const char *e = getenv("TDGL_PCG_PREDICT")) ctx->pcg_predict_from_guess = strcmp(e, "last") != 0;
     ctx->status_dev = ctx->d_status.p;
     HIP_TRY(ctx, ctx->scal.alloc(S_COUNT));

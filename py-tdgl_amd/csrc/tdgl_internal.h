@@ -808,7 +808,9 @@ struct DirectFactors {
     bool fp32 = false;                     // the pools and the dense tiles are stored in fp32
     // the preconditioner's application in the dissection order: map[i] = the context's index of dissection position i
     DevBuf<int32_t> map;
-    DevBuf<double> bp, xp, z;              // gathered residual / solution in dissection order / z in the context's order
+    // gathered residual / solution in dissection order (the rank-level dissection, and one GPU with TDGL_PD_TWO_PASS: the
+    // folded application needs neither) / z in the context's order
+    DevBuf<double> bp, xp, z;
     // rank-level dissection (schur.inc): the levels are those of this rank's interior block A_II (n_local sites,
     // positive definite: plain inverse of the top separator, no gauge), Gamma = the interface between the ranks
     int64_t n_local = 0;                   // > 0: rank-level dissection
@@ -957,6 +959,10 @@ struct tdgl_ctx {
     // Work queued behind a status copy while the host waits for it (poisson.inc: sync_status).  TDGL_NO_SYNC_SHADOW,
     // read once when the context is created, restores the order without it (tests, A/B runs).
     bool sync_shadow_disabled = false;
+    // The factor preconditioner as gather, sequence, scatter (factors.inc: precond_direct_apply).  TDGL_PD_TWO_PASS, read
+    // once when the context is created, restores that order (tests, A/B runs); the counters say which one ran.
+    bool pd_two_pass = false;
+    int64_t pd_applies_folded = 0, pd_applies_two_pass = 0;
     tdgl::Event ev_status;                // recorded right behind the status copy: the host waits for it, not for the stream
     int64_t stat_edge_launches = 0;       // formations of J_s / J_n since the last reset (tdgl_get_edge_current_launches)
     // collapsed coarse chain (tdgl_poisson_set_collapsed_tail): everything from level `tail_level`

@@ -512,6 +512,7 @@ SIGNATURES = {
     "tdgl_apply_mu_boundary_laplacian": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_vcycle": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_precond_apply": (C.c_int, [_CTX, c_f64p, c_f64p, c_f64p]),
+    "tdgl_get_precond_apply_stats": (C.c_int, [_CTX, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tdgl_vcycle_stored": (C.c_int, [_CTX, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]),
     "tdgl_get_poisson_index_forms": (C.c_int, [_CTX, C.POINTER(C.c_int32)]),
     "tdgl_host_blr_form": (C.c_int, [C.c_int64, c_f64p, C.c_double, C.POINTER(BlrForm)]),

@@ -713,8 +713,9 @@ class TDGLContext:
     def build_precond_direct(self, rtol=1e-10) -> bool:
         """Three levels of nested dissection as the CG's PRECONDITIONER (`tdgl_poisson_set_substructure_precond`; the
         counterpart of the reference's LU, operators.py:305-308, above `SUB2_MAX_SITES`): factors formed on the host in
-        the dissection's order (`_pd_order`), stored in fp32 on the device, applied through a gather / scatter so that
-        the context keeps its reverse Cuthill-McKee order.  Checked on a white-noise right-hand side from a zero guess
+        the dissection's order (`_pd_order`), stored in fp32 on the device; the first level's two kernels read the
+        residual and write the result through the dissection's map, so that the context keeps its reverse
+        Cuthill-McKee order.  Checked on a white-noise right-hand side from a zero guess
         (the CG must get to ``rtol`` in at most three applications); returns whether it is on."""
         from . import substructure
 
@@ -741,8 +742,11 @@ class TDGLContext:
             return False
         self.setup_times["substructure_device"] = t_dev
         tiles = self.precond_direct_layout()  # per level: G blocks as 16 x 16 tiles on or below the diagonal?
+        # (the permutation: r read and z written through the map, 12 bytes per site each; as separate gather and scatter
+        # kernels -- TDGL_PD_TWO_PASS -- 20 each: the vector once more in the dissection's order)
+        perm_bytes = 20 if self.precond_apply_stats()["two_pass"] else 12
         info = dict(levels=3, storage="fp32", symmetric_tiles=[bool(t) for t in tiles], **_level_counts(levels),
-                    bytes_per_application=_factor_bytes(levels, tiles, word=4) + 2 * 20 * self.n,
+                    bytes_per_application=_factor_bytes(levels, tiles, word=4) + 2 * perm_bytes * self.n,
                     t_apply_us=round(ta.value, 1), t_vcycle_us=round(tv.value, 1))
         blr = self.precond_direct_blr()
         if blr["on"]:  # (the top separator's tiles replaced by the block low-rank form)
@@ -1722,6 +1726,13 @@ class TDGLContext:
         rz = np.zeros(1)
         self._chk(self._lib.tdgl_precond_apply(self._ctx, p_f64(r), p_f64(z), p_f64(rz)))
         return z, float(rz[0])
+
+    def precond_apply_stats(self):
+        """`tdgl_get_precond_apply_stats`: ``dict(folded, two_pass)`` -- applications of the factor preconditioner so far,
+        by the order they took (``TDGL_PD_TWO_PASS`` at context creation selects the second)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._chk(self._lib.tdgl_get_precond_apply_stats(self._ctx, C.byref(a), C.byref(b)))
+        return dict(folded=a.value, two_pass=b.value)
 
     def vcycle_stored(self, r, q=None):
         """`tdgl_vcycle_stored`: one application of the V-cycle in the precisions the CG applies it in
