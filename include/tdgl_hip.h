@@ -370,6 +370,15 @@ int tdgl_poisson_schur_begin(tdgl_ctx *ctx, const tdgl_schur_piece *piece);
 int tdgl_poisson_schur_complement(tdgl_ctx *ctx, double *out);
 int tdgl_poisson_schur_finish(tdgl_ctx *ctx, const double *S, int32_t fp32_storage, double *t_apply_us, double *t_vcycle_us);
 int tdgl_poisson_set_precond_times(tdgl_ctx *ctx, double t_apply_us, double t_vcycle_us);
+/* ONE application z = M r of the rank-level dissection, the counterpart of tdgl_precond_apply for a context whose
+ * preconditioner it is.  COLLECTIVE: every rank calls it at the same point; it contains the application's one
+ * all-reduce of n_gamma doubles and no halo exchange.  r and z are [n_owned] in the rank's local site order (ghost
+ * entries are neither read nor written by an application); *rz = r . z over the owned rows, the scatter kernel's
+ * per-workgroup partials added in index order.  Works on buffers of its own: the CG's vectors, partials, guess and
+ * counters are untouched (tdgl_get_comm_stats counts the all-reduce).  TDGL_ERR_NOT_READY (with a message) on any
+ * other context.  tdgl_poisson_schur_begin itself refuses (TDGL_ERR_NOT_READY) a context created with a site
+ * permutation: the piece's local sites are taken as device indices. */
+int tdgl_precond_schur_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz);
 int tdgl_get_precond_direct_stats(tdgl_ctx *ctx, int64_t *out4, double *out4d, int32_t reset);
 int tdgl_get_precond_direct_layout(tdgl_ctx *ctx, int32_t *sym_rows3);
 /* With fp32 storage on one GPU the top separator's pseudo-inverse is kept in block low-rank form: every tile pair

@@ -94,6 +94,11 @@ extern "C" int tdgl_poisson_schur_begin(tdgl_ctx *ctx, const tdgl_schur_piece *p
         if (pc->gi_indices[k] < 0 || pc->gi_indices[k] >= nI) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_begin: A_GI column out of range");
     for (int64_t k = 0; k < pc->ig_indptr[nI]; ++k)
         if (pc->ig_indices[k] < 0 || pc->ig_indices[k] >= ng) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_poisson_schur_begin: A_IG column out of range");
+    // `interior` and `gamma_owned_local` are uploaded as device indices: right only where the context's order is the
+    // caller's (n_owned < n_sites implies it; a single-process context may carry a site permutation)
+    for (int64_t i = 0; i < ctx->n; ++i)
+        if (ctx->perm[i] != (int32_t)i)
+            TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_poisson_schur_begin: this context has a site permutation; the piece's local sites are device indices (create the context without site_perm)");
     auto f = std::make_unique<DirectFactors>();
     HIP_TRY(ctx, f->map.upload(std::vector<int32_t>(pc->interior, pc->interior + nI)));
     HIP_TRY(ctx, f->owner_local.upload(owner));
@@ -171,6 +176,35 @@ static int precond_schur_apply(tdgl_ctx *ctx, const double *r, double *z, double
     hipLaunchKernelGGL(k_schur_scatter, dim3(ctx->npart), dim3(BLOCK), 0, ctx->stream, nI, (const int32_t *)f.map.p, (const double *)f.y.p,
                        (const double *)f.v.p, f.ngo, (const int32_t *)f.go_local.p, (const int32_t *)f.go_gid.p, (const double *)f.xg.p, r, z,
                        rz_part);
+    return TDGL_OK;
+}
+
+// Per-kernel entry point (tests of the rank-level dissection): ONE application z = M r of this rank's share, COLLECTIVE
+// like the application inside the CG -- every rank calls it at the same point, its one all-reduce of n_gamma doubles
+// pairs with the other ranks'.  r and z [n_own] in the rank's local site order (ghosts are neither read nor written by
+// an application); buffers of its own: the CG's vectors, partials and counters are not touched (the factors' own work
+// vectors are: every application overwrites them).  *rz = k_schur_scatter's partials added up in index order.
+extern "C" int tdgl_precond_schur_apply(tdgl_ctx *ctx, const double *r, double *z, double *rz) {
+    CTX_GUARD(ctx);
+    if (!r || !z || !rz) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_precond_schur_apply: null argument");
+    if (!ctx->direct || ctx->direct->n_local == 0 || !precond_factors_available(ctx))
+        TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_precond_schur_apply: the preconditioner of this context is not the rank-level dissection (tdgl_poisson_schur_begin ... _finish)");
+    TDGL_TRY(comm_ready(ctx));
+    const size_t bytes = (size_t)ctx->n_own * sizeof(double);
+    DevBuf<double> in, out, part;
+    HIP_TRY(ctx, in.alloc(ctx->n_pad));
+    HIP_TRY(ctx, out.alloc(ctx->n_pad));
+    HIP_TRY(ctx, part.alloc((size_t)ctx->npart));
+    HIP_TRY(ctx, hipMemcpyAsync(in.p, r, bytes, hipMemcpyHostToDevice, ctx->stream));
+    TDGL_TRY(precond_schur_apply(ctx, in.p, out.p, part.p));
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<double> h((size_t)ctx->npart);
+    HIP_TRY(ctx, hipMemcpyAsync(h.data(), part.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(z, out.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    double s = 0.0;
+    for (double v : h) s += v;
+    *rz = s;
     return TDGL_OK;
 }
 

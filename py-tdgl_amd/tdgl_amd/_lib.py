@@ -346,6 +346,7 @@ SIGNATURES = {
     "tdgl_poisson_schur_complement": (C.c_int, [_CTX, c_f64p]),
     "tdgl_poisson_schur_finish": (C.c_int, [_CTX, c_f64p, C.c_int32, c_f64p, c_f64p]),
     "tdgl_poisson_set_precond_times": (C.c_int, [_CTX, C.c_double, C.c_double]),
+    "tdgl_precond_schur_apply": (C.c_int, [_CTX, c_f64p, c_f64p, c_f64p]),
     "tdgl_get_precond_direct_stats": (C.c_int, [_CTX, C.POINTER(C.c_int64), c_f64p, C.c_int32]),
     "tdgl_get_precond_direct_layout": (C.c_int, [_CTX, C.POINTER(C.c_int32)]),
     "tdgl_get_precond_direct_blr": (C.c_int, [_CTX, c_i64p, c_f64p]),

@@ -767,12 +767,13 @@ class TDGLContext:
         self.precond_direct_stats(reset=True)
         return True
 
-    def build_schur_precond(self, piece, allreduce_sum, allreduce_max, choice=None) -> bool:
+    def build_schur_precond(self, piece, allreduce_sum, allreduce_max, choice=None, fp32_storage=True) -> bool:
         """One-process-per-GPU mode: this rank's share of the RANK-LEVEL nested dissection (`schur_dd.SchurPiece`) as the
         CG's second preconditioner (`tdgl_poisson_schur_begin` ... `_finish`).  ``allreduce_sum(array) -> array`` /
         ``allreduce_max(array) -> array`` over the bootstrap group: the interface complement is summed ONCE, the measured
         times of the two preconditioners are agreed on (so that every rank takes the same choice in every solve).  Every
-        rank calls this at the same point; returns whether the preconditioner is on (the same answer on every rank)."""
+        rank calls this at the same point; returns whether the preconditioner is on (the same answer on every rank).
+        ``fp32_storage=False`` keeps the local factors and the interface's pseudo-inverse in fp64 (tests)."""
         from . import substructure
 
         ok = 1.0
@@ -813,16 +814,17 @@ class TDGLContext:
         with _Stopwatch(self.setup_times, "schur_sum"):
             S = np.ascontiguousarray(allreduce_sum(S))
         ta, tv = C.c_double(0.0), C.c_double(0.0)
-        self._chk(self._lib.tdgl_poisson_schur_finish(self._ctx, p_f64(S), 1, C.byref(ta), C.byref(tv)))
+        self._chk(self._lib.tdgl_poisson_schur_finish(self._ctx, p_f64(S), int(bool(fp32_storage)), C.byref(ta), C.byref(tv)))
         times = allreduce_max(np.array([ta.value, tv.value]))
         self._chk(self._lib.tdgl_poisson_set_precond_times(self._ctx, float(times[0]), float(times[1])))
         self._chk(self._lib.tdgl_poisson_precond_choice(self._ctx, int(self.PD_CHOICE if choice is None else choice)))
         self.setup_times["substructure_device"] = t_dev
         tiles = self.precond_direct_layout()
+        word = 4 if fp32_storage else 8
         self.precond_direct = dict(
-            kind="rank-level nested dissection", levels=len(levels), storage="fp32", symmetric_tiles=[bool(t) for t in tiles[:len(levels)]], interior=int(piece.n_interior), interface=ng,
+            kind="rank-level nested dissection", levels=len(levels), storage="fp32" if fp32_storage else "fp64", symmetric_tiles=[bool(t) for t in tiles[:len(levels)]], interior=int(piece.n_interior), interface=ng,
             interface_owned=int(len(keep["gl"])), parts=levels[0].n_parts, separator=levels[0].n_sep,
-            bytes_per_application=int(2 * _factor_bytes(levels, tiles, word=4, top=False) + 4 * ng * ng // 2
+            bytes_per_application=int(2 * _factor_bytes(levels, tiles, word=word, top=False) + word * ng * ng // 2
                                       + 12 * (piece.A_GI.nnz + piece.A_IG.nnz)),
             allreduce_doubles_per_application=ng, t_apply_us=round(float(times[0]), 1), t_vcycle_us=round(float(times[1]), 1))
         self.precond_direct_stats(reset=True)
@@ -1725,6 +1727,18 @@ class TDGLContext:
         z = np.empty(self.n)
         rz = np.zeros(1)
         self._chk(self._lib.tdgl_precond_apply(self._ctx, p_f64(r), p_f64(z), p_f64(rz)))
+        return z, float(rz[0])
+
+    def precond_schur_apply(self, r_own):
+        """`tdgl_precond_schur_apply`: one application of the rank-level dissection on this rank's owned rows (local site
+        order), ``(z_own, r . z)``.  COLLECTIVE: every rank calls it at the same point (one all-reduce of |Gamma| doubles).
+        The CG's state stays as it is."""
+        r = f64(r_own)
+        if r.shape != (self.n_owned,):
+            raise ValueError(f"r must be [{self.n_owned}] (the owned sites), got {r.shape}")
+        z = np.empty(self.n_owned)
+        rz = np.zeros(1)
+        self._chk(self._lib.tdgl_precond_schur_apply(self._ctx, p_f64(r), p_f64(z), p_f64(rz)))
         return z, float(rz[0])
 
     def precond_apply_stats(self):

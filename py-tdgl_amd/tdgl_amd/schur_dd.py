@@ -22,8 +22,8 @@ one sum of |Gamma| doubles, one exchange of z's first ghost layer and the CG's o
 two-level distributed AMG cycle needs ~9 iterations of (exchange + two sums).
 
 This module holds the host side: the cover, each rank's index sets and coupling blocks, the local dissection order.
-`distributed.DistributedTDGL` drives the device (`tdgl_poisson_set_schur_*`), `tests/dist_model.py` restates the
-application in NumPy for the CPU tests.
+`distributed.DistributedTDGL` drives the device (`tdgl_poisson_schur_*`), `tests/dist_model.py` restates the
+application in NumPy for the CPU tests, `tests/schur_rank_model.py` rank by rank for the check of one device rank.
 """
 
 from dataclasses import dataclass

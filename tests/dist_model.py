@@ -217,34 +217,24 @@ def schur_setup_dist(lp, piece):
     pseudo-inverse on every rank."""
     import scipy.sparse.linalg as spla
 
+    from schur_rank_model import schur_share
     from tdgl_amd.schur_dd import interface_pinv
 
     lu = spla.splu(piece.A_II.tocsc())
-    touched = np.unique(piece.A_IG.indices)
-    X = lu.solve(piece.A_IG[:, touched].toarray())
-    S = piece.A_GG_owned.toarray()
-    S[np.ix_(touched, touched)] -= piece.A_GI[touched] @ X
-    t = torch.from_numpy(S)
+    t = torch.from_numpy(schur_share(piece, lu.solve))
     dist.all_reduce(t)
     return lu, interface_pinv(t.numpy())
 
 
 def schur_apply_dist(lp, piece, lu, Spinv, r_own, counts=None):
     """One application ``z = M r`` on the owned rows: two local solves, ONE all-reduce of |Gamma| doubles, a replicated
-    dense product (the sequence of csrc/schur.inc: precond_schur_apply)."""
-    r_loc = np.zeros(lp.n_loc)
-    r_loc[: lp.n_own] = r_own
-    y = lu.solve(r_loc[piece.interior])
-    t = np.zeros(piece.n_gamma)
-    t[piece.gamma_owned_gid] = r_loc[piece.gamma_owned_local]
-    t -= piece.A_GI @ y
-    t = allreduce_sum(t)
+    dense product (the sequence of csrc/schur.inc: precond_schur_apply).  The rank-local halves are those of
+    tests/schur_rank_model.py; this is the gloo wrapper around them."""
+    from schur_rank_model import interface_share, interior_solve, result_from_interface
+
+    y = interior_solve(piece, lu.solve, r_own)
+    t = allreduce_sum(interface_share(piece, r_own, y))
     if counts is not None:
         counts["allreduces"] = counts.get("allreduces", 0) + 1
         counts["allreduce_values"] = counts.get("allreduce_values", 0) + piece.n_gamma
-    xg = Spinv @ t
-    xi = y - lu.solve(piece.A_IG @ xg)
-    z = np.zeros(lp.n_own)
-    z[piece.interior] = xi  # (interior ids are owned ids: < n_own)
-    z[piece.gamma_owned_local] = xg[piece.gamma_owned_gid]
-    return z
+    return result_from_interface(piece, lu.solve, lp.n_own, y, Spinv @ t)
