@@ -668,6 +668,34 @@ int tdgl_set_mu_boundary_table(tdgl_ctx *ctx, int32_t n_nodes, const double *tim
                                const int32_t *group_ptr, const int32_t *group_pos, const double *density);
 int tdgl_set_epsilon_table(tdgl_ctx *ctx, const double *epsilon0, int32_t n_nodes, const double *times,
                            const double *factor);
+/* Gaussian hot spots in the disorder parameter -- a photon's hot spot in a nanowire detector, a laser spot scanned over a
+ * film, a heater pulse --, evaluated by tdgl_run itself:
+ *   epsilon(r, t) = eps0(r) - sum_{k < K} a_k(t) exp(-|r - c_k(t)|^2 / (2 sigma_k(t)^2)),  1 <= K <= TDGL_EPS_SPOTS_MAX.
+ *   tdgl_set_epsilon_spots        sites [n_sites, 2] and eps0 [n_sites] in the caller's site order; per spot the nodes
+ *                                 tab_off[k] .. tab_off[k + 1] of tab_times (strictly increasing) with the centre tab_cx, tab_cy,
+ *                                 the amplitude tab_amp and the width tab_sigma, each piecewise linear in t and constant outside
+ *                                 the nodes.  Checked before anything in force is touched, so that a refused call leaves a
+ *                                 working epsilon: n_spots in [1, 4], every value finite, a >= 0 and sigma > 0 at every node
+ *                                 (with sigma^2 a normal number, about sigma >= 1.5e-154: a smaller one would make a site at
+ *                                 the spot's centre 0 / 0), eps0 <= 1 -- hence epsilon <= eps0 <= 1 and finite at all times.  Sets epsilon = epsilon(r, 0).
+ *                                 n_spots = 0 switches the spots off and leaves epsilon as last written.  Per site, spots in
+ *                                 spot order, every operation rounded on its own (no fused multiply-add):
+ *                                   dx = x - cx; dy = y - cy; d2 = dx*dx + dy*dy; den = 2.0 * (s*s); g = exp(-(d2 / den));
+ *                                   acc = eps0; acc = acc - a*g
+ *                                 -- what NumPy computes from the same values but for exp.  Both time loops use one kernel
+ *                                 (32 bytes per site) and agree to the last bit; the loop with one synchronisation per step skips
+ *                                 the pass when all 4 K values equal those applied last.
+ *   tdgl_update_epsilon_spots     applies values [n_spots][4] = cx, cy, a, sigma now.
+ *   tdgl_get_epsilon_spot_values  the n_spots x 4 values of the epsilon in force (n_spots = 0: no spots are set).
+ *   tdgl_get_epsilon              the epsilon in force [n_sites] in the caller's site order, whatever set it.
+ * Spots, tdgl_set_epsilon_table and tdgl_set_epsilon exclude each other: the later call wins. */
+#define TDGL_EPS_SPOTS_MAX 4
+int tdgl_set_epsilon_spots(tdgl_ctx *ctx, const double *sites, const double *eps0, int32_t n_spots, const int32_t *tab_off,
+                           const double *tab_times, const double *tab_cx, const double *tab_cy, const double *tab_amp,
+                           const double *tab_sigma);
+int tdgl_update_epsilon_spots(tdgl_ctx *ctx, const double *values);
+int tdgl_get_epsilon_spot_values(tdgl_ctx *ctx, int32_t *n_spots, double *values);
+int tdgl_get_epsilon(tdgl_ctx *ctx, double *epsilon);
 /* Initial / seed values of psi [n] complex and mu [n] (solver.py:284-288, 732-752). */
 int tdgl_set_state(tdgl_ctx *ctx, const double *psi, const double *mu);
 /* SolverOptions fields + resets the controller state (tentative_dt = dt_init,
@@ -1202,6 +1230,16 @@ int tdgl_ensemble_set_mu_boundary_table(tdgl_ensemble *ens, int32_t r, int32_t n
                                         const double *density);
 int tdgl_ensemble_set_epsilon_table(tdgl_ensemble *ens, int32_t r, const double *epsilon0, int32_t n_nodes,
                                     const double *times, const double *factor);
+/* set_epsilon_spots: replica r's hot spots with the arguments and rules of tdgl_set_epsilon_spots (n_spots and the nodes may
+ *   differ between replicas; n_spots = 0: off); sets the replica's epsilon to epsilon(r, 0).  The site coordinates are the
+ *   ensemble's and are stored at the first call: the `sites` of later calls are checked but not stored.  Spots,
+ *   set_epsilon_table and tdgl_ensemble_set_epsilon replace each other for the replica.  (tdgl_ensemble_set_epsilon goes
+ *   through the context's tdgl_set_epsilon, as the other plain setters go through theirs: it also switches off a table or
+ *   spots the CONTEXT itself carried -- an ensemble's context is its scratch, not a run of its own.)  get_epsilon: replica r's epsilon in force [n_sites], in the caller's order, whatever set it. */
+int tdgl_ensemble_set_epsilon_spots(tdgl_ensemble *ens, int32_t r, const double *sites, const double *eps0, int32_t n_spots,
+                                    const int32_t *tab_off, const double *tab_times, const double *tab_cx, const double *tab_cy,
+                                    const double *tab_amp, const double *tab_sigma);
+int tdgl_ensemble_get_epsilon(tdgl_ensemble *ens, int32_t r, double *epsilon);
 /* The same probe sites for every replica. */
 int tdgl_ensemble_set_probes(tdgl_ensemble *ens, const int32_t *sites, int32_t n_probe);
 /* The context's census (tdgl_set_census, called before this) for every replica; a context without one switches it

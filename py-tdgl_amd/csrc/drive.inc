@@ -86,6 +86,14 @@ static void launch_ra_eps_table(tdgl_ctx *ctx) {
                        ctx->eps.p, (int)T.t.size(), (const double *)T.d_t.p, (const double *)T.d_f.p, (const StepCtl *)ctx->d_ctl.p);
 }
 
+// epsilon = epsilon0 - the spots of S, into eps: at the values sv (ctl == nullptr, the host has decided) or at the time of the
+// run-ahead loop's attempt.  xy, eps0: the owner's (a replica's lie in its ensemble's arrays)
+static void launch_eps_spots(tdgl_ctx *ctx, const EpsSpots &S, const EpsSpotValues &sv, const double2 *xy, const double *eps0, double *eps,
+                             const StepCtl *ctl) {
+    hipLaunchKernelGGL(k_eps_spots, dim3(grid_for(ctx->n_pad)), dim3(BLOCK), 0, ctx->stream, ctx->n_pad, sv, S.tabs, (const double *)S.d_pool.p, xy,
+                       eps0, eps, S.d_applied.p, ctl);
+}
+
 // ---- what the setters refuse (the tables are piecewise linear, evaluated inside tdgl_run by table_value, kernels.inc) ----------
 static bool table_times_ok(const double *times, int32_t n) {
     for (int32_t k = 0; k < n; ++k)
@@ -122,6 +130,36 @@ static int check_mu_table(tdgl_ctx *ctx, const char *who, int32_t n_nodes, const
 static int check_eps_table(tdgl_ctx *ctx, const char *who, const double *epsilon0, int32_t n_nodes, const double *times, const double *factor) {
     if (!epsilon0) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: bad table (times must increase strictly)", who);
     return check_link_table(ctx, who, n_nodes, times, factor);
+}
+
+// a width the kernel can divide by: finite, > 0, and sigma^2 neither 0 nor subnormal (else a site at the centre would get 0 / 0)
+static bool eps_sigma_ok(double s) {
+    return std::isfinite(s) && s > 0.0 && s * s >= std::numeric_limits<double>::min();
+}
+
+// ... and the hot spots of tdgl_set_epsilon_spots and tdgl_ensemble_set_epsilon_spots.  With a >= 0 and epsilon0 <= 1 epsilon
+// stays <= 1 at every time (solver.py:215), so nothing is checked per step
+static int check_eps_spots(tdgl_ctx *ctx, const char *who, const double *sites, const double *eps0, int32_t n_spots, const int32_t *tab_off,
+                           const double *times, const double *cx, const double *cy, const double *amp, const double *sigma) {
+    if (n_spots < 1 || n_spots > EPS_SPOTS_MAX) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: n_spots must be in [0, %d]", who, EPS_SPOTS_MAX);
+    if (!sites || !eps0 || !tab_off || !times || !cx || !cy || !amp || !sigma) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: null argument", who);
+    for (int64_t i = 0; i < 2 * ctx->n; ++i)
+        if (!std::isfinite(sites[i])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: sites: non-finite coordinate", who);
+    for (int64_t i = 0; i < ctx->n; ++i)
+        if (!(std::isfinite(eps0[i]) && eps0[i] <= 1.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: eps0 must be finite and <= 1", who);
+    if (tab_off[0] != 0) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: tab_off must start at 0", who);
+    for (int32_t k = 0; k < n_spots; ++k) {
+        const int32_t o = tab_off[k], nn = tab_off[k + 1] - o;
+        if (nn < 1) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: spot %d has no nodes (tab_off)", who, k);
+        if (!table_times_ok(times + o, nn)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: spot %d: tab_times must be finite and increase strictly", who, k);
+        for (int32_t i = o; i < o + nn; ++i) {
+            if (!std::isfinite(cx[i])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: spot %d: non-finite tab_cx", who, k);
+            if (!std::isfinite(cy[i])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: spot %d: non-finite tab_cy", who, k);
+            if (!(std::isfinite(amp[i]) && amp[i] >= 0.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: spot %d: tab_amp must be finite and >= 0", who, k);
+            if (!eps_sigma_ok(sigma[i])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "%s: spot %d: tab_sigma must be finite and > 0, with a normal square", who, k);
+        }
+    }
+    return TDGL_OK;
 }
 
 // what tdgl_set_link_terms and tdgl_ensemble_set_link_terms refuse: the rules of tdgl_set_link_ramp and check_link_table, term by term
@@ -480,9 +518,17 @@ extern "C" int tdgl_set_epsilon(tdgl_ctx *ctx, const double *epsilon) {
     CTX_GUARD(ctx);
     if (!epsilon) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_set_epsilon: null epsilon");
     TDGL_TRY(upload_sites(ctx, epsilon, ctx->eps));
+    ctx->eps_tab.clear(), ctx->eps_spots.clear();  // (plain values, a table and spots exclude each other: the later call wins)
     ctx->have_eps = true;
     ctx->choice.reset();
     return TDGL_OK;
+}
+
+extern "C" int tdgl_get_epsilon(tdgl_ctx *ctx, double *epsilon) {
+    CTX_GUARD(ctx);
+    if (!epsilon) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_get_epsilon: null epsilon");
+    if (!ctx->have_eps) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_get_epsilon: no epsilon is set");
+    return download_sites(ctx, (const double *)ctx->eps.p, epsilon);
 }
 
 // mu_boundary -> boundary term of the Poisson right-hand side (everything queued on the stream)
@@ -616,6 +662,68 @@ bool EpsTable::step(double time) {
     return true;
 }
 
+void EpsSpots::forget() {
+    for (auto &row : last)
+        for (double &x : row) x = NAN;
+}
+
+void EpsSpots::clear() {
+    n_spots = 0;
+    pool.clear();
+    tabs = EpsSpotTabs{};
+    forget();
+    xy.release(), eps0.release(), d_pool.release(), d_applied.release();
+    on_device = false;
+}
+
+void EpsSpots::set(int32_t n, const int32_t *tab_off, const double *times, const double *cx, const double *cy, const double *amp,
+                   const double *sigma) {
+    n_spots = n;
+    const int32_t T = tab_off[n];
+    tabs = EpsSpotTabs{};
+    tabs.n = n, tabs.T = T, tabs.base = 0;
+    for (int32_t k = 0; k <= n; ++k) tabs.off[k] = tab_off[k];
+    pool.assign(times, times + T);
+    for (const double *q : {cx, cy, amp, sigma}) pool.insert(pool.end(), q, q + T);
+    forget();
+}
+
+int EpsSpots::to_device(tdgl_ctx *ctx, const double *sites, const double *eps0_ref) {
+    HIP_TRY(ctx, xy.alloc(ctx->n_pad));
+    TDGL_TRY(upload_sites(ctx, reinterpret_cast<const double2 *>(sites), xy));
+    HIP_TRY(ctx, eps0.alloc(ctx->n_pad));
+    TDGL_TRY(upload_sites(ctx, eps0_ref, eps0));
+    HIP_TRY(ctx, d_pool.upload(pool));
+    HIP_TRY(ctx, d_applied.alloc(1));
+    on_device = ctx->n_own == ctx->n;  // (the run-ahead loop is the single GPU's)
+    return TDGL_OK;
+}
+
+EpsSpotValues EpsSpots::values_at(double time) const { return eps_spot_values_at(tabs, pool.data(), time); }
+
+EpsSpotValues EpsSpots::values() const {
+    EpsSpotValues sv{};
+    sv.n = n_spots;
+    for (int k = 0; k < n_spots; ++k)
+        for (int j = 0; j < 4; ++j) sv.v[k][j] = last[k][j];
+    return sv;
+}
+
+void EpsSpots::applied(const EpsSpotValues &sv) {
+    for (int k = 0; k < n_spots; ++k)
+        for (int j = 0; j < 4; ++j) last[k][j] = sv.v[k][j];
+}
+
+// like EpsTable::step: the pass is skipped when all 4 K values equal those applied last
+bool EpsSpots::step(double time) {
+    const EpsSpotValues now = values_at(time);
+    bool changed = false;
+    for (int k = 0; k < n_spots; ++k)
+        for (int j = 0; j < 4; ++j) changed |= !(now.v[k][j] == last[k][j]);
+    if (changed) applied(now);
+    return changed;
+}
+
 }  // namespace tdgl
 
 extern "C" int tdgl_set_mu_boundary_table(tdgl_ctx *ctx, int32_t n_nodes, const double *times, int32_t n_groups,
@@ -643,7 +751,75 @@ extern "C" int tdgl_set_epsilon_table(tdgl_ctx *ctx, const double *epsilon0, int
     if (T.eps0.n == 0) HIP_TRY(ctx, T.eps0.alloc(ctx->n_pad));
     TDGL_TRY(upload_sites(ctx, epsilon0, T.eps0));
     T.set(n_nodes, times, factor);
+    ctx->eps_spots.clear();  // (a table and spots exclude each other: the later call wins)
     if (ctx->n_own == ctx->n) TDGL_TRY(T.to_device(ctx));  // device copy for the run-ahead loop
+    return TDGL_OK;
+}
+
+// epsilon(r, t) = epsilon0(r) - sum_k a_k(t) exp(-|r - c_k(t)|^2 / (2 sigma_k(t)^2)); sets epsilon = epsilon(r, 0)
+extern "C" int tdgl_set_epsilon_spots(tdgl_ctx *ctx, const double *sites, const double *eps0, int32_t n_spots, const int32_t *tab_off,
+                                      const double *tab_times, const double *tab_cx, const double *tab_cy, const double *tab_amp,
+                                      const double *tab_sigma) {
+    CTX_GUARD(ctx);
+    if (n_spots == 0) {  // off: epsilon stays as last written
+        ctx->eps_spots.clear();
+        return TDGL_OK;
+    }
+    // everything is checked, and the device's copies are complete, before anything in force is touched
+    TDGL_TRY(check_eps_spots(ctx, "tdgl_set_epsilon_spots", sites, eps0, n_spots, tab_off, tab_times, tab_cx, tab_cy, tab_amp, tab_sigma));
+    EpsSpots next;
+    next.set(n_spots, tab_off, tab_times, tab_cx, tab_cy, tab_amp, tab_sigma);
+    TDGL_TRY(next.to_device(ctx, sites, eps0));
+    (void)next.step(0.0);
+    launch_eps_spots(ctx, next, next.values(), next.xy.p, next.eps0.p, ctx->eps.p, nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // (only now: a failure above leaves the table or the spots that were in force)
+    ctx->eps_tab.clear();
+    ctx->eps_spots = std::move(next);
+    ctx->have_eps = true;
+    ctx->choice.reset();
+    return TDGL_OK;
+}
+
+// applies cx, cy, a, sigma of every spot now: what the loop with one synchronisation per step does itself
+extern "C" int tdgl_update_epsilon_spots(tdgl_ctx *ctx, const double *values) {
+    CTX_GUARD(ctx);
+    EpsSpots &S = ctx->eps_spots;
+    if (!S.on()) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "call tdgl_set_epsilon_spots first");
+    if (!values) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_epsilon_spots: null values");
+    EpsSpotValues sv{};
+    sv.n = S.n_spots;
+    for (int k = 0; k < S.n_spots; ++k) {
+        const double *q = values + 4 * k;
+        if (!(std::isfinite(q[0]) && std::isfinite(q[1]))) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_epsilon_spots: spot %d: non-finite centre", k);
+        if (!(std::isfinite(q[2]) && q[2] >= 0.0)) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_epsilon_spots: spot %d: the amplitude must be finite and >= 0", k);
+        if (!eps_sigma_ok(q[3])) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_update_epsilon_spots: spot %d: sigma must be finite and > 0, with a normal square", k);
+        for (int j = 0; j < 4; ++j) sv.v[k][j] = q[j];
+    }
+    S.applied(sv);
+    launch_eps_spots(ctx, S, sv, S.xy.p, S.eps0.p, ctx->eps.p, nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->have_eps = true;
+    return TDGL_OK;
+}
+
+// the K x 4 values of the epsilon in force (n_spots = 0: no spots are set): the host's record, or -- after a run-ahead batch,
+// whose values the host did not see -- what the kernel left
+extern "C" int tdgl_get_epsilon_spot_values(tdgl_ctx *ctx, int32_t *n_spots, double *values) {
+    CTX_GUARD(ctx);
+    if (!n_spots || !values) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_get_epsilon_spot_values: null output");
+    const EpsSpots &S = ctx->eps_spots;
+    *n_spots = S.n_spots;
+    if (!S.on()) return TDGL_OK;
+    EpsSpotValues sv = S.values();
+    if (std::isnan(sv.v[0][0]) && S.d_applied.p) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(&sv, S.d_applied.p, sizeof(sv), hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < S.n_spots; ++k)
+        for (int j = 0; j < 4; ++j) values[4 * k + j] = sv.v[k][j];
     return TDGL_OK;
 }
 
@@ -661,6 +837,11 @@ static int apply_time_tables(tdgl_ctx *ctx) {
     if (E.on() && E.step(ctx->loop.time)) {
         hipLaunchKernelGGL(k_scale, dim3(grid_for(ctx->n_pad)), dim3(BLOCK), 0, ctx->stream, ctx->n_pad, E.last,
                            (const double *)E.eps0.p, ctx->eps.p);
+        ctx->have_eps = true;
+    }
+    EpsSpots &S = ctx->eps_spots;
+    if (S.on() && S.step(ctx->loop.time)) {
+        launch_eps_spots(ctx, S, S.values(), S.xy.p, S.eps0.p, ctx->eps.p, nullptr);
         ctx->have_eps = true;
     }
     return TDGL_OK;

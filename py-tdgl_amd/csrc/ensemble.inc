@@ -328,6 +328,19 @@ __global__ __launch_bounds__(BLOCK) void k_ens_eps_table(int64_t n_pad, const do
     eps_table_body(i, eps0 + o, eps + o, nn, times + t0, factor + t0, c->time);
 }
 
+// T3: epsilon = epsilon0_r - replica r's hot spots (k_eps_spots) at its own time; tabs[r]: where its nodes lie in the pool
+// (n = 0: the replica has no spots and returns at once).  xy: the ensemble's site coordinates
+__global__ __launch_bounds__(BLOCK) void k_ens_eps_spots(int64_t n_pad, const double2 *__restrict__ xy, const double *__restrict__ eps0,
+                                                         double *__restrict__ eps, const EpsSpotTabs *__restrict__ tabs,
+                                                         const double *__restrict__ pool, const StepCtl *__restrict__ ctl) {
+    const int r = blockIdx.y;
+    const StepCtl *c = ctl + r;
+    const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+    if (tabs[r].n == 0 || c->poisoned || i >= n_pad) return;
+    const int64_t o = (int64_t)r * n_pad;
+    eps_spots_body(i, eps_spot_values_at(tabs[r], pool, c->time), xy, eps0 + o, eps + o);
+}
+
 }  // namespace tdgl
 
 struct EnsReplica {
@@ -336,6 +349,7 @@ struct EnsReplica {
     FieldArrays field;  // a moving field: the replica's own bases and A_0 (its descriptors and tables live in the ensemble's pools)
     MuTable mu_tab;    // tabulated terminal currents / separable epsilon: the host's nodes (their device copy is the ensemble's pools)
     EpsTable eps_tab;
+    EpsSpots eps_spots;  // hot spots in epsilon: likewise (and the site coordinates are the ensemble's)
 };
 
 struct tdgl_ensemble {
@@ -352,13 +366,16 @@ struct tdgl_ensemble {
     // (m_pad), the boundary term before dA/dt (n_pad), mu_boundary (nb), epsilon0 (n_pad); the tables as pools
     DevBuf<double> A, Aprev, dadt, cvec, mu_b, eps0;
     DevBuf<double> mu_t, mu_dens, eps_t, eps_f;
+    DevBuf<double2> spot_xy;            // hot spots: the site coordinates [n_pad], stored once ...
+    DevBuf<double> spot_pool;           // ... and every replica's nodes
+    DevBuf<EpsSpotTabs> spot_tabs;      // [R]
     DevBuf<int32_t> mu_toff, mu_group, eps_off, ramping, moved;  // ramping[r]: the replica's field moves in this batch
     DevBuf<int64_t> mu_doff;
     // the moving fields: per replica FIELD_TERMS_MAX descriptors, the pools of their tables' nodes, the replicas' bases and A_0
     DevBuf<FieldTerm> term_desc;
     DevBuf<double> tab_term_t, tab_term_v;
     DevBuf<const double *> term_bases, term_a0;
-    bool tables_dirty = true, any_mu_table = false, any_eps_table = false;  // (dirty: the pools and their offsets exist from the first run on)
+    bool tables_dirty = true, any_mu_table = false, any_eps_table = false, any_eps_spots = false;  // (dirty: the pools and their offsets exist from the first run on)
     std::vector<int32_t> h_ramping;
     std::vector<StepCtl> h_ctl;
     std::vector<StepRec> h_rec;
@@ -695,10 +712,57 @@ extern "C" int tdgl_ensemble_set_epsilon_table(tdgl_ensemble *e, int32_t r, cons
         TDGL_TRY(upload_sites(ctx, epsilon0, tmp));
         TDGL_TRY(ens_copy(ctx, e->eps0.p + r * e->n_pad, tmp.p, e->n_pad));
     }
-    if (n_nodes != 0) p.eps_tab.set(n_nodes, times, factor);
+    if (n_nodes != 0) p.eps_tab.set(n_nodes, times, factor), p.eps_spots.clear();
     else p.eps_tab.clear();
     e->tables_dirty = true;
     return TDGL_OK;
+}
+
+// replica r's epsilon(r, t) = epsilon0(r) - its hot spots (tdgl_set_epsilon_spots' arguments and rules); n_spots = 0: off.
+// The site coordinates are the ensemble's: stored at the first call
+extern "C" int tdgl_ensemble_set_epsilon_spots(tdgl_ensemble *e, int32_t r, const double *sites, const double *eps0, int32_t n_spots,
+                                               const int32_t *tab_off, const double *tab_times, const double *tab_cx, const double *tab_cy,
+                                               const double *tab_amp, const double *tab_sigma) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    EnsReplica &p = e->rep[r];
+    if (n_spots == 0) {
+        p.eps_spots.clear();
+        e->tables_dirty = true;
+        return TDGL_OK;
+    }
+    TDGL_TRY(check_eps_spots(ctx, "tdgl_ensemble_set_epsilon_spots", sites, eps0, n_spots, tab_off, tab_times, tab_cx, tab_cy, tab_amp, tab_sigma));
+    if (e->eps0.n == 0) HIP_TRY(ctx, e->eps0.alloc((size_t)e->R * e->n_pad));
+    if (e->spot_xy.n == 0) {
+        DevBuf<double2> xy;
+        HIP_TRY(ctx, xy.alloc(e->n_pad));
+        TDGL_TRY(upload_sites(ctx, reinterpret_cast<const double2 *>(sites), xy));
+        e->spot_xy.take(xy);
+    }
+    DevBuf<double> tmp;
+    HIP_TRY(ctx, tmp.alloc(e->n_pad));
+    TDGL_TRY(upload_sites(ctx, eps0, tmp));
+    TDGL_TRY(ens_copy(ctx, e->eps0.p + r * e->n_pad, tmp.p, e->n_pad));
+    p.eps_tab.clear();
+    EpsSpots &S = p.eps_spots;
+    S.clear();
+    S.set(n_spots, tab_off, tab_times, tab_cx, tab_cy, tab_amp, tab_sigma);
+    // epsilon = epsilon(r, 0), by the single run's kernel at the host's values
+    launch_eps_spots(ctx, S, S.values_at(0.0), e->spot_xy.p, e->eps0.p + r * e->n_pad, e->eps.p + r * e->n_pad, nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    p.have_eps = true;
+    e->tables_dirty = true;
+    return TDGL_OK;
+}
+
+// replica r's epsilon in force, in the caller's site order, whatever set it
+extern "C" int tdgl_ensemble_get_epsilon(tdgl_ensemble *e, int32_t r, double *epsilon) {
+    TDGL_TRY(ens_check(e, r));
+    tdgl_ctx *ctx = e->ctx;
+    if (!epsilon) TDGL_FAIL(ctx, TDGL_ERR_ARG, "tdgl_ensemble_get_epsilon: null epsilon");
+    if (!e->rep[r].have_eps) TDGL_FAIL(ctx, TDGL_ERR_NOT_READY, "tdgl_ensemble_get_epsilon: replica %d has no epsilon", r);
+    return download_sites(ctx, (const double *)(e->eps.p + r * e->n_pad), epsilon);
 }
 
 // the replicas' tables as pools on the device
@@ -709,7 +773,9 @@ static int ens_upload_tables(tdgl_ensemble *e) {
     std::vector<int32_t> toff(R + 1, 0), eoff(R + 1, 0), group((size_t)R * nb, -1);
     std::vector<int64_t> doff(R, 0);
     std::vector<double> mt, md, et, ef;
-    e->any_mu_table = e->any_eps_table = false;
+    e->any_mu_table = e->any_eps_table = e->any_eps_spots = false;
+    std::vector<EpsSpotTabs> stabs((size_t)R, EpsSpotTabs{});
+    std::vector<double> spool;
     for (int r = 0; r < R; ++r) {
         const EnsReplica &p = e->rep[r];
         doff[r] = (int64_t)md.size();
@@ -725,6 +791,16 @@ static int ens_upload_tables(tdgl_ensemble *e) {
         eoff[r + 1] = (int32_t)et.size();
         e->any_mu_table |= M.on();
         e->any_eps_table |= E.on();
+        if (p.eps_spots.on()) {
+            stabs[r] = p.eps_spots.tabs;
+            stabs[r].base = (int64_t)spool.size();
+            spool.insert(spool.end(), p.eps_spots.pool.begin(), p.eps_spots.pool.end());
+            e->any_eps_spots = true;
+        }
+    }
+    if (e->any_eps_spots) {  // (an ensemble without spots allocates nothing for them)
+        HIP_TRY(ctx, e->spot_tabs.upload(stabs));
+        HIP_TRY(ctx, e->spot_pool.upload(spool));
     }
     std::vector<FieldTerm> desc((size_t)R * FIELD_TERMS_MAX, FieldTerm{});
     std::vector<const double *> bases((size_t)R, nullptr), a0s((size_t)R, nullptr);
@@ -770,7 +846,12 @@ extern "C" int tdgl_ensemble_set_epsilon(tdgl_ensemble *e, int32_t r, const doub
     tdgl_ctx *ctx = e->ctx;
     TDGL_TRY(tdgl_set_epsilon(ctx, epsilon));
     TDGL_TRY(ens_copy(ctx, e->eps.p + r * e->n_pad, ctx->eps.p, e->n_pad));
-    e->rep[r].have_eps = true;
+    EnsReplica &p = e->rep[r];
+    if (p.eps_tab.on() || p.eps_spots.on()) {  // (plain values, a table and spots exclude each other: the later call wins)
+        p.eps_tab.clear(), p.eps_spots.clear();
+        e->tables_dirty = true;
+    }
+    p.have_eps = true;
     return TDGL_OK;
 }
 
@@ -902,6 +983,10 @@ static void ens_queue_drives(tdgl_ensemble *e, bool ramping) {
     if (e->any_eps_table)
         hipLaunchKernelGGL(k_ens_eps_table, dim3(grid_for(e->n_pad), R), dim3(BLOCK), 0, ctx->stream, e->n_pad, (const double *)e->eps0.p,
                            e->eps.p, (const int32_t *)e->eps_off.p, (const double *)e->eps_t.p, (const double *)e->eps_f.p,
+                           (const StepCtl *)e->d_ctl.p);
+    if (e->any_eps_spots)
+        hipLaunchKernelGGL(k_ens_eps_spots, dim3(grid_for(e->n_pad), R), dim3(BLOCK), 0, ctx->stream, e->n_pad, (const double2 *)e->spot_xy.p,
+                           (const double *)e->eps0.p, e->eps.p, (const EpsSpotTabs *)e->spot_tabs.p, (const double *)e->spot_pool.p,
                            (const StepCtl *)e->d_ctl.p);
     if (!ramping) return;
     const SellPattern &pat = ctx->lap_pat;

@@ -868,6 +868,62 @@ __global__ __launch_bounds__(BLOCK) void k_ra_eps_table(int64_t n, const double 
     eps_table_body(i, eps0, eps, n_nodes, times, factor, ctl->time);
 }
 
+// ---- Gaussian hot spots in epsilon (EpsSpots, tdgl_set_epsilon_spots) --------------------------------------------------------
+// epsilon(r, t) = epsilon0(r) - sum_k a_k(t) exp(-|r - c_k(t)|^2 / (2 sigma_k(t)^2)), K <= EPS_SPOTS_MAX spots whose centre x, y,
+// amplitude and width are piecewise-linear tables over the spot's own nodes.
+// The four values of every spot at `time`: the host's step rule and every lane of the kernels evaluate THIS (table_value), so
+// the values are the same bits wherever they are formed.  pool: the nodes' times, then cx, cy, a, sigma, tabs.T apart, from tabs.base
+__host__ __device__ inline EpsSpotValues eps_spot_values_at(const EpsSpotTabs &tabs, const double *__restrict__ pool, double time) {
+    EpsSpotValues sv{};
+    sv.n = tabs.n;
+    const double *p = pool + tabs.base;
+    for (int k = 0; k < EPS_SPOTS_MAX; ++k) {
+        if (k >= tabs.n) break;
+        const int32_t off = tabs.off[k], nn = tabs.off[k + 1] - off;
+        for (int j = 0; j < 4; ++j) sv.v[k][j] = table_value(p + off, p + (int64_t)(j + 1) * tabs.T + off, nn, time);
+    }
+    return sv;
+}
+
+// One lane per site, spots in spot order; every operation rounded on its own (no contraction: the pragma, and the empty asm
+// between a product and the sum or difference that takes it), so that NumPy restates it operation for operation -- all but
+// exp.  32 bytes per site: the coordinates as one double2, epsilon0 read, epsilon written.  (s*s is a normal number -- the
+// setters check it --, so den > 0 and a site at a spot's centre gets g = exp(-0) = 1, never 0 / 0.)
+__device__ __forceinline__ void eps_spots_body(int64_t i, const EpsSpotValues &sv, const double2 *__restrict__ xy,
+                                               const double *__restrict__ eps0, double *__restrict__ eps) {
+#pragma clang fp contract(off)
+    const double2 r = xy[i];
+    double acc = eps0[i];
+#pragma unroll
+    for (int k = 0; k < EPS_SPOTS_MAX; ++k) {
+        if (k >= sv.n) break;
+        const double dx = r.x - sv.v[k][0], dy = r.y - sv.v[k][1], s = sv.v[k][3];
+        double xx = dx * dx, yy = dy * dy, ss = s * s;
+        asm volatile("" : "+v"(xx), "+v"(yy), "+v"(ss));
+        const double d2 = xx + yy, den = 2.0 * ss;
+        const double g = exp(-(d2 / den));
+        double p = sv.v[k][2] * g;
+        asm volatile("" : "+v"(p));
+        acc = acc - p;
+    }
+    eps[i] = acc;
+}
+
+// ctl: the run-ahead loop's controller -- every lane evaluates the tables at ctl->time, uniformly across the wavefront, and a
+// poisoned attempt returns at once; nullptr: the host has decided, the values are `host`'s.  The first lane leaves the values it
+// applied in `applied` (what tdgl_get_epsilon_spot_values reports after a batch the host did not see).
+__global__ __launch_bounds__(BLOCK) void k_eps_spots(int64_t n, EpsSpotValues host, EpsSpotTabs tabs, const double *__restrict__ pool,
+                                                     const double2 *__restrict__ xy, const double *__restrict__ eps0,
+                                                     double *__restrict__ eps, EpsSpotValues *__restrict__ applied,
+                                                     const StepCtl *__restrict__ ctl) {
+    if (ctl && ctl->poisoned) return;
+    const int64_t i = blockIdx.x * (int64_t)BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const EpsSpotValues sv = ctl ? eps_spot_values_at(tabs, pool, ctl->time) : host;
+    if (i == 0 && applied) *applied = sv;
+    eps_spots_body(i, sv, xy, eps0, eps);
+}
+
 __global__ void k_probes(int n_probe, const int32_t *__restrict__ sites,
                          const double2 *__restrict__ psi, const double *__restrict__ mu,
                          double *__restrict__ out) {

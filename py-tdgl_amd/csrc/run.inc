@@ -365,7 +365,7 @@ static bool run_ahead_ok(const tdgl_ctx *ctx) {
     if (ctx->loop.ramping() ? !(ctx->loop.runner_dt > 0.0) : ctx->loop.field.has_dadt) return false;
     // (the plans of the direct solve: no screening, currents every step)
     return !off && dense_on(ctx) && (ctx->direct->dense.tiles > 0) && currents_plan_runs_ahead(step_plan(ctx)) &&
-           ctx->mu_tab.runs_ahead() && ctx->eps_tab.runs_ahead() && ctx->have_links &&
+           ctx->mu_tab.runs_ahead() && ctx->eps_tab.runs_ahead() && ctx->eps_spots.runs_ahead() && ctx->have_links &&
            ctx->have_state && ctx->have_eps && (!ctl.adaptive || (ctl.adaptive_window >= 1 && ctl.adaptive_window <= RA_HIST_MAX));
 }
 
@@ -383,12 +383,15 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
     const int np_ = (int)ctx->probes.size();
     const bool probing = np_ > 0 && want_probes;
     const bool owed_on_entry = ctx->currents.owed();
-    const bool mu_table = ctx->mu_tab.on(), eps_table = ctx->eps_tab.on();
+    const bool mu_table = ctx->mu_tab.on(), eps_table = ctx->eps_tab.on(), eps_spots = ctx->eps_spots.on();
     if (mu_table) TDGL_TRY(ctx->mu_tab.handed_to_device(ctx));
     if (eps_table) ctx->eps_tab.handed_to_device();
+    if (eps_spots) ctx->eps_spots.handed_to_device();
     for (int s = 0; s < batch; ++s) {
         if (mu_table) launch_ra_mu_table(ctx);
         if (eps_table) launch_ra_eps_table(ctx);
+        if (eps_spots)
+            launch_eps_spots(ctx, ctx->eps_spots, EpsSpotValues{}, ctx->eps_spots.xy.p, ctx->eps_spots.eps0.p, ctx->eps.p, ctx->d_ctl.p);
         if (ramping) {
             // A(t) moves: the owed currents of psi^n first (they belong to the links and dA/dt of the step that produced
             // it), then what TDGLSolver.update does before the psi update (solver.py:626-642) -- all of it skipped by
@@ -439,7 +442,7 @@ static int run_ahead(tdgl_ctx *ctx, int batch, double end_time, double *out_dt, 
         ctx->stat_host_syncs += 1;
         HIP_TRY(ctx, e);
     }
-    if (eps_table) ctx->have_eps = true;
+    if (eps_table || eps_spots) ctx->have_eps = true;
     const int done = h.n_done;
     // (mu and b are a pair when the last attempt that ran was accepted)
     if (guard) direct_guard_read(ctx, done > 0 && done <= batch && h.last_ok != 0);

@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <numeric>
 #include <string>
@@ -514,6 +515,52 @@ struct EpsTable {
     void handed_to_device();
 };
 
+// Gaussian hot spots epsilon(r, t) = epsilon0(r) - sum_k a_k(t) exp(-|r - c_k(t)|^2 / (2 sigma_k(t)^2)) (tdgl_set_epsilon_spots,
+// tdgl_ensemble_set_epsilon_spots): per spot the centre x, y, the amplitude and the width, each piecewise linear over the spot's
+// own nodes.  What the kernels take by value: the four values of every spot, and where the nodes lie in the owner's pool
+// (times, then cx, cy, a, sigma, T apart, from base; spot k: nodes off[k] .. off[k + 1])
+constexpr int EPS_SPOTS_MAX = 4;
+struct EpsSpotValues {
+    double v[EPS_SPOTS_MAX][4];  // cx, cy, a, sigma
+    int32_t n, pad;
+};
+struct EpsSpotTabs {
+    int32_t off[EPS_SPOTS_MAX + 1];
+    int32_t n, T;
+    int64_t base;
+};
+// ... and their one owner, next to EpsTable and likewise: the loop with one synchronisation per step evaluates the tables on
+// the host (step) and hands k_eps_spots the values, the run-ahead loop hands it the controller.  A replica of an ensemble
+// keeps the nodes only (the ensemble's pools are its device copy).  Its functions (drive.inc) are the only writers of its members.
+struct EpsSpots {
+    int n_spots = 0;
+    std::vector<double> pool;        // the host's nodes: every spot's times, then cx, cy, a, sigma (as the device's pool)
+    EpsSpotTabs tabs{};
+    double last[EPS_SPOTS_MAX][4];   // the values the host applied last (NaN: void)
+    DevBuf<double2> xy;              // site coordinates [n_pad] ...
+    DevBuf<double> eps0;             // ... and the static part, internal site order
+    DevBuf<double> d_pool;
+    DevBuf<EpsSpotValues> d_applied; // what the kernel applied last (read when the host's record is void)
+    bool on_device = false;
+
+    EpsSpots() { forget(); }
+    bool on() const { return n_spots > 0; }
+    bool runs_ahead() const { return !on() || on_device; }
+    void clear();
+    // from validated arguments (check_eps_spots)
+    void set(int32_t n, const int32_t *tab_off, const double *times, const double *cx, const double *cy, const double *amp,
+             const double *sigma);
+    // the device's copies: the caller's site coordinates [n, 2] and static part [n] through upload_sites' permutation, the
+    // nodes, and whether the run-ahead loop (the single GPU's) may evaluate them
+    int to_device(tdgl_ctx *ctx, const double *sites, const double *eps0_ref);
+    EpsSpotValues values_at(double time) const;
+    EpsSpotValues values() const;             // `last` as the kernel takes it
+    bool step(double time);                   // true: a value at `time`, now in `last`, differs from the one applied last
+    void applied(const EpsSpotValues &sv);    // the caller's values went to the device (tdgl_update_epsilon_spots)
+    void handed_to_device() { forget(); }     // a run-ahead batch is about to apply values the host does not see
+    void forget();
+};
+
 // The time loop's bookkeeping on the host, one per trajectory (tdgl_ctx, every replica of an ensemble): the controller
 // (solver.py:316-320, 475-485, 698-707), Runner.dt / time / step (runner.py:260-263, 429-433), the retry state a run-ahead
 // batch leaves behind and the moving applied field (FieldDrive).  The classic loop drives it event by event (begin_step,
@@ -905,6 +952,7 @@ struct tdgl_ctx {
     // piecewise-linear time tables evaluated by tdgl_run itself before every step (drive.inc)
     tdgl::MuTable mu_tab;
     tdgl::EpsTable eps_tab;
+    tdgl::EpsSpots eps_spots;
     // boundary term: c = mu_boundary_laplacian @ mu_boundary
     tdgl::DevBuf<int32_t> b_s0, b_s1;
     tdgl::DevBuf<int32_t> d_b_sites;      // the sites that boundary edges touch, each once (ensure_boundary_sites)

@@ -17,8 +17,8 @@ from .device import Device, Layer, Polygon, TerminalInfo  # noqa: F401
 from .finite_volume import EdgeMesh, Mesh  # noqa: F401
 from .operators import MeshOperators  # noqa: F401
 from .parameter import (  # noqa: F401
-    CompositeParameter, Constant, ConstantField, CurrentLoop, LinearRamp, MovingCurrentLoop, Parameter, PiecewiseLinear, Scale,
-    SeparableEpsilon, TabulatedCurrents, TabulatedRamp,
+    CompositeParameter, Constant, ConstantField, CurrentLoop, HotSpot, HotSpotEpsilon, LinearRamp, MovingCurrentLoop, Parameter,
+    PiecewiseLinear, Scale, SeparableEpsilon, TabulatedCurrents, TabulatedRamp,
 )
 from .options import SolverOptions, SolverOptionsError, SparseSolver  # noqa: F401
 from .solution import WINDING_UNDEFINED, BiotSavartField, BoundaryPhases, DynamicsData, Fluxoid, Solution, TDGLData  # noqa: F401

@@ -385,6 +385,10 @@ SIGNATURES = {
     "tdgl_set_mu_boundary": (C.c_int, [_CTX, c_f64p]),
     "tdgl_set_mu_boundary_table": (C.c_int, [_CTX, C.c_int32, c_f64p, C.c_int32, c_i32p, c_i32p, c_f64p]),
     "tdgl_set_epsilon_table": (C.c_int, [_CTX, c_f64p, C.c_int32, c_f64p, c_f64p]),
+    "tdgl_set_epsilon_spots": (C.c_int, [_CTX, c_f64p, c_f64p, C.c_int32, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "tdgl_update_epsilon_spots": (C.c_int, [_CTX, c_f64p]),
+    "tdgl_get_epsilon_spot_values": (C.c_int, [_CTX, c_i32p, c_f64p]),
+    "tdgl_get_epsilon": (C.c_int, [_CTX, c_f64p]),
     "tdgl_set_state": (C.c_int, [_CTX, c_f64p, c_f64p]),
     "tdgl_set_controller": (C.c_int, [_CTX, C.POINTER(Controller)]),
     "tdgl_set_probes": (C.c_int, [_CTX, c_i32p, C.c_int32]),
@@ -486,6 +490,9 @@ SIGNATURES = {
     "tdgl_ensemble_set_mu_boundary_table": (
         C.c_int, [_ENS, C.c_int32, C.c_int32, c_f64p, C.c_int32, c_i32p, c_i32p, c_f64p]),
     "tdgl_ensemble_set_epsilon_table": (C.c_int, [_ENS, C.c_int32, c_f64p, C.c_int32, c_f64p, c_f64p]),
+    "tdgl_ensemble_set_epsilon_spots": (
+        C.c_int, [_ENS, C.c_int32, c_f64p, c_f64p, C.c_int32, c_i32p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p]),
+    "tdgl_ensemble_get_epsilon": (C.c_int, [_ENS, C.c_int32, c_f64p]),
     "tdgl_ensemble_set_controller": (C.c_int, [_ENS, C.c_int32, C.POINTER(Controller)]),
     "tdgl_ensemble_begin_stage": (C.c_int, [_ENS, C.c_int32]),
     "tdgl_ensemble_set_probes": (C.c_int, [_ENS, c_i32p, C.c_int32]),

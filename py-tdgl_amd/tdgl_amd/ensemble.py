@@ -26,8 +26,8 @@ import numpy as np
 from . import _lib
 from ._lib import c128, f64, p_f64, p_i32
 from .device import Device
-from .hipcore import (FIELD_TERMS_MAX, TDGLContext, controller_struct, epsilon_table_args, link_table_args, link_terms_args,
-                      mu_boundary_table_args, probe_args, read_census, read_loop_state)
+from .hipcore import (FIELD_TERMS_MAX, TDGLContext, controller_struct, epsilon_spots_args, epsilon_table_args, link_table_args,
+                      link_terms_args, mu_boundary_table_args, probe_args, read_census, read_loop_state)
 from .options import SolverOptions, SolverOptionsError
 from .runloop import RunRecord, check_epsilon_table, check_seed
 from .solution import Solution
@@ -96,8 +96,9 @@ def _refuse_options(options: SolverOptions, n_sites: int) -> None:
 
 def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
     """Time dependence the ensemble evaluates on the device passes: a separable A whose factor is a LinearRamp or a
-    TabulatedRamp, a sum of a static field and such products, TabulatedCurrents, a SeparableEpsilon.  Anything else
-    raises."""
+    TabulatedRamp, a sum of a static field and such products, TabulatedCurrents, a SeparableEpsilon, a HotSpotEpsilon of
+    up to four spots (wherever a SeparableEpsilon may stand).  Anything else raises."""
+    spots = getattr(rep, "_eps_spots", None)
     if rep.field.refusal is not None:
         raise ValueError(f"solve_ensemble: replica {r}: a time-dependent applied_vector_potential is supported only as "
                          "LinearRamp(...) * (static field), TabulatedRamp(...) * (static field), or a sum (static field) + f_1 * "
@@ -105,10 +106,10 @@ def _refuse_dynamic(r: int, rep: TDGLSolver) -> None:
     if rep.dynamic_currents and rep._current_table is None:
         raise ValueError(f"solve_ensemble: replica {r}: time-dependent terminal_currents are not supported "
                          "(TabulatedCurrents are).")
-    if rep.dynamic_epsilon and rep._eps_table is None:
+    if rep.dynamic_epsilon and rep._eps_table is None and spots is None:
         raise ValueError(f"solve_ensemble: replica {r}: a time-dependent disorder_epsilon is not supported "
                          "(SeparableEpsilon is).")
-    if rep.device_evaluates_field() and (rep._current_table is not None or rep._eps_table is not None):
+    if rep.device_evaluates_field() and (rep._current_table is not None or rep._eps_table is not None or spots is not None):
         raise ValueError(f"solve_ensemble: replica {r}: {rep.field.noun} combined with TabulatedCurrents or a SeparableEpsilon "
                          "in one replica is not supported.")
 
@@ -133,7 +134,8 @@ def solve_ensemble(
     Time-dependent replicas: ``applied_vector_potential`` may be ``LinearRamp(...) * <static field>`` or
     ``TabulatedRamp(...) * <static field>`` (tables of any length, each replica its own), or a sum of a static field
     and up to four such products (`Parameter.separable_terms`; each replica its own terms),
-    ``terminal_currents`` a ``TabulatedCurrents``, ``disorder_epsilon`` a ``SeparableEpsilon`` (one kind of table or
+    ``terminal_currents`` a ``TabulatedCurrents``, ``disorder_epsilon`` a ``SeparableEpsilon`` or a ``HotSpotEpsilon`` of up
+    to four spots -- one replica per bias current or per absorption site -- (one kind of table or
     ramp per replica, except that tabulated currents and a separable epsilon may go together).  Static, ramped and
     tabulated replicas may share one ensemble.
 
@@ -160,7 +162,7 @@ def solve_ensemble(
 def solve_ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
                                  gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
                                  seed_states=None, vector_potential_ramp=None, epsilon_table=None,
-                                 vector_potential_table=None, vector_potential_terms=None) -> List[Solution]:
+                                 vector_potential_table=None, vector_potential_terms=None, epsilon_spots=None) -> List[Solution]:
     """``solve_ensemble`` from dimensionless inputs (``TDGLSolver.from_dimensionless``): ``link_exponents`` A[m, 2]
     (an array, or a list of them), ``epsilon`` (a scalar or an [n] array, or a list), ``currents``
     ({terminal: dimensionless current} or a ``TabulatedCurrents``, or a list), ``seed_states`` (None or a list of
@@ -171,10 +173,11 @@ def solve_ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, e
     ``vector_potential_table`` ``(A_base[m, 2], times, values)``: A(t) = TabulatedRamp(times, values)(t) * A_base (in a
     replica without a ramp; ``link_exponents`` may be None as for a ramp), ``vector_potential_terms`` ``(A0[m, 2] or
     None, [(A_k[m, 2], spec_k), ...])`` as in ``TDGLSolver.from_dimensionless`` (in a replica without ramp and table;
-    ``link_exponents`` may be None)."""
+    ``link_exponents`` may be None), ``epsilon_spots`` ``(eps0, [spot, ...])`` as in ``TDGLSolver.from_dimensionless`` (in a
+    replica without an ``epsilon_table``)."""
     return ensemble_dimensionless(mesh, options, link_exponents, epsilon, u, gamma, terminal_info, currents, probe_points,
                                   seed_states, vector_potential_ramp, epsilon_table, vector_potential_table,
-                                  vector_potential_terms).solve()
+                                  vector_potential_terms, epsilon_spots).solve()
 
 
 def _one_or_list(value, is_one):
@@ -211,7 +214,7 @@ def _with_epsilon_table(rep: TDGLSolver, table, n: int) -> None:
 def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon=1.0, u: float = 5.79,
                            gamma: float = 10.0, terminal_info=(), currents=None, probe_points=None,
                            seed_states=None, vector_potential_ramp=None, epsilon_table=None,
-                           vector_potential_table=None, vector_potential_terms=None) -> "EnsembleSolver":
+                           vector_potential_table=None, vector_potential_terms=None, epsilon_spots=None) -> "EnsembleSolver":
     """The `EnsembleSolver` behind `solve_ensemble_dimensionless` (its ``solve()`` returns the solutions)."""
     _refuse_options(options, len(mesh.sites))
     per = dict(link_exponents=link_exponents, currents=currents, seed_states=seed_states)
@@ -221,8 +224,9 @@ def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon
     tables = _one_or_list(epsilon_table, lambda v: isinstance(v, tuple) and len(v) == 3)
     fields = _one_or_list(vector_potential_table, lambda v: isinstance(v, tuple) and len(v) == 3)
     sums = _one_or_list(vector_potential_terms, lambda v: isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], list))
+    spots = _one_or_list(epsilon_spots, lambda v: isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], list))
     for name, v in (("vector_potential_ramp", ramps), ("epsilon_table", tables), ("vector_potential_table", fields),
-                    ("vector_potential_terms", sums)):
+                    ("vector_potential_terms", sums), ("epsilon_spots", spots)):
         if not isinstance(v, _Same):
             per[name] = v
     R, args = broadcast_replicas(**per)
@@ -231,6 +235,7 @@ def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon
     tables = args.get("epsilon_table", [getattr(tables, "value", None)] * R)
     fields = args.get("vector_potential_table", [getattr(fields, "value", None)] * R)
     sums = args.get("vector_potential_terms", [getattr(sums, "value", None)] * R)
+    spots = args.get("epsilon_spots", [getattr(spots, "value", None)] * R)
     reps = []
     for r in range(R):
         if ramps[r] is not None and fields[r] is not None:
@@ -238,11 +243,14 @@ def ensemble_dimensionless(mesh, options: SolverOptions, link_exponents, epsilon
         if sums[r] is not None and (ramps[r] is not None or fields[r] is not None):
             raise ValueError(f"solve_ensemble: replica {r}: vector_potential_terms excludes vector_potential_ramp and "
                              "vector_potential_table.")
+        if spots[r] is not None and tables[r] is not None:
+            raise ValueError(f"solve_ensemble: replica {r}: epsilon_spots and epsilon_table exclude each other.")
         # (link_exponents None: the field's value at t = 0, `applied_field.from_dimensionless`)
         rep = _ReplicaInputs.from_dimensionless(mesh, options, args["link_exponents"][r], eps[r], u, gamma,
                                                 terminal_info=terminal_info, current_func=args["currents"][r],
                                                 probe_points=probe_points, vector_potential_ramp=ramps[r],
-                                                vector_potential_table=fields[r], vector_potential_terms=sums[r])
+                                                vector_potential_table=fields[r], vector_potential_terms=sums[r],
+                                                epsilon_spots=spots[r])
         if tables[r] is not None:
             _with_epsilon_table(rep, tables[r], len(mesh.sites))
         _refuse_dynamic(r, rep)
@@ -328,6 +336,20 @@ class EnsembleContext:
     def set_epsilon_table(self, r, epsilon0, times, factors):
         """``TDGLContext.set_epsilon_table`` for replica r; ``times=None``: off."""
         self._chk(self._lib.tdgl_ensemble_set_epsilon_table(self._ens, r, *epsilon_table_args(self.ctx.n, epsilon0, times, factors)))
+
+    def set_epsilon_spots(self, r, sites, eps0, spots):
+        """``TDGLContext.set_epsilon_spots`` for replica r (the site coordinates are the ensemble's: kept from the first
+        call); ``spots`` empty or None: off."""
+        if not spots:
+            self._chk(self._lib.tdgl_ensemble_set_epsilon_spots(self._ens, r, None, None, 0, None, None, None, None, None, None))
+            return
+        self._chk(self._lib.tdgl_ensemble_set_epsilon_spots(self._ens, r, *epsilon_spots_args(self.ctx.n, sites, eps0, spots)))
+
+    def epsilon(self, r):
+        """Replica r's disorder parameter ``epsilon[n]`` in force on the device, whatever set it."""
+        eps = np.zeros(self.ctx.n)
+        self._chk(self._lib.tdgl_ensemble_get_epsilon(self._ens, r, p_f64(eps)))
+        return eps
 
     def set_state(self, r, psi, mu):
         psi, mu = c128(psi), f64(mu)
@@ -491,6 +513,10 @@ class EnsembleSolver:
                 eps0, times, values = rep._eps_table
                 check_epsilon_table(eps0, values, prefix=f"replica {r}: ")
                 ens.set_epsilon_table(r, eps0, times, values)
+                rep._epsilon_on_device = True
+            if getattr(rep, "_eps_spots", None) is not None:
+                eps0, spots = rep._eps_spots
+                ens.set_epsilon_spots(r, rep.sites, eps0, spots)
                 rep._epsilon_on_device = True
             seed = getattr(rep, "seed_state", None)
             if rep.seed_solution is not None:

@@ -66,6 +66,36 @@ def epsilon_table_args(n: int, epsilon0, times, factors) -> tuple:
     return p_f64(e0), len(t), p_f64(t), p_f64(fac)
 
 
+EPS_SPOTS_MAX = 4  # TDGL_EPS_SPOTS_MAX
+
+
+def epsilon_spots_args(n: int, sites, eps0, spots) -> tuple:
+    """``(sites, eps0, n_spots, tab_off, tab_times, tab_cx, tab_cy, tab_amp, tab_sigma)`` of tdgl_set_epsilon_spots on ``n``
+    sites from ``sites`` [n, 2], the static part ``eps0`` (a number or [n]) and ``spots``: a list of `parameter.HotSpot`
+    or of ``dict(times=, centers=, amplitudes=, sigmas=)``.  Shapes, the number of spots and the rules a `HotSpot` checks
+    itself are refused here with ``ValueError``; the library checks the values once more."""
+    from .parameter import HotSpot
+
+    spots = [s if isinstance(s, HotSpot) else HotSpot(s["times"], s["centers"], s["amplitudes"], s["sigmas"]) for s in spots]
+    if not 1 <= len(spots) <= EPS_SPOTS_MAX:
+        raise ValueError(f"epsilon_spots: between 1 and {EPS_SPOTS_MAX} spots, got {len(spots)}.")
+    xy = f64(sites)
+    if xy.shape != (n, 2):
+        raise ValueError(f"epsilon_spots: sites must have shape ({n}, 2), got {xy.shape}.")
+    if not np.all(np.isfinite(xy)):
+        raise ValueError("epsilon_spots: sites must be finite.")
+    e0 = np.asarray(eps0, dtype=float)
+    if e0.shape not in ((), (n,)):
+        raise ValueError(f"epsilon_spots: eps0 must be a number or have shape ({n},), got {e0.shape}.")
+    e0 = f64(np.broadcast_to(e0, (n,)))
+    if not np.all(np.isfinite(e0)) or np.any(e0 > 1):
+        raise ValueError("epsilon_spots: eps0 must be finite and <= 1 (the disorder parameter epsilon must be <= 1).")
+    off = i32(np.concatenate([[0], np.cumsum([len(s.times) for s in spots])]))
+    cols = [f64(np.concatenate([v(s) for s in spots])) for v in (
+        lambda s: s.times, lambda s: s.centers[:, 0], lambda s: s.centers[:, 1], lambda s: s.amplitudes, lambda s: s.sigmas)]
+    return (p_f64(xy), p_f64(e0), len(spots), p_i32(off), *[p_f64(c) for c in cols])
+
+
 def link_table_args(times, values) -> tuple:
     """``(n_nodes, times, values)`` of tdgl_set_link_table; ``times=None``: off."""
     if times is None:
@@ -360,6 +390,7 @@ class TDGLContext:
         else:
             perm = i32(reorder)
         self.perm = perm
+        self._n_eps_spots = 0  # hot spots in force (set_epsilon_spots)
         self.iperm = np.empty(self.n, dtype=np.int64)
         self.iperm[perm] = np.arange(self.n)
         fixed = i32([] if fixed_sites is None else fixed_sites)
@@ -1393,6 +1424,7 @@ class TDGLContext:
     def set_epsilon(self, eps):
         eps = f64(np.broadcast_to(eps, (self.n,)))
         self._chk(self._lib.tdgl_set_epsilon(self._ctx, p_f64(eps)))
+        self._n_eps_spots = 0  # (plain values, a table and spots replace each other)
 
     def set_mu_boundary(self, mu_b):
         mu_b = f64(mu_b)
@@ -1406,6 +1438,38 @@ class TDGLContext:
     def set_epsilon_table(self, epsilon0, times, factors):
         """epsilon(r, t) = factor(t) * epsilon0(r) evaluated inside `run`; ``times=None``: off."""
         self._chk(self._lib.tdgl_set_epsilon_table(self._ctx, *epsilon_table_args(self.n, epsilon0, times, factors)))
+        if times is not None:
+            self._n_eps_spots = 0
+
+    def set_epsilon_spots(self, sites, eps0, spots):
+        """epsilon(r, t) = eps0(r) - sum_k a_k(t) exp(-|r - c_k(t)|^2 / (2 sigma_k(t)^2)) evaluated inside `run`
+        (`epsilon_spots_args`); sets epsilon to its value at t = 0.  ``spots`` empty or None: off."""
+        if not spots:
+            self._chk(self._lib.tdgl_set_epsilon_spots(self._ctx, None, None, 0, None, None, None, None, None, None))
+            self._n_eps_spots = 0
+            return
+        args = epsilon_spots_args(self.n, sites, eps0, spots)
+        self._chk(self._lib.tdgl_set_epsilon_spots(self._ctx, *args))
+        self._n_eps_spots = args[2]
+
+    def update_epsilon_spots(self, values):
+        """Apply the spots' ``[K, 4]`` values (cx, cy, a, sigma) now."""
+        v = f64(np.asarray(values, dtype=float).reshape(-1, 4))
+        if len(v) != self._n_eps_spots:
+            raise ValueError(f"update_epsilon_spots: {self._n_eps_spots} spots are set, got values for {len(v)}.")
+        self._chk(self._lib.tdgl_update_epsilon_spots(self._ctx, p_f64(v)))
+
+    def epsilon_spot_values(self):
+        """``[K, 4]``: centre x, y, amplitude and width of every spot of the epsilon in force (empty: none are set)."""
+        n, v = C.c_int32(0), np.zeros(4 * EPS_SPOTS_MAX)
+        self._chk(self._lib.tdgl_get_epsilon_spot_values(self._ctx, C.byref(n), p_f64(v)))
+        return v[:4 * n.value].reshape(n.value, 4)
+
+    def epsilon(self):
+        """The disorder parameter ``epsilon[n]`` in force on the device, whatever set it."""
+        eps = np.zeros(self.n)
+        self._chk(self._lib.tdgl_get_epsilon(self._ctx, p_f64(eps)))
+        return eps
 
     def set_state(self, psi, mu):
         psi, mu = c128(psi), f64(mu)

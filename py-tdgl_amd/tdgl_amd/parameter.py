@@ -596,3 +596,108 @@ class SeparableEpsilon:
 
     def __call__(self, r, *, t=0.0, vectorized=True):
         return self.factor(t) * self.static_values(np.atleast_2d(r))
+
+
+# ---- Gaussian hot spots in epsilon, evaluated on the device ---------------------------------------
+EPS_SPOTS_MAX = 4  # TDGL_EPS_SPOTS_MAX
+
+
+def table_value(times, values, t: float) -> float:
+    """The library's ``table_value`` (csrc/kernels.inc) restated operation for operation: linear between the nodes,
+    constant outside -- ``v[k-1] + (v[k] - v[k-1]) * ((t - t[k-1]) / (t[k] - t[k-1]))`` with ``t[k]`` the first node
+    behind ``t``.  What host and device evaluate for every table; `np.interp` rounds differently."""
+    t = float(t)
+    if t <= times[0]:
+        return float(values[0])
+    if t >= times[-1]:
+        return float(values[-1])
+    hi = int(np.searchsorted(times, t, side="right"))
+    t0, t1 = float(times[hi - 1]), float(times[hi])
+    v0, v1 = float(values[hi - 1]), float(values[hi])
+    return v0 + (v1 - v0) * ((t - t0) / (t1 - t0))
+
+
+class HotSpot:
+    """One Gaussian spot ``a(t) exp(-|r - c(t)|^2 / (2 sigma(t)^2))``: the centre, the amplitude ``a >= 0`` and the width
+    ``sigma > 0`` at the nodes ``times`` (strictly increasing), each linear between the nodes and constant outside them.
+    ``amplitudes`` and ``sigmas`` may be single numbers, ``centers`` a single point.  Lengths and time are those the solver
+    hands to a ``disorder_epsilon``."""
+
+    def __init__(self, times, centers, amplitudes, sigmas):
+        self.times = np.atleast_1d(np.asarray(times, dtype=float))
+        n = len(self.times)
+        if self.times.ndim != 1 or n < 1:
+            raise ValueError("HotSpot: times must be one-dimensional with at least one node.")
+        centers = np.asarray(centers, dtype=float)
+        if centers.shape == (2,):
+            centers = np.broadcast_to(centers, (n, 2))
+        self.centers = np.array(centers, dtype=float)
+        amplitudes, sigmas = np.asarray(amplitudes, dtype=float), np.asarray(sigmas, dtype=float)
+        if self.centers.shape != (n, 2):
+            raise ValueError(f"HotSpot: centers must have shape (n_nodes, 2) = ({n}, 2), got {self.centers.shape}.")
+        for name, v in (("amplitudes", amplitudes), ("sigmas", sigmas)):
+            if v.shape not in ((), (n,)):
+                raise ValueError(f"HotSpot: {name} must be a number or have shape (n_nodes,) = ({n},), got {v.shape}.")
+        self.amplitudes = amplitudes * np.ones(n)
+        self.sigmas = sigmas * np.ones(n)
+        if not np.all(np.isfinite(self.times)) or np.any(np.diff(self.times) <= 0):
+            raise ValueError("HotSpot: times must be finite and increase strictly.")
+        if not np.all(np.isfinite(self.centers)):
+            raise ValueError("HotSpot: centers must be finite.")
+        if not (np.all(np.isfinite(self.amplitudes)) and np.all(self.amplitudes >= 0)):
+            raise ValueError("HotSpot: amplitudes must be finite and >= 0.")
+        # (sigma^2 a normal number: with a smaller one a site at the spot's centre would get 0 / 0)
+        if not (np.all(np.isfinite(self.sigmas)) and np.all(self.sigmas > 0)
+                and np.all(self.sigmas * self.sigmas >= np.finfo(float).tiny)):
+            raise ValueError("HotSpot: sigmas must be finite and > 0, with a normal square.")
+
+    def values(self, t: float) -> tuple:
+        """``(cx, cy, a, sigma)`` at ``t``, by the library's `table_value`."""
+        return tuple(table_value(self.times, v, t)
+                     for v in (self.centers[:, 0], self.centers[:, 1], self.amplitudes, self.sigmas))
+
+
+def hot_spot_epsilon(sites, eps0, values) -> np.ndarray:
+    """``eps0 - sum_k a_k exp(-|r - c_k|^2 / (2 sigma_k^2))`` at ``values[k] = (cx, cy, a, sigma)``, with the library's
+    operations in the library's order (k_eps_spots): all but ``exp`` are the same bits."""
+    sites = np.asarray(sites, dtype=float)
+    x, y = sites[:, 0], sites[:, 1]
+    acc = np.array(eps0, dtype=float) * np.ones(len(sites))
+    for cx, cy, a, s in values:
+        dx, dy = x - float(cx), y - float(cy)
+        d2 = dx * dx + dy * dy
+        den = 2.0 * (float(s) * float(s))
+        g = np.exp(-(d2 / den))
+        acc = acc - float(a) * g
+    return acc
+
+
+class HotSpotEpsilon:
+    """``disorder_epsilon(r, t) = static(r) - sum_k a_k(t) exp(-|r - c_k(t)|^2 / (2 sigma_k(t)^2))``: a local, moving,
+    growing and fading suppression of the critical temperature -- a photon's hot spot in a nanowire detector, a laser spot
+    scanned over a film, a heater pulse.  ``static`` (<= 1): a number, an array over the sites or a callable
+    ``static(r[n, 2]) -> [n]`` (an array goes with the site array it was made for: a call at a single point or at another
+    number of points raises); ``spots``: `HotSpot` s.  Has the reference's calling convention (``epsilon(r, *, t,
+    vectorized=True)``), so it works wherever a callable does; with at most ``EPS_SPOTS_MAX`` spots the solver keeps
+    ``static`` and the sites on the device and the time loop evaluates the spots itself (`tdgl_set_epsilon_spots`)."""
+
+    def __init__(self, static=1.0, spots=()):
+        self.static = static
+        self.spots = [spots] if isinstance(spots, HotSpot) else list(spots)
+        if not self.spots or not all(isinstance(s, HotSpot) for s in self.spots):
+            raise ValueError("HotSpotEpsilon: spots must be a non-empty list of HotSpot.")
+
+    def static_values(self, sites) -> np.ndarray:
+        s = np.asarray(self.static(np.asarray(sites)) if callable(self.static) else self.static, dtype=float)
+        if s.ndim > 0 and s.shape != (len(sites),):
+            raise ValueError(f"HotSpotEpsilon: static has shape {s.shape}, but epsilon was asked at {len(sites)} point(s): an "
+                             "array-valued static belongs to the whole site array (vectorized=True); use a number or a callable.")
+        return s * np.ones(len(sites))
+
+    def spot_values(self, t: float) -> list:
+        return [s.values(t) for s in self.spots]
+
+    def __call__(self, r, *, t=0.0, vectorized=True):
+        r = np.asarray(r, dtype=float)
+        out = hot_spot_epsilon(np.atleast_2d(r), self.static_values(np.atleast_2d(r)), self.spot_values(t))
+        return out if r.ndim == 2 else float(out[0])

@@ -129,11 +129,15 @@ class TDGLSolver:
         self.epsilon_func = None
         self.dynamic_epsilon = False
         self._eps_table = None
-        from .parameter import SeparableEpsilon, TabulatedCurrents
+        self._eps_spots = None
+        from .parameter import EPS_SPOTS_MAX, HotSpotEpsilon, SeparableEpsilon, TabulatedCurrents
 
         if isinstance(disorder_epsilon, SeparableEpsilon):  # factor(t) * static(r): evaluated on the device
             eps0 = disorder_epsilon.static_values(self.sites)
             self._eps_table = (eps0, disorder_epsilon.factor.times, disorder_epsilon.factor.values)
+        # static(r) - Gaussian spots: evaluated on the device too (more spots than it takes: the per-step callable)
+        if isinstance(disorder_epsilon, HotSpotEpsilon) and len(disorder_epsilon.spots) <= EPS_SPOTS_MAX:
+            self._eps_spots = (disorder_epsilon.static_values(self.sites), list(disorder_epsilon.spots))
         if callable(disorder_epsilon):
             spec = inspect.getfullargspec(disorder_epsilon)
             self.dynamic_epsilon = "t" in spec.kwonlyargs
@@ -202,7 +206,7 @@ class TDGLSolver:
                            current_func=None, probe_points=None, device=None,
                            vector_potential_func=None, epsilon_func=None,
                            screening=None, vector_potential_ramp=None, vector_potential_table=None,
-                           vector_potential_terms=None, vector_potential_loops=None) -> "TDGLSolver":
+                           vector_potential_terms=None, vector_potential_loops=None, epsilon_spots=None) -> "TDGLSolver":
         """Build a solver directly from dimensionless inputs -- the arrays the reference's
         ``__init__`` ends up with (solver.py:185, 214, 225, 254-256): ``A[m, 2]``,
         ``epsilon[n]``, ``TerminalInfo`` records and ``t -> {name: dimensionless current}``.
@@ -219,7 +223,11 @@ class TDGLSolver:
         ``vector_potential_loops``: a list of up to two ``dict(radius=, times=, centers=[n, 3] (or z= with centers
         [n, 2]), currents=)`` for moving current loops on top of ``vector_potential_terms`` or, without terms, of
         ``link_exponents`` (then the static part): lengths in the mesh's units, the film at z = 0, the currents with
-        mu_0, the units and the field scale folded in (`tdgl_set_link_loops`); it excludes the ramp and the table too."""
+        mu_0, the units and the field scale folded in (`tdgl_set_link_loops`); it excludes the ramp and the table too.
+        ``epsilon_spots``: ``(eps0, spots)`` for ``epsilon(r, t) = eps0(r) - sum_k a_k(t) exp(-|r - c_k(t)|^2 / (2
+        sigma_k(t)^2))`` with ``eps0`` a number or ``[n]`` and ``spots`` a list of up to four `HotSpot` (or ``dict(times=,
+        centers=[n, 2], amplitudes=, sigmas=)``), lengths in the mesh's units, evaluated by the library
+        (`tdgl_set_epsilon_spots`; ``epsilon`` is then its value at t = 0); it excludes ``epsilon_func``."""
         self = object.__new__(cls)
         options.validate()
         self.device = device
@@ -239,6 +247,20 @@ class TDGLSolver:
         self.epsilon_func = epsilon_func
         self.dynamic_epsilon = epsilon_func is not None
         self.epsilon = np.asarray(epsilon, dtype=float) * np.ones(len(mesh.sites))
+        self._eps_spots = None
+        if epsilon_spots is not None:
+            if epsilon_func is not None:
+                raise ValueError("epsilon_spots and epsilon_func exclude each other.")
+            from .parameter import HotSpot, HotSpotEpsilon
+
+            eps0, spots = epsilon_spots
+            spots = [s if isinstance(s, HotSpot) else HotSpot(s["times"], s["centers"], s["amplitudes"], s["sigmas"]) for s in spots]
+            source = HotSpotEpsilon(np.asarray(eps0, dtype=float) * np.ones(len(mesh.sites)), spots)
+            self._eps_spots = (source.static, spots)
+            self.disorder_epsilon = source
+            self.epsilon_func = lambda t: source(mesh.sites, t=t)  # noqa: E731
+            self.dynamic_epsilon = True
+            self.epsilon = self.epsilon_func(0.0)
         if np.any(self.epsilon > 1):
             raise ValueError("The disorder parameter epsilon must be <= 1")
         info = [t if isinstance(t, TerminalInfo) else TerminalInfo(
@@ -351,6 +373,10 @@ class TDGLSolver:
             check_epsilon_table(eps0, values)
             self.ctx.set_epsilon_table(eps0, times, values)
             self._epsilon_on_device = True
+        if self._eps_spots is not None:
+            eps0, spots = self._eps_spots
+            self.ctx.set_epsilon_spots(self.sites, eps0, spots)
+            self._epsilon_on_device = True
         self._device_holds = None  # (psi, mu) arrays known to equal the device state
 
     def _current_table_arrays(self):
@@ -396,7 +422,8 @@ class TDGLSolver:
         return self.field.on_device
 
     def device_evaluates_epsilon(self) -> bool:
-        """epsilon(t) is a table the time loop evaluates itself (tdgl_set_epsilon_table); the host keeps a copy."""
+        """epsilon(t) is a table or a sum of hot spots the time loop evaluates itself (tdgl_set_epsilon_table,
+        tdgl_set_epsilon_spots); the host keeps a copy."""
         return self.dynamic_epsilon and self._epsilon_on_device
 
     def update_dynamic_inputs(self, time: float, dt_prev: float) -> None:
